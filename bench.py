@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/sec of the batched rollout hot path on N MI355X (driver contract).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[1], the configuration the metric is quoted on): flamingo_light_v1 x 4096 envs per GPU,
@@ -12,9 +12,14 @@ Philox(seed 1234, key (n, j)), auto-reset on.  One "step" = one control step of 
 Inputs (actions, commands) are resident in HBM before the timed region.  Weak scaling: 4096 envs per GPU; shards are
 independent (no data-path collective); one all-reduce of reporter statistics closes the timed region.
 
-Extra objects on the JSON line: "roofline" (algorithmic bytes of the step kernel / its mean launch duration from HIP
-events on the launch stream, against the 8 TB/s HBM peak) and "cpu_baseline" (the fp64 CPU oracle on the CPU twins of the fleet's
-own envs: one thread, then every host core; bounded sample; rank 0 at N = 1 only).
+A plain run sets up, warms up, times the K steps and prints the JSON line; its "roofline" object (algorithmic bytes of the step
+kernel / its mean launch duration from HIP events on the launch stream, against the 8 TB/s HBM peak) comes from that same timed
+run.  --full adds what takes runs of its own: "cpu_baseline" (the fp64 CPU oracle on the CPU twins of the fleet's own envs: one
+thread, then every host core; bounded sample; rank 0 at N = 1 only) and "config.rollout" (the same fleet through cosim_rollout
+after the timed region).
+
+--dump-outputs DIR writes what the last timed step returned to its caller (state, terminated, truncated and the info arrays of
+rank 0's shard) as DIR/<name>.npy in float32; the inputs are fixed by the seed, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -236,6 +241,31 @@ def pmc_traffic(workload, split_substeps=0):
                             "and info write-back, plus register-spill scratch in the kernels that spill)", **extra}
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, outputs):
+    """`outputs` = (state, terminated, truncated, info) of one step: every array a caller receives, as float32 .npy files.  Over
+    DUMP_LIMIT_BYTES in all, a fixed seeded sample of env rows is written instead (the same rows for every array; env_rows.npy)."""
+    import torch
+    state, term, trunc, info = outputs
+    arrays = {"state": state, "terminated": term, "truncated": trunc}
+    arrays.update({f"info_{k}": v for k, v in info.items() if torch.is_tensor(v)})
+    n = state.shape[0]
+    row_bytes = sum(v[0].numel() * 4 for v in arrays.values())
+    rows = None
+    if row_bytes * n + 128 * len(arrays) > DUMP_LIMIT_BYTES:
+        k = max(1, (DUMP_LIMIT_BYTES - 128 * (len(arrays) + 1)) // (row_bytes + 8))   # + env_rows.npy, + .npy headers
+        rows = np.sort(np.random.default_rng(1234).choice(n, size=k, replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    idx = None if rows is None else torch.as_tensor(rows, device=state.device)
+    for name, v in arrays.items():
+        v = v if idx is None else v.index_select(0, idx)
+        np.save(os.path.join(out_dir, f"{name}.npy"), v.detach().to(torch.float32).cpu().numpy())
+    if rows is not None:
+        np.save(os.path.join(out_dir, "env_rows.npy"), rows.astype(np.float64))
+
+
 def free_port():
     import socket
     with socket.socket() as sk:
@@ -291,19 +321,25 @@ def main(argv=None):
     ap.add_argument("--warmup", type=int, default=100)
     ap.add_argument("--envs-per-gpu", type=int, default=0)
     ap.add_argument("--workload", default="light_flat", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the CPU baseline (rank 0 at N = 1) and the cosim_rollout leg")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (rank 0's shard) to DIR/<name>.npy in float32")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--streams", type=int, default=4,
                     help="env.step() issues each control step of the per-GPU fleet as S launches over contiguous env ranges on S "
                          "engine-owned HIP streams (BatchedEnv(ranges=S, deferred_join=True): a range's next control step fills the tail "
                          "of the others' launches); 1 = one launch on the caller's stream")
     ap.add_argument("--caller-streams", action="store_true",
                     help="A/B: the round-2 arrangement, the CALLER builds the S streams and calls env.step_range per range")
-    ap.add_argument("--no-rollout", action="store_true", help="skip the extra cosim_rollout measurement after the timed region")
+    ap.add_argument("--no-rollout", action="store_true", help="with --full: skip the extra cosim_rollout measurement after the timed region")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo only to rehearse ranks on one GPU)")
     ap.add_argument("--single-device", action="store_true", help="rehearsal: every rank uses cuda:0 (with --backend gloo)")
     ap.add_argument("--report-every", type=int, default=16, help="reporter statistics are sampled every this many timed steps")
     ap.add_argument("--selftest-launch", action="store_true", help="launcher / collective skeleton only, no GPU work (CPU test)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         raise SystemExit(self_launch(args, argv))     # the children are the ranks; this process never touches the GPU
@@ -312,7 +348,7 @@ def main(argv=None):
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     cpu_line = None
-    if world == 1 and args.gpus == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.gpus == 1 and args.full and not args.no_cpu_baseline:
         # before anything in this process touches the GPU: the all-cores leg forks worker processes
         cpu_line = cpu_baseline(args.workload)
 
@@ -370,6 +406,7 @@ def main(argv=None):
     torch.cuda.synchronize()
 
     def fleet_step(t, report):
+        """One control step of the fleet; returns what env.step hands its caller (the fleet's buffers and info views)."""
         a = actions[t]
         if args.caller_streams:
             for i in range(S):
@@ -377,14 +414,15 @@ def main(argv=None):
                     env.step_range(ranges[i][0], ranges[i][1], a)
                     if report:
                         reporter.write_info_range(ranges[i][0], ranges[i][1])
-            return
-        env.step(a)
+            return env.state, env.terminated, env.truncated, env._info(a)
+        out = env.step(a)
         if report:   # reporter statistics of this step: each range's info rows are reduced on that range's own stream
             for i in range(S):
                 with torch.cuda.stream(streams[i]):
                     reporter.write_info_range(ranges[i][0], ranges[i][1])
                 if S > 1:
                     env.range_mark(i)
+        return out
 
     if args.caller_streams:
         for st_ in streams:
@@ -411,7 +449,7 @@ def main(argv=None):
     sync()
     t0 = time.perf_counter()
     for t in range(args.warmup, total_steps):
-        fleet_step(t, (t - args.warmup) % args.report_every == 0)   # sampled: first timed step, then every k-th
+        last = fleet_step(t, (t - args.warmup) % args.report_every == 0)   # sampled: first timed step, then every k-th
     t_issue = time.perf_counter()
     env.join()                                          # the deferred join: the caller's stream now waits for every range
     torch.cuda.synchronize()
@@ -444,7 +482,9 @@ def main(argv=None):
     # A second, separately labelled number (never `value`): the same fleet continuing for another args.steps control steps through
     # cosim_rollout -- the whole table in one launch per range, for callers whose actions do not depend on the last state.
     rollout = None
-    if env.engine.query("rollout") == 1 and not args.caller_streams and not args.no_rollout:
+    if args.dump_outputs and rank == 0:                  # before the rollout leg, which steps the same fleet further
+        dump_outputs(args.dump_outputs, last)
+    if args.full and env.engine.query("rollout") == 1 and not args.caller_streams and not args.no_rollout:
         acts_r = synthetic_actions(n, env_id0, total_steps + args.steps, nu, env.device)[total_steps:].contiguous()
         env.rollout(acts_r[:min(2, args.steps)])            # code-object load of the rollout kernels
         sync()

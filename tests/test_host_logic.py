@@ -296,32 +296,24 @@ def test_height_map_on_flat_terrain_is_refused():
     make_obs_config(ok, obs_to_dim("w4_p_v2", ok), 50.0, True)
 
 
-def test_one_env_info_stream_is_accepted_by_the_reference_reporter(tmp_path):
+def test_one_env_info_stream_is_accepted_by_the_reference_reporter(golden_dir):
     """SURVEY §8b 'info contract (Reporter drop-in)' / §8f N2: the single-env dicts that Runner / FleetReporter cut out of the
-    batched info are fed to the reference's own core/reporter.py (importable here: matplotlib only), which must build its PDF.
-    Skipped where the reference tree is not mounted (the GPU box)."""
-    ref = "/root/reference/core/reporter.py"
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not mounted")
-    import importlib.util
+    batched info are fed, step by step, into a history kept the way the reference's core/reporter.py keeps it, and every series
+    its PDF report reads (tests/golden/reporter_contract.json, recorded from that reporter) must convert and line up: scalars
+    where it takes a scalar, [T] and [T, n] float arrays where it plots them against time, every section's keys present."""
     import torch
     from cosim_amd.runner import Runner
-    spec = importlib.util.spec_from_file_location("ref_reporter", ref)
-    mod = importlib.util.module_from_spec(spec)
-    try:
-        spec.loader.exec_module(mod)
-    except ImportError as e:
-        pytest.skip(f"reference reporter not importable here: {e}")
+    with open(os.path.join(golden_dir, "reporter_contract.json")) as f:
+        contract = json.load(f)
 
     class FakeEnv:                       # the attributes Runner reads; info tensors shaped like BatchedEnv._info's
         num_envs, command_dim, auto_reset = 8, 4, False
-    N, nu = 8, 4
+    N, nu, T = 8, 4, 60
     run = Runner.__new__(Runner)
     run.env = FakeEnv()
-    cfg = make_config("flamingo_light_v1")
-    rep = mod.Reporter(str(tmp_path / "report.pdf"), cfg)
+    history = {}
     g = torch.Generator().manual_seed(0)
-    for t in range(60):
+    for t in range(T):
         buf = torch.randn((N, 4 + 3 * nu), generator=g)
         info = {"dt": 0.02, "action": torch.randn((N, nu), generator=g), "action_diff_RMSE": buf[:, 0], "lin_vel_x": buf[:, 1],
                 "lin_vel_y": buf[:, 2], "ang_vel_yaw": buf[:, 3], "torque": buf[:, 4:4 + nu], "set_points": buf[:, 4 + nu:4 + 2 * nu],
@@ -330,9 +322,28 @@ def test_one_env_info_stream_is_accepted_by_the_reference_reporter(tmp_path):
             info[f"user_command_{i}"] = torch.full((N,), 0.1 * i)
         one = run._one_env_info(info, 3)
         assert isinstance(one["lin_vel_x"], float) and one["torque"].shape == (nu,) and one["dt"] == 0.02
-        rep.write_info(one)
-    rep.generate_report()
-    assert os.path.getsize(tmp_path / "report.pdf") > 10000
+        for key, value in one.items():   # Reporter.write_info
+            history.setdefault(key, []).append(value)
+    for key in contract["first_scalar"]:
+        assert float(history[key][0]) == 0.02
+    cmd_keys = sorted(k for k in history if k.startswith(contract["series_1d_prefix"]))
+    assert cmd_keys == [f"user_command_{i}" for i in range(4)]
+    arrays = {}
+    for key in contract["series_1d"] + cmd_keys:
+        arrays[key] = np.array(history[key], dtype=float)
+        assert arrays[key].shape == (T,), key
+    for key in contract["series_2d"]:
+        arrays[key] = np.array(history[key], dtype=float)
+        assert arrays[key].ndim == 2 and arrays[key].shape[0] == T, key
+    assert arrays["torque"].shape == (T, nu)
+    for key, by in contract["columns_indexed_by"].items():
+        assert arrays[key].shape[1] >= arrays[by].shape[1], (key, by)
+    for sec in contract["sections"]:
+        assert all(k in history for k in sec.get("needs_all", [])), sec["title"]
+        assert not sec.get("needs_any") or any(k in history for k in sec["needs_any"]), sec["title"]
+        assert not sec.get("needs_prefix") or any(k.startswith(sec["needs_prefix"]) for k in history), sec["title"]
+    for key, a in arrays.items():
+        assert np.isfinite(a).all(), key
 
 
 @pytest.mark.parametrize("robot", ["w4_p_v2", "flamingo_p_v3", "humanoid_p_v0"])
