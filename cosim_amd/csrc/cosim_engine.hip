@@ -49,8 +49,8 @@ struct cosim_engine {
   int64_t env_id0 = 0;
   float tol32 = 1e-6f;
   float ls_scale = 1.f;
-  int max_newton = 50;
-  int max_ls = 24;
+  int max_newton = -1;   // explicit Newton iteration cap ("max_newton"); < 0: none, the model's iterations hold
+  int max_ls = 24;       // line-search cap below the model's ls_iterations (50 in every reference model): measured enough, see DESIGN.md
   int nsub_override = 0;
   int pair_coop = 1;
   int timing_stride = 1;   // kernel timing: an event pair around every n-th launch (the events themselves cost ~4 % of a short run at 1)
@@ -731,6 +731,13 @@ int cosim_destroy(cosim_engine_t* e) {
   return COSIM_OK;
 }
 
+// The iteration caps the solver runs with: the model's counts (iterations per precision level: 50 / 50 / 75 / 75 / 100), lowered
+// only by an explicit "max_newton" / "max_ls".  cosim_query reports the same numbers.
+static int newton_cap(const cosim_engine* e) {
+  return e->max_newton < 0 ? e->model.iterations : (e->max_newton < e->model.iterations ? e->max_newton : e->model.iterations);
+}
+static int ls_cap(const cosim_engine* e) { return e->max_ls < 0 ? e->model.ls_iterations : (e->max_ls < e->model.ls_iterations ? e->max_ls : e->model.ls_iterations); }
+
 int cosim_query(const cosim_engine_t* e, const char* name) {
   if (!e || !name) return fail(COSIM_EINVAL, "cosim_query: null argument");
   std::string n(name);
@@ -754,6 +761,9 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "pair_slots") return e->pair_slots;
   if (n == "stacked_dim") return e->ho.stacked_dim;
   if (n == "frame_dim") return e->ho.frame_dim;
+  if (n == "max_newton") return newton_cap(e);   // Newton iterations per substep the solver may take
+  if (n == "max_ls") return ls_cap(e);           // line-search evaluations per Newton iteration
+  if (n == "frame_skip") return e->model.frame_skip;
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
 }
 
@@ -863,7 +873,7 @@ static KArgs base_args(cosim_engine* e) {
   a.hull_cell = e->d_hull_cell; a.hull_cand = e->d_hull_cand; a.hfield_mip = e->d_hfield_mip;
   a.pairs = e->d_pairs; a.gext = e->d_gext;
   a.n_envs = e->n_envs; a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
-  a.tol32 = e->tol32; a.ls_scale = e->ls_scale; a.max_newton = e->max_newton; a.max_ls = e->max_ls; a.nsub_override = e->nsub_override; a.pair_coop = e->pair_coop; a.pair_boxbox = e->pair_boxbox; a.block_cull = e->block_cull; a.coop_walk = e->coop_walk;
+  a.tol32 = e->tol32; a.ls_scale = e->ls_scale; a.max_newton = newton_cap(e); a.max_ls = ls_cap(e); a.nsub_override = e->nsub_override; a.pair_coop = e->pair_coop; a.pair_boxbox = e->pair_boxbox; a.block_cull = e->block_cull; a.coop_walk = e->coop_walk;
   for (int k = 0; k < 4; k++) a.prio[k] = e->prio[k];
   a.ovf = nullptr; a.roll_steps = 1;
   a.xcon = e->d_xcon; a.xcnt = e->d_xcnt; a.xstate = e->d_xstate; a.nw = e->narrow_waves; a.sub_index = 0; a.sub_total = 0;

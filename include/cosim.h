@@ -80,7 +80,9 @@ int cosim_query(const cosim_engine_t* e, const char* name);
  * "dof_invweight0"[N,nv] "meaninertia"[N] "dof_frictionloss"[N,nv] "geom_friction"[N,ngeom] (sliding, already
  * max-combined with the ground; robot-robot pairs use the model's geom friction) "kp"[N,nu] "kd"[N,nu].  `host` points to
  * host memory, float32, row-major.  Engine scalars (count 1): "solver_tolerance" (fp32 Newton tolerance), "max_newton",
- * "max_ls" (iteration caps below the model's), "envs_per_wave" (1 | 2: kernel variant, 2 only for flat flamingo_light_v1 and
+ * "max_ls" (iteration caps below the model's iterations / ls_iterations, which still bound them; a negative value removes the
+ * engine's cap.  Defaults: no Newton cap, so every precision level runs its own 50 / 75 / 100 iterations; a line-search cap of 24
+ * against the reference models' 50, a deliberate deviation, DESIGN.md "Solver iteration caps"), "envs_per_wave" (1 | 2: kernel variant, 2 only for flat flamingo_light_v1 and
  * even env counts), "wave_priority" (count 4: s_setprio by solver lag -- Newton iterations taken as usual per substep, then the
  * lag thresholds of priority 1, 2, 3; a huge first threshold switches it off), "debug_substeps" (diagnostics: physics substeps
  * per control step, 0 = frame_skip), "boxbox_mode" (1, default: box-box geom pairs through the mjc_BoxBox routine, up to eight contacts
@@ -101,7 +103,8 @@ int cosim_query(const cosim_engine_t* e, const char* name);
  * their prisms; 0: every block goes on to the per-prism tests; same contacts either way).
  * cosim_query additionally answers "contact_slots" / "pair_slots" (capacity of the selected kernel variant: heightfields with cells
  * of 10 cm or more select the 48-slot variants of flamingo_light_v1 / w4_p_v2), "fixup_contact_slots" (capacity of the kernel that
- * redoes a control step whose contacts did not fit; 0: this model / terrain has none), "ranges" and "lds_bytes". */
+ * redoes a control step whose contacts did not fit; 0: this model / terrain has none), "ranges", "lds_bytes", "frame_skip" (physics
+ * substeps per control step: the precision level's) and "max_newton" / "max_ls" (the caps the solver runs with). */
 int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int count);
 
 /* Replaces env.reset() (reference envs/wrappers.py:245-256,303-307,385-389; flamingo_light_v1.py:209-232).

@@ -388,3 +388,43 @@ def test_hull_support_map_returns_the_vertex_of_the_full_scan(robot):
         assert st[2] == 6 * R * R and st[0] / st[2] < 12.0 and st[1] < len(V), st         # a handful of candidates per cell
         checked += 1
     assert checked >= 2
+
+
+PRECISION_LEVELS = {"low": (0.010, 2, 50), "medium": (0.005, 4, 50), "high": (0.0025, 8, 75), "ultra": (0.00125, 16, 75),
+                    "extreme": (0.000625, 32, 100)}   # timestep, frame_skip, Newton iterations (reference config/random_table.yaml)
+
+
+@pytest.mark.parametrize("level", list(PRECISION_LEVELS))
+@pytest.mark.parametrize("env_id", list(ROBOTS))
+def test_every_precision_level_reaches_the_model_blob_and_the_env_layer(env_id, level, monkeypatch):
+    """The level's timestep, frame_skip and iterations land in the compiled blob (what both the engine and the oracle step with),
+    the env layer keeps the reference's control_freq == 50 assertion exactly (flamingo_light_v1.py:36-42), info["dt"] is 0.02 and the
+    time limit (max_sim_step, in the engine's obs config too) does not depend on the level.  BatchedEnv is constructed up to the
+    engine, which a stub stands in for (its host-side bookkeeping is what is checked here; the GPU suite steps the real one)."""
+    import cosim_amd.batched_env as be
+    h, fs, iters = PRECISION_LEVELS[level]
+    cfg = make_config(env_id, random=dict(PARITY_RANDOM, precision=level), max_duration=7.3)
+    assert cfg["random_table"]["precision"][level] == {"timestep": h, "frame_skip": fs, "iterations": iters}
+    cm = compile_model(cfg)
+    b = cm.blob
+    assert (b.timestep, b.frame_skip, b.iterations) == (h, fs, iters)
+    assert b.ls_iterations == 50                                               # (the engine's line search stops at 24: cosim.h)
+
+    class _Stop(Exception):
+        pass
+
+    seen = {}
+
+    def stub_engine(cm_, obs, n, dev, seed, id0):
+        seen["obs"] = obs
+        raise _Stop
+
+    import torch
+    monkeypatch.setattr(torch.cuda, "is_available", lambda: True)
+    monkeypatch.setattr(be, "Engine", stub_engine)
+    env = be.BatchedEnv.__new__(be.BatchedEnv)
+    with pytest.raises(_Stop):
+        env.__init__(cfg, num_envs=2, compiled=cm)
+    assert env.control_freq == 50.0 and env.dt_ * env.frame_skip == 0.02      # info["dt"] (BatchedEnv._info)
+    assert env.frame_skip == fs and env.dt_ == h
+    assert env.max_sim_step == int(7.3 * 50.0) == 365 and seen["obs"].max_sim_step == 365
