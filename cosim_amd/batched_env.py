@@ -83,7 +83,7 @@ class _Data:
 class BatchedEnv:
     def __init__(self, config: dict, num_envs: Optional[int] = None, device: Optional[int] = None, seed: Optional[int] = None,
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
-                 ranges: Optional[int] = None, deferred_join: Optional[bool] = None):
+                 ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -91,7 +91,12 @@ class BatchedEnv:
         the tail of the others' current one; it fits callers whose next action does not need the whole fleet's last state (an
         action table; a policy evaluated per range on ``range_streams``).  With a deferred join the ``action`` tensor of a step must
         stay untouched until that step has run (at most two steps are in flight: an action table or three rotating buffers), and
-        ``receive_user_command`` joins first.  Defaults: ``config["engine"]`` / 1 / False."""
+        ``receive_user_command`` joins first.  Defaults: ``config["engine"]`` / 1 / False.
+
+        ``hfield_fixup`` (heightfield terrain, opt-in): a control step -- on the split pipeline of humanoid_p_v0 a substep -- whose
+        ground contacts exceed the fleet kernel's slots is redone by a kernel with 50 slots per ground geom (the most the narrowphase
+        emits) instead of being cut off and counted in ``dropped_contacts`` (``cosim_set_param "hfield_fixup"``).  Raises
+        ``ValueError`` where the engine has no such kernel (the plane).  Default: ``config["engine"]`` / False."""
         import torch  # plumbing only
 
         eng_cfg = config.get("engine", {})
@@ -164,6 +169,10 @@ class BatchedEnv:
                 self.engine.set_param("envs_per_wave", np.array([float(epw)]))
             except (ValueError, RuntimeError):
                 pass
+
+        self.hfield_fixup = bool(hfield_fixup if hfield_fixup is not None else eng_cfg.get("hfield_fixup", False))
+        if self.hfield_fixup:
+            self.engine.set_param("hfield_fixup", np.array([1.0]))
 
         self.ranges = int(ranges if ranges is not None else os.environ.get("COSIM_RANGES", eng_cfg.get("ranges", 1)))
         self.ranges = max(1, min(self.ranges, self.num_envs, 16))
@@ -365,6 +374,7 @@ class BatchedEnv:
                 "ls_evals": int(m[6]), "factorisations": int(m[7]), "dropped_contacts": int(m[8]), "dropped_limit_rows": int(m[9]),
                 "max_contacts": int(mi[:, 10].max().item()), "episodes_ended": int(m[11]),
                 # control steps redone by the large-capacity kernel because their contacts did not fit the fleet kernel's slots
+                # (heightfield fix-up on the split pipeline: substeps, the unit that pipeline redoes)
                 "fixup_steps": int(m[12]),
                 # heightfield: geoms whose prism walk hit the 32768-prism bound (counted in dropped_contacts too)
                 "truncated_walks": int(m[13])}

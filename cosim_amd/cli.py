@@ -23,6 +23,7 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     report:   report.json
     trace_env: 0
     percentiles: true
+    hfield_fixup: true                                                 # or engine: {hfield_fixup: true}; same as --hfield-fixup
 
 Flags given on the command line override the file.
 """
@@ -61,6 +62,8 @@ def main(argv=None) -> int:
     ap.add_argument("--pipelined", action="store_true",
                     help="policy -> step -> report per env range on the range's own stream, no fleet-wide barrier per step (ONNX MLP policies)")
     ap.add_argument("--ranges", type=int, default=4, help="env ranges of --pipelined")
+    ap.add_argument("--hfield-fixup", action="store_true",
+                    help="heightfield terrain: redo steps whose ground contacts exceed the fleet kernel's slots instead of cutting them off")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -73,7 +76,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles"}
+                               "trace_env", "percentiles", "hfield_fixup"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -95,6 +98,7 @@ def main(argv=None) -> int:
     args.report = pick(args.report, sess.get("report"), "")
     args.trace_env = int(pick(args.trace_env, sess.get("trace_env"), -1))
     args.percentiles = bool(args.percentiles or sess.get("percentiles", False))
+    args.hfield_fixup = bool(args.hfield_fixup or sess.get("hfield_fixup", False) or s_eng.get("hfield_fixup", False))
     # command time series: rows [t, c0, c1, ...]; --command is the row [0, c...]
     commands = [[float(x) for x in row] for row in (sess.get("commands") or [])]
     if args.command is not None:
@@ -130,7 +134,7 @@ def main(argv=None) -> int:
                 cfg[section][k].update(v)
             else:
                 cfg[section][k] = v
-    env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo,
+    env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
                      **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)

@@ -79,6 +79,13 @@ struct cosim_engine {
   // large-capacity kernel behind the fleet kernel (env_fixup_kernel): redoes the control step of envs whose contacts did not fit
   void (*launch_fix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
   int fix_contact_slots = 0;
+  // heightfield fix-up ("hfield_fixup", opt-in): a control step (fused kernel) or a solver substep (split pipeline) with more ground
+  // contacts than the fleet kernel's slots is redone with 50 (mjMAXCONPAIR) x ground-geom slots, the most the narrowphase can emit
+  void (*launch_hfix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;      // behind the fused kernel (whole control step)
+  void (*launch_stepfix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;   // behind each solver launch of the split pipeline
+  void (*launch_dbg_hfix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;  // cosim_debug_forward at that capacity (flamingo_light_v1)
+  int hfix_contact_slots = 0, hfix_lds_bytes = 0;
+  bool hfield_fixup = false;
   // split pipeline (env_narrow_kernel + env_step_kernel, one pair of launches per substep) where the model / terrain has one
   void (*launch_narrow)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
   void (*launch_stepx)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
@@ -120,6 +127,14 @@ static void launch_prof_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
 static void launch_fix_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs of the range
   hipLaunchKernelGGL((env_fixup_kernel<NV, NB, RPL, HF, GTM, SC, MCT>), dim3((grid + 63) / 64), dim3(64), 0, s, a);
+}
+template <int NV, int NB, int RPL, int GTM, bool SC, int MCT, int OCC>
+static void launch_hfix_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs of the range
+  hipLaunchKernelGGL((env_hf_fixup_kernel<NV, NB, RPL, GTM, SC, MCT, OCC>), dim3((grid + 63) / 64), dim3(64), 0, s, a);
+}
+template <int NV, int NB, int RPL, int GTM, bool SC, int MCT, int OCC>
+static void launch_stepfix_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs of the range
+  hipLaunchKernelGGL((env_step_fixup_kernel<NV, NB, RPL, GTM, SC, MCT, OCC>), dim3((grid + 63) / 64), dim3(64), 0, s, a);
 }
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
 static void launch_narrow_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs x waves per env
@@ -166,6 +181,23 @@ static void select_t(cosim_engine* e, bool hf, bool coarse = false) {
   e->contact_slots = hf ? LH::MC : LF::MC;
   e->pair_slots = hf ? LH::MCP : LF::MCP;
   e->geom_stage = hf ? 64 : LF::NGS;
+}
+
+// The heightfield fix-up behind the fleet kernel with MCT_FLEET ground-contact slots: MCT_FIX = 50 (mjMAXCONPAIR, XC) x the robot's
+// ground geoms slots, at the fleet kernel's register budget (waves per SIMD its LDS admits).  SPLIT: also the substep fix-up behind the
+// split pipeline's solver kernel, at that kernel's budget.  Installed as launch_fix only by cosim_set_param "hfield_fixup" 1.
+template <int NV, int NB, int RPL, int GTM, bool SC, int MCT_FLEET, int MCT_FIX, bool SPLIT = false>
+static void hfix_t(cosim_engine* e) {
+  using LF = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FLEET>::L;
+  using LX = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FIX>::L;
+  using LS = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FLEET, 2>::L;
+  using LSX = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FIX, 2>::L;
+  static_assert(sizeof(LX) <= 163840 && sizeof(LSX) <= 163840, "heightfield fix-up: the env's LDS exceeds the 160 KiB of a CU");
+  static_assert(MCT_FIX % XC == 0 && MCT_FIX <= XG * XC, "heightfield fix-up: whole geoms' worth of slots, within the split record");
+  e->launch_hfix = launch_hfix_t<NV, NB, RPL, GTM, SC, MCT_FIX, waves_per_simd(163840 / (int)sizeof(LF))>;
+  if constexpr (SPLIT) e->launch_stepfix = launch_stepfix_t<NV, NB, RPL, GTM, SC, MCT_FIX, waves_per_simd(163840 / (int)sizeof(LS))>;
+  e->hfix_contact_slots = MCT_FIX;
+  e->hfix_lds_bytes = (int)sizeof(LX);
 }
 
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -568,6 +600,10 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
   constexpr int G_LIGHT = GT_SPHERE | GT_CYLINDER | GT_MESH, G_MESH = GT_MESH, G_HUM = GT_BOX | GT_CYLINDER | GT_MESH;
   if (nv == 18 && nb <= 14 && (gtm & ~G_LIGHT) == 0) {   // flamingo_light_v1
     select_t<18, 14, 1, G_LIGHT, false, 0, 128, 48>(e, hf, coarse);
+    if (hf) {   // 13 ground geoms
+      hfix_t<18, 14, 1, G_LIGHT, false, 128, 650>(e);
+      e->launch_dbg_hfix = launch_t<18, 14, 1, true, G_LIGHT, false, 650>;
+    }
     if (!hf) {
       e->launch_prof = launch_prof_t<18, 14, 1, false, G_LIGHT, false, 0>; e->launch2 = launch2_t<18, 14, G_LIGHT>; e->launch_prof2 = launch_prof2_t<18, 14, G_LIGHT>;
       // the same robot on the plane with its ground contacts in twist space (32 slots instead of 12; cosim_set_param "contact_twist")
@@ -588,6 +624,7 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
     // frictionloss rows and at most 8 limit rows (8 hinges)
     // (no coarse-cell variant: at one row per lane the 64-slot kernel already fits the 12 waves per CU its registers allow)
     select_t<14, 10, 1, G_MESH, true, 32, 64, 64>(e, hf, coarse);
+    if (hf) hfix_t<14, 10, 1, G_MESH, true, 64, 400>(e);   // 8 ground geoms
     if (!hf) {
       // Plane: dense rows, like flamingo_light_v1.  With the friction-loss and limit rows in their dofs' lanes all 64 slots are contact
       // rows: 16 contacts, ground and robot-robot together (most seen in the bench: 16), and the dense solver iteration is cheaper
@@ -609,6 +646,7 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
   else if (nv == 22 && nb <= 18 && (gtm & ~G_MESH) == 0) {   // w4_p_v2
     // plane: at most 4 contacts per geom (17 geoms); 80 slots keep the env at 19 KB of LDS = the 8 waves per CU its 256 registers allow
     select_t<22, 18, 2, G_MESH, true, 80, 128, 48>(e, hf, coarse);
+    if (hf) hfix_t<22, 18, 2, G_MESH, true, 128, 850>(e);   // 17 ground geoms
     if (hf && coarse) e->launch_prof = launch_prof_t<22, 18, 2, true, G_MESH, true, 48>;   // diagnostic build of the config-3 kernel
   }
   else if (nv == 29 && nb <= 26 && (gtm & ~G_HUM) == 0) {     // humanoid_p_v0
@@ -620,11 +658,17 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
       e->launch_narrow = launch_narrow_t<29, 26, 2, true, G_HUM, true, 256>;
       e->launch_stepx = launch_stepx_t<29, 26, 2, true, G_HUM, true, 256>;
       e->split = true;
+      hfix_t<29, 26, 2, G_HUM, true, 256, 1100, true>(e);   // 22 ground geoms
     }
   }
   else { delete e; return fail(COSIM_EINVAL, "cosim_create: no kernel instantiation for this (nv, nbody); add one in cosim_engine.hip"); }
   if (nv != 18 && model->neq > 0) { delete e; return fail(COSIM_EINVAL, "cosim_create: this robot's kernels keep no rows for connect equalities"); }
   if (model->ngeom > e->geom_stage) { delete e; return fail(COSIM_EINVAL, "cosim_create: more collision geoms than the plane kernel stages contacts for"); }
+  if (e->launch_hfix) {   // the fix-up capacity must hold 50 contacts per ground geom; a model with more ground geoms has no fix-up
+    int nground = 0;
+    for (int g = 0; g < model->ngeom; g++) nground += model->geom_ground[g] != 0;
+    if (nground * XC > e->hfix_contact_slots) { e->launch_hfix = nullptr; e->launch_stepfix = nullptr; e->launch_dbg_hfix = nullptr; }
+  }
   {
     // support maps of the mesh geoms' hulls (geoms that share a hull slice share the map)
     std::vector<float> cells, cand;
@@ -754,7 +798,10 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "param_stride") return e->lay.p_stride;
   if (n == "lds_bytes") return e->lds_bytes;
   if (n == "contact_slots") return e->contact_slots;
-  if (n == "fixup_contact_slots") return e->launch_fix ? e->fix_contact_slots : 0;   // 0: no large-capacity kernel behind this one
+  if (n == "fixup_contact_slots") {   // 0: no large-capacity kernel behind this one
+    if (e->split && e->launch_stepx) return e->hfield_fixup && e->launch_stepfix ? e->hfix_contact_slots : 0;
+    return e->launch_fix ? e->fix_contact_slots : 0;
+  }
   if (n == "ranges") return e->n_ranges;
   if (n == "rollout") return e->launch_roll && e->epw == 1 ? 1 : 0;   // 1: cosim_rollout is available for this model / terrain
   if (n == "split") return (e->split && e->launch_stepx) ? e->narrow_waves : 0;   // waves per env of the narrowphase kernel; 0: fused kernel
@@ -821,7 +868,19 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
     return COSIM_OK;
   }
   else if (n == "fixup") {   // 0: no fix-up launches (contacts beyond the fleet kernel's slots are left out and counted, as in round 2)
-    if ((int)host[0] == 0) { e->launch_fix = nullptr; if (e->launch_roll_fix) { e->launch_roll = nullptr; e->launch_roll_fix = nullptr; } }
+    if ((int)host[0] == 0) {
+      e->launch_fix = nullptr; if (e->launch_roll_fix) { e->launch_roll = nullptr; e->launch_roll_fix = nullptr; }
+      e->launch_hfix = nullptr; e->launch_stepfix = nullptr; e->launch_dbg_hfix = nullptr; e->hfield_fixup = false;
+    }
+    return COSIM_OK;
+  }
+  else if (n == "hfield_fixup") {   // 1: heightfield steps whose ground contacts exceed the fleet kernel's slots are redone (opt-in)
+    const int v = (int)host[0];
+    if (v != 0 && v != 1) return fail(COSIM_EINVAL, "cosim_set_param: hfield_fixup must be 0 or 1");
+    if (!e->launch_hfix || e->epw != 1) return fail(COSIM_EINVAL, "cosim_set_param: no heightfield fix-up for this model / terrain / kernel variant");
+    e->hfield_fixup = v != 0;
+    e->launch_fix = v ? e->launch_hfix : nullptr;   // (heightfield engines have no other fix-up kernel)
+    e->fix_contact_slots = v ? e->hfix_contact_slots : 0;
     return COSIM_OK;
   }
   else if (n == "contact_twist") {   // 1: switch a dense-row kernel to its contact-twist variant (more contact slots), where one exists
@@ -1052,7 +1111,10 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev;
   a.env_first = first; a.env_count = count;
   if (e->split && e->launch_stepx && e->narrow_occ == 0) a.dbg = e->d_dbg;   // diagnostic narrowphase build accumulates its counters there
-  a.ovf = (e->launch_fix && e->epw == 1) ? e->d_ovf : nullptr;
+  // the fix-up behind this launch: the split pipeline's after each solver launch ("hfield_fixup"), else the one after the fleet kernel
+  const bool split = e->split && e->launch_stepx;
+  auto fix = split ? (e->hfield_fixup ? e->launch_stepfix : nullptr) : e->launch_fix;
+  a.ovf = (fix && e->epw == 1) ? e->d_ovf : nullptr;
   hipStream_t s = (hipStream_t)stream;
   // kernel timing: one HIP event pair per launch on the launch stream, read back in cosim_kernel_time() (no sync here)
   int slot = -1;
@@ -1065,18 +1127,23 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     e->ev_used += 2;
     HIP_TRY(hipEventRecord(e->ev[slot], s));
   }
-  if (e->split && e->launch_stepx) {
-    // one pair of launches per substep: the prism walk (narrow_waves waves per env), then the solver with the contacts it left
+  if (split) {
+    // one pair of launches per substep: the prism walk (narrow_waves waves per env), then the solver with the contacts it left; with
+    // "hfield_fixup", the substeps the solver gave up (more ground contacts than its slots) are redone right behind it from the same
+    // record.  The narrowphase kernel never flags: it is given no ovf.
+    KArgs an = a;
+    an.ovf = nullptr;
     const int fs = e->nsub_override > 0 ? e->nsub_override : e->model.frame_skip;
     for (int sub = 0; sub < fs; sub++) {
-      a.sub_index = sub; a.sub_total = fs;
-      e->launch_narrow(e, a, count * e->narrow_waves, s);
+      a.sub_index = sub; a.sub_total = fs; an.sub_index = sub; an.sub_total = fs;
+      e->launch_narrow(e, an, count * e->narrow_waves, s);
       e->launch_stepx(e, a, count, s);
+      if (a.ovf) fix(e, a, count, s);
     }
   } else (e->epw == 2 ? e->launch2 : e->launch)(e, a, count, s);
   HIP_TRY(hipGetLastError());
   if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
-  if (a.ovf) {   // envs the fleet kernel flagged (more contacts than it has slots for) are redone by the large-capacity kernel
+  if (a.ovf && !split) {   // envs the fleet kernel flagged (more contacts than it has slots for) are redone by the large-capacity kernel
     e->launch_fix(e, a, count, s);
     HIP_TRY(hipGetLastError());
   }
@@ -1153,6 +1220,7 @@ int cosim_debug_forward(cosim_engine_t* e, int env, const char* name, float* hos
   KArgs a = base_args(e);
   a.mode = MODE_DEBUG; a.dbg = e->d_dbg; a.dbg_env = env;
   if (e->split && e->launch_stepx) { e->launch_narrow(e, a, e->narrow_waves, 0); e->launch_stepx(e, a, 1, 0); }   // the product's own pair of kernels
+  else if (e->hfield_fixup && e->launch_dbg_hfix) e->launch_dbg_hfix(e, a, 1, 0);   // every contact the fix-up kernel would keep
   else (e->epw == 2 ? e->launch2 : e->launch)(e, a, 1, 0);   // two-per-wave kernel: both groups replay env `env`, same dump twice
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());

@@ -633,7 +633,8 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
                                          const int kstep = 0) {   // kstep: control step of a rollout launch (row of the [K][N][...] I/O buffers)
   static_assert(EPW == 1 || (EPW == 2 && !HF && !SC && NV <= 32 && NB <= 32), "two environments per wave: flat ground, no pairs");
   static_assert(MCT == 0 || EPW == 1, "contact-twist mode: one environment per wave");
-  static_assert(KM == 0 || (HF && MCT > 0 && EPW == 1 && !FIX && (!PROF || KM == 1)), "split pipeline: heightfield contact-twist kernels");
+  static_assert(KM == 0 || (HF && MCT > 0 && EPW == 1 && (!FIX || KM == 2) && (!PROF || KM == 1)),
+                "split pipeline: heightfield contact-twist kernels (a fix-up only of the solver's substep)");
   using KT = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>;
   // split pipeline: this launch is substep sub_index of sub_total; the control-step prologue runs in the first, the epilogue in the last
   const bool sub_first = KM == 0 || A.sub_total == 0 || A.sub_index == 0;
@@ -2016,6 +2017,10 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
           // more contacts than this kernel has slots for, and the engine has a large-capacity kernel: give the step up (nothing of
           // it has been written) and flag the env; env_fixup_kernel redoes it from the same state right after this launch
           // (readfirstlane: heightfield kernels read the count from LDS, which the compiler must take for a per-lane value)
+          // Split pipeline (KM == 2): the unit given up and redone is this launch's substep.  Nothing has been stored by then either:
+          // the control prologue of the first substep (delay filter, PD, applied command) lives in LDS until the write-back at the end
+          // of the substep, the state, xstate and meta words are written only there, and the narrowphase record this launch read is
+          // left as it was -- env_step_fixup_kernel reads the same record and redoes the substep from the same state.
           if (kmode == MODE_STEP && A.ovf != nullptr && __builtin_amdgcn_readfirstlane(ncon_all - ncon - npc) > 0) {
             if (ln == 0) A.ovf[env] = 1 + kstep;   // (rollout launch: the step the large-capacity kernel takes over at)
             return;
@@ -2830,6 +2835,7 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
           meta[0] = sim_step; meta[2] = has_prev;
           meta[5] += st_newton; meta[6] += st_ls; meta[7] += st_build; meta[3] += st_rows;
           meta[8] += st_dropcon + st_walkcut; meta[9] += st_droplim; meta[10] = max(meta[10], st_maxcon); meta[13] += st_walkcut;
+          if constexpr (FIX) { meta[12] += 1; A.ovf[env] = 0; }   // substeps redone by the large-capacity solver
         }
         return;
       }
@@ -3120,6 +3126,44 @@ __global__ __launch_bounds__(64, 4) void env_fixup_kernel(KArgs kernarg_block) {
     const int env = base + __builtin_ctzll(m);
     m &= m - 1;
     env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, true>(kargs_p, env, SS);
+    WSYNC();
+  }
+}
+
+// The heightfield fix-up kernels ("hfield_fixup" 1): the same flag scan, with MCT = 50 prisms (mjMAXCONPAIR) x the robot's ground
+// geoms slots, the most the heightfield narrowphase can emit -- no ground contact is ever left out for want of a slot.  OCC: waves per
+// SIMD the register allocator is asked for, the fleet kernel's (the fp64 MPR portal of the prism walk spills ~150 registers at the
+// plane fix-up's 128).  env_hf_fixup_kernel redoes a whole control step behind a fused fleet kernel; env_step_fixup_kernel redoes one
+// substep behind a solver launch of the split pipeline (env_step_kernel), from the contact record the narrowphase launch left.
+template <int NV, int NB, int RPL, int GTM, bool SC, int MCT, int OCC>
+__global__ __launch_bounds__(64, OCC) void env_hf_fixup_kernel(KArgs kernarg_block) {
+  KArgsP kargs_p = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
+  (void)kernarg_block;
+  __shared__ typename KTraits<NV, NB, RPL, true, SC, 1, MCT>::L SS[1];
+  const int base = A.env_first + (int)blockIdx.x * 64, e = base + (int)threadIdx.x;
+  const int fl = (e < A.env_first + A.env_count && e < A.n_envs) ? A.ovf[e] : 0;
+  unsigned long long m = __ballot(fl != 0);
+#pragma nounroll
+  while (m) {   // wave-uniform
+    const int env = base + __builtin_ctzll(m);
+    m &= m - 1;
+    env_body<NV, NB, RPL, true, GTM, SC, false, 1, MCT, true>(kargs_p, env, SS);
+    WSYNC();
+  }
+}
+template <int NV, int NB, int RPL, int GTM, bool SC, int MCT, int OCC>
+__global__ __launch_bounds__(64, OCC) void env_step_fixup_kernel(KArgs kernarg_block) {
+  KArgsP kargs_p = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
+  (void)kernarg_block;
+  __shared__ typename KTraits<NV, NB, RPL, true, SC, 1, MCT, 2>::L SS[1];
+  const int base = A.env_first + (int)blockIdx.x * 64, e = base + (int)threadIdx.x;
+  const int fl = (e < A.env_first + A.env_count && e < A.n_envs) ? A.ovf[e] : 0;
+  unsigned long long m = __ballot(fl != 0);
+#pragma nounroll
+  while (m) {   // wave-uniform
+    const int env = base + __builtin_ctzll(m);
+    m &= m - 1;
+    env_body<NV, NB, RPL, true, GTM, SC, false, 1, MCT, true, 2>(kargs_p, env, SS);
     WSYNC();
   }
 }

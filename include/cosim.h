@@ -94,7 +94,12 @@ int cosim_query(const cosim_engine_t* e, const char* name);
  * range stream before it blocks, default 2, 0 = unbounded: deep queues step slower on this runtime), "split" (heightfield kernels that have the two-kernel pipeline -- humanoid_p_v0:
  * the prism walk in a kernel of its own, "narrow_waves" (default 6) waves per env, and the solver one substep per launch; 0 goes back
  * to the fused kernel), "fixup" (0 switches the
- * large-capacity fix-up launches off: contacts beyond the fleet kernel's slots are then left out and counted), "support_map" (1,
+ * large-capacity fix-up launches off, the heightfield one included: contacts beyond the fleet kernel's slots are then left out and
+ * counted), "hfield_fixup" (heightfield terrain, opt-in, default 0; COSIM_EINVAL on the plane and with "envs_per_wave" 2: 1 redoes what
+ * does not fit the fleet kernel's ground-contact slots with 50 (mjMAXCONPAIR) slots per ground geom -- 650 flamingo_light_v1, 400
+ * flamingo_p_v3, 850 w4_p_v2, 1100 humanoid_p_v0 -- the most the narrowphase can emit, so no ground contact is left out for want of a
+ * slot; the fused kernel gives up and flags the control step, the split pipeline's solver launch the substep, and a fix-up launch on the
+ * same stream redoes it from the untouched state; robot-robot pair slots are unchanged), "support_map" (1,
  * default: support queries on mesh geoms with 32 or more hull vertices go through the hull's support map -- the few vertices that can
  * win in the direction's cube-map cell, same arg max as the scan; 0: every query scans the whole hull, for A/B runs and tests),
  * "timing_stride" (default 1: with cosim_set_timing on, an event pair around every launch; n: around every n-th launch -- the
@@ -103,7 +108,8 @@ int cosim_query(const cosim_engine_t* e, const char* name);
  * their prisms; 0: every block goes on to the per-prism tests; same contacts either way).
  * cosim_query additionally answers "contact_slots" / "pair_slots" (capacity of the selected kernel variant: heightfields with cells
  * of 10 cm or more select the 48-slot variants of flamingo_light_v1 / w4_p_v2), "fixup_contact_slots" (capacity of the kernel that
- * redoes a control step whose contacts did not fit; 0: this model / terrain has none), "ranges", "lds_bytes", "frame_skip" (physics
+ * redoes a control step -- on the split pipeline with "hfield_fixup", a substep -- whose contacts did not fit; 0: this model / terrain
+ * has none, or it is switched off: on a heightfield it is non-zero only while "hfield_fixup" is 1), "ranges", "lds_bytes", "frame_skip" (physics
  * substeps per control step: the precision level's) and "max_newton" / "max_ls" (the caps the solver runs with). */
 int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int count);
 
@@ -164,7 +170,10 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
                      uint8_t* terminated_dev, uint8_t* truncated_dev, float* info_out_dev, void* stream);
 
 /* Replaces env.get_data() reads (reference flamingo_light_v1.py:247-248; wrappers.py:360-367): copies
- * "qpos"[N,nq] / "qvel"[N,nv] / "qacc_warmstart"[N,nv] / "sim_step"[N] (as float) to a device buffer. */
+ * "qpos"[N,nq] / "qvel"[N,nv] / "qacc_warmstart"[N,nv] / "sim_step"[N] (as float) to a device buffer.  "meta"[N,16] (int32 bits):
+ * per-env counters, among them [8] contacts left out, [10] most contacts in one substep, [12] fix-up passes -- control steps redone
+ * by a large-capacity kernel; on the split pipeline with "hfield_fixup", substeps (the unit that pipeline redoes) -- and [13] prism
+ * walks cut at their bound (solver_stats() in cosim_amd/batched_env.py sums them). */
 int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream);
 /* Test / checkpoint hook: overwrite "qpos"/"qvel"/"qacc_warmstart" from a device buffer. */
 int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* stream);
