@@ -83,7 +83,8 @@ class _Data:
 class BatchedEnv:
     def __init__(self, config: dict, num_envs: Optional[int] = None, device: Optional[int] = None, seed: Optional[int] = None,
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
-                 ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None):
+                 ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
+                 spawn=None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -96,7 +97,11 @@ class BatchedEnv:
         ``hfield_fixup`` (heightfield terrain, opt-in): a control step -- on the split pipeline of humanoid_p_v0 a substep -- whose
         ground contacts exceed the fleet kernel's slots is redone by a kernel with 50 slots per ground geom (the most the narrowphase
         emits) instead of being cut off and counted in ``dropped_contacts`` (``cosim_set_param "hfield_fixup"``).  Raises
-        ``ValueError`` where the engine has no such kernel (the plane).  Default: ``config["engine"]`` / False."""
+        ``ValueError`` where the engine has no such kernel (the plane).  Default: ``config["engine"]`` / False.
+
+        ``spawn``: a spawn table -- an ``[M, 3]`` array of ``(x, y, yaw)`` or a dict ``{"pattern": "grid" | "uniform" | "poses",
+        "count", "extent", "yaw", "per_episode", "clearance", "poses"}`` (``cosim_amd/spawn.py``) -- see ``set_spawn``.  Default:
+        ``config["engine"].get("spawn")`` / none: every reset goes to the model's ``init_qpos``."""
         import torch  # plumbing only
 
         eng_cfg = config.get("engine", {})
@@ -189,6 +194,9 @@ class BatchedEnv:
             self.range_streams = [torch.cuda.ExternalStream(st, device=self.device) for _, _, st in rl]
 
         self._randomise(gain_noise)
+        spawn = spawn if spawn is not None else eng_cfg.get("spawn")
+        if spawn is not None:
+            self.set_spawn(spawn)
 
         N, t = self.num_envs, torch
         f32 = dict(dtype=t.float32, device=self.device)
@@ -358,6 +366,37 @@ class BatchedEnv:
                 x = t.as_tensor(v, dtype=t.float32, device=self.device).contiguous()
                 self.engine.set(name, x.data_ptr(), self._stream())
                 t.cuda.synchronize(self.device)
+
+    # ------------------------------------------------------------------ spawn table (cosim_spawn_set)
+    def set_spawn(self, spawn, clearance: Optional[float] = None, per_episode: Optional[bool] = None):
+        """Spread the fleet's resets over the terrain.  ``spawn``: ``[M, 3]`` rows ``(x, y, yaw)``, or the dict that
+        ``spawn.resolve`` documents (pose generators ``grid`` / ``uniform`` use the env's seed), or ``None`` / an empty array to
+        clear the table.  The engine lifts every row onto the heightfield on the device (no penetration, ``clearance`` metres of
+        extra height) and every later reset of an env -- ``reset()``, the auto-reset inside ``step()`` / ``rollout()``, the reset
+        after a non-finite state -- takes its base pose ``qpos[0:7]`` from row ``global env id mod M``, or with ``per_episode`` from
+        a row drawn anew for each episode.  Joint angles, init noise and velocities are as without a table.  Ranks of a distributed
+        run that set the same table give the results of one fleet.  Limits: yaw orientations only (others raise ``ValueError``);
+        position-mode commands stay world-frame targets; rows that are not finite or reach off the field raise ``ValueError``."""
+        from . import spawn as sp
+        if spawn is None or (not isinstance(spawn, dict) and np.asarray(spawn).size == 0):
+            self.engine.spawn_set(np.zeros((0, 3), dtype=np.float32), np.zeros((0, 4), dtype=np.float32), 0.0, False, self._stream())
+            return
+        xy, clr, per = sp.resolve(self.cm, spawn, self.seed)
+        clr = float(clearance) if clearance is not None else clr
+        per = bool(per_episode) if per_episode is not None else per
+        self.engine.spawn_set(xy, sp.footprint(self.cm), clr, per, self._stream())
+
+    def spawn_poses(self) -> np.ndarray:
+        """The placed table, host float32 ``[M, 7]`` = ``x, y, z, qw, qx, qy, qz`` (``[0, 7]`` with no table)."""
+        return self.engine.spawn_get()
+
+    def spawn_rows(self) -> np.ndarray:
+        """Per env: the table row its last reset took (int64 ``[N]``, engine meta word 14; meaningful once a table is set)."""
+        t = self.torch
+        buf = t.zeros((self.num_envs, 16), dtype=t.float32, device=self.device)
+        self.engine.get("meta", buf.data_ptr(), self._stream())
+        t.cuda.synchronize(self.device)
+        return buf.view(t.int32)[:, 14].cpu().numpy().astype(np.int64)
 
     def solver_stats(self):
         """Cumulative solver counters since creation (fleet sums): control steps, constraint rows (summed over

@@ -24,6 +24,7 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     trace_env: 0
     percentiles: true
     hfield_fixup: true                                                 # or engine: {hfield_fixup: true}; same as --hfield-fixup
+    spawn:    {pattern: uniform, count: 256, extent: 100.0, per_episode: true, clearance: 0.01}   # or engine: {spawn: {...}}; same as --spawn*
 
 Flags given on the command line override the file.
 """
@@ -64,6 +65,12 @@ def main(argv=None) -> int:
     ap.add_argument("--ranges", type=int, default=4, help="env ranges of --pipelined")
     ap.add_argument("--hfield-fixup", action="store_true",
                     help="heightfield terrain: redo steps whose ground contacts exceed the fleet kernel's slots instead of cutting them off")
+    ap.add_argument("--spawn", choices=["grid", "uniform"], default=None,
+                    help="spread resets over the terrain: a table of base poses on a grid / drawn uniformly, placed on the heightfield")
+    ap.add_argument("--spawn-count", type=int, default=None, help="rows of the spawn table (default: --num-envs)")
+    ap.add_argument("--spawn-extent", type=float, default=None, help="half-size (m) of the square the poses fill (default: the field minus the footprint)")
+    ap.add_argument("--spawn-per-episode", action="store_true", help="draw a row anew at every reset instead of row = env id mod count")
+    ap.add_argument("--spawn-clearance", type=float, default=None, help="extra height (m) above the no-penetration placement")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -76,7 +83,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -99,6 +106,20 @@ def main(argv=None) -> int:
     args.trace_env = int(pick(args.trace_env, sess.get("trace_env"), -1))
     args.percentiles = bool(args.percentiles or sess.get("percentiles", False))
     args.hfield_fixup = bool(args.hfield_fixup or sess.get("hfield_fixup", False) or s_eng.get("hfield_fixup", False))
+    # spawn table: the session's dict (top level or engine.spawn), overridden key by key by the flags; the table is built from the
+    # TOTAL env count and the seed, so every rank sets the same one
+    spawn = dict(sess.get("spawn") or s_eng.get("spawn") or {})
+    if args.spawn is not None:
+        spawn["pattern"] = args.spawn
+    for key, val in (("count", args.spawn_count), ("extent", args.spawn_extent), ("clearance", args.spawn_clearance)):
+        if val is not None:
+            spawn[key] = val
+    if args.spawn_per_episode:
+        spawn["per_episode"] = True
+    if spawn and "pattern" not in spawn and spawn.get("poses") is None:
+        ap.error("--spawn-* / spawn: needs a pattern (--spawn grid|uniform) or poses")
+    if spawn and spawn.get("pattern") in ("grid", "uniform"):
+        spawn.setdefault("count", args.num_envs)
     # command time series: rows [t, c0, c1, ...]; --command is the row [0, c...]
     commands = [[float(x) for x in row] for row in (sess.get("commands") or [])]
     if args.command is not None:
@@ -135,7 +156,7 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:

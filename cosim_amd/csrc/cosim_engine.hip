@@ -13,6 +13,7 @@
 
 #include "cosim_kernels.hip"
 #include "cosim_mlp.hip"
+#include "cosim_spawn.hip"
 
 using namespace cosim;
 
@@ -114,6 +115,10 @@ struct cosim_engine {
   int inflight = 2;   // 0: unbounded
   std::vector<hipEvent_t> ring;   // [n_ranges][inflight]
   long ring_pos = 0;
+  // spawn table (cosim_spawn_set): base poses the reset block takes instead of init_qpos[0:7]; placed by spawn_place_kernel
+  float* d_spawn = nullptr;       // [spawn_rows][8]
+  std::vector<float> h_spawn;     // host copy of the placed table (cosim_spawn_get)
+  int spawn_rows = 0, spawn_mode = 0;
 };
 
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
@@ -766,6 +771,7 @@ int cosim_destroy(cosim_engine_t* e) {
   hipFree(e->d_model); hipFree(e->d_obs); hipFree(e->d_state); hipFree(e->d_params); hipFree(e->d_dbg);
   hipFree(e->d_hull_vert); hipFree(e->d_hull_adr); hipFree(e->d_hull_nbr); hipFree(e->d_hfield);
   hipFree(e->d_hull_cell); hipFree(e->d_hull_cand); hipFree(e->d_hfield_mip);
+  hipFree(e->d_spawn);
   hipFree(e->d_pairs); hipFree(e->d_gext); hipFree(e->d_ovf); hipFree(e->d_xcon); hipFree(e->d_xcnt); hipFree(e->d_xstate);
   for (hipEvent_t x : e->ev) hipEventDestroy(x);
   for (hipStream_t x : e->rstream) hipStreamDestroy(x);
@@ -811,6 +817,8 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "max_newton") return newton_cap(e);   // Newton iterations per substep the solver may take
   if (n == "max_ls") return ls_cap(e);           // line-search evaluations per Newton iteration
   if (n == "frame_skip") return e->model.frame_skip;
+  if (n == "spawn_rows") return e->spawn_rows;   // rows of the spawn table (0: none, resets go to init_qpos)
+  if (n == "spawn_mode") return e->spawn_mode;   // 0: row = global env id mod rows; 1: drawn per episode
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
 }
 
@@ -935,6 +943,8 @@ static KArgs base_args(cosim_engine* e) {
   a.tol32 = e->tol32; a.ls_scale = e->ls_scale; a.max_newton = newton_cap(e); a.max_ls = ls_cap(e); a.nsub_override = e->nsub_override; a.pair_coop = e->pair_coop; a.pair_boxbox = e->pair_boxbox; a.block_cull = e->block_cull; a.coop_walk = e->coop_walk;
   for (int k = 0; k < 4; k++) a.prio[k] = e->prio[k];
   a.ovf = nullptr; a.roll_steps = 1;
+  a.spawn = e->d_spawn; a.spawn_rows = e->spawn_rows; a.spawn_mode = e->spawn_mode;
+  a.spawn_off = e->spawn_rows > 0 ? (unsigned)(((e->env_id0 % e->spawn_rows) + e->spawn_rows) % e->spawn_rows) : 0u;
   a.xcon = e->d_xcon; a.xcnt = e->d_xcnt; a.xstate = e->d_xstate; a.nw = e->narrow_waves; a.sub_index = 0; a.sub_total = 0;
   return a;
 }
@@ -1148,6 +1158,84 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     HIP_TRY(hipGetLastError());
   }
   return COSIM_OK;
+}
+
+// Spawn table: validate on the host (a message that names the row), upload, place every row on the heightfield with
+// spawn_place_kernel, keep the [rows][8] table on the device and a copy on the host.  Blocks until the table is placed (cold path).
+int cosim_spawn_set(cosim_engine_t* e, const float* xyyaw_host, int rows, const float* footprint_host, int n_foot, float clearance,
+                    int per_episode, void* stream) {
+  if (!e || rows < 0 || rows > (1 << 24)) return fail(COSIM_EINVAL, "cosim_spawn_set: null engine or rows outside 0..2^24");
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t cs = (hipStream_t)stream;
+  { int rc = join_ranges(e, cs); if (rc) return rc; }
+  if (rows == 0) {   // clear: resets go back to init_qpos (launches already enqueued keep the table they were given)
+    HIP_TRY(hipStreamSynchronize(cs));
+    HIP_TRY(hipFree(e->d_spawn));
+    e->d_spawn = nullptr; e->spawn_rows = 0; e->spawn_mode = 0; e->h_spawn.clear();
+    return COSIM_OK;
+  }
+  const cosim_model_t& m = e->model;
+  const bool hf = m.ground_type == CS_GEOM_HFIELD;
+  if (!xyyaw_host || n_foot < 0 || n_foot > 64 || (n_foot > 0 && !footprint_host)) return fail(COSIM_EINVAL, "cosim_spawn_set: bad argument");
+  if (!(clearance >= 0.f) || !std::isfinite(clearance)) return fail(COSIM_EINVAL, "cosim_spawn_set: clearance must be finite and >= 0");
+  if (hf && (long long)m.hfield_nrow * m.hfield_ncol > 0x7fffffffLL) return fail(COSIM_EINVAL, "cosim_spawn_set: heightfield too large");
+  for (int g = 0; g < 4 * n_foot; g++)
+    if (!std::isfinite(footprint_host[g])) return fail(COSIM_EINVAL, "cosim_spawn_set: non-finite footprint entry");
+  for (int g = 0; g < n_foot; g++)
+    if (footprint_host[4 * g + 2] < 0.f || footprint_host[4 * g + 3] < 0.f) return fail(COSIM_EINVAL, "cosim_spawn_set: footprint radius / free height must be >= 0");
+  for (int r = 0; r < rows; r++) {
+    const float x = xyyaw_host[3 * (size_t)r], y = xyyaw_host[3 * (size_t)r + 1], yaw = xyyaw_host[3 * (size_t)r + 2];
+    if (!std::isfinite(x) || !std::isfinite(y) || !std::isfinite(yaw))
+      return fail(COSIM_EINVAL, "cosim_spawn_set: row " + std::to_string(r) + " is not finite");
+    if (!hf) continue;
+    const double c = cos((double)yaw), s = sin((double)yaw);
+    for (int g = 0; g < n_foot; g++) {   // every footprint window must lie on the field: |l| + r <= s
+      const double ox = footprint_host[4 * g], oy = footprint_host[4 * g + 1], rb = footprint_host[4 * g + 2];
+      const double lx = (double)x + (c * ox - s * oy) - (double)(float)m.ground_pos[0], ly = (double)y + (s * ox + c * oy) - (double)(float)m.ground_pos[1];
+      if (fabs(lx) + rb > (double)(float)m.hfield_size[0] || fabs(ly) + rb > (double)(float)m.hfield_size[1])
+        return fail(COSIM_EINVAL, "cosim_spawn_set: row " + std::to_string(r) + " puts footprint geom " + std::to_string(g) + " off the heightfield");
+    }
+  }
+  if (rows != e->spawn_rows) {   // a new size: a new table (the same size is rewritten in place, the pointer stays for captured graphs)
+    HIP_TRY(hipStreamSynchronize(cs));
+    HIP_TRY(hipFree(e->d_spawn));
+    e->d_spawn = nullptr; e->spawn_rows = 0; e->h_spawn.clear();
+    HIP_TRY(hipMalloc(&e->d_spawn, (size_t)rows * 8 * sizeof(float)));
+  }
+  float *d_in = nullptr, *d_foot = nullptr;
+  std::vector<float> placed((size_t)rows * 8);
+  auto run = [&]() -> hipError_t {   // (one exit, so that the two input buffers are released on every path)
+    hipError_t r;
+    if ((r = hipMalloc(&d_in, (size_t)rows * 3 * sizeof(float))) != hipSuccess) return r;
+    if ((r = hipMalloc(&d_foot, (size_t)(n_foot > 0 ? n_foot : 1) * 4 * sizeof(float))) != hipSuccess) return r;
+    if ((r = hipMemcpy(d_in, xyyaw_host, (size_t)rows * 3 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return r;
+    if (n_foot > 0 && (r = hipMemcpy(d_foot, footprint_host, (size_t)n_foot * 4 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return r;
+    SpawnArgs a;
+    memset(&a, 0, sizeof a);
+    a.xyyaw = d_in; a.foot = reinterpret_cast<const float4*>(d_foot); a.out = e->d_spawn; a.hfield = hf ? e->d_hfield : nullptr;
+    a.rows = rows; a.n_foot = n_foot; a.nrow = m.hfield_nrow; a.ncol = m.hfield_ncol;
+    a.sx = (float)m.hfield_size[0]; a.sy = (float)m.hfield_size[1]; a.sz = (float)m.hfield_size[2];
+    a.gx = (float)m.ground_pos[0]; a.gy = (float)m.ground_pos[1];
+    a.init_z = (float)m.init_qpos[2]; a.clearance = clearance;
+    for (int k = 0; k < 4; k++) a.iq[k] = (float)m.init_qpos[3 + k];
+    hipLaunchKernelGGL(spawn_place_kernel, dim3(rows), dim3(64), 0, cs, a);   // behind the steps already on the stream: they keep the old rows
+    if ((r = hipGetLastError()) != hipSuccess) return r;
+    if ((r = hipStreamSynchronize(cs)) != hipSuccess) return r;
+    return hipMemcpy(placed.data(), e->d_spawn, placed.size() * sizeof(float), hipMemcpyDeviceToHost);
+  };
+  const hipError_t r = run();
+  (void)hipFree(d_in); (void)hipFree(d_foot);
+  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_spawn_set: ") + hipGetErrorString(r));
+  e->h_spawn.swap(placed);
+  e->spawn_rows = rows; e->spawn_mode = per_episode != 0;
+  return COSIM_OK;
+}
+
+int cosim_spawn_get(cosim_engine_t* e, float* poses_host, int capacity) {
+  if (!e || (capacity > 0 && !poses_host)) return fail(COSIM_EINVAL, "cosim_spawn_get: null argument");
+  const int n = e->spawn_rows < capacity ? e->spawn_rows : capacity;
+  for (int r = 0; r < n; r++) memcpy(poses_host + 7 * (size_t)r, e->h_spawn.data() + 8 * (size_t)r, 7 * sizeof(float));
+  return e->spawn_rows;
 }
 
 static int locate(cosim_engine* e, const std::string& n, int* off, int* width) {

@@ -81,6 +81,11 @@ struct KArgs {
   int roll_steps;         // rollout launch (env_rollout_kernel): control steps per launch; actions / state_out / terminated / truncated / info are then [roll_steps][N][...]
   int* ovf;               // [N] per-env flag "this control step needs the large-capacity kernel" (null: no such kernel; contacts that find no slot are left out and counted)
   int env_count;          // envs of this launch (the fix-up kernel scans ovf[env_first .. env_first + env_count))
+  // spawn table (cosim_spawn_set): a reset takes the base pose qpos[0:7] from a row instead of init_qpos; spawn_rows 0 = no table
+  const float* spawn;     // [spawn_rows][8]: x, y, z, qw, qx, qy, qz, --
+  int spawn_rows;
+  int spawn_mode;         // 0: row = global env id mod rows; 1: a draw per episode (purpose 5)
+  unsigned spawn_off;     // env_id0 mod spawn_rows, so that mode 0 needs no 64-bit division: row = (spawn_off + env) mod rows
 };
 
 // ------------------------------------------------------------------------------------------------ wave helpers
@@ -2880,6 +2885,13 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
   if (do_reset) {
     if (lane < nq) S.qpos[lane] = dm.rec[lane].init_qpos;
     if (lane < NV) { S.qvel[lane] = 0.f; S.qacc[lane] = 0.f; }
+    if (A.spawn_rows > 0) {   // base pose from the spawn table; the row is a function of the global env id (and the seed) only
+      const unsigned rows = (unsigned)A.spawn_rows;
+      const unsigned row = A.spawn_mode == 0 ? (A.spawn_off + (unsigned)env) % rows
+                                             : min(rows - 1u, (unsigned)(u01(philox_first(k0, k1, step_count, 5u, g0, g1)) * (float)rows));
+      if (lane < 7) S.qpos[lane] = A.spawn[8 * (size_t)row + lane];
+      if (lane == 0) meta[14] = (int)row;
+    }
     WSYNC();
     if (lane < dm.init_noise_nq)
       S.qpos[dm.rec[lane].n_qadr] += ob.init_noise * (2.f * u01(philox_first(k0, k1, step_count, 2u | ((unsigned)lane << 8), g0, g1)) - 1.f);
@@ -2887,6 +2899,10 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
     // sensors of the mj_forward at the reset state: zero velocity, IMU orientation from the base quaternion
     {
       float xq[4] = {S.qpos[3], S.qpos[4], S.qpos[5], S.qpos[6]}, sq[4];
+      // a spawn row's quaternion is q_yaw (x) init_quat, and a yaw about world z does not turn gravity in the body frame: the
+      // quaternion projected gravity is built from is the yaw-free one, so the reset's state vector does not carry the yaw's
+      // rounding (w^2 + z^2 is 1 only to an ulp) and is, bit for bit, that of a reset without a table
+      if (A.spawn_rows > 0) for (int k = 0; k < 4; k++) xq[k] = dm.rec[3 + k].init_qpos;
       qnorm(xq);
       qmul(sq, xq, dm.imu_quat);
       qnorm(sq);

@@ -100,6 +100,8 @@ def load_library():
     L.cosim_get.argtypes = [vp, ctypes.c_char_p, vp, vp]
     L.cosim_set.argtypes = [vp, ctypes.c_char_p, vp, vp]
     L.cosim_event_push.argtypes = [vp, vp, vp, vp]
+    L.cosim_spawn_set.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, ci, vp]
+    L.cosim_spawn_get.argtypes = [vp, vp, ci]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
     L.cosim_set_timing.argtypes = [vp, ci]
@@ -108,7 +110,7 @@ def load_library():
     for fn in ("cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "cosim_reset", "cosim_step", "cosim_step_range", "cosim_get",
                "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_rollout",
                "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
-               "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof"):
+               "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -121,7 +123,8 @@ def load_library():
 EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "cosim_reset", "cosim_step", "cosim_step_range", "cosim_get",
            "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_hull_support_check", "cosim_debug_support",
            "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
-           "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof"]
+           "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
+           "cosim_spawn_set", "cosim_spawn_get"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -266,6 +269,19 @@ class Engine:
 
     def push(self, v_ptr, mask_ptr, stream=None):
         self._check(self.L.cosim_event_push(self.h, v_ptr, mask_ptr, stream))
+
+    def spawn_set(self, xyyaw: np.ndarray, footprint: np.ndarray, clearance: float, per_episode: bool, stream=None):
+        """``cosim_spawn_set``: ``xyyaw`` [M, 3] (M = 0 clears the table), ``footprint`` [G, 4] = (ox, oy, r, free) per ground geom."""
+        xy = np.ascontiguousarray(xyyaw, dtype=np.float32).reshape(-1, 3)
+        fp = np.ascontiguousarray(footprint, dtype=np.float32).reshape(-1, 4)
+        self._check(self.L.cosim_spawn_set(self.h, xy.ctypes.data, int(xy.shape[0]), fp.ctypes.data, int(fp.shape[0]),
+                                           ctypes.c_float(clearance), int(bool(per_episode)), stream))
+
+    def spawn_get(self) -> np.ndarray:
+        """``cosim_spawn_get``: the placed poses, host float32 [M, 7] = x, y, z, qw, qx, qy, qz."""
+        out = np.zeros((self.query("spawn_rows"), 7), dtype=np.float32)
+        self._check(self.L.cosim_spawn_get(self.h, out.ctypes.data, int(out.shape[0])))
+        return out
 
     def debug_forward(self, env: int) -> np.ndarray:
         out = np.zeros(8192, dtype=np.float32)

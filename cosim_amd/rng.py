@@ -10,7 +10,9 @@ purpose | index << 8, gid_lo, gid_hi) -- so fleets drawn under two seeds are ind
 
 Device twin: ``philox()`` / ``u01()`` in ``csrc/cosim_kernels.hip``.
 Purposes: 0 action-delay draw, 1 sensor noise (index = frame element), 2 init-qpos noise
-(index = i-th noisy joint), 3 mass noise (host only, index = body id), 4 gain noise (host only).
+(index = i-th noisy joint), 3 mass noise (host only, index = body id), 4 gain noise (host only),
+5 spawn-table row of an episode (index 0; per-episode mode of ``cosim_spawn_set``), 6 spawn pose draws
+(host only: ``spawn.uniform_poses``, env id = table row, index 0 / 1 / 2 = x / y / yaw).
 """
 from __future__ import annotations
 
@@ -21,6 +23,7 @@ W0, W1 = np.uint32(0x9E3779B9), np.uint32(0xBB67AE85)
 MASK32 = np.uint64(0xFFFFFFFF)
 
 PURPOSE_DELAY, PURPOSE_SENSOR, PURPOSE_INIT, PURPOSE_MASS, PURPOSE_GAIN = 0, 1, 2, 3, 4
+PURPOSE_SPAWN, PURPOSE_SPAWN_POSE = 5, 6
 
 
 def philox4x32(k0, k1, c0, c1, c2, c3):

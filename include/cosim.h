@@ -110,7 +110,8 @@ int cosim_query(const cosim_engine_t* e, const char* name);
  * of 10 cm or more select the 48-slot variants of flamingo_light_v1 / w4_p_v2), "fixup_contact_slots" (capacity of the kernel that
  * redoes a control step -- on the split pipeline with "hfield_fixup", a substep -- whose contacts did not fit; 0: this model / terrain
  * has none, or it is switched off: on a heightfield it is non-zero only while "hfield_fixup" is 1), "ranges", "lds_bytes", "frame_skip" (physics
- * substeps per control step: the precision level's) and "max_newton" / "max_ls" (the caps the solver runs with). */
+ * substeps per control step: the precision level's), "max_newton" / "max_ls" (the caps the solver runs with) and "spawn_rows" /
+ * "spawn_mode" (cosim_spawn_set: rows of the spawn table, 0 = none; 0 = row by env id, 1 = drawn per episode). */
 int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int count);
 
 /* Replaces env.reset() (reference envs/wrappers.py:245-256,303-307,385-389; flamingo_light_v1.py:209-232).
@@ -173,10 +174,34 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
  * "qpos"[N,nq] / "qvel"[N,nv] / "qacc_warmstart"[N,nv] / "sim_step"[N] (as float) to a device buffer.  "meta"[N,16] (int32 bits):
  * per-env counters, among them [8] contacts left out, [10] most contacts in one substep, [12] fix-up passes -- control steps redone
  * by a large-capacity kernel; on the split pipeline with "hfield_fixup", substeps (the unit that pipeline redoes) -- and [13] prism
- * walks cut at their bound (solver_stats() in cosim_amd/batched_env.py sums them). */
+ * walks cut at their bound (solver_stats() in cosim_amd/batched_env.py sums them), [14] the spawn-table row the env's last reset
+ * took its base pose from (cosim_spawn_set; written only while a table is set), [15] unused. */
 int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream);
 /* Test / checkpoint hook: overwrite "qpos"/"qvel"/"qacc_warmstart" from a device buffer. */
 int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* stream);
+
+/* Spawn table (no reference counterpart: the reference resets its one robot to the model's init_qpos).  M = `rows` base poses
+ * spread over the terrain; every reset -- cosim_reset, the auto-reset inside every step / rollout / fix-up kernel, the reset after a
+ * non-finite state -- takes qpos[0:7] from a row instead of init_qpos[0:7]; joint angles, init noise and velocities are unchanged.
+ * xyyaw_host float[rows][3]: x, y, yaw per row.  A HIP kernel places each row on the heightfield: footprint_host float[n_foot][4] =
+ * (ox, oy, r, free) per ground geom -- horizontal offset of its bounding-sphere centre from the base, radius, and height of the
+ * sphere's lowest point above z = 0, all at init_qpos (cosim_amd/spawn.py footprint()) --, g_xy = (x, y) + R(yaw) (ox, oy), hmax_g =
+ * the highest heightfield sample among the vertices cmin..cmax x rmin..rmax with cmin = floor((lx - r + sx) / dx), cmax =
+ * ceil((lx + r + sx) / dx), lx = g_x - ground_pos.x, dx = 2 sx / (ncol - 1) (rows alike), and
+ *     z = init_qpos[2] + max(0, max_g(sz hmax_g - free_g)) + clearance,    quat = (cos yaw/2, 0, 0, sin yaw/2) (x) init_qpos[3:7]:
+ * no geom ends lower over the terrain than it was over z = 0 at init_qpos.  On plane ground z = init_qpos[2] + clearance.
+ * A yaw does not turn gravity in the body frame, so the state vector a reset returns takes projected gravity from init_qpos[3:7]:
+ * on plane ground it is, bit for bit, the state vector of a reset without a table.
+ * COSIM_EINVAL, with the row in the message, if a row is not finite or puts a footprint sphere off the field (|l| + r > s).
+ * rows = 0 clears the table; the same `rows` again rewrites it in place (the device pointer stays, captured graphs keep working);
+ * a new table takes effect at each env's next reset.  per_episode 0: row = global env id mod rows; 1: row = min(rows - 1,
+ * floor(u01(philox(seed, gid, step_count, purpose 5, index 0)) * rows)) with the step counter (meta word 1) of the launch that resets,
+ * the one its init-noise draw uses.  Both depend on the global env id and the seed only: shards that set the same table give the
+ * results of one fleet.  Joins the range streams and blocks until the table is placed.  With no table (the default) nothing changes. */
+int cosim_spawn_set(cosim_engine_t* e, const float* xyyaw_host, int rows, const float* footprint_host, int n_foot, float clearance,
+                    int per_episode, void* stream);
+/* The placed poses, float[rows][7] = x, y, z, qw, qx, qy, qz, to host memory (at most `capacity` rows); returns the table's row count. */
+int cosim_spawn_get(cosim_engine_t* e, float* poses_host, int capacity);
 
 /* Replaces env.event("push", v) (reference flamingo_light_v1.py:234-245): v_dev float[N,3] world-frame velocity,
  * mask_dev uint8[N] or NULL. */
