@@ -84,7 +84,7 @@ class BatchedEnv:
     def __init__(self, config: dict, num_envs: Optional[int] = None, device: Optional[int] = None, seed: Optional[int] = None,
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
-                 spawn=None):
+                 spawn=None, history=None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -101,7 +101,10 @@ class BatchedEnv:
 
         ``spawn``: a spawn table -- an ``[M, 3]`` array of ``(x, y, yaw)`` or a dict ``{"pattern": "grid" | "uniform" | "poses",
         "count", "extent", "yaw", "per_episode", "clearance", "poses"}`` (``cosim_amd/spawn.py``) -- see ``set_spawn``.  Default:
-        ``config["engine"].get("spawn")`` / none: every reset goes to the model's ``init_qpos``."""
+        ``config["engine"].get("spawn")`` / none: every reset goes to the model's ``init_qpos``.
+
+        ``history``: ``(slots, every)`` -- the engine keeps a ring of ``slots`` full-state captures, one after every ``every``-th
+        ``step()`` (``cosim_history_set``), see ``history()``.  Default: ``config["engine"].get("history")`` / none."""
         import torch  # plumbing only
 
         eng_cfg = config.get("engine", {})
@@ -208,6 +211,12 @@ class BatchedEnv:
         self._qpos = t.zeros((N, self.nq), **f32)
         self._qvel = t.zeros((N, self.nv), **f32)
         self.reset_flag = False
+        self.control_steps = 0          # control steps since the last whole-fleet reset (a restore sets it to the snapshot's)
+        self.history_cfg = None
+        history = history if history is not None else eng_cfg.get("history")
+        if history is not None and int(history[0]) > 0:
+            self.history_cfg = (int(history[0]), int(history[1]))
+            self.engine.history_set(*self.history_cfg)
 
     # ------------------------------------------------------------------ domain randomisation (XMLManager step 3)
     def _randomise(self, gain_noise: float):
@@ -260,6 +269,8 @@ class BatchedEnv:
             mptr = mask.data_ptr()
         self.engine.reset(mptr, self._cmd_ptr(), self.state.data_ptr(), self._stream())
         self.reset_flag = True
+        if mask is None:
+            self.control_steps = 0
         return self.state, {}
 
     def step(self, action):
@@ -271,6 +282,7 @@ class BatchedEnv:
         a = a.contiguous()
         self.engine.step(a.data_ptr(), self._cmd_ptr(), self.state.data_ptr(), self.terminated.data_ptr(),
                          self.truncated.data_ptr(), self.info_buf.data_ptr(), self._stream())
+        self.control_steps += 1
         if self.command_dim < 0 or self.command_dim > 6:
             raise ValueError(f"Invalid 'command_dim': expected 0> or <7; but got {self.command_dim}.")
         return self.state, self.terminated, self.truncated, self._info(a)
@@ -292,6 +304,7 @@ class BatchedEnv:
         inf = t.empty((K, self.num_envs, self.info_dim), dtype=t.float32, device=self.device) if info else None
         self.engine.rollout(K, a.data_ptr(), self._cmd_ptr(), states.data_ptr(), term.data_ptr(), trunc.data_ptr(),
                             inf.data_ptr() if info else None, self._stream())
+        self.control_steps += K
         self.state.copy_(states[-1]); self.terminated.copy_(term[-1]); self.truncated.copy_(trunc[-1])
         if info:
             self.info_buf.copy_(inf[-1])
@@ -306,6 +319,8 @@ class BatchedEnv:
             raise ValueError(f"Action dimension mismatch. Expected contiguous {(self.num_envs, self.action_dim)}, found {tuple(action.shape)}")
         self.engine.step_range(first, count, action.data_ptr(), self._cmd_ptr(), self.state.data_ptr(), self.terminated.data_ptr(),
                                self.truncated.data_ptr(), self.info_buf.data_ptr(), self._stream())
+        if first + count == self.num_envs:
+            self.control_steps += 1
 
     def join(self):
         """Deferred join: make the current stream wait for every range stream's work so far (``cosim_join``)."""
@@ -367,6 +382,100 @@ class BatchedEnv:
                 self.engine.set(name, x.data_ptr(), self._stream())
                 t.cuda.synchronize(self.device)
 
+    # ------------------------------------------------------------------ snapshots (cosim_snapshot / cosim_restore / history ring)
+    def snapshot_meta(self) -> dict:
+        """What a snapshot of this env records about where it came from, and what ``restore`` compares (``snapshot.META_FIELDS``)."""
+        return {"env_id": self.id, "terrain": self.config["env"]["terrain"], "precision": self.config["random"]["precision"],
+                "snapshot_floats": self.engine.query("snapshot_floats"), "state_stride": self.engine.query("state_stride"),
+                "param_stride": self.engine.query("param_stride"), "state_dim": self.state_dim, "n_envs": self.num_envs,
+                "env_id0": self.env_id0, "seed": self.seed}
+
+    def snapshot(self, policy=None):
+        """The whole fleet's state, bit for bit: engine rows (state record + parameter record of every env, ``cosim_snapshot``), the
+        last observation, the command buffer and the control-step count; with ``policy`` also ``policy.state()``.  Joins the range
+        streams; asynchronous on the current stream otherwise.  ``restore`` of it into this env -- or, through ``Snapshot.save`` /
+        ``load``, into an env built the same way in another process -- continues with the same bits."""
+        from .snapshot import Snapshot
+        t = self.torch
+        meta = self.snapshot_meta()
+        rows = t.empty((self.num_envs, meta["snapshot_floats"]), dtype=t.float32, device=self.device)
+        self.engine.snapshot(rows.data_ptr(), self._stream())      # (joins: state / user_command below are the newest step's)
+        return Snapshot(rows, self.state.clone(), self.user_command.clone(), self.control_steps, meta,
+                        policy.state() if policy is not None else None)
+
+    def restore(self, snap, src=None, mask=None, params: bool = False):
+        """Env ``d`` takes row ``src[d]`` of ``snap`` (``None``: row ``d``; the snapshot must then have ``num_envs`` rows); envs with
+        ``mask[d] == 0`` are left untouched.  ``params=False`` keeps every env's own parameter record (the robot in slot ``d`` keeps
+        its masses and gains); ``True`` restores it with the state.  One gather launch (``cosim_restore``).  Raises ``ValueError``
+        naming the first metadata field that disagrees with this env, or the first ``src`` entry outside the snapshot (those envs are
+        left untouched).  Returns the restored observation rows ``[N, state_dim]`` -- ``self.state``, which is what the interrupted
+        loop would feed its policy next -- or ``None`` for a snapshot without observation rows (``history()``): the engine keeps no
+        observation per ring slot and does not rebuild it (the applied command of the last step is not in the record), so a
+        policy that needs the observation gets it from the first ``step()`` after the restore.
+        A restored env in slot ``d`` draws from slot ``d``'s random streams (they are keyed by the global env id).  The diagnostic
+        counters (``solver_stats()``) are part of the rows and go back with them."""
+        from .snapshot import check_compatible
+        t = self.torch
+        check_compatible(snap.meta, self.snapshot_meta(), need_n_envs=src is None)
+        rows = t.as_tensor(snap.rows, dtype=t.float32, device=self.device).contiguous()
+        if rows.ndim != 2 or rows.shape[1] != snap.meta["snapshot_floats"]:
+            raise ValueError(f"snapshot rows have shape {tuple(rows.shape)}, expected [M, {snap.meta['snapshot_floats']}]")
+        if src is None and rows.shape[0] != self.num_envs:
+            raise ValueError(f"snapshot holds {rows.shape[0]} rows, this env has {self.num_envs} (give src to pick rows)")
+        sptr = mptr = None
+        if src is not None:
+            src = t.as_tensor(src, device=self.device).to(t.int32).contiguous()
+            if tuple(src.shape) != (self.num_envs,):
+                raise ValueError(f"src must have shape ({self.num_envs},), found {tuple(src.shape)}")
+            sptr = src.data_ptr()
+        if mask is not None:
+            mask = t.as_tensor(mask, device=self.device).to(t.uint8).contiguous()
+            if tuple(mask.shape) != (self.num_envs,):
+                raise ValueError(f"mask must have shape ({self.num_envs},), found {tuple(mask.shape)}")
+            mptr = mask.data_ptr()
+        # (the engine validates src before anything below indexes with it)
+        self.engine.restore(rows.data_ptr(), rows.shape[0], sptr, mptr, params, self._stream())
+        self.reset_flag = True
+        if mask is None:
+            self.control_steps = snap.steps
+
+        def put(dst, rows_):
+            x = t.as_tensor(rows_, dtype=t.float32, device=self.device)
+            if src is not None:
+                x = x[src.long()]
+            if mask is not None:
+                x = t.where(mask.bool()[:, None], x, dst)
+            dst.copy_(x)
+        if snap.command is not None:
+            self._last_cmd_host = None
+            put(self.user_command, snap.command)
+        if snap.obs is None:
+            return None
+        put(self.state, snap.obs)
+        return self.state
+
+    def fork(self, snap, row: int, params: bool = True):
+        """Every env starts from row ``row`` of ``snap`` (``restore`` with a constant ``src``), by default with that env's parameter
+        record.  The forks share no random streams with their source or each other: every stream is keyed by the global id of the
+        slot an env runs in, so they differ exactly where the randomisation says they should (noise, action delay, spawn draws)."""
+        row = int(row)
+        if not 0 <= row < snap.num_rows:
+            raise ValueError(f"fork: row {row} outside the snapshot's {snap.num_rows} rows")
+        return self.restore(snap, src=self.torch.full((self.num_envs,), row, dtype=self.torch.int32, device=self.device), params=params)
+
+    def history(self, age: int = 0):
+        """Capture ``age`` of the history ring (0 = newest; ``history=(slots, every)``) as a ``Snapshot`` whose ``steps`` is the
+        control step it was taken after.  It carries the engine rows only (``obs`` / ``command`` are ``None``): see ``restore``.
+        Raises ``ValueError`` if ``age >= slots`` or that capture does not exist yet.  Joins the range streams."""
+        from .snapshot import Snapshot
+        t = self.torch
+        meta = self.snapshot_meta()
+        rows = t.empty((self.num_envs, meta["snapshot_floats"]), dtype=t.float32, device=self.device)
+        ago = self.engine.history_get(age, rows.data_ptr(), self._stream())
+        snap = Snapshot(rows, None, None, self.control_steps - ago, meta)
+        snap.steps_ago = ago
+        return snap
+
     # ------------------------------------------------------------------ spawn table (cosim_spawn_set)
     def set_spawn(self, spawn, clearance: Optional[float] = None, per_episode: Optional[bool] = None):
         """Spread the fleet's resets over the terrain.  ``spawn``: ``[M, 3]`` rows ``(x, y, yaw)``, or the dict that
@@ -400,7 +509,9 @@ class BatchedEnv:
 
     def solver_stats(self):
         """Cumulative solver counters since creation (fleet sums): control steps, constraint rows (summed over
-        substeps), Newton iterations, line-search evaluations, Hessian factorisations, non-finite resets."""
+        substeps), Newton iterations, line-search evaluations, Hessian factorisations, non-finite resets.  The counters live in the
+        state record, so ``restore`` / ``fork`` put them back with the rest: afterwards they describe the restored history (a fork
+        copies its source's)."""
         t = self.torch
         buf = t.zeros((self.num_envs, 16), dtype=t.float32, device=self.device)
         self.engine.get("meta", buf.data_ptr(), self._stream())

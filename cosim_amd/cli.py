@@ -2,7 +2,8 @@
 
     python -m cosim_amd.cli --env flamingo_light_v1 --num-envs 4096 --steps 1000 --command 0.5 0 0 0 \\
         --policy sinusoid | random-mlp | path/to/actor.onnx  [--terrain rocky_hard] [--push-at 200 --push 0.5 0 0] \\
-        [--report report.json] [--trace-env 0]
+        [--report report.json] [--trace-env 0] [--checkpoint snap.npz --checkpoint-at 500] [--resume snap.npz [--fork-row 7]] \
+        [--history 8 10]
     python -m cosim_amd.cli --config session.yaml
 
 One process per GPU: under ``torchrun`` every rank simulates its shard of ``--num-envs`` and rank 0 writes the report.
@@ -71,6 +72,12 @@ def main(argv=None) -> int:
     ap.add_argument("--spawn-extent", type=float, default=None, help="half-size (m) of the square the poses fill (default: the field minus the footprint)")
     ap.add_argument("--spawn-per-episode", action="store_true", help="draw a row anew at every reset instead of row = env id mod count")
     ap.add_argument("--spawn-clearance", type=float, default=None, help="extra height (m) above the no-penetration placement")
+    ap.add_argument("--checkpoint", default=None, help="write a full-state snapshot (.npz) here after --checkpoint-at control steps, then go on")
+    ap.add_argument("--checkpoint-at", type=int, default=None, help="control step (of the session's clock) after which --checkpoint is written")
+    ap.add_argument("--resume", default=None, help="start from this snapshot instead of a reset; --steps more control steps are run")
+    ap.add_argument("--fork-row", type=int, default=None, help="with --resume: every env starts from this row of the file, parameters included")
+    ap.add_argument("--history", type=int, nargs=2, default=None, metavar=("SLOTS", "EVERY"),
+                    help="keep a ring of SLOTS full-state captures on the device, one after every EVERY-th control step")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -133,6 +140,16 @@ def main(argv=None) -> int:
     for row in pushes:
         if len(row) != 5 or row[1] <= row[0]:
             ap.error("pushes: rows are [t0, t1, vx, vy, vz] with t1 > t0")
+    if (args.checkpoint is None) != (args.checkpoint_at is None):
+        ap.error("--checkpoint and --checkpoint-at go together")
+    if args.fork_row is not None and not args.resume:
+        ap.error("--fork-row needs --resume")
+    if (args.checkpoint or args.resume) and (args.graph or args.pipelined):
+        ap.error("--checkpoint / --resume run the eager loop (no --graph / --pipelined)")
+    if args.history is not None and (args.history[0] < 1 or args.history[1] < 1):
+        ap.error("--history SLOTS EVERY: both at least 1")
+    if args.history is not None and args.graph:
+        ap.error("--history cannot be combined with --graph: a replayed graph would repeat the captured step's parity")
 
     import torch
     from .batched_env import BatchedEnv
@@ -143,6 +160,8 @@ def main(argv=None) -> int:
     from .runner import Runner, SinusoidPolicy
 
     rank, world = init_from_env(args.backend)
+    if world > 1 and (args.checkpoint or args.resume):
+        ap.error("--checkpoint / --resume: one process (a snapshot file holds one rank's envs)")
     lo, hi = shard_range(args.num_envs, rank, world)
     dev = int(os.environ.get("LOCAL_RANK", "0"))
     cfg = make_config(args.env, terrain=args.terrain, max_duration=args.max_duration, position_command=args.position_command,
@@ -156,7 +175,7 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     spawn=spawn or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, history=tuple(args.history) if args.history else None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:
@@ -193,6 +212,21 @@ def main(argv=None) -> int:
     # episodes ended are counted on the device (engine meta word 11) and read once after the run: a per-step `.item()` on the done
     # flags would drain the GPU queue at every control step
     on_step = None
+    resume = None
+    used = {}                                                      # what the report records about snapshots
+    if args.history:
+        used["history"] = list(args.history)
+    if args.resume:
+        from .snapshot import Snapshot
+        resume = Snapshot.load(args.resume, device=env.device)
+        used.update({"resume": args.resume, "resume_step": resume.steps})
+        if args.fork_row is not None:
+            used["fork_row"] = args.fork_row
+    if args.checkpoint:
+        def on_step(k, state, terminated, truncated, info):
+            if k + 1 == args.checkpoint_at:                        # after `checkpoint_at` control steps of the session's clock
+                env.snapshot(policy if hasattr(policy, "state") else None).save(args.checkpoint)
+                used.update({"checkpoint": args.checkpoint, "checkpoint_at": args.checkpoint_at})
     episodes0 = None
     torch.cuda.synchronize(env.device)
     episodes0 = env.solver_stats()["episodes_ended"]
@@ -202,15 +236,19 @@ def main(argv=None) -> int:
             ap.error("--pipelined runs one command and no push schedule (use Runner.test_pipelined with update_command for more)")
         n = run.test_pipelined(args.steps)
     else:
-        n = run.test_graphed(args.steps) if args.graph else run.test(max_steps=args.steps, on_step=on_step, before_step=before_step)
+        n = run.test_graphed(args.steps) if args.graph else run.test(max_steps=args.steps, on_step=on_step, before_step=before_step,
+                                                                           resume=resume, fork_row=args.fork_row)
     torch.cuda.synchronize(env.device)
     dt = time.perf_counter() - t0
     rep.episodes_ended = env.solver_stats()["episodes_ended"] - episodes0
-    out = rep.save(args.report) if (args.report and rank == 0) else rep.summary()
+    if args.checkpoint and "checkpoint" not in used:
+        print(f"warning: --checkpoint-at {args.checkpoint_at} was not reached, no snapshot written", file=sys.stderr)
+    out = rep.save(args.report, extra={"snapshot": used} if used else None) if (args.report and rank == 0) else rep.summary()
     if rank == 0:
         print(json.dumps({"env": args.env, "terrain": args.terrain, "envs_total": args.num_envs, "ranks": world, "control_steps": n,
                           "env_steps_per_s_this_rank": env.num_envs * n / dt, "episodes_ended": out["episodes_ended"],
                           "metrics": {k: round(v["mean"], 5) for k, v in out["metrics"].items()},
+                          **({"snapshot": used} if used else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()

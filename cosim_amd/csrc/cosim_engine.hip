@@ -14,6 +14,7 @@
 #include "cosim_kernels.hip"
 #include "cosim_mlp.hip"
 #include "cosim_spawn.hip"
+#include "cosim_snapshot.hip"
 
 using namespace cosim;
 
@@ -119,6 +120,16 @@ struct cosim_engine {
   float* d_spawn = nullptr;       // [spawn_rows][8]
   std::vector<float> h_spawn;     // host copy of the placed table (cosim_spawn_get)
   int spawn_rows = 0, spawn_mode = 0;
+  // snapshots (cosim_snapshot.hip).  A restore with parameters leaves h_params behind the device: the mirror is read back before the
+  // next per-env cosim_set_param edits it (that call rewrites the whole table from the mirror)
+  bool params_mirror_stale = false;
+  int* d_snap_err = nullptr;      // [2] error word of the gather kernel
+  int* h_snap_err = nullptr;      // pinned host copy
+  // history ring (cosim_history_set): every `hist_every`-th cosim_step packs each range's rows into slot (capture number) mod slots
+  float* d_hist = nullptr;        // [hist_slots][n_envs][snapshot_floats]
+  int hist_slots = 0, hist_every = 0;
+  long hist_calls = 0, hist_captures = 0;   // cosim_step calls / captures since cosim_history_set
+  std::vector<long> hist_call_of;           // per slot: the call count its capture was taken after
 };
 
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
@@ -437,6 +448,8 @@ static void default_params(cosim_engine* e) {
   e->params_dirty = true;
 }
 
+static int refresh_param_mirror(cosim_engine* e);
+
 static int upload_params(cosim_engine* e) {
   if (!e->params_dirty) return COSIM_OK;
   HIP_TRY(hipMemcpy(e->d_params, e->h_params.data(), e->h_params.size() * sizeof(float), hipMemcpyHostToDevice));
@@ -484,6 +497,48 @@ static int join_ranges(cosim_engine* e, hipStream_t stream) {
   }
   e->join_pending = false;
   return COSIM_OK;
+}
+
+// ---- snapshots and the history ring (cosim_snapshot.hip)
+static const char* const HIST_CAPTURE_MSG =
+    "cosim_step: a history is set (cosim_history_set) and the stream is being captured into a graph: a replayed graph would repeat "
+    "whatever step parity was captured; switch the history off or step eagerly";
+
+static SnapArgs snap_args(cosim_engine* e) {
+  SnapArgs a;
+  memset(&a, 0, sizeof a);
+  a.state = e->d_state; a.params = e->d_params; a.s_stride = e->lay.s_stride; a.p_stride = e->lay.p_stride;
+  a.n_envs = e->n_envs; a.n_rows = e->n_envs; a.env_first = 0; a.env_count = e->n_envs;
+  return a;
+}
+
+// h_params <- d_params after a restore with parameters (cold: blocks until the device is idle)
+static int refresh_param_mirror(cosim_engine* e) {
+  if (!e->params_mirror_stale) return COSIM_OK;
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(e->h_params.data(), e->d_params, e->h_params.size() * sizeof(float), hipMemcpyDeviceToHost));
+  e->params_mirror_stale = false;
+  return COSIM_OK;
+}
+
+// this cosim_step call is the `every`-th since the last capture
+static bool history_due(const cosim_engine* e) { return e->hist_slots > 0 && (e->hist_calls + 1) % e->hist_every == 0; }
+
+static int history_pack(cosim_engine* e, int first, int count, hipStream_t s) {
+  SnapArgs a = snap_args(e);
+  a.rows = e->d_hist + (size_t)(e->hist_captures % e->hist_slots) * e->n_envs * (size_t)(a.s_stride + a.p_stride);
+  a.env_first = first; a.env_count = count;
+  hipLaunchKernelGGL(snapshot_pack_kernel, dim3(count), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+static void history_count(cosim_engine* e) {   // after a cosim_step call was issued in full
+  if (e->hist_slots <= 0) return;
+  const bool due = history_due(e);
+  e->hist_calls++;
+  if (due) { e->hist_call_of[e->hist_captures % e->hist_slots] = e->hist_calls; e->hist_captures++; }
 }
 
 extern "C" {
@@ -772,6 +827,8 @@ int cosim_destroy(cosim_engine_t* e) {
   hipFree(e->d_hull_vert); hipFree(e->d_hull_adr); hipFree(e->d_hull_nbr); hipFree(e->d_hfield);
   hipFree(e->d_hull_cell); hipFree(e->d_hull_cand); hipFree(e->d_hfield_mip);
   hipFree(e->d_spawn);
+  hipFree(e->d_hist); hipFree(e->d_snap_err);
+  if (e->h_snap_err) hipHostFree(e->h_snap_err);
   hipFree(e->d_pairs); hipFree(e->d_gext); hipFree(e->d_ovf); hipFree(e->d_xcon); hipFree(e->d_xcnt); hipFree(e->d_xstate);
   for (hipEvent_t x : e->ev) hipEventDestroy(x);
   for (hipStream_t x : e->rstream) hipStreamDestroy(x);
@@ -819,6 +876,9 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "frame_skip") return e->model.frame_skip;
   if (n == "spawn_rows") return e->spawn_rows;   // rows of the spawn table (0: none, resets go to init_qpos)
   if (n == "spawn_mode") return e->spawn_mode;   // 0: row = global env id mod rows; 1: drawn per episode
+  if (n == "snapshot_floats") return e->lay.s_stride + e->lay.p_stride;   // float32 words of a snapshot row: state record + parameter record
+  if (n == "history_slots") return e->hist_slots;
+  if (n == "history_every") return e->hist_every;
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
 }
 
@@ -914,6 +974,7 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
   }
   else return fail(COSIM_EINVAL, "cosim_set_param: unknown parameter " + n);
   if (count != e->n_envs * width) return fail(COSIM_EINVAL, "cosim_set_param: " + n + " expects n_envs*" + std::to_string(width) + " values");
+  { int rc = refresh_param_mirror(e); if (rc) return rc; }
   for (int i = 0; i < e->n_envs; i++)
     memcpy(e->h_params.data() + (size_t)i * L.p_stride + off, host + (size_t)i * width, width * sizeof(float));
   e->params_dirty = true;
@@ -971,10 +1032,13 @@ int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* command
     HIP_TRY(hipSetDevice(e->device));
     hipStreamCaptureStatus cap1 = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap1));
+    if (e->hist_slots > 0 && cap1 != hipStreamCaptureStatusNone) return fail(COSIM_EINVAL, HIST_CAPTURE_MSG);
     const bool paced = e->inflight > 0 && cap1 == hipStreamCaptureStatusNone && (int)e->ring.size() >= e->inflight;
     if (paced && e->ring_pos >= e->inflight) HIP_TRY(hipEventSynchronize(e->ring[e->ring_pos % e->inflight]));
     int rc = cosim_step_range(e, 0, e->n_envs, actions_dev, commands_dev, state_out_dev, terminated_dev, truncated_dev, info_out_dev, stream);
     if (rc) return rc;
+    if (history_due(e)) { rc = history_pack(e, 0, e->n_envs, (hipStream_t)stream); if (rc) return rc; }
+    history_count(e);
     if (paced) { HIP_TRY(hipEventRecord(e->ring[e->ring_pos % e->inflight], (hipStream_t)stream)); e->ring_pos++; }
     return COSIM_OK;
   }
@@ -988,6 +1052,7 @@ int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* command
   // an idle caller stream).  Not while capturing: a query is illegal there, and the fork edge is what ties the range streams in.
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   HIP_TRY(hipStreamIsCapturing(cs, &cap));
+  if (e->hist_slots > 0 && cap != hipStreamCaptureStatusNone) return fail(COSIM_EINVAL, HIST_CAPTURE_MSG);
   bool wait_in = true;
   if (cap == hipStreamCaptureStatusNone) {
     const hipError_t q = hipStreamQuery(cs);
@@ -1005,8 +1070,11 @@ int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* command
     int rc = cosim_step_range(e, e->rfirst[i], e->rcount[i], actions_dev, commands_dev, state_out_dev, terminated_dev, truncated_dev, info_out_dev,
                               e->rstream[i]);
     if (rc) return rc;
+    // history capture: the range's rows on the range's own stream, behind its last launch of the step; no join, no extra event
+    if (history_due(e)) { rc = history_pack(e, e->rfirst[i], e->rcount[i], e->rstream[i]); if (rc) return rc; }
     if (paced) HIP_TRY(hipEventRecord(e->ring[(size_t)i * e->inflight + e->ring_pos % e->inflight], e->rstream[i]));
   }
+  history_count(e);
   if (e->inflight > 0 && cap == hipStreamCaptureStatusNone) e->ring_pos++;
   e->join_pending = true;
   if (!e->deferred_join) return join_ranges(e, cs);
@@ -1270,6 +1338,89 @@ int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* st
   if (rc) return rc;
   HIP_TRY(hipMemcpy2DAsync(e->d_state + off, e->lay.s_stride * sizeof(float), in_dev, width * sizeof(float), width * sizeof(float),
                            e->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return COSIM_OK;
+}
+
+int cosim_snapshot(cosim_engine_t* e, float* out_dev, void* stream) {
+  if (!e || !out_dev) return fail(COSIM_EINVAL, "cosim_snapshot: null argument");
+  if ((uintptr_t)out_dev & 15) return fail(COSIM_EINVAL, "cosim_snapshot: out_dev must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = upload_params(e);   // the row holds the parameters the next step would run with
+  if (rc) return rc;
+  rc = join_ranges(e, (hipStream_t)stream);
+  if (rc) return rc;
+  SnapArgs a = snap_args(e);
+  a.rows = out_dev;
+  hipLaunchKernelGGL(snapshot_pack_kernel, dim3(e->n_envs), dim3(64), 0, (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const int32_t* src_index_dev, const uint8_t* mask_dev,
+                  int with_params, void* stream) {
+  if (!e || !snap_dev || snap_rows < 1) return fail(COSIM_EINVAL, "cosim_restore: null argument or snap_rows < 1");
+  if ((uintptr_t)snap_dev & 15) return fail(COSIM_EINVAL, "cosim_restore: snap_dev must be 16-byte aligned");
+  if (!src_index_dev && snap_rows != e->n_envs)
+    return fail(COSIM_EINVAL, "cosim_restore: without a source index snap_rows must equal n_envs (" + std::to_string(e->n_envs) + "), got " +
+                                  std::to_string(snap_rows));
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t cs = (hipStream_t)stream;
+  int rc = upload_params(e);   // a pending upload first: the envs this restore leaves alone get their new parameters, the others the row's
+  if (rc) return rc;
+  rc = join_ranges(e, cs);
+  if (rc) return rc;
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  HIP_TRY(hipStreamIsCapturing(cs, &cap));
+  if (src_index_dev) {
+    if (!e->d_snap_err) {
+      if (cap != hipStreamCaptureStatusNone) return fail(COSIM_EINVAL, "cosim_restore: the first restore with a source index allocates; call it once outside the capture");
+      HIP_TRY(hipMalloc(&e->d_snap_err, 2 * sizeof(int)));
+      HIP_TRY(hipHostMalloc(&e->h_snap_err, 2 * sizeof(int), hipHostMallocDefault));
+    }
+    HIP_TRY(hipMemsetAsync(e->d_snap_err, 0, 2 * sizeof(int), cs));
+  }
+  SnapArgs a = snap_args(e);
+  a.rows = const_cast<float*>(snap_dev); a.n_rows = snap_rows; a.src = src_index_dev; a.mask = mask_dev;
+  a.err = src_index_dev ? e->d_snap_err : nullptr; a.with_params = with_params != 0;
+  hipLaunchKernelGGL(snapshot_gather_kernel, dim3(e->n_envs), dim3(64), 0, cs, a);
+  HIP_TRY(hipGetLastError());
+  if (with_params) e->params_mirror_stale = true;
+  if (src_index_dev && cap == hipStreamCaptureStatusNone) {   // the kernel skipped what it refused; report it
+    HIP_TRY(hipMemcpyAsync(e->h_snap_err, e->d_snap_err, 2 * sizeof(int), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(hipStreamSynchronize(cs));
+    if (e->h_snap_err[0] > 0)
+      return fail(COSIM_EINVAL, "cosim_restore: source index of env " + std::to_string(e->n_envs - e->h_snap_err[1]) + " is outside [0, " +
+                                    std::to_string(snap_rows) + "); " + std::to_string(e->h_snap_err[0]) + " env(s) were left untouched");
+  }
+  return COSIM_OK;
+}
+
+int cosim_history_set(cosim_engine_t* e, int slots, int every) {
+  if (!e || slots < 0 || slots > 65536 || (slots > 0 && every < 1)) return fail(COSIM_EINVAL, "cosim_history_set: slots must be 0..65536 and every >= 1");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());   // launches in flight may still write the old ring
+  HIP_TRY(hipFree(e->d_hist));
+  e->d_hist = nullptr; e->hist_slots = 0; e->hist_every = 0; e->hist_calls = 0; e->hist_captures = 0; e->hist_call_of.clear();
+  if (slots == 0) return COSIM_OK;
+  const size_t bytes = (size_t)slots * e->n_envs * (size_t)(e->lay.s_stride + e->lay.p_stride) * sizeof(float);
+  HIP_TRY(hipMalloc(&e->d_hist, bytes));
+  e->hist_slots = slots; e->hist_every = every; e->hist_call_of.assign(slots, 0);
+  return COSIM_OK;
+}
+
+int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago, void* stream) {
+  if (!e || !out_dev) return fail(COSIM_EINVAL, "cosim_history_get: null argument");
+  if (e->hist_slots <= 0) return fail(COSIM_EINVAL, "cosim_history_get: no history is set (cosim_history_set)");
+  if (age < 0 || age >= e->hist_slots) return fail(COSIM_EINVAL, "cosim_history_get: age " + std::to_string(age) + " outside the ring of " + std::to_string(e->hist_slots) + " slots");
+  if ((long)age >= e->hist_captures)
+    return fail(COSIM_EINVAL, "cosim_history_get: capture of age " + std::to_string(age) + " does not exist yet (" + std::to_string(e->hist_captures) + " taken)");
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = join_ranges(e, (hipStream_t)stream);
+  if (rc) return rc;
+  const int slot = (int)((e->hist_captures - 1 - age) % e->hist_slots);
+  const size_t row_floats = (size_t)e->n_envs * (size_t)(e->lay.s_stride + e->lay.p_stride);
+  HIP_TRY(hipMemcpyAsync(out_dev, e->d_hist + slot * row_floats, row_floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (steps_ago) *steps_ago = (int)(e->hist_calls - e->hist_call_of[slot]);
   return COSIM_OK;
 }
 

@@ -102,6 +102,10 @@ def load_library():
     L.cosim_event_push.argtypes = [vp, vp, vp, vp]
     L.cosim_spawn_set.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, ci, vp]
     L.cosim_spawn_get.argtypes = [vp, vp, ci]
+    L.cosim_snapshot.argtypes = [vp, vp, vp]
+    L.cosim_restore.argtypes = [vp, vp, ci, vp, vp, ci, vp]
+    L.cosim_history_set.argtypes = [vp, ci, ci]
+    L.cosim_history_get.argtypes = [vp, ci, vp, ctypes.POINTER(ci), vp]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
     L.cosim_set_timing.argtypes = [vp, ci]
@@ -110,7 +114,8 @@ def load_library():
     for fn in ("cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "cosim_reset", "cosim_step", "cosim_step_range", "cosim_get",
                "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_rollout",
                "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
-               "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get"):
+               "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
+               "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -124,7 +129,7 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_hull_support_check", "cosim_debug_support",
            "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
            "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
-           "cosim_spawn_set", "cosim_spawn_get"]
+           "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -282,6 +287,23 @@ class Engine:
         out = np.zeros((self.query("spawn_rows"), 7), dtype=np.float32)
         self._check(self.L.cosim_spawn_get(self.h, out.ctypes.data, int(out.shape[0])))
         return out
+
+    def snapshot(self, out_ptr, stream=None):
+        """``cosim_snapshot``: every env's row into ``out_ptr`` ``[N, snapshot_floats]``."""
+        self._check(self.L.cosim_snapshot(self.h, out_ptr, stream))
+
+    def restore(self, snap_ptr, snap_rows: int, src_ptr=None, mask_ptr=None, with_params: bool = False, stream=None):
+        """``cosim_restore``: env ``d`` takes row ``src[d]`` (``None``: row ``d``) of a ``[snap_rows, snapshot_floats]`` buffer."""
+        self._check(self.L.cosim_restore(self.h, snap_ptr, int(snap_rows), src_ptr, mask_ptr, int(bool(with_params)), stream))
+
+    def history_set(self, slots: int, every: int):
+        self._check(self.L.cosim_history_set(self.h, int(slots), int(every)))
+
+    def history_get(self, age: int, out_ptr, stream=None) -> int:
+        """``cosim_history_get``: capture ``age`` (0 = newest) into ``out_ptr``; returns how many ``step`` calls ago it was taken."""
+        ago = ctypes.c_int()
+        self._check(self.L.cosim_history_get(self.h, int(age), out_ptr, ctypes.byref(ago), stream))
+        return ago.value
 
     def debug_forward(self, env: int) -> np.ndarray:
         out = np.zeros(8192, dtype=np.float32)

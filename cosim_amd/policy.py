@@ -426,6 +426,24 @@ class LSTMPolicy:
             self.h_in.masked_fill_(done, 0.0)
             self.c_in.masked_fill_(done, 0.0)
 
+    def state(self) -> dict:
+        """The recurrent state ``h`` / ``c`` ``[N, H]`` (copies) for a ``Snapshot``."""
+        return {"h": self.h_in[0].clone(), "c": self.c_in[0].clone()}
+
+    def load_state(self, state: dict, src=None, mask=None):
+        """Counterpart of ``BatchedEnv.restore``: env ``d`` takes row ``src[d]`` of ``state["h"]`` / ``["c"]`` (``None``: row ``d``);
+        envs with ``mask[d] == 0`` keep theirs.  In place, so a captured graph keeps seeing the same tensors."""
+        t = self.torch
+        for name, dst in (("h", self.h_in), ("c", self.c_in)):
+            x = t.as_tensor(state[name], dtype=t.float32, device=self.device)
+            if src is not None:
+                x = x[t.as_tensor(src, device=self.device).long()]
+            if tuple(x.shape) != tuple(dst.shape[1:]):
+                raise ValueError(f"LSTMPolicy.load_state: {name} has shape {tuple(x.shape)}, expected {tuple(dst.shape[1:])}")
+            if mask is not None:
+                x = t.where((t.as_tensor(mask, device=self.device) != 0)[:, None], x, dst[0])
+            dst[0].copy_(x)
+
     def get_action(self, state):
         t = self.torch
         s = t.as_tensor(state, dtype=t.float32, device=self.device)

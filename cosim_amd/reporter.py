@@ -162,8 +162,10 @@ class FleetReporter:
             out["percentiles"] = self.percentiles()
         return out
 
-    def save(self, path: str):
+    def save(self, path: str, extra: Optional[dict] = None):
         out = self.summary()
+        if extra:
+            out.update(extra)
         if self.trace:
             out["trace_env"] = self.trace_env
             out["trace"] = {k: np.asarray([r[k] for r in self.trace]).tolist() for k in self.trace[0]}

@@ -31,6 +31,15 @@ class SinusoidPolicy:
         self.t += 1
         return a.clamp_(-1.0, 1.0)
 
+    def state(self) -> dict:
+        """The policy's own state for a ``Snapshot``: its clock (the phases are a function of the seed and the env ids)."""
+        return {"t": np.array(self.t, dtype=np.int64)}
+
+    def load_state(self, state: dict, src=None, mask=None):
+        """Counterpart of ``LSTMPolicy.load_state``; the clock is shared by the fleet, so ``src`` / ``mask`` select nothing."""
+        t = state["t"]
+        self.t = int(np.asarray(t.detach().cpu() if hasattr(t, "detach") else t).reshape(-1)[0])
+
 
 class Runner:
     """``Tester`` without the GUI: ``load_config`` / ``update_command`` / ``activate_push_event`` / ``test`` / ``stop``."""
@@ -63,15 +72,34 @@ class Runner:
                 out[k] = v
         return out
 
-    def test(self, max_steps: Optional[int] = None, on_step: Optional[Callable] = None, before_step: Optional[Callable] = None) -> int:
+    def test(self, max_steps: Optional[int] = None, on_step: Optional[Callable] = None, before_step: Optional[Callable] = None,
+             resume=None, fork_row: Optional[int] = None) -> int:
         """Run until every env is done (no auto-reset) or ``max_steps`` control steps (auto-reset); returns steps run.
         ``before_step(k)`` runs at the top of iteration k, where the reference's UI thread has written the key-driven command and
-        push flags the loop is about to read (core/tester.py:39,80: ``user_command`` / ``_push_event``)."""
+        push flags the loop is about to read (core/tester.py:39,80: ``user_command`` / ``_push_event``).
+
+        ``resume``: a ``Snapshot`` with observation rows (``BatchedEnv.snapshot``).  The reset is skipped: the fleet is restored
+        from it, parameters included, the policy's state too if the snapshot carries one, and the step index -- what ``before_step``
+        and ``on_step`` are given, so a session's command and push schedules -- starts at the snapshot's step count.  ``max_steps``
+        still counts the steps of this call.  ``fork_row``: every env starts from that row of the snapshot instead of its own."""
         env = self.env
-        state, _ = env.reset()
-        steps = 0
+        if resume is None:
+            state, _ = env.reset()
+            steps = 0
+        else:
+            src = None if fork_row is None else env.torch.full((env.num_envs,), int(fork_row), dtype=env.torch.int32, device=env.device)
+            state = env.fork(resume, fork_row, params=True) if fork_row is not None else env.restore(resume, params=True)
+            if state is None:
+                raise ValueError("Runner.test(resume=...): the snapshot has no observation rows (a history() capture); step the env "
+                                 "once after restoring it, or resume from a snapshot()")
+            if resume.policy_state is not None and hasattr(self.policy, "load_state"):
+                self.policy.load_state(resume.policy_state, src=src)
+            for i in range(max(env.command_dim, 0)):               # the command in force at the checkpoint (before_step may change it)
+                self.user_command[i] = float(env.user_command[0, i].item())
+            steps = resume.steps
+        start = steps
         done_all, done_seen = False, None
-        while not done_all and not self._stop and (max_steps is None or steps < max_steps):
+        while not done_all and not self._stop and (max_steps is None or steps - start < max_steps):
             if before_step is not None:
                 before_step(steps)
             env.receive_user_command(self.user_command)            # tester.py:68
@@ -91,7 +119,7 @@ class Runner:
                 # restarts one env early)
                 done_seen = (terminated | truncated) if done_seen is None else (done_seen | terminated | truncated)
                 done_all = bool(done_seen.all().item())
-        return steps
+        return steps - start
 
     def test_pipelined(self, max_steps: int, report_every: int = 1, inflight: int = 2) -> int:
         """The same loop -- policy -> step -> reporter, ``core/tester.py:66-97`` -- with NO fleet-wide barrier per step: the env was

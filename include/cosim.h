@@ -180,6 +180,44 @@ int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream)
 /* Test / checkpoint hook: overwrite "qpos"/"qvel"/"qacc_warmstart" from a device buffer. */
 int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* stream);
 
+/* Full-state snapshots (no reference counterpart: the reference has one env and no checkpoint).  A snapshot row is opaque and
+ * self-contained: cosim_query "snapshot_floats" float32 words = the env's whole state record ("state_stride": qpos, qvel, warm start,
+ * action-delay line, last action, the 16 meta words -- sim_step and the Philox step counter that keys every later noise, delay and
+ * spawn draw among them --, the per-field frequency cache, the observation stack) followed by its parameter record ("param_stride":
+ * masses, inverse weights, friction, gains); both are padded to 32 floats, so is the row.  Nothing else survives a control step: the
+ * split pipeline's per-step record ("xstate") is rewritten by the first launch of every control step before it is read, and the
+ * overflow flags are cleared by the fix-up launch that follows the launch that set them, so neither is part of the row.  A row does
+ * NOT carry the model, the terrain or the spawn table: restore rows only into an engine built like the one they came from (the rows
+ * cannot tell; cosim_amd/snapshot.py checks metadata).  The diagnostic counters in the meta words travel with the row: after a restore
+ * they describe the restored history.
+ * cosim_snapshot: joins the range streams, flushes a pending parameter upload (the row holds what the next step would run with; the
+ * only host-blocking part, and only after a cosim_set_param), then packs every env's row into out_dev [N][snapshot_floats] in one
+ * launch on `stream`; asynchronous, capturable.
+ * cosim_restore: joins, then env d takes row src_index_dev[d] of snap_dev [snap_rows][snapshot_floats] (NULL: row d, and snap_rows
+ * must equal N); envs with mask_dev[d] == 0 are left untouched; with_params 0 leaves every env's parameter record as it is (the robot
+ * in slot d keeps its masses and gains), 1 restores it too (the host mirror cosim_set_param edits is read back from the device before
+ * the next per-env cosim_set_param, which rewrites the whole table from it).  One launch of a gather kernel (csrc/cosim_snapshot.hip);
+ * the source is the caller's buffer, never the live state, so a permutation cannot alias.  An index outside [0, snap_rows) is refused
+ * by the kernel: it never reads the row, leaves that env untouched (the other envs are restored) and counts it in a device error
+ * word; with a source index the call then waits for `stream` and returns COSIM_EINVAL naming the first such env.  With src_index_dev
+ * NULL nothing can be out of range and the call is asynchronous; while `stream` is being captured the wait is skipped (refused envs
+ * are still skipped by the kernel).  A restored env in slot d draws from slot d's random streams (they are keyed by the global env
+ * id), so envs forked from one row share no random stream with their source or with each other.  snap_dev / out_dev: 16-byte aligned. */
+int cosim_snapshot(cosim_engine_t* e, float* out_dev, void* stream);
+int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const int32_t* src_index_dev, const uint8_t* mask_dev,
+                  int with_params, void* stream);
+/* History ring: snapshots taken by cosim_step itself, without the join a caller's cosim_snapshot needs (which would undo the
+ * deferred join of the range chains).  cosim_history_set(slots, every): slots 0 switches it off and frees it; otherwise cosim_step
+ * counts its calls from here on, and after every `every`-th call packs each range's rows into ring slot (capture number) mod slots on
+ * that range's own stream, behind the range's last launch of the step (fix-up launches included): no join, no extra event, nothing on
+ * the other steps.  Blocks until the device is idle (it frees / allocates slots x N rows).  cosim_reset, cosim_step_range and
+ * cosim_rollout neither capture nor count.  While `stream` is being captured into a graph and a history is set, cosim_step returns
+ * COSIM_EINVAL (a replayed graph would repeat whatever step parity was captured).  cosim_query answers "history_slots" /
+ * "history_every".  cosim_history_get: joins and copies capture `age` (0 = newest) to out_dev [N][snapshot_floats]; *steps_ago =
+ * cosim_step calls since it was taken; COSIM_EINVAL if age >= slots or that capture does not exist yet. */
+int cosim_history_set(cosim_engine_t* e, int slots, int every);
+int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago, void* stream);
+
 /* Spawn table (no reference counterpart: the reference resets its one robot to the model's init_qpos).  M = `rows` base poses
  * spread over the terrain; every reset -- cosim_reset, the auto-reset inside every step / rollout / fix-up kernel, the reset after a
  * non-finite state -- takes qpos[0:7] from a row instead of init_qpos[0:7]; joint angles, init noise and velocities are unchanged.
