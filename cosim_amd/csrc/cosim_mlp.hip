@@ -25,12 +25,15 @@ struct MlpArgs {
   int act[MLP_MAXL];   // 0 none, 1 relu, 2 tanh, 3 elu, 4 sigmoid, 5 leaky relu
   float act_alpha[MLP_MAXL];
   int nl, n, ld;       // ld: leading dimension of the LDS tiles (widest layer + 1: odd, conflict-free column reads)
-  float clip;          // > 0: clamp the output to [-clip, clip]
+  // > 0: clamp the output to [-clip, clip].  Non-finite rule (the interpreter's clamp and the reference's np.clip, core/policy.py:20):
+  // +-inf becomes +-clip, NaN stays NaN -- the clamp is two compares and selects, not fminf / fmaxf, which return the other operand
+  // and would turn a NaN action into -clip.  Relu keeps NaN for the same reason.
+  float clip;
 };
 
 __device__ __forceinline__ float mlp_act(float x, int kind, float alpha) {
   switch (kind) {
-    case 1: return fmaxf(x, 0.f);
+    case 1: return x < 0.f ? 0.f : x;   // not fmaxf: NaN stays NaN
     case 2: return tanhf(x);
     case 3: return x > 0.f ? x : alpha * (expf(x) - 1.f);
     case 4: return 1.f / (1.f + expf(-x));
@@ -89,7 +92,7 @@ __global__ __launch_bounds__(256) void mlp_forward_kernel(MlpArgs A) {
         const int row = (v & 3) + 8 * (v >> 2) + 4 * (l >> 5);
         float y = mlp_act(acc[v], A.act[L], A.act_alpha[L]);
         if (last) {
-          if (A.clip > 0.f) y = fminf(A.clip, fmaxf(-A.clip, y));
+          if (A.clip > 0.f) y = y < -A.clip ? -A.clip : (y > A.clip ? A.clip : y);
           if (col < O && n0 + row < A.n) A.out[(size_t)(n0 + row) * O + col] = y;
         } else if (col < O)
           tile(cur ^ 1, row, col) = y;

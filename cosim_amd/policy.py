@@ -8,6 +8,11 @@ build, so the file is read with a small protobuf wire-format decoder (``read_onn
 interpreter over the operator subset RL policy exports use (Gemm / MatMul / Add / activations / LSTM / shape glue).
 The GEMMs go through torch (rocBLAS / hipBLASLt): plain library matrix products, not part of the §8 hot path.
 
+Two rules the tests pin.  Non-finite values: a NaN that reaches the output stays NaN on both paths (the interpreter's ``clamp``, like
+the reference's ``np.clip``, propagates it; the fused kernel's Relu and final clip do the same), +-inf is clipped to +-1, and a bad
+row never touches another row.  Initialisers stored as fp16 or fp64 are cast to fp32 when the graph is loaded (such a graph runs
+through the interpreter; the fused kernel takes fp32 files only).
+
 PARITY UNPINNED against onnxruntime (no policy file ships with the reference; onnxruntime is absent): the
 tests compare with a numpy evaluation of the same graph.
 """
@@ -158,7 +163,9 @@ class OnnxGraph:
         import torch
         self.torch, self.device = torch, device
         self.nodes, self.inputs, self.outputs = model["nodes"], model["inputs"], model["outputs"]
-        self.const = {k: torch.as_tensor(np.ascontiguousarray(v), device=device) for k, v in model["init"].items()}
+        # fp16 / fp64 initialisers (exports of half- or double-precision checkpoints) are cast to fp32 on load: every op below runs in fp32
+        self.const = {k: torch.as_tensor(np.ascontiguousarray(v.astype(np.float32) if v.dtype in (np.float16, np.float64) else v), device=device)
+                      for k, v in model["init"].items()}
 
     def run(self, feeds: Dict[str, "object"]) -> List["object"]:
         t = self.torch
@@ -518,14 +525,19 @@ def write_onnx(path: str, nodes: List[dict], init: Dict[str, np.ndarray], inputs
         f.write(model)
 
 
-def write_random_mlp(path: str, state_dim: int, action_dim: int, hidden=(256, 128), seed: int = 0, activation: str = "Elu"):
-    """A random-weight actor with the usual export shape (Gemm + activation ... Gemm): stands in for the missing policy files."""
+def write_random_mlp(path: str, state_dim: int, action_dim: int, hidden=(256, 128), seed: int = 0, activation: str = "Elu",
+                     bias_scale: float = 0.0):
+    """A random-weight actor with the usual export shape (Gemm + activation ... Gemm): stands in for the missing policy files.
+    Biases are ``bias_scale * standard_normal`` from a generator of their own: the default 0 writes all-zero biases and exactly the
+    weights (and bytes) earlier versions wrote for the same seed."""
     rng = np.random.default_rng(seed)
+    brng = np.random.default_rng([seed, 1])
     dims = [state_dim, *hidden, action_dim]
     nodes, init, x = [], {}, "obs"
     for li in range(len(dims) - 1):
         w = (rng.standard_normal((dims[li + 1], dims[li])) / np.sqrt(dims[li])).astype(np.float32)
-        init[f"w{li}"], init[f"b{li}"] = w, np.zeros(dims[li + 1], dtype=np.float32)
+        b = (bias_scale * brng.standard_normal(dims[li + 1])).astype(np.float32) if bias_scale else np.zeros(dims[li + 1], dtype=np.float32)
+        init[f"w{li}"], init[f"b{li}"] = w, b
         y = f"h{li}" if li < len(dims) - 2 else "actions"
         nodes.append({"op": "Gemm", "inputs": [x, f"w{li}", f"b{li}"], "outputs": [y + "_lin" if li < len(dims) - 2 else y], "attrs": {"transB": 1}})
         if li < len(dims) - 2:
