@@ -84,7 +84,7 @@ class BatchedEnv:
     def __init__(self, config: dict, num_envs: Optional[int] = None, device: Optional[int] = None, seed: Optional[int] = None,
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
-                 spawn=None, history=None):
+                 spawn=None, history=None, ledger: Optional[int] = None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -104,7 +104,10 @@ class BatchedEnv:
         ``config["engine"].get("spawn")`` / none: every reset goes to the model's ``init_qpos``.
 
         ``history``: ``(slots, every)`` -- the engine keeps a ring of ``slots`` full-state captures, one after every ``every``-th
-        ``step()`` (``cosim_history_set``), see ``history()``.  Default: ``config["engine"].get("history")`` / none."""
+        ``step()`` (``cosim_history_set``), see ``history()``.  Default: ``config["engine"].get("history")`` / none.
+
+        ``ledger``: slots -- the engine keeps the last ``slots`` (1..4096) episode records of every env on the device
+        (``cosim_ledger_set``), see ``ledger()``.  Default: ``config["engine"].get("ledger")`` / none."""
         import torch  # plumbing only
 
         eng_cfg = config.get("engine", {})
@@ -217,6 +220,10 @@ class BatchedEnv:
         if history is not None and int(history[0]) > 0:
             self.history_cfg = (int(history[0]), int(history[1]))
             self.engine.history_set(*self.history_cfg)
+        self.ledger_slots = 0
+        ledger = ledger if ledger is not None else eng_cfg.get("ledger")
+        if ledger is not None and int(ledger) != 0:
+            self.set_ledger(int(ledger))
 
     # ------------------------------------------------------------------ domain randomisation (XMLManager step 3)
     def _randomise(self, gain_noise: float):
@@ -293,6 +300,8 @@ class BatchedEnv:
         Returns ``(states [K, N, state_dim], terminated [K, N], truncated [K, N], info_buf [K, N, info_dim] or None)``: row k is what
         ``step(actions[k])`` would have returned (auto-reset included).  ``self.state`` etc. keep the last row."""
         assert self.reset_flag is True, "Call 'reset()' before calling 'step()'."
+        if self.ledger_slots > 0 and not info:
+            raise ValueError("rollout(info=False): a ledger is set and is built from the info rows; pass info=True or set_ledger(0)")
         t = self.torch
         a = t.as_tensor(actions, dtype=t.float32, device=self.device).contiguous()
         if a.ndim != 3 or tuple(a.shape[1:]) != (self.num_envs, self.action_dim):
@@ -475,6 +484,32 @@ class BatchedEnv:
         snap = Snapshot(rows, None, None, self.control_steps - ago, meta)
         snap.steps_ago = ago
         return snap
+
+    # ------------------------------------------------------------------ episode ledger (cosim_ledger_set / cosim_ledger_get)
+    def set_ledger(self, slots: int):
+        """Keep the last ``slots`` episode records of every env on the device (0: switch the ledger off and free it).  Every env
+        starts an open episode at length 0; a later ``reset()`` starts it again.  Raises ``ValueError`` outside 0..4096.  Blocks
+        until the device is idle (it allocates)."""
+        self.engine.ledger_set(int(slots))
+        self.ledger_slots = int(slots)
+
+    def ledger(self, include_open: bool = False):
+        """The fleet's episodes so far as an ``EpisodeLedger`` (``cosim_amd/ledger.py``): one row per ended episode still in the
+        ring, sorted by (global env id, episode), each with its length, how it ended (terminated / truncated / after a non-finite
+        state / not begun at a reset), the spawn row it started from and the episode's mean and peak tracking error, torque and
+        action change.  ``include_open``: also the episodes still running (flag 16).  An episode the host cut -- ``reset()`` of its
+        env, ``restore``, ``set_state`` -- is discarded, not recorded.  Joins the range streams and reads the device once; nothing is
+        read per step.  The ledger is not part of a ``snapshot()``.  Raises ``ValueError`` if no ledger is set."""
+        from .ledger import WORDS, EpisodeLedger
+        if self.ledger_slots <= 0:
+            raise ValueError("ledger(): no ledger is set (BatchedEnv(ledger=SLOTS) or set_ledger)")
+        t = self.torch
+        rec = t.empty((self.num_envs, self.ledger_slots, WORDS), dtype=t.int32, device=self.device)
+        cnt = t.empty((self.num_envs,), dtype=t.int32, device=self.device)
+        opn = t.empty((self.num_envs, WORDS), dtype=t.int32, device=self.device) if include_open else None
+        self.engine.ledger_get(rec.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
+        t.cuda.current_stream(self.device).synchronize()
+        return EpisodeLedger.from_raw(rec.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, self.env_id0)
 
     # ------------------------------------------------------------------ spawn table (cosim_spawn_set)
     def set_spawn(self, spawn, clearance: Optional[float] = None, per_episode: Optional[bool] = None):

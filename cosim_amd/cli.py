@@ -3,7 +3,7 @@
     python -m cosim_amd.cli --env flamingo_light_v1 --num-envs 4096 --steps 1000 --command 0.5 0 0 0 \\
         --policy sinusoid | random-mlp | path/to/actor.onnx  [--terrain rocky_hard] [--push-at 200 --push 0.5 0 0] \\
         [--report report.json] [--trace-env 0] [--checkpoint snap.npz --checkpoint-at 500] [--resume snap.npz [--fork-row 7]] \
-        [--history 8 10]
+        [--history 8 10] [--ledger 4 [--ledger-out episodes.npz]]
     python -m cosim_amd.cli --config session.yaml
 
 One process per GPU: under ``torchrun`` every rank simulates its shard of ``--num-envs`` and rank 0 writes the report.
@@ -78,6 +78,9 @@ def main(argv=None) -> int:
     ap.add_argument("--fork-row", type=int, default=None, help="with --resume: every env starts from this row of the file, parameters included")
     ap.add_argument("--history", type=int, nargs=2, default=None, metavar=("SLOTS", "EVERY"),
                     help="keep a ring of SLOTS full-state captures on the device, one after every EVERY-th control step")
+    ap.add_argument("--ledger", type=int, default=None, metavar="SLOTS",
+                    help="keep the last SLOTS episode records of every env on the device; their summary goes into the report as \"episodes\"")
+    ap.add_argument("--ledger-out", default=None, metavar="PATH.npz", help="with --ledger: write this rank's episode records here")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -90,7 +93,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup", "spawn"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -148,6 +151,11 @@ def main(argv=None) -> int:
         ap.error("--checkpoint / --resume run the eager loop (no --graph / --pipelined)")
     if args.history is not None and (args.history[0] < 1 or args.history[1] < 1):
         ap.error("--history SLOTS EVERY: both at least 1")
+    args.ledger = int(pick(args.ledger, sess.get("ledger") if sess.get("ledger") is not None else s_eng.get("ledger"), 0))
+    if not 0 <= args.ledger <= 4096:
+        ap.error("--ledger SLOTS: 0..4096")
+    if args.ledger_out and args.ledger < 1:
+        ap.error("--ledger-out needs --ledger SLOTS")
     if args.history is not None and args.graph:
         ap.error("--history cannot be combined with --graph: a replayed graph would repeat the captured step's parity")
 
@@ -175,7 +183,7 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     spawn=spawn or None, history=tuple(args.history) if args.history else None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:
@@ -241,6 +249,9 @@ def main(argv=None) -> int:
     torch.cuda.synchronize(env.device)
     dt = time.perf_counter() - t0
     rep.episodes_ended = env.solver_stats()["episodes_ended"] - episodes0
+    if args.ledger_out:                                             # records stay per rank: one file each
+        path = args.ledger_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.ledger_out)[:1], rank, os.path.splitext(args.ledger_out)[1])
+        env.ledger().save(path)
     if args.checkpoint and "checkpoint" not in used:
         print(f"warning: --checkpoint-at {args.checkpoint_at} was not reached, no snapshot written", file=sys.stderr)
     out = rep.save(args.report, extra={"snapshot": used} if used else None) if (args.report and rank == 0) else rep.summary()
@@ -249,6 +260,8 @@ def main(argv=None) -> int:
                           "env_steps_per_s_this_rank": env.num_envs * n / dt, "episodes_ended": out["episodes_ended"],
                           "metrics": {k: round(v["mean"], 5) for k, v in out["metrics"].items()},
                           **({"snapshot": used} if used else {}),
+                          **({"episodes": {k: out["episodes"][k] for k in ("episodes", "terminated", "truncated", "non_finite", "lost", "length")}}
+                             if "episodes" in out else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()

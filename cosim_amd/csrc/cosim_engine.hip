@@ -15,6 +15,7 @@
 #include "cosim_mlp.hip"
 #include "cosim_spawn.hip"
 #include "cosim_snapshot.hip"
+#include "cosim_ledger.hip"
 
 using namespace cosim;
 
@@ -130,6 +131,13 @@ struct cosim_engine {
   int hist_slots = 0, hist_every = 0;
   long hist_calls = 0, hist_captures = 0;   // cosim_step calls / captures since cosim_history_set
   std::vector<long> hist_call_of;           // per slot: the call count its capture was taken after
+  // episode ledger (cosim_ledger_set, cosim_ledger.hip): ledger_step_kernel behind every range's last launch of a step / rollout
+  double* d_led_sum = nullptr;    // [LEDGER_NSUM][n_envs]
+  float* d_led_peak = nullptr;    // [2][n_envs]
+  int* d_led_acc = nullptr;       // [LEDGER_NINT][n_envs]
+  int* d_led_rec = nullptr;       // [n_envs][led_slots][16]
+  int led_slots = 0;
+  bool stepped = false;           // stepped (or restored / overwritten) since the last whole-fleet reset: such an episode gets flag 8
 };
 
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
@@ -541,6 +549,47 @@ static void history_count(cosim_engine* e) {   // after a cosim_step call was is
   if (due) { e->hist_call_of[e->hist_captures % e->hist_slots] = e->hist_calls; e->hist_captures++; }
 }
 
+// ---- episode ledger (cosim_ledger.hip)
+static const char* const LEDGER_INFO_MSG =
+    ": a ledger is set (cosim_ledger_set) and info_out_dev is NULL: the ledger is built from the step's info rows; pass an info "
+    "buffer or switch the ledger off";
+
+static LedgerArgs ledger_args(cosim_engine* e) {
+  LedgerArgs a;
+  memset(&a, 0, sizeof a);
+  a.state = e->d_state; a.sum = e->d_led_sum; a.peak = e->d_led_peak; a.acc = e->d_led_acc; a.rec = e->d_led_rec;
+  a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs; a.rows = 1;
+  a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.ncmd = e->ho.command_dim < 3 ? e->ho.command_dim : 3; a.cmd_stride = e->ho.command_dim;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.slots = e->led_slots; a.spawn_rows = e->spawn_rows;
+  return a;
+}
+
+// rows [0, K) of the step outputs of envs [first, first + count), behind the launches that wrote them on the same stream
+static int ledger_step(cosim_engine* e, int first, int count, int K, const float* info, const uint8_t* term, const uint8_t* trunc,
+                       const float* cmd, hipStream_t s) {
+  LedgerArgs a = ledger_args(e);
+  a.info = info; a.term = term; a.trunc = trunc; a.cmd = a.ncmd > 0 ? cmd : nullptr;
+  a.first = first; a.count = count; a.rows = K;
+  hipLaunchKernelGGL(ledger_step_kernel, dim3((count + 63) / 64), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode, what they had open is dropped
+static int ledger_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
+  if (e->led_slots <= 0) return COSIM_OK;
+  LedgerArgs a = ledger_args(e);
+  a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
+  hipLaunchKernelGGL(ledger_begin_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+static void ledger_free(cosim_engine* e) {
+  (void)hipFree(e->d_led_sum); (void)hipFree(e->d_led_peak); (void)hipFree(e->d_led_acc); (void)hipFree(e->d_led_rec);
+  e->d_led_sum = nullptr; e->d_led_peak = nullptr; e->d_led_acc = nullptr; e->d_led_rec = nullptr; e->led_slots = 0;
+}
+
 extern "C" {
 
 // Fused actor MLP (cosim_mlp.hip): out = clip(act_L(... act_1(x W_1^T + b_1) ...)).  All pointers are device pointers; dims has
@@ -828,6 +877,7 @@ int cosim_destroy(cosim_engine_t* e) {
   hipFree(e->d_hull_cell); hipFree(e->d_hull_cand); hipFree(e->d_hfield_mip);
   hipFree(e->d_spawn);
   hipFree(e->d_hist); hipFree(e->d_snap_err);
+  ledger_free(e);
   if (e->h_snap_err) hipHostFree(e->h_snap_err);
   hipFree(e->d_pairs); hipFree(e->d_gext); hipFree(e->d_ovf); hipFree(e->d_xcon); hipFree(e->d_xcnt); hipFree(e->d_xstate);
   for (hipEvent_t x : e->ev) hipEventDestroy(x);
@@ -879,6 +929,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "snapshot_floats") return e->lay.s_stride + e->lay.p_stride;   // float32 words of a snapshot row: state record + parameter record
   if (n == "history_slots") return e->hist_slots;
   if (n == "history_every") return e->hist_every;
+  if (n == "ledger_slots") return e->led_slots;   // records per env the episode ledger keeps (0: no ledger, no ledger launches)
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
 }
 
@@ -1022,7 +1073,8 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   if (e->split && e->launch_stepx) e->launch_stepx(e, a, e->n_envs, (hipStream_t)stream);
   else (e->epw == 2 ? e->launch2 : e->launch)(e, a, e->n_envs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  if (mask_dev == nullptr) e->stepped = false;
+  return ledger_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);   // behind the reset: meta[14] is the new episode's spawn row
 }
 
 int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* commands_dev, float* state_out_dev, uint8_t* terminated_dev,
@@ -1089,6 +1141,8 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
   if (!e || !actions_dev || !state_out_dev || !terminated_dev || !truncated_dev || steps < 1) return fail(COSIM_EINVAL, "cosim_rollout: bad argument");
   if (!e->launch_roll || e->epw != 1) return fail(COSIM_EINVAL, "cosim_rollout: no rollout kernel for this model / terrain / kernel variant");
   if (e->ho.command_dim > 0 && !commands_dev) return fail(COSIM_EINVAL, "cosim_rollout: commands_dev is required when command_dim > 0");
+  if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_rollout") + LEDGER_INFO_MSG);
+  e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
   if (rc) return rc;
@@ -1112,6 +1166,10 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
     HIP_TRY(hipGetLastError());
     if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
     if (a.ovf) { e->launch_roll_fix(e, a, a.env_count, s); HIP_TRY(hipGetLastError()); }
+    if (e->led_slots > 0) {
+      rc = ledger_step(e, a.env_first, a.env_count, steps, info_out_dev, terminated_dev, truncated_dev, commands_dev, s);
+      if (rc) return rc;
+    }
   }
   if (nr > 1) { e->join_pending = true; return join_ranges(e, cs); }
   return COSIM_OK;
@@ -1181,6 +1239,8 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   if (e->ho.command_dim > 0 && !commands_dev) return fail(COSIM_EINVAL, "cosim_step: commands_dev is required when command_dim > 0");
   if (first < 0 || count < 1 || first + count > e->n_envs) return fail(COSIM_EINVAL, "cosim_step_range: range outside the fleet");
   if (e->epw == 2 && ((first | count) & 1)) return fail(COSIM_EINVAL, "cosim_step_range: two-environments-per-wave kernel needs even ranges");
+  if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + LEDGER_INFO_MSG);
+  e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
   if (rc) return rc;
@@ -1225,6 +1285,8 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     e->launch_fix(e, a, count, s);
     HIP_TRY(hipGetLastError());
   }
+  // episode ledger: this step's rows of the range, behind the range's last launch of the step (plain device work: capturable)
+  if (e->led_slots > 0) return ledger_step(e, first, count, 1, info_out_dev, terminated_dev, truncated_dev, commands_dev, s);
   return COSIM_OK;
 }
 
@@ -1338,7 +1400,8 @@ int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* st
   if (rc) return rc;
   HIP_TRY(hipMemcpy2DAsync(e->d_state + off, e->lay.s_stride * sizeof(float), in_dev, width * sizeof(float), width * sizeof(float),
                            e->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  return COSIM_OK;
+  e->stepped = true;
+  return ledger_begin(e, nullptr, nullptr, 0, LEDGER_NO_RESET, (hipStream_t)stream);
 }
 
 int cosim_snapshot(cosim_engine_t* e, float* out_dev, void* stream) {
@@ -1385,6 +1448,9 @@ int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const
   hipLaunchKernelGGL(snapshot_gather_kernel, dim3(e->n_envs), dim3(64), 0, cs, a);
   HIP_TRY(hipGetLastError());
   if (with_params) e->params_mirror_stale = true;
+  e->stepped = true;
+  rc = ledger_begin(e, mask_dev, src_index_dev, snap_rows, LEDGER_NO_RESET, cs);
+  if (rc) return rc;
   if (src_index_dev && cap == hipStreamCaptureStatusNone) {   // the kernel skipped what it refused; report it
     HIP_TRY(hipMemcpyAsync(e->h_snap_err, e->d_snap_err, 2 * sizeof(int), hipMemcpyDeviceToHost, cs));
     HIP_TRY(hipStreamSynchronize(cs));
@@ -1421,6 +1487,52 @@ int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago
   const size_t row_floats = (size_t)e->n_envs * (size_t)(e->lay.s_stride + e->lay.p_stride);
   HIP_TRY(hipMemcpyAsync(out_dev, e->d_hist + slot * row_floats, row_floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
   if (steps_ago) *steps_ago = (int)(e->hist_calls - e->hist_call_of[slot]);
+  return COSIM_OK;
+}
+
+int cosim_ledger_set(cosim_engine_t* e, int slots) {
+  if (!e || slots < 0 || slots > 4096) return fail(COSIM_EINVAL, "cosim_ledger_set: slots must be 0..4096");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());   // every range's launches in flight may still write the old buffers
+  ledger_free(e);
+  if (slots == 0) return COSIM_OK;
+  const size_t N = (size_t)e->n_envs;
+  auto alloc = [&]() -> hipError_t {
+    hipError_t r;
+    if ((r = hipMalloc(&e->d_led_sum, LEDGER_NSUM * N * sizeof(double))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_led_peak, 2 * N * sizeof(float))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_led_acc, LEDGER_NINT * N * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_led_rec, N * slots * LEDGER_WORDS * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMemset(e->d_led_acc, 0, LEDGER_NINT * N * sizeof(int))) != hipSuccess) return r;
+    return hipMemset(e->d_led_rec, 0, N * slots * LEDGER_WORDS * sizeof(int));
+  };
+  const hipError_t r = alloc();
+  if (r != hipSuccess) { ledger_free(e); return fail(COSIM_EHIP, std::string("cosim_ledger_set: ") + hipGetErrorString(r)); }
+  e->led_slots = slots;
+  // every env starts an open episode at length 0 (the range streams do not order with the null stream: wait here, cold path)
+  int rc = ledger_begin(e, nullptr, nullptr, 0, e->stepped ? LEDGER_NO_RESET : 0, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return COSIM_OK;
+}
+
+int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream) {
+  if (!e || !records_dev || !counts_dev) return fail(COSIM_EINVAL, "cosim_ledger_get: null argument");
+  if (e->led_slots <= 0) return fail(COSIM_EINVAL, "cosim_ledger_get: no ledger is set (cosim_ledger_set)");
+  if (open_dev && ((uintptr_t)open_dev & 15)) return fail(COSIM_EINVAL, "cosim_ledger_get: open_dev must be 16-byte aligned");
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t cs = (hipStream_t)stream;
+  int rc = join_ranges(e, cs);
+  if (rc) return rc;
+  const size_t N = (size_t)e->n_envs;
+  HIP_TRY(hipMemcpyAsync(records_dev, e->d_led_rec, N * e->led_slots * LEDGER_WORDS * sizeof(int), hipMemcpyDeviceToDevice, cs));
+  HIP_TRY(hipMemcpyAsync(counts_dev, e->d_led_acc + 2 * N, N * sizeof(int), hipMemcpyDeviceToDevice, cs));
+  if (open_dev) {
+    LedgerArgs a = ledger_args(e);
+    a.rec = open_dev;
+    hipLaunchKernelGGL(ledger_open_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, cs, a);
+    HIP_TRY(hipGetLastError());
+  }
   return COSIM_OK;
 }
 
@@ -1481,6 +1593,7 @@ int cosim_profile_step(cosim_engine_t* e, const float* actions_dev, const float*
   KArgs a = base_args(e);
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = commands_dev; a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.dbg = e->d_dbg;
+  e->stepped = true;
   (e->epw == 2 ? e->launch_prof2 : e->launch_prof)(e, a, e->n_envs, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());

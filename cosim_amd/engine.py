@@ -106,6 +106,8 @@ def load_library():
     L.cosim_restore.argtypes = [vp, vp, ci, vp, vp, ci, vp]
     L.cosim_history_set.argtypes = [vp, ci, ci]
     L.cosim_history_get.argtypes = [vp, ci, vp, ctypes.POINTER(ci), vp]
+    L.cosim_ledger_set.argtypes = [vp, ci]
+    L.cosim_ledger_get.argtypes = [vp, vp, vp, vp, vp]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
     L.cosim_set_timing.argtypes = [vp, ci]
@@ -115,7 +117,7 @@ def load_library():
                "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_rollout",
                "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
                "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
-               "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get"):
+               "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -129,7 +131,8 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_hull_support_check", "cosim_debug_support",
            "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
            "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
-           "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get"]
+           "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
+           "cosim_ledger_set", "cosim_ledger_get"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -304,6 +307,14 @@ class Engine:
         ago = ctypes.c_int()
         self._check(self.L.cosim_history_get(self.h, int(age), out_ptr, ctypes.byref(ago), stream))
         return ago.value
+
+    def ledger_set(self, slots: int):
+        """``cosim_ledger_set``: a ring of ``slots`` episode records per env (0: off)."""
+        self._check(self.L.cosim_ledger_set(self.h, int(slots)))
+
+    def ledger_get(self, records_ptr, counts_ptr, open_ptr=None, stream=None):
+        """``cosim_ledger_get``: rings ``[N, slots, 16]``, ended-episode counts ``[N]`` and (or ``None``) open rows ``[N, 16]``, int32."""
+        self._check(self.L.cosim_ledger_get(self.h, records_ptr, counts_ptr, open_ptr, stream))
 
     def debug_forward(self, env: int) -> np.ndarray:
         out = np.zeros(8192, dtype=np.float32)

@@ -160,6 +160,27 @@ class FleetReporter:
         out = {"control_steps": self.steps, "envs": self.env.num_envs, "episodes_ended": self.episodes_ended, "metrics": self.acc.reduce()}
         if self.hist is not None:
             out["percentiles"] = self.percentiles()
+        if getattr(self.env, "ledger_slots", 0) > 0:
+            out["episodes"] = self.episodes()
+        return out
+
+    def episodes(self) -> dict:
+        """The env's episode ledger (``BatchedEnv(ledger=SLOTS)``) summarised: ``EpisodeLedger.summary()`` plus the per-spawn-row
+        counts.  Under ``torch.distributed`` the integer counts and the length sum are all-reduced (``fleet``); the records, and so
+        the quantiles and the means of record means, stay this rank's."""
+        import torch.distributed as dist
+        led = self.env.ledger()
+        out = led.summary()
+        out["by_spawn_row"] = {str(k): v for k, v in led.by_spawn_row().items()}
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            t = self.env.torch
+            c = led.counts()
+            keys = sorted(c)
+            v = t.tensor([c[k] for k in keys], dtype=t.int64, device=self.env.device)
+            dist.all_reduce(v, op=dist.ReduceOp.SUM)
+            fleet = {k: int(x) for k, x in zip(keys, v.cpu().tolist())}
+            fleet["length_mean"] = fleet["length_sum"] / fleet["episodes"] if fleet["episodes"] else None
+            out["fleet"] = fleet
         return out
 
     def save(self, path: str, extra: Optional[dict] = None):

@@ -218,6 +218,39 @@ int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const
 int cosim_history_set(cosim_engine_t* e, int slots, int every);
 int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago, void* stream);
 
+/* Episode ledger (no reference counterpart: the reference tests one robot and reads its flags on the host every step).  Per-episode
+ * outcomes of every env, kept on the device without a host read per step.  cosim_ledger_set(slots): 0 switches it off and frees its
+ * buffers (no launch then differs from an engine that never had one); 1..4096 allocates a ring of `slots` records per env and every
+ * env starts an open episode at length 0 -- with flag 8 if the engine has been stepped since its last whole-fleet cosim_reset.
+ * Blocks until the device is idle.  From then on cosim_step_range (so cosim_step, on every range's own stream, deferred join or not)
+ * and cosim_rollout launch ledger_step_kernel (csrc/cosim_ledger.hip) behind the range's last launch -- fix-up launches and the split
+ * pipeline's last substep included -- over the rows they were given (1 / `steps`): plain device work on persistent buffers, so a
+ * captured step carries it.  Both calls then need info_out_dev (COSIM_EINVAL without).  Per env and row, in this order: length and
+ * steps_seen + 1; six double sums += (double) of the fp32 values info[0] (action_diff_RMSE), info[1] (lin_vel_x),
+ * fabsf(cmd[i] - info[1 + i]) for i < min(command_dim, 3) (fp32 subtraction; raw user command, cosim_fleet_stats' convention) and
+ * (sum over j ascending of fabsf(info[4 + j])) / nu (fp32 sum, one fp32 divide); two fp32 peaks by fmaxf (NaN is ignored):
+ * max_j |torque_j| and |cmd[0] - info[1]|.  If terminated | truncated of the row is non-zero, one record goes to slot
+ * (episode mod slots) of the env's ring and the next episode begins: sums, peaks and length zero, flags clear, spawn row = meta
+ * word 14 (the auto-reset has written the new episode's row), nan_resets base = meta word 4.  Record, 16 int32 words:
+ *   [0] episode ordinal of this env since cosim_ledger_set (0-based)   [1] length in control steps
+ *   [2] flags: 1 terminated, 2 truncated, 4 meta word 4 advanced during the episode (a non-finite state reset the env), 8 the episode
+ *       did not begin at a reset (cosim_restore / cosim_set / a ledger set on a stepped fleet), 16 still open (open_dev rows only)
+ *   [3] spawn-table row the episode started from (-1 with no table)    [4] steps_seen: rows of this env since cosim_ledger_set
+ *   float32 bits: [5] mean action_diff_RMSE  [6..8] mean tracking error i (0 beyond command_dim)  [9] mean abs torque
+ *   [10] peak abs torque  [11] mean lin_vel_x  [12] peak tracking error 0;   [13..15] 0.   Means are (float)(sum / (double)length).
+ * A rollout's kernel sees the meta words as the launch left them: with several episodes of an env ending inside one cosim_rollout,
+ * flag 4 and the spawn row are exact per launch, not per row.
+ * cosim_reset begins a new episode for its mask's envs and discards what they had open (an episode the host cut is no outcome);
+ * cosim_restore does so for the envs it restored, cosim_set for all envs, both with flag 8.  An episode "ends" whenever a step
+ * returns a flag: without auto-reset a termination that persists yields one-step episodes.  cosim_profile_step does not feed the
+ * ledger, and the ledger is not part of a snapshot row.
+ * cosim_ledger_get: joins the range streams, then copies the rings to records_dev int32[N][slots][16], the per-env count of ended
+ * episodes to counts_dev int32[N] (the ring holds the last min(count, slots) of them; count - slots were overwritten) and, unless
+ * NULL, the open episodes formatted as records (flag 16; means 0 at length 0) to open_dev int32[N][16] (16-byte aligned).
+ * cosim_query answers "ledger_slots". */
+int cosim_ledger_set(cosim_engine_t* e, int slots);
+int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream);
+
 /* Spawn table (no reference counterpart: the reference resets its one robot to the model's init_qpos).  M = `rows` base poses
  * spread over the terrain; every reset -- cosim_reset, the auto-reset inside every step / rollout / fix-up kernel, the reset after a
  * non-finite state -- takes qpos[0:7] from a row instead of init_qpos[0:7]; joint angles, init noise and velocities are unchanged.
