@@ -84,7 +84,7 @@ class BatchedEnv:
     def __init__(self, config: dict, num_envs: Optional[int] = None, device: Optional[int] = None, seed: Optional[int] = None,
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
-                 spawn=None, history=None, ledger: Optional[int] = None):
+                 spawn=None, history=None, ledger: Optional[int] = None, scenarios=None, scenario_mode: Optional[str] = None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -107,7 +107,11 @@ class BatchedEnv:
         ``step()`` (``cosim_history_set``), see ``history()``.  Default: ``config["engine"].get("history")`` / none.
 
         ``ledger``: slots -- the engine keeps the last ``slots`` (1..4096) episode records of every env on the device
-        (``cosim_ledger_set``), see ``ledger()``.  Default: ``config["engine"].get("ledger")`` / none."""
+        (``cosim_ledger_set``), see ``ledger()``.  Default: ``config["engine"].get("ledger")`` / none.
+
+        ``scenarios``: a scenario table -- a ``ScenarioTable``, a list of scenarios, ``{"scenarios": [...]}`` or a YAML file
+        (``cosim_amd/scenario.py``) -- with ``scenario_mode`` ``"env"`` (default) or ``"cycle"``, see ``set_scenarios``.  Default:
+        ``config["engine"].get("scenarios")`` / ``config["engine"].get("scenario_mode")`` / none."""
         import torch  # plumbing only
 
         eng_cfg = config.get("engine", {})
@@ -224,6 +228,11 @@ class BatchedEnv:
         ledger = ledger if ledger is not None else eng_cfg.get("ledger")
         if ledger is not None and int(ledger) != 0:
             self.set_ledger(int(ledger))
+        self.scenario_table, self.scenario_mode = None, "env"
+        self._cmd_out = self._row_out = None
+        scenarios = scenarios if scenarios is not None else eng_cfg.get("scenarios")
+        if scenarios is not None:
+            self.set_scenarios(scenarios, scenario_mode if scenario_mode is not None else eng_cfg.get("scenario_mode", "env"))
 
     # ------------------------------------------------------------------ domain randomisation (XMLManager step 3)
     def _randomise(self, gain_noise: float):
@@ -300,6 +309,8 @@ class BatchedEnv:
         Returns ``(states [K, N, state_dim], terminated [K, N], truncated [K, N], info_buf [K, N, info_dim] or None)``: row k is what
         ``step(actions[k])`` would have returned (auto-reset included).  ``self.state`` etc. keep the last row."""
         assert self.reset_flag is True, "Call 'reset()' before calling 'step()'."
+        if self.scenario_table is not None:
+            raise ValueError("rollout(): a scenario table is set and one rollout launch reads one command row; step() or set_scenarios(None)")
         if self.ledger_slots > 0 and not info:
             raise ValueError("rollout(info=False): a ledger is set and is built from the info rows; pass info=True or set_ledger(0)")
         t = self.torch
@@ -356,7 +367,7 @@ class BatchedEnv:
                 "state": b[:, 4 + 2 * nu:],
             }
             for i in range(self.command_dim):
-                info[f"user_command_{i}"] = self.user_command[:, i]
+                info[f"user_command_{i}"] = self.applied_command[:, i]
             self._info_views = info
         info = dict(info)
         info["action"] = action
@@ -510,6 +521,59 @@ class BatchedEnv:
         self.engine.ledger_get(rec.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
         t.cuda.current_stream(self.device).synchronize()
         return EpisodeLedger.from_raw(rec.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, self.env_id0)
+
+    # ------------------------------------------------------------------ scenario table (cosim_scenario_set)
+    def set_scenarios(self, scenarios, mode: str = "env"):
+        """Give every env its own test: a table of S scenarios, each a command schedule and a push schedule keyed by the env's own
+        episode step (``cosim_amd/scenario.py``; ``None`` clears the table).  Env with global id ``g`` runs row ``g mod S`` (mode
+        ``"env"``) or, in mode ``"cycle"`` (needs ``auto_reset``), row ``(g + episodes it has ended) mod S``: one scenario per
+        episode.  The engine applies the schedule on the device ahead of every control step -- on every range's own stream, inside a
+        captured graph, under a deferred join -- with no host read: a keyframe replaces the env's whole command row
+        (``applied_command``; before a scenario's first keyframe ``user_command`` passes through), a push window sets ``qvel[0:3]``
+        before every step it covers, bit for bit as ``event("push")`` does.  A table of the sizes of the one that is set is rewritten in
+        place (captured graphs pick it up).  The schedule is a function of the state record alone: ``restore`` continues it, a fork
+        follows its slot's id, shards with the same table give one fleet's results.  Limits: the table is not part of a
+        ``snapshot()``; host commands and pushes still work, a scenario keyframe / push due in the same step overrides them;
+        ``rollout()`` raises while a table is set.  Raises ``ValueError`` naming the scenario and the row for a malformed table.
+        Joins the range streams and blocks until the device is idle."""
+        from .scenario import MODES, ScenarioTable
+        t = self.torch
+        if scenarios is None:
+            self.engine.scenario_set(None, 0, None, None, self._stream())
+            self.scenario_table, self.scenario_mode = None, "env"
+            self._info_views = None
+            return
+        if mode not in MODES:
+            raise ValueError(f"set_scenarios: mode must be 'env' or 'cycle', got {mode!r}")
+        table = ScenarioTable.build(scenarios, self.command_dim)
+        if self._cmd_out is None:                                   # persistent: captured graphs hold these pointers
+            self._cmd_out = t.zeros_like(self.user_command)
+            self._row_out = t.zeros((self.num_envs,), dtype=t.int32, device=self.device)
+        try:
+            self.engine.scenario_set(table.pack(), MODES[mode], self._cmd_out.data_ptr() if self.command_dim > 0 else None,
+                                     self._row_out.data_ptr(), self._stream())
+        except Exception:
+            if self.engine.query("scenario_rows") == 0:             # the engine dropped its table (a failed upload): so does the env
+                self.scenario_table, self.scenario_mode = None, "env"
+                self._info_views = None
+            raise
+        self.scenario_table, self.scenario_mode = table, mode
+        self._info_views = None
+
+    @property
+    def applied_command(self):
+        """The raw command rows ``[N, command_dim]`` the engine steps with: the scenario kernel's output while a table is set,
+        ``user_command`` itself otherwise."""
+        return self._cmd_out if self.scenario_table is not None else self.user_command
+
+    def scenario_rows(self) -> np.ndarray:
+        """Per env: the table row the last ``step()`` / ``reset()`` applied (int64 ``[N]``; ``-1`` with no table).  Joins and
+        synchronises."""
+        if self.scenario_table is None:
+            return np.full(self.num_envs, -1, dtype=np.int64)
+        self.join()
+        self.torch.cuda.current_stream(self.device).synchronize()
+        return self._row_out.cpu().numpy().astype(np.int64)
 
     # ------------------------------------------------------------------ spawn table (cosim_spawn_set)
     def set_spawn(self, spawn, clearance: Optional[float] = None, per_episode: Optional[bool] = None):

@@ -3,7 +3,7 @@
     python -m cosim_amd.cli --env flamingo_light_v1 --num-envs 4096 --steps 1000 --command 0.5 0 0 0 \\
         --policy sinusoid | random-mlp | path/to/actor.onnx  [--terrain rocky_hard] [--push-at 200 --push 0.5 0 0] \\
         [--report report.json] [--trace-env 0] [--checkpoint snap.npz --checkpoint-at 500] [--resume snap.npz [--fork-row 7]] \
-        [--history 8 10] [--ledger 4 [--ledger-out episodes.npz]]
+        [--history 8 10] [--ledger 4 [--ledger-out episodes.npz]] [--scenarios tests.yaml [--scenario-mode env|cycle]]
     python -m cosim_amd.cli --config session.yaml
 
 One process per GPU: under ``torchrun`` every rank simulates its shard of ``--num-envs`` and rank 0 writes the report.
@@ -26,6 +26,10 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     percentiles: true
     hfield_fixup: true                                                 # or engine: {hfield_fixup: true}; same as --hfield-fixup
     spawn:    {pattern: uniform, count: 256, extent: 100.0, per_episode: true, clearance: 0.01}   # or engine: {spawn: {...}}; same as --spawn*
+    scenarios: [{commands: [[0, 0.5, 0, 0, 0], [100, 1.0, 0, 0, 0]], pushes: [[150, 155, 0.5, 0, 0]]}, {commands: [[0, 0.2, 0, 0, 0]]}]
+    scenario_mode: cycle                                               # per-ENV schedules on the device, keyed by each env's own episode step
+                                                                       # (cosim_amd/scenario.py; or a YAML file: --scenarios); unlike
+                                                                       # commands: / pushes: they run under --graph and --pipelined too
 
 Flags given on the command line override the file.
 """
@@ -81,6 +85,10 @@ def main(argv=None) -> int:
     ap.add_argument("--ledger", type=int, default=None, metavar="SLOTS",
                     help="keep the last SLOTS episode records of every env on the device; their summary goes into the report as \"episodes\"")
     ap.add_argument("--ledger-out", default=None, metavar="PATH.npz", help="with --ledger: write this rank's episode records here")
+    ap.add_argument("--scenarios", default=None, metavar="FILE.yaml",
+                    help="scenario table: per-env command and push schedules applied on the device (also under --graph / --pipelined)")
+    ap.add_argument("--scenario-mode", choices=["env", "cycle"], default=None,
+                    help="env: row = env id mod S; cycle: every env walks through the scenarios, one per episode")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -93,7 +101,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -156,6 +164,10 @@ def main(argv=None) -> int:
         ap.error("--ledger SLOTS: 0..4096")
     if args.ledger_out and args.ledger < 1:
         ap.error("--ledger-out needs --ledger SLOTS")
+    scenarios = args.scenarios if args.scenarios is not None else (sess.get("scenarios") if sess.get("scenarios") is not None else s_eng.get("scenarios"))
+    scenario_mode = pick(args.scenario_mode, sess.get("scenario_mode", s_eng.get("scenario_mode")), "env")
+    if scenario_mode not in ("env", "cycle"):
+        ap.error("scenario_mode: env or cycle")
     if args.history is not None and args.graph:
         ap.error("--history cannot be combined with --graph: a replayed graph would repeat the captured step's parity")
 
@@ -183,7 +195,7 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:
@@ -262,6 +274,8 @@ def main(argv=None) -> int:
                           **({"snapshot": used} if used else {}),
                           **({"episodes": {k: out["episodes"][k] for k in ("episodes", "terminated", "truncated", "non_finite", "lost", "length")}}
                              if "episodes" in out else {}),
+                          **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
+                             if "by_scenario" in out.get("episodes", {}) else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()

@@ -16,6 +16,7 @@
 #include "cosim_spawn.hip"
 #include "cosim_snapshot.hip"
 #include "cosim_ledger.hip"
+#include "cosim_scenario.hip"
 
 using namespace cosim;
 
@@ -138,6 +139,12 @@ struct cosim_engine {
   int* d_led_rec = nullptr;       // [n_envs][led_slots][16]
   int led_slots = 0;
   bool stepped = false;           // stepped (or restored / overwritten) since the last whole-fleet reset: such an episode gets flag 8
+  // scenario table (cosim_scenario_set, cosim_scenario.hip): scenario_step_kernel ahead of every range's first launch of a step / reset
+  char* d_scn = nullptr;          // one allocation: key_adr | push_adr | key_t | push_t | key_cmd | push_v
+  ScnTable scn = {};              // device pointers into d_scn; n_scn 0: no table, no scenario launches
+  int scn_nkey = 0, scn_npush = 0;
+  float* scn_cmd_out = nullptr;   // [n_envs][command_dim] caller-owned: what the step kernels read as the command while a table is set
+  int32_t* scn_row_out = nullptr; // [n_envs] caller-owned
 };
 
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
@@ -561,6 +568,7 @@ static LedgerArgs ledger_args(cosim_engine* e) {
   a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs; a.rows = 1;
   a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.ncmd = e->ho.command_dim < 3 ? e->ho.command_dim : 3; a.cmd_stride = e->ho.command_dim;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.slots = e->led_slots; a.spawn_rows = e->spawn_rows;
+  if (e->scn.n_scn > 0) { a.scn_row = e->scn_row_out; a.scn_rows = e->scn.n_scn; a.scn_mode = e->scn.mode; a.scn_off = e->scn.gid_off; }
   return a;
 }
 
@@ -570,7 +578,7 @@ static int ledger_step(cosim_engine* e, int first, int count, int K, const float
   LedgerArgs a = ledger_args(e);
   a.info = info; a.term = term; a.trunc = trunc; a.cmd = a.ncmd > 0 ? cmd : nullptr;
   a.first = first; a.count = count; a.rows = K;
-  hipLaunchKernelGGL(ledger_step_kernel, dim3((count + 63) / 64), dim3(64), 0, s, a);
+  hipLaunchKernelGGL(a.scn_row != nullptr ? ledger_step_scn_kernel : ledger_step_kernel, dim3((count + 63) / 64), dim3(64), 0, s, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
 }
@@ -583,6 +591,29 @@ static int ledger_begin(cosim_engine* e, const uint8_t* mask, const int* src, in
   hipLaunchKernelGGL(ledger_begin_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, s, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
+}
+
+// ---- scenario table (cosim_scenario.hip)
+// the command buffer the step kernels, the ledger and the reporter read: the scenario kernel's output while a table is set
+static const float* scenario_cmd(const cosim_engine* e, const float* commands_dev) {
+  return e->scn.n_scn > 0 && e->ho.command_dim > 0 ? e->scn_cmd_out : commands_dev;
+}
+
+// ahead of the step (reset: of the reset, for the envs under its mask) of envs [first, first + count) on the same stream
+static int scenario_launch(cosim_engine* e, int first, int count, const float* commands_dev, const uint8_t* mask, int reset, hipStream_t s) {
+  ScnArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->scn; a.state = e->d_state; a.cmd_in = commands_dev; a.cmd_out = e->scn_cmd_out; a.row_out = e->scn_row_out; a.mask = mask;
+  a.n_envs = e->n_envs; a.first = first; a.count = count;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.reset = reset;
+  hipLaunchKernelGGL(scenario_step_kernel, dim3((count + 63) / 64), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+static void scenario_free(cosim_engine* e) {
+  (void)hipFree(e->d_scn);
+  e->d_scn = nullptr; memset(&e->scn, 0, sizeof e->scn); e->scn_nkey = 0; e->scn_npush = 0; e->scn_cmd_out = nullptr; e->scn_row_out = nullptr;
 }
 
 static void ledger_free(cosim_engine* e) {
@@ -878,6 +909,7 @@ int cosim_destroy(cosim_engine_t* e) {
   hipFree(e->d_spawn);
   hipFree(e->d_hist); hipFree(e->d_snap_err);
   ledger_free(e);
+  scenario_free(e);
   if (e->h_snap_err) hipHostFree(e->h_snap_err);
   hipFree(e->d_pairs); hipFree(e->d_gext); hipFree(e->d_ovf); hipFree(e->d_xcon); hipFree(e->d_xcnt); hipFree(e->d_xstate);
   for (hipEvent_t x : e->ev) hipEventDestroy(x);
@@ -930,6 +962,8 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "history_slots") return e->hist_slots;
   if (n == "history_every") return e->hist_every;
   if (n == "ledger_slots") return e->led_slots;   // records per env the episode ledger keeps (0: no ledger, no ledger launches)
+  if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
+  if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
 }
 
@@ -1068,8 +1102,14 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   if (rc) return rc;
   rc = join_ranges(e, (hipStream_t)stream);
   if (rc) return rc;
+  if (e->scn.n_scn > 0) {   // the reset's state vector carries the scenario's first command
+    if (e->ho.command_dim > 0 && !commands_dev)
+      return fail(COSIM_EINVAL, "cosim_reset: a scenario table is set (cosim_scenario_set) and commands_dev is NULL: the scenario kernel passes the caller's command through where a scenario has no keyframe yet");
+    rc = scenario_launch(e, 0, e->n_envs, commands_dev, mask_dev, 1, (hipStream_t)stream);
+    if (rc) return rc;
+  }
   KArgs a = base_args(e);
-  a.mode = MODE_RESET; a.mask = mask_dev; a.commands = commands_dev; a.state_out = state_out_dev;
+  a.mode = MODE_RESET; a.mask = mask_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
   if (e->split && e->launch_stepx) e->launch_stepx(e, a, e->n_envs, (hipStream_t)stream);
   else (e->epw == 2 ? e->launch2 : e->launch)(e, a, e->n_envs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
@@ -1142,6 +1182,8 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
   if (!e->launch_roll || e->epw != 1) return fail(COSIM_EINVAL, "cosim_rollout: no rollout kernel for this model / terrain / kernel variant");
   if (e->ho.command_dim > 0 && !commands_dev) return fail(COSIM_EINVAL, "cosim_rollout: commands_dev is required when command_dim > 0");
   if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_rollout") + LEDGER_INFO_MSG);
+  if (e->scn.n_scn > 0)
+    return fail(COSIM_EINVAL, "cosim_rollout: a scenario table is set (cosim_scenario_set): one launch reads one command row; step with cosim_step or clear the table");
   e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
@@ -1245,7 +1287,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   int rc = upload_params(e);
   if (rc) return rc;
   KArgs a = base_args(e);
-  a.mode = MODE_STEP; a.actions = actions_dev; a.commands = commands_dev; a.state_out = state_out_dev;
+  a.mode = MODE_STEP; a.actions = actions_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev;
   a.env_first = first; a.env_count = count;
   if (e->split && e->launch_stepx && e->narrow_occ == 0) a.dbg = e->d_dbg;   // diagnostic narrowphase build accumulates its counters there
@@ -1265,6 +1307,9 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     e->ev_used += 2;
     HIP_TRY(hipEventRecord(e->ev[slot], s));
   }
+  // scenario table: this step's command and push of every env of the range, ahead of the step's first launch (plain device work:
+  // capturable); inside the timing pair, so cosim_kernel_time() includes it
+  if (e->scn.n_scn > 0) { rc = scenario_launch(e, first, count, commands_dev, nullptr, 0, s); if (rc) return rc; }
   if (split) {
     // one pair of launches per substep: the prism walk (narrow_waves waves per env), then the solver with the contacts it left; with
     // "hfield_fixup", the substeps the solver gave up (more ground contacts than its slots) are redone right behind it from the same
@@ -1286,7 +1331,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     HIP_TRY(hipGetLastError());
   }
   // episode ledger: this step's rows of the range, behind the range's last launch of the step (plain device work: capturable)
-  if (e->led_slots > 0) return ledger_step(e, first, count, 1, info_out_dev, terminated_dev, truncated_dev, commands_dev, s);
+  if (e->led_slots > 0) return ledger_step(e, first, count, 1, info_out_dev, terminated_dev, truncated_dev, scenario_cmd(e, commands_dev), s);
   return COSIM_OK;
 }
 
@@ -1530,9 +1575,85 @@ int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_de
   if (open_dev) {
     LedgerArgs a = ledger_args(e);
     a.rec = open_dev;
-    hipLaunchKernelGGL(ledger_open_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, cs, a);
+    hipLaunchKernelGGL(a.scn_row != nullptr ? ledger_open_scn_kernel : ledger_open_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, cs, a);
     HIP_TRY(hipGetLastError());
   }
+  return COSIM_OK;
+}
+
+// Scenario table: validate on the host (a message that names the scenario and the row), join the ranges, wait for the device and
+// upload.  A table of the sizes of the one that is set is rewritten in place: the device pointers stay, captured graphs pick it up.
+int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, const int32_t* key_t, const float* key_cmd, const int32_t* push_adr,
+                       const int32_t* push_t, const float* push_v, int mode, float* cmd_out_dev, int32_t* row_out_dev, void* stream) {
+  if (!e) return fail(COSIM_EINVAL, "cosim_scenario_set: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_scn == 0) {   // clear (launches in flight still read the table: wait for them)
+    int rc = join_ranges(e, (hipStream_t)stream);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    scenario_free(e);
+    return COSIM_OK;
+  }
+  const int cd = e->ho.command_dim;
+  if (n_scn < 1 || n_scn > SCN_MAX_ROWS) return fail(COSIM_EINVAL, "cosim_scenario_set: " + std::to_string(n_scn) + " scenarios: must be 1..65536 (0 clears the table)");
+  if (mode != SCN_MODE_ENV && mode != SCN_MODE_CYCLE) return fail(COSIM_EINVAL, "cosim_scenario_set: mode must be 0 (env) or 1 (cycle)");
+  if (mode == SCN_MODE_CYCLE && !e->ho.auto_reset)
+    return fail(COSIM_EINVAL, "cosim_scenario_set: mode cycle needs auto_reset: without it the episode count advances on every flagged step");
+  if (!key_adr || !push_adr || !row_out_dev || (cd > 0 && !cmd_out_dev)) return fail(COSIM_EINVAL, "cosim_scenario_set: null argument");
+  if (key_adr[0] != 0 || push_adr[0] != 0) return fail(COSIM_EINVAL, "cosim_scenario_set: key_adr[0] and push_adr[0] must be 0");
+  for (int s = 0; s < n_scn; s++) {
+    const long long nk = (long long)key_adr[s + 1] - key_adr[s], np = (long long)push_adr[s + 1] - push_adr[s];
+    const std::string who = "cosim_scenario_set: scenario " + std::to_string(s);
+    if (nk < 0 || np < 0) return fail(COSIM_EINVAL, who + ": row addresses must not decrease");
+    if (nk > SCN_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(nk) + " keyframes, at most 64");
+    if (np > SCN_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(np) + " push windows, at most 64");
+    if ((nk > 0 && (!key_t || (cd > 0 && !key_cmd))) || (np > 0 && (!push_t || !push_v))) return fail(COSIM_EINVAL, who + ": null table array");
+    for (int k = key_adr[s]; k < key_adr[s + 1]; k++) {
+      const std::string row = who + ", keyframe " + std::to_string(k - key_adr[s]);
+      if (key_t[k] < 0 || key_t[k] >= SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": time " + std::to_string(key_t[k]) + " outside [0, 2^30)");
+      if (k > key_adr[s] && key_t[k] <= key_t[k - 1])
+        return fail(COSIM_EINVAL, row + ": time " + std::to_string(key_t[k]) + " does not increase (previous " + std::to_string(key_t[k - 1]) + ")");
+      for (int c = 0; c < cd; c++)
+        if (!std::isfinite(key_cmd[(size_t)k * cd + c])) return fail(COSIM_EINVAL, row + ": command " + std::to_string(c) + " is not finite");
+    }
+    for (int p = push_adr[s]; p < push_adr[s + 1]; p++) {
+      const std::string row = who + ", push window " + std::to_string(p - push_adr[s]);
+      const int t0 = push_t[2 * p], t1 = push_t[2 * p + 1];
+      if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": times outside [0, 2^30)");
+      if (t1 <= t0) return fail(COSIM_EINVAL, row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0));
+      for (int c = 0; c < 3; c++)
+        if (!std::isfinite(push_v[3 * (size_t)p + c])) return fail(COSIM_EINVAL, row + ": velocity " + std::to_string(c) + " is not finite");
+    }
+  }
+  const int nkey = key_adr[n_scn], npush = push_adr[n_scn];
+  int rc = join_ranges(e, (hipStream_t)stream);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());   // every range's launches in flight may still read the table / write the old output buffers
+  // key_adr | push_adr | key_t | push_t | key_cmd | push_v, every array 4-byte words
+  const size_t o_kadr = 0, o_padr = o_kadr + (size_t)n_scn + 1, o_kt = o_padr + (size_t)n_scn + 1, o_pt = o_kt + (size_t)nkey,
+               o_kc = o_pt + 2 * (size_t)npush, o_pv = o_kc + (size_t)nkey * cd, words = o_pv + 3 * (size_t)npush;
+  // other sizes: a new allocation, which replaces the old one only once it is filled (a failure leaves the table that was set)
+  const bool in_place = n_scn == e->scn.n_scn && nkey == e->scn_nkey && npush == e->scn_npush;
+  char* d_new = e->d_scn;
+  if (!in_place) HIP_TRY(hipMalloc(&d_new, words * 4));
+  std::vector<int32_t> h(words, 0);
+  memcpy(&h[o_kadr], key_adr, ((size_t)n_scn + 1) * 4);
+  memcpy(&h[o_padr], push_adr, ((size_t)n_scn + 1) * 4);
+  if (nkey > 0) { memcpy(&h[o_kt], key_t, (size_t)nkey * 4); if (cd > 0) memcpy(&h[o_kc], key_cmd, (size_t)nkey * cd * 4); }
+  if (npush > 0) { memcpy(&h[o_pt], push_t, 2 * (size_t)npush * 4); memcpy(&h[o_pv], push_v, 3 * (size_t)npush * 4); }
+  const hipError_t r = hipMemcpy(d_new, h.data(), words * 4, hipMemcpyHostToDevice);
+  if (r != hipSuccess) {   // a new allocation is dropped and the old table stays; an in-place rewrite may be half written: no table then
+    if (in_place) scenario_free(e); else (void)hipFree(d_new);
+    return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
+  }
+  if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
+  const int32_t* base = reinterpret_cast<const int32_t*>(e->d_scn);
+  e->scn.key_adr = base + o_kadr; e->scn.push_adr = base + o_padr; e->scn.key_t = base + o_kt; e->scn.push_t = base + o_pt;
+  e->scn.key_cmd = reinterpret_cast<const float*>(base + o_kc); e->scn.push_v = reinterpret_cast<const float*>(base + o_pv);
+  e->scn.n_scn = n_scn; e->scn.mode = mode; e->scn.cd = cd;
+  e->scn.gid_off = (unsigned)(((e->env_id0 % n_scn) + n_scn) % n_scn);
+  e->scn_nkey = nkey; e->scn_npush = npush;
+  e->scn_cmd_out = cmd_out_dev; e->scn_row_out = row_out_dev;
   return COSIM_OK;
 }
 

@@ -14,6 +14,9 @@
 //   acc   int[LEDGER_NINT][N]     0 length, 1 steps_seen, 2 episodes ended (= ordinal of the open one), 3 open flags (bit 8),
 //                                 4 spawn row the open episode started from, 5 meta[4] (nan_resets) at its start
 //   rec   int[N][slots][16]       the ring: episode o of an env lies in slot o mod slots
+// While a scenario table is set (cosim_scenario.hip) word 13 of a record is the scenario row of its episode + 1: for an episode that
+// closes, the row scenario_step_kernel wrote ahead of the step that ended it; for an open one, the table's rule at the live meta words.
+#include "cosim_scenario.h"
 namespace cosim {
 
 constexpr int LEDGER_NSUM = 6, LEDGER_NINT = 6, LEDGER_WORDS = 16;
@@ -35,23 +38,29 @@ struct LedgerArgs {
   int n_envs, first, count, rows;   // rows: K
   int info_dim, nu, ncmd, cmd_stride, s_stride, s_meta, slots, spawn_rows;
   int flag;                // begin: open flags of the new episode
+  const int* scn_row;      // [N] rows the scenario kernel wrote ahead of this step, or null: no table (word 13 stays 0)
+  int scn_rows, scn_mode;
+  unsigned scn_off;
 };
 
 __device__ __forceinline__ float ledger_mean(double s, int n) { return n > 0 ? (float)(s / (double)n) : 0.f; }
 
 // one record from an accumulator, as four 16-byte stores
 __device__ __forceinline__ void ledger_store(int* dst, int episode, int length, int flags, int spawn, int seen, const double* s, float pk_tq,
-                                             float pk_tr) {
+                                             float pk_tr, int scn = 0) {
   int4* d = reinterpret_cast<int4*>(dst);
   d[0] = make_int4(episode, length, flags, spawn);
   d[1] = make_int4(seen, __float_as_int(ledger_mean(s[0], length)), __float_as_int(ledger_mean(s[2], length)),
                    __float_as_int(ledger_mean(s[3], length)));
   d[2] = make_int4(__float_as_int(ledger_mean(s[4], length)), __float_as_int(ledger_mean(s[5], length)), __float_as_int(pk_tq),
                    __float_as_int(ledger_mean(s[1], length)));
-  d[3] = make_int4(__float_as_int(pk_tr), 0, 0, 0);
+  d[3] = make_int4(__float_as_int(pk_tr), scn, 0, 0);
 }
 
-__global__ __launch_bounds__(64) void ledger_step_kernel(LedgerArgs a) {
+// SCN: a scenario table is set.  The two cases are kernels of their own, so that an engine without a table launches the very
+// code it launched before there were tables.
+template <bool SCN>
+__device__ __forceinline__ void ledger_step_body(const LedgerArgs& a) {
   const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
   if (i >= a.count) return;   // the last wave's tail
   const int env = a.first + i;
@@ -67,6 +76,7 @@ __global__ __launch_bounds__(64) void ledger_step_kernel(LedgerArgs a) {
   // row of the episode an auto-reset began
   const int* meta = reinterpret_cast<const int*>(a.state + (size_t)env * a.s_stride + a.s_meta);
   const int nan_now = meta[4], spawn_now = a.spawn_rows > 0 ? meta[14] : -1;
+  const int scn = SCN ? a.scn_row[env] + 1 : 0;
   float c[3] = {0.f, 0.f, 0.f};
   for (int k = 0; k < 3; k++)
     if (k < a.ncmd) c[k] = a.cmd[(size_t)env * a.cmd_stride + k];
@@ -97,7 +107,7 @@ __global__ __launch_bounds__(64) void ledger_step_kernel(LedgerArgs a) {
     if (te | tr) {
       const int flags = (te ? LEDGER_TERMINATED : 0) | (tr ? LEDGER_TRUNCATED : 0) | (nan_now != nan0 ? LEDGER_NONFINITE : 0) | oflags;
       ledger_store(a.rec + ((size_t)env * a.slots + (size_t)(episode % a.slots)) * LEDGER_WORDS, episode, length, flags, spawn, seen, s,
-                   pk_tq, pk_tr);
+                   pk_tq, pk_tr, scn);
       episode++;
 #pragma unroll
       for (int f = 0; f < LEDGER_NSUM; f++) s[f] = 0.0;
@@ -110,6 +120,8 @@ __global__ __launch_bounds__(64) void ledger_step_kernel(LedgerArgs a) {
   a.acc[env] = length; a.acc[N + env] = seen; a.acc[2 * N + env] = episode; a.acc[3 * N + env] = oflags; a.acc[4 * N + env] = spawn;
   a.acc[5 * N + env] = nan0;
 }
+__global__ __launch_bounds__(64) void ledger_step_kernel(LedgerArgs a) { ledger_step_body<false>(a); }
+__global__ __launch_bounds__(64) void ledger_step_scn_kernel(LedgerArgs a) { ledger_step_body<true>(a); }
 
 // the masked envs begin an episode; what they had open is discarded (an episode the host cut short is not an outcome)
 __global__ __launch_bounds__(64) void ledger_begin_kernel(LedgerArgs a) {
@@ -129,7 +141,8 @@ __global__ __launch_bounds__(64) void ledger_begin_kernel(LedgerArgs a) {
 }
 
 // the open accumulators as records (flag 16) into rec [N][16]
-__global__ __launch_bounds__(64) void ledger_open_kernel(LedgerArgs a) {
+template <bool SCN>
+__device__ __forceinline__ void ledger_open_body(const LedgerArgs& a) {
   const int env = (int)blockIdx.x * 64 + (int)threadIdx.x;
   if (env >= a.n_envs) return;
   const size_t N = (size_t)a.n_envs;
@@ -138,8 +151,16 @@ __global__ __launch_bounds__(64) void ledger_open_kernel(LedgerArgs a) {
   for (int f = 0; f < LEDGER_NSUM; f++) s[f] = a.sum[f * N + env];
   const int* meta = reinterpret_cast<const int*>(a.state + (size_t)env * a.s_stride + a.s_meta);
   const int flags = LEDGER_OPEN | a.acc[3 * N + env] | (meta[4] != a.acc[5 * N + env] ? LEDGER_NONFINITE : 0);
+  int scn = 0;
+  if (SCN) {
+    ScnTable T = {};
+    T.n_scn = a.scn_rows; T.mode = a.scn_mode; T.gid_off = a.scn_off;
+    scn = scenario_row(T, env, meta[11]) + 1;
+  }
   ledger_store(a.rec + (size_t)env * LEDGER_WORDS, a.acc[2 * N + env], a.acc[env], flags, a.acc[4 * N + env], a.acc[N + env], s, a.peak[env],
-               a.peak[N + env]);
+               a.peak[N + env], scn);
 }
+__global__ __launch_bounds__(64) void ledger_open_kernel(LedgerArgs a) { ledger_open_body<false>(a); }
+__global__ __launch_bounds__(64) void ledger_open_scn_kernel(LedgerArgs a) { ledger_open_body<true>(a); }
 
 }  // namespace cosim

@@ -108,6 +108,7 @@ def load_library():
     L.cosim_history_get.argtypes = [vp, ci, vp, ctypes.POINTER(ci), vp]
     L.cosim_ledger_set.argtypes = [vp, ci]
     L.cosim_ledger_get.argtypes = [vp, vp, vp, vp, vp]
+    L.cosim_scenario_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
     L.cosim_set_timing.argtypes = [vp, ci]
@@ -117,7 +118,8 @@ def load_library():
                "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_rollout",
                "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
                "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
-               "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get"):
+               "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get",
+               "cosim_scenario_set"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -132,7 +134,7 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
            "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
            "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
-           "cosim_ledger_set", "cosim_ledger_get"]
+           "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -315,6 +317,25 @@ class Engine:
     def ledger_get(self, records_ptr, counts_ptr, open_ptr=None, stream=None):
         """``cosim_ledger_get``: rings ``[N, slots, 16]``, ended-episode counts ``[N]`` and (or ``None``) open rows ``[N, 16]``, int32."""
         self._check(self.L.cosim_ledger_get(self.h, records_ptr, counts_ptr, open_ptr, stream))
+
+    def scenario_set(self, csr, mode: int, cmd_out_ptr, row_out_ptr, stream=None):
+        """``cosim_scenario_set``: ``csr`` = the six host arrays ``(key_adr, key_t, key_cmd, push_adr, push_t, push_v)`` of
+        ``ScenarioTable.pack`` (``None``: clear the table); ``cmd_out_ptr`` ``[N, command_dim]`` float32 and ``row_out_ptr`` ``[N]``
+        int32 are persistent device buffers the caller keeps alive."""
+        if csr is None:
+            self._check(self.L.cosim_scenario_set(self.h, 0, None, None, None, None, None, None, 0, None, None, stream))
+            return
+        ka, kt, kc, pa, pt, pv = csr
+        ka, pa = np.ascontiguousarray(ka, dtype=np.int32), np.ascontiguousarray(pa, dtype=np.int32)
+        kt, pt = np.ascontiguousarray(kt, dtype=np.int32), np.ascontiguousarray(pt, dtype=np.int32)
+        kc, pv = np.ascontiguousarray(kc, dtype=np.float32), np.ascontiguousarray(pv, dtype=np.float32)
+        if ka.shape != pa.shape or ka.ndim != 1 or ka.size < 1:
+            raise ValueError("scenario_set: key_adr and push_adr must both be [S + 1]")
+        nk, npw, cd = int(max(ka.max(), 0)), int(max(pa.max(), 0)), self.query("command_dim")
+        if kt.size < nk or kc.size < nk * cd or pt.size < 2 * npw or pv.size < 3 * npw:   # (the engine reads the arrays up to the addresses)
+            raise ValueError(f"scenario_set: the table arrays are shorter than their row addresses ({nk} keyframes, {npw} push windows)")
+        self._check(self.L.cosim_scenario_set(self.h, int(ka.size) - 1, ka.ctypes.data, kt.ctypes.data, kc.ctypes.data, pa.ctypes.data,
+                                              pt.ctypes.data, pv.ctypes.data, int(mode), cmd_out_ptr, row_out_ptr, stream))
 
     def debug_forward(self, env: int) -> np.ndarray:
         out = np.zeros(8192, dtype=np.float32)

@@ -17,6 +17,7 @@ TERMINATED, TRUNCATED, NONFINITE, NO_RESET, OPEN = 1, 2, 4, 8, 16
 INT_FIELDS = {"episode": 0, "length": 1, "flags": 2, "spawn_row": 3, "steps_seen": 4}
 FLOAT_FIELDS = {"mean_action_diff_RMSE": 5, "mean_tracking_err_0": 6, "mean_tracking_err_1": 7, "mean_tracking_err_2": 8,
                 "mean_abs_torque": 9, "peak_abs_torque": 10, "mean_lin_vel_x": 11, "peak_tracking_err_0": 12}
+SCENARIO_WORD = 13   # scenario row + 1 (0: no scenario table)
 NSUM = 6   # action_diff_RMSE, lin_vel_x, tracking error 0..2, mean abs torque
 
 
@@ -37,6 +38,7 @@ class EpisodeLedger:
             setattr(self, name, self.words[:, w])
         for name, w in FLOAT_FIELDS.items():
             setattr(self, name, self.words[:, w].view(np.float32))
+        self.scenario = self.words[:, SCENARIO_WORD] - 1   # scenario-table row of the episode; -1: no table was set
 
     def __len__(self):
         return len(self.words)
@@ -102,6 +104,25 @@ class EpisodeLedger:
             out[int(r)] = {"episodes": int(sel.sum()), "terminated": int(term[sel].sum()), "terminated_share": float(term[sel].mean())}
         return out
 
+    def by_scenario(self) -> dict:
+        """Per scenario-table row (``-1``: no table): ended episodes that ran it, the share of them that terminated, length
+        quantiles (control steps) and the means over those episodes of the record means (non-finite records left out)."""
+        m = self.ended()
+        rows, term, n = self.scenario[m], (self.flags[m] & TERMINATED) != 0, self.length[m].astype(np.float64)
+        out = {}
+        for r in np.unique(rows):
+            sel = rows == r
+            means = {}
+            for name in FLOAT_FIELDS:
+                v = getattr(self, name)[m][sel].astype(np.float64)
+                ok = np.isfinite(v)
+                means[name] = float(v[ok].mean()) if ok.any() else None
+            out[int(r)] = {"episodes": int(sel.sum()), "terminated": int(term[sel].sum()), "terminated_share": float(term[sel].mean()),
+                           "length": {"mean": float(n[sel].mean()), "min": int(n[sel].min()), "p50": float(np.quantile(n[sel], 0.5)),
+                                      "max": int(n[sel].max())},
+                           "means": means}
+        return out
+
     def save(self, path: str):
         """One ``.npz`` of plain arrays (no pickle)."""
         np.savez(path, words=self.words, env=self.env, lost=self.lost, header=np.array([self.slots, self.env_id0], dtype=np.int64))
@@ -113,7 +134,7 @@ class EpisodeLedger:
             return cls(z["words"], z["env"], z["lost"], int(h[0]), int(h[1]))
 
 
-def _records(episode, length, flags, spawn, seen, s, peak) -> np.ndarray:
+def _records(episode, length, flags, spawn, seen, s, peak, scenario=None) -> np.ndarray:
     """``ledger_store``: the 16 words of one record per column of the accumulators."""
     n = len(episode)
     w = np.zeros((n, WORDS), dtype=np.int32)
@@ -123,11 +144,14 @@ def _records(episode, length, flags, spawn, seen, s, peak) -> np.ndarray:
         mean = np.where(length[None, :] > 0, s / np.maximum(length, 1).astype(np.float64)[None, :], 0.0).astype(np.float32)
     f[:, 5], f[:, 6], f[:, 7], f[:, 8], f[:, 9], f[:, 11] = mean[0], mean[2], mean[3], mean[4], mean[5], mean[1]
     f[:, 10], f[:, 12] = peak[0], peak[1]
+    if scenario is not None:
+        w[:, SCENARIO_WORD] = np.asarray(scenario, dtype=np.int32) + 1
     return w
 
 
 def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spawn_rows, slots: int, nu: int, command_dim: int,
-                     include_open: bool = False, initial_flags: int = 0, begins: Sequence = (), env_id0: int = 0) -> EpisodeLedger:
+                     include_open: bool = False, initial_flags: int = 0, begins: Sequence = (), env_id0: int = 0, scenario_rows=None,
+                     open_scenario_rows=None) -> EpisodeLedger:
     """Numpy twin of ``ledger_step_kernel`` / ``ledger_begin_kernel`` / ``ledger_open_kernel``: sequential float64 adds of float32
     values, float32 subtraction / sum / divide where the kernel does them in float32, ``np.fmax`` for the peaks.
 
@@ -136,7 +160,10 @@ def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spa
     the engine's meta words 4 / 14 BEFORE step k in row k and after the last step in row K (``None``: no non-finite reset / no
     spawn table, -1); step k's record logic reads row k + 1, which is what the kernel finds behind step k.  ``initial_flags``: 8 if
     the ledger was set on a stepped fleet.  ``begins``: ``(k, mask or None, flag)`` -- a host reset (flag 0) or restore / set (flag
-    8) of the masked envs before step k (k = K: after the last step)."""
+    8) of the masked envs before step k (k = K: after the last step).  ``scenario_rows`` ``[K, N]`` (a scenario table was set): the
+    row each env ran in step k (``BatchedEnv.scenario_rows()`` after the step) -- word 13 of a record that step k closes is that
+    row + 1; ``commands`` is then the per-step applied command.  ``open_scenario_rows`` ``[N]``: the rows of the open records (the
+    table's rule at the meta words after the last step)."""
     info = np.asarray(info_rows, dtype=np.float32)
     K, N = info.shape[0], info.shape[1]
     te_all, tr_all = np.asarray(terminated).reshape(K, N), np.asarray(truncated).reshape(K, N)
@@ -145,6 +172,7 @@ def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spa
     nan_all = np.zeros((K + 1, N), dtype=np.int32) if nan_resets is None else np.asarray(nan_resets, dtype=np.int32).reshape(K + 1, N)
     spawn_all = np.full((K + 1, N), -1, dtype=np.int32) if spawn_rows is None else np.asarray(spawn_rows, dtype=np.int32).reshape(K + 1, N)
     slots = int(slots)
+    scn_all = None if scenario_rows is None else np.asarray(scenario_rows, dtype=np.int32).reshape(K, N)
     s = np.zeros((NSUM, N), dtype=np.float64)
     peak = np.zeros((2, N), dtype=np.float32)
     length, seen, episode = (np.zeros(N, dtype=np.int32) for _ in range(3))
@@ -195,7 +223,8 @@ def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spa
             if done.any():
                 i = np.nonzero(done)[0]
                 flags = (te[i] * TERMINATED) | (tr[i] * TRUNCATED) | ((nan_all[k + 1][i] != nan0[i]) * NONFINITE) | oflags[i]
-                ring[i, episode[i] % slots] = _records(episode[i], length[i], flags.astype(np.int32), spawn[i], seen[i], s[:, i], peak[:, i])
+                ring[i, episode[i] % slots] = _records(episode[i], length[i], flags.astype(np.int32), spawn[i], seen[i], s[:, i], peak[:, i],
+                                                         None if scn_all is None else scn_all[k][i])
                 episode[i] += 1
                 s[:, i] = 0.0
                 peak[:, i] = 0.0
@@ -207,7 +236,7 @@ def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spa
         open_rows = None
         if include_open:
             flags = OPEN | oflags | ((nan_all[K] != nan0) * NONFINITE)
-            open_rows = _records(episode, length, flags.astype(np.int32), spawn, seen, s, peak)
+            open_rows = _records(episode, length, flags.astype(np.int32), spawn, seen, s, peak, open_scenario_rows)
     return EpisodeLedger.from_raw(ring, episode, open_rows, env_id0)
 
 
@@ -220,7 +249,7 @@ def same_records(a: EpisodeLedger, b: EpisodeLedger) -> Optional[str]:
         return "env ids differ"
     if not np.array_equal(a.lost, b.lost):
         return "lost counts differ"
-    for name, w in list(INT_FIELDS.items()) + [("padding", 13), ("padding", 14), ("padding", 15)]:
+    for name, w in list(INT_FIELDS.items()) + [("scenario + 1", SCENARIO_WORD), ("padding", 14), ("padding", 15)]:
         bad = np.nonzero(a.words[:, w] != b.words[:, w])[0]
         if len(bad):
             r = bad[0]

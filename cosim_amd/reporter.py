@@ -70,7 +70,7 @@ class FleetReporter:
         if first < 0 or count <= 0 or first + count > e.num_envs:
             raise ValueError("write_info_range: range outside the fleet")
         rc = self._lib.cosim_fleet_stats(e.info_buf.data_ptr() + first * e.info_buf.shape[1] * 4, count, e.info_buf.shape[1], nu,
-                                         e.user_command.data_ptr() + first * e.user_command.shape[1] * 4, e.user_command.shape[1], cd,
+                                         e.applied_command.data_ptr() + first * e.user_command.shape[1] * 4, e.user_command.shape[1], cd,
                                          self.acc.buf.data_ptr(), t.cuda.current_stream(e.device).cuda_stream)
         if rc != 0:
             raise RuntimeError(self._lib.cosim_last_error().decode())
@@ -83,7 +83,7 @@ class FleetReporter:
             return
         e, t = self.env, self.env.torch
         rc = self._lib.cosim_fleet_hist(e.info_buf.data_ptr() + first * e.info_buf.shape[1] * 4, count, e.info_buf.shape[1], e.action_dim,
-                                        e.user_command.data_ptr() + first * e.user_command.shape[1] * 4, e.user_command.shape[1],
+                                        e.applied_command.data_ptr() + first * e.user_command.shape[1] * 4, e.user_command.shape[1],
                                         min(e.command_dim, 3), self._hist_hi_dev.data_ptr(), NBINS, self.hist.data_ptr(),
                                         t.cuda.current_stream(e.device).cuda_stream)
         if rc != 0:
@@ -117,15 +117,15 @@ class FleetReporter:
 
     def write_info(self, info):
         """``info``: the dict of ``BatchedEnv.step`` (on the GPU fast path it is only a token: the statistics are reduced from
-        the env's own ``info_buf`` / ``user_command`` buffers, which the dict's entries are views of)."""
+        the env's own ``info_buf`` / ``applied_command`` buffers, which the dict's entries are views of)."""
         t = self.env.torch
         nu, cd = self.env.action_dim, min(self.env.command_dim, 3)
         # one row per env: [action_diff_RMSE, lin_vel_x, lin_vel_y, ang_vel_yaw, |torque|..., |command - measured|...]
         # (command tracking as in reporter.py:506-508: applied command 0, 1 vs base linear velocity, 2 vs yaw rate)
         if self._fast and self._lib is not None:
-            # BatchedEnv on a GPU: the info dict is views of info_buf / user_command -> one launch of the engine's reducer
+            # BatchedEnv on a GPU: the info dict is views of info_buf / applied_command -> one launch of the engine's reducer
             e = self.env
-            rc = self._lib.cosim_fleet_stats(e.info_buf.data_ptr(), e.num_envs, e.info_buf.shape[1], nu, e.user_command.data_ptr(),
+            rc = self._lib.cosim_fleet_stats(e.info_buf.data_ptr(), e.num_envs, e.info_buf.shape[1], nu, e.applied_command.data_ptr(),
                                              e.user_command.shape[1], cd, self.acc.buf.data_ptr(),
                                              t.cuda.current_stream(e.device).cuda_stream)
             if rc != 0:
@@ -172,6 +172,8 @@ class FleetReporter:
         led = self.env.ledger()
         out = led.summary()
         out["by_spawn_row"] = {str(k): v for k, v in led.by_spawn_row().items()}
+        if getattr(self.env, "scenario_table", None) is not None:
+            out["by_scenario"] = {str(k): v for k, v in led.by_scenario().items()}
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             t = self.env.torch
             c = led.counts()

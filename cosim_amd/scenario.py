@@ -1,0 +1,182 @@
+"""Scenario tables: per-env command and push schedules kept on the device (``cosim_scenario_set``, csrc/cosim_scenario.hip).
+
+The reference's tester gives its one robot a test while it runs: the operator changes the command and holds the push button
+(core/tester.py:41-53,68,80-81).  A ``ScenarioTable`` is S such tests; the engine gives every env of a fleet its own -- row
+``global env id mod S`` (mode ``env``), advanced by one per episode of the env in mode ``cycle`` -- keyed by the env's own episode
+clock, with no host read per step.  ``reference_schedule`` is the numpy twin of the kernel's rule (rows and commands exact),
+``push_reference`` a float64 statement of the push arithmetic, ``sweep`` a generator of scenario grids.  No torch, no GPU here.
+
+A scenario is a mapping ``{"commands": [[t, c0, c1, ...], ...], "pushes": [[t0, t1, vx, vy, vz], ...]}``: from episode step ``t`` on
+the command is that row (whole row; before the first keyframe the caller's command passes through); a push is held for
+``t0 <= t < t1`` (the last LISTED window that holds wins).  Either list may be missing or empty.
+"""
+from __future__ import annotations
+
+import itertools
+import math
+from typing import Iterable, Iterator, Sequence
+
+import numpy as np
+
+MODES = {"env": 0, "cycle": 1}
+MAX_ROWS, MAX_ITEMS, MAX_TIME = 65536, 64, 1 << 30
+
+
+class ScenarioTable:
+    """S scenarios, validated.  ``keys[s]`` is a list of ``(t, command float32[command_dim])``, ``pushes[s]`` a list of
+    ``(t0, t1, v float32[3])``.  ``pack()`` gives the CSR arrays of the C ABI, ``from_csr`` reads them back."""
+
+    def __init__(self, scenarios: Sequence, command_dim: int):
+        self.command_dim = int(command_dim)
+        if self.command_dim < 0:
+            raise ValueError("ScenarioTable: command_dim must be >= 0")
+        scenarios = list(scenarios)
+        if not 1 <= len(scenarios) <= MAX_ROWS:
+            raise ValueError(f"ScenarioTable: {len(scenarios)} scenarios: must be 1..{MAX_ROWS}")
+        self.keys, self.pushes = [], []
+        for s, sc in enumerate(scenarios):
+            sc = sc or {}
+            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "name"}:
+                raise ValueError(f"ScenarioTable: scenario {s}: a mapping with the keys 'commands' and 'pushes' is expected, got {sc!r}")
+            keys, pushes = [], []
+            for r, row in enumerate(sc.get("commands") or []):
+                who = f"ScenarioTable: scenario {s}, keyframe {r}"
+                row = [float(x) for x in row]
+                if len(row) != 1 + self.command_dim:
+                    raise ValueError(f"{who}: {len(row)} values, expected [t, c0 .. c{self.command_dim - 1}]")
+                if not all(math.isfinite(x) for x in row):
+                    raise ValueError(f"{who}: non-finite value")
+                if row[0] != int(row[0]) or not 0 <= row[0] < MAX_TIME:
+                    raise ValueError(f"{who}: time {row[0]} must be a control step in [0, 2^30)")
+                if keys and int(row[0]) <= keys[-1][0]:
+                    raise ValueError(f"{who}: time {int(row[0])} does not increase (previous {keys[-1][0]})")
+                keys.append((int(row[0]), np.asarray(row[1:], dtype=np.float32)))
+            for r, row in enumerate(sc.get("pushes") or []):
+                who = f"ScenarioTable: scenario {s}, push window {r}"
+                row = [float(x) for x in row]
+                if len(row) != 5:
+                    raise ValueError(f"{who}: {len(row)} values, expected [t0, t1, vx, vy, vz]")
+                if not all(math.isfinite(x) for x in row):
+                    raise ValueError(f"{who}: non-finite value")
+                if row[0] != int(row[0]) or row[1] != int(row[1]) or not 0 <= row[0] < MAX_TIME or not 0 <= row[1] <= MAX_TIME:
+                    raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
+                if row[1] <= row[0]:
+                    raise ValueError(f"{who}: t1 {int(row[1])} is not after t0 {int(row[0])}")
+                pushes.append((int(row[0]), int(row[1]), np.asarray(row[2:], dtype=np.float32)))
+            for what, lst in (("keyframes", keys), ("push windows", pushes)):
+                if len(lst) > MAX_ITEMS:
+                    raise ValueError(f"ScenarioTable: scenario {s}: {len(lst)} {what}, at most {MAX_ITEMS}")
+            self.keys.append(keys)
+            self.pushes.append(pushes)
+
+    def __len__(self):
+        return len(self.keys)
+
+    @property
+    def has_push(self) -> bool:
+        return any(self.pushes)
+
+    @classmethod
+    def build(cls, spec, command_dim: int) -> "ScenarioTable":
+        """From a ``ScenarioTable`` (returned as is), a list of scenarios, a mapping ``{"scenarios": [...]}`` or the path of a YAML
+        file holding either."""
+        if isinstance(spec, cls):
+            if spec.command_dim != int(command_dim):
+                raise ValueError(f"ScenarioTable: built for command_dim {spec.command_dim}, the env has {command_dim}")
+            return spec
+        if isinstance(spec, (str, bytes)) or hasattr(spec, "__fspath__"):
+            import yaml
+            with open(spec) as f:
+                spec = yaml.safe_load(f)
+        if isinstance(spec, dict):
+            if "scenarios" not in spec:
+                raise ValueError("ScenarioTable: a mapping must hold the key 'scenarios'")
+            spec = spec["scenarios"]
+        if not isinstance(spec, (list, tuple)):
+            raise ValueError(f"ScenarioTable: expected a list of scenarios, got {type(spec).__name__}")
+        return cls(spec, command_dim)
+
+    def to_list(self) -> list:
+        return [{"commands": [[t] + [float(x) for x in c] for t, c in keys], "pushes": [[t0, t1] + [float(x) for x in v] for t0, t1, v in pushes]}
+                for keys, pushes in zip(self.keys, self.pushes)]
+
+    def pack(self):
+        """``(key_adr int32[S + 1], key_t int32[nk], key_cmd float32[nk, command_dim], push_adr int32[S + 1], push_t int32[np, 2],
+        push_v float32[np, 3])``."""
+        key_adr = np.cumsum([0] + [len(k) for k in self.keys]).astype(np.int32)
+        push_adr = np.cumsum([0] + [len(p) for p in self.pushes]).astype(np.int32)
+        key_t = np.array([t for keys in self.keys for t, _ in keys], dtype=np.int32)
+        key_cmd = np.array([c for keys in self.keys for _, c in keys], dtype=np.float32).reshape(len(key_t), self.command_dim)
+        push_t = np.array([(t0, t1) for pushes in self.pushes for t0, t1, _ in pushes], dtype=np.int32).reshape(-1, 2)
+        push_v = np.array([v for pushes in self.pushes for _, _, v in pushes], dtype=np.float32).reshape(-1, 3)
+        return key_adr, key_t, key_cmd, push_adr, push_t, push_v
+
+    @classmethod
+    def from_csr(cls, key_adr, key_t, key_cmd, push_adr, push_t, push_v, command_dim: int) -> "ScenarioTable":
+        key_cmd = np.asarray(key_cmd, dtype=np.float32).reshape(-1, int(command_dim))
+        push_t, push_v = np.asarray(push_t).reshape(-1, 2), np.asarray(push_v, dtype=np.float32).reshape(-1, 3)
+        out = []
+        for s in range(len(key_adr) - 1):
+            out.append({"commands": [[int(key_t[k])] + key_cmd[k].tolist() for k in range(int(key_adr[s]), int(key_adr[s + 1]))],
+                        "pushes": [[int(push_t[p, 0]), int(push_t[p, 1])] + push_v[p].tolist()
+                                   for p in range(int(push_adr[s]), int(push_adr[s + 1]))]})
+        return cls(out, command_dim)
+
+
+def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = ()) -> Iterator[dict]:
+    """The cartesian product command rows x push speeds x directions x push times as scenarios, commands outermost: each holds its
+    command from episode step 0 and one push of ``speed`` m/s along the world direction ``angle`` (radians about z, 0 = +x) held over
+    ``(t0, t1)``.  With no speeds or no times the product is over the commands alone (no push).
+    ``len(list(sweep(C, V, D, T))) == len(C) * len(V) * len(D) * len(T)``."""
+    commands = [[float(x) for x in c] for c in commands]
+    speeds, directions, times = [float(v) for v in push_speeds], [float(a) for a in directions], [tuple(int(x) for x in w) for w in push_times]
+    if not speeds or not times:
+        for c in commands:
+            yield {"commands": [[0] + c], "pushes": []}
+        return
+    for c, v, a, (t0, t1) in itertools.product(commands, speeds, directions, times):
+        yield {"commands": [[0] + c], "pushes": [[t0, t1, v * math.cos(a), v * math.sin(a), 0.0]]}
+
+
+def scenario_rows(n_scn: int, mode, gid, ep) -> np.ndarray:
+    """The rule's row per env: ``gid mod S`` (mode ``env`` / 0) or ``(gid mod S + uint32(ep) mod S) mod S`` (``cycle`` / 1)."""
+    S = int(n_scn)
+    mode = MODES[mode] if isinstance(mode, str) else int(mode)
+    gid = np.asarray(gid, dtype=np.int64)
+    row = np.mod(gid, S)                                           # non-negative for negative ids too
+    if mode == 1:
+        ep32 = np.asarray(ep, dtype=np.int64) & 0xFFFFFFFF          # the meta word as uint32
+        row = (row + ep32 % S) % S
+    return row.astype(np.int32)
+
+
+def reference_schedule(table: ScenarioTable, mode, gid, t, ep, base_cmd):
+    """Numpy twin of ``scenario_step_kernel`` for N envs: global ids ``gid``, episode steps ``t`` (meta word 0), episodes ended ``ep``
+    (meta word 11), the caller's commands ``base_cmd`` ``[N, >= command_dim]``.  Returns ``(row int32[N], cmd float32[N,
+    command_dim], push_mask bool[N], push_v float32[N, 3])``: the command each env is given and the world velocity of the push that
+    is due (zero rows where none is).  Rows and commands are exact."""
+    gid, t = np.asarray(gid, dtype=np.int64).reshape(-1), np.asarray(t, dtype=np.int64).reshape(-1)
+    N, cd = len(gid), table.command_dim
+    row = scenario_rows(len(table), mode, gid, np.asarray(ep).reshape(-1))
+    cmd = np.array(np.asarray(base_cmd, dtype=np.float32).reshape(N, -1)[:, :cd], dtype=np.float32)
+    mask, v = np.zeros(N, dtype=bool), np.zeros((N, 3), dtype=np.float32)
+    for i in range(N):
+        for kt, c in table.keys[row[i]]:
+            if kt > t[i]:
+                break
+            cmd[i] = c
+        for t0, t1, pv in table.pushes[row[i]]:
+            if t0 <= t[i] < t1:
+                mask[i], v[i] = True, pv
+    return row, cmd, mask, v
+
+
+def push_reference(quat, v) -> np.ndarray:
+    """``qvel[0:3]`` after a push of world velocity ``v`` at base quaternion ``quat = (w, x, y, z)`` (used raw, reference
+    flamingo_light_v1.py:234-243), in float64: ``(R^T v)[0:2]`` and ``v[2]``."""
+    w, x, y, z = (np.asarray(quat, dtype=np.float64)[..., k] for k in range(4))
+    v = np.asarray(v, dtype=np.float64)
+    R00, R01 = 1 - 2 * y * y - 2 * z * z, 2 * x * y - 2 * z * w
+    R10, R11 = 2 * x * y + 2 * z * w, 1 - 2 * x * x - 2 * z * z
+    R20, R21 = 2 * x * z - 2 * y * w, 2 * y * z + 2 * x * w
+    return np.stack([R00 * v[..., 0] + R10 * v[..., 1] + R20 * v[..., 2], R01 * v[..., 0] + R11 * v[..., 1] + R21 * v[..., 2], v[..., 2]], axis=-1)

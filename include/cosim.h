@@ -237,7 +237,7 @@ int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago
  *       did not begin at a reset (cosim_restore / cosim_set / a ledger set on a stepped fleet), 16 still open (open_dev rows only)
  *   [3] spawn-table row the episode started from (-1 with no table)    [4] steps_seen: rows of this env since cosim_ledger_set
  *   float32 bits: [5] mean action_diff_RMSE  [6..8] mean tracking error i (0 beyond command_dim)  [9] mean abs torque
- *   [10] peak abs torque  [11] mean lin_vel_x  [12] peak tracking error 0;   [13..15] 0.   Means are (float)(sum / (double)length).
+ *   [10] peak abs torque  [11] mean lin_vel_x  [12] peak tracking error 0;   [13] scenario row + 1 (0: no scenario table)   [14..15] 0.   Means are (float)(sum / (double)length).
  * A rollout's kernel sees the meta words as the launch left them: with several episodes of an env ending inside one cosim_rollout,
  * flag 4 and the spawn row are exact per launch, not per row.
  * cosim_reset begins a new episode for its mask's envs and discards what they had open (an episode the host cut is no outcome);
@@ -250,6 +250,39 @@ int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago
  * cosim_query answers "ledger_slots". */
 int cosim_ledger_set(cosim_engine_t* e, int slots);
 int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream);
+
+/* Scenario table (the reference's tester changes the command and holds the push button of its ONE robot while it runs,
+ * core/tester.py:41-53,68,80-81): per-env command and push schedules, kept and applied on the device.  S = n_scn scenarios in CSR
+ * form, host arrays: scenario s owns command keyframes [key_adr[s], key_adr[s + 1]) -- times key_t int32, strictly increasing, rows
+ * key_cmd float[.][command_dim] -- and push windows [push_adr[s], push_adr[s + 1]) -- push_t int32[.][2] = (t0, t1) with t1 > t0,
+ * world velocities push_v float[.][3], in listed order, possibly overlapping.  At most 64 keyframes and 64 windows per scenario,
+ * either list may be empty; times are control steps of the episode, 0 <= t < 2^30; 1 <= S <= 65536.
+ * From then on cosim_step_range (so cosim_step, on every range's own stream, deferred join or not) launches scenario_step_kernel
+ * (csrc/cosim_scenario.hip) AHEAD of the range's first launch of the control step -- on the split pipeline once per control step,
+ * ahead of the first narrowphase launch.  Per env: t = meta word 0 (steps of the running episode, 0 right after any reset, the
+ * auto-reset inside the previous step included), ep = meta word 11 (episodes ended), gid = env_id0 + env;
+ *   row = gid mod S (mode 0, "env")  or  (gid mod S + ep mod S) mod S with ep as uint32 (mode 1, "cycle": one scenario per episode);
+ *   command: cmd_out_dev[env][:] = the last keyframe of the row with key_t <= t, whole row; none: commands_dev[env][:] of the call;
+ *   push: the last LISTED window of the row with t0 <= t < t1, if any, sets qvel[0:3] of the record with cosim_event_push's bits, from
+ *   the pre-step quaternion, before every step of the window;   row_out_dev[env] = row.
+ * The step kernels, the fix-up kernels, the ledger and (through cmd_out_dev) the caller's reporter read cmd_out_dev as the command.
+ * cosim_reset runs the same kernel ahead of the reset launch for the envs under its mask with t = 0 and no push: the reset's state
+ * vector carries the scenario's first command.  Nothing is kept per env -- the rule is a function of words of the state record -- so a
+ * restored snapshot continues its schedule, a fork follows its slot's global id, and shards that set the same table give one
+ * fleet's results.  Plain device work on persistent buffers: a captured step carries it.  The table is not part of a snapshot row.
+ * A host command or cosim_event_push still works; a scenario keyframe / push due in the same step overrides it.
+ * cmd_out_dev float[N][command_dim] and row_out_dev int32[N] are caller-owned and must outlive the table.  n_scn = 0 clears the
+ * table (no launch then differs from an engine that never had one).  A table of the sizes (S, keyframes, windows) of the one that is
+ * set is rewritten in place: the device pointers stay, captured graphs keep working and pick up the new values.  The call joins the
+ * ranges and blocks until the device is idle and the table uploaded.  Validated on the host before anything is launched or changed,
+ * the message names the scenario and the row (COSIM_EINVAL): non-finite values, keyframe times that do not increase, t1 <= t0, more
+ * than 64 keyframes / windows, S out of range, mode 1 without auto_reset (meta word 11 would advance on every flagged step).
+ * cosim_rollout returns COSIM_EINVAL while a table is set (one launch reads one command row); cosim_profile_step ignores the table.
+ * While a table is set, word 13 of a ledger record is the scenario row of its episode + 1 (0 with no table) and the ledger's
+ * tracking errors are against cmd_out_dev.  cosim_query answers "scenario_rows" and "scenario_mode". */
+int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, const int32_t* key_t, const float* key_cmd,
+                       const int32_t* push_adr, const int32_t* push_t, const float* push_v, int mode,
+                       float* cmd_out_dev /*[N][command_dim]*/, int32_t* row_out_dev /*[N]*/, void* stream);
 
 /* Spawn table (no reference counterpart: the reference resets its one robot to the model's init_qpos).  M = `rows` base poses
  * spread over the terrain; every reset -- cosim_reset, the auto-reset inside every step / rollout / fix-up kernel, the reset after a
