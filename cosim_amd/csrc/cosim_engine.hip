@@ -71,6 +71,12 @@ struct cosim_engine {
   int t_launches = 0;
   void (*launch)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
   void (*launch_prof)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;  // diagnostic build (light_v1 flat only)
+  // step-only instantiation of the fleet kernel (the mode compiled in as MODE_STEP: no reset branch, no debug dump; the two dense
+  // plane fleets have one).  cosim_step / cosim_rollout launch it while step_kernel is set; reset, debug forward, replay and the
+  // profiler build stay on the general instantiation ("step_kernel" 0 puts the steps there too: the A/B switch)
+  void (*launch_step)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
+  void (*launch_roll_step)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
+  bool step_kernel = true;
   void (*launch2)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;      // two environments per wave (reset / step)
   void (*launch_prof2)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
   void (*launch_ct)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;       // contact-twist variant of a dense-row kernel
@@ -152,6 +158,10 @@ static void launch_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
   hipLaunchKernelGGL((env_kernel<NV, NB, RPL, HF, GTM, SC, false, 1, MCT>), dim3(grid), dim3(64), 0, s, a);
 }
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
+static void launch_step_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
+  hipLaunchKernelGGL((env_kernel<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, MODE_STEP>), dim3(grid), dim3(64), 0, s, a);
+}
+template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
 static void launch_prof_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
   hipLaunchKernelGGL((env_kernel<NV, NB, RPL, HF, GTM, SC, true, 1, MCT>), dim3(grid), dim3(64), 0, s, a);
 }
@@ -181,6 +191,10 @@ static void launch_stepx_t(cosim_engine* e, const KArgs& a, int grid, hipStream_
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
 static void launch_roll_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
   hipLaunchKernelGGL((env_rollout_kernel<NV, NB, RPL, HF, GTM, SC, MCT>), dim3(grid), dim3(64), 0, s, a);
+}
+template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
+static void launch_roll_step_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
+  hipLaunchKernelGGL((env_rollout_kernel<NV, NB, RPL, HF, GTM, SC, MCT, MODE_STEP>), dim3(grid), dim3(64), 0, s, a);
 }
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
 static void launch_roll_fix_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs of the range
@@ -756,6 +770,8 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
       e->launch_fix = launch_fix_t<18, 14, 1, false, G_LIGHT, false, 40>;
       e->fix_contact_slots = 40;
       e->launch_roll = launch_roll_t<18, 14, 1, false, G_LIGHT, false, 0>;
+      e->launch_step = launch_step_t<18, 14, 1, false, G_LIGHT, false, 0>;
+      e->launch_roll_step = launch_roll_step_t<18, 14, 1, false, G_LIGHT, false, 0>;
       e->launch_roll_fix = launch_roll_fix_t<18, 14, 1, false, G_LIGHT, false, 40>;
     }
   }
@@ -948,6 +964,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
     return e->launch_fix ? e->fix_contact_slots : 0;
   }
   if (n == "ranges") return e->n_ranges;
+  if (n == "step_kernel") return (e->step_kernel && e->launch_step && e->epw == 1) ? 1 : 0;   // 1: steps run the step-only instantiation of the fleet kernel
   if (n == "rollout") return e->launch_roll && e->epw == 1 ? 1 : 0;   // 1: cosim_rollout is available for this model / terrain
   if (n == "split") return (e->split && e->launch_stepx) ? e->narrow_waves : 0;   // waves per env of the narrowphase kernel; 0: fused kernel
   if (n == "pair_slots") return e->pair_slots;
@@ -1020,6 +1037,12 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
     HIP_TRY(hipMemcpy(e->d_model, &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
     return COSIM_OK;
   }
+  else if (n == "step_kernel") {   // 1: cosim_step / cosim_rollout launch the step-only instantiation where the fleet has one (default); 0: the general one
+    const int v = (int)host[0];
+    if (v != 0 && v != 1) return fail(COSIM_EINVAL, "cosim_set_param: step_kernel must be 0 or 1");
+    e->step_kernel = v != 0;
+    return COSIM_OK;
+  }
   else if (n == "fixup") {   // 0: no fix-up launches (contacts beyond the fleet kernel's slots are left out and counted, as in round 2)
     if ((int)host[0] == 0) {
       e->launch_fix = nullptr; if (e->launch_roll_fix) { e->launch_roll = nullptr; e->launch_roll_fix = nullptr; }
@@ -1041,6 +1064,7 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
       if (!e->launch_ct) return fail(COSIM_EINVAL, "cosim_set_param: no contact-twist variant for this model / terrain");
       e->launch = e->launch_ct; e->launch_prof = e->launch_ct_prof; e->launch2 = nullptr; e->launch_prof2 = nullptr; e->epw = 1;
       e->launch_fix = nullptr; e->launch_roll = nullptr; e->launch_roll_fix = nullptr;
+      e->launch_step = nullptr; e->launch_roll_step = nullptr;   // (the contact-twist kernels have no step-only instantiation)
       if (e->model.nv == 14) e->pair_slots = 8;
       e->lds_bytes = e->ct_lds_bytes; e->contact_slots = e->ct_contact_slots;
     }
@@ -1204,7 +1228,7 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
     a.env_count = nr > 1 ? e->rcount[i] : e->n_envs;
     int slot = -1;
     if (e->timing && e->ev_used + 2 <= (int)e->ev.size()) { slot = e->ev_used; e->ev_used += 2; HIP_TRY(hipEventRecord(e->ev[slot], s)); }
-    e->launch_roll(e, a, a.env_count, s);
+    (e->step_kernel && e->launch_roll_step ? e->launch_roll_step : e->launch_roll)(e, a, a.env_count, s);
     HIP_TRY(hipGetLastError());
     if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
     if (a.ovf) { e->launch_roll_fix(e, a, a.env_count, s); HIP_TRY(hipGetLastError()); }
@@ -1323,7 +1347,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
       e->launch_stepx(e, a, count, s);
       if (a.ovf) fix(e, a, count, s);
     }
-  } else (e->epw == 2 ? e->launch2 : e->launch)(e, a, count, s);
+  } else (e->epw == 2 ? e->launch2 : (e->step_kernel && e->launch_step ? e->launch_step : e->launch))(e, a, count, s);
   HIP_TRY(hipGetLastError());
   if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
   if (a.ovf && !split) {   // envs the fleet kernel flagged (more contacts than it has slots for) are redone by the large-capacity kernel

@@ -633,7 +633,10 @@ typedef const KArgs __attribute__((address_space(4)))* KArgsP;
 // kernel redoing a step that the fleet's kernel gave up on (see env_fixup_kernel); otherwise, where the engine has such a kernel
 // (A.ovf != null), a step whose contacts do not fit this kernel's slots is abandoned before anything is written and flagged.
 // KM: see KTraits.  wsel: (KM == 1) which of the env's A.nw narrowphase waves this is.
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, bool PROF, int EPW, int MCT, bool FIX, int KM = 0>
+// KMODE: -1 the general body (the mode is A.mode, a runtime value: reset, step and debug forward share the code); MODE_STEP the
+// step-only body: the mode is a constant, so no reset-mode branch and no debug dump is compiled in and A.mode is never read.  The
+// arithmetic of a step is the same instruction sequence in both (tests/test_gpu_step_kernel.py compares them bit for bit).
+template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, bool PROF, int EPW, int MCT, bool FIX, int KM = 0, int KMODE = -1>
 __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::L (&SS)[EPW], const int wsel = 0,
                                          const int kstep = 0) {   // kstep: control step of a rollout launch (row of the [K][N][...] I/O buffers)
   static_assert(EPW == 1 || (EPW == 2 && !HF && !SC && NV <= 32 && NB <= 32), "two environments per wave: flat ground, no pairs");
@@ -656,7 +659,8 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
   constexpr int NGENMAX = L::NGEN;
   constexpr int EPL = (TRI + 63) / 64;
   // the fix-up kernel only ever steps (a constant there: its loop over flagged envs then has no exit the compiler must treat as divergent)
-  const int kmode = FIX ? (int)MODE_STEP : A.mode;
+  static_assert(KMODE == -1 || KMODE == MODE_STEP, "the mode is either read from the argument block or compiled in as MODE_STEP");
+  const int kmode = (FIX || KMODE == MODE_STEP) ? (int)MODE_STEP : A.mode;
   const int wlane = threadIdx.x;
   const int hb = EPW == 1 ? 0 : (wlane & 32);          // first lane of this lane's group
   const int lane = EPW == 1 ? wlane : (wlane & 31);     // role index inside the group
@@ -3035,16 +3039,16 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
 // SIMD (4.4 -> 3.7 M env-steps/s on light_rocky); 9 and 10 keep asking for 3 (the fine-cell kernels were tuned there)
 constexpr int waves_per_simd(int per_cu) { return per_cu >= 15 ? 4 : per_cu >= 9 ? 3 : per_cu >= 5 ? 2 : 1; }
 
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, bool PROF = false, int EPW = 1, int MCT = 0>
+template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, bool PROF = false, int EPW = 1, int MCT = 0, int KMODE = -1>
 // waves per SIMD the register allocator is asked for = what the LDS footprint admits (160 KiB per CU, 4 SIMDs): asking for more makes
 // the compiler spill for nothing, asking for less wastes resident waves
 __global__ __launch_bounds__(64, (EPW == 2 ? 2 : waves_per_simd(163840 / (int)sizeof(typename KTraits<NV, NB, RPL, HF, SC, EPW, MCT>::L)))) void env_kernel(KArgs kernarg_block) {
   KArgsP kargs_p = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
   (void)kernarg_block;
   __shared__ typename KTraits<NV, NB, RPL, HF, SC, EPW, MCT>::L SS[EPW];
-  const int env = A.mode == MODE_DEBUG ? A.dbg_env : A.env_first + (int)blockIdx.x * EPW + (EPW == 1 ? 0 : ((int)threadIdx.x >> 5));
+  const int env = (KMODE == -1 && A.mode == MODE_DEBUG) ? A.dbg_env : A.env_first + (int)blockIdx.x * EPW + (EPW == 1 ? 0 : ((int)threadIdx.x >> 5));
   if (env >= A.n_envs) return;
-  env_body<NV, NB, RPL, HF, GTM, SC, PROF, EPW, MCT, false>(kargs_p, env, SS);
+  env_body<NV, NB, RPL, HF, GTM, SC, PROF, EPW, MCT, false, 0, KMODE>(kargs_p, env, SS);
 }
 
 // Split pipeline (heightfield kernels whose narrowphase dwarfs everything else: humanoid_p_v0 on 1 cm stairs cells spends 89 % of a
@@ -3081,7 +3085,7 @@ __global__ __launch_bounds__(64, waves_per_simd(163840 / (int)sizeof(typename KT
 // the wave's own stores must be what its loads see: release / acquire at agent scope (write-back + L1 invalidate).  A dense fleet
 // kernel that meets more contacts than it has slots at step k flags the env with k + 1 and leaves: env_rollout_fix_kernel takes the
 // env from step k to the end with the large-capacity body.
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
+template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT, int KMODE = -1>
 __global__ __launch_bounds__(64, waves_per_simd(163840 / (int)sizeof(typename KTraits<NV, NB, RPL, HF, SC, 1, MCT>::L))) void env_rollout_kernel(KArgs kernarg_block) {
   KArgsP kargs_p = (KArgsP)__builtin_amdgcn_kernarg_segment_ptr();
   (void)kernarg_block;
@@ -3091,7 +3095,7 @@ __global__ __launch_bounds__(64, waves_per_simd(163840 / (int)sizeof(typename KT
   const int K = A.roll_steps;
 #pragma nounroll
   for (int k = 0; k < K; k++) {
-    env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, false>(kargs_p, env, SS, 0, k);
+    env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, false, 0, KMODE>(kargs_p, env, SS, 0, k);
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (A.ovf != nullptr && __builtin_amdgcn_readfirstlane(A.ovf[env]) != 0) break;   // abandoned at step k: the fix kernel continues

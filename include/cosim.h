@@ -105,7 +105,11 @@ int cosim_query(const cosim_engine_t* e, const char* name);
  * "timing_stride" (default 1: with cosim_set_timing on, an event pair around every launch; n: around every n-th launch -- the
  * events cost ~4 % of a 20-step run at 1, choose n coprime with "ranges" so that every range is sampled),
  * "block_cull" (1, default: the narrowphase kernel of the split pipeline tests blocks of 8 prisms -- height and oriented box -- before
- * their prisms; 0: every block goes on to the per-prism tests; same contacts either way).
+ * their prisms; 0: every block goes on to the per-prism tests; same contacts either way), "step_kernel" (1, default: cosim_step /
+ * cosim_step_range / cosim_rollout launch the step-only instantiation of the fleet kernel where the fleet has one -- the dense plane
+ * kernel of flamingo_light_v1 and its rollout kernel: the kernel mode compiled in, no reset branch, no debug dump; 0: the general
+ * instantiation that reset, debug forward and replay always run; the same bits either way, kept as the A/B switch;
+ * cosim_query "step_kernel" answers 1 while steps run the step-only instantiation, 0 otherwise).
  * cosim_query additionally answers "contact_slots" / "pair_slots" (capacity of the selected kernel variant: heightfields with cells
  * of 10 cm or more select the 48-slot variants of flamingo_light_v1 / w4_p_v2), "fixup_contact_slots" (capacity of the kernel that
  * redoes a control step -- on the split pipeline with "hfield_fixup", a substep -- whose contacts did not fit; 0: this model / terrain
