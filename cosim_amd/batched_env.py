@@ -84,7 +84,8 @@ class BatchedEnv:
     def __init__(self, config: dict, num_envs: Optional[int] = None, device: Optional[int] = None, seed: Optional[int] = None,
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
-                 spawn=None, history=None, ledger: Optional[int] = None, scenarios=None, scenario_mode: Optional[str] = None):
+                 spawn=None, history=None, ledger: Optional[int] = None, scenarios=None, scenario_mode: Optional[str] = None,
+                 fall=None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -111,7 +112,11 @@ class BatchedEnv:
 
         ``scenarios``: a scenario table -- a ``ScenarioTable``, a list of scenarios, ``{"scenarios": [...]}`` or a YAML file
         (``cosim_amd/scenario.py``) -- with ``scenario_mode`` ``"env"`` (default) or ``"cycle"``, see ``set_scenarios``.  Default:
-        ``config["engine"].get("scenarios")`` / ``config["engine"].get("scenario_mode")`` / none."""
+        ``config["engine"].get("scenarios")`` / ``config["engine"].get("scenario_mode")`` / none.
+
+        ``fall``: a fall rule -- a ``FallRule`` or a dict ``{"tilt", "height", "grace", "bodies"}`` (``cosim_amd/fall.py``) -- see
+        ``set_fall``.  Default: ``config["engine"].get("fall")`` / none: an episode ends early only through the robot's own
+        ``_is_done``."""
         import torch  # plumbing only
 
         eng_cfg = config.get("engine", {})
@@ -202,6 +207,11 @@ class BatchedEnv:
             rl = [self.engine.range(i) for i in range(self.ranges)]
             self.range_list = [(f, c) for f, c, _ in rl]
             self.range_streams = [torch.cuda.ExternalStream(st, device=self.device) for _, _, st in rl]
+
+        self.fall_rule = None
+        fall = fall if fall is not None else eng_cfg.get("fall")
+        if fall is not None:
+            self.set_fall(fall)
 
         self._randomise(gain_noise)
         spawn = spawn if spawn is not None else eng_cfg.get("spawn")
@@ -404,7 +414,8 @@ class BatchedEnv:
 
     # ------------------------------------------------------------------ snapshots (cosim_snapshot / cosim_restore / history ring)
     def snapshot_meta(self) -> dict:
-        """What a snapshot of this env records about where it came from, and what ``restore`` compares (``snapshot.META_FIELDS``)."""
+        """What a snapshot of this env records about where it came from, and what ``restore`` compares (``snapshot.META_FIELDS``).
+        Neither the scenario table nor the fall rule is part of it: set them again on the env you restore into."""
         return {"env_id": self.id, "terrain": self.config["env"]["terrain"], "precision": self.config["random"]["precision"],
                 "snapshot_floats": self.engine.query("snapshot_floats"), "state_stride": self.engine.query("state_stride"),
                 "param_stride": self.engine.query("param_stride"), "state_dim": self.state_dim, "n_envs": self.num_envs,
@@ -521,6 +532,40 @@ class BatchedEnv:
         self.engine.ledger_get(rec.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
         t.cuda.current_stream(self.device).synchronize()
         return EpisodeLedger.from_raw(rec.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, self.env_id0)
+
+    # ------------------------------------------------------------------ fall rules (cosim_fall_set)
+    def set_fall(self, rule):
+        """End episodes on the robot's posture: ``rule`` is a ``FallRule``, a dict of its arguments (``tilt`` radians, ``height``
+        metres, ``grace`` control steps, ``bodies`` names) or ``None`` to clear it (``cosim_amd/fall.py``).  The step kernel tests
+        the pose every control step ends in -- inside ``step()``, every step of a ``rollout()``, the fix-up kernels, the split
+        pipeline -- and a rule that fires ends the episode there like any other end: ``terminated``, the info row of the fallen
+        step, the auto-reset and its observation, ``episodes_ended``, the ledger record (flags 32 tilt / 64 height / 128 body
+        contact), the next scenario in mode ``"cycle"``.  ``end_cause()`` tells why.  ``bodies`` replaces the robot's own
+        ``_is_done`` body list (``[]``: no body rule) until the rule is cleared.  Limits: tilt and height are tested on single
+        steps, from episode step ``grace + 1`` on; the body rule knows no grace; the thresholds are kernel arguments, so a captured
+        graph keeps the rule it was captured with -- set the rule before capturing; the rule is not part of a ``snapshot()`` (set
+        it again on the env you restore into).  Raises ``ValueError`` naming the field or the body the model does not have.  Blocks
+        until the device is idle when the body list changes."""
+        from .fall import FallRule
+        rule = FallRule.build(rule)
+        if rule is not None and rule.is_off():
+            rule = None
+        if rule is None:
+            self.engine.fall_set(-1.0, 0.0, 0, None)
+            self.fall_rule = None
+            return
+        ids = rule.body_ids(self.cm.body_names)
+        self.engine.fall_set(rule.min_up, rule.min_height, rule.grace, ids)
+        self.fall_rule = rule
+
+    def end_cause(self):
+        """Per env: why its latest episode ended while a fall rule was set -- int32 tensor ``[N]``, engine meta word 15: bit 1 tilt,
+        2 height, 4 body contact, 0 for a time limit, a non-finite state or no end yet.  Joins and synchronises."""
+        t = self.torch
+        buf = t.zeros((self.num_envs, 16), dtype=t.float32, device=self.device)
+        self.engine.get("meta", buf.data_ptr(), self._stream())
+        t.cuda.synchronize(self.device)
+        return buf.view(t.int32)[:, 15].clone()
 
     # ------------------------------------------------------------------ scenario table (cosim_scenario_set)
     def set_scenarios(self, scenarios, mode: str = "env"):

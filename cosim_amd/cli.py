@@ -3,7 +3,8 @@
     python -m cosim_amd.cli --env flamingo_light_v1 --num-envs 4096 --steps 1000 --command 0.5 0 0 0 \\
         --policy sinusoid | random-mlp | path/to/actor.onnx  [--terrain rocky_hard] [--push-at 200 --push 0.5 0 0] \\
         [--report report.json] [--trace-env 0] [--checkpoint snap.npz --checkpoint-at 500] [--resume snap.npz [--fork-row 7]] \
-        [--history 8 10] [--ledger 4 [--ledger-out episodes.npz]] [--scenarios tests.yaml [--scenario-mode env|cycle]]
+        [--history 8 10] [--ledger 4 [--ledger-out episodes.npz]] [--scenarios tests.yaml [--scenario-mode env|cycle]] \
+        [--fall-tilt 0.8 --fall-height 0.1 --fall-grace 5 --fall-bodies base_link,left_leg_link]
     python -m cosim_amd.cli --config session.yaml
 
 One process per GPU: under ``torchrun`` every rank simulates its shard of ``--num-envs`` and rank 0 writes the report.
@@ -30,6 +31,9 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     scenario_mode: cycle                                               # per-ENV schedules on the device, keyed by each env's own episode step
                                                                        # (cosim_amd/scenario.py; or a YAML file: --scenarios); unlike
                                                                        # commands: / pushes: they run under --graph and --pipelined too
+    fall:     {tilt: 0.8, height: 0.1, grace: 5, bodies: [base_link]}  # fall rule (cosim_amd/fall.py): end an episode on tilt (rad), base
+                                                                       # height (m) or contact of the listed bodies; or engine: {fall: {...}};
+                                                                       # same as --fall-*; runs under --graph and --pipelined too
 
 Flags given on the command line override the file.
 """
@@ -89,6 +93,10 @@ def main(argv=None) -> int:
                     help="scenario table: per-env command and push schedules applied on the device (also under --graph / --pipelined)")
     ap.add_argument("--scenario-mode", choices=["env", "cycle"], default=None,
                     help="env: row = env id mod S; cycle: every env walks through the scenarios, one per episode")
+    ap.add_argument("--fall-tilt", type=float, default=None, metavar="RAD", help="fall rule: end an episode when the base tilts further than this from upright")
+    ap.add_argument("--fall-height", type=float, default=None, metavar="M", help="fall rule: end an episode when the base is lower than this above the ground under it")
+    ap.add_argument("--fall-grace", type=int, default=None, metavar="STEPS", help="fall rule: control steps at the start of an episode without the tilt / height test")
+    ap.add_argument("--fall-bodies", default=None, metavar="a,b,c", help="fall rule: bodies whose contact force ends the episode (replaces the robot's own list)")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -101,7 +109,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -168,6 +176,19 @@ def main(argv=None) -> int:
     scenario_mode = pick(args.scenario_mode, sess.get("scenario_mode", s_eng.get("scenario_mode")), "env")
     if scenario_mode not in ("env", "cycle"):
         ap.error("scenario_mode: env or cycle")
+    # fall rule: the session's dict (top level or engine.fall), overridden key by key by the flags
+    fall = dict(sess.get("fall") or s_eng.get("fall") or {})
+    for key, val in (("tilt", args.fall_tilt), ("height", args.fall_height), ("grace", args.fall_grace)):
+        if val is not None:
+            fall[key] = val
+    if args.fall_bodies is not None:
+        fall["bodies"] = [b for b in args.fall_bodies.split(",") if b]
+    if fall:
+        from .fall import FallRule
+        try:
+            FallRule.build(fall)
+        except ValueError as e:
+            ap.error(f"--fall-* / fall: {e}")
     if args.history is not None and args.graph:
         ap.error("--history cannot be combined with --graph: a replayed graph would repeat the captured step's parity")
 
@@ -195,7 +216,7 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:
@@ -272,7 +293,8 @@ def main(argv=None) -> int:
                           "env_steps_per_s_this_rank": env.num_envs * n / dt, "episodes_ended": out["episodes_ended"],
                           "metrics": {k: round(v["mean"], 5) for k, v in out["metrics"].items()},
                           **({"snapshot": used} if used else {}),
-                          **({"episodes": {k: out["episodes"][k] for k in ("episodes", "terminated", "truncated", "non_finite", "lost", "length")}}
+                          **({"episodes": {k: out["episodes"][k] for k in ("episodes", "terminated", "truncated", "non_finite", "lost", "length") +
+                                           (("fell", "fell_tilt", "fell_height", "fell_contact") if env.fall_rule is not None else ())}}
                              if "episodes" in out else {}),
                           **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
                              if "by_scenario" in out.get("episodes", {}) else {}),

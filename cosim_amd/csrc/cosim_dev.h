@@ -96,7 +96,9 @@ struct Layout {
   // [6] line-search evaluations [7] Hessian factorisations (cumulative since creation; [3] per substep) [8] contacts left out for
   // lack of slots / rows [9] limit rows left out [10] most contacts detected in one substep [11] episodes ended
   // [12] control steps redone by the large-capacity kernel (env_fixup_kernel) [13] heightfield prism walks cut short (also in [8])
-  // [14] spawn-table row of the env's last reset (written only while a table is set) [15] unused
+  // [14] spawn-table row of the env's last reset (written only while a table is set)
+  // [15] cause of the env's latest episode end (written only while a fall rule is set, cosim_fall_set): 1 tilt | 2 height | 4 body
+  // contact; 0: time limit, non-finite state or no rule fired
   static constexpr int NMETA = 16;
   // parameter record
   int p_mass, p_binvw, p_dinvw, p_floss, p_gmu, p_kp, p_kd, p_mean, p_stride;

@@ -151,6 +151,11 @@ struct cosim_engine {
   int scn_nkey = 0, scn_npush = 0;
   float* scn_cmd_out = nullptr;   // [n_envs][command_dim] caller-owned: what the step kernels read as the command while a table is set
   int32_t* scn_row_out = nullptr; // [n_envs] caller-owned
+  // fall rules (cosim_fall_set): kernel arguments of every step launch; fall_mask 0 = none (meta word 15 is not written)
+  float fall_min_up = -1.f, fall_min_height = 0.f;
+  int fall_grace = 0, fall_mask = 0;
+  int model_term_mode = 0;              // the model's own _is_done list, restored when a body-list override is cleared
+  unsigned model_term_bodymask = 0u;
 };
 
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
@@ -582,6 +587,7 @@ static LedgerArgs ledger_args(cosim_engine* e) {
   a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs; a.rows = 1;
   a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.ncmd = e->ho.command_dim < 3 ? e->ho.command_dim : 3; a.cmd_stride = e->ho.command_dim;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.slots = e->led_slots; a.spawn_rows = e->spawn_rows;
+  a.fall = e->fall_mask != 0;
   if (e->scn.n_scn > 0) { a.scn_row = e->scn_row_out; a.scn_rows = e->scn.n_scn; a.scn_mode = e->scn.mode; a.scn_off = e->scn.gid_off; }
   return a;
 }
@@ -853,8 +859,9 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
   }
   HIP_TRY(hipMalloc(&e->d_model, sizeof(DevModel)));
   HIP_TRY(hipMalloc(&e->d_obs, sizeof(DevObs)));
+  e->model_term_mode = e->hm.term_mode; e->model_term_bodymask = e->hm.term_bodymask;
   HIP_TRY(hipMemcpy(e->d_model, &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_obs, &e->ho, sizeof(DevObs), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->d_obs,&e->ho, sizeof(DevObs), hipMemcpyHostToDevice));
   HIP_TRY(hipMalloc(&e->d_state, (size_t)n_envs * e->lay.s_stride * sizeof(float)));
   HIP_TRY(hipMemset(e->d_state, 0, (size_t)n_envs * e->lay.s_stride * sizeof(float)));
   HIP_TRY(hipMalloc(&e->d_params, (size_t)n_envs * e->lay.p_stride * sizeof(float)));
@@ -981,6 +988,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "ledger_slots") return e->led_slots;   // records per env the episode ledger keeps (0: no ledger, no ledger launches)
   if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
   if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
+  if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
 }
 
@@ -1116,6 +1124,7 @@ static KArgs base_args(cosim_engine* e) {
   a.spawn = e->d_spawn; a.spawn_rows = e->spawn_rows; a.spawn_mode = e->spawn_mode;
   a.spawn_off = e->spawn_rows > 0 ? (unsigned)(((e->env_id0 % e->spawn_rows) + e->spawn_rows) % e->spawn_rows) : 0u;
   a.xcon = e->d_xcon; a.xcnt = e->d_xcnt; a.xstate = e->d_xstate; a.nw = e->narrow_waves; a.sub_index = 0; a.sub_total = 0;
+  a.fall_min_up = e->fall_min_up; a.fall_min_height = e->fall_min_height; a.fall_grace = e->fall_grace; a.fall_mask = e->fall_mask;
   return a;
 }
 
@@ -1427,6 +1436,38 @@ int cosim_spawn_set(cosim_engine_t* e, const float* xyyaw_host, int rows, const 
   if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_spawn_set: ") + hipGetErrorString(r));
   e->h_spawn.swap(placed);
   e->spawn_rows = rows; e->spawn_mode = per_episode != 0;
+  return COSIM_OK;
+}
+
+// ---- fall rules (the rule itself is in env_body, cosim_kernels.hip)
+int cosim_fall_set(cosim_engine_t* e, float min_up, float min_height, int grace_steps, const int32_t* body_ids, int n_bodies) {
+  if (!e) return fail(COSIM_EINVAL, "cosim_fall_set: null engine");
+  if (!std::isfinite(min_up)) return fail(COSIM_EINVAL, "cosim_fall_set: min_up is not finite");
+  if (!std::isfinite(min_height)) return fail(COSIM_EINVAL, "cosim_fall_set: min_height is not finite");
+  if (grace_steps < 0) return fail(COSIM_EINVAL, "cosim_fall_set: grace_steps " + std::to_string(grace_steps) + " is negative");
+  if (n_bodies > 0 && !body_ids) return fail(COSIM_EINVAL, "cosim_fall_set: n_bodies > 0 and body_ids is NULL");
+  if (n_bodies > CS_MAXBODY) return fail(COSIM_EINVAL, "cosim_fall_set: more than " + std::to_string(CS_MAXBODY) + " bodies");
+  unsigned bodymask = 0u;
+  for (int i = 0; i < n_bodies; i++) {
+    if (body_ids[i] <= 0 || body_ids[i] >= e->model.nbody)
+      return fail(COSIM_EINVAL, "cosim_fall_set: body id " + std::to_string(body_ids[i]) + " is not a body of the robot (1.." +
+                                    std::to_string(e->model.nbody - 1) + ")");
+    bodymask |= 1u << body_ids[i];
+  }
+  const int term_mode = n_bodies < 0 ? e->model_term_mode : (bodymask != 0u ? 1 : 0);
+  if (n_bodies < 0) bodymask = e->model_term_bodymask;
+  if (term_mode != e->hm.term_mode || bodymask != e->hm.term_bodymask) {   // the device model changes: no launch may be reading it
+    HIP_TRY(hipSetDevice(e->device));
+    int rc = join_ranges(e, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    e->hm.term_mode = term_mode; e->hm.term_bodymask = bodymask;
+    HIP_TRY(hipMemcpy(e->d_model, &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
+  }
+  const int posture = (min_up > -1.f ? 1 : 0) | (min_height > 0.f ? 2 : 0);
+  const bool on = posture != 0 || n_bodies >= 0;   // everything off: the model's own list, no cause bookkeeping
+  e->fall_min_up = min_up; e->fall_min_height = min_height; e->fall_grace = grace_steps;
+  e->fall_mask = on ? (posture | (term_mode == 1 ? 4 : 0)) : 0;
   return COSIM_OK;
 }
 

@@ -86,6 +86,11 @@ struct KArgs {
   int spawn_rows;
   int spawn_mode;         // 0: row = global env id mod rows; 1: a draw per episode (purpose 5)
   unsigned spawn_off;     // env_id0 mod spawn_rows, so that mode 0 needs no 64-bit division: row = (spawn_off + env) mod rows
+  // fall rules (cosim_fall_set): evaluated once per control step on the end-of-step pose; fall_mask 0 = no rule, meta[15] is not written
+  float fall_min_up;      // tilt: ends the episode when 1 - 2 (qx^2 + qy^2) < fall_min_up
+  float fall_min_height;  // height: ends it when qpos[2] - ground < fall_min_height
+  int fall_grace;         // the posture rules hold from episode step fall_grace + 1 on
+  int fall_mask;          // 1 tilt | 2 height | 4 a body-contact list is in force (DevModel::term_mode 1) and its hits are recorded
 };
 
 // ------------------------------------------------------------------------------------------------ wave helpers
@@ -2858,6 +2863,35 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
       bad = grp_ballot<LW>(nf_, hb) != 0ull;
     }
     if (sim_step == ob.max_sim_step) truncated = 1;
+    // ---- fall rules (cosim_fall_set): posture of the end-of-step state, before any reset.  Every lane of the env's group reads the
+    // same three LDS words and takes the same branches.  Up to here only the body-contact ballot above has set `terminated`.
+    const int fall_mask = A.fall_mask;
+    if (fall_mask != 0) {
+      int cause = terminated ? 4 : 0;
+      if (sim_step > A.fall_grace) {   // the episode clock is 1 on the first step after a reset
+        const float qx = S.qpos[4], qy = S.qpos[5];
+        // world-z component of the base's z axis from the quaternion as stored; the roundings are pinned (no FMA contraction) so that
+        // the numpy twin (cosim_amd/fall.py) repeats them.  NaN compares false: the non-finite check owns that case
+        const float up = __fsub_rn(1.f, __fmul_rn(2.f, __fadd_rn(__fmul_rn(qx, qx), __fmul_rn(qy, qy))));
+        if ((fall_mask & 1) && up < A.fall_min_up) cause |= 1;
+        if (fall_mask & 2) {
+          float ground = dm.ground_pos[2];
+          bool inside = true;
+          if constexpr (HF) {   // the terrain under the base, looked up as the height-map observation does (origin under the base)
+            Terrain T;
+            T.data = A.hfield; T.mip = A.hfield_mip; T.nrow = dm.hfield_nrow; T.ncol = dm.hfield_ncol;
+            T.sx = dm.hfield_size[0]; T.sy = dm.hfield_size[1]; T.sz = dm.hfield_size[2]; T.gz = dm.ground_pos[2];
+            T.ox = (double)S.qpos[0] - (double)dm.ground_pos[0]; T.oy = (double)S.qpos[1] - (double)dm.ground_pos[1];
+            T.dx = 2.0 * (double)T.sx / (double)(T.ncol - 1); T.dy = 2.0 * (double)T.sy / (double)(T.nrow - 1);
+            ground = terrain_height(T, 0.f, 0.f, inside);
+          }
+          if (inside && S.qpos[2] - ground < A.fall_min_height) cause |= 2;   // off the field: no verdict
+        }
+      }
+      if (cause & 3) terminated = 1;
+      // the cause of this episode end into meta[15]: 0 for a time limit or a non-finite state (cosim_dev.h)
+      if (lane == 0 && (terminated || truncated || bad)) meta[15] = bad ? 0 : cause;
+    }
     if (bad) terminated = 1;
     do_reset = bad || ((terminated || truncated) && ob.auto_reset);
   }

@@ -20,14 +20,15 @@
 namespace cosim {
 
 constexpr int LEDGER_NSUM = 6, LEDGER_NINT = 6, LEDGER_WORDS = 16;
-enum { LEDGER_TERMINATED = 1, LEDGER_TRUNCATED = 2, LEDGER_NONFINITE = 4, LEDGER_NO_RESET = 8, LEDGER_OPEN = 16 };
+enum { LEDGER_TERMINATED = 1, LEDGER_TRUNCATED = 2, LEDGER_NONFINITE = 4, LEDGER_NO_RESET = 8, LEDGER_OPEN = 16,
+       LEDGER_FELL_TILT = 32, LEDGER_FELL_HEIGHT = 64, LEDGER_FELL_CONTACT = 128 };   // (meta word 15 & 7) << 5
 
 struct LedgerArgs {
   const float* info;       // [K][N][info_dim] the caller's info rows
   const uint8_t* term;     // [K][N]
   const uint8_t* trunc;    // [K][N]
   const float* cmd;        // [N][cmd_stride] raw user commands, or null with ncmd 0
-  const float* state;      // [N][s_stride] live state records (meta words 4 and 14 are read)
+  const float* state;      // [N][s_stride] live state records (meta words 4, 14 and 15 are read)
   double* sum;
   float* peak;
   int* acc;
@@ -38,6 +39,7 @@ struct LedgerArgs {
   int n_envs, first, count, rows;   // rows: K
   int info_dim, nu, ncmd, cmd_stride, s_stride, s_meta, slots, spawn_rows;
   int flag;                // begin: open flags of the new episode
+  int fall;                // a fall rule is set (cosim_fall_set): meta word 15 holds the cause of the env's latest episode end
   const int* scn_row;      // [N] rows the scenario kernel wrote ahead of this step, or null: no table (word 13 stays 0)
   int scn_rows, scn_mode;
   unsigned scn_off;
@@ -73,9 +75,11 @@ __device__ __forceinline__ void ledger_step_body(const LedgerArgs& a) {
   int length = a.acc[env], seen = a.acc[N + env], episode = a.acc[2 * N + env], oflags = a.acc[3 * N + env], spawn = a.acc[4 * N + env],
       nan0 = a.acc[5 * N + env];
   // the meta words as the range's last launch left them: [4] has advanced if a non-finite state reset the env, [14] is already the
-  // row of the episode an auto-reset began
+  // row of the episode an auto-reset began, [15] is the cause of the latest episode end (like the other two exact per launch, not per
+  // row of a rollout; with no fall rule the word is not read: a rule that was set and cleared may have left one behind)
   const int* meta = reinterpret_cast<const int*>(a.state + (size_t)env * a.s_stride + a.s_meta);
   const int nan_now = meta[4], spawn_now = a.spawn_rows > 0 ? meta[14] : -1;
+  const int fell = a.fall ? (meta[15] & 7) << 5 : 0;
   const int scn = SCN ? a.scn_row[env] + 1 : 0;
   float c[3] = {0.f, 0.f, 0.f};
   for (int k = 0; k < 3; k++)
@@ -105,7 +109,7 @@ __device__ __forceinline__ void ledger_step_body(const LedgerArgs& a) {
     if (a.ncmd > 0) pk_tr = fmaxf(pk_tr, e0);
     const int te = a.term[r] != 0, tr = a.trunc[r] != 0;
     if (te | tr) {
-      const int flags = (te ? LEDGER_TERMINATED : 0) | (tr ? LEDGER_TRUNCATED : 0) | (nan_now != nan0 ? LEDGER_NONFINITE : 0) | oflags;
+      const int flags = (te ? LEDGER_TERMINATED : 0) | (tr ? LEDGER_TRUNCATED : 0) | (nan_now != nan0 ? LEDGER_NONFINITE : 0) | oflags | fell;
       ledger_store(a.rec + ((size_t)env * a.slots + (size_t)(episode % a.slots)) * LEDGER_WORDS, episode, length, flags, spawn, seen, s,
                    pk_tq, pk_tr, scn);
       episode++;

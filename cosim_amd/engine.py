@@ -109,6 +109,7 @@ def load_library():
     L.cosim_ledger_set.argtypes = [vp, ci]
     L.cosim_ledger_get.argtypes = [vp, vp, vp, vp, vp]
     L.cosim_scenario_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
+    L.cosim_fall_set.argtypes = [vp, ctypes.c_float, ctypes.c_float, ci, vp, ci]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
     L.cosim_set_timing.argtypes = [vp, ci]
@@ -119,7 +120,7 @@ def load_library():
                "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
                "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
                "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get",
-               "cosim_scenario_set"):
+               "cosim_scenario_set", "cosim_fall_set"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -134,7 +135,7 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
            "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
            "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
-           "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set"]
+           "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -336,6 +337,16 @@ class Engine:
             raise ValueError(f"scenario_set: the table arrays are shorter than their row addresses ({nk} keyframes, {npw} push windows)")
         self._check(self.L.cosim_scenario_set(self.h, int(ka.size) - 1, ka.ctypes.data, kt.ctypes.data, kc.ctypes.data, pa.ctypes.data,
                                               pt.ctypes.data, pv.ctypes.data, int(mode), cmd_out_ptr, row_out_ptr, stream))
+
+    def fall_set(self, min_up: float, min_height: float, grace_steps: int, body_ids=None):
+        """``cosim_fall_set``: ``min_up <= -1`` / ``min_height <= 0`` switch the tilt / height rule off; ``body_ids`` ``None`` leaves the
+        model's own ``_is_done`` list alone, an int array (possibly empty) replaces it."""
+        if body_ids is None:
+            self._check(self.L.cosim_fall_set(self.h, ctypes.c_float(min_up), ctypes.c_float(min_height), int(grace_steps), None, -1))
+            return
+        ids = np.ascontiguousarray(body_ids, dtype=np.int32).reshape(-1)
+        self._check(self.L.cosim_fall_set(self.h, ctypes.c_float(min_up), ctypes.c_float(min_height), int(grace_steps),
+                                          ids.ctypes.data if ids.size else None, int(ids.size)))
 
     def debug_forward(self, env: int) -> np.ndarray:
         out = np.zeros(8192, dtype=np.float32)

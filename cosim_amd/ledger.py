@@ -14,6 +14,8 @@ import numpy as np
 
 WORDS = 16
 TERMINATED, TRUNCATED, NONFINITE, NO_RESET, OPEN = 1, 2, 4, 8, 16
+FELL_TILT, FELL_HEIGHT, FELL_CONTACT = 32, 64, 128   # a fall rule ended the episode (cosim_amd/fall.py): (cause & 7) << 5
+FELL = FELL_TILT | FELL_HEIGHT | FELL_CONTACT
 INT_FIELDS = {"episode": 0, "length": 1, "flags": 2, "spawn_row": 3, "steps_seen": 4}
 FLOAT_FIELDS = {"mean_action_diff_RMSE": 5, "mean_tracking_err_0": 6, "mean_tracking_err_1": 7, "mean_tracking_err_2": 8,
                 "mean_abs_torque": 9, "peak_abs_torque": 10, "mean_lin_vel_x": 11, "peak_tracking_err_0": 12}
@@ -72,7 +74,9 @@ class EpisodeLedger:
         f, n = self.flags[m], self.length[m].astype(np.int64)
         return {"episodes": int(m.sum()), "terminated": int(((f & TERMINATED) != 0).sum()), "truncated": int(((f & TRUNCATED) != 0).sum()),
                 "non_finite": int(((f & NONFINITE) != 0).sum()), "no_reset_start": int(((f & NO_RESET) != 0).sum()),
-                "length_sum": int(n.sum()), "lost": int(self.lost.sum())}
+                "length_sum": int(n.sum()), "lost": int(self.lost.sum()),
+                "fell": int(((f & FELL) != 0).sum()), "fell_tilt": int(((f & FELL_TILT) != 0).sum()),
+                "fell_height": int(((f & FELL_HEIGHT) != 0).sum()), "fell_contact": int(((f & FELL_CONTACT) != 0).sum())}
 
     def summary(self) -> dict:
         """Episodes, how they ended, length quantiles (control steps) and the means over episodes of the record means (non-finite
@@ -84,6 +88,7 @@ class EpisodeLedger:
         out["length"] = ({"mean": float(n.mean()), "min": int(n.min()), "p25": float(np.quantile(n, 0.25)), "p50": float(np.quantile(n, 0.5)),
                           "p75": float(np.quantile(n, 0.75)), "max": int(n.max())} if e else None)
         out["terminated_share"] = out["terminated"] / e if e else None
+        out["fell_share"] = out["fell"] / e if e else None
         means, skipped = {}, 0
         for name in FLOAT_FIELDS:
             v = getattr(self, name)[m].astype(np.float64)
@@ -94,21 +99,32 @@ class EpisodeLedger:
         out["non_finite_records"] = skipped
         return out
 
-    def by_spawn_row(self) -> dict:
-        """Per spawn-table row (``-1``: no table): ended episodes that started there and the share of them that terminated."""
+    def _with_fell(self, fell: Optional[bool]) -> bool:
+        """Whether the per-row tables carry the ``fell`` columns: asked for, or (``None``) some ended record has a fall flag.  A
+        ledger kept without a fall rule so keeps the tables it had before there were rules."""
+        return bool(fell) if fell is not None else bool(((self.flags[self.ended()] & FELL) != 0).any())
+
+    def by_spawn_row(self, fell: Optional[bool] = None) -> dict:
+        """Per spawn-table row (``-1``: no table): ended episodes that started there and the share of them that terminated; with
+        ``fell`` (default: if any record has a fall flag) also the count and share a fall rule ended (flags 32 / 64 / 128)."""
+        with_fell = self._with_fell(fell)
         m = self.ended()
-        rows, term = self.spawn_row[m], (self.flags[m] & TERMINATED) != 0
+        rows, term, fallen = self.spawn_row[m], (self.flags[m] & TERMINATED) != 0, (self.flags[m] & FELL) != 0
         out = {}
         for r in np.unique(rows):
             sel = rows == r
             out[int(r)] = {"episodes": int(sel.sum()), "terminated": int(term[sel].sum()), "terminated_share": float(term[sel].mean())}
+            if with_fell:
+                out[int(r)].update({"fell": int(fallen[sel].sum()), "fell_share": float(fallen[sel].mean())})
         return out
 
-    def by_scenario(self) -> dict:
-        """Per scenario-table row (``-1``: no table): ended episodes that ran it, the share of them that terminated, length
+    def by_scenario(self, fell: Optional[bool] = None) -> dict:
+        """Per scenario-table row (``-1``: no table): ended episodes that ran it, the share of them that terminated -- with ``fell``
+        (default: if any record has a fall flag) also the count and share a fall rule ended --, length
         quantiles (control steps) and the means over those episodes of the record means (non-finite records left out)."""
         m = self.ended()
         rows, term, n = self.scenario[m], (self.flags[m] & TERMINATED) != 0, self.length[m].astype(np.float64)
+        fallen, with_fell = (self.flags[m] & FELL) != 0, self._with_fell(fell)
         out = {}
         for r in np.unique(rows):
             sel = rows == r
@@ -118,6 +134,7 @@ class EpisodeLedger:
                 ok = np.isfinite(v)
                 means[name] = float(v[ok].mean()) if ok.any() else None
             out[int(r)] = {"episodes": int(sel.sum()), "terminated": int(term[sel].sum()), "terminated_share": float(term[sel].mean()),
+                           **({"fell": int(fallen[sel].sum()), "fell_share": float(fallen[sel].mean())} if with_fell else {}),
                            "length": {"mean": float(n[sel].mean()), "min": int(n[sel].min()), "p50": float(np.quantile(n[sel], 0.5)),
                                       "max": int(n[sel].max())},
                            "means": means}
@@ -151,7 +168,7 @@ def _records(episode, length, flags, spawn, seen, s, peak, scenario=None) -> np.
 
 def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spawn_rows, slots: int, nu: int, command_dim: int,
                      include_open: bool = False, initial_flags: int = 0, begins: Sequence = (), env_id0: int = 0, scenario_rows=None,
-                     open_scenario_rows=None) -> EpisodeLedger:
+                     open_scenario_rows=None, causes=None) -> EpisodeLedger:
     """Numpy twin of ``ledger_step_kernel`` / ``ledger_begin_kernel`` / ``ledger_open_kernel``: sequential float64 adds of float32
     values, float32 subtraction / sum / divide where the kernel does them in float32, ``np.fmax`` for the peaks.
 
@@ -163,7 +180,9 @@ def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spa
     8) of the masked envs before step k (k = K: after the last step).  ``scenario_rows`` ``[K, N]`` (a scenario table was set): the
     row each env ran in step k (``BatchedEnv.scenario_rows()`` after the step) -- word 13 of a record that step k closes is that
     row + 1; ``commands`` is then the per-step applied command.  ``open_scenario_rows`` ``[N]``: the rows of the open records (the
-    table's rule at the meta words after the last step)."""
+    table's rule at the meta words after the last step).  ``causes`` ``[K, N]`` (a fall rule was set, cosim_amd/fall.py): the
+    engine's meta word 15 after step k (``BatchedEnv.end_cause()``) -- a record that step k closes gets ``(cause & 7) << 5`` in
+    its flags; ``None`` (no rule): the records of a ledger without fall rules, bit for bit."""
     info = np.asarray(info_rows, dtype=np.float32)
     K, N = info.shape[0], info.shape[1]
     te_all, tr_all = np.asarray(terminated).reshape(K, N), np.asarray(truncated).reshape(K, N)
@@ -173,6 +192,7 @@ def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spa
     spawn_all = np.full((K + 1, N), -1, dtype=np.int32) if spawn_rows is None else np.asarray(spawn_rows, dtype=np.int32).reshape(K + 1, N)
     slots = int(slots)
     scn_all = None if scenario_rows is None else np.asarray(scenario_rows, dtype=np.int32).reshape(K, N)
+    cause_all = None if causes is None else np.asarray(causes, dtype=np.int32).reshape(K, N)
     s = np.zeros((NSUM, N), dtype=np.float64)
     peak = np.zeros((2, N), dtype=np.float32)
     length, seen, episode = (np.zeros(N, dtype=np.int32) for _ in range(3))
@@ -223,6 +243,8 @@ def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spa
             if done.any():
                 i = np.nonzero(done)[0]
                 flags = (te[i] * TERMINATED) | (tr[i] * TRUNCATED) | ((nan_all[k + 1][i] != nan0[i]) * NONFINITE) | oflags[i]
+                if cause_all is not None:
+                    flags = flags | ((cause_all[k][i] & 7) << 5)
                 ring[i, episode[i] % slots] = _records(episode[i], length[i], flags.astype(np.int32), spawn[i], seen[i], s[:, i], peak[:, i],
                                                          None if scn_all is None else scn_all[k][i])
                 episode[i] += 1

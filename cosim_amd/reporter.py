@@ -165,15 +165,16 @@ class FleetReporter:
         return out
 
     def episodes(self) -> dict:
-        """The env's episode ledger (``BatchedEnv(ledger=SLOTS)``) summarised: ``EpisodeLedger.summary()`` plus the per-spawn-row
-        counts.  Under ``torch.distributed`` the integer counts and the length sum are all-reduced (``fleet``); the records, and so
+        """The env's episode ledger (``BatchedEnv(ledger=SLOTS)``) summarised: ``EpisodeLedger.summary()`` -- the ``fell`` counts per cause of a
+        fall rule among it -- plus the per-spawn-row counts.  Under ``torch.distributed`` the integer counts and the length sum are all-reduced (``fleet``); the records, and so
         the quantiles and the means of record means, stay this rank's."""
         import torch.distributed as dist
         led = self.env.ledger()
         out = led.summary()
-        out["by_spawn_row"] = {str(k): v for k, v in led.by_spawn_row().items()}
+        fell = True if getattr(self.env, "fall_rule", None) is not None else None   # a fall rule is set: the fell columns, zeros included
+        out["by_spawn_row"] = {str(k): v for k, v in led.by_spawn_row(fell).items()}
         if getattr(self.env, "scenario_table", None) is not None:
-            out["by_scenario"] = {str(k): v for k, v in led.by_scenario().items()}
+            out["by_scenario"] = {str(k): v for k, v in led.by_scenario(fell).items()}
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             t = self.env.torch
             c = led.counts()

@@ -179,7 +179,8 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
  * per-env counters, among them [8] contacts left out, [10] most contacts in one substep, [12] fix-up passes -- control steps redone
  * by a large-capacity kernel; on the split pipeline with "hfield_fixup", substeps (the unit that pipeline redoes) -- and [13] prism
  * walks cut at their bound (solver_stats() in cosim_amd/batched_env.py sums them), [14] the spawn-table row the env's last reset
- * took its base pose from (cosim_spawn_set; written only while a table is set), [15] unused. */
+ * took its base pose from (cosim_spawn_set; written only while a table is set), [15] the cause of the env's latest episode end
+ * (cosim_fall_set; written only while a fall rule is set). */
 int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream);
 /* Test / checkpoint hook: overwrite "qpos"/"qvel"/"qacc_warmstart" from a device buffer. */
 int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* stream);
@@ -238,12 +239,14 @@ int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago
  * word 14 (the auto-reset has written the new episode's row), nan_resets base = meta word 4.  Record, 16 int32 words:
  *   [0] episode ordinal of this env since cosim_ledger_set (0-based)   [1] length in control steps
  *   [2] flags: 1 terminated, 2 truncated, 4 meta word 4 advanced during the episode (a non-finite state reset the env), 8 the episode
- *       did not begin at a reset (cosim_restore / cosim_set / a ledger set on a stepped fleet), 16 still open (open_dev rows only)
+ *       did not begin at a reset (cosim_restore / cosim_set / a ledger set on a stepped fleet), 16 still open (open_dev rows only),
+ *       32 / 64 / 128 a fall rule ended it: tilt / height / body contact = (meta word 15 & 7) << 5, read while a rule is set
+ *       (cosim_fall_set) behind the step that closed the record; 0 with no rule
  *   [3] spawn-table row the episode started from (-1 with no table)    [4] steps_seen: rows of this env since cosim_ledger_set
  *   float32 bits: [5] mean action_diff_RMSE  [6..8] mean tracking error i (0 beyond command_dim)  [9] mean abs torque
  *   [10] peak abs torque  [11] mean lin_vel_x  [12] peak tracking error 0;   [13] scenario row + 1 (0: no scenario table)   [14..15] 0.   Means are (float)(sum / (double)length).
  * A rollout's kernel sees the meta words as the launch left them: with several episodes of an env ending inside one cosim_rollout,
- * flag 4 and the spawn row are exact per launch, not per row.
+ * flag 4, the spawn row and the fall cause (flags 32 / 64 / 128) are exact per launch, not per row.
  * cosim_reset begins a new episode for its mask's envs and discards what they had open (an episode the host cut is no outcome);
  * cosim_restore does so for the envs it restored, cosim_set for all envs, both with flag 8.  An episode "ends" whenever a step
  * returns a flag: without auto-reset a termination that persists yields one-step episodes.  cosim_profile_step does not feed the
@@ -287,6 +290,29 @@ int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_de
 int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, const int32_t* key_t, const float* key_cmd,
                        const int32_t* push_adr, const int32_t* push_t, const float* push_v, int mode,
                        float* cmd_out_dev /*[N][command_dim]*/, int32_t* row_out_dev /*[N]*/, void* stream);
+
+/* Fall rules (the reference ends an episode early only through a robot's own _is_done, which is an empty body list for
+ * flamingo_light_v1 and False for w4_p_v2 and humanoid_p_v0): the step kernels end an episode on the posture of the state a control
+ * step ends in, per cause.  Evaluated once per control step (every step of a rollout launch, the last substep launch of the split
+ * pipeline, the fix-up kernels), before the info row, the auto-reset and the reset observation, so a fall is an episode end like any
+ * other: terminated = 1, the info row of the fallen step, the reset state vector, meta word 11, the ledger, scenario mode "cycle".
+ *   tilt (cause bit 1):   up = 1 - 2 (qx^2 + qy^2) of qpos[3:7] as stored (the world-z component of the base's z axis) < min_up, so
+ *                         min_up = cos(max tilt); min_up <= -1 switches the rule off;
+ *   height (cause bit 2): qpos[2] - ground < min_height; ground = the plane's z, or the heightfield's elevation under the base (the
+ *                         height-map observation's lookup; off the field the rule does not fire); min_height <= 0 switches it off;
+ *   body contact (bit 4): the robot's _is_done rule (cfrc_ext of the listed bodies, any signed component > 1.0).  n_bodies < 0 leaves
+ *                         the model's own list alone; n_bodies >= 0 replaces it by body_ids (0 bodies: no body rule) in the device
+ *                         model, which is uploaded again (the call blocks until the device is idle).
+ * Tilt and height hold only while the episode clock (meta word 0, 1 on the first step after a reset) is > grace_steps; the body rule
+ * is the model's block unchanged and knows no grace.  NaN compares false: a non-finite state is the non-finite check's case.  While
+ * any rule is set, every episode end writes its cause into meta word 15 (the OR of the bits; 0 for a time limit, a non-finite state
+ * or no rule firing), and bit 4 is recorded for the model's own list too.  min_up <= -1, min_height <= 0 and n_bodies < 0 together
+ * switch everything off: the model's own list is restored and meta word 15 is no longer written (no launch then differs from an
+ * engine that never had a rule).  COSIM_EINVAL, naming the value: body id 0 (the world) or >= nbody, grace_steps < 0, a non-finite
+ * threshold.  cosim_query "fall" answers the mask of rules in force (1 | 2 | 4, 0 for none).
+ * The thresholds travel as kernel arguments: a captured graph keeps the values it was captured with.  Set the rule before capturing.
+ * The rule is not part of a snapshot row (the cause word is, like every meta word). */
+int cosim_fall_set(cosim_engine_t* e, float min_up, float min_height, int grace_steps, const int32_t* body_ids, int n_bodies);
 
 /* Spawn table (no reference counterpart: the reference resets its one robot to the model's init_qpos).  M = `rows` base poses
  * spread over the terrain; every reset -- cosim_reset, the auto-reset inside every step / rollout / fix-up kernel, the reset after a
