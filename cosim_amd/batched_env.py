@@ -85,7 +85,7 @@ class BatchedEnv:
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
                  spawn=None, history=None, ledger: Optional[int] = None, scenarios=None, scenario_mode: Optional[str] = None,
-                 fall=None):
+                 fall=None, failure_traces=None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -116,7 +116,12 @@ class BatchedEnv:
 
         ``fall``: a fall rule -- a ``FallRule`` or a dict ``{"tilt", "height", "grace", "bodies"}`` (``cosim_amd/fall.py``) -- see
         ``set_fall``.  Default: ``config["engine"].get("fall")`` / none: an episode ends early only through the robot's own
-        ``_is_done``."""
+        ``_is_done``.
+
+        ``failure_traces``: ``(frames, keep)`` or ``{"frames", "keep", "on"}`` -- the engine keeps every env's last ``frames``
+        control steps and freezes them as a trace when an episode ends with a selected cause (``cosim_ftrace_set``), see
+        ``set_failure_traces`` / ``failure_traces()``.  Default: ``config["engine"].get("failure_traces")`` / none; ``False``: none
+        whatever the config says."""
         import torch  # plumbing only
 
         eng_cfg = config.get("engine", {})
@@ -238,6 +243,10 @@ class BatchedEnv:
         ledger = ledger if ledger is not None else eng_cfg.get("ledger")
         if ledger is not None and int(ledger) != 0:
             self.set_ledger(int(ledger))
+        self.failure_traces_cfg = None
+        failure_traces = failure_traces if failure_traces is not None else eng_cfg.get("failure_traces")
+        if failure_traces is not None and failure_traces is not False:   # False: off whatever the config says
+            self.set_failure_traces(failure_traces)
         self.scenario_table, self.scenario_mode = None, "env"
         self._cmd_out = self._row_out = None
         scenarios = scenarios if scenarios is not None else eng_cfg.get("scenarios")
@@ -321,6 +330,8 @@ class BatchedEnv:
         assert self.reset_flag is True, "Call 'reset()' before calling 'step()'."
         if self.scenario_table is not None:
             raise ValueError("rollout(): a scenario table is set and one rollout launch reads one command row; step() or set_scenarios(None)")
+        if self.failure_traces_cfg is not None:
+            raise ValueError("rollout(): failure traces are set and one rollout launch leaves one state record for all its steps; step() or set_failure_traces(None)")
         if self.ledger_slots > 0 and not info:
             raise ValueError("rollout(info=False): a ledger is set and is built from the info rows; pass info=True or set_ledger(0)")
         t = self.torch
@@ -532,6 +543,50 @@ class BatchedEnv:
         self.engine.ledger_get(rec.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
         t.cuda.current_stream(self.device).synchronize()
         return EpisodeLedger.from_raw(rec.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, self.env_id0)
+
+    # ------------------------------------------------------------------ failure traces (cosim_ftrace_set / cosim_ftrace_get)
+    def set_failure_traces(self, spec, on=None):
+        """Keep every env's last ``frames`` control steps on the device and freeze them as a trace when an episode ends with a
+        selected cause: ``spec`` is ``(frames, keep)`` or ``{"frames", "keep", "on"}`` (frames 1..1024, the ``keep`` 1..64 newest
+        traces per env stay), ``None`` switches the feature off and frees its buffers.  ``on``: names out of ``"terminated"``,
+        ``"truncated"``, ``"nonfinite"``, ``"tilt"``, ``"height"``, ``"contact"`` -- default ``("terminated", "nonfinite")``:
+        everything but a plain time limit.  A frame is one control step: the state it started from, the action, the applied command,
+        the info row and the flags (``cosim_amd/ftrace.py``); the engine copies it on every range's own stream, inside a captured
+        graph, under a deferred join, with no host read.  The ``action`` tensor of a step must stay untouched until that step has run
+        (it is read behind the step).  Every env starts in an empty window; ``reset()``, ``restore`` and ``set_state`` empty the
+        windows of the envs they touch.  Set traces and the ledger together (both in the constructor) and their episode ordinals
+        agree.  Limits: a scenario push applied ahead of a step shows in the next frame's state and in the info row, not in the
+        frame's own state; the pose a terminal step ends in is not captured (the last frame holds the pose one control step earlier
+        and the terminal info row); traces are not part of a ``snapshot()``; ``rollout()`` raises while traces are set.  Raises
+        ``ValueError`` naming the value out of range or the unknown name.  Blocks until the device is idle (it allocates)."""
+        from .ftrace import resolve
+        if spec is None:
+            self.engine.ftrace_set(0, 0, 0)
+            self.failure_traces_cfg = None
+            return
+        frames, keep, mask = resolve(spec, on)
+        self.failure_traces_cfg = None
+        self.engine.ftrace_set(frames, keep, mask)
+        self.failure_traces_cfg = (frames, keep, mask)
+
+    def failure_traces(self, include_open: bool = False):
+        """The fleet's kept traces as a ``FailureTraces`` (``cosim_amd/ftrace.py``): one row per trace, sorted by (global env id,
+        episode), with the frames in time order.  ``include_open``: also the windows still running (flag 16).  Joins the range
+        streams and reads the device once.  Raises ``ValueError`` if no traces are set."""
+        from .ftrace import HDR, FailureTraces
+        if self.failure_traces_cfg is None:
+            raise ValueError("failure_traces(): no failure traces are set (BatchedEnv(failure_traces=(FRAMES, KEEP)) or set_failure_traces)")
+        frames, keep, mask = self.failure_traces_cfg
+        t = self.torch
+        F = self.engine.query("ftrace_frame_words")
+        buf = t.empty((self.num_envs, keep + 1, HDR + frames * F), dtype=t.int32, device=self.device)
+        cnt = t.empty((self.num_envs, 3), dtype=t.int32, device=self.device)
+        opn = t.empty((self.num_envs, HDR), dtype=t.int32, device=self.device) if include_open else None
+        self.engine.ftrace_get(buf.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
+        t.cuda.current_stream(self.device).synchronize()
+        dims = {"nq": self.nq, "nv": self.nv, "nu": self.action_dim, "command_dim": self.command_dim, "info_dim": self.info_dim}
+        return FailureTraces.from_raw(buf.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, dims, mask,
+                                      self.env_id0)
 
     # ------------------------------------------------------------------ fall rules (cosim_fall_set)
     def set_fall(self, rule):

@@ -17,7 +17,7 @@ class SingleEnv:
     """N = 1 adapter over :class:`BatchedEnv` with the reference's ``BaseEnv`` semantics (wrappers.py:8-85)."""
 
     def __init__(self, config: dict):
-        self.env = BatchedEnv(config, num_envs=1, auto_reset=False, ledger=0)   # one env, flags read every step: no ledger
+        self.env = BatchedEnv(config, num_envs=1, auto_reset=False, ledger=0, failure_traces=False)   # one env, flags read every step: no ledger, no traces
         e = self.env
         self.config = config
         self.id, self.action_dim, self.state_dim = e.id, e.action_dim, e.state_dim

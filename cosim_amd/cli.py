@@ -4,6 +4,7 @@
         --policy sinusoid | random-mlp | path/to/actor.onnx  [--terrain rocky_hard] [--push-at 200 --push 0.5 0 0] \\
         [--report report.json] [--trace-env 0] [--checkpoint snap.npz --checkpoint-at 500] [--resume snap.npz [--fork-row 7]] \
         [--history 8 10] [--ledger 4 [--ledger-out episodes.npz]] [--scenarios tests.yaml [--scenario-mode env|cycle]] \
+        [--failure-traces 50 2 [--failure-traces-on terminated tilt] [--failure-traces-out traces.npz]] \
         [--fall-tilt 0.8 --fall-height 0.1 --fall-grace 5 --fall-bodies base_link,left_leg_link]
     python -m cosim_amd.cli --config session.yaml
 
@@ -97,6 +98,12 @@ def main(argv=None) -> int:
     ap.add_argument("--fall-height", type=float, default=None, metavar="M", help="fall rule: end an episode when the base is lower than this above the ground under it")
     ap.add_argument("--fall-grace", type=int, default=None, metavar="STEPS", help="fall rule: control steps at the start of an episode without the tilt / height test")
     ap.add_argument("--fall-bodies", default=None, metavar="a,b,c", help="fall rule: bodies whose contact force ends the episode (replaces the robot's own list)")
+    ap.add_argument("--failure-traces", type=int, nargs=2, default=None, metavar=("FRAMES", "KEEP"),
+                    help="keep every env's last FRAMES control steps on the device and freeze them as a trace when an episode ends with a "
+                         "selected cause; the KEEP newest traces per env stay (also under --graph / --pipelined)")
+    ap.add_argument("--failure-traces-on", nargs="+", default=None, metavar="NAME",
+                    help="causes that freeze a window: terminated truncated nonfinite tilt height contact (default: terminated nonfinite)")
+    ap.add_argument("--failure-traces-out", default=None, metavar="PATH.npz", help="with --failure-traces: write this rank's traces here")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -109,7 +116,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -189,6 +196,23 @@ def main(argv=None) -> int:
             FallRule.build(fall)
         except ValueError as e:
             ap.error(f"--fall-* / fall: {e}")
+    # failure traces: the session's value (top level or engine.failure_traces: [frames, keep] or a mapping), overridden by the flags
+    ftrace = sess.get("failure_traces") if sess.get("failure_traces") is not None else s_eng.get("failure_traces")
+    if ftrace is not None and not isinstance(ftrace, dict):
+        ftrace = {"frames": list(ftrace)[0], "keep": list(ftrace)[1]} if len(list(ftrace)) == 2 else ap.error("failure_traces: [FRAMES, KEEP] or a mapping")
+    ftrace = dict(ftrace or {})
+    if args.failure_traces is not None:
+        ftrace["frames"], ftrace["keep"] = args.failure_traces
+    if args.failure_traces_on is not None:
+        ftrace["on"] = list(args.failure_traces_on)
+    if (args.failure_traces_on is not None or args.failure_traces_out) and "frames" not in ftrace:
+        ap.error("--failure-traces-on / --failure-traces-out need --failure-traces FRAMES KEEP")
+    if ftrace:
+        from .ftrace import resolve as ftrace_resolve
+        try:
+            ftrace_resolve(ftrace)
+        except ValueError as e:
+            ap.error(f"--failure-traces / failure_traces: {e}")
     if args.history is not None and args.graph:
         ap.error("--history cannot be combined with --graph: a replayed graph would repeat the captured step's parity")
 
@@ -216,7 +240,7 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, failure_traces=ftrace or False, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:
@@ -285,6 +309,10 @@ def main(argv=None) -> int:
     if args.ledger_out:                                             # records stay per rank: one file each
         path = args.ledger_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.ledger_out)[:1], rank, os.path.splitext(args.ledger_out)[1])
         env.ledger().save(path)
+    traces = env.failure_traces() if ftrace else None                # traces stay per rank, like the ledger's records
+    if args.failure_traces_out:
+        path = args.failure_traces_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.failure_traces_out)[:1], rank, os.path.splitext(args.failure_traces_out)[1])
+        traces.save(path)
     if args.checkpoint and "checkpoint" not in used:
         print(f"warning: --checkpoint-at {args.checkpoint_at} was not reached, no snapshot written", file=sys.stderr)
     out = rep.save(args.report, extra={"snapshot": used} if used else None) if (args.report and rank == 0) else rep.summary()
@@ -296,6 +324,7 @@ def main(argv=None) -> int:
                           **({"episodes": {k: out["episodes"][k] for k in ("episodes", "terminated", "truncated", "non_finite", "lost", "length") +
                                            (("fell", "fell_tilt", "fell_height", "fell_contact") if env.fall_rule is not None else ())}}
                              if "episodes" in out else {}),
+                          **({"failure_traces": traces.summary()} if traces is not None else {}),
                           **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
                              if "by_scenario" in out.get("episodes", {}) else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}

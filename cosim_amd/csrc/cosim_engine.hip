@@ -16,6 +16,7 @@
 #include "cosim_spawn.hip"
 #include "cosim_snapshot.hip"
 #include "cosim_ledger.hip"
+#include "cosim_ftrace.hip"
 #include "cosim_scenario.hip"
 
 using namespace cosim;
@@ -144,6 +145,10 @@ struct cosim_engine {
   int* d_led_acc = nullptr;       // [LEDGER_NINT][n_envs]
   int* d_led_rec = nullptr;       // [n_envs][led_slots][16]
   int led_slots = 0;
+  // failure traces (cosim_ftrace_set, cosim_ftrace.hip): ftrace_step_kernel behind every range's last launch of a step, behind the ledger's
+  int* d_ft_buf = nullptr;        // [n_envs][ft_keep + 1][FT_HDR + ft_frames * F]
+  int* d_ft_cnt = nullptr;        // [n_envs][FT_NCNT]
+  int ft_frames = 0, ft_keep = 0, ft_mask = 0;
   bool stepped = false;           // stepped (or restored / overwritten) since the last whole-fleet reset: such an episode gets flag 8
   // scenario table (cosim_scenario_set, cosim_scenario.hip): scenario_step_kernel ahead of every range's first launch of a step / reset
   char* d_scn = nullptr;          // one allocation: key_adr | push_adr | key_t | push_t | key_cmd | push_v
@@ -641,6 +646,53 @@ static void ledger_free(cosim_engine* e) {
   e->d_led_sum = nullptr; e->d_led_peak = nullptr; e->d_led_acc = nullptr; e->d_led_rec = nullptr; e->led_slots = 0;
 }
 
+// ---- failure traces (cosim_ftrace.hip)
+static const char* const FTRACE_INFO_MSG =
+    ": failure traces are set (cosim_ftrace_set) and info_out_dev is NULL: a frame holds the step's info row; pass an info buffer or "
+    "switch the traces off";
+
+static int ftrace_words(const cosim_engine* e) {
+  return ftrace_frame_words(e->model.nq, e->model.nv, e->model.nu, e->ho.command_dim, e->ho.info_dim);
+}
+
+static FtArgs ftrace_args(cosim_engine* e) {
+  FtArgs a;
+  memset(&a, 0, sizeof a);
+  a.state = e->d_state; a.buf = e->d_ft_buf; a.cnt = e->d_ft_cnt;
+  a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
+  a.nq = e->model.nq; a.nv = e->model.nv; a.nu = e->model.nu; a.cd = e->ho.command_dim; a.info_dim = e->ho.info_dim; a.F = ftrace_words(e);
+  a.s_stride = e->lay.s_stride; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.s_meta = e->lay.s_meta;
+  a.frames = e->ft_frames; a.keep = e->ft_keep; a.on_mask = e->ft_mask; a.spawn_rows = e->spawn_rows; a.fall = e->fall_mask != 0;
+  if (e->scn.n_scn > 0) { a.scn_row = e->scn_row_out; a.scn_rows = e->scn.n_scn; a.scn_mode = e->scn.mode; a.scn_off = e->scn.gid_off; }
+  return a;
+}
+
+// this step's frame of envs [first, first + count), behind the launches that wrote the step's outputs on the same stream
+static int ftrace_step(cosim_engine* e, int first, int count, const float* actions, const float* cmd, const float* info, const uint8_t* term,
+                       const uint8_t* trunc, hipStream_t s) {
+  FtArgs a = ftrace_args(e);
+  a.actions = actions; a.cmd = a.cd > 0 ? cmd : nullptr; a.info = info; a.term = term; a.trunc = trunc;
+  a.first = first; a.count = count;
+  hipLaunchKernelGGL(ftrace_step_kernel, dim3(count), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode in an empty window
+static int ftrace_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
+  if (e->ft_frames <= 0) return COSIM_OK;
+  FtArgs a = ftrace_args(e);
+  a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
+  hipLaunchKernelGGL(ftrace_begin_kernel, dim3(e->n_envs), dim3(64), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+static void ftrace_free(cosim_engine* e) {
+  (void)hipFree(e->d_ft_buf); (void)hipFree(e->d_ft_cnt);
+  e->d_ft_buf = nullptr; e->d_ft_cnt = nullptr; e->ft_frames = 0; e->ft_keep = 0; e->ft_mask = 0;
+}
+
 extern "C" {
 
 // Fused actor MLP (cosim_mlp.hip): out = clip(act_L(... act_1(x W_1^T + b_1) ...)).  All pointers are device pointers; dims has
@@ -932,6 +984,7 @@ int cosim_destroy(cosim_engine_t* e) {
   hipFree(e->d_spawn);
   hipFree(e->d_hist); hipFree(e->d_snap_err);
   ledger_free(e);
+  ftrace_free(e);
   scenario_free(e);
   if (e->h_snap_err) hipHostFree(e->h_snap_err);
   hipFree(e->d_pairs); hipFree(e->d_gext); hipFree(e->d_ovf); hipFree(e->d_xcon); hipFree(e->d_xcnt); hipFree(e->d_xstate);
@@ -986,6 +1039,10 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "history_slots") return e->hist_slots;
   if (n == "history_every") return e->hist_every;
   if (n == "ledger_slots") return e->led_slots;   // records per env the episode ledger keeps (0: no ledger, no ledger launches)
+  if (n == "ftrace_frames") return e->ft_frames;  // frames per failure-trace window (0: no traces, no trace launches)
+  if (n == "ftrace_keep") return e->ft_keep;      // traces kept per env
+  if (n == "ftrace_frame_words") return ftrace_words(e);   // F: 32-bit words of a frame for this model (answered with traces off too)
+  if (n == "ftrace_mask") return e->ft_mask;      // ledger flags that freeze a window
   if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
   if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
   if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
@@ -1147,7 +1204,9 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   else (e->epw == 2 ? e->launch2 : e->launch)(e, a, e->n_envs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   if (mask_dev == nullptr) e->stepped = false;
-  return ledger_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);   // behind the reset: meta[14] is the new episode's spawn row
+  rc = ledger_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);   // behind the reset: meta[14] is the new episode's spawn row
+  if (rc) return rc;
+  return ftrace_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* commands_dev, float* state_out_dev, uint8_t* terminated_dev,
@@ -1215,6 +1274,8 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
   if (!e->launch_roll || e->epw != 1) return fail(COSIM_EINVAL, "cosim_rollout: no rollout kernel for this model / terrain / kernel variant");
   if (e->ho.command_dim > 0 && !commands_dev) return fail(COSIM_EINVAL, "cosim_rollout: commands_dev is required when command_dim > 0");
   if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_rollout") + LEDGER_INFO_MSG);
+  if (e->ft_frames > 0)
+    return fail(COSIM_EINVAL, "cosim_rollout: failure traces are set (cosim_ftrace_set): one launch leaves one state record for all its steps, so the per-step state is not there to copy; step with cosim_step or switch the traces off");
   if (e->scn.n_scn > 0)
     return fail(COSIM_EINVAL, "cosim_rollout: a scenario table is set (cosim_scenario_set): one launch reads one command row; step with cosim_step or clear the table");
   e->stepped = true;
@@ -1315,6 +1376,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   if (first < 0 || count < 1 || first + count > e->n_envs) return fail(COSIM_EINVAL, "cosim_step_range: range outside the fleet");
   if (e->epw == 2 && ((first | count) & 1)) return fail(COSIM_EINVAL, "cosim_step_range: two-environments-per-wave kernel needs even ranges");
   if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + LEDGER_INFO_MSG);
+  if (e->ft_frames > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + FTRACE_INFO_MSG);
   e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
@@ -1364,7 +1426,9 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     HIP_TRY(hipGetLastError());
   }
   // episode ledger: this step's rows of the range, behind the range's last launch of the step (plain device work: capturable)
-  if (e->led_slots > 0) return ledger_step(e, first, count, 1, info_out_dev, terminated_dev, truncated_dev, scenario_cmd(e, commands_dev), s);
+  if (e->led_slots > 0) { rc = ledger_step(e, first, count, 1, info_out_dev, terminated_dev, truncated_dev, scenario_cmd(e, commands_dev), s); if (rc) return rc; }
+  // failure traces: this step's frame of the range, behind the ledger's launch (reads the caller's action rows: they outlive the step)
+  if (e->ft_frames > 0) return ftrace_step(e, first, count, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
   return COSIM_OK;
 }
 
@@ -1511,7 +1575,9 @@ int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* st
   HIP_TRY(hipMemcpy2DAsync(e->d_state + off, e->lay.s_stride * sizeof(float), in_dev, width * sizeof(float), width * sizeof(float),
                            e->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   e->stepped = true;
-  return ledger_begin(e, nullptr, nullptr, 0, LEDGER_NO_RESET, (hipStream_t)stream);
+  rc = ledger_begin(e, nullptr, nullptr, 0, LEDGER_NO_RESET, (hipStream_t)stream);
+  if (rc) return rc;
+  return ftrace_begin(e, nullptr, nullptr, 0, FT_NO_RESET, (hipStream_t)stream);
 }
 
 int cosim_snapshot(cosim_engine_t* e, float* out_dev, void* stream) {
@@ -1560,6 +1626,8 @@ int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const
   if (with_params) e->params_mirror_stale = true;
   e->stepped = true;
   rc = ledger_begin(e, mask_dev, src_index_dev, snap_rows, LEDGER_NO_RESET, cs);
+  if (rc) return rc;
+  rc = ftrace_begin(e, mask_dev, src_index_dev, snap_rows, FT_NO_RESET, cs);
   if (rc) return rc;
   if (src_index_dev && cap == hipStreamCaptureStatusNone) {   // the kernel skipped what it refused; report it
     HIP_TRY(hipMemcpyAsync(e->h_snap_err, e->d_snap_err, 2 * sizeof(int), hipMemcpyDeviceToHost, cs));
@@ -1641,6 +1709,60 @@ int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_de
     LedgerArgs a = ledger_args(e);
     a.rec = open_dev;
     hipLaunchKernelGGL(a.scn_row != nullptr ? ledger_open_scn_kernel : ledger_open_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, cs, a);
+    HIP_TRY(hipGetLastError());
+  }
+  return COSIM_OK;
+}
+
+int cosim_ftrace_set(cosim_engine_t* e, int frames, int keep, int on_mask) {
+  if (!e) return fail(COSIM_EINVAL, "cosim_ftrace_set: null engine");
+  if (frames < 0 || frames > FT_MAX_FRAMES) return fail(COSIM_EINVAL, "cosim_ftrace_set: frames " + std::to_string(frames) + " outside 0..1024 (0 switches the traces off)");
+  if (frames > 0 && (keep < 1 || keep > FT_MAX_KEEP)) return fail(COSIM_EINVAL, "cosim_ftrace_set: keep " + std::to_string(keep) + " outside 1..64");
+  if (frames > 0 && (on_mask == 0 || (on_mask & ~FT_ON_ALL) != 0))
+    return fail(COSIM_EINVAL, "cosim_ftrace_set: on_mask " + std::to_string(on_mask) + " must be a non-empty subset of 1|2|4|32|64|128");
+  HIP_TRY(hipSetDevice(e->device));
+  HIP_TRY(hipDeviceSynchronize());   // every range's launches in flight may still write the old buffers
+  ftrace_free(e);
+  if (frames == 0) return COSIM_OK;
+  const size_t N = (size_t)e->n_envs;
+  const size_t bytes = N * (size_t)(keep + 1) * ftrace_buf_words(frames, ftrace_words(e)) * sizeof(int);
+  auto alloc = [&]() -> hipError_t {
+    hipError_t r;
+    if ((r = hipMalloc(&e->d_ft_buf, bytes)) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_ft_cnt, N * FT_NCNT * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMemset(e->d_ft_cnt, 0, N * FT_NCNT * sizeof(int))) != hipSuccess) return r;
+    return hipMemset(e->d_ft_buf, 0, bytes);
+  };
+  const hipError_t r = alloc();
+  if (r != hipSuccess) {
+    ftrace_free(e);
+    (void)hipGetLastError();
+    return fail(COSIM_EHIP, "cosim_ftrace_set: " + std::to_string(bytes) + " bytes of trace buffers: " + hipGetErrorString(r));
+  }
+  e->ft_frames = frames; e->ft_keep = keep; e->ft_mask = on_mask;
+  // every env starts an open episode in an empty window (the range streams do not order with the null stream: wait here, cold path)
+  int rc = ftrace_begin(e, nullptr, nullptr, 0, e->stepped ? FT_NO_RESET : 0, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return COSIM_OK;
+}
+
+int cosim_ftrace_get(cosim_engine_t* e, int32_t* buffers_dev, int32_t* counts_dev, int32_t* open_dev, void* stream) {
+  if (!e || !buffers_dev || !counts_dev) return fail(COSIM_EINVAL, "cosim_ftrace_get: null argument");
+  if (e->ft_frames <= 0) return fail(COSIM_EINVAL, "cosim_ftrace_get: no failure traces are set (cosim_ftrace_set)");
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t cs = (hipStream_t)stream;
+  int rc = join_ranges(e, cs);
+  if (rc) return rc;
+  const size_t N = (size_t)e->n_envs;
+  const size_t bytes = N * (size_t)(e->ft_keep + 1) * ftrace_buf_words(e->ft_frames, ftrace_words(e)) * sizeof(int);
+  HIP_TRY(hipMemcpyAsync(buffers_dev, e->d_ft_buf, bytes, hipMemcpyDeviceToDevice, cs));
+  // counters 0..2 of every env: working buffer, traces triggered, traces lost
+  HIP_TRY(hipMemcpy2DAsync(counts_dev, 3 * sizeof(int), e->d_ft_cnt, FT_NCNT * sizeof(int), 3 * sizeof(int), N, hipMemcpyDeviceToDevice, cs));
+  if (open_dev) {
+    FtArgs a = ftrace_args(e);
+    a.open_out = open_dev;
+    hipLaunchKernelGGL(ftrace_open_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, cs, a);
     HIP_TRY(hipGetLastError());
   }
   return COSIM_OK;

@@ -108,6 +108,8 @@ def load_library():
     L.cosim_history_get.argtypes = [vp, ci, vp, ctypes.POINTER(ci), vp]
     L.cosim_ledger_set.argtypes = [vp, ci]
     L.cosim_ledger_get.argtypes = [vp, vp, vp, vp, vp]
+    L.cosim_ftrace_set.argtypes = [vp, ci, ci, ci]
+    L.cosim_ftrace_get.argtypes = [vp, vp, vp, vp, vp]
     L.cosim_scenario_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
     L.cosim_fall_set.argtypes = [vp, ctypes.c_float, ctypes.c_float, ci, vp, ci]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
@@ -120,7 +122,7 @@ def load_library():
                "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
                "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
                "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get",
-               "cosim_scenario_set", "cosim_fall_set"):
+               "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -135,7 +137,7 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
            "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
            "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
-           "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set"]
+           "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -318,6 +320,15 @@ class Engine:
     def ledger_get(self, records_ptr, counts_ptr, open_ptr=None, stream=None):
         """``cosim_ledger_get``: rings ``[N, slots, 16]``, ended-episode counts ``[N]`` and (or ``None``) open rows ``[N, 16]``, int32."""
         self._check(self.L.cosim_ledger_get(self.h, records_ptr, counts_ptr, open_ptr, stream))
+
+    def ftrace_set(self, frames: int, keep: int, on_mask: int):
+        """``cosim_ftrace_set``: a window of ``frames`` control steps and ``keep`` frozen traces per env (``frames`` 0: off)."""
+        self._check(self.L.cosim_ftrace_set(self.h, int(frames), int(keep), int(on_mask)))
+
+    def ftrace_get(self, buffers_ptr, counts_ptr, open_ptr=None, stream=None):
+        """``cosim_ftrace_get``: buffers ``[N, keep + 1, 16 + frames * F]``, counters ``[N, 3]`` (working buffer, triggered, lost) and
+        (or ``None``) open headers ``[N, 16]``, int32."""
+        self._check(self.L.cosim_ftrace_get(self.h, buffers_ptr, counts_ptr, open_ptr, stream))
 
     def scenario_set(self, csr, mode: int, cmd_out_ptr, row_out_ptr, stream=None):
         """``cosim_scenario_set``: ``csr`` = the six host arrays ``(key_adr, key_t, key_cmd, push_adr, push_t, push_v)`` of

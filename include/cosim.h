@@ -258,6 +258,51 @@ int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago
 int cosim_ledger_set(cosim_engine_t* e, int slots);
 int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream);
 
+/* Failure traces (no reference counterpart): a per-env flight recorder on the device.  The ledger says that an episode failed, how and
+ * after how many steps; a trace holds what the robot did in its last `frames` control steps before that.  cosim_ftrace_set(frames,
+ * keep, on_mask): frames 0 switches the feature off and frees its buffers (no launch then differs from an engine that never had
+ * it); otherwise frames is 1..1024, keep 1..64 and on_mask a non-empty subset of 1|2|4|32|64|128 (the ledger's flags: the causes
+ * that freeze a window).  Every env gets keep + 1 buffers of 16 + frames * F int32 words -- a header, then a ring of frames -- and
+ * starts an open episode in an empty window, with flag 8 if the engine has been stepped since its last whole-fleet cosim_reset.
+ * Blocks until the device is idle; an allocation failure returns COSIM_EHIP with the byte count in the message.
+ * Frame, F = "ftrace_frame_words" 32-bit words (a multiple of 4; every word a plain copy, NaN stays NaN):
+ *   [0] 1-based step of the episode   [1] 1 terminated | 2 truncated   [2..3] 0
+ *   qpos[nq], qvel[nv]: the state record as the previous step, or the reset, left it -- the state the step started from
+ *   action[nu]: the caller's raw action row   command[command_dim]: the applied command (cmd_out_dev while a scenario table is set)
+ *   info[info_dim]: the step's info row (on a done step: written before the auto-reset, it describes the step that ended)
+ *   zero padding up to F.
+ * From then on cosim_step_range (so cosim_step, on every range's own stream, deferred join or not, captured or not) launches
+ * ftrace_step_kernel (csrc/cosim_ftrace.hip) behind the range's last launch of the step, behind the ledger's.  Per env, in this
+ * order: the outcome part (words 0..3, action, command, info) of the frame at the ring cursor; if terminated | truncated is set,
+ * flags as the ledger builds them, and if flags & on_mask != 0 the header below is written, the working index moves to the next
+ * buffer modulo keep + 1 (nothing is copied: the keep buffers behind the working one are the latest keep traces, an older one is
+ * overwritten and counted as lost) -- otherwise the window is emptied in place -- and the next episode begins at ring position 0
+ * (spawn row = meta word 14, nan_resets base = meta word 4); with no flag the cursor advances modulo frames; last, the state part
+ * (qpos, qvel) of the frame at the new cursor is copied from the live state record: after a done step under auto-reset that is the
+ * new episode's reset pose.  Header, 16 int32 words:
+ *   [0] episode ordinal of this env since cosim_ftrace_set (the ledger's, if both were set together)   [1] length in control steps
+ *   [2] flags, the ledger's meanings and values: 1 terminated, 2 truncated, 4 meta word 4 advanced, 8 did not begin at a reset,
+ *       16 open (open_dev rows only), 32 / 64 / 128 = (meta word 15 & 7) << 5, read only while a fall rule is set
+ *   [3] valid frames = min(length, frames)   [4] ring position of the oldest valid frame (time order: oldest, oldest + 1, ... modulo
+ *       frames)   [5] spawn-table row the episode started from (-1 with no table)   [6] scenario row + 1 (0: no table)
+ *   [7] steps_seen: steps of this env since cosim_ftrace_set   [8..15] 0.
+ * The kernel reads actions_dev, info_out_dev, the flags and the command buffer of the step: like the ledger's command buffer, the
+ * ACTION BUFFER MUST OUTLIVE THE STEP (stay untouched until the range's stream has run it).  cosim_step* then needs info_out_dev
+ * (COSIM_EINVAL without).  cosim_rollout returns COSIM_EINVAL while traces are set: one launch leaves one state record for K steps,
+ * the per-step state is not there to copy.  cosim_profile_step does not feed the recorder.  cosim_reset begins a new episode for its
+ * mask's envs and discards their open window (flag 0); cosim_restore does so for the envs it restored, cosim_set for all envs, both
+ * with flag 8: nothing is kept for an episode the host cut.  Limits: a scenario push applied ahead of the step is not in the frame's
+ * state part (it shows in the next frame and in the info row); the pose a terminal step ends in is reset inside the step kernel and
+ * is not captured (the last frame holds the pose one control step earlier and the terminal info row); traces are not part of a
+ * snapshot row.
+ * cosim_ftrace_get: joins the range streams, then copies every buffer to buffers_dev int32[N][keep + 1][16 + frames * F], per env
+ * the working buffer index, the count of traces triggered and of traces lost to counts_dev int32[N][3] (the kept traces are the
+ * min(triggered, keep) buffers behind the working one) and, unless NULL, the headers of the open windows (flag 16) to open_dev
+ * int32[N][16]; an open window's cursor frame already holds the next step's starting state, so its [3] is min(length, frames - 1).
+ * COSIM_EINVAL with nothing set.  cosim_query answers "ftrace_frames", "ftrace_keep", "ftrace_frame_words" and "ftrace_mask". */
+int cosim_ftrace_set(cosim_engine_t* e, int frames, int keep, int on_mask);
+int cosim_ftrace_get(cosim_engine_t* e, int32_t* buffers_dev, int32_t* counts_dev, int32_t* open_dev, void* stream);
+
 /* Scenario table (the reference's tester changes the command and holds the push button of its ONE robot while it runs,
  * core/tester.py:41-53,68,80-81): per-env command and push schedules, kept and applied on the device.  S = n_scn scenarios in CSR
  * form, host arrays: scenario s owns command keyframes [key_adr[s], key_adr[s + 1]) -- times key_t int32, strictly increasing, rows
