@@ -18,8 +18,12 @@
 #include "cosim_ledger.hip"
 #include "cosim_ftrace.hip"
 #include "cosim_scenario.hip"
+#include "cosim_plan.h"
 
 using namespace cosim;
+
+struct cosim_engine;
+using launch_fn = void (*)(cosim_engine*, const KArgs&, int n, hipStream_t);
 
 static thread_local std::string g_err;
 static int fail(int code, const std::string& msg) {
@@ -70,45 +74,15 @@ struct cosim_engine {
   int ev_used = 0;
   double t_accum_ms = 0.0;
   int t_launches = 0;
-  void (*launch)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  void (*launch_prof)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;  // diagnostic build (light_v1 flat only)
-  // step-only instantiation of the fleet kernel (the mode compiled in as MODE_STEP: no reset branch, no debug dump; the two dense
-  // plane fleets have one).  cosim_step / cosim_rollout launch it while step_kernel is set; reset, debug forward, replay and the
-  // profiler build stay on the general instantiation ("step_kernel" 0 puts the steps there too: the A/B switch)
-  void (*launch_step)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  void (*launch_roll_step)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  bool step_kernel = true;
-  void (*launch2)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;      // two environments per wave (reset / step)
-  void (*launch_prof2)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  void (*launch_ct)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;       // contact-twist variant of a dense-row kernel
-  void (*launch_ct_prof)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  int ct_lds_bytes = 0, ct_contact_slots = 0;
-  int epw = 1;   // environments per wave of the reset / step launches
-  int lds_bytes = 0;
-  int geom_stage = 64;   // plane kernels: geom lanes that can stage their contacts
-  int contact_slots = 0, pair_slots = 0;   // ground-contact / robot-robot contact capacity of the selected kernel
-  // large-capacity kernel behind the fleet kernel (env_fixup_kernel): redoes the control step of envs whose contacts did not fit
-  void (*launch_fix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  int fix_contact_slots = 0;
-  // heightfield fix-up ("hfield_fixup", opt-in): a control step (fused kernel) or a solver substep (split pipeline) with more ground
-  // contacts than the fleet kernel's slots is redone with 50 (mjMAXCONPAIR) x ground-geom slots, the most the narrowphase can emit
-  void (*launch_hfix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;      // behind the fused kernel (whole control step)
-  void (*launch_stepfix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;   // behind each solver launch of the split pipeline
-  void (*launch_dbg_hfix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;  // cosim_debug_forward at that capacity (flamingo_light_v1)
-  int hfix_contact_slots = 0, hfix_lds_bytes = 0;
-  bool hfield_fixup = false;
-  // split pipeline (env_narrow_kernel + env_step_kernel, one pair of launches per substep) where the model / terrain has one
-  void (*launch_narrow)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  void (*launch_stepx)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  bool split = false;
-  int narrow_waves = 6;
-  int narrow_occ = 2;   // narrowphase kernel variant: waves per SIMD its registers are allocated for (0: diagnostic build)
-  float *d_xcon = nullptr, *d_xstate = nullptr;
+  // which kernel runs when (cosim_plan.h): what this model / terrain has (cosim_create fills it, constant afterwards), what
+  // cosim_set_param asked for, and make_plan() of the two: recomputed after every accepted switch, read by every launch site and cosim_query
+  KernelSet<launch_fn> kernels;
+  Switches sw;
+  Plan<launch_fn> plan;
+  int narrow_waves = 6;   // split pipeline: waves per env of the narrowphase kernel
+  float *d_xcon = nullptr, *d_xstate = nullptr;   // split pipeline: contact record and state between the two kernels of a substep
   int* d_xcnt = nullptr;
   int* d_ovf = nullptr;   // [n_envs] flags, set by the fleet kernel, cleared by the fix-up kernel
-  // rollout launches (cosim_rollout): K control steps per launch where the variant has such a kernel
-  void (*launch_roll)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
-  void (*launch_roll_fix)(cosim_engine*, const KArgs&, int grid, hipStream_t) = nullptr;
   // range launches: cosim_step issues the fleet as n_ranges launches over contiguous env ranges on engine-owned streams, so that a
   // range's next control step fills the tail of the others' launches (a launch ends with its slowest env)
   int n_ranges = 1;
@@ -163,96 +137,120 @@ struct cosim_engine {
   unsigned model_term_bodymask = 0u;
 };
 
+// One launcher for every kernel: n envs (narrowphase: envs x waves per env) at ENVS_PER_BLOCK envs per one-wave block -- 1, 2 (two envs
+// per wave) or 64 (the fix-up kernels: a wave scans the flags of 64 envs)
+template <auto KERNEL, int ENVS_PER_BLOCK = 1>
+static void launch_k(cosim_engine*, const KArgs& a, int n, hipStream_t s) {
+  hipLaunchKernelGGL(KERNEL, dim3((n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK), dim3(64), 0, s, a);
+}
+// a KernelSet entry: KERNEL behind its launcher, with the capacities of the LDS layout L it is instantiated with
+template <class L, auto KERNEL, int ENVS_PER_BLOCK = 1>
+static Kernel<launch_fn> entry(bool hf) { return {launch_k<KERNEL, ENVS_PER_BLOCK>, (int)sizeof(L), L::MC, L::MCP, hf ? 64 : L::NGS}; }
+
+// The kernels of one robot on one ground type at one capacity.  MCT: ground-contact slots of a contact-twist kernel, 0: dense contact rows
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((env_kernel<NV, NB, RPL, HF, GTM, SC, false, 1, MCT>), dim3(grid), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_step_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((env_kernel<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, MODE_STEP>), dim3(grid), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_prof_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((env_kernel<NV, NB, RPL, HF, GTM, SC, true, 1, MCT>), dim3(grid), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_fix_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs of the range
-  hipLaunchKernelGGL((env_fixup_kernel<NV, NB, RPL, HF, GTM, SC, MCT>), dim3((grid + 63) / 64), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, int GTM, bool SC, int MCT, int OCC>
-static void launch_hfix_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs of the range
-  hipLaunchKernelGGL((env_hf_fixup_kernel<NV, NB, RPL, GTM, SC, MCT, OCC>), dim3((grid + 63) / 64), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, int GTM, bool SC, int MCT, int OCC>
-static void launch_stepfix_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs of the range
-  hipLaunchKernelGGL((env_step_fixup_kernel<NV, NB, RPL, GTM, SC, MCT, OCC>), dim3((grid + 63) / 64), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_narrow_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs x waves per env
-  if (e->narrow_occ >= 4) hipLaunchKernelGGL((env_narrow_kernel<NV, NB, RPL, HF, GTM, SC, MCT, 4>), dim3(grid), dim3(64), 0, s, a);
-  else if (e->narrow_occ == 3) hipLaunchKernelGGL((env_narrow_kernel<NV, NB, RPL, HF, GTM, SC, MCT, 3>), dim3(grid), dim3(64), 0, s, a);
-  else if (e->narrow_occ == 2) hipLaunchKernelGGL((env_narrow_kernel<NV, NB, RPL, HF, GTM, SC, MCT, 2>), dim3(grid), dim3(64), 0, s, a);
-  else hipLaunchKernelGGL((env_narrow_kernel<NV, NB, RPL, HF, GTM, SC, MCT, 2, true>), dim3(grid), dim3(64), 0, s, a);   // narrow_occupancy 0: diagnostic build
-}
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_stepx_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((env_step_kernel<NV, NB, RPL, HF, GTM, SC, MCT>), dim3(grid), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_roll_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((env_rollout_kernel<NV, NB, RPL, HF, GTM, SC, MCT>), dim3(grid), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_roll_step_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((env_rollout_kernel<NV, NB, RPL, HF, GTM, SC, MCT, MODE_STEP>), dim3(grid), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, int MCT>
-static void launch_roll_fix_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = envs of the range
-  hipLaunchKernelGGL((env_rollout_fix_kernel<NV, NB, RPL, HF, GTM, SC, MCT>), dim3((grid + 63) / 64), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int GTM>
-static void launch2_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {   // grid = number of envs
-  hipLaunchKernelGGL((env_kernel<NV, NB, 2, false, GTM, false, false, 2>), dim3((grid + 1) / 2), dim3(64), 0, s, a);
-}
-template <int NV, int NB, int GTM>
-static void launch_prof2_t(cosim_engine* e, const KArgs& a, int grid, hipStream_t s) {
-  hipLaunchKernelGGL((env_kernel<NV, NB, 2, false, GTM, false, true, 2>), dim3((grid + 1) / 2), dim3(64), 0, s, a);
-}
-// MCT_FLAT / MCT_HF / MCT_HFC: ground-contact slots of the contact-twist kernels on a plane / on a heightfield / on a COARSE
-// heightfield (cells of 10 cm or more: the reference's rocky_* and slope_* fields have 55 cm cells, a geom lies over a handful of
-// prisms, and the slots that stairs with 1 cm cells need would only cost resident waves; 0: dense contact rows)
-template <int NV, int NB, int RPL, int GTM, bool SC, int MCT_FLAT, int MCT_HF, int MCT_HFC = MCT_HF>
-static void select_t(cosim_engine* e, bool hf, bool coarse = false) {
-  using LH = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_HF>::L;
-  using LC = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_HFC>::L;
-  using LF = typename KTraits<NV, NB, RPL, false, SC, 1, MCT_FLAT>::L;
-  if (hf && coarse && MCT_HFC != MCT_HF) {
-    e->launch = launch_t<NV, NB, RPL, true, GTM, SC, MCT_HFC>;
-    e->lds_bytes = (int)sizeof(LC); e->contact_slots = LC::MC; e->pair_slots = LC::MCP; e->geom_stage = 64;
-    return;
+struct Fam {
+  // the LDS layout of kernel mode KM: 0 the fused kernels, 1 the narrowphase kernel, 2 the solver kernel and its substep fix-up
+  template <int KM> using LK = typename KTraits<NV, NB, RPL, HF, SC, 1, MCT, KM>::L;
+  template <auto KERNEL, int ENVS_PER_BLOCK = 1, int KM = 0> static Kernel<launch_fn> of() { return entry<LK<KM>, KERNEL, ENVS_PER_BLOCK>(HF); }
+  // KMODE -1: the general instantiation; MODE_STEP: the step-only one (no reset branch, no debug dump).  PROF: the diagnostic build
+  template <int KMODE = -1, bool PROF = false> static Kernel<launch_fn> fleet() { return of<env_kernel<NV, NB, RPL, HF, GTM, SC, PROF, 1, MCT, KMODE>>(); }
+  static Kernel<launch_fn> prof() { return fleet<-1, true>(); }
+  static Kernel<launch_fn> fix() { return of<env_fixup_kernel<NV, NB, RPL, HF, GTM, SC, MCT>, 64>(); }
+  template <int KMODE = -1> static Kernel<launch_fn> roll() { return of<env_rollout_kernel<NV, NB, RPL, HF, GTM, SC, MCT, KMODE>>(); }
+  static Kernel<launch_fn> roll_fix() { return of<env_rollout_fix_kernel<NV, NB, RPL, HF, GTM, SC, MCT>, 64>(); }
+  static Kernel<launch_fn> solver() { return of<env_step_kernel<NV, NB, RPL, HF, GTM, SC, MCT>, 1, 2>(); }
+  template <int OCC, bool PROF = false> static Kernel<launch_fn> narrow() { return of<env_narrow_kernel<NV, NB, RPL, HF, GTM, SC, MCT, OCC, PROF>, 1, 1>(); }
+  // The heightfield fix-ups behind a fleet kernel with MCT_FLEET slots: MCT = 50 (mjMAXCONPAIR, XC) x the robot's ground geoms, at the
+  // register budget of the kernel they follow (waves per SIMD its LDS admits): hfix behind the fused kernel, stepfix behind the solver
+  template <int MCT_FLEET, int KM> static constexpr int OCC = waves_per_simd(163840 / (int)sizeof(typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FLEET, KM>::L));
+  template <int MCT_FLEET> static Kernel<launch_fn> hfix() {
+    static_assert(HF && sizeof(LK<0>) <= 163840, "heightfield fix-up: the env's LDS exceeds the 160 KiB of a CU");
+    static_assert(MCT % XC == 0 && MCT <= XG * XC, "heightfield fix-up: whole geoms' worth of slots, within the split record");
+    return of<env_hf_fixup_kernel<NV, NB, RPL, GTM, SC, MCT, OCC<MCT_FLEET, 0>>, 64>();
   }
-  e->launch = hf ? launch_t<NV, NB, RPL, true, GTM, SC, MCT_HF> : launch_t<NV, NB, RPL, false, GTM, SC, MCT_FLAT>;
-  e->lds_bytes = hf ? (int)sizeof(LH) : (int)sizeof(LF);
-  e->contact_slots = hf ? LH::MC : LF::MC;
-  e->pair_slots = hf ? LH::MCP : LF::MCP;
-  e->geom_stage = hf ? 64 : LF::NGS;
+  template <int MCT_FLEET> static Kernel<launch_fn> stepfix() {
+    static_assert(HF && sizeof(LK<2>) <= 163840, "heightfield fix-up: the env's LDS exceeds the 160 KiB of a CU");
+    return of<env_step_fixup_kernel<NV, NB, RPL, GTM, SC, MCT, OCC<MCT_FLEET, 2>>, 64, 2>();
+  }
+};
+
+// What each robot has on the plane / a heightfield / a COARSE heightfield (cells of 10 cm or more: the reference's rocky_* and slope_*
+// fields have 55 cm cells, a geom lies over a handful of prisms, and the slots that stairs with 1 cm cells need would only cost
+// resident waves).  RPL = constraint rows per lane; the kernels are specialised on the geom types present.
+constexpr int G_LIGHT = GT_SPHERE | GT_CYLINDER | GT_MESH, G_MESH = GT_MESH, G_HUM = GT_BOX | GT_CYLINDER | GT_MESH;
+
+static KernelSet<launch_fn> light_v1_kernels(bool hf, bool coarse) {
+  KernelSet<launch_fn> k;
+  if (hf) {   // 13 ground geoms
+    k.fleet = coarse ? Fam<18, 14, 1, true, G_LIGHT, false, 48>::fleet() : Fam<18, 14, 1, true, G_LIGHT, false, 128>::fleet();
+    using X = Fam<18, 14, 1, true, G_LIGHT, false, 650>;
+    k.hfix = X::hfix<128>(); k.dbg_hfix = X::fleet();
+    return k;
+  }
+  using D = Fam<18, 14, 1, false, G_LIGHT, false, 0>;    // dense rows: 14 contacts
+  k.fleet = D::fleet(); k.fleet_step = D::fleet<MODE_STEP>(); k.fleet_prof = D::prof();
+  k.roll = D::roll(); k.roll_step = D::roll<MODE_STEP>();
+  // (kept: pair_slots answers the dense layout's 1 although this robot has no pairs)
+  using L2 = typename KTraits<18, 14, 2, false, false, 2, 0>::L;
+  k.epw2 = entry<L2, env_kernel<18, 14, 2, false, G_LIGHT, false, false, 2>, 2>(false);
+  k.epw2_prof = entry<L2, env_kernel<18, 14, 2, false, G_LIGHT, false, true, 2>, 2>(false);
+  // the same robot with its ground contacts in twist space (32 slots instead of 14; cosim_set_param "contact_twist")
+  using T = Fam<18, 14, 1, false, G_LIGHT, false, 32>;
+  k.ct = T::fleet(); k.ct_prof = T::prof();
+  k.ct.pair_slots = k.fleet.pair_slots;   // (kept: "contact_twist" 1 left the answer at the dense kernel's 1; this kernel has none)
+  // ... and with 40 slots (four per ground geom at most: 7 hulls, 2 cylinders, 4 spheres -> 40 is the most the plane narrowphase
+  // can emit) as the kernel that redoes the rare control step with more than 14 contacts: nothing is ever left out
+  using X = Fam<18, 14, 1, false, G_LIGHT, false, 40>;
+  k.fix = X::fix(); k.roll_fix = X::roll_fix();
+  return k;
 }
 
-// The heightfield fix-up behind the fleet kernel with MCT_FLEET ground-contact slots: MCT_FIX = 50 (mjMAXCONPAIR, XC) x the robot's
-// ground geoms slots, at the fleet kernel's register budget (waves per SIMD its LDS admits).  SPLIT: also the substep fix-up behind the
-// split pipeline's solver kernel, at that kernel's budget.  Installed as launch_fix only by cosim_set_param "hfield_fixup" 1.
-template <int NV, int NB, int RPL, int GTM, bool SC, int MCT_FLEET, int MCT_FIX, bool SPLIT = false>
-static void hfix_t(cosim_engine* e) {
-  using LF = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FLEET>::L;
-  using LX = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FIX>::L;
-  using LS = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FLEET, 2>::L;
-  using LSX = typename KTraits<NV, NB, RPL, true, SC, 1, MCT_FIX, 2>::L;
-  static_assert(sizeof(LX) <= 163840 && sizeof(LSX) <= 163840, "heightfield fix-up: the env's LDS exceeds the 160 KiB of a CU");
-  static_assert(MCT_FIX % XC == 0 && MCT_FIX <= XG * XC, "heightfield fix-up: whole geoms' worth of slots, within the split record");
-  e->launch_hfix = launch_hfix_t<NV, NB, RPL, GTM, SC, MCT_FIX, waves_per_simd(163840 / (int)sizeof(LF))>;
-  if constexpr (SPLIT) e->launch_stepfix = launch_stepfix_t<NV, NB, RPL, GTM, SC, MCT_FIX, waves_per_simd(163840 / (int)sizeof(LS))>;
-  e->hfix_contact_slots = MCT_FIX;
-  e->hfix_lds_bytes = (int)sizeof(LX);
+static KernelSet<launch_fn> p_v3_kernels(bool hf, bool) {
+  KernelSet<launch_fn> k;
+  if (hf) {   // 8 ground geoms
+    // one row per lane: with the ground contacts in twist space the dense rows are the robot-robot contacts (8 slots = 32 rows), 8
+    // frictionloss rows and at most 8 limit rows (8 hinges)
+    // (no coarse-cell variant: at one row per lane the 64-slot kernel already fits the 12 waves per CU its registers allow)
+    k.fleet = Fam<14, 10, 1, true, G_MESH, true, 64>::fleet();
+    k.hfix = Fam<14, 10, 1, true, G_MESH, true, 400>::hfix<64>();
+    return k;
+  }
+  // Plane: dense rows, like flamingo_light_v1.  With the friction-loss and limit rows in their dofs' lanes all 64 slots are contact
+  // rows: 16 contacts, ground and robot-robot together (most seen in the bench: 16), and the dense solver iteration is cheaper
+  // than the contact-twist one at these counts (kernel 0.325 ms against 0.400 per 1024 envs).  A control step with more is redone
+  // by the contact-twist kernel (32 ground slots = four per geom, the narrowphase's maximum, + 8 pair slots) right behind it;
+  // cosim_set_param "contact_twist" 1 makes that kernel the fleet kernel, as in round 2.
+  using D = Fam<14, 10, 1, false, G_MESH, true, 0>;
+  using T = Fam<14, 10, 1, false, G_MESH, true, 32>;
+  k.fleet = D::fleet(); k.fleet_prof = D::prof(); k.roll = D::roll();
+  k.fleet.pair_slots = 0;   // (kept: the dense kernel's pairs share the one contact list, the answer has been 0)
+  k.ct = T::fleet(); k.ct_prof = T::prof(); k.fix = T::fix(); k.roll_fix = T::roll_fix();
+  return k;
+}
+
+static KernelSet<launch_fn> w4_kernels(bool hf, bool coarse) {
+  KernelSet<launch_fn> k;
+  // plane: at most 4 contacts per geom (17 geoms); 80 slots keep the env at 19 KB of LDS = the 8 waves per CU its 256 registers allow
+  if (!hf) k.fleet = Fam<22, 18, 2, false, G_MESH, true, 80>::fleet();
+  else if (coarse) { k.fleet = Fam<22, 18, 2, true, G_MESH, true, 48>::fleet(); k.fleet_prof = Fam<22, 18, 2, true, G_MESH, true, 48>::prof(); }
+  else k.fleet = Fam<22, 18, 2, true, G_MESH, true, 128>::fleet();
+  if (hf) k.hfix = Fam<22, 18, 2, true, G_MESH, true, 850>::hfix<128>();   // 17 ground geoms
+  return k;
+}
+
+static KernelSet<launch_fn> humanoid_kernels(bool hf, bool) {
+  KernelSet<launch_fn> k;
+  // plane: at most 4 contacts per geom (22 geoms); 96 slots = 6 waves per CU instead of 5
+  if (!hf) { k.fleet = Fam<29, 26, 2, false, G_HUM, true, 96>::fleet(); return k; }
+  using H = Fam<29, 26, 2, true, G_HUM, true, 256>;
+  using X = Fam<29, 26, 2, true, G_HUM, true, 1100>;   // 22 ground geoms
+  k.fleet = H::fleet(); k.fleet_prof = H::prof();
+  // the prism walk in a kernel of its own, several waves per env (default; cosim_set_param "split" 0 goes back to the fused kernel)
+  k.narrow[0] = H::narrow<2, true>(); k.narrow[1] = H::narrow<2>(); k.narrow[2] = H::narrow<3>(); k.narrow[3] = H::narrow<4>();
+  k.solver = H::solver();
+  k.hfix = X::hfix<256>(); k.stepfix = X::stepfix<256>();
+  return k;
 }
 
 static int round_up(int x, int m) { return (x + m - 1) / m * m; }
@@ -512,7 +510,7 @@ static int set_ranges(cosim_engine* e, int n) {
   for (int i = 0; i < n * e->inflight; i++) { hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); e->ring.push_back(ev); }
   if (n == 1) return COSIM_OK;
   if (!e->ev_in) HIP_TRY(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
-  const int unit = e->epw == 2 ? 2 : 1, units = e->n_envs / unit;
+  const int unit = e->sw.epw == 2 ? 2 : 1, units = e->n_envs / unit;
   int first = 0;
   for (int i = 0; i < n; i++) {
     int cnt = (units / n + (i < units % n ? 1 : 0)) * unit;
@@ -809,80 +807,21 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
       default: delete e; return fail(COSIM_EINVAL, "cosim_create: collision geom type not implemented in the HIP engine");
     }
   }
-  constexpr int G_LIGHT = GT_SPHERE | GT_CYLINDER | GT_MESH, G_MESH = GT_MESH, G_HUM = GT_BOX | GT_CYLINDER | GT_MESH;
-  if (nv == 18 && nb <= 14 && (gtm & ~G_LIGHT) == 0) {   // flamingo_light_v1
-    select_t<18, 14, 1, G_LIGHT, false, 0, 128, 48>(e, hf, coarse);
-    if (hf) {   // 13 ground geoms
-      hfix_t<18, 14, 1, G_LIGHT, false, 128, 650>(e);
-      e->launch_dbg_hfix = launch_t<18, 14, 1, true, G_LIGHT, false, 650>;
-    }
-    if (!hf) {
-      e->launch_prof = launch_prof_t<18, 14, 1, false, G_LIGHT, false, 0>; e->launch2 = launch2_t<18, 14, G_LIGHT>; e->launch_prof2 = launch_prof2_t<18, 14, G_LIGHT>;
-      // the same robot on the plane with its ground contacts in twist space (32 slots instead of 12; cosim_set_param "contact_twist")
-      e->launch_ct = launch_t<18, 14, 1, false, G_LIGHT, false, 32>;
-      e->launch_ct_prof = launch_prof_t<18, 14, 1, false, G_LIGHT, false, 32>;
-      e->ct_lds_bytes = (int)sizeof(typename KTraits<18, 14, 1, false, false, 1, 32>::L);
-      e->ct_contact_slots = 32;
-      // ... and with 40 slots (four per ground geom at most: 7 hulls, 2 cylinders, 4 spheres -> 40 is the most the plane narrowphase
-      // can emit) as the kernel that redoes the rare control step with more than 14 contacts: nothing is ever left out
-      e->launch_fix = launch_fix_t<18, 14, 1, false, G_LIGHT, false, 40>;
-      e->fix_contact_slots = 40;
-      e->launch_roll = launch_roll_t<18, 14, 1, false, G_LIGHT, false, 0>;
-      e->launch_step = launch_step_t<18, 14, 1, false, G_LIGHT, false, 0>;
-      e->launch_roll_step = launch_roll_step_t<18, 14, 1, false, G_LIGHT, false, 0>;
-      e->launch_roll_fix = launch_roll_fix_t<18, 14, 1, false, G_LIGHT, false, 40>;
-    }
-  }
-  else if (nv == 14 && nb <= 10 && (gtm & ~G_MESH) == 0) {   // flamingo_p_v3
-    // one row per lane: with the ground contacts in twist space the dense rows are the robot-robot contacts (8 slots = 32 rows), 8
-    // frictionloss rows and at most 8 limit rows (8 hinges)
-    // (no coarse-cell variant: at one row per lane the 64-slot kernel already fits the 12 waves per CU its registers allow)
-    select_t<14, 10, 1, G_MESH, true, 32, 64, 64>(e, hf, coarse);
-    if (hf) hfix_t<14, 10, 1, G_MESH, true, 64, 400>(e);   // 8 ground geoms
-    if (!hf) {
-      // Plane: dense rows, like flamingo_light_v1.  With the friction-loss and limit rows in their dofs' lanes all 64 slots are contact
-      // rows: 16 contacts, ground and robot-robot together (most seen in the bench: 16), and the dense solver iteration is cheaper
-      // than the contact-twist one at these counts (kernel 0.325 ms against 0.400 per 1024 envs).  A control step with more is redone
-      // by the contact-twist kernel (32 ground slots = four per geom, the narrowphase's maximum, + 8 pair slots) right behind it;
-      // cosim_set_param "contact_twist" 1 makes that kernel the fleet kernel, as in round 2.
-      e->launch_ct = e->launch; e->launch_ct_prof = launch_prof_t<14, 10, 1, false, G_MESH, true, 32>;
-      e->ct_lds_bytes = e->lds_bytes; e->ct_contact_slots = e->contact_slots;
-      using LD_ = typename KTraits<14, 10, 1, false, true, 1, 0>::L;
-      e->launch = launch_t<14, 10, 1, false, G_MESH, true, 0>;
-      e->launch_prof = launch_prof_t<14, 10, 1, false, G_MESH, true, 0>;
-      e->lds_bytes = (int)sizeof(LD_); e->contact_slots = LD_::MC; e->pair_slots = 0;
-      e->launch_fix = launch_fix_t<14, 10, 1, false, G_MESH, true, 32>;
-      e->fix_contact_slots = 32;
-      e->launch_roll = launch_roll_t<14, 10, 1, false, G_MESH, true, 0>;
-      e->launch_roll_fix = launch_roll_fix_t<14, 10, 1, false, G_MESH, true, 32>;
-    }
-  }
-  else if (nv == 22 && nb <= 18 && (gtm & ~G_MESH) == 0) {   // w4_p_v2
-    // plane: at most 4 contacts per geom (17 geoms); 80 slots keep the env at 19 KB of LDS = the 8 waves per CU its 256 registers allow
-    select_t<22, 18, 2, G_MESH, true, 80, 128, 48>(e, hf, coarse);
-    if (hf) hfix_t<22, 18, 2, G_MESH, true, 128, 850>(e);   // 17 ground geoms
-    if (hf && coarse) e->launch_prof = launch_prof_t<22, 18, 2, true, G_MESH, true, 48>;   // diagnostic build of the config-3 kernel
-  }
-  else if (nv == 29 && nb <= 26 && (gtm & ~G_HUM) == 0) {     // humanoid_p_v0
-    // plane: at most 4 contacts per geom (22 geoms); 96 slots = 6 waves per CU instead of 5
-    select_t<29, 26, 2, G_HUM, true, 96, 256>(e, hf);
-    if (hf) {
-      e->launch_prof = launch_prof_t<29, 26, 2, true, G_HUM, true, 256>;
-      // the prism walk in a kernel of its own, several waves per env (default; cosim_set_param "split" 0 goes back to the fused kernel)
-      e->launch_narrow = launch_narrow_t<29, 26, 2, true, G_HUM, true, 256>;
-      e->launch_stepx = launch_stepx_t<29, 26, 2, true, G_HUM, true, 256>;
-      e->split = true;
-      hfix_t<29, 26, 2, G_HUM, true, 256, 1100, true>(e);   // 22 ground geoms
-    }
-  }
+  KernelSet<launch_fn> ks;
+  if (nv == 18 && nb <= 14 && (gtm & ~G_LIGHT) == 0) ks = light_v1_kernels(hf, coarse);
+  else if (nv == 14 && nb <= 10 && (gtm & ~G_MESH) == 0) ks = p_v3_kernels(hf, coarse);
+  else if (nv == 22 && nb <= 18 && (gtm & ~G_MESH) == 0) ks = w4_kernels(hf, coarse);
+  else if (nv == 29 && nb <= 26 && (gtm & ~G_HUM) == 0) ks = humanoid_kernels(hf, coarse);
   else { delete e; return fail(COSIM_EINVAL, "cosim_create: no kernel instantiation for this (nv, nbody); add one in cosim_engine.hip"); }
   if (nv != 18 && model->neq > 0) { delete e; return fail(COSIM_EINVAL, "cosim_create: this robot's kernels keep no rows for connect equalities"); }
-  if (model->ngeom > e->geom_stage) { delete e; return fail(COSIM_EINVAL, "cosim_create: more collision geoms than the plane kernel stages contacts for"); }
-  if (e->launch_hfix) {   // the fix-up capacity must hold 50 contacts per ground geom; a model with more ground geoms has no fix-up
+  if (model->ngeom > ks.fleet.geom_stage) { delete e; return fail(COSIM_EINVAL, "cosim_create: more collision geoms than the plane kernel stages contacts for"); }
+  if (has(ks.hfix)) {   // the fix-up capacity must hold 50 contacts per ground geom; a model with more ground geoms has no heightfield fix-up
     int nground = 0;
     for (int g = 0; g < model->ngeom; g++) nground += model->geom_ground[g] != 0;
-    if (nground * XC > e->hfix_contact_slots) { e->launch_hfix = nullptr; e->launch_stepfix = nullptr; e->launch_dbg_hfix = nullptr; }
+    if (nground * XC > ks.hfix.contact_slots) ks.hfix = ks.stepfix = ks.dbg_hfix = {};
   }
+  e->kernels = ks;
+  e->plan = make_plan(e->kernels, e->sw);
   {
     // support maps of the mesh geoms' hulls (geoms that share a hull slice share the map)
     std::vector<float> cells, cand;
@@ -918,7 +857,7 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
   HIP_TRY(hipMemset(e->d_state, 0, (size_t)n_envs * e->lay.s_stride * sizeof(float)));
   HIP_TRY(hipMalloc(&e->d_params, (size_t)n_envs * e->lay.p_stride * sizeof(float)));
   HIP_TRY(hipMalloc(&e->d_dbg, 8192 * sizeof(float)));
-  if (e->launch_stepx) {
+  if (has(e->kernels.solver)) {   // the split pipeline's buffers
     HIP_TRY(hipMalloc(&e->d_xcon, (size_t)n_envs * XG * XC * 8 * sizeof(float)));
     HIP_TRY(hipMalloc(&e->d_xcnt, (size_t)n_envs * XG * sizeof(int)));
     HIP_TRY(hipMalloc(&e->d_xstate, (size_t)n_envs * XS * sizeof(float)));
@@ -1017,17 +956,14 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "n_envs") return e->n_envs;
   if (n == "state_stride") return e->lay.s_stride;
   if (n == "param_stride") return e->lay.p_stride;
-  if (n == "lds_bytes") return e->lds_bytes;
-  if (n == "contact_slots") return e->contact_slots;
-  if (n == "fixup_contact_slots") {   // 0: no large-capacity kernel behind this one
-    if (e->split && e->launch_stepx) return e->hfield_fixup && e->launch_stepfix ? e->hfix_contact_slots : 0;
-    return e->launch_fix ? e->fix_contact_slots : 0;
-  }
+  if (n == "lds_bytes") return e->plan.lds_bytes;
+  if (n == "contact_slots") return e->plan.contact_slots;
+  if (n == "fixup_contact_slots") return e->plan.fixup_contact_slots;   // 0: no large-capacity kernel behind this one
   if (n == "ranges") return e->n_ranges;
-  if (n == "step_kernel") return (e->step_kernel && e->launch_step && e->epw == 1) ? 1 : 0;   // 1: steps run the step-only instantiation of the fleet kernel
-  if (n == "rollout") return e->launch_roll && e->epw == 1 ? 1 : 0;   // 1: cosim_rollout is available for this model / terrain
-  if (n == "split") return (e->split && e->launch_stepx) ? e->narrow_waves : 0;   // waves per env of the narrowphase kernel; 0: fused kernel
-  if (n == "pair_slots") return e->pair_slots;
+  if (n == "step_kernel") return e->plan.step_kernel;   // 1: steps run the step-only instantiation of the fleet kernel
+  if (n == "rollout") return has(e->plan.rollout);      // 1: cosim_rollout is available for this model / terrain
+  if (n == "split") return e->plan.split * e->narrow_waves;   // waves per env of the narrowphase kernel; 0: fused kernel
+  if (n == "pair_slots") return e->plan.pair_slots;
   if (n == "stacked_dim") return e->ho.stacked_dim;
   if (n == "frame_dim") return e->ho.frame_dim;
   if (n == "max_newton") return newton_cap(e);   // Newton iterations per substep the solver may take
@@ -1084,68 +1020,29 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
     e->inflight = v;
     return set_ranges(e, e->n_ranges);
   }
-  else if (n == "split") {   // 0: the fused kernel; 1: narrowphase and solver as kernels of their own, one pair of launches per substep
-    if ((int)host[0] != 0 && !e->launch_stepx) return fail(COSIM_EINVAL, "cosim_set_param: no split pipeline for this model / terrain");
-    e->split = (int)host[0] != 0;
-    return COSIM_OK;
-  }
   else if (n == "narrow_waves") {   // waves per env of the narrowphase kernel (wave w takes the geoms g % waves == w)
     const int v = (int)host[0];
     if (v < 1 || v > 24) return fail(COSIM_EINVAL, "cosim_set_param: narrow_waves must be 1..24");
     e->narrow_waves = v;
     return COSIM_OK;
   }
-  else if (n == "narrow_occupancy") { e->narrow_occ = (int)host[0]; return COSIM_OK; }   // 2 | 3 | 4 (tuning)
   else if (n == "support_map") {   // 0: mesh support queries scan the whole hull (A/B and tests); 1: through the support maps (default)
     HIP_TRY(hipDeviceSynchronize());
     for (int g = 0; g < 64; g++) e->hm.g_hullmap[g] = (int)host[0] != 0 ? e->hullmap_of_geom[g] : -1;
     HIP_TRY(hipMemcpy(e->d_model, &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
     return COSIM_OK;
   }
-  else if (n == "step_kernel") {   // 1: cosim_step / cosim_rollout launch the step-only instantiation where the fleet has one (default); 0: the general one
-    const int v = (int)host[0];
-    if (v != 0 && v != 1) return fail(COSIM_EINVAL, "cosim_set_param: step_kernel must be 0 or 1");
-    e->step_kernel = v != 0;
-    return COSIM_OK;
-  }
-  else if (n == "fixup") {   // 0: no fix-up launches (contacts beyond the fleet kernel's slots are left out and counted, as in round 2)
-    if ((int)host[0] == 0) {
-      e->launch_fix = nullptr; if (e->launch_roll_fix) { e->launch_roll = nullptr; e->launch_roll_fix = nullptr; }
-      e->launch_hfix = nullptr; e->launch_stepfix = nullptr; e->launch_dbg_hfix = nullptr; e->hfield_fixup = false;
-    }
-    return COSIM_OK;
-  }
-  else if (n == "hfield_fixup") {   // 1: heightfield steps whose ground contacts exceed the fleet kernel's slots are redone (opt-in)
-    const int v = (int)host[0];
-    if (v != 0 && v != 1) return fail(COSIM_EINVAL, "cosim_set_param: hfield_fixup must be 0 or 1");
-    if (!e->launch_hfix || e->epw != 1) return fail(COSIM_EINVAL, "cosim_set_param: no heightfield fix-up for this model / terrain / kernel variant");
-    e->hfield_fixup = v != 0;
-    e->launch_fix = v ? e->launch_hfix : nullptr;   // (heightfield engines have no other fix-up kernel)
-    e->fix_contact_slots = v ? e->hfix_contact_slots : 0;
-    return COSIM_OK;
-  }
-  else if (n == "contact_twist") {   // 1: switch a dense-row kernel to its contact-twist variant (more contact slots), where one exists
-    if ((int)host[0] != 0) {
-      if (!e->launch_ct) return fail(COSIM_EINVAL, "cosim_set_param: no contact-twist variant for this model / terrain");
-      e->launch = e->launch_ct; e->launch_prof = e->launch_ct_prof; e->launch2 = nullptr; e->launch_prof2 = nullptr; e->epw = 1;
-      e->launch_fix = nullptr; e->launch_roll = nullptr; e->launch_roll_fix = nullptr;
-      e->launch_step = nullptr; e->launch_roll_step = nullptr;   // (the contact-twist kernels have no step-only instantiation)
-      if (e->model.nv == 14) e->pair_slots = 8;
-      e->lds_bytes = e->ct_lds_bytes; e->contact_slots = e->ct_contact_slots;
-    }
-    return COSIM_OK;
+  else if (is_switch(n)) {   // "split", "narrow_occupancy", "step_kernel", "fixup", "hfield_fixup", "contact_twist", "envs_per_wave": DESIGN 4.17
+    if (const char* refused = switch_set(e->kernels, e->sw, n, (int)host[0], e->n_envs)) return fail(COSIM_EINVAL, refused);
+    e->plan = make_plan(e->kernels, e->sw);
+    // two envs per wave: even range sizes (kept: "contact_twist" 1 under two envs per wave goes back to one without splitting again)
+    return n == "envs_per_wave" && e->n_ranges > 1 ? set_ranges(e, e->n_ranges) : COSIM_OK;
   }
   else if (n == "timing_stride") { e->timing_stride = (int)host[0] >= 1 ? (int)host[0] : 1; return COSIM_OK; }   // time every n-th launch
   else if (n == "coop_walk") { e->coop_walk = (int)host[0] != 0; return COSIM_OK; }   // 1: the round-2 cooperative walk of hulls with few prisms under them (A/B)
   else if (n == "block_cull") { e->block_cull = (int)host[0] != 0; return COSIM_OK; }   // narrowphase kernel's block tests (default 1); 0 for A/B runs and tests
   else if (n == "boxbox_mode") { e->pair_boxbox = (int)host[0] != 0; return COSIM_OK; }   // 1: box-box pairs through mjc_BoxBox (default), 0: through MPR
   else if (n == "pair_mode") { e->pair_coop = (int)host[0] != 0; return COSIM_OK; }   // 1: hull pairs one at a time, wave-cooperative scans
-  else if (n == "envs_per_wave") {   // 2: the two-environments-per-wave kernel (flat flamingo_light_v1, even env counts); 1: one per wave
-    const int w = (int)host[0];
-    if (w != 1 && !(w == 2 && e->launch2 && e->n_envs % 2 == 0)) return fail(COSIM_EINVAL, "cosim_set_param: envs_per_wave not available for this model / env count");
-    e->epw = w;
-    return e->n_ranges > 1 ? set_ranges(e, e->n_ranges) : COSIM_OK;   // (two envs per wave: even range sizes)
-  }
   else return fail(COSIM_EINVAL, "cosim_set_param: unknown parameter " + n);
   if (count != e->n_envs * width) return fail(COSIM_EINVAL, "cosim_set_param: " + n + " expects n_envs*" + std::to_string(width) + " values");
   { int rc = refresh_param_mirror(e); if (rc) return rc; }
@@ -1200,8 +1097,7 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   }
   KArgs a = base_args(e);
   a.mode = MODE_RESET; a.mask = mask_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
-  if (e->split && e->launch_stepx) e->launch_stepx(e, a, e->n_envs, (hipStream_t)stream);
-  else (e->epw == 2 ? e->launch2 : e->launch)(e, a, e->n_envs, (hipStream_t)stream);
+  e->plan.reset.launch(e, a, e->n_envs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   if (mask_dev == nullptr) e->stepped = false;
   rc = ledger_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);   // behind the reset: meta[14] is the new episode's spawn row
@@ -1271,7 +1167,8 @@ int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* command
 int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const float* commands_dev, float* state_out_dev, uint8_t* terminated_dev,
                   uint8_t* truncated_dev, float* info_out_dev, void* stream) {
   if (!e || !actions_dev || !state_out_dev || !terminated_dev || !truncated_dev || steps < 1) return fail(COSIM_EINVAL, "cosim_rollout: bad argument");
-  if (!e->launch_roll || e->epw != 1) return fail(COSIM_EINVAL, "cosim_rollout: no rollout kernel for this model / terrain / kernel variant");
+  const Plan<launch_fn>& p = e->plan;
+  if (!has(p.rollout)) return fail(COSIM_EINVAL, "cosim_rollout: no rollout kernel for this model / terrain / kernel variant");
   if (e->ho.command_dim > 0 && !commands_dev) return fail(COSIM_EINVAL, "cosim_rollout: commands_dev is required when command_dim > 0");
   if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_rollout") + LEDGER_INFO_MSG);
   if (e->ft_frames > 0)
@@ -1288,7 +1185,7 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
   KArgs a = base_args(e);
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = commands_dev; a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev; a.roll_steps = steps;
-  a.ovf = e->launch_roll_fix ? e->d_ovf : nullptr;
+  a.ovf = has(p.rollout_fix) ? e->d_ovf : nullptr;
   const int nr = e->n_ranges > 1 ? e->n_ranges : 1;
   if (nr > 1) HIP_TRY(hipEventRecord(e->ev_in, cs));
   for (int i = 0; i < nr; i++) {
@@ -1298,10 +1195,10 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
     a.env_count = nr > 1 ? e->rcount[i] : e->n_envs;
     int slot = -1;
     if (e->timing && e->ev_used + 2 <= (int)e->ev.size()) { slot = e->ev_used; e->ev_used += 2; HIP_TRY(hipEventRecord(e->ev[slot], s)); }
-    (e->step_kernel && e->launch_roll_step ? e->launch_roll_step : e->launch_roll)(e, a, a.env_count, s);
+    p.rollout.launch(e, a, a.env_count, s);
     HIP_TRY(hipGetLastError());
     if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
-    if (a.ovf) { e->launch_roll_fix(e, a, a.env_count, s); HIP_TRY(hipGetLastError()); }
+    if (a.ovf) { p.rollout_fix.launch(e, a, a.env_count, s); HIP_TRY(hipGetLastError()); }
     if (e->led_slots > 0) {
       rc = ledger_step(e, a.env_first, a.env_count, steps, info_out_dev, terminated_dev, truncated_dev, commands_dev, s);
       if (rc) return rc;
@@ -1374,7 +1271,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   if (!e || !actions_dev || !state_out_dev || !terminated_dev || !truncated_dev) return fail(COSIM_EINVAL, "cosim_step: null argument");
   if (e->ho.command_dim > 0 && !commands_dev) return fail(COSIM_EINVAL, "cosim_step: commands_dev is required when command_dim > 0");
   if (first < 0 || count < 1 || first + count > e->n_envs) return fail(COSIM_EINVAL, "cosim_step_range: range outside the fleet");
-  if (e->epw == 2 && ((first | count) & 1)) return fail(COSIM_EINVAL, "cosim_step_range: two-environments-per-wave kernel needs even ranges");
+  if (e->sw.epw == 2 && ((first | count) & 1)) return fail(COSIM_EINVAL, "cosim_step_range: two-environments-per-wave kernel needs even ranges");
   if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + LEDGER_INFO_MSG);
   if (e->ft_frames > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + FTRACE_INFO_MSG);
   e->stepped = true;
@@ -1385,11 +1282,10 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev;
   a.env_first = first; a.env_count = count;
-  if (e->split && e->launch_stepx && e->narrow_occ == 0) a.dbg = e->d_dbg;   // diagnostic narrowphase build accumulates its counters there
+  const Plan<launch_fn>& p = e->plan;
+  if (p.narrow_diag) a.dbg = e->d_dbg;   // diagnostic narrowphase build accumulates its counters there
   // the fix-up behind this launch: the split pipeline's after each solver launch ("hfield_fixup"), else the one after the fleet kernel
-  const bool split = e->split && e->launch_stepx;
-  auto fix = split ? (e->hfield_fixup ? e->launch_stepfix : nullptr) : e->launch_fix;
-  a.ovf = (fix && e->epw == 1) ? e->d_ovf : nullptr;
+  a.ovf = has(p.fixup) ? e->d_ovf : nullptr;
   hipStream_t s = (hipStream_t)stream;
   // kernel timing: one HIP event pair per launch on the launch stream, read back in cosim_kernel_time() (no sync here)
   int slot = -1;
@@ -1405,7 +1301,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   // scenario table: this step's command and push of every env of the range, ahead of the step's first launch (plain device work:
   // capturable); inside the timing pair, so cosim_kernel_time() includes it
   if (e->scn.n_scn > 0) { rc = scenario_launch(e, first, count, commands_dev, nullptr, 0, s); if (rc) return rc; }
-  if (split) {
+  if (p.split) {
     // one pair of launches per substep: the prism walk (narrow_waves waves per env), then the solver with the contacts it left; with
     // "hfield_fixup", the substeps the solver gave up (more ground contacts than its slots) are redone right behind it from the same
     // record.  The narrowphase kernel never flags: it is given no ovf.
@@ -1414,15 +1310,15 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     const int fs = e->nsub_override > 0 ? e->nsub_override : e->model.frame_skip;
     for (int sub = 0; sub < fs; sub++) {
       a.sub_index = sub; a.sub_total = fs; an.sub_index = sub; an.sub_total = fs;
-      e->launch_narrow(e, an, count * e->narrow_waves, s);
-      e->launch_stepx(e, a, count, s);
-      if (a.ovf) fix(e, a, count, s);
+      p.narrow.launch(e, an, count * e->narrow_waves, s);
+      p.step.launch(e, a, count, s);
+      if (a.ovf) p.fixup.launch(e, a, count, s);
     }
-  } else (e->epw == 2 ? e->launch2 : (e->step_kernel && e->launch_step ? e->launch_step : e->launch))(e, a, count, s);
+  } else p.step.launch(e, a, count, s);
   HIP_TRY(hipGetLastError());
   if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
-  if (a.ovf && !split) {   // envs the fleet kernel flagged (more contacts than it has slots for) are redone by the large-capacity kernel
-    e->launch_fix(e, a, count, s);
+  if (a.ovf && !p.split) {   // envs the fleet kernel flagged (more contacts than it has slots for) are redone by the large-capacity kernel
+    p.fixup.launch(e, a, count, s);
     HIP_TRY(hipGetLastError());
   }
   // episode ledger: this step's rows of the range, behind the range's last launch of the step (plain device work: capturable)
@@ -1878,9 +1774,10 @@ int cosim_debug_forward(cosim_engine_t* e, int env, const char* name, float* hos
   HIP_TRY(hipMemset(e->d_dbg, 0, 8192 * sizeof(float)));
   KArgs a = base_args(e);
   a.mode = MODE_DEBUG; a.dbg = e->d_dbg; a.dbg_env = env;
-  if (e->split && e->launch_stepx) { e->launch_narrow(e, a, e->narrow_waves, 0); e->launch_stepx(e, a, 1, 0); }   // the product's own pair of kernels
-  else if (e->hfield_fixup && e->launch_dbg_hfix) e->launch_dbg_hfix(e, a, 1, 0);   // every contact the fix-up kernel would keep
-  else (e->epw == 2 ? e->launch2 : e->launch)(e, a, 1, 0);   // two-per-wave kernel: both groups replay env `env`, same dump twice
+  // split: the product's own pair of kernels; with the heightfield fix-up on, every contact the fix-up kernel would keep (where the
+  // fleet kernel exists at that capacity); else the kernel that resets (two-per-wave: both groups replay env `env`, same dump twice)
+  if (e->plan.split) e->plan.narrow.launch(e, a, e->narrow_waves, 0);
+  e->plan.debug.launch(e, a, 1, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   int n = capacity < 8192 ? capacity : 8192;
@@ -1891,7 +1788,7 @@ int cosim_debug_forward(cosim_engine_t* e, int env, const char* name, float* hos
 int cosim_profile_step(cosim_engine_t* e, const float* actions_dev, const float* commands_dev, float* state_out_dev, uint8_t* terminated_dev,
                        uint8_t* truncated_dev, double* cycles_out16) {
   if (!e || !actions_dev || !state_out_dev || !terminated_dev || !truncated_dev || !cycles_out16) return fail(COSIM_EINVAL, "cosim_profile_step: null argument");
-  if (!e->launch_prof) return fail(COSIM_EINVAL, "cosim_profile_step: no diagnostic kernel for this model");
+  if (!has(e->plan.prof)) return fail(COSIM_EINVAL, "cosim_profile_step: no diagnostic kernel for this model");
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
   if (rc) return rc;
@@ -1902,12 +1799,12 @@ int cosim_profile_step(cosim_engine_t* e, const float* actions_dev, const float*
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = commands_dev; a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.dbg = e->d_dbg;
   e->stepped = true;
-  (e->epw == 2 ? e->launch_prof2 : e->launch_prof)(e, a, e->n_envs, 0);
+  e->plan.prof.launch(e, a, e->n_envs, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   unsigned long long raw[32];
   HIP_TRY(hipMemcpy(raw, e->d_dbg, sizeof raw, hipMemcpyDeviceToHost));
-  for (int i = 0; i < 32; i++) cycles_out16[i] = (double)raw[i] / (double)(e->n_envs / e->epw);   // per wave
+  for (int i = 0; i < 32; i++) cycles_out16[i] = (double)raw[i] / (double)(e->n_envs / e->sw.epw);   // per wave
   return COSIM_OK;
 }
 

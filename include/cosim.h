@@ -115,7 +115,11 @@ int cosim_query(const cosim_engine_t* e, const char* name);
  * redoes a control step -- on the split pipeline with "hfield_fixup", a substep -- whose contacts did not fit; 0: this model / terrain
  * has none, or it is switched off: on a heightfield it is non-zero only while "hfield_fixup" is 1), "ranges", "lds_bytes", "frame_skip" (physics
  * substeps per control step: the precision level's), "max_newton" / "max_ls" (the caps the solver runs with) and "spawn_rows" /
- * "spawn_mode" (cosim_spawn_set: rows of the spawn table, 0 = none; 0 = row by env id, 1 = drawn per episode). */
+ * "spawn_mode" (cosim_spawn_set: rows of the spawn table, 0 = none; 0 = row by env id, 1 = drawn per episode).
+ * Two of the kernel switches are one-way for the life of the engine: "contact_twist" 1 (a later 0 does nothing; it also ends
+ * "envs_per_wave" 2, the plane fix-up, the step-only kernel and cosim_rollout) and "fixup" 0 (a later non-zero value does nothing, and
+ * "hfield_fixup", either value, is refused from then on).  The others ("split", "step_kernel", "hfield_fixup", "envs_per_wave",
+ * "narrow_occupancy") go back and forth; DESIGN.md section 4.17 has the rules in one table. */
 int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int count);
 
 /* Replaces env.reset() (reference envs/wrappers.py:245-256,303-307,385-389; flamingo_light_v1.py:209-232).
