@@ -85,7 +85,7 @@ class BatchedEnv:
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
                  spawn=None, history=None, ledger: Optional[int] = None, scenarios=None, scenario_mode: Optional[str] = None,
-                 fall=None, failure_traces=None):
+                 fall=None, failure_traces=None, streams: Optional[int] = None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -94,6 +94,12 @@ class BatchedEnv:
         action table; a policy evaluated per range on ``range_streams``).  With a deferred join the ``action`` tensor of a step must
         stay untouched until that step has run (at most two steps are in flight: an action table or three rotating buffers), and
         ``receive_user_command`` joins first.  Defaults: ``config["engine"]`` / 1 / False.
+
+        ``streams``: how many engine-owned streams carry the ranges (``cosim_set_param "range_streams"``).  Default (``None`` / 0): as
+        many as the process has hardware queues for -- half of ``GPU_MAX_HW_QUEUES`` (4 when unset), at most one per range.  With
+        fewer streams than ranges, consecutive ranges form a group that is stepped as one launch sequence over their union:
+        ``range_list`` keeps the ``ranges`` entries, the ``range_streams`` of a group are one and the same stream, and the results
+        are the same bit for bit.  ``engine.query("range_streams")`` reports the number in use.
 
         ``hfield_fixup`` (heightfield terrain, opt-in): a control step -- on the split pipeline of humanoid_p_v0 a substep -- whose
         ground contacts exceed the fleet kernel's slots is redone by a kernel with 50 slots per ground geom (the most the narrowphase
@@ -205,6 +211,9 @@ class BatchedEnv:
         self.range_list = [(0, self.num_envs)]
         self.range_streams = [None]
         if self.ranges > 1:
+            streams = streams if streams is not None else os.environ.get("COSIM_RANGE_STREAMS")   # (the variable: A/B runs of unchanged callers)
+            if streams:
+                self.engine.set_param("range_streams", np.array([float(streams)]))
             self.engine.set_param("ranges", np.array([float(self.ranges)]))
             self.engine.set_param("deferred_join", np.array([float(self.deferred_join)]))
             if os.environ.get("COSIM_INFLIGHT"):               # steps the host may run ahead of each range stream (tuning runs)

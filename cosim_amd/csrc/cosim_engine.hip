@@ -19,6 +19,7 @@
 #include "cosim_ftrace.hip"
 #include "cosim_scenario.hip"
 #include "cosim_plan.h"
+#include "cosim_ranges.h"
 
 using namespace cosim;
 
@@ -83,21 +84,27 @@ struct cosim_engine {
   float *d_xcon = nullptr, *d_xstate = nullptr;   // split pipeline: contact record and state between the two kernels of a substep
   int* d_xcnt = nullptr;
   int* d_ovf = nullptr;   // [n_envs] flags, set by the fleet kernel, cleared by the fix-up kernel
-  // range launches: cosim_step issues the fleet as n_ranges launches over contiguous env ranges on engine-owned streams, so that a
-  // range's next control step fills the tail of the others' launches (a launch ends with its slowest env)
+  // range launches: the fleet is cut into n_ranges contiguous env ranges, carried by n_streams <= n_ranges engine-owned streams
+  // (cosim_ranges.h: as many as the process has hardware queues for).  cosim_step issues one launch sequence per stream over the
+  // union of its group of consecutive ranges, so that a group's next control step fills the tail of the others' launches (a launch
+  // ends with its slowest env)
   int n_ranges = 1;
+  int n_streams = 1;            // P: streams (= groups = launch sequences per step) in use
+  int range_streams_req = 0;    // "range_streams": 0 auto (range_stream_count of the process's GPU_MAX_HW_QUEUES), >= 1 asked for
   bool deferred_join = false;   // true: cosim_step does not make the caller's stream wait for the range streams (cosim_join does)
   bool join_pending = false;
-  std::vector<hipStream_t> rstream;
-  std::vector<hipEvent_t> rdone;   // one per range: recorded after the range's last launch
+  std::vector<hipStream_t> rstream;   // [n_streams]
+  std::vector<hipEvent_t> rdone;      // one per stream: recorded at join time
   hipEvent_t ev_in = nullptr;      // recorded on the caller's stream, waited on by the range streams: the step's inputs are ready
-  std::vector<int> rfirst, rcount;
-  // flow control of the range launches: the host stays at most `inflight` control steps ahead of each range (a ring of events per
-  // range; cosim_step blocks on the oldest).  Deep queues are slow on this runtime: with the host hundreds of steps ahead the four
+  std::vector<int> rfirst, rcount;   // [n_ranges] envs of each range
+  std::vector<int> rgroup;           // [n_ranges] the stream (group) that carries the range
+  std::vector<int> gfirst, gcount;   // [n_streams] envs of each group: the union of its ranges
+  // flow control of the range launches: the host stays at most `inflight` control steps ahead of each stream (a ring of events per
+  // stream; cosim_step blocks on the oldest).  Deep queues are slow on this runtime: with the host hundreds of steps ahead the four
   // range chains step at 12.0 M env-steps/s, held to 2 ... 16 steps ahead at 13.6 ... 13.7 M (1: 13.35, 64: 13.3; MI355X, ROCm 7.2).
   // Short runs gain most from a shallow queue (20 timed steps: 2 -> 12.9 M, 4 -> 12.4, 8 -> 12.2, 16 -> 11.4, unbounded 10.9).
   int inflight = 2;   // 0: unbounded
-  std::vector<hipEvent_t> ring;   // [n_ranges][inflight]
+  std::vector<hipEvent_t> ring;   // [n_streams][inflight]
   long ring_pos = 0;
   // spawn table (cosim_spawn_set): base poses the reset block takes instead of init_qpos[0:7]; placed by spawn_place_kernel
   float* d_spawn = nullptr;       // [spawn_rows][8]
@@ -494,32 +501,43 @@ static int upload_params(cosim_engine* e) {
   return COSIM_OK;
 }
 
-// n contiguous ranges of n_envs / n envs (the first n_envs % n one longer; even sizes for the two-envs-per-wave kernel), each with
-// a non-blocking stream of its own and a "done" event
+// GPU_MAX_HW_QUEUES as this process was started with, read once (the runtime reads it at its first call too)
+static int process_hw_queues() {
+  static const int q = hw_queues_from_env(getenv("GPU_MAX_HW_QUEUES"));
+  return q;
+}
+
+// n contiguous ranges of n_envs / n envs (the first n_envs % n one longer; even sizes for the two-envs-per-wave kernel) in
+// P = range_streams_in_use(...) groups of consecutive ranges, each group with a non-blocking stream of its own and a "done" event
 static int set_ranges(cosim_engine* e, int n) {
   if (n < 1 || n > 16 || n > e->n_envs) return fail(COSIM_EINVAL, "cosim_set_param: ranges must be 1..16 and at most n_envs");
   HIP_TRY(hipSetDevice(e->device));
   for (hipStream_t x : e->rstream) { HIP_TRY(hipStreamSynchronize(x)); HIP_TRY(hipStreamDestroy(x)); }
   for (hipEvent_t x : e->rdone) HIP_TRY(hipEventDestroy(x));
-  e->rstream.clear(); e->rdone.clear(); e->rfirst.clear(); e->rcount.clear();
+  e->rstream.clear(); e->rdone.clear(); e->rfirst.clear(); e->rcount.clear(); e->rgroup.clear(); e->gfirst.clear(); e->gcount.clear();
   e->join_pending = false;
   e->n_ranges = n;
+  const int P = e->n_streams = range_streams_in_use(e->range_streams_req, n, process_hw_queues());
   for (hipEvent_t x : e->ring) HIP_TRY(hipEventDestroy(x));
   e->ring.clear();
   e->ring_pos = 0;
-  for (int i = 0; i < n * e->inflight; i++) { hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); e->ring.push_back(ev); }
+  for (int i = 0; i < P * e->inflight; i++) { hipEvent_t ev; HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming)); e->ring.push_back(ev); }
   if (n == 1) return COSIM_OK;
   if (!e->ev_in) HIP_TRY(hipEventCreateWithFlags(&e->ev_in, hipEventDisableTiming));
-  const int unit = e->sw.epw == 2 ? 2 : 1, units = e->n_envs / unit;
-  int first = 0;
+  const int unit = e->sw.epw == 2 ? 2 : 1;
   for (int i = 0; i < n; i++) {
-    int cnt = (units / n + (i < units % n ? 1 : 0)) * unit;
-    if (i == n - 1) cnt = e->n_envs - first;
+    int first, cnt;
+    range_bounds(e->n_envs, n, unit, i, &first, &cnt);
+    e->rfirst.push_back(first); e->rcount.push_back(cnt); e->rgroup.push_back(group_of(i, n, P));
+  }
+  for (int g = 0; g < P; g++) {
+    const int r0 = group_first(g, n, P), r1 = group_first(g + 1, n, P);
     hipStream_t st; hipEvent_t ev;
     HIP_TRY(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+    e->rstream.push_back(st);
     HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    e->rstream.push_back(st); e->rdone.push_back(ev); e->rfirst.push_back(first); e->rcount.push_back(cnt);
-    first += cnt;
+    e->rdone.push_back(ev);
+    e->gfirst.push_back(e->rfirst[r0]); e->gcount.push_back(e->rfirst[r1 - 1] + e->rcount[r1 - 1] - e->rfirst[r0]);
   }
   return COSIM_OK;
 }
@@ -528,7 +546,7 @@ static int set_ranges(cosim_engine* e, int n) {
 // event marks everything enqueued before it), not after every range launch -- a deferred-join caller pays no marker packets per step
 static int join_ranges(cosim_engine* e, hipStream_t stream) {
   if (!e->join_pending) return COSIM_OK;
-  for (int i = 0; i < e->n_ranges; i++) {
+  for (int i = 0; i < (int)e->rstream.size(); i++) {
     HIP_TRY(hipEventRecord(e->rdone[i], e->rstream[i]));
     HIP_TRY(hipStreamWaitEvent(stream, e->rdone[i], 0));
   }
@@ -774,19 +792,12 @@ const char* cosim_last_error(void) { return g_err.c_str(); }
 int cosim_model_sizeof(void) { return (int)sizeof(cosim_model_t); }
 int cosim_obs_config_sizeof(void) { return (int)sizeof(cosim_obs_config_t); }
 
-int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* hull_adr, const int* hull_nbr, const float* hfield,
-                 const cosim_obs_config_t* obs, int n_envs, int device, uint64_t seed, int64_t env_id0, cosim_engine_t** out) {
-  if (!model || !obs || !out || n_envs < 1) return fail(COSIM_EINVAL, "cosim_create: null argument or n_envs < 1");
-  if (model->magic != CS_MODEL_MAGIC || model->magic_end != CS_MODEL_MAGIC) return fail(COSIM_EINVAL, "cosim_create: model blob magic mismatch (layout drift?)");
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(COSIM_ENOGPU, "cosim_create: no HIP device available");
-  if (device < 0 || device >= ndev) return fail(COSIM_EINVAL, "cosim_create: bad device index");
-  HIP_TRY(hipSetDevice(device));
-  cosim_engine* e = new cosim_engine();
-  e->n_envs = n_envs; e->device = device; e->model = *model; e->obs_cfg = *obs; e->seed = seed; e->env_id0 = env_id0;
+// everything cosim_create allocates, into a fresh engine; on an error the caller frees whatever was allocated so far (cosim_destroy)
+static int create_fill(cosim_engine* e, const cosim_model_t* model, const float* hull_vert, const int* hull_adr, const int* hull_nbr,
+                       const float* hfield, int n_envs) {
   int rc = build_dev_model(e);
   if (rc == COSIM_OK) rc = build_dev_obs(e);
-  if (rc != COSIM_OK) { delete e; return rc; }
+  if (rc != COSIM_OK) return rc;
   build_layout(e);
   const int nv = model->nv, nb = model->nbody;
   // kernel instantiations: (nv, nbody) of the four cosim robots; RPL = constraint rows per lane
@@ -804,7 +815,7 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
       case CS_GEOM_CYLINDER: gtm |= GT_CYLINDER; break;
       case CS_GEOM_BOX: gtm |= GT_BOX; break;
       case CS_GEOM_MESH: gtm |= GT_MESH; break;
-      default: delete e; return fail(COSIM_EINVAL, "cosim_create: collision geom type not implemented in the HIP engine");
+      default: return fail(COSIM_EINVAL, "cosim_create: collision geom type not implemented in the HIP engine");
     }
   }
   KernelSet<launch_fn> ks;
@@ -812,9 +823,9 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
   else if (nv == 14 && nb <= 10 && (gtm & ~G_MESH) == 0) ks = p_v3_kernels(hf, coarse);
   else if (nv == 22 && nb <= 18 && (gtm & ~G_MESH) == 0) ks = w4_kernels(hf, coarse);
   else if (nv == 29 && nb <= 26 && (gtm & ~G_HUM) == 0) ks = humanoid_kernels(hf, coarse);
-  else { delete e; return fail(COSIM_EINVAL, "cosim_create: no kernel instantiation for this (nv, nbody); add one in cosim_engine.hip"); }
-  if (nv != 18 && model->neq > 0) { delete e; return fail(COSIM_EINVAL, "cosim_create: this robot's kernels keep no rows for connect equalities"); }
-  if (model->ngeom > ks.fleet.geom_stage) { delete e; return fail(COSIM_EINVAL, "cosim_create: more collision geoms than the plane kernel stages contacts for"); }
+  else { return fail(COSIM_EINVAL, "cosim_create: no kernel instantiation for this (nv, nbody); add one in cosim_engine.hip"); }
+  if (nv != 18 && model->neq > 0) { return fail(COSIM_EINVAL, "cosim_create: this robot's kernels keep no rows for connect equalities"); }
+  if (model->ngeom > ks.fleet.geom_stage) { return fail(COSIM_EINVAL, "cosim_create: more collision geoms than the plane kernel stages contacts for"); }
   if (has(ks.hfix)) {   // the fix-up capacity must hold 50 contacts per ground geom; a model with more ground geoms has no heightfield fix-up
     int nground = 0;
     for (int g = 0; g < model->ngeom; g++) nground += model->geom_ground[g] != 0;
@@ -833,10 +844,10 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
           e->hullmap_of_geom[g] = e->hullmap_of_geom[h];
       if (e->hullmap_of_geom[g] >= 0) continue;
       const int adr = model->geom_hulladr[g], num = model->geom_hullnum[g];
-      if (adr < 0 || adr + num > model->nhullvert) { delete e; return fail(COSIM_EINVAL, "cosim_create: geom hull slice outside the hull vertex array"); }
+      if (adr < 0 || adr + num > model->nhullvert) { return fail(COSIM_EINVAL, "cosim_create: geom hull slice outside the hull vertex array"); }
       for (int v = adr; v < adr + num; v++)
         for (int k = hull_adr[v]; k < hull_adr[v + 1]; k++)
-          if (k < 0 || k >= model->nhulledge || hull_nbr[k] < 0 || hull_nbr[k] >= num) { delete e; return fail(COSIM_EINVAL, "cosim_create: hull neighbour graph out of range"); }
+          if (k < 0 || k >= model->nhulledge || hull_nbr[k] < 0 || hull_nbr[k] >= num) { return fail(COSIM_EINVAL, "cosim_create: hull neighbour graph out of range"); }
       e->hullmap_of_geom[g] = (int)(cells.size() / (4 * HM_REC));
       build_support_map(hull_vert + 3 * (size_t)adr, num, hull_adr + adr, hull_nbr, cells, cand);
     }
@@ -909,7 +920,27 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
     HIP_TRY(hipMemcpy(e->d_hfield_mip, mip.data(), mip.size() * sizeof(float), hipMemcpyHostToDevice));
   }
   default_params(e);
-  { int rc2 = set_ranges(e, 1); if (rc2) return rc2; }   // (allocates the pacing events of the single-launch path)
+  return set_ranges(e, 1);   // (allocates the pacing events of the single-launch path)
+}
+
+
+int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* hull_adr, const int* hull_nbr, const float* hfield,
+                 const cosim_obs_config_t* obs, int n_envs, int device, uint64_t seed, int64_t env_id0, cosim_engine_t** out) {
+  if (!model || !obs || !out || n_envs < 1) return fail(COSIM_EINVAL, "cosim_create: null argument or n_envs < 1");
+  if (model->magic != CS_MODEL_MAGIC || model->magic_end != CS_MODEL_MAGIC) return fail(COSIM_EINVAL, "cosim_create: model blob magic mismatch (layout drift?)");
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(COSIM_ENOGPU, "cosim_create: no HIP device available");
+  if (device < 0 || device >= ndev) return fail(COSIM_EINVAL, "cosim_create: bad device index");
+  HIP_TRY(hipSetDevice(device));
+  cosim_engine* e = new cosim_engine();
+  e->n_envs = n_envs; e->device = device; e->model = *model; e->obs_cfg = *obs; e->seed = seed; e->env_id0 = env_id0;
+  const int rc = create_fill(e, model, hull_vert, hull_adr, hull_nbr, hfield, n_envs);
+  if (rc != COSIM_OK) {   // one cleanup path: the engine, its buffers, streams and events (the message survives it)
+    const std::string msg = g_err;
+    cosim_destroy(e);
+    g_err = msg;
+    return rc;
+  }
   *out = e;
   return COSIM_OK;
 }
@@ -930,6 +961,7 @@ int cosim_destroy(cosim_engine_t* e) {
   for (hipEvent_t x : e->ev) hipEventDestroy(x);
   for (hipStream_t x : e->rstream) hipStreamDestroy(x);
   for (hipEvent_t x : e->rdone) hipEventDestroy(x);
+  for (hipEvent_t x : e->ring) hipEventDestroy(x);   // the pacing events: [n_streams][inflight]
   if (e->ev_in) hipEventDestroy(e->ev_in);
   delete e;
   return COSIM_OK;
@@ -960,6 +992,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "contact_slots") return e->plan.contact_slots;
   if (n == "fixup_contact_slots") return e->plan.fixup_contact_slots;   // 0: no large-capacity kernel behind this one
   if (n == "ranges") return e->n_ranges;
+  if (n == "range_streams") return e->n_streams;   // P: engine-owned streams (launch sequences per step) that carry the ranges
   if (n == "step_kernel") return e->plan.step_kernel;   // 1: steps run the step-only instantiation of the fleet kernel
   if (n == "rollout") return has(e->plan.rollout);      // 1: cosim_rollout is available for this model / terrain
   if (n == "split") return e->plan.split * e->narrow_waves;   // waves per env of the narrowphase kernel; 0: fused kernel
@@ -1010,6 +1043,12 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
   }
   else if (n == "debug_substeps") { e->nsub_override = (int)host[0]; return COSIM_OK; }
   else if (n == "ranges") return set_ranges(e, (int)host[0]);
+  else if (n == "range_streams") {   // streams that carry the ranges: >= 1 asks for that many (at most one per range), 0: by the hardware queues
+    const int v = (int)host[0];
+    if (v < 0 || v > 16) return fail(COSIM_EINVAL, "cosim_set_param: range_streams must be 0..16 (0: as many as the hardware queues carry)");
+    e->range_streams_req = v;
+    return set_ranges(e, e->n_ranges);
+  }
   else if (n == "deferred_join") {   // 1: cosim_step leaves the join of the range streams to cosim_join (or to the next call that touches the state)
     e->deferred_join = (int)host[0] != 0;
     return COSIM_OK;
@@ -1123,7 +1162,7 @@ int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* command
     return COSIM_OK;
   }
   // fork: the range streams wait for whatever the caller's stream has been given so far (the step's inputs), then each steps its
-  // range; join: the caller's stream waits for every range -- now, or (deferred_join) at the next cosim_join / state access, which
+  // group of ranges as one launch sequence over their union; join: the caller's stream waits for every range -- now, or (deferred_join) at the next cosim_join / state access, which
   // is what lets a range's next control step overlap the tail of the others' current one
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
@@ -1141,17 +1180,17 @@ int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* command
     (void)hipGetLastError();   // hipErrorNotReady is sticky in hipGetLastError
   }
   if (wait_in) HIP_TRY(hipEventRecord(e->ev_in, cs));
-  for (int i = 0; i < e->n_ranges; i++) {
+  for (int i = 0; i < e->n_streams; i++) {
     if (wait_in) HIP_TRY(hipStreamWaitEvent(e->rstream[i], e->ev_in, 0));
     // (not while capturing: a captured step is replayed, the host does not pace it)
     const bool paced = e->inflight > 0 && cap == hipStreamCaptureStatusNone;
-    if (paced && e->ring_pos >= e->inflight)   // the step `inflight` steps back has left this range's stream
+    if (paced && e->ring_pos >= e->inflight)   // the step `inflight` steps back has left this stream
       HIP_TRY(hipEventSynchronize(e->ring[(size_t)i * e->inflight + e->ring_pos % e->inflight]));
-    int rc = cosim_step_range(e, e->rfirst[i], e->rcount[i], actions_dev, commands_dev, state_out_dev, terminated_dev, truncated_dev, info_out_dev,
+    int rc = cosim_step_range(e, e->gfirst[i], e->gcount[i], actions_dev, commands_dev, state_out_dev, terminated_dev, truncated_dev, info_out_dev,
                               e->rstream[i]);
     if (rc) return rc;
-    // history capture: the range's rows on the range's own stream, behind its last launch of the step; no join, no extra event
-    if (history_due(e)) { rc = history_pack(e, e->rfirst[i], e->rcount[i], e->rstream[i]); if (rc) return rc; }
+    // history capture: the group's rows on the group's own stream, behind its last launch of the step; no join, no extra event
+    if (history_due(e)) { rc = history_pack(e, e->gfirst[i], e->gcount[i], e->rstream[i]); if (rc) return rc; }
     if (paced) HIP_TRY(hipEventRecord(e->ring[(size_t)i * e->inflight + e->ring_pos % e->inflight], e->rstream[i]));
   }
   history_count(e);
@@ -1186,13 +1225,13 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = commands_dev; a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev; a.roll_steps = steps;
   a.ovf = has(p.rollout_fix) ? e->d_ovf : nullptr;
-  const int nr = e->n_ranges > 1 ? e->n_ranges : 1;
-  if (nr > 1) HIP_TRY(hipEventRecord(e->ev_in, cs));
+  const int nr = e->n_ranges > 1 ? e->n_streams : 1;   // launch sequences: one per group of ranges
+  if (e->n_ranges > 1) HIP_TRY(hipEventRecord(e->ev_in, cs));
   for (int i = 0; i < nr; i++) {
-    hipStream_t s = nr > 1 ? e->rstream[i] : cs;
-    if (nr > 1) HIP_TRY(hipStreamWaitEvent(s, e->ev_in, 0));
-    a.env_first = nr > 1 ? e->rfirst[i] : 0;
-    a.env_count = nr > 1 ? e->rcount[i] : e->n_envs;
+    hipStream_t s = e->n_ranges > 1 ? e->rstream[i] : cs;
+    if (e->n_ranges > 1) HIP_TRY(hipStreamWaitEvent(s, e->ev_in, 0));
+    a.env_first = e->n_ranges > 1 ? e->gfirst[i] : 0;
+    a.env_count = e->n_ranges > 1 ? e->gcount[i] : e->n_envs;
     int slot = -1;
     if (e->timing && e->ev_used + 2 <= (int)e->ev.size()) { slot = e->ev_used; e->ev_used += 2; HIP_TRY(hipEventRecord(e->ev[slot], s)); }
     p.rollout.launch(e, a, a.env_count, s);
@@ -1204,7 +1243,7 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
       if (rc) return rc;
     }
   }
-  if (nr > 1) { e->join_pending = true; return join_ranges(e, cs); }
+  if (e->n_ranges > 1) { e->join_pending = true; return join_ranges(e, cs); }
   return COSIM_OK;
 }
 
@@ -1254,7 +1293,7 @@ int cosim_range(const cosim_engine_t* e, int i, int* first, int* count, void** s
   if (!e || i < 0 || i >= e->n_ranges) return fail(COSIM_EINVAL, "cosim_range: bad argument");
   if (first) *first = e->n_ranges > 1 ? e->rfirst[i] : 0;
   if (count) *count = e->n_ranges > 1 ? e->rcount[i] : e->n_envs;
-  if (stream) *stream = e->n_ranges > 1 ? (void*)e->rstream[i] : nullptr;
+  if (stream) *stream = e->n_ranges > 1 ? (void*)e->rstream[e->rgroup[i]] : nullptr;   // ranges of one group report the same stream
   return COSIM_OK;
 }
 
