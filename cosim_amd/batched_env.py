@@ -655,6 +655,10 @@ class BatchedEnv:
         if mode not in MODES:
             raise ValueError(f"set_scenarios: mode must be 'env' or 'cycle', got {mode!r}")
         table = ScenarioTable.build(scenarios, self.command_dim)
+        if table.params is None:                                    # parameter windows: names and "*" against this env's model
+            table.resolve(self.param_names())
+        elif table.has_params:
+            self._check_param_items(table)
         if self._cmd_out is None:                                   # persistent: captured graphs hold these pointers
             self._cmd_out = t.zeros_like(self.user_command)
             self._row_out = t.zeros((self.num_envs,), dtype=t.int32, device=self.device)
@@ -668,6 +672,41 @@ class BatchedEnv:
             raise
         self.scenario_table, self.scenario_mode = table, mode
         self._info_views = None
+        # parameter windows ride with the table: set the ones it holds, clear what an earlier table left
+        if table.has_params:
+            self.engine.scenario_params_set(table.pack_params())
+        elif self.engine.query("scenario_param_items") > 0:
+            self.engine.scenario_params_set(None)
+
+    def param_names(self) -> dict:
+        """The names a parameter window's ``index`` may use on this env, per field (``scenario.param_names``)."""
+        from .scenario import param_names
+        return param_names(self.cm)
+
+    def param_layout(self) -> dict:
+        """Word offsets of ``kp``, ``kd``, ``geom_friction`` and ``dof_frictionloss`` in a parameter record, and its ``stride``."""
+        from .scenario import param_layout
+        q = self.engine.query
+        lay = param_layout(q("nbody"), q("nv"), q("ngeom"), q("action_dim"))
+        assert lay["stride"] == q("param_stride")
+        return lay
+
+    def _check_param_items(self, table):
+        """A table resolved elsewhere: its items must fit this env's model (the engine checks again, this names the window)."""
+        width = {f: len(n) for f, n in self.param_names().items()}
+        from .scenario import _FIELD_NAMES
+        for s, items in enumerate(table.params):
+            for k, (_, _, field, index, _, _) in enumerate(items):
+                if not 0 <= index < width[_FIELD_NAMES[field]]:
+                    raise ValueError(f"set_scenarios: scenario {s}, parameter item {k}: index {index} out of range: "
+                                     f"'{_FIELD_NAMES[field]}' has {width[_FIELD_NAMES[field]]} entries")
+
+    def effective_params(self) -> np.ndarray:
+        """The parameter records the step kernels read, host float32 ``[N, param_stride]``: while the scenario table holds parameter
+        windows the EFFECTIVE records as the last ``step()`` / ``reset()`` / ``set_scenarios`` wrote them (base values with every
+        window applied that held at the env's clock before that step), otherwise the base records.  ``set_param``, ``snapshot()``
+        and the history ring always hold the base.  Joins and synchronises."""
+        return self.engine.scenario_params_get()
 
     @property
     def applied_command(self):

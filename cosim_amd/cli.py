@@ -327,6 +327,8 @@ def main(argv=None) -> int:
                           **({"failure_traces": traces.summary()} if traces is not None else {}),
                           **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
                              if "by_scenario" in out.get("episodes", {}) else {}),
+                          **({"param_windows": sum(len(w) for w in env.scenario_table.param_windows)}   # as listed in the table
+                             if env.scenario_table is not None and env.scenario_table.has_params else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()

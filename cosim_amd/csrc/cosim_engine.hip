@@ -18,6 +18,7 @@
 #include "cosim_ledger.hip"
 #include "cosim_ftrace.hip"
 #include "cosim_scenario.hip"
+#include "cosim_scnparams.hip"
 #include "cosim_plan.h"
 #include "cosim_ranges.h"
 
@@ -137,6 +138,10 @@ struct cosim_engine {
   int scn_nkey = 0, scn_npush = 0;
   float* scn_cmd_out = nullptr;   // [n_envs][command_dim] caller-owned: what the step kernels read as the command while a table is set
   int32_t* scn_row_out = nullptr; // [n_envs] caller-owned
+  // parameter windows of the scenario table (cosim_scenario_params_set, cosim_scnparams.hip): scnparams_step_kernel behind every scenario launch
+  char* d_scnpar = nullptr;       // one allocation: adr | t | word | op | value
+  ScnParTable scnpar = {};        // device pointers into d_scnpar; n_items 0: no windows, no launches, the step kernels read d_params
+  float* d_params_eff = nullptr;  // [n_envs][p_stride] effective records: what base_args hands the step kernels while windows are set
   // fall rules (cosim_fall_set): kernel arguments of every step launch; fall_mask 0 = none (meta word 15 is not written)
   float fall_min_up = -1.f, fall_min_height = 0.f;
   int fall_grace = 0, fall_mask = 0;
@@ -652,7 +657,26 @@ static int scenario_launch(cosim_engine* e, int first, int count, const float* c
   return COSIM_OK;
 }
 
+// the windows go with their table (the caller has waited for the device)
+static void scnparams_free(cosim_engine* e) {
+  (void)hipFree(e->d_scnpar); (void)hipFree(e->d_params_eff);
+  e->d_scnpar = nullptr; e->d_params_eff = nullptr; memset(&e->scnpar, 0, sizeof e->scnpar);
+}
+
+// directly behind scenario_launch, same envs, same stream: the effective parameter records of this step (reset: of the masked envs at t = 0)
+static int scnparams_launch(cosim_engine* e, int first, int count, const uint8_t* mask, int reset, hipStream_t s) {
+  ScnParArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->scn; a.par = e->scnpar; a.state = e->d_state; a.base = e->d_params; a.eff = e->d_params_eff; a.mask = mask;
+  a.n_envs = e->n_envs; a.first = first; a.count = count;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.p_stride = e->lay.p_stride; a.reset = reset;
+  hipLaunchKernelGGL(scnparams_step_kernel, dim3((count + SCNPAR_WAVES - 1) / SCNPAR_WAVES), dim3(64 * SCNPAR_WAVES), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
 static void scenario_free(cosim_engine* e) {
+  scnparams_free(e);
   (void)hipFree(e->d_scn);
   e->d_scn = nullptr; memset(&e->scn, 0, sizeof e->scn); e->scn_nkey = 0; e->scn_npush = 0; e->scn_cmd_out = nullptr; e->scn_row_out = nullptr;
 }
@@ -1013,6 +1037,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "ftrace_frame_words") return ftrace_words(e);   // F: 32-bit words of a frame for this model (answered with traces off too)
   if (n == "ftrace_mask") return e->ft_mask;      // ledger flags that freeze a window
   if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
+  if (n == "scenario_param_items") return e->scnpar.n_items;   // expanded parameter-window items of the table (0: none, no launches)
   if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
   if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
@@ -1106,7 +1131,8 @@ static int drain_events(cosim_engine* e) {
 static KArgs base_args(cosim_engine* e) {
   KArgs a;
   memset(&a, 0, sizeof a);
-  a.dm = e->d_model; a.ob = e->d_obs; a.lay = e->lay; a.state = e->d_state; a.params = e->d_params;
+  a.dm = e->d_model; a.ob = e->d_obs; a.lay = e->lay; a.state = e->d_state;
+  a.params = e->scnpar.n_items > 0 ? e->d_params_eff : e->d_params;   // parameter windows: the effective records (cosim_scnparams.hip)
   a.hull_vert = e->d_hull_vert; a.hull_adr = e->d_hull_adr; a.hull_nbr = e->d_hull_nbr; a.hfield = e->d_hfield;
   a.hull_cell = e->d_hull_cell; a.hull_cand = e->d_hull_cand; a.hfield_mip = e->d_hfield_mip;
   a.pairs = e->d_pairs; a.gext = e->d_gext;
@@ -1133,6 +1159,7 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
       return fail(COSIM_EINVAL, "cosim_reset: a scenario table is set (cosim_scenario_set) and commands_dev is NULL: the scenario kernel passes the caller's command through where a scenario has no keyframe yet");
     rc = scenario_launch(e, 0, e->n_envs, commands_dev, mask_dev, 1, (hipStream_t)stream);
     if (rc) return rc;
+    if (e->scnpar.n_items > 0) { rc = scnparams_launch(e, 0, e->n_envs, mask_dev, 1, (hipStream_t)stream); if (rc) return rc; }
   }
   KArgs a = base_args(e);
   a.mode = MODE_RESET; a.mask = mask_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
@@ -1340,6 +1367,9 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   // scenario table: this step's command and push of every env of the range, ahead of the step's first launch (plain device work:
   // capturable); inside the timing pair, so cosim_kernel_time() includes it
   if (e->scn.n_scn > 0) { rc = scenario_launch(e, first, count, commands_dev, nullptr, 0, s); if (rc) return rc; }
+  // parameter windows: this step's effective parameter records of the range, ahead of every launch that reads them (the substep
+  // launches of the split pipeline and the fix-up kernels' redo included: all are handed the same pointer by base_args)
+  if (e->scnpar.n_items > 0) { rc = scnparams_launch(e, first, count, nullptr, 0, s); if (rc) return rc; }
   if (p.split) {
     // one pair of launches per substep: the prism walk (narrow_waves waves per env), then the solver with the contacts it left; with
     // "hfield_fixup", the substeps the solver gave up (more ground contacts than its slots) are redone right behind it from the same
@@ -1769,6 +1799,7 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
     return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
   }
   if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
+  if (n_scn != e->scn.n_scn) scnparams_free(e);   // parameter windows are rows of the table they were set for: another S drops them
   const int32_t* base = reinterpret_cast<const int32_t*>(e->d_scn);
   e->scn.key_adr = base + o_kadr; e->scn.push_adr = base + o_padr; e->scn.key_t = base + o_kt; e->scn.push_t = base + o_pt;
   e->scn.key_cmd = reinterpret_cast<const float*>(base + o_kc); e->scn.push_v = reinterpret_cast<const float*>(base + o_pv);
@@ -1777,6 +1808,119 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
   e->scn_nkey = nkey; e->scn_npush = npush;
   e->scn_cmd_out = cmd_out_dev; e->scn_row_out = row_out_dev;
   return COSIM_OK;
+}
+
+// Parameter windows of the scenario table that is set: validate on the host (a message that names the scenario and the row), resolve
+// field + index to a word of the parameter record, join the ranges, wait for the device, upload, and write every env's effective
+// record once.  Items of the count of the ones that are set are rewritten in place: the device pointers stay, captured graphs pick
+// the new values up.
+int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t, const int32_t* field, const int32_t* index,
+                              const int32_t* op, const float* value) {
+  if (!e) return fail(COSIM_EINVAL, "cosim_scenario_params_set: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_scn == 0) {   // clear (launches in flight still read the effective records: wait for them)
+    int rc = join_ranges(e, 0);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    scnparams_free(e);
+    return COSIM_OK;
+  }
+  if (e->scn.n_scn == 0)
+    return fail(COSIM_EINVAL, "cosim_scenario_params_set: no scenario table is set (cosim_scenario_set): parameter windows are rows of a table; set the table first");
+  if (n_scn != e->scn.n_scn)
+    return fail(COSIM_EINVAL, "cosim_scenario_params_set: " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.n_scn));
+  if (!adr) return fail(COSIM_EINVAL, "cosim_scenario_params_set: null argument");
+  if (adr[0] != 0) return fail(COSIM_EINVAL, "cosim_scenario_params_set: adr[0] must be 0");
+  const cosim_model_t& m = e->model;
+  const Layout& L = e->lay;
+  std::vector<int32_t> words;
+  for (int s = 0; s < n_scn; s++) {
+    const long long ni = (long long)adr[s + 1] - adr[s];
+    const std::string who = "cosim_scenario_params_set: scenario " + std::to_string(s);
+    if (ni < 0) return fail(COSIM_EINVAL, who + ": row addresses must not decrease");
+    if (ni > SCNPAR_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(ni) + " parameter items, at most 256");
+    if (ni > 0 && (!t || !field || !index || !op || !value)) return fail(COSIM_EINVAL, who + ": null table array");
+    for (int i = adr[s]; i < adr[s + 1]; i++) {
+      const std::string row = who + ", parameter item " + std::to_string(i - adr[s]);
+      const int t0 = t[2 * i], t1 = t[2 * i + 1];
+      if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": times outside [0, 2^30)");
+      if (t1 <= t0) return fail(COSIM_EINVAL, row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0));
+      int off, width;
+      const char* name;
+      switch (field[i]) {
+        case SCNPAR_KP: off = L.p_kp; width = m.nu; name = "kp"; break;
+        case SCNPAR_KD: off = L.p_kd; width = m.nu; name = "kd"; break;
+        case SCNPAR_GEOM_FRICTION: off = L.p_gmu; width = m.ngeom; name = "geom_friction"; break;
+        case SCNPAR_DOF_FRICTIONLOSS: off = L.p_floss; width = m.nv; name = "dof_frictionloss"; break;
+        case SCNPAR_BODY_MASS: case SCNPAR_BODY_INVWEIGHT0: case SCNPAR_DOF_INVWEIGHT0: case SCNPAR_MEANINERTIA:
+          return fail(COSIM_EINVAL, row + ": field " + std::to_string(field[i]) + " (body_mass, body_invweight0, dof_invweight0, meaninertia) is refused: the mass "
+                      "fields are consistent only as a set computed on the host in fp64; a payload change in mid-episode is out of scope");
+        default: return fail(COSIM_EINVAL, row + ": unknown field " + std::to_string(field[i]) + " (0 kp, 1 kd, 2 geom_friction, 3 dof_frictionloss)");
+      }
+      if (index[i] < 0 || index[i] >= width)
+        return fail(COSIM_EINVAL, row + ": index " + std::to_string(index[i]) + " out of range: " + name + " has " + std::to_string(width) + " entries");
+      if (op[i] != SCNPAR_SCALE && op[i] != SCNPAR_SET) return fail(COSIM_EINVAL, row + ": unknown op " + std::to_string(op[i]) + " (0 scale, 1 set)");
+      if (!std::isfinite(value[i])) return fail(COSIM_EINVAL, row + ": value is not finite");
+      words.push_back(off + index[i]);
+    }
+  }
+  const int n = adr[n_scn];
+  if (n == 0) return fail(COSIM_EINVAL, "cosim_scenario_params_set: the table holds no parameter item (n_scn = 0 clears the windows)");
+  int rc = upload_params(e);   // the effective records written below are built from the current base
+  if (rc) return rc;
+  rc = join_ranges(e, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());   // launches in flight may still read the items
+  // adr | t | word | op | value, every array 4-byte words
+  const size_t o_adr = 0, o_t = o_adr + (size_t)n_scn + 1, o_w = o_t + 2 * (size_t)n, o_op = o_w + (size_t)n, o_v = o_op + (size_t)n, total = o_v + (size_t)n;
+  const bool in_place = e->scnpar.n_items == n && e->scnpar.n_scn == n_scn;
+  char* d_new = e->d_scnpar;
+  float* d_eff = e->d_params_eff;
+  if (!in_place) HIP_TRY(hipMalloc(&d_new, total * 4));
+  if (!d_eff) {
+    const hipError_t r = hipMalloc(&d_eff, (size_t)e->n_envs * L.p_stride * sizeof(float));
+    if (r != hipSuccess) { if (!in_place) (void)hipFree(d_new); return fail(COSIM_EHIP, std::string("cosim_scenario_params_set: ") + hipGetErrorString(r)); }
+    e->d_params_eff = d_eff;
+  }
+  std::vector<int32_t> h(total, 0);
+  memcpy(&h[o_adr], adr, ((size_t)n_scn + 1) * 4);
+  memcpy(&h[o_t], t, 2 * (size_t)n * 4);
+  memcpy(&h[o_w], words.data(), (size_t)n * 4);
+  memcpy(&h[o_op], op, (size_t)n * 4);
+  memcpy(&h[o_v], value, (size_t)n * 4);
+  const hipError_t r = hipMemcpy(d_new, h.data(), total * 4, hipMemcpyHostToDevice);
+  if (r != hipSuccess) {   // a new allocation is dropped and the old items stay; an in-place rewrite may be half written: no windows then
+    if (in_place) scnparams_free(e);
+    else { (void)hipFree(d_new); if (e->scnpar.n_items == 0) { (void)hipFree(e->d_params_eff); e->d_params_eff = nullptr; } }
+    return fail(COSIM_EHIP, std::string("cosim_scenario_params_set: ") + hipGetErrorString(r));
+  }
+  if (!in_place) { (void)hipFree(e->d_scnpar); e->d_scnpar = d_new; }
+  const int32_t* base = reinterpret_cast<const int32_t*>(e->d_scnpar);
+  e->scnpar.adr = base + o_adr; e->scnpar.t = base + o_t; e->scnpar.word = base + o_w; e->scnpar.op = base + o_op;
+  e->scnpar.value = reinterpret_cast<const float*>(base + o_v);
+  e->scnpar.n_scn = n_scn; e->scnpar.n_items = n;
+  // every env's effective record once, at its current clock: no row is ever unwritten
+  rc = scnparams_launch(e, 0, e->n_envs, nullptr, 0, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return COSIM_OK;
+}
+
+// The effective parameter records [N][param_stride] as the last step / reset / cosim_scenario_params_set left them (with no windows
+// set: the base records), to host memory; joins first.  Returns param_stride.
+int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity) {
+  if (!e || !host) return fail(COSIM_EINVAL, "cosim_scenario_params_get: null argument");
+  const size_t words = (size_t)e->n_envs * e->lay.p_stride;
+  if (capacity < 0 || (size_t)capacity < words)
+    return fail(COSIM_EINVAL, "cosim_scenario_params_get: capacity " + std::to_string(capacity) + " floats, the records take " + std::to_string(words));
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = upload_params(e);
+  if (rc) return rc;
+  rc = join_ranges(e, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(host, e->scnpar.n_items > 0 ? e->d_params_eff : e->d_params, words * sizeof(float), hipMemcpyDeviceToHost));
+  return e->lay.p_stride;
 }
 
 __global__ void push_kernel(float* state, Layout lay, const float* v, const uint8_t* mask, int n) {

@@ -111,6 +111,8 @@ def load_library():
     L.cosim_ftrace_set.argtypes = [vp, ci, ci, ci]
     L.cosim_ftrace_get.argtypes = [vp, vp, vp, vp, vp]
     L.cosim_scenario_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
+    L.cosim_scenario_params_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
+    L.cosim_scenario_params_get.argtypes = [vp, vp, ci]
     L.cosim_fall_set.argtypes = [vp, ctypes.c_float, ctypes.c_float, ci, vp, ci]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
@@ -122,7 +124,8 @@ def load_library():
                "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
                "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
                "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get",
-               "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get"):
+               "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get", "cosim_scenario_params_set",
+               "cosim_scenario_params_get"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -137,7 +140,8 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
            "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
            "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
-           "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get"]
+           "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get",
+           "cosim_scenario_params_set", "cosim_scenario_params_get"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -348,6 +352,30 @@ class Engine:
             raise ValueError(f"scenario_set: the table arrays are shorter than their row addresses ({nk} keyframes, {npw} push windows)")
         self._check(self.L.cosim_scenario_set(self.h, int(ka.size) - 1, ka.ctypes.data, kt.ctypes.data, kc.ctypes.data, pa.ctypes.data,
                                               pt.ctypes.data, pv.ctypes.data, int(mode), cmd_out_ptr, row_out_ptr, stream))
+
+    def scenario_params_set(self, csr):
+        """``cosim_scenario_params_set``: ``csr`` = the six host arrays ``(adr, t, field, index, op, value)`` of
+        ``ScenarioTable.pack_params`` (``None``: clear the windows)."""
+        if csr is None:
+            self._check(self.L.cosim_scenario_params_set(self.h, 0, None, None, None, None, None, None))
+            return
+        adr, t, field, index, op, value = csr
+        adr, t = np.ascontiguousarray(adr, dtype=np.int32), np.ascontiguousarray(t, dtype=np.int32)
+        field, index, op = (np.ascontiguousarray(x, dtype=np.int32) for x in (field, index, op))
+        value = np.ascontiguousarray(value, dtype=np.float32)
+        if adr.ndim != 1 or adr.size < 1:
+            raise ValueError("scenario_params_set: adr must be [S + 1]")
+        n = int(max(adr.max(), 0))
+        if t.size < 2 * n or min(field.size, index.size, op.size, value.size) < n:   # (the engine reads the arrays up to the addresses)
+            raise ValueError(f"scenario_params_set: the item arrays are shorter than their row addresses ({n} items)")
+        self._check(self.L.cosim_scenario_params_set(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, field.ctypes.data, index.ctypes.data,
+                                                     op.ctypes.data, value.ctypes.data))
+
+    def scenario_params_get(self) -> np.ndarray:
+        """``cosim_scenario_params_get``: the effective parameter records, host float32 ``[N, param_stride]``."""
+        out = np.zeros((self.num_envs, self.query("param_stride")), dtype=np.float32)
+        self._check(self.L.cosim_scenario_params_get(self.h, out.ctypes.data, int(out.size)))
+        return out
 
     def fall_set(self, min_up: float, min_height: float, grace_steps: int, body_ids=None):
         """``cosim_fall_set``: ``min_up <= -1`` / ``min_height <= 0`` switch the tilt / height rule off; ``body_ids`` ``None`` leaves the

@@ -9,6 +9,14 @@ clock, with no host read per step.  ``reference_schedule`` is the numpy twin of 
 A scenario is a mapping ``{"commands": [[t, c0, c1, ...], ...], "pushes": [[t0, t1, vx, vy, vz], ...]}``: from episode step ``t`` on
 the command is that row (whole row; before the first keyframe the caller's command passes through); a push is held for
 ``t0 <= t < t1`` (the last LISTED window that holds wins).  Either list may be missing or empty.
+
+Parameter windows (``cosim_scenario_params_set``, csrc/cosim_scnparams.hip): a scenario may also hold ``"params": [[t0, t1, field,
+index, op, value], ...]``.  While ``t0 <= t < t1`` word ``field[index]`` of the env's EFFECTIVE parameter record is ``base * value``
+(``op`` ``"scale"``, one float32 multiply) or ``value`` (``"set"``); the last LISTED window that holds wins, per word; outside every
+window the word is the base value.  Fields: ``"kp"`` / ``"kd"`` (index = actuator), ``"geom_friction"`` (index = geom; the mixed
+ground-contact friction) and ``"dof_frictionloss"`` (index = dof).  ``index`` is an int, a name of the model (actuator, geom or joint
+name; needs ``names``, see ``param_names``) or ``"*"`` for every entry of the field; names and ``"*"`` are expanded here, on the host.
+The mass fields are refused.  ``reference_params`` is the numpy twin of the kernel's rule, exact.
 """
 from __future__ import annotations
 
@@ -20,23 +28,53 @@ import numpy as np
 
 MODES = {"env": 0, "cycle": 1}
 MAX_ROWS, MAX_ITEMS, MAX_TIME = 65536, 64, 1 << 30
+PARAM_FIELDS = {"kp": 0, "kd": 1, "geom_friction": 2, "dof_frictionloss": 3}
+PARAM_OPS = {"scale": 0, "set": 1}
+MAX_PARAM_ITEMS = 256
+# consistent only as a set that compile.env_constants computes in fp64 on the host
+REFUSED_PARAM_FIELDS = ("body_mass", "body_invweight0", "dof_invweight0", "meaninertia")
+_FIELD_NAMES = {v: k for k, v in PARAM_FIELDS.items()}
+_OP_NAMES = {v: k for k, v in PARAM_OPS.items()}
+
+
+def param_names(cm) -> dict:
+    """The names an ``index`` of a parameter window may use, per field, from a compiled model: actuator names for ``kp`` / ``kd``,
+    geom names for ``geom_friction``, and for ``dof_frictionloss`` the name of the joint each dof belongs to (a free joint's name
+    expands to its six dofs).  The length of a list is the field's width."""
+    from .model import get_field
+    acts = [a["name"] for a in cm.spec["actuators"]]
+    jid = np.asarray(get_field(cm.blob, "dof_jntid"))[:cm.blob.nv]
+    return {"kp": acts, "kd": acts, "geom_friction": list(cm.geom_names), "dof_frictionloss": [cm.joint_names[int(j)] for j in jid]}
+
+
+def param_layout(nbody: int, nv: int, ngeom: int, nu: int) -> dict:
+    """Word offsets of the fields a window may name in a parameter record, and the record's ``stride`` (the engine's build_layout:
+    body_mass, body_invweight0 [nbody] | dof_invweight0, dof_frictionloss [nv] | geom_friction [ngeom] | kp, kd [nu] | meaninertia,
+    rounded up to 32 words)."""
+    floss = 2 * nbody + nv
+    gmu = floss + nv
+    kp = gmu + ngeom
+    return {"dof_frictionloss": floss, "geom_friction": gmu, "kp": kp, "kd": kp + nu, "stride": -(-(kp + 2 * nu + 1) // 32) * 32}
 
 
 class ScenarioTable:
     """S scenarios, validated.  ``keys[s]`` is a list of ``(t, command float32[command_dim])``, ``pushes[s]`` a list of
     ``(t0, t1, v float32[3])``.  ``pack()`` gives the CSR arrays of the C ABI, ``from_csr`` reads them back."""
 
-    def __init__(self, scenarios: Sequence, command_dim: int):
+    def __init__(self, scenarios: Sequence, command_dim: int, names: dict = None):
+        """``names`` (``param_names(compiled_model)``, or any mapping field -> list of entry names) is what parameter windows are
+        resolved against: it gives every field its width and the names an ``index`` may use.  Without it windows are kept as
+        written and ``resolve(names)`` expands them later (``BatchedEnv.set_scenarios`` does)."""
         self.command_dim = int(command_dim)
         if self.command_dim < 0:
             raise ValueError("ScenarioTable: command_dim must be >= 0")
         scenarios = list(scenarios)
         if not 1 <= len(scenarios) <= MAX_ROWS:
             raise ValueError(f"ScenarioTable: {len(scenarios)} scenarios: must be 1..{MAX_ROWS}")
-        self.keys, self.pushes = [], []
+        self.keys, self.pushes, self.param_windows, self.params = [], [], [], None
         for s, sc in enumerate(scenarios):
             sc = sc or {}
-            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "name"}:
+            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "name"}:
                 raise ValueError(f"ScenarioTable: scenario {s}: a mapping with the keys 'commands' and 'pushes' is expected, got {sc!r}")
             keys, pushes = [], []
             for r, row in enumerate(sc.get("commands") or []):
@@ -68,6 +106,49 @@ class ScenarioTable:
                     raise ValueError(f"ScenarioTable: scenario {s}: {len(lst)} {what}, at most {MAX_ITEMS}")
             self.keys.append(keys)
             self.pushes.append(pushes)
+            self.param_windows.append(_param_windows(s, sc.get("params") or []))
+        if names is not None or not self.has_params:
+            self.resolve(names or {})
+
+    @property
+    def has_params(self) -> bool:
+        return any(self.param_windows)
+
+    def resolve(self, names: dict) -> "ScenarioTable":
+        """Expand the windows against ``names`` (field -> list of entry names): ``self.params[s]`` becomes the list of items ``(t0, t1,
+        field id, index, op id, float32 value)`` in listed order, ``"*"`` and names that several entries share expanded in index
+        order.  Raises ``ValueError`` naming the scenario and the row: unknown name, index out of range, more than 256 items."""
+        out = []
+        for s, wins in enumerate(self.param_windows):
+            items = []
+            for r, (t0, t1, field, index, op, value) in enumerate(wins):
+                who = f"ScenarioTable: scenario {s}, parameter window {r}"
+                if field not in names:
+                    raise ValueError(f"{who}: field '{field}' needs the model's names to be resolved (param_names)")
+                entries = list(names[field])
+                if isinstance(index, str):
+                    idx = list(range(len(entries))) if index == "*" else [i for i, n in enumerate(entries) if n == index]
+                    if not idx:
+                        raise ValueError(f"{who}: unknown name '{index}' for field '{field}'")
+                else:
+                    if not 0 <= index < len(entries):
+                        raise ValueError(f"{who}: index {index} out of range: '{field}' has {len(entries)} entries")
+                    idx = [index]
+                items += [(t0, t1, PARAM_FIELDS[field], i, PARAM_OPS[op], value) for i in idx]
+            if len(items) > MAX_PARAM_ITEMS:
+                raise ValueError(f"ScenarioTable: scenario {s}: {len(items)} parameter items after expansion, at most {MAX_PARAM_ITEMS}")
+            out.append(items)
+        self.params = out
+        return self
+
+    @property
+    def n_param_items(self) -> int:
+        return sum(len(p) for p in self._resolved())
+
+    def _resolved(self):
+        if self.params is None:
+            raise ValueError("ScenarioTable: the parameter windows are not resolved yet: pass names= or call resolve(param_names(model))")
+        return self.params
 
     def __len__(self):
         return len(self.keys)
@@ -97,8 +178,12 @@ class ScenarioTable:
         return cls(spec, command_dim)
 
     def to_list(self) -> list:
-        return [{"commands": [[t] + [float(x) for x in c] for t, c in keys], "pushes": [[t0, t1] + [float(x) for x in v] for t0, t1, v in pushes]}
-                for keys, pushes in zip(self.keys, self.pushes)]
+        out = [{"commands": [[t] + [float(x) for x in c] for t, c in keys], "pushes": [[t0, t1] + [float(x) for x in v] for t0, t1, v in pushes]}
+               for keys, pushes in zip(self.keys, self.pushes)]
+        for sc, wins in zip(out, self.param_windows):
+            if wins:
+                sc["params"] = [[t0, t1, field, index, op, float(value)] for t0, t1, field, index, op, value in wins]
+        return out
 
     def pack(self):
         """``(key_adr int32[S + 1], key_t int32[nk], key_cmd float32[nk, command_dim], push_adr int32[S + 1], push_t int32[np, 2],
@@ -110,6 +195,31 @@ class ScenarioTable:
         push_t = np.array([(t0, t1) for pushes in self.pushes for t0, t1, _ in pushes], dtype=np.int32).reshape(-1, 2)
         push_v = np.array([v for pushes in self.pushes for _, _, v in pushes], dtype=np.float32).reshape(-1, 3)
         return key_adr, key_t, key_cmd, push_adr, push_t, push_v
+
+    def pack_params(self):
+        """``(adr int32[S + 1], t int32[n, 2], field int32[n], index int32[n], op int32[n], value float32[n])``: the expanded items
+        in the CSR form of ``cosim_scenario_params_set``."""
+        P = self._resolved()
+        adr = np.cumsum([0] + [len(p) for p in P]).astype(np.int32)
+        flat = [it for p in P for it in p]
+        col = lambda k, dt: np.array([it[k] for it in flat], dtype=dt)
+        return (adr, np.array([(it[0], it[1]) for it in flat], dtype=np.int32).reshape(-1, 2), col(2, np.int32), col(3, np.int32), col(4, np.int32),
+                col(5, np.float32))
+
+    def params_from_csr(self, adr, t, field, index, op, value, names: dict = None) -> "ScenarioTable":
+        """A table with this one's commands and pushes and the windows that the CSR arrays of ``pack_params`` hold (one window per
+        item, int indices), resolved against ``names`` if given."""
+        t = np.asarray(t).reshape(-1, 2)
+        scn = self.to_list()
+        if len(adr) != len(scn) + 1:
+            raise ValueError(f"ScenarioTable: parameter windows for {len(adr) - 1} scenarios, the table has {len(scn)}")
+        for s, sc in enumerate(scn):
+            sc.pop("params", None)
+            rows = [[int(t[i, 0]), int(t[i, 1]), _FIELD_NAMES.get(int(field[i]), int(field[i])), int(index[i]), _OP_NAMES.get(int(op[i]), int(op[i])),
+                     float(np.float32(value[i]))] for i in range(int(adr[s]), int(adr[s + 1]))]
+            if rows:
+                sc["params"] = rows
+        return type(self)(scn, self.command_dim, names=names)
 
     @classmethod
     def from_csr(cls, key_adr, key_t, key_cmd, push_adr, push_t, push_v, command_dim: int) -> "ScenarioTable":
@@ -123,11 +233,54 @@ class ScenarioTable:
         return cls(out, command_dim)
 
 
-def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = ()) -> Iterator[dict]:
+def _param_windows(s: int, rows) -> list:
+    """The ``"params"`` rows of scenario ``s``, checked for everything that needs no model."""
+    out = []
+    for r, row in enumerate(rows):
+        who = f"ScenarioTable: scenario {s}, parameter window {r}"
+        if not isinstance(row, (list, tuple)) or len(row) != 6:
+            raise ValueError(f"{who}: expected [t0, t1, field, index, op, value], got {row!r}")
+        t0, t1, field, index, op, value = row
+        try:
+            t0f, t1f, value = float(t0), float(t1), float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: times and value must be numbers, got {row!r}") from None
+        if not math.isfinite(value) or abs(value) > float(np.finfo(np.float32).max):   # (finite as float32 too)
+            raise ValueError(f"{who}: non-finite value")
+        if not (math.isfinite(t0f) and math.isfinite(t1f)) or t0f != int(t0f) or t1f != int(t1f) or not 0 <= t0f < MAX_TIME or not 0 <= t1f <= MAX_TIME:
+            raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
+        if t1f <= t0f:
+            raise ValueError(f"{who}: t1 {int(t1f)} is not after t0 {int(t0f)}")
+        if field in REFUSED_PARAM_FIELDS:
+            raise ValueError(f"{who}: field '{field}' is refused: body_mass, body_invweight0, dof_invweight0 and meaninertia are consistent only "
+                             "as a set that compile.env_constants computes in fp64 on the host; a payload change in mid-episode is out of scope")
+        if field not in PARAM_FIELDS:
+            raise ValueError(f"{who}: unknown field {field!r} (one of {', '.join(PARAM_FIELDS)})")
+        if op not in PARAM_OPS:
+            raise ValueError(f"{who}: unknown op {op!r} ('scale' or 'set')")
+        if isinstance(index, (bool, float)) or not isinstance(index, (int, np.integer, str)):
+            raise ValueError(f"{who}: index must be an int, a name or '*', got {index!r}")
+        out.append((int(t0f), int(t1f), field, index if isinstance(index, str) else int(index), op, value))
+    return out
+
+
+def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = (),
+          params: Iterable = ()) -> Iterator[dict]:
     """The cartesian product command rows x push speeds x directions x push times as scenarios, commands outermost: each holds its
     command from episode step 0 and one push of ``speed`` m/s along the world direction ``angle`` (radians about z, 0 = +x) held over
     ``(t0, t1)``.  With no speeds or no times the product is over the commands alone (no push).
-    ``len(list(sweep(C, V, D, T))) == len(C) * len(V) * len(D) * len(T)``."""
+    ``len(list(sweep(C, V, D, T))) == len(C) * len(V) * len(D) * len(T)``.  ``params``: a list of window lists (each a scenario's
+    ``"params"`` value, possibly empty) is one more cartesian axis, innermost: every scenario above is emitted once per window list,
+    ``len(...) * len(P)`` scenarios in all."""
+    params = [[list(w) for w in wins] for wins in params]
+    if params:
+        for sc in sweep(commands, push_speeds, directions, push_times):
+            for wins in params:
+                out = dict(sc)
+                if wins:
+                    out["params"] = [list(w) for w in wins]
+                yield out
+        return
     commands = [[float(x) for x in c] for c in commands]
     speeds, directions, times = [float(v) for v in push_speeds], [float(a) for a in directions], [tuple(int(x) for x in w) for w in push_times]
     if not speeds or not times:
@@ -169,6 +322,23 @@ def reference_schedule(table: ScenarioTable, mode, gid, t, ep, base_cmd):
             if t0 <= t[i] < t1:
                 mask[i], v[i] = True, pv
     return row, cmd, mask, v
+
+
+def reference_params(table: ScenarioTable, mode, gid, t, ep, base_params, layout: dict) -> np.ndarray:
+    """Numpy twin of ``scnparams_step_kernel`` for N envs: global ids ``gid``, episode steps ``t`` (meta word 0), episodes ended ``ep``
+    (meta word 11), the base parameter records ``base_params`` ``[N, stride]`` and ``layout`` (``param_layout``: word offset per
+    field).  Returns the effective records float32 ``[N, stride]``, exact: a word under no window that holds is the base word."""
+    gid, t = np.asarray(gid, dtype=np.int64).reshape(-1), np.asarray(t, dtype=np.int64).reshape(-1)
+    base = np.ascontiguousarray(base_params, dtype=np.float32).reshape(len(gid), -1)
+    eff = base.copy()
+    row = scenario_rows(len(table), mode, gid, np.asarray(ep).reshape(-1))
+    items = table._resolved()
+    for i in range(len(gid)):
+        for t0, t1, field, index, op, value in items[row[i]]:
+            if t0 <= t[i] < t1:
+                w = layout[_FIELD_NAMES[field]] + index
+                eff[i, w] = np.float32(value) if op == PARAM_OPS["set"] else base[i, w] * np.float32(value)
+    return eff
 
 
 def push_reference(quat, v) -> np.ndarray:

@@ -346,6 +346,37 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
                        const int32_t* push_adr, const int32_t* push_t, const float* push_v, int mode,
                        float* cmd_out_dev /*[N][command_dim]*/, int32_t* row_out_dev /*[N]*/, void* stream);
 
+/* Parameter windows: timed gain and friction changes per env, as rows of the scenario table that is set (the reference randomises PD
+ * gains, ground friction and joint friction loss once per robot, at construction; a window changes them while the robot runs).
+ * Scenario s owns the items [adr[s], adr[s + 1]), CSR as above (adr[n_scn + 1]); item i holds t[i] = (t0, t1), field[i] (0 kp, 1 kd --
+ * index = actuator; 2 geom_friction -- index = geom, the mixed ground-contact friction max(ground, geom) that cosim_set_param
+ * "geom_friction" sets; 3 dof_frictionloss -- index = dof), index[i], op[i] (0 scale, 1 set) and value[i].  With the clock t and the
+ * row rule of the scenario table, while t0 <= t < t1 word field[index] of the env's EFFECTIVE parameter record is base * value (scale:
+ * one fp32 multiply) or value (set); the last LISTED item of the row that names the word and holds wins; outside every window the
+ * word is the base value, bit for bit.  kp = kd = 0 gives exactly zero torque in both actuator modes: a limp joint.
+ * Base and effective records: the per-env parameter record that cosim_set_param, the host mirror, cosim_snapshot / cosim_restore and
+ * the history ring read and write stays the BASE record -- a snapshot taken inside a window holds base values.  While windows are set
+ * a second buffer holds the effective records, a kernel (cosim_scnparams.hip) rewrites a range's rows directly behind the scenario
+ * kernel, ahead of every launch of the control step on the range's own stream (and ahead of a reset's launch, for the envs under its
+ * mask, with t = 0), and every step kernel is handed the effective buffer instead of the base one.  The effective record is a
+ * function of (base record, state record, table): a restored run continues bit for bit once the same windows are set again.  The
+ * pointer travels as a kernel argument: set or clear the windows before capturing a graph; items of the count of the ones that are
+ * set are rewritten in place, and a captured graph picks the new values up.  The call joins the ranges, blocks until the device is
+ * idle, and writes every env's effective record once.
+ * n_scn = 0 clears the windows (no launch, pointer or byte then differs from an engine that never had any); otherwise n_scn must be
+ * the "scenario_rows" of the table that is set.  cosim_scenario_set with another S, or clearing the table, drops the windows.
+ * Validated on the host before anything is launched or changed, the message names the scenario and the item (COSIM_EINVAL): a
+ * non-finite value, t1 <= t0, times outside [0, 2^30), an unknown field or op, an index out of range, more than 256 items in a
+ * scenario, no table set or another S.  Fields 4 body_mass, 5 body_invweight0, 6 dof_invweight0 and 7 meaninertia are refused: they
+ * are consistent only as a set computed on the host in fp64, and a payload change in mid-episode is out of scope.
+ * cosim_rollout stays refused (a scenario table is set); cosim_profile_step and cosim_debug_forward read whatever effective records
+ * the last step left.  cosim_query "scenario_param_items" answers the number of items (0: none). */
+int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t /*[n][2]*/, const int32_t* field,
+                              const int32_t* index, const int32_t* op, const float* value);
+/* The effective parameter records float[N][param_stride] as the last step / reset / cosim_scenario_params_set left them (with no
+ * windows set: the base records), to host memory of `capacity` floats; joins the ranges first.  Returns param_stride. */
+int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
+
 /* Fall rules (the reference ends an episode early only through a robot's own _is_done, which is an empty body list for
  * flamingo_light_v1 and False for w4_p_v2 and humanoid_p_v0): the step kernels end an episode on the posture of the state a control
  * step ends in, per cause.  Evaluated once per control step (every step of a rollout launch, the last substep launch of the split
