@@ -622,7 +622,39 @@ struct KTraits {
   static constexpr bool NRM = CT ? HF : (HF || SC);
   static constexpr int MCPT = SC ? (NV >= 22 ? 12 : 8) : 0;
   using L = EnvLds<NV, NB, RPL, NRM, 64 / EPW, MCT, MCPT, HF, KM == 1>;
+  // Newton row loops (J^T f, Hessian tile): dense rows whose LDS reads are issued together ahead of one wait (8; 1: one row per
+  // trip and a wait each).  The FMA / MFMA order is the same for every width, so are the bits.  1 where the kernel has no
+  // registers to spare and the batch made it spill more (flamingo_p_v3's kernels, flamingo_light_v1's contact-twist plane
+  // kernels; the rollout kernels pass 1 to env_body themselves): DESIGN 4.2.
+  static constexpr int ROWB = (NV == 14 || (NV == 18 && !HF && MCT > 0)) ? 1 : 8;
 };
+
+// Ends a batch of LDS reads: the values pass through one statement, so all their reads are issued ahead of it and none of their
+// consumers moves above it (the compiler would otherwise pair each read with its use and wait once per pair).
+template <int N>
+__device__ __forceinline__ void lds_batch_join(float (&a)[N], float (&b)[N]) {
+  static_assert(N == 2 || N == 4 || N == 8, "batch widths of the row loops");
+  if constexpr (N == 8)
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(a[4]), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]),
+                                          "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]), "+v"(b[4]), "+v"(b[5]), "+v"(b[6]), "+v"(b[7]));
+  else if constexpr (N == 4)
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3]), "+v"(b[0]), "+v"(b[1]), "+v"(b[2]), "+v"(b[3]));
+  else
+    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(a[0]), "+v"(a[1]), "+v"(b[0]), "+v"(b[1]));
+}
+
+// Rows r .. r + N - 1 of qc += J^T f for dof `ln`: N rows' reads, one wait, then the FMAs in row order (explicit fmaf: written as
+// qc += j * f the batch comes out as packed multiplies and separate adds under the product build's SLP threshold).
+template <int N, class LDS>
+__device__ __forceinline__ float jtf_rows(LDS& S, const int ln, const int r, float qc) {
+  float jv[N], fv[N];
+#pragma unroll
+  for (int k = 0; k < N; k++) { jv[k] = S.J[r + k][ln]; fv[k] = S.w.r.rowf[r + k]; }
+  lds_batch_join(jv, fv);
+#pragma unroll
+  for (int k = 0; k < N; k++) qc = __builtin_fmaf(jv[k], fv[k], qc);
+  return qc;
+}
 
 // ------------------------------------------------------------------------------------------------ the kernel
 // HF: heightfield ground; SC: robot-robot (self) collision pairs; PROF: diagnostic build with s_memtime phase stamps;
@@ -641,7 +673,8 @@ typedef const KArgs __attribute__((address_space(4)))* KArgsP;
 // KMODE: -1 the general body (the mode is A.mode, a runtime value: reset, step and debug forward share the code); MODE_STEP the
 // step-only body: the mode is a constant, so no reset-mode branch and no debug dump is compiled in and A.mode is never read.  The
 // arithmetic of a step is the same instruction sequence in both (tests/test_gpu_step_kernel.py compares them bit for bit).
-template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, bool PROF, int EPW, int MCT, bool FIX, int KM = 0, int KMODE = -1>
+template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, bool PROF, int EPW, int MCT, bool FIX, int KM = 0, int KMODE = -1,
+          int ROWB = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::ROWB>
 __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::L (&SS)[EPW], const int wsel = 0,
                                          const int kstep = 0) {   // kstep: control step of a rollout launch (row of the [K][N][...] I/O buffers)
   static_assert(EPW == 1 || (EPW == 2 && !HF && !SC && NV <= 32 && NB <= 32), "two environments per wave: flat ground, no pairs");
@@ -2301,7 +2334,15 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
         float qc = 0.f;
         if (ln < NV) {
           qc = qcu;
-          for (int r = 0; r < ngen; r++) qc += S.J[r][ln] * S.w.r.rowf[r];
+          if constexpr (ROWB > 1) {
+            // one FMA chain in ascending row order, as below: full batches, then one of four rows, then single rows
+            int r = 0;
+            if constexpr (ROWB >= 8) for (; r + 8 <= ngen; r += 8) qc = jtf_rows<8>(S, ln, r, qc);
+            if (r + 4 <= ngen) { qc = jtf_rows<4>(S, ln, r, qc); r += 4; }
+            for (; r < ngen; r++) qc = __builtin_fmaf(S.J[r][ln], S.w.r.rowf[r], qc);
+          } else {
+            for (int r = 0; r < ngen; r++) qc += S.J[r][ln] * S.w.r.rowf[r];
+          }
           if constexpr (CT) {
             // J^T f of the ground contacts: cdof . (sum of the wrenches on the bodies this dof moves)
             float W[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
@@ -2353,17 +2394,47 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
             typedef float f32x16 __attribute__((ext_vector_type(16)));
             const int col = ln & 31, half = ln >> 5;
             f32x16 acc;
+            const int colc = col < NV ? col : 0;   // lanes past NV feed tile rows / columns that are never stored
 #pragma unroll
             for (int v = 0; v < 16; v++) {
               const int row = (v & 3) + 8 * (v >> 2) + 4 * half;
-              acc[v] = (row < NV && col < NV) ? S.M[row < NV ? row : 0][col < NV ? col : 0] : 0.f;
+              if constexpr (ROWB > 1) {
+                // read by every lane and selected afterwards: the tile's reads are in flight together, no branch around each.  Rows past
+                // NV in both halves: zero without a read; rows below it in both: a constant offset from the lane's base
+                const int rlo = (v & 3) + 8 * (v >> 2);
+                if (rlo >= NV) acc[v] = 0.f;
+                else if (rlo + 4 < NV) { const float m = S.M[row][colc]; acc[v] = col < NV ? m : 0.f; }
+                else { const float m = S.M[row < NV ? row : 0][colc]; acc[v] = (row < NV && col < NV) ? m : 0.f; }
+              } else {
+                acc[v] = (row < NV && col < NV) ? S.M[row < NV ? row : 0][colc] : 0.f;
+              }
             }
-            const int colc = col < NV ? col : 0;   // lanes past NV feed tile rows / columns that are never stored
-            for (int r0 = 0; r0 < ngen; r0 += 2) {
-              const int r = r0 + half;
-              const float jv = r < ngen ? S.J[r < ngen ? r : 0][colc] : 0.f;
-              const float dv = S.w.r.rowD[r < ngen ? r : 0];
-              acc = __builtin_amdgcn_mfma_f32_32x32x2f32(jv * dv, jv, acc, 0, 0, 0);
+            if constexpr (ROWB > 1) {
+              // HB instructions' operands per wait; the instructions themselves in the order of the one-per-trip loop, on the one
+              // accumulator, and none for row pairs past ngen (the test is the same for the whole wave)
+              constexpr int HB = ROWB / 2;
+              for (int r0 = 0; r0 < ngen; r0 += 2 * HB) {
+                float jv[HB], dv[HB];
+#pragma unroll
+                for (int k = 0; k < HB; k++) {
+                  const int r = r0 + 2 * k + half, rc = r < ngen ? r : 0;
+                  jv[k] = S.J[rc][colc];
+                  dv[k] = S.w.r.rowD[rc];
+                }
+                lds_batch_join(jv, dv);
+#pragma unroll
+                for (int k = 0; k < HB; k++) {
+                  const float j = r0 + 2 * k + half < ngen ? jv[k] : 0.f;
+                  if (r0 + 2 * k < ngen) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(j * dv[k], j, acc, 0, 0, 0);
+                }
+              }
+            } else {
+              for (int r0 = 0; r0 < ngen; r0 += 2) {
+                const int r = r0 + half;
+                const float jv = r < ngen ? S.J[r < ngen ? r : 0][colc] : 0.f;
+                const float dv = S.w.r.rowD[r < ngen ? r : 0];
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(jv * dv, jv, acc, 0, 0, 0);
+              }
             }
 #pragma unroll
             for (int v = 0; v < 16; v++) {
@@ -3129,7 +3200,7 @@ __global__ __launch_bounds__(64, waves_per_simd(163840 / (int)sizeof(typename KT
   const int K = A.roll_steps;
 #pragma nounroll
   for (int k = 0; k < K; k++) {
-    env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, false, 0, KMODE>(kargs_p, env, SS, 0, k);
+    env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, false, 0, KMODE, 1>(kargs_p, env, SS, 0, k);   // row batch 1: KTraits::ROWB
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (A.ovf != nullptr && __builtin_amdgcn_readfirstlane(A.ovf[env]) != 0) break;   // abandoned at step k: the fix kernel continues
