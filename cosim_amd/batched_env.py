@@ -85,7 +85,7 @@ class BatchedEnv:
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
                  spawn=None, history=None, ledger: Optional[int] = None, scenarios=None, scenario_mode: Optional[str] = None,
-                 fall=None, failure_traces=None, streams: Optional[int] = None):
+                 fall=None, failure_traces=None, streams: Optional[int] = None, check_slots: Optional[int] = None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -119,6 +119,11 @@ class BatchedEnv:
         ``scenarios``: a scenario table -- a ``ScenarioTable``, a list of scenarios, ``{"scenarios": [...]}`` or a YAML file
         (``cosim_amd/scenario.py``) -- with ``scenario_mode`` ``"env"`` (default) or ``"cycle"``, see ``set_scenarios``.  Default:
         ``config["engine"].get("scenarios")`` / ``config["engine"].get("scenario_mode")`` / none.
+
+        ``check_slots``: arm the checks the scenario table holds (a scenario's ``"checks"``, ``cosim_amd/scenario.py``): the engine
+        judges them on the device and keeps the last ``check_slots`` (1..64) verdict records of every env, see ``set_scenarios`` /
+        ``verdicts()``.  Default: ``config["engine"].get("check_slots")`` / none: a table's checks are carried but not evaluated,
+        and no launch, pointer or byte differs from a table without checks.
 
         ``fall``: a fall rule -- a ``FallRule`` or a dict ``{"tilt", "height", "grace", "bodies"}`` (``cosim_amd/fall.py``) -- see
         ``set_fall``.  Default: ``config["engine"].get("fall")`` / none: an episode ends early only through the robot's own
@@ -258,9 +263,11 @@ class BatchedEnv:
             self.set_failure_traces(failure_traces)
         self.scenario_table, self.scenario_mode = None, "env"
         self._cmd_out = self._row_out = None
+        self.check_slots = 0
         scenarios = scenarios if scenarios is not None else eng_cfg.get("scenarios")
         if scenarios is not None:
-            self.set_scenarios(scenarios, scenario_mode if scenario_mode is not None else eng_cfg.get("scenario_mode", "env"))
+            self.set_scenarios(scenarios, scenario_mode if scenario_mode is not None else eng_cfg.get("scenario_mode", "env"),
+                               check_slots=check_slots if check_slots is not None else eng_cfg.get("check_slots"))
 
     # ------------------------------------------------------------------ domain randomisation (XMLManager step 3)
     def _randomise(self, gain_noise: float):
@@ -632,7 +639,7 @@ class BatchedEnv:
         return buf.view(t.int32)[:, 15].clone()
 
     # ------------------------------------------------------------------ scenario table (cosim_scenario_set)
-    def set_scenarios(self, scenarios, mode: str = "env"):
+    def set_scenarios(self, scenarios, mode: str = "env", check_slots: Optional[int] = None):
         """Give every env its own test: a table of S scenarios, each a command schedule and a push schedule keyed by the env's own
         episode step (``cosim_amd/scenario.py``; ``None`` clears the table).  Env with global id ``g`` runs row ``g mod S`` (mode
         ``"env"``) or, in mode ``"cycle"`` (needs ``auto_reset``), row ``(g + episodes it has ended) mod S``: one scenario per
@@ -644,13 +651,24 @@ class BatchedEnv:
         follows its slot's id, shards with the same table give one fleet's results.  Limits: the table is not part of a
         ``snapshot()``; host commands and pushes still work, a scenario keyframe / push due in the same step overrides them;
         ``rollout()`` raises while a table is set.  Raises ``ValueError`` naming the scenario and the row for a malformed table.
-        Joins the range streams and blocks until the device is idle."""
+        Joins the range streams and blocks until the device is idle.
+
+        ``check_slots`` (1..64) arms the table's checks (``cosim_scenario_checks_set``): behind every control step the engine samples
+        every item of the env's scenario whose window holds at the step's pre-step episode clock -- the clock this step's keyframes
+        and pushes were keyed on -- and closes the items into one verdict record when the episode ends, on the device, with no host
+        read; ``verdicts()`` reads them.  Every call begins every env's episode anew for the checks (flag 8 on a stepped fleet);
+        ``reset()``, ``restore`` and ``set_state`` do so for the envs they touch, and an episode the host cuts leaves no record.
+        Items of the same counts are rewritten in place (captured graphs pick them up).  ``None`` / 0: the checks are not
+        evaluated (what an earlier call armed is cleared).  Set the ledger, the traces and the checks together and their episode
+        ordinals agree.  Limits: state signals take no sample on a step that ends the episode; checks are not part of a
+        ``snapshot()``."""
         from .scenario import MODES, ScenarioTable
         t = self.torch
         if scenarios is None:
             self.engine.scenario_set(None, 0, None, None, self._stream())
             self.scenario_table, self.scenario_mode = None, "env"
             self._info_views = None
+            self.check_slots = 0
             return
         if mode not in MODES:
             raise ValueError(f"set_scenarios: mode must be 'env' or 'cycle', got {mode!r}")
@@ -659,6 +677,9 @@ class BatchedEnv:
             table.resolve(self.param_names())
         elif table.has_params:
             self._check_param_items(table)
+        check_slots = int(check_slots or 0)
+        if check_slots and table.has_checks:                        # names and ranges against this env's model
+            table.resolve_checks(self.check_names())
         if self._cmd_out is None:                                   # persistent: captured graphs hold these pointers
             self._cmd_out = t.zeros_like(self.user_command)
             self._row_out = t.zeros((self.num_envs,), dtype=t.int32, device=self.device)
@@ -669,6 +690,7 @@ class BatchedEnv:
             if self.engine.query("scenario_rows") == 0:             # the engine dropped its table (a failed upload): so does the env
                 self.scenario_table, self.scenario_mode = None, "env"
                 self._info_views = None
+                self.check_slots = 0
             raise
         self.scenario_table, self.scenario_mode = table, mode
         self._info_views = None
@@ -677,6 +699,36 @@ class BatchedEnv:
             self.engine.scenario_params_set(table.pack_params())
         elif self.engine.query("scenario_param_items") > 0:
             self.engine.scenario_params_set(None)
+        # so do the checks, once they are armed
+        self.check_slots = 0
+        if check_slots and table.has_checks:
+            self.engine.scenario_checks_set(table.pack_checks(), check_slots)
+            self.check_slots = check_slots
+        elif self.engine.query("scenario_check_items") > 0:
+            self.engine.scenario_checks_set(None)
+
+    def check_names(self) -> dict:
+        """What a check's ``index`` is resolved against on this env (``scenario.check_names``)."""
+        from .scenario import check_names
+        return check_names(self.cm, self.info_dim, self.command_dim)
+
+    def verdicts(self, include_open: bool = False):
+        """The verdicts of the fleet's episodes so far as a ``Verdicts`` (``cosim_amd/checks.py``): one row per ended episode still in
+        the ring, sorted by (global env id, episode), with the fail / incomplete / passed flag, the value and the step of every item
+        of its scenario.  ``include_open``: also the episodes still running (flag 16).  Joins the range streams and reads the device
+        once; nothing is read per step.  Raises ``ValueError`` if no checks are armed."""
+        from .checks import Verdicts
+        if self.check_slots <= 0:
+            raise ValueError("verdicts(): no checks are armed (BatchedEnv(scenarios=TABLE, check_slots=SLOTS) or set_scenarios(..., check_slots=))")
+        t = self.torch
+        W = self.engine.query("scenario_check_words")
+        rec = t.empty((self.num_envs, self.check_slots, W), dtype=t.int32, device=self.device)
+        cnt = t.empty((self.num_envs,), dtype=t.int32, device=self.device)
+        opn = t.empty((self.num_envs, W), dtype=t.int32, device=self.device) if include_open else None
+        self.engine.scenario_checks_get(rec.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
+        t.cuda.current_stream(self.device).synchronize()
+        return Verdicts.from_raw(rec.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, self.scenario_table,
+                                 self.env_id0)
 
     def param_names(self) -> dict:
         """The names a parameter window's ``index`` may use on this env, per field (``scenario.param_names``)."""

@@ -104,6 +104,12 @@ def main(argv=None) -> int:
     ap.add_argument("--failure-traces-on", nargs="+", default=None, metavar="NAME",
                     help="causes that freeze a window: terminated truncated nonfinite tilt height contact (default: terminated nonfinite)")
     ap.add_argument("--failure-traces-out", default=None, metavar="PATH.npz", help="with --failure-traces: write this rank's traces here")
+    ap.add_argument("--check-slots", type=int, default=None, metavar="SLOTS",
+                    help="judge the checks of the scenario table on the device and keep the last SLOTS (1..64) verdict records of every env; "
+                         "their summary goes into the report as \"episodes.checks\" (also under --graph / --pipelined)")
+    ap.add_argument("--verdicts-out", default=None, metavar="PATH.npz", help="with --check-slots: write this rank's verdict records here")
+    ap.add_argument("--require-pass", action="store_true",
+                    help="with --check-slots: exit status 3 if any ended episode failed a check (a sweep can gate a CI job)")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -116,7 +122,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces", "check_slots"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -183,6 +189,13 @@ def main(argv=None) -> int:
     scenario_mode = pick(args.scenario_mode, sess.get("scenario_mode", s_eng.get("scenario_mode")), "env")
     if scenario_mode not in ("env", "cycle"):
         ap.error("scenario_mode: env or cycle")
+    args.check_slots = int(pick(args.check_slots, sess.get("check_slots") if sess.get("check_slots") is not None else s_eng.get("check_slots"), 0))
+    if not 0 <= args.check_slots <= 64:
+        ap.error("--check-slots SLOTS: 1..64")
+    if (args.verdicts_out or args.require_pass) and args.check_slots < 1:
+        ap.error("--verdicts-out / --require-pass need --check-slots SLOTS")
+    if args.check_slots and scenarios is None:
+        ap.error("--check-slots needs --scenarios: checks are rows of a scenario table")
     # fall rule: the session's dict (top level or engine.fall), overridden key by key by the flags
     fall = dict(sess.get("fall") or s_eng.get("fall") or {})
     for key, val in (("tilt", args.fall_tilt), ("height", args.fall_height), ("grace", args.fall_grace)):
@@ -240,7 +253,9 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, failure_traces=ftrace or False, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, failure_traces=ftrace or False, check_slots=args.check_slots or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+    if args.check_slots and env.check_slots < 1:
+        ap.error("--check-slots: the scenario table holds no checks")
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:
@@ -313,6 +328,10 @@ def main(argv=None) -> int:
     if args.failure_traces_out:
         path = args.failure_traces_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.failure_traces_out)[:1], rank, os.path.splitext(args.failure_traces_out)[1])
         traces.save(path)
+    verdicts = env.verdicts() if args.check_slots else None          # verdict records stay per rank too
+    if args.verdicts_out:
+        path = args.verdicts_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.verdicts_out)[:1], rank, os.path.splitext(args.verdicts_out)[1])
+        verdicts.save(path)
     if args.checkpoint and "checkpoint" not in used:
         print(f"warning: --checkpoint-at {args.checkpoint_at} was not reached, no snapshot written", file=sys.stderr)
     out = rep.save(args.report, extra={"snapshot": used} if used else None) if (args.report and rank == 0) else rep.summary()
@@ -323,7 +342,9 @@ def main(argv=None) -> int:
                           **({"snapshot": used} if used else {}),
                           **({"episodes": {k: out["episodes"][k] for k in ("episodes", "terminated", "truncated", "non_finite", "lost", "length") +
                                            (("fell", "fell_tilt", "fell_height", "fell_contact") if env.fall_rule is not None else ())}}
-                             if "episodes" in out else {}),
+                             if "terminated" in out.get("episodes", {}) else {}),
+                          **({"checks": {k: v for k, v in out["episodes"]["checks"].get("fleet", out["episodes"]["checks"]).items()
+                                         if k not in ("checks", "by_scenario")}} if verdicts is not None else {}),
                           **({"failure_traces": traces.summary()} if traces is not None else {}),
                           **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
                              if "by_scenario" in out.get("episodes", {}) else {}),
@@ -332,6 +353,10 @@ def main(argv=None) -> int:
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()
+    if args.require_pass:                                            # every rank judges the fleet's count (all-reduced in the report)
+        c = out["episodes"]["checks"]
+        if c.get("fleet", c)["episodes_failed"] > 0:
+            return 3
     return 0
 
 

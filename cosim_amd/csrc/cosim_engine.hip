@@ -19,6 +19,7 @@
 #include "cosim_ftrace.hip"
 #include "cosim_scenario.hip"
 #include "cosim_scnparams.hip"
+#include "cosim_checks.hip"
 #include "cosim_plan.h"
 #include "cosim_ranges.h"
 
@@ -142,6 +143,17 @@ struct cosim_engine {
   char* d_scnpar = nullptr;       // one allocation: adr | t | word | op | value
   ScnParTable scnpar = {};        // device pointers into d_scnpar; n_items 0: no windows, no launches, the step kernels read d_params
   float* d_params_eff = nullptr;  // [n_envs][p_stride] effective records: what base_args hands the step kernels while windows are set
+  // checks of the scenario table (cosim_scenario_checks_set, cosim_checks.hip): checks_step_kernel behind every range's last launch of a
+  // step, behind the ledger's
+  char* d_chk = nullptr;          // one allocation: adr | t | signal | index | mode | cmp | bound
+  ChkTable chk = {};              // device pointers into d_chk; n_scn 0: no checks, no launches
+  float* d_chk_ext = nullptr;     // [n_envs][I]
+  int* d_chk_aux = nullptr;       // [n_envs][I]
+  int* d_chk_n = nullptr;         // [n_envs][I]
+  double* d_chk_sum = nullptr;    // [n_envs][I]
+  int* d_chk_cnt = nullptr;       // [n_envs][CHK_NCNT]
+  int* d_chk_rec = nullptr;       // [n_envs][chk_slots][8 + 2 I]
+  int chk_slots = 0;
   // fall rules (cosim_fall_set): kernel arguments of every step launch; fall_mask 0 = none (meta word 15 is not written)
   float fall_min_up = -1.f, fall_min_height = 0.f;
   int fall_grace = 0, fall_mask = 0;
@@ -675,8 +687,55 @@ static int scnparams_launch(cosim_engine* e, int first, int count, const uint8_t
   return COSIM_OK;
 }
 
+// ---- checks of the scenario table (cosim_checks.hip)
+static const char* const CHECKS_INFO_MSG =
+    ": scenario checks are set (cosim_scenario_checks_set) and info_out_dev is NULL: the checks sample the step's info row; pass an "
+    "info buffer or clear the checks";
+
+static ChkArgs checks_args(cosim_engine* e) {
+  ChkArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->chk; a.state = e->d_state; a.scn_row = e->scn_row_out;
+  a.ext = e->d_chk_ext; a.aux = e->d_chk_aux; a.n = e->d_chk_n; a.sum = e->d_chk_sum; a.cnt = e->d_chk_cnt; a.rec = e->d_chk_rec;
+  a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
+  a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.cmd_stride = e->ho.command_dim;
+  a.s_stride = e->lay.s_stride; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.s_meta = e->lay.s_meta; a.slots = e->chk_slots;
+  a.scn_mode = e->scn.mode; a.scn_off = e->scn.gid_off;
+  return a;
+}
+
+// this step's samples of envs [first, first + count), behind the launches that wrote the step's outputs on the same stream
+static int checks_step(cosim_engine* e, int first, int count, const float* cmd, const float* info, const uint8_t* term, const uint8_t* trunc,
+                       hipStream_t s) {
+  ChkArgs a = checks_args(e);
+  a.cmd = a.cmd_stride > 0 ? cmd : nullptr; a.info = info; a.term = term; a.trunc = trunc;
+  a.first = first; a.count = count;
+  hipLaunchKernelGGL(checks_step_kernel, dim3((count + CHK_WAVES - 1) / CHK_WAVES), dim3(64 * CHK_WAVES), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode with clean accumulators
+static int checks_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
+  if (e->chk.n_scn <= 0) return COSIM_OK;
+  ChkArgs a = checks_args(e);
+  a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
+  hipLaunchKernelGGL(checks_begin_kernel, dim3((e->n_envs + CHK_WAVES - 1) / CHK_WAVES), dim3(64 * CHK_WAVES), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// the checks go with their table (the caller has waited for the device)
+static void checks_free(cosim_engine* e) {
+  (void)hipFree(e->d_chk); (void)hipFree(e->d_chk_ext); (void)hipFree(e->d_chk_aux); (void)hipFree(e->d_chk_n); (void)hipFree(e->d_chk_sum);
+  (void)hipFree(e->d_chk_cnt); (void)hipFree(e->d_chk_rec);
+  e->d_chk = nullptr; e->d_chk_ext = nullptr; e->d_chk_aux = nullptr; e->d_chk_n = nullptr; e->d_chk_sum = nullptr; e->d_chk_cnt = nullptr;
+  e->d_chk_rec = nullptr; e->chk_slots = 0; memset(&e->chk, 0, sizeof e->chk);
+}
+
 static void scenario_free(cosim_engine* e) {
   scnparams_free(e);
+  checks_free(e);
   (void)hipFree(e->d_scn);
   e->d_scn = nullptr; memset(&e->scn, 0, sizeof e->scn); e->scn_nkey = 0; e->scn_npush = 0; e->scn_cmd_out = nullptr; e->scn_row_out = nullptr;
 }
@@ -1038,6 +1097,9 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "ftrace_mask") return e->ft_mask;      // ledger flags that freeze a window
   if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
   if (n == "scenario_param_items") return e->scnpar.n_items;   // expanded parameter-window items of the table (0: none, no launches)
+  if (n == "scenario_check_items") return e->chk.n_scn > 0 ? e->chk.I : 0;   // I: items per env a verdict record holds (0: no checks, no launches)
+  if (n == "scenario_check_slots") return e->chk_slots;                      // verdict records per env
+  if (n == "scenario_check_words") return e->chk.n_scn > 0 ? checks_words(e->chk.I) : 0;   // 32-bit words of a verdict record: 8 + 2 I
   if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
   if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
@@ -1168,7 +1230,9 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   if (mask_dev == nullptr) e->stepped = false;
   rc = ledger_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);   // behind the reset: meta[14] is the new episode's spawn row
   if (rc) return rc;
-  return ftrace_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
+  rc = ftrace_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
+  if (rc) return rc;
+  return checks_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* commands_dev, float* state_out_dev, uint8_t* terminated_dev,
@@ -1340,6 +1404,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   if (e->sw.epw == 2 && ((first | count) & 1)) return fail(COSIM_EINVAL, "cosim_step_range: two-environments-per-wave kernel needs even ranges");
   if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + LEDGER_INFO_MSG);
   if (e->ft_frames > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + FTRACE_INFO_MSG);
+  if (e->chk.n_scn > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + CHECKS_INFO_MSG);
   e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
@@ -1393,7 +1458,9 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   // episode ledger: this step's rows of the range, behind the range's last launch of the step (plain device work: capturable)
   if (e->led_slots > 0) { rc = ledger_step(e, first, count, 1, info_out_dev, terminated_dev, truncated_dev, scenario_cmd(e, commands_dev), s); if (rc) return rc; }
   // failure traces: this step's frame of the range, behind the ledger's launch (reads the caller's action rows: they outlive the step)
-  if (e->ft_frames > 0) return ftrace_step(e, first, count, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
+  if (e->ft_frames > 0) { rc = ftrace_step(e, first, count, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s); if (rc) return rc; }
+  // scenario checks: this step's samples of the range, behind the ledger's launch (they only read what the step wrote)
+  if (e->chk.n_scn > 0) return checks_step(e, first, count, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
   return COSIM_OK;
 }
 
@@ -1542,7 +1609,9 @@ int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* st
   e->stepped = true;
   rc = ledger_begin(e, nullptr, nullptr, 0, LEDGER_NO_RESET, (hipStream_t)stream);
   if (rc) return rc;
-  return ftrace_begin(e, nullptr, nullptr, 0, FT_NO_RESET, (hipStream_t)stream);
+  rc = ftrace_begin(e, nullptr, nullptr, 0, FT_NO_RESET, (hipStream_t)stream);
+  if (rc) return rc;
+  return checks_begin(e, nullptr, nullptr, 0, CHK_NO_RESET, (hipStream_t)stream);
 }
 
 int cosim_snapshot(cosim_engine_t* e, float* out_dev, void* stream) {
@@ -1593,6 +1662,8 @@ int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const
   rc = ledger_begin(e, mask_dev, src_index_dev, snap_rows, LEDGER_NO_RESET, cs);
   if (rc) return rc;
   rc = ftrace_begin(e, mask_dev, src_index_dev, snap_rows, FT_NO_RESET, cs);
+  if (rc) return rc;
+  rc = checks_begin(e, mask_dev, src_index_dev, snap_rows, CHK_NO_RESET, cs);
   if (rc) return rc;
   if (src_index_dev && cap == hipStreamCaptureStatusNone) {   // the kernel skipped what it refused; report it
     HIP_TRY(hipMemcpyAsync(e->h_snap_err, e->d_snap_err, 2 * sizeof(int), hipMemcpyDeviceToHost, cs));
@@ -1799,7 +1870,7 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
     return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
   }
   if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
-  if (n_scn != e->scn.n_scn) scnparams_free(e);   // parameter windows are rows of the table they were set for: another S drops them
+  if (n_scn != e->scn.n_scn) { scnparams_free(e); checks_free(e); }   // parameter windows and checks are rows of the table they were set for: another S drops them
   const int32_t* base = reinterpret_cast<const int32_t*>(e->d_scn);
   e->scn.key_adr = base + o_kadr; e->scn.push_adr = base + o_padr; e->scn.key_t = base + o_kt; e->scn.push_t = base + o_pt;
   e->scn.key_cmd = reinterpret_cast<const float*>(base + o_kc); e->scn.push_v = reinterpret_cast<const float*>(base + o_pv);
@@ -1921,6 +1992,147 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity) {
   HIP_TRY(hipDeviceSynchronize());
   HIP_TRY(hipMemcpy(host, e->scnpar.n_items > 0 ? e->d_params_eff : e->d_params, words * sizeof(float), hipMemcpyDeviceToHost));
   return e->lay.p_stride;
+}
+
+// Checks of the scenario table that is set: validate on the host (a message that names the scenario and the item), join the ranges,
+// wait for the device, upload, and begin every env's episode with clean accumulators.  Items of the counts of the ones that are set
+// (same S, same row addresses, same slots) are rewritten in place: the device pointers, the counters and the records stay, and
+// captured graphs pick the new values up.
+int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t, const int32_t* signal, const int32_t* index,
+                              const int32_t* mode, const int32_t* cmp, const float* bound, int slots) {
+  if (!e) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_scn == 0) {   // clear (launches in flight still read the items: wait for them)
+    int rc = join_ranges(e, 0);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    checks_free(e);
+    return COSIM_OK;
+  }
+  if (e->scn.n_scn == 0)
+    return fail(COSIM_EINVAL, "cosim_scenario_checks_set: no scenario table is set (cosim_scenario_set): checks are rows of a table; set the table first");
+  if (n_scn != e->scn.n_scn)
+    return fail(COSIM_EINVAL, "cosim_scenario_checks_set: " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.n_scn));
+  if (slots < 1 || slots > CHK_MAX_SLOTS) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: slots " + std::to_string(slots) + " outside 1..64");
+  if (!adr) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: null argument");
+  if (adr[0] != 0) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: adr[0] must be 0");
+  const cosim_model_t& m = e->model;
+  const int ncmd = e->ho.command_dim < 3 ? e->ho.command_dim : 3;
+  int most = 0;
+  for (int s = 0; s < n_scn; s++) {
+    const long long ni = (long long)adr[s + 1] - adr[s];
+    const std::string who = "cosim_scenario_checks_set: scenario " + std::to_string(s);
+    if (ni < 0) return fail(COSIM_EINVAL, who + ": row addresses must not decrease");
+    if (ni > CHK_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(ni) + " check items, at most 64");
+    if (ni > 0 && (!t || !signal || !index || !mode || !cmp || !bound)) return fail(COSIM_EINVAL, who + ": null table array");
+    if ((int)ni > most) most = (int)ni;
+    for (int i = adr[s]; i < adr[s + 1]; i++) {
+      const std::string row = who + ", check item " + std::to_string(i - adr[s]);
+      const int t0 = t[2 * i], t1 = t[2 * i + 1];
+      if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": times outside [0, 2^30)");
+      if (t1 <= t0) return fail(COSIM_EINVAL, row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0));
+      int width;
+      const char* name;
+      switch (signal[i]) {
+        case CHK_INFO: width = e->ho.info_dim; name = "info"; break;
+        case CHK_ABS_INFO: width = e->ho.info_dim; name = "abs_info"; break;
+        case CHK_TRACKING_ERROR: width = ncmd; name = "tracking_error"; break;
+        case CHK_TORQUE_MAX: width = 1; name = "torque_max"; break;
+        case CHK_UP: width = m.nq >= 7 ? 1 : 0; name = "up"; break;
+        case CHK_QPOS: width = m.nq; name = "qpos"; break;
+        case CHK_QVEL: width = m.nv; name = "qvel"; break;
+        case CHK_ABS_QVEL: width = m.nv; name = "abs_qvel"; break;
+        default:
+          return fail(COSIM_EINVAL, row + ": unknown signal " + std::to_string(signal[i]) +
+                                        " (0 info, 1 abs_info, 2 tracking_error, 3 torque_max, 4 up, 5 qpos, 6 qvel, 7 abs_qvel)");
+      }
+      if (index[i] < 0 || index[i] >= width)
+        return fail(COSIM_EINVAL, row + ": index " + std::to_string(index[i]) + " out of range: " + name + " has " + std::to_string(width) + " entries");
+      if (mode[i] < 0 || mode[i] >= CHK_NMODE) return fail(COSIM_EINVAL, row + ": unknown mode " + std::to_string(mode[i]) + " (0 always, 1 settle, 2 mean)");
+      if (cmp[i] != CHK_LT && cmp[i] != CHK_GT) return fail(COSIM_EINVAL, row + ": unknown cmp " + std::to_string(cmp[i]) + " (0 <, 1 >)");
+      if (!std::isfinite(bound[i])) return fail(COSIM_EINVAL, row + ": bound is not finite");
+    }
+  }
+  const int n = adr[n_scn];
+  if (n == 0) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: the table holds no check item (n_scn = 0 clears the checks)");
+  const int I = (most + 1) & ~1;
+  int rc = join_ranges(e, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());   // launches in flight may still read the items
+  // adr | t | signal | index | mode | cmp | bound, every array 4-byte words
+  const size_t o_adr = 0, o_t = o_adr + (size_t)n_scn + 1, o_s = o_t + 2 * (size_t)n, o_i = o_s + (size_t)n, o_m = o_i + (size_t)n,
+               o_c = o_m + (size_t)n, o_b = o_c + (size_t)n, total = o_b + (size_t)n;
+  std::vector<int32_t> h(total, 0);
+  memcpy(&h[o_adr], adr, ((size_t)n_scn + 1) * 4);
+  memcpy(&h[o_t], t, 2 * (size_t)n * 4);
+  memcpy(&h[o_s], signal, (size_t)n * 4);
+  memcpy(&h[o_i], index, (size_t)n * 4);
+  memcpy(&h[o_m], mode, (size_t)n * 4);
+  memcpy(&h[o_c], cmp, (size_t)n * 4);
+  memcpy(&h[o_b], bound, (size_t)n * 4);
+  bool in_place = e->chk.n_scn == n_scn && e->chk.n_items == n && e->chk.I == I && e->chk_slots == slots;
+  if (in_place) {   // the same counts row by row?  (the row addresses set are read back: cold path)
+    std::vector<int32_t> old((size_t)n_scn + 1);
+    HIP_TRY(hipMemcpy(old.data(), e->d_chk, old.size() * 4, hipMemcpyDeviceToHost));
+    in_place = memcmp(old.data(), adr, old.size() * 4) == 0;
+  }
+  if (in_place) {   // pointers, counters and records stay; the open episodes begin again, as below: no verdict mixes two sets of values
+    const hipError_t r = hipMemcpy(e->d_chk, h.data(), total * 4, hipMemcpyHostToDevice);
+    if (r != hipSuccess) { checks_free(e); return fail(COSIM_EHIP, std::string("cosim_scenario_checks_set: ") + hipGetErrorString(r)); }
+    rc = checks_begin(e, nullptr, nullptr, 0, e->stepped ? CHK_NO_RESET : 0, 0);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    return COSIM_OK;
+  }
+  checks_free(e);
+  const size_t N = (size_t)e->n_envs, W = (size_t)checks_words(I);
+  auto alloc = [&]() -> hipError_t {
+    hipError_t r;
+    if ((r = hipMalloc(&e->d_chk, total * 4)) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_chk_ext, N * I * sizeof(float))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_chk_aux, N * I * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_chk_n, N * I * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_chk_sum, N * I * sizeof(double))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_chk_cnt, N * CHK_NCNT * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_chk_rec, N * slots * W * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMemset(e->d_chk_cnt, 0, N * CHK_NCNT * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMemset(e->d_chk_rec, 0, N * slots * W * sizeof(int))) != hipSuccess) return r;
+    return hipMemcpy(e->d_chk, h.data(), total * 4, hipMemcpyHostToDevice);
+  };
+  const hipError_t r = alloc();
+  if (r != hipSuccess) { checks_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_checks_set: ") + hipGetErrorString(r)); }
+  const int32_t* base = reinterpret_cast<const int32_t*>(e->d_chk);
+  e->chk.adr = base + o_adr; e->chk.t = base + o_t; e->chk.signal = base + o_s; e->chk.index = base + o_i; e->chk.mode = base + o_m;
+  e->chk.cmp = base + o_c; e->chk.bound = reinterpret_cast<const float*>(base + o_b);
+  e->chk.n_scn = n_scn; e->chk.n_items = n; e->chk.I = I;
+  e->chk_slots = slots;
+  // every env starts an open episode with clean accumulators at its current clock (the range streams do not order with the null
+  // stream: wait here, cold path)
+  rc = checks_begin(e, nullptr, nullptr, 0, e->stepped ? CHK_NO_RESET : 0, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return COSIM_OK;
+}
+
+// The verdict rings int32[N][slots][words], the ended-episode counts int32[N] and (or NULL) the open episodes as flag-16 records
+// int32[N][words]; joins the ranges, asynchronous on the caller's stream otherwise.
+int cosim_scenario_checks_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream) {
+  if (!e || !records_dev || !counts_dev) return fail(COSIM_EINVAL, "cosim_scenario_checks_get: null argument");
+  if (e->chk.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_checks_get: no checks are set (cosim_scenario_checks_set)");
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t cs = (hipStream_t)stream;
+  int rc = join_ranges(e, cs);
+  if (rc) return rc;
+  const size_t N = (size_t)e->n_envs, W = (size_t)checks_words(e->chk.I);
+  HIP_TRY(hipMemcpyAsync(records_dev, e->d_chk_rec, N * e->chk_slots * W * sizeof(int), hipMemcpyDeviceToDevice, cs));
+  HIP_TRY(hipMemcpy2DAsync(counts_dev, sizeof(int), e->d_chk_cnt, CHK_NCNT * sizeof(int), sizeof(int), N, hipMemcpyDeviceToDevice, cs));
+  if (open_dev) {
+    ChkArgs a = checks_args(e);
+    a.rec = open_dev;
+    hipLaunchKernelGGL(checks_open_kernel, dim3((e->n_envs + CHK_WAVES - 1) / CHK_WAVES), dim3(64 * CHK_WAVES), 0, cs, a);
+    HIP_TRY(hipGetLastError());
+  }
+  return COSIM_OK;
 }
 
 __global__ void push_kernel(float* state, Layout lay, const float* v, const uint8_t* mask, int n) {

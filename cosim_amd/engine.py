@@ -113,6 +113,8 @@ def load_library():
     L.cosim_scenario_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
     L.cosim_scenario_params_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
     L.cosim_scenario_params_get.argtypes = [vp, vp, ci]
+    L.cosim_scenario_checks_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]
+    L.cosim_scenario_checks_get.argtypes = [vp, vp, vp, vp, vp]
     L.cosim_fall_set.argtypes = [vp, ctypes.c_float, ctypes.c_float, ci, vp, ci]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
@@ -125,7 +127,7 @@ def load_library():
                "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
                "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get",
                "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get", "cosim_scenario_params_set",
-               "cosim_scenario_params_get"):
+               "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -141,7 +143,7 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
            "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
            "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get",
-           "cosim_scenario_params_set", "cosim_scenario_params_get"]
+           "cosim_scenario_params_set", "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -370,6 +372,29 @@ class Engine:
             raise ValueError(f"scenario_params_set: the item arrays are shorter than their row addresses ({n} items)")
         self._check(self.L.cosim_scenario_params_set(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, field.ctypes.data, index.ctypes.data,
                                                      op.ctypes.data, value.ctypes.data))
+
+    def scenario_checks_set(self, csr, slots: int = 0):
+        """``cosim_scenario_checks_set``: ``csr`` = the seven host arrays ``(adr, t, signal, index, mode, cmp, bound)`` of
+        ``ScenarioTable.pack_checks`` (``None``: clear the checks); ``slots`` verdict records per env."""
+        if csr is None:
+            self._check(self.L.cosim_scenario_checks_set(self.h, 0, None, None, None, None, None, None, None, 0))
+            return
+        adr, t, signal, index, mode, cmp, bound = csr
+        adr, t = np.ascontiguousarray(adr, dtype=np.int32), np.ascontiguousarray(t, dtype=np.int32)
+        signal, index, mode, cmp = (np.ascontiguousarray(x, dtype=np.int32) for x in (signal, index, mode, cmp))
+        bound = np.ascontiguousarray(bound, dtype=np.float32)
+        if adr.ndim != 1 or adr.size < 1:
+            raise ValueError("scenario_checks_set: adr must be [S + 1]")
+        n = int(max(adr.max(), 0))
+        if t.size < 2 * n or min(signal.size, index.size, mode.size, cmp.size, bound.size) < n:   # (the engine reads the arrays up to the addresses)
+            raise ValueError(f"scenario_checks_set: the item arrays are shorter than their row addresses ({n} items)")
+        self._check(self.L.cosim_scenario_checks_set(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, signal.ctypes.data,
+                                                     index.ctypes.data, mode.ctypes.data, cmp.ctypes.data, bound.ctypes.data, int(slots)))
+
+    def scenario_checks_get(self, records_ptr, counts_ptr, open_ptr=None, stream=None):
+        """``cosim_scenario_checks_get``: rings ``[N, slots, words]``, ended-episode counts ``[N]`` and (or ``None``) open rows ``[N,
+        words]``, int32."""
+        self._check(self.L.cosim_scenario_checks_get(self.h, records_ptr, counts_ptr, open_ptr, stream))
 
     def scenario_params_get(self) -> np.ndarray:
         """``cosim_scenario_params_get``: the effective parameter records, host float32 ``[N, param_stride]``."""

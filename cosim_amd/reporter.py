@@ -162,6 +162,26 @@ class FleetReporter:
             out["percentiles"] = self.percentiles()
         if getattr(self.env, "ledger_slots", 0) > 0:
             out["episodes"] = self.episodes()
+        if getattr(self.env, "check_slots", 0) > 0:
+            out.setdefault("episodes", {})["checks"] = self.checks()
+        return out
+
+    def checks(self) -> dict:
+        """The verdicts of the env's scenario checks (``BatchedEnv(scenarios=TABLE, check_slots=SLOTS)``) summarised:
+        ``Verdicts.summary()`` plus ``by_scenario``.  Under ``torch.distributed`` the integer counts are all-reduced (``fleet``, with the
+        shares of the whole fleet); the records, and so the per-check tables, stay this rank's."""
+        import torch.distributed as dist
+        from .checks import Verdicts
+        v = self.env.verdicts()
+        out = v.summary()
+        out["by_scenario"] = {str(k): x for k, x in v.by_scenario().items()}
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            t = self.env.torch
+            c = v.counts()
+            keys = sorted(c)
+            x = t.tensor([c[k] for k in keys], dtype=t.int64, device=self.env.device)
+            dist.all_reduce(x, op=dist.ReduceOp.SUM)
+            out["fleet"] = Verdicts.with_shares({k: int(y) for k, y in zip(keys, x.cpu().tolist())})
         return out
 
     def episodes(self) -> dict:

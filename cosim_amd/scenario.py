@@ -17,6 +17,14 @@ window the word is the base value.  Fields: ``"kp"`` / ``"kd"`` (index = actuato
 ground-contact friction) and ``"dof_frictionloss"`` (index = dof).  ``index`` is an int, a name of the model (actuator, geom or joint
 name; needs ``names``, see ``param_names``) or ``"*"`` for every entry of the field; names and ``"*"`` are expanded here, on the host.
 The mass fields are refused.  ``reference_params`` is the numpy twin of the kernel's rule, exact.
+
+Checks (``cosim_scenario_checks_set``, csrc/cosim_checks.hip): a scenario may hold ``"checks": [[t0, t1, signal, index, mode, op, bound],
+...]`` (an optional eighth entry names the item; or a dict with those keys and ``"name"``): a timed pass / fail criterion on a signal of
+the step, judged on the device.  ``signal``: ``"info"`` / ``"abs_info"`` (index = column of the info row: an int, a column name
+``action_diff_RMSE``, ``lin_vel_x``, ``lin_vel_y``, ``ang_vel_yaw``, or ``torque[k]`` / ``set_points[k]`` / ``state[k]``),
+``"tracking_error"`` (index = command entry), ``"torque_max"``, ``"up"`` (index 0), ``"qpos"`` / ``"qvel"`` / ``"abs_qvel"`` (index = an
+int or a joint name: the joint's first qpos / dof address).  ``mode`` ``"always"`` / ``"settle"`` / ``"mean"``, ``op`` ``"<"`` / ``">"``.
+``cosim_amd/checks.py`` has the verdict container and the numpy twin.
 """
 from __future__ import annotations
 
@@ -31,6 +39,11 @@ MAX_ROWS, MAX_ITEMS, MAX_TIME = 65536, 64, 1 << 30
 PARAM_FIELDS = {"kp": 0, "kd": 1, "geom_friction": 2, "dof_frictionloss": 3}
 PARAM_OPS = {"scale": 0, "set": 1}
 MAX_PARAM_ITEMS = 256
+CHECK_SIGNALS = {"info": 0, "abs_info": 1, "tracking_error": 2, "torque_max": 3, "up": 4, "qpos": 5, "qvel": 6, "abs_qvel": 7}
+CHECK_MODES = {"always": 0, "settle": 1, "mean": 2}
+CHECK_OPS = {"<": 0, ">": 1}
+MAX_CHECK_ITEMS = 64
+_CHECK_KEYS = ("t0", "t1", "signal", "index", "mode", "op", "bound")
 # consistent only as a set that compile.env_constants computes in fp64 on the host
 REFUSED_PARAM_FIELDS = ("body_mass", "body_invweight0", "dof_invweight0", "meaninertia")
 _FIELD_NAMES = {v: k for k, v in PARAM_FIELDS.items()}
@@ -45,6 +58,25 @@ def param_names(cm) -> dict:
     acts = [a["name"] for a in cm.spec["actuators"]]
     jid = np.asarray(get_field(cm.blob, "dof_jntid"))[:cm.blob.nv]
     return {"kp": acts, "kd": acts, "geom_friction": list(cm.geom_names), "dof_frictionloss": [cm.joint_names[int(j)] for j in jid]}
+
+
+def info_columns(nu: int, info_dim: int) -> dict:
+    """Column name -> ``(first column, width)`` of an info row: ``action_diff_RMSE``, ``lin_vel_x``, ``lin_vel_y``, ``ang_vel_yaw``,
+    ``torque [nu]``, ``set_points [nu]``, ``state [the rest]`` (``BatchedEnv._info``)."""
+    nu, info_dim = int(nu), int(info_dim)
+    return {"action_diff_RMSE": (0, 1), "lin_vel_x": (1, 1), "lin_vel_y": (2, 1), "ang_vel_yaw": (3, 1), "torque": (4, nu),
+            "set_points": (4 + nu, nu), "state": (4 + 2 * nu, max(info_dim - 4 - 2 * nu, 0))}
+
+
+def check_names(cm, info_dim: int, command_dim: int) -> dict:
+    """What the ``index`` of a check is resolved against, from a compiled model: ``{"info": info_columns, "info_dim", "command_dim",
+    "nq", "nv", "qpos": {joint: first qpos address}, "qvel": {joint: first dof address}}``."""
+    from .model import get_field
+    b = cm.blob
+    nj = len(cm.joint_names)
+    qadr, dadr = np.asarray(get_field(b, "jnt_qposadr"))[:nj], np.asarray(get_field(b, "jnt_dofadr"))[:nj]
+    return {"info": info_columns(b.nu, info_dim), "info_dim": int(info_dim), "command_dim": int(command_dim), "nq": int(b.nq), "nv": int(b.nv),
+            "qpos": {n: int(qadr[j]) for j, n in enumerate(cm.joint_names)}, "qvel": {n: int(dadr[j]) for j, n in enumerate(cm.joint_names)}}
 
 
 def param_layout(nbody: int, nv: int, ngeom: int, nu: int) -> dict:
@@ -72,9 +104,10 @@ class ScenarioTable:
         if not 1 <= len(scenarios) <= MAX_ROWS:
             raise ValueError(f"ScenarioTable: {len(scenarios)} scenarios: must be 1..{MAX_ROWS}")
         self.keys, self.pushes, self.param_windows, self.params = [], [], [], None
+        self.check_rows, self.checks = [], None
         for s, sc in enumerate(scenarios):
             sc = sc or {}
-            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "name"}:
+            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "name"}:
                 raise ValueError(f"ScenarioTable: scenario {s}: a mapping with the keys 'commands' and 'pushes' is expected, got {sc!r}")
             keys, pushes = [], []
             for r, row in enumerate(sc.get("commands") or []):
@@ -107,8 +140,63 @@ class ScenarioTable:
             self.keys.append(keys)
             self.pushes.append(pushes)
             self.param_windows.append(_param_windows(s, sc.get("params") or []))
+            self.check_rows.append(_check_rows(s, sc.get("checks") or []))
         if names is not None or not self.has_params:
             self.resolve(names or {})
+        cn = (names or {}).get("checks")
+        if cn is not None or not any(isinstance(r[3], str) for rows in self.check_rows for r in rows):
+            self.resolve_checks(cn)
+
+    @property
+    def has_checks(self) -> bool:
+        return any(self.check_rows)
+
+    def resolve_checks(self, names: dict = None) -> "ScenarioTable":
+        """Resolve the checks against ``names`` (``check_names(compiled_model, info_dim, command_dim)``): ``self.checks[s]`` becomes the
+        list of items ``(t0, t1, signal id, index, mode id, op id, float32 bound, name)``.  With ``names`` ``None`` only int indices
+        resolve and no range is checked (the engine checks them).  Raises ``ValueError`` naming the scenario and the item."""
+        out = []
+        for s, rows in enumerate(self.check_rows):
+            items = []
+            for r, (t0, t1, signal, index, mode, op, bound, name) in enumerate(rows):
+                who = f"ScenarioTable: scenario {s}, check item {r}"
+                if isinstance(index, str):
+                    if names is None:
+                        raise ValueError(f"{who}: index '{index}' needs the model's names to be resolved (check_names)")
+                    index = _check_index(who, signal, index, names)
+                if names is not None:
+                    width = {"info": names["info_dim"], "abs_info": names["info_dim"], "tracking_error": min(names["command_dim"], 3),
+                             "torque_max": 1, "up": 1 if names["nq"] >= 7 else 0, "qpos": names["nq"], "qvel": names["nv"], "abs_qvel": names["nv"]}[signal]
+                    if not 0 <= index < width:
+                        raise ValueError(f"{who}: index {index} out of range: '{signal}' has {width} entries")
+                items.append((t0, t1, CHECK_SIGNALS[signal], int(index), CHECK_MODES[mode], CHECK_OPS[op], np.float32(bound),
+                              name if name is not None else f"{signal}[{index}] {mode} {op} {float(np.float32(bound))!r} @{t0}:{t1}"))
+            out.append(items)
+        self.checks = out
+        return self
+
+    def _resolved_checks(self):
+        if self.checks is None:
+            raise ValueError("ScenarioTable: the checks are not resolved yet: call resolve_checks(check_names(model, info_dim, command_dim))")
+        return self.checks
+
+    @property
+    def n_check_items(self) -> int:
+        return sum(len(c) for c in self.check_rows)
+
+    def pack_checks(self):
+        """``(adr int32[S + 1], t int32[n, 2], signal int32[n], index int32[n], mode int32[n], cmp int32[n], bound float32[n])``: the items
+        in the CSR form of ``cosim_scenario_checks_set``."""
+        C = self._resolved_checks()
+        adr = np.cumsum([0] + [len(c) for c in C]).astype(np.int32)
+        flat = [it for c in C for it in c]
+        col = lambda k, dt: np.array([it[k] for it in flat], dtype=dt)   # noqa: E731
+        return (adr, np.array([(it[0], it[1]) for it in flat], dtype=np.int32).reshape(-1, 2), col(2, np.int32), col(3, np.int32), col(4, np.int32),
+                col(5, np.int32), col(6, np.float32))
+
+    def check_item_names(self) -> list:
+        """Per scenario, the names of its items (the given name, or one made from the item's fields)."""
+        return [[it[7] for it in c] for c in self._resolved_checks()]
 
     @property
     def has_params(self) -> bool:
@@ -183,6 +271,10 @@ class ScenarioTable:
         for sc, wins in zip(out, self.param_windows):
             if wins:
                 sc["params"] = [[t0, t1, field, index, op, float(value)] for t0, t1, field, index, op, value in wins]
+        for sc, rows in zip(out, self.check_rows):
+            if rows:
+                sc["checks"] = [[t0, t1, signal, index, mode, op, float(bound)] + ([name] if name is not None else [])
+                                for t0, t1, signal, index, mode, op, bound, name in rows]
         return out
 
     def pack(self):
@@ -264,14 +356,91 @@ def _param_windows(s: int, rows) -> list:
     return out
 
 
+def _check_index(who: str, signal: str, index: str, names: dict) -> int:
+    """A check's index given as a name: an info column (``name`` or ``name[k]``) or a joint."""
+    if signal in ("info", "abs_info"):
+        base, k = index, 0
+        if index.endswith("]") and "[" in index:
+            base, _, rest = index[:-1].partition("[")
+            try:
+                k = int(rest)
+            except ValueError:
+                raise ValueError(f"{who}: unknown info column '{index}'") from None
+        if base not in names["info"]:
+            raise ValueError(f"{who}: unknown info column '{index}' (one of {', '.join(names['info'])})")
+        first, width = names["info"][base]
+        if not 0 <= k < width:
+            raise ValueError(f"{who}: '{index}' out of range: '{base}' has {width} entries")
+        return first + k
+    if signal in ("qpos", "qvel", "abs_qvel"):
+        table = names["qpos" if signal == "qpos" else "qvel"]
+        if index not in table:
+            raise ValueError(f"{who}: unknown joint '{index}' for signal '{signal}'")
+        return table[index]
+    raise ValueError(f"{who}: signal '{signal}' takes an int index, got '{index}'")
+
+
+def _check_rows(s: int, rows) -> list:
+    """The ``"checks"`` rows of scenario ``s``, checked for everything that needs no model: ``(t0, t1, signal, index, mode, op, bound,
+    name or None)``."""
+    out = []
+    if len(rows) > MAX_CHECK_ITEMS:
+        raise ValueError(f"ScenarioTable: scenario {s}: {len(rows)} check items, at most {MAX_CHECK_ITEMS}")
+    for r, row in enumerate(rows):
+        who = f"ScenarioTable: scenario {s}, check item {r}"
+        name = None
+        if isinstance(row, dict):
+            if set(row) - set(_CHECK_KEYS) - {"name"} or any(k not in row for k in _CHECK_KEYS if k != "index"):
+                raise ValueError(f"{who}: a mapping with the keys {', '.join(_CHECK_KEYS)} (and 'name') is expected, got {row!r}")
+            name = row.get("name")
+            row = [row.get(k, 0) for k in _CHECK_KEYS]
+        elif isinstance(row, (list, tuple)) and len(row) == 8:
+            row, name = list(row[:7]), row[7]
+        if not isinstance(row, (list, tuple)) or len(row) != 7:
+            raise ValueError(f"{who}: expected [t0, t1, signal, index, mode, op, bound] and an optional name, got {row!r}")
+        t0, t1, signal, index, mode, op, bound = row
+        try:
+            t0f, t1f, bound = float(t0), float(t1), float(bound)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: times and bound must be numbers, got {row!r}") from None
+        if not math.isfinite(bound) or abs(bound) > float(np.finfo(np.float32).max):
+            raise ValueError(f"{who}: non-finite bound")
+        if not (math.isfinite(t0f) and math.isfinite(t1f)) or t0f != int(t0f) or t1f != int(t1f) or not 0 <= t0f < MAX_TIME or not 0 <= t1f <= MAX_TIME:
+            raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
+        if t1f <= t0f:
+            raise ValueError(f"{who}: t1 {int(t1f)} is not after t0 {int(t0f)}")
+        if signal not in CHECK_SIGNALS:
+            raise ValueError(f"{who}: unknown signal {signal!r} (one of {', '.join(CHECK_SIGNALS)})")
+        if mode not in CHECK_MODES:
+            raise ValueError(f"{who}: unknown mode {mode!r} ('always', 'settle' or 'mean')")
+        if op not in CHECK_OPS:
+            raise ValueError(f"{who}: unknown op {op!r} ('<' or '>')")
+        if isinstance(index, (bool, float)) or not isinstance(index, (int, np.integer, str)):
+            raise ValueError(f"{who}: index must be an int or a name, got {index!r}")
+        if name is not None and not isinstance(name, str):
+            raise ValueError(f"{who}: the name must be a string, got {name!r}")
+        out.append((int(t0f), int(t1f), signal, index if isinstance(index, str) else int(index), mode, op, bound, name))
+    return out
+
+
 def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = (),
-          params: Iterable = ()) -> Iterator[dict]:
+          params: Iterable = (), checks: Iterable = ()) -> Iterator[dict]:
     """The cartesian product command rows x push speeds x directions x push times as scenarios, commands outermost: each holds its
     command from episode step 0 and one push of ``speed`` m/s along the world direction ``angle`` (radians about z, 0 = +x) held over
     ``(t0, t1)``.  With no speeds or no times the product is over the commands alone (no push).
     ``len(list(sweep(C, V, D, T))) == len(C) * len(V) * len(D) * len(T)``.  ``params``: a list of window lists (each a scenario's
     ``"params"`` value, possibly empty) is one more cartesian axis, innermost: every scenario above is emitted once per window list,
-    ``len(...) * len(P)`` scenarios in all."""
+    ``len(...) * len(P)`` scenarios in all.  ``checks``: a list of check lists (each a scenario's ``"checks"`` value, possibly empty)
+    is one more axis, innermost of all: ``len(...) * len(K)`` scenarios."""
+    checks = [list(c) for c in checks]
+    if checks:
+        for sc in sweep(commands, push_speeds, directions, push_times, params):
+            for cl in checks:
+                out = dict(sc)
+                if cl:
+                    out["checks"] = [dict(c) if isinstance(c, dict) else list(c) for c in cl]
+                yield out
+        return
     params = [[list(w) for w in wins] for wins in params]
     if params:
         for sc in sweep(commands, push_speeds, directions, push_times):

@@ -377,6 +377,42 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
  * windows set: the base records), to host memory of `capacity` floats; joins the ranges first.  Returns param_stride. */
 int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
 
+/* Checks of the scenario table that is set: per-scenario pass / fail criteria judged on the device (cosim_amd/csrc/cosim_checks.h has
+ * the rule).  Scenario s owns the items [adr[s], adr[s + 1]) (at most 64).  Item i takes one sample per control step whose PRE-STEP
+ * episode clock t (meta word 0 as the scenario kernel read it ahead of that step) holds t[2i] <= t < t[2i + 1]:
+ *   signal  0 info[index]  1 |info[index]|  2 tracking_error |cmd[index] - info[1 + index]| (cmd: the applied command, index <
+ *           min(command_dim, 3))  3 torque_max: max_j |info[4 + j]|  4 up: 1 - 2 (qx^2 + qy^2) of qpos[3:7]  5 qpos[index]
+ *           6 qvel[index]  7 |qvel[index]|.  Signals 4..7 read the state record behind the step (the pose the step ended in) and
+ *           take no sample on a row with a done flag (the auto-reset has replaced the pose); 0..3 are sampled on done rows.
+ *   cmp     0: ok = v < bound, 1: ok = v > bound; NaN is not ok.
+ *   mode    0 always: every sample ok; aux = t of the first sample not ok (-1: none).  1 settle: ok from some step on to the end of
+ *           the window; aux = t of the last sample not ok (-1: none), fails iff the window is complete and aux == t1 - 1.  2 mean:
+ *           double sum of the samples, value (float)(sum / n), aux = n.  The value of an always / settle item is the sample furthest
+ *           on the failing side; with no sample the value word is 0x7fc00000.
+ * An item is incomplete iff it took fewer than t1 - t0 samples when its record is written.  When a row carries a done flag the
+ * episode's items are closed into one record of 8 + 2 I int32 words (I: the largest item count of any scenario, rounded up to
+ * even) in slot (episode mod slots) of the env's ring: 0 episode ordinal since the checks were set, 1 length, 2 flags (1 terminated |
+ * 2 truncated | 8 did not begin at a reset | 16 open), 3 scenario row + 1, 4..5 fail mask (low, high), 6..7 incomplete mask, then
+ * per item the value bits and aux.  (env, episode) joins a record to the ledger's and the failure traces' when all were set
+ * together.  cosim_reset begins the masked envs' episodes (flag 0), cosim_restore / cosim_set and this call on a stepped fleet with
+ * flag 8; an episode the host cuts leaves no record.  checks_step_kernel runs behind every range's last launch of a control step,
+ * behind the ledger's launch, on the range's own stream: no host read, no join, a captured step carries it; it only reads what the
+ * step wrote.  Items of the counts of the ones that are set (same row addresses, same slots) are rewritten in place: a captured
+ * graph picks the new values up; every call begins every env's episode anew.
+ * n_scn = 0 clears the checks (no launch, pointer or byte then differs from an engine that never had any); otherwise n_scn must be
+ * the "scenario_rows" of the table that is set.  cosim_scenario_set with another S, or clearing the table, drops the checks.
+ * Validated on the host before anything changes, the message names the scenario and the item (COSIM_EINVAL): a non-finite bound,
+ * t1 <= t0, times outside [0, 2^30), an unknown signal / mode / cmp, an index out of range for the model, more than 64 items,
+ * slots outside 1..64, no table set or another S.  While checks are set cosim_step without info_out_dev returns COSIM_EINVAL;
+ * cosim_rollout stays refused (a scenario table is set); cosim_profile_step does not feed the checks; checks are not part of a
+ * snapshot.  cosim_query answers "scenario_check_items" (I; 0: none), "scenario_check_slots" and "scenario_check_words". */
+int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t /*[n][2]*/, const int32_t* signal,
+                              const int32_t* index, const int32_t* mode, const int32_t* cmp, const float* bound, int slots);
+/* records_dev int32[N][slots][words], counts_dev int32[N] (episodes ended per env: the ring holds the last min(count, slots)),
+ * open_dev int32[N][words] or NULL (the open episodes as flag-16 records).  Joins the ranges, like cosim_ledger_get; asynchronous on
+ * `stream` otherwise. */
+int cosim_scenario_checks_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream);
+
 /* Fall rules (the reference ends an episode early only through a robot's own _is_done, which is an empty body list for
  * flamingo_light_v1 and False for w4_p_v2 and humanoid_p_v0): the step kernels end an episode on the posture of the state a control
  * step ends in, per cause.  Evaluated once per control step (every step of a rollout launch, the last substep launch of the split
