@@ -85,7 +85,8 @@ class BatchedEnv:
                  auto_reset: bool = True, env_id0: int = 0, gain_noise: float = 0.0, compiled: Optional[CompiledModel] = None,
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
                  spawn=None, history=None, ledger: Optional[int] = None, scenarios=None, scenario_mode: Optional[str] = None,
-                 fall=None, failure_traces=None, streams: Optional[int] = None, check_slots: Optional[int] = None):
+                 fall=None, failure_traces=None, streams: Optional[int] = None, check_slots: Optional[int] = None,
+                 curves: Optional[bool] = None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -124,6 +125,11 @@ class BatchedEnv:
         judges them on the device and keeps the last ``check_slots`` (1..64) verdict records of every env, see ``set_scenarios`` /
         ``verdicts()``.  Default: ``config["engine"].get("check_slots")`` / none: a table's checks are carried but not evaluated,
         and no launch, pointer or byte differs from a table without checks.
+
+        ``curves``: arm the response curves the scenario table holds (a scenario's ``"curves"``, ``cosim_amd/scenario.py``): the engine
+        keeps per-scenario ensemble time series on the device, see ``set_scenarios`` / ``curves()``.  Default:
+        ``config["engine"].get("curves")`` / off: a table's curves are carried but not armed, and no launch, pointer or byte differs
+        from a table without curves.
 
         ``fall``: a fall rule -- a ``FallRule`` or a dict ``{"tilt", "height", "grace", "bodies"}`` (``cosim_amd/fall.py``) -- see
         ``set_fall``.  Default: ``config["engine"].get("fall")`` / none: an episode ends early only through the robot's own
@@ -264,10 +270,12 @@ class BatchedEnv:
         self.scenario_table, self.scenario_mode = None, "env"
         self._cmd_out = self._row_out = None
         self.check_slots = 0
+        self.curves_armed = False
         scenarios = scenarios if scenarios is not None else eng_cfg.get("scenarios")
         if scenarios is not None:
             self.set_scenarios(scenarios, scenario_mode if scenario_mode is not None else eng_cfg.get("scenario_mode", "env"),
-                               check_slots=check_slots if check_slots is not None else eng_cfg.get("check_slots"))
+                               check_slots=check_slots if check_slots is not None else eng_cfg.get("check_slots"),
+                               curves=curves if curves is not None else eng_cfg.get("curves"))
 
     # ------------------------------------------------------------------ domain randomisation (XMLManager step 3)
     def _randomise(self, gain_noise: float):
@@ -639,7 +647,7 @@ class BatchedEnv:
         return buf.view(t.int32)[:, 15].clone()
 
     # ------------------------------------------------------------------ scenario table (cosim_scenario_set)
-    def set_scenarios(self, scenarios, mode: str = "env", check_slots: Optional[int] = None):
+    def set_scenarios(self, scenarios, mode: str = "env", check_slots: Optional[int] = None, curves: Optional[bool] = None):
         """Give every env its own test: a table of S scenarios, each a command schedule and a push schedule keyed by the env's own
         episode step (``cosim_amd/scenario.py``; ``None`` clears the table).  Env with global id ``g`` runs row ``g mod S`` (mode
         ``"env"``) or, in mode ``"cycle"`` (needs ``auto_reset``), row ``(g + episodes it has ended) mod S``: one scenario per
@@ -661,7 +669,16 @@ class BatchedEnv:
         Items of the same counts are rewritten in place (captured graphs pick them up).  ``None`` / 0: the checks are not
         evaluated (what an earlier call armed is cleared).  Set the ledger, the traces and the checks together and their episode
         ordinals agree.  Limits: state signals take no sample on a step that ends the episode; checks are not part of a
-        ``snapshot()``."""
+        ``snapshot()``.
+
+        ``curves=True`` arms the table's response curves (``cosim_scenario_curves_set``): behind every control step the engine stages
+        one sample of every curve item of the env's scenario that is due at the step's pre-step episode clock, and when the episode
+        ends folds its samples into the cells of (scenario, item, outcome) with integer atomics, on the device, with no host read;
+        ``curves()`` reads them.  Every call empties the cells and begins every env's episode anew for the curves; ``reset()``,
+        ``restore`` and ``set_state`` discard what the envs they touch had staged, so an episode the host cuts is in no cell.  Items
+        of the same counts and sizes are rewritten in place (captured graphs pick them up).  ``None`` / ``False``: the curves are not
+        armed (what an earlier call armed is cleared).  Limits: state signals take no sample on a step that ends the episode; open
+        episodes are not in the cells; curves are not part of a ``snapshot()``."""
         from .scenario import MODES, ScenarioTable
         t = self.torch
         if scenarios is None:
@@ -669,6 +686,7 @@ class BatchedEnv:
             self.scenario_table, self.scenario_mode = None, "env"
             self._info_views = None
             self.check_slots = 0
+            self.curves_armed = False
             return
         if mode not in MODES:
             raise ValueError(f"set_scenarios: mode must be 'env' or 'cycle', got {mode!r}")
@@ -680,6 +698,8 @@ class BatchedEnv:
         check_slots = int(check_slots or 0)
         if check_slots and table.has_checks:                        # names and ranges against this env's model
             table.resolve_checks(self.check_names())
+        if curves and table.has_curves:
+            table.resolve_curves(self.check_names())
         if self._cmd_out is None:                                   # persistent: captured graphs hold these pointers
             self._cmd_out = t.zeros_like(self.user_command)
             self._row_out = t.zeros((self.num_envs,), dtype=t.int32, device=self.device)
@@ -691,6 +711,7 @@ class BatchedEnv:
                 self.scenario_table, self.scenario_mode = None, "env"
                 self._info_views = None
                 self.check_slots = 0
+                self.curves_armed = False
             raise
         self.scenario_table, self.scenario_mode = table, mode
         self._info_views = None
@@ -706,6 +727,33 @@ class BatchedEnv:
             self.check_slots = check_slots
         elif self.engine.query("scenario_check_items") > 0:
             self.engine.scenario_checks_set(None)
+        # and the curves
+        self.curves_armed = False
+        if curves and table.has_curves:
+            self.engine.scenario_curves_set(table.pack_curves())
+            self.curves_armed = True
+        elif self.engine.query("scenario_curve_items") > 0:
+            self.engine.scenario_curves_set(None)
+
+    def curves(self):
+        """The response curves of the fleet's ended episodes so far as a ``Curves`` (``cosim_amd/curves.py``): per (scenario, item)
+        the sample times and, per outcome class and time bin, count, mean, min, max, histogram and quantiles.  Joins the range streams
+        and reads the device once; nothing is read per step.  Raises ``ValueError`` if no curves are armed."""
+        from .curves import Curves
+        if not self.curves_armed:
+            raise ValueError("curves(): no curves are armed (BatchedEnv(scenarios=TABLE, curves=True) or set_scenarios(..., curves=True))")
+        t = self.torch
+        cells = t.empty((self.engine.query("scenario_curve_words"),), dtype=t.int32, device=self.device)
+        self.engine.scenario_curves_get(cells.data_ptr(), self._stream())
+        t.cuda.current_stream(self.device).synchronize()
+        return Curves.from_raw(cells.cpu().numpy().view(np.uint32), self.scenario_table)
+
+    def clear_curves(self):
+        """Empty the cells and begin every env's episode anew for the curves (what was staged is discarded).  Joins the range streams
+        and blocks until the device is idle."""
+        if not self.curves_armed:
+            raise ValueError("clear_curves(): no curves are armed")
+        self.engine.scenario_curves_clear()
 
     def check_names(self) -> dict:
         """What a check's ``index`` is resolved against on this env (``scenario.check_names``)."""

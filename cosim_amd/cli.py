@@ -110,6 +110,11 @@ def main(argv=None) -> int:
     ap.add_argument("--verdicts-out", default=None, metavar="PATH.npz", help="with --check-slots: write this rank's verdict records here")
     ap.add_argument("--require-pass", action="store_true",
                     help="with --check-slots: exit status 3 if any ended episode failed a check (a sweep can gate a CI job)")
+    ap.add_argument("--curves", action="store_true", default=None,
+                    help="keep the response curves of the scenario table on the device (a scenario's \"curves\"): per-scenario ensemble time "
+                         "series split by outcome; their summary goes into the report as \"episodes.curves\" (also under --graph / --pipelined)")
+    ap.add_argument("--curves-out", default=None, metavar="PATH.npz",
+                    help="with --curves: write the curves here (under torchrun: the whole fleet's, all-reduced, from rank 0)")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -122,7 +127,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces", "check_slots"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces", "check_slots", "curves"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -196,6 +201,11 @@ def main(argv=None) -> int:
         ap.error("--verdicts-out / --require-pass need --check-slots SLOTS")
     if args.check_slots and scenarios is None:
         ap.error("--check-slots needs --scenarios: checks are rows of a scenario table")
+    args.curves = bool(pick(args.curves, sess.get("curves") if sess.get("curves") is not None else s_eng.get("curves"), False))
+    if args.curves_out and not args.curves:
+        ap.error("--curves-out needs --curves")
+    if args.curves and scenarios is None:
+        ap.error("--curves needs --scenarios: curves are rows of a scenario table")
     # fall rule: the session's dict (top level or engine.fall), overridden key by key by the flags
     fall = dict(sess.get("fall") or s_eng.get("fall") or {})
     for key, val in (("tilt", args.fall_tilt), ("height", args.fall_height), ("grace", args.fall_grace)):
@@ -253,9 +263,11 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, failure_traces=ftrace or False, check_slots=args.check_slots or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, failure_traces=ftrace or False, check_slots=args.check_slots or None, curves=args.curves or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.check_slots and env.check_slots < 1:
         ap.error("--check-slots: the scenario table holds no checks")
+    if args.curves and not env.curves_armed:
+        ap.error("--curves: the scenario table holds no curves")
     if args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:
@@ -332,6 +344,10 @@ def main(argv=None) -> int:
     if args.verdicts_out:
         path = args.verdicts_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.verdicts_out)[:1], rank, os.path.splitext(args.verdicts_out)[1])
         verdicts.save(path)
+    if args.curves_out:                                              # the fleet's curves: the cells are all-reduced, every rank holds them
+        fleet = rep.fleet_curves()
+        if rank == 0:
+            fleet.save(args.curves_out)
     if args.checkpoint and "checkpoint" not in used:
         print(f"warning: --checkpoint-at {args.checkpoint_at} was not reached, no snapshot written", file=sys.stderr)
     out = rep.save(args.report, extra={"snapshot": used} if used else None) if (args.report and rank == 0) else rep.summary()
@@ -345,6 +361,7 @@ def main(argv=None) -> int:
                              if "terminated" in out.get("episodes", {}) else {}),
                           **({"checks": {k: v for k, v in out["episodes"]["checks"].get("fleet", out["episodes"]["checks"]).items()
                                          if k not in ("checks", "by_scenario")}} if verdicts is not None else {}),
+                          **({"curves": out["episodes"]["curves"]} if args.curves else {}),
                           **({"failure_traces": traces.summary()} if traces is not None else {}),
                           **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
                              if "by_scenario" in out.get("episodes", {}) else {}),

@@ -20,6 +20,7 @@
 #include "cosim_scenario.hip"
 #include "cosim_scnparams.hip"
 #include "cosim_checks.hip"
+#include "cosim_curves.hip"
 #include "cosim_plan.h"
 #include "cosim_ranges.h"
 
@@ -154,6 +155,14 @@ struct cosim_engine {
   int* d_chk_cnt = nullptr;       // [n_envs][CHK_NCNT]
   int* d_chk_rec = nullptr;       // [n_envs][chk_slots][8 + 2 I]
   int chk_slots = 0;
+  // response curves of the scenario table (cosim_scenario_curves_set, cosim_curves.hip): curves_step_kernel behind every range's last
+  // launch of a step, behind the checks'
+  char* d_cur = nullptr;          // one allocation: adr | t | signal | index | bins | nt | soff | coff | cw | lo | hi | inv_w
+  CurTable cur = {};              // device pointers into d_cur; n_scn 0: no curves, no launches
+  int* d_cur_stage = nullptr;     // [n_envs][SW]
+  int* d_cur_clk = nullptr;       // [n_envs]
+  unsigned* d_cur_cells = nullptr;   // cur_words 32-bit words
+  size_t cur_words = 0;
   // fall rules (cosim_fall_set): kernel arguments of every step launch; fall_mask 0 = none (meta word 15 is not written)
   float fall_min_up = -1.f, fall_min_height = 0.f;
   int fall_grace = 0, fall_mask = 0;
@@ -733,9 +742,62 @@ static void checks_free(cosim_engine* e) {
   e->d_chk_rec = nullptr; e->chk_slots = 0; memset(&e->chk, 0, sizeof e->chk);
 }
 
+// ---- response curves of the scenario table (cosim_curves.hip)
+static const char* const CURVES_INFO_MSG =
+    ": response curves are set (cosim_scenario_curves_set) and info_out_dev is NULL: the curves sample the step's info row; pass an "
+    "info buffer or clear the curves";
+
+static CurArgs curves_args(cosim_engine* e) {
+  CurArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->cur; a.state = e->d_state; a.scn_row = e->scn_row_out;
+  a.stage = e->d_cur_stage; a.clk = e->d_cur_clk; a.cells = e->d_cur_cells;
+  a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
+  a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.cmd_stride = e->ho.command_dim;
+  a.s_stride = e->lay.s_stride; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.s_meta = e->lay.s_meta;
+  return a;
+}
+
+// this step's samples and folds of envs [first, first + count), behind the launches that wrote the step's outputs on the same stream
+static int curves_step(cosim_engine* e, int first, int count, const float* cmd, const float* info, const uint8_t* term, const uint8_t* trunc,
+                       hipStream_t s) {
+  CurArgs a = curves_args(e);
+  a.cmd = a.cmd_stride > 0 ? cmd : nullptr; a.info = info; a.term = term; a.trunc = trunc;
+  a.first = first; a.count = count;
+  hipLaunchKernelGGL(curves_step_kernel, dim3((count + CUR_WAVES - 1) / CUR_WAVES), dim3(64 * CUR_WAVES), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode with an empty stage
+static int curves_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, hipStream_t s) {
+  if (e->cur.n_scn <= 0) return COSIM_OK;
+  CurArgs a = curves_args(e);
+  a.mask = mask; a.src = src; a.n_rows = n_rows;
+  hipLaunchKernelGGL(curves_begin_kernel, dim3((e->n_envs + CUR_WAVES - 1) / CUR_WAVES), dim3(64 * CUR_WAVES), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// every cell back to empty
+static int curves_zero(cosim_engine* e, hipStream_t s) {
+  CurArgs a = curves_args(e);
+  hipLaunchKernelGGL(curves_clear_kernel, dim3(2 * e->cur.n_items), dim3(256), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// the curves go with their table (the caller has waited for the device)
+static void curves_free(cosim_engine* e) {
+  (void)hipFree(e->d_cur); (void)hipFree(e->d_cur_stage); (void)hipFree(e->d_cur_clk); (void)hipFree(e->d_cur_cells);
+  e->d_cur = nullptr; e->d_cur_stage = nullptr; e->d_cur_clk = nullptr; e->d_cur_cells = nullptr; e->cur_words = 0;
+  memset(&e->cur, 0, sizeof e->cur);
+}
+
 static void scenario_free(cosim_engine* e) {
   scnparams_free(e);
   checks_free(e);
+  curves_free(e);
   (void)hipFree(e->d_scn);
   e->d_scn = nullptr; memset(&e->scn, 0, sizeof e->scn); e->scn_nkey = 0; e->scn_npush = 0; e->scn_cmd_out = nullptr; e->scn_row_out = nullptr;
 }
@@ -1099,6 +1161,9 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "scenario_param_items") return e->scnpar.n_items;   // expanded parameter-window items of the table (0: none, no launches)
   if (n == "scenario_check_items") return e->chk.n_scn > 0 ? e->chk.I : 0;   // I: items per env a verdict record holds (0: no checks, no launches)
   if (n == "scenario_check_slots") return e->chk_slots;                      // verdict records per env
+  if (n == "scenario_curve_items") return e->cur.n_items;   // curve items of the table (0: no curves, no launches)
+  if (n == "scenario_curve_words") return (int)e->cur_words;   // 32-bit words of all cells (at most 2^26)
+  if (n == "scenario_curve_stage_words") return e->cur.n_scn > 0 ? e->cur.SW : 0;   // stage words per env
   if (n == "scenario_check_words") return e->chk.n_scn > 0 ? checks_words(e->chk.I) : 0;   // 32-bit words of a verdict record: 8 + 2 I
   if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
   if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
@@ -1232,7 +1297,9 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   if (rc) return rc;
   rc = ftrace_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
   if (rc) return rc;
-  return checks_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
+  rc = checks_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
+  if (rc) return rc;
+  return curves_begin(e, mask_dev, nullptr, 0, (hipStream_t)stream);
 }
 
 int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* commands_dev, float* state_out_dev, uint8_t* terminated_dev,
@@ -1405,6 +1472,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + LEDGER_INFO_MSG);
   if (e->ft_frames > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + FTRACE_INFO_MSG);
   if (e->chk.n_scn > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + CHECKS_INFO_MSG);
+  if (e->cur.n_scn > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + CURVES_INFO_MSG);
   e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
@@ -1460,7 +1528,9 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   // failure traces: this step's frame of the range, behind the ledger's launch (reads the caller's action rows: they outlive the step)
   if (e->ft_frames > 0) { rc = ftrace_step(e, first, count, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s); if (rc) return rc; }
   // scenario checks: this step's samples of the range, behind the ledger's launch (they only read what the step wrote)
-  if (e->chk.n_scn > 0) return checks_step(e, first, count, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
+  if (e->chk.n_scn > 0) { rc = checks_step(e, first, count, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s); if (rc) return rc; }
+  // response curves: this step's samples and folds of the range, behind the checks' launch (they only read what the step wrote)
+  if (e->cur.n_scn > 0) return curves_step(e, first, count, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
   return COSIM_OK;
 }
 
@@ -1611,7 +1681,9 @@ int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* st
   if (rc) return rc;
   rc = ftrace_begin(e, nullptr, nullptr, 0, FT_NO_RESET, (hipStream_t)stream);
   if (rc) return rc;
-  return checks_begin(e, nullptr, nullptr, 0, CHK_NO_RESET, (hipStream_t)stream);
+  rc = checks_begin(e, nullptr, nullptr, 0, CHK_NO_RESET, (hipStream_t)stream);
+  if (rc) return rc;
+  return curves_begin(e, nullptr, nullptr, 0, (hipStream_t)stream);
 }
 
 int cosim_snapshot(cosim_engine_t* e, float* out_dev, void* stream) {
@@ -1664,6 +1736,8 @@ int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const
   rc = ftrace_begin(e, mask_dev, src_index_dev, snap_rows, FT_NO_RESET, cs);
   if (rc) return rc;
   rc = checks_begin(e, mask_dev, src_index_dev, snap_rows, CHK_NO_RESET, cs);
+  if (rc) return rc;
+  rc = curves_begin(e, mask_dev, src_index_dev, snap_rows, cs);
   if (rc) return rc;
   if (src_index_dev && cap == hipStreamCaptureStatusNone) {   // the kernel skipped what it refused; report it
     HIP_TRY(hipMemcpyAsync(e->h_snap_err, e->d_snap_err, 2 * sizeof(int), hipMemcpyDeviceToHost, cs));
@@ -1870,7 +1944,7 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
     return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
   }
   if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
-  if (n_scn != e->scn.n_scn) { scnparams_free(e); checks_free(e); }   // parameter windows and checks are rows of the table they were set for: another S drops them
+  if (n_scn != e->scn.n_scn) { scnparams_free(e); checks_free(e); curves_free(e); }   // parameter windows, checks and curves are rows of the table they were set for: another S drops them
   const int32_t* base = reinterpret_cast<const int32_t*>(e->d_scn);
   e->scn.key_adr = base + o_kadr; e->scn.push_adr = base + o_padr; e->scn.key_t = base + o_kt; e->scn.push_t = base + o_pt;
   e->scn.key_cmd = reinterpret_cast<const float*>(base + o_kc); e->scn.push_v = reinterpret_cast<const float*>(base + o_pv);
@@ -2132,6 +2206,164 @@ int cosim_scenario_checks_get(cosim_engine_t* e, int32_t* records_dev, int32_t* 
     hipLaunchKernelGGL(checks_open_kernel, dim3((e->n_envs + CHK_WAVES - 1) / CHK_WAVES), dim3(64 * CHK_WAVES), 0, cs, a);
     HIP_TRY(hipGetLastError());
   }
+  return COSIM_OK;
+}
+
+// Response curves of the scenario table that is set: validate on the host (a message that names the scenario and the item), join the
+// ranges, wait for the device, upload, empty the cells and begin every env's episode with an empty stage.  Items of the counts and
+// sizes of the ones that are set (same S, same row addresses, same T and B item by item) are rewritten in place: the device
+// pointers stay, and captured graphs pick the new values up.
+int cosim_scenario_curves_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t, const int32_t* signal, const int32_t* index,
+                              const float* lo, const float* hi, const int32_t* bins) {
+  if (!e) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: null engine");
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_scn == 0) {   // clear (launches in flight still read the items: wait for them)
+    int rc = join_ranges(e, 0);
+    if (rc) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    curves_free(e);
+    return COSIM_OK;
+  }
+  if (e->scn.n_scn == 0)
+    return fail(COSIM_EINVAL, "cosim_scenario_curves_set: no scenario table is set (cosim_scenario_set): curves are rows of a table; set the table first");
+  if (n_scn != e->scn.n_scn)
+    return fail(COSIM_EINVAL, "cosim_scenario_curves_set: " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.n_scn));
+  if (!adr) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: null argument");
+  if (adr[0] != 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: adr[0] must be 0");
+  const cosim_model_t& m = e->model;
+  const int ncmd = e->ho.command_dim < 3 ? e->ho.command_dim : 3;
+  for (int s = 0; s < n_scn; s++) {   // the row addresses first: the item loop below reads the arrays through them
+    const long long ni = (long long)adr[s + 1] - adr[s];
+    const std::string who = "cosim_scenario_curves_set: scenario " + std::to_string(s);
+    if (ni < 0) return fail(COSIM_EINVAL, who + ": row addresses must not decrease");
+    if (ni > CUR_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(ni) + " curve items, at most 8");
+    if (ni > 0 && (!t || !signal || !index || !lo || !hi || !bins)) return fail(COSIM_EINVAL, who + ": null table array");
+  }
+  const int n = adr[n_scn];
+  if (n == 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: the table holds no curve item (n_scn = 0 clears the curves)");
+  std::vector<int32_t> nt(n), soff(n), coff(n), cw(n);
+  std::vector<float> inv_w(n, 0.f);
+  size_t cells = 0, most = 0;
+  for (int s = 0; s < n_scn; s++) {
+    size_t row_words = 0;
+    for (int i = adr[s]; i < adr[s + 1]; i++) {
+      const std::string row = "cosim_scenario_curves_set: scenario " + std::to_string(s) + ", curve item " + std::to_string(i - adr[s]);
+      const int t0 = t[3 * i], t1 = t[3 * i + 1], every = t[3 * i + 2], B = bins[i];
+      if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": times outside [0, 2^30)");
+      if (t1 <= t0) return fail(COSIM_EINVAL, row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0));
+      if (every < 1) return fail(COSIM_EINVAL, row + ": every " + std::to_string(every) + " is below 1");
+      const int T = curves_nt(t0, t1, every);
+      if (T > CUR_MAX_T) return fail(COSIM_EINVAL, row + ": " + std::to_string(T) + " time bins, at most 1024");
+      if (B < 0 || B > CUR_MAX_BINS) return fail(COSIM_EINVAL, row + ": bins " + std::to_string(B) + " outside 0..64");
+      if (!std::isfinite(lo[i]) || !std::isfinite(hi[i])) return fail(COSIM_EINVAL, row + ": lo / hi is not finite");
+      if (B > 0 && !(hi[i] > lo[i])) return fail(COSIM_EINVAL, row + ": hi is not above lo");
+      int width;
+      const char* name;
+      switch (signal[i]) {
+        case CHK_INFO: width = e->ho.info_dim; name = "info"; break;
+        case CHK_ABS_INFO: width = e->ho.info_dim; name = "abs_info"; break;
+        case CHK_TRACKING_ERROR: width = ncmd; name = "tracking_error"; break;
+        case CHK_TORQUE_MAX: width = 1; name = "torque_max"; break;
+        case CHK_UP: width = m.nq >= 7 ? 1 : 0; name = "up"; break;
+        case CHK_QPOS: width = m.nq; name = "qpos"; break;
+        case CHK_QVEL: width = m.nv; name = "qvel"; break;
+        case CHK_ABS_QVEL: width = m.nv; name = "abs_qvel"; break;
+        default:
+          return fail(COSIM_EINVAL, row + ": unknown signal " + std::to_string(signal[i]) +
+                                        " (0 info, 1 abs_info, 2 tracking_error, 3 torque_max, 4 up, 5 qpos, 6 qvel, 7 abs_qvel)");
+      }
+      if (index[i] < 0 || index[i] >= width)
+        return fail(COSIM_EINVAL, row + ": index " + std::to_string(index[i]) + " out of range: " + name + " has " + std::to_string(width) + " entries");
+      nt[i] = T; soff[i] = (int32_t)row_words; cw[i] = curves_cell_words(T, B);
+      if (cells + 2 * (size_t)cw[i] > CUR_MAX_BYTES / 4) return fail(COSIM_EINVAL, row + ": the cells would exceed 256 MiB (a design limit)");
+      coff[i] = (int32_t)cells;
+      cells += 2 * (size_t)cw[i];
+      row_words += (size_t)T;
+      if (B > 0) inv_w[i] = (float)((double)B / ((double)hi[i] - (double)lo[i]));
+    }
+    if (row_words > most) most = row_words;
+  }
+  const size_t N = (size_t)e->n_envs, SW = most;
+  if (N * SW > CUR_MAX_BYTES / 4)
+    return fail(COSIM_EINVAL, "cosim_scenario_curves_set: the stage, " + std::to_string(SW) + " words for each of " + std::to_string(N) +
+                                  " envs, would exceed 256 MiB (a design limit)");
+  int rc = join_ranges(e, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());   // launches in flight may still read the items
+  // adr | t | signal | index | bins | nt | soff | coff | cw | lo | hi | inv_w, every array 4-byte words
+  const size_t o_adr = 0, o_t = o_adr + (size_t)n_scn + 1, o_s = o_t + 3 * (size_t)n, o_i = o_s + (size_t)n, o_b = o_i + (size_t)n,
+               o_nt = o_b + (size_t)n, o_so = o_nt + (size_t)n, o_co = o_so + (size_t)n, o_cw = o_co + (size_t)n, o_lo = o_cw + (size_t)n,
+               o_hi = o_lo + (size_t)n, o_w = o_hi + (size_t)n, total = o_w + (size_t)n;
+  std::vector<int32_t> h(total, 0);
+  memcpy(&h[o_adr], adr, ((size_t)n_scn + 1) * 4);
+  memcpy(&h[o_t], t, 3 * (size_t)n * 4);
+  memcpy(&h[o_s], signal, (size_t)n * 4);
+  memcpy(&h[o_i], index, (size_t)n * 4);
+  memcpy(&h[o_b], bins, (size_t)n * 4);
+  memcpy(&h[o_nt], nt.data(), (size_t)n * 4);
+  memcpy(&h[o_so], soff.data(), (size_t)n * 4);
+  memcpy(&h[o_co], coff.data(), (size_t)n * 4);
+  memcpy(&h[o_cw], cw.data(), (size_t)n * 4);
+  memcpy(&h[o_lo], lo, (size_t)n * 4);
+  memcpy(&h[o_hi], hi, (size_t)n * 4);
+  memcpy(&h[o_w], inv_w.data(), (size_t)n * 4);
+  bool in_place = e->cur.n_scn == n_scn && e->cur.n_items == n && e->cur.SW == (int)SW && e->cur_words == cells;
+  if (in_place) {   // the same counts and sizes item by item?  (what is set is read back: cold path)
+    std::vector<int32_t> old(total);
+    HIP_TRY(hipMemcpy(old.data(), e->d_cur, total * 4, hipMemcpyDeviceToHost));
+    in_place = memcmp(&old[o_adr], &h[o_adr], ((size_t)n_scn + 1) * 4) == 0 && memcmp(&old[o_b], &h[o_b], 5 * (size_t)n * 4) == 0;
+  }
+  if (!in_place) {
+    curves_free(e);
+    auto alloc = [&]() -> hipError_t {
+      hipError_t r;
+      if ((r = hipMalloc(&e->d_cur, total * 4)) != hipSuccess) return r;
+      if ((r = hipMalloc(&e->d_cur_stage, (N * SW > 0 ? N * SW : 1) * sizeof(int))) != hipSuccess) return r;
+      if ((r = hipMalloc(&e->d_cur_clk, N * sizeof(int))) != hipSuccess) return r;
+      return hipMalloc(&e->d_cur_cells, cells * sizeof(unsigned));
+    };
+    const hipError_t r = alloc();
+    if (r != hipSuccess) { curves_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_set: ") + hipGetErrorString(r)); }
+    const int32_t* base = reinterpret_cast<const int32_t*>(e->d_cur);
+    e->cur.adr = base + o_adr; e->cur.t = base + o_t; e->cur.signal = base + o_s; e->cur.index = base + o_i; e->cur.bins = base + o_b;
+    e->cur.nt = base + o_nt; e->cur.soff = base + o_so; e->cur.coff = base + o_co; e->cur.cw = base + o_cw;
+    e->cur.lo = reinterpret_cast<const float*>(base + o_lo); e->cur.hi = reinterpret_cast<const float*>(base + o_hi);
+    e->cur.inv_w = reinterpret_cast<const float*>(base + o_w);
+    e->cur.n_scn = n_scn; e->cur.n_items = n; e->cur.SW = (int)SW;
+    e->cur_words = cells;
+  }
+  const hipError_t r = hipMemcpy(e->d_cur, h.data(), total * 4, hipMemcpyHostToDevice);
+  if (r != hipSuccess) { curves_free(e); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_set: ") + hipGetErrorString(r)); }
+  return cosim_scenario_curves_clear(e);
+}
+
+// Every cell back to empty and every env's episode begun anew with an empty stage at its current clock (the range streams do not
+// order with the null stream: join and wait, cold path).
+int cosim_scenario_curves_clear(cosim_engine_t* e) {
+  if (!e) return fail(COSIM_EINVAL, "cosim_scenario_curves_clear: null engine");
+  if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_clear: no curves are set (cosim_scenario_curves_set)");
+  HIP_TRY(hipSetDevice(e->device));
+  int rc = join_ranges(e, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  rc = curves_zero(e, 0);
+  if (rc) return rc;
+  rc = curves_begin(e, nullptr, nullptr, 0, 0);
+  if (rc) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return COSIM_OK;
+}
+
+// The cells, uint32[scenario_curve_words], of the episodes that have ended; joins the ranges, asynchronous on the caller's stream
+// otherwise.
+int cosim_scenario_curves_get(cosim_engine_t* e, uint32_t* cells_dev, void* stream) {
+  if (!e || !cells_dev) return fail(COSIM_EINVAL, "cosim_scenario_curves_get: null argument");
+  if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_get: no curves are set (cosim_scenario_curves_set)");
+  HIP_TRY(hipSetDevice(e->device));
+  hipStream_t cs = (hipStream_t)stream;
+  int rc = join_ranges(e, cs);
+  if (rc) return rc;
+  HIP_TRY(hipMemcpyAsync(cells_dev, e->d_cur_cells, e->cur_words * sizeof(unsigned), hipMemcpyDeviceToDevice, cs));
   return COSIM_OK;
 }
 

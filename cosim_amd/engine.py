@@ -115,6 +115,9 @@ def load_library():
     L.cosim_scenario_params_get.argtypes = [vp, vp, ci]
     L.cosim_scenario_checks_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]
     L.cosim_scenario_checks_get.argtypes = [vp, vp, vp, vp, vp]
+    L.cosim_scenario_curves_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.cosim_scenario_curves_get.argtypes = [vp, vp, vp]
+    L.cosim_scenario_curves_clear.argtypes = [vp]
     L.cosim_fall_set.argtypes = [vp, ctypes.c_float, ctypes.c_float, ci, vp, ci]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
@@ -127,7 +130,8 @@ def load_library():
                "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
                "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get",
                "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get", "cosim_scenario_params_set",
-               "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get"):
+               "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get", "cosim_scenario_curves_set",
+               "cosim_scenario_curves_get", "cosim_scenario_curves_clear"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -143,7 +147,8 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
            "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
            "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get",
-           "cosim_scenario_params_set", "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get"]
+           "cosim_scenario_params_set", "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get",
+           "cosim_scenario_curves_set", "cosim_scenario_curves_get", "cosim_scenario_curves_clear"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -395,6 +400,32 @@ class Engine:
         """``cosim_scenario_checks_get``: rings ``[N, slots, words]``, ended-episode counts ``[N]`` and (or ``None``) open rows ``[N,
         words]``, int32."""
         self._check(self.L.cosim_scenario_checks_get(self.h, records_ptr, counts_ptr, open_ptr, stream))
+
+    def scenario_curves_set(self, csr):
+        """``cosim_scenario_curves_set``: ``csr`` = the seven host arrays ``(adr, t [n, 3], signal, index, lo, hi, bins)`` of
+        ``ScenarioTable.pack_curves`` (``None``: clear the curves)."""
+        if csr is None:
+            self._check(self.L.cosim_scenario_curves_set(self.h, 0, None, None, None, None, None, None, None))
+            return
+        adr, t, signal, index, lo, hi, bins = csr
+        adr, t = np.ascontiguousarray(adr, dtype=np.int32), np.ascontiguousarray(t, dtype=np.int32)
+        signal, index, bins = (np.ascontiguousarray(x, dtype=np.int32) for x in (signal, index, bins))
+        lo, hi = np.ascontiguousarray(lo, dtype=np.float32), np.ascontiguousarray(hi, dtype=np.float32)
+        if adr.ndim != 1 or adr.size < 1:
+            raise ValueError("scenario_curves_set: adr must be [S + 1]")
+        n = int(max(adr.max(), 0))
+        if t.size < 3 * n or min(signal.size, index.size, lo.size, hi.size, bins.size) < n:   # (the engine reads the arrays up to the addresses)
+            raise ValueError(f"scenario_curves_set: the item arrays are shorter than their row addresses ({n} items)")
+        self._check(self.L.cosim_scenario_curves_set(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, signal.ctypes.data,
+                                                     index.ctypes.data, lo.ctypes.data, hi.ctypes.data, bins.ctypes.data))
+
+    def scenario_curves_get(self, cells_ptr, stream=None):
+        """``cosim_scenario_curves_get``: the cells, uint32 ``[scenario_curve_words]``."""
+        self._check(self.L.cosim_scenario_curves_get(self.h, cells_ptr, stream))
+
+    def scenario_curves_clear(self):
+        """``cosim_scenario_curves_clear``: empty cells, every env's episode begun anew."""
+        self._check(self.L.cosim_scenario_curves_clear(self.h))
 
     def scenario_params_get(self) -> np.ndarray:
         """``cosim_scenario_params_get``: the effective parameter records, host float32 ``[N, param_stride]``."""

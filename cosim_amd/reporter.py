@@ -164,7 +164,29 @@ class FleetReporter:
             out["episodes"] = self.episodes()
         if getattr(self.env, "check_slots", 0) > 0:
             out.setdefault("episodes", {})["checks"] = self.checks()
+        if getattr(self.env, "curves_armed", False):
+            out.setdefault("episodes", {})["curves"] = self.fleet_curves().summary()
         return out
+
+    def fleet_curves(self):
+        """The env's response curves (``BatchedEnv(scenarios=TABLE, curves=True)``) as a ``Curves``.  Under ``torch.distributed`` the
+        cells are all-reduced -- SUM for the counts, the fixed-point sums and the histograms, MIN / MAX for the extremes' keys -- so
+        ranks that set the same table hold one fleet's curves, exactly."""
+        import torch.distributed as dist
+        from .curves import Curves
+        cv = self.env.curves()
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            t = self.env.torch
+            kind = cv.word_kinds()
+            cells = cv.cells.copy()
+            for k, op, view in ((0, dist.ReduceOp.SUM, None), (3, dist.ReduceOp.SUM, np.int64), (1, dist.ReduceOp.MIN, None), (2, dist.ReduceOp.MAX, None)):
+                w = cells[kind == k]
+                x = t.tensor((w.view(view) if view is not None else w).astype(np.int64), dtype=t.int64, device=self.env.device)
+                dist.all_reduce(x, op=op)
+                y = x.cpu().numpy()
+                cells[kind == k] = y.view(np.uint32) if view is not None else y.astype(np.uint32)
+            cv = Curves(cells, cv.adr, cv.spec, cv.lohi, cv.bins, cv.names)
+        return cv
 
     def checks(self) -> dict:
         """The verdicts of the env's scenario checks (``BatchedEnv(scenarios=TABLE, check_slots=SLOTS)``) summarised:

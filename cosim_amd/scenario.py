@@ -25,6 +25,14 @@ the step, judged on the device.  ``signal``: ``"info"`` / ``"abs_info"`` (index 
 ``"tracking_error"`` (index = command entry), ``"torque_max"``, ``"up"`` (index 0), ``"qpos"`` / ``"qvel"`` / ``"abs_qvel"`` (index = an
 int or a joint name: the joint's first qpos / dof address).  ``mode`` ``"always"`` / ``"settle"`` / ``"mean"``, ``op`` ``"<"`` / ``">"``.
 ``cosim_amd/checks.py`` has the verdict container and the numpy twin.
+
+Response curves (``cosim_scenario_curves_set``, csrc/cosim_curves.hip): a scenario may hold ``"curves": [[t0, t1, every, signal, index,
+lo, hi, bins], ...]`` (an optional ninth entry names the item; or a dict with those keys and ``"name"``), at most 8: the signal --
+``signal`` / ``index`` exactly as in a check -- is sampled at every control step whose pre-step episode clock ``t`` holds ``t0 <= t <
+t1`` and ``(t - t0) % every == 0``, into time bin ``(t - t0) // every`` of ``ceil((t1 - t0) / every) <= 1024``; when the episode ends
+its samples go into per-(scenario, item, outcome) cells on the device: count, fixed-point sum, min, max and a histogram of ``bins``
+(0..64; 0: none) equal bins over ``[lo, hi)`` plus an underflow and an overflow row.  ``cosim_amd/curves.py`` has the container and the
+numpy twin.
 """
 from __future__ import annotations
 
@@ -44,6 +52,8 @@ CHECK_MODES = {"always": 0, "settle": 1, "mean": 2}
 CHECK_OPS = {"<": 0, ">": 1}
 MAX_CHECK_ITEMS = 64
 _CHECK_KEYS = ("t0", "t1", "signal", "index", "mode", "op", "bound")
+MAX_CURVE_ITEMS, MAX_CURVE_T, MAX_CURVE_BINS = 8, 1024, 64
+_CURVE_KEYS = ("t0", "t1", "every", "signal", "index", "lo", "hi", "bins")
 # consistent only as a set that compile.env_constants computes in fp64 on the host
 REFUSED_PARAM_FIELDS = ("body_mass", "body_invweight0", "dof_invweight0", "meaninertia")
 _FIELD_NAMES = {v: k for k, v in PARAM_FIELDS.items()}
@@ -105,9 +115,10 @@ class ScenarioTable:
             raise ValueError(f"ScenarioTable: {len(scenarios)} scenarios: must be 1..{MAX_ROWS}")
         self.keys, self.pushes, self.param_windows, self.params = [], [], [], None
         self.check_rows, self.checks = [], None
+        self.curve_rows, self.curves = [], None
         for s, sc in enumerate(scenarios):
             sc = sc or {}
-            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "name"}:
+            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "name"}:
                 raise ValueError(f"ScenarioTable: scenario {s}: a mapping with the keys 'commands' and 'pushes' is expected, got {sc!r}")
             keys, pushes = [], []
             for r, row in enumerate(sc.get("commands") or []):
@@ -141,11 +152,65 @@ class ScenarioTable:
             self.pushes.append(pushes)
             self.param_windows.append(_param_windows(s, sc.get("params") or []))
             self.check_rows.append(_check_rows(s, sc.get("checks") or []))
+            self.curve_rows.append(_curve_rows(s, sc.get("curves") or []))
         if names is not None or not self.has_params:
             self.resolve(names or {})
         cn = (names or {}).get("checks")
         if cn is not None or not any(isinstance(r[3], str) for rows in self.check_rows for r in rows):
             self.resolve_checks(cn)
+        if cn is not None or not any(isinstance(r[4], str) for rows in self.curve_rows for r in rows):
+            self.resolve_curves(cn)
+
+    @property
+    def has_curves(self) -> bool:
+        return any(self.curve_rows)
+
+    def resolve_curves(self, names: dict = None) -> "ScenarioTable":
+        """Resolve the curves against ``names`` (``check_names(compiled_model, info_dim, command_dim)``: the checks' name tables):
+        ``self.curves[s]`` becomes the list of items ``(t0, t1, every, signal id, index, float32 lo, float32 hi, bins, name)``.  With
+        ``names`` ``None`` only int indices resolve and no range is checked (the engine checks them).  Raises ``ValueError`` naming
+        the scenario and the item."""
+        out = []
+        for s, rows in enumerate(self.curve_rows):
+            items = []
+            for r, (t0, t1, every, signal, index, lo, hi, bins, name) in enumerate(rows):
+                who = f"ScenarioTable: scenario {s}, curve item {r}"
+                if isinstance(index, str):
+                    if names is None:
+                        raise ValueError(f"{who}: index '{index}' needs the model's names to be resolved (check_names)")
+                    index = _check_index(who, signal, index, names)
+                if names is not None:
+                    width = _signal_width(signal, names)
+                    if not 0 <= index < width:
+                        raise ValueError(f"{who}: index {index} out of range: '{signal}' has {width} entries")
+                items.append((t0, t1, every, CHECK_SIGNALS[signal], int(index), np.float32(lo), np.float32(hi), bins,
+                              name if name is not None else f"{signal}[{index}] @{t0}:{t1}:{every}"))
+            out.append(items)
+        self.curves = out
+        return self
+
+    def _resolved_curves(self):
+        if self.curves is None:
+            raise ValueError("ScenarioTable: the curves are not resolved yet: call resolve_curves(check_names(model, info_dim, command_dim))")
+        return self.curves
+
+    @property
+    def n_curve_items(self) -> int:
+        return sum(len(c) for c in self.curve_rows)
+
+    def pack_curves(self):
+        """``(adr int32[S + 1], t int32[n, 3] (t0, t1, every), signal int32[n], index int32[n], lo float32[n], hi float32[n], bins
+        int32[n])``: the items in the CSR form of ``cosim_scenario_curves_set``."""
+        C = self._resolved_curves()
+        adr = np.cumsum([0] + [len(c) for c in C]).astype(np.int32)
+        flat = [it for c in C for it in c]
+        col = lambda k, dt: np.array([it[k] for it in flat], dtype=dt)   # noqa: E731
+        return (adr, np.array([it[:3] for it in flat], dtype=np.int32).reshape(-1, 3), col(3, np.int32), col(4, np.int32), col(5, np.float32),
+                col(6, np.float32), col(7, np.int32))
+
+    def curve_item_names(self) -> list:
+        """Per scenario, the names of its curve items (the given name, or one made from the item's fields)."""
+        return [[it[8] for it in c] for c in self._resolved_curves()]
 
     @property
     def has_checks(self) -> bool:
@@ -275,6 +340,10 @@ class ScenarioTable:
             if rows:
                 sc["checks"] = [[t0, t1, signal, index, mode, op, float(bound)] + ([name] if name is not None else [])
                                 for t0, t1, signal, index, mode, op, bound, name in rows]
+        for sc, rows in zip(out, self.curve_rows):
+            if rows:
+                sc["curves"] = [[t0, t1, every, signal, index, float(lo), float(hi), bins] + ([name] if name is not None else [])
+                                for t0, t1, every, signal, index, lo, hi, bins, name in rows]
         return out
 
     def pack(self):
@@ -380,6 +449,63 @@ def _check_index(who: str, signal: str, index: str, names: dict) -> int:
     raise ValueError(f"{who}: signal '{signal}' takes an int index, got '{index}'")
 
 
+def _signal_width(signal: str, names: dict) -> int:
+    """How many entries a signal's ``index`` may name on the model behind ``names``."""
+    return {"info": names["info_dim"], "abs_info": names["info_dim"], "tracking_error": min(names["command_dim"], 3), "torque_max": 1,
+            "up": 1 if names["nq"] >= 7 else 0, "qpos": names["nq"], "qvel": names["nv"], "abs_qvel": names["nv"]}[signal]
+
+
+def _curve_rows(s: int, rows) -> list:
+    """The ``"curves"`` rows of scenario ``s``, checked for everything that needs no model: ``(t0, t1, every, signal, index, lo, hi,
+    bins, name or None)``."""
+    out = []
+    if not isinstance(rows, (list, tuple)):
+        raise ValueError(f"ScenarioTable: scenario {s}: 'curves' must be a list of items, got {rows!r}")
+    if len(rows) > MAX_CURVE_ITEMS:
+        raise ValueError(f"ScenarioTable: scenario {s}: {len(rows)} curve items, at most {MAX_CURVE_ITEMS}")
+    for r, row in enumerate(rows):
+        who = f"ScenarioTable: scenario {s}, curve item {r}"
+        name = None
+        if isinstance(row, dict):
+            if set(row) - set(_CURVE_KEYS) - {"name"} or any(k not in row for k in _CURVE_KEYS if k not in ("index", "every", "bins")):
+                raise ValueError(f"{who}: a mapping with the keys {', '.join(_CURVE_KEYS)} (and 'name') is expected, got {row!r}")
+            name = row.get("name")
+            row = [row.get(k, {"every": 1}.get(k, 0)) for k in _CURVE_KEYS]
+        elif isinstance(row, (list, tuple)) and len(row) == 9:
+            row, name = list(row[:8]), row[8]
+        if not isinstance(row, (list, tuple)) or len(row) != 8:
+            raise ValueError(f"{who}: expected [t0, t1, every, signal, index, lo, hi, bins] and an optional name, got {row!r}")
+        t0, t1, every, signal, index, lo, hi, bins = row
+        try:
+            t0f, t1f, evf, lo, hi, bf = float(t0), float(t1), float(every), float(lo), float(hi), float(bins)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: times, every, lo, hi and bins must be numbers, got {row!r}") from None
+        fmax = float(np.finfo(np.float32).max)
+        if not (math.isfinite(lo) and math.isfinite(hi)) or abs(lo) > fmax or abs(hi) > fmax:
+            raise ValueError(f"{who}: non-finite lo / hi")
+        if not (math.isfinite(t0f) and math.isfinite(t1f)) or t0f != int(t0f) or t1f != int(t1f) or not 0 <= t0f < MAX_TIME or not 0 <= t1f <= MAX_TIME:
+            raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
+        if t1f <= t0f:
+            raise ValueError(f"{who}: t1 {int(t1f)} is not after t0 {int(t0f)}")
+        if not math.isfinite(evf) or evf != int(evf) or evf < 1:
+            raise ValueError(f"{who}: every must be a whole number of control steps >= 1, got {every!r}")
+        T = -(-(int(t1f) - int(t0f)) // int(evf))
+        if T > MAX_CURVE_T:
+            raise ValueError(f"{who}: {T} time bins, at most {MAX_CURVE_T}")
+        if not math.isfinite(bf) or bf != int(bf) or not 0 <= bf <= MAX_CURVE_BINS:
+            raise ValueError(f"{who}: bins must be 0..{MAX_CURVE_BINS}, got {bins!r}")
+        if int(bf) > 0 and not float(np.float32(hi)) > float(np.float32(lo)):
+            raise ValueError(f"{who}: hi {hi!r} is not above lo {lo!r}")
+        if signal not in CHECK_SIGNALS:
+            raise ValueError(f"{who}: unknown signal {signal!r} (one of {', '.join(CHECK_SIGNALS)})")
+        if isinstance(index, (bool, float)) or not isinstance(index, (int, np.integer, str)):
+            raise ValueError(f"{who}: index must be an int or a name, got {index!r}")
+        if name is not None and not isinstance(name, str):
+            raise ValueError(f"{who}: the name must be a string, got {name!r}")
+        out.append((int(t0f), int(t1f), int(evf), signal, index if isinstance(index, str) else int(index), lo, hi, int(bf), name))
+    return out
+
+
 def _check_rows(s: int, rows) -> list:
     """The ``"checks"`` rows of scenario ``s``, checked for everything that needs no model: ``(t0, t1, signal, index, mode, op, bound,
     name or None)``."""
@@ -424,14 +550,24 @@ def _check_rows(s: int, rows) -> list:
 
 
 def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = (),
-          params: Iterable = (), checks: Iterable = ()) -> Iterator[dict]:
+          params: Iterable = (), checks: Iterable = (), curves: Iterable = ()) -> Iterator[dict]:
     """The cartesian product command rows x push speeds x directions x push times as scenarios, commands outermost: each holds its
     command from episode step 0 and one push of ``speed`` m/s along the world direction ``angle`` (radians about z, 0 = +x) held over
     ``(t0, t1)``.  With no speeds or no times the product is over the commands alone (no push).
     ``len(list(sweep(C, V, D, T))) == len(C) * len(V) * len(D) * len(T)``.  ``params``: a list of window lists (each a scenario's
     ``"params"`` value, possibly empty) is one more cartesian axis, innermost: every scenario above is emitted once per window list,
     ``len(...) * len(P)`` scenarios in all.  ``checks``: a list of check lists (each a scenario's ``"checks"`` value, possibly empty)
-    is one more axis, innermost of all: ``len(...) * len(K)`` scenarios."""
+    is one more axis, inside the parameters: ``len(...) * len(K)`` scenarios.  ``curves``: a list of curve lists (each a scenario's
+    ``"curves"`` value, possibly empty) is one more axis, innermost of all."""
+    curves = [list(c) for c in curves]
+    if curves:
+        for sc in sweep(commands, push_speeds, directions, push_times, params, checks):
+            for cl in curves:
+                out = dict(sc)
+                if cl:
+                    out["curves"] = [dict(c) if isinstance(c, dict) else list(c) for c in cl]
+                yield out
+        return
     checks = [list(c) for c in checks]
     if checks:
         for sc in sweep(commands, push_speeds, directions, push_times, params):

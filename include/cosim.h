@@ -413,6 +413,42 @@ int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
  * `stream` otherwise. */
 int cosim_scenario_checks_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream);
 
+/* Response curves of the scenario table that is set: per scenario, the ensemble time series of a signal over the episode clock,
+ * split by outcome, kept on the device (cosim_amd/csrc/cosim_curves.h has the rule).  Scenario s owns the items [adr[s], adr[s + 1])
+ * (at most 8).  Item i = (t0, t1, every) = t[3i .. 3i + 2], signal, index (the checks' signals, above), lo, hi, bins (B, 0..64) takes
+ * one sample at every control step whose PRE-STEP episode clock t holds t0 <= t < t1 and (t - t0) % every == 0, into time bin
+ * j = (t - t0) / every of T = ceil((t1 - t0) / every) <= 1024.  Signals 4..7 take no sample on a row with a done flag, 0..3 do.
+ * Samples are staged per env (int32[N][stage words], plain stores; 0x7fc00000 = no sample, a NaN or +-inf sample is 0x7fc00001).
+ * When a row carries a done flag the episode's staged bins are folded into the cells of (scenario row, item, class) -- class 1 if
+ * `terminated` is set (a fall rule included), else 0 -- and the stage is emptied.  The cells are 32-bit words; item i of the table
+ * (in CSR order) owns two blocks of cw = ((B + 8) T rounded up to even) words, class 0 then class 1, one item after the other, the
+ * time bin innermost:  count[T] | nan[T] | min[T] | max[T] | sum[T] (int64) | hist[B + 2][T].
+ *   a non-finite sample adds 1 to nan[j] and nothing else;  a finite v adds 1 to count[j] and llrint((double)clamp(v, +-2^20) * 2^20)
+ *   (round to nearest even) to sum[j], takes the unsigned min / max of key(v) = bits ^ (bits >> 31 ? 0xffffffff : 0x80000000) into
+ *   min[j] / max[j] (empty: 0xffffffff / 0), and with B > 0 adds 1 to hist row 0 if v < lo, B + 1 if v >= hi, else
+ *   1 + min((int)((v - lo) * inv_w), B - 1) in fp32, inv_w = float32(B / (double(hi) - double(lo))).
+ * Every update is an integer atomic, so the cells are a function of the set of ended episodes alone: not of the ranges, the streams
+ * or the arrival order.  cosim_reset, cosim_restore, cosim_set and this call discard what the envs they touch had staged (an
+ * episode the host cuts is in no cell); an episode that did not begin at a reset contributes the bins it sampled; open episodes are
+ * not in the cells.  curves_step_kernel runs behind every range's last launch of a control step, behind the checks' launch, on the
+ * range's own stream: no host read, no join, a captured step carries it; it only reads what the step wrote.  Items of the counts and
+ * sizes of the ones that are set (same row addresses, same T and B) are rewritten in place: a captured graph picks the new values
+ * up; every call empties the cells.
+ * n_scn = 0 clears the curves (no launch, pointer or byte then differs from an engine that never had any); otherwise n_scn must be
+ * the "scenario_rows" of the table that is set.  cosim_scenario_set with another S, or clearing the table, drops the curves.
+ * Validated on the host before anything changes, the message names the scenario and the item (COSIM_EINVAL): non-finite lo / hi,
+ * hi <= lo with bins > 0, t1 <= t0, times outside [0, 2^30), every < 1, T > 1024, more than 8 items, bins outside 0..64, an unknown
+ * signal, an index out of range for the model, cells or stage above 256 MiB each (a design limit), no table set or another S.
+ * While curves are set cosim_step without info_out_dev returns COSIM_EINVAL; cosim_rollout stays refused (a scenario table is set);
+ * cosim_profile_step does not feed the curves; curves are not part of a snapshot.  cosim_query answers "scenario_curve_items" (0:
+ * none), "scenario_curve_words" (all cells) and "scenario_curve_stage_words" (per env). */
+int cosim_scenario_curves_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t /*[n][3]: t0, t1, every*/,
+                              const int32_t* signal, const int32_t* index, const float* lo, const float* hi, const int32_t* bins);
+/* cells_dev uint32[scenario_curve_words].  Joins the ranges, like cosim_ledger_get; asynchronous on `stream` otherwise. */
+int cosim_scenario_curves_get(cosim_engine_t* e, uint32_t* cells_dev, void* stream);
+/* Empties the cells and begins every env's episode anew (what was staged is discarded).  Joins the ranges and waits for the device. */
+int cosim_scenario_curves_clear(cosim_engine_t* e);
+
 /* Fall rules (the reference ends an episode early only through a robot's own _is_done, which is an empty body list for
  * flamingo_light_v1 and False for w4_p_v2 and humanoid_p_v0): the step kernels end an episode on the posture of the state a control
  * step ends in, per cause.  Evaluated once per control step (every step of a rollout launch, the last substep launch of the split
