@@ -23,6 +23,7 @@
 #include "cosim_curves.hip"
 #include "cosim_plan.h"
 #include "cosim_ranges.h"
+#include "cosim_tables.h"
 
 using namespace cosim;
 
@@ -34,6 +35,7 @@ static int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+#define RC_TRY(...) do { const int _rc = (__VA_ARGS__); if (_rc) return _rc; } while (0)   // a COSIM_* code of a call that has set the message
 #define HIP_TRY(expr)                                                                         \
   do {                                                                                        \
     hipError_t _e = (expr);                                                                   \
@@ -175,6 +177,14 @@ struct cosim_engine {
 template <auto KERNEL, int ENVS_PER_BLOCK = 1>
 static void launch_k(cosim_engine*, const KArgs& a, int n, hipStream_t s) {
   hipLaunchKernelGGL(KERNEL, dim3((n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK), dim3(64), 0, s, a);
+}
+// ... and one for the small kernels beside them (ledger, traces, scenario family, snapshots): `count` envs (rows, cell blocks) at
+// PER_BLOCK of them per block of THREADS threads
+template <int PER_BLOCK, int THREADS, class K, class A>
+static int launch_small(K kernel, const A& a, int count, hipStream_t s) {
+  hipLaunchKernelGGL(kernel, dim3((count + PER_BLOCK - 1) / PER_BLOCK), dim3(THREADS), 0, s, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
 }
 // a KernelSet entry: KERNEL behind its launcher, with the capacities of the LDS layout L it is instantiated with
 template <class L, auto KERNEL, int ENVS_PER_BLOCK = 1>
@@ -610,9 +620,7 @@ static int history_pack(cosim_engine* e, int first, int count, hipStream_t s) {
   SnapArgs a = snap_args(e);
   a.rows = e->d_hist + (size_t)(e->hist_captures % e->hist_slots) * e->n_envs * (size_t)(a.s_stride + a.p_stride);
   a.env_first = first; a.env_count = count;
-  hipLaunchKernelGGL(snapshot_pack_kernel, dim3(count), dim3(64), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<1, 64>(snapshot_pack_kernel, a, count, s);
 }
 
 static void history_count(cosim_engine* e) {   // after a cosim_step call was issued in full
@@ -645,9 +653,7 @@ static int ledger_step(cosim_engine* e, int first, int count, int K, const float
   LedgerArgs a = ledger_args(e);
   a.info = info; a.term = term; a.trunc = trunc; a.cmd = a.ncmd > 0 ? cmd : nullptr;
   a.first = first; a.count = count; a.rows = K;
-  hipLaunchKernelGGL(a.scn_row != nullptr ? ledger_step_scn_kernel : ledger_step_kernel, dim3((count + 63) / 64), dim3(64), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<64, 64>(a.scn_row != nullptr ? ledger_step_scn_kernel : ledger_step_kernel, a, count, s);
 }
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode, what they had open is dropped
@@ -655,9 +661,7 @@ static int ledger_begin(cosim_engine* e, const uint8_t* mask, const int* src, in
   if (e->led_slots <= 0) return COSIM_OK;
   LedgerArgs a = ledger_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
-  hipLaunchKernelGGL(ledger_begin_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<64, 64>(ledger_begin_kernel, a, e->n_envs, s);
 }
 
 // ---- scenario table (cosim_scenario.hip)
@@ -673,9 +677,7 @@ static int scenario_launch(cosim_engine* e, int first, int count, const float* c
   a.tab = e->scn; a.state = e->d_state; a.cmd_in = commands_dev; a.cmd_out = e->scn_cmd_out; a.row_out = e->scn_row_out; a.mask = mask;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.reset = reset;
-  hipLaunchKernelGGL(scenario_step_kernel, dim3((count + 63) / 64), dim3(64), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<64, 64>(scenario_step_kernel, a, count, s);
 }
 
 // the windows go with their table (the caller has waited for the device)
@@ -691,9 +693,7 @@ static int scnparams_launch(cosim_engine* e, int first, int count, const uint8_t
   a.tab = e->scn; a.par = e->scnpar; a.state = e->d_state; a.base = e->d_params; a.eff = e->d_params_eff; a.mask = mask;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.p_stride = e->lay.p_stride; a.reset = reset;
-  hipLaunchKernelGGL(scnparams_step_kernel, dim3((count + SCNPAR_WAVES - 1) / SCNPAR_WAVES), dim3(64 * SCNPAR_WAVES), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<SCNPAR_WAVES, 64 * SCNPAR_WAVES>(scnparams_step_kernel, a, count, s);
 }
 
 // ---- checks of the scenario table (cosim_checks.hip)
@@ -719,9 +719,7 @@ static int checks_step(cosim_engine* e, int first, int count, const float* cmd, 
   ChkArgs a = checks_args(e);
   a.cmd = a.cmd_stride > 0 ? cmd : nullptr; a.info = info; a.term = term; a.trunc = trunc;
   a.first = first; a.count = count;
-  hipLaunchKernelGGL(checks_step_kernel, dim3((count + CHK_WAVES - 1) / CHK_WAVES), dim3(64 * CHK_WAVES), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<CHK_WAVES, 64 * CHK_WAVES>(checks_step_kernel, a, count, s);
 }
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode with clean accumulators
@@ -729,9 +727,7 @@ static int checks_begin(cosim_engine* e, const uint8_t* mask, const int* src, in
   if (e->chk.n_scn <= 0) return COSIM_OK;
   ChkArgs a = checks_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
-  hipLaunchKernelGGL(checks_begin_kernel, dim3((e->n_envs + CHK_WAVES - 1) / CHK_WAVES), dim3(64 * CHK_WAVES), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<CHK_WAVES, 64 * CHK_WAVES>(checks_begin_kernel, a, e->n_envs, s);
 }
 
 // the checks go with their table (the caller has waited for the device)
@@ -764,9 +760,7 @@ static int curves_step(cosim_engine* e, int first, int count, const float* cmd, 
   CurArgs a = curves_args(e);
   a.cmd = a.cmd_stride > 0 ? cmd : nullptr; a.info = info; a.term = term; a.trunc = trunc;
   a.first = first; a.count = count;
-  hipLaunchKernelGGL(curves_step_kernel, dim3((count + CUR_WAVES - 1) / CUR_WAVES), dim3(64 * CUR_WAVES), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<CUR_WAVES, 64 * CUR_WAVES>(curves_step_kernel, a, count, s);
 }
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode with an empty stage
@@ -774,18 +768,11 @@ static int curves_begin(cosim_engine* e, const uint8_t* mask, const int* src, in
   if (e->cur.n_scn <= 0) return COSIM_OK;
   CurArgs a = curves_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows;
-  hipLaunchKernelGGL(curves_begin_kernel, dim3((e->n_envs + CUR_WAVES - 1) / CUR_WAVES), dim3(64 * CUR_WAVES), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<CUR_WAVES, 64 * CUR_WAVES>(curves_begin_kernel, a, e->n_envs, s);
 }
 
 // every cell back to empty
-static int curves_zero(cosim_engine* e, hipStream_t s) {
-  CurArgs a = curves_args(e);
-  hipLaunchKernelGGL(curves_clear_kernel, dim3(2 * e->cur.n_items), dim3(256), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
-}
+static int curves_zero(cosim_engine* e, hipStream_t s) { return launch_small<1, 256>(curves_clear_kernel, curves_args(e), 2 * e->cur.n_items, s); }
 
 // the curves go with their table (the caller has waited for the device)
 static void curves_free(cosim_engine* e) {
@@ -834,9 +821,7 @@ static int ftrace_step(cosim_engine* e, int first, int count, const float* actio
   FtArgs a = ftrace_args(e);
   a.actions = actions; a.cmd = a.cd > 0 ? cmd : nullptr; a.info = info; a.term = term; a.trunc = trunc;
   a.first = first; a.count = count;
-  hipLaunchKernelGGL(ftrace_step_kernel, dim3(count), dim3(64), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<1, 64>(ftrace_step_kernel, a, count, s);
 }
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode in an empty window
@@ -844,14 +829,40 @@ static int ftrace_begin(cosim_engine* e, const uint8_t* mask, const int* src, in
   if (e->ft_frames <= 0) return COSIM_OK;
   FtArgs a = ftrace_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
-  hipLaunchKernelGGL(ftrace_begin_kernel, dim3(e->n_envs), dim3(64), 0, s, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<1, 64>(ftrace_begin_kernel, a, e->n_envs, s);
 }
 
 static void ftrace_free(cosim_engine* e) {
   (void)hipFree(e->d_ft_buf); (void)hipFree(e->d_ft_cnt);
   e->d_ft_buf = nullptr; e->d_ft_cnt = nullptr; e->ft_frames = 0; e->ft_keep = 0; e->ft_mask = 0;
+}
+
+// ---- the observers: ledger, failure traces, checks, curves -- in that order at every site.  Each kernel writes only its own buffers.
+static_assert(LEDGER_NO_RESET == FT_NO_RESET && FT_NO_RESET == CHK_NO_RESET, "one flag value for \"did not begin at a reset\"");
+
+// behind a reset / set / restore on the same stream: the masked envs (null: all; with a restore's source index: those it did not
+// refuse) begin an episode; flag 0 or LEDGER_NO_RESET.  Behind the reset because meta[14] is the new episode's spawn row
+static int observers_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
+  RC_TRY(ledger_begin(e, mask, src, n_rows, flag, s));
+  RC_TRY(ftrace_begin(e, mask, src, n_rows, flag, s));
+  RC_TRY(checks_begin(e, mask, src, n_rows, flag, s));
+  return curves_begin(e, mask, src, n_rows, s);
+}
+
+// behind the last launch of a step (rollout: of `rows` steps, where only the ledger can be armed) of envs [first, first + count) on
+// the same stream: plain device work, capturable.  They only read what the step wrote, and the caller's action rows, which outlive it
+static int observers_step(cosim_engine* e, int first, int count, int rows, const float* actions, const float* cmd, const float* info,
+                          const uint8_t* term, const uint8_t* trunc, hipStream_t s) {
+  if (e->led_slots > 0) RC_TRY(ledger_step(e, first, count, rows, info, term, trunc, cmd, s));
+  if (e->ft_frames > 0) RC_TRY(ftrace_step(e, first, count, actions, cmd, info, term, trunc, s));
+  if (e->chk.n_scn > 0) RC_TRY(checks_step(e, first, count, cmd, info, term, trunc, s));
+  if (e->cur.n_scn > 0) RC_TRY(curves_step(e, first, count, cmd, info, term, trunc, s));
+  return COSIM_OK;
+}
+
+// why a step without info_out_dev is refused: the first armed observer's words, null if none is armed
+static const char* observers_info_msg(const cosim_engine* e) {
+  return e->led_slots > 0 ? LEDGER_INFO_MSG : e->ft_frames > 0 ? FTRACE_INFO_MSG : e->chk.n_scn > 0 ? CHECKS_INFO_MSG : e->cur.n_scn > 0 ? CURVES_INFO_MSG : nullptr;
 }
 
 extern "C" {
@@ -1236,7 +1247,8 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
   else if (n == "pair_mode") { e->pair_coop = (int)host[0] != 0; return COSIM_OK; }   // 1: hull pairs one at a time, wave-cooperative scans
   else return fail(COSIM_EINVAL, "cosim_set_param: unknown parameter " + n);
   if (count != e->n_envs * width) return fail(COSIM_EINVAL, "cosim_set_param: " + n + " expects n_envs*" + std::to_string(width) + " values");
-  { int rc = refresh_param_mirror(e); if (rc) return rc; }
+  int rc = refresh_param_mirror(e);
+  if (rc) return rc;
   for (int i = 0; i < e->n_envs; i++)
     memcpy(e->h_params.data() + (size_t)i * L.p_stride + off, host + (size_t)i * width, width * sizeof(float));
   e->params_dirty = true;
@@ -1277,29 +1289,20 @@ static KArgs base_args(cosim_engine* e) {
 int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* commands_dev, float* state_out_dev, void* stream) {
   if (!e || !state_out_dev) return fail(COSIM_EINVAL, "cosim_reset: null argument");
   HIP_TRY(hipSetDevice(e->device));
-  int rc = upload_params(e);
-  if (rc) return rc;
-  rc = join_ranges(e, (hipStream_t)stream);
-  if (rc) return rc;
+  RC_TRY(upload_params(e));
+  RC_TRY(join_ranges(e, (hipStream_t)stream));
   if (e->scn.n_scn > 0) {   // the reset's state vector carries the scenario's first command
     if (e->ho.command_dim > 0 && !commands_dev)
       return fail(COSIM_EINVAL, "cosim_reset: a scenario table is set (cosim_scenario_set) and commands_dev is NULL: the scenario kernel passes the caller's command through where a scenario has no keyframe yet");
-    rc = scenario_launch(e, 0, e->n_envs, commands_dev, mask_dev, 1, (hipStream_t)stream);
-    if (rc) return rc;
-    if (e->scnpar.n_items > 0) { rc = scnparams_launch(e, 0, e->n_envs, mask_dev, 1, (hipStream_t)stream); if (rc) return rc; }
+    RC_TRY(scenario_launch(e, 0, e->n_envs, commands_dev, mask_dev, 1, (hipStream_t)stream));
+    if (e->scnpar.n_items > 0) RC_TRY(scnparams_launch(e, 0, e->n_envs, mask_dev, 1, (hipStream_t)stream));
   }
   KArgs a = base_args(e);
   a.mode = MODE_RESET; a.mask = mask_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
   e->plan.reset.launch(e, a, e->n_envs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   if (mask_dev == nullptr) e->stepped = false;
-  rc = ledger_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);   // behind the reset: meta[14] is the new episode's spawn row
-  if (rc) return rc;
-  rc = ftrace_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
-  if (rc) return rc;
-  rc = checks_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
-  if (rc) return rc;
-  return curves_begin(e, mask_dev, nullptr, 0, (hipStream_t)stream);
+  return observers_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
 }
 
 int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* commands_dev, float* state_out_dev, uint8_t* terminated_dev,
@@ -1374,11 +1377,9 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
     return fail(COSIM_EINVAL, "cosim_rollout: a scenario table is set (cosim_scenario_set): one launch reads one command row; step with cosim_step or clear the table");
   e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
-  int rc = upload_params(e);
-  if (rc) return rc;
+  RC_TRY(upload_params(e));
   hipStream_t cs = (hipStream_t)stream;
-  rc = join_ranges(e, cs);
-  if (rc) return rc;
+  RC_TRY(join_ranges(e, cs));
   KArgs a = base_args(e);
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = commands_dev; a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev; a.roll_steps = steps;
@@ -1396,10 +1397,7 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
     HIP_TRY(hipGetLastError());
     if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
     if (a.ovf) { p.rollout_fix.launch(e, a, a.env_count, s); HIP_TRY(hipGetLastError()); }
-    if (e->led_slots > 0) {
-      rc = ledger_step(e, a.env_first, a.env_count, steps, info_out_dev, terminated_dev, truncated_dev, commands_dev, s);
-      if (rc) return rc;
-    }
+    RC_TRY(observers_step(e, a.env_first, a.env_count, steps, actions_dev, commands_dev, info_out_dev, terminated_dev, truncated_dev, s));
   }
   if (e->n_ranges > 1) { e->join_pending = true; return join_ranges(e, cs); }
   return COSIM_OK;
@@ -1469,14 +1467,10 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   if (e->ho.command_dim > 0 && !commands_dev) return fail(COSIM_EINVAL, "cosim_step: commands_dev is required when command_dim > 0");
   if (first < 0 || count < 1 || first + count > e->n_envs) return fail(COSIM_EINVAL, "cosim_step_range: range outside the fleet");
   if (e->sw.epw == 2 && ((first | count) & 1)) return fail(COSIM_EINVAL, "cosim_step_range: two-environments-per-wave kernel needs even ranges");
-  if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + LEDGER_INFO_MSG);
-  if (e->ft_frames > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + FTRACE_INFO_MSG);
-  if (e->chk.n_scn > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + CHECKS_INFO_MSG);
-  if (e->cur.n_scn > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_step") + CURVES_INFO_MSG);
+  if (!info_out_dev && observers_info_msg(e)) return fail(COSIM_EINVAL, std::string("cosim_step") + observers_info_msg(e));
   e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
-  int rc = upload_params(e);
-  if (rc) return rc;
+  RC_TRY(upload_params(e));
   KArgs a = base_args(e);
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev;
@@ -1499,10 +1493,10 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   }
   // scenario table: this step's command and push of every env of the range, ahead of the step's first launch (plain device work:
   // capturable); inside the timing pair, so cosim_kernel_time() includes it
-  if (e->scn.n_scn > 0) { rc = scenario_launch(e, first, count, commands_dev, nullptr, 0, s); if (rc) return rc; }
+  if (e->scn.n_scn > 0) RC_TRY(scenario_launch(e, first, count, commands_dev, nullptr, 0, s));
   // parameter windows: this step's effective parameter records of the range, ahead of every launch that reads them (the substep
   // launches of the split pipeline and the fix-up kernels' redo included: all are handed the same pointer by base_args)
-  if (e->scnpar.n_items > 0) { rc = scnparams_launch(e, first, count, nullptr, 0, s); if (rc) return rc; }
+  if (e->scnpar.n_items > 0) RC_TRY(scnparams_launch(e, first, count, nullptr, 0, s));
   if (p.split) {
     // one pair of launches per substep: the prism walk (narrow_waves waves per env), then the solver with the contacts it left; with
     // "hfield_fixup", the substeps the solver gave up (more ground contacts than its slots) are redone right behind it from the same
@@ -1523,15 +1517,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     p.fixup.launch(e, a, count, s);
     HIP_TRY(hipGetLastError());
   }
-  // episode ledger: this step's rows of the range, behind the range's last launch of the step (plain device work: capturable)
-  if (e->led_slots > 0) { rc = ledger_step(e, first, count, 1, info_out_dev, terminated_dev, truncated_dev, scenario_cmd(e, commands_dev), s); if (rc) return rc; }
-  // failure traces: this step's frame of the range, behind the ledger's launch (reads the caller's action rows: they outlive the step)
-  if (e->ft_frames > 0) { rc = ftrace_step(e, first, count, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s); if (rc) return rc; }
-  // scenario checks: this step's samples of the range, behind the ledger's launch (they only read what the step wrote)
-  if (e->chk.n_scn > 0) { rc = checks_step(e, first, count, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s); if (rc) return rc; }
-  // response curves: this step's samples and folds of the range, behind the checks' launch (they only read what the step wrote)
-  if (e->cur.n_scn > 0) return curves_step(e, first, count, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
-  return COSIM_OK;
+  return observers_step(e, first, count, 1, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
 }
 
 // Spawn table: validate on the host (a message that names the row), upload, place every row on the heightfield with
@@ -1670,35 +1656,23 @@ int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* st
   if (!e || !name || !in_dev) return fail(COSIM_EINVAL, "cosim_set: null argument");
   HIP_TRY(hipSetDevice(e->device));
   int off, width;
-  int rc = locate(e, name, &off, &width);
-  if (rc) return rc;
-  rc = join_ranges(e, (hipStream_t)stream);
-  if (rc) return rc;
+  RC_TRY(locate(e, name, &off, &width));
+  RC_TRY(join_ranges(e, (hipStream_t)stream));
   HIP_TRY(hipMemcpy2DAsync(e->d_state + off, e->lay.s_stride * sizeof(float), in_dev, width * sizeof(float), width * sizeof(float),
                            e->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   e->stepped = true;
-  rc = ledger_begin(e, nullptr, nullptr, 0, LEDGER_NO_RESET, (hipStream_t)stream);
-  if (rc) return rc;
-  rc = ftrace_begin(e, nullptr, nullptr, 0, FT_NO_RESET, (hipStream_t)stream);
-  if (rc) return rc;
-  rc = checks_begin(e, nullptr, nullptr, 0, CHK_NO_RESET, (hipStream_t)stream);
-  if (rc) return rc;
-  return curves_begin(e, nullptr, nullptr, 0, (hipStream_t)stream);
+  return observers_begin(e, nullptr, nullptr, 0, LEDGER_NO_RESET, (hipStream_t)stream);
 }
 
 int cosim_snapshot(cosim_engine_t* e, float* out_dev, void* stream) {
   if (!e || !out_dev) return fail(COSIM_EINVAL, "cosim_snapshot: null argument");
   if ((uintptr_t)out_dev & 15) return fail(COSIM_EINVAL, "cosim_snapshot: out_dev must be 16-byte aligned");
   HIP_TRY(hipSetDevice(e->device));
-  int rc = upload_params(e);   // the row holds the parameters the next step would run with
-  if (rc) return rc;
-  rc = join_ranges(e, (hipStream_t)stream);
-  if (rc) return rc;
+  RC_TRY(upload_params(e));   // the row holds the parameters the next step would run with
+  RC_TRY(join_ranges(e, (hipStream_t)stream));
   SnapArgs a = snap_args(e);
   a.rows = out_dev;
-  hipLaunchKernelGGL(snapshot_pack_kernel, dim3(e->n_envs), dim3(64), 0, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return launch_small<1, 64>(snapshot_pack_kernel, a, e->n_envs, (hipStream_t)stream);
 }
 
 int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const int32_t* src_index_dev, const uint8_t* mask_dev,
@@ -1710,10 +1684,8 @@ int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const
                                   std::to_string(snap_rows));
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
-  int rc = upload_params(e);   // a pending upload first: the envs this restore leaves alone get their new parameters, the others the row's
-  if (rc) return rc;
-  rc = join_ranges(e, cs);
-  if (rc) return rc;
+  RC_TRY(upload_params(e));   // a pending upload first: the envs this restore leaves alone get their new parameters, the others the row's
+  RC_TRY(join_ranges(e, cs));
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   HIP_TRY(hipStreamIsCapturing(cs, &cap));
   if (src_index_dev) {
@@ -1727,18 +1699,10 @@ int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const
   SnapArgs a = snap_args(e);
   a.rows = const_cast<float*>(snap_dev); a.n_rows = snap_rows; a.src = src_index_dev; a.mask = mask_dev;
   a.err = src_index_dev ? e->d_snap_err : nullptr; a.with_params = with_params != 0;
-  hipLaunchKernelGGL(snapshot_gather_kernel, dim3(e->n_envs), dim3(64), 0, cs, a);
-  HIP_TRY(hipGetLastError());
+  RC_TRY(launch_small<1, 64>(snapshot_gather_kernel, a, e->n_envs, cs));
   if (with_params) e->params_mirror_stale = true;
   e->stepped = true;
-  rc = ledger_begin(e, mask_dev, src_index_dev, snap_rows, LEDGER_NO_RESET, cs);
-  if (rc) return rc;
-  rc = ftrace_begin(e, mask_dev, src_index_dev, snap_rows, FT_NO_RESET, cs);
-  if (rc) return rc;
-  rc = checks_begin(e, mask_dev, src_index_dev, snap_rows, CHK_NO_RESET, cs);
-  if (rc) return rc;
-  rc = curves_begin(e, mask_dev, src_index_dev, snap_rows, cs);
-  if (rc) return rc;
+  RC_TRY(observers_begin(e, mask_dev, src_index_dev, snap_rows, LEDGER_NO_RESET, cs));
   if (src_index_dev && cap == hipStreamCaptureStatusNone) {   // the kernel skipped what it refused; report it
     HIP_TRY(hipMemcpyAsync(e->h_snap_err, e->d_snap_err, 2 * sizeof(int), hipMemcpyDeviceToHost, cs));
     HIP_TRY(hipStreamSynchronize(cs));
@@ -1798,8 +1762,7 @@ int cosim_ledger_set(cosim_engine_t* e, int slots) {
   if (r != hipSuccess) { ledger_free(e); return fail(COSIM_EHIP, std::string("cosim_ledger_set: ") + hipGetErrorString(r)); }
   e->led_slots = slots;
   // every env starts an open episode at length 0 (the range streams do not order with the null stream: wait here, cold path)
-  int rc = ledger_begin(e, nullptr, nullptr, 0, e->stepped ? LEDGER_NO_RESET : 0, 0);
-  if (rc) return rc;
+  RC_TRY(ledger_begin(e, nullptr, nullptr, 0, e->stepped ? LEDGER_NO_RESET : 0, 0));
   HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
 }
@@ -1810,16 +1773,14 @@ int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_de
   if (open_dev && ((uintptr_t)open_dev & 15)) return fail(COSIM_EINVAL, "cosim_ledger_get: open_dev must be 16-byte aligned");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
-  int rc = join_ranges(e, cs);
-  if (rc) return rc;
+  RC_TRY(join_ranges(e, cs));
   const size_t N = (size_t)e->n_envs;
   HIP_TRY(hipMemcpyAsync(records_dev, e->d_led_rec, N * e->led_slots * LEDGER_WORDS * sizeof(int), hipMemcpyDeviceToDevice, cs));
   HIP_TRY(hipMemcpyAsync(counts_dev, e->d_led_acc + 2 * N, N * sizeof(int), hipMemcpyDeviceToDevice, cs));
   if (open_dev) {
     LedgerArgs a = ledger_args(e);
     a.rec = open_dev;
-    hipLaunchKernelGGL(a.scn_row != nullptr ? ledger_open_scn_kernel : ledger_open_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, cs, a);
-    HIP_TRY(hipGetLastError());
+    return launch_small<64, 64>(a.scn_row != nullptr ? ledger_open_scn_kernel : ledger_open_kernel, a, e->n_envs, cs);
   }
   return COSIM_OK;
 }
@@ -1851,8 +1812,7 @@ int cosim_ftrace_set(cosim_engine_t* e, int frames, int keep, int on_mask) {
   }
   e->ft_frames = frames; e->ft_keep = keep; e->ft_mask = on_mask;
   // every env starts an open episode in an empty window (the range streams do not order with the null stream: wait here, cold path)
-  int rc = ftrace_begin(e, nullptr, nullptr, 0, e->stepped ? FT_NO_RESET : 0, 0);
-  if (rc) return rc;
+  RC_TRY(ftrace_begin(e, nullptr, nullptr, 0, e->stepped ? FT_NO_RESET : 0, 0));
   HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
 }
@@ -1862,8 +1822,7 @@ int cosim_ftrace_get(cosim_engine_t* e, int32_t* buffers_dev, int32_t* counts_de
   if (e->ft_frames <= 0) return fail(COSIM_EINVAL, "cosim_ftrace_get: no failure traces are set (cosim_ftrace_set)");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
-  int rc = join_ranges(e, cs);
-  if (rc) return rc;
+  RC_TRY(join_ranges(e, cs));
   const size_t N = (size_t)e->n_envs;
   const size_t bytes = N * (size_t)(e->ft_keep + 1) * ftrace_buf_words(e->ft_frames, ftrace_words(e)) * sizeof(int);
   HIP_TRY(hipMemcpyAsync(buffers_dev, e->d_ft_buf, bytes, hipMemcpyDeviceToDevice, cs));
@@ -1872,181 +1831,118 @@ int cosim_ftrace_get(cosim_engine_t* e, int32_t* buffers_dev, int32_t* counts_de
   if (open_dev) {
     FtArgs a = ftrace_args(e);
     a.open_out = open_dev;
-    hipLaunchKernelGGL(ftrace_open_kernel, dim3((e->n_envs + 63) / 64), dim3(64), 0, cs, a);
-    HIP_TRY(hipGetLastError());
+    return launch_small<64, 64>(ftrace_open_kernel, a, e->n_envs, cs);
   }
   return COSIM_OK;
 }
 
-// Scenario table: validate on the host (a message that names the scenario and the row), join the ranges, wait for the device and
-// upload.  A table of the sizes of the one that is set is rewritten in place: the device pointers stay, captured graphs pick it up.
+// ---- the setters of the scenario family: clear, refusals, validator (cosim_tables.h), join and wait, pack, in place or fresh, upload
+static TableDims table_dims(const cosim_engine* e) {
+  return {e->model.nq, e->model.nv, e->model.nu, e->model.ngeom, e->ho.info_dim, e->ho.command_dim, e->lay.p_kp, e->lay.p_kd, e->lay.p_gmu, e->lay.p_floss};
+}
+
+// every range's launches in flight may still read a table and write the buffers that go with it: join the ranges, wait for the device
+static int table_quiesce(cosim_engine* e, hipStream_t s) {
+  RC_TRY(join_ranges(e, s));
+  HIP_TRY(hipDeviceSynchronize());
+  return COSIM_OK;
+}
+
+// n_scn = 0 clears
+static int table_clear(cosim_engine* e, hipStream_t s, void (*drop)(cosim_engine*)) {
+  RC_TRY(table_quiesce(e, s));
+  drop(e);
+  return COSIM_OK;
+}
+
+// windows, checks and curves (`what`) are rows of the scenario table that is set
+static int table_rows_match(const cosim_engine* e, const std::string& fn, const char* what, int n_scn) {
+  if (e->scn.n_scn == 0) return fail(COSIM_EINVAL, fn + ": no scenario table is set (cosim_scenario_set): " + what + " are rows of a table; set the table first");
+  if (n_scn != e->scn.n_scn) return fail(COSIM_EINVAL, fn + ": " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.n_scn));
+  return COSIM_OK;
+}
+
+// the image that is set, read back for the in-place test (cold path)
+static int table_download(const char* d, const WordPacker& pk, std::vector<int32_t>& old) {
+  old.resize(pk.words());
+  HIP_TRY(hipMemcpy(old.data(), d, pk.bytes(), hipMemcpyDeviceToHost));
+  return COSIM_OK;
+}
+
+// Scenario table.  A table of the sizes of the one that is set is rewritten in place: the device pointers stay, captured graphs pick
+// it up.
 int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, const int32_t* key_t, const float* key_cmd, const int32_t* push_adr,
                        const int32_t* push_t, const float* push_v, int mode, float* cmd_out_dev, int32_t* row_out_dev, void* stream) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_set: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) {   // clear (launches in flight still read the table: wait for them)
-    int rc = join_ranges(e, (hipStream_t)stream);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    scenario_free(e);
-    return COSIM_OK;
-  }
+  if (n_scn == 0) return table_clear(e, (hipStream_t)stream, scenario_free);
   const int cd = e->ho.command_dim;
   if (n_scn < 1 || n_scn > SCN_MAX_ROWS) return fail(COSIM_EINVAL, "cosim_scenario_set: " + std::to_string(n_scn) + " scenarios: must be 1..65536 (0 clears the table)");
   if (mode != SCN_MODE_ENV && mode != SCN_MODE_CYCLE) return fail(COSIM_EINVAL, "cosim_scenario_set: mode must be 0 (env) or 1 (cycle)");
   if (mode == SCN_MODE_CYCLE && !e->ho.auto_reset)
     return fail(COSIM_EINVAL, "cosim_scenario_set: mode cycle needs auto_reset: without it the episode count advances on every flagged step");
-  if (!key_adr || !push_adr || !row_out_dev || (cd > 0 && !cmd_out_dev)) return fail(COSIM_EINVAL, "cosim_scenario_set: null argument");
-  if (key_adr[0] != 0 || push_adr[0] != 0) return fail(COSIM_EINVAL, "cosim_scenario_set: key_adr[0] and push_adr[0] must be 0");
-  for (int s = 0; s < n_scn; s++) {
-    const long long nk = (long long)key_adr[s + 1] - key_adr[s], np = (long long)push_adr[s + 1] - push_adr[s];
-    const std::string who = "cosim_scenario_set: scenario " + std::to_string(s);
-    if (nk < 0 || np < 0) return fail(COSIM_EINVAL, who + ": row addresses must not decrease");
-    if (nk > SCN_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(nk) + " keyframes, at most 64");
-    if (np > SCN_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(np) + " push windows, at most 64");
-    if ((nk > 0 && (!key_t || (cd > 0 && !key_cmd))) || (np > 0 && (!push_t || !push_v))) return fail(COSIM_EINVAL, who + ": null table array");
-    for (int k = key_adr[s]; k < key_adr[s + 1]; k++) {
-      const std::string row = who + ", keyframe " + std::to_string(k - key_adr[s]);
-      if (key_t[k] < 0 || key_t[k] >= SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": time " + std::to_string(key_t[k]) + " outside [0, 2^30)");
-      if (k > key_adr[s] && key_t[k] <= key_t[k - 1])
-        return fail(COSIM_EINVAL, row + ": time " + std::to_string(key_t[k]) + " does not increase (previous " + std::to_string(key_t[k - 1]) + ")");
-      for (int c = 0; c < cd; c++)
-        if (!std::isfinite(key_cmd[(size_t)k * cd + c])) return fail(COSIM_EINVAL, row + ": command " + std::to_string(c) + " is not finite");
-    }
-    for (int p = push_adr[s]; p < push_adr[s + 1]; p++) {
-      const std::string row = who + ", push window " + std::to_string(p - push_adr[s]);
-      const int t0 = push_t[2 * p], t1 = push_t[2 * p + 1];
-      if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": times outside [0, 2^30)");
-      if (t1 <= t0) return fail(COSIM_EINVAL, row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0));
-      for (int c = 0; c < 3; c++)
-        if (!std::isfinite(push_v[3 * (size_t)p + c])) return fail(COSIM_EINVAL, row + ": velocity " + std::to_string(c) + " is not finite");
-    }
-  }
-  const int nkey = key_adr[n_scn], npush = push_adr[n_scn];
-  int rc = join_ranges(e, (hipStream_t)stream);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());   // every range's launches in flight may still read the table / write the old output buffers
-  // key_adr | push_adr | key_t | push_t | key_cmd | push_v, every array 4-byte words
-  const size_t o_kadr = 0, o_padr = o_kadr + (size_t)n_scn + 1, o_kt = o_padr + (size_t)n_scn + 1, o_pt = o_kt + (size_t)nkey,
-               o_kc = o_pt + 2 * (size_t)npush, o_pv = o_kc + (size_t)nkey * cd, words = o_pv + 3 * (size_t)npush;
+  if (!row_out_dev || (cd > 0 && !cmd_out_dev)) return fail(COSIM_EINVAL, "cosim_scenario_set: null argument");
+  const ScnRaw raw = {n_scn, key_adr, key_t, key_cmd, push_adr, push_t, push_v};
+  const ScnShape v = validate_scenario(table_dims(e), raw);
+  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  RC_TRY(table_quiesce(e, (hipStream_t)stream));
+  ScnTable tab = {};
+  WordPacker pk;
+  pack_scenario(pk, tab, cd, raw, v);
   // other sizes: a new allocation, which replaces the old one only once it is filled (a failure leaves the table that was set)
-  const bool in_place = n_scn == e->scn.n_scn && nkey == e->scn_nkey && npush == e->scn_npush;
+  const bool in_place = n_scn == e->scn.n_scn && v.nkey == e->scn_nkey && v.npush == e->scn_npush;
   char* d_new = e->d_scn;
-  if (!in_place) HIP_TRY(hipMalloc(&d_new, words * 4));
-  std::vector<int32_t> h(words, 0);
-  memcpy(&h[o_kadr], key_adr, ((size_t)n_scn + 1) * 4);
-  memcpy(&h[o_padr], push_adr, ((size_t)n_scn + 1) * 4);
-  if (nkey > 0) { memcpy(&h[o_kt], key_t, (size_t)nkey * 4); if (cd > 0) memcpy(&h[o_kc], key_cmd, (size_t)nkey * cd * 4); }
-  if (npush > 0) { memcpy(&h[o_pt], push_t, 2 * (size_t)npush * 4); memcpy(&h[o_pv], push_v, 3 * (size_t)npush * 4); }
-  const hipError_t r = hipMemcpy(d_new, h.data(), words * 4, hipMemcpyHostToDevice);
+  if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
+  const hipError_t r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
   if (r != hipSuccess) {   // a new allocation is dropped and the old table stays; an in-place rewrite may be half written: no table then
     if (in_place) scenario_free(e); else (void)hipFree(d_new);
     return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
   }
   if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
   if (n_scn != e->scn.n_scn) { scnparams_free(e); checks_free(e); curves_free(e); }   // parameter windows, checks and curves are rows of the table they were set for: another S drops them
-  const int32_t* base = reinterpret_cast<const int32_t*>(e->d_scn);
-  e->scn.key_adr = base + o_kadr; e->scn.push_adr = base + o_padr; e->scn.key_t = base + o_kt; e->scn.push_t = base + o_pt;
-  e->scn.key_cmd = reinterpret_cast<const float*>(base + o_kc); e->scn.push_v = reinterpret_cast<const float*>(base + o_pv);
-  e->scn.n_scn = n_scn; e->scn.mode = mode; e->scn.cd = cd;
-  e->scn.gid_off = (unsigned)(((e->env_id0 % n_scn) + n_scn) % n_scn);
-  e->scn_nkey = nkey; e->scn_npush = npush;
+  pk.patch(e->d_scn);
+  tab.mode = mode;
+  tab.gid_off = (unsigned)(((e->env_id0 % n_scn) + n_scn) % n_scn);
+  e->scn = tab;
+  e->scn_nkey = v.nkey; e->scn_npush = v.npush;
   e->scn_cmd_out = cmd_out_dev; e->scn_row_out = row_out_dev;
   return COSIM_OK;
 }
 
-// Parameter windows of the scenario table that is set: validate on the host (a message that names the scenario and the row), resolve
-// field + index to a word of the parameter record, join the ranges, wait for the device, upload, and write every env's effective
-// record once.  Items of the count of the ones that are set are rewritten in place: the device pointers stay, captured graphs pick
-// the new values up.
+// Parameter windows of the scenario table that is set; every env's effective record is written once.  Items of the count of the ones
+// that are set are rewritten in place: the device pointers stay, captured graphs pick the new values up.
 int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t, const int32_t* field, const int32_t* index,
                               const int32_t* op, const float* value) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_params_set: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) {   // clear (launches in flight still read the effective records: wait for them)
-    int rc = join_ranges(e, 0);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    scnparams_free(e);
-    return COSIM_OK;
-  }
-  if (e->scn.n_scn == 0)
-    return fail(COSIM_EINVAL, "cosim_scenario_params_set: no scenario table is set (cosim_scenario_set): parameter windows are rows of a table; set the table first");
-  if (n_scn != e->scn.n_scn)
-    return fail(COSIM_EINVAL, "cosim_scenario_params_set: " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.n_scn));
-  if (!adr) return fail(COSIM_EINVAL, "cosim_scenario_params_set: null argument");
-  if (adr[0] != 0) return fail(COSIM_EINVAL, "cosim_scenario_params_set: adr[0] must be 0");
-  const cosim_model_t& m = e->model;
-  const Layout& L = e->lay;
-  std::vector<int32_t> words;
-  for (int s = 0; s < n_scn; s++) {
-    const long long ni = (long long)adr[s + 1] - adr[s];
-    const std::string who = "cosim_scenario_params_set: scenario " + std::to_string(s);
-    if (ni < 0) return fail(COSIM_EINVAL, who + ": row addresses must not decrease");
-    if (ni > SCNPAR_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(ni) + " parameter items, at most 256");
-    if (ni > 0 && (!t || !field || !index || !op || !value)) return fail(COSIM_EINVAL, who + ": null table array");
-    for (int i = adr[s]; i < adr[s + 1]; i++) {
-      const std::string row = who + ", parameter item " + std::to_string(i - adr[s]);
-      const int t0 = t[2 * i], t1 = t[2 * i + 1];
-      if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": times outside [0, 2^30)");
-      if (t1 <= t0) return fail(COSIM_EINVAL, row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0));
-      int off, width;
-      const char* name;
-      switch (field[i]) {
-        case SCNPAR_KP: off = L.p_kp; width = m.nu; name = "kp"; break;
-        case SCNPAR_KD: off = L.p_kd; width = m.nu; name = "kd"; break;
-        case SCNPAR_GEOM_FRICTION: off = L.p_gmu; width = m.ngeom; name = "geom_friction"; break;
-        case SCNPAR_DOF_FRICTIONLOSS: off = L.p_floss; width = m.nv; name = "dof_frictionloss"; break;
-        case SCNPAR_BODY_MASS: case SCNPAR_BODY_INVWEIGHT0: case SCNPAR_DOF_INVWEIGHT0: case SCNPAR_MEANINERTIA:
-          return fail(COSIM_EINVAL, row + ": field " + std::to_string(field[i]) + " (body_mass, body_invweight0, dof_invweight0, meaninertia) is refused: the mass "
-                      "fields are consistent only as a set computed on the host in fp64; a payload change in mid-episode is out of scope");
-        default: return fail(COSIM_EINVAL, row + ": unknown field " + std::to_string(field[i]) + " (0 kp, 1 kd, 2 geom_friction, 3 dof_frictionloss)");
-      }
-      if (index[i] < 0 || index[i] >= width)
-        return fail(COSIM_EINVAL, row + ": index " + std::to_string(index[i]) + " out of range: " + name + " has " + std::to_string(width) + " entries");
-      if (op[i] != SCNPAR_SCALE && op[i] != SCNPAR_SET) return fail(COSIM_EINVAL, row + ": unknown op " + std::to_string(op[i]) + " (0 scale, 1 set)");
-      if (!std::isfinite(value[i])) return fail(COSIM_EINVAL, row + ": value is not finite");
-      words.push_back(off + index[i]);
-    }
-  }
-  const int n = adr[n_scn];
-  if (n == 0) return fail(COSIM_EINVAL, "cosim_scenario_params_set: the table holds no parameter item (n_scn = 0 clears the windows)");
-  int rc = upload_params(e);   // the effective records written below are built from the current base
-  if (rc) return rc;
-  rc = join_ranges(e, 0);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());   // launches in flight may still read the items
-  // adr | t | word | op | value, every array 4-byte words
-  const size_t o_adr = 0, o_t = o_adr + (size_t)n_scn + 1, o_w = o_t + 2 * (size_t)n, o_op = o_w + (size_t)n, o_v = o_op + (size_t)n, total = o_v + (size_t)n;
-  const bool in_place = e->scnpar.n_items == n && e->scnpar.n_scn == n_scn;
+  if (n_scn == 0) return table_clear(e, 0, scnparams_free);
+  RC_TRY(table_rows_match(e, "cosim_scenario_params_set", "parameter windows", n_scn));
+  const ParRaw raw = {n_scn, adr, t, field, index, op, value};
+  const ParShape v = validate_params(table_dims(e), raw);
+  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  RC_TRY(upload_params(e));   // the effective records written below are built from the current base
+  RC_TRY(table_quiesce(e, 0));
+  ScnParTable tab = {};
+  WordPacker pk;
+  pack_params(pk, tab, raw, v);
+  const bool in_place = e->scnpar.n_items == v.n && e->scnpar.n_scn == n_scn;
   char* d_new = e->d_scnpar;
-  float* d_eff = e->d_params_eff;
-  if (!in_place) HIP_TRY(hipMalloc(&d_new, total * 4));
-  if (!d_eff) {
-    const hipError_t r = hipMalloc(&d_eff, (size_t)e->n_envs * L.p_stride * sizeof(float));
-    if (r != hipSuccess) { if (!in_place) (void)hipFree(d_new); return fail(COSIM_EHIP, std::string("cosim_scenario_params_set: ") + hipGetErrorString(r)); }
-    e->d_params_eff = d_eff;
+  if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
+  if (!e->d_params_eff) {
+    const hipError_t r = hipMalloc(&e->d_params_eff, (size_t)e->n_envs * e->lay.p_stride * sizeof(float));
+    if (r != hipSuccess) { e->d_params_eff = nullptr; if (!in_place) (void)hipFree(d_new); return fail(COSIM_EHIP, std::string("cosim_scenario_params_set: ") + hipGetErrorString(r)); }
   }
-  std::vector<int32_t> h(total, 0);
-  memcpy(&h[o_adr], adr, ((size_t)n_scn + 1) * 4);
-  memcpy(&h[o_t], t, 2 * (size_t)n * 4);
-  memcpy(&h[o_w], words.data(), (size_t)n * 4);
-  memcpy(&h[o_op], op, (size_t)n * 4);
-  memcpy(&h[o_v], value, (size_t)n * 4);
-  const hipError_t r = hipMemcpy(d_new, h.data(), total * 4, hipMemcpyHostToDevice);
+  const hipError_t r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
   if (r != hipSuccess) {   // a new allocation is dropped and the old items stay; an in-place rewrite may be half written: no windows then
     if (in_place) scnparams_free(e);
     else { (void)hipFree(d_new); if (e->scnpar.n_items == 0) { (void)hipFree(e->d_params_eff); e->d_params_eff = nullptr; } }
     return fail(COSIM_EHIP, std::string("cosim_scenario_params_set: ") + hipGetErrorString(r));
   }
   if (!in_place) { (void)hipFree(e->d_scnpar); e->d_scnpar = d_new; }
-  const int32_t* base = reinterpret_cast<const int32_t*>(e->d_scnpar);
-  e->scnpar.adr = base + o_adr; e->scnpar.t = base + o_t; e->scnpar.word = base + o_w; e->scnpar.op = base + o_op;
-  e->scnpar.value = reinterpret_cast<const float*>(base + o_v);
-  e->scnpar.n_scn = n_scn; e->scnpar.n_items = n;
+  pk.patch(e->d_scnpar);
+  e->scnpar = tab;
   // every env's effective record once, at its current clock: no row is ever unwritten
-  rc = scnparams_launch(e, 0, e->n_envs, nullptr, 0, 0);
-  if (rc) return rc;
+  RC_TRY(scnparams_launch(e, 0, e->n_envs, nullptr, 0, 0));
   HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
 }
@@ -2068,101 +1964,33 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity) {
   return e->lay.p_stride;
 }
 
-// Checks of the scenario table that is set: validate on the host (a message that names the scenario and the item), join the ranges,
-// wait for the device, upload, and begin every env's episode with clean accumulators.  Items of the counts of the ones that are set
-// (same S, same row addresses, same slots) are rewritten in place: the device pointers, the counters and the records stay, and
-// captured graphs pick the new values up.
+// Checks of the scenario table that is set; every env's episode begins with clean accumulators.  Items of the counts of the ones that
+// are set (same S, same row addresses, same slots) are rewritten in place: the device pointers, the counters and the records stay,
+// and captured graphs pick the new values up.
 int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t, const int32_t* signal, const int32_t* index,
                               const int32_t* mode, const int32_t* cmp, const float* bound, int slots) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) {   // clear (launches in flight still read the items: wait for them)
-    int rc = join_ranges(e, 0);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
+  if (n_scn == 0) return table_clear(e, 0, checks_free);
+  RC_TRY(table_rows_match(e, "cosim_scenario_checks_set", "checks", n_scn));
+  const ChkRaw raw = {n_scn, adr, t, signal, index, mode, cmp, bound, slots};
+  const ChkShape v = validate_checks(table_dims(e), raw);
+  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  RC_TRY(table_quiesce(e, 0));
+  ChkTable tab = {};
+  WordPacker pk;
+  pack_checks(pk, tab, raw, v);
+  bool in_place = e->chk.n_scn == n_scn && e->chk.n_items == v.n && e->chk.I == v.I && e->chk_slots == slots;
+  if (in_place) {
+    std::vector<int32_t> old;
+    RC_TRY(table_download(e->d_chk, pk, old));
+    in_place = checks_same_rows(pk, tab, old.data());
+  }
+  const size_t N = (size_t)e->n_envs, I = (size_t)v.I, W = (size_t)checks_words(v.I);
+  auto alloc = [&]() -> hipError_t {   // everything anew: the table, clean accumulators, counters and records at zero
     checks_free(e);
-    return COSIM_OK;
-  }
-  if (e->scn.n_scn == 0)
-    return fail(COSIM_EINVAL, "cosim_scenario_checks_set: no scenario table is set (cosim_scenario_set): checks are rows of a table; set the table first");
-  if (n_scn != e->scn.n_scn)
-    return fail(COSIM_EINVAL, "cosim_scenario_checks_set: " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.n_scn));
-  if (slots < 1 || slots > CHK_MAX_SLOTS) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: slots " + std::to_string(slots) + " outside 1..64");
-  if (!adr) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: null argument");
-  if (adr[0] != 0) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: adr[0] must be 0");
-  const cosim_model_t& m = e->model;
-  const int ncmd = e->ho.command_dim < 3 ? e->ho.command_dim : 3;
-  int most = 0;
-  for (int s = 0; s < n_scn; s++) {
-    const long long ni = (long long)adr[s + 1] - adr[s];
-    const std::string who = "cosim_scenario_checks_set: scenario " + std::to_string(s);
-    if (ni < 0) return fail(COSIM_EINVAL, who + ": row addresses must not decrease");
-    if (ni > CHK_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(ni) + " check items, at most 64");
-    if (ni > 0 && (!t || !signal || !index || !mode || !cmp || !bound)) return fail(COSIM_EINVAL, who + ": null table array");
-    if ((int)ni > most) most = (int)ni;
-    for (int i = adr[s]; i < adr[s + 1]; i++) {
-      const std::string row = who + ", check item " + std::to_string(i - adr[s]);
-      const int t0 = t[2 * i], t1 = t[2 * i + 1];
-      if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": times outside [0, 2^30)");
-      if (t1 <= t0) return fail(COSIM_EINVAL, row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0));
-      int width;
-      const char* name;
-      switch (signal[i]) {
-        case CHK_INFO: width = e->ho.info_dim; name = "info"; break;
-        case CHK_ABS_INFO: width = e->ho.info_dim; name = "abs_info"; break;
-        case CHK_TRACKING_ERROR: width = ncmd; name = "tracking_error"; break;
-        case CHK_TORQUE_MAX: width = 1; name = "torque_max"; break;
-        case CHK_UP: width = m.nq >= 7 ? 1 : 0; name = "up"; break;
-        case CHK_QPOS: width = m.nq; name = "qpos"; break;
-        case CHK_QVEL: width = m.nv; name = "qvel"; break;
-        case CHK_ABS_QVEL: width = m.nv; name = "abs_qvel"; break;
-        default:
-          return fail(COSIM_EINVAL, row + ": unknown signal " + std::to_string(signal[i]) +
-                                        " (0 info, 1 abs_info, 2 tracking_error, 3 torque_max, 4 up, 5 qpos, 6 qvel, 7 abs_qvel)");
-      }
-      if (index[i] < 0 || index[i] >= width)
-        return fail(COSIM_EINVAL, row + ": index " + std::to_string(index[i]) + " out of range: " + name + " has " + std::to_string(width) + " entries");
-      if (mode[i] < 0 || mode[i] >= CHK_NMODE) return fail(COSIM_EINVAL, row + ": unknown mode " + std::to_string(mode[i]) + " (0 always, 1 settle, 2 mean)");
-      if (cmp[i] != CHK_LT && cmp[i] != CHK_GT) return fail(COSIM_EINVAL, row + ": unknown cmp " + std::to_string(cmp[i]) + " (0 <, 1 >)");
-      if (!std::isfinite(bound[i])) return fail(COSIM_EINVAL, row + ": bound is not finite");
-    }
-  }
-  const int n = adr[n_scn];
-  if (n == 0) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: the table holds no check item (n_scn = 0 clears the checks)");
-  const int I = (most + 1) & ~1;
-  int rc = join_ranges(e, 0);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());   // launches in flight may still read the items
-  // adr | t | signal | index | mode | cmp | bound, every array 4-byte words
-  const size_t o_adr = 0, o_t = o_adr + (size_t)n_scn + 1, o_s = o_t + 2 * (size_t)n, o_i = o_s + (size_t)n, o_m = o_i + (size_t)n,
-               o_c = o_m + (size_t)n, o_b = o_c + (size_t)n, total = o_b + (size_t)n;
-  std::vector<int32_t> h(total, 0);
-  memcpy(&h[o_adr], adr, ((size_t)n_scn + 1) * 4);
-  memcpy(&h[o_t], t, 2 * (size_t)n * 4);
-  memcpy(&h[o_s], signal, (size_t)n * 4);
-  memcpy(&h[o_i], index, (size_t)n * 4);
-  memcpy(&h[o_m], mode, (size_t)n * 4);
-  memcpy(&h[o_c], cmp, (size_t)n * 4);
-  memcpy(&h[o_b], bound, (size_t)n * 4);
-  bool in_place = e->chk.n_scn == n_scn && e->chk.n_items == n && e->chk.I == I && e->chk_slots == slots;
-  if (in_place) {   // the same counts row by row?  (the row addresses set are read back: cold path)
-    std::vector<int32_t> old((size_t)n_scn + 1);
-    HIP_TRY(hipMemcpy(old.data(), e->d_chk, old.size() * 4, hipMemcpyDeviceToHost));
-    in_place = memcmp(old.data(), adr, old.size() * 4) == 0;
-  }
-  if (in_place) {   // pointers, counters and records stay; the open episodes begin again, as below: no verdict mixes two sets of values
-    const hipError_t r = hipMemcpy(e->d_chk, h.data(), total * 4, hipMemcpyHostToDevice);
-    if (r != hipSuccess) { checks_free(e); return fail(COSIM_EHIP, std::string("cosim_scenario_checks_set: ") + hipGetErrorString(r)); }
-    rc = checks_begin(e, nullptr, nullptr, 0, e->stepped ? CHK_NO_RESET : 0, 0);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
-    return COSIM_OK;
-  }
-  checks_free(e);
-  const size_t N = (size_t)e->n_envs, W = (size_t)checks_words(I);
-  auto alloc = [&]() -> hipError_t {
     hipError_t r;
-    if ((r = hipMalloc(&e->d_chk, total * 4)) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_chk, pk.bytes())) != hipSuccess) return r;
     if ((r = hipMalloc(&e->d_chk_ext, N * I * sizeof(float))) != hipSuccess) return r;
     if ((r = hipMalloc(&e->d_chk_aux, N * I * sizeof(int))) != hipSuccess) return r;
     if ((r = hipMalloc(&e->d_chk_n, N * I * sizeof(int))) != hipSuccess) return r;
@@ -2170,20 +1998,17 @@ int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
     if ((r = hipMalloc(&e->d_chk_cnt, N * CHK_NCNT * sizeof(int))) != hipSuccess) return r;
     if ((r = hipMalloc(&e->d_chk_rec, N * slots * W * sizeof(int))) != hipSuccess) return r;
     if ((r = hipMemset(e->d_chk_cnt, 0, N * CHK_NCNT * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMemset(e->d_chk_rec, 0, N * slots * W * sizeof(int))) != hipSuccess) return r;
-    return hipMemcpy(e->d_chk, h.data(), total * 4, hipMemcpyHostToDevice);
+    return hipMemset(e->d_chk_rec, 0, N * slots * W * sizeof(int));
   };
-  const hipError_t r = alloc();
+  hipError_t r = in_place ? hipSuccess : alloc();
+  if (r == hipSuccess) r = hipMemcpy(e->d_chk, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
   if (r != hipSuccess) { checks_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_checks_set: ") + hipGetErrorString(r)); }
-  const int32_t* base = reinterpret_cast<const int32_t*>(e->d_chk);
-  e->chk.adr = base + o_adr; e->chk.t = base + o_t; e->chk.signal = base + o_s; e->chk.index = base + o_i; e->chk.mode = base + o_m;
-  e->chk.cmp = base + o_c; e->chk.bound = reinterpret_cast<const float*>(base + o_b);
-  e->chk.n_scn = n_scn; e->chk.n_items = n; e->chk.I = I;
+  pk.patch(e->d_chk);
+  e->chk = tab;
   e->chk_slots = slots;
-  // every env starts an open episode with clean accumulators at its current clock (the range streams do not order with the null
-  // stream: wait here, cold path)
-  rc = checks_begin(e, nullptr, nullptr, 0, e->stepped ? CHK_NO_RESET : 0, 0);
-  if (rc) return rc;
+  // every env starts an open episode with clean accumulators at its current clock -- in place too: no verdict mixes two sets of values
+  // (the range streams do not order with the null stream: wait here, cold path)
+  RC_TRY(checks_begin(e, nullptr, nullptr, 0, e->stepped ? CHK_NO_RESET : 0, 0));
   HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
 }
@@ -2195,145 +2020,55 @@ int cosim_scenario_checks_get(cosim_engine_t* e, int32_t* records_dev, int32_t* 
   if (e->chk.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_checks_get: no checks are set (cosim_scenario_checks_set)");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
-  int rc = join_ranges(e, cs);
-  if (rc) return rc;
+  RC_TRY(join_ranges(e, cs));
   const size_t N = (size_t)e->n_envs, W = (size_t)checks_words(e->chk.I);
   HIP_TRY(hipMemcpyAsync(records_dev, e->d_chk_rec, N * e->chk_slots * W * sizeof(int), hipMemcpyDeviceToDevice, cs));
   HIP_TRY(hipMemcpy2DAsync(counts_dev, sizeof(int), e->d_chk_cnt, CHK_NCNT * sizeof(int), sizeof(int), N, hipMemcpyDeviceToDevice, cs));
   if (open_dev) {
     ChkArgs a = checks_args(e);
     a.rec = open_dev;
-    hipLaunchKernelGGL(checks_open_kernel, dim3((e->n_envs + CHK_WAVES - 1) / CHK_WAVES), dim3(64 * CHK_WAVES), 0, cs, a);
-    HIP_TRY(hipGetLastError());
+    return launch_small<CHK_WAVES, 64 * CHK_WAVES>(checks_open_kernel, a, e->n_envs, cs);
   }
   return COSIM_OK;
 }
 
-// Response curves of the scenario table that is set: validate on the host (a message that names the scenario and the item), join the
-// ranges, wait for the device, upload, empty the cells and begin every env's episode with an empty stage.  Items of the counts and
-// sizes of the ones that are set (same S, same row addresses, same T and B item by item) are rewritten in place: the device
-// pointers stay, and captured graphs pick the new values up.
+// Response curves of the scenario table that is set; the cells are emptied and every env's episode begins with an empty stage.  Items
+// of the counts and sizes of the ones that are set (same S, same row addresses, same T and B item by item) are rewritten in place:
+// the device pointers stay, and captured graphs pick the new values up.
 int cosim_scenario_curves_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t, const int32_t* signal, const int32_t* index,
                               const float* lo, const float* hi, const int32_t* bins) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) {   // clear (launches in flight still read the items: wait for them)
-    int rc = join_ranges(e, 0);
-    if (rc) return rc;
-    HIP_TRY(hipDeviceSynchronize());
+  if (n_scn == 0) return table_clear(e, 0, curves_free);
+  RC_TRY(table_rows_match(e, "cosim_scenario_curves_set", "curves", n_scn));
+  const CurRaw raw = {n_scn, adr, t, signal, index, lo, hi, bins};
+  const CurShape v = validate_curves(table_dims(e), e->n_envs, raw);
+  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  RC_TRY(table_quiesce(e, 0));
+  CurTable tab = {};
+  WordPacker pk;
+  pack_curves(pk, tab, raw, v);
+  bool in_place = e->cur.n_scn == n_scn && e->cur.n_items == v.n && e->cur.SW == (int)v.SW && e->cur_words == v.cells;
+  if (in_place) {
+    std::vector<int32_t> old;
+    RC_TRY(table_download(e->d_cur, pk, old));
+    in_place = curves_same_sizes(pk, tab, old.data());
+  }
+  const size_t N = (size_t)e->n_envs;
+  auto alloc = [&]() -> hipError_t {   // everything anew: the table, the stage, the clocks and the cells
     curves_free(e);
-    return COSIM_OK;
-  }
-  if (e->scn.n_scn == 0)
-    return fail(COSIM_EINVAL, "cosim_scenario_curves_set: no scenario table is set (cosim_scenario_set): curves are rows of a table; set the table first");
-  if (n_scn != e->scn.n_scn)
-    return fail(COSIM_EINVAL, "cosim_scenario_curves_set: " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.n_scn));
-  if (!adr) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: null argument");
-  if (adr[0] != 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: adr[0] must be 0");
-  const cosim_model_t& m = e->model;
-  const int ncmd = e->ho.command_dim < 3 ? e->ho.command_dim : 3;
-  for (int s = 0; s < n_scn; s++) {   // the row addresses first: the item loop below reads the arrays through them
-    const long long ni = (long long)adr[s + 1] - adr[s];
-    const std::string who = "cosim_scenario_curves_set: scenario " + std::to_string(s);
-    if (ni < 0) return fail(COSIM_EINVAL, who + ": row addresses must not decrease");
-    if (ni > CUR_MAX_ITEMS) return fail(COSIM_EINVAL, who + ": " + std::to_string(ni) + " curve items, at most 8");
-    if (ni > 0 && (!t || !signal || !index || !lo || !hi || !bins)) return fail(COSIM_EINVAL, who + ": null table array");
-  }
-  const int n = adr[n_scn];
-  if (n == 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: the table holds no curve item (n_scn = 0 clears the curves)");
-  std::vector<int32_t> nt(n), soff(n), coff(n), cw(n);
-  std::vector<float> inv_w(n, 0.f);
-  size_t cells = 0, most = 0;
-  for (int s = 0; s < n_scn; s++) {
-    size_t row_words = 0;
-    for (int i = adr[s]; i < adr[s + 1]; i++) {
-      const std::string row = "cosim_scenario_curves_set: scenario " + std::to_string(s) + ", curve item " + std::to_string(i - adr[s]);
-      const int t0 = t[3 * i], t1 = t[3 * i + 1], every = t[3 * i + 2], B = bins[i];
-      if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return fail(COSIM_EINVAL, row + ": times outside [0, 2^30)");
-      if (t1 <= t0) return fail(COSIM_EINVAL, row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0));
-      if (every < 1) return fail(COSIM_EINVAL, row + ": every " + std::to_string(every) + " is below 1");
-      const int T = curves_nt(t0, t1, every);
-      if (T > CUR_MAX_T) return fail(COSIM_EINVAL, row + ": " + std::to_string(T) + " time bins, at most 1024");
-      if (B < 0 || B > CUR_MAX_BINS) return fail(COSIM_EINVAL, row + ": bins " + std::to_string(B) + " outside 0..64");
-      if (!std::isfinite(lo[i]) || !std::isfinite(hi[i])) return fail(COSIM_EINVAL, row + ": lo / hi is not finite");
-      if (B > 0 && !(hi[i] > lo[i])) return fail(COSIM_EINVAL, row + ": hi is not above lo");
-      int width;
-      const char* name;
-      switch (signal[i]) {
-        case CHK_INFO: width = e->ho.info_dim; name = "info"; break;
-        case CHK_ABS_INFO: width = e->ho.info_dim; name = "abs_info"; break;
-        case CHK_TRACKING_ERROR: width = ncmd; name = "tracking_error"; break;
-        case CHK_TORQUE_MAX: width = 1; name = "torque_max"; break;
-        case CHK_UP: width = m.nq >= 7 ? 1 : 0; name = "up"; break;
-        case CHK_QPOS: width = m.nq; name = "qpos"; break;
-        case CHK_QVEL: width = m.nv; name = "qvel"; break;
-        case CHK_ABS_QVEL: width = m.nv; name = "abs_qvel"; break;
-        default:
-          return fail(COSIM_EINVAL, row + ": unknown signal " + std::to_string(signal[i]) +
-                                        " (0 info, 1 abs_info, 2 tracking_error, 3 torque_max, 4 up, 5 qpos, 6 qvel, 7 abs_qvel)");
-      }
-      if (index[i] < 0 || index[i] >= width)
-        return fail(COSIM_EINVAL, row + ": index " + std::to_string(index[i]) + " out of range: " + name + " has " + std::to_string(width) + " entries");
-      nt[i] = T; soff[i] = (int32_t)row_words; cw[i] = curves_cell_words(T, B);
-      if (cells + 2 * (size_t)cw[i] > CUR_MAX_BYTES / 4) return fail(COSIM_EINVAL, row + ": the cells would exceed 256 MiB (a design limit)");
-      coff[i] = (int32_t)cells;
-      cells += 2 * (size_t)cw[i];
-      row_words += (size_t)T;
-      if (B > 0) inv_w[i] = (float)((double)B / ((double)hi[i] - (double)lo[i]));
-    }
-    if (row_words > most) most = row_words;
-  }
-  const size_t N = (size_t)e->n_envs, SW = most;
-  if (N * SW > CUR_MAX_BYTES / 4)
-    return fail(COSIM_EINVAL, "cosim_scenario_curves_set: the stage, " + std::to_string(SW) + " words for each of " + std::to_string(N) +
-                                  " envs, would exceed 256 MiB (a design limit)");
-  int rc = join_ranges(e, 0);
-  if (rc) return rc;
-  HIP_TRY(hipDeviceSynchronize());   // launches in flight may still read the items
-  // adr | t | signal | index | bins | nt | soff | coff | cw | lo | hi | inv_w, every array 4-byte words
-  const size_t o_adr = 0, o_t = o_adr + (size_t)n_scn + 1, o_s = o_t + 3 * (size_t)n, o_i = o_s + (size_t)n, o_b = o_i + (size_t)n,
-               o_nt = o_b + (size_t)n, o_so = o_nt + (size_t)n, o_co = o_so + (size_t)n, o_cw = o_co + (size_t)n, o_lo = o_cw + (size_t)n,
-               o_hi = o_lo + (size_t)n, o_w = o_hi + (size_t)n, total = o_w + (size_t)n;
-  std::vector<int32_t> h(total, 0);
-  memcpy(&h[o_adr], adr, ((size_t)n_scn + 1) * 4);
-  memcpy(&h[o_t], t, 3 * (size_t)n * 4);
-  memcpy(&h[o_s], signal, (size_t)n * 4);
-  memcpy(&h[o_i], index, (size_t)n * 4);
-  memcpy(&h[o_b], bins, (size_t)n * 4);
-  memcpy(&h[o_nt], nt.data(), (size_t)n * 4);
-  memcpy(&h[o_so], soff.data(), (size_t)n * 4);
-  memcpy(&h[o_co], coff.data(), (size_t)n * 4);
-  memcpy(&h[o_cw], cw.data(), (size_t)n * 4);
-  memcpy(&h[o_lo], lo, (size_t)n * 4);
-  memcpy(&h[o_hi], hi, (size_t)n * 4);
-  memcpy(&h[o_w], inv_w.data(), (size_t)n * 4);
-  bool in_place = e->cur.n_scn == n_scn && e->cur.n_items == n && e->cur.SW == (int)SW && e->cur_words == cells;
-  if (in_place) {   // the same counts and sizes item by item?  (what is set is read back: cold path)
-    std::vector<int32_t> old(total);
-    HIP_TRY(hipMemcpy(old.data(), e->d_cur, total * 4, hipMemcpyDeviceToHost));
-    in_place = memcmp(&old[o_adr], &h[o_adr], ((size_t)n_scn + 1) * 4) == 0 && memcmp(&old[o_b], &h[o_b], 5 * (size_t)n * 4) == 0;
-  }
-  if (!in_place) {
-    curves_free(e);
-    auto alloc = [&]() -> hipError_t {
-      hipError_t r;
-      if ((r = hipMalloc(&e->d_cur, total * 4)) != hipSuccess) return r;
-      if ((r = hipMalloc(&e->d_cur_stage, (N * SW > 0 ? N * SW : 1) * sizeof(int))) != hipSuccess) return r;
-      if ((r = hipMalloc(&e->d_cur_clk, N * sizeof(int))) != hipSuccess) return r;
-      return hipMalloc(&e->d_cur_cells, cells * sizeof(unsigned));
-    };
-    const hipError_t r = alloc();
-    if (r != hipSuccess) { curves_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_set: ") + hipGetErrorString(r)); }
-    const int32_t* base = reinterpret_cast<const int32_t*>(e->d_cur);
-    e->cur.adr = base + o_adr; e->cur.t = base + o_t; e->cur.signal = base + o_s; e->cur.index = base + o_i; e->cur.bins = base + o_b;
-    e->cur.nt = base + o_nt; e->cur.soff = base + o_so; e->cur.coff = base + o_co; e->cur.cw = base + o_cw;
-    e->cur.lo = reinterpret_cast<const float*>(base + o_lo); e->cur.hi = reinterpret_cast<const float*>(base + o_hi);
-    e->cur.inv_w = reinterpret_cast<const float*>(base + o_w);
-    e->cur.n_scn = n_scn; e->cur.n_items = n; e->cur.SW = (int)SW;
-    e->cur_words = cells;
-  }
-  const hipError_t r = hipMemcpy(e->d_cur, h.data(), total * 4, hipMemcpyHostToDevice);
-  if (r != hipSuccess) { curves_free(e); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_set: ") + hipGetErrorString(r)); }
+    hipError_t r;
+    if ((r = hipMalloc(&e->d_cur, pk.bytes())) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_cur_stage, (N * v.SW > 0 ? N * v.SW : 1) * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_cur_clk, N * sizeof(int))) != hipSuccess) return r;
+    return hipMalloc(&e->d_cur_cells, v.cells * sizeof(unsigned));
+  };
+  hipError_t r = in_place ? hipSuccess : alloc();
+  if (r == hipSuccess) r = hipMemcpy(e->d_cur, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) { curves_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_set: ") + hipGetErrorString(r)); }
+  pk.patch(e->d_cur);
+  e->cur = tab;
+  e->cur_words = v.cells;
   return cosim_scenario_curves_clear(e);
 }
 
@@ -2343,13 +2078,10 @@ int cosim_scenario_curves_clear(cosim_engine_t* e) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_curves_clear: null engine");
   if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_clear: no curves are set (cosim_scenario_curves_set)");
   HIP_TRY(hipSetDevice(e->device));
-  int rc = join_ranges(e, 0);
-  if (rc) return rc;
+  RC_TRY(join_ranges(e, 0));
   HIP_TRY(hipDeviceSynchronize());
-  rc = curves_zero(e, 0);
-  if (rc) return rc;
-  rc = curves_begin(e, nullptr, nullptr, 0, 0);
-  if (rc) return rc;
+  RC_TRY(curves_zero(e, 0));
+  RC_TRY(curves_begin(e, nullptr, nullptr, 0, 0));
   HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
 }
@@ -2361,8 +2093,7 @@ int cosim_scenario_curves_get(cosim_engine_t* e, uint32_t* cells_dev, void* stre
   if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_get: no curves are set (cosim_scenario_curves_set)");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
-  int rc = join_ranges(e, cs);
-  if (rc) return rc;
+  RC_TRY(join_ranges(e, cs));
   HIP_TRY(hipMemcpyAsync(cells_dev, e->d_cur_cells, e->cur_words * sizeof(unsigned), hipMemcpyDeviceToDevice, cs));
   return COSIM_OK;
 }

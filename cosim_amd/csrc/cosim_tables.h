@@ -1,0 +1,331 @@
+// cosim_tables.h — what the host does with a table of the scenario family before it reaches the device (cosim_scenario_set,
+// cosim_scenario_params_set, cosim_scenario_checks_set, cosim_scenario_curves_set, include/cosim.h): the rules every such table is
+// held to, one validator per setter, and the packer that lays a table's arrays into one allocation.  Plain C++ with no HIP in it:
+// cosim_engine.hip and a host program (tests/tables_host.cpp) both compile it.
+//
+// A validator takes the caller's raw arrays and what it needs to know of the engine (TableDims); it returns the refusal as
+// cosim_last_error words it (empty: the table is good) and the values the setter derives from the table.  Where a table has several
+// faults the first one in the order of the code below is reported: a row's addresses, then its items, one row after the other.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "cosim_curves.h"
+#include "cosim_scnparams.h"
+
+namespace cosim {
+
+struct TableDims {
+  int nq, nv, nu, ngeom, info_dim, command_dim;
+  int p_kp, p_kd, p_gmu, p_floss;   // offsets in the parameter record
+};
+
+// ---- the shared rules; each returns the refusal, empty if there is none
+// what an id selects: the name the messages use, how many entries it has, and (parameter fields) where they lie in the record
+struct TabEntry { const char* name; int width, off; };
+// "0 info, 1 abs_info, ..."
+inline std::string tab_id_list(const TabEntry* e, int n) {
+  std::string s;
+  for (int k = 0; k < n; k++) s += (k ? ", " : "") + std::to_string(k) + " " + e[k].name;
+  return s;
+}
+inline std::string index_rule(const std::string& row, int index, const TabEntry& e) {
+  if (index >= 0 && index < e.width) return "";
+  return row + ": index " + std::to_string(index) + " out of range: " + e.name + " has " + std::to_string(e.width) + " entries";
+}
+
+// One CSR row-address array and the items it addresses.
+struct RowAdr {
+  const char* name;     // of the array in the messages
+  const int32_t* adr;   // [S + 1]
+  const char* noun;     // of its items in the messages
+  int cap;              // most items a row may hold
+  bool arrays;          // the item arrays are all there
+};
+// the address arrays as a whole: all there, each beginning at 0
+template <size_t NR>
+inline std::string row_heads(const std::string& fn, const RowAdr (&rows)[NR]) {
+  std::string names;
+  bool zero = true;
+  for (const RowAdr& r : rows) {
+    if (!r.adr) return fn + ": null argument";
+    zero = zero && r.adr[0] == 0;
+    names += (names.empty() ? "" : " and ") + std::string(r.name) + "[0]";
+  }
+  return zero ? "" : fn + ": " + names + " must be 0";
+}
+// row s of them (who: "<function>: scenario <s>"): non-decreasing, within the cap, and no items without their arrays
+template <size_t NR>
+inline std::string row_rule(const std::string& who, const RowAdr (&rows)[NR], int s) {
+  for (const RowAdr& r : rows)
+    if (r.adr[s + 1] < r.adr[s]) return who + ": row addresses must not decrease";
+  for (const RowAdr& r : rows) {
+    const long long ni = (long long)r.adr[s + 1] - r.adr[s];
+    if (ni > r.cap) return who + ": " + std::to_string(ni) + " " + r.noun + ", at most " + std::to_string(r.cap);
+  }
+  for (const RowAdr& r : rows)
+    if (r.adr[s + 1] > r.adr[s] && !r.arrays) return who + ": null table array";
+  return "";
+}
+
+// a window [t0, t1) of episode steps
+inline std::string window_rule(const std::string& row, int t0, int t1) {
+  if (t0 < 0 || t0 >= SCN_MAX_TIME || t1 < 0 || t1 > SCN_MAX_TIME) return row + ": times outside [0, 2^30)";
+  if (t1 <= t0) return row + ": t1 " + std::to_string(t1) + " is not after t0 " + std::to_string(t0);
+  return "";
+}
+
+// the signals of checks and curves (checks_signal, cosim_checks.h)
+inline std::string signal_rule(const std::string& row, const TableDims& d, int signal, int index) {
+  const int ncmd = d.command_dim < 3 ? d.command_dim : 3;
+  const TabEntry sig[CHK_NSIGNAL] = {{"info", d.info_dim, 0}, {"abs_info", d.info_dim, 0}, {"tracking_error", ncmd, 0}, {"torque_max", 1, 0},
+                                     {"up", d.nq >= 7 ? 1 : 0, 0}, {"qpos", d.nq, 0}, {"qvel", d.nv, 0}, {"abs_qvel", d.nv, 0}};
+  if (signal < 0 || signal >= CHK_NSIGNAL) return row + ": unknown signal " + std::to_string(signal) + " (" + tab_id_list(sig, CHK_NSIGNAL) + ")";
+  return index_rule(row, index, sig[signal]);
+}
+
+// the fields of a parameter window; *word: the word of the parameter record that field + index name
+inline std::string field_rule(const std::string& row, const TableDims& d, int field, int index, int32_t* word) {
+  const TabEntry fld[4] = {{"kp", d.nu, d.p_kp}, {"kd", d.nu, d.p_kd}, {"geom_friction", d.ngeom, d.p_gmu}, {"dof_frictionloss", d.nv, d.p_floss}};
+  if (field >= SCNPAR_BODY_MASS && field <= SCNPAR_MEANINERTIA)
+    return row + ": field " + std::to_string(field) + " (body_mass, body_invweight0, dof_invweight0, meaninertia) is refused: the mass "
+           "fields are consistent only as a set computed on the host in fp64; a payload change in mid-episode is out of scope";
+  if (field < 0 || field >= 4) return row + ": unknown field " + std::to_string(field) + " (" + tab_id_list(fld, 4) + ")";
+  *word = fld[field].off + index;
+  return index_rule(row, index, fld[field]);
+}
+
+// ---- the packer: the 4-byte arrays of a table, one behind the other in one allocation
+class WordPacker {
+ public:
+  // the next array of the image: n words from src; patch() will point *slot at them
+  template <class T>
+  void add(const T** slot, const T* src, size_t n) {
+    static_assert(sizeof(T) == 4, "arrays of 4-byte words");
+    arr_.push_back({slot, img_.size(), n});
+    img_.resize(img_.size() + n, 0);
+    if (n > 0) memcpy(&img_[arr_.back().off], src, n * 4);
+  }
+  const int32_t* data() const { return img_.data(); }
+  size_t words() const { return img_.size(); }
+  size_t bytes() const { return img_.size() * 4; }
+  // the table's pointers, once the address the image lies at (or will be copied to) is known
+  void patch(const void* base) const {
+    for (const Arr& a : arr_) {
+      const int32_t* p = static_cast<const int32_t*>(base) + a.off;
+      memcpy(a.slot, &p, sizeof p);
+    }
+  }
+  // whether the array behind `slot` holds the words it holds in `old`, an image of the same arrays with the same sizes
+  bool same(const void* slot, const int32_t* old) const {
+    for (const Arr& a : arr_)
+      if (a.slot == slot) return a.n == 0 || memcmp(&img_[a.off], old + a.off, a.n * 4) == 0;
+    return false;
+  }
+
+ private:
+  struct Arr { void* slot; size_t off, n; };
+  std::vector<Arr> arr_;
+  std::vector<int32_t> img_;
+};
+
+#define TAB_TRY(expr) do { v.err = (expr); if (!v.err.empty()) return v; } while (0)
+
+// ---- cosim_scenario_set.  Image: key_adr | push_adr | key_t | push_t | key_cmd | push_v
+struct ScnRaw {
+  int n_scn;   // 1 .. SCN_MAX_ROWS (the setter has checked)
+  const int32_t *key_adr, *key_t; const float* key_cmd;
+  const int32_t *push_adr, *push_t; const float* push_v;
+};
+struct ScnShape { std::string err; int nkey = 0, npush = 0; };
+
+inline ScnShape validate_scenario(const TableDims& d, const ScnRaw& r) {
+  const std::string fn = "cosim_scenario_set";
+  const int cd = d.command_dim;
+  ScnShape v;
+  const RowAdr rows[2] = {{"key_adr", r.key_adr, "keyframes", SCN_MAX_ITEMS, r.key_t && (cd == 0 || r.key_cmd)},
+                          {"push_adr", r.push_adr, "push windows", SCN_MAX_ITEMS, r.push_t && r.push_v}};
+  TAB_TRY(row_heads(fn, rows));
+  for (int s = 0; s < r.n_scn; s++) {
+    const std::string who = fn + ": scenario " + std::to_string(s);
+    TAB_TRY(row_rule(who, rows, s));
+    for (int k = r.key_adr[s]; k < r.key_adr[s + 1]; k++) {
+      const std::string row = who + ", keyframe " + std::to_string(k - r.key_adr[s]);
+      const int t = r.key_t[k];
+      if (t < 0 || t >= SCN_MAX_TIME) TAB_TRY(row + ": time " + std::to_string(t) + " outside [0, 2^30)");
+      if (k > r.key_adr[s] && t <= r.key_t[k - 1])
+        TAB_TRY(row + ": time " + std::to_string(t) + " does not increase (previous " + std::to_string(r.key_t[k - 1]) + ")");
+      for (int c = 0; c < cd; c++)
+        if (!std::isfinite(r.key_cmd[(size_t)k * cd + c])) TAB_TRY(row + ": command " + std::to_string(c) + " is not finite");
+    }
+    for (int p = r.push_adr[s]; p < r.push_adr[s + 1]; p++) {
+      const std::string row = who + ", push window " + std::to_string(p - r.push_adr[s]);
+      TAB_TRY(window_rule(row, r.push_t[2 * p], r.push_t[2 * p + 1]));
+      for (int c = 0; c < 3; c++)
+        if (!std::isfinite(r.push_v[3 * (size_t)p + c])) TAB_TRY(row + ": velocity " + std::to_string(c) + " is not finite");
+    }
+  }
+  v.nkey = r.key_adr[r.n_scn]; v.npush = r.push_adr[r.n_scn];
+  return v;
+}
+
+inline void pack_scenario(WordPacker& pk, ScnTable& tab, int cd, const ScnRaw& r, const ScnShape& v) {
+  const size_t S1 = (size_t)r.n_scn + 1, nk = (size_t)v.nkey, np = (size_t)v.npush;
+  pk.add(&tab.key_adr, r.key_adr, S1); pk.add(&tab.push_adr, r.push_adr, S1); pk.add(&tab.key_t, r.key_t, nk); pk.add(&tab.push_t, r.push_t, 2 * np);
+  pk.add(&tab.key_cmd, r.key_cmd, nk * cd); pk.add(&tab.push_v, r.push_v, 3 * np);
+  tab.n_scn = r.n_scn; tab.cd = cd;
+}
+
+// ---- cosim_scenario_params_set.  Image: adr | t | word | op | value
+struct ParRaw {
+  int n_scn;   // that of the scenario table that is set
+  const int32_t *adr, *t, *field, *index, *op; const float* value;
+};
+struct ParShape { std::string err; int n = 0; std::vector<int32_t> word; };
+
+inline ParShape validate_params(const TableDims& d, const ParRaw& r) {
+  const std::string fn = "cosim_scenario_params_set";
+  ParShape v;
+  const RowAdr rows[1] = {{"adr", r.adr, "parameter items", SCNPAR_MAX_ITEMS, r.t && r.field && r.index && r.op && r.value}};
+  TAB_TRY(row_heads(fn, rows));
+  for (int s = 0; s < r.n_scn; s++) {
+    const std::string who = fn + ": scenario " + std::to_string(s);
+    TAB_TRY(row_rule(who, rows, s));
+    for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
+      const std::string row = who + ", parameter item " + std::to_string(i - r.adr[s]);
+      int32_t word = 0;
+      TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
+      TAB_TRY(field_rule(row, d, r.field[i], r.index[i], &word));
+      if (r.op[i] != SCNPAR_SCALE && r.op[i] != SCNPAR_SET) TAB_TRY(row + ": unknown op " + std::to_string(r.op[i]) + " (0 scale, 1 set)");
+      if (!std::isfinite(r.value[i])) TAB_TRY(row + ": value is not finite");
+      v.word.push_back(word);
+    }
+  }
+  v.n = r.adr[r.n_scn];
+  if (v.n == 0) TAB_TRY(fn + ": the table holds no parameter item (n_scn = 0 clears the windows)");
+  return v;
+}
+
+inline void pack_params(WordPacker& pk, ScnParTable& tab, const ParRaw& r, const ParShape& v) {
+  const size_t n = (size_t)v.n;
+  pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.t, r.t, 2 * n); pk.add(&tab.word, v.word.data(), n); pk.add(&tab.op, r.op, n);
+  pk.add(&tab.value, r.value, n);
+  tab.n_scn = r.n_scn; tab.n_items = v.n;
+}
+
+// ---- cosim_scenario_checks_set.  Image: adr | t | signal | index | mode | cmp | bound
+struct ChkRaw {
+  int n_scn;   // that of the scenario table that is set
+  const int32_t *adr, *t, *signal, *index, *mode, *cmp; const float* bound;
+  int slots;
+};
+struct ChkShape { std::string err; int n = 0, I = 0; };   // I: the largest row, rounded up to even
+
+inline ChkShape validate_checks(const TableDims& d, const ChkRaw& r) {
+  const std::string fn = "cosim_scenario_checks_set";
+  ChkShape v;
+  if (r.slots < 1 || r.slots > CHK_MAX_SLOTS) TAB_TRY(fn + ": slots " + std::to_string(r.slots) + " outside 1..64");
+  const RowAdr rows[1] = {{"adr", r.adr, "check items", CHK_MAX_ITEMS, r.t && r.signal && r.index && r.mode && r.cmp && r.bound}};
+  TAB_TRY(row_heads(fn, rows));
+  int most = 0;
+  for (int s = 0; s < r.n_scn; s++) {
+    const std::string who = fn + ": scenario " + std::to_string(s);
+    TAB_TRY(row_rule(who, rows, s));
+    if (r.adr[s + 1] - r.adr[s] > most) most = r.adr[s + 1] - r.adr[s];
+    for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
+      const std::string row = who + ", check item " + std::to_string(i - r.adr[s]);
+      TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
+      TAB_TRY(signal_rule(row, d, r.signal[i], r.index[i]));
+      if (r.mode[i] < 0 || r.mode[i] >= CHK_NMODE) TAB_TRY(row + ": unknown mode " + std::to_string(r.mode[i]) + " (0 always, 1 settle, 2 mean)");
+      if (r.cmp[i] != CHK_LT && r.cmp[i] != CHK_GT) TAB_TRY(row + ": unknown cmp " + std::to_string(r.cmp[i]) + " (0 <, 1 >)");
+      if (!std::isfinite(r.bound[i])) TAB_TRY(row + ": bound is not finite");
+    }
+  }
+  v.n = r.adr[r.n_scn];
+  if (v.n == 0) TAB_TRY(fn + ": the table holds no check item (n_scn = 0 clears the checks)");
+  v.I = (most + 1) & ~1;
+  return v;
+}
+
+inline void pack_checks(WordPacker& pk, ChkTable& tab, const ChkRaw& r, const ChkShape& v) {
+  const size_t n = (size_t)v.n;
+  pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.t, r.t, 2 * n); pk.add(&tab.signal, r.signal, n); pk.add(&tab.index, r.index, n);
+  pk.add(&tab.mode, r.mode, n); pk.add(&tab.cmp, r.cmp, n); pk.add(&tab.bound, r.bound, n);
+  tab.n_scn = r.n_scn; tab.n_items = v.n; tab.I = v.I;
+}
+
+// A table of the S, n and I of the one whose image `old` is may be written over it (the counters and the verdict records keep their
+// meaning) if every row holds as many items as before.
+inline bool checks_same_rows(const WordPacker& pk, const ChkTable& tab, const int32_t* old) { return pk.same(&tab.adr, old); }
+
+// ---- cosim_scenario_curves_set.  Image: adr | t | signal | index | bins | nt | soff | coff | cw | lo | hi | inv_w
+struct CurRaw {
+  int n_scn;   // that of the scenario table that is set
+  const int32_t *adr, *t, *signal, *index; const float *lo, *hi; const int32_t* bins;
+};
+struct CurShape {
+  std::string err;
+  int n = 0;
+  std::vector<int32_t> nt, soff, coff, cw;   // per item: T, first stage word, first cell word, cell words of one class
+  std::vector<float> inv_w;
+  size_t cells = 0, SW = 0;   // 32-bit words of all cells; stage words per env: the largest sum of T over a row
+};
+
+inline CurShape validate_curves(const TableDims& d, int n_envs, const CurRaw& r) {
+  const std::string fn = "cosim_scenario_curves_set";
+  CurShape v;
+  const RowAdr rows[1] = {{"adr", r.adr, "curve items", CUR_MAX_ITEMS, r.t && r.signal && r.index && r.lo && r.hi && r.bins}};
+  TAB_TRY(row_heads(fn, rows));
+  for (int s = 0; s < r.n_scn; s++) TAB_TRY(row_rule(fn + ": scenario " + std::to_string(s), rows, s));   // all rows first: n sizes the arrays below
+  v.n = r.adr[r.n_scn];
+  if (v.n == 0) TAB_TRY(fn + ": the table holds no curve item (n_scn = 0 clears the curves)");
+  v.nt.resize(v.n); v.soff.resize(v.n); v.coff.resize(v.n); v.cw.resize(v.n); v.inv_w.assign(v.n, 0.f);
+  for (int s = 0; s < r.n_scn; s++) {
+    size_t row_words = 0;
+    for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
+      const std::string row = fn + ": scenario " + std::to_string(s) + ", curve item " + std::to_string(i - r.adr[s]);
+      const int t0 = r.t[3 * i], t1 = r.t[3 * i + 1], every = r.t[3 * i + 2], B = r.bins[i];
+      TAB_TRY(window_rule(row, t0, t1));
+      if (every < 1) TAB_TRY(row + ": every " + std::to_string(every) + " is below 1");
+      const int T = curves_nt(t0, t1, every);
+      if (T > CUR_MAX_T) TAB_TRY(row + ": " + std::to_string(T) + " time bins, at most 1024");
+      if (B < 0 || B > CUR_MAX_BINS) TAB_TRY(row + ": bins " + std::to_string(B) + " outside 0..64");
+      if (!std::isfinite(r.lo[i]) || !std::isfinite(r.hi[i])) TAB_TRY(row + ": lo / hi is not finite");
+      if (B > 0 && !(r.hi[i] > r.lo[i])) TAB_TRY(row + ": hi is not above lo");
+      TAB_TRY(signal_rule(row, d, r.signal[i], r.index[i]));
+      v.nt[i] = T; v.soff[i] = (int32_t)row_words; v.cw[i] = curves_cell_words(T, B);
+      if (v.cells + 2 * (size_t)v.cw[i] > CUR_MAX_BYTES / 4) TAB_TRY(row + ": the cells would exceed 256 MiB (a design limit)");
+      v.coff[i] = (int32_t)v.cells;
+      v.cells += 2 * (size_t)v.cw[i];
+      row_words += (size_t)T;
+      if (B > 0) v.inv_w[i] = (float)((double)B / ((double)r.hi[i] - (double)r.lo[i]));
+    }
+    if (row_words > v.SW) v.SW = row_words;
+  }
+  if ((size_t)n_envs * v.SW > CUR_MAX_BYTES / 4)
+    TAB_TRY(fn + ": the stage, " + std::to_string((long long)v.SW) + " words for each of " + std::to_string(n_envs) + " envs, would exceed 256 MiB (a design limit)");
+  return v;
+}
+
+inline void pack_curves(WordPacker& pk, CurTable& tab, const CurRaw& r, const CurShape& v) {
+  const size_t n = (size_t)v.n;
+  pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.t, r.t, 3 * n); pk.add(&tab.signal, r.signal, n); pk.add(&tab.index, r.index, n);
+  pk.add(&tab.bins, r.bins, n); pk.add(&tab.nt, v.nt.data(), n); pk.add(&tab.soff, v.soff.data(), n); pk.add(&tab.coff, v.coff.data(), n);
+  pk.add(&tab.cw, v.cw.data(), n); pk.add(&tab.lo, r.lo, n); pk.add(&tab.hi, r.hi, n); pk.add(&tab.inv_w, v.inv_w.data(), n);
+  tab.n_scn = r.n_scn; tab.n_items = v.n; tab.SW = (int)v.SW;
+}
+
+// A table of the S, n, SW and cell words of the one whose image `old` is may be written over it (the stage and the cells keep their
+// layout) if every row holds as many items as before and every item has the T and B it had.
+inline bool curves_same_sizes(const WordPacker& pk, const CurTable& tab, const int32_t* old) {
+  return pk.same(&tab.adr, old) && pk.same(&tab.bins, old) && pk.same(&tab.nt, old) && pk.same(&tab.soff, old) && pk.same(&tab.coff, old) &&
+         pk.same(&tab.cw, old);
+}
+
+#undef TAB_TRY
+
+}  // namespace cosim
