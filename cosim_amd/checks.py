@@ -152,6 +152,20 @@ class Verdicts:
             out[int(r)] = {**self.with_shares(self._shares(sel)), "checks": self._by_name(sel)}
         return out
 
+    def by_policy(self, table, scenario: bool = False) -> dict:
+        """``summary()`` per policy of a ``policy.PolicyTable`` (or of an int array with the policy of each local env), keyed by the
+        policy's name, with ``scenario`` by ``(name, scenario row)``: as ``EpisodeLedger.by_policy``."""
+        from .ledger import policy_of_records
+        pol, names = policy_of_records(table, self.env, self.env_id0)
+        m = self.ended()
+        out = {}
+        for k in np.unique(pol[m]):
+            mk = m & (pol == k)
+            for s in (np.unique(self.scenario[mk]) if scenario else [None]):
+                sel = mk if s is None else mk & (self.scenario == s)
+                out[names[int(k)] if s is None else (names[int(k)], int(s))] = {**self.with_shares(self._shares(sel)), "checks": self._by_name(sel)}
+        return out
+
     def join(self, ledger) -> np.ndarray:
         """Per verdict row, the row of ``ledger`` (an ``EpisodeLedger``, or anything with ``env`` and ``episode`` columns such as
         ``FailureTraces``) with the same (env, episode), or -1: int64 ``[R]``.  The ordinals agree when both were set together."""

@@ -20,6 +20,9 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     random:   {sensor_noise: low, action_delay_prob: 0.05, ...}        # overrides of the GUI defaults (config.make_config)
     observation: {stack_size: 3, ...}                                   # likewise
     policy:   {kind: sinusoid | random-mlp | onnx, onnx_file: actor.onnx, use_lstm: false, h_in_dim: 256, c_in_dim: 256}
+    policy:   {onnx_files: [a.onnx, b.onnx], assign: interleave | cross, names: [base, tuned]}   # a policy table (policy.PolicyTable): every env
+                                                                       # driven by one of the files; same as --policy a.onnx b.onnx
+                                                                       # --policy-assign --policy-names; the report gets episodes.by_policy
     steps:    1000
     commands: [[0, 0.5, 0, 0, 0], [200, 1.0, 0, 0.3, 0]]              # from control step t on: user_command = c0 .. c3
     pushes:   [[300, 310, 0.5, 0, 0]]                                   # held for steps t0 <= k < t1: event("push", [vx, vy, vz])
@@ -57,7 +60,11 @@ def main(argv=None) -> int:
     ap.add_argument("--terrain", default=None)
     ap.add_argument("--num-envs", type=int, default=None, help="total over all ranks")
     ap.add_argument("--steps", type=int, default=None, help="control steps (50 Hz)")
-    ap.add_argument("--policy", default=None, help="sinusoid | random-mlp | <file.onnx>")
+    ap.add_argument("--policy", default=None, nargs="+", metavar="POLICY",
+                    help="sinusoid | random-mlp | <file.onnx>, or several ONNX actor files: a policy table, every env driven by one of them")
+    ap.add_argument("--policy-assign", choices=["interleave", "cross"], default=None,
+                    help="several --policy files: env g runs policy g mod K (interleave, the default) or (g // S) mod K with S scenarios (cross)")
+    ap.add_argument("--policy-names", nargs="+", default=None, metavar="NAME", help="several --policy files: their names in the report (default: the file stems)")
     ap.add_argument("--lstm", action="store_true", help="the ONNX file is an LSTM policy with h_in / c_in inputs")
     ap.add_argument("--hidden-dim", type=int, default=256, help="h_in_dim = c_in_dim of an LSTM policy")
     ap.add_argument("--command", type=float, nargs="*", default=None)
@@ -142,7 +149,29 @@ def main(argv=None) -> int:
     args.seed = int(pick(args.seed, s_eng.get("seed"), 1234))
     args.steps = int(pick(args.steps, sess.get("steps"), 500))
     kind = s_pol.get("kind")
+    unknown = set(s_pol) - {"kind", "onnx_file", "onnx_files", "assign", "names", "use_lstm", "h_in_dim", "c_in_dim"}
+    if unknown:
+        ap.error(f"--config: unknown keys policy.{sorted(unknown)}")
+    # one policy, or several ONNX files: a policy table (policy.PolicyTable)
+    policy_files = list(args.policy) if args.policy is not None else list(s_pol.get("onnx_files") or [])
+    if len(policy_files) == 1:
+        args.policy, policy_files = policy_files[0], []
+    elif policy_files:
+        args.policy = None
     args.policy = pick(args.policy, s_pol.get("onnx_file") if kind == "onnx" else kind, "sinusoid")
+    policy_assign = pick(args.policy_assign, s_pol.get("assign"), "interleave")
+    policy_names = args.policy_names if args.policy_names is not None else s_pol.get("names")
+    if policy_files:
+        if args.lstm or s_pol.get("use_lstm", False):
+            ap.error("--policy with several files: a policy table takes MLP actors only (no --lstm)")
+        if any(p in ("sinusoid", "random-mlp") for p in policy_files):
+            ap.error("--policy with several values: ONNX files only (sinusoid / random-mlp stand alone)")
+        if policy_assign not in ("interleave", "cross"):
+            ap.error("policy.assign: interleave or cross")
+        if policy_names is not None and len(policy_names) != len(policy_files):
+            ap.error("--policy-names: one name per --policy file")
+    elif args.policy_assign is not None or args.policy_names is not None:
+        ap.error("--policy-assign / --policy-names need several --policy files")
     args.lstm = bool(args.lstm or s_pol.get("use_lstm", False))
     if s_pol.get("h_in_dim") is not None:
         args.hidden_dim = int(s_pol["h_in_dim"])
@@ -268,7 +297,16 @@ def main(argv=None) -> int:
         ap.error("--check-slots: the scenario table holds no checks")
     if args.curves and not env.curves_armed:
         ap.error("--curves: the scenario table holds no curves")
-    if args.policy == "sinusoid":
+    if policy_files:
+        n_scn = len(env.scenario_table) if env.scenario_table is not None else 0
+        if policy_assign == "cross" and n_scn < 1:
+            ap.error("--policy-assign cross needs --scenarios")
+        try:
+            policy = build_policy({"policy": {"use_lstm": False, "onnx_files": policy_files, "assign": policy_assign}}, num_envs=env.num_envs,
+                                  device=env.device, env_id0=lo, scenarios=n_scn, ranges=env.range_list, names=policy_names)
+        except ValueError as e:
+            ap.error(str(e))
+    elif args.policy == "sinusoid":
         policy = SinusoidPolicy(env.num_envs, env.action_dim, env.device, env_id0=lo, seed=args.seed)
     else:
         path = args.policy
@@ -282,7 +320,7 @@ def main(argv=None) -> int:
                  "graph would replay one frozen action")
     if args.graph and (pushes or len(commands) > 1 or args.trace_env >= 0):
         ap.error("--graph replays one captured control step: pushes, command changes and --trace-env need the eager loop")
-    if args.pipelined and (not hasattr(policy, "get_action_into") or args.graph or args.trace_env >= 0):
+    if args.pipelined and (not (hasattr(policy, "get_action_into") or hasattr(policy, "get_action_range")) or args.graph or args.trace_env >= 0):
         ap.error("--pipelined needs an ONNX MLP policy (random-mlp or a file) and excludes --graph / --trace-env")
     rep = FleetReporter(env, trace_env=args.trace_env if args.trace_env >= 0 else None, percentiles=args.percentiles)
     run = Runner(env, policy, reporter=rep)
@@ -365,6 +403,8 @@ def main(argv=None) -> int:
                           **({"failure_traces": traces.summary()} if traces is not None else {}),
                           **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
                              if "by_scenario" in out.get("episodes", {}) else {}),
+                          **({"by_policy": {k: {q: v.get("fleet", v)[q] for q in ("episodes", "terminated_share")} for k, v in out["episodes"]["by_policy"].items()}}
+                             if "by_policy" in out.get("episodes", {}) else {}),
                           **({"param_windows": sum(len(w) for w in env.scenario_table.param_windows)}   # as listed in the table
                              if env.scenario_table is not None and env.scenario_table.has_params else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}

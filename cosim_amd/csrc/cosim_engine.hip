@@ -865,6 +865,16 @@ static const char* observers_info_msg(const cosim_engine* e) {
   return e->led_slots > 0 ? LEDGER_INFO_MSG : e->ft_frames > 0 ? FTRACE_INFO_MSG : e->chk.n_scn > 0 ? CHECKS_INFO_MSG : e->cur.n_scn > 0 ? CURVES_INFO_MSG : nullptr;
 }
 
+// what cosim_policy_table_create hands out: the device copies of a checked table and the launch shape of every range
+struct cosim_policy_table {
+  int n = 0, device = 0, ld = 0, n_tiles = 0;
+  float* d_image = nullptr;
+  PolDesc* d_desc = nullptr;
+  int32_t* d_rows = nullptr;
+  PolTile* d_tiles = nullptr;
+  std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count)
+};
+
 extern "C" {
 
 // Fused actor MLP (cosim_mlp.hip): out = clip(act_L(... act_1(x W_1^T + b_1) ...)).  All pointers are device pointers; dims has
@@ -897,6 +907,70 @@ int cosim_mlp_forward(const float* x_dev, int n, int n_layers, const int* dims, 
   }
   hipLaunchKernelGGL(mlp_forward_kernel, dim3((n + 31) / 32), dim3(256), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// Policy table (cosim_poltab.h, mlp_grouped_kernel): K actors over one fleet, one launch per evaluation.  create checks and packs the
+// host arrays, builds the tile list and uploads everything once; forward only launches.
+int cosim_policy_table_create(int n_policies, const int* n_layers, const int* dims, const int* act, const float* act_alpha,
+                              const float* const* w_host, const float* const* b_host, int n, const int* policy_of_row, int n_ranges,
+                              const int* ranges, cosim_policy_table** out) {
+  if (!out) return fail(COSIM_EINVAL, "cosim_policy_table_create: null argument");
+  *out = nullptr;
+  const PolRaw raw = {n_policies, n_layers, dims, act, act_alpha, w_host, b_host, n, policy_of_row, n_ranges, ranges};
+  const PolShape shape = validate_policy_table(raw);
+  if (!shape.err.empty()) return fail(COSIM_EINVAL, shape.err);
+  const PolImage im = pack_policy_image(raw);
+  const PolTiles tl = build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges);
+  cosim_policy_table* p = new cosim_policy_table;
+  p->n = n; p->ld = shape.maxd | 1; p->n_tiles = (int)tl.tiles.size(); p->tile_span = tl.tile_span;
+  const size_t lds = (size_t)2 * 32 * p->ld * sizeof(float);
+  static size_t lds_allowed[64] = {0};   // per device, as cosim_mlp_forward
+  auto upload = [&]() -> int {
+    HIP_TRY(hipGetDevice(&p->device));
+    if (p->device < 0 || p->device >= 64) return fail(COSIM_EINVAL, "cosim_policy_table_create: device index out of range");
+    const size_t b_img = im.words.size() * 4, b_desc = im.desc.size() * sizeof(PolDesc), b_rows = tl.rows.size() * 4, b_tiles = tl.tiles.size() * sizeof(PolTile);
+    HIP_TRY(hipMalloc(&p->d_image, b_img)); HIP_TRY(hipMalloc(&p->d_desc, b_desc)); HIP_TRY(hipMalloc(&p->d_rows, b_rows)); HIP_TRY(hipMalloc(&p->d_tiles, b_tiles));
+    HIP_TRY(hipMemcpy(p->d_image, im.words.data(), b_img, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_desc, im.desc.data(), b_desc, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_rows, tl.rows.data(), b_rows, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_tiles, tl.tiles.data(), b_tiles, hipMemcpyHostToDevice));
+    if (lds > lds_allowed[p->device]) {
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      lds_allowed[p->device] = lds;
+    }
+    return COSIM_OK;
+  };
+  const int rc = upload();
+  if (rc) { cosim_policy_table_destroy(p); return rc; }
+  *out = p;
+  return COSIM_OK;
+}
+
+// range: an index into the ranges given to create, or -1 for all of them.  No allocation, no host read of device memory and no
+// synchronisation: the launch can be captured in a graph.
+int cosim_policy_table_forward(cosim_policy_table* p, const float* x_dev, float* out_dev, int range, float clip, void* stream) {
+  if (!p || !x_dev || !out_dev) return fail(COSIM_EINVAL, "cosim_policy_table_forward: null argument");
+  const int n_ranges = (int)p->tile_span.size() / 2;
+  if (range < -1 || range >= n_ranges)
+    return fail(COSIM_EINVAL, "cosim_policy_table_forward: range " + std::to_string(range) + " outside -1.." + std::to_string(n_ranges - 1));
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != p->device)
+    return fail(COSIM_EINVAL, "cosim_policy_table_forward: the table lives on device " + std::to_string(p->device) + ", the current device is " + std::to_string(dev));
+  PolTabArgs a;
+  a.x = x_dev; a.out = out_dev; a.image = p->d_image; a.desc = p->d_desc; a.rows = p->d_rows; a.tiles = p->d_tiles;
+  a.tile_first = range < 0 ? 0 : p->tile_span[2 * range]; a.ld = p->ld; a.clip = clip;
+  const int tile_count = range < 0 ? p->n_tiles : p->tile_span[2 * range + 1];
+  hipLaunchKernelGGL(mlp_grouped_kernel, dim3(tile_count), dim3(256), (size_t)2 * 32 * p->ld * sizeof(float), (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+int cosim_policy_table_destroy(cosim_policy_table* p) {
+  if (!p) return COSIM_OK;
+  (void)hipFree(p->d_image); (void)hipFree(p->d_desc); (void)hipFree(p->d_rows); (void)hipFree(p->d_tiles);
+  delete p;
   return COSIM_OK;
 }
 

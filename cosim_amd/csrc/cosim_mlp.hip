@@ -11,6 +11,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cosim_poltab.h"
+
 namespace cosim {
 
 constexpr int MLP_MAXL = 6;      // layers
@@ -42,28 +44,29 @@ __device__ __forceinline__ float mlp_act(float x, int kind, float alpha) {
   }
 }
 
-__global__ __launch_bounds__(256) void mlp_forward_kernel(MlpArgs A) {
+// One layer of the chain as the layer loop reads it.
+struct MlpLayer {
+  const float *W, *Bv;   // [O, I] row-major; [O] or null
+  int I, O, act;
+  float alpha;
+};
+
+// The layer loop of one 32-env tile whose input rows stand in tile 0 of `lds` ([2][32][ld]; the caller has synchronised).  Both
+// kernels below run it.  layer_of(L): layer L; out_row(r): the row of `out` that tile row r is written to, < 0 for none.  An output
+// element is a chain of MFMA steps over k whose operands are the env's own inputs and the weights: which tile row the env sits in,
+// and what the other rows hold, does not enter it.
+template <class LayerOf, class RowOf>
+__device__ __forceinline__ void mlp_layers(float* lds, int ld, int nl, float clip, float* out, LayerOf layer_of, RowOf out_row) {
   typedef float f32x16 __attribute__((ext_vector_type(16)));
-  extern __shared__ float mlp_lds[];   // [2][32][ld]
-  const int ld = A.ld;
-  auto tile = [&](int which, int r, int c) -> float& { return mlp_lds[(which * 32 + r) * ld + c]; };
+  auto tile = [&](int which, int r, int c) -> float& { return lds[(which * 32 + r) * ld + c]; };
   const int t = threadIdx.x, l = t & 63, wave = t >> 6;
-  const int n0 = blockIdx.x * 32;
-  // the input tile, coalesced
-  {
-    const int I = A.dims[0];
-    for (int e = t; e < 32 * I; e += 256) {
-      const int r = e / I, c = e - r * I;
-      tile(0, r, c) = (n0 + r < A.n) ? A.x[(size_t)(n0 + r) * I + c] : 0.f;
-    }
-  }
-  __syncthreads();
   int cur = 0;
-  for (int L = 0; L < A.nl; L++) {
-    const int I = A.dims[L], O = A.dims[L + 1];
-    const float* W = A.w[L];
-    const float* Bv = A.b[L];
-    const bool last = L == A.nl - 1;
+  for (int L = 0; L < nl; L++) {
+    const MlpLayer ly = layer_of(L);
+    const int I = ly.I, O = ly.O;
+    const float* W = ly.W;
+    const float* Bv = ly.Bv;
+    const bool last = L == nl - 1;
     const int row_a = l & 31, kk = l >> 5;
     for (int ti = wave; ti * 32 < O; ti += 4) {
       const int o0 = ti * 32, col = o0 + (l & 31);
@@ -90,10 +93,11 @@ __global__ __launch_bounds__(256) void mlp_forward_kernel(MlpArgs A) {
 #pragma unroll
       for (int v = 0; v < 16; v++) {
         const int row = (v & 3) + 8 * (v >> 2) + 4 * (l >> 5);
-        float y = mlp_act(acc[v], A.act[L], A.act_alpha[L]);
+        float y = mlp_act(acc[v], ly.act, ly.alpha);
         if (last) {
-          if (A.clip > 0.f) y = y < -A.clip ? -A.clip : (y > A.clip ? A.clip : y);
-          if (col < O && n0 + row < A.n) A.out[(size_t)(n0 + row) * O + col] = y;
+          if (clip > 0.f) y = y < -clip ? -clip : (y > clip ? clip : y);
+          const long long orow = out_row(row);
+          if (col < O && orow >= 0) out[(size_t)orow * O + col] = y;
         } else if (col < O)
           tile(cur ^ 1, row, col) = y;
       }
@@ -101,6 +105,67 @@ __global__ __launch_bounds__(256) void mlp_forward_kernel(MlpArgs A) {
     __syncthreads();
     cur ^= 1;
   }
+}
+
+__global__ __launch_bounds__(256) void mlp_forward_kernel(MlpArgs A) {
+  extern __shared__ float mlp_lds[];   // [2][32][ld]
+  const int ld = A.ld;
+  const int t = threadIdx.x;
+  const int n0 = blockIdx.x * 32;
+  // the input tile, coalesced
+  {
+    const int I = A.dims[0];
+    for (int e = t; e < 32 * I; e += 256) {
+      const int r = e / I, c = e - r * I;
+      mlp_lds[r * ld + c] = (n0 + r < A.n) ? A.x[(size_t)(n0 + r) * I + c] : 0.f;
+    }
+  }
+  __syncthreads();
+  mlp_layers(mlp_lds, ld, A.nl, A.clip, A.out,
+             [&](int L) { return MlpLayer{A.w[L], A.b[L], A.dims[L], A.dims[L + 1], A.act[L], A.act_alpha[L]}; },
+             [&](int row) -> long long { return n0 + row < A.n ? (long long)(n0 + row) : -1; });
+}
+
+// K policies over one fleet in one launch (cosim_policy_table_forward; the table is made and checked by cosim_poltab.h): a workgroup
+// takes one TILE -- up to 32 envs of one policy, rows[start .. start + count) -- gathers their input rows into the LDS tile (zeros
+// behind `count`), runs the layer loop above with its policy's weights out of the table's one image, and scatters the output rows.
+// A launch covers tiles tile_first .. tile_first + gridDim.x, so one range of envs can be evaluated alone on a stream of its own.
+struct PolTabArgs {
+  const float* x;          // [n, in_dim]
+  float* out;              // [n, out_dim]
+  const float* image;      // every policy's weights and biases
+  const PolDesc* desc;     // [K]
+  const int32_t* rows;     // [n] env-local rows grouped by (range, policy)
+  const PolTile* tiles;
+  int tile_first, ld;      // ld: (widest layer of any policy) | 1
+  float clip;              // as MlpArgs::clip
+};
+
+__global__ __launch_bounds__(256) void mlp_grouped_kernel(PolTabArgs A) {
+  extern __shared__ float mlp_lds[];   // [2][32][ld]
+  __shared__ int tile_row[32];         // the env each tile row holds, -1 behind the tile's count
+  const int ld = A.ld;
+  const int t = threadIdx.x;
+  // the tile and its policy: indices out of blockIdx alone, so wave-uniform (scalar loads)
+  const PolTile T = A.tiles[A.tile_first + blockIdx.x];
+  const PolDesc* D = A.desc + T.policy;
+  if (t < 32) tile_row[t] = t < T.count ? A.rows[T.start + t] : -1;
+  __syncthreads();
+  // the input tile: a row is dims[0] contiguous floats, consecutive lanes take consecutive words of it
+  {
+    const int I = D->dims[0];
+    for (int e = t; e < 32 * I; e += 256) {
+      const int r = e / I, c = e - r * I, src = tile_row[r];
+      mlp_lds[r * ld + c] = src >= 0 ? A.x[(size_t)src * I + c] : 0.f;
+    }
+  }
+  __syncthreads();
+  mlp_layers(mlp_lds, ld, D->nl, A.clip, A.out,
+             [&](int L) {
+               const int bo = D->boff[L];
+               return MlpLayer{A.image + D->woff[L], bo >= 0 ? A.image + bo : nullptr, D->dims[L], D->dims[L + 1], D->act[L], D->alpha[L]};
+             },
+             [&](int row) -> long long { return tile_row[row]; });
 }
 
 // One LSTM cell step for N environments (the recurrent policy of core/policy.py:24-47: the ONNX LSTM node with sequence length 1,

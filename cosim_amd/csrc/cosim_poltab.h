@@ -1,0 +1,170 @@
+// cosim_poltab.h — what the host does with a policy table before it reaches the device (cosim_policy_table_create, include/cosim.h):
+// K actor MLPs over one fleet, every env assigned to one of them, evaluated by ONE launch of mlp_grouped_kernel (cosim_mlp.hip).  The
+// kernel trusts the row list, the tile list and the offsets it is given, so all of them are made and checked here: the descriptor
+// of a policy, the validator, the tile-list builder and the packer of the weight image.  Plain C++ with no HIP in it, in the manner of
+// cosim_tables.h: cosim_engine.hip and a host program (tests/poltab_host.cpp) both compile it.
+//
+// WordPacker (cosim_tables.h) is not used for the image: it lays arrays end to end and patches POINTERS, while a weight matrix has to
+// begin at a multiple of 4 words (the kernel's float4 path) and a descriptor holds word OFFSETS, -1 among them.
+#pragma once
+#include <stdint.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+namespace cosim {
+
+constexpr int POL_MAXK = 64;      // policies of a table
+constexpr int POL_MAXL = 6;       // = MLP_MAXL
+constexpr int POL_MAXD = 512;     // = MLP_MAXD
+constexpr int POL_TILE = 32;      // envs of a tile: the rows of one MFMA tile
+
+// One policy as the kernel reads it: 32 words.  woff / boff: word offsets of layer l's weights [dims[l+1], dims[l]] (row-major) and
+// bias [dims[l+1]] into the table's one weight image; boff -1: the layer has no bias.
+struct PolDesc {
+  int32_t nl;
+  int32_t dims[POL_MAXL + 1];
+  int32_t act[POL_MAXL];      // 0 none, 1 relu, 2 tanh, 3 elu, 4 sigmoid, 5 leaky relu
+  float alpha[POL_MAXL];
+  int32_t woff[POL_MAXL];
+  int32_t boff[POL_MAXL];
+};
+static_assert(sizeof(PolDesc) == 32 * 4, "PolDesc is 32 words");
+
+// rows[start .. start + count) are the env-local rows of one tile, all of policy `policy`
+struct PolTile { int32_t policy, start, count, pad; };
+
+// the caller's arrays (host memory)
+struct PolRaw {
+  int K;
+  const int32_t* nl;          // [K]
+  const int32_t* dims;        // [K][7]
+  const int32_t* act;         // [K][6]
+  const float* alpha;         // [K][6] or null (1 everywhere)
+  const float* const* w;      // [K][6] host pointers
+  const float* const* b;      // [K][6] host pointers, null entries (or a null array): no bias
+  int n;                      // envs
+  const int32_t* policy_of_row;   // [n]
+  int n_ranges;
+  const int32_t* ranges;      // [n_ranges][2]: (first, count), ascending, covering [0, n)
+};
+
+struct PolShape {
+  std::string err;
+  int maxd = 0;               // the widest layer of any policy
+};
+
+#define POL_TRY(expr) do { v.err = (expr); if (!v.err.empty()) return v; } while (0)
+
+inline PolShape validate_policy_table(const PolRaw& r) {
+  const std::string fn = "cosim_policy_table_create";
+  PolShape v;
+  if (r.K < 1 || r.K > POL_MAXK) POL_TRY(fn + ": " + std::to_string(r.K) + " policies, outside 1..64");
+  if (r.n <= 0) POL_TRY(fn + ": n " + std::to_string(r.n) + " is not positive");
+  if (!r.nl || !r.dims || !r.act || !r.w || !r.policy_of_row || !r.ranges) POL_TRY(fn + ": null argument");
+  for (int k = 0; k < r.K; k++) {
+    const std::string who = fn + ": policy " + std::to_string(k);
+    const int nl = r.nl[k];
+    if (nl < 1 || nl > POL_MAXL) POL_TRY(who + ": " + std::to_string(nl) + " layers, outside 1..6");
+    const int32_t* d = r.dims + (size_t)k * (POL_MAXL + 1);
+    for (int l = 0; l <= nl; l++) {
+      if (d[l] < 1 || d[l] > POL_MAXD) POL_TRY(who + ": width " + std::to_string(d[l]) + " of layer " + std::to_string(l) + " outside 1..512");
+      if (d[l] > v.maxd) v.maxd = d[l];
+    }
+    const int32_t* d0 = r.dims;
+    if (d[0] != d0[0])
+      POL_TRY(who + ": input width " + std::to_string(d[0]) + " differs from policy 0's " + std::to_string(d0[0]));
+    if (d[nl] != d0[r.nl[0]])
+      POL_TRY(who + ": output width " + std::to_string(d[nl]) + " differs from policy 0's " + std::to_string(d0[r.nl[0]]));
+    for (int l = 0; l < nl; l++) {
+      const int a = r.act[(size_t)k * POL_MAXL + l];
+      if (a < 0 || a > 5) POL_TRY(who + ", layer " + std::to_string(l) + ": unknown activation " + std::to_string(a) + " (0 none .. 5 leaky relu)");
+      if (!r.w[(size_t)k * POL_MAXL + l]) POL_TRY(who + ", layer " + std::to_string(l) + ": null weight");
+    }
+  }
+  for (int i = 0; i < r.n; i++)
+    if (r.policy_of_row[i] < 0 || r.policy_of_row[i] >= r.K)
+      POL_TRY(fn + ": row " + std::to_string(i) + " is assigned to policy " + std::to_string(r.policy_of_row[i]) + ", outside [0, " + std::to_string(r.K) + ")");
+  if (r.n_ranges < 1 || r.n_ranges > r.n) POL_TRY(fn + ": " + std::to_string(r.n_ranges) + " ranges, outside 1..n");
+  long long next = 0;
+  for (int i = 0; i < r.n_ranges; i++) {
+    const long long first = r.ranges[2 * i], count = r.ranges[2 * i + 1];
+    const std::string who = fn + ": range " + std::to_string(i) + " (" + std::to_string(first) + ", " + std::to_string(count) + ")";
+    if (count < 1) POL_TRY(who + " is empty");
+    if (first < next) POL_TRY(who + " overlaps the one before it");
+    if (first > next) POL_TRY(who + " leaves rows from " + std::to_string(next) + " uncovered");
+    next = first + count;
+    if (next > r.n) POL_TRY(who + " ends past n " + std::to_string(r.n));
+  }
+  if (next != r.n) POL_TRY(fn + ": the ranges leave rows from " + std::to_string(next) + " uncovered");
+  return v;
+}
+
+#undef POL_TRY
+
+// ---- the tile list.  Of a VALIDATED table: per range, per policy, that policy's rows of the range in ascending order, cut into tiles
+// of at most 32.  Every row is in exactly one tile, a tile has one policy and 1..32 rows, no tile crosses a range, and a range's tiles
+// are tile_span[2 i] .. + tile_span[2 i + 1] of the list.
+struct PolTiles {
+  std::vector<int32_t> rows;        // [n]
+  std::vector<PolTile> tiles;
+  std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count)
+};
+
+inline PolTiles build_policy_tiles(const int32_t* policy_of_row, int K, const int32_t* ranges, int n_ranges) {
+  PolTiles t;
+  for (int i = 0; i < n_ranges; i++) {
+    const int first = ranges[2 * i], count = ranges[2 * i + 1];
+    const int tile_first = (int)t.tiles.size();
+    for (int k = 0; k < K; k++) {
+      int open = 0;   // rows of the tile being filled
+      for (int r = first; r < first + count; r++) {
+        if (policy_of_row[r] != k) continue;
+        if (open == 0 || open == POL_TILE) {
+          t.tiles.push_back({k, (int32_t)t.rows.size(), 0, 0});
+          open = 0;
+        }
+        t.rows.push_back(r);
+        t.tiles.back().count = ++open;
+      }
+    }
+    t.tile_span.push_back(tile_first);
+    t.tile_span.push_back((int32_t)t.tiles.size() - tile_first);
+  }
+  return t;
+}
+
+// ---- the image: per policy, per layer the weights (begun at a multiple of 4 words, so the float4 reads of a layer whose input width
+// is a multiple of 4 are 16-byte aligned) and then the bias if there is one.  Of a VALIDATED table.
+struct PolImage {
+  std::vector<float> words;
+  std::vector<PolDesc> desc;   // [K]
+};
+
+inline PolImage pack_policy_image(const PolRaw& r) {
+  PolImage im;
+  im.desc.resize(r.K);
+  for (int k = 0; k < r.K; k++) {
+    PolDesc& d = im.desc[k];
+    memset(&d, 0, sizeof d);
+    d.nl = r.nl[k];
+    for (int l = 0; l <= POL_MAXL; l++) d.dims[l] = l <= d.nl ? r.dims[(size_t)k * (POL_MAXL + 1) + l] : 0;
+    for (int l = 0; l < POL_MAXL; l++) { d.woff[l] = -1; d.boff[l] = -1; d.alpha[l] = 1.f; }
+    for (int l = 0; l < d.nl; l++) {
+      const size_t q = (size_t)k * POL_MAXL + l, nw = (size_t)d.dims[l] * d.dims[l + 1], nb = (size_t)d.dims[l + 1];
+      d.act[l] = r.act[q];
+      if (r.alpha) d.alpha[l] = r.alpha[q];
+      im.words.resize((im.words.size() + 3) & ~(size_t)3, 0.f);
+      d.woff[l] = (int32_t)im.words.size();
+      im.words.insert(im.words.end(), r.w[q], r.w[q] + nw);
+      if (r.b && r.b[q]) {
+        d.boff[l] = (int32_t)im.words.size();
+        im.words.insert(im.words.end(), r.b[q], r.b[q] + nb);
+      }
+    }
+  }
+  return im;
+}
+
+}  // namespace cosim

@@ -123,21 +123,38 @@ class EpisodeLedger:
         (default: if any record has a fall flag) also the count and share a fall rule ended --, length
         quantiles (control steps) and the means over those episodes of the record means (non-finite records left out)."""
         m = self.ended()
-        rows, term, n = self.scenario[m], (self.flags[m] & TERMINATED) != 0, self.length[m].astype(np.float64)
-        fallen, with_fell = (self.flags[m] & FELL) != 0, self._with_fell(fell)
+        with_fell = self._with_fell(fell)
+        return {int(r): self._cell(m & (self.scenario == r), with_fell) for r in np.unique(self.scenario[m])}
+
+    def _cell(self, sel, with_fell: bool) -> dict:
+        """The columns of ``by_scenario()`` / ``by_policy()`` over the records under mask ``sel`` (at least one, all ended)."""
+        term, n, fallen = (self.flags[sel] & TERMINATED) != 0, self.length[sel].astype(np.float64), (self.flags[sel] & FELL) != 0
+        means = {}
+        for name in FLOAT_FIELDS:
+            v = getattr(self, name)[sel].astype(np.float64)
+            ok = np.isfinite(v)
+            means[name] = float(v[ok].mean()) if ok.any() else None
+        return {"episodes": int(sel.sum()), "terminated": int(term.sum()), "terminated_share": float(term.mean()),
+                **({"fell": int(fallen.sum()), "fell_share": float(fallen.mean())} if with_fell else {}),
+                "length": {"mean": float(n.mean()), "min": int(n.min()), "p50": float(np.quantile(n, 0.5)), "max": int(n.max())},
+                "means": means}
+
+    def by_policy(self, table, scenario: bool = False, fell: Optional[bool] = None) -> dict:
+        """Per policy of a ``policy.PolicyTable`` (or of an int array: the policy of each LOCAL env, named "0", "1", ...): the columns
+        of ``by_scenario()`` over the ended episodes of the envs that policy drives, keyed by the policy's name -- with ``scenario``
+        by ``(name, scenario row)``, the checkpoint x scenario matrix.  An env's policy is looked up from its global id; a policy
+        (or a cell) without an ended episode has no entry."""
+        pol, names = policy_of_records(table, self.env, self.env_id0)
+        m = self.ended()
+        with_fell = self._with_fell(fell)
         out = {}
-        for r in np.unique(rows):
-            sel = rows == r
-            means = {}
-            for name in FLOAT_FIELDS:
-                v = getattr(self, name)[m][sel].astype(np.float64)
-                ok = np.isfinite(v)
-                means[name] = float(v[ok].mean()) if ok.any() else None
-            out[int(r)] = {"episodes": int(sel.sum()), "terminated": int(term[sel].sum()), "terminated_share": float(term[sel].mean()),
-                           **({"fell": int(fallen[sel].sum()), "fell_share": float(fallen[sel].mean())} if with_fell else {}),
-                           "length": {"mean": float(n[sel].mean()), "min": int(n[sel].min()), "p50": float(np.quantile(n[sel], 0.5)),
-                                      "max": int(n[sel].max())},
-                           "means": means}
+        for k in np.unique(pol[m]):
+            mk = m & (pol == k)
+            if not scenario:
+                out[names[int(k)]] = self._cell(mk, with_fell)
+                continue
+            for s in np.unique(self.scenario[mk]):
+                out[(names[int(k)], int(s))] = self._cell(mk & (self.scenario == s), with_fell)
         return out
 
     def save(self, path: str):
@@ -149,6 +166,20 @@ class EpisodeLedger:
         with np.load(path, allow_pickle=False) as z:
             h = z["header"]
             return cls(z["words"], z["env"], z["lost"], int(h[0]), int(h[1]))
+
+
+def policy_of_records(table, env, env_id0: int):
+    """``(policy index int64 [R], names)`` for records of the global env ids ``env``: ``table`` is a ``policy.PolicyTable`` (its
+    ``policy_of`` and ``names``) or an int array holding the policy of each local env (env ``env_id0 + i`` is entry ``i``)."""
+    env = np.asarray(env, dtype=np.int64)
+    if hasattr(table, "policy_of"):
+        return np.asarray(table.policy_of(env), dtype=np.int64), list(table.names)
+    a = np.asarray(table, dtype=np.int64).reshape(-1)
+    loc = env - int(env_id0)
+    if loc.size and (loc.min() < 0 or loc.max() >= len(a)):
+        raise ValueError(f"by_policy: the array names the policy of {len(a)} local envs, the records hold env ids "
+                         f"{int(env.min())}..{int(env.max())} (first id {env_id0})")
+    return a[loc], [str(k) for k in range(int(a.max()) + 1 if a.size else 0)]
 
 
 def _records(episode, length, flags, spawn, seen, s, peak, scenario=None) -> np.ndarray:

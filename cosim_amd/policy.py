@@ -18,6 +18,7 @@ tests compare with a numpy evaluation of the same graph.
 """
 from __future__ import annotations
 
+import os
 import struct
 from typing import Dict, List, Optional
 
@@ -463,8 +464,186 @@ class LSTMPolicy:
         return action.squeeze(0) if single else action
 
 
-def build_policy(config: dict, policy_path: str, num_envs: int = 1, device=None):
-    """``core/policy.py:49-53``."""
+class PolicyTable:
+    """K actor checkpoints over ONE fleet: env ``g`` (global id) is driven by policy ``policy_of(g)`` for the whole run, and one launch
+    of the grouped kernel (``cosim_policy_table_forward``, csrc/cosim_mlp.hip) evaluates all of them -- every env gets the bits
+    ``MLPPolicy(file, fused=True)`` gives it.  All policies meet the same terrain, spawn table, scenario table, fall rule and noise
+    streams (those are keyed by global env id), so one run is the comparison; ``EpisodeLedger.by_policy`` / ``Verdicts.by_policy``
+    break the outcomes down.
+
+    ``assign``: ``"interleave"`` -- ``g mod K``; ``"cross"`` -- ``(g // S) mod K`` with ``S = scenarios`` (in scenario mode ``env``, where
+    env ``g`` runs scenario ``g mod S``, every (scenario, policy) pair gets the same share of envs); or an int array with one entry per
+    LOCAL env.  ``ranges``: the env's ``range_list`` (``get_action_range`` evaluates one of them on the current stream); default: one
+    range.  Every file must be a Gemm / activation chain (``_mlp_chain``) with the first file's input and output width.  On a
+    non-CUDA device, or with ``fused=False``, each policy's interpreter runs on its own rows and the results are scattered: the
+    torch twin of the kernel.  Stateless: a ``Snapshot`` stores nothing for it.
+
+    Out of scope: recurrent policies, files with different observation layouts, an assignment that changes per episode."""
+
+    graph_safe = True     # get_action is one launch on persistent tensors
+
+    def __init__(self, policy_paths, num_envs: int, device=None, assign="interleave", env_id0: int = 0, scenarios: int = 0,
+                 ranges=None, names=None, fused: Optional[bool] = None):
+        import torch
+        self.torch = torch
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        paths = [str(p) for p in policy_paths]
+        K, N = len(paths), int(num_envs)
+        if K < 1:
+            raise ValueError("PolicyTable: no policy file")
+        if N < 1:
+            raise ValueError(f"PolicyTable: num_envs {N} is not positive")
+        self.paths, self.num_envs, self.env_id0, self.scenarios = paths, N, int(env_id0), int(scenarios)
+        self.names = [os.path.splitext(os.path.basename(p))[0] for p in paths] if names is None else [str(x) for x in names]
+        if len(self.names) != K or len(set(self.names)) != K:
+            raise ValueError(f"PolicyTable: names must be {K} different strings, got {self.names}")
+        chains, models = [], []
+        for p in paths:
+            model = read_onnx(p)
+            if any(n["op"] == "LSTM" for n in model["nodes"]):
+                raise ValueError(f"PolicyTable: {p}: an LSTM policy (recurrent policies in a table are out of scope)")
+            chain = _mlp_chain(model)
+            if chain is None:
+                raise ValueError(f"PolicyTable: {p}: the graph is not a plain Gemm / activation chain (1..6 layers, widths up to 512, fp32)")
+            i0, o0 = (chains[0][0][0].shape[1], chains[0][-1][0].shape[0]) if chains else (chain[0][0].shape[1], chain[-1][0].shape[0])
+            if chain[0][0].shape[1] != i0:
+                raise ValueError(f"PolicyTable: {p}: input width {chain[0][0].shape[1]} differs from {i0} of {paths[0]}")
+            if chain[-1][0].shape[0] != o0:
+                raise ValueError(f"PolicyTable: {p}: output width {chain[-1][0].shape[0]} differs from {o0} of {paths[0]}")
+            chains.append(chain)
+            models.append(model)
+        self.in_dim, self.out_dim = int(chains[0][0][0].shape[1]), int(chains[0][-1][0].shape[0])
+        self.assign = assign if isinstance(assign, str) else "explicit"
+        if isinstance(assign, str):
+            if assign not in ("interleave", "cross"):
+                raise ValueError(f"PolicyTable: assign '{assign}': interleave, cross or an int array")
+            if assign == "cross" and self.scenarios < 1:
+                raise ValueError("PolicyTable: assign 'cross' needs scenarios >= 1 (the scenario count of the table)")
+            self._explicit = None
+        else:
+            a = np.asarray(assign)
+            if a.shape != (N,) or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"PolicyTable: an explicit assign has one integer per local env ({N}), got shape {a.shape} {a.dtype}")
+            if a.min() < 0 or a.max() >= K:
+                raise ValueError(f"PolicyTable: assign holds {int(a.min())}..{int(a.max())}, outside [0, {K})")
+            self._explicit = a.astype(np.int32)
+        self.policy_of_env = self.policy_of(np.arange(self.env_id0, self.env_id0 + N, dtype=np.int64))
+        self.ranges = [(0, N)] if ranges is None else [(int(f), int(c)) for f, c in ranges]
+        nxt = 0
+        for f, c in self.ranges:
+            if f != nxt or c < 1:
+                raise ValueError(f"PolicyTable: ranges {self.ranges} do not tile [0, {N}) in order")
+            nxt = f + c
+        if nxt != N:
+            raise ValueError(f"PolicyTable: ranges {self.ranges} do not tile [0, {N}) in order")
+        self._out = torch.zeros((N, self.out_dim), dtype=torch.float32, device=self.device)
+        self._handle = None
+        if fused is not False and self.device.type == "cuda":
+            self._create(chains)
+        elif fused:
+            raise ValueError("fused=True needs a GPU device")
+        else:
+            idx = [np.nonzero(self.policy_of_env == k)[0] for k in range(K)]
+            self._rows = [torch.as_tensor(i, dtype=torch.int64, device=self.device) for i in idx]
+            self._range_rows = [[torch.as_tensor(i[(i >= f) & (i < f + c)], dtype=torch.int64, device=self.device) for i in idx] for f, c in self.ranges]
+            self._graphs = [OnnxGraph(m, self.device) for m in models]
+
+    def policy_of(self, global_env_ids) -> np.ndarray:
+        """The policy index int32 of each global env id (an explicit assignment knows this rank's envs only)."""
+        g = np.asarray(global_env_ids, dtype=np.int64)
+        K = len(self.paths)
+        if self._explicit is not None:
+            loc = g - self.env_id0
+            if loc.size and (loc.min() < 0 or loc.max() >= self.num_envs):
+                raise ValueError(f"PolicyTable.policy_of: an explicit assignment covers env ids {self.env_id0}..{self.env_id0 + self.num_envs - 1}")
+            return self._explicit[loc]
+        return ((g % K) if self.assign == "interleave" else ((g // self.scenarios) % K)).astype(np.int32)
+
+    def _create(self, chains):
+        import ctypes
+        from .engine import load_library
+        L = load_library()
+        K, ML = len(chains), 6
+        nl = (ctypes.c_int * K)(*[len(c) for c in chains])
+        dims, act, alpha = (ctypes.c_int * (K * (ML + 1)))(), (ctypes.c_int * (K * ML))(), (ctypes.c_float * (K * ML))()
+        w, b, keep = (ctypes.c_void_p * (K * ML))(), (ctypes.c_void_p * (K * ML))(), []
+        for k, chain in enumerate(chains):
+            dims[k * (ML + 1)] = chain[0][0].shape[1]
+            for li, (wl, bl, a, al) in enumerate(chain):
+                dims[k * (ML + 1) + li + 1] = wl.shape[0]
+                act[k * ML + li], alpha[k * ML + li] = a, al
+                wl = np.ascontiguousarray(wl, dtype=np.float32)
+                keep.append(wl)
+                w[k * ML + li] = wl.ctypes.data
+                if bl is not None:
+                    bl = np.ascontiguousarray(bl, dtype=np.float32)
+                    keep.append(bl)
+                    b[k * ML + li] = bl.ctypes.data
+        por = np.ascontiguousarray(self.policy_of_env, dtype=np.int32)
+        rng = np.ascontiguousarray(np.asarray(self.ranges, dtype=np.int32).reshape(-1, 2))
+        handle = ctypes.c_void_p()
+        with self.torch.cuda.device(self.device):
+            rc = L.cosim_policy_table_create(K, nl, dims, act, alpha, w, b, self.num_envs, por.ctypes.data, len(self.ranges), rng.ctypes.data,
+                                             ctypes.byref(handle))
+        if rc != 0:
+            raise RuntimeError(L.cosim_last_error().decode())
+        self._lib, self._handle = L, handle
+
+    def state(self):
+        """Nothing: a table is stateless, so ``env.snapshot(table)`` stores no policy state."""
+        return None
+
+    def close(self):
+        if self._handle is not None:
+            self._lib.cosim_policy_table_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _launch(self, x, out, i: int):
+        t = self.torch
+        if x.shape != (self.num_envs, self.in_dim) or out.shape != (self.num_envs, self.out_dim):
+            raise ValueError(f"PolicyTable: state {tuple(x.shape)} / action {tuple(out.shape)}, expected ({self.num_envs}, {self.in_dim}) / "
+                             f"({self.num_envs}, {self.out_dim})")
+        if self._handle is not None:
+            if not (x.is_cuda and out.is_cuda and x.dtype == t.float32 and out.dtype == t.float32 and x.is_contiguous() and out.is_contiguous()):
+                raise ValueError("PolicyTable: state and action must be contiguous fp32 tensors on the table's device")
+            rc = self._lib.cosim_policy_table_forward(self._handle, x.data_ptr(), out.data_ptr(), i, 1.0, t.cuda.current_stream(self.device).cuda_stream)
+            if rc != 0:
+                raise RuntimeError(self._lib.cosim_last_error().decode())
+            return
+        rows = self._rows if i < 0 else self._range_rows[i]
+        for g, idx in zip(self._graphs, rows):
+            if idx.numel():
+                out[idx] = g.run({g.inputs[0]: x[idx]})[0].clamp(-1.0, 1.0)
+
+    def get_action(self, state):
+        """``[N, action_dim]`` in [-1, 1]: the table's persistent output tensor (the next call overwrites it)."""
+        t = self.torch
+        x = t.as_tensor(state, dtype=t.float32, device=self.device).contiguous()
+        self._launch(x, self._out, -1)
+        return self._out
+
+    def get_action_range(self, i: int, state, action):
+        """Writes the rows of range ``i`` of ``ranges`` into ``action`` (``[N, action_dim]``) from ``state`` (``[N, in_dim]``), both whole-fleet
+        contiguous fp32 tensors, on the CURRENT stream and without allocating; the other rows of ``action`` stay as they are."""
+        if not 0 <= int(i) < len(self.ranges):
+            raise ValueError(f"PolicyTable.get_action_range: range {i} outside 0..{len(self.ranges) - 1}")
+        self._launch(state, action, int(i))
+
+
+def build_policy(config: dict, policy_path: str = None, num_envs: int = 1, device=None, **table_args):
+    """``core/policy.py:49-53``.  With a list of files in ``config["policy"]["onnx_files"]``: a ``PolicyTable`` over them
+    (``config["policy"]["assign"]``, default interleave; ``table_args``: ``env_id0``, ``scenarios``, ``ranges``, ``names``)."""
+    files = config["policy"].get("onnx_files")
+    if files:
+        if config["policy"].get("use_lstm"):
+            raise ValueError("build_policy: a policy table takes MLP actors only (recurrent policies in a table are out of scope)")
+        return PolicyTable(list(files), num_envs=num_envs, device=device, assign=config["policy"].get("assign", "interleave"), **table_args)
     if config["policy"]["use_lstm"]:
         return LSTMPolicy(config, policy_path, num_envs=num_envs, device=device)
     return MLPPolicy(policy_path, device=device)

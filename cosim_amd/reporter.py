@@ -42,6 +42,7 @@ class FleetReporter:
             self._lib.cosim_last_error.restype = ctypes.c_char_p
         self.steps = 0
         self.episodes_ended = 0
+        self.policy_table = None      # a policy.PolicyTable (Runner sets it): summary() then breaks episodes and checks down by policy
         self.hist = None
         if percentiles:
             if self._lib is None:
@@ -204,6 +205,27 @@ class FleetReporter:
             x = t.tensor([c[k] for k in keys], dtype=t.int64, device=self.env.device)
             dist.all_reduce(x, op=dist.ReduceOp.SUM)
             out["fleet"] = Verdicts.with_shares({k: int(y) for k, y in zip(keys, x.cpu().tolist())})
+        if self.policy_table is not None:
+            out["by_policy"] = self._by_policy(v.by_policy(self.policy_table), v.by_policy(self.policy_table, scenario=True),
+                                               [k for k in v.counts() if k != "lost"], Verdicts.with_shares)
+        return out
+
+    def _by_policy(self, per_policy: dict, per_cell: dict, count_keys, finish) -> dict:
+        """The report's ``by_policy``: name -> that policy's columns, its ``by_scenario`` rows (the checkpoint x scenario matrix) where
+        the records name a scenario, and under ``torch.distributed`` ``fleet``: the integer counts ``count_keys`` all-reduced over
+        ranks (every rank holds the same names in the same order) and finished by ``finish``."""
+        import torch.distributed as dist
+        names = list(self.policy_table.names)
+        out = {name: dict(per_policy[name]) for name in names if name in per_policy}
+        for (name, s), cell in per_cell.items():
+            if s >= 0:
+                out[name].setdefault("by_scenario", {})[str(s)] = cell
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            t = self.env.torch
+            x = t.tensor([[per_policy.get(name, {}).get(k, 0) for k in count_keys] for name in names], dtype=t.int64, device=self.env.device)
+            dist.all_reduce(x, op=dist.ReduceOp.SUM)
+            for name, row in zip(names, x.cpu().tolist()):
+                out.setdefault(name, {})["fleet"] = finish({k: int(y) for k, y in zip(count_keys, row)})
         return out
 
     def episodes(self) -> dict:
@@ -226,6 +248,12 @@ class FleetReporter:
             fleet = {k: int(x) for k, x in zip(keys, v.cpu().tolist())}
             fleet["length_mean"] = fleet["length_sum"] / fleet["episodes"] if fleet["episodes"] else None
             out["fleet"] = fleet
+        if self.policy_table is not None:
+            def shares(c):
+                e = c["episodes"]
+                return {**c, "terminated_share": c["terminated"] / e if e else None, **({"fell_share": c["fell"] / e if e else None} if "fell" in c else {})}
+            out["by_policy"] = self._by_policy(led.by_policy(self.policy_table, fell=fell), led.by_policy(self.policy_table, scenario=True, fell=fell),
+                                               ["episodes", "terminated"] + (["fell"] if fell else []), shares)
         return out
 
     def save(self, path: str, extra: Optional[dict] = None):

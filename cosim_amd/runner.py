@@ -48,6 +48,8 @@ class Runner:
         self.env, self.policy, self.reporter, self.report_env = env, policy, reporter, report_env
         self.user_command = np.zeros(max(env.command_dim, 0), dtype=np.float32)
         self._push_event, self._push_vel, self._stop = False, None, False
+        if hasattr(policy, "policy_of") and hasattr(reporter, "policy_table"):
+            reporter.policy_table = policy                         # a policy.PolicyTable: the report breaks the outcomes down by policy
 
     def update_command(self, index: int, value: float):            # tester.py:41-46
         if index < self.env.command_dim:
@@ -134,9 +136,13 @@ class Runner:
             raise ValueError("test_pipelined needs an env built with ranges > 1")
         if not env.auto_reset:
             raise ValueError("test_pipelined needs auto_reset=True (no per-step host check of the done flags)")
-        if not hasattr(self.policy, "get_action_into") or not getattr(self.policy, "graph_safe", False):
+        by_range = hasattr(self.policy, "get_action_range")        # a policy.PolicyTable: one launch per range over the whole-fleet tensors
+        if by_range and [tuple(r) for r in self.policy.ranges] != [tuple(r) for r in env.range_list]:
+            raise ValueError(f"test_pipelined: the policy table was built with ranges {list(self.policy.ranges)}, the env has "
+                             f"{list(env.range_list)}; build it with ranges=env.range_list")
+        if not (by_range or hasattr(self.policy, "get_action_into")) or not getattr(self.policy, "graph_safe", False):
             raise ValueError(f"test_pipelined: {type(self.policy).__name__} cannot be evaluated per range on a stream of its own "
-                             "(needs get_action_into and no per-env or host-side state); use Runner.test")
+                             "(needs get_action_into or get_action_range, and no per-env or host-side state); use Runner.test")
         if self.reporter is not None and not hasattr(self.reporter, "write_info_range"):
             raise ValueError("test_pipelined: the reporter must reduce per range (reporter.FleetReporter)")
         env.reset()
@@ -165,7 +171,10 @@ class Runner:
                 if inflight > 0 and steps >= inflight:
                     ring[i][steps % inflight].synchronize()
                 with t.cuda.stream(env.range_streams[i]):
-                    self.policy.get_action_into(env.state[first:first + count], action[first:first + count])   # tester.py:70
+                    if by_range:
+                        self.policy.get_action_range(i, env.state, action)                                        # tester.py:70
+                    else:
+                        self.policy.get_action_into(env.state[first:first + count], action[first:first + count])
                     env.step_range(first, count, action)                                                          # :90
                     if sample:
                         self.reporter.write_info_range(first, count)                                              # :92

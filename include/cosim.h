@@ -525,6 +525,31 @@ int cosim_profile_step(cosim_engine_t* e, const float* actions_dev, const float*
 int cosim_mlp_forward(const float* x_dev, int n, int n_layers, const int* dims, const float* const* w_dev, const float* const* b_dev,
                       const int* act, const float* act_alpha, float clip, float* out_dev, void* stream);
 
+/* Policy table: K actor MLPs (checkpoints) over one fleet, every env assigned to one of them, all evaluated by ONE launch -- the
+ * single-run comparison "which checkpoint is best on these scenarios".  Stateless with respect to cosim_engine_t, as cosim_mlp_forward.
+ *
+ * create: HOST arrays in, an opaque handle out.  n_layers[K] (1..6); dims[K][7] (entries 0..n_layers used, each 1..512; every
+ * policy has policy 0's input and output width); act[K][6] / act_alpha[K][6] as cosim_mlp_forward (act_alpha may be NULL: 1);
+ * w_host[K][6] / b_host[K][6]: host pointers of layer l's [dims[l+1], dims[l]] weights and [dims[l+1]] bias (b_host, or an entry
+ * of it, NULL: no bias).  policy_of_row[n]: the policy in [0, K) of env-local row i.  ranges[n_ranges][2]: (first, count) env
+ * ranges, ascending, covering [0, n) exactly -- forward can evaluate one of them alone, on its own stream.  The call validates
+ * everything (K outside 1..64, layer counts, widths, activation codes, assignments, ranges, n <= 0: COSIM_EINVAL with the reason in
+ * cosim_last_error, nothing reaches the device), packs every weight into one image (a matrix begins at a multiple of 4 words),
+ * groups the rows of each range by policy into tiles of at most 32, and uploads image, descriptors, rows and tiles to the CURRENT
+ * device, which the handle records.
+ * forward: out_dev[i] = clip(policy_of_row[i](x_dev[i])) for the rows of range `range` (an index into `ranges`), or of all ranges
+ * for -1; x_dev is [n, dims[0]], out_dev [n, dims[n_layers]], both whole-fleet device arrays; rows outside the range are not
+ * written.  Every env gets the bits cosim_mlp_forward gives for its policy; the non-finite rule is the same.  Refuses a null pointer,
+ * a range index out of bounds and a current device other than the table's.  No allocation, no host read, no synchronisation: it
+ * can be captured in a graph.
+ * Out of scope: recurrent policies, differing observation layouts, an assignment that changes per episode. */
+typedef struct cosim_policy_table cosim_policy_table_t;
+int cosim_policy_table_create(int n_policies, const int* n_layers, const int* dims, const int* act, const float* act_alpha,
+                              const float* const* w_host, const float* const* b_host, int n, const int* policy_of_row, int n_ranges,
+                              const int* ranges, cosim_policy_table_t** out);
+int cosim_policy_table_forward(cosim_policy_table_t* table, const float* x_dev, float* out_dev, int range, float clip, void* stream);
+int cosim_policy_table_destroy(cosim_policy_table_t* table);
+
 /* The recurrent policy's cell (reference core/policy.py:24-47: an ONNX LSTM node fed one step at a time with h_in / c_in kept by the
  * caller): one LSTM step for all N envs in one launch.  Gate order and layouts are ONNX's: w_dev [4H, I], r_dev [4H, H], b_dev [8H]
  * (Wb then Rb) or NULL, gates i, o, f, c; default activations.  h_out_dev / c_out_dev may alias h_dev / c_dev (in-place state). */
