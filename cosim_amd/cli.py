@@ -22,7 +22,10 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     policy:   {kind: sinusoid | random-mlp | onnx, onnx_file: actor.onnx, use_lstm: false, h_in_dim: 256, c_in_dim: 256}
     policy:   {onnx_files: [a.onnx, b.onnx], assign: interleave | cross, names: [base, tuned]}   # a policy table (policy.PolicyTable): every env
                                                                        # driven by one of the files; same as --policy a.onnx b.onnx
-                                                                       # --policy-assign --policy-names; the report gets episodes.by_policy
+                                                                       # --policy-assign --policy-names; the report gets episodes.by_policy.
+                                                                       # Files with h_in / c_in inputs make a recurrent table
+                                                                       # (policy.RecurrentPolicyTable): the kind is detected from the files,
+                                                                       # all of one kind; use_lstm belongs to a single onnx_file
     steps:    1000
     commands: [[0, 0.5, 0, 0, 0], [200, 1.0, 0, 0.3, 0]]              # from control step t on: user_command = c0 .. c3
     pushes:   [[300, 310, 0.5, 0, 0]]                                   # held for steps t0 <= k < t1: event("push", [vx, vy, vz])
@@ -61,11 +64,12 @@ def main(argv=None) -> int:
     ap.add_argument("--num-envs", type=int, default=None, help="total over all ranks")
     ap.add_argument("--steps", type=int, default=None, help="control steps (50 Hz)")
     ap.add_argument("--policy", default=None, nargs="+", metavar="POLICY",
-                    help="sinusoid | random-mlp | <file.onnx>, or several ONNX actor files: a policy table, every env driven by one of them")
+                    help="sinusoid | random-mlp | <file.onnx>, or several ONNX actor files: a policy table, every env driven by one of them "
+                         "(MLP actors, or recurrent ones with h_in / c_in inputs: the kind is detected from the files, all of one kind)")
     ap.add_argument("--policy-assign", choices=["interleave", "cross"], default=None,
                     help="several --policy files: env g runs policy g mod K (interleave, the default) or (g // S) mod K with S scenarios (cross)")
     ap.add_argument("--policy-names", nargs="+", default=None, metavar="NAME", help="several --policy files: their names in the report (default: the file stems)")
-    ap.add_argument("--lstm", action="store_true", help="the ONNX file is an LSTM policy with h_in / c_in inputs")
+    ap.add_argument("--lstm", action="store_true", help="the ONNX file is an LSTM policy with h_in / c_in inputs (a single --policy file; several recurrent files need no flag)")
     ap.add_argument("--hidden-dim", type=int, default=256, help="h_in_dim = c_in_dim of an LSTM policy")
     ap.add_argument("--command", type=float, nargs="*", default=None)
     ap.add_argument("--position-command", action="store_true")
@@ -78,7 +82,7 @@ def main(argv=None) -> int:
     ap.add_argument("--percentiles", action="store_true", help="p5 / p50 / p95 of tracking error, |torque| and action-RMSE in the report")
     ap.add_argument("--graph", action="store_true", help="capture policy -> step -> report in a HIP graph and replay it (ONNX policies)")
     ap.add_argument("--pipelined", action="store_true",
-                    help="policy -> step -> report per env range on the range's own stream, no fleet-wide barrier per step (ONNX MLP policies)")
+                    help="policy -> step -> report per env range on the range's own stream, no fleet-wide barrier per step (an ONNX MLP policy, or a policy table of either kind)")
     ap.add_argument("--ranges", type=int, default=4, help="env ranges of --pipelined")
     ap.add_argument("--hfield-fixup", action="store_true",
                     help="heightfield terrain: redo steps whose ground contacts exceed the fleet kernel's slots instead of cutting them off")

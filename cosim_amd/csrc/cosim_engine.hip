@@ -875,6 +875,16 @@ struct cosim_policy_table {
   std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count)
 };
 
+// what cosim_recurrent_table_create hands out: as above, with the launch's two leading dimensions and the state tensors' row stride
+struct cosim_recurrent_table {
+  int n = 0, device = 0, ld_m = 0, ld_x = 0, hmax = 0, n_tiles = 0;
+  float* d_image = nullptr;
+  RecDesc* d_desc = nullptr;
+  int32_t* d_rows = nullptr;
+  PolTile* d_tiles = nullptr;
+  std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count)
+};
+
 extern "C" {
 
 // Fused actor MLP (cosim_mlp.hip): out = clip(act_L(... act_1(x W_1^T + b_1) ...)).  All pointers are device pointers; dims has
@@ -974,6 +984,79 @@ int cosim_policy_table_destroy(cosim_policy_table* p) {
   return COSIM_OK;
 }
 
+// Recurrent policy table (cosim_rectab.h, lstm_actor_grouped_kernel): K recurrent actors over one fleet, one launch per evaluation.
+// create checks and packs the host arrays, builds the tile list and uploads everything once; forward only launches.
+int cosim_recurrent_table_create(int n_policies, const int* n_enc, const int* enc_dims, const int* enc_act, const float* enc_alpha,
+                                 const float* const* enc_w_host, const float* const* enc_b_host, const int* lstm_in, const int* hidden,
+                                 const float* const* lstm_w_host, const float* const* lstm_r_host, const float* const* lstm_b_host,
+                                 const int* n_head, const int* head_dims, const int* head_act, const float* head_alpha,
+                                 const float* const* head_w_host, const float* const* head_b_host, int n, const int* policy_of_row,
+                                 int n_ranges, const int* ranges, cosim_recurrent_table** out) {
+  if (!out) return fail(COSIM_EINVAL, "cosim_recurrent_table_create: null argument");
+  *out = nullptr;
+  const RecRaw raw = {n_policies, n_enc, enc_dims, enc_act, enc_alpha, enc_w_host, enc_b_host, lstm_in, hidden, lstm_w_host, lstm_r_host, lstm_b_host,
+                      n_head, head_dims, head_act, head_alpha, head_w_host, head_b_host, n, policy_of_row, n_ranges, ranges};
+  int dev = 0, lds_limit = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return fail(COSIM_EINVAL, "cosim_recurrent_table_create: device index out of range");
+  HIP_TRY(hipDeviceGetAttribute(&lds_limit, hipDeviceAttributeMaxSharedMemoryPerBlock, dev));
+  const RecShape shape = validate_recurrent_table(raw, lds_limit);
+  if (!shape.err.empty()) return fail(COSIM_EINVAL, shape.err);
+  const RecImage im = pack_recurrent_image(raw);
+  const PolTiles tl = build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges);
+  cosim_recurrent_table* p = new cosim_recurrent_table;
+  p->n = n; p->device = dev; p->ld_m = shape.ld_m; p->ld_x = shape.ld_x; p->hmax = shape.hmax;
+  p->n_tiles = (int)tl.tiles.size(); p->tile_span = tl.tile_span;
+  const size_t lds = (size_t)rec_lds_dynamic(p->ld_m, p->ld_x);
+  static size_t lds_allowed[64] = {0};   // per device, as cosim_mlp_forward
+  auto upload = [&]() -> int {
+    const size_t b_img = im.words.size() * 4, b_desc = im.desc.size() * sizeof(RecDesc), b_rows = tl.rows.size() * 4, b_tiles = tl.tiles.size() * sizeof(PolTile);
+    HIP_TRY(hipMalloc(&p->d_image, b_img)); HIP_TRY(hipMalloc(&p->d_desc, b_desc)); HIP_TRY(hipMalloc(&p->d_rows, b_rows)); HIP_TRY(hipMalloc(&p->d_tiles, b_tiles));
+    HIP_TRY(hipMemcpy(p->d_image, im.words.data(), b_img, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_desc, im.desc.data(), b_desc, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_rows, tl.rows.data(), b_rows, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_tiles, tl.tiles.data(), b_tiles, hipMemcpyHostToDevice));
+    if (lds > lds_allowed[dev]) {
+      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_actor_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+      lds_allowed[dev] = lds;
+    }
+    return COSIM_OK;
+  };
+  const int rc = upload();
+  if (rc) { cosim_recurrent_table_destroy(p); return rc; }
+  *out = p;
+  return COSIM_OK;
+}
+
+// h_dev / c_dev: the table's state, [n, hmax] with hmax the widest hidden size, updated in place.  done_a_dev / done_b_dev: [n] bytes
+// or null; a row with either set starts from a zero state.  No allocation, no host read of device memory and no synchronisation.
+int cosim_recurrent_table_forward(cosim_recurrent_table* p, const float* x_dev, float* h_dev, float* c_dev, float* out_dev,
+                                  const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range, float clip, void* stream) {
+  if (!p || !x_dev || !h_dev || !c_dev || !out_dev) return fail(COSIM_EINVAL, "cosim_recurrent_table_forward: null argument");
+  const int n_ranges = (int)p->tile_span.size() / 2;
+  if (range < -1 || range >= n_ranges)
+    return fail(COSIM_EINVAL, "cosim_recurrent_table_forward: range " + std::to_string(range) + " outside -1.." + std::to_string(n_ranges - 1));
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != p->device)
+    return fail(COSIM_EINVAL, "cosim_recurrent_table_forward: the table lives on device " + std::to_string(p->device) + ", the current device is " + std::to_string(dev));
+  RecTabArgs a;
+  a.x = x_dev; a.h = h_dev; a.c = c_dev; a.out = out_dev; a.done_a = done_a_dev; a.done_b = done_b_dev;
+  a.image = p->d_image; a.desc = p->d_desc; a.rows = p->d_rows; a.tiles = p->d_tiles;
+  a.tile_first = range < 0 ? 0 : p->tile_span[2 * range]; a.ld_m = p->ld_m; a.ld_x = p->ld_x; a.hmax = p->hmax; a.clip = clip;
+  const int tile_count = range < 0 ? p->n_tiles : p->tile_span[2 * range + 1];
+  hipLaunchKernelGGL(lstm_actor_grouped_kernel, dim3(tile_count), dim3(256), (size_t)rec_lds_dynamic(p->ld_m, p->ld_x), (hipStream_t)stream, a);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+int cosim_recurrent_table_destroy(cosim_recurrent_table* p) {
+  if (!p) return COSIM_OK;
+  (void)hipFree(p->d_image); (void)hipFree(p->d_desc); (void)hipFree(p->d_rows); (void)hipFree(p->d_tiles);
+  delete p;
+  return COSIM_OK;
+}
+
 int cosim_lstm_cell(const float* x_dev, const float* h_dev, const float* c_dev, int n, int in_dim, int hidden, const float* w_dev,
                     const float* r_dev, const float* b_dev, float* h_out_dev, float* c_out_dev, void* stream) {
   if (!x_dev || !h_dev || !c_dev || !w_dev || !r_dev || !h_out_dev || !c_out_dev || n <= 0) return fail(COSIM_EINVAL, "cosim_lstm_cell: bad argument");
@@ -981,6 +1064,7 @@ int cosim_lstm_cell(const float* x_dev, const float* h_dev, const float* c_dev, 
   LstmArgs a;
   a.x = x_dev; a.h = h_dev; a.c = c_dev; a.W = w_dev; a.R = r_dev; a.B = b_dev; a.h_out = h_out_dev; a.c_out = c_out_dev;
   a.n = n; a.I = in_dim; a.H = hidden; a.ld = (in_dim + hidden) | 1;
+  a.vec = in_dim % 4 == 0 && hidden % 4 == 0 && ((uintptr_t)w_dev | (uintptr_t)r_dev) % 16 == 0;
   const size_t lds = (size_t)32 * a.ld * sizeof(float);
   static size_t lds_allowed[64] = {0};   // per device
   int dev = 0;

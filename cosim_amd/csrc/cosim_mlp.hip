@@ -12,6 +12,7 @@
 #include <stdint.h>
 
 #include "cosim_poltab.h"
+#include "cosim_rectab.h"
 
 namespace cosim {
 
@@ -177,10 +178,98 @@ struct LstmArgs {
   const float *W, *R, *B;      // [4H, I], [4H, H], [8H] (Wb then Rb) or null
   float *h_out, *c_out;        // [n, H]; may alias h / c (each element is read before the workgroup that owns its rows writes it)
   int n, I, H, ld;
+  int vec;                     // I and H are multiples of 4 and W, R are 16-byte aligned: the float4 path of lstm_gate_tiles
 };
 
+typedef float lstm_f32x16 __attribute__((ext_vector_type(16)));
+
+// The cell's inner part, shared by lstm_cell_kernel and lstm_actor_grouped_kernel.  The four gate tiles (i, o, f, c) of 32 envs x the 32
+// hidden units col - (l & 31) ..: `xh` is the LDS tile [32][ld] holding [x | h] of the envs, the accumulators start at Wb + Rb and take
+// one MFMA step per pair (k, k + 1), k ascending over [x | h] -- that order is the contract (the bits of h' and c').  How the weights are
+// fetched is not: with `vec` a lane reads four words of its W / R row at once and feeds two steps from them.
+__device__ __forceinline__ void lstm_gate_tiles(const float* xh, int ld, int I, int H, const float* W, const float* R, const float* B, bool vec,
+                                                int col, lstm_f32x16 (&acc)[4]) {
+  const int l = threadIdx.x & 63, row_a = l & 31, kk = l >> 5, K = I + H;
+  const bool cok = col < H;
+  const int wc = cok ? col : 0;
+#pragma unroll
+  for (int q = 0; q < 4; q++) {
+    const float bias = (B != nullptr && cok) ? B[q * H + col] + B[4 * H + q * H + col] : 0.f;
+#pragma unroll
+    for (int v = 0; v < 16; v++) acc[q][v] = bias;
+  }
+  // One loop for both ways of fetching.  A turn takes LSTM_QUADS quads of k -- per quad the pairs (k, k + 1) and (k + 2, k + 3) -- and
+  // fetches the operands of all of them before the first MFMA: a wave runs alone on its SIMD here (the LDS tile leaves room for one or
+  // two workgroups), so one round trip to L2 per quad was what a step cost; now it is one per turn.  The loads are unconditional (a
+  // column or quad past the end reads a valid address and is zeroed or skipped), so they are not fenced in by branches.  With `vec`
+  // neither pair straddles x and h and K is a multiple of 4.
+  constexpr int LSTM_QUADS = 4;
+  const float* a_row = xh + row_a * ld;
+  for (int k0 = 0; k0 < K; k0 += 4 * LSTM_QUADS) {
+    float a0[LSTM_QUADS], a1[LSTM_QUADS], w0[LSTM_QUADS][4], w1[LSTM_QUADS][4];
+#pragma unroll
+    for (int u = 0; u < LSTM_QUADS; u++) {
+      const int ka = k0 + 4 * u + kk, kb = ka + 2;
+      a0[u] = ka < K ? a_row[ka] : 0.f;
+      a1[u] = kb < K ? a_row[kb] : 0.f;
+    }
+    if (vec) {
+      float4 w4[LSTM_QUADS][4];
+#pragma unroll
+      for (int u = 0; u < LSTM_QUADS; u++) {
+        const int kq = k0 + 4 * u, kc = kq < K ? kq : K - 4;
+        const bool in_x = kc < I;
+        const float* M = in_x ? W : R;
+        const int width = in_x ? I : H, kw = in_x ? kc : kc - I;
+#pragma unroll
+        for (int q = 0; q < 4; q++) w4[u][q] = *reinterpret_cast<const float4*>(M + (size_t)(q * H + wc) * width + kw);
+      }
+#pragma unroll
+      for (int u = 0; u < LSTM_QUADS; u++)
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          // the four words as they were loaded: without this the compiler narrows each load to the words a lane selects below, and
+          // pays for it with a branch on kk and a full wait per load
+          asm volatile("" : "+v"(w4[u][q].x), "+v"(w4[u][q].y), "+v"(w4[u][q].z), "+v"(w4[u][q].w));
+          w0[u][q] = cok ? (kk ? w4[u][q].y : w4[u][q].x) : 0.f;
+          w1[u][q] = cok ? (kk ? w4[u][q].w : w4[u][q].z) : 0.f;
+        }
+    } else {
+#pragma unroll
+      for (int u = 0; u < LSTM_QUADS; u++) {
+        const int ka = k0 + 4 * u + kk, kb = ka + 2;
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+          w0[u][q] = w1[u][q] = 0.f;
+          if (cok && ka < K) w0[u][q] = ka < I ? W[(size_t)(q * H + col) * I + ka] : R[(size_t)(q * H + col) * H + (ka - I)];
+          if (cok && kb < K) w1[u][q] = kb < I ? W[(size_t)(q * H + col) * I + kb] : R[(size_t)(q * H + col) * H + (kb - I)];
+        }
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < LSTM_QUADS; u++) {
+      const int kq = k0 + 4 * u;   // the branches are wave-uniform: no step past K, as in a loop over pairs
+      if (kq < K) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0[u], w0[u][q], acc[q], 0, 0, 0);
+      }
+      if (kq + 2 < K) {
+#pragma unroll
+        for (int q = 0; q < 4; q++) acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[u], w1[u][q], acc[q], 0, 0, 0);
+      }
+    }
+  }
+}
+
+// The gate arithmetic of one (env, hidden unit): pre-activations of i, o, f, c and the old cell state in, c' and h' out.
+__device__ __forceinline__ void lstm_gates(float gi, float go, float gf, float gc, float c, float& c_new, float& h_new) {
+  const float ig = 1.f / (1.f + expf(-gi)), og = 1.f / (1.f + expf(-go)), fg = 1.f / (1.f + expf(-gf));
+  const float cn = fg * c + ig * tanhf(gc);
+  c_new = cn;
+  h_new = og * tanhf(cn);
+}
+
 __global__ __launch_bounds__(256) void lstm_cell_kernel(LstmArgs A) {
-  typedef float f32x16 __attribute__((ext_vector_type(16)));
   extern __shared__ float lstm_lds[];   // [32][ld]: x then h of 32 environments
   const int t = threadIdx.x, l = t & 63, wave = t >> 6, n0 = blockIdx.x * 32, I = A.I, H = A.H, K = I + H, ld = A.ld;
   for (int e = t; e < 32 * K; e += 256) {
@@ -190,41 +279,124 @@ __global__ __launch_bounds__(256) void lstm_cell_kernel(LstmArgs A) {
     lstm_lds[r * ld + k] = v;
   }
   __syncthreads();
-  const int row_a = l & 31, kk = l >> 5;
   // every c this workgroup needs is read before any of its h / c is written (in-place update across launches is safe; h_out may
   // alias h because h was staged in LDS above and other workgroups own other rows)
   for (int ti = wave; ti * 32 < H; ti += 4) {
     const int col = ti * 32 + (l & 31);
-    const bool cok = col < H;
-    f32x16 acc[4];
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-      const float bias = (A.B != nullptr && cok) ? A.B[q * H + col] + A.B[4 * H + q * H + col] : 0.f;
-#pragma unroll
-      for (int v = 0; v < 16; v++) acc[q][v] = bias;
-    }
-    for (int k0 = 0; k0 < K; k0 += 2) {
-      const int k = k0 + kk;
-      const float a = k < K ? lstm_lds[row_a * ld + k] : 0.f;
-#pragma unroll
-      for (int q = 0; q < 4; q++) {
-        float w = 0.f;
-        if (cok && k < K) w = k < I ? A.W[(size_t)(q * H + col) * I + k] : A.R[(size_t)(q * H + col) * H + (k - I)];
-        acc[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, w, acc[q], 0, 0, 0);
-      }
-    }
+    lstm_f32x16 acc[4];
+    lstm_gate_tiles(lstm_lds, ld, I, H, A.W, A.R, A.B, A.vec != 0, col, acc);
 #pragma unroll
     for (int v = 0; v < 16; v++) {
       const int row = (v & 3) + 8 * (v >> 2) + 4 * (l >> 5);
-      if (cok && n0 + row < A.n) {
+      if (col < H && n0 + row < A.n) {
         const size_t o = (size_t)(n0 + row) * H + col;
-        const float ig = 1.f / (1.f + expf(-acc[0][v])), og = 1.f / (1.f + expf(-acc[1][v])), fg = 1.f / (1.f + expf(-acc[2][v]));
-        const float cn = fg * A.c[o] + ig * tanhf(acc[3][v]);
+        float cn, hn;
+        lstm_gates(acc[0][v], acc[1][v], acc[2][v], acc[3][v], A.c[o], cn, hn);
         A.c_out[o] = cn;
-        A.h_out[o] = og * tanhf(cn);
+        A.h_out[o] = hn;
       }
     }
   }
+}
+
+// K recurrent actors over one fleet in one launch (cosim_recurrent_table_forward; the table is made and checked by cosim_rectab.h).  A
+// workgroup takes one tile of the same tile list as mlp_grouped_kernel -- up to 32 envs of one policy -- and runs the whole actor on it:
+// the encoder layers (if any) with mlp_layers, the LSTM cell with the functions above on the envs' rows of the table's state tensors h / c
+// ([n, hmax], a policy of hidden size H uses columns 0 .. H), updated in place, and the head layers with mlp_layers on h'.  An env whose
+// done_a / done_b byte is set starts from h = c = 0: the episode reset folded into the forward, a select, so a NaN state ends with its
+// episode.  LDS: [2][32][ld_m] (encoder / head ping-pong) then [32][ld_x] ([x_enc | h]).  A row is in exactly one tile, h is staged before
+// anything is written and c[o] is read by the lane that writes it, so the update in place is safe.
+struct RecTabArgs {
+  const float* x;          // [n, in_dim]
+  float *h, *c;            // [n, hmax]
+  float* out;              // [n, out_dim]
+  const uint8_t *done_a, *done_b;   // [n] or null
+  const float* image;
+  const RecDesc* desc;     // [K]
+  const int32_t* rows;
+  const PolTile* tiles;
+  int tile_first, ld_m, ld_x, hmax;
+  float clip;              // as MlpArgs::clip
+};
+
+__global__ __launch_bounds__(256) void lstm_actor_grouped_kernel(RecTabArgs A) {
+  extern __shared__ float rec_lds[];   // [2][32][ld_m], [32][ld_x]
+  __shared__ int tile_row[32];         // the env each tile row holds, -1 behind the tile's count
+  __shared__ int tile_fresh[32];       // != 0: the env's episode ended, its state reads as zero
+  const int ld = A.ld_m, ldx = A.ld_x, hmax = A.hmax;
+  const int t = threadIdx.x, l = t & 63, wave = t >> 6;
+  float* xh = rec_lds + 2 * 32 * ld;
+  // the tile and its policy: indices out of blockIdx alone, so wave-uniform (scalar loads)
+  const PolTile T = A.tiles[A.tile_first + blockIdx.x];
+  const RecDesc* D = A.desc + T.policy;
+  if (t < 32) {
+    const int r = t < T.count ? A.rows[T.start + t] : -1;
+    int fresh = 0;
+    if (r >= 0) fresh = (A.done_a != nullptr && A.done_a[r] != 0) || (A.done_b != nullptr && A.done_b[r] != 0);
+    tile_row[t] = r;
+    tile_fresh[t] = fresh;
+  }
+  __syncthreads();
+  const int ne = D->ne, I0 = D->edims[0], I = D->I, H = D->H;
+  {
+    // the observation rows: into the encoder's input tile, or straight into [x | h] when there is no encoder
+    float* dst = ne > 0 ? rec_lds : xh;
+    const int dld = ne > 0 ? ld : ldx;
+    for (int e = t; e < 32 * I0; e += 256) {
+      const int r = e / I0, c = e - r * I0, src = tile_row[r];
+      dst[r * dld + c] = src >= 0 ? A.x[(size_t)src * I0 + c] : 0.f;
+    }
+    for (int e = t; e < 32 * H; e += 256) {
+      const int r = e / H, k = e - r * H, src = tile_row[r];
+      xh[r * ldx + I + k] = (src >= 0 && !tile_fresh[r]) ? A.h[(size_t)src * hmax + k] : 0.f;
+    }
+  }
+  __syncthreads();
+  if (ne > 0) {
+    // the last encoder layer reads tile (ne - 1) & 1; its output rows go to the other tile, [32][I], and from there into [x_enc | h]
+    float* enc = rec_lds + (ne & 1) * 32 * ld;
+    mlp_layers(rec_lds, ld, ne, 0.f, enc,
+               [&](int L) {
+                 const int bo = D->eboff[L];
+                 return MlpLayer{A.image + D->ewoff[L], bo >= 0 ? A.image + bo : nullptr, D->edims[L], D->edims[L + 1], D->eact[L], D->ealpha[L]};
+               },
+               [&](int row) -> long long { return row; });
+    for (int e = t; e < 32 * I; e += 256) {
+      const int r = e / I, k = e - r * I;
+      xh[r * ldx + k] = enc[r * I + k];
+    }
+    __syncthreads();
+  }
+  const float* W = A.image + D->woff;
+  const float* R = A.image + D->roff;
+  const float* B = D->boff >= 0 ? A.image + D->boff : nullptr;
+  for (int ti = wave; ti * 32 < H; ti += 4) {
+    const int col = ti * 32 + (l & 31);
+    lstm_f32x16 acc[4];
+    lstm_gate_tiles(xh, ldx, I, H, W, R, B, D->vec != 0, col, acc);
+#pragma unroll
+    for (int v = 0; v < 16; v++) {
+      const int row = (v & 3) + 8 * (v >> 2) + 4 * (l >> 5), src = tile_row[row];
+      if (col < H) {
+        float hn = 0.f;
+        if (src >= 0) {
+          const size_t o = (size_t)src * hmax + col;
+          float cn;
+          lstm_gates(acc[0][v], acc[1][v], acc[2][v], acc[3][v], tile_fresh[row] ? 0.f : A.c[o], cn, hn);
+          A.c[o] = cn;
+          A.h[o] = hn;
+        }
+        rec_lds[row * ld + col] = hn;   // h' is the head's input tile
+      }
+    }
+  }
+  __syncthreads();
+  mlp_layers(rec_lds, ld, D->nh, A.clip, A.out,
+             [&](int L) {
+               const int bo = D->hboff[L];
+               return MlpLayer{A.image + D->hwoff[L], bo >= 0 ? A.image + bo : nullptr, D->hdims[L], D->hdims[L + 1], D->hact[L], D->halpha[L]};
+             },
+             [&](int row) -> long long { return tile_row[row]; });
 }
 
 // Reporter side of the loop (core/reporter.py:210-218, 429-442, 506-508): count / sum / sum of squares per metric column over

@@ -305,33 +305,116 @@ OnnxGraph._lstm_cell_hip = _lstm_cell_hip
 _ACT = {"Relu": 1, "Tanh": 2, "Elu": 3, "Sigmoid": 4, "LeakyRelu": 5}
 
 
-def _mlp_chain(model: dict):
-    """The graph as a plain actor MLP -- Gemm(transB=1, alpha=beta=1) [+ activation] ... -- or None if it is anything else."""
-    nodes, init = model["nodes"], model["init"]
-    if len(model["inputs"]) != 1 or len(model["outputs"]) != 1:
-        return None
-    layers, cur, i = [], model["inputs"][0], 0
+def _gemm_layers(nodes, i: int, cur: str, init: dict, src=lambda name: name):
+    """The Gemm(transB=1, alpha=beta=1) [+ activation] layers that follow one another from ``nodes[i]`` on, the first fed by ``cur``:
+    ``(layers, cur, i)`` with ``i`` the first node that is not of that shape.  ``src(name)``: the tensor a name stands for."""
+    layers = []
     while i < len(nodes):
         n = nodes[i]
         a = n["attrs"]
-        if n["op"] != "Gemm" or n["inputs"][0] != cur or a.get("transB", 0) != 1 or a.get("transA", 0) or \
+        if n["op"] != "Gemm" or src(n["inputs"][0]) != cur or a.get("transB", 0) != 1 or a.get("transA", 0) or \
                 a.get("alpha", 1.0) != 1.0 or a.get("beta", 1.0) != 1.0 or n["inputs"][1] not in init:
-            return None
+            break
         w = init[n["inputs"][1]]
         b = init.get(n["inputs"][2]) if len(n["inputs"]) > 2 and n["inputs"][2] else None
         if w.ndim != 2 or w.dtype != np.float32 or (b is not None and (b.shape != (w.shape[0],) or b.dtype != np.float32)):
-            return None
+            break
         cur, act, alpha = n["outputs"][0], 0, 1.0
         i += 1
-        if i < len(nodes) and nodes[i]["op"] in _ACT and nodes[i]["inputs"] == [cur]:
+        if i < len(nodes) and nodes[i]["op"] in _ACT and [src(x) for x in nodes[i]["inputs"]] == [cur]:
             act = _ACT[nodes[i]["op"]]
             alpha = float(nodes[i]["attrs"].get("alpha", 1.0 if act == 3 else 0.01))
             cur = nodes[i]["outputs"][0]
             i += 1
         layers.append((w, b, act, alpha))
-    if cur != model["outputs"][0] or not 1 <= len(layers) <= 6 or any(max(w.shape) > 512 for w, *_ in layers):
+    return layers, cur, i
+
+
+def _mlp_chain(model: dict):
+    """The graph as a plain actor MLP -- Gemm(transB=1, alpha=beta=1) [+ activation] ... -- or None if it is anything else."""
+    nodes = model["nodes"]
+    if len(model["inputs"]) != 1 or len(model["outputs"]) != 1:
+        return None
+    layers, cur, i = _gemm_layers(nodes, 0, model["inputs"][0], model["init"])
+    if i != len(nodes) or cur != model["outputs"][0] or not 1 <= len(layers) <= 6 or any(max(w.shape) > 512 for w, *_ in layers):
         return None
     return layers
+
+
+_SHAPE_ONLY = ("Unsqueeze", "Squeeze", "Reshape", "Identity")
+
+
+def _recurrent_actor(model: dict):
+    """The graph as a recurrent actor: inputs (obs, "h_in", "c_in"), outputs (action, h_out, c_out); 0..3 Gemm / activation layers on
+    ``obs``, ONE LSTM node (forward, layout 0, default activations, one step per call, ``initial_h`` / ``initial_c`` wired to ``h_in`` /
+    ``c_in``), 1..3 Gemm / activation layers from ``Y`` or ``Y_h`` to the action; ``Unsqueeze`` / ``Squeeze`` / ``Reshape`` / ``Identity``
+    nodes that only move unit axes may sit between them.  Returns ``(parts, None)`` -- ``parts``: ``enc`` and ``head`` (layers as
+    ``_mlp_chain`` gives them), ``W [4H, I]``, ``R [4H, H]``, ``B [8H]`` or None, ``I``, ``H`` -- or ``(None, reason)``."""
+    init = model["init"]
+    if len(model["inputs"]) != 3 or model["inputs"][1:] != ["h_in", "c_in"]:
+        return None, f"the inputs are {model['inputs']}, not (obs, 'h_in', 'c_in')"
+    if len(model["outputs"]) != 3:
+        return None, f"{len(model['outputs'])} outputs, not (action, h_out, c_out)"
+    stands_for, body = {}, []
+    for n in model["nodes"]:
+        if n["op"] in _SHAPE_ONLY:
+            if n["op"] == "Reshape" and (n["inputs"][1] not in init or int((np.asarray(init[n["inputs"][1]]).ravel() != 1).sum()) > 2):
+                return None, "a Reshape that does more than move unit axes"
+            stands_for[n["outputs"][0]] = n["inputs"][0]
+        else:
+            body.append(n)
+
+    def src(name):
+        while name in stands_for:
+            name = stands_for[name]
+        return name
+    n_lstm = sum(1 for n in body if n["op"] == "LSTM")
+    if n_lstm == 0:
+        return None, "no LSTM node"
+    if n_lstm > 1:
+        return None, "a second LSTM node (stacked cells are out of scope)"
+    enc, cur, i = _gemm_layers(body, 0, model["inputs"][0], init, src)
+    if body[i]["op"] != "LSTM" or src(body[i]["inputs"][0]) != cur:
+        return None, f"node '{body[i]['op']}' between the observation and the LSTM node is not part of a Gemm / activation chain"
+    n = body[i]
+    a, ins, outs = n["attrs"], n["inputs"] + [""] * 8, n["outputs"] + [""] * 3
+    if a.get("direction", "forward") != "forward":
+        return None, f"LSTM direction '{a.get('direction')}' (forward only)"
+    if a.get("layout", 0):
+        return None, "LSTM layout 1 (layout 0 only)"
+    if a.get("activations") or a.get("clip") is not None or a.get("input_forget", 0) or ins[4] or ins[7]:
+        return None, "LSTM with non-default activations, clip, input_forget, sequence_lens or peepholes"
+    if src(ins[5]) != "h_in":
+        return None, "initial_h is not wired to h_in"
+    if src(ins[6]) != "c_in":
+        return None, "initial_c is not wired to c_in"
+    if ins[1] not in init or ins[2] not in init or (ins[3] and ins[3] not in init):
+        return None, "LSTM weights that are not initialisers"
+    W, R, B = init[ins[1]], init[ins[2]], init[ins[3]] if ins[3] else None
+    if W.dtype != np.float32 or R.dtype != np.float32 or (B is not None and B.dtype != np.float32):
+        return None, "LSTM weights that are not fp32"
+    if W.ndim != 3 or W.shape[0] != 1 or R.ndim != 3 or R.shape[0] != 1 or W.shape[1] % 4:
+        return None, f"LSTM weights of shape {W.shape} / {R.shape}, not [1, 4H, I] / [1, 4H, H]"
+    H, I = W.shape[1] // 4, W.shape[2]
+    if R.shape != (1, 4 * H, H) or (B is not None and B.shape != (1, 8 * H)) or a.get("hidden_size", H) != H:
+        return None, f"LSTM shapes W {W.shape}, R {R.shape}, B {None if B is None else B.shape}, hidden_size {a.get('hidden_size')} do not agree"
+    if enc and enc[-1][0].shape[0] != I:
+        return None, f"the LSTM's input width {I} differs from the encoder's output width {enc[-1][0].shape[0]}"
+    if src(model["outputs"][1]) != outs[1] or not outs[1] or src(model["outputs"][2]) != outs[2] or not outs[2]:
+        return None, "the second and third output are not the LSTM's Y_h and Y_c"
+    first = body[i + 1]["inputs"][0] if i + 1 < len(body) and body[i + 1]["inputs"] else ""
+    if not first or src(first) not in (outs[0], outs[1]):
+        return None, "the head does not read the LSTM's Y or Y_h"
+    head, cur, j = _gemm_layers(body, i + 1, src(first), init, src)
+    if j != len(body) or src(model["outputs"][0]) != cur:
+        return None, "the head is not a Gemm / activation chain from the LSTM's output to the action" + \
+            (f" (node '{body[j]['op']}')" if j < len(body) else "")
+    if len(enc) > 3 or not 1 <= len(head) <= 3:
+        return None, f"{len(enc)} encoder and {len(head)} head layers (0..3 and 1..3)"
+    if head[0][0].shape[1] != H:
+        return None, f"the head's input width {head[0][0].shape[1]} differs from the hidden size {H}"
+    return {"enc": enc, "head": head, "W": W[0], "R": R[0], "B": None if B is None else B[0], "I": int(I), "H": int(H),
+            "in_dim": int(enc[0][0].shape[1] if enc else I), "out_dim": int(head[-1][0].shape[0])}, None
 
 
 class MLPPolicy:
@@ -464,7 +547,76 @@ class LSTMPolicy:
         return action.squeeze(0) if single else action
 
 
-class PolicyTable:
+class _FleetTable:
+    """What the tables of this module share: the files and their names, the assignment of envs to policies and the env ranges."""
+
+    def _setup_fleet(self, policy_paths, num_envs, device, env_id0, scenarios, names):
+        import torch
+        self.torch = torch
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        who = type(self).__name__
+        paths = [str(p) for p in policy_paths]
+        K, N = len(paths), int(num_envs)
+        if K < 1:
+            raise ValueError(f"{who}: no policy file")
+        if N < 1:
+            raise ValueError(f"{who}: num_envs {N} is not positive")
+        self.paths, self.num_envs, self.env_id0, self.scenarios = paths, N, int(env_id0), int(scenarios)
+        self.names = [os.path.splitext(os.path.basename(p))[0] for p in paths] if names is None else [str(x) for x in names]
+        if len(self.names) != K or len(set(self.names)) != K:
+            raise ValueError(f"{who}: names must be {K} different strings, got {self.names}")
+
+    def _setup_assign(self, assign, ranges):
+        who, K, N = type(self).__name__, len(self.paths), self.num_envs
+        self.assign = assign if isinstance(assign, str) else "explicit"
+        if isinstance(assign, str):
+            if assign not in ("interleave", "cross"):
+                raise ValueError(f"{who}: assign '{assign}': interleave, cross or an int array")
+            if assign == "cross" and self.scenarios < 1:
+                raise ValueError(f"{who}: assign 'cross' needs scenarios >= 1 (the scenario count of the table)")
+            self._explicit = None
+        else:
+            a = np.asarray(assign)
+            if a.shape != (N,) or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f"{who}: an explicit assign has one integer per local env ({N}), got shape {a.shape} {a.dtype}")
+            if a.min() < 0 or a.max() >= K:
+                raise ValueError(f"{who}: assign holds {int(a.min())}..{int(a.max())}, outside [0, {K})")
+            self._explicit = a.astype(np.int32)
+        self.policy_of_env = self.policy_of(np.arange(self.env_id0, self.env_id0 + N, dtype=np.int64))
+        self.ranges = [(0, N)] if ranges is None else [(int(f), int(c)) for f, c in ranges]
+        nxt = 0
+        for f, c in self.ranges:
+            if f != nxt or c < 1:
+                raise ValueError(f"{who}: ranges {self.ranges} do not tile [0, {N}) in order")
+            nxt = f + c
+        if nxt != N:
+            raise ValueError(f"{who}: ranges {self.ranges} do not tile [0, {N}) in order")
+
+    def _policy_rows(self):
+        """Per policy the int64 row tensors of its envs, and the same per range: what the torch twins index with."""
+        t, K = self.torch, len(self.paths)
+        idx = [np.nonzero(self.policy_of_env == k)[0] for k in range(K)]
+        rows = [t.as_tensor(i, dtype=t.int64, device=self.device) for i in idx]
+        range_rows = [[t.as_tensor(i[(i >= f) & (i < f + c)], dtype=t.int64, device=self.device) for i in idx] for f, c in self.ranges]
+        return rows, range_rows
+
+    def policy_of(self, global_env_ids) -> np.ndarray:
+        """The policy index int32 of each global env id (an explicit assignment knows this rank's envs only)."""
+        g = np.asarray(global_env_ids, dtype=np.int64)
+        K = len(self.paths)
+        if self._explicit is not None:
+            loc = g - self.env_id0
+            if loc.size and (loc.min() < 0 or loc.max() >= self.num_envs):
+                raise ValueError(f"{type(self).__name__}.policy_of: an explicit assignment covers env ids {self.env_id0}..{self.env_id0 + self.num_envs - 1}")
+            return self._explicit[loc]
+        return ((g % K) if self.assign == "interleave" else ((g // self.scenarios) % K)).astype(np.int32)
+
+    def _check_range(self, i):
+        if not 0 <= int(i) < len(self.ranges):
+            raise ValueError(f"{type(self).__name__}.get_action_range: range {i} outside 0..{len(self.ranges) - 1}")
+
+
+class PolicyTable(_FleetTable):
     """K actor checkpoints over ONE fleet: env ``g`` (global id) is driven by policy ``policy_of(g)`` for the whole run, and one launch
     of the grouped kernel (``cosim_policy_table_forward``, csrc/cosim_mlp.hip) evaluates all of them -- every env gets the bits
     ``MLPPolicy(file, fused=True)`` gives it.  All policies meet the same terrain, spawn table, scenario table, fall rule and noise
@@ -485,18 +637,8 @@ class PolicyTable:
     def __init__(self, policy_paths, num_envs: int, device=None, assign="interleave", env_id0: int = 0, scenarios: int = 0,
                  ranges=None, names=None, fused: Optional[bool] = None):
         import torch
-        self.torch = torch
-        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-        paths = [str(p) for p in policy_paths]
-        K, N = len(paths), int(num_envs)
-        if K < 1:
-            raise ValueError("PolicyTable: no policy file")
-        if N < 1:
-            raise ValueError(f"PolicyTable: num_envs {N} is not positive")
-        self.paths, self.num_envs, self.env_id0, self.scenarios = paths, N, int(env_id0), int(scenarios)
-        self.names = [os.path.splitext(os.path.basename(p))[0] for p in paths] if names is None else [str(x) for x in names]
-        if len(self.names) != K or len(set(self.names)) != K:
-            raise ValueError(f"PolicyTable: names must be {K} different strings, got {self.names}")
+        self._setup_fleet(policy_paths, num_envs, device, env_id0, scenarios, names)
+        paths, K, N = self.paths, len(self.paths), self.num_envs
         chains, models = [], []
         for p in paths:
             model = read_onnx(p)
@@ -513,29 +655,7 @@ class PolicyTable:
             chains.append(chain)
             models.append(model)
         self.in_dim, self.out_dim = int(chains[0][0][0].shape[1]), int(chains[0][-1][0].shape[0])
-        self.assign = assign if isinstance(assign, str) else "explicit"
-        if isinstance(assign, str):
-            if assign not in ("interleave", "cross"):
-                raise ValueError(f"PolicyTable: assign '{assign}': interleave, cross or an int array")
-            if assign == "cross" and self.scenarios < 1:
-                raise ValueError("PolicyTable: assign 'cross' needs scenarios >= 1 (the scenario count of the table)")
-            self._explicit = None
-        else:
-            a = np.asarray(assign)
-            if a.shape != (N,) or not np.issubdtype(a.dtype, np.integer):
-                raise ValueError(f"PolicyTable: an explicit assign has one integer per local env ({N}), got shape {a.shape} {a.dtype}")
-            if a.min() < 0 or a.max() >= K:
-                raise ValueError(f"PolicyTable: assign holds {int(a.min())}..{int(a.max())}, outside [0, {K})")
-            self._explicit = a.astype(np.int32)
-        self.policy_of_env = self.policy_of(np.arange(self.env_id0, self.env_id0 + N, dtype=np.int64))
-        self.ranges = [(0, N)] if ranges is None else [(int(f), int(c)) for f, c in ranges]
-        nxt = 0
-        for f, c in self.ranges:
-            if f != nxt or c < 1:
-                raise ValueError(f"PolicyTable: ranges {self.ranges} do not tile [0, {N}) in order")
-            nxt = f + c
-        if nxt != N:
-            raise ValueError(f"PolicyTable: ranges {self.ranges} do not tile [0, {N}) in order")
+        self._setup_assign(assign, ranges)
         self._out = torch.zeros((N, self.out_dim), dtype=torch.float32, device=self.device)
         self._handle = None
         if fused is not False and self.device.type == "cuda":
@@ -543,21 +663,8 @@ class PolicyTable:
         elif fused:
             raise ValueError("fused=True needs a GPU device")
         else:
-            idx = [np.nonzero(self.policy_of_env == k)[0] for k in range(K)]
-            self._rows = [torch.as_tensor(i, dtype=torch.int64, device=self.device) for i in idx]
-            self._range_rows = [[torch.as_tensor(i[(i >= f) & (i < f + c)], dtype=torch.int64, device=self.device) for i in idx] for f, c in self.ranges]
+            self._rows, self._range_rows = self._policy_rows()
             self._graphs = [OnnxGraph(m, self.device) for m in models]
-
-    def policy_of(self, global_env_ids) -> np.ndarray:
-        """The policy index int32 of each global env id (an explicit assignment knows this rank's envs only)."""
-        g = np.asarray(global_env_ids, dtype=np.int64)
-        K = len(self.paths)
-        if self._explicit is not None:
-            loc = g - self.env_id0
-            if loc.size and (loc.min() < 0 or loc.max() >= self.num_envs):
-                raise ValueError(f"PolicyTable.policy_of: an explicit assignment covers env ids {self.env_id0}..{self.env_id0 + self.num_envs - 1}")
-            return self._explicit[loc]
-        return ((g % K) if self.assign == "interleave" else ((g // self.scenarios) % K)).astype(np.int32)
 
     def _create(self, chains):
         import ctypes
@@ -631,19 +738,208 @@ class PolicyTable:
     def get_action_range(self, i: int, state, action):
         """Writes the rows of range ``i`` of ``ranges`` into ``action`` (``[N, action_dim]``) from ``state`` (``[N, in_dim]``), both whole-fleet
         contiguous fp32 tensors, on the CURRENT stream and without allocating; the other rows of ``action`` stay as they are."""
-        if not 0 <= int(i) < len(self.ranges):
-            raise ValueError(f"PolicyTable.get_action_range: range {i} outside 0..{len(self.ranges) - 1}")
+        self._check_range(i)
         self._launch(state, action, int(i))
 
 
+class RecurrentPolicyTable(_FleetTable):
+    """K RECURRENT actor checkpoints over one fleet: ``PolicyTable`` for files of ``LSTMPolicy``'s kind (inputs ``(obs, "h_in", "c_in")``,
+    outputs ``(action, h_out, c_out)``; the graph shape ``_recurrent_actor`` recognises).  One launch of the fused actor kernel
+    (``cosim_recurrent_table_forward``, csrc/cosim_mlp.hip) runs encoder, LSTM cell and head of every env's own policy and updates the
+    recurrent state in place -- every env gets the bits ``cosim_mlp_forward`` -> ``cosim_lstm_cell`` -> ``cosim_mlp_forward`` give it.
+
+    The table owns the state: ``h`` and ``c``, ``[N, Hmax]`` with ``Hmax`` the largest hidden size; a policy with hidden size ``H`` uses
+    columns ``0 .. H`` of its rows, the rest stay zero.  ``reset`` / ``state`` / ``load_state`` are ``LSTMPolicy``'s.  ``get_action_range``
+    takes ``done=(terminated, truncated)`` (uint8 ``[N]``): an env with either set starts from a zero state in this very launch, the
+    episode reset of ``Runner.test`` folded into the forward.  Constructor arguments as ``PolicyTable``.  On a non-CUDA device, or with
+    ``fused=False``, each policy's interpreter runs on its own rows against slices of the state: the torch twin.
+
+    Out of scope: tables that mix MLP and recurrent files, GRU cells, stacked or multi-step LSTM nodes, per-episode reassignment."""
+
+    graph_safe = True     # one launch on persistent tensors
+    recurrent = True      # Runner.test_pipelined hands get_action_range the env's done flags
+
+    def __init__(self, policy_paths, num_envs: int, device=None, assign="interleave", env_id0: int = 0, scenarios: int = 0,
+                 ranges=None, names=None, fused: Optional[bool] = None):
+        import torch
+        self._setup_fleet(policy_paths, num_envs, device, env_id0, scenarios, names)
+        paths, N = self.paths, self.num_envs
+        parts, models = [], []
+        for p in paths:
+            model = read_onnx(p)
+            part, why = _recurrent_actor(model)
+            if part is None:
+                raise ValueError(f"RecurrentPolicyTable: {p}: not a recurrent actor: {why}")
+            if parts and part["in_dim"] != parts[0]["in_dim"]:
+                raise ValueError(f"RecurrentPolicyTable: {p}: input width {part['in_dim']} differs from {parts[0]['in_dim']} of {paths[0]}")
+            if parts and part["out_dim"] != parts[0]["out_dim"]:
+                raise ValueError(f"RecurrentPolicyTable: {p}: output width {part['out_dim']} differs from {parts[0]['out_dim']} of {paths[0]}")
+            parts.append(part)
+            models.append(model)
+        self.in_dim, self.out_dim = parts[0]["in_dim"], parts[0]["out_dim"]
+        self.hidden = [part["H"] for part in parts]
+        self._setup_assign(assign, ranges)
+        self.h = torch.zeros((N, max(self.hidden)), dtype=torch.float32, device=self.device)
+        self.c = torch.zeros_like(self.h)
+        self._out = torch.zeros((N, self.out_dim), dtype=torch.float32, device=self.device)
+        self._handle = None
+        if fused is not False and self.device.type == "cuda":
+            self._create(parts)
+        elif fused:
+            raise ValueError("fused=True needs a GPU device")
+        else:
+            self._rows, self._range_rows = self._policy_rows()
+            self._graphs = [OnnxGraph(m, self.device) for m in models]
+
+    def _create(self, parts):
+        import ctypes
+        from .engine import load_library
+        L = load_library()
+        K, ML = len(parts), 3
+        ci, cf, vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+        keep = []
+
+        def host(a):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            keep.append(a)
+            return a.ctypes.data
+
+        def layers(key, first_width):
+            n, dims, act, alpha = (ci * K)(), (ci * (K * (ML + 1)))(), (ci * (K * ML))(), (cf * (K * ML))()
+            w, b = (vp * (K * ML))(), (vp * (K * ML))()
+            for k, part in enumerate(parts):
+                n[k] = len(part[key])
+                dims[k * (ML + 1)] = part[first_width]
+                for li, (wl, bl, a, al) in enumerate(part[key]):
+                    dims[k * (ML + 1) + li + 1] = wl.shape[0]
+                    act[k * ML + li], alpha[k * ML + li] = a, al
+                    w[k * ML + li] = host(wl)
+                    if bl is not None:
+                        b[k * ML + li] = host(bl)
+            return n, dims, act, alpha, w, b
+        enc, head = layers("enc", "in_dim"), layers("head", "H")
+        lstm_in, hidden = (ci * K)(*[p["I"] for p in parts]), (ci * K)(*[p["H"] for p in parts])
+        W, R, B = (vp * K)(*[host(p["W"]) for p in parts]), (vp * K)(*[host(p["R"]) for p in parts]), (vp * K)()
+        for k, part in enumerate(parts):
+            if part["B"] is not None:
+                B[k] = host(part["B"])
+        por = np.ascontiguousarray(self.policy_of_env, dtype=np.int32)
+        rng = np.ascontiguousarray(np.asarray(self.ranges, dtype=np.int32).reshape(-1, 2))
+        handle = vp()
+        with self.torch.cuda.device(self.device):
+            rc = L.cosim_recurrent_table_create(K, *enc, lstm_in, hidden, W, R, B, *head, self.num_envs, por.ctypes.data, len(self.ranges),
+                                                rng.ctypes.data, ctypes.byref(handle))
+        if rc != 0:
+            import re
+            msg = L.cosim_last_error().decode()
+            m = re.search(r": policy (\d+)", msg)              # the validator names the policy it refuses: name its file
+            raise ValueError(f"RecurrentPolicyTable: {self.paths[int(m.group(1))] + ': ' if m else ''}{msg}")
+        self._lib, self._handle = L, handle
+
+    def close(self):
+        if self._handle is not None:
+            self._lib.cosim_recurrent_table_destroy(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def reset(self, mask=None):
+        """Zero the recurrent state (of the masked envs), as ``LSTMPolicy.reset``: a fill, so a non-finite state does not survive."""
+        if mask is None:
+            self.h.zero_(); self.c.zero_()
+        else:
+            done = (self.torch.as_tensor(mask, device=self.device) != 0)[:, None]
+            self.h.masked_fill_(done, 0.0)
+            self.c.masked_fill_(done, 0.0)
+
+    def state(self) -> dict:
+        """The recurrent state ``h`` / ``c`` ``[N, Hmax]`` (copies) for a ``Snapshot``."""
+        return {"h": self.h.clone(), "c": self.c.clone()}
+
+    def load_state(self, state: dict, src=None, mask=None):
+        """As ``LSTMPolicy.load_state``: env ``d`` takes row ``src[d]`` of ``state["h"]`` / ``["c"]`` (``None``: row ``d``); envs with
+        ``mask[d] == 0`` keep theirs.  In place.  A row is only meaningful for an env of the same policy as the one it was taken from."""
+        t = self.torch
+        for name, dst in (("h", self.h), ("c", self.c)):
+            x = t.as_tensor(state[name], dtype=t.float32, device=self.device)
+            if src is not None:
+                x = x[t.as_tensor(src, device=self.device).long()]
+            if tuple(x.shape) != tuple(dst.shape):
+                raise ValueError(f"RecurrentPolicyTable.load_state: {name} has shape {tuple(x.shape)}, expected {tuple(dst.shape)}")
+            if mask is not None:
+                x = t.where((t.as_tensor(mask, device=self.device) != 0)[:, None], x, dst)
+            dst.copy_(x)
+
+    def _launch(self, x, out, i: int, done=None):
+        t = self.torch
+        if x.shape != (self.num_envs, self.in_dim) or out.shape != (self.num_envs, self.out_dim):
+            raise ValueError(f"RecurrentPolicyTable: state {tuple(x.shape)} / action {tuple(out.shape)}, expected ({self.num_envs}, {self.in_dim}) / "
+                             f"({self.num_envs}, {self.out_dim})")
+        if done is not None:
+            for d in done:
+                if d.shape != (self.num_envs,) or d.dtype not in (t.uint8, t.bool) or not d.is_contiguous() or d.device != self.h.device:
+                    raise ValueError(f"RecurrentPolicyTable: done is (terminated, truncated), contiguous uint8 [{self.num_envs}] tensors on the table's device")
+        if self._handle is not None:
+            if not (x.is_cuda and out.is_cuda and x.dtype == t.float32 and out.dtype == t.float32 and x.is_contiguous() and out.is_contiguous()):
+                raise ValueError("RecurrentPolicyTable: state and action must be contiguous fp32 tensors on the table's device")
+            da, db = (None, None) if done is None else (done[0].data_ptr(), done[1].data_ptr())
+            rc = self._lib.cosim_recurrent_table_forward(self._handle, x.data_ptr(), self.h.data_ptr(), self.c.data_ptr(), out.data_ptr(), da, db, i, 1.0,
+                                                         t.cuda.current_stream(self.device).cuda_stream)
+            if rc != 0:
+                raise RuntimeError(self._lib.cosim_last_error().decode())
+            return
+        rows = self._rows if i < 0 else self._range_rows[i]
+        fresh = None if done is None else ((done[0] != 0) | (done[1] != 0))
+        for g, idx, H in zip(self._graphs, rows, self.hidden):
+            if not idx.numel():
+                continue
+            h, c = self.h[idx, :H], self.c[idx, :H]
+            if fresh is not None:
+                h, c = h.masked_fill(fresh[idx, None], 0.0), c.masked_fill(fresh[idx, None], 0.0)
+            action, h_out, c_out = g.run({g.inputs[0]: x[idx], "h_in": h.unsqueeze(0), "c_in": c.unsqueeze(0)})[:3]
+            self.h[idx, :H] = h_out.reshape(-1, H)
+            self.c[idx, :H] = c_out.reshape(-1, H)
+            out[idx] = action.reshape(-1, self.out_dim).clamp(-1.0, 1.0)
+
+    def get_action(self, state):
+        """``[N, action_dim]`` in [-1, 1]: the table's persistent output tensor (the next call overwrites it); ``h`` / ``c`` move one step."""
+        t = self.torch
+        x = t.as_tensor(state, dtype=t.float32, device=self.device).contiguous()
+        self._launch(x, self._out, -1)
+        return self._out
+
+    def get_action_range(self, i: int, state, action, done=None):
+        """One step of the envs of range ``i``: their rows of ``action`` and of ``h`` / ``c`` are written, every other row stays as it is.
+        ``state`` / ``action`` as ``PolicyTable.get_action_range``; on the CURRENT stream, without allocating.  ``done``: see the class."""
+        self._check_range(i)
+        self._launch(state, action, int(i), done)
+
+
+def open_policy_table(policy_paths, **table_args):
+    """A table over several files, its kind taken from the files: ``RecurrentPolicyTable`` if every file has the inputs
+    ``(obs, "h_in", "c_in")``, ``PolicyTable`` if none has; a mix is refused (a table is all one kind)."""
+    paths = [str(p) for p in policy_paths]
+    kinds = [read_onnx(p)["inputs"][1:3] == ["h_in", "c_in"] for p in paths]
+    if kinds and any(k != kinds[0] for k in kinds):
+        other = paths[kinds.index(not kinds[0])]
+        raise ValueError(f"open_policy_table: {other}: {'a recurrent' if not kinds[0] else 'an MLP'} actor among "
+                         f"{'MLP' if not kinds[0] else 'recurrent'} ones ({paths[0]}); a table is all one kind")
+    return (RecurrentPolicyTable if kinds and kinds[0] else PolicyTable)(paths, **table_args)
+
+
 def build_policy(config: dict, policy_path: str = None, num_envs: int = 1, device=None, **table_args):
-    """``core/policy.py:49-53``.  With a list of files in ``config["policy"]["onnx_files"]``: a ``PolicyTable`` over them
-    (``config["policy"]["assign"]``, default interleave; ``table_args``: ``env_id0``, ``scenarios``, ``ranges``, ``names``)."""
+    """``core/policy.py:49-53``.  With a list of files in ``config["policy"]["onnx_files"]``: a table over them -- ``PolicyTable`` or,
+    for recurrent files, ``RecurrentPolicyTable``; the kind is detected from the files (``open_policy_table``), ``use_lstm`` belongs to
+    a single file (``config["policy"]["assign"]``, default interleave; ``table_args``: ``env_id0``, ``scenarios``, ``ranges``, ``names``)."""
     files = config["policy"].get("onnx_files")
     if files:
         if config["policy"].get("use_lstm"):
             raise ValueError("build_policy: a policy table takes MLP actors only (recurrent policies in a table are out of scope)")
-        return PolicyTable(list(files), num_envs=num_envs, device=device, assign=config["policy"].get("assign", "interleave"), **table_args)
+        return open_policy_table(list(files), num_envs=num_envs, device=device, assign=config["policy"].get("assign", "interleave"), **table_args)
     if config["policy"]["use_lstm"]:
         return LSTMPolicy(config, policy_path, num_envs=num_envs, device=device)
     return MLPPolicy(policy_path, device=device)
@@ -702,6 +998,62 @@ def write_onnx(path: str, nodes: List[dict], init: Dict[str, np.ndarray], inputs
     model = _enc(1, 0, 8) + _enc(7, 2, g) + _enc(8, 2, _enc(2, 0, 17))
     with open(path, "wb") as f:
         f.write(model)
+
+
+def write_recurrent_actor(path: str, enc, lstm, head, read: str = "Y_h"):
+    """A recurrent actor of the shape ``_recurrent_actor`` recognises and ``LSTMPolicy`` runs.  ``enc`` / ``head``: layers
+    ``(w [O, I], b [O] or None, op or None, alpha)``; ``lstm``: ``(W [4H, I], R [4H, H], B [8H] or None)``; ``read``: the LSTM output
+    the head takes, ``"Y_h"`` or ``"Y"``."""
+    nodes, init = [], {}
+
+    def chain(layers, x, tag, last_name=None):
+        for li, (w, b, op, alpha) in enumerate(layers):
+            init[f"{tag}w{li}"] = np.asarray(w, np.float32)
+            ins = [x, f"{tag}w{li}"]
+            if b is not None:
+                init[f"{tag}b{li}"] = np.asarray(b, np.float32)
+                ins.append(f"{tag}b{li}")
+            last = last_name is not None and li == len(layers) - 1
+            lin = last_name if last and op is None else f"{tag}lin{li}"
+            nodes.append({"op": "Gemm", "inputs": ins, "outputs": [lin], "attrs": {"transB": 1}})
+            x = lin
+            if op is not None:
+                x = last_name if last else f"{tag}a{li}"
+                nodes.append({"op": op, "inputs": [lin], "outputs": [x], "attrs": {"alpha": float(alpha)} if op in ("Elu", "LeakyRelu") else {}})
+        return x
+    x = chain(enc, "obs", "e")
+    W, R, B = lstm
+    H = R.shape[1]
+    init["W"], init["R"] = np.asarray(W, np.float32)[None], np.asarray(R, np.float32)[None]
+    if B is not None:
+        init["B"] = np.asarray(B, np.float32)[None]
+    nodes.append({"op": "Unsqueeze", "inputs": [x], "outputs": ["x3"], "attrs": {"axes": [0]}})
+    nodes.append({"op": "LSTM", "inputs": ["x3", "W", "R", "B" if B is not None else "", "", "h_in", "c_in"], "outputs": ["Y", "h_out", "c_out"],
+                  "attrs": {"hidden_size": int(H)}})
+    nodes.append({"op": "Squeeze", "inputs": ["Y" if read == "Y" else "h_out"], "outputs": ["hs"], "attrs": {"axes": [0, 1] if read == "Y" else [0]}})
+    chain(head, "hs", "h", last_name="actions")
+    write_onnx(path, nodes, init, ["obs", "h_in", "c_in"], ["actions", "h_out", "c_out"])
+
+
+def write_random_lstm(path: str, state_dim: int, action_dim: int, hidden: int = 256, encoder=(), head=(128,), seed: int = 0,
+                      activation: str = "Elu", bias_scale: float = 0.0):
+    """A random-weight recurrent actor (``encoder`` widths -> LSTM(``hidden``) -> ``head`` widths -> action): the recurrent
+    counterpart of ``write_random_mlp``.  Weights N(0, 1 / fan_in); biases ``bias_scale * standard_normal`` (0: none but zeros)."""
+    rng = np.random.default_rng([seed, 2])
+
+    def layers(dims, act_last):
+        out = []
+        for li in range(len(dims) - 1):
+            w = (rng.standard_normal((dims[li + 1], dims[li])) / np.sqrt(dims[li])).astype(np.float32)
+            b = (bias_scale * rng.standard_normal(dims[li + 1])).astype(np.float32)
+            out.append((w, b, activation if (act_last or li < len(dims) - 2) else None, 1.0))
+        return out
+    enc = layers([state_dim, *encoder], True)
+    I = encoder[-1] if encoder else state_dim
+    W = (rng.standard_normal((4 * hidden, I)) / np.sqrt(I)).astype(np.float32)
+    R = (rng.standard_normal((4 * hidden, hidden)) / np.sqrt(hidden)).astype(np.float32)
+    B = (bias_scale * rng.standard_normal(8 * hidden)).astype(np.float32)
+    write_recurrent_actor(path, enc, (W, R, B), layers([hidden, *head, action_dim], False))
 
 
 def write_random_mlp(path: str, state_dim: int, action_dim: int, hidden=(256, 128), seed: int = 0, activation: str = "Elu",

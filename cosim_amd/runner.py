@@ -128,7 +128,9 @@ class Runner:
         built with ``ranges=S`` (S > 1), and each range of envs runs its own chain policy(range) -> step(range) -> reporter(range) on
         the range's own stream (``BatchedEnv.range_streams``).  A range's next control step then fills the tail of the others'
         launches, as in the bench; the policy only ever needs the states of its own range.  Needs an auto-reset env, a stateless
-        device policy with ``get_action_into`` (``policy.MLPPolicy``) and a ``FleetReporter`` (or none).  The user command and a held
+        device policy with ``get_action_into`` (``policy.MLPPolicy``) or a policy table (``policy.PolicyTable``; a
+        ``policy.RecurrentPolicyTable`` keeps its state per env on the device and is handed each range's done flags, so an episode's
+        reset happens in the range's next forward) and a ``FleetReporter`` (or none).  The user command and a held
         push are read before each step like in ``test`` (changing them joins the ranges first).  ``inflight``: how many steps the host
         may run ahead of each range (deep queues step slower)."""
         env, t = self.env, self.env.torch
@@ -146,6 +148,11 @@ class Runner:
         if self.reporter is not None and not hasattr(self.reporter, "write_info_range"):
             raise ValueError("test_pipelined: the reporter must reduce per range (reporter.FleetReporter)")
         env.reset()
+        # a policy.RecurrentPolicyTable: it starts from a zero state, and from then on a range's episode resets ride on its own stream,
+        # folded into the range's next forward by the done flags its last step wrote
+        recurrent = by_range and getattr(self.policy, "recurrent", False)
+        if recurrent:
+            self.policy.reset()
         episodes0 = env.solver_stats()["episodes_ended"]
         env.receive_user_command(self.user_command)
         last_cmd = self.user_command.copy()
@@ -171,7 +178,9 @@ class Runner:
                 if inflight > 0 and steps >= inflight:
                     ring[i][steps % inflight].synchronize()
                 with t.cuda.stream(env.range_streams[i]):
-                    if by_range:
+                    if recurrent:
+                        self.policy.get_action_range(i, env.state, action, done=(env.terminated, env.truncated))  # tester.py:70, :57-60
+                    elif by_range:
                         self.policy.get_action_range(i, env.state, action)                                        # tester.py:70
                     else:
                         self.policy.get_action_into(env.state[first:first + count], action[first:first + count])

@@ -556,6 +556,40 @@ int cosim_policy_table_destroy(cosim_policy_table_t* table);
 int cosim_lstm_cell(const float* x_dev, const float* h_dev, const float* c_dev, int n, int in_dim, int hidden, const float* w_dev,
                     const float* r_dev, const float* b_dev, float* h_out_dev, float* c_out_dev, void* stream);
 
+/* Recurrent policy table: K recurrent actors (LSTM checkpoints) over one fleet in ONE launch.  A policy is 0..3 encoder layers
+ * (Gemm + activation, as cosim_mlp_forward), one LSTM cell (as cosim_lstm_cell) and 1..3 head layers; the hidden size may differ
+ * between policies.  Stateless with respect to cosim_engine_t; the recurrent state belongs to the caller.
+ *
+ * create: HOST arrays in, an opaque handle out.  n_enc[K] (0..3); enc_dims[K][4] (entry 0: the observation width, entries 0..n_enc
+ * used); enc_act / enc_alpha [K][3]; enc_w_host / enc_b_host [K][3] host pointers (enc_b_host, or an entry, NULL: no bias).
+ * lstm_in[K] / hidden[K]: the cell's input width (= the encoder's last width, the observation width without an encoder) and hidden
+ * size H; lstm_w_host[K] [4H, I], lstm_r_host[K] [4H, H], lstm_b_host[K] [8H] (the array or an entry NULL: no bias).  n_head[K]
+ * (1..3); head_dims[K][4] (entry 0 = H, the last used entry the action width); head_act / head_alpha / head_w_host / head_b_host as
+ * the encoder's.  Widths are 1..512, lstm_in + hidden <= 1200, every policy has policy 0's observation and action width.
+ * policy_of_row / ranges as cosim_policy_table_create.  The call validates everything (COSIM_EINVAL with the reason in
+ * cosim_last_error; nothing reaches the device), among it the LDS a workgroup needs -- 4 * 32 * (2 ld_m + ld_x) + 256 bytes with
+ * ld_m = (widest encoder / head width or H of any policy) | 1 and ld_x = (largest lstm_in + hidden) | 1 -- against what the current
+ * device allows, naming the policy and both byte counts; packs every matrix into one image (each begins at a multiple of 4 words),
+ * builds the tiles and uploads them to the CURRENT device.
+ * forward: for the rows of range `range` (-1: all) one step of each row's policy: out_dev[i] = clip(head(h')) with
+ * (h', c') = cell(encoder(x_dev[i]), h, c).  h_dev / c_dev are [n, Hmax] (Hmax: the largest hidden size; a policy with hidden size H
+ * uses columns 0 .. H of its rows, the others are never touched) and are updated IN PLACE.  done_a_dev / done_b_dev: [n] bytes or
+ * NULL (the env's terminated / truncated flags); a row with either byte non-zero reads h = c = 0 -- a select, so a non-finite state
+ * does not survive.  Rows outside the range are neither read nor written.  Every env gets the bits of cosim_mlp_forward (encoder,
+ * clip 0) -> cosim_lstm_cell -> cosim_mlp_forward (head, clip) of its own policy.  Refuses a null x / h / c / out, a range index out
+ * of bounds and a current device other than the table's.  No allocation, no host read, no synchronisation: it can be captured.
+ * Out of scope: tables that mix MLP and recurrent actors, GRU cells, stacked or multi-step LSTM nodes. */
+typedef struct cosim_recurrent_table cosim_recurrent_table_t;
+int cosim_recurrent_table_create(int n_policies, const int* n_enc, const int* enc_dims, const int* enc_act, const float* enc_alpha,
+                                 const float* const* enc_w_host, const float* const* enc_b_host, const int* lstm_in, const int* hidden,
+                                 const float* const* lstm_w_host, const float* const* lstm_r_host, const float* const* lstm_b_host,
+                                 const int* n_head, const int* head_dims, const int* head_act, const float* head_alpha,
+                                 const float* const* head_w_host, const float* const* head_b_host, int n, const int* policy_of_row,
+                                 int n_ranges, const int* ranges, cosim_recurrent_table_t** out);
+int cosim_recurrent_table_forward(cosim_recurrent_table_t* table, const float* x_dev, float* h_dev, float* c_dev, float* out_dev,
+                                  const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range, float clip, void* stream);
+int cosim_recurrent_table_destroy(cosim_recurrent_table_t* table);
+
 /* Reporter side (reference core/reporter.py:210-218 write_info, :429-442, :506-508): fleet statistics of one step's info in one
  * launch.  acc_dev is double[3][K], K = 4 + nu + ncmd <= 32: count, sum, sum of squares of info[:, 0:4], |info[:, 4:4+nu]| (torque)
  * and |cmd[:, i] - info[:, 1 + i]| for i < ncmd <= 3 (command tracking); cmd_dev is [N, cmd_stride]. */
