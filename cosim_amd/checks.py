@@ -154,9 +154,10 @@ class Verdicts:
 
     def by_policy(self, table, scenario: bool = False) -> dict:
         """``summary()`` per policy of a ``policy.PolicyTable`` (or of an int array with the policy of each local env), keyed by the
-        policy's name, with ``scenario`` by ``(name, scenario row)``: as ``EpisodeLedger.by_policy``."""
+        policy's name, with ``scenario`` by ``(name, scenario row)``: as ``EpisodeLedger.by_policy``, a rotating table included (a
+        record belongs to the policy of its episode ordinal)."""
         from .ledger import policy_of_records
-        pol, names = policy_of_records(table, self.env, self.env_id0)
+        pol, names = policy_of_records(table, self.env, self.env_id0, self.episode)
         m = self.ended()
         out = {}
         for k in np.unique(pol[m]):

@@ -20,9 +20,9 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     random:   {sensor_noise: low, action_delay_prob: 0.05, ...}        # overrides of the GUI defaults (config.make_config)
     observation: {stack_size: 3, ...}                                   # likewise
     policy:   {kind: sinusoid | random-mlp | onnx, onnx_file: actor.onnx, use_lstm: false, h_in_dim: 256, c_in_dim: 256}
-    policy:   {onnx_files: [a.onnx, b.onnx], assign: interleave | cross, names: [base, tuned]}   # a policy table (policy.PolicyTable): every env
+    policy:   {onnx_files: [a.onnx, b.onnx], assign: interleave | cross, names: [base, tuned], rotate: 1}   # a policy table (policy.PolicyTable): every env
                                                                        # driven by one of the files; same as --policy a.onnx b.onnx
-                                                                       # --policy-assign --policy-names; the report gets episodes.by_policy.
+                                                                       # --policy-assign --policy-names --policy-rotate; the report gets episodes.by_policy.
                                                                        # Files with h_in / c_in inputs make a recurrent table
                                                                        # (policy.RecurrentPolicyTable): the kind is detected from the files,
                                                                        # all of one kind; use_lstm belongs to a single onnx_file
@@ -68,6 +68,9 @@ def main(argv=None) -> int:
                          "(MLP actors, or recurrent ones with h_in / c_in inputs: the kind is detected from the files, all of one kind)")
     ap.add_argument("--policy-assign", choices=["interleave", "cross"], default=None,
                     help="several --policy files: env g runs policy g mod K (interleave, the default) or (g // S) mod K with S scenarios (cross)")
+    ap.add_argument("--policy-rotate", type=int, default=None, metavar="EVERY",
+                    help="several --policy files: every env moves to the next file after EVERY of its episodes (a paired design: every robot meets every "
+                         "checkpoint); episodes.by_policy attributes each episode to the file that drove it")
     ap.add_argument("--policy-names", nargs="+", default=None, metavar="NAME", help="several --policy files: their names in the report (default: the file stems)")
     ap.add_argument("--lstm", action="store_true", help="the ONNX file is an LSTM policy with h_in / c_in inputs (a single --policy file; several recurrent files need no flag)")
     ap.add_argument("--hidden-dim", type=int, default=256, help="h_in_dim = c_in_dim of an LSTM policy")
@@ -153,7 +156,7 @@ def main(argv=None) -> int:
     args.seed = int(pick(args.seed, s_eng.get("seed"), 1234))
     args.steps = int(pick(args.steps, sess.get("steps"), 500))
     kind = s_pol.get("kind")
-    unknown = set(s_pol) - {"kind", "onnx_file", "onnx_files", "assign", "names", "use_lstm", "h_in_dim", "c_in_dim"}
+    unknown = set(s_pol) - {"kind", "onnx_file", "onnx_files", "assign", "rotate", "names", "use_lstm", "h_in_dim", "c_in_dim"}
     if unknown:
         ap.error(f"--config: unknown keys policy.{sorted(unknown)}")
     # one policy, or several ONNX files: a policy table (policy.PolicyTable)
@@ -165,7 +168,10 @@ def main(argv=None) -> int:
     args.policy = pick(args.policy, s_pol.get("onnx_file") if kind == "onnx" else kind, "sinusoid")
     policy_assign = pick(args.policy_assign, s_pol.get("assign"), "interleave")
     policy_names = args.policy_names if args.policy_names is not None else s_pol.get("names")
+    policy_rotate = pick(args.policy_rotate, s_pol.get("rotate"), None)
     if policy_files:
+        if policy_rotate is not None and (isinstance(policy_rotate, bool) or not isinstance(policy_rotate, int) or policy_rotate < 1):
+            ap.error(f"--policy-rotate / policy.rotate: {policy_rotate!r} is not an integer >= 1")
         if args.lstm or s_pol.get("use_lstm", False):
             ap.error("--policy with several files: a policy table takes MLP actors only (no --lstm)")
         if any(p in ("sinusoid", "random-mlp") for p in policy_files):
@@ -176,6 +182,8 @@ def main(argv=None) -> int:
             ap.error("--policy-names: one name per --policy file")
     elif args.policy_assign is not None or args.policy_names is not None:
         ap.error("--policy-assign / --policy-names need several --policy files")
+    elif policy_rotate is not None:
+        ap.error("--policy-rotate needs several --policy files")
     args.lstm = bool(args.lstm or s_pol.get("use_lstm", False))
     if s_pol.get("h_in_dim") is not None:
         args.hidden_dim = int(s_pol["h_in_dim"])
@@ -306,7 +314,7 @@ def main(argv=None) -> int:
         if policy_assign == "cross" and n_scn < 1:
             ap.error("--policy-assign cross needs --scenarios")
         try:
-            policy = build_policy({"policy": {"use_lstm": False, "onnx_files": policy_files, "assign": policy_assign}}, num_envs=env.num_envs,
+            policy = build_policy({"policy": {"use_lstm": False, "onnx_files": policy_files, "assign": policy_assign, "rotate": policy_rotate}}, num_envs=env.num_envs,
                                   device=env.device, env_id0=lo, scenarios=n_scn, ranges=env.range_list, names=policy_names)
         except ValueError as e:
             ap.error(str(e))
@@ -398,6 +406,7 @@ def main(argv=None) -> int:
                           "env_steps_per_s_this_rank": env.num_envs * n / dt, "episodes_ended": out["episodes_ended"],
                           "metrics": {k: round(v["mean"], 5) for k, v in out["metrics"].items()},
                           **({"snapshot": used} if used else {}),
+                          **({"policy_table": f"files={len(policy_files)} assign={policy_assign} rotate={policy_rotate}"} if policy_files and policy_rotate else {}),
                           **({"episodes": {k: out["episodes"][k] for k in ("episodes", "terminated", "truncated", "non_finite", "lost", "length") +
                                            (("fell", "fell_tilt", "fell_height", "fell_contact") if env.fall_rule is not None else ())}}
                              if "terminated" in out.get("episodes", {}) else {}),

@@ -865,25 +865,137 @@ static const char* observers_info_msg(const cosim_engine* e) {
   return e->led_slots > 0 ? LEDGER_INFO_MSG : e->ft_frames > 0 ? FTRACE_INFO_MSG : e->chk.n_scn > 0 ? CHECKS_INFO_MSG : e->cur.n_scn > 0 ? CURVES_INFO_MSG : nullptr;
 }
 
+// what cosim_policy_table_rotate adds to a table (cosim_poltab.h, poltab_regroup_kernel): `every` 0 means not armed
+struct PolRotate {
+  int every = 0;
+  int32_t* d_base = nullptr;      // [n] create's policy_of_row
+  PolRange* d_ranges = nullptr;   // [n_ranges]
+  int32_t* d_ntiles = nullptr;    // [n_ranges] the tiles each range holds now
+};
+
 // what cosim_policy_table_create hands out: the device copies of a checked table and the launch shape of every range
 struct cosim_policy_table {
-  int n = 0, device = 0, ld = 0, n_tiles = 0;
+  int n = 0, device = 0, ld = 0, n_tiles = 0, K = 0;
   float* d_image = nullptr;
   PolDesc* d_desc = nullptr;
   int32_t* d_rows = nullptr;
   PolTile* d_tiles = nullptr;
-  std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count)
+  std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count); armed: (tile_first, capacity)
+  std::vector<int32_t> por, ranges; // create's policy_of_row [n] and ranges [n_ranges][2]
+  PolRotate rot;
 };
 
 // what cosim_recurrent_table_create hands out: as above, with the launch's two leading dimensions and the state tensors' row stride
 struct cosim_recurrent_table {
-  int n = 0, device = 0, ld_m = 0, ld_x = 0, hmax = 0, n_tiles = 0;
+  int n = 0, device = 0, ld_m = 0, ld_x = 0, hmax = 0, n_tiles = 0, K = 0;
   float* d_image = nullptr;
   RecDesc* d_desc = nullptr;
   int32_t* d_rows = nullptr;
   PolTile* d_tiles = nullptr;
-  std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count)
+  std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count); armed: (tile_first, capacity)
+  std::vector<int32_t> por, ranges;
+  PolRotate rot;
 };
+
+// ---- rotation, the same for both kinds of table (Table: one of the two structs above; fn: the entry point's name for the messages)
+static void rotate_free(PolRotate& r) {
+  (void)hipFree(r.d_base); (void)hipFree(r.d_ranges); (void)hipFree(r.d_ntiles);
+  r = PolRotate();
+}
+
+// Arms a table: keeps create's assignment on the device as the base, lays the static lists out again with every range's span of
+// tiles as wide as policy_tile_capacity (padding: count 0) and swaps the tile buffer for that one.  The table is unchanged on failure.
+template <class Table>
+static int table_rotate(Table* p, int every, const std::string& fn) {
+  if (!p) return fail(COSIM_EINVAL, fn + ": null argument");
+  if (every < 1) return fail(COSIM_EINVAL, fn + ": every " + std::to_string(every) + " is below 1");
+  if (p->rot.every) return fail(COSIM_EINVAL, fn + ": the table already rotates (every " + std::to_string(p->rot.every) + ")");
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != p->device)
+    return fail(COSIM_EINVAL, fn + ": the table lives on device " + std::to_string(p->device) + ", the current device is " + std::to_string(dev));
+  const int n_ranges = (int)p->ranges.size() / 2;
+  const PolTiles tl = build_policy_tiles(p->por.data(), p->K, p->ranges.data(), n_ranges);
+  std::vector<PolRange> rg(n_ranges);
+  std::vector<int32_t> nt(n_ranges), span(2 * n_ranges);
+  int cap_total = 0;
+  for (int i = 0; i < n_ranges; i++) {
+    rg[i] = {p->ranges[2 * i], p->ranges[2 * i + 1], cap_total, policy_tile_capacity(p->ranges[2 * i + 1], p->K)};
+    nt[i] = tl.tile_span[2 * i + 1];
+    span[2 * i] = cap_total; span[2 * i + 1] = rg[i].tile_cap;
+    cap_total += rg[i].tile_cap;
+  }
+  std::vector<PolTile> tiles((size_t)cap_total, PolTile{0, 0, 0, 0});
+  for (int i = 0; i < n_ranges; i++)
+    for (int j = 0; j < nt[i]; j++) tiles[(size_t)rg[i].tile_first + j] = tl.tiles[(size_t)tl.tile_span[2 * i] + j];
+  PolRotate r;
+  PolTile* d_tiles = nullptr;
+  auto upload = [&]() -> int {
+    HIP_TRY(hipMalloc(&r.d_base, p->por.size() * 4)); HIP_TRY(hipMalloc(&r.d_ranges, rg.size() * sizeof(PolRange)));
+    HIP_TRY(hipMalloc(&r.d_ntiles, nt.size() * 4)); HIP_TRY(hipMalloc(&d_tiles, tiles.size() * sizeof(PolTile)));
+    HIP_TRY(hipMemcpy(r.d_base, p->por.data(), p->por.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.d_ranges, rg.data(), rg.size() * sizeof(PolRange), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(r.d_ntiles, nt.data(), nt.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(PolTile), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(p->d_rows, tl.rows.data(), tl.rows.size() * 4, hipMemcpyHostToDevice));
+    return COSIM_OK;
+  };
+  const int rc = upload();
+  if (rc) { rotate_free(r); (void)hipFree(d_tiles); return rc; }
+  (void)hipFree(p->d_tiles);
+  p->d_tiles = d_tiles; p->n_tiles = cap_total; p->tile_span = span;
+  r.every = every;
+  p->rot = r;
+  return COSIM_OK;
+}
+
+// What the plain and the rotating forward of both tables check (pointers: the entry point's own arrays are all there).  0 or the error.
+template <class Table>
+static int table_forward_checks(Table* p, bool pointers, bool rotating, const int32_t* episode_dev, int range, const char* fn) {
+  const auto who = [fn]() { return std::string(fn); };   // a message is only put together where a call is refused
+  if (!p || !pointers || (rotating && !episode_dev)) return fail(COSIM_EINVAL, who() + ": null argument");
+  if (rotating && !p->rot.every) return fail(COSIM_EINVAL, who() + ": the table does not rotate (cosim_*_table_rotate arms it)");
+  if (!rotating && p->rot.every)
+    return fail(COSIM_EINVAL, who() + ": the table rotates (every " + std::to_string(p->rot.every) + "): its lists change per step, use " + who() + "_rotating");
+  const int n_ranges = (int)p->tile_span.size() / 2;
+  if (range < -1 || range >= n_ranges)
+    return fail(COSIM_EINVAL, who() + ": range " + std::to_string(range) + " outside -1.." + std::to_string(n_ranges - 1));
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != p->device)
+    return fail(COSIM_EINVAL, who() + ": the table lives on device " + std::to_string(p->device) + ", the current device is " + std::to_string(dev));
+  return COSIM_OK;
+}
+
+template <class Table>
+static int table_regroup(Table* p, int32_t* episode_dev, int32_t* policy_now_dev, const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range,
+                         hipStream_t s) {
+  PolRegroupArgs g;
+  g.base = p->rot.d_base; g.episode = episode_dev; g.policy_now = policy_now_dev; g.done_a = done_a_dev; g.done_b = done_b_dev;
+  g.ranges = p->rot.d_ranges; g.rows = p->d_rows; g.tiles = p->d_tiles; g.n_tiles = p->rot.d_ntiles;
+  g.range_first = range < 0 ? 0 : range; g.K = p->K; g.every = p->rot.every;
+  hipLaunchKernelGGL(poltab_regroup_kernel, dim3(range < 0 ? (int)p->tile_span.size() / 2 : 1), dim3(RG_THREADS), 0, s, g);
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
+// one range's lists as they stand, after everything queued on the device: rows_host [count of the range], tiles_host [its capacity][4]
+template <class Table>
+static int table_lists(Table* p, int range, int* rows_host, int* tiles_host, int* n_tiles_out, const std::string& fn) {
+  if (!p || !rows_host || !tiles_host || !n_tiles_out) return fail(COSIM_EINVAL, fn + ": null argument");
+  const int n_ranges = (int)p->tile_span.size() / 2;
+  if (range < 0 || range >= n_ranges) return fail(COSIM_EINVAL, fn + ": range " + std::to_string(range) + " outside 0.." + std::to_string(n_ranges - 1));
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev != p->device)
+    return fail(COSIM_EINVAL, fn + ": the table lives on device " + std::to_string(p->device) + ", the current device is " + std::to_string(dev));
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(rows_host, p->d_rows + p->ranges[2 * range], (size_t)p->ranges[2 * range + 1] * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tiles_host, p->d_tiles + p->tile_span[2 * range], (size_t)p->tile_span[2 * range + 1] * sizeof(PolTile), hipMemcpyDeviceToHost));
+  if (p->rot.every) HIP_TRY(hipMemcpy(n_tiles_out, p->rot.d_ntiles + range, 4, hipMemcpyDeviceToHost));
+  else *n_tiles_out = p->tile_span[2 * range + 1];
+  return COSIM_OK;
+}
 
 extern "C" {
 
@@ -933,7 +1045,8 @@ int cosim_policy_table_create(int n_policies, const int* n_layers, const int* di
   const PolImage im = pack_policy_image(raw);
   const PolTiles tl = build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges);
   cosim_policy_table* p = new cosim_policy_table;
-  p->n = n; p->ld = shape.maxd | 1; p->n_tiles = (int)tl.tiles.size(); p->tile_span = tl.tile_span;
+  p->n = n; p->ld = shape.maxd | 1; p->n_tiles = (int)tl.tiles.size(); p->tile_span = tl.tile_span; p->K = n_policies;
+  p->por.assign(policy_of_row, policy_of_row + n); p->ranges.assign(ranges, ranges + 2 * n_ranges);
   const size_t lds = (size_t)2 * 32 * p->ld * sizeof(float);
   static size_t lds_allowed[64] = {0};   // per device, as cosim_mlp_forward
   auto upload = [&]() -> int {
@@ -959,27 +1072,40 @@ int cosim_policy_table_create(int n_policies, const int* n_layers, const int* di
 
 // range: an index into the ranges given to create, or -1 for all of them.  No allocation, no host read of device memory and no
 // synchronisation: the launch can be captured in a graph.
-int cosim_policy_table_forward(cosim_policy_table* p, const float* x_dev, float* out_dev, int range, float clip, void* stream) {
-  if (!p || !x_dev || !out_dev) return fail(COSIM_EINVAL, "cosim_policy_table_forward: null argument");
-  const int n_ranges = (int)p->tile_span.size() / 2;
-  if (range < -1 || range >= n_ranges)
-    return fail(COSIM_EINVAL, "cosim_policy_table_forward: range " + std::to_string(range) + " outside -1.." + std::to_string(n_ranges - 1));
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev != p->device)
-    return fail(COSIM_EINVAL, "cosim_policy_table_forward: the table lives on device " + std::to_string(p->device) + ", the current device is " + std::to_string(dev));
+static int policy_table_launch(cosim_policy_table* p, const float* x_dev, float* out_dev, int range, float clip, hipStream_t s) {
   PolTabArgs a;
   a.x = x_dev; a.out = out_dev; a.image = p->d_image; a.desc = p->d_desc; a.rows = p->d_rows; a.tiles = p->d_tiles;
   a.tile_first = range < 0 ? 0 : p->tile_span[2 * range]; a.ld = p->ld; a.clip = clip;
   const int tile_count = range < 0 ? p->n_tiles : p->tile_span[2 * range + 1];
-  hipLaunchKernelGGL(mlp_grouped_kernel, dim3(tile_count), dim3(256), (size_t)2 * 32 * p->ld * sizeof(float), (hipStream_t)stream, a);
+  hipLaunchKernelGGL(mlp_grouped_kernel, dim3(tile_count), dim3(256), (size_t)2 * 32 * p->ld * sizeof(float), s, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
+}
+
+int cosim_policy_table_forward(cosim_policy_table* p, const float* x_dev, float* out_dev, int range, float clip, void* stream) {
+  RC_TRY(table_forward_checks(p, x_dev && out_dev, false, nullptr, range, "cosim_policy_table_forward"));
+  return policy_table_launch(p, x_dev, out_dev, range, clip, (hipStream_t)stream);
+}
+
+// Rotation (cosim_poltab.h): arm once, then every evaluation is the regroup launch and the grouped launch over the capacity, both
+// with constant grids -- no allocation, no host read, no synchronisation, so the pair can be captured.
+int cosim_policy_table_rotate(cosim_policy_table* p, int every) { return table_rotate(p, every, "cosim_policy_table_rotate"); }
+
+int cosim_policy_table_forward_rotating(cosim_policy_table* p, const float* x_dev, float* out_dev, int32_t* episode_dev, int32_t* policy_now_dev,
+                                        const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range, float clip, void* stream) {
+  RC_TRY(table_forward_checks(p, x_dev && out_dev, true, episode_dev, range, "cosim_policy_table_forward_rotating"));
+  RC_TRY(table_regroup(p, episode_dev, policy_now_dev, done_a_dev, done_b_dev, range, (hipStream_t)stream));
+  return policy_table_launch(p, x_dev, out_dev, range, clip, (hipStream_t)stream);
+}
+
+int cosim_policy_table_lists(cosim_policy_table* p, int range, int* rows_host, int* tiles_host, int* n_tiles_out) {
+  return table_lists(p, range, rows_host, tiles_host, n_tiles_out, "cosim_policy_table_lists");
 }
 
 int cosim_policy_table_destroy(cosim_policy_table* p) {
   if (!p) return COSIM_OK;
   (void)hipFree(p->d_image); (void)hipFree(p->d_desc); (void)hipFree(p->d_rows); (void)hipFree(p->d_tiles);
+  rotate_free(p->rot);
   delete p;
   return COSIM_OK;
 }
@@ -1006,7 +1132,8 @@ int cosim_recurrent_table_create(int n_policies, const int* n_enc, const int* en
   const PolTiles tl = build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges);
   cosim_recurrent_table* p = new cosim_recurrent_table;
   p->n = n; p->device = dev; p->ld_m = shape.ld_m; p->ld_x = shape.ld_x; p->hmax = shape.hmax;
-  p->n_tiles = (int)tl.tiles.size(); p->tile_span = tl.tile_span;
+  p->n_tiles = (int)tl.tiles.size(); p->tile_span = tl.tile_span; p->K = n_policies;
+  p->por.assign(policy_of_row, policy_of_row + n); p->ranges.assign(ranges, ranges + 2 * n_ranges);
   const size_t lds = (size_t)rec_lds_dynamic(p->ld_m, p->ld_x);
   static size_t lds_allowed[64] = {0};   // per device, as cosim_mlp_forward
   auto upload = [&]() -> int {
@@ -1030,29 +1157,44 @@ int cosim_recurrent_table_create(int n_policies, const int* n_enc, const int* en
 
 // h_dev / c_dev: the table's state, [n, hmax] with hmax the widest hidden size, updated in place.  done_a_dev / done_b_dev: [n] bytes
 // or null; a row with either set starts from a zero state.  No allocation, no host read of device memory and no synchronisation.
-int cosim_recurrent_table_forward(cosim_recurrent_table* p, const float* x_dev, float* h_dev, float* c_dev, float* out_dev,
-                                  const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range, float clip, void* stream) {
-  if (!p || !x_dev || !h_dev || !c_dev || !out_dev) return fail(COSIM_EINVAL, "cosim_recurrent_table_forward: null argument");
-  const int n_ranges = (int)p->tile_span.size() / 2;
-  if (range < -1 || range >= n_ranges)
-    return fail(COSIM_EINVAL, "cosim_recurrent_table_forward: range " + std::to_string(range) + " outside -1.." + std::to_string(n_ranges - 1));
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev != p->device)
-    return fail(COSIM_EINVAL, "cosim_recurrent_table_forward: the table lives on device " + std::to_string(p->device) + ", the current device is " + std::to_string(dev));
+static int recurrent_table_launch(cosim_recurrent_table* p, const float* x_dev, float* h_dev, float* c_dev, float* out_dev, const uint8_t* done_a_dev,
+                                  const uint8_t* done_b_dev, int range, float clip, hipStream_t s) {
   RecTabArgs a;
   a.x = x_dev; a.h = h_dev; a.c = c_dev; a.out = out_dev; a.done_a = done_a_dev; a.done_b = done_b_dev;
   a.image = p->d_image; a.desc = p->d_desc; a.rows = p->d_rows; a.tiles = p->d_tiles;
   a.tile_first = range < 0 ? 0 : p->tile_span[2 * range]; a.ld_m = p->ld_m; a.ld_x = p->ld_x; a.hmax = p->hmax; a.clip = clip;
   const int tile_count = range < 0 ? p->n_tiles : p->tile_span[2 * range + 1];
-  hipLaunchKernelGGL(lstm_actor_grouped_kernel, dim3(tile_count), dim3(256), (size_t)rec_lds_dynamic(p->ld_m, p->ld_x), (hipStream_t)stream, a);
+  hipLaunchKernelGGL(lstm_actor_grouped_kernel, dim3(tile_count), dim3(256), (size_t)rec_lds_dynamic(p->ld_m, p->ld_x), s, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
+}
+
+int cosim_recurrent_table_forward(cosim_recurrent_table* p, const float* x_dev, float* h_dev, float* c_dev, float* out_dev,
+                                  const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range, float clip, void* stream) {
+  RC_TRY(table_forward_checks(p, x_dev && h_dev && c_dev && out_dev, false, nullptr, range, "cosim_recurrent_table_forward"));
+  return recurrent_table_launch(p, x_dev, h_dev, c_dev, out_dev, done_a_dev, done_b_dev, range, clip, (hipStream_t)stream);
+}
+
+// Rotation, as the MLP table's.  The done bytes do both jobs: the regroup launch counts the ended episode and moves the row to its
+// next policy, the actor launch behind it starts that policy from h = c = 0.
+int cosim_recurrent_table_rotate(cosim_recurrent_table* p, int every) { return table_rotate(p, every, "cosim_recurrent_table_rotate"); }
+
+int cosim_recurrent_table_forward_rotating(cosim_recurrent_table* p, const float* x_dev, float* h_dev, float* c_dev, float* out_dev,
+                                           int32_t* episode_dev, int32_t* policy_now_dev, const uint8_t* done_a_dev, const uint8_t* done_b_dev,
+                                           int range, float clip, void* stream) {
+  RC_TRY(table_forward_checks(p, x_dev && h_dev && c_dev && out_dev, true, episode_dev, range, "cosim_recurrent_table_forward_rotating"));
+  RC_TRY(table_regroup(p, episode_dev, policy_now_dev, done_a_dev, done_b_dev, range, (hipStream_t)stream));
+  return recurrent_table_launch(p, x_dev, h_dev, c_dev, out_dev, done_a_dev, done_b_dev, range, clip, (hipStream_t)stream);
+}
+
+int cosim_recurrent_table_lists(cosim_recurrent_table* p, int range, int* rows_host, int* tiles_host, int* n_tiles_out) {
+  return table_lists(p, range, rows_host, tiles_host, n_tiles_out, "cosim_recurrent_table_lists");
 }
 
 int cosim_recurrent_table_destroy(cosim_recurrent_table* p) {
   if (!p) return COSIM_OK;
   (void)hipFree(p->d_image); (void)hipFree(p->d_desc); (void)hipFree(p->d_rows); (void)hipFree(p->d_tiles);
+  rotate_free(p->rot);
   delete p;
   return COSIM_OK;
 }

@@ -149,6 +149,7 @@ __global__ __launch_bounds__(256) void mlp_grouped_kernel(PolTabArgs A) {
   const int t = threadIdx.x;
   // the tile and its policy: indices out of blockIdx alone, so wave-uniform (scalar loads)
   const PolTile T = A.tiles[A.tile_first + blockIdx.x];
+  if (T.count == 0) return;            // a padding tile of a rotating table (poltab_regroup_kernel); a static table holds none
   const PolDesc* D = A.desc + T.policy;
   if (t < 32) tile_row[t] = t < T.count ? A.rows[T.start + t] : -1;
   __syncthreads();
@@ -167,6 +168,105 @@ __global__ __launch_bounds__(256) void mlp_grouped_kernel(PolTabArgs A) {
                return MlpLayer{A.image + D->woff[L], bo >= 0 ? A.image + bo : nullptr, D->dims[L], D->dims[L + 1], D->act[L], D->alpha[L]};
              },
              [&](int row) -> long long { return tile_row[row]; });
+}
+
+// The lists of a ROTATING table, rebuilt on the device ahead of every grouped launch (cosim_policy_table_forward_rotating; rule and
+// capacity: cosim_poltab.h).  One workgroup per env range.  It (1) advances the episode counter of every row whose done byte is set and
+// takes the row's policy from the rule, (2) rewrites the range's span of `rows` and `tiles` to exactly what build_policy_tiles gives for
+// that assignment -- policies ascending, rows ascending within a policy, tiles of at most 32 -- pads the span to its capacity with
+// tiles of count 0 (the grouped kernels return on those, so their grid is the capacity: a constant) and leaves the true tile count in
+// n_tiles[range].  A stable counting sort: a histogram of the range over policies (LDS integer adds: a sum, whatever their order),
+// its scan, then the rows 1024 at a time in ascending order, each placed at (its policy's first slot) + (rows of that policy in earlier
+// chunks: a cursor in LDS) + (in earlier waves of the chunk: wcnt) + (in lower lanes of its wave: a ballot).  No step depends on which
+// lane or wave arrives first, so the lists are a function of the counters alone.
+struct PolRange { int32_t first, count, tile_first, tile_cap; };   // rows [first, first + count), tiles [tile_first, tile_first + tile_cap)
+
+struct PolRegroupArgs {
+  const int32_t* base;              // [n] the static assignment, checked by create
+  int32_t* episode;                 // [n] ended episodes per row, the caller's
+  int32_t* policy_now;              // [n] or null: the policy each row is evaluated with
+  const uint8_t *done_a, *done_b;   // [n] or null
+  const PolRange* ranges;
+  int32_t* rows;                    // [n]
+  PolTile* tiles;                   // [sum of tile_cap]
+  int32_t* n_tiles;                 // [ranges]
+  int range_first, K, every;
+};
+
+constexpr int RG_THREADS = 1024, RG_WAVES = RG_THREADS / 64;   // the kernel is bound by the latency of a turn, not by its lanes: wide turns, few of them
+
+__global__ __launch_bounds__(RG_THREADS) void poltab_regroup_kernel(PolRegroupArgs A) {
+  __shared__ int hist[POL_MAXK];       // rows of each policy in the range
+  __shared__ int slot[POL_MAXK];       // where the next row of each policy goes, relative to the range's span of rows
+  __shared__ int tile0[POL_MAXK + 1];  // the first tile of each policy, relative to the range's span of tiles; [K]: the tile count
+  __shared__ int wcnt[RG_WAVES][64];          // rows of each policy in each wave of the chunk at hand
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6, K = A.K;
+  const int ri = A.range_first + blockIdx.x;
+  const PolRange R = A.ranges[ri];
+  if (t < POL_MAXK) hist[t] = 0;
+  wcnt[wave][lane] = 0;
+  __syncthreads();
+  for (int i = t; i < R.count; i += RG_THREADS) {
+    const int r = R.first + i;
+    const bool ended = (A.done_a != nullptr && A.done_a[r] != 0) || (A.done_b != nullptr && A.done_b[r] != 0);
+    const int e = episodes_after(A.episode[r], ended);
+    A.episode[r] = e;
+    const int k = policy_at(A.base[r], e, A.every, K);
+    if (A.policy_now != nullptr) A.policy_now[r] = k;
+    atomicAdd(&hist[k], 1);
+  }
+  __syncthreads();
+  if (t == 0) {   // K <= 64 words: a serial scan costs less than the barriers of a parallel one
+    int r = 0, tl = 0;
+    for (int k = 0; k < K; k++) {
+      slot[k] = r; tile0[k] = tl;
+      r += hist[k]; tl += (hist[k] + POL_TILE - 1) / POL_TILE;
+    }
+    tile0[K] = tl;
+    A.n_tiles[ri] = tl;
+  }
+  __syncthreads();
+  // the tiles: a policy's j-th tile begins 32 j rows into the policy's rows; behind the last one the padding
+  for (int j = t; j < R.tile_cap; j += RG_THREADS) {
+    PolTile T = {0, 0, 0, 0};
+    if (j < tile0[K]) {
+      int k = 0;
+      while (tile0[k + 1] <= j) k++;   // ends: tile0[K] > j
+      const int q = j - tile0[k], left = hist[k] - POL_TILE * q;
+      T.policy = k; T.start = R.first + slot[k] + POL_TILE * q; T.count = left < POL_TILE ? left : POL_TILE;
+    }
+    A.tiles[R.tile_first + j] = T;
+  }
+  // the rows.  `slot` is first written behind two barriers of the first turn, when every thread has left the loop above
+  for (int i0 = 0; i0 < R.count; i0 += RG_THREADS) {
+    const int i = i0 + t, r = R.first + i;
+    const bool valid = i < R.count;
+    // episode[r] is this thread's own write of the first loop (same i = t + RG_THREADS m)
+    const int k = valid ? policy_at(A.base[r], A.episode[r], A.every, K) : -1;
+    int rank = 0;
+    unsigned long long todo = __ballot(valid);
+    while (todo) {   // one turn per policy met in the wave; `todo` comes from ballots, so the loop is wave-uniform
+      const int leader = __ffsll(todo) - 1;
+      const int kk = __shfl(k, leader);
+      const unsigned long long same = __ballot(valid && k == kk);
+      if (valid && k == kk) rank = __popcll(same & ((1ull << lane) - 1ull));
+      if (lane == leader) wcnt[wave][kk] = __popcll(same);
+      todo &= ~same;
+    }
+    __syncthreads();
+    if (valid) {
+      int pos = slot[k] + rank;
+      for (int w = 0; w < wave; w++) pos += wcnt[w][k];
+      A.rows[R.first + pos] = r;
+    }
+    __syncthreads();
+    if (t < K) {
+      int sum = 0;
+      for (int w = 0; w < RG_WAVES; w++) { sum += wcnt[w][t]; wcnt[w][t] = 0; }
+      slot[t] += sum;
+    }
+    __syncthreads();
+  }
 }
 
 // One LSTM cell step for N environments (the recurrent policy of core/policy.py:24-47: the ONNX LSTM node with sequence length 1,
@@ -328,6 +428,7 @@ __global__ __launch_bounds__(256) void lstm_actor_grouped_kernel(RecTabArgs A) {
   float* xh = rec_lds + 2 * 32 * ld;
   // the tile and its policy: indices out of blockIdx alone, so wave-uniform (scalar loads)
   const PolTile T = A.tiles[A.tile_first + blockIdx.x];
+  if (T.count == 0) return;            // a padding tile of a rotating table, as in mlp_grouped_kernel
   const RecDesc* D = A.desc + T.policy;
   if (t < 32) {
     const int r = t < T.count ? A.rows[T.start + t] : -1;

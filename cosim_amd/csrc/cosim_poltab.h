@@ -135,6 +135,35 @@ inline PolTiles build_policy_tiles(const int32_t* policy_of_row, int K, const in
   return t;
 }
 
+// ---- a ROTATING table (cosim_policy_table_rotate): the policy of a row changes when its env ends an episode, so the lists above are
+// rebuilt on the device before every evaluation (poltab_regroup_kernel, cosim_mlp.hip).  The rule and the size of the buffers are here,
+// for the host, the kernel and the host program alike.
+#if defined(__HIPCC__)
+#define POL_HD __host__ __device__
+#else
+#define POL_HD
+#endif
+
+// The policy of a row whose static assignment is `base` (in [0, K)) after `episodes` ended episodes: every `every` (>= 1) episodes the
+// next one, (base + episodes / every) mod K.  The sum is never formed unreduced, so a count near INT32_MAX does not overflow; a
+// negative count reads as 0.
+POL_HD inline int32_t policy_at(int32_t base, int32_t episodes, int32_t every, int32_t K) {
+  const uint32_t steps = (uint32_t)(episodes < 0 ? 0 : episodes) / (uint32_t)every;
+  return (int32_t)(((uint32_t)base + steps % (uint32_t)K) % (uint32_t)K);
+}
+
+// The counter after a control step: one more if the env's episode ended, held at INT32_MAX.
+POL_HD inline int32_t episodes_after(int32_t episodes, bool ended) {
+  return (ended && episodes < INT32_MAX) ? episodes + 1 : episodes;
+}
+
+// The tiles a range of `count` rows can need under ANY assignment to K policies: a policy with c rows has c / 32 full tiles and at most
+// one partial one, the full tiles of all policies are at most count / 32, and a partial tile needs a policy with a row.  One row on each
+// of min(K, count) policies meets it.
+POL_HD inline int32_t policy_tile_capacity(int32_t count, int32_t K) {
+  return count / POL_TILE + (K < count ? K : count);
+}
+
 // ---- the image: per policy, per layer the weights (begun at a multiple of 4 words, so the float4 reads of a layer whose input width
 // is a multiple of 4 are 16-byte aligned) and then the bias if there is one.  Of a VALIDATED table.
 struct PolImage {

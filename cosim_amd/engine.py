@@ -129,6 +129,12 @@ def load_library():
     L.cosim_recurrent_table_create.argtypes = [ci] + [vp] * 17 + [ci, vp, ci, vp, ctypes.POINTER(vp)]
     L.cosim_recurrent_table_forward.argtypes = [vp] * 7 + [ci, ctypes.c_float, vp]
     L.cosim_recurrent_table_destroy.argtypes = [vp]
+    L.cosim_policy_table_rotate.argtypes = [vp, ci]
+    L.cosim_policy_table_forward_rotating.argtypes = [vp] * 7 + [ci, ctypes.c_float, vp]
+    L.cosim_policy_table_lists.argtypes = [vp, ci, vp, vp, ctypes.POINTER(ci)]
+    L.cosim_recurrent_table_rotate.argtypes = [vp, ci]
+    L.cosim_recurrent_table_forward_rotating.argtypes = [vp] * 9 + [ci, ctypes.c_float, vp]
+    L.cosim_recurrent_table_lists.argtypes = [vp, ci, vp, vp, ctypes.POINTER(ci)]
     L.cosim_last_error.restype = ctypes.c_char_p
     for fn in ("cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "cosim_reset", "cosim_step", "cosim_step_range", "cosim_get",
                "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_rollout",
@@ -138,7 +144,9 @@ def load_library():
                "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get", "cosim_scenario_params_set",
                "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get", "cosim_scenario_curves_set",
                "cosim_scenario_curves_get", "cosim_scenario_curves_clear", "cosim_policy_table_create", "cosim_policy_table_forward",
-               "cosim_policy_table_destroy", "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy"):
+               "cosim_policy_table_destroy", "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
+               "cosim_policy_table_rotate", "cosim_policy_table_forward_rotating", "cosim_policy_table_lists", "cosim_recurrent_table_rotate",
+               "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -157,7 +165,9 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_scenario_params_set", "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get",
            "cosim_scenario_curves_set", "cosim_scenario_curves_get", "cosim_scenario_curves_clear",
            "cosim_policy_table_create", "cosim_policy_table_forward", "cosim_policy_table_destroy",
-           "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy"]
+           "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
+           "cosim_policy_table_rotate", "cosim_policy_table_forward_rotating", "cosim_policy_table_lists",
+           "cosim_recurrent_table_rotate", "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:

@@ -143,8 +143,10 @@ class EpisodeLedger:
         """Per policy of a ``policy.PolicyTable`` (or of an int array: the policy of each LOCAL env, named "0", "1", ...): the columns
         of ``by_scenario()`` over the ended episodes of the envs that policy drives, keyed by the policy's name -- with ``scenario``
         by ``(name, scenario row)``, the checkpoint x scenario matrix.  An env's policy is looked up from its global id; a policy
-        (or a cell) without an ended episode has no entry."""
-        pol, names = policy_of_records(table, self.env, self.env_id0)
+        (or a cell) without an ended episode has no entry.  Under a ROTATING table a record belongs to the policy that drove that episode,
+        ``table.policy_of(env, episode ordinal)``: the ordinals are the table's counters when the ledger was armed in the env's
+        constructor and the table drove the env from its first step."""
+        pol, names = policy_of_records(table, self.env, self.env_id0, self.episode)
         m = self.ended()
         with_fell = self._with_fell(fell)
         out = {}
@@ -168,11 +170,16 @@ class EpisodeLedger:
             return cls(z["words"], z["env"], z["lost"], int(h[0]), int(h[1]))
 
 
-def policy_of_records(table, env, env_id0: int):
+def policy_of_records(table, env, env_id0: int, episode=None):
     """``(policy index int64 [R], names)`` for records of the global env ids ``env``: ``table`` is a ``policy.PolicyTable`` (its
-    ``policy_of`` and ``names``) or an int array holding the policy of each local env (env ``env_id0 + i`` is entry ``i``)."""
+    ``policy_of`` and ``names``) or an int array holding the policy of each local env (env ``env_id0 + i`` is entry ``i``).
+    ``episode``: the records' episode ordinals, which a rotating table (``rotate_every``) attributes by; others ignore them."""
     env = np.asarray(env, dtype=np.int64)
     if hasattr(table, "policy_of"):
+        if getattr(table, "rotate_every", None) is not None:
+            if episode is None:
+                raise ValueError("by_policy: the table rotates, so a record is attributed by (env, episode ordinal): pass the records' ordinals")
+            return np.asarray(table.policy_of(env, np.asarray(episode, dtype=np.int64)), dtype=np.int64), list(table.names)
         return np.asarray(table.policy_of(env), dtype=np.int64), list(table.names)
     a = np.asarray(table, dtype=np.int64).reshape(-1)
     loc = env - int(env_id0)

@@ -582,7 +582,7 @@ class _FleetTable:
             if a.min() < 0 or a.max() >= K:
                 raise ValueError(f"{who}: assign holds {int(a.min())}..{int(a.max())}, outside [0, {K})")
             self._explicit = a.astype(np.int32)
-        self.policy_of_env = self.policy_of(np.arange(self.env_id0, self.env_id0 + N, dtype=np.int64))
+        self.policy_of_env = self._base_of(np.arange(self.env_id0, self.env_id0 + N, dtype=np.int64))
         self.ranges = [(0, N)] if ranges is None else [(int(f), int(c)) for f, c in ranges]
         nxt = 0
         for f, c in self.ranges:
@@ -600,8 +600,8 @@ class _FleetTable:
         range_rows = [[t.as_tensor(i[(i >= f) & (i < f + c)], dtype=t.int64, device=self.device) for i in idx] for f, c in self.ranges]
         return rows, range_rows
 
-    def policy_of(self, global_env_ids) -> np.ndarray:
-        """The policy index int32 of each global env id (an explicit assignment knows this rank's envs only)."""
+    def _base_of(self, global_env_ids) -> np.ndarray:
+        """The static assignment: the policy index int32 of each global env id (an explicit assignment knows this rank's envs only)."""
         g = np.asarray(global_env_ids, dtype=np.int64)
         K = len(self.paths)
         if self._explicit is not None:
@@ -610,6 +610,91 @@ class _FleetTable:
                 raise ValueError(f"{type(self).__name__}.policy_of: an explicit assignment covers env ids {self.env_id0}..{self.env_id0 + self.num_envs - 1}")
             return self._explicit[loc]
         return ((g % K) if self.assign == "interleave" else ((g // self.scenarios) % K)).astype(np.int32)
+
+    def policy_of(self, global_env_ids, episodes=None) -> np.ndarray:
+        """The policy index int32 of each global env id; of a rotating table in the env's episode number ``episodes[i]`` (the episodes
+        it had ended before: a ledger record's ordinal), ``(base + episodes // rotate_every) mod K``."""
+        base = self._base_of(global_env_ids)
+        if self.rotate_every is None:
+            return base
+        if episodes is None:
+            raise ValueError(f"{type(self).__name__}.policy_of: the table rotates every {self.rotate_every} episode(s), so an env's policy depends on "
+                             "its episode: pass episodes= (policy_of_env is the assignment of episode 0)")
+        e = np.broadcast_to(np.asarray(episodes, dtype=np.int64), base.shape)
+        K = len(self.paths)
+        return ((base + (np.maximum(e, 0) // self.rotate_every) % K) % K).astype(np.int32)
+
+    rotate_every = None   # None: the assignment holds for the whole run
+
+    def _setup_rotate(self, rotate_every):
+        """``rotate_every`` checked; a rotating table gets its counters: ``episode`` (ended episodes per env) and ``policy_now`` (the
+        policy each env was last evaluated with), ``[N]`` int32 on the table's device, persistent."""
+        t, who = self.torch, type(self).__name__
+        if rotate_every is None:
+            return
+        if isinstance(rotate_every, bool) or not isinstance(rotate_every, (int, np.integer)) or int(rotate_every) < 1:
+            raise ValueError(f"{who}: rotate_every {rotate_every!r}: an integer >= 1 (episodes a checkpoint keeps an env), or None")
+        self.rotate_every = int(rotate_every)
+        self._base = t.as_tensor(self.policy_of_env, dtype=t.int32, device=self.device)
+        self.episode = t.zeros(self.num_envs, dtype=t.int32, device=self.device)
+        self.policy_now = self._base.clone()
+
+    def _arm(self, rotate_fn):
+        if self.rotate_every is not None and self._handle is not None:
+            with self.torch.cuda.device(self.device):
+                if rotate_fn(self._handle, self.rotate_every) != 0:
+                    raise RuntimeError(self._lib.cosim_last_error().decode())
+
+    def _advance(self, mask):
+        """The masked envs ended an episode: their counters go up by one (held at INT32_MAX).  Device work on persistent tensors: an
+        add and a maximum -- a counter that would wrap comes out below the old one, and the old one is kept."""
+        t = self.torch
+        ended = t.as_tensor(mask, device=self.device)
+        if ended.dtype != t.bool:
+            ended = ended != 0
+        t.maximum(self.episode, self.episode + ended, out=self.episode)
+
+    def rewind(self):
+        """Back to episode 0 for every env: the counters of a rotating table are zeroed (``reset()`` without a mask leaves them)."""
+        if self.rotate_every is not None:
+            self.episode.zero_()
+            self.policy_now.copy_(self._base)
+
+    def _twin_rows(self, i, done):
+        """The torch twin of the regroup launch for range ``i`` (-1: all): counters advanced by ``done``, ``policy_now`` from the rule, and
+        per policy the int64 rows it drives now."""
+        t, K = self.torch, len(self.paths)
+        first, count = (0, self.num_envs) if i < 0 else self.ranges[i]
+        sl = slice(first, first + count)
+        if done is not None:
+            ended = (done[0][sl] != 0) | (done[1][sl] != 0)
+            self.episode[sl] += (ended & (self.episode[sl] < 2147483647)).to(t.int32)
+        now = (self._base[sl] + (self.episode[sl].clamp(min=0) // self.rotate_every) % K) % K
+        self.policy_now[sl] = now
+        return [first + t.nonzero(now == k)[:, 0] for k in range(K)]
+
+    def _check_done(self, done):
+        t, who = self.torch, type(self).__name__
+        if done is not None:
+            for d in done:
+                if d.shape != (self.num_envs,) or d.dtype not in (t.uint8, t.bool) or not d.is_contiguous() or d.device != self._out.device:
+                    raise ValueError(f"{who}: done is (terminated, truncated), contiguous uint8 [{self.num_envs}] tensors on the table's device")
+
+    def _load_counters(self, state, src, mask):
+        """``load_state`` for the counters of a rotating table: env ``d`` takes ``state["episode"][src[d]]``, masked as the rest."""
+        t, who = self.torch, type(self).__name__
+        if self.rotate_every is None:
+            return
+        if state is None or "episode" not in state:
+            raise ValueError(f"{who}.load_state: the state carries no episode counters (it was taken from a table that does not rotate)")
+        x = t.as_tensor(state["episode"], dtype=t.int32, device=self.device)
+        if src is not None:
+            x = x[t.as_tensor(src, device=self.device).long()]
+        if tuple(x.shape) != (self.num_envs,):
+            raise ValueError(f"{who}.load_state: episode has shape {tuple(x.shape)}, expected ({self.num_envs},)")
+        if mask is not None:
+            x = t.where(t.as_tensor(mask, device=self.device) != 0, x, self.episode)
+        self.episode.copy_(x)
 
     def _check_range(self, i):
         if not 0 <= int(i) < len(self.ranges):
@@ -630,12 +715,25 @@ class PolicyTable(_FleetTable):
     non-CUDA device, or with ``fused=False``, each policy's interpreter runs on its own rows and the results are scattered: the
     torch twin of the kernel.  Stateless: a ``Snapshot`` stores nothing for it.
 
-    Out of scope: recurrent policies, files with different observation layouts, an assignment that changes per episode."""
+    ``rotate_every=R`` (an integer >= 1; ``None``: everything above, unchanged) makes the design PAIRED: env ``g`` is driven by policy
+    ``(policy_of_env + e // R) mod K`` in its episode number ``e``, so every robot meets every checkpoint and two checkpoints can be
+    compared on the same robot, floor and noise slot.  ``episode`` (``[N]`` int32, the episodes each env has ended) and ``policy_now``
+    (``[N]`` int32, the policy each env was last evaluated with) are persistent tensors; a device kernel regroups the envs ahead of
+    every evaluation (``cosim_policy_table_forward_rotating``) and each env still gets the bits of ``MLPPolicy`` of the file that
+    drives it now.  ``reset(mask)`` (a rotating table's only: a static one has no ``reset``) means "these envs ended an episode" and advances their counters (``Runner.test`` /
+    ``test_graphed`` call it); ``get_action_range(..., done=(terminated, truncated))`` folds the same advance into the range's
+    launch (``Runner.test_pipelined``); ``reset()`` leaves the counters alone, ``rewind()`` zeroes them; ``state()`` /
+    ``load_state`` carry them, so a ``Snapshot`` continues the rotation.  ``policy_of(g, episodes)`` applies the rule;
+    ``policy_of_env`` stays the assignment of episode 0.  The counter follows the ledger's episode ordinal when the table drives the
+    env from its first step and the ledger is armed in the env's constructor.
+
+    Out of scope: recurrent policies (``RecurrentPolicyTable``), files with different observation layouts, rotation keyed by anything
+    but the table's own episode count."""
 
     graph_safe = True     # get_action is one launch on persistent tensors
 
     def __init__(self, policy_paths, num_envs: int, device=None, assign="interleave", env_id0: int = 0, scenarios: int = 0,
-                 ranges=None, names=None, fused: Optional[bool] = None):
+                 ranges=None, names=None, fused: Optional[bool] = None, rotate_every=None):
         import torch
         self._setup_fleet(policy_paths, num_envs, device, env_id0, scenarios, names)
         paths, K, N = self.paths, len(self.paths), self.num_envs
@@ -657,9 +755,13 @@ class PolicyTable(_FleetTable):
         self.in_dim, self.out_dim = int(chains[0][0][0].shape[1]), int(chains[0][-1][0].shape[0])
         self._setup_assign(assign, ranges)
         self._out = torch.zeros((N, self.out_dim), dtype=torch.float32, device=self.device)
+        self._setup_rotate(rotate_every)
+        if self.rotate_every is not None:
+            self.reset = self._reset_rotating
         self._handle = None
         if fused is not False and self.device.type == "cuda":
             self._create(chains)
+            self._arm(self._lib.cosim_policy_table_rotate)
         elif fused:
             raise ValueError("fused=True needs a GPU device")
         else:
@@ -697,8 +799,21 @@ class PolicyTable(_FleetTable):
         self._lib, self._handle = L, handle
 
     def state(self):
-        """Nothing: a table is stateless, so ``env.snapshot(table)`` stores no policy state."""
-        return None
+        """Nothing for a static table: it is stateless, so ``env.snapshot(table)`` stores no policy state.  A rotating one: its episode
+        counters (a copy)."""
+        return None if self.rotate_every is None else {"episode": self.episode.clone()}
+
+    def load_state(self, state, src=None, mask=None):
+        """Counterpart of ``state()``, as ``LSTMPolicy.load_state``: env ``d`` takes the counter of row ``src[d]`` (``None``: row ``d``), envs
+        with ``mask[d] == 0`` keep theirs; in place.  Nothing to do for a static table."""
+        self._load_counters(state, src, mask)
+
+    def _reset_rotating(self, mask=None):
+        """``reset(mask)`` of a ROTATING table: the masked envs ended an episode, their counters advance (device work, graph-safe);
+        ``reset()`` leaves the counters alone (``rewind()`` zeroes them).  A static table has no ``reset`` at all, so a runner that asks
+        ``hasattr(policy, "reset")`` does for it exactly what it did before there was rotation."""
+        if mask is not None:
+            self._advance(mask)
 
     def close(self):
         if self._handle is not None:
@@ -711,19 +826,28 @@ class PolicyTable(_FleetTable):
         except Exception:  # noqa: BLE001
             pass
 
-    def _launch(self, x, out, i: int):
+    def _launch(self, x, out, i: int, done=None):
         t = self.torch
         if x.shape != (self.num_envs, self.in_dim) or out.shape != (self.num_envs, self.out_dim):
             raise ValueError(f"PolicyTable: state {tuple(x.shape)} / action {tuple(out.shape)}, expected ({self.num_envs}, {self.in_dim}) / "
                              f"({self.num_envs}, {self.out_dim})")
+        rotating = self.rotate_every is not None
+        if done is not None:
+            self._check_done(done)
         if self._handle is not None:
             if not (x.is_cuda and out.is_cuda and x.dtype == t.float32 and out.dtype == t.float32 and x.is_contiguous() and out.is_contiguous()):
                 raise ValueError("PolicyTable: state and action must be contiguous fp32 tensors on the table's device")
-            rc = self._lib.cosim_policy_table_forward(self._handle, x.data_ptr(), out.data_ptr(), i, 1.0, t.cuda.current_stream(self.device).cuda_stream)
+            stream = t.cuda.current_stream(self.device).cuda_stream
+            if rotating:
+                da, db = (None, None) if done is None else (done[0].data_ptr(), done[1].data_ptr())
+                rc = self._lib.cosim_policy_table_forward_rotating(self._handle, x.data_ptr(), out.data_ptr(), self.episode.data_ptr(),
+                                                                   self.policy_now.data_ptr(), da, db, i, 1.0, stream)
+            else:
+                rc = self._lib.cosim_policy_table_forward(self._handle, x.data_ptr(), out.data_ptr(), i, 1.0, stream)
             if rc != 0:
                 raise RuntimeError(self._lib.cosim_last_error().decode())
             return
-        rows = self._rows if i < 0 else self._range_rows[i]
+        rows = self._twin_rows(i, done) if rotating else (self._rows if i < 0 else self._range_rows[i])
         for g, idx in zip(self._graphs, rows):
             if idx.numel():
                 out[idx] = g.run({g.inputs[0]: x[idx]})[0].clamp(-1.0, 1.0)
@@ -735,11 +859,19 @@ class PolicyTable(_FleetTable):
         self._launch(x, self._out, -1)
         return self._out
 
-    def get_action_range(self, i: int, state, action):
+    def get_action_range(self, i: int, state, action, done=None):
         """Writes the rows of range ``i`` of ``ranges`` into ``action`` (``[N, action_dim]``) from ``state`` (``[N, in_dim]``), both whole-fleet
-        contiguous fp32 tensors, on the CURRENT stream and without allocating; the other rows of ``action`` stay as they are."""
+        contiguous fp32 tensors, on the CURRENT stream and without allocating; the other rows of ``action`` stay as they are.
+        ``done=(terminated, truncated)`` (uint8 ``[N]``): a rotating table needs it -- an env of the range with either set has ended an
+        episode, and its counter advances in this very launch; a static table ignores it."""
         self._check_range(i)
-        self._launch(state, action, int(i))
+        if self.rotate_every is None:
+            self._launch(state, action, int(i))
+            return
+        if done is None:
+            raise ValueError("PolicyTable.get_action_range: the table rotates, pass done=(terminated, truncated) (the range's episode ends advance "
+                             "its counters in this launch)")
+        self._launch(state, action, int(i), done)
 
 
 class RecurrentPolicyTable(_FleetTable):
@@ -754,13 +886,18 @@ class RecurrentPolicyTable(_FleetTable):
     episode reset of ``Runner.test`` folded into the forward.  Constructor arguments as ``PolicyTable``.  On a non-CUDA device, or with
     ``fused=False``, each policy's interpreter runs on its own rows against slices of the state: the torch twin.
 
-    Out of scope: tables that mix MLP and recurrent files, GRU cells, stacked or multi-step LSTM nodes, per-episode reassignment."""
+    ``rotate_every=R``: as ``PolicyTable`` -- the same rule, counters (``episode``, ``policy_now``), ``rewind()`` and ``policy_of``.  The done
+    flags do both jobs: ``reset(mask)`` (or ``done=``) zeroes the masked envs' state and advances their counters, so the next policy of
+    an env starts from ``h = c = 0``; ``state()`` / ``load_state`` carry ``h``, ``c`` and the counters.
+
+    Out of scope: tables that mix MLP and recurrent files, GRU cells, stacked or multi-step LSTM nodes, rotation keyed by anything but
+    the table's own episode count."""
 
     graph_safe = True     # one launch on persistent tensors
     recurrent = True      # Runner.test_pipelined hands get_action_range the env's done flags
 
     def __init__(self, policy_paths, num_envs: int, device=None, assign="interleave", env_id0: int = 0, scenarios: int = 0,
-                 ranges=None, names=None, fused: Optional[bool] = None):
+                 ranges=None, names=None, fused: Optional[bool] = None, rotate_every=None):
         import torch
         self._setup_fleet(policy_paths, num_envs, device, env_id0, scenarios, names)
         paths, N = self.paths, self.num_envs
@@ -782,9 +919,11 @@ class RecurrentPolicyTable(_FleetTable):
         self.h = torch.zeros((N, max(self.hidden)), dtype=torch.float32, device=self.device)
         self.c = torch.zeros_like(self.h)
         self._out = torch.zeros((N, self.out_dim), dtype=torch.float32, device=self.device)
+        self._setup_rotate(rotate_every)
         self._handle = None
         if fused is not False and self.device.type == "cuda":
             self._create(parts)
+            self._arm(self._lib.cosim_recurrent_table_rotate)
         elif fused:
             raise ValueError("fused=True needs a GPU device")
         else:
@@ -848,17 +987,23 @@ class RecurrentPolicyTable(_FleetTable):
             pass
 
     def reset(self, mask=None):
-        """Zero the recurrent state (of the masked envs), as ``LSTMPolicy.reset``: a fill, so a non-finite state does not survive."""
+        """Zero the recurrent state (of the masked envs), as ``LSTMPolicy.reset``: a fill, so a non-finite state does not survive.  With a
+        mask the envs ended an episode: a rotating table advances their counters too; ``reset()`` leaves the counters alone."""
         if mask is None:
             self.h.zero_(); self.c.zero_()
         else:
             done = (self.torch.as_tensor(mask, device=self.device) != 0)[:, None]
             self.h.masked_fill_(done, 0.0)
             self.c.masked_fill_(done, 0.0)
+            if self.rotate_every is not None:
+                self._advance(mask)
 
     def state(self) -> dict:
-        """The recurrent state ``h`` / ``c`` ``[N, Hmax]`` (copies) for a ``Snapshot``."""
-        return {"h": self.h.clone(), "c": self.c.clone()}
+        """The recurrent state ``h`` / ``c`` ``[N, Hmax]`` (copies) for a ``Snapshot``; of a rotating table the episode counters too."""
+        out = {"h": self.h.clone(), "c": self.c.clone()}
+        if self.rotate_every is not None:
+            out["episode"] = self.episode.clone()
+        return out
 
     def load_state(self, state: dict, src=None, mask=None):
         """As ``LSTMPolicy.load_state``: env ``d`` takes row ``src[d]`` of ``state["h"]`` / ``["c"]`` (``None``: row ``d``); envs with
@@ -873,6 +1018,7 @@ class RecurrentPolicyTable(_FleetTable):
             if mask is not None:
                 x = t.where((t.as_tensor(mask, device=self.device) != 0)[:, None], x, dst)
             dst.copy_(x)
+        self._load_counters(state, src, mask)
 
     def _launch(self, x, out, i: int, done=None):
         t = self.torch
@@ -887,12 +1033,17 @@ class RecurrentPolicyTable(_FleetTable):
             if not (x.is_cuda and out.is_cuda and x.dtype == t.float32 and out.dtype == t.float32 and x.is_contiguous() and out.is_contiguous()):
                 raise ValueError("RecurrentPolicyTable: state and action must be contiguous fp32 tensors on the table's device")
             da, db = (None, None) if done is None else (done[0].data_ptr(), done[1].data_ptr())
-            rc = self._lib.cosim_recurrent_table_forward(self._handle, x.data_ptr(), self.h.data_ptr(), self.c.data_ptr(), out.data_ptr(), da, db, i, 1.0,
-                                                         t.cuda.current_stream(self.device).cuda_stream)
+            stream = t.cuda.current_stream(self.device).cuda_stream
+            if self.rotate_every is not None:
+                rc = self._lib.cosim_recurrent_table_forward_rotating(self._handle, x.data_ptr(), self.h.data_ptr(), self.c.data_ptr(), out.data_ptr(),
+                                                                      self.episode.data_ptr(), self.policy_now.data_ptr(), da, db, i, 1.0, stream)
+            else:
+                rc = self._lib.cosim_recurrent_table_forward(self._handle, x.data_ptr(), self.h.data_ptr(), self.c.data_ptr(), out.data_ptr(), da, db, i, 1.0,
+                                                             stream)
             if rc != 0:
                 raise RuntimeError(self._lib.cosim_last_error().decode())
             return
-        rows = self._rows if i < 0 else self._range_rows[i]
+        rows = self._twin_rows(i, done) if self.rotate_every is not None else (self._rows if i < 0 else self._range_rows[i])
         fresh = None if done is None else ((done[0] != 0) | (done[1] != 0))
         for g, idx, H in zip(self._graphs, rows, self.hidden):
             if not idx.numel():
@@ -916,6 +1067,9 @@ class RecurrentPolicyTable(_FleetTable):
         """One step of the envs of range ``i``: their rows of ``action`` and of ``h`` / ``c`` are written, every other row stays as it is.
         ``state`` / ``action`` as ``PolicyTable.get_action_range``; on the CURRENT stream, without allocating.  ``done``: see the class."""
         self._check_range(i)
+        if self.rotate_every is not None and done is None:
+            raise ValueError("RecurrentPolicyTable.get_action_range: the table rotates, pass done=(terminated, truncated) (the range's episode "
+                             "ends advance its counters in this launch)")
         self._launch(state, action, int(i), done)
 
 
@@ -934,11 +1088,14 @@ def open_policy_table(policy_paths, **table_args):
 def build_policy(config: dict, policy_path: str = None, num_envs: int = 1, device=None, **table_args):
     """``core/policy.py:49-53``.  With a list of files in ``config["policy"]["onnx_files"]``: a table over them -- ``PolicyTable`` or,
     for recurrent files, ``RecurrentPolicyTable``; the kind is detected from the files (``open_policy_table``), ``use_lstm`` belongs to
-    a single file (``config["policy"]["assign"]``, default interleave; ``table_args``: ``env_id0``, ``scenarios``, ``ranges``, ``names``)."""
+    a single file (``config["policy"]["assign"]``, default interleave; ``config["policy"]["rotate"]``: the table's ``rotate_every``, default
+    none; ``table_args``: ``env_id0``, ``scenarios``, ``ranges``, ``names``)."""
     files = config["policy"].get("onnx_files")
     if files:
         if config["policy"].get("use_lstm"):
             raise ValueError("build_policy: a policy table takes MLP actors only (recurrent policies in a table are out of scope)")
+        if config["policy"].get("rotate") is not None:
+            table_args = {"rotate_every": config["policy"]["rotate"], **table_args}
         return open_policy_table(list(files), num_envs=num_envs, device=device, assign=config["policy"].get("assign", "interleave"), **table_args)
     if config["policy"]["use_lstm"]:
         return LSTMPolicy(config, policy_path, num_envs=num_envs, device=device)

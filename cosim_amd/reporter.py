@@ -42,7 +42,7 @@ class FleetReporter:
             self._lib.cosim_last_error.restype = ctypes.c_char_p
         self.steps = 0
         self.episodes_ended = 0
-        self.policy_table = None      # a policy.PolicyTable (Runner sets it): summary() then breaks episodes and checks down by policy
+        self.policy_table = None      # a policy.PolicyTable (Runner sets it): summary() then breaks episodes and checks down by policy (a rotating one: by the policy of each record's episode ordinal)
         self.hist = None
         if percentiles:
             if self._lib is None:

@@ -50,6 +50,9 @@ class Runner:
         self._push_event, self._push_vel, self._stop = False, None, False
         if hasattr(policy, "policy_of") and hasattr(reporter, "policy_table"):
             reporter.policy_table = policy                         # a policy.PolicyTable: the report breaks the outcomes down by policy
+        if getattr(policy, "rotate_every", None) is not None and not env.auto_reset:
+            raise ValueError(f"Runner: {type(policy).__name__}(rotate_every={policy.rotate_every}) moves an env to its next policy when an episode "
+                             "ends, which needs an env built with auto_reset=True (as scenario mode 'cycle' does)")
 
     def update_command(self, index: int, value: float):            # tester.py:41-46
         if index < self.env.command_dim:
@@ -150,7 +153,9 @@ class Runner:
         env.reset()
         # a policy.RecurrentPolicyTable: it starts from a zero state, and from then on a range's episode resets ride on its own stream,
         # folded into the range's next forward by the done flags its last step wrote
+        # a rotating table of either kind takes the same flags: they advance the range's episode counters in the same launch
         recurrent = by_range and getattr(self.policy, "recurrent", False)
+        with_done = recurrent or (by_range and getattr(self.policy, "rotate_every", None) is not None)
         if recurrent:
             self.policy.reset()
         episodes0 = env.solver_stats()["episodes_ended"]
@@ -178,7 +183,7 @@ class Runner:
                 if inflight > 0 and steps >= inflight:
                     ring[i][steps % inflight].synchronize()
                 with t.cuda.stream(env.range_streams[i]):
-                    if recurrent:
+                    if with_done:
                         self.policy.get_action_range(i, env.state, action, done=(env.terminated, env.truncated))  # tester.py:70, :57-60
                     elif by_range:
                         self.policy.get_action_range(i, env.state, action)                                        # tester.py:70

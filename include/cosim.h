@@ -542,12 +542,37 @@ int cosim_mlp_forward(const float* x_dev, int n, int n_layers, const int* dims, 
  * written.  Every env gets the bits cosim_mlp_forward gives for its policy; the non-finite rule is the same.  Refuses a null pointer,
  * a range index out of bounds and a current device other than the table's.  No allocation, no host read, no synchronisation: it
  * can be captured in a graph.
- * Out of scope: recurrent policies, differing observation layouts, an assignment that changes per episode. */
+ * Out of scope: recurrent policies (the recurrent table below), differing observation layouts.
+ *
+ * ROTATION -- the paired design: every env is driven by every policy, one per episode.
+ *   policy(row, e) = (policy_of_row[row] + e / every) mod K        e: the episodes the row has ended, counted by the table's launches
+ * rotate: arms a table once (every >= 1; below 1, or a second call: COSIM_EINVAL with the value in cosim_last_error).  create's
+ * policy_of_row stays on the device as the base, and each range's span of the tile list is widened to the most tiles ANY assignment
+ * of its rows can need, count / 32 + min(K, count), seeded with the static lists and padded with tiles of 0 rows.
+ * forward_rotating: two launches on `stream`.  The first (poltab_regroup_kernel, one workgroup per range) adds 1 to episode_dev[i]
+ * ([n] int32, the CALLER's, as the recurrent table's h / c are) for every row of the range with done_a_dev[i] or done_b_dev[i]
+ * non-zero (either may be NULL; the counter stops at INT32_MAX, a negative one reads as 0), writes the row's policy under the rule to
+ * policy_now_dev[i] ([n] int32 or NULL) and rebuilds the range's rows and tiles to what create would have built for that assignment:
+ * policies ascending, rows ascending within a policy, tiles of at most 32 rows, none across a range.  The order is fixed by ballots
+ * and scans, never by which atomic arrives first, so the lists are a function of the counters alone.  The second is forward's
+ * kernel over the range's capacity -- a constant grid; a padding tile returns at once -- so every env gets the bits
+ * cosim_mlp_forward gives for the policy that drives it now.  Refuses an unarmed table, a null x / out / episode, a range out of
+ * bounds and a foreign device.  No allocation, no host read, no synchronisation: the pair can be captured, and a replay advances
+ * the counters again.  forward on an armed table is refused (its lists belong to the last rotating call).
+ * lists: a SYNCHRONOUS read-back of one range's lists for tests and debugging: rows_host [count of the range], tiles_host
+ * [capacity of the range][4] (policy, start, count, 0; start indexes the whole row list), *n_tiles_out the tiles in use.  On an
+ * unarmed table the capacity is the range's tile count.
+ * Out of scope: rotation keyed by anything but the table's own episode count. */
 typedef struct cosim_policy_table cosim_policy_table_t;
 int cosim_policy_table_create(int n_policies, const int* n_layers, const int* dims, const int* act, const float* act_alpha,
                               const float* const* w_host, const float* const* b_host, int n, const int* policy_of_row, int n_ranges,
                               const int* ranges, cosim_policy_table_t** out);
 int cosim_policy_table_forward(cosim_policy_table_t* table, const float* x_dev, float* out_dev, int range, float clip, void* stream);
+int cosim_policy_table_rotate(cosim_policy_table_t* table, int every);
+int cosim_policy_table_forward_rotating(cosim_policy_table_t* table, const float* x_dev, float* out_dev, int32_t* episode_dev,
+                                        int32_t* policy_now_dev, const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range,
+                                        float clip, void* stream);
+int cosim_policy_table_lists(cosim_policy_table_t* table, int range, int* rows_host, int* tiles_host, int* n_tiles_out);
 int cosim_policy_table_destroy(cosim_policy_table_t* table);
 
 /* The recurrent policy's cell (reference core/policy.py:24-47: an ONNX LSTM node fed one step at a time with h_in / c_in kept by the
@@ -578,6 +603,9 @@ int cosim_lstm_cell(const float* x_dev, const float* h_dev, const float* c_dev, 
  * does not survive.  Rows outside the range are neither read nor written.  Every env gets the bits of cosim_mlp_forward (encoder,
  * clip 0) -> cosim_lstm_cell -> cosim_mlp_forward (head, clip) of its own policy.  Refuses a null x / h / c / out, a range index out
  * of bounds and a current device other than the table's.  No allocation, no host read, no synchronisation: it can be captured.
+ * rotate / forward_rotating / lists: as cosim_policy_table_*'s, same rule, same regroup launch ahead of the actor launch.  The done
+ * bytes do both jobs: they count the ended episode, which moves the row to its next policy, and that policy starts from h = c = 0
+ * by the select above -- columns beyond its hidden size are never read, whatever the policy before it left there.
  * Out of scope: tables that mix MLP and recurrent actors, GRU cells, stacked or multi-step LSTM nodes. */
 typedef struct cosim_recurrent_table cosim_recurrent_table_t;
 int cosim_recurrent_table_create(int n_policies, const int* n_enc, const int* enc_dims, const int* enc_act, const float* enc_alpha,
@@ -588,6 +616,11 @@ int cosim_recurrent_table_create(int n_policies, const int* n_enc, const int* en
                                  int n_ranges, const int* ranges, cosim_recurrent_table_t** out);
 int cosim_recurrent_table_forward(cosim_recurrent_table_t* table, const float* x_dev, float* h_dev, float* c_dev, float* out_dev,
                                   const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range, float clip, void* stream);
+int cosim_recurrent_table_rotate(cosim_recurrent_table_t* table, int every);
+int cosim_recurrent_table_forward_rotating(cosim_recurrent_table_t* table, const float* x_dev, float* h_dev, float* c_dev, float* out_dev,
+                                           int32_t* episode_dev, int32_t* policy_now_dev, const uint8_t* done_a_dev,
+                                           const uint8_t* done_b_dev, int range, float clip, void* stream);
+int cosim_recurrent_table_lists(cosim_recurrent_table_t* table, int range, int* rows_host, int* tiles_host, int* n_tiles_out);
 int cosim_recurrent_table_destroy(cosim_recurrent_table_t* table);
 
 /* Reporter side (reference core/reporter.py:210-218 write_info, :429-442, :506-508): fleet statistics of one step's info in one
