@@ -271,6 +271,7 @@ class BatchedEnv:
         self._cmd_out = self._row_out = None
         self.check_slots = 0
         self.curves_armed = False
+        self._curve_groups = None                                   # (tensor, G, names) of set_curve_groups: the tensor is kept alive here
         scenarios = scenarios if scenarios is not None else eng_cfg.get("scenarios")
         if scenarios is not None:
             self.set_scenarios(scenarios, scenario_mode if scenario_mode is not None else eng_cfg.get("scenario_mode", "env"),
@@ -676,8 +677,9 @@ class BatchedEnv:
         ends folds its samples into the cells of (scenario, item, outcome) with integer atomics, on the device, with no host read;
         ``curves()`` reads them.  Every call empties the cells and begins every env's episode anew for the curves; ``reset()``,
         ``restore`` and ``set_state`` discard what the envs they touch had staged, so an episode the host cuts is in no cell.  Items
-        of the same counts and sizes are rewritten in place (captured graphs pick them up).  ``None`` / ``False``: the curves are not
-        armed (what an earlier call armed is cleared).  Limits: state signals take no sample on a step that ends the episode; open
+        of the same counts and sizes are rewritten in place (captured graphs pick them up; groups set by ``set_curve_groups`` stay).
+        Any other call FORGETS the groups of ``set_curve_groups`` -- the cells they split are freed -- so set them again.  ``None`` /
+        ``False``: the curves are not armed (what an earlier call armed is cleared).  Limits: state signals take no sample on a step that ends the episode; open
         episodes are not in the cells; curves are not part of a ``snapshot()``."""
         from .scenario import MODES, ScenarioTable
         t = self.torch
@@ -687,6 +689,7 @@ class BatchedEnv:
             self._info_views = None
             self.check_slots = 0
             self.curves_armed = False
+            self._curve_groups = None
             return
         if mode not in MODES:
             raise ValueError(f"set_scenarios: mode must be 'env' or 'cycle', got {mode!r}")
@@ -712,6 +715,7 @@ class BatchedEnv:
                 self._info_views = None
                 self.check_slots = 0
                 self.curves_armed = False
+                self._curve_groups = None
             raise
         self.scenario_table, self.scenario_mode = table, mode
         self._info_views = None
@@ -734,19 +738,77 @@ class BatchedEnv:
             self.curves_armed = True
         elif self.engine.query("scenario_curve_items") > 0:
             self.engine.scenario_curves_set(None)
+        if not self.curves_armed or self.engine.query("scenario_curve_groups") == 0:   # the engine dropped the groups with the cells they split
+            self._curve_groups = None
+
+    def set_curve_groups(self, groups, n_groups: Optional[int] = None, names=None):
+        """Split the armed response curves by one device word per env (``cosim_scenario_curves_groups``): the cells become ``n_groups``
+        planes, and an episode is folded into the plane its env's word names WHEN THE FOLD READS IT -- behind the step that ended the
+        episode, on the range's own stream, ahead of whatever is enqueued there next.  ``groups``: a ``PolicyTable`` /
+        ``RecurrentPolicyTable`` (its ``curve_groups()``: curves by policy, under rotation too, since a rotating table rewrites
+        ``policy_now`` only in its forward; the table must drive the env from its first step), or an int32 device tensor ``[N]``
+        (then ``n_groups``, 1..64, is required; ``names``: one string per group), or ``None`` to go back to ungrouped curves.  The env
+        holds a reference to the tensor; its contents may change between steps and between replays of a captured graph, but the
+        pointer and ``n_groups`` are kernel arguments: set the groups before capturing.  A word outside ``[0, n_groups)`` leaves its
+        episode in no plane (``curve_groups_lost()`` counts those).  Every call empties the cells and begins every env's episode anew
+        for the curves.  ``curves()`` then returns grouped ``Curves``.  An in-place rewrite of the items by ``set_scenarios`` (same
+        counts and sizes) keeps the groups; any other ``set_scenarios`` forgets them, as does disarming the curves: call this again.
+        Any other per-env key works the same way -- the per-spawn-row view is a tensor of ``spawn_rows()``.  Raises ``ValueError`` if no
+        curves are armed."""
+        t = self.torch
+        if not self.curves_armed:
+            raise ValueError("set_curve_groups(): no curves are armed (BatchedEnv(scenarios=TABLE, curves=True) or set_scenarios(..., curves=True)): "
+                             "groups split the cells of armed curves")
+        if groups is None:
+            self.engine.scenario_curves_groups(0, None)
+            self._curve_groups = None
+            return
+        if hasattr(groups, "curve_groups"):
+            if n_groups is not None:
+                raise ValueError("set_curve_groups(): a policy table brings its own n_groups (its policy count); pass n_groups with a tensor only")
+            if getattr(groups, "num_envs", self.num_envs) != self.num_envs:
+                raise ValueError(f"set_curve_groups(): the table was built for {groups.num_envs} envs, the env has {self.num_envs}")
+            words, n_groups, tab_names = groups.curve_groups()
+            names = tab_names if names is None else names
+        else:
+            words = groups
+            if n_groups is None:
+                raise ValueError("set_curve_groups(): a group tensor needs n_groups (the words that count are 0 .. n_groups - 1)")
+        if not isinstance(words, t.Tensor) or words.dtype != t.int32 or tuple(words.shape) != (self.num_envs,) or not words.is_contiguous() \
+                or words.device != self.device:
+            what = f"{type(words).__name__}" if not isinstance(words, t.Tensor) else f"{words.dtype} {tuple(words.shape)} on {words.device}"
+            raise ValueError(f"set_curve_groups(): groups must be a contiguous int32 tensor [{self.num_envs}] on {self.device}, got {what}")
+        if isinstance(n_groups, bool) or not isinstance(n_groups, (int, np.integer)) or not 1 <= int(n_groups) <= 64:
+            raise ValueError(f"set_curve_groups(): n_groups {n_groups!r}: an integer 1..64 (None as groups clears them)")
+        n_groups = int(n_groups)
+        names = [str(g) for g in range(n_groups)] if names is None else [str(x) for x in names]
+        if len(names) != n_groups or len(set(names)) != n_groups:
+            raise ValueError(f"set_curve_groups(): names must be {n_groups} different strings, got {names}")
+        self.engine.scenario_curves_groups(n_groups, words.data_ptr())
+        self._curve_groups = (words, n_groups, names)
+
+    def curve_groups_lost(self) -> int:
+        """Ended episodes whose group word was outside ``[0, n_groups)`` since the cells were last emptied: they are in no plane.  Joins
+        the range streams and reads one device word (a synchronising call); 0 with no groups set."""
+        return self.engine.query("scenario_curve_ungrouped") if self.curves_armed else 0
 
     def curves(self):
         """The response curves of the fleet's ended episodes so far as a ``Curves`` (``cosim_amd/curves.py``): per (scenario, item)
-        the sample times and, per outcome class and time bin, count, mean, min, max, histogram and quantiles.  Joins the range streams
-        and reads the device once; nothing is read per step.  Raises ``ValueError`` if no curves are armed."""
+        the sample times and, per outcome class and time bin, count, mean, min, max, histogram and quantiles; with groups set
+        (``set_curve_groups``) the grouped ``Curves``, one plane per group.  Joins the range streams and reads the device once; nothing is
+        read per step.  Raises ``ValueError`` if no curves are armed."""
         from .curves import Curves
         if not self.curves_armed:
             raise ValueError("curves(): no curves are armed (BatchedEnv(scenarios=TABLE, curves=True) or set_scenarios(..., curves=True))")
         t = self.torch
-        cells = t.empty((self.engine.query("scenario_curve_words"),), dtype=t.int32, device=self.device)
+        G = self.engine.query("scenario_curve_groups")
+        cells = t.empty((max(G, 1) * self.engine.query("scenario_curve_words"),), dtype=t.int32, device=self.device)
         self.engine.scenario_curves_get(cells.data_ptr(), self._stream())
         t.cuda.current_stream(self.device).synchronize()
-        return Curves.from_raw(cells.cpu().numpy().view(np.uint32), self.scenario_table)
+        if G == 0:
+            return Curves.from_raw(cells.cpu().numpy().view(np.uint32), self.scenario_table)
+        return Curves.from_raw(cells.cpu().numpy().view(np.uint32), self.scenario_table, groups=G, group_names=self._curve_groups[2],
+                               ungrouped=self.engine.query("scenario_curve_ungrouped"))
 
     def clear_curves(self):
         """Empty the cells and begin every env's episode anew for the curves (what was staged is discarded).  Joins the range streams

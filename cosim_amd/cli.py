@@ -129,6 +129,9 @@ def main(argv=None) -> int:
                          "series split by outcome; their summary goes into the report as \"episodes.curves\" (also under --graph / --pipelined)")
     ap.add_argument("--curves-out", default=None, metavar="PATH.npz",
                     help="with --curves: write the curves here (under torchrun: the whole fleet's, all-reduced, from rank 0)")
+    ap.add_argument("--curves-by", default=None, choices=["policy"], metavar="KEY",
+                    help="with --curves and several --policy files: split the curves by the policy that drove each ended episode (under "
+                         "--policy-rotate too); the report gains \"episodes.curves.by_policy\" and --curves-out writes the grouped file")
     ap.add_argument("--backend", default="nccl")
     args = ap.parse_args(argv)
 
@@ -141,7 +144,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces", "check_slots", "curves"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces", "check_slots", "curves", "curves_by"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -247,6 +250,14 @@ def main(argv=None) -> int:
         ap.error("--curves-out needs --curves")
     if args.curves and scenarios is None:
         ap.error("--curves needs --scenarios: curves are rows of a scenario table")
+    args.curves_by = pick(args.curves_by, sess.get("curves_by"), None)
+    if args.curves_by is not None:
+        if args.curves_by != "policy":
+            ap.error(f"--curves-by / curves_by: {args.curves_by!r}: policy")
+        if not args.curves:
+            ap.error("--curves-by policy needs --curves: it splits the response curves")
+        if not policy_files:
+            ap.error("--curves-by policy needs a policy table: several --policy files (policy.onnx_files)")
     # fall rule: the session's dict (top level or engine.fall), overridden key by key by the flags
     fall = dict(sess.get("fall") or s_eng.get("fall") or {})
     for key, val in (("tilt", args.fall_tilt), ("height", args.fall_height), ("grace", args.fall_grace)):
@@ -327,6 +338,8 @@ def main(argv=None) -> int:
             write_random_mlp(path, env.state_dim, env.action_dim, seed=args.seed)
         pc = {"policy": {"use_lstm": bool(args.lstm), "h_in_dim": args.hidden_dim, "c_in_dim": args.hidden_dim}}
         policy = build_policy(pc, path, num_envs=env.num_envs, device=env.device)
+    if args.curves_by == "policy":                                   # before the run, and so before the capture under --graph
+        env.set_curve_groups(policy)
     if args.graph and not getattr(policy, "graph_safe", False):
         ap.error("--graph needs an ONNX policy (random-mlp or a file): the sinusoid drive keeps its clock on the host, a captured "
                  "graph would replay one frozen action")
@@ -412,7 +425,8 @@ def main(argv=None) -> int:
                              if "terminated" in out.get("episodes", {}) else {}),
                           **({"checks": {k: v for k, v in out["episodes"]["checks"].get("fleet", out["episodes"]["checks"]).items()
                                          if k not in ("checks", "by_scenario")}} if verdicts is not None else {}),
-                          **({"curves": out["episodes"]["curves"]} if args.curves else {}),
+                          **({"curves": {k: ({name: {q: v[q] for q in ("episodes", "episodes_truncated", "episodes_terminated")} for name, v in x.items()}
+                                             if k == "by_policy" else x) for k, x in out["episodes"]["curves"].items()}} if args.curves else {}),
                           **({"failure_traces": traces.summary()} if traces is not None else {}),
                           **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
                              if "by_scenario" in out.get("episodes", {}) else {}),

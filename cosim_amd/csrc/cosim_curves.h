@@ -20,6 +20,12 @@
 // Every cell update is an integer operation that commutes, handed to the caller's `At` (the kernel: atomics that discard their
 // result; the host program: plain operations), so the cells are a function of the set of ended episodes alone.
 //
+// Groups (cosim_scenario_curves_groups): with G groups the cells are G planes, each a whole cell image of the layout above (the same
+// coff / cw, W words), plane g at word g * W.  Sampling, staging and the clock do not change.  The fold reads the env's group word
+// once, as it stands then, and folds the episode into that plane; a word outside [0, G) touches no cell, the stage still goes back to
+// "no sample", and the episode is counted in one device word, `ungrouped`.  Each plane being a whole image, the planes merged word
+// kind by word kind (counts, sums and histograms add, extremes merge on their keys) are the cells without groups.
+//
 // The bodies are written per lane: in the sampling phase lane `lane` of `nl` handles the items lane, lane + nl, ...; in the fold
 // phase the items are walked by every lane and the lanes stride over an item's time bins.
 #pragma once
@@ -30,7 +36,7 @@
 
 namespace cosim {
 
-constexpr int CUR_MAX_ITEMS = 8, CUR_MAX_T = 1024, CUR_MAX_BINS = 64;
+constexpr int CUR_MAX_ITEMS = 8, CUR_MAX_T = 1024, CUR_MAX_BINS = 64, CUR_MAX_GROUPS = 64;
 constexpr int CUR_NONE = 0x7fc00000;        // stage word: no sample
 constexpr int CUR_NONFINITE = 0x7fc00001;   // stage word: a NaN or +-inf sample
 constexpr size_t CUR_MAX_BYTES = (size_t)256 << 20;   // of the cells and of the stage, each (a design limit)
@@ -68,6 +74,11 @@ struct CurArgs {
   int n_envs, first, count;
   int info_dim, nu, cmd_stride;
   int s_stride, s_qpos, s_qvel, s_meta;
+  // groups (cosim_scenario_curves_groups); all zero: no groups, one plane
+  const int32_t* group;    // [N] the caller's group word of every env, read on a row with a done flag only
+  int n_groups;            // G: the cells are G planes, each a whole cell image; plane g starts at word g * plane_words
+  size_t plane_words;      // W: the cell words of one plane
+  unsigned* ungrouped;     // one word: the ended episodes whose group word was outside [0, G)
 };
 
 SCN_HD int curves_nt(int t0, int t1, int every) { return (int)(((long long)t1 - t0 + every - 1) / every); }
@@ -167,6 +178,30 @@ SCN_HD void curves_fold_lane(const CurArgs& a, int env, int lane, int nl, int ro
       if (B > 0) at.add(cell + (size_t)(6 + curves_hist_row(v, l, h, w, B)) * n + j, 1u);
     }
   }
+}
+
+// Fold phase with groups: the episode goes into plane `g` (the env's group word as the fold read it, the same value in every lane) by
+// curves_fold_lane's arithmetic.  A word outside [0, G) touches no cell: the episode's staged bins go back to "no sample" and lane 0
+// counts the episode in `ungrouped`.
+template <class At>
+SCN_HD void curves_fold_group_lane(const CurArgs& a, int env, int lane, int nl, int row, int cls, int g, At& at) {
+  if (g >= 0 && g < a.n_groups) {
+    CurArgs p = a;
+    p.cells = a.cells + (size_t)g * a.plane_words;
+    curves_fold_lane(p, env, lane, nl, row, cls, at);
+    return;
+  }
+  const CurTable& T = a.tab;
+  SCN_TAB(int32_t) nt = SCN_TAB_CAST(int32_t, T.nt);
+  SCN_TAB(int32_t) soff = SCN_TAB_CAST(int32_t, T.soff);
+  int i0, ni;
+  curves_row_items(T, row, &i0, &ni);
+  for (int k = 0; k < ni; k++) {
+    int* st = a.stage + (size_t)env * T.SW + soff[i0 + k];
+    const int n = nt[i0 + k];
+    for (int j = lane; j < n; j += nl) st[j] = CUR_NONE;
+  }
+  if (lane == 0) at.add(a.ungrouped, 1u);
 }
 
 // whether the begin rule applies to env (mask and restore source, as checks_begin_applies reads them)

@@ -165,6 +165,11 @@ struct cosim_engine {
   int* d_cur_clk = nullptr;       // [n_envs]
   unsigned* d_cur_cells = nullptr;   // cur_words 32-bit words
   size_t cur_words = 0;
+  // groups of the curves (cosim_scenario_curves_groups): with G > 0 the cells are G planes of cur_words, and the step launches
+  // curves_step_grouped_kernel, which reads the caller's group word of an env when its episode ends
+  int cur_groups = 0;                     // G; 0: no groups, one plane, curves_step_kernel
+  const int32_t* cur_group = nullptr;     // [n_envs], the caller's
+  unsigned* d_cur_ungrouped = nullptr;    // one word: ended episodes whose group word was outside [0, G)
   // fall rules (cosim_fall_set): kernel arguments of every step launch; fall_mask 0 = none (meta word 15 is not written)
   float fall_min_up = -1.f, fall_min_height = 0.f;
   int fall_grace = 0, fall_mask = 0;
@@ -751,6 +756,7 @@ static CurArgs curves_args(cosim_engine* e) {
   a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
   a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.cmd_stride = e->ho.command_dim;
   a.s_stride = e->lay.s_stride; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.s_meta = e->lay.s_meta;
+  if (e->cur_groups > 0) { a.group = e->cur_group; a.n_groups = e->cur_groups; a.plane_words = e->cur_words; a.ungrouped = e->d_cur_ungrouped; }
   return a;
 }
 
@@ -760,7 +766,7 @@ static int curves_step(cosim_engine* e, int first, int count, const float* cmd, 
   CurArgs a = curves_args(e);
   a.cmd = a.cmd_stride > 0 ? cmd : nullptr; a.info = info; a.term = term; a.trunc = trunc;
   a.first = first; a.count = count;
-  return launch_small<CUR_WAVES, 64 * CUR_WAVES>(curves_step_kernel, a, count, s);
+  return launch_small<CUR_WAVES, 64 * CUR_WAVES>(e->cur_groups > 0 ? curves_step_grouped_kernel : curves_step_kernel, a, count, s);
 }
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode with an empty stage
@@ -771,13 +777,17 @@ static int curves_begin(cosim_engine* e, const uint8_t* mask, const int* src, in
   return launch_small<CUR_WAVES, 64 * CUR_WAVES>(curves_begin_kernel, a, e->n_envs, s);
 }
 
-// every cell back to empty
-static int curves_zero(cosim_engine* e, hipStream_t s) { return launch_small<1, 256>(curves_clear_kernel, curves_args(e), 2 * e->cur.n_items, s); }
+// every cell back to empty; with groups every plane, and the `ungrouped` word to zero
+static int curves_zero(cosim_engine* e, hipStream_t s) {
+  if (e->cur_groups > 0) return launch_small<1, 256>(curves_clear_grouped_kernel, curves_args(e), 2 * e->cur.n_items * e->cur_groups, s);
+  return launch_small<1, 256>(curves_clear_kernel, curves_args(e), 2 * e->cur.n_items, s);
+}
 
 // the curves go with their table (the caller has waited for the device)
 static void curves_free(cosim_engine* e) {
-  (void)hipFree(e->d_cur); (void)hipFree(e->d_cur_stage); (void)hipFree(e->d_cur_clk); (void)hipFree(e->d_cur_cells);
+  (void)hipFree(e->d_cur); (void)hipFree(e->d_cur_stage); (void)hipFree(e->d_cur_clk); (void)hipFree(e->d_cur_cells); (void)hipFree(e->d_cur_ungrouped);
   e->d_cur = nullptr; e->d_cur_stage = nullptr; e->d_cur_clk = nullptr; e->d_cur_cells = nullptr; e->cur_words = 0;
+  e->d_cur_ungrouped = nullptr; e->cur_groups = 0; e->cur_group = nullptr;   // the groups go with the cells they split
   memset(&e->cur, 0, sizeof e->cur);
 }
 
@@ -1430,6 +1440,17 @@ static int newton_cap(const cosim_engine* e) {
 }
 static int ls_cap(const cosim_engine* e) { return e->max_ls < 0 ? e->model.ls_iterations : (e->max_ls < e->model.ls_iterations ? e->max_ls : e->model.ls_iterations); }
 
+// "scenario_curve_ungrouped": joins the ranges, waits and reads the device word (0 with no groups); held at INT_MAX
+static int curves_ungrouped(cosim_engine* e) {
+  if (e->cur_groups <= 0) return 0;
+  HIP_TRY(hipSetDevice(e->device));
+  RC_TRY(join_ranges(e, 0));
+  HIP_TRY(hipDeviceSynchronize());
+  unsigned v = 0;
+  HIP_TRY(hipMemcpy(&v, e->d_cur_ungrouped, sizeof v, hipMemcpyDeviceToHost));
+  return v > 2147483647u ? 2147483647 : (int)v;
+}
+
 int cosim_query(const cosim_engine_t* e, const char* name) {
   if (!e || !name) return fail(COSIM_EINVAL, "cosim_query: null argument");
   std::string n(name);
@@ -1474,6 +1495,8 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "scenario_check_slots") return e->chk_slots;                      // verdict records per env
   if (n == "scenario_curve_items") return e->cur.n_items;   // curve items of the table (0: no curves, no launches)
   if (n == "scenario_curve_words") return (int)e->cur_words;   // 32-bit words of all cells (at most 2^26)
+  if (n == "scenario_curve_groups") return e->cur_groups;   // G of cosim_scenario_curves_groups (0: no groups)
+  if (n == "scenario_curve_ungrouped") return curves_ungrouped(const_cast<cosim_engine_t*>(e));   // synchronising: joins, reads one device word
   if (n == "scenario_curve_stage_words") return e->cur.n_scn > 0 ? e->cur.SW : 0;   // stage words per env
   if (n == "scenario_check_words") return e->chk.n_scn > 0 ? checks_words(e->chk.I) : 0;   // 32-bit words of a verdict record: 8 + 2 I
   if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
@@ -2386,15 +2409,41 @@ int cosim_scenario_curves_clear(cosim_engine_t* e) {
   return COSIM_OK;
 }
 
-// The cells, uint32[scenario_curve_words], of the episodes that have ended; joins the ranges, asynchronous on the caller's stream
-// otherwise.
+// Groups of the curves that are set: the cells become n_groups planes, and an ended episode is folded into the plane its env's word of
+// group_dev ([n_envs] int32, the caller's, kept alive by the caller) names when the fold reads it.  n_groups = 0: back to one plane.
+// Every call empties the cells.  Refusals first, then join and wait, allocate, clear, begin.
+int cosim_scenario_curves_groups(cosim_engine_t* e, int n_groups, const int32_t* group_dev) {
+  if (!e) return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: null engine");
+  if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: no curves are set (cosim_scenario_curves_set): groups split the cells of curves");
+  if (n_groups < 0 || n_groups > CUR_MAX_GROUPS)
+    return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: n_groups " + std::to_string(n_groups) + " outside 0..64 (0: no groups)");
+  if (n_groups > 0 && !group_dev) return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: n_groups " + std::to_string(n_groups) + " with a null group_dev");
+  if ((size_t)n_groups * e->cur_words * sizeof(unsigned) > CUR_MAX_BYTES)
+    return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: " + std::to_string(n_groups) + " planes of " + std::to_string(e->cur_words) +
+                                  " words: the cells would exceed 256 MiB (a design limit)");
+  HIP_TRY(hipSetDevice(e->device));
+  RC_TRY(table_quiesce(e, 0));
+  // the new planes replace the old ones only once both allocations stand (a failure leaves the cells and the groups that were set)
+  unsigned* cells = nullptr;
+  unsigned* lost = e->d_cur_ungrouped;
+  hipError_t r = hipMalloc(&cells, (size_t)(n_groups > 0 ? n_groups : 1) * e->cur_words * sizeof(unsigned));
+  if (r == hipSuccess && n_groups > 0 && !lost) r = hipMalloc(&lost, sizeof(unsigned));
+  if (r != hipSuccess) { (void)hipFree(cells); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_groups: ") + hipGetErrorString(r)); }
+  (void)hipFree(e->d_cur_cells);
+  e->d_cur_cells = cells; e->d_cur_ungrouped = lost;
+  e->cur_groups = n_groups; e->cur_group = n_groups > 0 ? group_dev : nullptr;
+  return cosim_scenario_curves_clear(e);
+}
+
+// The cells, uint32[max(G, 1) * scenario_curve_words] (plane after plane), of the episodes that have ended; joins the ranges,
+// asynchronous on the caller's stream otherwise.
 int cosim_scenario_curves_get(cosim_engine_t* e, uint32_t* cells_dev, void* stream) {
   if (!e || !cells_dev) return fail(COSIM_EINVAL, "cosim_scenario_curves_get: null argument");
   if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_get: no curves are set (cosim_scenario_curves_set)");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
   RC_TRY(join_ranges(e, cs));
-  HIP_TRY(hipMemcpyAsync(cells_dev, e->d_cur_cells, e->cur_words * sizeof(unsigned), hipMemcpyDeviceToDevice, cs));
+  HIP_TRY(hipMemcpyAsync(cells_dev, e->d_cur_cells, (size_t)(e->cur_groups > 0 ? e->cur_groups : 1) * e->cur_words * sizeof(unsigned), hipMemcpyDeviceToDevice, cs));
   return COSIM_OK;
 }
 

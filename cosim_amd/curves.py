@@ -17,6 +17,7 @@ import numpy as np
 from .checks import UP, _signal
 
 NONE_BITS, NONFINITE_BITS = 0x7FC00000, 0x7FC00001
+MAX_GROUPS = 64                                   # planes of grouped cells (cosim_scenario_curves_groups)
 TRUNCATED, TERMINATED = 0, 1                       # outcome classes
 OUTCOMES = {None: None, "truncated": TRUNCATED, "terminated": TERMINATED}
 FIX = 1 << 20                                     # the sum is in units of 2^-20, samples clamped to +-2^20
@@ -141,9 +142,15 @@ class Curve:
 class Curves:
     """The cells of a table's curve items.  ``cells`` uint32 ``[words]`` is what the engine keeps (include/cosim.h); ``adr`` int64 ``[S
     + 1]`` the items of every scenario; ``spec`` int64 ``[n, 5]`` (t0, t1, every, signal, index) + ``bins`` ``[n]``, ``lohi`` float32
-    ``[n, 2]``, ``names[s][k]``.  ``curves[s, k]`` (k: an item's position or name) is that item's ``Curve``."""
+    ``[n, 2]``, ``names[s][k]``.  ``curves[s, k]`` (k: an item's position or name) is that item's ``Curve``.
 
-    def __init__(self, cells, adr, spec, lohi, bins, names):
+    With ``groups=G`` (``cosim_scenario_curves_groups``) ``cells`` is ``[G * W]``: G planes, each a whole cell image of W words, plane g
+    the episodes whose env carried group word g when they ended; ``group_names`` names the planes (default ``"0" .. "G-1"``) and
+    ``ungrouped`` counts the episodes whose word was outside ``[0, G)`` (they are in no plane).  ``curves[s, k]`` stays the curve over
+    ALL groups -- the planes merged, exactly -- so code written for ungrouped curves reads the same numbers; ``curves[s, k, g]`` (g: a
+    plane's index or name) is one group's curve, ``group(g)`` that plane as a plain ``Curves``, ``by_group()`` all of them by name."""
+
+    def __init__(self, cells, adr, spec, lohi, bins, names, groups=1, group_names=None, ungrouped=0):
         self.adr = np.ascontiguousarray(adr, dtype=np.int64).reshape(-1)
         self.spec = np.ascontiguousarray(spec, dtype=np.int64).reshape(-1, 5)
         self.lohi = np.ascontiguousarray(lohi, dtype=np.float32).reshape(-1, 2)
@@ -151,25 +158,39 @@ class Curves:
         self.names = [list(n) for n in names]
         self._lay = layout((self.adr, self.spec[:, :3], None, None, None, None, self.bins))
         self.cells = np.ascontiguousarray(cells, dtype=np.uint32).reshape(-1)
-        if self.cells.size != self._lay["words"]:
-            raise ValueError(f"Curves: {self.cells.size} cell words, the items need {self._lay['words']}")
+        if isinstance(groups, bool) or not isinstance(groups, (int, np.integer)) or not 1 <= int(groups) <= MAX_GROUPS:
+            raise ValueError(f"Curves: groups {groups!r}: an integer 1..{MAX_GROUPS}")
+        self.groups, self.ungrouped = int(groups), int(ungrouped)
+        self.grouped = self.groups > 1 or group_names is not None    # a group axis: ``summary`` and ``save`` carry it
+        self.group_names = [str(g) for g in range(self.groups)] if group_names is None else [str(x) for x in group_names]
+        if len(self.group_names) != self.groups or len(set(self.group_names)) != self.groups:
+            raise ValueError(f"Curves: group_names must be {self.groups} different strings, got {self.group_names}")
+        if self.cells.size != self.groups * self._lay["words"]:
+            raise ValueError(f"Curves: {self.cells.size} cell words, the items need {self._lay['words']}" +
+                             (f" in each of {self.groups} planes" if self.groups > 1 else ""))
+
+    @property
+    def plane_words(self) -> int:
+        """W: the cell words of one plane."""
+        return int(self._lay["words"])
 
     @classmethod
-    def from_raw(cls, cells, table) -> "Curves":
+    def from_raw(cls, cells, table, groups=1, group_names=None, ungrouped=0) -> "Curves":
         """From what ``cosim_scenario_curves_get`` copies and the ``ScenarioTable`` whose curves were set."""
         adr, t, signal, index, lo, hi, bins = table.pack_curves()
         return cls(cells, adr, np.concatenate([t.astype(np.int64), signal[:, None].astype(np.int64), index[:, None].astype(np.int64)], axis=1),
-                   np.stack([lo, hi], axis=1), bins, table.curve_item_names())
+                   np.stack([lo, hi], axis=1), bins, table.curve_item_names(), groups=groups, group_names=group_names, ungrouped=ungrouped)
 
     @classmethod
-    def empty(cls, table) -> "Curves":
-        c = cls.from_raw(np.zeros(layout(table.pack_curves())["words"], dtype=np.uint32), table)
+    def empty(cls, table, groups=1, group_names=None) -> "Curves":
+        c = cls.from_raw(np.zeros(groups * layout(table.pack_curves())["words"], dtype=np.uint32), table, groups, group_names)
         for _, _, base, T, _ in c._blocks():
-            c.cells[base + 2 * T:base + 3 * T] = 0xFFFFFFFF
+            for g in range(c.groups):
+                c.cells[g * c.plane_words + base + 2 * T:g * c.plane_words + base + 3 * T] = 0xFFFFFFFF
         return c
 
     def _blocks(self):
-        """``(flat item, class, first word, T, B)`` of every block of cells."""
+        """``(flat item, class, first word, T, B)`` of every block of cells of ONE plane."""
         L = self._lay
         for i in range(len(self.bins)):
             for c in (0, 1):
@@ -177,11 +198,38 @@ class Curves:
 
     def word_kinds(self) -> np.ndarray:
         """Per cell word how two fleets' cells merge: 0 add as uint32, 1 unsigned min, 2 unsigned max, 3 half of an int64 that adds
-        (the two halves are neighbours)."""
-        kind = np.zeros(self.cells.size, dtype=np.int8)
+        (the two halves are neighbours).  With groups: one plane's kinds tiled over the planes."""
+        kind = np.zeros(self.plane_words, dtype=np.int8)
         for _, _, b, T, _ in self._blocks():
             kind[b + 2 * T:b + 3 * T], kind[b + 3 * T:b + 4 * T], kind[b + 4 * T:b + 6 * T] = 1, 2, 3
-        return kind
+        return np.tile(kind, self.groups)
+
+    def _group_index(self, g) -> int:
+        if isinstance(g, str):
+            if g not in self.group_names:
+                raise KeyError(f"Curves: no group '{g}' (the groups are {self.group_names})")
+            return self.group_names.index(g)
+        if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= int(g) < self.groups:
+            raise KeyError(f"Curves: no group {g!r} (there are {self.groups})")
+        return int(g)
+
+    def group(self, g) -> "Curves":
+        """Plane ``g`` (an index or a name) as a plain ungrouped ``Curves`` (a copy of its words)."""
+        g = self._group_index(g)
+        W = self.plane_words
+        return Curves(self.cells[g * W:(g + 1) * W].copy(), self.adr, self.spec, self.lohi, self.bins, self.names)
+
+    def by_group(self) -> dict:
+        """``{group name: that plane as a plain Curves}``, in plane order."""
+        return {name: self.group(g) for g, name in enumerate(self.group_names)}
+
+    def merged(self) -> "Curves":
+        """The planes merged into one by ``merge``'s rule, as a plain ungrouped ``Curves``: the cells the same episodes give without
+        groups (when ``ungrouped == 0``).  Of ungrouped curves: a copy."""
+        out = self.group(0)
+        for g in range(1, self.groups):
+            out = out.merge(self.group(g))
+        return out
 
     @property
     def n_scenarios(self) -> int:
@@ -192,6 +240,10 @@ class Curves:
         return [(s, k) for s in range(self.n_scenarios) for k in range(int(self.adr[s + 1] - self.adr[s]))]
 
     def __getitem__(self, key) -> Curve:
+        if len(key) == 3:
+            return self.group(key[2])[key[0], key[1]]
+        if self.groups > 1:
+            return self.merged()[key]
         s, k = key
         if not 0 <= s < self.n_scenarios:
             raise KeyError(f"Curves: no scenario {s}")
@@ -216,24 +268,37 @@ class Curves:
         return (np.array_equal(self.adr, other.adr) and np.array_equal(self.spec, other.spec) and np.array_equal(self.bins, other.bins)
                 and np.array_equal(self.lohi.view(np.uint32), other.lohi.view(np.uint32)))
 
+    def _same_groups(self, other) -> bool:
+        return self.groups == other.groups and self.group_names == other.group_names
+
     def merge(self, other: "Curves") -> "Curves":
-        """The curves of both fleets together, exact: counts, sums and histograms add as integers, the extremes merge on their keys."""
+        """The curves of both fleets together, exact: counts, sums and histograms add as integers, the extremes merge on their keys.
+        Grouped curves merge plane by plane (the same G and names on both sides) and their ``ungrouped`` counts add."""
         if not self._same_items(other):
             raise ValueError("Curves.merge: the two sets of curves were taken with different items")
+        if not self._same_groups(other):
+            raise ValueError(f"Curves.merge: the two sets of curves were taken with different groups: {self.groups} {self.group_names} "
+                             f"against {other.groups} {other.group_names}")
         out = self.cells.copy()
-        for _, _, b, T, B in self._blocks():
-            a, o = out[b:b + (B + 8) * T], other.cells[b:b + (B + 8) * T]
-            for lo, hi in ((0, 2 * T), (6 * T, (B + 8) * T)):
-                a[lo:hi] += o[lo:hi]
-            a[2 * T:3 * T] = np.minimum(a[2 * T:3 * T], o[2 * T:3 * T])
-            a[3 * T:4 * T] = np.maximum(a[3 * T:4 * T], o[3 * T:4 * T])
-            s = np.ascontiguousarray(a[4 * T:6 * T]).view(np.int64) + np.ascontiguousarray(o[4 * T:6 * T]).view(np.int64)
-            a[4 * T:6 * T] = s.view(np.uint32)
-        return Curves(out, self.adr, self.spec, self.lohi, self.bins, self.names)
+        W = self.plane_words
+        for _, _, b0, T, B in self._blocks():
+            for g in range(self.groups):
+                b = g * W + b0
+                a, o = out[b:b + (B + 8) * T], other.cells[b:b + (B + 8) * T]
+                for lo, hi in ((0, 2 * T), (6 * T, (B + 8) * T)):
+                    a[lo:hi] += o[lo:hi]
+                a[2 * T:3 * T] = np.minimum(a[2 * T:3 * T], o[2 * T:3 * T])
+                a[3 * T:4 * T] = np.maximum(a[3 * T:4 * T], o[3 * T:4 * T])
+                s = np.ascontiguousarray(a[4 * T:6 * T]).view(np.int64) + np.ascontiguousarray(o[4 * T:6 * T]).view(np.int64)
+                a[4 * T:6 * T] = s.view(np.uint32)
+        return Curves(out, self.adr, self.spec, self.lohi, self.bins, self.names, groups=self.groups,
+                      group_names=self.group_names if self.grouped else None, ungrouped=self.ungrouped + other.ungrouped)
 
     def episodes(self) -> np.ndarray:
         """int64 ``[S, 2]``: per scenario and outcome class, the samples (finite or not) of its fullest time bin -- the ended episodes
-        that reached that bin; an episode that ended ahead of every window is in none."""
+        that reached that bin; an episode that ended ahead of every window is in none.  With groups: of the planes merged."""
+        if self.groups > 1:
+            return self.merged().episodes()
         out = np.zeros((self.n_scenarios, 2), dtype=np.int64)
         for s, k in self.items():
             c = self[s, k]
@@ -241,7 +306,12 @@ class Curves:
         return out
 
     def summary(self) -> dict:
-        """Item count, episodes folded (``episodes()``, summed over the scenarios) and samples, by outcome class."""
+        """Item count, episodes folded (``episodes()``, summed over the scenarios) and samples, by outcome class.  Grouped curves add
+        ``groups``, ``ungrouped`` and ``by_group``: per group name that plane's own summary."""
+        if self.grouped:                                               # the planes merged, as without groups, and every plane's own
+            out = self.merged().summary()
+            out.update({"groups": self.groups, "ungrouped": self.ungrouped, "by_group": {name: p.summary() for name, p in self.by_group().items()}})
+            return out
         e = self.episodes().sum(axis=0)
         n = np.zeros(2, dtype=np.int64)
         bad = 0
@@ -256,14 +326,20 @@ class Curves:
         """One ``.npz`` of plain arrays (no pickle)."""
         I = max([len(n) for n in self.names] + [1])
         names = np.array([[(n[k] if k < len(n) else "") for k in range(I)] for n in self.names], dtype=np.str_).reshape(len(self.names), I)
-        np.savez(path, cells=self.cells, adr=self.adr, spec=self.spec, lohi=self.lohi, bins=self.bins, names=names)
+        more = {}
+        if self.grouped:                     # ungrouped curves keep the file of before there were groups
+            more = {"groups": np.int64(self.groups), "group_names": np.array(self.group_names, dtype=np.str_), "ungrouped": np.int64(self.ungrouped)}
+        np.savez(path, cells=self.cells, adr=self.adr, spec=self.spec, lohi=self.lohi, bins=self.bins, names=names, **more)
 
     @classmethod
     def load(cls, path: str) -> "Curves":
         with np.load(path, allow_pickle=False) as z:
             adr = z["adr"]
             names = [[str(z["names"][s, k]) for k in range(int(adr[s + 1] - adr[s]))] for s in range(len(adr) - 1)]
-            return cls(z["cells"], adr, z["spec"], z["lohi"], z["bins"], names)
+            if "groups" not in z.files:                                # a file without a group axis
+                return cls(z["cells"], adr, z["spec"], z["lohi"], z["bins"], names)
+            return cls(z["cells"], adr, z["spec"], z["lohi"], z["bins"], names, groups=int(z["groups"]),
+                       group_names=[str(x) for x in z["group_names"]], ungrouped=int(z["ungrouped"]))
 
 
 def same_curves(a: Curves, b: Curves) -> Optional[str]:
@@ -271,9 +347,16 @@ def same_curves(a: Curves, b: Curves) -> Optional[str]:
     difference."""
     if not a._same_items(b):
         return "the items differ"
+    if not a._same_groups(b):
+        return f"the groups differ: {a.groups} {a.group_names} against {b.groups} {b.group_names}"
+    if a.ungrouped != b.ungrouped:
+        return f"ungrouped episodes: {a.ungrouped} against {b.ungrouped}"
     bad = np.nonzero(a.cells != b.cells)[0]
     if len(bad):
         w = int(bad[0])
+        if a.groups > 1:
+            g = w // a.plane_words
+            return f"{len(bad)} words differ in all; group {g} ('{a.group_names[g]}'): {same_curves(a.group(g), b.group(g))}"
         for i, c, base, T, B in a._blocks():
             if base <= w < base + int(a._lay["cw"][i]):
                 r = w - base
@@ -297,14 +380,22 @@ def hist_row(v, lo, hi, inv_w, B: int) -> int:
 
 
 def reference_curves(table, info_rows, terminated, truncated, commands, qpos, qvel, clock, scenario_rows, nu: int, begins: Sequence = (),
-                     clears: Sequence = ()) -> Curves:
-    """Numpy twin of ``curves_step_kernel`` / ``curves_begin_kernel`` (and of ``cosim_scenario_curves_clear``).
+                     clears: Sequence = (), groups=None, n_groups: int = 0, group_names=None) -> Curves:
+    """Numpy twin of ``curves_step_kernel`` / ``curves_step_grouped_kernel`` / ``curves_begin_kernel`` (and of
+    ``cosim_scenario_curves_clear``).
 
     The per-step records are ``reference_checks``'s (``cosim_amd/checks.py``): ``info_rows`` ``[K, N, info_dim]``, ``terminated`` /
     ``truncated`` ``[K, N]``, ``commands`` ``[K, N, >= command_dim]`` (or ``[N, .]``), ``qpos`` / ``qvel`` read back behind step k,
     ``clock`` ``[K + 1, N]`` (meta word 0 before step k, row K: after the last step), ``scenario_rows`` ``[K, N]``.  ``begins``: ``(k,
     mask or None, flag)`` -- the host cut the masked envs' episodes before step k (the flag is ignored: a curve keeps no flags).
-    ``clears``: steps k before which the cells were emptied and every env's episode begun anew."""
+    ``clears``: steps k before which the cells were emptied and every env's episode begun anew.
+
+    ``groups`` int ``[K, N]`` with ``n_groups = G >= 1``: each env's group word as the fold of step k reads it; the result is the grouped
+    twin -- an episode that ends in step k goes into plane ``groups[k, e]``, a word outside ``[0, G)`` into none (its stage is emptied and
+    ``ungrouped`` counts it; a clear zeroes the count)."""
+    G = int(n_groups)
+    if (groups is None) != (G == 0):
+        raise ValueError("reference_curves: groups ([K, N] ints) and n_groups (>= 1) go together")
     C = table._resolved_curves()
     csr = table.pack_curves()
     L = layout(csr)
@@ -319,14 +410,16 @@ def reference_curves(table, info_rows, terminated, truncated, commands, qpos, qv
     qpos, qvel = np.asarray(qpos, dtype=np.float32), np.asarray(qvel, dtype=np.float32)
     clock_all = np.asarray(clock, dtype=np.int64).reshape(K + 1, N)
     rows_all = np.asarray(scenario_rows, dtype=np.int64).reshape(K, N)
-    out = Curves.empty(table)
+    out = Curves.empty(table, max(G, 1), group_names)
     cells = out.cells
+    grp = None if groups is None else np.asarray(groups, dtype=np.int64).reshape(K, N)
     stage = np.full((N, max(L["stage_words"], 1)), NONE_BITS, dtype=np.int64)
     clk = clock_all[0].copy()
 
     def begin(k):
         if k in clears:
-            cells[:] = Curves.empty(table).cells
+            cells[:] = Curves.empty(table, max(G, 1)).cells
+            out.ungrouped = 0
             stage[:] = NONE_BITS
             clk[:] = clock_all[k]
         for kb, mask, _ in begins:
@@ -350,12 +443,21 @@ def reference_curves(table, info_rows, terminated, truncated, commands, qpos, qv
                         continue
                     bits = int(np.float32(_signal(sig, idx, info[k, e], c, qpos[k, e], qvel[k, e], int(nu))).view(np.uint32))
                     stage[e, L["soff"][adr[row] + j] + (t - t0) // every] = bits if (bits & 0x7F800000) != 0x7F800000 else NONFINITE_BITS
+                plane = 0
+                if done and grp is not None:
+                    plane = int(grp[k, e])
+                    if not 0 <= plane < G:                              # in no plane: the stage is emptied, the episode counted
+                        for j, it in enumerate(C[row]):
+                            i = int(adr[row]) + j
+                            stage[e, int(L["soff"][i]):int(L["soff"][i]) + int(L["T"][i])] = NONE_BITS
+                        out.ungrouped += 1
+                        done = False
                 if done:
                     cls = 1 if te else 0
                     for j, it in enumerate(C[row]):
                         i = int(adr[row]) + j
                         T, B = int(L["T"][i]), int(it[7])
-                        base = int(L["coff"][i] + cls * L["cw"][i])
+                        base = plane * int(L["words"]) + int(L["coff"][i] + cls * L["cw"][i])
                         st = stage[e, int(L["soff"][i]):int(L["soff"][i]) + T]
                         for b in np.nonzero(st != NONE_BITS)[0]:
                             bits = int(st[b])

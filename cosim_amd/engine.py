@@ -118,6 +118,7 @@ def load_library():
     L.cosim_scenario_curves_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.cosim_scenario_curves_get.argtypes = [vp, vp, vp]
     L.cosim_scenario_curves_clear.argtypes = [vp]
+    L.cosim_scenario_curves_groups.argtypes = [vp, ci, vp]
     L.cosim_fall_set.argtypes = [vp, ctypes.c_float, ctypes.c_float, ci, vp, ci]
     L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
     L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
@@ -143,8 +144,8 @@ def load_library():
                "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get",
                "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get", "cosim_scenario_params_set",
                "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get", "cosim_scenario_curves_set",
-               "cosim_scenario_curves_get", "cosim_scenario_curves_clear", "cosim_policy_table_create", "cosim_policy_table_forward",
-               "cosim_policy_table_destroy", "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
+               "cosim_scenario_curves_get", "cosim_scenario_curves_clear", "cosim_scenario_curves_groups", "cosim_policy_table_create",
+               "cosim_policy_table_forward", "cosim_policy_table_destroy", "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
                "cosim_policy_table_rotate", "cosim_policy_table_forward_rotating", "cosim_policy_table_lists", "cosim_recurrent_table_rotate",
                "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists"):
         getattr(L, fn).restype = ci
@@ -163,7 +164,7 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
            "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get",
            "cosim_scenario_params_set", "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get",
-           "cosim_scenario_curves_set", "cosim_scenario_curves_get", "cosim_scenario_curves_clear",
+           "cosim_scenario_curves_set", "cosim_scenario_curves_get", "cosim_scenario_curves_clear", "cosim_scenario_curves_groups",
            "cosim_policy_table_create", "cosim_policy_table_forward", "cosim_policy_table_destroy",
            "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
            "cosim_policy_table_rotate", "cosim_policy_table_forward_rotating", "cosim_policy_table_lists",
@@ -438,8 +439,13 @@ class Engine:
         self._check(self.L.cosim_scenario_curves_set(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, signal.ctypes.data,
                                                      index.ctypes.data, lo.ctypes.data, hi.ctypes.data, bins.ctypes.data))
 
+    def scenario_curves_groups(self, n_groups: int, group_ptr=None):
+        """``cosim_scenario_curves_groups``: the cells become ``n_groups`` planes keyed by the int32 ``[N]`` device words at ``group_ptr``
+        (the caller keeps them alive); ``n_groups = 0``: no groups.  Every call empties the cells."""
+        self._check(self.L.cosim_scenario_curves_groups(self.h, int(n_groups), group_ptr))
+
     def scenario_curves_get(self, cells_ptr, stream=None):
-        """``cosim_scenario_curves_get``: the cells, uint32 ``[scenario_curve_words]``."""
+        """``cosim_scenario_curves_get``: the cells, uint32 ``[max(scenario_curve_groups, 1) * scenario_curve_words]``."""
         self._check(self.L.cosim_scenario_curves_get(self.h, cells_ptr, stream))
 
     def scenario_curves_clear(self):

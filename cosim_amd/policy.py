@@ -654,6 +654,21 @@ class _FleetTable:
             ended = ended != 0
         t.maximum(self.episode, self.episode + ended, out=self.episode)
 
+    def curve_groups(self):
+        """``(group, K, names)`` for ``BatchedEnv.set_curve_groups``: ``group`` is an int32 device tensor ``[N]`` with each env's policy
+        index, which the curves' fold reads when an episode ends.  A rotating table hands out ``policy_now`` itself -- it is rewritten
+        only by the table's forward, so behind the step that ended an episode it still names the policy that drove it; a static table
+        a persistent tensor of ``policy_of_env``, created once.  The table must drive the env from its first step."""
+        t = self.torch
+        if self.device.type != "cuda":
+            raise ValueError(f"{type(self).__name__}.curve_groups: the table is on '{self.device}'; the curves' fold reads the group words on the "
+                             "GPU that runs the env")
+        if self.rotate_every is not None:
+            return self.policy_now, len(self.paths), list(self.names)
+        if getattr(self, "_curve_group", None) is None:
+            self._curve_group = t.as_tensor(np.ascontiguousarray(self.policy_of_env, dtype=np.int32), device=self.device)
+        return self._curve_group, len(self.paths), list(self.names)
+
     def rewind(self):
         """Back to episode 0 for every env: the counters of a rotating table are zeroed (``reset()`` without a mask leaves them)."""
         if self.rotate_every is not None:
@@ -706,7 +721,7 @@ class PolicyTable(_FleetTable):
     of the grouped kernel (``cosim_policy_table_forward``, csrc/cosim_mlp.hip) evaluates all of them -- every env gets the bits
     ``MLPPolicy(file, fused=True)`` gives it.  All policies meet the same terrain, spawn table, scenario table, fall rule and noise
     streams (those are keyed by global env id), so one run is the comparison; ``EpisodeLedger.by_policy`` / ``Verdicts.by_policy``
-    break the outcomes down.
+    break the outcomes down, and ``env.set_curve_groups(table)`` splits the response curves by policy (``curve_groups()``).
 
     ``assign``: ``"interleave"`` -- ``g mod K``; ``"cross"`` -- ``(g // S) mod K`` with ``S = scenarios`` (in scenario mode ``env``, where
     env ``g`` runs scenario ``g mod S``, every (scenario, policy) pair gets the same share of envs); or an int array with one entry per

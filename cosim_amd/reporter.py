@@ -166,13 +166,18 @@ class FleetReporter:
         if getattr(self.env, "check_slots", 0) > 0:
             out.setdefault("episodes", {})["checks"] = self.checks()
         if getattr(self.env, "curves_armed", False):
-            out.setdefault("episodes", {})["curves"] = self.fleet_curves().summary()
+            cs = self.fleet_curves().summary()
+            if "by_group" in cs:                                       # set_curve_groups(policy table): the planes are the policies
+                cs["by_policy"] = cs.pop("by_group")
+            out.setdefault("episodes", {})["curves"] = cs
         return out
 
     def fleet_curves(self):
         """The env's response curves (``BatchedEnv(scenarios=TABLE, curves=True)``) as a ``Curves``.  Under ``torch.distributed`` the
         cells are all-reduced -- SUM for the counts, the fixed-point sums and the histograms, MIN / MAX for the extremes' keys -- so
-        ranks that set the same table hold one fleet's curves, exactly."""
+        ranks that set the same table hold one fleet's curves, exactly.  With groups set (``env.set_curve_groups``) the reduction
+        covers all G planes (one plane's word kinds, tiled) and the ``ungrouped`` count; ``summary()`` then reports ``by_policy``: per
+        group name that plane's own summary."""
         import torch.distributed as dist
         from .curves import Curves
         cv = self.env.curves()
@@ -186,7 +191,10 @@ class FleetReporter:
                 dist.all_reduce(x, op=op)
                 y = x.cpu().numpy()
                 cells[kind == k] = y.view(np.uint32) if view is not None else y.astype(np.uint32)
-            cv = Curves(cells, cv.adr, cv.spec, cv.lohi, cv.bins, cv.names)
+            lost = t.tensor([cv.ungrouped], dtype=t.int64, device=self.env.device)
+            dist.all_reduce(lost, op=dist.ReduceOp.SUM)
+            cv = Curves(cells, cv.adr, cv.spec, cv.lohi, cv.bins, cv.names, groups=cv.groups, group_names=cv.group_names if cv.grouped else None,
+                        ungrouped=int(lost.item()))
         return cv
 
     def checks(self) -> dict:

@@ -444,10 +444,30 @@ int cosim_scenario_checks_get(cosim_engine_t* e, int32_t* records_dev, int32_t* 
  * none), "scenario_curve_words" (all cells) and "scenario_curve_stage_words" (per env). */
 int cosim_scenario_curves_set(cosim_engine_t* e, int n_scn, const int32_t* adr, const int32_t* t /*[n][3]: t0, t1, every*/,
                               const int32_t* signal, const int32_t* index, const float* lo, const float* hi, const int32_t* bins);
-/* cells_dev uint32[scenario_curve_words].  Joins the ranges, like cosim_ledger_get; asynchronous on `stream` otherwise. */
+/* cells_dev uint32[max(G, 1) * scenario_curve_words]: with groups (below) plane after plane.  Joins the ranges, like
+ * cosim_ledger_get; asynchronous on `stream` otherwise. */
 int cosim_scenario_curves_get(cosim_engine_t* e, uint32_t* cells_dev, void* stream);
-/* Empties the cells and begins every env's episode anew (what was staged is discarded).  Joins the ranges and waits for the device. */
+/* Empties the cells (every plane, and the "ungrouped" count) and begins every env's episode anew (what was staged is discarded).
+ * Joins the ranges and waits for the device. */
 int cosim_scenario_curves_clear(cosim_engine_t* e);
+/* Groups: split the cells of the curves that are set by one caller-supplied word per env.  With n_groups = G (1..64) the cells are G
+ * planes, each a whole cell image of the layout above (W = "scenario_curve_words" words, the same offsets), plane g at word g * W.
+ * group_dev is int32[n_envs] on the device, owned and kept alive by the caller, as the history buffers are.  Sampling, staging and the
+ * clock do not change; at the fold (a row with a done flag) curves_step_grouped_kernel reads the env's word once and folds the episode
+ * into that plane.  ATTRIBUTION: an episode belongs to the word as it stands when the fold reads it -- behind the step that ended the
+ * episode, on the range's own stream, ahead of whatever the caller enqueues on that stream next.  The engine reads the word on done
+ * rows only and never writes it; its contents may change between steps and between replays of a captured graph.  A word outside
+ * [0, G) touches no cell: the episode's stage still goes back to "no sample" and one device word counts it.  The planes merged word
+ * kind by word kind (counts, sums, histograms add; extremes merge on their keys) are the cells without groups.
+ * n_groups = 0 goes back to one plane and curves_step_kernel (no launch, pointer or byte then differs from curves without groups).
+ * Every call empties the cells and begins every env's episode anew, as cosim_scenario_curves_set does.  An in-place rewrite of the
+ * items (cosim_scenario_curves_set with the same counts and sizes) keeps the groups; whatever frees or reallocates the curves
+ * (other sizes, clearing them, another S, clearing the table) drops them.  The pointer and G are kernel arguments: set the groups
+ * before capturing a graph.  COSIM_EINVAL, naming the value: no curves set, n_groups outside 0..64, a null group_dev with
+ * n_groups > 0, G * W * 4 bytes above 256 MiB.  cosim_query answers "scenario_curve_groups" (G, 0: none) and
+ * "scenario_curve_ungrouped" (ended episodes whose word was outside [0, G) since the cells were last emptied) -- the latter is a
+ * SYNCHRONISING query: it joins the ranges, waits for the device and reads one device word. */
+int cosim_scenario_curves_groups(cosim_engine_t* e, int n_groups, const int32_t* group_dev);
 
 /* Fall rules (the reference ends an episode early only through a robot's own _is_done, which is an empty body list for
  * flamingo_light_v1 and False for w4_p_v2 and humanoid_p_v0): the step kernels end an episode on the posture of the state a control
