@@ -883,11 +883,10 @@ struct PolRotate {
   int32_t* d_ntiles = nullptr;    // [n_ranges] the tiles each range holds now
 };
 
-// what cosim_policy_table_create hands out: the device copies of a checked table and the launch shape of every range
-struct cosim_policy_table {
-  int n = 0, device = 0, ld = 0, n_tiles = 0, K = 0;
+// what both kinds of table are made of: the device copies of a checked table and the launch shape of every range
+struct TableCore {
+  int n = 0, device = 0, K = 0, n_tiles = 0;
   float* d_image = nullptr;
-  PolDesc* d_desc = nullptr;
   int32_t* d_rows = nullptr;
   PolTile* d_tiles = nullptr;
   std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count); armed: (tile_first, capacity)
@@ -895,28 +894,62 @@ struct cosim_policy_table {
   PolRotate rot;
 };
 
-// what cosim_recurrent_table_create hands out: as above, with the launch's two leading dimensions and the state tensors' row stride
-struct cosim_recurrent_table {
-  int n = 0, device = 0, ld_m = 0, ld_x = 0, hmax = 0, n_tiles = 0, K = 0;
-  float* d_image = nullptr;
-  RecDesc* d_desc = nullptr;
-  int32_t* d_rows = nullptr;
-  PolTile* d_tiles = nullptr;
-  std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count); armed: (tile_first, capacity)
-  std::vector<int32_t> por, ranges;
-  PolRotate rot;
+// what cosim_policy_table_create hands out: the core, the descriptors and the launch's leading dimension
+struct cosim_policy_table : TableCore {
+  PolDesc* d_desc = nullptr;
+  int ld = 0;
 };
 
-// ---- rotation, the same for both kinds of table (Table: one of the two structs above; fn: the entry point's name for the messages)
+// what cosim_recurrent_table_create hands out: as above, with the launch's two leading dimensions and the state tensors' row stride
+struct cosim_recurrent_table : TableCore {
+  RecDesc* d_desc = nullptr;
+  int ld_m = 0, ld_x = 0, hmax = 0;
+};
+
+// `Kernel` needs `lds` bytes of dynamic LDS on the current device: the attribute is raised when that is more than any call before asked
+// for.  The high-water marks are per kernel and per device -- the attribute belongs to the function on the device it was set on.
+template <auto Kernel>
+static int kernel_needs_lds(size_t lds, const char* fn) {
+  static size_t lds_allowed[64] = {0};
+  int dev = 0;
+  HIP_TRY(hipGetDevice(&dev));
+  if (dev < 0 || dev >= 64) return fail(COSIM_EINVAL, std::string(fn) + ": device index out of range");
+  if (lds > lds_allowed[dev]) {
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    lds_allowed[dev] = lds;
+  }
+  return COSIM_OK;
+}
+
+// Fills a fresh core on the current device from create's checked arrays: the image, the descriptors (`desc_bytes` of them, into
+// *d_desc), the row list and the tile list.  On an error the caller destroys the table, which frees whatever was allocated so far.
+static int table_upload(TableCore& t, const std::vector<float>& image, const void* desc, size_t desc_bytes, void** d_desc, const PolTiles& tl) {
+  t.n = (int)tl.rows.size(); t.n_tiles = (int)tl.tiles.size(); t.tile_span = tl.tile_span;
+  HIP_TRY(hipGetDevice(&t.device));
+  const size_t b_img = image.size() * 4, b_rows = tl.rows.size() * 4, b_tiles = tl.tiles.size() * sizeof(PolTile);
+  HIP_TRY(hipMalloc(&t.d_image, b_img)); HIP_TRY(hipMalloc(d_desc, desc_bytes)); HIP_TRY(hipMalloc(&t.d_rows, b_rows)); HIP_TRY(hipMalloc(&t.d_tiles, b_tiles));
+  HIP_TRY(hipMemcpy(t.d_image, image.data(), b_img, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(*d_desc, desc, desc_bytes, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(t.d_rows, tl.rows.data(), b_rows, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(t.d_tiles, tl.tiles.data(), b_tiles, hipMemcpyHostToDevice));
+  return COSIM_OK;
+}
+
 static void rotate_free(PolRotate& r) {
   (void)hipFree(r.d_base); (void)hipFree(r.d_ranges); (void)hipFree(r.d_ntiles);
   r = PolRotate();
 }
 
+// everything table_upload and table_rotate allocated (the descriptors are the table's own)
+static void table_free(TableCore& t) {
+  (void)hipFree(t.d_image); (void)hipFree(t.d_rows); (void)hipFree(t.d_tiles);
+  rotate_free(t.rot);
+}
+
+// ---- rotation, the same for both kinds of table (fn: the entry point's name for the messages)
 // Arms a table: keeps create's assignment on the device as the base, lays the static lists out again with every range's span of
 // tiles as wide as policy_tile_capacity (padding: count 0) and swaps the tile buffer for that one.  The table is unchanged on failure.
-template <class Table>
-static int table_rotate(Table* p, int every, const std::string& fn) {
+static int table_rotate(TableCore* p, int every, const std::string& fn) {
   if (!p) return fail(COSIM_EINVAL, fn + ": null argument");
   if (every < 1) return fail(COSIM_EINVAL, fn + ": every " + std::to_string(every) + " is below 1");
   if (p->rot.every) return fail(COSIM_EINVAL, fn + ": the table already rotates (every " + std::to_string(p->rot.every) + ")");
@@ -960,8 +993,7 @@ static int table_rotate(Table* p, int every, const std::string& fn) {
 }
 
 // What the plain and the rotating forward of both tables check (pointers: the entry point's own arrays are all there).  0 or the error.
-template <class Table>
-static int table_forward_checks(Table* p, bool pointers, bool rotating, const int32_t* episode_dev, int range, const char* fn) {
+static int table_forward_checks(TableCore* p, bool pointers, bool rotating, const int32_t* episode_dev, int range, const char* fn) {
   const auto who = [fn]() { return std::string(fn); };   // a message is only put together where a call is refused
   if (!p || !pointers || (rotating && !episode_dev)) return fail(COSIM_EINVAL, who() + ": null argument");
   if (rotating && !p->rot.every) return fail(COSIM_EINVAL, who() + ": the table does not rotate (cosim_*_table_rotate arms it)");
@@ -977,8 +1009,7 @@ static int table_forward_checks(Table* p, bool pointers, bool rotating, const in
   return COSIM_OK;
 }
 
-template <class Table>
-static int table_regroup(Table* p, int32_t* episode_dev, int32_t* policy_now_dev, const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range,
+static int table_regroup(TableCore* p, int32_t* episode_dev, int32_t* policy_now_dev, const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range,
                          hipStream_t s) {
   PolRegroupArgs g;
   g.base = p->rot.d_base; g.episode = episode_dev; g.policy_now = policy_now_dev; g.done_a = done_a_dev; g.done_b = done_b_dev;
@@ -990,8 +1021,7 @@ static int table_regroup(Table* p, int32_t* episode_dev, int32_t* policy_now_dev
 }
 
 // one range's lists as they stand, after everything queued on the device: rows_host [count of the range], tiles_host [its capacity][4]
-template <class Table>
-static int table_lists(Table* p, int range, int* rows_host, int* tiles_host, int* n_tiles_out, const std::string& fn) {
+static int table_lists(TableCore* p, int range, int* rows_host, int* tiles_host, int* n_tiles_out, const std::string& fn) {
   if (!p || !rows_host || !tiles_host || !n_tiles_out) return fail(COSIM_EINVAL, fn + ": null argument");
   const int n_ranges = (int)p->tile_span.size() / 2;
   if (range < 0 || range >= n_ranges) return fail(COSIM_EINVAL, fn + ": range " + std::to_string(range) + " outside 0.." + std::to_string(n_ranges - 1));
@@ -1029,14 +1059,7 @@ int cosim_mlp_forward(const float* x_dev, int n, int n_layers, const int* dims, 
   }
   a.x = x_dev; a.out = out_dev; a.nl = n_layers; a.n = n; a.clip = clip; a.ld = maxd | 1;
   const size_t lds = (size_t)2 * 32 * a.ld * sizeof(float);
-  static size_t lds_allowed[64] = {0};   // per device: the attribute belongs to the function on the device it was set on
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(COSIM_EINVAL, "cosim_mlp_forward: device index out of range");
-  if (lds > lds_allowed[dev]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_forward_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    lds_allowed[dev] = lds;
-  }
+  RC_TRY(kernel_needs_lds<mlp_forward_kernel>(lds, "cosim_mlp_forward"));
   hipLaunchKernelGGL(mlp_forward_kernel, dim3((n + 31) / 32), dim3(256), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
@@ -1053,28 +1076,12 @@ int cosim_policy_table_create(int n_policies, const int* n_layers, const int* di
   const PolShape shape = validate_policy_table(raw);
   if (!shape.err.empty()) return fail(COSIM_EINVAL, shape.err);
   const PolImage im = pack_policy_image(raw);
-  const PolTiles tl = build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges);
   cosim_policy_table* p = new cosim_policy_table;
-  p->n = n; p->ld = shape.maxd | 1; p->n_tiles = (int)tl.tiles.size(); p->tile_span = tl.tile_span; p->K = n_policies;
+  p->K = n_policies; p->ld = shape.maxd | 1;
   p->por.assign(policy_of_row, policy_of_row + n); p->ranges.assign(ranges, ranges + 2 * n_ranges);
-  const size_t lds = (size_t)2 * 32 * p->ld * sizeof(float);
-  static size_t lds_allowed[64] = {0};   // per device, as cosim_mlp_forward
-  auto upload = [&]() -> int {
-    HIP_TRY(hipGetDevice(&p->device));
-    if (p->device < 0 || p->device >= 64) return fail(COSIM_EINVAL, "cosim_policy_table_create: device index out of range");
-    const size_t b_img = im.words.size() * 4, b_desc = im.desc.size() * sizeof(PolDesc), b_rows = tl.rows.size() * 4, b_tiles = tl.tiles.size() * sizeof(PolTile);
-    HIP_TRY(hipMalloc(&p->d_image, b_img)); HIP_TRY(hipMalloc(&p->d_desc, b_desc)); HIP_TRY(hipMalloc(&p->d_rows, b_rows)); HIP_TRY(hipMalloc(&p->d_tiles, b_tiles));
-    HIP_TRY(hipMemcpy(p->d_image, im.words.data(), b_img, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_desc, im.desc.data(), b_desc, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_rows, tl.rows.data(), b_rows, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_tiles, tl.tiles.data(), b_tiles, hipMemcpyHostToDevice));
-    if (lds > lds_allowed[p->device]) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(mlp_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      lds_allowed[p->device] = lds;
-    }
-    return COSIM_OK;
-  };
-  const int rc = upload();
+  int rc = kernel_needs_lds<mlp_grouped_kernel>((size_t)2 * 32 * p->ld * sizeof(float), "cosim_policy_table_create");
+  if (!rc) rc = table_upload(*p, im.words, im.desc.data(), im.desc.size() * sizeof(PolDesc), (void**)&p->d_desc,
+                             build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges));
   if (rc) { cosim_policy_table_destroy(p); return rc; }
   *out = p;
   return COSIM_OK;
@@ -1114,8 +1121,8 @@ int cosim_policy_table_lists(cosim_policy_table* p, int range, int* rows_host, i
 
 int cosim_policy_table_destroy(cosim_policy_table* p) {
   if (!p) return COSIM_OK;
-  (void)hipFree(p->d_image); (void)hipFree(p->d_desc); (void)hipFree(p->d_rows); (void)hipFree(p->d_tiles);
-  rotate_free(p->rot);
+  (void)hipFree(p->d_desc);
+  table_free(*p);
   delete p;
   return COSIM_OK;
 }
@@ -1139,27 +1146,12 @@ int cosim_recurrent_table_create(int n_policies, const int* n_enc, const int* en
   const RecShape shape = validate_recurrent_table(raw, lds_limit);
   if (!shape.err.empty()) return fail(COSIM_EINVAL, shape.err);
   const RecImage im = pack_recurrent_image(raw);
-  const PolTiles tl = build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges);
   cosim_recurrent_table* p = new cosim_recurrent_table;
-  p->n = n; p->device = dev; p->ld_m = shape.ld_m; p->ld_x = shape.ld_x; p->hmax = shape.hmax;
-  p->n_tiles = (int)tl.tiles.size(); p->tile_span = tl.tile_span; p->K = n_policies;
+  p->K = n_policies; p->ld_m = shape.ld_m; p->ld_x = shape.ld_x; p->hmax = shape.hmax;
   p->por.assign(policy_of_row, policy_of_row + n); p->ranges.assign(ranges, ranges + 2 * n_ranges);
-  const size_t lds = (size_t)rec_lds_dynamic(p->ld_m, p->ld_x);
-  static size_t lds_allowed[64] = {0};   // per device, as cosim_mlp_forward
-  auto upload = [&]() -> int {
-    const size_t b_img = im.words.size() * 4, b_desc = im.desc.size() * sizeof(RecDesc), b_rows = tl.rows.size() * 4, b_tiles = tl.tiles.size() * sizeof(PolTile);
-    HIP_TRY(hipMalloc(&p->d_image, b_img)); HIP_TRY(hipMalloc(&p->d_desc, b_desc)); HIP_TRY(hipMalloc(&p->d_rows, b_rows)); HIP_TRY(hipMalloc(&p->d_tiles, b_tiles));
-    HIP_TRY(hipMemcpy(p->d_image, im.words.data(), b_img, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_desc, im.desc.data(), b_desc, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_rows, tl.rows.data(), b_rows, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_tiles, tl.tiles.data(), b_tiles, hipMemcpyHostToDevice));
-    if (lds > lds_allowed[dev]) {
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_actor_grouped_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      lds_allowed[dev] = lds;
-    }
-    return COSIM_OK;
-  };
-  const int rc = upload();
+  int rc = kernel_needs_lds<lstm_actor_grouped_kernel>((size_t)rec_lds_dynamic(p->ld_m, p->ld_x), "cosim_recurrent_table_create");
+  if (!rc) rc = table_upload(*p, im.words, im.desc.data(), im.desc.size() * sizeof(RecDesc), (void**)&p->d_desc,
+                             build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges));
   if (rc) { cosim_recurrent_table_destroy(p); return rc; }
   *out = p;
   return COSIM_OK;
@@ -1203,8 +1195,8 @@ int cosim_recurrent_table_lists(cosim_recurrent_table* p, int range, int* rows_h
 
 int cosim_recurrent_table_destroy(cosim_recurrent_table* p) {
   if (!p) return COSIM_OK;
-  (void)hipFree(p->d_image); (void)hipFree(p->d_desc); (void)hipFree(p->d_rows); (void)hipFree(p->d_tiles);
-  rotate_free(p->rot);
+  (void)hipFree(p->d_desc);
+  table_free(*p);
   delete p;
   return COSIM_OK;
 }
@@ -1218,14 +1210,7 @@ int cosim_lstm_cell(const float* x_dev, const float* h_dev, const float* c_dev, 
   a.n = n; a.I = in_dim; a.H = hidden; a.ld = (in_dim + hidden) | 1;
   a.vec = in_dim % 4 == 0 && hidden % 4 == 0 && ((uintptr_t)w_dev | (uintptr_t)r_dev) % 16 == 0;
   const size_t lds = (size_t)32 * a.ld * sizeof(float);
-  static size_t lds_allowed[64] = {0};   // per device
-  int dev = 0;
-  HIP_TRY(hipGetDevice(&dev));
-  if (dev < 0 || dev >= 64) return fail(COSIM_EINVAL, "cosim_lstm_cell: device index out of range");
-  if (lds > lds_allowed[dev]) {
-    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(lstm_cell_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    lds_allowed[dev] = lds;
-  }
+  RC_TRY(kernel_needs_lds<lstm_cell_kernel>(lds, "cosim_lstm_cell"));
   hipLaunchKernelGGL(lstm_cell_kernel, dim3((n + 31) / 32), dim3(256), lds, (hipStream_t)stream, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;

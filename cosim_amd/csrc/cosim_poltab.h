@@ -55,6 +55,45 @@ struct PolShape {
   int maxd = 0;               // the widest layer of any policy
 };
 
+// ---- the checks both kinds of table make (cosim_rectab.h calls them too).  Each answers the refusal, or an empty string; `who` names
+// the entry point and the policy, `label` is "", "encoder " or "head ".
+inline std::string check_widths(const std::string& who, const char* label, const int32_t* dims, int nl) {
+  for (int l = 0; l <= nl; l++)
+    if (dims[l] < 1 || dims[l] > POL_MAXD)
+      return who + ": " + label + "width " + std::to_string(dims[l]) + " of layer " + std::to_string(l) + " outside 1..512";
+  return "";
+}
+
+inline std::string check_layers(const std::string& who, const char* label, const int32_t* act, const float* const* w, int nl) {
+  for (int l = 0; l < nl; l++) {
+    const std::string layer = who + ", " + label + "layer " + std::to_string(l);
+    if (act[l] < 0 || act[l] > 5) return layer + ": unknown activation " + std::to_string(act[l]) + " (0 none .. 5 leaky relu)";
+    if (!w[l]) return layer + ": null weight";
+  }
+  return "";
+}
+
+// the fleet half: every row's policy is in [0, K), and the ranges tile [0, n) in order
+inline std::string check_fleet(const std::string& fn, int K, int n, const int32_t* policy_of_row, int n_ranges, const int32_t* ranges) {
+  const auto S = [](long long x) { return std::to_string(x); };
+  for (int i = 0; i < n; i++)
+    if (policy_of_row[i] < 0 || policy_of_row[i] >= K)
+      return fn + ": row " + S(i) + " is assigned to policy " + S(policy_of_row[i]) + ", outside [0, " + S(K) + ")";
+  if (n_ranges < 1 || n_ranges > n) return fn + ": " + S(n_ranges) + " ranges, outside 1..n";
+  long long next = 0;
+  for (int i = 0; i < n_ranges; i++) {
+    const long long first = ranges[2 * i], count = ranges[2 * i + 1];
+    const std::string who = fn + ": range " + S(i) + " (" + S(first) + ", " + S(count) + ")";
+    if (count < 1) return who + " is empty";
+    if (first < next) return who + " overlaps the one before it";
+    if (first > next) return who + " leaves rows from " + S(next) + " uncovered";
+    next = first + count;
+    if (next > n) return who + " ends past n " + S(n);
+  }
+  if (next != n) return fn + ": the ranges leave rows from " + S(next) + " uncovered";
+  return "";
+}
+
 #define POL_TRY(expr) do { v.err = (expr); if (!v.err.empty()) return v; } while (0)
 
 inline PolShape validate_policy_table(const PolRaw& r) {
@@ -68,36 +107,16 @@ inline PolShape validate_policy_table(const PolRaw& r) {
     const int nl = r.nl[k];
     if (nl < 1 || nl > POL_MAXL) POL_TRY(who + ": " + std::to_string(nl) + " layers, outside 1..6");
     const int32_t* d = r.dims + (size_t)k * (POL_MAXL + 1);
-    for (int l = 0; l <= nl; l++) {
-      if (d[l] < 1 || d[l] > POL_MAXD) POL_TRY(who + ": width " + std::to_string(d[l]) + " of layer " + std::to_string(l) + " outside 1..512");
-      if (d[l] > v.maxd) v.maxd = d[l];
-    }
+    POL_TRY(check_widths(who, "", d, nl));
+    for (int l = 0; l <= nl; l++) v.maxd = d[l] > v.maxd ? d[l] : v.maxd;
     const int32_t* d0 = r.dims;
     if (d[0] != d0[0])
       POL_TRY(who + ": input width " + std::to_string(d[0]) + " differs from policy 0's " + std::to_string(d0[0]));
     if (d[nl] != d0[r.nl[0]])
       POL_TRY(who + ": output width " + std::to_string(d[nl]) + " differs from policy 0's " + std::to_string(d0[r.nl[0]]));
-    for (int l = 0; l < nl; l++) {
-      const int a = r.act[(size_t)k * POL_MAXL + l];
-      if (a < 0 || a > 5) POL_TRY(who + ", layer " + std::to_string(l) + ": unknown activation " + std::to_string(a) + " (0 none .. 5 leaky relu)");
-      if (!r.w[(size_t)k * POL_MAXL + l]) POL_TRY(who + ", layer " + std::to_string(l) + ": null weight");
-    }
+    POL_TRY(check_layers(who, "", r.act + (size_t)k * POL_MAXL, r.w + (size_t)k * POL_MAXL, nl));
   }
-  for (int i = 0; i < r.n; i++)
-    if (r.policy_of_row[i] < 0 || r.policy_of_row[i] >= r.K)
-      POL_TRY(fn + ": row " + std::to_string(i) + " is assigned to policy " + std::to_string(r.policy_of_row[i]) + ", outside [0, " + std::to_string(r.K) + ")");
-  if (r.n_ranges < 1 || r.n_ranges > r.n) POL_TRY(fn + ": " + std::to_string(r.n_ranges) + " ranges, outside 1..n");
-  long long next = 0;
-  for (int i = 0; i < r.n_ranges; i++) {
-    const long long first = r.ranges[2 * i], count = r.ranges[2 * i + 1];
-    const std::string who = fn + ": range " + std::to_string(i) + " (" + std::to_string(first) + ", " + std::to_string(count) + ")";
-    if (count < 1) POL_TRY(who + " is empty");
-    if (first < next) POL_TRY(who + " overlaps the one before it");
-    if (first > next) POL_TRY(who + " leaves rows from " + std::to_string(next) + " uncovered");
-    next = first + count;
-    if (next > r.n) POL_TRY(who + " ends past n " + std::to_string(r.n));
-  }
-  if (next != r.n) POL_TRY(fn + ": the ranges leave rows from " + std::to_string(next) + " uncovered");
+  POL_TRY(check_fleet(fn, r.K, r.n, r.policy_of_row, r.n_ranges, r.ranges));
   return v;
 }
 
@@ -166,8 +185,23 @@ POL_HD inline int32_t policy_tile_capacity(int32_t count, int32_t K) {
 
 // ---- the image: per policy, per layer the weights (begun at a multiple of 4 words, so the float4 reads of a layer whose input width
 // is a multiple of 4 are 16-byte aligned) and then the bias if there is one.  Of a VALIDATED table.
+// A weight image as it grows: a matrix begins at a multiple of 4 words (zero padding), a bias follows what is there.  Both answer the
+// word offset of what they appended; a null bias appends nothing and answers -1.
+struct ImageWords : std::vector<float> {
+  int32_t matrix(const float* p, size_t n) {
+    resize((size() + 3) & ~(size_t)3, 0.f);
+    return bias(p, n);
+  }
+  int32_t bias(const float* p, size_t n) {
+    if (!p) return -1;
+    const int32_t off = (int32_t)size();
+    insert(end(), p, p + n);
+    return off;
+  }
+};
+
 struct PolImage {
-  std::vector<float> words;
+  ImageWords words;
   std::vector<PolDesc> desc;   // [K]
 };
 
@@ -181,16 +215,11 @@ inline PolImage pack_policy_image(const PolRaw& r) {
     for (int l = 0; l <= POL_MAXL; l++) d.dims[l] = l <= d.nl ? r.dims[(size_t)k * (POL_MAXL + 1) + l] : 0;
     for (int l = 0; l < POL_MAXL; l++) { d.woff[l] = -1; d.boff[l] = -1; d.alpha[l] = 1.f; }
     for (int l = 0; l < d.nl; l++) {
-      const size_t q = (size_t)k * POL_MAXL + l, nw = (size_t)d.dims[l] * d.dims[l + 1], nb = (size_t)d.dims[l + 1];
+      const size_t q = (size_t)k * POL_MAXL + l;
       d.act[l] = r.act[q];
       if (r.alpha) d.alpha[l] = r.alpha[q];
-      im.words.resize((im.words.size() + 3) & ~(size_t)3, 0.f);
-      d.woff[l] = (int32_t)im.words.size();
-      im.words.insert(im.words.end(), r.w[q], r.w[q] + nw);
-      if (r.b && r.b[q]) {
-        d.boff[l] = (int32_t)im.words.size();
-        im.words.insert(im.words.end(), r.b[q], r.b[q] + nb);
-      }
+      d.woff[l] = im.words.matrix(r.w[q], (size_t)d.dims[l] * d.dims[l + 1]);
+      d.boff[l] = im.words.bias(r.b ? r.b[q] : nullptr, (size_t)d.dims[l + 1]);
     }
   }
   return im;

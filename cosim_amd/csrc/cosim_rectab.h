@@ -104,25 +104,15 @@ inline RecShape validate_recurrent_table(const RecRaw& r, long long lds_limit) {
     if ((long long)I + H > REC_MAXK) REC_TRY(who + ": LSTM input width + hidden size " + S(I) + " + " + S(H) + " exceeds 1200");
     const int32_t* ed = r.edims + (size_t)k * (REC_MAXE + 1);
     const int32_t* hd = r.hdims + (size_t)k * (REC_MAXH + 1);
-    for (int l = 0; l <= ne; l++)
-      if (ed[l] < 1 || ed[l] > POL_MAXD) REC_TRY(who + ": encoder width " + S(ed[l]) + " of layer " + S(l) + " outside 1..512");
+    REC_TRY(check_widths(who, "encoder ", ed, ne));
     if (H < 1 || H > POL_MAXD) REC_TRY(who + ": hidden size " + S(H) + " outside 1..512");
-    for (int l = 0; l <= nh; l++)
-      if (hd[l] < 1 || hd[l] > POL_MAXD) REC_TRY(who + ": head width " + S(hd[l]) + " of layer " + S(l) + " outside 1..512");
+    REC_TRY(check_widths(who, "head ", hd, nh));
     if (ed[0] != r.edims[0]) REC_TRY(who + ": input width " + S(ed[0]) + " differs from policy 0's " + S(r.edims[0]));
     if (hd[nh] != r.hdims[r.nh[0]]) REC_TRY(who + ": output width " + S(hd[nh]) + " differs from policy 0's " + S(r.hdims[r.nh[0]]));
     if (I != ed[ne]) REC_TRY(who + ": the LSTM's input width " + S(I) + " differs from the encoder's output width " + S(ed[ne]));
     if (hd[0] != H) REC_TRY(who + ": the head's input width " + S(hd[0]) + " differs from the hidden size " + S(H));
-    for (int l = 0; l < ne; l++) {
-      const int a = r.eact[(size_t)k * REC_MAXE + l];
-      if (a < 0 || a > 5) REC_TRY(who + ", encoder layer " + S(l) + ": unknown activation " + S(a) + " (0 none .. 5 leaky relu)");
-      if (!r.ew[(size_t)k * REC_MAXE + l]) REC_TRY(who + ", encoder layer " + S(l) + ": null weight");
-    }
-    for (int l = 0; l < nh; l++) {
-      const int a = r.hact[(size_t)k * REC_MAXH + l];
-      if (a < 0 || a > 5) REC_TRY(who + ", head layer " + S(l) + ": unknown activation " + S(a) + " (0 none .. 5 leaky relu)");
-      if (!r.hw[(size_t)k * REC_MAXH + l]) REC_TRY(who + ", head layer " + S(l) + ": null weight");
-    }
+    REC_TRY(check_layers(who, "encoder ", r.eact + (size_t)k * REC_MAXE, r.ew + (size_t)k * REC_MAXE, ne));
+    REC_TRY(check_layers(who, "head ", r.hact + (size_t)k * REC_MAXH, r.hw + (size_t)k * REC_MAXH, nh));
     if (!r.W[k] || !r.R[k]) REC_TRY(who + ": null LSTM weight");
     RecDesc d;
     memset(&d, 0, sizeof d);
@@ -141,21 +131,7 @@ inline RecShape validate_recurrent_table(const RecRaw& r, long long lds_limit) {
   if (lds_limit > 0 && rec_lds_bytes(v.ld_m, v.ld_x) > lds_limit)
     REC_TRY(fn + ": the table needs " + S(rec_lds_bytes(v.ld_m, v.ld_x)) + " bytes of LDS (two tiles of 32 x " + S(v.ld_m) + " words, one of 32 x " +
             S(v.ld_x) + ", " + S(REC_STATIC_LDS) + " static), the device allows " + S(lds_limit));
-  for (int i = 0; i < r.n; i++)
-    if (r.policy_of_row[i] < 0 || r.policy_of_row[i] >= r.K)
-      REC_TRY(fn + ": row " + S(i) + " is assigned to policy " + S(r.policy_of_row[i]) + ", outside [0, " + S(r.K) + ")");
-  if (r.n_ranges < 1 || r.n_ranges > r.n) REC_TRY(fn + ": " + S(r.n_ranges) + " ranges, outside 1..n");
-  long long next = 0;
-  for (int i = 0; i < r.n_ranges; i++) {
-    const long long first = r.ranges[2 * i], count = r.ranges[2 * i + 1];
-    const std::string who = fn + ": range " + S(i) + " (" + S(first) + ", " + S(count) + ")";
-    if (count < 1) REC_TRY(who + " is empty");
-    if (first < next) REC_TRY(who + " overlaps the one before it");
-    if (first > next) REC_TRY(who + " leaves rows from " + S(next) + " uncovered");
-    next = first + count;
-    if (next > r.n) REC_TRY(who + " ends past n " + S(r.n));
-  }
-  if (next != r.n) REC_TRY(fn + ": the ranges leave rows from " + S(next) + " uncovered");
+  REC_TRY(check_fleet(fn, r.K, r.n, r.policy_of_row, r.n_ranges, r.ranges));
   return v;
 }
 
@@ -164,25 +140,14 @@ inline RecShape validate_recurrent_table(const RecRaw& r, long long lds_limit) {
 // ---- the image: per policy the encoder layers, W, R, B and the head layers; every matrix begins at a multiple of 4 words (the float4
 // reads of a layer whose input width is a multiple of 4 are then 16-byte aligned), a bias follows its matrix.  Of a VALIDATED table.
 struct RecImage {
-  std::vector<float> words;
+  ImageWords words;
   std::vector<RecDesc> desc;   // [K]
 };
 
 inline RecImage pack_recurrent_image(const RecRaw& r) {
   RecImage im;
   im.desc.resize(r.K);
-  auto matrix = [&](const float* p, size_t n) -> int32_t {
-    im.words.resize((im.words.size() + 3) & ~(size_t)3, 0.f);
-    const int32_t off = (int32_t)im.words.size();
-    im.words.insert(im.words.end(), p, p + n);
-    return off;
-  };
-  auto bias = [&](const float* p, size_t n) -> int32_t {
-    if (!p) return -1;
-    const int32_t off = (int32_t)im.words.size();
-    im.words.insert(im.words.end(), p, p + n);
-    return off;
-  };
+  auto& words = im.words;
   for (int k = 0; k < r.K; k++) {
     RecDesc& d = im.desc[k];
     memset(&d, 0, sizeof d);
@@ -195,18 +160,18 @@ inline RecImage pack_recurrent_image(const RecRaw& r) {
       const size_t q = (size_t)k * REC_MAXE + l;
       d.eact[l] = r.eact[q];
       if (r.ealpha) d.ealpha[l] = r.ealpha[q];
-      d.ewoff[l] = matrix(r.ew[q], (size_t)d.edims[l] * d.edims[l + 1]);
-      d.eboff[l] = bias(r.eb ? r.eb[q] : nullptr, (size_t)d.edims[l + 1]);
+      d.ewoff[l] = words.matrix(r.ew[q], (size_t)d.edims[l] * d.edims[l + 1]);
+      d.eboff[l] = words.bias(r.eb ? r.eb[q] : nullptr, (size_t)d.edims[l + 1]);
     }
-    d.woff = matrix(r.W[k], (size_t)4 * d.H * d.I);
-    d.roff = matrix(r.R[k], (size_t)4 * d.H * d.H);
-    d.boff = bias(r.B ? r.B[k] : nullptr, (size_t)8 * d.H);
+    d.woff = words.matrix(r.W[k], (size_t)4 * d.H * d.I);
+    d.roff = words.matrix(r.R[k], (size_t)4 * d.H * d.H);
+    d.boff = words.bias(r.B ? r.B[k] : nullptr, (size_t)8 * d.H);
     for (int l = 0; l < d.nh; l++) {
       const size_t q = (size_t)k * REC_MAXH + l;
       d.hact[l] = r.hact[q];
       if (r.halpha) d.halpha[l] = r.halpha[q];
-      d.hwoff[l] = matrix(r.hw[q], (size_t)d.hdims[l] * d.hdims[l + 1]);
-      d.hboff[l] = bias(r.hb ? r.hb[q] : nullptr, (size_t)d.hdims[l + 1]);
+      d.hwoff[l] = words.matrix(r.hw[q], (size_t)d.hdims[l] * d.hdims[l + 1]);
+      d.hboff[l] = words.bias(r.hb ? r.hb[q] : nullptr, (size_t)d.hdims[l + 1]);
     }
     d.vec = (d.I % 4 == 0 && d.H % 4 == 0) ? 1 : 0;
   }

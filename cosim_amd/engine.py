@@ -136,8 +136,10 @@ def load_library():
     L.cosim_recurrent_table_rotate.argtypes = [vp, ci]
     L.cosim_recurrent_table_forward_rotating.argtypes = [vp] * 9 + [ci, ctypes.c_float, vp]
     L.cosim_recurrent_table_lists.argtypes = [vp, ci, vp, vp, ctypes.POINTER(ci)]
+    L.cosim_mlp_forward.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp]
+    L.cosim_lstm_cell.argtypes = [vp] * 3 + [ci] * 3 + [vp] * 6
     L.cosim_last_error.restype = ctypes.c_char_p
-    for fn in ("cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "cosim_reset", "cosim_step", "cosim_step_range", "cosim_get",
+    for fn in ("cosim_mlp_forward", "cosim_lstm_cell","cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "cosim_reset", "cosim_step", "cosim_step_range", "cosim_get",
                "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_rollout",
                "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
                "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",

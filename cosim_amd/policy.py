@@ -5,7 +5,8 @@ The reference runs an ONNX file through onnxruntime on the CPU, one state at a t
 clipped to [-1, 1], LSTM ``h``/``c`` carried between calls — is kept over ``[N, state_dim]`` device tensors, so the
 rollout loop never leaves the GPU.  onnxruntime and the ``onnx`` package are not available in this
 build, so the file is read with a small protobuf wire-format decoder (``read_onnx``) and the graph is run by a tiny
-interpreter over the operator subset RL policy exports use (Gemm / MatMul / Add / activations / LSTM / shape glue).
+interpreter over the operator subset RL policy exports use (Gemm / MatMul / Add / activations / LSTM / shape glue);
+both, and the writer of synthetic policies, live in ``onnx_io.py`` and are re-exported here.
 The GEMMs go through torch (rocBLAS / hipBLASLt): plain library matrix products, not part of the §8 hot path.
 
 Two rules the tests pin.  Non-finite values: a NaN that reaches the output stays NaN on both paths (the interpreter's ``clamp``, like
@@ -18,288 +19,14 @@ tests compare with a numpy evaluation of the same graph.
 """
 from __future__ import annotations
 
+import ctypes
 import os
-import struct
-from typing import Dict, List, Optional
+from typing import Optional
 
 import numpy as np
 
-# ---------------------------------------------------------------------------------------------- protobuf wire format
-_DT = {1: np.float32, 6: np.int32, 7: np.int64, 10: np.float16, 11: np.float64}
-
-
-def _varint(b: bytes, i: int):
-    r, s = 0, 0
-    while True:
-        c = b[i]
-        i += 1
-        r |= (c & 0x7F) << s
-        if c < 0x80:
-            return r, i
-        s += 7
-
-
-def _fields(b: bytes):
-    """(field number, wire type, value) over one message; length-delimited values come back as bytes."""
-    i, n = 0, len(b)
-    while i < n:
-        key, i = _varint(b, i)
-        f, w = key >> 3, key & 7
-        if w == 0:
-            v, i = _varint(b, i)
-        elif w == 1:
-            v, i = b[i:i + 8], i + 8
-        elif w == 2:
-            ln, i = _varint(b, i)
-            v, i = b[i:i + ln], i + ln
-        elif w == 5:
-            v, i = b[i:i + 4], i + 4
-        else:
-            raise ValueError(f"unsupported protobuf wire type {w}")
-        yield f, w, v
-
-
-def _packed_varints(v) -> List[int]:
-    if isinstance(v, int):
-        return [v]
-    out, i = [], 0
-    while i < len(v):
-        x, i = _varint(v, i)
-        out.append(x)
-    return out
-
-
-def _signed(x: int) -> int:
-    return x - (1 << 64) if x >= (1 << 63) else x
-
-
-def _tensor(b: bytes):
-    dims, dt, name, raw, fdata, idata = [], 1, "", None, [], []
-    for f, w, v in _fields(b):
-        if f == 1:
-            dims += [_signed(x) for x in _packed_varints(v)]
-        elif f == 2:
-            dt = v
-        elif f == 8:
-            name = v.decode()
-        elif f == 9:
-            raw = v
-        elif f == 4:
-            fdata.append(np.frombuffer(v, dtype="<f4") if w == 2 else np.frombuffer(v, dtype="<f4", count=1))
-        elif f == 7:
-            idata += [_signed(x) for x in _packed_varints(v)]
-    if dt not in _DT:
-        raise NotImplementedError(f"ONNX tensor data type {dt} ({name})")
-    if raw is not None:
-        a = np.frombuffer(raw, dtype=np.dtype(_DT[dt]).newbyteorder("<"))
-    elif fdata:
-        a = np.concatenate(fdata)
-    else:
-        a = np.asarray(idata, dtype=_DT[dt])
-    return name, a.astype(_DT[dt]).reshape(dims)
-
-
-def _attribute(b: bytes):
-    name, val, ints, floats = "", None, [], []
-    for f, w, v in _fields(b):
-        if f == 1:
-            name = v.decode()
-        elif f == 2:
-            val = struct.unpack("<f", v)[0]
-        elif f == 3:
-            val = _signed(v)
-        elif f == 4:
-            val = v.decode(errors="replace")
-        elif f == 5:
-            val = _tensor(v)[1]
-        elif f == 7:
-            floats += list(np.frombuffer(v, dtype="<f4")) if w == 2 else [struct.unpack("<f", v)[0]]
-        elif f == 8:
-            ints += [_signed(x) for x in _packed_varints(v)]
-    if ints:
-        val = ints
-    elif floats:
-        val = floats
-    return name, val
-
-
-def read_onnx(path: str) -> dict:
-    """ModelProto -> {"nodes": [{op, inputs, outputs, attrs}], "init": {name: ndarray}, "inputs": [...], "outputs": [...]}."""
-    data = open(path, "rb").read()
-    graph = None
-    for f, w, v in _fields(data):
-        if f == 7:
-            graph = v
-    if graph is None:
-        raise ValueError(f"{path}: no graph in the ONNX model")
-    nodes, init, inputs, outputs = [], {}, [], []
-    for f, w, v in _fields(graph):
-        if f == 1:
-            n = {"op": "", "inputs": [], "outputs": [], "attrs": {}}
-            for g, _, x in _fields(v):
-                if g == 1:
-                    n["inputs"].append(x.decode())
-                elif g == 2:
-                    n["outputs"].append(x.decode())
-                elif g == 4:
-                    n["op"] = x.decode()
-                elif g == 5:
-                    k, a = _attribute(x)
-                    n["attrs"][k] = a
-            nodes.append(n)
-        elif f == 5:
-            k, a = _tensor(v)
-            init[k] = a
-        elif f in (11, 12):
-            name = next((x.decode() for g, _, x in _fields(v) if g == 1), "")
-            (inputs if f == 11 else outputs).append(name)
-    return {"nodes": nodes, "init": init, "inputs": [i for i in inputs if i not in init], "outputs": outputs}
-
-
-# ---------------------------------------------------------------------------------------------- graph interpreter
-class OnnxGraph:
-    """Runs the operator subset of RL policy exports on torch tensors (weights resident on ``device``)."""
-
-    def __init__(self, model: dict, device):
-        import torch
-        self.torch, self.device = torch, device
-        self.nodes, self.inputs, self.outputs = model["nodes"], model["inputs"], model["outputs"]
-        # fp16 / fp64 initialisers (exports of half- or double-precision checkpoints) are cast to fp32 on load: every op below runs in fp32
-        self.const = {k: torch.as_tensor(np.ascontiguousarray(v.astype(np.float32) if v.dtype in (np.float16, np.float64) else v), device=device)
-                      for k, v in model["init"].items()}
-
-    def run(self, feeds: Dict[str, "object"]) -> List["object"]:
-        t = self.torch
-        env = dict(self.const)
-        env.update(feeds)
-        for n in self.nodes:
-            x = [env[i] if i else None for i in n["inputs"]]
-            a, op = n["attrs"], n["op"]
-            if op == "Gemm":
-                A = x[0].transpose(-1, -2) if a.get("transA", 0) else x[0]
-                B = x[1].transpose(-1, -2) if a.get("transB", 0) else x[1]
-                al, be = a.get("alpha", 1.0), a.get("beta", 1.0)
-                if len(x) > 2 and x[2] is not None and A.dim() == 2 and x[2].dim() <= 2:
-                    y = t.addmm(x[2], A, B, beta=be, alpha=al)      # one library GEMM with the bias folded in
-                else:
-                    y = al * (A @ B)
-                    if len(x) > 2 and x[2] is not None:
-                        y = y + be * x[2]
-            elif op == "MatMul":
-                y = x[0] @ x[1]
-            elif op in ("Add", "Sub", "Mul", "Div"):
-                y = {"Add": t.add, "Sub": t.sub, "Mul": t.mul, "Div": t.div}[op](x[0], x[1])
-            elif op == "Relu":
-                y = t.relu(x[0])
-            elif op == "Tanh":
-                y = t.tanh(x[0])
-            elif op == "Sigmoid":
-                y = t.sigmoid(x[0])
-            elif op == "Elu":
-                y = t.nn.functional.elu(x[0], alpha=a.get("alpha", 1.0))
-            elif op == "LeakyRelu":
-                y = t.nn.functional.leaky_relu(x[0], negative_slope=a.get("alpha", 0.01))
-            elif op == "Softplus":
-                y = t.nn.functional.softplus(x[0])
-            elif op == "Identity":
-                y = x[0]
-            elif op == "Clip":
-                lo = x[1] if len(x) > 1 and x[1] is not None else a.get("min")
-                hi = x[2] if len(x) > 2 and x[2] is not None else a.get("max")
-                y = t.clamp(x[0], min=None if lo is None else float(lo), max=None if hi is None else float(hi))
-            elif op == "Flatten":
-                ax = a.get("axis", 1)
-                y = x[0].reshape(int(np.prod(x[0].shape[:ax])) if ax else 1, -1)
-            elif op == "Concat":
-                y = t.cat(x, dim=a.get("axis", 0))
-            elif op in ("Squeeze", "Unsqueeze"):
-                axes = a.get("axes")
-                if axes is None:
-                    axes = [int(v) for v in x[1].tolist()] if len(x) > 1 and x[1] is not None else None
-                y = x[0]
-                if op == "Squeeze":
-                    for ax in sorted([ax % y.dim() for ax in axes], reverse=True) if axes is not None else []:
-                        y = y.squeeze(ax)
-                    if axes is None:
-                        y = y.squeeze()
-                else:
-                    for ax in sorted(axes):
-                        y = y.unsqueeze(ax)
-            elif op == "Reshape":
-                shape = [int(v) for v in x[1].tolist()]
-                shape = [x[0].shape[i] if s == 0 else s for i, s in enumerate(shape)]
-                y = x[0].reshape(shape)
-            elif op == "Transpose":
-                y = x[0].permute(a["perm"]) if "perm" in a else x[0].permute(*reversed(range(x[0].dim())))
-            elif op == "Constant":
-                y = t.as_tensor(np.ascontiguousarray(a["value"]), device=self.device)
-            elif op == "LSTM":
-                outs = self._lstm(x, a)
-                for name, val in zip(n["outputs"], outs):
-                    if name:
-                        env[name] = val
-                continue
-            else:
-                raise NotImplementedError(f"ONNX operator '{op}' is not in the policy subset of cosim_amd.policy")
-            env[n["outputs"][0]] = y
-        return [env[o] for o in self.outputs]
-
-    def _lstm(self, x, a):
-        """ONNX LSTM, one direction, default activations: X [T,B,I], W [1,4H,I] (i o f c), R [1,4H,H], B [1,8H]."""
-        t = self.torch
-        if a.get("direction", "forward") != "forward" or a.get("layout", 0):
-            raise NotImplementedError("LSTM: only direction=forward, layout=0")
-        X, W, R = x[0], x[1][0], x[2][0]
-        H = R.shape[1]
-        Bv = x[3][0] if len(x) > 3 and x[3] is not None else t.zeros(8 * H, device=X.device)
-        h = x[5][0] if len(x) > 5 and x[5] is not None else t.zeros((X.shape[1], H), device=X.device)
-        c = x[6][0] if len(x) > 6 and x[6] is not None else t.zeros((X.shape[1], H), device=X.device)
-        if X.is_cuda and X.shape[0] == 1 and X.dtype == t.float32:
-            # one step for all envs: the engine's fused cell (gates on the matrix pipe + activations, one launch)
-            out = self._lstm_cell_hip(X[0], h, c, W, R, Bv)
-            if out is not None:
-                hn, cn = out
-                return hn.unsqueeze(0).unsqueeze(1), hn.unsqueeze(0), cn.unsqueeze(0)
-        bias = Bv[:4 * H] + Bv[4 * H:]
-        ys = []
-        for s in range(X.shape[0]):
-            g = X[s] @ W.T + h @ R.T + bias
-            i, o, f, cc = g[:, :H], g[:, H:2 * H], g[:, 2 * H:3 * H], g[:, 3 * H:]
-            c = t.sigmoid(f) * c + t.sigmoid(i) * t.tanh(cc)
-            h = t.sigmoid(o) * t.tanh(c)
-            ys.append(h)
-        return t.stack(ys).unsqueeze(1), h.unsqueeze(0), c.unsqueeze(0)
-
-
-def _lstm_cell_hip(self, x, h, c, W, R, Bv):
-    """``cosim_lstm_cell`` (csrc/cosim_mlp.hip): None when the library is not available (the interpreter's own ops then run)."""
-    import ctypes
-    t = self.torch
-    if getattr(self, "_lstm_lib", None) is None:
-        try:
-            from .engine import load_library
-            L = load_library()
-            L.cosim_lstm_cell.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_int] * 3 + [ctypes.c_void_p] * 6
-            L.cosim_lstm_cell.restype = ctypes.c_int
-            L.cosim_last_error.restype = ctypes.c_char_p
-            self._lstm_lib = L
-        except Exception:  # noqa: BLE001
-            self._lstm_lib = False
-    if not self._lstm_lib:
-        return None
-    x, h, c, W, R, Bv = (a.contiguous() for a in (x, h, c, W, R, Bv))
-    hn, cn = t.empty_like(h), t.empty_like(c)
-    rc = self._lstm_lib.cosim_lstm_cell(x.data_ptr(), h.data_ptr(), c.data_ptr(), x.shape[0], x.shape[1], h.shape[1], W.data_ptr(), R.data_ptr(),
-                                        Bv.data_ptr(), hn.data_ptr(), cn.data_ptr(), t.cuda.current_stream(x.device).cuda_stream)
-    if rc == -1:      # COSIM_EINVAL: a shape the fused cell does not take (in_dim + hidden > 1200): the interpreter's own ops run
-        return None
-    if rc != 0:
-        raise RuntimeError(self._lstm_lib.cosim_last_error().decode())
-    return hn, cn
-
-
-OnnxGraph._lstm_cell_hip = _lstm_cell_hip
-
+from .onnx_io import (OnnxGraph, _enc, _enc_varint, read_onnx, write_onnx, write_random_lstm, write_random_mlp,  # noqa: F401 (re-exported)
+                      write_recurrent_actor)
 
 # ---------------------------------------------------------------------------------------------- the reference's classes, batched
 _ACT = {"Relu": 1, "Tanh": 2, "Elu": 3, "Sigmoid": 4, "LeakyRelu": 5}
@@ -424,7 +151,6 @@ class MLPPolicy:
     (``cosim_mlp_forward``, csrc/cosim_mlp.hip) when the policy lives on a GPU; anything else goes through the interpreter."""
 
     def __init__(self, policy_path: str, device=None, fused: Optional[bool] = None):
-        import ctypes
         import torch
         self.torch = torch
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -437,15 +163,11 @@ class MLPPolicy:
         self._fused = None
         if chain is not None:
             from .engine import load_library
-            L = load_library()
-            L.cosim_mlp_forward.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
-                                            ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
-            L.cosim_last_error.restype = ctypes.c_char_p
             ws = [torch.as_tensor(np.ascontiguousarray(w), device=self.device) for w, *_ in chain]
             bs = [None if b is None else torch.as_tensor(np.ascontiguousarray(b), device=self.device) for _, b, *_ in chain]
             nl = len(chain)
             self._fused = dict(
-                L=L, nl=nl, keep=(ws, bs),
+                L=load_library(), nl=nl, keep=(ws, bs),
                 dims=(ctypes.c_int * (nl + 1))(chain[0][0].shape[1], *[w.shape[0] for w, *_ in chain]),
                 w=(ctypes.c_void_p * nl)(*[w.data_ptr() for w in ws]),
                 b=(ctypes.c_void_p * nl)(*[None if b is None else b.data_ptr() for b in bs]),
@@ -455,6 +177,14 @@ class MLPPolicy:
 
     graph_safe = True     # stateless: get_action is pure device work
 
+    def _forward(self, x, out):
+        """One launch of the fused kernel on the CURRENT stream: ``out[:] = actor(x)``, both contiguous fp32 rows on the policy's device."""
+        f = self._fused
+        rc = f["L"].cosim_mlp_forward(x.data_ptr(), x.shape[0], f["nl"], f["dims"], f["w"], f["b"], f["act"], f["alpha"], 1.0, out.data_ptr(),
+                                      self.torch.cuda.current_stream(self.device).cuda_stream)
+        if rc != 0:
+            raise RuntimeError(f["L"].cosim_last_error().decode())
+
     def get_action(self, state):
         t = self.torch
         s = t.as_tensor(state, dtype=t.float32, device=self.device)
@@ -462,18 +192,13 @@ class MLPPolicy:
         x = s.unsqueeze(0) if single else s
         f = self._fused
         if f is not None and x.shape[1] == f["in_dim"]:
-            x = x.contiguous()
             if f["out"] is None or f["out"].shape[0] != x.shape[0]:
                 f["out"] = t.empty((x.shape[0], f["out_dim"]), dtype=t.float32, device=self.device)
-            rc = f["L"].cosim_mlp_forward(x.data_ptr(), x.shape[0], f["nl"], f["dims"], f["w"], f["b"], f["act"], f["alpha"], 1.0,
-                                          f["out"].data_ptr(), t.cuda.current_stream(self.device).cuda_stream)
-            if rc != 0:
-                raise RuntimeError(f["L"].cosim_last_error().decode())
             out = f["out"]
+            self._forward(x.contiguous(), out)
         else:
             out = self.graph.run({self.input_name: x})[0].clamp(-1.0, 1.0)
         return out.squeeze(0) if single else out
-
 
     def get_action_into(self, state_rows, out_rows):
         """``out_rows[:] = get_action(state_rows)`` on the CURRENT stream without allocating: for callers that evaluate the policy per
@@ -482,10 +207,20 @@ class MLPPolicy:
         if f is None or state_rows.shape[1] != f["in_dim"] or not (state_rows.is_contiguous() and out_rows.is_contiguous()):
             out_rows.copy_(self.get_action(state_rows))
             return
-        rc = f["L"].cosim_mlp_forward(state_rows.data_ptr(), state_rows.shape[0], f["nl"], f["dims"], f["w"], f["b"], f["act"], f["alpha"], 1.0,
-                                      out_rows.data_ptr(), self.torch.cuda.current_stream(self.device).cuda_stream)
-        if rc != 0:
-            raise RuntimeError(f["L"].cosim_last_error().decode())
+        self._forward(state_rows, out_rows)
+
+
+def _take_rows(t, dst, stored, src, mask, name: str):
+    """Env ``d`` takes row ``src[d]`` of the stored ``[N, ...]`` tensor (``src`` None: row ``d``) into ``dst``; envs with ``mask[d] == 0`` keep
+    theirs.  In place, so a captured graph keeps seeing the same tensor.  A shape other than ``dst``'s is refused under ``name``."""
+    x = t.as_tensor(stored, dtype=dst.dtype, device=dst.device)
+    if src is not None:
+        x = x[t.as_tensor(src, device=dst.device).long()]
+    if tuple(x.shape) != tuple(dst.shape):
+        raise ValueError(f"{name} has shape {tuple(x.shape)}, expected {tuple(dst.shape)}")
+    if mask is not None:
+        x = t.where((t.as_tensor(mask, device=dst.device) != 0)[(...,) + (None,) * (dst.dim() - 1)], x, dst)
+    dst.copy_(x)
 
 
 class LSTMPolicy:
@@ -524,16 +259,8 @@ class LSTMPolicy:
     def load_state(self, state: dict, src=None, mask=None):
         """Counterpart of ``BatchedEnv.restore``: env ``d`` takes row ``src[d]`` of ``state["h"]`` / ``["c"]`` (``None``: row ``d``);
         envs with ``mask[d] == 0`` keep theirs.  In place, so a captured graph keeps seeing the same tensors."""
-        t = self.torch
         for name, dst in (("h", self.h_in), ("c", self.c_in)):
-            x = t.as_tensor(state[name], dtype=t.float32, device=self.device)
-            if src is not None:
-                x = x[t.as_tensor(src, device=self.device).long()]
-            if tuple(x.shape) != tuple(dst.shape[1:]):
-                raise ValueError(f"LSTMPolicy.load_state: {name} has shape {tuple(x.shape)}, expected {tuple(dst.shape[1:])}")
-            if mask is not None:
-                x = t.where((t.as_tensor(mask, device=self.device) != 0)[:, None], x, dst[0])
-            dst[0].copy_(x)
+            _take_rows(self.torch, dst[0], state[name], src, mask, f"LSTMPolicy.load_state: {name}")
 
     def get_action(self, state):
         t = self.torch
@@ -639,11 +366,109 @@ class _FleetTable:
         self.episode = t.zeros(self.num_envs, dtype=t.int32, device=self.device)
         self.policy_now = self._base.clone()
 
-    def _arm(self, rotate_fn):
-        if self.rotate_every is not None and self._handle is not None:
-            with self.torch.cuda.device(self.device):
-                if rotate_fn(self._handle, self.rotate_every) != 0:
-                    raise RuntimeError(self._lib.cosim_last_error().decode())
+    _entry = None         # the subclass's family of entry points: "cosim_policy_table" has _create, _rotate, _destroy ...
+    recurrent = False     # a recurrent table's done flags also zero the state, so its static launch takes them too
+
+    @staticmethod
+    def _pack_layers(chains, first_widths, max_layers):
+        """K chains of ``(w, b, act, alpha)`` layers as a create entry point takes them: ``((n, dims, act, alpha, w, b), keep)`` -- the ctypes
+        arrays ``[K]``, ``[K][max_layers + 1]`` and four times ``[K][max_layers]`` (a null ``b``: no bias), and the host arrays they point
+        into.  ``first_widths[k]``: the input width of chain ``k`` (a chain may be empty)."""
+        K, ML = len(chains), max_layers
+        ci, cf, vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
+        n, dims, act, alpha = (ci * K)(*[len(c) for c in chains]), (ci * (K * (ML + 1)))(), (ci * (K * ML))(), (cf * (K * ML))()
+        w, b, keep = (vp * (K * ML))(), (vp * (K * ML))(), []
+        for k, chain in enumerate(chains):
+            dims[k * (ML + 1)] = first_widths[k]
+            for li, (wl, bl, a, al) in enumerate(chain):
+                q = k * ML + li
+                dims[k * (ML + 1) + li + 1] = wl.shape[0]
+                act[q], alpha[q] = a, al
+                for arr, ptrs in ((wl, w), (bl, b)):
+                    if arr is not None:
+                        keep.append(np.ascontiguousarray(arr, dtype=np.float32))
+                        ptrs[q] = keep[-1].ctypes.data
+        return (n, dims, act, alpha, w, b), keep
+
+    def _open(self, *policy_args):
+        """The create entry point on the policies' arrays and the fleet's; arms a rotating table.  The library's words if create refuses."""
+        from .engine import load_library
+        L = load_library()
+        por = np.ascontiguousarray(self.policy_of_env, dtype=np.int32)
+        rng = np.ascontiguousarray(np.asarray(self.ranges, dtype=np.int32).reshape(-1, 2))
+        handle = ctypes.c_void_p()
+        with self.torch.cuda.device(self.device):
+            if getattr(L, self._entry + "_create")(len(self.paths), *policy_args, self.num_envs, por.ctypes.data, len(self.ranges), rng.ctypes.data,
+                                                    ctypes.byref(handle)) != 0:
+                return L.cosim_last_error().decode()
+            self._lib, self._handle = L, handle
+            if self.rotate_every is not None and getattr(L, self._entry + "_rotate")(handle, self.rotate_every) != 0:
+                raise RuntimeError(L.cosim_last_error().decode())
+
+    def _setup_eval(self, fused, models, layers):
+        """How the table evaluates: the library's table on a GPU (``_create(layers)``), else the torch twin over ``models``."""
+        self._handle = None
+        if fused is not False and self.device.type == "cuda":
+            self._create(layers)
+        elif fused:
+            raise ValueError("fused=True needs a GPU device")
+        else:
+            self._rows, self._range_rows = self._policy_rows()
+            self._graphs = [OnnxGraph(m, self.device) for m in models]
+
+    def close(self):
+        if self._handle is not None:
+            getattr(self._lib, self._entry + "_destroy")(self._handle)
+            self._handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # noqa: BLE001
+            pass
+
+    def _launch(self, x, out, i: int, done=None):
+        """One evaluation of range ``i`` (-1: all): the rotating or the static library call, or the torch twin on the rows of each policy."""
+        t = self.torch
+        if x.shape != (self.num_envs, self.in_dim) or out.shape != (self.num_envs, self.out_dim):
+            raise ValueError(f"{type(self).__name__}: state {tuple(x.shape)} / action {tuple(out.shape)}, expected ({self.num_envs}, {self.in_dim}) / "
+                             f"({self.num_envs}, {self.out_dim})")
+        if done is not None:
+            self._check_done(done)
+        rotating = self.rotate_every is not None
+        if self._handle is None:
+            self._twin(x, out, self._twin_rows(i, done) if rotating else (self._rows if i < 0 else self._range_rows[i]), done)
+            return
+        if not (x.is_cuda and out.is_cuda and x.dtype == t.float32 and out.dtype == t.float32 and x.is_contiguous() and out.is_contiguous()):
+            raise ValueError(f"{type(self).__name__}: state and action must be contiguous fp32 tensors on the table's device")
+        da, db = (None, None) if done is None else (done[0].data_ptr(), done[1].data_ptr())
+        forward = self._forward_rotating if rotating else self._forward
+        if forward(x.data_ptr(), out.data_ptr(), da, db, i, t.cuda.current_stream(self.device).cuda_stream) != 0:
+            raise RuntimeError(self._lib.cosim_last_error().decode())
+
+    def get_action(self, state):
+        """``[N, action_dim]`` in [-1, 1]: the table's persistent output tensor (the next call overwrites it); a recurrent table's ``h`` /
+        ``c`` move one step."""
+        t = self.torch
+        x = t.as_tensor(state, dtype=t.float32, device=self.device).contiguous()
+        self._launch(x, self._out, -1)
+        return self._out
+
+    def get_action_range(self, i: int, state, action, done=None):
+        """Writes the rows of range ``i`` of ``ranges`` into ``action`` (``[N, action_dim]``) from ``state`` (``[N, in_dim]``), both whole-fleet
+        contiguous fp32 tensors, on the CURRENT stream and without allocating; the other rows of ``action`` (and of a recurrent table's
+        ``h`` / ``c``) stay as they are.  ``done=(terminated, truncated)`` (uint8 ``[N]``): a rotating table needs it -- an env of the range
+        with either set has ended an episode, and its counter advances in this very launch; a recurrent table starts such an env from
+        a zero state; a static ``PolicyTable`` ignores it."""
+        if not 0 <= int(i) < len(self.ranges):
+            raise ValueError(f"{type(self).__name__}.get_action_range: range {i} outside 0..{len(self.ranges) - 1}")
+        if self.rotate_every is None:
+            self._launch(state, action, int(i), done if self.recurrent else None)
+            return
+        if done is None:
+            raise ValueError(f"{type(self).__name__}.get_action_range: the table rotates, pass done=(terminated, truncated) (the range's episode "
+                             "ends advance its counters in this launch)")
+        self._launch(state, action, int(i), done)
 
     def _advance(self, mask):
         """The masked envs ended an episode: their counters go up by one (held at INT32_MAX).  Device work on persistent tensors: an
@@ -689,31 +514,19 @@ class _FleetTable:
         return [first + t.nonzero(now == k)[:, 0] for k in range(K)]
 
     def _check_done(self, done):
-        t, who = self.torch, type(self).__name__
-        if done is not None:
-            for d in done:
-                if d.shape != (self.num_envs,) or d.dtype not in (t.uint8, t.bool) or not d.is_contiguous() or d.device != self._out.device:
-                    raise ValueError(f"{who}: done is (terminated, truncated), contiguous uint8 [{self.num_envs}] tensors on the table's device")
+        t = self.torch
+        for d in done:
+            if d.shape != (self.num_envs,) or d.dtype not in (t.uint8, t.bool) or not d.is_contiguous() or d.device != self._out.device:
+                raise ValueError(f"{type(self).__name__}: done is (terminated, truncated), contiguous uint8 [{self.num_envs}] tensors on the table's device")
 
     def _load_counters(self, state, src, mask):
         """``load_state`` for the counters of a rotating table: env ``d`` takes ``state["episode"][src[d]]``, masked as the rest."""
-        t, who = self.torch, type(self).__name__
+        who = type(self).__name__
         if self.rotate_every is None:
             return
         if state is None or "episode" not in state:
             raise ValueError(f"{who}.load_state: the state carries no episode counters (it was taken from a table that does not rotate)")
-        x = t.as_tensor(state["episode"], dtype=t.int32, device=self.device)
-        if src is not None:
-            x = x[t.as_tensor(src, device=self.device).long()]
-        if tuple(x.shape) != (self.num_envs,):
-            raise ValueError(f"{who}.load_state: episode has shape {tuple(x.shape)}, expected ({self.num_envs},)")
-        if mask is not None:
-            x = t.where(t.as_tensor(mask, device=self.device) != 0, x, self.episode)
-        self.episode.copy_(x)
-
-    def _check_range(self, i):
-        if not 0 <= int(i) < len(self.ranges):
-            raise ValueError(f"{type(self).__name__}.get_action_range: range {i} outside 0..{len(self.ranges) - 1}")
+        _take_rows(self.torch, self.episode, state["episode"], src, mask, f"{who}.load_state: episode")
 
 
 class PolicyTable(_FleetTable):
@@ -773,45 +586,27 @@ class PolicyTable(_FleetTable):
         self._setup_rotate(rotate_every)
         if self.rotate_every is not None:
             self.reset = self._reset_rotating
-        self._handle = None
-        if fused is not False and self.device.type == "cuda":
-            self._create(chains)
-            self._arm(self._lib.cosim_policy_table_rotate)
-        elif fused:
-            raise ValueError("fused=True needs a GPU device")
-        else:
-            self._rows, self._range_rows = self._policy_rows()
-            self._graphs = [OnnxGraph(m, self.device) for m in models]
+        self._setup_eval(fused, models, chains)
+
+    _entry = "cosim_policy_table"
 
     def _create(self, chains):
-        import ctypes
-        from .engine import load_library
-        L = load_library()
-        K, ML = len(chains), 6
-        nl = (ctypes.c_int * K)(*[len(c) for c in chains])
-        dims, act, alpha = (ctypes.c_int * (K * (ML + 1)))(), (ctypes.c_int * (K * ML))(), (ctypes.c_float * (K * ML))()
-        w, b, keep = (ctypes.c_void_p * (K * ML))(), (ctypes.c_void_p * (K * ML))(), []
-        for k, chain in enumerate(chains):
-            dims[k * (ML + 1)] = chain[0][0].shape[1]
-            for li, (wl, bl, a, al) in enumerate(chain):
-                dims[k * (ML + 1) + li + 1] = wl.shape[0]
-                act[k * ML + li], alpha[k * ML + li] = a, al
-                wl = np.ascontiguousarray(wl, dtype=np.float32)
-                keep.append(wl)
-                w[k * ML + li] = wl.ctypes.data
-                if bl is not None:
-                    bl = np.ascontiguousarray(bl, dtype=np.float32)
-                    keep.append(bl)
-                    b[k * ML + li] = bl.ctypes.data
-        por = np.ascontiguousarray(self.policy_of_env, dtype=np.int32)
-        rng = np.ascontiguousarray(np.asarray(self.ranges, dtype=np.int32).reshape(-1, 2))
-        handle = ctypes.c_void_p()
-        with self.torch.cuda.device(self.device):
-            rc = L.cosim_policy_table_create(K, nl, dims, act, alpha, w, b, self.num_envs, por.ctypes.data, len(self.ranges), rng.ctypes.data,
-                                             ctypes.byref(handle))
-        if rc != 0:
-            raise RuntimeError(L.cosim_last_error().decode())
-        self._lib, self._handle = L, handle
+        layers, keep = self._pack_layers(chains, [c[0][0].shape[1] for c in chains], 6)   # keep: alive until create has copied them
+        msg = self._open(*layers)
+        if msg is not None:
+            raise RuntimeError(msg)
+
+    def _forward(self, x, out, da, db, i, stream):
+        return self._lib.cosim_policy_table_forward(self._handle, x, out, i, 1.0, stream)
+
+    def _forward_rotating(self, x, out, da, db, i, stream):
+        return self._lib.cosim_policy_table_forward_rotating(self._handle, x, out, self.episode.data_ptr(), self.policy_now.data_ptr(), da, db, i, 1.0,
+                                                             stream)
+
+    def _twin(self, x, out, rows, done):
+        for g, idx in zip(self._graphs, rows):
+            if idx.numel():
+                out[idx] = g.run({g.inputs[0]: x[idx]})[0].clamp(-1.0, 1.0)
 
     def state(self):
         """Nothing for a static table: it is stateless, so ``env.snapshot(table)`` stores no policy state.  A rotating one: its episode
@@ -829,64 +624,6 @@ class PolicyTable(_FleetTable):
         ``hasattr(policy, "reset")`` does for it exactly what it did before there was rotation."""
         if mask is not None:
             self._advance(mask)
-
-    def close(self):
-        if self._handle is not None:
-            self._lib.cosim_policy_table_destroy(self._handle)
-            self._handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
-
-    def _launch(self, x, out, i: int, done=None):
-        t = self.torch
-        if x.shape != (self.num_envs, self.in_dim) or out.shape != (self.num_envs, self.out_dim):
-            raise ValueError(f"PolicyTable: state {tuple(x.shape)} / action {tuple(out.shape)}, expected ({self.num_envs}, {self.in_dim}) / "
-                             f"({self.num_envs}, {self.out_dim})")
-        rotating = self.rotate_every is not None
-        if done is not None:
-            self._check_done(done)
-        if self._handle is not None:
-            if not (x.is_cuda and out.is_cuda and x.dtype == t.float32 and out.dtype == t.float32 and x.is_contiguous() and out.is_contiguous()):
-                raise ValueError("PolicyTable: state and action must be contiguous fp32 tensors on the table's device")
-            stream = t.cuda.current_stream(self.device).cuda_stream
-            if rotating:
-                da, db = (None, None) if done is None else (done[0].data_ptr(), done[1].data_ptr())
-                rc = self._lib.cosim_policy_table_forward_rotating(self._handle, x.data_ptr(), out.data_ptr(), self.episode.data_ptr(),
-                                                                   self.policy_now.data_ptr(), da, db, i, 1.0, stream)
-            else:
-                rc = self._lib.cosim_policy_table_forward(self._handle, x.data_ptr(), out.data_ptr(), i, 1.0, stream)
-            if rc != 0:
-                raise RuntimeError(self._lib.cosim_last_error().decode())
-            return
-        rows = self._twin_rows(i, done) if rotating else (self._rows if i < 0 else self._range_rows[i])
-        for g, idx in zip(self._graphs, rows):
-            if idx.numel():
-                out[idx] = g.run({g.inputs[0]: x[idx]})[0].clamp(-1.0, 1.0)
-
-    def get_action(self, state):
-        """``[N, action_dim]`` in [-1, 1]: the table's persistent output tensor (the next call overwrites it)."""
-        t = self.torch
-        x = t.as_tensor(state, dtype=t.float32, device=self.device).contiguous()
-        self._launch(x, self._out, -1)
-        return self._out
-
-    def get_action_range(self, i: int, state, action, done=None):
-        """Writes the rows of range ``i`` of ``ranges`` into ``action`` (``[N, action_dim]``) from ``state`` (``[N, in_dim]``), both whole-fleet
-        contiguous fp32 tensors, on the CURRENT stream and without allocating; the other rows of ``action`` stay as they are.
-        ``done=(terminated, truncated)`` (uint8 ``[N]``): a rotating table needs it -- an env of the range with either set has ended an
-        episode, and its counter advances in this very launch; a static table ignores it."""
-        self._check_range(i)
-        if self.rotate_every is None:
-            self._launch(state, action, int(i))
-            return
-        if done is None:
-            raise ValueError("PolicyTable.get_action_range: the table rotates, pass done=(terminated, truncated) (the range's episode ends advance "
-                             "its counters in this launch)")
-        self._launch(state, action, int(i), done)
 
 
 class RecurrentPolicyTable(_FleetTable):
@@ -935,71 +672,42 @@ class RecurrentPolicyTable(_FleetTable):
         self.c = torch.zeros_like(self.h)
         self._out = torch.zeros((N, self.out_dim), dtype=torch.float32, device=self.device)
         self._setup_rotate(rotate_every)
-        self._handle = None
-        if fused is not False and self.device.type == "cuda":
-            self._create(parts)
-            self._arm(self._lib.cosim_recurrent_table_rotate)
-        elif fused:
-            raise ValueError("fused=True needs a GPU device")
-        else:
-            self._rows, self._range_rows = self._policy_rows()
-            self._graphs = [OnnxGraph(m, self.device) for m in models]
+        self._setup_eval(fused, models, parts)
+
+    _entry = "cosim_recurrent_table"
 
     def _create(self, parts):
-        import ctypes
-        from .engine import load_library
-        L = load_library()
-        K, ML = len(parts), 3
-        ci, cf, vp = ctypes.c_int, ctypes.c_float, ctypes.c_void_p
-        keep = []
-
-        def host(a):
-            a = np.ascontiguousarray(a, dtype=np.float32)
-            keep.append(a)
-            return a.ctypes.data
-
-        def layers(key, first_width):
-            n, dims, act, alpha = (ci * K)(), (ci * (K * (ML + 1)))(), (ci * (K * ML))(), (cf * (K * ML))()
-            w, b = (vp * (K * ML))(), (vp * (K * ML))()
-            for k, part in enumerate(parts):
-                n[k] = len(part[key])
-                dims[k * (ML + 1)] = part[first_width]
-                for li, (wl, bl, a, al) in enumerate(part[key]):
-                    dims[k * (ML + 1) + li + 1] = wl.shape[0]
-                    act[k * ML + li], alpha[k * ML + li] = a, al
-                    w[k * ML + li] = host(wl)
-                    if bl is not None:
-                        b[k * ML + li] = host(bl)
-            return n, dims, act, alpha, w, b
-        enc, head = layers("enc", "in_dim"), layers("head", "H")
-        lstm_in, hidden = (ci * K)(*[p["I"] for p in parts]), (ci * K)(*[p["H"] for p in parts])
-        W, R, B = (vp * K)(*[host(p["W"]) for p in parts]), (vp * K)(*[host(p["R"]) for p in parts]), (vp * K)()
-        for k, part in enumerate(parts):
-            if part["B"] is not None:
-                B[k] = host(part["B"])
-        por = np.ascontiguousarray(self.policy_of_env, dtype=np.int32)
-        rng = np.ascontiguousarray(np.asarray(self.ranges, dtype=np.int32).reshape(-1, 2))
-        handle = vp()
-        with self.torch.cuda.device(self.device):
-            rc = L.cosim_recurrent_table_create(K, *enc, lstm_in, hidden, W, R, B, *head, self.num_envs, por.ctypes.data, len(self.ranges),
-                                                rng.ctypes.data, ctypes.byref(handle))
-        if rc != 0:
+        K, vp = len(parts), ctypes.c_void_p
+        enc, keep_e = self._pack_layers([p["enc"] for p in parts], [p["in_dim"] for p in parts], 3)
+        head, keep_h = self._pack_layers([p["head"] for p in parts], [p["H"] for p in parts], 3)
+        cell = {key: [None if p[key] is None else np.ascontiguousarray(p[key], dtype=np.float32) for p in parts] for key in "WRB"}
+        lstm_in, hidden = (ctypes.c_int * K)(*[p["I"] for p in parts]), (ctypes.c_int * K)(*[p["H"] for p in parts])
+        W, R, B = ((vp * K)(*[None if a is None else a.ctypes.data for a in cell[key]]) for key in "WRB")
+        msg = self._open(*enc, lstm_in, hidden, W, R, B, *head)
+        if msg is not None:
             import re
-            msg = L.cosim_last_error().decode()
             m = re.search(r": policy (\d+)", msg)              # the validator names the policy it refuses: name its file
             raise ValueError(f"RecurrentPolicyTable: {self.paths[int(m.group(1))] + ': ' if m else ''}{msg}")
-        self._lib, self._handle = L, handle
 
-    def close(self):
-        if self._handle is not None:
-            self._lib.cosim_recurrent_table_destroy(self._handle)
-            self._handle = None
+    def _forward(self, x, out, da, db, i, stream):
+        return self._lib.cosim_recurrent_table_forward(self._handle, x, self.h.data_ptr(), self.c.data_ptr(), out, da, db, i, 1.0, stream)
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:  # noqa: BLE001
-            pass
+    def _forward_rotating(self, x, out, da, db, i, stream):
+        return self._lib.cosim_recurrent_table_forward_rotating(self._handle, x, self.h.data_ptr(), self.c.data_ptr(), out, self.episode.data_ptr(),
+                                                                self.policy_now.data_ptr(), da, db, i, 1.0, stream)
+
+    def _twin(self, x, out, rows, done):
+        fresh = None if done is None else ((done[0] != 0) | (done[1] != 0))
+        for g, idx, H in zip(self._graphs, rows, self.hidden):
+            if not idx.numel():
+                continue
+            h, c = self.h[idx, :H], self.c[idx, :H]
+            if fresh is not None:
+                h, c = h.masked_fill(fresh[idx, None], 0.0), c.masked_fill(fresh[idx, None], 0.0)
+            action, h_out, c_out = g.run({g.inputs[0]: x[idx], "h_in": h.unsqueeze(0), "c_in": c.unsqueeze(0)})[:3]
+            self.h[idx, :H] = h_out.reshape(-1, H)
+            self.c[idx, :H] = c_out.reshape(-1, H)
+            out[idx] = action.reshape(-1, self.out_dim).clamp(-1.0, 1.0)
 
     def reset(self, mask=None):
         """Zero the recurrent state (of the masked envs), as ``LSTMPolicy.reset``: a fill, so a non-finite state does not survive.  With a
@@ -1023,69 +731,9 @@ class RecurrentPolicyTable(_FleetTable):
     def load_state(self, state: dict, src=None, mask=None):
         """As ``LSTMPolicy.load_state``: env ``d`` takes row ``src[d]`` of ``state["h"]`` / ``["c"]`` (``None``: row ``d``); envs with
         ``mask[d] == 0`` keep theirs.  In place.  A row is only meaningful for an env of the same policy as the one it was taken from."""
-        t = self.torch
         for name, dst in (("h", self.h), ("c", self.c)):
-            x = t.as_tensor(state[name], dtype=t.float32, device=self.device)
-            if src is not None:
-                x = x[t.as_tensor(src, device=self.device).long()]
-            if tuple(x.shape) != tuple(dst.shape):
-                raise ValueError(f"RecurrentPolicyTable.load_state: {name} has shape {tuple(x.shape)}, expected {tuple(dst.shape)}")
-            if mask is not None:
-                x = t.where((t.as_tensor(mask, device=self.device) != 0)[:, None], x, dst)
-            dst.copy_(x)
+            _take_rows(self.torch, dst, state[name], src, mask, f"RecurrentPolicyTable.load_state: {name}")
         self._load_counters(state, src, mask)
-
-    def _launch(self, x, out, i: int, done=None):
-        t = self.torch
-        if x.shape != (self.num_envs, self.in_dim) or out.shape != (self.num_envs, self.out_dim):
-            raise ValueError(f"RecurrentPolicyTable: state {tuple(x.shape)} / action {tuple(out.shape)}, expected ({self.num_envs}, {self.in_dim}) / "
-                             f"({self.num_envs}, {self.out_dim})")
-        if done is not None:
-            for d in done:
-                if d.shape != (self.num_envs,) or d.dtype not in (t.uint8, t.bool) or not d.is_contiguous() or d.device != self.h.device:
-                    raise ValueError(f"RecurrentPolicyTable: done is (terminated, truncated), contiguous uint8 [{self.num_envs}] tensors on the table's device")
-        if self._handle is not None:
-            if not (x.is_cuda and out.is_cuda and x.dtype == t.float32 and out.dtype == t.float32 and x.is_contiguous() and out.is_contiguous()):
-                raise ValueError("RecurrentPolicyTable: state and action must be contiguous fp32 tensors on the table's device")
-            da, db = (None, None) if done is None else (done[0].data_ptr(), done[1].data_ptr())
-            stream = t.cuda.current_stream(self.device).cuda_stream
-            if self.rotate_every is not None:
-                rc = self._lib.cosim_recurrent_table_forward_rotating(self._handle, x.data_ptr(), self.h.data_ptr(), self.c.data_ptr(), out.data_ptr(),
-                                                                      self.episode.data_ptr(), self.policy_now.data_ptr(), da, db, i, 1.0, stream)
-            else:
-                rc = self._lib.cosim_recurrent_table_forward(self._handle, x.data_ptr(), self.h.data_ptr(), self.c.data_ptr(), out.data_ptr(), da, db, i, 1.0,
-                                                             stream)
-            if rc != 0:
-                raise RuntimeError(self._lib.cosim_last_error().decode())
-            return
-        rows = self._twin_rows(i, done) if self.rotate_every is not None else (self._rows if i < 0 else self._range_rows[i])
-        fresh = None if done is None else ((done[0] != 0) | (done[1] != 0))
-        for g, idx, H in zip(self._graphs, rows, self.hidden):
-            if not idx.numel():
-                continue
-            h, c = self.h[idx, :H], self.c[idx, :H]
-            if fresh is not None:
-                h, c = h.masked_fill(fresh[idx, None], 0.0), c.masked_fill(fresh[idx, None], 0.0)
-            action, h_out, c_out = g.run({g.inputs[0]: x[idx], "h_in": h.unsqueeze(0), "c_in": c.unsqueeze(0)})[:3]
-            self.h[idx, :H] = h_out.reshape(-1, H)
-            self.c[idx, :H] = c_out.reshape(-1, H)
-            out[idx] = action.reshape(-1, self.out_dim).clamp(-1.0, 1.0)
-
-    def get_action(self, state):
-        """``[N, action_dim]`` in [-1, 1]: the table's persistent output tensor (the next call overwrites it); ``h`` / ``c`` move one step."""
-        t = self.torch
-        x = t.as_tensor(state, dtype=t.float32, device=self.device).contiguous()
-        self._launch(x, self._out, -1)
-        return self._out
-
-    def get_action_range(self, i: int, state, action, done=None):
-        """One step of the envs of range ``i``: their rows of ``action`` and of ``h`` / ``c`` are written, every other row stays as it is.
-        ``state`` / ``action`` as ``PolicyTable.get_action_range``; on the CURRENT stream, without allocating.  ``done``: see the class."""
-        self._check_range(i)
-        if self.rotate_every is not None and done is None:
-            raise ValueError("RecurrentPolicyTable.get_action_range: the table rotates, pass done=(terminated, truncated) (the range's episode "
-                             "ends advance its counters in this launch)")
-        self._launch(state, action, int(i), done)
 
 
 def open_policy_table(policy_paths, **table_args):
@@ -1115,135 +763,3 @@ def build_policy(config: dict, policy_path: str = None, num_envs: int = 1, devic
     if config["policy"]["use_lstm"]:
         return LSTMPolicy(config, policy_path, num_envs=num_envs, device=device)
     return MLPPolicy(policy_path, device=device)
-
-
-# ---------------------------------------------------------------------------------------------- writer (tests / synthetic policies)
-def _enc_varint(x: int) -> bytes:
-    x &= (1 << 64) - 1
-    out = bytearray()
-    while True:
-        c = x & 0x7F
-        x >>= 7
-        out.append(c | (0x80 if x else 0))
-        if not x:
-            return bytes(out)
-
-
-def _enc(field: int, wire: int, payload) -> bytes:
-    key = _enc_varint((field << 3) | wire)
-    if wire == 0:
-        return key + _enc_varint(payload)
-    if wire == 2:
-        return key + _enc_varint(len(payload)) + payload
-    return key + payload
-
-
-def write_onnx(path: str, nodes: List[dict], init: Dict[str, np.ndarray], inputs: List[str], outputs: List[str]):
-    """Minimal ONNX writer for the same subset (no policy ships with the reference: synthetic policies and the tests use it)."""
-    def tensor(name, a):
-        a = np.ascontiguousarray(a)
-        dt = {np.dtype(np.float32): 1, np.dtype(np.int64): 7}[a.dtype]
-        return b"".join(_enc(1, 0, int(d)) for d in a.shape) + _enc(2, 0, dt) + _enc(8, 2, name.encode()) + _enc(9, 2, a.tobytes())
-
-    def attr(k, v):
-        b = _enc(1, 2, k.encode())
-        if isinstance(v, float):
-            return b + _enc(2, 5, struct.pack("<f", v)) + _enc(20, 0, 1)
-        if isinstance(v, int):
-            return b + _enc(3, 0, v) + _enc(20, 0, 2)
-        if isinstance(v, str):
-            return b + _enc(4, 2, v.encode()) + _enc(20, 0, 3)
-        return b + b"".join(_enc(8, 0, int(x)) for x in v) + _enc(20, 0, 7)
-
-    g = b""
-    for n in nodes:
-        nb = b"".join(_enc(1, 2, i.encode()) for i in n["inputs"]) + b"".join(_enc(2, 2, o.encode()) for o in n["outputs"])
-        nb += _enc(4, 2, n["op"].encode()) + b"".join(_enc(5, 2, attr(k, v)) for k, v in n.get("attrs", {}).items())
-        g += _enc(1, 2, nb)
-    g += _enc(2, 2, b"cosim_amd_policy")
-    for k, a in init.items():
-        g += _enc(5, 2, tensor(k, a))
-    for name in inputs:
-        g += _enc(11, 2, _enc(1, 2, name.encode()))
-    for name in outputs:
-        g += _enc(12, 2, _enc(1, 2, name.encode()))
-    model = _enc(1, 0, 8) + _enc(7, 2, g) + _enc(8, 2, _enc(2, 0, 17))
-    with open(path, "wb") as f:
-        f.write(model)
-
-
-def write_recurrent_actor(path: str, enc, lstm, head, read: str = "Y_h"):
-    """A recurrent actor of the shape ``_recurrent_actor`` recognises and ``LSTMPolicy`` runs.  ``enc`` / ``head``: layers
-    ``(w [O, I], b [O] or None, op or None, alpha)``; ``lstm``: ``(W [4H, I], R [4H, H], B [8H] or None)``; ``read``: the LSTM output
-    the head takes, ``"Y_h"`` or ``"Y"``."""
-    nodes, init = [], {}
-
-    def chain(layers, x, tag, last_name=None):
-        for li, (w, b, op, alpha) in enumerate(layers):
-            init[f"{tag}w{li}"] = np.asarray(w, np.float32)
-            ins = [x, f"{tag}w{li}"]
-            if b is not None:
-                init[f"{tag}b{li}"] = np.asarray(b, np.float32)
-                ins.append(f"{tag}b{li}")
-            last = last_name is not None and li == len(layers) - 1
-            lin = last_name if last and op is None else f"{tag}lin{li}"
-            nodes.append({"op": "Gemm", "inputs": ins, "outputs": [lin], "attrs": {"transB": 1}})
-            x = lin
-            if op is not None:
-                x = last_name if last else f"{tag}a{li}"
-                nodes.append({"op": op, "inputs": [lin], "outputs": [x], "attrs": {"alpha": float(alpha)} if op in ("Elu", "LeakyRelu") else {}})
-        return x
-    x = chain(enc, "obs", "e")
-    W, R, B = lstm
-    H = R.shape[1]
-    init["W"], init["R"] = np.asarray(W, np.float32)[None], np.asarray(R, np.float32)[None]
-    if B is not None:
-        init["B"] = np.asarray(B, np.float32)[None]
-    nodes.append({"op": "Unsqueeze", "inputs": [x], "outputs": ["x3"], "attrs": {"axes": [0]}})
-    nodes.append({"op": "LSTM", "inputs": ["x3", "W", "R", "B" if B is not None else "", "", "h_in", "c_in"], "outputs": ["Y", "h_out", "c_out"],
-                  "attrs": {"hidden_size": int(H)}})
-    nodes.append({"op": "Squeeze", "inputs": ["Y" if read == "Y" else "h_out"], "outputs": ["hs"], "attrs": {"axes": [0, 1] if read == "Y" else [0]}})
-    chain(head, "hs", "h", last_name="actions")
-    write_onnx(path, nodes, init, ["obs", "h_in", "c_in"], ["actions", "h_out", "c_out"])
-
-
-def write_random_lstm(path: str, state_dim: int, action_dim: int, hidden: int = 256, encoder=(), head=(128,), seed: int = 0,
-                      activation: str = "Elu", bias_scale: float = 0.0):
-    """A random-weight recurrent actor (``encoder`` widths -> LSTM(``hidden``) -> ``head`` widths -> action): the recurrent
-    counterpart of ``write_random_mlp``.  Weights N(0, 1 / fan_in); biases ``bias_scale * standard_normal`` (0: none but zeros)."""
-    rng = np.random.default_rng([seed, 2])
-
-    def layers(dims, act_last):
-        out = []
-        for li in range(len(dims) - 1):
-            w = (rng.standard_normal((dims[li + 1], dims[li])) / np.sqrt(dims[li])).astype(np.float32)
-            b = (bias_scale * rng.standard_normal(dims[li + 1])).astype(np.float32)
-            out.append((w, b, activation if (act_last or li < len(dims) - 2) else None, 1.0))
-        return out
-    enc = layers([state_dim, *encoder], True)
-    I = encoder[-1] if encoder else state_dim
-    W = (rng.standard_normal((4 * hidden, I)) / np.sqrt(I)).astype(np.float32)
-    R = (rng.standard_normal((4 * hidden, hidden)) / np.sqrt(hidden)).astype(np.float32)
-    B = (bias_scale * rng.standard_normal(8 * hidden)).astype(np.float32)
-    write_recurrent_actor(path, enc, (W, R, B), layers([hidden, *head, action_dim], False))
-
-
-def write_random_mlp(path: str, state_dim: int, action_dim: int, hidden=(256, 128), seed: int = 0, activation: str = "Elu",
-                     bias_scale: float = 0.0):
-    """A random-weight actor with the usual export shape (Gemm + activation ... Gemm): stands in for the missing policy files.
-    Biases are ``bias_scale * standard_normal`` from a generator of their own: the default 0 writes all-zero biases and exactly the
-    weights (and bytes) earlier versions wrote for the same seed."""
-    rng = np.random.default_rng(seed)
-    brng = np.random.default_rng([seed, 1])
-    dims = [state_dim, *hidden, action_dim]
-    nodes, init, x = [], {}, "obs"
-    for li in range(len(dims) - 1):
-        w = (rng.standard_normal((dims[li + 1], dims[li])) / np.sqrt(dims[li])).astype(np.float32)
-        b = (bias_scale * brng.standard_normal(dims[li + 1])).astype(np.float32) if bias_scale else np.zeros(dims[li + 1], dtype=np.float32)
-        init[f"w{li}"], init[f"b{li}"] = w, b
-        y = f"h{li}" if li < len(dims) - 2 else "actions"
-        nodes.append({"op": "Gemm", "inputs": [x, f"w{li}", f"b{li}"], "outputs": [y + "_lin" if li < len(dims) - 2 else y], "attrs": {"transB": 1}})
-        if li < len(dims) - 2:
-            nodes.append({"op": activation, "inputs": [y + "_lin"], "outputs": [y]})
-        x = y
-    write_onnx(path, nodes, init, ["obs"], ["actions"])

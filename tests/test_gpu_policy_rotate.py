@@ -289,6 +289,56 @@ def test_recurrent_bits_and_stale_columns(tmp_path, every):
     tab.close()
 
 
+def test_recurrent_entry_point_refusals(tmp_path):
+    """``test_entry_point_refusals`` for the ``cosim_recurrent_table_*`` family: every refusal by its whole message, which begins with the
+    recurrent entry point's own name."""
+    import torch
+    from cosim_amd.policy import write_recurrent_actor
+    files = []
+    for k, (enc, lstm, head) in enumerate(REC[:2]):
+        files.append(str(tmp_path / f"r{k}.onnx"))
+        write_recurrent_actor(files[-1], enc, lstm, head)
+    n = 8
+    tab = RecurrentPolicyTable(files, num_envs=n, device=DEV)
+    L, p = tab._lib, tab._handle
+    stream = torch.cuda.current_stream().cuda_stream
+    x, out = torch.zeros((n, 11), device=DEV), torch.zeros((n, 4), device=DEV)
+    h, c = torch.zeros((n, 20), device=DEV), torch.zeros((n, 20), device=DEV)
+    ep = torch.zeros(n, dtype=torch.int32, device=DEV)
+    ptr = {"x": x.data_ptr(), "h": h.data_ptr(), "c": c.data_ptr(), "out": out.data_ptr(), "episode": ep.data_ptr()}
+
+    def rotating(r=0, da=None, db=None, **other):
+        a = {**ptr, **other}
+        return L.cosim_recurrent_table_forward_rotating(p, a["x"], a["h"], a["c"], a["out"], a["episode"], None, da, db, r, 1.0, stream)
+
+    def err():
+        return L.cosim_last_error().decode()
+    assert rotating() == -1
+    assert err() == "cosim_recurrent_table_forward_rotating: the table does not rotate (cosim_*_table_rotate arms it)"
+    for every in (0, -3):
+        assert L.cosim_recurrent_table_rotate(p, every) == -1 and err() == f"cosim_recurrent_table_rotate: every {every} is below 1"
+    assert L.cosim_recurrent_table_rotate(p, 2) == 0
+    assert L.cosim_recurrent_table_rotate(p, 3) == -1 and err() == "cosim_recurrent_table_rotate: the table already rotates (every 2)"
+    assert L.cosim_recurrent_table_forward(p, ptr["x"], ptr["h"], ptr["c"], ptr["out"], None, None, 0, 1.0, stream) == -1
+    assert err() == ("cosim_recurrent_table_forward: the table rotates (every 2): its lists change per step, use "
+                     "cosim_recurrent_table_forward_rotating")
+    for name in ptr:
+        assert rotating(**{name: None}) == -1 and err() == "cosim_recurrent_table_forward_rotating: null argument", name
+    for r in (1, -2):
+        assert rotating(r) == -1 and err() == f"cosim_recurrent_table_forward_rotating: range {r} outside -1..0"
+    used = ctypes.c_int()
+    rows, tiles = np.zeros(n, np.int32), np.zeros((_capacity(n, 2), 4), np.int32)
+    assert L.cosim_recurrent_table_lists(p, 1, rows.ctypes.data, tiles.ctypes.data, ctypes.byref(used)) == -1
+    assert err() == "cosim_recurrent_table_lists: range 1 outside 0..0"
+    # either done pointer may be null, and policy_now is optional
+    term = torch.ones(n, dtype=torch.uint8, device=DEV)
+    assert rotating(-1, None, term.data_ptr()) == 0
+    assert rotating(-1, term.data_ptr(), None) == 0
+    torch.cuda.synchronize()
+    assert (ep.cpu().numpy() == 2).all() and bool(torch.isfinite(out).all())
+    tab.close()
+
+
 # ---------------------------------------------------------------------------------------------------------------------- 7 - 9: loops
 NE, STEPS = 64, 40
 CHECKS = [[0, 5, "up", 0, "always", ">", -2.0, "upright"]]
