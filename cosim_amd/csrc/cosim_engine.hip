@@ -2524,6 +2524,79 @@ int cosim_debug_support(cosim_engine_t* e, int geom, const float* dirs_host, int
   return COSIM_OK;
 }
 
+// Test hooks: the device's pair routines (MPR on primitives, MPR prism - primitive, box-box) on pairs given in host arrays; the engine
+// handle names the device only.  Kinds without an O(1) support in these kernels are rejected (no silent zero-size geom).
+namespace {
+struct DbgBuf {   // a device buffer that lives for one call
+  void* p = nullptr;
+  ~DbgBuf() { if (p) (void)hipFree(p); }
+  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
+  hipError_t upload(const void* host, size_t bytes) {
+    const hipError_t r = alloc(bytes);
+    return r != hipSuccess ? r : hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
+  }
+  hipError_t download(void* host, size_t bytes) const { return hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost); }
+};
+bool prim_kind(int k) { return k == CS_GEOM_SPHERE || k == CS_GEOM_CYLINDER || k == CS_GEOM_BOX; }
+hipError_t dbg_finish() {
+  const hipError_t r = hipGetLastError();
+  return r != hipSuccess ? r : hipDeviceSynchronize();
+}
+}  // namespace
+
+int cosim_debug_mpr_prims(cosim_engine_t* e, const int* kinds_host, const float* geo_host, int n, int coop, int* irec_host, float* frec_host) {
+  if (!e || !kinds_host || !geo_host || !irec_host || !frec_host || n < 1) return fail(COSIM_EINVAL, "cosim_debug_mpr_prims: bad argument");
+  for (int i = 0; i < 2 * n; i++)
+    if (!prim_kind(kinds_host[i])) return fail(COSIM_EINVAL, "cosim_debug_mpr_prims: geom kind is not sphere / cylinder / box");
+  HIP_TRY(hipSetDevice(e->device));
+  DbgBuf kinds, geo, irec, frec;
+  hipError_t r;
+  if ((r = kinds.upload(kinds_host, (size_t)n * 2 * sizeof(int))) == hipSuccess && (r = geo.upload(geo_host, (size_t)n * 20 * sizeof(float))) == hipSuccess &&
+      (r = irec.alloc((size_t)n * 3 * sizeof(int))) == hipSuccess && (r = frec.alloc((size_t)n * 7 * sizeof(float))) == hipSuccess) {
+    if (coop) hipLaunchKernelGGL(mpr_prims_probe_kernel<true>, dim3(n), dim3(64), 0, 0, (const int*)kinds.p, (const float*)geo.p, n, (int*)irec.p, (float*)frec.p);
+    else hipLaunchKernelGGL(mpr_prims_probe_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, 0, (const int*)kinds.p, (const float*)geo.p, n, (int*)irec.p, (float*)frec.p);
+    if ((r = dbg_finish()) == hipSuccess && (r = irec.download(irec_host, (size_t)n * 3 * sizeof(int))) == hipSuccess)
+      r = frec.download(frec_host, (size_t)n * 7 * sizeof(float));
+  }
+  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_mpr_prims: ") + hipGetErrorString(r));
+  return COSIM_OK;
+}
+
+int cosim_debug_mpr_prism(cosim_engine_t* e, const float* prism_host, const int* kinds_host, const float* geo_host, int n, int* irec_host, float* frec_host) {
+  if (!e || !prism_host || !kinds_host || !geo_host || !irec_host || !frec_host || n < 1) return fail(COSIM_EINVAL, "cosim_debug_mpr_prism: bad argument");
+  for (int i = 0; i < n; i++)
+    if (!prim_kind(kinds_host[i])) return fail(COSIM_EINVAL, "cosim_debug_mpr_prism: geom kind is not sphere / cylinder / box");
+  HIP_TRY(hipSetDevice(e->device));
+  DbgBuf prism, kinds, geo, irec, frec;
+  hipError_t r;
+  if ((r = prism.upload(prism_host, (size_t)n * 10 * sizeof(float))) == hipSuccess && (r = kinds.upload(kinds_host, (size_t)n * sizeof(int))) == hipSuccess &&
+      (r = geo.upload(geo_host, (size_t)n * 10 * sizeof(float))) == hipSuccess && (r = irec.alloc((size_t)n * 3 * sizeof(int))) == hipSuccess &&
+      (r = frec.alloc((size_t)n * 7 * sizeof(float))) == hipSuccess) {
+    hipLaunchKernelGGL(mpr_prism_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, (const float*)prism.p, (const int*)kinds.p, (const float*)geo.p, n, (int*)irec.p,
+                       (float*)frec.p);
+    if ((r = dbg_finish()) == hipSuccess && (r = irec.download(irec_host, (size_t)n * 3 * sizeof(int))) == hipSuccess)
+      r = frec.download(frec_host, (size_t)n * 7 * sizeof(float));
+  }
+  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_mpr_prism: ") + hipGetErrorString(r));
+  return COSIM_OK;
+}
+
+int cosim_debug_box_box(cosim_engine_t* e, const float* geo_host, const float* margin_host, int n, int* count_host, float* out_host) {
+  if (!e || !geo_host || !margin_host || !count_host || !out_host || n < 1) return fail(COSIM_EINVAL, "cosim_debug_box_box: bad argument");
+  HIP_TRY(hipSetDevice(e->device));
+  DbgBuf geo, margin, cnt, out;
+  hipError_t r;
+  if ((r = geo.upload(geo_host, (size_t)n * 20 * sizeof(float))) == hipSuccess && (r = margin.upload(margin_host, (size_t)n * sizeof(float))) == hipSuccess &&
+      (r = cnt.alloc((size_t)n * sizeof(int))) == hipSuccess && (r = out.alloc((size_t)n * 35 * sizeof(float))) == hipSuccess &&
+      (r = hipMemset(out.p, 0, (size_t)n * 35 * sizeof(float))) == hipSuccess) {
+    hipLaunchKernelGGL(box_box_probe_kernel, dim3(n), dim3(64), 0, 0, (const float*)geo.p, (const float*)margin.p, n, (int*)cnt.p, (float*)out.p);
+    if ((r = dbg_finish()) == hipSuccess && (r = cnt.download(count_host, (size_t)n * sizeof(int))) == hipSuccess)
+      r = out.download(out_host, (size_t)n * 35 * sizeof(float));
+  }
+  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_box_box: ") + hipGetErrorString(r));
+  return COSIM_OK;
+}
+
 int cosim_debug_counters(cosim_engine_t* e, unsigned long long* out32, int clear) {   // the 32 64-bit words diagnostic kernels accumulate into
   if (!e || !out32) return fail(COSIM_EINVAL, "cosim_debug_counters: null argument");
   HIP_TRY(hipSetDevice(e->device));

@@ -3321,4 +3321,77 @@ __global__ void support_probe_kernel(const DevModel* dmp, HullGraph H, int geom,
   }
 }
 
+// Diagnostic / test kernels: the pair routines of the narrowphase on pairs given directly (cosim_debug_mpr_prims, cosim_debug_mpr_prism,
+// cosim_debug_box_box), through the instantiations the fleet kernels run.  A geom is geo[10] = pos[3], quat[4], size[3] with centre =
+// pos.  Record per pair: irec[3] = mpr_probe's answer, mpr_penetration's return value, iterations; frec[7] = depth, normal[3], pos[3].
+constexpr int GT_PRIMS = GT_SPHERE | GT_CYLINDER | GT_BOX;
+__device__ __forceinline__ void probe_cobj(CObj& o, int kind, const float* g) {
+  o.kind = kind;
+  for (int k = 0; k < 3; k++) { o.pos[k] = g[k]; o.center[k] = g[k]; o.size[k] = g[7 + k]; }
+  for (int k = 0; k < 4; k++) o.q[k] = g[3 + k];
+  o.adr = 0; o.num = 0; o.map = -1;
+}
+template <class SUP>
+__device__ __forceinline__ void probe_pair(const SUP& sup, const float* c1, const float* c2, bool store, int* irec, float* frec) {
+  const bool maybe = mpr_probe(sup, c1, c2);
+  float depth = 0.f, nr[3] = {0.f, 0.f, 0.f}, pos[3] = {0.f, 0.f, 0.f};
+  int nit = 0;
+  const bool hit = mpr_penetration(sup, c1, c2, depth, nr, pos, &nit);
+  if (store) {
+    irec[0] = maybe ? 1 : 0; irec[1] = hit ? 1 : 0; irec[2] = nit;
+    frec[0] = depth;
+    for (int k = 0; k < 3; k++) { frec[1 + k] = nr[k]; frec[4 + k] = pos[k]; }
+  }
+}
+// COOP false: one pair per lane (MprPair<.., false>, the lane-parallel route); true: one pair per wave, all lanes with the same values
+// (MprPair<.., true>, the route of the hull pairs).  Lanes past the end run the last pair and store nothing.
+template <bool COOP>
+__global__ __launch_bounds__(64) void mpr_prims_probe_kernel(const int* kinds, const float* geo, int n, int* irec, float* frec) {
+  const int ln = threadIdx.x, i = COOP ? (int)blockIdx.x : (int)blockIdx.x * 64 + ln, j = min(i, n - 1);
+  CObj a, b;
+  probe_cobj(a, kinds[2 * (size_t)j], geo + 20 * (size_t)j);
+  probe_cobj(b, kinds[2 * (size_t)j + 1], geo + 20 * (size_t)j + 10);
+  const HullGraph H{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const MprPair<GT_PRIMS, COOP> sup{a, b, H, ln};
+  probe_pair(sup, a.center, b.center, i < n && (!COOP || ln == 0), irec + 3 * (size_t)j, frec + 7 * (size_t)j);
+}
+// (prism, primitive) pairs, one per lane: prism[10] = x[3], y[3], top z[3], bottom z; the prism's centre as hfield_geom computes it
+__global__ __launch_bounds__(64) void mpr_prism_probe_kernel(const float* prism, const int* kinds, const float* geo, int n, int* irec, float* frec) {
+  const int ln = threadIdx.x, i = (int)blockIdx.x * 64 + ln, j = min(i, n - 1);
+  const float* pp = prism + 10 * (size_t)j;
+  PrismObj P;
+  for (int k = 0; k < 3; k++) { P.x[k] = pp[k]; P.y[k] = pp[3 + k]; P.zt[k] = pp[6 + k]; }
+  P.zb = pp[9];
+  CObj g;
+  probe_cobj(g, kinds[j], geo + 10 * (size_t)j);
+  const float c1[3] = {(P.x[0] + P.x[1] + P.x[2]) * (1.f / 3.f), (P.y[0] + P.y[1] + P.y[2]) * (1.f / 3.f),
+                       (P.zt[0] + P.zt[1] + P.zt[2] + 3.f * P.zb) * (1.f / 6.f)};
+  const HullGraph H{nullptr, nullptr, nullptr, nullptr, nullptr};
+  const MprPrismGeom<GT_PRIMS, false> sup{P, g, H, ln};
+  probe_pair(sup, c1, g.center, i < n, irec + 3 * (size_t)j, frec + 7 * (size_t)j);
+}
+// box pairs, one per wave, compacted as the fleet kernel does (ballot, lane order, first eight): cnt = contacts before the cap of
+// eight, out[35] = normal[3], then {pos[3], dist} per kept contact
+__global__ __launch_bounds__(64) void box_box_probe_kernel(const float* geo, const float* margin, int n, int* cnt, float* out) {
+  const int ln = threadIdx.x, i = (int)blockIdx.x;
+  if (i >= n) return;
+  const float *g1 = geo + 20 * (size_t)i, *g2 = g1 + 10;
+  float p1[3], q1[4], s1[3], p2[3], q2[4], s2[3];
+  for (int k = 0; k < 3; k++) { p1[k] = g1[k]; s1[k] = g1[7 + k]; p2[k] = g2[k]; s2[k] = g2[7 + k]; }
+  for (int k = 0; k < 4; k++) { q1[k] = g1[3 + k]; q2[k] = g2[3 + k]; }
+  float bp[3] = {0.f, 0.f, 0.f}, bn[3] = {0.f, 0.f, 1.f}, bd = 0.f;
+  const bool okb = box_box_lane(p1, q1, s1, p2, q2, s2, margin[i], ln, bp, bd, bn);
+  const unsigned long long km = __ballot(okb);
+  const int rank = __popcll(km & lanemask_lt(ln));
+  float* o = out + 35 * (size_t)i;
+  if (ln == 0) {
+    cnt[i] = (int)__popcll(km);
+    for (int k = 0; k < 3; k++) o[k] = bn[k];
+  }
+  if (okb && rank < 8) {
+    for (int k = 0; k < 3; k++) o[3 + 4 * rank + k] = bp[k];
+    o[3 + 4 * rank + 3] = bd;
+  }
+}
+
 }  // namespace cosim

@@ -93,6 +93,9 @@ def load_library():
     L.cosim_step_range.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
     L.cosim_join.argtypes = [vp, vp]
     L.cosim_debug_support.argtypes = [vp, ci, vp, ci, vp, ci]
+    L.cosim_debug_mpr_prims.argtypes = [vp, vp, vp, ci, ci, vp, vp]
+    L.cosim_debug_mpr_prism.argtypes = [vp, vp, vp, vp, ci, vp, vp]
+    L.cosim_debug_box_box.argtypes = [vp, vp, vp, ci, vp, vp]
     L.cosim_hull_support_check.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp]
     L.cosim_rollout.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.cosim_range.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(vp)]
@@ -149,7 +152,8 @@ def load_library():
                "cosim_scenario_curves_get", "cosim_scenario_curves_clear", "cosim_scenario_curves_groups", "cosim_policy_table_create",
                "cosim_policy_table_forward", "cosim_policy_table_destroy", "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
                "cosim_policy_table_rotate", "cosim_policy_table_forward_rotating", "cosim_policy_table_lists", "cosim_recurrent_table_rotate",
-               "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists"):
+               "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists", "cosim_debug_mpr_prims",
+               "cosim_debug_mpr_prism", "cosim_debug_box_box"):
         getattr(L, fn).restype = ci
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
@@ -170,7 +174,8 @@ EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "c
            "cosim_policy_table_create", "cosim_policy_table_forward", "cosim_policy_table_destroy",
            "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
            "cosim_policy_table_rotate", "cosim_policy_table_forward_rotating", "cosim_policy_table_lists",
-           "cosim_recurrent_table_rotate", "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists"]
+           "cosim_recurrent_table_rotate", "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists",
+           "cosim_debug_mpr_prims", "cosim_debug_mpr_prism", "cosim_debug_box_box"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:

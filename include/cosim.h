@@ -168,6 +168,21 @@ int cosim_hull_support_check(const float* verts, int n, const int* adr, const in
 /* Test hook (GPU): the device's own support routines on mesh geom `geom` at identity pose, for n_dirs directions (host float[n][3]):
  * out_host [n_dirs][6] = support point from the lane-parallel routine, then from the wave-cooperative one.  use_map 0: full scans. */
 int cosim_debug_support(cosim_engine_t* e, int geom, const float* dirs_host, int n_dirs, float* out_host, int use_map);
+/* Test hooks (GPU): the device's pair routines of the narrowphase on pairs given in host arrays, through the instantiations the fleet
+ * kernels run.  The engine handle names the device only; any robot's engine will do.  A geom is geo[10] = pos[3], quat[4] (w, x, y, z),
+ * size[3]; kinds are CS_GEOM_SPHERE / CS_GEOM_CYLINDER / CS_GEOM_BOX (anything else: COSIM_EINVAL); a geom's MPR centre is its pos.
+ * Record per pair: irec[3] = mpr_probe's answer, mpr_penetration's return value, loop iterations; frec[7] = depth, normal[3]
+ * (geom 1 -> geom 2), pos[3].
+ *   cosim_debug_mpr_prims: kinds [n][2], geo [n][2][10]; coop 0 = one pair per lane (the lane-parallel route), 1 = one pair per wave
+ *     (the wave-cooperative instantiation the hull pairs take).
+ *   cosim_debug_mpr_prism: heightfield prism (geom 1) against a primitive: prism [n][10] = x[3], y[3], top z[3], common bottom z (the
+ *     prism's centre is the mean of its six vertices, as in the heightfield walk), kinds [n], geo [n][10].
+ *   cosim_debug_box_box: box pairs geo [n][2][10] and margin [n], one pair per wave, contacts compacted as the step kernel does;
+ *     count [n] = contacts before the cap of eight, out [n][35] = normal[3] (box 1 -> box 2), then {pos[3], dist} of the first eight. */
+int cosim_debug_mpr_prims(cosim_engine_t* e, const int* kinds_host, const float* geo_host, int n, int coop, int* irec_host, float* frec_host);
+int cosim_debug_mpr_prism(cosim_engine_t* e, const float* prism_host, const int* kinds_host, const float* geo_host, int n, int* irec_host,
+                          float* frec_host);
+int cosim_debug_box_box(cosim_engine_t* e, const float* geo_host, const float* margin_host, int n, int* count_host, float* out_host);
 int cosim_join(cosim_engine_t* e, void* stream);
 /* Range i of "ranges": its first env, env count and stream (hipStream_t; NULL when ranges == 1; the ranges of one group -- see
  * "range_streams" -- report the same stream).  Work enqueued on that stream from

@@ -507,9 +507,48 @@ static int ccd_eq(double a, double b) {
 }
 static int vec_eq0(const double* v) { return ccd_eq(v[0], 0) && ccd_eq(v[1], 0) && ccd_eq(v[2], 0); }
 
+/* fp32-supports switch (process-global, default off): every primitive / prism support point is computed in fp32 from the fp32-rounded
+ * pose and size and returned rounded to fp32, the portal arithmetic stays fp64 -- the device's "fp32 supports, fp64 portal" arithmetic
+ * (csrc/cosim_mpr.h) restated on the CPU.  Not a bit twin of the device (which rotates by the quaternion, not by a rounded matrix): it
+ * is the stand-in that lets the bounds of tests/test_narrowphase_host.py be set without a GPU.  Mesh hulls are not affected. */
+static int g_fp32_supports = 0;
+void oracle_set_fp32_supports(int on) { g_fp32_supports = on; }
+int oracle_get_fp32_supports(void) { return g_fp32_supports; }
+static float sign0f(float x) { return x > 0 ? 1.0f : (x < 0 ? -1.0f : 0.0f); }
+static void co_support_f32(const cobj_t* o, const double* dir, double* out) {
+  const float d[3] = {(float)dir[0], (float)dir[1], (float)dir[2]};
+  if (o->kind == CO_PRISM) {
+    int i0 = d[2] < 0 ? 0 : 3, best = i0;
+    float bd = 0;
+    for (int i = i0; i < i0 + 3; i++) {
+      float t = (float)o->prism[i][0] * d[0] + (float)o->prism[i][1] * d[1] + (float)o->prism[i][2] * d[2];
+      if (i == i0 || t > bd) { bd = t; best = i; }
+    }
+    for (int k = 0; k < 3; k++) out[k] = (double)(float)o->prism[best][k];
+    return;
+  }
+  float m[9], l[3], r[3] = {0, 0, 0}, s[3] = {(float)o->size[0], (float)o->size[1], (float)o->size[2]};
+  for (int k = 0; k < 9; k++) m[k] = (float)o->mat[k];
+  for (int k = 0; k < 3; k++) l[k] = m[k] * d[0] + m[3 + k] * d[1] + m[6 + k] * d[2];
+  switch (o->kind) {
+    case CO_SPHERE: for (int k = 0; k < 3; k++) r[k] = l[k] * s[0]; break;
+    case CO_CYLINDER: {
+      float t = sqrtf(l[0] * l[0] + l[1] * l[1]);
+      if (t > (float)MINVAL) { r[0] = l[0] / t * s[0]; r[1] = l[1] / t * s[0]; }
+      r[2] = sign0f(l[2]) * s[1];
+    } break;
+    default: for (int k = 0; k < 3; k++) r[k] = sign0f(l[k]) * s[k];
+  }
+  for (int k = 0; k < 3; k++) {
+    float w = m[3 * k] * r[0] + m[3 * k + 1] * r[1] + m[3 * k + 2] * r[2];
+    out[k] = (double)((float)o->pos[k] + w);
+  }
+}
+
 /* mjccd_support (engine_collision_convex.c): furthest point of the geom along the unit world direction dir */
 static void co_support(const cobj_t* o, const double* dir, double* out) {
   double l[3], r[3] = {0, 0, 0};
+  if (g_fp32_supports && o->kind != CO_MESH) { co_support_f32(o, dir, out); return; }
   if (o->kind == CO_PRISM) { /* prism support: bottom triangle for dir z < 0, else top */
     int i0 = dir[2] < 0 ? 0 : 3, best = i0;
     double bd = dot3(o->prism[i0], dir);
@@ -1763,6 +1802,81 @@ int oracle_mpr_prims(int k1, const double* pose1, const double* size1, int k2, c
   o1.kind = k1; memcpy(o1.pos, pose1, 24); memcpy(o1.mat, pose1 + 3, 72); memcpy(o1.size, size1, 24); memcpy(o1.center, pose1, 24);
   o2.kind = k2; memcpy(o2.pos, pose2, 24); memcpy(o2.mat, pose2 + 3, 72); memcpy(o2.size, size2, 24); memcpy(o2.center, pose2, 24);
   return mpr_penetration(&o1, &o2, out7, out7 + 1, out7 + 4);
+}
+
+/* MPR between a heightfield prism (geom 1, as in hfield_collide) and a primitive (geom 2): the prism-primitive twin of oracle_mpr_prims.
+ * prism10 = x[3], y[3], top z[3], common bottom z (the device's PrismObj); the prism's centre is the mean of its six vertices. */
+static void prism_cobj(cobj_t* o, const double* prism10) {
+  memset(o, 0, sizeof *o);
+  o->kind = CO_PRISM;
+  for (int i = 0; i < 3; i++) {
+    o->prism[i][0] = o->prism[3 + i][0] = prism10[i];
+    o->prism[i][1] = o->prism[3 + i][1] = prism10[3 + i];
+    o->prism[i][2] = prism10[9];
+    o->prism[3 + i][2] = prism10[6 + i];
+  }
+  for (int k = 0; k < 3; k++) {
+    for (int q = 0; q < 6; q++) o->center[k] += o->prism[q][k] / 6.0;
+    if (g_fp32_supports) o->center[k] = (double)(float)o->center[k];   /* the device keeps the centre in fp32 */
+  }
+}
+int oracle_mpr_prism(const double* prism10, int k2, const double* pose2, const double* size2, double* out7) {
+  cobj_t o1, o2;
+  prism_cobj(&o1, prism10);
+  memset(&o2, 0, sizeof o2);
+  o2.kind = k2; memcpy(o2.pos, pose2, 24); memcpy(o2.mat, pose2 + 3, 72); memcpy(o2.size, size2, 24); memcpy(o2.center, pose2, 24);
+  return mpr_penetration(&o1, &o2, out7, out7 + 1, out7 + 4);
+}
+/* Batched forms for the narrowphase tests: geoms as the device probes take them, geo10 = pos[3], quat[4] (w, x, y, z; used as given,
+ * like the device does), size[3], kinds in CS_GEOM_* codes.  out8 per pair = hit (1 / 0), depth, dir[3], pos[3]. */
+static int prim_cobj(cobj_t* o, int cs_kind, const double* geo10) {
+  memset(o, 0, sizeof *o);
+  o->kind = cs_kind == CS_GEOM_SPHERE ? CO_SPHERE : cs_kind == CS_GEOM_CYLINDER ? CO_CYLINDER : cs_kind == CS_GEOM_BOX ? CO_BOX : -1;
+  memcpy(o->pos, geo10, 24); memcpy(o->center, geo10, 24); memcpy(o->size, geo10 + 7, 24);
+  quat2mat(o->mat, geo10 + 3);
+  return o->kind;
+}
+int oracle_mpr_prims_n(int n, const int* kinds, const double* geo, double* out8) {
+  for (int i = 0; i < n; i++) {
+    cobj_t o1, o2;
+    double* o = out8 + 8 * (size_t)i;
+    if (prim_cobj(&o1, kinds[2 * i], geo + 20 * (size_t)i) < 0 || prim_cobj(&o2, kinds[2 * i + 1], geo + 20 * (size_t)i + 10) < 0) return -1;
+    memset(o, 0, 8 * sizeof(double));
+    o[0] = mpr_penetration(&o1, &o2, o + 1, o + 2, o + 5) == 0;
+  }
+  return 0;
+}
+int oracle_mpr_prism_n(int n, const double* prism, const int* kinds, const double* geo, double* out8) {
+  for (int i = 0; i < n; i++) {
+    cobj_t o1, o2;
+    double* o = out8 + 8 * (size_t)i;
+    prism_cobj(&o1, prism + 10 * (size_t)i);
+    if (prim_cobj(&o2, kinds[i], geo + 10 * (size_t)i) < 0) return -1;
+    memset(o, 0, 8 * sizeof(double));
+    o[0] = mpr_penetration(&o1, &o2, o + 1, o + 2, o + 5) == 0;
+  }
+  return 0;
+}
+/* out36 per pair = count, nrm[3], 8 x {pos[3], dist}.  f32_mats: the rotation matrices are formed in fp32 from the quaternion and
+ * rounded, the stand-in for the device's fp32 frame arithmetic (positions and sizes are fp32 values already in the tests). */
+void oracle_box_box_n(int n, const double* geo, const double* margin, int f32_mats, double* out36) {
+  for (int i = 0; i < n; i++) {
+    const double *g1 = geo + 20 * (size_t)i, *g2 = g1 + 10;
+    double m[2][9], *o = out36 + 36 * (size_t)i;
+    for (int s = 0; s < 2; s++) {
+      const double* q = (s ? g2 : g1) + 3;
+      if (!f32_mats) { quat2mat(m[s], q); continue; }
+      const float w = (float)q[0], x = (float)q[1], y = (float)q[2], z = (float)q[3];
+      const float f[9] = {w * w + x * x - y * y - z * z, 2 * (x * y - w * z), 2 * (x * z + w * y), 2 * (x * y + w * z), w * w - x * x + y * y - z * z,
+                          2 * (y * z - w * x), 2 * (x * z - w * y), 2 * (y * z + w * x), w * w - x * x - y * y + z * z};
+      for (int k = 0; k < 9; k++) m[s][k] = (double)f[k];
+    }
+    bb_point_t pt[8];
+    memset(o, 0, 36 * sizeof(double));
+    int c = box_box_points(g1, m[0], g1 + 7, g2, m[1], g2 + 7, margin[i], pt, o + 1);
+    o[0] = c;
+    for (int k = 0; k < c; k++) { memcpy(o + 4 + 4 * k, pt[k].pos, 24); o[4 + 4 * k + 3] = pt[k].dist; }
+  }
 }
 
 /* One control step of the robot-env layer (reference flamingo_light_v1.py:131-154): PD torque from the (already

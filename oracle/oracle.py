@@ -57,6 +57,11 @@ def lib():
         L.oracle_set_boxbox_mpr.argtypes = [ctypes.c_void_p, ctypes.c_int]
         L.oracle_box_box.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_double, ctypes.c_void_p,
                                      ctypes.c_void_p]
+        L.oracle_mpr_prism.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+        L.oracle_set_fp32_supports.argtypes = [ctypes.c_int]
+        L.oracle_mpr_prims_n.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 3
+        L.oracle_mpr_prism_n.argtypes = [ctypes.c_int] + [ctypes.c_void_p] * 4
+        L.oracle_box_box_n.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p]
         L.oracle_ray_down.restype = ctypes.c_double
         L.oracle_ray_down.argtypes = [ctypes.c_void_p, ctypes.c_double, ctypes.c_double, ctypes.c_double]
         _lib = L
@@ -207,3 +212,50 @@ def box_box(pos1, mat1, size1, pos2, mat2, size2, margin=0.0):
     n = L.oracle_box_box(p1.ctypes.data, s1.ctypes.data, p2.ctypes.data, s2.ctypes.data, float(margin), out.ctypes.data, nrm.ctypes.data)
     out = out.reshape(8, 4)[:n]
     return out[:, :3].copy(), out[:, 3].copy(), nrm
+
+
+class fp32_supports:
+    """Context: the oracle's primitive / prism support points in fp32 (cosim_oracle.c co_support_f32), the CPU stand-in for the
+    device's "fp32 supports, fp64 portal" MPR.  Process-global switch, restored on exit."""
+
+    def __enter__(self):
+        self.was = lib().oracle_get_fp32_supports()
+        lib().oracle_set_fp32_supports(1)
+
+    def __exit__(self, *exc):
+        lib().oracle_set_fp32_supports(self.was)
+
+
+def mpr_prims_n(kinds, geo):
+    """MPR on n primitive pairs: kinds [n, 2] (CS_GEOM_* codes), geo [n, 2, 10] = pos, quat, size.  Returns [n, 8] = hit, depth,
+    normal (geom 1 -> geom 2), position."""
+    kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+    geo = np.ascontiguousarray(geo, dtype=np.float64)
+    n = len(kinds)
+    assert kinds.shape == (n, 2) and geo.shape == (n, 2, 10)
+    out = np.zeros((n, 8))
+    assert lib().oracle_mpr_prims_n(n, kinds.ctypes.data, geo.ctypes.data, out.ctypes.data) == 0, "geom kind without a primitive support"
+    return out
+
+
+def mpr_prism_n(prism, kinds, geo):
+    """MPR between n heightfield prisms (geom 1; [n, 10] = x3, y3, top z3, bottom z) and primitives (kinds [n], geo [n, 10])."""
+    prism = np.ascontiguousarray(prism, dtype=np.float64)
+    kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+    geo = np.ascontiguousarray(geo, dtype=np.float64)
+    n = len(kinds)
+    assert prism.shape == (n, 10) and geo.shape == (n, 10)
+    out = np.zeros((n, 8))
+    assert lib().oracle_mpr_prism_n(n, prism.ctypes.data, kinds.ctypes.data, geo.ctypes.data, out.ctypes.data) == 0
+    return out
+
+
+def box_box_n(geo, margin, f32_mats=False):
+    """mjc_BoxBox restatement on n box pairs (geo [n, 2, 10], margin [n]): (count [n], normal [n, 3], points [n, 8, 4] = pos, dist)."""
+    geo = np.ascontiguousarray(geo, dtype=np.float64)
+    margin = np.ascontiguousarray(margin, dtype=np.float64)
+    n = len(geo)
+    assert geo.shape == (n, 2, 10) and margin.shape == (n,)
+    out = np.zeros((n, 36))
+    lib().oracle_box_box_n(n, geo.ctypes.data, margin.ctypes.data, int(f32_mats), out.ctypes.data)
+    return out[:, 0].astype(int), out[:, 1:4].copy(), out[:, 4:].reshape(n, 8, 4).copy()
