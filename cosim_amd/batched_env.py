@@ -73,6 +73,20 @@ def draw_env_params(config: dict, cm: CompiledModel, seed: int, gids, gain_noise
     return {"body_mass": mass, "kp": kp, "kd": kd}
 
 
+# COSIM_* overrides of engine parameters for A/B and tuning runs, applied by the constructor in this order: (variable, parameter,
+# tolerate-refusal -- the engine may refuse a variant the model's kernels do not have, and the run goes on without it)
+_ENV_OVERRIDES = (
+    ("COSIM_WAVE_PRIORITY", "wave_priority", False),       # "base,t1,t2,t3"
+    ("COSIM_CONTACT_TWIST", "contact_twist", True),        # "1": dense-row kernel -> its contact-twist variant
+    ("COSIM_LS_SCALE", "ls_tolerance_scale", False),       # line-search gradient tolerance multiplier
+    ("COSIM_PAIR_MODE", "pair_mode", False),               # "1": hull pairs wave-cooperative
+    ("COSIM_SPLIT", "split", True),                        # split pipeline of the heightfield humanoid kernels
+    ("COSIM_NARROW_WAVES", "narrow_waves", True),
+    ("COSIM_NARROW_OCC", "narrow_occupancy", True),
+    ("COSIM_ENVS_PER_WAVE", "envs_per_wave", True),        # 1 | 2: overrides the engine's choice where the variant exists
+)
+
+
 class _Data:
     """What ``get_data()`` hands out: batched ``qpos`` / ``qvel`` views (reference: the MjData object)."""
 
@@ -186,31 +200,13 @@ class BatchedEnv:
         self.engine = Engine(self.cm, obs_cfg, self.num_envs, dev, self.seed, self.env_id0)
         assert self.engine.query("state_dim") == self.state_dim
         self.info_dim = self.engine.query("info_dim")
-        # kernel variant: COSIM_ENVS_PER_WAVE=1|2 overrides the engine's choice where the variant exists (A/B runs)
-        prio = os.environ.get("COSIM_WAVE_PRIORITY")           # "base,t1,t2,t3" (tuning runs)
-        if prio:
-            self.engine.set_param("wave_priority", np.array([float(x) for x in prio.split(",")]))
-        if os.environ.get("COSIM_CONTACT_TWIST") == "1":       # dense-row kernel -> its contact-twist variant (A/B runs)
-            try:
-                self.engine.set_param("contact_twist", np.array([1.0]))
-            except (ValueError, RuntimeError):
-                pass
-        if os.environ.get("COSIM_LS_SCALE"):                   # line-search gradient tolerance multiplier (tuning runs)
-            self.engine.set_param("ls_tolerance_scale", np.array([float(os.environ["COSIM_LS_SCALE"])]))
-        if os.environ.get("COSIM_PAIR_MODE"):                  # "1": hull pairs wave-cooperative (A/B runs)
-            self.engine.set_param("pair_mode", np.array([float(os.environ["COSIM_PAIR_MODE"])]))
-        for var, name in (("COSIM_SPLIT", "split"), ("COSIM_NARROW_WAVES", "narrow_waves"), ("COSIM_NARROW_OCC", "narrow_occupancy")):
-            if os.environ.get(var):                            # split pipeline of the heightfield humanoid kernels (A/B and tuning runs)
+        for var, name, tolerant in _ENV_OVERRIDES:
+            if os.environ.get(var):
                 try:
-                    self.engine.set_param(name, np.array([float(os.environ[var])]))
+                    self.engine.set_param(name, np.array([float(x) for x in os.environ[var].split(",")]))
                 except (ValueError, RuntimeError):
-                    pass
-        epw = os.environ.get("COSIM_ENVS_PER_WAVE")
-        if epw:
-            try:
-                self.engine.set_param("envs_per_wave", np.array([float(epw)]))
-            except (ValueError, RuntimeError):
-                pass
+                    if not tolerant:
+                        raise
 
         self.hfield_fixup = bool(hfield_fixup if hfield_fixup is not None else eng_cfg.get("hfield_fixup", False))
         if self.hfield_fixup:
@@ -299,6 +295,13 @@ class BatchedEnv:
     def _cmd_ptr(self):
         return self.user_command.data_ptr() if self.command_dim > 0 else None
 
+    def _mask_ptr(self, mask):
+        """``(mask as a contiguous uint8 device tensor, its pointer)`` of an env mask, ``(None, None)`` for none."""
+        if mask is None:
+            return None, None
+        mask = self.torch.as_tensor(mask, device=self.device).to(self.torch.uint8).contiguous()
+        return mask, mask.data_ptr()
+
     def receive_user_command(self, user_command):
         """Store the raw user command(s); scaling / position-mode transform happen in the next kernel launch
         from the pre-step pose, exactly where ``CommandWrapper.receive_user_command`` reads ``get_data()``."""
@@ -322,11 +325,7 @@ class BatchedEnv:
         self.user_command[:, :self.command_dim] = uc[:, :self.command_dim]
 
     def reset(self, mask=None):
-        t = self.torch
-        mptr = None
-        if mask is not None:
-            mask = t.as_tensor(mask, device=self.device).to(t.uint8).contiguous()
-            mptr = mask.data_ptr()
+        mask, mptr = self._mask_ptr(mask)
         self.engine.reset(mptr, self._cmd_ptr(), self.state.data_ptr(), self._stream())
         self.reset_flag = True
         if mask is None:
@@ -426,10 +425,7 @@ class BatchedEnv:
             if v.shape[0] == 1:
                 v = v.expand(self.num_envs, 3)
             v = v.contiguous()
-            mptr = None
-            if mask is not None:
-                mask = t.as_tensor(mask, device=self.device).to(t.uint8).contiguous()
-                mptr = mask.data_ptr()
+            mask, mptr = self._mask_ptr(mask)
             self.engine.push(v.data_ptr(), mptr, self._stream())
         else:
             raise NotImplementedError(f"event:{event} is not supported.")
@@ -489,17 +485,15 @@ class BatchedEnv:
             raise ValueError(f"snapshot rows have shape {tuple(rows.shape)}, expected [M, {snap.meta['snapshot_floats']}]")
         if src is None and rows.shape[0] != self.num_envs:
             raise ValueError(f"snapshot holds {rows.shape[0]} rows, this env has {self.num_envs} (give src to pick rows)")
-        sptr = mptr = None
+        sptr = None
         if src is not None:
             src = t.as_tensor(src, device=self.device).to(t.int32).contiguous()
             if tuple(src.shape) != (self.num_envs,):
                 raise ValueError(f"src must have shape ({self.num_envs},), found {tuple(src.shape)}")
             sptr = src.data_ptr()
-        if mask is not None:
-            mask = t.as_tensor(mask, device=self.device).to(t.uint8).contiguous()
-            if tuple(mask.shape) != (self.num_envs,):
-                raise ValueError(f"mask must have shape ({self.num_envs},), found {tuple(mask.shape)}")
-            mptr = mask.data_ptr()
+        mask, mptr = self._mask_ptr(mask)
+        if mask is not None and tuple(mask.shape) != (self.num_envs,):
+            raise ValueError(f"mask must have shape ({self.num_envs},), found {tuple(mask.shape)}")
         # (the engine validates src before anything below indexes with it)
         self.engine.restore(rows.data_ptr(), rows.shape[0], sptr, mptr, params, self._stream())
         self.reset_flag = True
@@ -543,6 +537,26 @@ class BatchedEnv:
         snap.steps_ago = ago
         return snap
 
+    def _read_records(self, get, ring_shape, count_shape, open_shape, include_open: bool):
+        """The reader under ``ledger()`` / ``failure_traces()`` / ``verdicts()``: one ``get(rings, counts, open rows or None, stream)``
+        into fresh int32 device tensors of the given per-env shapes, one synchronisation, then the three as host arrays (the
+        ``from_raw`` arguments; the open rows ``None`` unless ``include_open``)."""
+        t = self.torch
+        rec = t.empty((self.num_envs, *ring_shape), dtype=t.int32, device=self.device)
+        cnt = t.empty((self.num_envs, *count_shape), dtype=t.int32, device=self.device)
+        opn = t.empty((self.num_envs, *open_shape), dtype=t.int32, device=self.device) if include_open else None
+        get(rec.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
+        t.cuda.current_stream(self.device).synchronize()
+        return rec.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None
+
+    def _meta_words(self):
+        """The engine's 16 meta words of every env as an int32 device tensor ``[N, 16]``.  Joins and synchronises."""
+        t = self.torch
+        buf = t.zeros((self.num_envs, 16), dtype=t.float32, device=self.device)
+        self.engine.get("meta", buf.data_ptr(), self._stream())
+        t.cuda.synchronize(self.device)
+        return buf.view(t.int32)
+
     # ------------------------------------------------------------------ episode ledger (cosim_ledger_set / cosim_ledger_get)
     def set_ledger(self, slots: int):
         """Keep the last ``slots`` episode records of every env on the device (0: switch the ledger off and free it).  Every env
@@ -561,13 +575,8 @@ class BatchedEnv:
         from .ledger import WORDS, EpisodeLedger
         if self.ledger_slots <= 0:
             raise ValueError("ledger(): no ledger is set (BatchedEnv(ledger=SLOTS) or set_ledger)")
-        t = self.torch
-        rec = t.empty((self.num_envs, self.ledger_slots, WORDS), dtype=t.int32, device=self.device)
-        cnt = t.empty((self.num_envs,), dtype=t.int32, device=self.device)
-        opn = t.empty((self.num_envs, WORDS), dtype=t.int32, device=self.device) if include_open else None
-        self.engine.ledger_get(rec.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
-        t.cuda.current_stream(self.device).synchronize()
-        return EpisodeLedger.from_raw(rec.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, self.env_id0)
+        return EpisodeLedger.from_raw(*self._read_records(self.engine.ledger_get, (self.ledger_slots, WORDS), (), (WORDS,), include_open),
+                                      self.env_id0)
 
     # ------------------------------------------------------------------ failure traces (cosim_ftrace_set / cosim_ftrace_get)
     def set_failure_traces(self, spec, on=None):
@@ -602,16 +611,10 @@ class BatchedEnv:
         if self.failure_traces_cfg is None:
             raise ValueError("failure_traces(): no failure traces are set (BatchedEnv(failure_traces=(FRAMES, KEEP)) or set_failure_traces)")
         frames, keep, mask = self.failure_traces_cfg
-        t = self.torch
         F = self.engine.query("ftrace_frame_words")
-        buf = t.empty((self.num_envs, keep + 1, HDR + frames * F), dtype=t.int32, device=self.device)
-        cnt = t.empty((self.num_envs, 3), dtype=t.int32, device=self.device)
-        opn = t.empty((self.num_envs, HDR), dtype=t.int32, device=self.device) if include_open else None
-        self.engine.ftrace_get(buf.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
-        t.cuda.current_stream(self.device).synchronize()
         dims = {"nq": self.nq, "nv": self.nv, "nu": self.action_dim, "command_dim": self.command_dim, "info_dim": self.info_dim}
-        return FailureTraces.from_raw(buf.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, dims, mask,
-                                      self.env_id0)
+        return FailureTraces.from_raw(*self._read_records(self.engine.ftrace_get, (keep + 1, HDR + frames * F), (3,), (HDR,), include_open),
+                                      dims, mask, self.env_id0)
 
     # ------------------------------------------------------------------ fall rules (cosim_fall_set)
     def set_fall(self, rule):
@@ -641,11 +644,7 @@ class BatchedEnv:
     def end_cause(self):
         """Per env: why its latest episode ended while a fall rule was set -- int32 tensor ``[N]``, engine meta word 15: bit 1 tilt,
         2 height, 4 body contact, 0 for a time limit, a non-finite state or no end yet.  Joins and synchronises."""
-        t = self.torch
-        buf = t.zeros((self.num_envs, 16), dtype=t.float32, device=self.device)
-        self.engine.get("meta", buf.data_ptr(), self._stream())
-        t.cuda.synchronize(self.device)
-        return buf.view(t.int32)[:, 15].clone()
+        return self._meta_words()[:, 15].clone()
 
     # ------------------------------------------------------------------ scenario table (cosim_scenario_set)
     def set_scenarios(self, scenarios, mode: str = "env", check_slots: Optional[int] = None, curves: Optional[bool] = None):
@@ -685,11 +684,7 @@ class BatchedEnv:
         t = self.torch
         if scenarios is None:
             self.engine.scenario_set(None, 0, None, None, self._stream())
-            self.scenario_table, self.scenario_mode = None, "env"
-            self._info_views = None
-            self.check_slots = 0
-            self.curves_armed = False
-            self._curve_groups = None
+            self._drop_scenarios()
             return
         if mode not in MODES:
             raise ValueError(f"set_scenarios: mode must be 'env' or 'cycle', got {mode!r}")
@@ -711,11 +706,7 @@ class BatchedEnv:
                                      self._row_out.data_ptr(), self._stream())
         except Exception:
             if self.engine.query("scenario_rows") == 0:             # the engine dropped its table (a failed upload): so does the env
-                self.scenario_table, self.scenario_mode = None, "env"
-                self._info_views = None
-                self.check_slots = 0
-                self.curves_armed = False
-                self._curve_groups = None
+                self._drop_scenarios()
             raise
         self.scenario_table, self.scenario_mode = table, mode
         self._info_views = None
@@ -740,6 +731,14 @@ class BatchedEnv:
             self.engine.scenario_curves_set(None)
         if not self.curves_armed or self.engine.query("scenario_curve_groups") == 0:   # the engine dropped the groups with the cells they split
             self._curve_groups = None
+
+    def _drop_scenarios(self):
+        """The env forgets its scenario table and what rode with it (checks, curves, curve groups)."""
+        self.scenario_table, self.scenario_mode = None, "env"
+        self._info_views = None
+        self.check_slots = 0
+        self.curves_armed = False
+        self._curve_groups = None
 
     def set_curve_groups(self, groups, n_groups: Optional[int] = None, names=None):
         """Split the armed response curves by one device word per env (``cosim_scenario_curves_groups``): the cells become ``n_groups``
@@ -830,15 +829,9 @@ class BatchedEnv:
         from .checks import Verdicts
         if self.check_slots <= 0:
             raise ValueError("verdicts(): no checks are armed (BatchedEnv(scenarios=TABLE, check_slots=SLOTS) or set_scenarios(..., check_slots=))")
-        t = self.torch
         W = self.engine.query("scenario_check_words")
-        rec = t.empty((self.num_envs, self.check_slots, W), dtype=t.int32, device=self.device)
-        cnt = t.empty((self.num_envs,), dtype=t.int32, device=self.device)
-        opn = t.empty((self.num_envs, W), dtype=t.int32, device=self.device) if include_open else None
-        self.engine.scenario_checks_get(rec.data_ptr(), cnt.data_ptr(), opn.data_ptr() if include_open else None, self._stream())
-        t.cuda.current_stream(self.device).synchronize()
-        return Verdicts.from_raw(rec.cpu().numpy(), cnt.cpu().numpy(), opn.cpu().numpy() if include_open else None, self.scenario_table,
-                                 self.env_id0)
+        return Verdicts.from_raw(*self._read_records(self.engine.scenario_checks_get, (self.check_slots, W), (), (W,), include_open),
+                                 self.scenario_table, self.env_id0)
 
     def param_names(self) -> dict:
         """The names a parameter window's ``index`` may use on this env, per field (``scenario.param_names``)."""
@@ -910,22 +903,14 @@ class BatchedEnv:
 
     def spawn_rows(self) -> np.ndarray:
         """Per env: the table row its last reset took (int64 ``[N]``, engine meta word 14; meaningful once a table is set)."""
-        t = self.torch
-        buf = t.zeros((self.num_envs, 16), dtype=t.float32, device=self.device)
-        self.engine.get("meta", buf.data_ptr(), self._stream())
-        t.cuda.synchronize(self.device)
-        return buf.view(t.int32)[:, 14].cpu().numpy().astype(np.int64)
+        return self._meta_words()[:, 14].cpu().numpy().astype(np.int64)
 
     def solver_stats(self):
         """Cumulative solver counters since creation (fleet sums): control steps, constraint rows (summed over
         substeps), Newton iterations, line-search evaluations, Hessian factorisations, non-finite resets.  The counters live in the
         state record, so ``restore`` / ``fork`` put them back with the rest: afterwards they describe the restored history (a fork
         copies its source's)."""
-        t = self.torch
-        buf = t.zeros((self.num_envs, 16), dtype=t.float32, device=self.device)
-        self.engine.get("meta", buf.data_ptr(), self._stream())
-        t.cuda.synchronize(self.device)
-        mi = buf.view(t.int32).to(t.int64)
+        mi = self._meta_words().to(self.torch.int64)
         m = mi.sum(dim=0).cpu().numpy()
         # dropped_*: contacts / limit rows that found no slot (0 unless an env was stepped with a truncated constraint set);
         # max_contacts: most contacts detected in one substep by any env of the fleet

@@ -14,8 +14,10 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from . import records as rc
+from .records import NO_RESET, OPEN, TERMINATED, TRUNCATED  # noqa: F401
+
 HDR = 8
-TERMINATED, TRUNCATED, NO_RESET, OPEN = 1, 2, 8, 16
 NONE_BITS = 0x7FC00000          # value word with no sample behind it
 INFO, ABS_INFO, TRACKING_ERROR, TORQUE_MAX, UP, QPOS, QVEL, ABS_QVEL = range(8)
 ALWAYS, SETTLE, MEAN = range(3)
@@ -68,21 +70,9 @@ class Verdicts:
     def from_raw(cls, records, counts, open_rows, table, env_id0: int = 0) -> "Verdicts":
         """From what ``cosim_scenario_checks_get`` copies: rings ``[N, slots, W]``, ended-episode counts ``[N]``, open rows ``[N, W]`` or
         ``None``; ``table``: the ``ScenarioTable`` whose checks were set."""
-        records = np.asarray(records, dtype=np.int32)
-        counts = np.asarray(counts, dtype=np.int64).reshape(-1)
-        N, slots, W = records.shape
-        kept = np.minimum(counts, slots)
-        env = np.repeat(np.arange(N, dtype=np.int64), kept)
-        start = np.repeat(counts - kept, kept)
-        ordinal = start + (np.arange(len(env), dtype=np.int64) - np.repeat(np.cumsum(kept) - kept, kept))
-        words = records[env, ordinal % max(slots, 1)]
-        if open_rows is not None:
-            words = np.concatenate([words, np.asarray(open_rows, dtype=np.int32).reshape(N, W)])
-            env = np.concatenate([env, np.arange(N, dtype=np.int64)])
-            order = np.lexsort((words[:, 0], env))   # an env's open episode carries the next ordinal: it sorts last
-            words, env = words[order], env[order]
+        words, env, lost = rc.unroll_rings(records, counts, open_rows)
         names, mode, t = item_tables(table)
-        return cls(words, env + int(env_id0), counts - kept, names, mode, t, slots, env_id0)
+        return cls(words, env + int(env_id0), lost, names, mode, t, np.shape(records)[1], env_id0)
 
     def ended(self) -> np.ndarray:
         """Mask of the rows that are ended episodes (not flag 16)."""
@@ -156,36 +146,26 @@ class Verdicts:
         """``summary()`` per policy of a ``policy.PolicyTable`` (or of an int array with the policy of each local env), keyed by the
         policy's name, with ``scenario`` by ``(name, scenario row)``: as ``EpisodeLedger.by_policy``, a rotating table included (a
         record belongs to the policy of its episode ordinal)."""
-        from .ledger import policy_of_records
-        pol, names = policy_of_records(table, self.env, self.env_id0, self.episode)
-        m = self.ended()
-        out = {}
-        for k in np.unique(pol[m]):
-            mk = m & (pol == k)
-            for s in (np.unique(self.scenario[mk]) if scenario else [None]):
-                sel = mk if s is None else mk & (self.scenario == s)
-                out[names[int(k)] if s is None else (names[int(k)], int(s))] = {**self.with_shares(self._shares(sel)), "checks": self._by_name(sel)}
-        return out
+        return {key: {**self.with_shares(self._shares(sel)), "checks": self._by_name(sel)} for key, sel in rc.policy_cells(self, table, scenario)}
 
     def join(self, ledger) -> np.ndarray:
         """Per verdict row, the row of ``ledger`` (an ``EpisodeLedger``, or anything with ``env`` and ``episode`` columns such as
         ``FailureTraces``) with the same (env, episode), or -1: int64 ``[R]``.  The ordinals agree when both were set together."""
-        key = {(int(e), int(o)): i for i, (e, o) in enumerate(zip(ledger.env, ledger.episode))}
-        return np.array([key.get((int(e), int(o)), -1) for e, o in zip(self.env, self.episode)], dtype=np.int64)
+        return rc.join(self, ledger)
 
     def save(self, path: str):
         """One ``.npz`` of plain arrays (no pickle)."""
         S, I = self.item_mode.shape
         names = np.array([[(n[k] if k < len(n) else "") for k in range(I)] for n in self.names], dtype=np.str_).reshape(S, I)
         np.savez(path, words=self.words, env=self.env, lost=self.lost, names=names, item_mode=self.item_mode, item_t=self.item_t,
-                 header=np.array([self.slots, self.env_id0], dtype=np.int64))
+                 header=rc.header(self.slots, self.env_id0))
 
     @classmethod
     def load(cls, path: str) -> "Verdicts":
         with np.load(path, allow_pickle=False) as z:
-            h, mode = z["header"], z["item_mode"]
+            mode = z["item_mode"]
             names = [[str(z["names"][s, k]) for k in range(mode.shape[1]) if mode[s, k] >= 0] for s in range(mode.shape[0])]
-            return cls(z["words"], z["env"], z["lost"], names, mode, z["item_t"], int(h[0]), int(h[1]))
+            return cls(z["words"], z["env"], z["lost"], names, mode, z["item_t"], *rc.read_header(z))
 
 
 def item_tables(table):
@@ -202,17 +182,14 @@ def item_tables(table):
 def same_verdicts(a: Verdicts, b: Verdicts) -> Optional[str]:
     """``None`` if two sets of verdicts hold the same rows word for word (floats as their bits), else a sentence naming the first
     difference."""
-    if len(a) != len(b):
-        return f"{len(a)} records against {len(b)}"
-    if not np.array_equal(a.env, b.env):
-        return "env ids differ"
-    if not np.array_equal(a.lost, b.lost):
-        return f"lost counts differ: {a.lost.tolist()} against {b.lost.tolist()}"
+    head = rc.same_rows(a, b, lost_values=True)
+    if head is not None:
+        return head
     if a.words.shape != b.words.shape:
         return f"record words {a.words.shape[1]} against {b.words.shape[1]}"
-    bad = np.argwhere(a.words != b.words)
-    if len(bad):
-        r, w = bad[0]
+    bad = rc.first_difference(a.words, b.words)
+    if bad is not None:
+        r, w = bad
         return f"row {r} (env {a.env[r]}, episode {a.words[r, 0]}), word {w}: {a.words[r, w]} against {b.words[r, w]}"
     return None
 

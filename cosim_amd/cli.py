@@ -56,6 +56,24 @@ import time
 import numpy as np
 
 
+def session_opt(sess: dict):
+    """``opt(flag_value, key, default)`` over a session mapping: the flag if given, else the session's top-level ``key``, else
+    ``session["engine"][key]``, else ``default``.  Given means ``is not None``: a top-level ``0`` / ``False`` wins over the engine's."""
+    s_eng = sess.get("engine", {}) or {}
+
+    def opt(flag_value, key, default):
+        return next((v for v in (flag_value, sess.get(key), s_eng.get(key)) if v is not None), default)
+    return opt
+
+
+def rank_path(path: str, rank: int, world: int) -> str:
+    """Where a rank writes a per-rank output: ``path`` itself in a single process, else ``stem.rank<rank>.ext``."""
+    if world == 1:
+        return path
+    stem, ext = os.path.splitext(path)
+    return "%s.rank%d%s" % (stem, rank, ext)
+
+
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(prog="cosim_amd.cli", description=__doc__.split("\n")[0])
     ap.add_argument("--config", default="", help="YAML session file (see the module docstring); flags override it")
@@ -149,6 +167,8 @@ def main(argv=None) -> int:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
 
+    opt = session_opt(sess)
+
     def pick(flag, file_value, default):
         return flag if flag is not None else (file_value if file_value is not None else default)
     args.env = pick(args.env, s_env.get("id"), "flamingo_light_v1")
@@ -229,23 +249,23 @@ def main(argv=None) -> int:
         ap.error("--checkpoint / --resume run the eager loop (no --graph / --pipelined)")
     if args.history is not None and (args.history[0] < 1 or args.history[1] < 1):
         ap.error("--history SLOTS EVERY: both at least 1")
-    args.ledger = int(pick(args.ledger, sess.get("ledger") if sess.get("ledger") is not None else s_eng.get("ledger"), 0))
+    args.ledger = int(opt(args.ledger, "ledger", 0))
     if not 0 <= args.ledger <= 4096:
         ap.error("--ledger SLOTS: 0..4096")
     if args.ledger_out and args.ledger < 1:
         ap.error("--ledger-out needs --ledger SLOTS")
-    scenarios = args.scenarios if args.scenarios is not None else (sess.get("scenarios") if sess.get("scenarios") is not None else s_eng.get("scenarios"))
+    scenarios = opt(args.scenarios, "scenarios", None)
     scenario_mode = pick(args.scenario_mode, sess.get("scenario_mode", s_eng.get("scenario_mode")), "env")
     if scenario_mode not in ("env", "cycle"):
         ap.error("scenario_mode: env or cycle")
-    args.check_slots = int(pick(args.check_slots, sess.get("check_slots") if sess.get("check_slots") is not None else s_eng.get("check_slots"), 0))
+    args.check_slots = int(opt(args.check_slots, "check_slots", 0))
     if not 0 <= args.check_slots <= 64:
         ap.error("--check-slots SLOTS: 1..64")
     if (args.verdicts_out or args.require_pass) and args.check_slots < 1:
         ap.error("--verdicts-out / --require-pass need --check-slots SLOTS")
     if args.check_slots and scenarios is None:
         ap.error("--check-slots needs --scenarios: checks are rows of a scenario table")
-    args.curves = bool(pick(args.curves, sess.get("curves") if sess.get("curves") is not None else s_eng.get("curves"), False))
+    args.curves = bool(opt(args.curves, "curves", False))
     if args.curves_out and not args.curves:
         ap.error("--curves-out needs --curves")
     if args.curves and scenarios is None:
@@ -272,7 +292,7 @@ def main(argv=None) -> int:
         except ValueError as e:
             ap.error(f"--fall-* / fall: {e}")
     # failure traces: the session's value (top level or engine.failure_traces: [frames, keep] or a mapping), overridden by the flags
-    ftrace = sess.get("failure_traces") if sess.get("failure_traces") is not None else s_eng.get("failure_traces")
+    ftrace = opt(None, "failure_traces", None)
     if ftrace is not None and not isinstance(ftrace, dict):
         ftrace = {"frames": list(ftrace)[0], "keep": list(ftrace)[1]} if len(list(ftrace)) == 2 else ap.error("failure_traces: [FRAMES, KEEP] or a mapping")
     ftrace = dict(ftrace or {})
@@ -397,16 +417,13 @@ def main(argv=None) -> int:
     dt = time.perf_counter() - t0
     rep.episodes_ended = env.solver_stats()["episodes_ended"] - episodes0
     if args.ledger_out:                                             # records stay per rank: one file each
-        path = args.ledger_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.ledger_out)[:1], rank, os.path.splitext(args.ledger_out)[1])
-        env.ledger().save(path)
+        env.ledger().save(rank_path(args.ledger_out, rank, world))
     traces = env.failure_traces() if ftrace else None                # traces stay per rank, like the ledger's records
     if args.failure_traces_out:
-        path = args.failure_traces_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.failure_traces_out)[:1], rank, os.path.splitext(args.failure_traces_out)[1])
-        traces.save(path)
+        traces.save(rank_path(args.failure_traces_out, rank, world))
     verdicts = env.verdicts() if args.check_slots else None          # verdict records stay per rank too
     if args.verdicts_out:
-        path = args.verdicts_out if world == 1 else "%s.rank%d%s" % (*os.path.splitext(args.verdicts_out)[:1], rank, os.path.splitext(args.verdicts_out)[1])
-        verdicts.save(path)
+        verdicts.save(rank_path(args.verdicts_out, rank, world))
     if args.curves_out:                                              # the fleet's curves: the cells are all-reduced, every rank holds them
         fleet = rep.fleet_curves()
         if rank == 0:

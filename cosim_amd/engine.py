@@ -68,11 +68,84 @@ def build_library(force: bool = False, verbose: bool = False) -> str:
     return LIB_PATH
 
 
+_vp, _ci, _cf, _cs = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_char_p
+_pci, _pvp = ctypes.POINTER(_ci), ctypes.POINTER(_vp)
+
+# The C ABI of include/cosim.h, one row per entry point: (name, restype, argtypes).  The only place a signature is written;
+# load_library applies it, EXPORTS lists its names, tests/test_python_core_host.py holds every arity against the header.
+_ABI_ROWS = (
+    ("cosim_create", _ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, ctypes.c_uint64, ctypes.c_int64, _pvp]),
+    ("cosim_destroy", _ci, [_vp]),
+    ("cosim_query", _ci, [_vp, _cs]),
+    ("cosim_set_param", _ci, [_vp, _cs, _vp, _ci]),
+    ("cosim_reset", _ci, [_vp] * 5),
+    ("cosim_step", _ci, [_vp] * 8),
+    ("cosim_step_range", _ci, [_vp, _ci, _ci] + [_vp] * 7),
+    ("cosim_join", _ci, [_vp, _vp]),
+    ("cosim_rollout", _ci, [_vp, _ci] + [_vp] * 7),
+    ("cosim_range", _ci, [_vp, _ci, _pci, _pci, _pvp]),
+    ("cosim_range_mark", _ci, [_vp, _ci]),
+    ("cosim_get", _ci, [_vp, _cs, _vp, _vp]),
+    ("cosim_set", _ci, [_vp, _cs, _vp, _vp]),
+    ("cosim_event_push", _ci, [_vp] * 4),
+    ("cosim_spawn_set", _ci, [_vp, _vp, _ci, _vp, _ci, _cf, _ci, _vp]),
+    ("cosim_spawn_get", _ci, [_vp, _vp, _ci]),
+    ("cosim_snapshot", _ci, [_vp] * 3),
+    ("cosim_restore", _ci, [_vp, _vp, _ci, _vp, _vp, _ci, _vp]),
+    ("cosim_history_set", _ci, [_vp, _ci, _ci]),
+    ("cosim_history_get", _ci, [_vp, _ci, _vp, _pci, _vp]),
+    ("cosim_ledger_set", _ci, [_vp, _ci]),
+    ("cosim_ledger_get", _ci, [_vp] * 5),
+    ("cosim_ftrace_set", _ci, [_vp, _ci, _ci, _ci]),
+    ("cosim_ftrace_get", _ci, [_vp] * 5),
+    ("cosim_scenario_set", _ci, [_vp, _ci] + [_vp] * 6 + [_ci, _vp, _vp, _vp]),
+    ("cosim_scenario_params_set", _ci, [_vp, _ci] + [_vp] * 6),
+    ("cosim_scenario_params_get", _ci, [_vp, _vp, _ci]),
+    ("cosim_scenario_checks_set", _ci, [_vp, _ci] + [_vp] * 7 + [_ci]),
+    ("cosim_scenario_checks_get", _ci, [_vp] * 5),
+    ("cosim_scenario_curves_set", _ci, [_vp, _ci] + [_vp] * 7),
+    ("cosim_scenario_curves_get", _ci, [_vp] * 3),
+    ("cosim_scenario_curves_clear", _ci, [_vp]),
+    ("cosim_scenario_curves_groups", _ci, [_vp, _ci, _vp]),
+    ("cosim_fall_set", _ci, [_vp, _cf, _cf, _ci, _vp, _ci]),
+    ("cosim_debug_forward", _ci, [_vp, _ci, _cs, _vp, _ci]),
+    ("cosim_debug_counters", _ci, [_vp, _vp, _ci]),
+    ("cosim_debug_support", _ci, [_vp, _ci, _vp, _ci, _vp, _ci]),
+    ("cosim_debug_mpr_prims", _ci, [_vp, _vp, _vp, _ci, _ci, _vp, _vp]),
+    ("cosim_debug_mpr_prism", _ci, [_vp, _vp, _vp, _vp, _ci, _vp, _vp]),
+    ("cosim_debug_box_box", _ci, [_vp, _vp, _vp, _ci, _vp, _vp]),
+    ("cosim_hull_support_check", _ci, [_vp, _ci, _vp, _vp, _vp, _ci, _vp, _vp, _vp]),
+    ("cosim_kernel_time", _ci, [_vp, ctypes.POINTER(_cf), _pci]),
+    ("cosim_set_timing", _ci, [_vp, _ci]),
+    ("cosim_profile_step", _ci, [_vp] * 7),
+    ("cosim_policy_table_create", _ci, [_ci] + [_vp] * 6 + [_ci, _vp, _ci, _vp, _pvp]),
+    ("cosim_policy_table_forward", _ci, [_vp, _vp, _vp, _ci, _cf, _vp]),
+    ("cosim_policy_table_destroy", _ci, [_vp]),
+    ("cosim_policy_table_rotate", _ci, [_vp, _ci]),
+    ("cosim_policy_table_forward_rotating", _ci, [_vp] * 7 + [_ci, _cf, _vp]),
+    ("cosim_policy_table_lists", _ci, [_vp, _ci, _vp, _vp, _pci]),
+    ("cosim_recurrent_table_create", _ci, [_ci] + [_vp] * 17 + [_ci, _vp, _ci, _vp, _pvp]),
+    ("cosim_recurrent_table_forward", _ci, [_vp] * 7 + [_ci, _cf, _vp]),
+    ("cosim_recurrent_table_destroy", _ci, [_vp]),
+    ("cosim_recurrent_table_rotate", _ci, [_vp, _ci]),
+    ("cosim_recurrent_table_forward_rotating", _ci, [_vp] * 9 + [_ci, _cf, _vp]),
+    ("cosim_recurrent_table_lists", _ci, [_vp, _ci, _vp, _vp, _pci]),
+    ("cosim_mlp_forward", _ci, [_vp, _ci, _ci] + [_vp] * 5 + [_cf, _vp, _vp]),
+    ("cosim_lstm_cell", _ci, [_vp] * 3 + [_ci] * 3 + [_vp] * 6),
+    ("cosim_fleet_stats", _ci, [_vp, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _vp]),
+    ("cosim_fleet_hist", _ci, [_vp, _ci, _ci, _ci, _vp, _ci, _ci, _vp, _ci, _vp, _vp]),
+    ("cosim_last_error", _cs, []),
+    ("cosim_model_sizeof", _ci, []),
+    ("cosim_obs_config_sizeof", _ci, []),
+)
+ABI = {name: (restype, argtypes) for name, restype, argtypes in _ABI_ROWS}
+EXPORTS = list(ABI)
+
 _lib = None
 
 
 def load_library():
-    """Load ``libcosim_hip.so``; raises if it has not been built (no fallback)."""
+    """Load ``libcosim_hip.so`` and type every entry point from ``ABI``; raises if it has not been built (no fallback)."""
     global _lib
     if _lib is not None:
         return _lib
@@ -83,99 +156,15 @@ def load_library():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the HIP engine has no CPU fallback)")
     L = ctypes.CDLL(LIB_PATH)
-    vp, ci = ctypes.c_void_p, ctypes.c_int
-    L.cosim_create.argtypes = [vp, vp, vp, vp, vp, vp, ci, ci, ctypes.c_uint64, ctypes.c_int64, ctypes.POINTER(vp)]
-    L.cosim_destroy.argtypes = [vp]
-    L.cosim_query.argtypes = [vp, ctypes.c_char_p]
-    L.cosim_set_param.argtypes = [vp, ctypes.c_char_p, vp, ci]
-    L.cosim_reset.argtypes = [vp, vp, vp, vp, vp]
-    L.cosim_step.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.cosim_step_range.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.cosim_join.argtypes = [vp, vp]
-    L.cosim_debug_support.argtypes = [vp, ci, vp, ci, vp, ci]
-    L.cosim_debug_mpr_prims.argtypes = [vp, vp, vp, ci, ci, vp, vp]
-    L.cosim_debug_mpr_prism.argtypes = [vp, vp, vp, vp, ci, vp, vp]
-    L.cosim_debug_box_box.argtypes = [vp, vp, vp, ci, vp, vp]
-    L.cosim_hull_support_check.argtypes = [vp, ci, vp, vp, vp, ci, vp, vp, vp]
-    L.cosim_rollout.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.cosim_range.argtypes = [vp, ci, ctypes.POINTER(ci), ctypes.POINTER(ci), ctypes.POINTER(vp)]
-    L.cosim_range_mark.argtypes = [vp, ci]
-    L.cosim_get.argtypes = [vp, ctypes.c_char_p, vp, vp]
-    L.cosim_set.argtypes = [vp, ctypes.c_char_p, vp, vp]
-    L.cosim_event_push.argtypes = [vp, vp, vp, vp]
-    L.cosim_spawn_set.argtypes = [vp, vp, ci, vp, ci, ctypes.c_float, ci, vp]
-    L.cosim_spawn_get.argtypes = [vp, vp, ci]
-    L.cosim_snapshot.argtypes = [vp, vp, vp]
-    L.cosim_restore.argtypes = [vp, vp, ci, vp, vp, ci, vp]
-    L.cosim_history_set.argtypes = [vp, ci, ci]
-    L.cosim_history_get.argtypes = [vp, ci, vp, ctypes.POINTER(ci), vp]
-    L.cosim_ledger_set.argtypes = [vp, ci]
-    L.cosim_ledger_get.argtypes = [vp, vp, vp, vp, vp]
-    L.cosim_ftrace_set.argtypes = [vp, ci, ci, ci]
-    L.cosim_ftrace_get.argtypes = [vp, vp, vp, vp, vp]
-    L.cosim_scenario_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp]
-    L.cosim_scenario_params_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp]
-    L.cosim_scenario_params_get.argtypes = [vp, vp, ci]
-    L.cosim_scenario_checks_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp, ci]
-    L.cosim_scenario_checks_get.argtypes = [vp, vp, vp, vp, vp]
-    L.cosim_scenario_curves_set.argtypes = [vp, ci, vp, vp, vp, vp, vp, vp, vp]
-    L.cosim_scenario_curves_get.argtypes = [vp, vp, vp]
-    L.cosim_scenario_curves_clear.argtypes = [vp]
-    L.cosim_scenario_curves_groups.argtypes = [vp, ci, vp]
-    L.cosim_fall_set.argtypes = [vp, ctypes.c_float, ctypes.c_float, ci, vp, ci]
-    L.cosim_debug_forward.argtypes = [vp, ci, ctypes.c_char_p, vp, ci]
-    L.cosim_kernel_time.argtypes = [vp, ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ci)]
-    L.cosim_set_timing.argtypes = [vp, ci]
-    L.cosim_profile_step.argtypes = [vp] * 7
-    L.cosim_policy_table_create.argtypes = [ci, vp, vp, vp, vp, vp, vp, ci, vp, ci, vp, ctypes.POINTER(vp)]
-    L.cosim_policy_table_forward.argtypes = [vp, vp, vp, ci, ctypes.c_float, vp]
-    L.cosim_policy_table_destroy.argtypes = [vp]
-    L.cosim_recurrent_table_create.argtypes = [ci] + [vp] * 17 + [ci, vp, ci, vp, ctypes.POINTER(vp)]
-    L.cosim_recurrent_table_forward.argtypes = [vp] * 7 + [ci, ctypes.c_float, vp]
-    L.cosim_recurrent_table_destroy.argtypes = [vp]
-    L.cosim_policy_table_rotate.argtypes = [vp, ci]
-    L.cosim_policy_table_forward_rotating.argtypes = [vp] * 7 + [ci, ctypes.c_float, vp]
-    L.cosim_policy_table_lists.argtypes = [vp, ci, vp, vp, ctypes.POINTER(ci)]
-    L.cosim_recurrent_table_rotate.argtypes = [vp, ci]
-    L.cosim_recurrent_table_forward_rotating.argtypes = [vp] * 9 + [ci, ctypes.c_float, vp]
-    L.cosim_recurrent_table_lists.argtypes = [vp, ci, vp, vp, ctypes.POINTER(ci)]
-    L.cosim_mlp_forward.argtypes = [vp, ci, ci, vp, vp, vp, vp, vp, ctypes.c_float, vp, vp]
-    L.cosim_lstm_cell.argtypes = [vp] * 3 + [ci] * 3 + [vp] * 6
-    L.cosim_last_error.restype = ctypes.c_char_p
-    for fn in ("cosim_mlp_forward", "cosim_lstm_cell","cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "cosim_reset", "cosim_step", "cosim_step_range", "cosim_get",
-               "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_rollout",
-               "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
-               "cosim_profile_step", "cosim_model_sizeof", "cosim_obs_config_sizeof", "cosim_spawn_set", "cosim_spawn_get",
-               "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get", "cosim_ledger_set", "cosim_ledger_get",
-               "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get", "cosim_scenario_params_set",
-               "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get", "cosim_scenario_curves_set",
-               "cosim_scenario_curves_get", "cosim_scenario_curves_clear", "cosim_scenario_curves_groups", "cosim_policy_table_create",
-               "cosim_policy_table_forward", "cosim_policy_table_destroy", "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
-               "cosim_policy_table_rotate", "cosim_policy_table_forward_rotating", "cosim_policy_table_lists", "cosim_recurrent_table_rotate",
-               "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists", "cosim_debug_mpr_prims",
-               "cosim_debug_mpr_prism", "cosim_debug_box_box"):
-        getattr(L, fn).restype = ci
+    for name, (restype, argtypes) in ABI.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):
         raise RuntimeError("cosim_model_t layout mismatch between include/cosim_model.h and libcosim_hip.so: rebuild")
     if L.cosim_obs_config_sizeof() != ctypes.sizeof(ObsConfig):
         raise RuntimeError("cosim_obs_config_t layout mismatch: rebuild libcosim_hip.so")
     _lib = L
     return L
-
-
-EXPORTS = ["cosim_create", "cosim_destroy", "cosim_query", "cosim_set_param", "cosim_reset", "cosim_step", "cosim_step_range", "cosim_get",
-           "cosim_join", "cosim_range", "cosim_range_mark", "cosim_debug_counters", "cosim_rollout", "cosim_hull_support_check", "cosim_debug_support",
-           "cosim_set", "cosim_event_push", "cosim_debug_forward", "cosim_kernel_time", "cosim_set_timing",
-           "cosim_profile_step", "cosim_mlp_forward", "cosim_lstm_cell", "cosim_fleet_stats", "cosim_fleet_hist", "cosim_last_error", "cosim_model_sizeof", "cosim_obs_config_sizeof",
-           "cosim_spawn_set", "cosim_spawn_get", "cosim_snapshot", "cosim_restore", "cosim_history_set", "cosim_history_get",
-           "cosim_ledger_set", "cosim_ledger_get", "cosim_scenario_set", "cosim_fall_set", "cosim_ftrace_set", "cosim_ftrace_get",
-           "cosim_scenario_params_set", "cosim_scenario_params_get", "cosim_scenario_checks_set", "cosim_scenario_checks_get",
-           "cosim_scenario_curves_set", "cosim_scenario_curves_get", "cosim_scenario_curves_clear", "cosim_scenario_curves_groups",
-           "cosim_policy_table_create", "cosim_policy_table_forward", "cosim_policy_table_destroy",
-           "cosim_recurrent_table_create", "cosim_recurrent_table_forward", "cosim_recurrent_table_destroy",
-           "cosim_policy_table_rotate", "cosim_policy_table_forward_rotating", "cosim_policy_table_lists",
-           "cosim_recurrent_table_rotate", "cosim_recurrent_table_forward_rotating", "cosim_recurrent_table_lists",
-           "cosim_debug_mpr_prims", "cosim_debug_mpr_prism", "cosim_debug_box_box"]
 
 
 def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: float, auto_reset: bool) -> ObsConfig:
@@ -239,6 +228,14 @@ def make_obs_config(config: dict, obs_to_dim: Dict[str, int], control_freq: floa
 
 def _unknown(name, obs_to_dim):
     return obs_to_dim[name]  # raises KeyError like wrappers.py:116 does for names no env provides
+
+
+def _columns(arrays, dtypes):
+    """The host arrays of a CSR table, each contiguous in the dtype its column has in the C ABI."""
+    arrays = tuple(arrays)
+    if len(arrays) != len(dtypes):
+        raise ValueError(f"expected {len(dtypes)} table arrays, got {len(arrays)}")
+    return [np.ascontiguousarray(x, dtype=dt) for x, dt in zip(arrays, dtypes)]
 
 
 class Engine:
@@ -368,6 +365,22 @@ class Engine:
         (or ``None``) open headers ``[N, 16]``, int32."""
         self._check(self.L.cosim_ftrace_get(self.h, buffers_ptr, counts_ptr, open_ptr, stream))
 
+    def _csr_set(self, who: str, csr, dtypes, t_width: int, tail=()):
+        """The body the ``scenario_*_set`` wrappers share: ``csr`` = ``(adr [S + 1], t [n, t_width], one column [n] per entry of
+        dtypes)`` goes to entry point ``cosim_<who>`` as contiguous host arrays, followed by the integers ``tail``; ``None`` clears
+        (S = 0, null arrays, zeros for ``tail``).  ``who`` is also the word the two refusals begin with."""
+        fn = getattr(self.L, "cosim_" + who)
+        if csr is None:
+            self._check(fn(self.h, 0, *[None] * (2 + len(dtypes)), *[0] * len(tail)))
+            return
+        adr, t, *cols = _columns(csr, (np.int32, np.int32, *dtypes))
+        if adr.ndim != 1 or adr.size < 1:
+            raise ValueError(f"{who}: adr must be [S + 1]")
+        n = int(max(adr.max(), 0))
+        if t.size < t_width * n or min(c.size for c in cols) < n:   # (the engine reads the arrays up to the addresses)
+            raise ValueError(f"{who}: the item arrays are shorter than their row addresses ({n} items)")
+        self._check(fn(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, *[c.ctypes.data for c in cols], *tail))
+
     def scenario_set(self, csr, mode: int, cmd_out_ptr, row_out_ptr, stream=None):
         """``cosim_scenario_set``: ``csr`` = the six host arrays ``(key_adr, key_t, key_cmd, push_adr, push_t, push_v)`` of
         ``ScenarioTable.pack`` (``None``: clear the table); ``cmd_out_ptr`` ``[N, command_dim]`` float32 and ``row_out_ptr`` ``[N]``
@@ -375,10 +388,7 @@ class Engine:
         if csr is None:
             self._check(self.L.cosim_scenario_set(self.h, 0, None, None, None, None, None, None, 0, None, None, stream))
             return
-        ka, kt, kc, pa, pt, pv = csr
-        ka, pa = np.ascontiguousarray(ka, dtype=np.int32), np.ascontiguousarray(pa, dtype=np.int32)
-        kt, pt = np.ascontiguousarray(kt, dtype=np.int32), np.ascontiguousarray(pt, dtype=np.int32)
-        kc, pv = np.ascontiguousarray(kc, dtype=np.float32), np.ascontiguousarray(pv, dtype=np.float32)
+        ka, kt, kc, pa, pt, pv = _columns(csr, (np.int32, np.int32, np.float32, np.int32, np.int32, np.float32))
         if ka.shape != pa.shape or ka.ndim != 1 or ka.size < 1:
             raise ValueError("scenario_set: key_adr and push_adr must both be [S + 1]")
         nk, npw, cd = int(max(ka.max(), 0)), int(max(pa.max(), 0)), self.query("command_dim")
@@ -390,38 +400,12 @@ class Engine:
     def scenario_params_set(self, csr):
         """``cosim_scenario_params_set``: ``csr`` = the six host arrays ``(adr, t, field, index, op, value)`` of
         ``ScenarioTable.pack_params`` (``None``: clear the windows)."""
-        if csr is None:
-            self._check(self.L.cosim_scenario_params_set(self.h, 0, None, None, None, None, None, None))
-            return
-        adr, t, field, index, op, value = csr
-        adr, t = np.ascontiguousarray(adr, dtype=np.int32), np.ascontiguousarray(t, dtype=np.int32)
-        field, index, op = (np.ascontiguousarray(x, dtype=np.int32) for x in (field, index, op))
-        value = np.ascontiguousarray(value, dtype=np.float32)
-        if adr.ndim != 1 or adr.size < 1:
-            raise ValueError("scenario_params_set: adr must be [S + 1]")
-        n = int(max(adr.max(), 0))
-        if t.size < 2 * n or min(field.size, index.size, op.size, value.size) < n:   # (the engine reads the arrays up to the addresses)
-            raise ValueError(f"scenario_params_set: the item arrays are shorter than their row addresses ({n} items)")
-        self._check(self.L.cosim_scenario_params_set(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, field.ctypes.data, index.ctypes.data,
-                                                     op.ctypes.data, value.ctypes.data))
+        self._csr_set("scenario_params_set", csr, (np.int32, np.int32, np.int32, np.float32), 2)
 
     def scenario_checks_set(self, csr, slots: int = 0):
         """``cosim_scenario_checks_set``: ``csr`` = the seven host arrays ``(adr, t, signal, index, mode, cmp, bound)`` of
         ``ScenarioTable.pack_checks`` (``None``: clear the checks); ``slots`` verdict records per env."""
-        if csr is None:
-            self._check(self.L.cosim_scenario_checks_set(self.h, 0, None, None, None, None, None, None, None, 0))
-            return
-        adr, t, signal, index, mode, cmp, bound = csr
-        adr, t = np.ascontiguousarray(adr, dtype=np.int32), np.ascontiguousarray(t, dtype=np.int32)
-        signal, index, mode, cmp = (np.ascontiguousarray(x, dtype=np.int32) for x in (signal, index, mode, cmp))
-        bound = np.ascontiguousarray(bound, dtype=np.float32)
-        if adr.ndim != 1 or adr.size < 1:
-            raise ValueError("scenario_checks_set: adr must be [S + 1]")
-        n = int(max(adr.max(), 0))
-        if t.size < 2 * n or min(signal.size, index.size, mode.size, cmp.size, bound.size) < n:   # (the engine reads the arrays up to the addresses)
-            raise ValueError(f"scenario_checks_set: the item arrays are shorter than their row addresses ({n} items)")
-        self._check(self.L.cosim_scenario_checks_set(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, signal.ctypes.data,
-                                                     index.ctypes.data, mode.ctypes.data, cmp.ctypes.data, bound.ctypes.data, int(slots)))
+        self._csr_set("scenario_checks_set", csr, (np.int32, np.int32, np.int32, np.int32, np.float32), 2, (int(slots),))
 
     def scenario_checks_get(self, records_ptr, counts_ptr, open_ptr=None, stream=None):
         """``cosim_scenario_checks_get``: rings ``[N, slots, words]``, ended-episode counts ``[N]`` and (or ``None``) open rows ``[N,
@@ -431,20 +415,7 @@ class Engine:
     def scenario_curves_set(self, csr):
         """``cosim_scenario_curves_set``: ``csr`` = the seven host arrays ``(adr, t [n, 3], signal, index, lo, hi, bins)`` of
         ``ScenarioTable.pack_curves`` (``None``: clear the curves)."""
-        if csr is None:
-            self._check(self.L.cosim_scenario_curves_set(self.h, 0, None, None, None, None, None, None, None))
-            return
-        adr, t, signal, index, lo, hi, bins = csr
-        adr, t = np.ascontiguousarray(adr, dtype=np.int32), np.ascontiguousarray(t, dtype=np.int32)
-        signal, index, bins = (np.ascontiguousarray(x, dtype=np.int32) for x in (signal, index, bins))
-        lo, hi = np.ascontiguousarray(lo, dtype=np.float32), np.ascontiguousarray(hi, dtype=np.float32)
-        if adr.ndim != 1 or adr.size < 1:
-            raise ValueError("scenario_curves_set: adr must be [S + 1]")
-        n = int(max(adr.max(), 0))
-        if t.size < 3 * n or min(signal.size, index.size, lo.size, hi.size, bins.size) < n:   # (the engine reads the arrays up to the addresses)
-            raise ValueError(f"scenario_curves_set: the item arrays are shorter than their row addresses ({n} items)")
-        self._check(self.L.cosim_scenario_curves_set(self.h, int(adr.size) - 1, adr.ctypes.data, t.ctypes.data, signal.ctypes.data,
-                                                     index.ctypes.data, lo.ctypes.data, hi.ctypes.data, bins.ctypes.data))
+        self._csr_set("scenario_curves_set", csr, (np.int32, np.int32, np.float32, np.float32, np.int32), 3)
 
     def scenario_curves_groups(self, n_groups: int, group_ptr=None):
         """``cosim_scenario_curves_groups``: the cells become ``n_groups`` planes keyed by the int32 ``[N]`` device words at ``group_ptr``
@@ -487,8 +458,6 @@ class Engine:
 
     def debug_counters(self, clear: bool = True) -> np.ndarray:
         out = np.zeros(32, dtype=np.uint64)
-        self.L.cosim_debug_counters.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]
-        self.L.cosim_debug_counters.restype = ctypes.c_int
         self._check(self.L.cosim_debug_counters(self.h, out.ctypes.data, int(clear)))
         return out
 

@@ -14,10 +14,11 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from . import records as rc
+from .records import FELL_CONTACT, FELL_HEIGHT, FELL_TILT, NO_RESET, NONFINITE, OPEN, TERMINATED, TRUNCATED
+
 HDR, FRAME_HDR, NCNT = 16, 4, 16
 MAX_FRAMES, MAX_KEEP = 1024, 64
-TERMINATED, TRUNCATED, NONFINITE, NO_RESET, OPEN = 1, 2, 4, 8, 16      # the ledger's flags (cosim_amd/ledger.py)
-FELL_TILT, FELL_HEIGHT, FELL_CONTACT = 32, 64, 128
 ON_NAMES = {"terminated": TERMINATED, "truncated": TRUNCATED, "nonfinite": NONFINITE, "tilt": FELL_TILT, "height": FELL_HEIGHT,
             "contact": FELL_CONTACT}
 ON_ALL = sum(ON_NAMES.values())
@@ -143,17 +144,12 @@ class FailureTraces:
             raise ValueError(f"FailureTraces.from_raw: buffers of {buffers.shape[2]} words are not 16 + frames * {F}")
         counts = np.asarray(counts, dtype=np.int64).reshape(N, 3)
         work, trig = counts[:, 0], counts[:, 1]
-        kept = np.minimum(trig, keep)
-        env = np.repeat(np.arange(N, dtype=np.int64), kept)
-        age = np.repeat(kept, kept) - 1 - (np.arange(len(env), dtype=np.int64) - np.repeat(np.cumsum(kept) - kept, kept))   # oldest first
-        b = (work[env] - 1 - age) % nbuf
+        env, k, kept = rc.kept_rows(trig, keep)
+        b = (work[env] - (kept[env] - k)) % nbuf                                  # oldest first: age kept - 1 - k behind the working buffer
         headers = buffers[env, b, :HDR]
         if open_rows is not None:
-            headers = np.concatenate([headers, np.asarray(open_rows, dtype=np.int32).reshape(N, HDR)])
-            env = np.concatenate([env, np.arange(N, dtype=np.int64)])
-            b = np.concatenate([b, work])
-            order = np.lexsort((headers[:, 0], env))                              # an env's open window carries the next ordinal
-            headers, env, b = headers[order], env[order], b[order]
+            headers, env, order = rc.merge_open(headers, env, np.asarray(open_rows, dtype=np.int32).reshape(N, HDR))
+            b = np.concatenate([b, work])[order]
         rings = buffers[env, b, HDR:].reshape(len(env), T, F)
         pos = (headers[:, 4:5].astype(np.int64) + np.arange(T)[None, :]) % T
         words = np.take_along_axis(rings, pos[:, :, None], axis=1)
@@ -192,8 +188,7 @@ class FailureTraces:
     def join(self, ledger) -> np.ndarray:
         """Per trace, the row of ``ledger`` (an ``EpisodeLedger``) with the same (env, episode), or -1 (the ledger's ring has
         overwritten it, or the two were not set together).  The ordinals agree when traces and ledger are set together."""
-        at = {(int(e), int(o)): i for i, (e, o) in enumerate(zip(ledger.env, ledger.episode))}
-        return np.array([at.get((int(e), int(o)), -1) for e, o in zip(self.env, self.episode)], dtype=np.int64)
+        return rc.join(self, ledger)
 
     def save(self, path: str):
         """One ``.npz`` of plain arrays, the metadata as JSON bytes (no pickle)."""
@@ -208,18 +203,13 @@ class FailureTraces:
 
 def same_traces(a: FailureTraces, b: FailureTraces) -> Optional[str]:
     """``None`` if two sets hold the same rows, word for word (floats as bits), else a sentence naming the first difference."""
-    if len(a) != len(b):
-        return f"{len(a)} traces against {len(b)}"
-    if a.meta != b.meta:
-        return f"metadata differs: {a.meta} against {b.meta}"
-    if not np.array_equal(a.env, b.env):
-        return "env ids differ"
-    if not np.array_equal(a.lost, b.lost):
-        return "lost counts differ"
+    head = rc.same_rows(a, b, "traces", meta=True)
+    if head is not None:
+        return head
     for name, x, y in (("header", a.headers, b.headers), ("frame", a.words.reshape(len(a), -1), b.words.reshape(len(b), -1))):
-        bad = np.argwhere(x != y)
-        if len(bad):
-            r, w = bad[0]
+        bad = rc.first_difference(x, y)
+        if bad is not None:
+            r, w = bad
             return f"{name} word {w} of row {r} (env {a.env[r]}, episode {a.headers[r, 0]}): {x[r, w]} against {y[r, w]}"
     return None
 

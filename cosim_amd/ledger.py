@@ -12,10 +12,11 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from . import records as rc
+from .records import (FELL, FELL_CONTACT, FELL_HEIGHT, FELL_TILT, NO_RESET, NONFINITE, OPEN, TERMINATED, TRUNCATED,  # noqa: F401
+                      policy_of_records)
+
 WORDS = 16
-TERMINATED, TRUNCATED, NONFINITE, NO_RESET, OPEN = 1, 2, 4, 8, 16
-FELL_TILT, FELL_HEIGHT, FELL_CONTACT = 32, 64, 128   # a fall rule ended the episode (cosim_amd/fall.py): (cause & 7) << 5
-FELL = FELL_TILT | FELL_HEIGHT | FELL_CONTACT
 INT_FIELDS = {"episode": 0, "length": 1, "flags": 2, "spawn_row": 3, "steps_seen": 4}
 FLOAT_FIELDS = {"mean_action_diff_RMSE": 5, "mean_tracking_err_0": 6, "mean_tracking_err_1": 7, "mean_tracking_err_2": 8,
                 "mean_abs_torque": 9, "peak_abs_torque": 10, "mean_lin_vel_x": 11, "peak_tracking_err_0": 12}
@@ -49,20 +50,8 @@ class EpisodeLedger:
     def from_raw(cls, records, counts, open_rows=None, env_id0: int = 0) -> "EpisodeLedger":
         """From what ``cosim_ledger_get`` copies: rings ``[N, slots, 16]``, ended-episode counts ``[N]``, open rows ``[N, 16]`` or
         ``None``.  Episode ``o`` of an env lies in slot ``o mod slots``; the ring holds the last ``min(count, slots)``."""
-        records = np.asarray(records, dtype=np.int32)
-        counts = np.asarray(counts, dtype=np.int64).reshape(-1)
-        N, slots = records.shape[0], records.shape[1]
-        kept = np.minimum(counts, slots)
-        env = np.repeat(np.arange(N, dtype=np.int64), kept)
-        start = np.repeat(counts - kept, kept)
-        ordinal = start + (np.arange(len(env), dtype=np.int64) - np.repeat(np.cumsum(kept) - kept, kept))
-        words = records[env, ordinal % max(slots, 1)]
-        if open_rows is not None:
-            words = np.concatenate([words, np.asarray(open_rows, dtype=np.int32).reshape(N, WORDS)])
-            env = np.concatenate([env, np.arange(N, dtype=np.int64)])
-            order = np.lexsort((words[:, 0], env))   # an env's open episode carries the next ordinal: it sorts last
-            words, env = words[order], env[order]
-        return cls(words, env + int(env_id0), counts - kept, slots, env_id0)
+        words, env, lost = rc.unroll_rings(records, counts, open_rows)
+        return cls(words, env + int(env_id0), lost, np.shape(records)[1], env_id0)
 
     def ended(self) -> np.ndarray:
         """Mask of the rows that are ended episodes (not flag 16)."""
@@ -146,47 +135,17 @@ class EpisodeLedger:
         (or a cell) without an ended episode has no entry.  Under a ROTATING table a record belongs to the policy that drove that episode,
         ``table.policy_of(env, episode ordinal)``: the ordinals are the table's counters when the ledger was armed in the env's
         constructor and the table drove the env from its first step."""
-        pol, names = policy_of_records(table, self.env, self.env_id0, self.episode)
-        m = self.ended()
         with_fell = self._with_fell(fell)
-        out = {}
-        for k in np.unique(pol[m]):
-            mk = m & (pol == k)
-            if not scenario:
-                out[names[int(k)]] = self._cell(mk, with_fell)
-                continue
-            for s in np.unique(self.scenario[mk]):
-                out[(names[int(k)], int(s))] = self._cell(mk & (self.scenario == s), with_fell)
-        return out
+        return {key: self._cell(sel, with_fell) for key, sel in rc.policy_cells(self, table, scenario)}
 
     def save(self, path: str):
         """One ``.npz`` of plain arrays (no pickle)."""
-        np.savez(path, words=self.words, env=self.env, lost=self.lost, header=np.array([self.slots, self.env_id0], dtype=np.int64))
+        np.savez(path, words=self.words, env=self.env, lost=self.lost, header=rc.header(self.slots, self.env_id0))
 
     @classmethod
     def load(cls, path: str) -> "EpisodeLedger":
         with np.load(path, allow_pickle=False) as z:
-            h = z["header"]
-            return cls(z["words"], z["env"], z["lost"], int(h[0]), int(h[1]))
-
-
-def policy_of_records(table, env, env_id0: int, episode=None):
-    """``(policy index int64 [R], names)`` for records of the global env ids ``env``: ``table`` is a ``policy.PolicyTable`` (its
-    ``policy_of`` and ``names``) or an int array holding the policy of each local env (env ``env_id0 + i`` is entry ``i``).
-    ``episode``: the records' episode ordinals, which a rotating table (``rotate_every``) attributes by; others ignore them."""
-    env = np.asarray(env, dtype=np.int64)
-    if hasattr(table, "policy_of"):
-        if getattr(table, "rotate_every", None) is not None:
-            if episode is None:
-                raise ValueError("by_policy: the table rotates, so a record is attributed by (env, episode ordinal): pass the records' ordinals")
-            return np.asarray(table.policy_of(env, np.asarray(episode, dtype=np.int64)), dtype=np.int64), list(table.names)
-        return np.asarray(table.policy_of(env), dtype=np.int64), list(table.names)
-    a = np.asarray(table, dtype=np.int64).reshape(-1)
-    loc = env - int(env_id0)
-    if loc.size and (loc.min() < 0 or loc.max() >= len(a)):
-        raise ValueError(f"by_policy: the array names the policy of {len(a)} local envs, the records hold env ids "
-                         f"{int(env.min())}..{int(env.max())} (first id {env_id0})")
-    return a[loc], [str(k) for k in range(int(a.max()) + 1 if a.size else 0)]
+            return cls(z["words"], z["env"], z["lost"], *rc.read_header(z))
 
 
 def _records(episode, length, flags, spawn, seen, s, peak, scenario=None) -> np.ndarray:
@@ -303,12 +262,9 @@ def reference_ledger(info_rows, terminated, truncated, commands, nan_resets, spa
 def same_records(a: EpisodeLedger, b: EpisodeLedger) -> Optional[str]:
     """``None`` if two ledgers hold the same rows -- ints as ints, floats as float32 bits, two non-finite floats count as equal --,
     else a sentence naming the first difference."""
-    if len(a) != len(b):
-        return f"{len(a)} records against {len(b)}"
-    if not np.array_equal(a.env, b.env):
-        return "env ids differ"
-    if not np.array_equal(a.lost, b.lost):
-        return "lost counts differ"
+    head = rc.same_rows(a, b)
+    if head is not None:
+        return head
     for name, w in list(INT_FIELDS.items()) + [("scenario + 1", SCENARIO_WORD), ("padding", 14), ("padding", 15)]:
         bad = np.nonzero(a.words[:, w] != b.words[:, w])[0]
         if len(bad):

@@ -34,12 +34,8 @@ class FleetReporter:
         self._fast = hasattr(env, "info_buf") and hasattr(env, "user_command")   # BatchedEnv: the info dict is views of these
         self._lib = None
         if self._fast and str(env.device).startswith("cuda") and len(self.names) <= 32:
-            import ctypes
             from .engine import load_library
-            self._lib = load_library()
-            self._lib.cosim_fleet_stats.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                                                    ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
-            self._lib.cosim_last_error.restype = ctypes.c_char_p
+            self._lib = load_library()                                # (typed there: engine.ABI)
         self.steps = 0
         self.episodes_ended = 0
         self.policy_table = None      # a policy.PolicyTable (Runner sets it): summary() then breaks episodes and checks down by policy (a rotating one: by the policy of each record's episode ordinal)
@@ -47,7 +43,6 @@ class FleetReporter:
         if percentiles:
             if self._lib is None:
                 raise RuntimeError("FleetReporter(percentiles=True) needs the BatchedEnv GPU path (libcosim_hip.so)")
-            import ctypes
             from .model import get_field
             t = env.torch
             blob = env.cm.blob
@@ -55,8 +50,6 @@ class FleetReporter:
             self.hist_hi = np.array([2.0, 8.0, 8.0, 8.0] + [max(1e-3, m) for m in maxtq] + [8.0] * min(cd, 3), dtype=np.float32)
             self._hist_hi_dev = t.tensor(self.hist_hi, device=env.device)
             self.hist = t.zeros((len(self.names), NBINS), dtype=t.float64, device=env.device)
-            self._lib.cosim_fleet_hist.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int,
-                                                   ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
 
     def write_info_range(self, first: int, count: int):
         """GPU fast path for a fleet stepped as several ranges on streams of their own (``BatchedEnv.step_range``): reduce the info
@@ -207,16 +200,21 @@ class FleetReporter:
         out = v.summary()
         out["by_scenario"] = {str(k): x for k, x in v.by_scenario().items()}
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            t = self.env.torch
-            c = v.counts()
-            keys = sorted(c)
-            x = t.tensor([c[k] for k in keys], dtype=t.int64, device=self.env.device)
-            dist.all_reduce(x, op=dist.ReduceOp.SUM)
-            out["fleet"] = Verdicts.with_shares({k: int(y) for k, y in zip(keys, x.cpu().tolist())})
+            out["fleet"] = Verdicts.with_shares(self._allreduce_counts(v.counts()))
         if self.policy_table is not None:
             out["by_policy"] = self._by_policy(v.by_policy(self.policy_table), v.by_policy(self.policy_table, scenario=True),
                                                [k for k in v.counts() if k != "lost"], Verdicts.with_shares)
         return out
+
+    def _allreduce_counts(self, counts: dict) -> dict:
+        """A dict of integer counts summed over the ranks of ``torch.distributed`` (one all-reduce; every rank holds the same keys),
+        in sorted key order."""
+        import torch.distributed as dist
+        t = self.env.torch
+        keys = sorted(counts)
+        x = t.tensor([counts[k] for k in keys], dtype=t.int64, device=self.env.device)
+        dist.all_reduce(x, op=dist.ReduceOp.SUM)
+        return {k: int(y) for k, y in zip(keys, x.cpu().tolist())}
 
     def _by_policy(self, per_policy: dict, per_cell: dict, count_keys, finish) -> dict:
         """The report's ``by_policy``: name -> that policy's columns, its ``by_scenario`` rows (the checkpoint x scenario matrix) where
@@ -229,11 +227,9 @@ class FleetReporter:
             if s >= 0:
                 out[name].setdefault("by_scenario", {})[str(s)] = cell
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            t = self.env.torch
-            x = t.tensor([[per_policy.get(name, {}).get(k, 0) for k in count_keys] for name in names], dtype=t.int64, device=self.env.device)
-            dist.all_reduce(x, op=dist.ReduceOp.SUM)
-            for name, row in zip(names, x.cpu().tolist()):
-                out.setdefault(name, {})["fleet"] = finish({k: int(y) for k, y in zip(count_keys, row)})
+            fleet = self._allreduce_counts({(name, k): per_policy.get(name, {}).get(k, 0) for name in names for k in count_keys})
+            for name in names:
+                out.setdefault(name, {})["fleet"] = finish({k: fleet[(name, k)] for k in count_keys})
         return out
 
     def episodes(self) -> dict:
@@ -248,12 +244,7 @@ class FleetReporter:
         if getattr(self.env, "scenario_table", None) is not None:
             out["by_scenario"] = {str(k): v for k, v in led.by_scenario(fell).items()}
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            t = self.env.torch
-            c = led.counts()
-            keys = sorted(c)
-            v = t.tensor([c[k] for k in keys], dtype=t.int64, device=self.env.device)
-            dist.all_reduce(v, op=dist.ReduceOp.SUM)
-            fleet = {k: int(x) for k, x in zip(keys, v.cpu().tolist())}
+            fleet = self._allreduce_counts(led.counts())
             fleet["length_mean"] = fleet["length_sum"] / fleet["episodes"] if fleet["episodes"] else None
             out["fleet"] = fleet
         if self.policy_table is not None:

@@ -170,23 +170,11 @@ class ScenarioTable:
         ``self.curves[s]`` becomes the list of items ``(t0, t1, every, signal id, index, float32 lo, float32 hi, bins, name)``.  With
         ``names`` ``None`` only int indices resolve and no range is checked (the engine checks them).  Raises ``ValueError`` naming
         the scenario and the item."""
-        out = []
-        for s, rows in enumerate(self.curve_rows):
-            items = []
-            for r, (t0, t1, every, signal, index, lo, hi, bins, name) in enumerate(rows):
-                who = f"ScenarioTable: scenario {s}, curve item {r}"
-                if isinstance(index, str):
-                    if names is None:
-                        raise ValueError(f"{who}: index '{index}' needs the model's names to be resolved (check_names)")
-                    index = _check_index(who, signal, index, names)
-                if names is not None:
-                    width = _signal_width(signal, names)
-                    if not 0 <= index < width:
-                        raise ValueError(f"{who}: index {index} out of range: '{signal}' has {width} entries")
-                items.append((t0, t1, every, CHECK_SIGNALS[signal], int(index), np.float32(lo), np.float32(hi), bins,
-                              name if name is not None else f"{signal}[{index}] @{t0}:{t1}:{every}"))
-            out.append(items)
-        self.curves = out
+        def item(row, index):
+            t0, t1, every, signal, _, lo, hi, bins, name = row
+            return (t0, t1, every, CHECK_SIGNALS[signal], index, np.float32(lo), np.float32(hi), bins,
+                    name if name is not None else f"{signal}[{index}] @{t0}:{t1}:{every}")
+        self.curves = _resolve_items(self.curve_rows, "curve", 3, item, names)
         return self
 
     def _resolved_curves(self):
@@ -201,12 +189,7 @@ class ScenarioTable:
     def pack_curves(self):
         """``(adr int32[S + 1], t int32[n, 3] (t0, t1, every), signal int32[n], index int32[n], lo float32[n], hi float32[n], bins
         int32[n])``: the items in the CSR form of ``cosim_scenario_curves_set``."""
-        C = self._resolved_curves()
-        adr = np.cumsum([0] + [len(c) for c in C]).astype(np.int32)
-        flat = [it for c in C for it in c]
-        col = lambda k, dt: np.array([it[k] for it in flat], dtype=dt)   # noqa: E731
-        return (adr, np.array([it[:3] for it in flat], dtype=np.int32).reshape(-1, 3), col(3, np.int32), col(4, np.int32), col(5, np.float32),
-                col(6, np.float32), col(7, np.int32))
+        return _pack_items(self._resolved_curves(), 3, (np.int32, np.int32, np.float32, np.float32, np.int32))
 
     def curve_item_names(self) -> list:
         """Per scenario, the names of its curve items (the given name, or one made from the item's fields)."""
@@ -220,24 +203,11 @@ class ScenarioTable:
         """Resolve the checks against ``names`` (``check_names(compiled_model, info_dim, command_dim)``): ``self.checks[s]`` becomes the
         list of items ``(t0, t1, signal id, index, mode id, op id, float32 bound, name)``.  With ``names`` ``None`` only int indices
         resolve and no range is checked (the engine checks them).  Raises ``ValueError`` naming the scenario and the item."""
-        out = []
-        for s, rows in enumerate(self.check_rows):
-            items = []
-            for r, (t0, t1, signal, index, mode, op, bound, name) in enumerate(rows):
-                who = f"ScenarioTable: scenario {s}, check item {r}"
-                if isinstance(index, str):
-                    if names is None:
-                        raise ValueError(f"{who}: index '{index}' needs the model's names to be resolved (check_names)")
-                    index = _check_index(who, signal, index, names)
-                if names is not None:
-                    width = {"info": names["info_dim"], "abs_info": names["info_dim"], "tracking_error": min(names["command_dim"], 3),
-                             "torque_max": 1, "up": 1 if names["nq"] >= 7 else 0, "qpos": names["nq"], "qvel": names["nv"], "abs_qvel": names["nv"]}[signal]
-                    if not 0 <= index < width:
-                        raise ValueError(f"{who}: index {index} out of range: '{signal}' has {width} entries")
-                items.append((t0, t1, CHECK_SIGNALS[signal], int(index), CHECK_MODES[mode], CHECK_OPS[op], np.float32(bound),
-                              name if name is not None else f"{signal}[{index}] {mode} {op} {float(np.float32(bound))!r} @{t0}:{t1}"))
-            out.append(items)
-        self.checks = out
+        def item(row, index):
+            t0, t1, signal, _, mode, op, bound, name = row
+            return (t0, t1, CHECK_SIGNALS[signal], index, CHECK_MODES[mode], CHECK_OPS[op], np.float32(bound),
+                    name if name is not None else f"{signal}[{index}] {mode} {op} {float(np.float32(bound))!r} @{t0}:{t1}")
+        self.checks = _resolve_items(self.check_rows, "check", 2, item, names)
         return self
 
     def _resolved_checks(self):
@@ -252,12 +222,7 @@ class ScenarioTable:
     def pack_checks(self):
         """``(adr int32[S + 1], t int32[n, 2], signal int32[n], index int32[n], mode int32[n], cmp int32[n], bound float32[n])``: the items
         in the CSR form of ``cosim_scenario_checks_set``."""
-        C = self._resolved_checks()
-        adr = np.cumsum([0] + [len(c) for c in C]).astype(np.int32)
-        flat = [it for c in C for it in c]
-        col = lambda k, dt: np.array([it[k] for it in flat], dtype=dt)   # noqa: E731
-        return (adr, np.array([(it[0], it[1]) for it in flat], dtype=np.int32).reshape(-1, 2), col(2, np.int32), col(3, np.int32), col(4, np.int32),
-                col(5, np.int32), col(6, np.float32))
+        return _pack_items(self._resolved_checks(), 2, (np.int32, np.int32, np.int32, np.int32, np.float32))
 
     def check_item_names(self) -> list:
         """Per scenario, the names of its items (the given name, or one made from the item's fields)."""
@@ -349,23 +314,14 @@ class ScenarioTable:
     def pack(self):
         """``(key_adr int32[S + 1], key_t int32[nk], key_cmd float32[nk, command_dim], push_adr int32[S + 1], push_t int32[np, 2],
         push_v float32[np, 3])``."""
-        key_adr = np.cumsum([0] + [len(k) for k in self.keys]).astype(np.int32)
-        push_adr = np.cumsum([0] + [len(p) for p in self.pushes]).astype(np.int32)
-        key_t = np.array([t for keys in self.keys for t, _ in keys], dtype=np.int32)
-        key_cmd = np.array([c for keys in self.keys for _, c in keys], dtype=np.float32).reshape(len(key_t), self.command_dim)
-        push_t = np.array([(t0, t1) for pushes in self.pushes for t0, t1, _ in pushes], dtype=np.int32).reshape(-1, 2)
-        push_v = np.array([v for pushes in self.pushes for _, _, v in pushes], dtype=np.float32).reshape(-1, 3)
-        return key_adr, key_t, key_cmd, push_adr, push_t, push_v
+        key_adr, key_t, key_cmd = _pack_items(self.keys, 1, (np.float32,))
+        push_adr, push_t, push_v = _pack_items(self.pushes, 2, (np.float32,))
+        return key_adr, key_t.reshape(-1), key_cmd.reshape(len(key_t), self.command_dim), push_adr, push_t, push_v.reshape(-1, 3)
 
     def pack_params(self):
         """``(adr int32[S + 1], t int32[n, 2], field int32[n], index int32[n], op int32[n], value float32[n])``: the expanded items
         in the CSR form of ``cosim_scenario_params_set``."""
-        P = self._resolved()
-        adr = np.cumsum([0] + [len(p) for p in P]).astype(np.int32)
-        flat = [it for p in P for it in p]
-        col = lambda k, dt: np.array([it[k] for it in flat], dtype=dt)
-        return (adr, np.array([(it[0], it[1]) for it in flat], dtype=np.int32).reshape(-1, 2), col(2, np.int32), col(3, np.int32), col(4, np.int32),
-                col(5, np.float32))
+        return _pack_items(self._resolved(), 2, (np.int32, np.int32, np.int32, np.float32))
 
     def params_from_csr(self, adr, t, field, index, op, value, names: dict = None) -> "ScenarioTable":
         """A table with this one's commands and pushes and the windows that the CSR arrays of ``pack_params`` hold (one window per
@@ -453,6 +409,38 @@ def _signal_width(signal: str, names: dict) -> int:
     """How many entries a signal's ``index`` may name on the model behind ``names``."""
     return {"info": names["info_dim"], "abs_info": names["info_dim"], "tracking_error": min(names["command_dim"], 3), "torque_max": 1,
             "up": 1 if names["nq"] >= 7 else 0, "qpos": names["nq"], "qvel": names["nv"], "abs_qvel": names["nv"]}[signal]
+
+
+def _resolve_items(rows_per_scenario, kind: str, at: int, item, names) -> list:
+    """The resolver under ``resolve_checks`` / ``resolve_curves``: per scenario the list ``item(row, index)`` of its rows, ``index``
+    being the row's ``index`` (entry ``at + 1``; ``at``: its ``signal``) as an int -- a name looked up in ``names``, and with
+    ``names`` held against the signal's width."""
+    out = []
+    for s, rows in enumerate(rows_per_scenario):
+        items = []
+        for r, row in enumerate(rows):
+            who = f"ScenarioTable: scenario {s}, {kind} item {r}"
+            signal, index = row[at], row[at + 1]
+            if isinstance(index, str):
+                if names is None:
+                    raise ValueError(f"{who}: index '{index}' needs the model's names to be resolved (check_names)")
+                index = _check_index(who, signal, index, names)
+            if names is not None:
+                width = _signal_width(signal, names)
+                if not 0 <= index < width:
+                    raise ValueError(f"{who}: index {index} out of range: '{signal}' has {width} entries")
+            items.append(item(row, int(index)))
+        out.append(items)
+    return out
+
+
+def _pack_items(per_scenario, n_t: int, dtypes) -> tuple:
+    """The packer under the ``pack*`` methods: ``(adr int32[S + 1], t int32[n, n_t], one array [n] per entry of dtypes)`` from
+    per-scenario lists of items that begin with ``n_t`` times, followed by the columns."""
+    adr = np.cumsum([0] + [len(c) for c in per_scenario]).astype(np.int32)
+    flat = [it for c in per_scenario for it in c]
+    t = np.array([it[:n_t] for it in flat], dtype=np.int32).reshape(-1, n_t)
+    return (adr, t, *(np.array([it[n_t + k] for it in flat], dtype=dt) for k, dt in enumerate(dtypes)))
 
 
 def _curve_rows(s: int, rows) -> list:
