@@ -661,6 +661,11 @@ class BatchedEnv:
         ``rollout()`` raises while a table is set.  Raises ``ValueError`` naming the scenario and the row for a malformed table.
         Joins the range streams and blocks until the device is idle.
 
+        Observation faults ride with the table (a scenario's ``"faults"``, ``cosim_set_param "obs_faults"``): behind every control step
+        and reset one small kernel changes what the policy SEES of the envs whose scenario holds an item at the observation's own
+        clock -- the newest frame of ``state`` and of the record's observation stack, so the next step's roll carries the faulted
+        frame on -- and nothing else; ``obs_faults()`` returns the expanded items.  They act from the next ``step()`` / ``reset()`` on.
+
         ``check_slots`` (1..64) arms the table's checks (``cosim_scenario_checks_set``): behind every control step the engine samples
         every item of the env's scenario whose window holds at the step's pre-step episode clock -- the clock this step's keyframes
         and pushes were keyed on -- and closes the items into one verdict record when the episode ends, on the device, with no host
@@ -693,6 +698,8 @@ class BatchedEnv:
             table.resolve(self.param_names())
         elif table.has_params:
             self._check_param_items(table)
+        if table.has_faults:                                        # observation names, "*" and ranges against this env's observation config
+            table.resolve_faults(self.fault_names())
         check_slots = int(check_slots or 0)
         if check_slots and table.has_checks:                        # names and ranges against this env's model
             table.resolve_checks(self.check_names())
@@ -715,6 +722,11 @@ class BatchedEnv:
             self.engine.scenario_params_set(table.pack_params())
         elif self.engine.query("scenario_param_items") > 0:
             self.engine.scenario_params_set(None)
+        # so do the observation faults
+        if table.has_faults:
+            self.engine.scenario_faults_set(table.pack_faults())
+        elif self.engine.query("obs_faults") > 0:
+            self.engine.scenario_faults_set(None)
         # so do the checks, once they are armed
         self.check_slots = 0
         if check_slots and table.has_checks:
@@ -832,6 +844,21 @@ class BatchedEnv:
         W = self.engine.query("scenario_check_words")
         return Verdicts.from_raw(*self._read_records(self.engine.scenario_checks_get, (self.check_slots, W), (), (W,), include_open),
                                  self.scenario_table, self.env_id0)
+
+    def fault_names(self) -> dict:
+        """What an observation fault's ``obs`` / ``index`` are resolved against on this env (``scenario.fault_names``)."""
+        from .scenario import fault_names
+        return fault_names(self.stacked_obs_order, self.non_stacked_obs_order, self.obs_to_dim, self.stack_size)
+
+    def obs_faults(self) -> list:
+        """The expanded observation-fault items of the scenario table that is set, per scenario: ``(t0, t1, frame element, op id,
+        ordinal of the listed item, float32 value)`` (``ScenarioTable.faults``); an empty list per scenario without any, ``[]`` with
+        no table.  ``cosim_query "obs_faults"`` counts them."""
+        if self.scenario_table is None:
+            return []
+        items = [list(f) for f in self.scenario_table.faults]
+        assert sum(len(f) for f in items) == self.engine.query("obs_faults")
+        return items
 
     def param_names(self) -> dict:
         """The names a parameter window's ``index`` may use on this env, per field (``scenario.param_names``)."""

@@ -451,6 +451,8 @@ def main(argv=None) -> int:
                              if "by_policy" in out.get("episodes", {}) else {}),
                           **({"param_windows": sum(len(w) for w in env.scenario_table.param_windows)}   # as listed in the table
                              if env.scenario_table is not None and env.scenario_table.has_params else {}),
+                          **({"obs_faults": env.scenario_table.n_fault_items}                           # expanded items, as the engine counts them
+                             if env.scenario_table is not None and env.scenario_table.has_faults else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()

@@ -19,6 +19,7 @@
 #include "cosim_ftrace.hip"
 #include "cosim_scenario.hip"
 #include "cosim_scnparams.hip"
+#include "cosim_obsfault.hip"
 #include "cosim_checks.hip"
 #include "cosim_curves.hip"
 #include "cosim_plan.h"
@@ -145,6 +146,9 @@ struct cosim_engine {
   // parameter windows of the scenario table (cosim_scenario_params_set, cosim_scnparams.hip): scnparams_step_kernel behind every scenario launch
   char* d_scnpar = nullptr;       // one allocation: adr | t | word | op | value
   ScnParTable scnpar = {};        // device pointers into d_scnpar; n_items 0: no windows, no launches, the step kernels read d_params
+  // observation faults of the scenario table (cosim_set_param "obs_faults", cosim_obsfault.hip): obsfault_step_kernel behind every step's / reset's last launch
+  char* d_obsflt = nullptr;       // one allocation: adr | item
+  ObsFaultTable obsflt = {};      // device pointers into d_obsflt; n_items 0: no faults, no launches
   float* d_params_eff = nullptr;  // [n_envs][p_stride] effective records: what base_args hands the step kernels while windows are set
   // checks of the scenario table (cosim_scenario_checks_set, cosim_checks.hip): checks_step_kernel behind every range's last launch of a
   // step, behind the ledger's
@@ -701,6 +705,25 @@ static int scnparams_launch(cosim_engine* e, int first, int count, const uint8_t
   return launch_small<SCNPAR_WAVES, 64 * SCNPAR_WAVES>(scnparams_step_kernel, a, count, s);
 }
 
+// the faults go with their table (the caller has waited for the device)
+static void obsfault_free(cosim_engine* e) {
+  (void)hipFree(e->d_obsflt);
+  e->d_obsflt = nullptr; memset(&e->obsflt, 0, sizeof e->obsflt);
+}
+
+// behind the last launch of a step (reset: of the reset, for the envs under its mask) that writes the state record or state_out of
+// envs [first, first + count), same stream: what the policy sees of those envs
+static int obsfault_launch(cosim_engine* e, int first, int count, float* state_out, const uint8_t* mask, hipStream_t s) {
+  ObsFaultArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->scn; a.flt = e->obsflt; a.state = e->d_state; a.state_out = state_out; a.mask = mask;
+  a.n_envs = e->n_envs; a.first = first; a.count = count;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_stack = e->lay.s_stack;
+  a.sd = e->ho.stacked_dim; a.S = e->ho.stack_size; a.frame_dim = e->ho.frame_dim; a.state_dim = e->ho.state_dim;
+  a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
+  return launch_small<OBF_WAVES, 64 * OBF_WAVES>(obsfault_step_kernel, a, count, s);
+}
+
 // ---- checks of the scenario table (cosim_checks.hip)
 static const char* const CHECKS_INFO_MSG =
     ": scenario checks are set (cosim_scenario_checks_set) and info_out_dev is NULL: the checks sample the step's info row; pass an "
@@ -793,6 +816,7 @@ static void curves_free(cosim_engine* e) {
 
 static void scenario_free(cosim_engine* e) {
   scnparams_free(e);
+  obsfault_free(e);
   checks_free(e);
   curves_free(e);
   (void)hipFree(e->d_scn);
@@ -1476,6 +1500,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "ftrace_mask") return e->ft_mask;      // ledger flags that freeze a window
   if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
   if (n == "scenario_param_items") return e->scnpar.n_items;   // expanded parameter-window items of the table (0: none, no launches)
+  if (n == "obs_faults") return e->obsflt.n_items;   // expanded observation-fault items of the table (0: none, no launches)
   if (n == "scenario_check_items") return e->chk.n_scn > 0 ? e->chk.I : 0;   // I: items per env a verdict record holds (0: no checks, no launches)
   if (n == "scenario_check_slots") return e->chk_slots;                      // verdict records per env
   if (n == "scenario_curve_items") return e->cur.n_items;   // curve items of the table (0: no curves, no launches)
@@ -1488,6 +1513,8 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
 }
+
+static int obsfault_set(cosim_engine* e, const int32_t* words, int count);   // (below, with the other tables of the scenario family)
 
 int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int count) {
   if (!e || !name || !host) return fail(COSIM_EINVAL, "cosim_set_param: null argument");
@@ -1503,6 +1530,7 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
   else if (n == "kp") { off = L.p_kp; width = m.nu; }
   else if (n == "kd") { off = L.p_kd; width = m.nu; }
   else if (n == "meaninertia") { off = L.p_mean; width = 1; }
+  else if (n == "obs_faults") return obsfault_set(e, reinterpret_cast<const int32_t*>(host), count);   // a table of 32-bit words, not floats (include/cosim.h)
   else if (n == "solver_tolerance") { e->tol32 = host[0]; return COSIM_OK; }
   else if (n == "ls_tolerance_scale") { e->ls_scale = host[0]; return COSIM_OK; }
   else if (n == "max_newton") { e->max_newton = (int)host[0]; return COSIM_OK; }
@@ -1609,6 +1637,7 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   a.mode = MODE_RESET; a.mask = mask_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
   e->plan.reset.launch(e, a, e->n_envs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
+  if (e->obsflt.n_items > 0) RC_TRY(obsfault_launch(e, 0, e->n_envs, state_out_dev, mask_dev, (hipStream_t)stream));   // the reset's observation is a fill at clock 0
   if (mask_dev == nullptr) e->stepped = false;
   return observers_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
 }
@@ -1820,10 +1849,17 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     }
   } else p.step.launch(e, a, count, s);
   HIP_TRY(hipGetLastError());
-  if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
+  const bool faults = e->obsflt.n_items > 0;   // observation faults: the timing pair closes behind their launch
+  if (slot >= 0 && !faults) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
   if (a.ovf && !p.split) {   // envs the fleet kernel flagged (more contacts than it has slots for) are redone by the large-capacity kernel
     p.fixup.launch(e, a, count, s);
     HIP_TRY(hipGetLastError());
+  }
+  // observation faults: behind the last launch that writes the range's state records or state_out (the redo included: a redone env's
+  // observation is faulted once), ahead of the observers and the history pack, which then hold what the policy saw
+  if (faults) {
+    RC_TRY(obsfault_launch(e, first, count, state_out_dev, nullptr, s));
+    if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
   }
   return observers_step(e, first, count, 1, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
 }
@@ -2207,7 +2243,7 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
     return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
   }
   if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
-  if (n_scn != e->scn.n_scn) { scnparams_free(e); checks_free(e); curves_free(e); }   // parameter windows, checks and curves are rows of the table they were set for: another S drops them
+  if (n_scn != e->scn.n_scn) { scnparams_free(e); obsfault_free(e); checks_free(e); curves_free(e); }   // parameter windows, faults, checks and curves are rows of the table they were set for: another S drops them
   pk.patch(e->d_scn);
   tab.mode = mode;
   tab.gid_off = (unsigned)(((e->env_id0 % n_scn) + n_scn) % n_scn);
@@ -2252,6 +2288,47 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   // every env's effective record once, at its current clock: no row is ever unwritten
   RC_TRY(scnparams_launch(e, 0, e->n_envs, nullptr, 0, 0));
   HIP_TRY(hipDeviceSynchronize());
+  return COSIM_OK;
+}
+
+// Observation faults of the scenario table that is set (cosim_set_param "obs_faults"): `words` is S | adr[S + 1] | t[n][2] | elem[n] |
+// op[n] | ord[n] | value[n] (float bits), n = adr[S]; S = 0 clears.  Items of the counts of the ones that are set are rewritten in
+// place: the device pointers stay, captured graphs pick the new values up.  Nothing is launched: the faults act from the next step
+// or reset on.
+static int obsfault_set(cosim_engine* e, const int32_t* words, int count) {
+  const std::string fn = OBF_SETTER;
+  if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the faults)");
+  const int n_scn = words[0];
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_scn == 0) return table_clear(e, 0, obsfault_free);
+  RC_TRY(table_rows_match(e, fn, "observation faults", n_scn));
+  if (count < n_scn + 2) return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words do not hold the row addresses of " + std::to_string(n_scn) + " scenarios");
+  const int32_t* adr = words + 1;
+  const long long n = adr[n_scn];   // (validate_faults holds every row inside [0, adr[S]] before it reads an item by these addresses)
+  if (n < 0 || (long long)count != n_scn + 2 + 6 * n)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios and " + std::to_string(n) + " items takes " +
+                                  std::to_string(n_scn + 2 + 6 * (n < 0 ? 0 : n)));
+  const int32_t *t = adr + n_scn + 1, *elem = t + 2 * n, *op = elem + n, *ord = op + n;
+  const float* value = reinterpret_cast<const float*>(ord + n);
+  const ObsDims dims = {e->ho.frame_dim, e->ho.stacked_dim, e->ho.stack_size, e->ho.el_field, CS_OBS_COMMAND};
+  const FltRaw raw = {n_scn, adr, t, elem, op, ord, value};
+  const FltShape v = validate_faults(dims, raw);
+  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  RC_TRY(table_quiesce(e, 0));
+  ObsFaultTable tab = {};
+  WordPacker pk;
+  pack_faults(pk, tab, raw, v);
+  const bool in_place = e->obsflt.n_items == v.n && e->obsflt.n_scn == n_scn;
+  char* d_new = e->d_obsflt;
+  if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
+  const hipError_t r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) {   // a new allocation is dropped and the old items stay; an in-place rewrite may be half written: no faults then
+    if (in_place) obsfault_free(e); else (void)hipFree(d_new);
+    return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
+  }
+  if (!in_place) { (void)hipFree(e->d_obsflt); e->d_obsflt = d_new; }
+  pk.patch(e->d_obsflt);
+  e->obsflt = tab;
   return COSIM_OK;
 }
 

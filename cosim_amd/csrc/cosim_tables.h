@@ -1,5 +1,5 @@
 // cosim_tables.h — what the host does with a table of the scenario family before it reaches the device (cosim_scenario_set,
-// cosim_scenario_params_set, cosim_scenario_checks_set, cosim_scenario_curves_set, include/cosim.h): the rules every such table is
+// cosim_scenario_params_set, cosim_set_param "obs_faults", cosim_scenario_checks_set, cosim_scenario_curves_set, include/cosim.h): the rules every such table is
 // held to, one validator per setter, and the packer that lays a table's arrays into one allocation.  Plain C++ with no HIP in it:
 // cosim_engine.hip and a host program (tests/tables_host.cpp) both compile it.
 //
@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "cosim_curves.h"
+#include "cosim_obsfault.h"
 #include "cosim_scnparams.h"
 
 namespace cosim {
@@ -214,6 +215,59 @@ inline void pack_params(WordPacker& pk, ScnParTable& tab, const ParRaw& r, const
   const size_t n = (size_t)v.n;
   pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.t, r.t, 2 * n); pk.add(&tab.word, v.word.data(), n); pk.add(&tab.op, r.op, n);
   pk.add(&tab.value, r.value, n);
+  tab.n_scn = r.n_scn; tab.n_items = v.n;
+}
+
+// ---- cosim_set_param "obs_faults".  Image: adr | item ([n + OBF_CHUNK - 1][4]: t0, t1, e | op << 16 | ord << 24, value: cosim_obsfault.h)
+// what a fault item is held against of the observation frame
+struct ObsDims {
+  int frame_dim, stacked_dim, stack_size;
+  const unsigned char* el_field;   // [frame_dim] CS_OBS_* of every frame element
+  int command_field;               // CS_OBS_COMMAND
+};
+struct FltRaw {
+  int n_scn;   // that of the scenario table that is set
+  const int32_t *adr, *t, *elem, *op, *ord; const float* value;
+};
+struct FltShape { std::string err; int n = 0; std::vector<int32_t> item; };
+
+inline FltShape validate_faults(const ObsDims& d, const FltRaw& r) {
+  const std::string fn = OBF_SETTER;
+  FltShape v;
+  const RowAdr rows[1] = {{"adr", r.adr, "fault items", OBF_MAX_ITEMS, r.t && r.elem && r.op && r.ord && r.value}};
+  TAB_TRY(row_heads(fn, rows));
+  // all rows first: the item arrays hold adr[S] items (the setter sized them so), and 0 = adr[0] <= ... <= adr[S] keeps every row inside
+  for (int s = 0; s < r.n_scn; s++) TAB_TRY(row_rule(fn + ": scenario " + std::to_string(s), rows, s));
+  for (int s = 0; s < r.n_scn; s++) {
+    const std::string who = fn + ": scenario " + std::to_string(s);
+    for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
+      const std::string row = who + ", fault item " + std::to_string(i - r.adr[s]);
+      const int e = r.elem[i], op = r.op[i];
+      TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
+      if (e < 0 || e >= d.frame_dim) TAB_TRY(row + ": element " + std::to_string(e) + " out of range: the frame has " + std::to_string(d.frame_dim) + " elements");
+      if (d.el_field[e] == d.command_field)
+        TAB_TRY(row + ": element " + std::to_string(e) + " is a command word and is refused: the command words are the scenario's keyframes");
+      if (op < OBF_SCALE || op > OBF_DROP) TAB_TRY(row + ": unknown op " + std::to_string(op) + " (0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop)");
+      if (!std::isfinite(r.value[i])) TAB_TRY(row + ": value is not finite");
+      if (op == OBF_NOISE && r.value[i] < 0.f) TAB_TRY(row + ": a noise amplitude must be >= 0");
+      if (op == OBF_DROP && !(r.value[i] >= 0.f && r.value[i] <= 1.f)) TAB_TRY(row + ": a drop probability must lie in [0, 1]");
+      if ((op == OBF_HOLD || op == OBF_DROP) && (e >= d.stacked_dim || d.stack_size < 2))
+        TAB_TRY(row + ": hold / drop needs a stacked element and stack_size >= 2: there is no previous frame in the record");
+      if (r.ord[i] < 0 || r.ord[i] >= OBF_MAX_ITEMS) TAB_TRY(row + ": ordinal " + std::to_string(r.ord[i]) + " outside 0..255");
+      int32_t vb;
+      memcpy(&vb, &r.value[i], 4);
+      v.item.push_back(r.t[2 * i]); v.item.push_back(r.t[2 * i + 1]);
+      v.item.push_back((int32_t)((unsigned)e | (unsigned)op << 16 | (unsigned)r.ord[i] << 24)); v.item.push_back(vb);
+    }
+  }
+  v.n = r.adr[r.n_scn];
+  if (v.n == 0) TAB_TRY(fn + ": the table holds no fault item (n_scn = 0 clears the faults)");
+  v.item.resize(v.item.size() + 4 * (OBF_CHUNK - 1), 0);   // records that never hold: the kernel fetches OBF_CHUNK at a time
+  return v;
+}
+
+inline void pack_faults(WordPacker& pk, ObsFaultTable& tab, const FltRaw& r, const FltShape& v) {
+  pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.item, v.item.data(), v.item.size());
   tab.n_scn = r.n_scn; tab.n_items = v.n;
 }
 

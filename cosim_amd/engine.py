@@ -402,6 +402,25 @@ class Engine:
         ``ScenarioTable.pack_params`` (``None``: clear the windows)."""
         self._csr_set("scenario_params_set", csr, (np.int32, np.int32, np.int32, np.float32), 2)
 
+    def scenario_faults_set(self, csr):
+        """Observation faults, through ``cosim_set_param "obs_faults"`` (they have no entry point of their own): ``csr`` = the six host
+        arrays ``(adr, t, elem, op, ord, value)`` of ``ScenarioTable.pack_faults`` (``None``: clear the faults), sent as one table of
+        32-bit words ``S | adr | t | elem | op | ord | value`` (include/cosim.h)."""
+        if csr is None:
+            words = np.zeros(1, dtype=np.int32)
+        else:
+            adr, t, *cols = _columns(csr, (np.int32, np.int32, np.int32, np.int32, np.int32, np.float32))
+            if adr.ndim != 1 or adr.size < 1:
+                raise ValueError("scenario_faults_set: adr must be [S + 1]")
+            n = int(max(adr[-1], 0))
+            if t.size != 2 * n or any(c.size != n for c in cols):  # (the engine reads the arrays by the last address)
+                raise ValueError(f"scenario_faults_set: the item arrays are shorter than their row addresses ({n} items)"
+                                 if t.size < 2 * n or min(c.size for c in cols) < n else
+                                 f"scenario_faults_set: the item arrays are longer than their row addresses ({n} items)")
+            words = np.concatenate([np.array([adr.size - 1], dtype=np.int32), adr, t.reshape(-1), *[c.view(np.int32).reshape(-1) for c in cols]])
+        words = np.ascontiguousarray(words, dtype=np.int32)
+        self._check(self.L.cosim_set_param(self.h, b"obs_faults", words.ctypes.data, int(words.size)))
+
     def scenario_checks_set(self, csr, slots: int = 0):
         """``cosim_scenario_checks_set``: ``csr`` = the seven host arrays ``(adr, t, signal, index, mode, cmp, bound)`` of
         ``ScenarioTable.pack_checks`` (``None``: clear the checks); ``slots`` verdict records per env."""

@@ -12,7 +12,9 @@ Device twin: ``philox()`` / ``u01()`` in ``csrc/cosim_kernels.hip``.
 Purposes: 0 action-delay draw, 1 sensor noise (index = frame element), 2 init-qpos noise
 (index = i-th noisy joint), 3 mass noise (host only, index = body id), 4 gain noise (host only),
 5 spawn-table row of an episode (index 0; per-episode mode of ``cosim_spawn_set``), 6 spawn pose draws
-(host only: ``spawn.uniform_poses``, env id = table row, index 0 / 1 / 2 = x / y / yaw).
+(host only: ``spawn.uniform_poses``, env id = table row, index 0 / 1 / 2 = x / y / yaw), 7 observation faults of a scenario table
+(``csrc/cosim_obsfault.h``; step = meta word 1 as the step that produced the observation left it; ``noise``: index = frame element
+``e`` (< 256), mapped by ``fault_noise_u``; ``drop``: index = ``0x10000 + ord``, the listed item's ordinal, mapped by ``fault_drop_u``).
 """
 from __future__ import annotations
 
@@ -24,6 +26,8 @@ MASK32 = np.uint64(0xFFFFFFFF)
 
 PURPOSE_DELAY, PURPOSE_SENSOR, PURPOSE_INIT, PURPOSE_MASS, PURPOSE_GAIN = 0, 1, 2, 3, 4
 PURPOSE_SPAWN, PURPOSE_SPAWN_POSE = 5, 6
+PURPOSE_OBS_FAULT = 7
+FAULT_DROP_INDEX = 0x10000
 
 
 def philox4x32(k0, k1, c0, c1, c2, c3):
@@ -66,3 +70,23 @@ def uniform(seed: int, env_ids, step, purpose: int, index):
     c1 = np.uint32(purpose) | (np.asarray(index, dtype=np.uint32) << np.uint32(8))
     c0, _, _, _ = philox4x32(k0, k1, np.asarray(step, dtype=np.uint32), c1, g0, g1)
     return u01(c0)
+
+
+def first_word(seed: int, env_ids, step, purpose: int, index):
+    """First output word of the stream, uint32; shape = broadcast(env_ids, step, index)."""
+    k0, k1 = seed_key(seed)
+    g0, g1 = env_words(env_ids)
+    c1 = np.uint32(purpose) | (np.asarray(index, dtype=np.uint32) << np.uint32(8))
+    return philox4x32(k0, k1, np.asarray(step, dtype=np.uint32), c1, g0, g1)[0]
+
+
+def fault_noise_u(x):
+    """uint32 -> float32 in [-1, 1): ``(x >> 8) * 2^-23 - 1``, exact (the device ``obsfault_noise_u``)."""
+    x = np.asarray(x, dtype=np.uint32)
+    return ((x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 8388608.0) - np.float32(1.0)).astype(np.float32)
+
+
+def fault_drop_u(x):
+    """uint32 -> float32 in [0, 1): ``(x >> 8) * 2^-24``, exact (the device ``obsfault_drop_u``)."""
+    x = np.asarray(x, dtype=np.uint32)
+    return ((x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)

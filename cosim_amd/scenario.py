@@ -33,6 +33,20 @@ t1`` and ``(t - t0) % every == 0``, into time bin ``(t - t0) // every`` of ``cei
 its samples go into per-(scenario, item, outcome) cells on the device: count, fixed-point sum, min, max and a histogram of ``bins``
 (0..64; 0: none) equal bins over ``[lo, hi)`` plus an underflow and an overflow row.  ``cosim_amd/curves.py`` has the container and the
 numpy twin.
+
+Observation faults (``cosim_set_param "obs_faults"``, csrc/cosim_obsfault.hip): a scenario may hold ``"faults": [[t0, t1, obs, index, op,
+value], ...]`` (an optional seventh entry names the item; or a dict with those keys and ``"name"``): a timed change of what the POLICY
+SEES.  ``obs`` is a name of the env's ``stacked_obs_order`` / ``non_stacked_obs_order`` (``dof_pos``, ``dof_vel``, ``ang_vel``,
+``lin_vel``, ``projected_gravity``, ``last_action``, ``height_map``; ``command`` is refused: the command words are the scenario's
+keyframes), ``index`` an int in ``[0, dim)`` or ``"*"``, ``value`` in the units the policy sees (after the observation's ``scale``).
+The window is keyed on the observation's OWN clock ``t_obs``: 0 for a reset's observation, k after the k-th step of the episode -- the
+``t`` the commands and pushes of the NEXT step are keyed on, so a push over ``[150, 155)`` and a fault over ``[150, 200)`` start on the
+same policy decision.  Ops, applied to the newest frame's value ``x`` in listed order, composing (float32): ``"scale"`` ``x * value``,
+``"bias"`` ``x + value``, ``"set"`` ``value``, ``"noise"`` ``x + value * u`` with ``u`` uniform in ``[-1, 1)`` (``value >= 0``),
+``"hold"`` the element's value in the previous frame (what the policy saw one step earlier, faults included: a frozen sensor),
+``"drop"`` with probability ``value`` in ``[0, 1]`` per step and listed item as ``"hold"`` (all elements of the item together: a lost
+packet).  ``"hold"`` / ``"drop"`` need a stacked observation and ``stack_size >= 2``; at ``t_obs = 0`` they change nothing.  At most 256
+items per scenario after expansion.  ``reference_obs_faults`` is the numpy twin of the kernel's rule, exact.
 """
 from __future__ import annotations
 
@@ -56,6 +70,10 @@ MAX_CURVE_ITEMS, MAX_CURVE_T, MAX_CURVE_BINS = 8, 1024, 64
 _CURVE_KEYS = ("t0", "t1", "every", "signal", "index", "lo", "hi", "bins")
 # consistent only as a set that compile.env_constants computes in fp64 on the host
 REFUSED_PARAM_FIELDS = ("body_mass", "body_invweight0", "dof_invweight0", "meaninertia")
+FAULT_OPS = {"scale": 0, "bias": 1, "set": 2, "noise": 3, "hold": 4, "drop": 5}
+MAX_FAULT_ITEMS = 256
+_FAULT_KEYS = ("t0", "t1", "obs", "index", "op", "value")
+_FAULT_OP_NAMES = {v: k for k, v in FAULT_OPS.items()}
 _FIELD_NAMES = {v: k for k, v in PARAM_FIELDS.items()}
 _OP_NAMES = {v: k for k, v in PARAM_OPS.items()}
 
@@ -68,6 +86,26 @@ def param_names(cm) -> dict:
     acts = [a["name"] for a in cm.spec["actuators"]]
     jid = np.asarray(get_field(cm.blob, "dof_jntid"))[:cm.blob.nv]
     return {"kp": acts, "kd": acts, "geom_friction": list(cm.geom_names), "dof_frictionloss": [cm.joint_names[int(j)] for j in jid]}
+
+
+def fault_names(stacked_obs_order, non_stacked_obs_order, obs_to_dim: dict, stack_size: int) -> dict:
+    """What a fault's ``obs`` / ``index`` are resolved against: ``{"stacked": [(name, dim), ...], "non_stacked": [(name, dim), ...],
+    "stack_size"}`` in the order of the observation frame (frame element ``e`` counts through the stacked names, then the others)."""
+    return {"stacked": [(n, int(obs_to_dim[n])) for n in stacked_obs_order],
+            "non_stacked": [(n, int(obs_to_dim[n])) for n in non_stacked_obs_order], "stack_size": int(stack_size)}
+
+
+def fault_layout(names: dict) -> dict:
+    """The frame layout ``reference_obs_faults`` takes, from ``fault_names``: ``stacked_dim``, ``frame_dim``, ``stack_size``,
+    ``state_dim`` and ``command`` (the frame elements of the command field)."""
+    sd = sum(d for _, d in names["stacked"])
+    fd = sd + sum(d for _, d in names["non_stacked"])
+    cmd, e = [], 0
+    for n, d in list(names["stacked"]) + list(names["non_stacked"]):
+        cmd += list(range(e, e + d)) if n == "command" else []
+        e += d
+    S = int(names["stack_size"])
+    return {"stacked_dim": sd, "frame_dim": fd, "stack_size": S, "state_dim": S * sd + fd - sd, "command": cmd}
 
 
 def info_columns(nu: int, info_dim: int) -> dict:
@@ -116,9 +154,10 @@ class ScenarioTable:
         self.keys, self.pushes, self.param_windows, self.params = [], [], [], None
         self.check_rows, self.checks = [], None
         self.curve_rows, self.curves = [], None
+        self.fault_rows, self.faults = [], None
         for s, sc in enumerate(scenarios):
             sc = sc or {}
-            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "name"}:
+            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "faults", "name"}:
                 raise ValueError(f"ScenarioTable: scenario {s}: a mapping with the keys 'commands' and 'pushes' is expected, got {sc!r}")
             keys, pushes = [], []
             for r, row in enumerate(sc.get("commands") or []):
@@ -153,6 +192,7 @@ class ScenarioTable:
             self.param_windows.append(_param_windows(s, sc.get("params") or []))
             self.check_rows.append(_check_rows(s, sc.get("checks") or []))
             self.curve_rows.append(_curve_rows(s, sc.get("curves") or []))
+            self.fault_rows.append(_fault_rows(s, sc.get("faults") or []))
         if names is not None or not self.has_params:
             self.resolve(names or {})
         cn = (names or {}).get("checks")
@@ -160,6 +200,94 @@ class ScenarioTable:
             self.resolve_checks(cn)
         if cn is not None or not any(isinstance(r[4], str) for rows in self.curve_rows for r in rows):
             self.resolve_curves(cn)
+        fn = (names or {}).get("faults")
+        if fn is not None or not self.has_faults:
+            self.resolve_faults(fn or {"stacked": [], "non_stacked": [], "stack_size": 1})
+
+    @property
+    def has_faults(self) -> bool:
+        return any(self.fault_rows)
+
+    def resolve_faults(self, names: dict) -> "ScenarioTable":
+        """Expand the faults against ``names`` (``fault_names(...)``, ``BatchedEnv.fault_names()``): ``self.faults[s]`` becomes the list
+        of items ``(t0, t1, frame element e, op id, ord, float32 value)`` in listed order, ``"*"`` expanded in index order; ``ord`` is
+        the ordinal of the listed item (its elements share one ``drop`` draw).  Raises ``ValueError`` naming the scenario and the item:
+        unknown name, index out of range, ``hold`` / ``drop`` without a previous frame, more than 256 items."""
+        first, e = {}, 0
+        for stacked, lst in ((True, names["stacked"]), (False, names["non_stacked"])):
+            for n, d in lst:
+                first.setdefault(n, (e, int(d), stacked))
+                e += int(d)
+        out = []
+        for s, rows in enumerate(self.fault_rows):
+            items = []
+            for r, (t0, t1, obs, index, op, value, _) in enumerate(rows):
+                who = f"ScenarioTable: scenario {s}, fault item {r}"
+                if obs not in first:
+                    raise ValueError(f"{who}: unknown observation '{obs}' (the env observes {', '.join(first) or 'nothing'})")
+                e0, dim, stacked = first[obs]
+                if op in ("hold", "drop") and (not stacked or int(names["stack_size"]) < 2):
+                    raise ValueError(f"{who}: op '{op}' on '{obs}' needs a stacked observation and stack_size >= 2: there is no previous "
+                                     "frame in the record")
+                if index == "*":
+                    idx = list(range(dim))
+                else:
+                    if not 0 <= index < dim:
+                        raise ValueError(f"{who}: index {index} out of range: '{obs}' has {dim} entries")
+                    idx = [index]
+                items += [(t0, t1, e0 + i, FAULT_OPS[op], r, np.float32(value)) for i in idx]
+            if len(items) > MAX_FAULT_ITEMS:
+                raise ValueError(f"ScenarioTable: scenario {s}: {len(items)} fault items after expansion, at most {MAX_FAULT_ITEMS}")
+            out.append(items)
+        self.faults = out
+        return self
+
+    def _resolved_faults(self):
+        if self.faults is None:
+            raise ValueError("ScenarioTable: the faults are not resolved yet: pass names={'faults': fault_names(...)} or call resolve_faults")
+        return self.faults
+
+    @property
+    def n_fault_items(self) -> int:
+        return sum(len(f) for f in self._resolved_faults())
+
+    def pack_faults(self):
+        """``(adr int32[S + 1], t int32[n, 2], elem int32[n], op int32[n], ord int32[n], value float32[n])``: the expanded items in
+        the CSR form ``Engine.scenario_faults_set`` sends through ``cosim_set_param "obs_faults"``."""
+        return _pack_items(self._resolved_faults(), 2, (np.int32, np.int32, np.int32, np.float32))
+
+    def faults_from_csr(self, adr, t, elem, op, ord, value, names: dict) -> "ScenarioTable":
+        """A table with everything of this one but the faults, which are those the CSR arrays of ``pack_faults`` hold: the items of
+        one ``ord`` become one listed item again (``"*"`` if they cover the observation, else one item per element), resolved
+        against ``names`` (``fault_names``)."""
+        t = np.asarray(t).reshape(-1, 2)
+        scn = self.to_list()
+        if len(adr) != len(scn) + 1:
+            raise ValueError(f"ScenarioTable: faults for {len(adr) - 1} scenarios, the table has {len(scn)}")
+        spans, e = [], 0
+        for n, d in list(names["stacked"]) + list(names["non_stacked"]):
+            spans.append((n, e, int(d)))
+            e += int(d)
+        for s, sc in enumerate(scn):
+            sc.pop("faults", None)
+            rows, i, i1 = [], int(adr[s]), int(adr[s + 1])
+            while i < i1:
+                j = i
+                while j < i1 and int(ord[j]) == int(ord[i]):
+                    j += 1
+                e0 = int(elem[i])
+                span = [sp for sp in spans if sp[1] <= e0 < sp[1] + sp[2]]
+                if not span:
+                    raise ValueError(f"ScenarioTable: scenario {s}, fault item {i - int(adr[s])}: element {e0} outside the frame")
+                n, first, d = span[0]
+                whole = j - i == d and [int(x) for x in elem[i:j]] == list(range(first, first + d)) and d > 1
+                head = [int(t[i, 0]), int(t[i, 1]), n]
+                tail = [_FAULT_OP_NAMES.get(int(op[i]), int(op[i])), float(np.float32(value[i]))]
+                rows += [head + ["*"] + tail] if whole else [head + [int(elem[k]) - first] + tail for k in range(i, j)]
+                i = j
+            if rows:
+                sc["faults"] = rows
+        return type(self)(scn, self.command_dim).resolve_faults(names)
 
     @property
     def has_curves(self) -> bool:
@@ -309,6 +437,10 @@ class ScenarioTable:
             if rows:
                 sc["curves"] = [[t0, t1, every, signal, index, float(lo), float(hi), bins] + ([name] if name is not None else [])
                                 for t0, t1, every, signal, index, lo, hi, bins, name in rows]
+        for sc, rows in zip(out, self.fault_rows):
+            if rows:
+                sc["faults"] = [[t0, t1, obs, index, op, float(value)] + ([name] if name is not None else [])
+                                for t0, t1, obs, index, op, value, name in rows]
         return out
 
     def pack(self):
@@ -378,6 +510,53 @@ def _param_windows(s: int, rows) -> list:
         if isinstance(index, (bool, float)) or not isinstance(index, (int, np.integer, str)):
             raise ValueError(f"{who}: index must be an int, a name or '*', got {index!r}")
         out.append((int(t0f), int(t1f), field, index if isinstance(index, str) else int(index), op, value))
+    return out
+
+
+def _fault_rows(s: int, rows) -> list:
+    """The ``"faults"`` rows of scenario ``s``, checked for everything that needs no observation config: ``(t0, t1, obs, index, op,
+    value, name or None)``.  The messages are those of ``_param_windows``."""
+    out = []
+    if not isinstance(rows, (list, tuple)):
+        raise ValueError(f"ScenarioTable: scenario {s}: 'faults' must be a list of items, got {rows!r}")
+    for r, row in enumerate(rows):
+        who = f"ScenarioTable: scenario {s}, fault item {r}"
+        name = None
+        if isinstance(row, dict):
+            if set(row) - set(_FAULT_KEYS) - {"name"} or any(k not in row for k in _FAULT_KEYS if k not in ("index", "value")):
+                raise ValueError(f"{who}: a mapping with the keys {', '.join(_FAULT_KEYS)} (and 'name') is expected, got {row!r}")
+            name = row.get("name")
+            row = [row.get(k, {"index": "*"}.get(k, 0.0)) for k in _FAULT_KEYS]
+        elif isinstance(row, (list, tuple)) and len(row) == 7:
+            row, name = list(row[:6]), row[6]
+        if not isinstance(row, (list, tuple)) or len(row) != 6:
+            raise ValueError(f"{who}: expected [t0, t1, obs, index, op, value] and an optional name, got {row!r}")
+        t0, t1, obs, index, op, value = row
+        try:
+            t0f, t1f, value = float(t0), float(t1), float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: times and value must be numbers, got {row!r}") from None
+        if not math.isfinite(value) or abs(value) > float(np.finfo(np.float32).max):   # (finite as float32 too)
+            raise ValueError(f"{who}: non-finite value")
+        if not (math.isfinite(t0f) and math.isfinite(t1f)) or t0f != int(t0f) or t1f != int(t1f) or not 0 <= t0f < MAX_TIME or not 0 <= t1f <= MAX_TIME:
+            raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
+        if t1f <= t0f:
+            raise ValueError(f"{who}: t1 {int(t1f)} is not after t0 {int(t0f)}")
+        if obs == "command":
+            raise ValueError(f"{who}: observation 'command' is refused: the command words are the scenario's keyframes ('commands')")
+        if not isinstance(obs, str):
+            raise ValueError(f"{who}: obs must be the name of an observation, got {obs!r}")
+        if op not in FAULT_OPS:
+            raise ValueError(f"{who}: unknown op {op!r} (one of {', '.join(FAULT_OPS)})")
+        if op == "noise" and value < 0:
+            raise ValueError(f"{who}: a noise amplitude must be >= 0, got {value!r}")
+        if op == "drop" and not 0.0 <= value <= 1.0:
+            raise ValueError(f"{who}: a drop probability must lie in [0, 1], got {value!r}")
+        if isinstance(index, (bool, float)) or not (isinstance(index, (int, np.integer)) or index == "*"):
+            raise ValueError(f"{who}: index must be an int or '*', got {index!r}")
+        if name is not None and not isinstance(name, str):
+            raise ValueError(f"{who}: the name must be a string, got {name!r}")
+        out.append((int(t0f), int(t1f), obs, index if isinstance(index, str) else int(index), op, value, name))
     return out
 
 
@@ -538,7 +717,7 @@ def _check_rows(s: int, rows) -> list:
 
 
 def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = (),
-          params: Iterable = (), checks: Iterable = (), curves: Iterable = ()) -> Iterator[dict]:
+          params: Iterable = (), checks: Iterable = (), curves: Iterable = (), faults: Iterable = ()) -> Iterator[dict]:
     """The cartesian product command rows x push speeds x directions x push times as scenarios, commands outermost: each holds its
     command from episode step 0 and one push of ``speed`` m/s along the world direction ``angle`` (radians about z, 0 = +x) held over
     ``(t0, t1)``.  With no speeds or no times the product is over the commands alone (no push).
@@ -546,7 +725,17 @@ def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable =
     ``"params"`` value, possibly empty) is one more cartesian axis, innermost: every scenario above is emitted once per window list,
     ``len(...) * len(P)`` scenarios in all.  ``checks``: a list of check lists (each a scenario's ``"checks"`` value, possibly empty)
     is one more axis, inside the parameters: ``len(...) * len(K)`` scenarios.  ``curves``: a list of curve lists (each a scenario's
-    ``"curves"`` value, possibly empty) is one more axis, innermost of all."""
+    ``"curves"`` value, possibly empty) is one more axis, inside the checks.  ``faults``: a list of fault lists (each a scenario's
+    ``"faults"`` value, possibly empty) is one more axis, inside the curves and innermost of all: ``len(...) * len(F)`` scenarios."""
+    faults = [list(f) for f in faults]
+    if faults:
+        for sc in sweep(commands, push_speeds, directions, push_times, params, checks, curves):
+            for fl in faults:
+                out = dict(sc)
+                if fl:
+                    out["faults"] = [dict(f) if isinstance(f, dict) else list(f) for f in fl]
+                yield out
+        return
     curves = [list(c) for c in curves]
     if curves:
         for sc in sweep(commands, push_speeds, directions, push_times, params, checks):
@@ -632,6 +821,74 @@ def reference_params(table: ScenarioTable, mode, gid, t, ep, base_params, layout
                 w = layout[_FIELD_NAMES[field]] + index
                 eff[i, w] = np.float32(value) if op == PARAM_OPS["set"] else base[i, w] * np.float32(value)
     return eff
+
+
+def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count, seed: int, frames, layout: dict, active=None) -> np.ndarray:
+    """Numpy twin of ``obsfault_step_kernel`` over a run of K observations of N envs, exact.  ``gid`` ``[N]`` global ids; per
+    observation k the POST-step meta words ``t_obs[k]`` (word 0), ``ep[k]`` (word 11) and ``step_count[k]`` (word 1), each ``[K, N]``;
+    ``frames`` ``[K, N, frame_dim]`` float32, the CLEAN newest frame of every observation (the first ``stacked_dim`` words and the
+    non-stacked tail of a fault-free run's ``state_out`` row); ``layout`` (``fault_layout``).  ``active`` ``[K, N]`` bool (default: all):
+    observations an env did not take part in (a masked reset's other envs) leave its stack alone and repeat its row.  The twin
+    emulates the roll and the fill -- an env's first observation must be a fill (``t_obs = 0``) -- and returns the faulted
+    ``state_out`` rows ``[K, N, state_dim]``, stack rows included."""
+    from . import rng
+    gid = np.asarray(gid, dtype=np.int64).reshape(-1)
+    N, sd, fd, S = len(gid), int(layout["stacked_dim"]), int(layout["frame_dim"]), int(layout["stack_size"])
+    frames = np.ascontiguousarray(frames, dtype=np.float32).reshape(-1, N, fd)
+    K = frames.shape[0]
+    t_obs, ep, step_count = (np.asarray(a).reshape(K, N) for a in (t_obs, ep, step_count))
+    active = np.ones((K, N), dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(K, N)
+    cmd = np.zeros(sd, dtype=bool)
+    cmd[[e for e in layout.get("command", []) if e < sd]] = True
+    items = table._resolved_faults()
+    stack = np.full((N, S, sd), np.nan, dtype=np.float32)
+    out = np.full((K, N, S * sd + fd - sd), np.nan, dtype=np.float32)
+    u32 = np.uint32
+    for k in range(K):
+        act, fill = active[k], active[k] & (t_obs[k] == 0)
+        roll = act & ~fill
+        if S > 1:
+            stack[roll, 1:] = stack[roll, :-1]
+        stack[roll, 0] = frames[k, roll, :sd]
+        stack[fill] = frames[k, fill, None, :sd]
+        tail = frames[k, :, sd:].copy()
+        row = scenario_rows(len(table), mode, gid, ep[k])
+        for r in np.unique(row[act]):
+            for t0, t1, e, op, ordinal, value in items[r]:
+                m = act & (row == r) & (t0 <= t_obs[k]) & (t_obs[k] < t1)
+                if not m.any():
+                    continue
+                x = stack[m, 0, e] if e < sd else tail[m, e - sd]
+                name = _FAULT_OP_NAMES[op]
+                if name == "drop":
+                    lost = rng.fault_drop_u(rng.first_word(seed, gid[m].astype(np.uint64), step_count[k, m].astype(u32),
+                                                           rng.PURPOSE_OBS_FAULT, rng.FAULT_DROP_INDEX + ordinal)) < np.float32(value)
+                else:
+                    lost = np.ones(int(m.sum()), dtype=bool)
+                if name == "scale":
+                    x = x * np.float32(value)
+                elif name == "bias":
+                    x = x + np.float32(value)
+                elif name == "set":
+                    x = np.full_like(x, np.float32(value))
+                elif name == "noise":
+                    u = rng.fault_noise_u(rng.first_word(seed, gid[m].astype(np.uint64), step_count[k, m].astype(u32), rng.PURPOSE_OBS_FAULT, e))
+                    x = x + (np.float32(value) * u).astype(np.float32)
+                else:                                               # hold / drop: the previous frame, but for a fill
+                    take = lost & (t_obs[k, m] > 0)
+                    x = np.where(take, stack[m, 1, e], x)
+                x = x.astype(np.float32)
+                if e >= sd:
+                    tail[m, e - sd] = x
+                else:
+                    stack[m, 0, e] = x
+                    f = m & fill
+                    stack[f, :, e] = stack[f, 0, e][:, None]        # a fill left the first frame in every row
+        rows_out = stack.copy()
+        rows_out[:, :, cmd] = frames[k, :, None, :sd][:, :, cmd]    # every stack row of state_out holds the applied command
+        new = np.concatenate([rows_out.reshape(N, S * sd), tail], axis=1)
+        out[k] = np.where(act[:, None], new, out[k - 1] if k > 0 else new)
+    return out
 
 
 def push_reference(quat, v) -> np.ndarray:

@@ -392,6 +392,37 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
  * windows set: the base records), to host memory of `capacity` floats; joins the ranges first.  Returns param_stride. */
 int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
 
+/* Observation faults of the scenario table that is set: timed sensor bias, noise, freeze and loss per env, applied on the device to
+ * what the policy SEES (cosim_amd/csrc/cosim_obsfault.h has the rule).  They have no entry point of their own: the table travels
+ * through cosim_set_param(e, "obs_faults", words, count), where `words` points at `count` 32-BIT WORDS, not floats:
+ *   S | adr[S + 1] | t[n][2] | elem[n] | op[n] | ord[n] | value[n] (float bits),   n = adr[S],   count = S + 2 + 6 n
+ * (int32 but for value); the one word 0 clears the faults.  Scenario s owns the items [adr[s], adr[s + 1]) (at most 256).
+ * Item i names ONE frame element elem[i] (0 <= e < frame_dim, the index space of the observation frame: e < stacked_dim is stacked; an
+ * element of the command field is refused, the command words are the scenario's keyframes), an op[i], a value[i] in the units the
+ * policy sees (after the observation's scale) and ord[i] (0..255), the ordinal of the listed item it was expanded from.  It holds while
+ * t[2i] <= t_obs < t[2i + 1] of the observation's OWN clock: meta word 0 as the step that produced the observation left it, 0 for a
+ * reset's observation (the auto-reset inside a terminal step included), k after the k-th step of the episode -- the value the scenario
+ * kernel reads as t ahead of the next step.  The row is that of cosim_scenario_set on the post-step meta words.
+ * For every element under at least one holding item, starting from the value x the step kernel wrote for the newest frame, the holding
+ * items that name it apply in listed order, composing (fp32, no contraction):
+ *   0 scale x * value | 1 bias x + value | 2 set value | 3 noise x + value * u, u uniform in [-1, 1) (value >= 0)
+ *   4 hold: the element of the previous frame (stack row 1), faults included: a sensor frozen at its last value
+ *   5 drop: with probability value in [0, 1] per step and listed item as hold; all elements of one ord are lost together
+ * Draws: Philox4x32-10 keyed (seed_lo, seed_hi), counter (meta word 1 post-step, 7 | index << 8, gid_lo, gid_hi); noise: index = e,
+ * drop: index = 0x10000 + ord.  hold and drop need a stacked element and stack_size >= 2; at t_obs = 0 they are the identity.
+ * The result goes to row 0 of the state record's observation stack and to the newest frame of state_out (at t_obs = 0, a fill, to every
+ * row of both), so the next step's roll carries the faulted frame on; nothing else of the record is written and nothing is kept per
+ * env: a restored run continues bit for bit once the same items are set again.  One small kernel (cosim_obsfault.hip) runs behind the
+ * last launch of every control step that writes the record or state_out, on each stream group's own stream inside the step's timing
+ * pair, ahead of the ledger, the checks, the curves, the traces and the history pack, and behind a reset's launch for the envs under
+ * its mask: it works under a deferred join and inside a captured graph (set or clear the faults before capturing; items of the counts
+ * of the ones that are set are rewritten in place and a captured graph picks the new values up).  The call joins the ranges and
+ * blocks until the device is idle; it launches nothing.  S = 0 clears the faults (no launch, pointer or byte then differs from an
+ * engine that never had any); otherwise S must be the "scenario_rows" of the table that is set.  cosim_scenario_set with another S,
+ * or clearing the table, drops them.  Validated on the host before anything is changed, the message names the scenario and the item
+ * (COSIM_EINVAL).  cosim_rollout stays refused (a scenario table is set); cosim_profile_step and cosim_debug_forward ignore the faults.
+ * cosim_query "obs_faults" answers the number of items (0: none). */
+
 /* Checks of the scenario table that is set: per-scenario pass / fail criteria judged on the device (cosim_amd/csrc/cosim_checks.h has
  * the rule).  Scenario s owns the items [adr[s], adr[s + 1]) (at most 64).  Item i takes one sample per control step whose PRE-STEP
  * episode clock t (meta word 0 as the scenario kernel read it ahead of that step) holds t[2i] <= t < t[2i + 1]:
