@@ -666,6 +666,13 @@ class BatchedEnv:
         clock -- the newest frame of ``state`` and of the record's observation stack, so the next step's roll carries the faulted
         frame on -- and nothing else; ``obs_faults()`` returns the expanded items.  They act from the next ``step()`` / ``reset()`` on.
 
+        Action faults ride with the table too (a scenario's ``"action_faults"``, ``cosim_set_param "action_faults"``): ahead of every
+        control step one small kernel writes the EFFECTIVE action of every env -- the caller's action with the items applied that hold
+        at the env's pre-step episode clock -- and the step kernels are handed that buffer instead of ``actions``; ``last_action`` in
+        the observation stays the policy's own output.  ``action_faults()`` returns the expanded items, ``effective_action()`` what the
+        last step's kernels were handed.  They act from the next ``step()`` on.  Limits: set before capturing a graph; not part of a
+        ``snapshot()`` (nothing is kept per env: the same table set again continues bit for bit).
+
         ``check_slots`` (1..64) arms the table's checks (``cosim_scenario_checks_set``): behind every control step the engine samples
         every item of the env's scenario whose window holds at the step's pre-step episode clock -- the clock this step's keyframes
         and pushes were keyed on -- and closes the items into one verdict record when the episode ends, on the device, with no host
@@ -700,6 +707,8 @@ class BatchedEnv:
             self._check_param_items(table)
         if table.has_faults:                                        # observation names, "*" and ranges against this env's observation config
             table.resolve_faults(self.fault_names())
+        if table.has_action_faults:                                 # actuator names, "*" and ranges against this env's model
+            table.resolve_action_faults(self.actuator_names())
         check_slots = int(check_slots or 0)
         if check_slots and table.has_checks:                        # names and ranges against this env's model
             table.resolve_checks(self.check_names())
@@ -727,6 +736,11 @@ class BatchedEnv:
             self.engine.scenario_faults_set(table.pack_faults())
         elif self.engine.query("obs_faults") > 0:
             self.engine.scenario_faults_set(None)
+        # and the action faults
+        if table.has_action_faults:
+            self.engine.scenario_action_faults_set(table.pack_action_faults())
+        elif self.engine.query("action_faults") > 0:
+            self.engine.scenario_action_faults_set(None)
         # so do the checks, once they are armed
         self.check_slots = 0
         if check_slots and table.has_checks:
@@ -859,6 +873,29 @@ class BatchedEnv:
         items = [list(f) for f in self.scenario_table.faults]
         assert sum(len(f) for f in items) == self.engine.query("obs_faults")
         return items
+
+    def actuator_names(self) -> list:
+        """The model's actuator names in order: what an action fault's ``index`` is resolved against."""
+        return list(self.param_names()["kp"])
+
+    def action_faults(self) -> list:
+        """The expanded action-fault items of the scenario table that is set, per scenario: ``(t0, t1, actuator, op id, ordinal of the
+        listed item, float32 value)`` (``ScenarioTable.action_faults``); an empty list per scenario without any, ``[]`` with no table.
+        ``cosim_query "action_faults"`` counts them."""
+        if self.scenario_table is None:
+            return []
+        items = [list(f) for f in self.scenario_table.action_faults]
+        assert sum(len(f) for f in items) == self.engine.query("action_faults")
+        return items
+
+    def effective_action(self):
+        """What the last ``step()``'s kernels were handed as the action while action faults are set: a float32 tensor ``[N, nu]`` (a
+        copy; zeros before the first step), ``None`` when no action faults are set.  Joins the ranges."""
+        if self.engine.query("action_faults") == 0:
+            return None
+        out = self.torch.empty((self.num_envs, self.action_dim), dtype=self.torch.float32, device=self.device)
+        self.engine.get("action_effective", out.data_ptr(), self._stream())
+        return out
 
     def param_names(self) -> dict:
         """The names a parameter window's ``index`` may use on this env, per field (``scenario.param_names``)."""

@@ -37,7 +37,9 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     scenarios: [{commands: [[0, 0.5, 0, 0, 0], [100, 1.0, 0, 0, 0]], pushes: [[150, 155, 0.5, 0, 0]]}, {commands: [[0, 0.2, 0, 0, 0]]}]
     scenario_mode: cycle                                               # per-ENV schedules on the device, keyed by each env's own episode step
                                                                        # (cosim_amd/scenario.py; or a YAML file: --scenarios); unlike
-                                                                       # commands: / pushes: they run under --graph and --pipelined too
+                                                                       # commands: / pushes: they run under --graph and --pipelined too;
+                                                                       # a scenario may also hold params:, faults:, action_faults:
+                                                                       # ([[t0, t1, index, op, value], ...]: what the motors are told), ...
     fall:     {tilt: 0.8, height: 0.1, grace: 5, bodies: [base_link]}  # fall rule (cosim_amd/fall.py): end an episode on tilt (rad), base
                                                                        # height (m) or contact of the listed bodies; or engine: {fall: {...}};
                                                                        # same as --fall-*; runs under --graph and --pipelined too
@@ -453,6 +455,8 @@ def main(argv=None) -> int:
                              if env.scenario_table is not None and env.scenario_table.has_params else {}),
                           **({"obs_faults": env.scenario_table.n_fault_items}                           # expanded items, as the engine counts them
                              if env.scenario_table is not None and env.scenario_table.has_faults else {}),
+                          **({"action_faults": env.scenario_table.n_action_fault_items}                 # likewise
+                             if env.scenario_table is not None and env.scenario_table.has_action_faults else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()

@@ -20,6 +20,7 @@
 #include "cosim_scenario.hip"
 #include "cosim_scnparams.hip"
 #include "cosim_obsfault.hip"
+#include "cosim_actfault.hip"
 #include "cosim_checks.hip"
 #include "cosim_curves.hip"
 #include "cosim_plan.h"
@@ -149,6 +150,13 @@ struct cosim_engine {
   // observation faults of the scenario table (cosim_set_param "obs_faults", cosim_obsfault.hip): obsfault_step_kernel behind every step's / reset's last launch
   char* d_obsflt = nullptr;       // one allocation: adr | item
   ObsFaultTable obsflt = {};      // device pointers into d_obsflt; n_items 0: no faults, no launches
+  // action faults of the scenario table (cosim_set_param "action_faults", cosim_actfault.hip): actfault_step_kernel ahead of every control
+  // step's first launch, actfault_obs_kernel behind its last
+  char* d_actflt = nullptr;       // one allocation: adr | item
+  ActFaultTable actflt = {};      // device pointers into d_actflt; n_items 0: no faults, no launches, the step kernels read the caller's actions
+  float* d_actions_eff = nullptr; // [n_envs][nu] effective actions: what the step kernels are handed while faults are set
+  float* d_actions_raw = nullptr; // [n_envs][nu] the caller's actions of the last step (last_action is rebuilt from them)
+  bool act_in_obs = false;        // the observation has last_action elements
   float* d_params_eff = nullptr;  // [n_envs][p_stride] effective records: what base_args hands the step kernels while windows are set
   // checks of the scenario table (cosim_scenario_checks_set, cosim_checks.hip): checks_step_kernel behind every range's last launch of a
   // step, behind the ledger's
@@ -724,6 +732,35 @@ static int obsfault_launch(cosim_engine* e, int first, int count, float* state_o
   return launch_small<OBF_WAVES, 64 * OBF_WAVES>(obsfault_step_kernel, a, count, s);
 }
 
+// the action faults go with their table too (the caller has waited for the device)
+static void actfault_free(cosim_engine* e) {
+  (void)hipFree(e->d_actflt); (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw);
+  e->d_actflt = nullptr; e->d_actions_eff = nullptr; e->d_actions_raw = nullptr; memset(&e->actflt, 0, sizeof e->actflt);
+}
+
+// ahead of the first launch of a control step of envs [first, first + count), same stream, behind the scenario and parameter-window
+// kernels: the effective and the raw action rows of those envs
+static int actfault_launch(cosim_engine* e, int first, int count, const float* actions, hipStream_t s) {
+  ActFaultArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->scn; a.flt = e->actflt; a.state = e->d_state; a.actions = actions; a.eff = e->d_actions_eff; a.raw = e->d_actions_raw;
+  a.n_envs = e->n_envs; a.first = first; a.count = count;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_lastact = e->lay.s_lastact; a.nu = e->model.nu;
+  a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
+  return launch_small<ACF_WAVES, 64 * ACF_WAVES>(actfault_step_kernel, a, count, s);
+}
+
+// behind the last launch of the step that writes the state record or state_out of those envs, same stream: last_action as the policy
+// put it out
+static int actfault_obs_launch(cosim_engine* e, int first, int count, float* state_out, hipStream_t s) {
+  ActObsArgs a;
+  memset(&a, 0, sizeof a);
+  a.ob = e->d_obs; a.state = e->d_state; a.state_out = state_out; a.raw = e->d_actions_raw;
+  a.n_envs = e->n_envs; a.first = first; a.count = count;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_cache = e->lay.s_cache; a.s_stack = e->lay.s_stack; a.nu = e->model.nu;
+  return launch_small<ACF_WAVES, 64 * ACF_WAVES>(actfault_obs_kernel, a, count, s);
+}
+
 // ---- checks of the scenario table (cosim_checks.hip)
 static const char* const CHECKS_INFO_MSG =
     ": scenario checks are set (cosim_scenario_checks_set) and info_out_dev is NULL: the checks sample the step's info row; pass an "
@@ -817,6 +854,7 @@ static void curves_free(cosim_engine* e) {
 static void scenario_free(cosim_engine* e) {
   scnparams_free(e);
   obsfault_free(e);
+  actfault_free(e);
   checks_free(e);
   curves_free(e);
   (void)hipFree(e->d_scn);
@@ -1501,6 +1539,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
   if (n == "scenario_param_items") return e->scnpar.n_items;   // expanded parameter-window items of the table (0: none, no launches)
   if (n == "obs_faults") return e->obsflt.n_items;   // expanded observation-fault items of the table (0: none, no launches)
+  if (n == "action_faults") return e->actflt.n_items;   // expanded action-fault items of the table (0: none, no launches, the caller's action pointer)
   if (n == "scenario_check_items") return e->chk.n_scn > 0 ? e->chk.I : 0;   // I: items per env a verdict record holds (0: no checks, no launches)
   if (n == "scenario_check_slots") return e->chk_slots;                      // verdict records per env
   if (n == "scenario_curve_items") return e->cur.n_items;   // curve items of the table (0: no curves, no launches)
@@ -1515,6 +1554,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
 }
 
 static int obsfault_set(cosim_engine* e, const int32_t* words, int count);   // (below, with the other tables of the scenario family)
+static int actfault_set(cosim_engine* e, const int32_t* words, int count);
 
 int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int count) {
   if (!e || !name || !host) return fail(COSIM_EINVAL, "cosim_set_param: null argument");
@@ -1531,6 +1571,7 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
   else if (n == "kd") { off = L.p_kd; width = m.nu; }
   else if (n == "meaninertia") { off = L.p_mean; width = 1; }
   else if (n == "obs_faults") return obsfault_set(e, reinterpret_cast<const int32_t*>(host), count);   // a table of 32-bit words, not floats (include/cosim.h)
+  else if (n == "action_faults") return actfault_set(e, reinterpret_cast<const int32_t*>(host), count);   // likewise
   else if (n == "solver_tolerance") { e->tol32 = host[0]; return COSIM_OK; }
   else if (n == "ls_tolerance_scale") { e->ls_scale = host[0]; return COSIM_OK; }
   else if (n == "max_newton") { e->max_newton = (int)host[0]; return COSIM_OK; }
@@ -1834,6 +1875,13 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   // parameter windows: this step's effective parameter records of the range, ahead of every launch that reads them (the substep
   // launches of the split pipeline and the fix-up kernels' redo included: all are handed the same pointer by base_args)
   if (e->scnpar.n_items > 0) RC_TRY(scnparams_launch(e, first, count, nullptr, 0, s));
+  // action faults: this step's effective actions of the range, ahead of every launch that reads the action (the fused and step-only
+  // kernels, the two-envs-per-wave kernel, the split pipeline's first substep and the fix-up kernels' redo: all read a.actions)
+  const bool act_faults = e->actflt.n_items > 0;
+  if (act_faults) {
+    RC_TRY(actfault_launch(e, first, count, actions_dev, s));
+    a.actions = e->d_actions_eff;
+  }
   if (p.split) {
     // one pair of launches per substep: the prism walk (narrow_waves waves per env), then the solver with the contacts it left; with
     // "hfield_fixup", the substeps the solver gave up (more ground contacts than its slots) are redone right behind it from the same
@@ -1857,6 +1905,8 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   }
   // observation faults: behind the last launch that writes the range's state records or state_out (the redo included: a redone env's
   // observation is faulted once), ahead of the observers and the history pack, which then hold what the policy saw
+  // action faults: last_action is what the policy put out, not what the bus delivered; the observation faults compose on top
+  if (act_faults && e->act_in_obs) RC_TRY(actfault_obs_launch(e, first, count, state_out_dev, s));
   if (faults) {
     RC_TRY(obsfault_launch(e, first, count, state_out_dev, nullptr, s));
     if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
@@ -1986,6 +2036,14 @@ static int locate(cosim_engine* e, const std::string& n, int* off, int* width) {
 int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream) {
   if (!e || !name || !out_dev) return fail(COSIM_EINVAL, "cosim_get: null argument");
   HIP_TRY(hipSetDevice(e->device));
+  const bool act_eff = std::string(name) == "action_effective";
+  if (act_eff || std::string(name) == "action_raw") {   // [N][nu], contiguous: the last step's rows of the action faults' buffers
+    if (e->actflt.n_items == 0) return fail(COSIM_EINVAL, std::string("cosim_get: ") + name + ": no action faults are set (cosim_set_param \"action_faults\")");
+    RC_TRY(join_ranges(e, (hipStream_t)stream));
+    HIP_TRY(hipMemcpyAsync(out_dev, act_eff ? e->d_actions_eff : e->d_actions_raw, (size_t)e->n_envs * e->model.nu * sizeof(float),
+                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return COSIM_OK;
+  }
   int off, width;
   int rc = locate(e, name, &off, &width);
   if (rc) return rc;
@@ -2243,7 +2301,7 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
     return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
   }
   if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
-  if (n_scn != e->scn.n_scn) { scnparams_free(e); obsfault_free(e); checks_free(e); curves_free(e); }   // parameter windows, faults, checks and curves are rows of the table they were set for: another S drops them
+  if (n_scn != e->scn.n_scn) { scnparams_free(e); obsfault_free(e); actfault_free(e); checks_free(e); curves_free(e); }   // parameter windows, faults, checks and curves are rows of the table they were set for: another S drops them
   pk.patch(e->d_scn);
   tab.mode = mode;
   tab.gid_off = (unsigned)(((e->env_id0 % n_scn) + n_scn) % n_scn);
@@ -2329,6 +2387,60 @@ static int obsfault_set(cosim_engine* e, const int32_t* words, int count) {
   if (!in_place) { (void)hipFree(e->d_obsflt); e->d_obsflt = d_new; }
   pk.patch(e->d_obsflt);
   e->obsflt = tab;
+  return COSIM_OK;
+}
+
+// Action faults of the scenario table that is set (cosim_set_param "action_faults"): `words` is S | adr[S + 1] | t[n][2] | elem[n] |
+// op[n] | ord[n] | value[n] (float bits), elem an actuator, n = adr[S]; S = 0 clears.  Items of the counts of the ones that are set
+// are rewritten in place: the device pointers stay, captured graphs pick the new values up.  Nothing is launched: the faults act
+// from the next step on.
+static int actfault_set(cosim_engine* e, const int32_t* words, int count) {
+  const std::string fn = ACF_SETTER;
+  if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the faults)");
+  const int n_scn = words[0];
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_scn == 0) return table_clear(e, 0, actfault_free);
+  RC_TRY(table_rows_match(e, fn, "action faults", n_scn));
+  if (count < n_scn + 2) return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words do not hold the row addresses of " + std::to_string(n_scn) + " scenarios");
+  const int32_t* adr = words + 1;
+  const long long n = adr[n_scn];   // (validate_action_faults holds every row inside [0, adr[S]] before it reads an item by these addresses)
+  if (n < 0 || (long long)count != n_scn + 2 + 6 * n)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios and " + std::to_string(n) + " items takes " +
+                                  std::to_string(n_scn + 2 + 6 * (n < 0 ? 0 : n)));
+  const int32_t *t = adr + n_scn + 1, *elem = t + 2 * n, *op = elem + n, *ord = op + n;
+  const float* value = reinterpret_cast<const float*>(ord + n);
+  const FltRaw raw = {n_scn, adr, t, elem, op, ord, value};
+  const FltShape v = validate_action_faults(e->model.nu, raw);
+  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  RC_TRY(table_quiesce(e, 0));
+  ActFaultTable tab = {};
+  WordPacker pk;
+  pack_action_faults(pk, tab, raw, v);
+  const bool in_place = e->actflt.n_items == v.n && e->actflt.n_scn == n_scn;
+  char* d_new = e->d_actflt;
+  if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
+  if (!e->d_actions_eff) {   // both buffers or neither; zeroed, so that a read ahead of the first step finds no stale bytes
+    const size_t bytes = (size_t)e->n_envs * e->model.nu * sizeof(float);
+    hipError_t r = hipMalloc(&e->d_actions_eff, bytes);
+    if (r == hipSuccess) { r = hipMalloc(&e->d_actions_raw, bytes); if (r != hipSuccess) { (void)hipFree(e->d_actions_eff); } }
+    if (r == hipSuccess) { r = hipMemset(e->d_actions_eff, 0, bytes); if (r == hipSuccess) r = hipMemset(e->d_actions_raw, 0, bytes); if (r != hipSuccess) { (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw); } }
+    if (r != hipSuccess) {
+      e->d_actions_eff = nullptr; e->d_actions_raw = nullptr;
+      if (!in_place) (void)hipFree(d_new);
+      return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
+    }
+  }
+  const hipError_t r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) {   // a new allocation is dropped and the old items stay; an in-place rewrite may be half written: no faults then
+    if (in_place) actfault_free(e);
+    else { (void)hipFree(d_new); if (e->actflt.n_items == 0) actfault_free(e); }
+    return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
+  }
+  if (!in_place) { (void)hipFree(e->d_actflt); e->d_actflt = d_new; }
+  pk.patch(e->d_actflt);
+  e->actflt = tab;
+  e->act_in_obs = false;
+  for (int el = 0; el < e->ho.frame_dim; el++) e->act_in_obs = e->act_in_obs || e->ho.el_field[el] == CS_OBS_LAST_ACTION;
   return COSIM_OK;
 }
 

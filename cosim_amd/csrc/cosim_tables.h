@@ -1,5 +1,5 @@
 // cosim_tables.h — what the host does with a table of the scenario family before it reaches the device (cosim_scenario_set,
-// cosim_scenario_params_set, cosim_set_param "obs_faults", cosim_scenario_checks_set, cosim_scenario_curves_set, include/cosim.h): the rules every such table is
+// cosim_scenario_params_set, cosim_set_param "obs_faults" / "action_faults", cosim_scenario_checks_set, cosim_scenario_curves_set, include/cosim.h): the rules every such table is
 // held to, one validator per setter, and the packer that lays a table's arrays into one allocation.  Plain C++ with no HIP in it:
 // cosim_engine.hip and a host program (tests/tables_host.cpp) both compile it.
 //
@@ -14,6 +14,7 @@
 #include <string>
 #include <vector>
 
+#include "cosim_actfault.h"
 #include "cosim_curves.h"
 #include "cosim_obsfault.h"
 #include "cosim_scnparams.h"
@@ -267,6 +268,45 @@ inline FltShape validate_faults(const ObsDims& d, const FltRaw& r) {
 }
 
 inline void pack_faults(WordPacker& pk, ObsFaultTable& tab, const FltRaw& r, const FltShape& v) {
+  pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.item, v.item.data(), v.item.size());
+  tab.n_scn = r.n_scn; tab.n_items = v.n;
+}
+
+// ---- cosim_set_param "action_faults".  Image: adr | item ([n + ACF_CHUNK - 1][4]: t0, t1, j | op << 16 | ord << 24, value: cosim_actfault.h)
+// (the raw columns are those of the observation faults, `elem` an actuator index)
+inline FltShape validate_action_faults(int nu, const FltRaw& r) {
+  const std::string fn = ACF_SETTER;
+  FltShape v;
+  const RowAdr rows[1] = {{"adr", r.adr, "action-fault items", ACF_MAX_ITEMS, r.t && r.elem && r.op && r.ord && r.value}};
+  TAB_TRY(row_heads(fn, rows));
+  // all rows first: the item arrays hold adr[S] items (the setter sized them so), and 0 = adr[0] <= ... <= adr[S] keeps every row inside
+  for (int s = 0; s < r.n_scn; s++) TAB_TRY(row_rule(fn + ": scenario " + std::to_string(s), rows, s));
+  for (int s = 0; s < r.n_scn; s++) {
+    const std::string who = fn + ": scenario " + std::to_string(s);
+    for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
+      const std::string row = who + ", action-fault item " + std::to_string(i - r.adr[s]);
+      const int j = r.elem[i], op = r.op[i];
+      TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
+      if (j < 0 || j >= nu) TAB_TRY(row + ": actuator " + std::to_string(j) + " out of range: the model has " + std::to_string(nu) + " actuators");
+      if (op < ACF_SCALE || op > ACF_CLIP) TAB_TRY(row + ": unknown op " + std::to_string(op) + " (0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop, 6 clip)");
+      if (!std::isfinite(r.value[i])) TAB_TRY(row + ": value is not finite");
+      if (op == ACF_NOISE && r.value[i] < 0.f) TAB_TRY(row + ": a noise amplitude must be >= 0");
+      if (op == ACF_CLIP && r.value[i] < 0.f) TAB_TRY(row + ": a clip bound must be >= 0");
+      if (op == ACF_DROP && !(r.value[i] >= 0.f && r.value[i] <= 1.f)) TAB_TRY(row + ": a drop probability must lie in [0, 1]");
+      if (r.ord[i] < 0 || r.ord[i] >= ACF_MAX_ITEMS) TAB_TRY(row + ": ordinal " + std::to_string(r.ord[i]) + " outside 0..255");
+      int32_t vb;
+      memcpy(&vb, &r.value[i], 4);
+      v.item.push_back(r.t[2 * i]); v.item.push_back(r.t[2 * i + 1]);
+      v.item.push_back((int32_t)((unsigned)j | (unsigned)op << 16 | (unsigned)r.ord[i] << 24)); v.item.push_back(vb);
+    }
+  }
+  v.n = r.adr[r.n_scn];
+  if (v.n == 0) TAB_TRY(fn + ": the table holds no action-fault item (n_scn = 0 clears the faults)");
+  v.item.resize(v.item.size() + 4 * (ACF_CHUNK - 1), 0);   // records that never hold: the kernel fetches ACF_CHUNK at a time
+  return v;
+}
+
+inline void pack_action_faults(WordPacker& pk, ActFaultTable& tab, const FltRaw& r, const FltShape& v) {
   pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.item, v.item.data(), v.item.size());
   tab.n_scn = r.n_scn; tab.n_items = v.n;
 }

@@ -77,7 +77,7 @@ _ABI_ROWS = (
     ("cosim_create", _ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, ctypes.c_uint64, ctypes.c_int64, _pvp]),
     ("cosim_destroy", _ci, [_vp]),
     ("cosim_query", _ci, [_vp, _cs]),
-    ("cosim_set_param", _ci, [_vp, _cs, _vp, _ci]),
+    ("cosim_set_param", _ci, [_vp, _cs, _vp, _ci]),      # also the word tables "obs_faults" and "action_faults": no entry point of their own
     ("cosim_reset", _ci, [_vp] * 5),
     ("cosim_step", _ci, [_vp] * 8),
     ("cosim_step_range", _ci, [_vp, _ci, _ci] + [_vp] * 7),
@@ -402,24 +402,35 @@ class Engine:
         ``ScenarioTable.pack_params`` (``None``: clear the windows)."""
         self._csr_set("scenario_params_set", csr, (np.int32, np.int32, np.int32, np.float32), 2)
 
-    def scenario_faults_set(self, csr):
-        """Observation faults, through ``cosim_set_param "obs_faults"`` (they have no entry point of their own): ``csr`` = the six host
-        arrays ``(adr, t, elem, op, ord, value)`` of ``ScenarioTable.pack_faults`` (``None``: clear the faults), sent as one table of
-        32-bit words ``S | adr | t | elem | op | ord | value`` (include/cosim.h)."""
+    def _word_table_set(self, who: str, param: bytes, csr):
+        """The body of the two setters that have no entry point of their own: ``csr`` = the six host arrays ``(adr, t, elem, op, ord,
+        value)`` (``None``: clear), sent through ``cosim_set_param`` ``param`` as one table of 32-bit words ``S | adr | t | elem | op |
+        ord | value`` (include/cosim.h)."""
         if csr is None:
             words = np.zeros(1, dtype=np.int32)
         else:
             adr, t, *cols = _columns(csr, (np.int32, np.int32, np.int32, np.int32, np.int32, np.float32))
             if adr.ndim != 1 or adr.size < 1:
-                raise ValueError("scenario_faults_set: adr must be [S + 1]")
+                raise ValueError(f"{who}: adr must be [S + 1]")
             n = int(max(adr[-1], 0))
             if t.size != 2 * n or any(c.size != n for c in cols):  # (the engine reads the arrays by the last address)
-                raise ValueError(f"scenario_faults_set: the item arrays are shorter than their row addresses ({n} items)"
+                raise ValueError(f"{who}: the item arrays are shorter than their row addresses ({n} items)"
                                  if t.size < 2 * n or min(c.size for c in cols) < n else
-                                 f"scenario_faults_set: the item arrays are longer than their row addresses ({n} items)")
+                                 f"{who}: the item arrays are longer than their row addresses ({n} items)")
             words = np.concatenate([np.array([adr.size - 1], dtype=np.int32), adr, t.reshape(-1), *[c.view(np.int32).reshape(-1) for c in cols]])
         words = np.ascontiguousarray(words, dtype=np.int32)
-        self._check(self.L.cosim_set_param(self.h, b"obs_faults", words.ctypes.data, int(words.size)))
+        self._check(self.L.cosim_set_param(self.h, param, words.ctypes.data, int(words.size)))
+
+    def scenario_faults_set(self, csr):
+        """Observation faults, through ``cosim_set_param "obs_faults"`` (they have no entry point of their own): ``csr`` = the six host
+        arrays ``(adr, t, elem, op, ord, value)`` of ``ScenarioTable.pack_faults`` (``None``: clear the faults), sent as one table of
+        32-bit words ``S | adr | t | elem | op | ord | value`` (include/cosim.h)."""
+        self._word_table_set("scenario_faults_set", b"obs_faults", csr)
+
+    def scenario_action_faults_set(self, csr):
+        """Action faults, through ``cosim_set_param "action_faults"``: ``csr`` = the six host arrays ``(adr, t, actuator, op, ord,
+        value)`` of ``ScenarioTable.pack_action_faults`` (``None``: clear the faults), the word table of the observation faults."""
+        self._word_table_set("scenario_action_faults_set", b"action_faults", csr)
 
     def scenario_checks_set(self, csr, slots: int = 0):
         """``cosim_scenario_checks_set``: ``csr`` = the seven host arrays ``(adr, t, signal, index, mode, cmp, bound)`` of

@@ -14,7 +14,9 @@ Purposes: 0 action-delay draw, 1 sensor noise (index = frame element), 2 init-qp
 5 spawn-table row of an episode (index 0; per-episode mode of ``cosim_spawn_set``), 6 spawn pose draws
 (host only: ``spawn.uniform_poses``, env id = table row, index 0 / 1 / 2 = x / y / yaw), 7 observation faults of a scenario table
 (``csrc/cosim_obsfault.h``; step = meta word 1 as the step that produced the observation left it; ``noise``: index = frame element
-``e`` (< 256), mapped by ``fault_noise_u``; ``drop``: index = ``0x10000 + ord``, the listed item's ordinal, mapped by ``fault_drop_u``).
+``e`` (< 256), mapped by ``fault_noise_u``; ``drop``: index = ``0x10000 + ord``, the listed item's ordinal, mapped by ``fault_drop_u``),
+8 action faults of a scenario table (``csrc/cosim_actfault.h``; step = meta word 1 as the step FINDS it; ``noise``: index = actuator
+``j``; ``drop``: index = ``0x10000 + ord``; the same two maps).
 """
 from __future__ import annotations
 
@@ -27,6 +29,7 @@ MASK32 = np.uint64(0xFFFFFFFF)
 PURPOSE_DELAY, PURPOSE_SENSOR, PURPOSE_INIT, PURPOSE_MASS, PURPOSE_GAIN = 0, 1, 2, 3, 4
 PURPOSE_SPAWN, PURPOSE_SPAWN_POSE = 5, 6
 PURPOSE_OBS_FAULT = 7
+PURPOSE_ACTION_FAULT = 8
 FAULT_DROP_INDEX = 0x10000
 
 

@@ -47,6 +47,18 @@ same policy decision.  Ops, applied to the newest frame's value ``x`` in listed 
 ``"drop"`` with probability ``value`` in ``[0, 1]`` per step and listed item as ``"hold"`` (all elements of the item together: a lost
 packet).  ``"hold"`` / ``"drop"`` need a stacked observation and ``stack_size >= 2``; at ``t_obs = 0`` they change nothing.  At most 256
 items per scenario after expansion.  ``reference_obs_faults`` is the numpy twin of the kernel's rule, exact.
+
+Action faults (``cosim_set_param "action_faults"``, csrc/cosim_actfault.hip): a scenario may hold ``"action_faults": [[t0, t1, index, op,
+value], ...]`` (an optional sixth entry names the item; or a dict with those keys and ``"name"``): a timed change of what the MOTORS
+ARE TOLD, the channel from the policy to the drives.  ``index`` is an actuator index, an actuator name of the model or ``"*"``,
+``value`` in the units of the policy's output (the raw action, before ``a_scale``).  The window is keyed on the env's PRE-STEP episode
+clock ``t`` (the clock keyframes, pushes and parameter windows use).  Ops, applied to the caller's action word ``x`` in listed order,
+composing (float32): ``"scale"``, ``"bias"``, ``"set"``, ``"noise"`` as for an observation fault (Philox purpose 8), ``"hold"`` the action the
+step kernel was given one step earlier (the effective one: a held channel stays frozen through the window), ``"drop"`` with probability
+``value`` per step and listed item as ``"hold"`` (all actuators of the item together: a lost packet, the drive keeps its last set point),
+``"clip"`` ``x > value ? value : (x < -value ? -value : x)`` (a saturating output; NaN stays NaN).  At episode step 0 ``"hold"`` / ``"drop"``
+change nothing.  ``last_action`` in the observation stays the policy's own output.  At most 256 items per scenario after expansion.
+``reference_action_faults`` is the numpy twin of one step of the kernel's rule, exact.
 """
 from __future__ import annotations
 
@@ -74,6 +86,10 @@ FAULT_OPS = {"scale": 0, "bias": 1, "set": 2, "noise": 3, "hold": 4, "drop": 5}
 MAX_FAULT_ITEMS = 256
 _FAULT_KEYS = ("t0", "t1", "obs", "index", "op", "value")
 _FAULT_OP_NAMES = {v: k for k, v in FAULT_OPS.items()}
+ACTION_FAULT_OPS = {"scale": 0, "bias": 1, "set": 2, "noise": 3, "hold": 4, "drop": 5, "clip": 6}
+MAX_ACTION_FAULT_ITEMS = 256
+_ACTION_FAULT_KEYS = ("t0", "t1", "index", "op", "value")
+_ACTION_FAULT_OP_NAMES = {v: k for k, v in ACTION_FAULT_OPS.items()}
 _FIELD_NAMES = {v: k for k, v in PARAM_FIELDS.items()}
 _OP_NAMES = {v: k for k, v in PARAM_OPS.items()}
 
@@ -155,9 +171,10 @@ class ScenarioTable:
         self.check_rows, self.checks = [], None
         self.curve_rows, self.curves = [], None
         self.fault_rows, self.faults = [], None
+        self.action_fault_rows, self.action_faults = [], None
         for s, sc in enumerate(scenarios):
             sc = sc or {}
-            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "faults", "name"}:
+            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "faults", "action_faults", "name"}:
                 raise ValueError(f"ScenarioTable: scenario {s}: a mapping with the keys 'commands' and 'pushes' is expected, got {sc!r}")
             keys, pushes = [], []
             for r, row in enumerate(sc.get("commands") or []):
@@ -193,6 +210,7 @@ class ScenarioTable:
             self.check_rows.append(_check_rows(s, sc.get("checks") or []))
             self.curve_rows.append(_curve_rows(s, sc.get("curves") or []))
             self.fault_rows.append(_fault_rows(s, sc.get("faults") or []))
+            self.action_fault_rows.append(_action_fault_rows(s, sc.get("action_faults") or []))
         if names is not None or not self.has_params:
             self.resolve(names or {})
         cn = (names or {}).get("checks")
@@ -203,6 +221,84 @@ class ScenarioTable:
         fn = (names or {}).get("faults")
         if fn is not None or not self.has_faults:
             self.resolve_faults(fn or {"stacked": [], "non_stacked": [], "stack_size": 1})
+
+        an = (names or {}).get("action_faults")
+        if an is not None or not self.has_action_faults:
+            self.resolve_action_faults(an or [])
+
+    @property
+    def has_action_faults(self) -> bool:
+        return any(self.action_fault_rows)
+
+    def resolve_action_faults(self, actuators) -> "ScenarioTable":
+        """Expand the action faults against ``actuators`` (the model's actuator names in order, ``BatchedEnv.actuator_names()``):
+        ``self.action_faults[s]`` becomes the list of items ``(t0, t1, actuator j, op id, ord, float32 value)`` in listed order, ``"*"``
+        expanded in index order; ``ord`` is the ordinal of the listed item (its actuators share one ``drop`` draw).  Raises
+        ``ValueError`` naming the scenario and the item: unknown actuator, index out of range, more than 256 items."""
+        actuators = list(actuators)
+        nu = len(actuators)
+        out = []
+        for s, rows in enumerate(self.action_fault_rows):
+            items = []
+            for r, (t0, t1, index, op, value, _) in enumerate(rows):
+                who = f"ScenarioTable: scenario {s}, action-fault item {r}"
+                if index == "*":
+                    idx = list(range(nu))
+                elif isinstance(index, str):
+                    idx = [i for i, n in enumerate(actuators) if n == index]
+                    if not idx:
+                        raise ValueError(f"{who}: unknown actuator '{index}' (the model has {', '.join(map(str, actuators)) or 'none'})")
+                else:
+                    if not 0 <= index < nu:
+                        raise ValueError(f"{who}: index {index} out of range: the model has {nu} actuators")
+                    idx = [index]
+                items += [(t0, t1, j, ACTION_FAULT_OPS[op], r, np.float32(value)) for j in idx]
+            if len(items) > MAX_ACTION_FAULT_ITEMS:
+                raise ValueError(f"ScenarioTable: scenario {s}: {len(items)} action-fault items after expansion, at most {MAX_ACTION_FAULT_ITEMS}")
+            out.append(items)
+        self.action_faults = out
+        return self
+
+    def _resolved_action_faults(self):
+        if self.action_faults is None:
+            raise ValueError("ScenarioTable: the action faults are not resolved yet: pass names={'action_faults': [actuator names]} or call "
+                             "resolve_action_faults")
+        return self.action_faults
+
+    @property
+    def n_action_fault_items(self) -> int:
+        return sum(len(f) for f in self._resolved_action_faults())
+
+    def pack_action_faults(self):
+        """``(adr int32[S + 1], t int32[n, 2], actuator int32[n], op int32[n], ord int32[n], value float32[n])``: the expanded items in
+        the CSR form ``Engine.scenario_action_faults_set`` sends through ``cosim_set_param "action_faults"``."""
+        return _pack_items(self._resolved_action_faults(), 2, (np.int32, np.int32, np.int32, np.float32))
+
+    def action_faults_from_csr(self, adr, t, elem, op, ord, value, actuators) -> "ScenarioTable":
+        """A table with everything of this one but the action faults, which are those the CSR arrays of ``pack_action_faults`` hold:
+        the items of one ``ord`` become one listed item again (``"*"`` if they cover every actuator, else one item per actuator),
+        resolved against ``actuators``."""
+        t = np.asarray(t).reshape(-1, 2)
+        actuators = list(actuators)
+        nu = len(actuators)
+        scn = self.to_list()
+        if len(adr) != len(scn) + 1:
+            raise ValueError(f"ScenarioTable: action faults for {len(adr) - 1} scenarios, the table has {len(scn)}")
+        for s, sc in enumerate(scn):
+            sc.pop("action_faults", None)
+            rows, i, i1 = [], int(adr[s]), int(adr[s + 1])
+            while i < i1:
+                j = i
+                while j < i1 and int(ord[j]) == int(ord[i]):
+                    j += 1
+                whole = nu > 1 and [int(x) for x in elem[i:j]] == list(range(nu))
+                head = [int(t[i, 0]), int(t[i, 1])]
+                tail = [_ACTION_FAULT_OP_NAMES.get(int(op[i]), int(op[i])), float(np.float32(value[i]))]
+                rows += [head + ["*"] + tail] if whole else [head + [int(elem[k])] + tail for k in range(i, j)]
+                i = j
+            if rows:
+                sc["action_faults"] = rows
+        return type(self)(scn, self.command_dim).resolve_action_faults(actuators)
 
     @property
     def has_faults(self) -> bool:
@@ -441,6 +537,10 @@ class ScenarioTable:
             if rows:
                 sc["faults"] = [[t0, t1, obs, index, op, float(value)] + ([name] if name is not None else [])
                                 for t0, t1, obs, index, op, value, name in rows]
+        for sc, rows in zip(out, self.action_fault_rows):
+            if rows:
+                sc["action_faults"] = [[t0, t1, index, op, float(value)] + ([name] if name is not None else [])
+                                       for t0, t1, index, op, value, name in rows]
         return out
 
     def pack(self):
@@ -557,6 +657,51 @@ def _fault_rows(s: int, rows) -> list:
         if name is not None and not isinstance(name, str):
             raise ValueError(f"{who}: the name must be a string, got {name!r}")
         out.append((int(t0f), int(t1f), obs, index if isinstance(index, str) else int(index), op, value, name))
+    return out
+
+
+def _action_fault_rows(s: int, rows) -> list:
+    """The ``"action_faults"`` rows of scenario ``s``, checked for everything that needs no model: ``(t0, t1, index, op, value, name or
+    None)``.  The messages are those of ``_fault_rows``."""
+    out = []
+    if not isinstance(rows, (list, tuple)):
+        raise ValueError(f"ScenarioTable: scenario {s}: 'action_faults' must be a list of items, got {rows!r}")
+    for r, row in enumerate(rows):
+        who = f"ScenarioTable: scenario {s}, action-fault item {r}"
+        name = None
+        if isinstance(row, dict):
+            if set(row) - set(_ACTION_FAULT_KEYS) - {"name"} or any(k not in row for k in _ACTION_FAULT_KEYS if k not in ("index", "value")):
+                raise ValueError(f"{who}: a mapping with the keys {', '.join(_ACTION_FAULT_KEYS)} (and 'name') is expected, got {row!r}")
+            name = row.get("name")
+            row = [row.get(k, {"index": "*"}.get(k, 0.0)) for k in _ACTION_FAULT_KEYS]
+        elif isinstance(row, (list, tuple)) and len(row) == 6:
+            row, name = list(row[:5]), row[5]
+        if not isinstance(row, (list, tuple)) or len(row) != 5:
+            raise ValueError(f"{who}: expected [t0, t1, index, op, value] and an optional name, got {row!r}")
+        t0, t1, index, op, value = row
+        try:
+            t0f, t1f, value = float(t0), float(t1), float(value)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: times and value must be numbers, got {row!r}") from None
+        if not math.isfinite(value) or abs(value) > float(np.finfo(np.float32).max):   # (finite as float32 too)
+            raise ValueError(f"{who}: non-finite value")
+        if not (math.isfinite(t0f) and math.isfinite(t1f)) or t0f != int(t0f) or t1f != int(t1f) or not 0 <= t0f < MAX_TIME or not 0 <= t1f <= MAX_TIME:
+            raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
+        if t1f <= t0f:
+            raise ValueError(f"{who}: t1 {int(t1f)} is not after t0 {int(t0f)}")
+        if not isinstance(op, str) or op not in ACTION_FAULT_OPS:
+            raise ValueError(f"{who}: unknown op {op!r} (one of {', '.join(ACTION_FAULT_OPS)})")
+        if op == "noise" and value < 0:
+            raise ValueError(f"{who}: a noise amplitude must be >= 0, got {value!r}")
+        if op == "clip" and value < 0:
+            raise ValueError(f"{who}: a clip bound must be >= 0, got {value!r}")
+        if op == "drop" and not 0.0 <= value <= 1.0:
+            raise ValueError(f"{who}: a drop probability must lie in [0, 1], got {value!r}")
+        if isinstance(index, (bool, float)) or not isinstance(index, (int, np.integer, str)):
+            raise ValueError(f"{who}: index must be an int, an actuator name or '*', got {index!r}")
+        if name is not None and not isinstance(name, str):
+            raise ValueError(f"{who}: the name must be a string, got {name!r}")
+        out.append((int(t0f), int(t1f), index if isinstance(index, str) else int(index), op, value, name))
     return out
 
 
@@ -717,7 +862,8 @@ def _check_rows(s: int, rows) -> list:
 
 
 def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = (),
-          params: Iterable = (), checks: Iterable = (), curves: Iterable = (), faults: Iterable = ()) -> Iterator[dict]:
+          params: Iterable = (), checks: Iterable = (), curves: Iterable = (), faults: Iterable = (),
+          action_faults: Iterable = ()) -> Iterator[dict]:
     """The cartesian product command rows x push speeds x directions x push times as scenarios, commands outermost: each holds its
     command from episode step 0 and one push of ``speed`` m/s along the world direction ``angle`` (radians about z, 0 = +x) held over
     ``(t0, t1)``.  With no speeds or no times the product is over the commands alone (no push).
@@ -726,7 +872,18 @@ def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable =
     ``len(...) * len(P)`` scenarios in all.  ``checks``: a list of check lists (each a scenario's ``"checks"`` value, possibly empty)
     is one more axis, inside the parameters: ``len(...) * len(K)`` scenarios.  ``curves``: a list of curve lists (each a scenario's
     ``"curves"`` value, possibly empty) is one more axis, inside the checks.  ``faults``: a list of fault lists (each a scenario's
-    ``"faults"`` value, possibly empty) is one more axis, inside the curves and innermost of all: ``len(...) * len(F)`` scenarios."""
+    ``"faults"`` value, possibly empty) is one more axis, inside the curves: ``len(...) * len(F)`` scenarios.  ``action_faults``: a list
+    of action-fault lists (each a scenario's ``"action_faults"`` value, possibly empty) is one more axis, inside the faults and innermost
+    of all: ``len(...) * len(A)`` scenarios."""
+    action_faults = [list(f) for f in action_faults]
+    if action_faults:
+        for sc in sweep(commands, push_speeds, directions, push_times, params, checks, curves, faults):
+            for fl in action_faults:
+                out = dict(sc)
+                if fl:
+                    out["action_faults"] = [dict(f) if isinstance(f, dict) else list(f) for f in fl]
+                yield out
+        return
     faults = [list(f) for f in faults]
     if faults:
         for sc in sweep(commands, push_speeds, directions, push_times, params, checks, curves):
@@ -889,6 +1046,51 @@ def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count,
         new = np.concatenate([rows_out.reshape(N, S * sd), tail], axis=1)
         out[k] = np.where(act[:, None], new, out[k - 1] if k > 0 else new)
     return out
+
+
+def reference_action_faults(table: ScenarioTable, mode, gid, t, ep, step_count, seed: int, raw, prev_eff) -> np.ndarray:
+    """Numpy twin of ONE step of ``actfault_step_kernel`` for N envs, exact.  ``gid`` ``[N]`` global ids; the PRE-STEP meta words ``t``
+    (word 0), ``ep`` (word 11) and ``step_count`` (word 1), each ``[N]``; ``raw`` ``[N, nu]`` float32, the caller's actions; ``prev_eff``
+    ``[N, nu]`` float32, the record's ``s_lastact``: the effective action of the env's previous step, zeros where that step ended the
+    episode (or none was taken).  Returns the effective actions ``[N, nu]``: an actuator under no holding item keeps the caller's
+    bits."""
+    from . import rng
+    gid = np.asarray(gid, dtype=np.int64).reshape(-1)
+    N = len(gid)
+    raw = np.ascontiguousarray(raw, dtype=np.float32).reshape(N, -1)
+    prev = np.ascontiguousarray(prev_eff, dtype=np.float32).reshape(N, -1)
+    t, ep, step_count = (np.asarray(a).reshape(N) for a in (t, ep, step_count))
+    eff = raw.copy()
+    items = table._resolved_action_faults()
+    row = scenario_rows(len(table), mode, gid, ep)
+    u32 = np.uint32
+    for r in np.unique(row):
+        for t0, t1, j, op, ordinal, value in items[r]:
+            m = (row == r) & (t0 <= t) & (t < t1)
+            if not m.any():
+                continue
+            x = eff[m, j]
+            v = np.float32(value)
+            name = _ACTION_FAULT_OP_NAMES[op]
+            if name == "scale":
+                x = x * v
+            elif name == "bias":
+                x = x + v
+            elif name == "set":
+                x = np.full_like(x, v)
+            elif name == "noise":
+                u = rng.fault_noise_u(rng.first_word(seed, gid[m].astype(np.uint64), step_count[m].astype(u32), rng.PURPOSE_ACTION_FAULT, j))
+                x = x + (v * u).astype(np.float32)
+            elif name == "clip":
+                x = np.where(x > v, v, np.where(x < -v, -v, x))
+            else:                                                   # hold / drop: the previous effective action, but at episode step 0
+                lost = np.ones(int(m.sum()), dtype=bool)
+                if name == "drop":
+                    lost = rng.fault_drop_u(rng.first_word(seed, gid[m].astype(np.uint64), step_count[m].astype(u32),
+                                                           rng.PURPOSE_ACTION_FAULT, rng.FAULT_DROP_INDEX + ordinal)) < v
+                x = np.where(lost & (t[m] > 0), prev[m, j], x)
+            eff[m, j] = x.astype(np.float32)
+    return eff
 
 
 def push_reference(quat, v) -> np.ndarray:

@@ -423,6 +423,49 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  * (COSIM_EINVAL).  cosim_rollout stays refused (a scenario table is set); cosim_profile_step and cosim_debug_forward ignore the faults.
  * cosim_query "obs_faults" answers the number of items (0: none). */
 
+/* Action faults of the scenario table that is set: timed actuator-command bias, noise, hold and loss per env, applied on the device to
+ * what the step kernels are HANDED as the action (cosim_amd/csrc/cosim_actfault.h has the rule).  Like the observation faults they have
+ * no entry point of their own: the table travels through cosim_set_param(e, "action_faults", words, count), `words` pointing at `count`
+ * 32-BIT WORDS:
+ *   S | adr[S + 1] | t[n][2] | elem[n] | op[n] | ord[n] | value[n] (float bits),   n = adr[S],   count = S + 2 + 6 n
+ * (int32 but for value); the one word 0 clears the faults.  Scenario s owns the items [adr[s], adr[s + 1]) (at most 256).
+ * Item i names ONE actuator elem[i] (0 <= elem < nu), an op[i], a value[i] in the units of the policy's output (the raw action, before
+ * a_scale) and ord[i] (0..255), the ordinal of the listed item it was expanded from.  It holds while t[2i] <= t < t[2i + 1] of the env's
+ * PRE-STEP episode clock (meta word 0 as the step finds it: the clock of keyframes, pushes and parameter windows); the row is that of
+ * cosim_scenario_set on the pre-step meta words.  For every actuator under at least one holding item, starting from the caller's action
+ * word x, the holding items that name it apply in listed order, composing (fp32, no contraction):
+ *   0 scale x * value | 1 bias x + value | 2 set value | 3 noise x + value * u, u uniform in [-1, 1) (value >= 0)
+ *   4 hold: the action the step kernel was given one step earlier (the record's last-action words): the EFFECTIVE one, so a held
+ *     channel stays frozen through the window
+ *   5 drop: with probability value in [0, 1] per step and listed item as hold; all actuators of one ord are lost together
+ *   6 clip: x > value ? value : (x < -value ? -value : x) (value >= 0); NaN stays NaN
+ * Draws: Philox4x32-10 keyed (seed_lo, seed_hi), counter (meta word 1 pre-step, 8 | index << 8, gid_lo, gid_hi); noise: index = elem,
+ * drop: index = 0x10000 + ord; the word-to-float maps of the observation faults.  At episode step 0 the record holds no previous action:
+ * hold and drop are the identity there.  An actuator under no holding item gets the caller's bits.  Nothing is kept per env: the
+ * effective action is a function of (state record, table, caller's action), and a restored run continues bit for bit once the same items
+ * are set again.
+ * One small kernel (actfault_step_kernel, cosim_actfault.hip) runs ahead of every control step, behind the scenario and the
+ * parameter-window kernels on each stream group's own stream, inside the step's timing pair: it reads the caller's actions_dev rows of
+ * the range and writes two engine-owned buffers [N][nu], the effective and the raw actions, for EVERY env of the range.  While items are
+ * set every launch of a control step that reads the action (the fused and step-only kernels, the two-envs-per-wave kernel, both
+ * fix-up kernels' redo, the split pipeline's substep launches) is handed the effective buffer instead of actions_dev; the record's
+ * last-action words and delay line, the info row (set_points, action_diff_RMSE) and the ledger's means therefore describe what the
+ * motors were told.  Failure traces keep copying the caller's tensor.  If the observation has last_action elements a second kernel
+ * (actfault_obs_kernel) runs behind the last launch of the step, ahead of the observation faults' kernel: for an env whose post-step
+ * clock is not 0, each last_action element that is due (clock % interval == 0) is rewritten with raw[index] * scale in the frequency
+ * cache, row 0 of the observation stack and the newest frame of state_out -- what the step kernel would have written had it been handed
+ * the raw action: a policy sees its own output, not what the bus delivered.  An env that was just reset keeps the zeros.  Observation
+ * faults on last_action compose on top.
+ * Both work under a deferred join and inside a captured graph; the buffer pointers are kernel arguments: set or clear the faults before
+ * capturing; items of the counts of the ones that are set are rewritten in place and a captured graph picks the new values up.  The
+ * call joins the ranges and blocks until the device is idle; it launches nothing.  S = 0 clears the faults (the engine then passes the
+ * caller's pointer and launches what it always did); otherwise S must be the "scenario_rows" of the table that is set.
+ * cosim_scenario_set with another S, or clearing the table, drops them.  Validated on the host before anything is changed -- S, 0 <= elem
+ * < nu, t0 < t1, a known op, a finite value, drop in [0, 1], clip and noise >= 0, at most 256 items per scenario --, the message names
+ * the scenario and the item (COSIM_EINVAL).  cosim_rollout stays refused (a scenario table is set); cosim_profile_step and
+ * cosim_debug_forward ignore the faults.  cosim_query "action_faults" answers the number of items (0: none); cosim_get
+ * "action_effective" / "action_raw" copy the last step's buffers [N][nu] to device memory (COSIM_EINVAL while no faults are set). */
+
 /* Checks of the scenario table that is set: per-scenario pass / fail criteria judged on the device (cosim_amd/csrc/cosim_checks.h has
  * the rule).  Scenario s owns the items [adr[s], adr[s + 1]) (at most 64).  Item i takes one sample per control step whose PRE-STEP
  * episode clock t (meta word 0 as the scenario kernel read it ahead of that step) holds t[2i] <= t < t[2i + 1]:
