@@ -21,6 +21,7 @@ from .compile import CompiledModel, compile_model, env_constants
 from .engine import Engine, make_obs_config
 from .model import get_field
 from .robots import ROBOTS, obs_to_dim as robot_obs_to_dim
+from .scenario import FAULT_KINDS
 
 
 def _cmd_slices(stacked, non_stacked, dims, stack_size, command_dim):
@@ -731,16 +732,11 @@ class BatchedEnv:
             self.engine.scenario_params_set(table.pack_params())
         elif self.engine.query("scenario_param_items") > 0:
             self.engine.scenario_params_set(None)
-        # so do the observation faults
-        if table.has_faults:
-            self.engine.scenario_faults_set(table.pack_faults())
-        elif self.engine.query("obs_faults") > 0:
-            self.engine.scenario_faults_set(None)
-        # and the action faults
-        if table.has_action_faults:
-            self.engine.scenario_action_faults_set(table.pack_action_faults())
-        elif self.engine.query("action_faults") > 0:
-            self.engine.scenario_action_faults_set(None)
+        for kind in FAULT_KINDS:                                    # so do the observation and the action faults
+            if any(getattr(table, kind.rows)):
+                getattr(self.engine, kind.setter)(table._pack_fault_items(kind))
+            elif self.engine.query(kind.param) > 0:
+                getattr(self.engine, kind.setter)(None)
         # so do the checks, once they are armed
         self.check_slots = 0
         if check_slots and table.has_checks:
@@ -864,15 +860,18 @@ class BatchedEnv:
         from .scenario import fault_names
         return fault_names(self.stacked_obs_order, self.non_stacked_obs_order, self.obs_to_dim, self.stack_size)
 
+    def _fault_items(self, kind) -> list:
+        if self.scenario_table is None:
+            return []
+        items = [list(f) for f in getattr(self.scenario_table, kind.key)]
+        assert sum(len(f) for f in items) == self.engine.query(kind.param)
+        return items
+
     def obs_faults(self) -> list:
         """The expanded observation-fault items of the scenario table that is set, per scenario: ``(t0, t1, frame element, op id,
         ordinal of the listed item, float32 value)`` (``ScenarioTable.faults``); an empty list per scenario without any, ``[]`` with
         no table.  ``cosim_query "obs_faults"`` counts them."""
-        if self.scenario_table is None:
-            return []
-        items = [list(f) for f in self.scenario_table.faults]
-        assert sum(len(f) for f in items) == self.engine.query("obs_faults")
-        return items
+        return self._fault_items(FAULT_KINDS[0])
 
     def actuator_names(self) -> list:
         """The model's actuator names in order: what an action fault's ``index`` is resolved against."""
@@ -882,11 +881,7 @@ class BatchedEnv:
         """The expanded action-fault items of the scenario table that is set, per scenario: ``(t0, t1, actuator, op id, ordinal of the
         listed item, float32 value)`` (``ScenarioTable.action_faults``); an empty list per scenario without any, ``[]`` with no table.
         ``cosim_query "action_faults"`` counts them."""
-        if self.scenario_table is None:
-            return []
-        items = [list(f) for f in self.scenario_table.action_faults]
-        assert sum(len(f) for f in items) == self.engine.query("action_faults")
-        return items
+        return self._fault_items(FAULT_KINDS[1])
 
     def effective_action(self):
         """What the last ``step()``'s kernels were handed as the action while action faults are set: a float32 tensor ``[N, nu]`` (a

@@ -320,6 +320,7 @@ def main(argv=None) -> int:
     from .policy import build_policy, write_random_mlp
     from .reporter import FleetReporter
     from .runner import Runner, SinusoidPolicy
+    from .scenario import FAULT_KINDS
 
     rank, world = init_from_env(args.backend)
     if world > 1 and (args.checkpoint or args.resume):
@@ -453,10 +454,8 @@ def main(argv=None) -> int:
                              if "by_policy" in out.get("episodes", {}) else {}),
                           **({"param_windows": sum(len(w) for w in env.scenario_table.param_windows)}   # as listed in the table
                              if env.scenario_table is not None and env.scenario_table.has_params else {}),
-                          **({"obs_faults": env.scenario_table.n_fault_items}                           # expanded items, as the engine counts them
-                             if env.scenario_table is not None and env.scenario_table.has_faults else {}),
-                          **({"action_faults": env.scenario_table.n_action_fault_items}                 # likewise
-                             if env.scenario_table is not None and env.scenario_table.has_action_faults else {}),
+                          **({kind.param: sum(len(f) for f in getattr(env.scenario_table, kind.key))     # expanded items, as the engine counts them
+                              for kind in FAULT_KINDS if env.scenario_table is not None and any(getattr(env.scenario_table, kind.rows))}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()

@@ -4,7 +4,7 @@
 // actfault_step_kernel runs behind scenario_step_kernel and scnparams_step_kernel, AHEAD of a range's first launch of a control step
 // on that range's own stream.  One wave per env, lane = actuator (nu <= 64): it reads the env's pre-step clock (meta[0]), step counter
 // (meta[1]) and episode count (meta[11]), looks its row up (scenario_row, cosim_scenario.h), loads the caller's action row
-// (coalesced), walks the row's 16-byte item records once (cosim_actfault.h has the rule) and stores the env's rows of the two
+// (coalesced), walks the row's 16-byte item records once (cosim_actfault.h and cosim_fault.h have the rule) and stores the env's rows of the two
 // engine-owned buffers: actions_raw, the caller's bits, and actions_eff, what every step kernel of the control step is handed as its
 // action while faults are set.  EVERY env of the range is written: one under no holding item gets a plain copy.
 // One wave per env, not several: the row, the clock and so every item record and every branch on "does this item hold" are the same
@@ -26,7 +26,7 @@ namespace cosim {
 
 struct ActFaultArgs {
   ScnTable tab;            // the scenario table (row rule)
-  ActFaultTable flt;
+  FaultTable flt;
   const float* state;      // [N][s_stride] live state records
   const float* actions;    // [N][nu] the caller's actions
   float* eff;              // [N][nu] effective actions
@@ -46,35 +46,28 @@ struct ActObsArgs {
   int s_stride, s_meta, s_cache, s_stack, nu;
 };
 
-constexpr int ACF_WAVES = 4;                 // envs per block
 constexpr int ACF_PASSES = MAXFRAME / 64;    // every frame fits
 static_assert(ACF_PASSES * 64 == MAXFRAME, "passes of 64 lanes");
 
-__global__ __launch_bounds__(64 * ACF_WAVES) void actfault_step_kernel(ActFaultArgs a) {
+__global__ __launch_bounds__(64 * FLT_WAVES) void actfault_step_kernel(ActFaultArgs a) {
   const int lane = (int)threadIdx.x & 63;
-  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * ACF_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
+  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * FLT_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
   if (i >= a.count) return;   // the last block's tail
   const int env = a.first + i;
   if (env >= a.n_envs) return;
   if (lane >= a.nu) return;
   const float* rec = a.state + (size_t)env * a.s_stride;
-  const int* meta = reinterpret_cast<const int*>(rec + a.s_meta);
-  const int t = __builtin_amdgcn_readfirstlane(meta[0]);
-  const int row = scenario_row(a.tab, env, __builtin_amdgcn_readfirstlane(meta[11]));
-  const unsigned long long gid = (unsigned long long)(a.env_id0 + env);
-  ActFaultEnv E;
-  E.lastact = rec + a.s_lastact;
-  E.k0 = a.seed_lo; E.k1 = a.seed_hi; E.c0 = (unsigned)__builtin_amdgcn_readfirstlane(meta[1]);
-  E.g0 = (unsigned)gid; E.g1 = (unsigned)(gid >> 32);
+  int t, row;
+  ActFaultEnv E = {fault_wave_key(a.tab, reinterpret_cast<const int*>(rec + a.s_meta), env, a.seed_lo, a.seed_hi, a.env_id0, &t, &row), rec + a.s_lastact};
   const size_t w = (size_t)env * a.nu + lane;
   const float x = a.actions[w];
   a.raw[w] = x;
   a.eff[w] = actfault_apply(a.flt, row, t, E, lane, x);
 }
 
-__global__ __launch_bounds__(64 * ACF_WAVES) void actfault_obs_kernel(ActObsArgs a) {
+__global__ __launch_bounds__(64 * FLT_WAVES) void actfault_obs_kernel(ActObsArgs a) {
   const int lane = (int)threadIdx.x & 63;
-  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * ACF_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
+  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * FLT_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
   if (i >= a.count) return;   // the last block's tail
   const int env = a.first + i;
   if (env >= a.n_envs) return;

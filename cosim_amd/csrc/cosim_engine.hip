@@ -149,11 +149,11 @@ struct cosim_engine {
   ScnParTable scnpar = {};        // device pointers into d_scnpar; n_items 0: no windows, no launches, the step kernels read d_params
   // observation faults of the scenario table (cosim_set_param "obs_faults", cosim_obsfault.hip): obsfault_step_kernel behind every step's / reset's last launch
   char* d_obsflt = nullptr;       // one allocation: adr | item
-  ObsFaultTable obsflt = {};      // device pointers into d_obsflt; n_items 0: no faults, no launches
+  FaultTable obsflt = {};         // device pointers into d_obsflt; n_items 0: no faults, no launches
   // action faults of the scenario table (cosim_set_param "action_faults", cosim_actfault.hip): actfault_step_kernel ahead of every control
   // step's first launch, actfault_obs_kernel behind its last
   char* d_actflt = nullptr;       // one allocation: adr | item
-  ActFaultTable actflt = {};      // device pointers into d_actflt; n_items 0: no faults, no launches, the step kernels read the caller's actions
+  FaultTable actflt = {};         // device pointers into d_actflt; n_items 0: no faults, no launches, the step kernels read the caller's actions
   float* d_actions_eff = nullptr; // [n_envs][nu] effective actions: what the step kernels are handed while faults are set
   float* d_actions_raw = nullptr; // [n_envs][nu] the caller's actions of the last step (last_action is rebuilt from them)
   bool act_in_obs = false;        // the observation has last_action elements
@@ -729,7 +729,7 @@ static int obsfault_launch(cosim_engine* e, int first, int count, float* state_o
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_stack = e->lay.s_stack;
   a.sd = e->ho.stacked_dim; a.S = e->ho.stack_size; a.frame_dim = e->ho.frame_dim; a.state_dim = e->ho.state_dim;
   a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
-  return launch_small<OBF_WAVES, 64 * OBF_WAVES>(obsfault_step_kernel, a, count, s);
+  return launch_small<FLT_WAVES, 64 * FLT_WAVES>(obsfault_step_kernel, a, count, s);
 }
 
 // the action faults go with their table too (the caller has waited for the device)
@@ -747,7 +747,7 @@ static int actfault_launch(cosim_engine* e, int first, int count, const float* a
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_lastact = e->lay.s_lastact; a.nu = e->model.nu;
   a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
-  return launch_small<ACF_WAVES, 64 * ACF_WAVES>(actfault_step_kernel, a, count, s);
+  return launch_small<FLT_WAVES, 64 * FLT_WAVES>(actfault_step_kernel, a, count, s);
 }
 
 // behind the last launch of the step that writes the state record or state_out of those envs, same stream: last_action as the policy
@@ -758,7 +758,7 @@ static int actfault_obs_launch(cosim_engine* e, int first, int count, float* sta
   a.ob = e->d_obs; a.state = e->d_state; a.state_out = state_out; a.raw = e->d_actions_raw;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_cache = e->lay.s_cache; a.s_stack = e->lay.s_stack; a.nu = e->model.nu;
-  return launch_small<ACF_WAVES, 64 * ACF_WAVES>(actfault_obs_kernel, a, count, s);
+  return launch_small<FLT_WAVES, 64 * FLT_WAVES>(actfault_obs_kernel, a, count, s);
 }
 
 // ---- checks of the scenario table (cosim_checks.hip)
@@ -2349,96 +2349,74 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   return COSIM_OK;
 }
 
-// Observation faults of the scenario table that is set (cosim_set_param "obs_faults"): `words` is S | adr[S + 1] | t[n][2] | elem[n] |
-// op[n] | ord[n] | value[n] (float bits), n = adr[S]; S = 0 clears.  Items of the counts of the ones that are set are rewritten in
-// place: the device pointers stay, captured graphs pick the new values up.  Nothing is launched: the faults act from the next step
-// or reset on.
-static int obsfault_set(cosim_engine* e, const int32_t* words, int count) {
-  const std::string fn = OBF_SETTER;
+// Faults of the scenario table that is set, either kind (cosim_set_param "obs_faults" / "action_faults"): `words` is S | adr[S + 1] |
+// t[n][2] | elem[n] | op[n] | ord[n] | value[n] (float bits), n = adr[S]; S = 0 clears.  Items of the counts of the ones that are
+// set are rewritten in place: the device pointers stay, captured graphs pick the new values up.  Nothing is launched: the faults
+// act from the next step (observations: or reset) on.  The kind gives its allocation and table, how they are dropped, its validator
+// (cosim_tables.h) and, if it has any, the buffers it needs beside the table: `buffers` allocates them ahead of the copy.
+static int fault_table_set(cosim_engine* e, const std::string& fn, const char* what, char*& d_tab, FaultTable& slot, void (*drop)(cosim_engine*),
+                           hipError_t (*buffers)(cosim_engine*), FltShape (*validate)(const cosim_engine*, const FltRaw&), const int32_t* words, int count) {
   if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the faults)");
   const int n_scn = words[0];
   HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) return table_clear(e, 0, obsfault_free);
-  RC_TRY(table_rows_match(e, fn, "observation faults", n_scn));
+  if (n_scn == 0) return table_clear(e, 0, drop);
+  RC_TRY(table_rows_match(e, fn, what, n_scn));
   if (count < n_scn + 2) return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words do not hold the row addresses of " + std::to_string(n_scn) + " scenarios");
   const int32_t* adr = words + 1;
-  const long long n = adr[n_scn];   // (validate_faults holds every row inside [0, adr[S]] before it reads an item by these addresses)
+  const long long n = adr[n_scn];   // (the validator holds every row inside [0, adr[S]] before it reads an item by these addresses)
   if (n < 0 || (long long)count != n_scn + 2 + 6 * n)
     return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios and " + std::to_string(n) + " items takes " +
                                   std::to_string(n_scn + 2 + 6 * (n < 0 ? 0 : n)));
   const int32_t *t = adr + n_scn + 1, *elem = t + 2 * n, *op = elem + n, *ord = op + n;
-  const float* value = reinterpret_cast<const float*>(ord + n);
-  const ObsDims dims = {e->ho.frame_dim, e->ho.stacked_dim, e->ho.stack_size, e->ho.el_field, CS_OBS_COMMAND};
-  const FltRaw raw = {n_scn, adr, t, elem, op, ord, value};
-  const FltShape v = validate_faults(dims, raw);
+  const FltRaw raw = {n_scn, adr, t, elem, op, ord, reinterpret_cast<const float*>(ord + n)};
+  const FltShape v = validate(e, raw);
   if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
   RC_TRY(table_quiesce(e, 0));
-  ObsFaultTable tab = {};
+  FaultTable tab = {};
   WordPacker pk;
   pack_faults(pk, tab, raw, v);
-  const bool in_place = e->obsflt.n_items == v.n && e->obsflt.n_scn == n_scn;
-  char* d_new = e->d_obsflt;
+  const bool in_place = slot.n_items == v.n && slot.n_scn == n_scn;
+  char* d_new = d_tab;
   if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
-  const hipError_t r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-  if (r != hipSuccess) {   // a new allocation is dropped and the old items stay; an in-place rewrite may be half written: no faults then
-    if (in_place) obsfault_free(e); else (void)hipFree(d_new);
+  hipError_t r = buffers ? buffers(e) : hipSuccess;
+  if (r != hipSuccess) {
+    if (!in_place) (void)hipFree(d_new);
     return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
   }
-  if (!in_place) { (void)hipFree(e->d_obsflt); e->d_obsflt = d_new; }
-  pk.patch(e->d_obsflt);
-  e->obsflt = tab;
+  r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) {   // a new allocation is dropped and the old items stay (with none set before, neither do the kind's buffers); an in-place rewrite may be half written: no faults then
+    if (in_place) drop(e);
+    else { (void)hipFree(d_new); if (slot.n_items == 0) drop(e); }
+    return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
+  }
+  if (!in_place) { (void)hipFree(d_tab); d_tab = d_new; }
+  pk.patch(d_tab);
+  slot = tab;
   return COSIM_OK;
 }
 
-// Action faults of the scenario table that is set (cosim_set_param "action_faults"): `words` is S | adr[S + 1] | t[n][2] | elem[n] |
-// op[n] | ord[n] | value[n] (float bits), elem an actuator, n = adr[S]; S = 0 clears.  Items of the counts of the ones that are set
-// are rewritten in place: the device pointers stay, captured graphs pick the new values up.  Nothing is launched: the faults act
-// from the next step on.
+static FltShape obsfault_validate(const cosim_engine* e, const FltRaw& raw) {
+  return validate_faults({e->ho.frame_dim, e->ho.stacked_dim, e->ho.stack_size, e->ho.el_field, CS_OBS_COMMAND}, raw);
+}
+static int obsfault_set(cosim_engine* e, const int32_t* words, int count) {
+  return fault_table_set(e, OBF_SETTER, "observation faults", e->d_obsflt, e->obsflt, obsfault_free, nullptr, obsfault_validate, words, count);
+}
+
+// the two action buffers: both or neither; zeroed, so that a read ahead of the first step finds no stale bytes
+static hipError_t actfault_buffers(cosim_engine* e) {
+  if (e->d_actions_eff) return hipSuccess;
+  const size_t bytes = (size_t)e->n_envs * e->model.nu * sizeof(float);
+  hipError_t r = hipMalloc(&e->d_actions_eff, bytes);
+  if (r == hipSuccess) r = hipMalloc(&e->d_actions_raw, bytes);
+  if (r == hipSuccess) r = hipMemset(e->d_actions_eff, 0, bytes);
+  if (r == hipSuccess) r = hipMemset(e->d_actions_raw, 0, bytes);
+  if (r != hipSuccess) { (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw); e->d_actions_eff = nullptr; e->d_actions_raw = nullptr; }
+  return r;
+}
+
+static FltShape actfault_validate(const cosim_engine* e, const FltRaw& raw) { return validate_action_faults(e->model.nu, raw); }
 static int actfault_set(cosim_engine* e, const int32_t* words, int count) {
-  const std::string fn = ACF_SETTER;
-  if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the faults)");
-  const int n_scn = words[0];
-  HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) return table_clear(e, 0, actfault_free);
-  RC_TRY(table_rows_match(e, fn, "action faults", n_scn));
-  if (count < n_scn + 2) return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words do not hold the row addresses of " + std::to_string(n_scn) + " scenarios");
-  const int32_t* adr = words + 1;
-  const long long n = adr[n_scn];   // (validate_action_faults holds every row inside [0, adr[S]] before it reads an item by these addresses)
-  if (n < 0 || (long long)count != n_scn + 2 + 6 * n)
-    return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios and " + std::to_string(n) + " items takes " +
-                                  std::to_string(n_scn + 2 + 6 * (n < 0 ? 0 : n)));
-  const int32_t *t = adr + n_scn + 1, *elem = t + 2 * n, *op = elem + n, *ord = op + n;
-  const float* value = reinterpret_cast<const float*>(ord + n);
-  const FltRaw raw = {n_scn, adr, t, elem, op, ord, value};
-  const FltShape v = validate_action_faults(e->model.nu, raw);
-  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
-  RC_TRY(table_quiesce(e, 0));
-  ActFaultTable tab = {};
-  WordPacker pk;
-  pack_action_faults(pk, tab, raw, v);
-  const bool in_place = e->actflt.n_items == v.n && e->actflt.n_scn == n_scn;
-  char* d_new = e->d_actflt;
-  if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
-  if (!e->d_actions_eff) {   // both buffers or neither; zeroed, so that a read ahead of the first step finds no stale bytes
-    const size_t bytes = (size_t)e->n_envs * e->model.nu * sizeof(float);
-    hipError_t r = hipMalloc(&e->d_actions_eff, bytes);
-    if (r == hipSuccess) { r = hipMalloc(&e->d_actions_raw, bytes); if (r != hipSuccess) { (void)hipFree(e->d_actions_eff); } }
-    if (r == hipSuccess) { r = hipMemset(e->d_actions_eff, 0, bytes); if (r == hipSuccess) r = hipMemset(e->d_actions_raw, 0, bytes); if (r != hipSuccess) { (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw); } }
-    if (r != hipSuccess) {
-      e->d_actions_eff = nullptr; e->d_actions_raw = nullptr;
-      if (!in_place) (void)hipFree(d_new);
-      return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
-    }
-  }
-  const hipError_t r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-  if (r != hipSuccess) {   // a new allocation is dropped and the old items stay; an in-place rewrite may be half written: no faults then
-    if (in_place) actfault_free(e);
-    else { (void)hipFree(d_new); if (e->actflt.n_items == 0) actfault_free(e); }
-    return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
-  }
-  if (!in_place) { (void)hipFree(e->d_actflt); e->d_actflt = d_new; }
-  pk.patch(e->d_actflt);
-  e->actflt = tab;
+  RC_TRY(fault_table_set(e, ACF_SETTER, "action faults", e->d_actflt, e->actflt, actfault_free, actfault_buffers, actfault_validate, words, count));
   e->act_in_obs = false;
   for (int el = 0; el < e->ho.frame_dim; el++) e->act_in_obs = e->act_in_obs || e->ho.el_field[el] == CS_OBS_LAST_ACTION;
   return COSIM_OK;

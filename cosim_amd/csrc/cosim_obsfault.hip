@@ -5,7 +5,7 @@
 // on the split pipeline the last substep's solver and fix-up) on that stream group's own stream, and behind a reset's launch for
 // the envs under its mask; ahead of the observers and the history pack.  One wave per env, lane = frame element in passes of 64:
 // it reads the env's post-step clock (meta[0]), step counter (meta[1]) and episode count (meta[11]), looks its row up (scenario_row,
-// cosim_scenario.h) and walks the row's 16-byte item records once (cosim_obsfault.h has the rule; the row is the same for the whole
+// cosim_scenario.h) and walks the row's 16-byte item records once (cosim_obsfault.h and cosim_fault.h have the rule; the row is the same for the whole
 // wave, so the item loads are scalar).  An env whose row has no item that holds leaves after its meta words and the row's records,
 // with nothing of its frame loaded.  The faulted values go to row 0 of the record's observation stack, so the next step's roll
 // carries them on as a sensor history would, and to state_out.
@@ -17,7 +17,7 @@ namespace cosim {
 
 struct ObsFaultArgs {
   ScnTable tab;            // the scenario table (row rule)
-  ObsFaultTable flt;
+  FaultTable flt;
   float* state;            // [N][s_stride] live state records
   float* state_out;        // [N][state_dim] the step's / reset's observation rows
   const uint8_t* mask;     // reset: uint8[N] or null
@@ -28,27 +28,20 @@ struct ObsFaultArgs {
   long long env_id0;
 };
 
-constexpr int OBF_WAVES = 4;                 // envs per block
 constexpr int OBF_PASSES = MAXFRAME / 64;    // every frame fits
 static_assert(OBF_PASSES * 64 == MAXFRAME, "passes of 64 lanes");
 
-__global__ __launch_bounds__(64 * OBF_WAVES) void obsfault_step_kernel(ObsFaultArgs a) {
+__global__ __launch_bounds__(64 * FLT_WAVES) void obsfault_step_kernel(ObsFaultArgs a) {
   const int lane = (int)threadIdx.x & 63;
-  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * OBF_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
+  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * FLT_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
   if (i >= a.count) return;   // the last block's tail
   const int env = a.first + i;
   if (env >= a.n_envs) return;
   if (a.mask != nullptr && a.mask[env] == 0) return;
   float* rec = a.state + (size_t)env * a.s_stride;
-  const int* meta = reinterpret_cast<const int*>(rec + a.s_meta);
-  const int t = __builtin_amdgcn_readfirstlane(meta[0]);
-  const int row = scenario_row(a.tab, env, __builtin_amdgcn_readfirstlane(meta[11]));
-  const unsigned long long gid = (unsigned long long)(a.env_id0 + env);
-  ObsFaultEnv E;
-  E.stack = rec + a.s_stack; E.out = a.state_out + (size_t)env * a.state_dim;
-  E.sd = a.sd; E.S = a.S; E.frame_dim = a.frame_dim;
-  E.k0 = a.seed_lo; E.k1 = a.seed_hi; E.c0 = (unsigned)__builtin_amdgcn_readfirstlane(meta[1]);
-  E.g0 = (unsigned)gid; E.g1 = (unsigned)(gid >> 32);
+  int t, row;
+  ObsFaultEnv E = {fault_wave_key(a.tab, reinterpret_cast<const int*>(rec + a.s_meta), env, a.seed_lo, a.seed_hi, a.env_id0, &t, &row),
+                   rec + a.s_stack, a.state_out + (size_t)env * a.state_dim, a.sd, a.S, a.frame_dim};
   obsfault_apply<OBF_PASSES>(a.flt, row, t, E, lane, 64, 0);
 }
 

@@ -219,96 +219,81 @@ inline void pack_params(WordPacker& pk, ScnParTable& tab, const ParRaw& r, const
   tab.n_scn = r.n_scn; tab.n_items = v.n;
 }
 
-// ---- cosim_set_param "obs_faults".  Image: adr | item ([n + OBF_CHUNK - 1][4]: t0, t1, e | op << 16 | ord << 24, value: cosim_obsfault.h)
-// what a fault item is held against of the observation frame
-struct ObsDims {
-  int frame_dim, stacked_dim, stack_size;
-  const unsigned char* el_field;   // [frame_dim] CS_OBS_* of every frame element
-  int command_field;               // CS_OBS_COMMAND
-};
+// ---- cosim_set_param "obs_faults" / "action_faults".  Image: adr | item ([n + FLT_CHUNK - 1][4]: t0, t1, el | op << 16 | ord << 24, value: cosim_fault.h)
 struct FltRaw {
   int n_scn;   // that of the scenario table that is set
   const int32_t *adr, *t, *elem, *op, *ord; const float* value;
 };
 struct FltShape { std::string err; int n = 0; std::vector<int32_t> item; };
+// what the two kinds differ in besides their rules: how the messages name the setter and an item, the highest op and the list an unknown one is answered with
+struct FltKind { const char *setter, *noun; int max_op; const char* ops; };
 
+// The rules of both kinds, in the order they are reported in.  elem_rule(row, el) is the kind's word on an element, ahead of the op;
+// op_rule(row, el, op, value) its word on an op the shared rules have passed, behind them.
+template <class ElemRule, class OpRule>
+inline FltShape validate_fault_items(const FltKind& kind, const FltRaw& r, ElemRule elem_rule, OpRule op_rule) {
+  const std::string fn = kind.setter, noun = kind.noun, nouns = noun + "s";
+  FltShape v;
+  const RowAdr rows[1] = {{"adr", r.adr, nouns.c_str(), FLT_MAX_ITEMS, r.t && r.elem && r.op && r.ord && r.value}};
+  TAB_TRY(row_heads(fn, rows));
+  // all rows first: the item arrays hold adr[S] items (the setter sized them so), and 0 = adr[0] <= ... <= adr[S] keeps every row inside
+  for (int s = 0; s < r.n_scn; s++) TAB_TRY(row_rule(fn + ": scenario " + std::to_string(s), rows, s));
+  for (int s = 0; s < r.n_scn; s++) {
+    const std::string who = fn + ": scenario " + std::to_string(s);
+    for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
+      const std::string row = who + ", " + noun + " " + std::to_string(i - r.adr[s]);
+      const int el = r.elem[i], op = r.op[i];
+      TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
+      TAB_TRY(elem_rule(row, el));
+      if (op < FLT_SCALE || op > kind.max_op) TAB_TRY(row + ": unknown op " + std::to_string(op) + " " + kind.ops);
+      if (!std::isfinite(r.value[i])) TAB_TRY(row + ": value is not finite");
+      if (op == FLT_NOISE && r.value[i] < 0.f) TAB_TRY(row + ": a noise amplitude must be >= 0");
+      if (op == FLT_DROP && !(r.value[i] >= 0.f && r.value[i] <= 1.f)) TAB_TRY(row + ": a drop probability must lie in [0, 1]");
+      TAB_TRY(op_rule(row, el, op, r.value[i]));
+      if (r.ord[i] < 0 || r.ord[i] >= FLT_MAX_ITEMS) TAB_TRY(row + ": ordinal " + std::to_string(r.ord[i]) + " outside 0..255");
+      int32_t vb;
+      memcpy(&vb, &r.value[i], 4);
+      v.item.push_back(r.t[2 * i]); v.item.push_back(r.t[2 * i + 1]);
+      v.item.push_back((int32_t)((unsigned)el | (unsigned)op << 16 | (unsigned)r.ord[i] << 24)); v.item.push_back(vb);
+    }
+  }
+  v.n = r.adr[r.n_scn];
+  if (v.n == 0) TAB_TRY(fn + ": the table holds no " + noun + " (n_scn = 0 clears the faults)");
+  v.item.resize(v.item.size() + 4 * (FLT_CHUNK - 1), 0);   // records that never hold: the kernels fetch FLT_CHUNK at a time
+  return v;
+}
+
+inline void pack_faults(WordPacker& pk, FaultTable& tab, const FltRaw& r, const FltShape& v) {
+  pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.item, v.item.data(), v.item.size());
+  tab.n_scn = r.n_scn; tab.n_items = v.n;
+}
+
+// observations: what a fault item is held against of the observation frame
+struct ObsDims {
+  int frame_dim, stacked_dim, stack_size;
+  const unsigned char* el_field;   // [frame_dim] CS_OBS_* of every frame element
+  int command_field;               // CS_OBS_COMMAND
+};
 inline FltShape validate_faults(const ObsDims& d, const FltRaw& r) {
-  const std::string fn = OBF_SETTER;
-  FltShape v;
-  const RowAdr rows[1] = {{"adr", r.adr, "fault items", OBF_MAX_ITEMS, r.t && r.elem && r.op && r.ord && r.value}};
-  TAB_TRY(row_heads(fn, rows));
-  // all rows first: the item arrays hold adr[S] items (the setter sized them so), and 0 = adr[0] <= ... <= adr[S] keeps every row inside
-  for (int s = 0; s < r.n_scn; s++) TAB_TRY(row_rule(fn + ": scenario " + std::to_string(s), rows, s));
-  for (int s = 0; s < r.n_scn; s++) {
-    const std::string who = fn + ": scenario " + std::to_string(s);
-    for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
-      const std::string row = who + ", fault item " + std::to_string(i - r.adr[s]);
-      const int e = r.elem[i], op = r.op[i];
-      TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
-      if (e < 0 || e >= d.frame_dim) TAB_TRY(row + ": element " + std::to_string(e) + " out of range: the frame has " + std::to_string(d.frame_dim) + " elements");
-      if (d.el_field[e] == d.command_field)
-        TAB_TRY(row + ": element " + std::to_string(e) + " is a command word and is refused: the command words are the scenario's keyframes");
-      if (op < OBF_SCALE || op > OBF_DROP) TAB_TRY(row + ": unknown op " + std::to_string(op) + " (0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop)");
-      if (!std::isfinite(r.value[i])) TAB_TRY(row + ": value is not finite");
-      if (op == OBF_NOISE && r.value[i] < 0.f) TAB_TRY(row + ": a noise amplitude must be >= 0");
-      if (op == OBF_DROP && !(r.value[i] >= 0.f && r.value[i] <= 1.f)) TAB_TRY(row + ": a drop probability must lie in [0, 1]");
-      if ((op == OBF_HOLD || op == OBF_DROP) && (e >= d.stacked_dim || d.stack_size < 2))
-        TAB_TRY(row + ": hold / drop needs a stacked element and stack_size >= 2: there is no previous frame in the record");
-      if (r.ord[i] < 0 || r.ord[i] >= OBF_MAX_ITEMS) TAB_TRY(row + ": ordinal " + std::to_string(r.ord[i]) + " outside 0..255");
-      int32_t vb;
-      memcpy(&vb, &r.value[i], 4);
-      v.item.push_back(r.t[2 * i]); v.item.push_back(r.t[2 * i + 1]);
-      v.item.push_back((int32_t)((unsigned)e | (unsigned)op << 16 | (unsigned)r.ord[i] << 24)); v.item.push_back(vb);
-    }
-  }
-  v.n = r.adr[r.n_scn];
-  if (v.n == 0) TAB_TRY(fn + ": the table holds no fault item (n_scn = 0 clears the faults)");
-  v.item.resize(v.item.size() + 4 * (OBF_CHUNK - 1), 0);   // records that never hold: the kernel fetches OBF_CHUNK at a time
-  return v;
+  const auto elem_rule = [&d](const std::string& row, int e) {
+    if (e < 0 || e >= d.frame_dim) return row + ": element " + std::to_string(e) + " out of range: the frame has " + std::to_string(d.frame_dim) + " elements";
+    if (d.el_field[e] != d.command_field) return std::string();
+    return row + ": element " + std::to_string(e) + " is a command word and is refused: the command words are the scenario's keyframes";
+  };
+  const auto op_rule = [&d](const std::string& row, int e, int op, float) {
+    if ((op != FLT_HOLD && op != FLT_DROP) || (e < d.stacked_dim && d.stack_size >= 2)) return std::string();
+    return row + ": hold / drop needs a stacked element and stack_size >= 2: there is no previous frame in the record";
+  };
+  return validate_fault_items({OBF_SETTER, "fault item", FLT_DROP, "(0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop)"}, r, elem_rule, op_rule);
 }
 
-inline void pack_faults(WordPacker& pk, ObsFaultTable& tab, const FltRaw& r, const FltShape& v) {
-  pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.item, v.item.data(), v.item.size());
-  tab.n_scn = r.n_scn; tab.n_items = v.n;
-}
-
-// ---- cosim_set_param "action_faults".  Image: adr | item ([n + ACF_CHUNK - 1][4]: t0, t1, j | op << 16 | ord << 24, value: cosim_actfault.h)
-// (the raw columns are those of the observation faults, `elem` an actuator index)
+// actions: `elem` is an actuator index
 inline FltShape validate_action_faults(int nu, const FltRaw& r) {
-  const std::string fn = ACF_SETTER;
-  FltShape v;
-  const RowAdr rows[1] = {{"adr", r.adr, "action-fault items", ACF_MAX_ITEMS, r.t && r.elem && r.op && r.ord && r.value}};
-  TAB_TRY(row_heads(fn, rows));
-  // all rows first: the item arrays hold adr[S] items (the setter sized them so), and 0 = adr[0] <= ... <= adr[S] keeps every row inside
-  for (int s = 0; s < r.n_scn; s++) TAB_TRY(row_rule(fn + ": scenario " + std::to_string(s), rows, s));
-  for (int s = 0; s < r.n_scn; s++) {
-    const std::string who = fn + ": scenario " + std::to_string(s);
-    for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
-      const std::string row = who + ", action-fault item " + std::to_string(i - r.adr[s]);
-      const int j = r.elem[i], op = r.op[i];
-      TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
-      if (j < 0 || j >= nu) TAB_TRY(row + ": actuator " + std::to_string(j) + " out of range: the model has " + std::to_string(nu) + " actuators");
-      if (op < ACF_SCALE || op > ACF_CLIP) TAB_TRY(row + ": unknown op " + std::to_string(op) + " (0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop, 6 clip)");
-      if (!std::isfinite(r.value[i])) TAB_TRY(row + ": value is not finite");
-      if (op == ACF_NOISE && r.value[i] < 0.f) TAB_TRY(row + ": a noise amplitude must be >= 0");
-      if (op == ACF_CLIP && r.value[i] < 0.f) TAB_TRY(row + ": a clip bound must be >= 0");
-      if (op == ACF_DROP && !(r.value[i] >= 0.f && r.value[i] <= 1.f)) TAB_TRY(row + ": a drop probability must lie in [0, 1]");
-      if (r.ord[i] < 0 || r.ord[i] >= ACF_MAX_ITEMS) TAB_TRY(row + ": ordinal " + std::to_string(r.ord[i]) + " outside 0..255");
-      int32_t vb;
-      memcpy(&vb, &r.value[i], 4);
-      v.item.push_back(r.t[2 * i]); v.item.push_back(r.t[2 * i + 1]);
-      v.item.push_back((int32_t)((unsigned)j | (unsigned)op << 16 | (unsigned)r.ord[i] << 24)); v.item.push_back(vb);
-    }
-  }
-  v.n = r.adr[r.n_scn];
-  if (v.n == 0) TAB_TRY(fn + ": the table holds no action-fault item (n_scn = 0 clears the faults)");
-  v.item.resize(v.item.size() + 4 * (ACF_CHUNK - 1), 0);   // records that never hold: the kernel fetches ACF_CHUNK at a time
-  return v;
-}
-
-inline void pack_action_faults(WordPacker& pk, ActFaultTable& tab, const FltRaw& r, const FltShape& v) {
-  pk.add(&tab.adr, r.adr, (size_t)r.n_scn + 1); pk.add(&tab.item, v.item.data(), v.item.size());
-  tab.n_scn = r.n_scn; tab.n_items = v.n;
+  const auto elem_rule = [nu](const std::string& row, int j) {
+    return j >= 0 && j < nu ? std::string() : row + ": actuator " + std::to_string(j) + " out of range: the model has " + std::to_string(nu) + " actuators";
+  };
+  const auto op_rule = [](const std::string& row, int, int op, float value) { return op == FLT_CLIP && value < 0.f ? row + ": a clip bound must be >= 0" : std::string(); };
+  return validate_fault_items({ACF_SETTER, "action-fault item", FLT_CLIP, "(0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop, 6 clip)"}, r, elem_rule, op_rule);
 }
 
 // ---- cosim_scenario_checks_set.  Image: adr | t | signal | index | mode | cmp | bound

@@ -16,7 +16,7 @@ Purposes: 0 action-delay draw, 1 sensor noise (index = frame element), 2 init-qp
 (``csrc/cosim_obsfault.h``; step = meta word 1 as the step that produced the observation left it; ``noise``: index = frame element
 ``e`` (< 256), mapped by ``fault_noise_u``; ``drop``: index = ``0x10000 + ord``, the listed item's ordinal, mapped by ``fault_drop_u``),
 8 action faults of a scenario table (``csrc/cosim_actfault.h``; step = meta word 1 as the step FINDS it; ``noise``: index = actuator
-``j``; ``drop``: index = ``0x10000 + ord``; the same two maps).
+``j``; ``drop``: index = ``0x10000 + ord``; the same two maps).  ``csrc/cosim_fault.h`` has the draws and the maps of both.
 """
 from __future__ import annotations
 
@@ -84,12 +84,12 @@ def first_word(seed: int, env_ids, step, purpose: int, index):
 
 
 def fault_noise_u(x):
-    """uint32 -> float32 in [-1, 1): ``(x >> 8) * 2^-23 - 1``, exact (the device ``obsfault_noise_u``)."""
+    """uint32 -> float32 in [-1, 1): ``(x >> 8) * 2^-23 - 1``, exact (the device ``fault_noise_u``, ``csrc/cosim_fault.h``)."""
     x = np.asarray(x, dtype=np.uint32)
     return ((x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 8388608.0) - np.float32(1.0)).astype(np.float32)
 
 
 def fault_drop_u(x):
-    """uint32 -> float32 in [0, 1): ``(x >> 8) * 2^-24``, exact (the device ``obsfault_drop_u``)."""
+    """uint32 -> float32 in [0, 1): ``(x >> 8) * 2^-24``, exact (the device ``fault_drop_u``, ``csrc/cosim_fault.h``)."""
     x = np.asarray(x, dtype=np.uint32)
     return ((x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)).astype(np.float32)

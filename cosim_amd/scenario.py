@@ -64,7 +64,7 @@ from __future__ import annotations
 
 import itertools
 import math
-from typing import Iterable, Iterator, Sequence
+from typing import Iterable, Iterator, NamedTuple, Sequence
 
 import numpy as np
 
@@ -83,13 +83,37 @@ _CURVE_KEYS = ("t0", "t1", "every", "signal", "index", "lo", "hi", "bins")
 # consistent only as a set that compile.env_constants computes in fp64 on the host
 REFUSED_PARAM_FIELDS = ("body_mass", "body_invweight0", "dof_invweight0", "meaninertia")
 FAULT_OPS = {"scale": 0, "bias": 1, "set": 2, "noise": 3, "hold": 4, "drop": 5}
-MAX_FAULT_ITEMS = 256
-_FAULT_KEYS = ("t0", "t1", "obs", "index", "op", "value")
-_FAULT_OP_NAMES = {v: k for k, v in FAULT_OPS.items()}
-ACTION_FAULT_OPS = {"scale": 0, "bias": 1, "set": 2, "noise": 3, "hold": 4, "drop": 5, "clip": 6}
-MAX_ACTION_FAULT_ITEMS = 256
-_ACTION_FAULT_KEYS = ("t0", "t1", "index", "op", "value")
-_ACTION_FAULT_OP_NAMES = {v: k for k, v in ACTION_FAULT_OPS.items()}
+ACTION_FAULT_OPS = dict(FAULT_OPS, clip=6)
+MAX_FAULT_ITEMS = MAX_ACTION_FAULT_ITEMS = 256
+
+
+class _FaultKind(NamedTuple):
+    """What the two kinds of fault differ in but for their resolvers and twins.  ``key`` is the scenario key and the attribute of the
+    expanded items, ``rows`` the attribute of the rows as written."""
+    key: str
+    rows: str
+    param: str           # the engine's name of the word table (cosim_set_param / cosim_query) ...
+    setter: str          # ... and the Engine method that sends it
+    what: str            # "faults": how the messages name the kind ...
+    noun: str            # ... and one item of it
+    keys: tuple          # the columns of a row
+    ops: dict
+    cap: int
+    index: str           # what an index may be, in the message ...
+    named: bool          # ... and whether a name is one
+    unresolved: str
+
+    @property
+    def op_names(self) -> dict:
+        return {v: k for k, v in self.ops.items()}
+
+
+_OBS_FAULTS = _FaultKind("faults", "fault_rows", "obs_faults", "scenario_faults_set", "faults", "fault item", ("t0", "t1", "obs", "index", "op", "value"), FAULT_OPS, MAX_FAULT_ITEMS,
+                         "an int or '*'", False, "pass names={'faults': fault_names(...)} or call resolve_faults")
+_ACTION_FAULTS = _FaultKind("action_faults", "action_fault_rows", "action_faults", "scenario_action_faults_set", "action faults", "action-fault item",
+                            ("t0", "t1", "index", "op", "value"), ACTION_FAULT_OPS, MAX_ACTION_FAULT_ITEMS, "an int, an actuator name or '*'", True,
+                            "pass names={'action_faults': [actuator names]} or call resolve_action_faults")
+FAULT_KINDS = (_OBS_FAULTS, _ACTION_FAULTS)
 _FIELD_NAMES = {v: k for k, v in PARAM_FIELDS.items()}
 _OP_NAMES = {v: k for k, v in PARAM_OPS.items()}
 
@@ -170,7 +194,7 @@ class ScenarioTable:
         self.keys, self.pushes, self.param_windows, self.params = [], [], [], None
         self.check_rows, self.checks = [], None
         self.curve_rows, self.curves = [], None
-        self.fault_rows, self.faults = [], None
+        self.fault_rows, self.faults = [], None                   # (the attributes the two _FaultKind name)
         self.action_fault_rows, self.action_faults = [], None
         for s, sc in enumerate(scenarios):
             sc = sc or {}
@@ -209,8 +233,8 @@ class ScenarioTable:
             self.param_windows.append(_param_windows(s, sc.get("params") or []))
             self.check_rows.append(_check_rows(s, sc.get("checks") or []))
             self.curve_rows.append(_curve_rows(s, sc.get("curves") or []))
-            self.fault_rows.append(_fault_rows(s, sc.get("faults") or []))
-            self.action_fault_rows.append(_action_fault_rows(s, sc.get("action_faults") or []))
+            for kind in FAULT_KINDS:
+                getattr(self, kind.rows).append(_fault_kind_rows(kind, s, sc.get(kind.key) or []))
         if names is not None or not self.has_params:
             self.resolve(names or {})
         cn = (names or {}).get("checks")
@@ -221,10 +245,58 @@ class ScenarioTable:
         fn = (names or {}).get("faults")
         if fn is not None or not self.has_faults:
             self.resolve_faults(fn or {"stacked": [], "non_stacked": [], "stack_size": 1})
-
         an = (names or {}).get("action_faults")
         if an is not None or not self.has_action_faults:
             self.resolve_action_faults(an or [])
+
+    # ---- faults, both kinds: the rows as written, their expansion, packing and the way back
+    def _expand_faults(self, kind: _FaultKind, elements) -> "ScenarioTable":
+        """``getattr(self, kind.key)[s]`` becomes the list of items ``(t0, t1, element, op id, ord, float32 value)`` in listed order:
+        ``elements(who, row)`` gives the elements a row names, in order; ``ord`` is the ordinal of the listed item (its elements
+        share one ``drop`` draw)."""
+        out = []
+        for s, rows in enumerate(getattr(self, kind.rows)):
+            items = []
+            for r, row in enumerate(rows):
+                items += [(row[0], row[1], e, kind.ops[row[-3]], r, np.float32(row[-2]))
+                          for e in elements(f"ScenarioTable: scenario {s}, {kind.noun} {r}", row)]
+            if len(items) > kind.cap:
+                raise ValueError(f"ScenarioTable: scenario {s}: {len(items)} {kind.noun}s after expansion, at most {kind.cap}")
+            out.append(items)
+        setattr(self, kind.key, out)
+        return self
+
+    def _resolved_items(self, kind: _FaultKind) -> list:
+        if getattr(self, kind.key) is None:
+            raise ValueError(f"ScenarioTable: the {kind.what} are not resolved yet: {kind.unresolved}")
+        return getattr(self, kind.key)
+
+    def _pack_fault_items(self, kind: _FaultKind):
+        return _pack_items(self._resolved_items(kind), 2, (np.int32, np.int32, np.int32, np.float32))
+
+    def _faults_from_csr(self, kind: _FaultKind, adr, t, elem, op, ord, value, listed) -> "ScenarioTable":
+        """A table with everything of this one but the faults of ``kind``, which are those the CSR arrays hold, not resolved yet: the
+        items of one ``ord`` become one listed item again.  ``listed(s, i, elements)`` says how: ``(the columns between the times and
+        the index, the elements as indices, whether they are the whole "*")``."""
+        t = np.asarray(t).reshape(-1, 2)
+        scn = self.to_list()
+        if len(adr) != len(scn) + 1:
+            raise ValueError(f"ScenarioTable: {kind.what} for {len(adr) - 1} scenarios, the table has {len(scn)}")
+        for s, sc in enumerate(scn):
+            sc.pop(kind.key, None)
+            rows, i, i1 = [], int(adr[s]), int(adr[s + 1])
+            while i < i1:
+                j = i
+                while j < i1 and int(ord[j]) == int(ord[i]):
+                    j += 1
+                cols, idx, whole = listed(s, i - int(adr[s]), [int(x) for x in elem[i:j]])
+                head = [int(t[i, 0]), int(t[i, 1])] + cols
+                tail = [kind.op_names.get(int(op[i]), int(op[i])), float(np.float32(value[i]))]
+                rows += [head + ["*"] + tail] if whole else [head + [k] + tail for k in idx]
+                i = j
+            if rows:
+                sc[kind.key] = rows
+        return type(self)(scn, self.command_dim)
 
     @property
     def has_action_faults(self) -> bool:
@@ -237,68 +309,37 @@ class ScenarioTable:
         ``ValueError`` naming the scenario and the item: unknown actuator, index out of range, more than 256 items."""
         actuators = list(actuators)
         nu = len(actuators)
-        out = []
-        for s, rows in enumerate(self.action_fault_rows):
-            items = []
-            for r, (t0, t1, index, op, value, _) in enumerate(rows):
-                who = f"ScenarioTable: scenario {s}, action-fault item {r}"
-                if index == "*":
-                    idx = list(range(nu))
-                elif isinstance(index, str):
-                    idx = [i for i, n in enumerate(actuators) if n == index]
-                    if not idx:
-                        raise ValueError(f"{who}: unknown actuator '{index}' (the model has {', '.join(map(str, actuators)) or 'none'})")
-                else:
-                    if not 0 <= index < nu:
-                        raise ValueError(f"{who}: index {index} out of range: the model has {nu} actuators")
-                    idx = [index]
-                items += [(t0, t1, j, ACTION_FAULT_OPS[op], r, np.float32(value)) for j in idx]
-            if len(items) > MAX_ACTION_FAULT_ITEMS:
-                raise ValueError(f"ScenarioTable: scenario {s}: {len(items)} action-fault items after expansion, at most {MAX_ACTION_FAULT_ITEMS}")
-            out.append(items)
-        self.action_faults = out
-        return self
 
-    def _resolved_action_faults(self):
-        if self.action_faults is None:
-            raise ValueError("ScenarioTable: the action faults are not resolved yet: pass names={'action_faults': [actuator names]} or call "
-                             "resolve_action_faults")
-        return self.action_faults
+        def elements(who, row):
+            index = row[2]
+            if index == "*":
+                return list(range(nu))
+            if isinstance(index, str):
+                idx = [i for i, n in enumerate(actuators) if n == index]
+                if not idx:
+                    raise ValueError(f"{who}: unknown actuator '{index}' (the model has {', '.join(map(str, actuators)) or 'none'})")
+                return idx
+            if not 0 <= index < nu:
+                raise ValueError(f"{who}: index {index} out of range: the model has {nu} actuators")
+            return [index]
+        return self._expand_faults(_ACTION_FAULTS, elements)
 
     @property
     def n_action_fault_items(self) -> int:
-        return sum(len(f) for f in self._resolved_action_faults())
+        return sum(len(f) for f in self._resolved_items(_ACTION_FAULTS))
 
     def pack_action_faults(self):
         """``(adr int32[S + 1], t int32[n, 2], actuator int32[n], op int32[n], ord int32[n], value float32[n])``: the expanded items in
         the CSR form ``Engine.scenario_action_faults_set`` sends through ``cosim_set_param "action_faults"``."""
-        return _pack_items(self._resolved_action_faults(), 2, (np.int32, np.int32, np.int32, np.float32))
+        return self._pack_fault_items(_ACTION_FAULTS)
 
     def action_faults_from_csr(self, adr, t, elem, op, ord, value, actuators) -> "ScenarioTable":
         """A table with everything of this one but the action faults, which are those the CSR arrays of ``pack_action_faults`` hold:
         the items of one ``ord`` become one listed item again (``"*"`` if they cover every actuator, else one item per actuator),
         resolved against ``actuators``."""
-        t = np.asarray(t).reshape(-1, 2)
-        actuators = list(actuators)
-        nu = len(actuators)
-        scn = self.to_list()
-        if len(adr) != len(scn) + 1:
-            raise ValueError(f"ScenarioTable: action faults for {len(adr) - 1} scenarios, the table has {len(scn)}")
-        for s, sc in enumerate(scn):
-            sc.pop("action_faults", None)
-            rows, i, i1 = [], int(adr[s]), int(adr[s + 1])
-            while i < i1:
-                j = i
-                while j < i1 and int(ord[j]) == int(ord[i]):
-                    j += 1
-                whole = nu > 1 and [int(x) for x in elem[i:j]] == list(range(nu))
-                head = [int(t[i, 0]), int(t[i, 1])]
-                tail = [_ACTION_FAULT_OP_NAMES.get(int(op[i]), int(op[i])), float(np.float32(value[i]))]
-                rows += [head + ["*"] + tail] if whole else [head + [int(elem[k])] + tail for k in range(i, j)]
-                i = j
-            if rows:
-                sc["action_faults"] = rows
-        return type(self)(scn, self.command_dim).resolve_action_faults(actuators)
+        nu = len(list(actuators))
+        listed = lambda s, i, elems: ([], elems, nu > 1 and elems == list(range(nu)))   # noqa: E731
+        return self._faults_from_csr(_ACTION_FAULTS, adr, t, elem, op, ord, value, listed).resolve_action_faults(actuators)
 
     @property
     def has_faults(self) -> bool:
@@ -314,76 +355,45 @@ class ScenarioTable:
             for n, d in lst:
                 first.setdefault(n, (e, int(d), stacked))
                 e += int(d)
-        out = []
-        for s, rows in enumerate(self.fault_rows):
-            items = []
-            for r, (t0, t1, obs, index, op, value, _) in enumerate(rows):
-                who = f"ScenarioTable: scenario {s}, fault item {r}"
-                if obs not in first:
-                    raise ValueError(f"{who}: unknown observation '{obs}' (the env observes {', '.join(first) or 'nothing'})")
-                e0, dim, stacked = first[obs]
-                if op in ("hold", "drop") and (not stacked or int(names["stack_size"]) < 2):
-                    raise ValueError(f"{who}: op '{op}' on '{obs}' needs a stacked observation and stack_size >= 2: there is no previous "
-                                     "frame in the record")
-                if index == "*":
-                    idx = list(range(dim))
-                else:
-                    if not 0 <= index < dim:
-                        raise ValueError(f"{who}: index {index} out of range: '{obs}' has {dim} entries")
-                    idx = [index]
-                items += [(t0, t1, e0 + i, FAULT_OPS[op], r, np.float32(value)) for i in idx]
-            if len(items) > MAX_FAULT_ITEMS:
-                raise ValueError(f"ScenarioTable: scenario {s}: {len(items)} fault items after expansion, at most {MAX_FAULT_ITEMS}")
-            out.append(items)
-        self.faults = out
-        return self
 
-    def _resolved_faults(self):
-        if self.faults is None:
-            raise ValueError("ScenarioTable: the faults are not resolved yet: pass names={'faults': fault_names(...)} or call resolve_faults")
-        return self.faults
+        def elements(who, row):
+            obs, index, op = row[2:5]
+            if obs not in first:
+                raise ValueError(f"{who}: unknown observation '{obs}' (the env observes {', '.join(first) or 'nothing'})")
+            e0, dim, stacked = first[obs]
+            if op in ("hold", "drop") and (not stacked or int(names["stack_size"]) < 2):
+                raise ValueError(f"{who}: op '{op}' on '{obs}' needs a stacked observation and stack_size >= 2: there is no previous "
+                                 "frame in the record")
+            if index != "*" and not 0 <= index < dim:
+                raise ValueError(f"{who}: index {index} out of range: '{obs}' has {dim} entries")
+            return [e0 + i for i in (range(dim) if index == "*" else [index])]
+        return self._expand_faults(_OBS_FAULTS, elements)
 
     @property
     def n_fault_items(self) -> int:
-        return sum(len(f) for f in self._resolved_faults())
+        return sum(len(f) for f in self._resolved_items(_OBS_FAULTS))
 
     def pack_faults(self):
         """``(adr int32[S + 1], t int32[n, 2], elem int32[n], op int32[n], ord int32[n], value float32[n])``: the expanded items in
         the CSR form ``Engine.scenario_faults_set`` sends through ``cosim_set_param "obs_faults"``."""
-        return _pack_items(self._resolved_faults(), 2, (np.int32, np.int32, np.int32, np.float32))
+        return self._pack_fault_items(_OBS_FAULTS)
 
     def faults_from_csr(self, adr, t, elem, op, ord, value, names: dict) -> "ScenarioTable":
         """A table with everything of this one but the faults, which are those the CSR arrays of ``pack_faults`` hold: the items of
         one ``ord`` become one listed item again (``"*"`` if they cover the observation, else one item per element), resolved
         against ``names`` (``fault_names``)."""
-        t = np.asarray(t).reshape(-1, 2)
-        scn = self.to_list()
-        if len(adr) != len(scn) + 1:
-            raise ValueError(f"ScenarioTable: faults for {len(adr) - 1} scenarios, the table has {len(scn)}")
         spans, e = [], 0
         for n, d in list(names["stacked"]) + list(names["non_stacked"]):
             spans.append((n, e, int(d)))
             e += int(d)
-        for s, sc in enumerate(scn):
-            sc.pop("faults", None)
-            rows, i, i1 = [], int(adr[s]), int(adr[s + 1])
-            while i < i1:
-                j = i
-                while j < i1 and int(ord[j]) == int(ord[i]):
-                    j += 1
-                e0 = int(elem[i])
-                span = [sp for sp in spans if sp[1] <= e0 < sp[1] + sp[2]]
-                if not span:
-                    raise ValueError(f"ScenarioTable: scenario {s}, fault item {i - int(adr[s])}: element {e0} outside the frame")
-                n, first, d = span[0]
-                whole = j - i == d and [int(x) for x in elem[i:j]] == list(range(first, first + d)) and d > 1
-                head = [int(t[i, 0]), int(t[i, 1]), n]
-                tail = [_FAULT_OP_NAMES.get(int(op[i]), int(op[i])), float(np.float32(value[i]))]
-                rows += [head + ["*"] + tail] if whole else [head + [int(elem[k]) - first] + tail for k in range(i, j)]
-                i = j
-            if rows:
-                sc["faults"] = rows
-        return type(self)(scn, self.command_dim).resolve_faults(names)
+
+        def listed(s, i, elems):
+            span = [sp for sp in spans if sp[1] <= elems[0] < sp[1] + sp[2]]
+            if not span:
+                raise ValueError(f"ScenarioTable: scenario {s}, fault item {i}: element {elems[0]} outside the frame")
+            n, first, d = span[0]
+            return [n], [k - first for k in elems], d > 1 and elems == list(range(first, first + d))
+        return self._faults_from_csr(_OBS_FAULTS, adr, t, elem, op, ord, value, listed).resolve_faults(names)
 
     @property
     def has_curves(self) -> bool:
@@ -533,14 +543,10 @@ class ScenarioTable:
             if rows:
                 sc["curves"] = [[t0, t1, every, signal, index, float(lo), float(hi), bins] + ([name] if name is not None else [])
                                 for t0, t1, every, signal, index, lo, hi, bins, name in rows]
-        for sc, rows in zip(out, self.fault_rows):
-            if rows:
-                sc["faults"] = [[t0, t1, obs, index, op, float(value)] + ([name] if name is not None else [])
-                                for t0, t1, obs, index, op, value, name in rows]
-        for sc, rows in zip(out, self.action_fault_rows):
-            if rows:
-                sc["action_faults"] = [[t0, t1, index, op, float(value)] + ([name] if name is not None else [])
-                                       for t0, t1, index, op, value, name in rows]
+        for kind in FAULT_KINDS:
+            for sc, rows in zip(out, getattr(self, kind.rows)):
+                if rows:
+                    sc[kind.key] = [[*row[:-2], float(row[-2])] + ([row[-1]] if row[-1] is not None else []) for row in rows]
         return out
 
     def pack(self):
@@ -613,25 +619,25 @@ def _param_windows(s: int, rows) -> list:
     return out
 
 
-def _fault_rows(s: int, rows) -> list:
-    """The ``"faults"`` rows of scenario ``s``, checked for everything that needs no observation config: ``(t0, t1, obs, index, op,
-    value, name or None)``.  The messages are those of ``_param_windows``."""
-    out = []
+def _fault_kind_rows(kind: _FaultKind, s: int, rows) -> list:
+    """The rows of ``kind`` of scenario ``s``, checked for everything that needs no observation config and no model: the columns of
+    ``kind.keys`` and ``name or None``.  The messages are those of ``_param_windows``."""
+    out, keys = [], kind.keys
     if not isinstance(rows, (list, tuple)):
-        raise ValueError(f"ScenarioTable: scenario {s}: 'faults' must be a list of items, got {rows!r}")
+        raise ValueError(f"ScenarioTable: scenario {s}: '{kind.key}' must be a list of items, got {rows!r}")
     for r, row in enumerate(rows):
-        who = f"ScenarioTable: scenario {s}, fault item {r}"
+        who = f"ScenarioTable: scenario {s}, {kind.noun} {r}"
         name = None
         if isinstance(row, dict):
-            if set(row) - set(_FAULT_KEYS) - {"name"} or any(k not in row for k in _FAULT_KEYS if k not in ("index", "value")):
-                raise ValueError(f"{who}: a mapping with the keys {', '.join(_FAULT_KEYS)} (and 'name') is expected, got {row!r}")
+            if set(row) - set(keys) - {"name"} or any(k not in row for k in keys if k not in ("index", "value")):
+                raise ValueError(f"{who}: a mapping with the keys {', '.join(keys)} (and 'name') is expected, got {row!r}")
             name = row.get("name")
-            row = [row.get(k, {"index": "*"}.get(k, 0.0)) for k in _FAULT_KEYS]
-        elif isinstance(row, (list, tuple)) and len(row) == 7:
-            row, name = list(row[:6]), row[6]
-        if not isinstance(row, (list, tuple)) or len(row) != 6:
-            raise ValueError(f"{who}: expected [t0, t1, obs, index, op, value] and an optional name, got {row!r}")
-        t0, t1, obs, index, op, value = row
+            row = [row.get(k, {"index": "*"}.get(k, 0.0)) for k in keys]
+        elif isinstance(row, (list, tuple)) and len(row) == len(keys) + 1:
+            row, name = list(row[:-1]), row[-1]
+        if not isinstance(row, (list, tuple)) or len(row) != len(keys):
+            raise ValueError(f"{who}: expected [{', '.join(keys)}] and an optional name, got {row!r}")
+        (t0, t1), (index, op, value) = row[:2], row[-3:]
         try:
             t0f, t1f, value = float(t0), float(t1), float(value)
         except (TypeError, ValueError):
@@ -642,66 +648,23 @@ def _fault_rows(s: int, rows) -> list:
             raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
         if t1f <= t0f:
             raise ValueError(f"{who}: t1 {int(t1f)} is not after t0 {int(t0f)}")
-        if obs == "command":
+        if "obs" in keys and row[2] == "command":
             raise ValueError(f"{who}: observation 'command' is refused: the command words are the scenario's keyframes ('commands')")
-        if not isinstance(obs, str):
-            raise ValueError(f"{who}: obs must be the name of an observation, got {obs!r}")
-        if op not in FAULT_OPS:
-            raise ValueError(f"{who}: unknown op {op!r} (one of {', '.join(FAULT_OPS)})")
-        if op == "noise" and value < 0:
-            raise ValueError(f"{who}: a noise amplitude must be >= 0, got {value!r}")
-        if op == "drop" and not 0.0 <= value <= 1.0:
-            raise ValueError(f"{who}: a drop probability must lie in [0, 1], got {value!r}")
-        if isinstance(index, (bool, float)) or not (isinstance(index, (int, np.integer)) or index == "*"):
-            raise ValueError(f"{who}: index must be an int or '*', got {index!r}")
-        if name is not None and not isinstance(name, str):
-            raise ValueError(f"{who}: the name must be a string, got {name!r}")
-        out.append((int(t0f), int(t1f), obs, index if isinstance(index, str) else int(index), op, value, name))
-    return out
-
-
-def _action_fault_rows(s: int, rows) -> list:
-    """The ``"action_faults"`` rows of scenario ``s``, checked for everything that needs no model: ``(t0, t1, index, op, value, name or
-    None)``.  The messages are those of ``_fault_rows``."""
-    out = []
-    if not isinstance(rows, (list, tuple)):
-        raise ValueError(f"ScenarioTable: scenario {s}: 'action_faults' must be a list of items, got {rows!r}")
-    for r, row in enumerate(rows):
-        who = f"ScenarioTable: scenario {s}, action-fault item {r}"
-        name = None
-        if isinstance(row, dict):
-            if set(row) - set(_ACTION_FAULT_KEYS) - {"name"} or any(k not in row for k in _ACTION_FAULT_KEYS if k not in ("index", "value")):
-                raise ValueError(f"{who}: a mapping with the keys {', '.join(_ACTION_FAULT_KEYS)} (and 'name') is expected, got {row!r}")
-            name = row.get("name")
-            row = [row.get(k, {"index": "*"}.get(k, 0.0)) for k in _ACTION_FAULT_KEYS]
-        elif isinstance(row, (list, tuple)) and len(row) == 6:
-            row, name = list(row[:5]), row[5]
-        if not isinstance(row, (list, tuple)) or len(row) != 5:
-            raise ValueError(f"{who}: expected [t0, t1, index, op, value] and an optional name, got {row!r}")
-        t0, t1, index, op, value = row
-        try:
-            t0f, t1f, value = float(t0), float(t1), float(value)
-        except (TypeError, ValueError):
-            raise ValueError(f"{who}: times and value must be numbers, got {row!r}") from None
-        if not math.isfinite(value) or abs(value) > float(np.finfo(np.float32).max):   # (finite as float32 too)
-            raise ValueError(f"{who}: non-finite value")
-        if not (math.isfinite(t0f) and math.isfinite(t1f)) or t0f != int(t0f) or t1f != int(t1f) or not 0 <= t0f < MAX_TIME or not 0 <= t1f <= MAX_TIME:
-            raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
-        if t1f <= t0f:
-            raise ValueError(f"{who}: t1 {int(t1f)} is not after t0 {int(t0f)}")
-        if not isinstance(op, str) or op not in ACTION_FAULT_OPS:
-            raise ValueError(f"{who}: unknown op {op!r} (one of {', '.join(ACTION_FAULT_OPS)})")
+        if "obs" in keys and not isinstance(row[2], str):
+            raise ValueError(f"{who}: obs must be the name of an observation, got {row[2]!r}")
+        if not isinstance(op, str) or op not in kind.ops:
+            raise ValueError(f"{who}: unknown op {op!r} (one of {', '.join(kind.ops)})")
         if op == "noise" and value < 0:
             raise ValueError(f"{who}: a noise amplitude must be >= 0, got {value!r}")
         if op == "clip" and value < 0:
             raise ValueError(f"{who}: a clip bound must be >= 0, got {value!r}")
         if op == "drop" and not 0.0 <= value <= 1.0:
             raise ValueError(f"{who}: a drop probability must lie in [0, 1], got {value!r}")
-        if isinstance(index, (bool, float)) or not isinstance(index, (int, np.integer, str)):
-            raise ValueError(f"{who}: index must be an int, an actuator name or '*', got {index!r}")
+        if isinstance(index, (bool, float)) or not (isinstance(index, (int, np.integer)) or (isinstance(index, str) and (kind.named or index == "*"))):
+            raise ValueError(f"{who}: index must be {kind.index}, got {index!r}")
         if name is not None and not isinstance(name, str):
             raise ValueError(f"{who}: the name must be a string, got {name!r}")
-        out.append((int(t0f), int(t1f), index if isinstance(index, str) else int(index), op, value, name))
+        out.append((int(t0f), int(t1f), *row[2:-3], index if isinstance(index, str) else int(index), op, value, name))
     return out
 
 
@@ -980,6 +943,28 @@ def reference_params(table: ScenarioTable, mode, gid, t, ep, base_params, layout
     return eff
 
 
+def _fault_op(name: str, el: int, ordinal: int, value, x, prev, first, draw) -> np.ndarray:
+    """One holding item ``name`` on the words ``x`` ``[M]`` of element ``el`` of M envs, float32, as ``fault_op`` / ``fault_walk``
+    (csrc/cosim_fault.h) compute it: ``prev`` ``[M]`` the previous words, ``first`` ``[M]`` bool the envs at clock 0 (hold and drop are
+    the identity there), ``draw(index)`` the envs' Philox words of the kind's purpose."""
+    from . import rng
+    v = np.float32(value)
+    if name == "scale":
+        x = x * v
+    elif name == "bias":
+        x = x + v
+    elif name == "set":
+        x = np.full_like(x, v)
+    elif name == "noise":
+        x = x + (v * rng.fault_noise_u(draw(el))).astype(np.float32)
+    elif name == "clip":
+        x = np.where(x > v, v, np.where(x < -v, -v, x))
+    else:                                                           # hold / drop: one draw for the listed item
+        lost = rng.fault_drop_u(draw(rng.FAULT_DROP_INDEX + ordinal)) < v if name == "drop" else True
+        x = np.where(lost & ~first, prev, x)
+    return x.astype(np.float32)
+
+
 def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count, seed: int, frames, layout: dict, active=None) -> np.ndarray:
     """Numpy twin of ``obsfault_step_kernel`` over a run of K observations of N envs, exact.  ``gid`` ``[N]`` global ids; per
     observation k the POST-step meta words ``t_obs[k]`` (word 0), ``ep[k]`` (word 11) and ``step_count[k]`` (word 1), each ``[K, N]``;
@@ -997,7 +982,7 @@ def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count,
     active = np.ones((K, N), dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(K, N)
     cmd = np.zeros(sd, dtype=bool)
     cmd[[e for e in layout.get("command", []) if e < sd]] = True
-    items = table._resolved_faults()
+    items = table._resolved_items(_OBS_FAULTS)
     stack = np.full((N, S, sd), np.nan, dtype=np.float32)
     out = np.full((K, N, S * sd + fd - sd), np.nan, dtype=np.float32)
     u32 = np.uint32
@@ -1016,25 +1001,8 @@ def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count,
                 if not m.any():
                     continue
                 x = stack[m, 0, e] if e < sd else tail[m, e - sd]
-                name = _FAULT_OP_NAMES[op]
-                if name == "drop":
-                    lost = rng.fault_drop_u(rng.first_word(seed, gid[m].astype(np.uint64), step_count[k, m].astype(u32),
-                                                           rng.PURPOSE_OBS_FAULT, rng.FAULT_DROP_INDEX + ordinal)) < np.float32(value)
-                else:
-                    lost = np.ones(int(m.sum()), dtype=bool)
-                if name == "scale":
-                    x = x * np.float32(value)
-                elif name == "bias":
-                    x = x + np.float32(value)
-                elif name == "set":
-                    x = np.full_like(x, np.float32(value))
-                elif name == "noise":
-                    u = rng.fault_noise_u(rng.first_word(seed, gid[m].astype(np.uint64), step_count[k, m].astype(u32), rng.PURPOSE_OBS_FAULT, e))
-                    x = x + (np.float32(value) * u).astype(np.float32)
-                else:                                               # hold / drop: the previous frame, but for a fill
-                    take = lost & (t_obs[k, m] > 0)
-                    x = np.where(take, stack[m, 1, e], x)
-                x = x.astype(np.float32)
+                draw = lambda index: rng.first_word(seed, gid[m].astype(np.uint64), step_count[k, m].astype(u32), rng.PURPOSE_OBS_FAULT, index)   # noqa: E731
+                x = _fault_op(_OBS_FAULTS.op_names[op], e, ordinal, value, x, stack[m, 1, e] if e < sd and S > 1 else x, t_obs[k, m] == 0, draw)
                 if e >= sd:
                     tail[m, e - sd] = x
                 else:
@@ -1061,7 +1029,7 @@ def reference_action_faults(table: ScenarioTable, mode, gid, t, ep, step_count, 
     prev = np.ascontiguousarray(prev_eff, dtype=np.float32).reshape(N, -1)
     t, ep, step_count = (np.asarray(a).reshape(N) for a in (t, ep, step_count))
     eff = raw.copy()
-    items = table._resolved_action_faults()
+    items = table._resolved_items(_ACTION_FAULTS)
     row = scenario_rows(len(table), mode, gid, ep)
     u32 = np.uint32
     for r in np.unique(row):
@@ -1069,27 +1037,8 @@ def reference_action_faults(table: ScenarioTable, mode, gid, t, ep, step_count, 
             m = (row == r) & (t0 <= t) & (t < t1)
             if not m.any():
                 continue
-            x = eff[m, j]
-            v = np.float32(value)
-            name = _ACTION_FAULT_OP_NAMES[op]
-            if name == "scale":
-                x = x * v
-            elif name == "bias":
-                x = x + v
-            elif name == "set":
-                x = np.full_like(x, v)
-            elif name == "noise":
-                u = rng.fault_noise_u(rng.first_word(seed, gid[m].astype(np.uint64), step_count[m].astype(u32), rng.PURPOSE_ACTION_FAULT, j))
-                x = x + (v * u).astype(np.float32)
-            elif name == "clip":
-                x = np.where(x > v, v, np.where(x < -v, -v, x))
-            else:                                                   # hold / drop: the previous effective action, but at episode step 0
-                lost = np.ones(int(m.sum()), dtype=bool)
-                if name == "drop":
-                    lost = rng.fault_drop_u(rng.first_word(seed, gid[m].astype(np.uint64), step_count[m].astype(u32),
-                                                           rng.PURPOSE_ACTION_FAULT, rng.FAULT_DROP_INDEX + ordinal)) < v
-                x = np.where(lost & (t[m] > 0), prev[m, j], x)
-            eff[m, j] = x.astype(np.float32)
+            draw = lambda index: rng.first_word(seed, gid[m].astype(np.uint64), step_count[m].astype(u32), rng.PURPOSE_ACTION_FAULT, index)   # noqa: E731
+            eff[m, j] = _fault_op(_ACTION_FAULTS.op_names[op], j, ordinal, value, eff[m, j], prev[m, j], t[m] == 0, draw)
     return eff
 
 

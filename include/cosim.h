@@ -393,7 +393,7 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
 int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
 
 /* Observation faults of the scenario table that is set: timed sensor bias, noise, freeze and loss per env, applied on the device to
- * what the policy SEES (cosim_amd/csrc/cosim_obsfault.h has the rule).  They have no entry point of their own: the table travels
+ * what the policy SEES (cosim_amd/csrc/cosim_obsfault.h over cosim_fault.h has the rule).  They have no entry point of their own: the table travels
  * through cosim_set_param(e, "obs_faults", words, count), where `words` points at `count` 32-BIT WORDS, not floats:
  *   S | adr[S + 1] | t[n][2] | elem[n] | op[n] | ord[n] | value[n] (float bits),   n = adr[S],   count = S + 2 + 6 n
  * (int32 but for value); the one word 0 clears the faults.  Scenario s owns the items [adr[s], adr[s + 1]) (at most 256).
@@ -424,7 +424,7 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  * cosim_query "obs_faults" answers the number of items (0: none). */
 
 /* Action faults of the scenario table that is set: timed actuator-command bias, noise, hold and loss per env, applied on the device to
- * what the step kernels are HANDED as the action (cosim_amd/csrc/cosim_actfault.h has the rule).  Like the observation faults they have
+ * what the step kernels are HANDED as the action (cosim_amd/csrc/cosim_actfault.h over cosim_fault.h has the rule).  Like the observation faults they have
  * no entry point of their own: the table travels through cosim_set_param(e, "action_faults", words, count), `words` pointing at `count`
  * 32-BIT WORDS:
  *   S | adr[S + 1] | t[n][2] | elem[n] | op[n] | ord[n] | value[n] (float bits),   n = adr[S],   count = S + 2 + 6 n

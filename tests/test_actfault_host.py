@@ -462,3 +462,163 @@ def test_code_size_of_existing_kernels_is_unchanged():
     assert head_a == head_b and len(a) >= 40
     new = [ln for ln in b if "actfault_" in ln]
     assert len(new) == 2 and [ln for ln in b if ln not in new] == a
+
+
+# ------------------------------------------------------------------------------------------------------------ one core under both kinds
+BOTH_CPP = r"""
+#include <stdio.h>
+#include "cosim_tables.h"
+// in: kind (0 observation, 1 action) width S | adr[S+1] | n x (t0 t1 elem op ord value_bits); out: the refusal (empty line: none).
+// width: nu, or the elements of a frame that is all stacked, two rows deep, and holds no command word
+int main() {
+  long long v; std::vector<long long> w;
+  while (scanf("%lld", &v) == 1) w.push_back(v);
+  size_t k = 0;
+  const int kind = (int)w[k++], width = (int)w[k++], S = (int)w[k++];
+  std::vector<int32_t> adr(S + 1);
+  for (auto& x : adr) x = (int32_t)w[k++];
+  const size_t n = (w.size() - k) / 6;
+  std::vector<int32_t> t(2 * n + 1), elem(n + 1), op(n + 1), ord(n + 1); std::vector<float> value(n + 1);
+  for (size_t i = 0; i < n; i++) {
+    t[2 * i] = (int32_t)w[k++]; t[2 * i + 1] = (int32_t)w[k++]; elem[i] = (int32_t)w[k++]; op[i] = (int32_t)w[k++]; ord[i] = (int32_t)w[k++];
+    const unsigned u = (unsigned)w[k++]; memcpy(&value[i], &u, 4);
+  }
+  const cosim::FltRaw raw = {S, adr.data(), t.data(), elem.data(), op.data(), ord.data(), value.data()};
+  const std::vector<unsigned char> field(width, 0);
+  const cosim::ObsDims dims = {width, width, 2, field.data(), 1};
+  const cosim::FltShape s = kind == 0 ? cosim::validate_faults(dims, raw) : cosim::validate_action_faults(width, raw);
+  printf("%s\n", s.err.c_str());
+  return 0;
+}
+"""
+
+
+@pytest.fixture(scope="module")
+def both_exe(tmp_path_factory):
+    tmp = tmp_path_factory.mktemp("fault_validate_both")
+    src, exe = str(tmp / "both.cpp"), str(tmp / "both")
+    with open(src, "w") as f:
+        f.write(BOTH_CPP)
+    subprocess.check_call([os.environ.get("CXX", "c++"), "-std=c++17", "-O1", "-g", "-Wno-unknown-pragmas", "-fsanitize=address,undefined",
+                           "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "cosim_amd", "csrc"), "-o", exe, src])
+    return exe
+
+
+def _both(exe, kind, adr, items):
+    words = [kind, NU, len(adr) - 1] + list(adr)
+    for t0, t1, e, op, o, v in items:
+        words += [t0, t1, e, op, o, int(np.array(v, dtype=f32).view(np.uint32))]
+    p = subprocess.run([exe], input=" ".join(str(w) for w in words), capture_output=True, text=True)
+    assert p.returncode == 0, p.stderr[-2000:]
+    return p.stdout.split("\n")[0]
+
+
+_OK = (0, 5, 1, 1, 0, 0.5)
+MALFORMED_TABLES = {
+    "bad window": ([0, 1, 2], [_OK, (5, 5, 0, 1, 0, 0.5)]),
+    "negative time": ([0, 1, 2], [_OK, (-1, 5, 0, 1, 0, 0.5)]),
+    "non-finite value": ([0, 1, 2], [_OK, (0, 5, 0, 2, 0, np.nan)]),
+    "negative noise": ([0, 1, 2], [_OK, (0, 5, 0, 3, 0, -0.5)]),
+    "drop above 1": ([0, 1, 2], [_OK, (0, 5, 0, 5, 0, 1.5)]),
+    "drop below 0": ([0, 1, 2], [_OK, (0, 5, 0, 5, 0, -0.5)]),
+    "ordinal 256": ([0, 1, 2], [_OK, (0, 5, 0, 1, 256, 0.5)]),
+    "257 items": ([0, 257], [_OK] * 257),
+    "decreasing addresses": ([0, 2, 1], [_OK, _OK]),
+    "adr[0] not 0": ([1, 2], [_OK, _OK]),
+    "empty table": ([0, 0, 0], []),
+}
+
+
+@pytest.mark.parametrize("case", sorted(MALFORMED_TABLES))
+def test_both_validators_refuse_the_same_rows_in_the_same_words(both_exe, case):
+    """validate_faults and validate_action_faults (csrc/cosim_tables.h) are entry points of one core: a table that is malformed in a
+    way that is no kind's own is refused by both, in the same words but for the setter's name and the noun."""
+    adr, items = MALFORMED_TABLES[case]
+    obs, act = _both(both_exe, 0, adr, items), _both(both_exe, 1, adr, items)
+    assert obs.startswith('cosim_set_param "obs_faults": ') and act.startswith('cosim_set_param "action_faults": ')
+    assert "action" not in obs
+    assert act.replace('cosim_set_param "action_faults"', 'cosim_set_param "obs_faults"').replace("action-fault item", "fault item") == obs
+    assert _both(both_exe, 0, [0, 1], [_OK]) == "" and _both(both_exe, 1, [0, 1], [_OK]) == ""
+
+
+MALFORMED_ROWS = {
+    "value no number": [0, 1, 0, "bias", "much"],
+    "nan": [0, 1, 0, "bias", float("nan")],
+    "inf as float32": [0, 1, 0, "set", 1e39],
+    "fractional time": [0.5, 1, 0, "bias", 1.0],
+    "negative time": [-1, 1, 0, "bias", 1.0],
+    "bad window": [5, 5, 0, "bias", 1.0],
+    "negative noise": [0, 1, 0, "noise", -0.1],
+    "drop above 1": [0, 1, 0, "drop", 1.5],
+    "drop below 0": [0, 1, 0, "drop", -0.5],
+    "float index": [0, 1, 1.0, "bias", 1.0],
+    "bool index": [0, 1, True, "bias", 1.0],
+    "name no string": [0, 1, 0, "bias", 1.0, 7],
+    "op no string": [0, 1, 0, 3, 1.0],
+}
+
+
+@pytest.mark.parametrize("case", sorted(MALFORMED_ROWS))
+def test_both_kinds_of_row_are_refused_in_the_same_words(case):
+    """The one row checker of cosim_amd/scenario.py under "faults" and "action_faults": the same malformed row, with and without the
+    obs column, is refused in the same words but for the noun, what an index may be, the op list and the echo of the row."""
+    from cosim_amd.scenario import ScenarioTable
+    row = MALFORMED_ROWS[case]
+    msg = {}
+    for key, r in (("action_faults", row), ("faults", row[:2] + ["ang_vel"] + row[2:])):
+        with pytest.raises(ValueError) as err:
+            ScenarioTable([{}, {key: [r]}], CD)
+        msg[key] = str(err.value).split(", got ")[0].split(" (one of ")[0]
+    assert msg["action_faults"].startswith("ScenarioTable: scenario 1, action-fault item 0: ")
+    assert msg["action_faults"].replace("action-fault item", "fault item").replace("an int, an actuator name or '*'", "an int or '*'") == msg["faults"]
+
+
+def test_clip_stays_an_action_op(both_exe):
+    """Op 6 is the actions' alone: the observation validator and the "faults" rows refuse it in the words they had."""
+    from cosim_amd.scenario import ACTION_FAULT_OPS, FAULT_OPS, ScenarioTable
+    assert "clip" not in FAULT_OPS and ACTION_FAULT_OPS["clip"] == 6 and {k: ACTION_FAULT_OPS[k] for k in FAULT_OPS} == FAULT_OPS
+    assert _both(both_exe, 0, [0, 1], [(0, 5, 0, 6, 0, 0.25)]) == ('cosim_set_param "obs_faults": scenario 0, fault item 0: unknown op 6 '
+                                                                  "(0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop)")
+    assert _both(both_exe, 1, [0, 1], [(0, 5, 0, 6, 0, 0.25)]) == ""
+    with pytest.raises(ValueError, match=r"scenario 0, fault item 0: unknown op 'clip' \(one of scale, bias, set, noise, hold, drop\)"):
+        ScenarioTable([{"faults": [[0, 1, "ang_vel", 0, "clip", 0.25]]}], CD)
+    with pytest.raises(ValueError, match=r"scenario 0, fault item 0: unknown op 6 \(one of scale, bias, set, noise, hold, drop\)"):
+        ScenarioTable([{"faults": [[0, 1, "ang_vel", 0, 6, 0.25]]}], CD)
+
+
+# ------------------------------------------------------------------------------------------------------------ the shared walk: resources, code size
+FAULT_KERNELS = ("obsfault_step_kernel", "actfault_step_kernel", "actfault_obs_kernel")
+
+
+def test_shared_walk_keeps_the_fault_kernels_resources_and_changes_no_other_kernel():
+    """tools/kres.py of the parent (profiles/actfault_kres_this.txt) and with the walk shared (fault_core_kres_this.txt): every other
+    kernel's line is identical, in the same order; the three fault kernels keep 0 AGPRs, spills, scratch and LDS and occupancy 8, with
+    no more VGPRs than the parent's build."""
+    head_a, a = _table_file("actfault_kres_this.txt")
+    head_b, b = _table_file("fault_core_kres_this.txt")
+    other = lambda lines: [ln for ln in lines if ln.split("(")[0] not in FAULT_KERNELS]   # noqa: E731
+    assert head_a == head_b and len(a) >= 40 and other(a) == other(b)
+    assert [ln.split("(")[0] for ln in a] == [ln.split("(")[0] for ln in b]
+    res = lambda lines: {ln.split("(")[0]: [int(x) for x in re.split(r"\s+", ln.strip())[-7:]] for ln in lines if ln.split("(")[0] in FAULT_KERNELS}   # noqa: E731
+    before, after = res(a), res(b)
+    assert sorted(before) == sorted(after) == sorted(FAULT_KERNELS)
+    for name in FAULT_KERNELS:
+        vgpr, agpr, sspill, vspill, scratch, occ, lds = after[name]
+        print(name, "VGPRs", before[name][0], "->", vgpr)
+        assert (agpr, sspill, vspill, scratch, lds) == (0, 0, 0, 0, 0) and occ == 8 and vgpr <= before[name][0], name
+
+
+def test_shared_walk_adds_no_code_bytes():
+    """tools/ksize.py --lib of the parent (profiles/actfault_ksize_this.txt) and with the walk shared (fault_core_ksize_this.txt): every
+    other kernel has the bytes it had, in the same order; no fault kernel has more code bytes than in the parent's build."""
+    head_a, a = _table_file("actfault_ksize_this.txt")
+    head_b, b = _table_file("fault_core_ksize_this.txt")
+    is_fault = lambda ln: any(k + "(" in ln for k in FAULT_KERNELS)   # noqa: E731
+    assert head_a == head_b and len(a) >= 40
+    assert [ln for ln in a if not is_fault(ln)] == [ln for ln in b if not is_fault(ln)]
+    size = lambda lines: {ln.split()[1].split("(")[0]: int(ln.split()[0]) for ln in lines if is_fault(ln)}   # noqa: E731
+    before, after = size(a), size(b)
+    assert sorted(before) == sorted(after) == sorted(FAULT_KERNELS)
+    for name in FAULT_KERNELS:
+        print(name, "bytes", before[name], "->", after[name])
+        assert after[name] <= before[name], name

@@ -470,6 +470,79 @@ def test_a_hold_fault_on_last_action_composes_on_the_restored_value():
     a.close(); b.close()
 
 
+# ------------------------------------------------------------------------------------------------------------ 4b: the shared walk's chunk edges
+def test_chunk_edges_of_the_shared_walk_under_both_kinds():
+    """Rows of 1, 4 and 5 expanded items of EACH kind (csrc/cosim_fault.h fetches FLT_CHUNK = 4 records at a time: one row is a
+    chunk, one a part of one, one a chunk and a part, and that one lies last, so its second fetch reads the array's zero padding),
+    6 envs in mode cycle from env_id0 = 7, 12 steps with the time limit in episode step 8: clock 0, a reset's fill and a changed row
+    all occur.  C runs the action faults alone: its effective actions are the action twin's, its observations the frames the
+    observation twin starts from.  Everything expected of A, which runs both kinds, is computed from them on the host before A takes
+    a step; every item is in force somewhere in it."""
+    from cosim_amd.scenario import fault_layout, reference_action_faults, reference_obs_faults, scenario_rows
+    cfg, cm = _model("flamingo_light_v1", "flat", max_duration=0.16)
+    n, steps, id0 = 6, 12, 7
+    scn = [
+        {"action_faults": [[2, 7, 2, "bias", 0.1]],
+         "faults": [[1, 6, "ang_vel", 0, "bias", 0.05]]},
+        {"action_faults": [[0, 8, 0, "noise", 0.1], [1, 8, 1, "drop", 0.6], [3, 8, 2, "hold", 0.0], [0, 5, 3, "scale", -1.0]],
+         "faults": [[0, 9, "ang_vel", 0, "noise", 0.05], [3, 9, "ang_vel", 1, "hold", 0.0], [1, 5, "ang_vel", 2, "drop", 0.6],
+                    [2, 4, "last_action", 1, "bias", 0.5]]},
+        {"action_faults": [[1, 8, "*", "drop", 0.5], [0, 3, 0, "clip", 0.2]],
+         "faults": [[0, 9, "ang_vel", 0, "scale", 2.0], [0, 2, "ang_vel", 1, "set", 0.25], [2, 9, "ang_vel", 2, "drop", 0.5],
+                    [1, 9, "last_action", 0, "hold", 0.0], [4, 7, "last_action", 3, "noise", 0.1]]},
+    ]
+    raw = _actions(n, steps, 4, seed=31)
+    gid = id0 + np.arange(n)
+    only_act = [{k: v for k, v in s.items() if k != "faults"} for s in scn]
+    c = _env(cfg, cm, n, scenarios=only_act, scenario_mode="cycle", env_id0=id0)
+    table = _table(c, scn)
+    assert [len(f) for f in table.action_faults] == [1, 4, 5] and [len(f) for f in table.faults] == [1, 4, 5]
+    lay = fault_layout(c.fault_names())
+    t = c.torch
+    c.reset()
+    pre, post, clean, eff_c = [], [_meta(c)], [c.state.cpu().numpy().copy()], []
+    for k in range(steps):
+        pre.append(_meta(c))
+        c.step(t.tensor(raw[k], device=c.device))
+        t.cuda.synchronize(c.device)
+        eff_c.append(c.effective_action().cpu().numpy().copy()); post.append(_meta(c)); clean.append(c.state.cpu().numpy().copy())
+    c.close()
+    pre, post = np.stack(pre), np.stack(post)
+    assert (post[1:, :, 0] == 0).any() and (pre[:, :, 11] > 0).any(), "no episode ended inside the run"
+    # the action twin, step by step as the record's s_lastact goes
+    prev, want_eff = np.zeros((n, 4), dtype=np.float32), []
+    for k in range(steps):
+        want_eff.append(reference_action_faults(table, "cycle", gid, pre[k, :, 0], pre[k, :, 11], pre[k, :, 1], c.seed, raw[k], prev))
+        prev = want_eff[-1].copy()
+        prev[post[k + 1, :, 0] == 0] = 0.0                          # the step ended the episode: the record holds zeros
+    for k in range(steps):
+        assert np.array_equal(_u(eff_c[k]), _u(want_eff[k])), f"step {k}: effective action of the fleet without observation faults"
+    sd, S = lay["stacked_dim"], lay["stack_size"]
+    frames = np.stack([np.concatenate([s[:, :sd], s[:, S * sd:]], axis=1) for s in clean])
+    want_obs = reference_obs_faults(table, "cycle", gid, post[:, :, 0], post[:, :, 11], post[:, :, 1], c.seed, frames, lay)
+    # every item of either kind is in force on some (env, step): the clocks are the pre-step ones for actions, the observations' own for faults
+    for items, clock, ep in ((table.action_faults, pre[:, :, 0], pre[:, :, 11]), (table.faults, post[:, :, 0], post[:, :, 11])):
+        rows = np.stack([scenario_rows(3, "cycle", gid, e) for e in ep])
+        assert len(np.unique(rows[:, 0])) > 1, "no env changed its row"
+        for r, its in enumerate(items):
+            for i, (t0, t1, *_) in enumerate(its):
+                assert ((rows == r) & (t0 <= clock) & (clock < t1)).any(), f"row {r}, item {i} never holds"
+    assert any((np.stack(want_eff) != raw).any(axis=(1, 2))) and (_u(want_obs) != _u(np.stack(clean))).any()
+    a = _env(cfg, cm, n, scenarios=scn, scenario_mode="cycle", env_id0=id0)
+    assert a.engine.query("action_faults") == 10 and a.engine.query("obs_faults") == 10
+    a.reset()
+    assert np.array_equal(_u(a.state.cpu().numpy()), _u(want_obs[0])), "the reset's observation"
+    for k in range(steps):
+        assert np.array_equal(_meta(a)[:, [0, 1, 11]], pre[k][:, [0, 1, 11]])
+        a.step(t.tensor(raw[k], device=a.device))
+        t.cuda.synchronize(a.device)
+        x, y = _u(a.effective_action().cpu().numpy()), _u(want_eff[k])
+        assert np.array_equal(x, y), f"step {k}: effective action, envs {np.nonzero((x != y).any(axis=1))[0]}"
+        x, y = _u(a.state.cpu().numpy()), _u(want_obs[k + 1])
+        assert np.array_equal(x, y), f"observation {k + 1}: envs {np.nonzero((x != y).any(axis=1))[0]}, words {np.nonzero((x != y).any(axis=0))[0][:12]}"
+    a.close()
+
+
 # ------------------------------------------------------------------------------------------------------------ 5: snapshot
 def test_snapshot_inside_a_hold_window_continues_and_a_fork_follows_its_slot(tmp_path):
     from cosim_amd.scenario import reference_action_faults
