@@ -2622,9 +2622,10 @@ int cosim_event_push(cosim_engine_t* e, const float* v_dev, const uint8_t* mask_
   return COSIM_OK;
 }
 
+static int debug_cholesky(cosim_engine_t* e, int nv, float* io, int capacity);
 int cosim_debug_forward(cosim_engine_t* e, int env, const char* name, float* host_out, int capacity) {
+  if (e && host_out && name && !strcmp(name, "cholesky")) return debug_cholesky(e, env, host_out, capacity);   // no env, no launch of a step kernel
   if (!e || !host_out || env < 0 || env >= e->n_envs) return fail(COSIM_EINVAL, "cosim_debug_forward: bad argument");
-  (void)name;
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
   if (rc) return rc;
@@ -2761,6 +2762,28 @@ int cosim_debug_box_box(cosim_engine_t* e, const float* geo_host, const float* m
       r = out.download(out_host, (size_t)n * 35 * sizeof(float));
   }
   if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_box_box: ") + hipGetErrorString(r));
+  return COSIM_OK;
+}
+
+// cosim_debug_forward "cholesky": both forms of the step kernels' in-register Cholesky and its solve on n matrices of order nv, one per
+// wave.  io holds rows [n][64][nv] and rhs [n][64] on entry, fac [n][2][nv][nv], dinv [n][2][nv] and sol [n][2][nv] on return.
+static int debug_cholesky(cosim_engine_t* e, int nv, float* io, int capacity) {
+  if (nv != 18 && nv != 10 && nv != 7) return fail(COSIM_EINVAL, "cosim_debug_forward cholesky: the order is not 18, 10 or 7");
+  const int per = 64 * (nv + 1), n = capacity / per;
+  if (capacity < per || capacity % per) return fail(COSIM_EINVAL, "cosim_debug_forward cholesky: capacity is not n * 64 * (order + 1)");
+  HIP_TRY(hipSetDevice(e->device));
+  DbgBuf in, out;
+  const size_t nfac = (size_t)n * 2 * nv * nv, nvec = (size_t)n * 2 * nv;   // nfac + 2 nvec < capacity: the answer fits the caller's block
+  hipError_t r;
+  if ((r = in.upload(io, (size_t)capacity * sizeof(float))) == hipSuccess && (r = out.alloc((nfac + 2 * nvec) * sizeof(float))) == hipSuccess &&
+      (r = hipMemset(out.p, 0, (nfac + 2 * nvec) * sizeof(float))) == hipSuccess) {
+    const float *rows = (const float*)in.p, *rhs = rows + (size_t)n * 64 * nv;
+    float *fac = (float*)out.p, *dinv = fac + nfac, *sol = dinv + nvec;
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, 0, rows, rhs, n, fac, dinv, sol); };
+    if (nv == 18) launch(chol_probe_kernel<18>); else if (nv == 10) launch(chol_probe_kernel<10>); else launch(chol_probe_kernel<7>);
+    if ((r = dbg_finish()) == hipSuccess) r = out.download(io, (nfac + 2 * nvec) * sizeof(float));
+  }
+  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_forward cholesky: ") + hipGetErrorString(r));
   return COSIM_OK;
 }
 

@@ -429,20 +429,136 @@ __device__ __forceinline__ void chol_lower(float (&a)[NV], float& dinv, int lane
     }
   }
 }
+// The packed form of the same factorisation (one environment per wave; KTraits::CHOLP picks it).  The row lives in aligned register
+// pairs p[m] = {a[2m], a[2m + 1]} and a pivot stage updates two trailing columns with one v_pk_fma_f32: the pair is destination and
+// addend, -a[J] (the low or the high half of its own pair, picked for both results by op_sel / op_sel_hi) the first multiplicand,
+// and the two broadcasts, read by two v_readlane into an aligned scalar pair, the second.  Each half is the fma(-aj, s, a) of the
+// scalar form: the same bits.  The scalar pairs are named registers (inline assembly cannot address the halves of a 64-bit
+// operand), declared as clobbers.  A chunk is up to four pairs, all its readlanes first: every packed FMA then sits at least two
+// instructions behind the second readlane it reads, which is the wait the scalar form bought with its grouping by four; a chunk of
+// two pairs or one fills it with s_nop.  An odd NV's last column is the low half of a pair whose high half is a garbage slot.
+// Pivot look-ahead: a stage updates column J + 1 on its own first, then the first half of the head of stage J + 1 (broadcast of the
+// pivot, clamp, rsqrt: it reads column J + 1 only) stands in front of the stage's packed updates of columns >= J + 2, which do not
+// read it, and the second half (dinv select, scaling of the column) behind them: the scheduler may fill the head's waits (readlane
+// -> VALU, rsqrt) with the chunks instead of s_nops, and the next pivot does not wait for trailing columns it never reads.  Every
+// value is computed by the operation, from the operands, of the scalar form.
+typedef float chol_pair __attribute__((ext_vector_type(2)));
+#define CHOL_RL(s, i) "v_readlane_b32 " s ", %[aj], %[k" #i "]\n\t"
+#define CHOL_PK(i, s, os) "v_pk_fma_f32 %[d" #i "], %[ajp], " s ", %[d" #i "] " os " neg_lo:[1,0,0] neg_hi:[1,0,0]\n\t"
+#define CHOL_OS_LO "op_sel_hi:[0,1,1]"
+#define CHOL_OS_HI "op_sel:[1,0,0] op_sel_hi:[1,1,1]"
+#define CHOL_CHUNK4(os)                                                                                                                  \
+  asm volatile(CHOL_RL("s88", 0) CHOL_RL("s89", 1) CHOL_RL("s90", 2) CHOL_RL("s91", 3) CHOL_RL("s92", 4) CHOL_RL("s93", 5) CHOL_RL("s94", 6)  \
+               CHOL_RL("s95", 7) CHOL_PK(0, "s[88:89]", os) CHOL_PK(1, "s[90:91]", os) CHOL_PK(2, "s[92:93]", os) CHOL_PK(3, "s[94:95]", os) \
+               : [d0] "+v"(p[M0]), [d1] "+v"(p[M0 + 1]), [d2] "+v"(p[M0 + 2]), [d3] "+v"(p[M0 + 3])                                         \
+               : [ajp] "v"(ajp), [aj] "v"(aj), [k0] "n"(2 * M0), [k1] "n"(2 * M0 + 1), [k2] "n"(2 * M0 + 2), [k3] "n"(2 * M0 + 3),          \
+                 [k4] "n"(2 * M0 + 4), [k5] "n"(2 * M0 + 5), [k6] "n"(2 * M0 + 6), [k7] "n"(2 * M0 + 7)                                     \
+               : "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95")
+#define CHOL_CHUNK3(os)                                                                                                                  \
+  asm volatile(CHOL_RL("s88", 0) CHOL_RL("s89", 1) CHOL_RL("s90", 2) CHOL_RL("s91", 3) CHOL_RL("s92", 4) CHOL_RL("s93", 5)                   \
+               CHOL_PK(0, "s[88:89]", os) CHOL_PK(1, "s[90:91]", os) CHOL_PK(2, "s[92:93]", os)                                             \
+               : [d0] "+v"(p[M0]), [d1] "+v"(p[M0 + 1]), [d2] "+v"(p[M0 + 2])                                                               \
+               : [ajp] "v"(ajp), [aj] "v"(aj), [k0] "n"(2 * M0), [k1] "n"(2 * M0 + 1), [k2] "n"(2 * M0 + 2), [k3] "n"(2 * M0 + 3),          \
+                 [k4] "n"(2 * M0 + 4), [k5] "n"(2 * M0 + 5)                                                                                 \
+               : "s88", "s89", "s90", "s91", "s92", "s93")
+#define CHOL_CHUNK2(os)                                                                                                                  \
+  asm volatile(CHOL_RL("s88", 0) CHOL_RL("s89", 1) CHOL_RL("s90", 2) CHOL_RL("s91", 3) CHOL_PK(0, "s[88:89]", os) "s_nop 0\n\t"            \
+               CHOL_PK(1, "s[90:91]", os)                                                                                                  \
+               : [d0] "+v"(p[M0]), [d1] "+v"(p[M0 + 1])                                                                                     \
+               : [ajp] "v"(ajp), [aj] "v"(aj), [k0] "n"(2 * M0), [k1] "n"(2 * M0 + 1), [k2] "n"(2 * M0 + 2), [k3] "n"(2 * M0 + 3)           \
+               : "s88", "s89", "s90", "s91")
+#define CHOL_CHUNK1(os)                                                                                                                  \
+  asm volatile(CHOL_RL("s88", 0) CHOL_RL("s89", 1) "s_nop 1\n\t" CHOL_PK(0, "s[88:89]", os)                                                \
+               : [d0] "+v"(p[M0]) : [ajp] "v"(ajp), [aj] "v"(aj), [k0] "n"(2 * M0), [k1] "n"(2 * M0 + 1) : "s88", "s89")
+// pairs M0 .. M0 + P - 1 -= aj * (aj of their two lanes each); HI: aj is the high half of ajp.  8 pairs go as 4 + 4, 7 as 4 + 3, 6 as
+// 3 + 3, 5 as 3 + 2: no chunk of one but the last pair of all
+template <int M0, int P, bool HI, int NP>
+__device__ __forceinline__ void chol_update_pk(chol_pair (&p)[NP], chol_pair ajp, float aj) {
+  constexpr int T = (P == 4 || P >= 7) ? 4 : P >= 3 ? 3 : P;
+  static_assert(M0 + P <= NP && 2 * (M0 + P) <= 64, "pairs of the row; a pad column's lane exists");
+  if constexpr (T == 4) { if constexpr (HI) CHOL_CHUNK4(CHOL_OS_HI); else CHOL_CHUNK4(CHOL_OS_LO); }
+  else if constexpr (T == 3) { if constexpr (HI) CHOL_CHUNK3(CHOL_OS_HI); else CHOL_CHUNK3(CHOL_OS_LO); }
+  else if constexpr (T == 2) { if constexpr (HI) CHOL_CHUNK2(CHOL_OS_HI); else CHOL_CHUNK2(CHOL_OS_LO); }
+  else if constexpr (T == 1) { if constexpr (HI) CHOL_CHUNK1(CHOL_OS_HI); else CHOL_CHUNK1(CHOL_OS_LO); }
+  if constexpr (P > T) chol_update_pk<M0 + T, P - T, HI, NP>(p, ajp, aj);
+}
+#undef CHOL_RL
+#undef CHOL_PK
+#undef CHOL_OS_LO
+#undef CHOL_OS_HI
+#undef CHOL_CHUNK4
+#undef CHOL_CHUNK3
+#undef CHOL_CHUNK2
+#undef CHOL_CHUNK1
+template <int K, int NP>
+__device__ __forceinline__ float chol_col(const chol_pair (&p)[NP]) { if constexpr (K & 1) return p[K / 2].y; else return p[K / 2].x; }
+template <int K, int NP>
+__device__ __forceinline__ void chol_set(chol_pair (&p)[NP], float v) { if constexpr (K & 1) p[K / 2].y = v; else p[K / 2].x = v; }
+// head of stage J in two parts: the pivot's clamp and rsqrt; then lane J's dinv and the scaling of column J.  The stage before puts
+// its packed updates between the two: they read the pair of column J - 1, of which column J is the other half when J is odd, so
+// they cannot follow the scaling, but they can fill the rsqrt's wait
+template <int J, int NP>
+__device__ __forceinline__ float chol_pivot_pk(chol_pair (&p)[NP]) { return rsqrtf(fmaxf(rl(chol_col<J>(p), J), 1e-30f)); }
+template <int J, int NP>
+__device__ __forceinline__ void chol_scale_pk(chol_pair (&p)[NP], float inv, float& dinv, int lane) {
+  dinv = (lane == J) ? inv : dinv;
+  chol_set<J>(p, chol_col<J>(p) * inv);  // column J of L in lanes >= J
+}
+template <int J, int NV, int NP>
+__device__ __forceinline__ void chol_stage_pk(chol_pair (&p)[NP], float& dinv, int lane) {
+  if constexpr (J + 1 < NV) {
+    const float aj = chol_col<J>(p);
+    chol_set<J + 1>(p, __builtin_fmaf(-aj, rl(aj, J + 1), chol_col<J + 1>(p)));
+    const float inv = chol_pivot_pk<J + 1>(p);
+    if constexpr (J + 2 < NV) {
+      // an odd column J + 2 is the high half of column J + 1's pair: on its own
+      if constexpr ((J + 2) & 1) chol_set<J + 2>(p, __builtin_fmaf(-aj, rl(aj, J + 2), chol_col<J + 2>(p)));
+      constexpr int M0 = (J + 3) / 2;
+      if constexpr (M0 < NP) {
+        // the one wait state between the VALU instruction that scaled column J and a v_readlane of it, wherever the scheduler puts the
+        // stage's first chunk (the hazard recogniser does not look inside inline assembly)
+        asm volatile("s_nop 0" : "+v"(p[J / 2]));
+        chol_update_pk<M0, NP - M0, (J & 1) != 0, NP>(p, p[J / 2], chol_col<J>(p));
+      }
+    }
+    chol_scale_pk<J + 1>(p, inv, dinv, lane);
+    chol_stage_pk<J + 1, NV>(p, dinv, lane);
+  }
+}
+template <int NV>
+__device__ __forceinline__ void chol_lower_pk(float (&a)[NV], float& dinv, int lane) {
+  constexpr int NP = (NV + 1) / 2;
+  chol_pair p[NP];
+#pragma unroll
+  for (int m = 0; m < NP; m++) { p[m].x = a[2 * m]; p[m].y = 2 * m + 1 < NV ? a[2 * m + 1 < NV ? 2 * m + 1 : 0] : 0.f; }
+  chol_scale_pk<0>(p, chol_pivot_pk<0>(p), dinv, lane);
+  chol_stage_pk<0, NV>(p, dinv, lane);
+#pragma unroll
+  for (int m = 0; m < NP; m++) { a[2 * m] = p[m].x; if (2 * m + 1 < NV) a[2 * m + 1 < NV ? 2 * m + 1 : 0] = p[m].y; }
+}
 // solve (L L^T) x = b.  L = D L1 with D = diag(L) and L1 unit lower triangular; the LDS matrix holds the strictly lower part
 // of L1 (row i scaled by 1 / L[i][i], zeros on and above the diagonal -- see chol_park), so
 //   L y = b    <=>  L1 y = D^-1 b         and        L^T x = y   <=>  L1^T (D x) = y,
 // and a substitution stage is one broadcast, one LDS read and one FMA with no lane masking (the zeros do it).
 // Lane i holds b_i and returns x_i; forward reads row i, backward reads column i (consecutive lanes -> consecutive banks).
 template <int NV, int LD, int LW>
-__device__ __forceinline__ float chol_solve_lds(const float (*Lm)[LD], float dinv, float b, int lane, int hb) {
+__device__ __forceinline__ float chol_fwd_lds(const float (*Lm)[LD], float dinv, float b, int lane, int hb) {
   const int li = lane < NV ? lane : 0;
   b *= dinv;
 #pragma unroll
   for (int j = 0; j < NV - 1; j++) b -= Lm[li][j] * grp_bcast<LW>(b, j, hb);
+  return b;
+}
+template <int NV, int LD, int LW>
+__device__ __forceinline__ float chol_bwd_lds(const float (*Lm)[LD], float dinv, float b, int lane, int hb) {
+  const int li = lane < NV ? lane : 0;
 #pragma unroll
   for (int j = NV - 1; j > 0; j--) b -= Lm[j][li] * grp_bcast<LW>(b, j, hb);
   return b * dinv;
+}
+template <int NV, int LD, int LW>
+__device__ __forceinline__ float chol_solve_lds(const float (*Lm)[LD], float dinv, float b, int lane, int hb) {
+  return chol_bwd_lds<NV, LD, LW>(Lm, dinv, chol_fwd_lds<NV, LD, LW>(Lm, dinv, b, lane, hb), lane, hb);
 }
 // row `lane` of the factor into LDS in the form chol_solve_lds reads
 template <int NV, int LD>
@@ -451,6 +567,23 @@ __device__ __forceinline__ void chol_park(float (*Lm)[LD], const float (&a)[NV],
 #pragma unroll
     for (int k = 0; k < NV; k++) Lm[lane][k] = k < lane ? a[k] * dinv : 0.f;
   }
+}
+// chol_park and the forward substitution of a factor this lane has just computed: the row's multipliers k < lane ? a[k] * dinv : 0 are
+// the products chol_park stores, taken from the registers they are stored from, so the forward loop waits for no LDS read (and for
+// no barrier behind the store; the caller places one before chol_bwd_lds, which reads other lanes' rows).  Lanes >= NV multiply by
+// the zeros of LDS row 0.  `a` is dead after the loop.
+template <int NV, int LD, int LW>
+__device__ __forceinline__ float chol_park_fwd(float (*Lm)[LD], float (&a)[NV], float dinv, float b, int lane, int hb) {
+#pragma unroll
+  for (int k = 0; k < NV; k++) a[k] = (k < lane && lane < NV) ? a[k] * dinv : 0.f;
+  if (lane < NV) {
+#pragma unroll
+    for (int k = 0; k < NV; k++) Lm[lane][k] = a[k];
+  }
+  b *= dinv;
+#pragma unroll
+  for (int j = 0; j < NV - 1; j++) b -= a[j] * grp_bcast<LW>(b, j, hb);
+  return b;
 }
 
 
@@ -627,6 +760,11 @@ struct KTraits {
   // registers to spare and the batch made it spill more (flamingo_p_v3's kernels, flamingo_light_v1's contact-twist plane
   // kernels; the rollout kernels pass 1 to env_body themselves): DESIGN 4.2.
   static constexpr int ROWB = (NV == 14 || (NV == 18 && !HF && MCT > 0)) ? 1 : 8;
+  // Newton / implicitfast Cholesky: the packed factorisation with pivot look-ahead (chol_lower_pk) and the forward substitution fed
+  // from the factor's registers (chol_park_fwd) instead of chol_lower / chol_park / chol_solve_lds.  The same bits.  On for
+  // flamingo_light_v1's plane kernels without contact twist (the headline kernel and its step-only twin); the kernels that are at
+  // their register budget keep the scalar form (the rollout kernels pass false to env_body themselves): DESIGN 4.2.
+  static constexpr bool CHOLP = NV == 18 && !HF && !SC && EPW == 1 && MCT == 0 && KM == 0;
 };
 
 // Ends a batch of LDS reads: the values pass through one statement, so all their reads are issued ahead of it and none of their
@@ -674,7 +812,7 @@ typedef const KArgs __attribute__((address_space(4)))* KArgsP;
 // step-only body: the mode is a constant, so no reset-mode branch and no debug dump is compiled in and A.mode is never read.  The
 // arithmetic of a step is the same instruction sequence in both (tests/test_gpu_step_kernel.py compares them bit for bit).
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, bool PROF, int EPW, int MCT, bool FIX, int KM = 0, int KMODE = -1,
-          int ROWB = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::ROWB>
+          int ROWB = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::ROWB, bool CHOLP = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::CHOLP>
 __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::L (&SS)[EPW], const int wsel = 0,
                                          const int kstep = 0) {   // kstep: control step of a rollout launch (row of the [K][N][...] I/O buffers)
   static_assert(EPW == 1 || (EPW == 2 && !HF && !SC && NV <= 32 && NB <= 32), "two environments per wave: flat ground, no pairs");
@@ -2380,6 +2518,7 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
         unsigned long long q0_ = 0;
         if (PROF) { __builtin_amdgcn_s_waitcnt(0); q0_ = __builtin_amdgcn_s_memtime(); }
         if (grp_ballot<LW>(changed, hb) != 0ull) st_build++;
+        float fwd_y;   // the forward substitution's result
         if (__ballot(changed) != 0ull) {
 #pragma unroll
           for (int rr = 0; rr < RPL; rr++) dact_fac[rr] = dact_cur[rr];
@@ -2551,13 +2690,22 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
               if (PROF && !HF) { __builtin_amdgcn_s_waitcnt(0); pext[2] += __builtin_amdgcn_s_memtime() - th0_; }   // [18] = tree pass
             }
           }
-          chol_lower<NV, LW>(a_row, dinv, ln, hb);
+          if constexpr (CHOLP) {
+            chol_lower_pk<NV>(a_row, dinv, ln);
+            WSYNC();
+            fwd_y = chol_park_fwd<NV, L::LD, LW>(S.u.H, a_row, dinv, grad_l, ln, hb);   // the stamp below then counts this forward loop as "Cholesky + park"
+          } else {
+            chol_lower<NV, LW>(a_row, dinv, ln, hb);
+            WSYNC();
+            chol_park<NV, L::LD>(S.u.H, a_row, dinv, ln);
+          }
           WSYNC();
-          chol_park<NV, L::LD>(S.u.H, a_row, dinv, ln);
-          WSYNC();
+        } else if constexpr (CHOLP) {
+          fwd_y = chol_fwd_lds<NV, L::LD, LW>(S.u.H, dinv, grad_l, ln, hb);   // the factor of an earlier iteration: its rows are in LDS only
         }
         if (PROF) { __builtin_amdgcn_s_waitcnt(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[11] += t_ - q0_; q0_ = t_; }   // Cholesky + park
-        const float mg = chol_solve_lds<NV, L::LD, LW>(S.u.H, dinv, grad_l, ln, hb);
+        if constexpr (!CHOLP) fwd_y = chol_fwd_lds<NV, L::LD, LW>(S.u.H, dinv, grad_l, ln, hb);
+        const float mg = chol_bwd_lds<NV, L::LD, LW>(S.u.H, dinv, fwd_y, ln, hb);
         if (ln < NV) S.sr[ln] = -mg;
         WSYNC();
         if (PROF) { __builtin_amdgcn_s_waitcnt(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[12] += t_ - q0_; }   // triangular solves
@@ -2864,12 +3012,22 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
 #pragma unroll
           for (int k = 0; k < NV; k++) a_row[k] = Mr[k];
         }
-        chol_lower<NV, LW>(a_row, dinv, ln, hb);
-        WSYNC();
-        chol_park<NV, L::LD>(S.u.H, a_row, dinv, ln);
-        WSYNC();
-        const float rhs = ln < NV ? qsm_l + S.qcon[ln] : 0.f;
-        const float qa = chol_solve_lds<NV, L::LD, LW>(S.u.H, dinv, rhs, ln, hb);
+        float qa;
+        if constexpr (CHOLP) {
+          chol_lower_pk<NV>(a_row, dinv, ln);
+          const float rhs = ln < NV ? qsm_l + S.qcon[ln] : 0.f;
+          WSYNC();
+          const float y = chol_park_fwd<NV, L::LD, LW>(S.u.H, a_row, dinv, rhs, ln, hb);
+          WSYNC();
+          qa = chol_bwd_lds<NV, L::LD, LW>(S.u.H, dinv, y, ln, hb);
+        } else {
+          chol_lower<NV, LW>(a_row, dinv, ln, hb);
+          WSYNC();
+          chol_park<NV, L::LD>(S.u.H, a_row, dinv, ln);
+          WSYNC();
+          const float rhs = ln < NV ? qsm_l + S.qcon[ln] : 0.f;
+          qa = chol_solve_lds<NV, L::LD, LW>(S.u.H, dinv, rhs, ln, hb);
+        }
         WSYNC();
         if (PROF) { __builtin_amdgcn_s_waitcnt(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[15] += t_ - pt0; }   // implicit solve done (advance follows)
         if (kmode != MODE_DEBUG) {
@@ -3200,7 +3358,7 @@ __global__ __launch_bounds__(64, waves_per_simd(163840 / (int)sizeof(typename KT
   const int K = A.roll_steps;
 #pragma nounroll
   for (int k = 0; k < K; k++) {
-    env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, false, 0, KMODE, 1>(kargs_p, env, SS, 0, k);   // row batch 1: KTraits::ROWB
+    env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, false, 0, KMODE, 1, false>(kargs_p, env, SS, 0, k);   // row batch 1, scalar Cholesky: KTraits::ROWB, CHOLP
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (A.ovf != nullptr && __builtin_amdgcn_readfirstlane(A.ovf[env]) != 0) break;   // abandoned at step k: the fix kernel continues
@@ -3391,6 +3549,46 @@ __global__ __launch_bounds__(64) void box_box_probe_kernel(const float* geo, con
   if (okb && rank < 8) {
     for (int k = 0; k < 3; k++) o[3 + 4 * rank + k] = bp[k];
     o[3 + 4 * rank + 3] = bd;
+  }
+}
+
+// Diagnostic / test kernel (cosim_debug_forward "cholesky"): both forms of the in-register Cholesky and its solve on matrices given directly, one per
+// wave.  rows [n][64][NV]: what each of the 64 lanes holds on entry (lane i < NV: row i; the slots k > i and the lanes >= NV are the
+// garbage slots of the routines and are the caller's to fill); rhs [n][64].  Form 0 is chol_lower / chol_park / chol_solve_lds, form 1
+// chol_lower_pk / chol_park_fwd / chol_bwd_lds.  fac [n][2][NV][NV]: the factor's lower triangle (zeros above the diagonal), dinv and
+// sol [n][2][NV].
+template <int NV>
+__global__ __launch_bounds__(64) void chol_probe_kernel(const float* rows, const float* rhs, int n, float* fac, float* dinv_out, float* sol) {
+  constexpr int LD = NV | 1;
+  __shared__ float Lm[NV][LD];
+  const int ln = threadIdx.x, i = (int)blockIdx.x;
+  if (i >= n) return;
+  const float* r = rows + ((size_t)i * 64 + ln) * NV;
+  const float b = rhs[(size_t)i * 64 + ln];
+#pragma unroll
+  for (int form = 0; form < 2; form++) {
+    float a[NV], dinv = 1.f, x;
+#pragma unroll
+    for (int k = 0; k < NV; k++) a[k] = r[k];
+    if (form == 0) chol_lower<NV, 64>(a, dinv, ln, 0); else chol_lower_pk<NV>(a, dinv, ln);
+    if (ln < NV) {
+      float* o = fac + (((size_t)i * 2 + form) * NV + ln) * NV;
+#pragma unroll
+      for (int k = 0; k < NV; k++) o[k] = k <= ln ? a[k] : 0.f;
+      dinv_out[((size_t)i * 2 + form) * NV + ln] = dinv;
+    }
+    WSYNC();
+    if (form == 0) {
+      chol_park<NV, LD>(Lm, a, dinv, ln);
+      WSYNC();
+      x = chol_solve_lds<NV, LD, 64>(Lm, dinv, b, ln, 0);
+    } else {
+      const float y = chol_park_fwd<NV, LD, 64>(Lm, a, dinv, b, ln, 0);
+      WSYNC();
+      x = chol_bwd_lds<NV, LD, 64>(Lm, dinv, y, ln, 0);
+    }
+    if (ln < NV) sol[((size_t)i * 2 + form) * NV + ln] = x;
+    WSYNC();
   }
 }
 

@@ -108,7 +108,7 @@ _ABI_ROWS = (
     ("cosim_scenario_curves_clear", _ci, [_vp]),
     ("cosim_scenario_curves_groups", _ci, [_vp, _ci, _vp]),
     ("cosim_fall_set", _ci, [_vp, _cf, _cf, _ci, _vp, _ci]),
-    ("cosim_debug_forward", _ci, [_vp, _ci, _cs, _vp, _ci]),
+    ("cosim_debug_forward", _ci, [_vp, _ci, _cs, _vp, _ci]),   # also the test hook "cholesky" (both forms of the in-register Cholesky): no entry point of its own
     ("cosim_debug_counters", _ci, [_vp, _vp, _ci]),
     ("cosim_debug_support", _ci, [_vp, _ci, _vp, _ci, _vp, _ci]),
     ("cosim_debug_mpr_prims", _ci, [_vp, _vp, _vp, _ci, _ci, _vp, _vp]),

@@ -610,6 +610,14 @@ int cosim_event_push(cosim_engine_t* e, const float* v_dev, const uint8_t* mask_
 
 /* Debug hook for the parity tests: runs ONE mj_forward-equivalent on env `env` in a diagnostic kernel and copies the
  * named intermediate to host doubles-as-float: "xpos" "xquat" "M" "cdof" "contacts" "J" "efc" "qacc" ... */
+/* name "cholesky" is a test hook of its own (no env is stepped; the handle names the device only): the step kernels' in-register
+ * Cholesky and its solve, in both forms the kernels are built with, on n matrices of order `env` (18, 10 or 7; anything else:
+ * COSIM_EINVAL), one per wave.  host_out is a block of capacity = n * 64 * (order + 1) floats, read and written.  On entry: rows
+ * [n][64][order], what each of the wave's 64 lanes holds: lane i < order row i of the symmetric matrix, of which the routines read
+ * the entries k <= i; the entries k > i and the lanes >= order are theirs to fill with anything; then rhs [n][64].  On return, from
+ * the start of the block: fac [n][2][order][order], the factor L with zeros above the diagonal; dinv [n][2][order] = 1 / L[i][i];
+ * sol [n][2][order], the solution of (L L^T) x = rhs.  Form 0 is the scalar factorisation and the solve from LDS, form 1 the packed
+ * factorisation with pivot look-ahead and the forward substitution from registers (KTraits::CHOLP). */
 int cosim_debug_forward(cosim_engine_t* e, int env, const char* name, float* host_out, int capacity);
 
 /* Average duration (ms) of the step kernel since the last call, measured with HIP events on the launch stream, and
