@@ -2623,8 +2623,10 @@ int cosim_event_push(cosim_engine_t* e, const float* v_dev, const uint8_t* mask_
 }
 
 static int debug_cholesky(cosim_engine_t* e, int nv, float* io, int capacity);
+static int debug_ldsbatch(cosim_engine_t* e, int nv, float* io, int capacity);
 int cosim_debug_forward(cosim_engine_t* e, int env, const char* name, float* host_out, int capacity) {
   if (e && host_out && name && !strcmp(name, "cholesky")) return debug_cholesky(e, env, host_out, capacity);   // no env, no launch of a step kernel
+  if (e && host_out && name && !strcmp(name, "ldsbatch")) return debug_ldsbatch(e, env, host_out, capacity);   // likewise
   if (!e || !host_out || env < 0 || env >= e->n_envs) return fail(COSIM_EINVAL, "cosim_debug_forward: bad argument");
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
@@ -2784,6 +2786,27 @@ static int debug_cholesky(cosim_engine_t* e, int nv, float* io, int capacity) {
     if ((r = dbg_finish()) == hipSuccess) r = out.download(io, (nfac + 2 * nvec) * sizeof(float));
   }
   if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_forward cholesky: ") + hipGetErrorString(r));
+  return COSIM_OK;
+}
+
+// cosim_debug_forward "ldsbatch": both forms of the solver primitives with batched LDS reads on n problems of order nv, one per wave
+// (ldsbatch_probe_kernel says what a problem holds).  io holds n blocks of 64 nv + nv nv + 3 nv floats on entry and n blocks of
+// 2 (64 + 2 nv) on return.
+static int debug_ldsbatch(cosim_engine_t* e, int nv, float* io, int capacity) {
+  if (nv != 18 && nv != 10 && nv != 7) return fail(COSIM_EINVAL, "cosim_debug_forward ldsbatch: the order is not 18, 10 or 7");
+  const int per = 64 * nv + nv * nv + 3 * nv, n = capacity / per;
+  if (capacity < per || capacity % per) return fail(COSIM_EINVAL, "cosim_debug_forward ldsbatch: capacity is not n * (64 nv + nv nv + 3 nv)");
+  HIP_TRY(hipSetDevice(e->device));
+  DbgBuf in, out;
+  const size_t nout = (size_t)n * 2 * (64 + 2 * nv);   // < capacity: the answer fits the caller's block
+  hipError_t r;
+  if ((r = in.upload(io, (size_t)capacity * sizeof(float))) == hipSuccess && (r = out.alloc(nout * sizeof(float))) == hipSuccess &&
+      (r = hipMemset(out.p, 0, nout * sizeof(float))) == hipSuccess) {
+    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, 0, (const float*)in.p, n, (float*)out.p); };
+    if (nv == 18) launch(ldsbatch_probe_kernel<18>); else if (nv == 10) launch(ldsbatch_probe_kernel<10>); else launch(ldsbatch_probe_kernel<7>);
+    if ((r = dbg_finish()) == hipSuccess) r = out.download(io, nout * sizeof(float));
+  }
+  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_forward ldsbatch: ") + hipGetErrorString(r));
   return COSIM_OK;
 }
 

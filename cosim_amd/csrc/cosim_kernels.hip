@@ -765,6 +765,11 @@ struct KTraits {
   // flamingo_light_v1's plane kernels without contact twist (the headline kernel and its step-only twin); the kernels that are at
   // their register budget keep the scalar form (the rollout kernels pass false to env_body themselves): DESIGN 4.2.
   static constexpr bool CHOLP = NV == 18 && !HF && !SC && EPW == 1 && MCT == 0 && KM == 0;
+  // Newton mat-vecs (M v, J v) and the triangular solves that read the factor from LDS: all operands of a site are read ahead of
+  // one wait (lds_pairs_join) instead of one wait per pair of terms.  The arithmetic of each site is the
+  // sequence the one-wait-per-pair form compiles to in these kernels, written out (dot_pinned, chol_*_lds_b): the same bits.  Under
+  // CHOLP's rule and for the same kernels; the rollout and fix-up kernels keep the old form: DESIGN 4.2.
+  static constexpr bool LDSB = CHOLP;
 };
 
 // Ends a batch of LDS reads: the values pass through one statement, so all their reads are issued ahead of it and none of their
@@ -794,6 +799,96 @@ __device__ __forceinline__ float jtf_rows(LDS& S, const int ln, const int r, flo
   return qc;
 }
 
+// KTraits::LDSB.  A batch of register pairs, each two neighbouring floats of an LDS row or column (one ds_read2_b32): (NV + 1) / 2 pairs
+// hold the NV terms of a row (nine for flamingo_light_v1; five and four are the test orders 10 and 7).  Pairs, not floats, because an
+// inline-assembly statement takes at most 30 operands.  An odd order's last pair reads its last float twice.
+typedef float lds_pair __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ lds_pair lds_pair_at(const float* p, int i0, int i1) { lds_pair r; r.x = p[i0]; r.y = p[i1]; return r; }
+#define LDSB_OPS4(a) "+v"(a[0]), "+v"(a[1]), "+v"(a[2]), "+v"(a[3])
+#define LDSB_OPS5(a) LDSB_OPS4(a), "+v"(a[4])
+#define LDSB_OPS9(a) LDSB_OPS5(a), "+v"(a[5]), "+v"(a[6]), "+v"(a[7]), "+v"(a[8])
+// lds_batch_join for one or two arrays of pairs
+template <int NP>
+__device__ __forceinline__ void lds_pairs_join(lds_pair (&a)[NP]) {
+  static_assert(NP == 9 || NP == 5 || NP == 4, "orders 18, 10 and 7");
+  if constexpr (NP == 9) asm volatile("s_waitcnt lgkmcnt(0)" : LDSB_OPS9(a));
+  else if constexpr (NP == 5) asm volatile("s_waitcnt lgkmcnt(0)" : LDSB_OPS5(a));
+  else asm volatile("s_waitcnt lgkmcnt(0)" : LDSB_OPS4(a));
+}
+template <int NP>
+__device__ __forceinline__ void lds_pairs_join(lds_pair (&a)[NP], lds_pair (&b)[NP]) {
+  static_assert(NP == 9 || NP == 5 || NP == 4, "orders 18, 10 and 7");
+  if constexpr (NP == 9) asm volatile("s_waitcnt lgkmcnt(0)" : LDSB_OPS9(a), LDSB_OPS9(b));
+  else if constexpr (NP == 5) asm volatile("s_waitcnt lgkmcnt(0)" : LDSB_OPS5(a), LDSB_OPS5(b));
+  else asm volatile("s_waitcnt lgkmcnt(0)" : LDSB_OPS4(a), LDSB_OPS4(b));
+}
+#undef LDSB_OPS9
+#undef LDSB_OPS5
+#undef LDSB_OPS4
+// The rounding of sum_k a_k b_k that the solver's mat-vecs keep: what `s = 0; for (k) s += a[k] * b[k]` compiles to in the NV = 18 plane
+// kernels under the product build's SLP threshold (read off their ISA at all four sites, M v and J v of qacc and of the search
+// direction): terms 0 .. 5 a chain of fused multiply-adds from fma(a0, b0, +0), every later term a rounded product and a rounded add,
+// in ascending order.  dot_term is term k of that chain; written out, the bits no longer depend on the vectoriser.
+// (the product and the sum of a later term are kept apart by the pragma: left to the default contraction, s + a * b fuses wherever the
+// vectoriser has not packed the product first, and __fmul_rn / __fadd_rn are plain operators to this compiler)
+__device__ __forceinline__ float mul_add_unfused(float a, float b, float s) {
+#pragma clang fp contract(off)
+  const float p = a * b;
+  return s + p;
+}
+__device__ __forceinline__ float dot_term(int k, float a, float b, float s) { return k < 6 ? __builtin_fmaf(a, b, s) : mul_add_unfused(a, b, s); }
+template <int NV>
+__device__ __forceinline__ float dot_pinned(const lds_pair (&a)[(NV + 1) / 2], const lds_pair (&b)[(NV + 1) / 2]) {
+  float s = 0.f;
+#pragma unroll
+  for (int k = 0; k < NV; k++) s = dot_term(k, (k & 1) ? a[k / 2].y : a[k / 2].x, (k & 1) ? b[k / 2].y : b[k / 2].x, s);
+  return s;
+}
+// Row . v for an NV-float LDS row and vector: both read as one batch behind one wait.  Each product reads v for itself, and the caller
+// keeps it under the branch of the lanes that have a row: with v shared between M v and J v, or with every lane reading at a
+// clamped row and no branch to bound the batch, the headline kernel spills registers.
+template <int NV>
+__device__ __forceinline__ float lds_row_dot(const float* Ar, const float* v) {
+  constexpr int NP = (NV + 1) / 2;
+  lds_pair vp[NP], ap[NP];
+#pragma unroll
+  for (int k = 0; k < NP; k++) {
+    const int i1 = 2 * k + 1 < NV ? 2 * k + 1 : NV - 1;
+    ap[k] = lds_pair_at(Ar, 2 * k, i1);
+    vp[k] = lds_pair_at(v, 2 * k, i1);
+  }
+  lds_pairs_join(ap, vp);
+  return dot_pinned<NV>(ap, vp);
+}
+// chol_fwd_lds / chol_bwd_lds with the NV - 1 multipliers of the lane's row / column read ahead of the substitution chain (none of
+// them depends on it); the chain is the same readlane and fma(-l, b_j, b) per stage.  The batch also reads one or two floats that no
+// stage uses (forward: the row's last column; backward: row 0 of the column), inside the factor.
+template <int NV, int LD, int LW>
+__device__ __forceinline__ float chol_fwd_lds_b(const float (*Lm)[LD], float dinv, float b, int lane, int hb) {
+  constexpr int NP = (NV + 1) / 2;
+  const float* Lr = Lm[lane < NV ? lane : 0];
+  lds_pair m[NP];
+#pragma unroll
+  for (int k = 0; k < NP; k++) m[k] = lds_pair_at(Lr, 2 * k, 2 * k + 1 < NV ? 2 * k + 1 : NV - 1);
+  lds_pairs_join(m);
+  b *= dinv;
+#pragma unroll
+  for (int j = 0; j < NV - 1; j++) b = __builtin_fmaf(-((j & 1) ? m[j / 2].y : m[j / 2].x), grp_bcast<LW>(b, j, hb), b);
+  return b;
+}
+template <int NV, int LD, int LW>
+__device__ __forceinline__ float chol_bwd_lds_b(const float (*Lm)[LD], float dinv, float b, int lane, int hb) {
+  constexpr int NP = (NV + 1) / 2;
+  const float* Lc = &Lm[0][lane < NV ? lane : 0];
+  lds_pair m[NP];   // m[k] = {L[2k][i], L[2k + 1][i]}
+#pragma unroll
+  for (int k = 0; k < NP; k++) m[k] = lds_pair_at(Lc, 2 * k * LD, (2 * k + 1 < NV ? 2 * k + 1 : NV - 1) * LD);
+  lds_pairs_join(m);
+#pragma unroll
+  for (int j = NV - 1; j > 0; j--) b = __builtin_fmaf(-((j & 1) ? m[j / 2].y : m[j / 2].x), grp_bcast<LW>(b, j, hb), b);
+  return b * dinv;
+}
+
 // ------------------------------------------------------------------------------------------------ the kernel
 // HF: heightfield ground; SC: robot-robot (self) collision pairs; PROF: diagnostic build with s_memtime phase stamps;
 // EPW: environments per wave (1: lane l of 64 plays object l; 2: two groups of 32 lanes, RPL rows per lane of the group)
@@ -812,11 +907,13 @@ typedef const KArgs __attribute__((address_space(4)))* KArgsP;
 // step-only body: the mode is a constant, so no reset-mode branch and no debug dump is compiled in and A.mode is never read.  The
 // arithmetic of a step is the same instruction sequence in both (tests/test_gpu_step_kernel.py compares them bit for bit).
 template <int NV, int NB, int RPL, bool HF, int GTM, bool SC, bool PROF, int EPW, int MCT, bool FIX, int KM = 0, int KMODE = -1,
-          int ROWB = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::ROWB, bool CHOLP = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::CHOLP>
+          int ROWB = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::ROWB, bool CHOLP = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::CHOLP,
+          bool LDSB = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::LDSB && !FIX>
 __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>::L (&SS)[EPW], const int wsel = 0,
                                          const int kstep = 0) {   // kstep: control step of a rollout launch (row of the [K][N][...] I/O buffers)
   static_assert(EPW == 1 || (EPW == 2 && !HF && !SC && NV <= 32 && NB <= 32), "two environments per wave: flat ground, no pairs");
   static_assert(MCT == 0 || EPW == 1, "contact-twist mode: one environment per wave");
+  static_assert(!LDSB || (NV == 18 && EPW == 1), "LDS batches: the rounding pinned for NV = 18, one environment per wave");
   static_assert(KM == 0 || (HF && MCT > 0 && EPW == 1 && (!FIX || KM == 2) && (!PROF || KM == 1)),
                 "split pipeline: heightfield contact-twist kernels (a fix-up only of the solver's substep)");
   using KT = KTraits<NV, NB, RPL, HF, SC, EPW, MCT, KM>;
@@ -2362,6 +2459,11 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
       // =========================================================== Newton solver (mj_solNewton), warm-started from qacc
       float Jaref[RPL], Jv[RPL], Ma = 0.f;
       float dinv = 1.f;
+      // diagnostic build, flat kernels: what "Newton total" holds beside its five sub-phases: [29] J qacc and M qacc, [30] the first
+      // constraint update, [31] the whole iteration loop (minus the sub-phases: the loop's head, ballot and priority update)
+      unsigned long long qn_ = 0;
+      if (PROF && !HF) qn_ = __builtin_amdgcn_s_memtime();
+#define NEWTON_PRE(i) do { if (PROF && !HF) { __builtin_amdgcn_s_waitcnt(0); const unsigned long long t_ = __builtin_amdgcn_s_memtime(); pext[i] += t_ - qn_; qn_ = t_; } } while (0)
       auto mulM = [&](const float* v) -> float {  // (M v)[lane]
         float s = 0.f;
         if (ln < NV) {
@@ -2380,9 +2482,17 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
         }
         return s;
       };
+      // LDSB: mulM and rowdot as one batch each (lds_row_dot), inside the same branches: the branch bounds the batch's live range
+      if constexpr (LDSB) {
 #pragma unroll
-      for (int rr = 0; rr < RPL; rr++) { Jaref[rr] = rdense[rr] ? rowdot(S.qacc, rr) - raref[rr] : 0.f; Jv[rr] = 0.f; }
-      Ma = mulM(S.qacc);
+        for (int rr = 0; rr < RPL; rr++) { Jaref[rr] = rdense[rr] ? lds_row_dot<NV>(S.J[ln + LW * rr], S.qacc) - raref[rr] : 0.f; Jv[rr] = 0.f; }
+        Ma = ln < NV ? lds_row_dot<NV>(S.M[ln], S.qacc) : 0.f;
+      } else {
+#pragma unroll
+        for (int rr = 0; rr < RPL; rr++) { Jaref[rr] = rdense[rr] ? rowdot(S.qacc, rr) - raref[rr] : 0.f; Jv[rr] = 0.f; }
+        Ma = mulM(S.qacc);
+      }
+      NEWTON_PRE(13);
       float qacc_l = ln < NV ? S.qacc[ln] : 0.f;
       const float qsm_l = ln < NV ? S.qsm[ln] : 0.f;
       float cost = 0.f, gauss = 0.f, grad_l = 0.f, gradnorm2 = 0.f;
@@ -2701,17 +2811,22 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
           }
           WSYNC();
         } else if constexpr (CHOLP) {
-          fwd_y = chol_fwd_lds<NV, L::LD, LW>(S.u.H, dinv, grad_l, ln, hb);   // the factor of an earlier iteration: its rows are in LDS only
+          // the factor of an earlier iteration: its rows are in LDS only
+          if constexpr (LDSB) fwd_y = chol_fwd_lds_b<NV, L::LD, LW>(S.u.H, dinv, grad_l, ln, hb);
+          else fwd_y = chol_fwd_lds<NV, L::LD, LW>(S.u.H, dinv, grad_l, ln, hb);
         }
         if (PROF) { __builtin_amdgcn_s_waitcnt(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[11] += t_ - q0_; q0_ = t_; }   // Cholesky + park
         if constexpr (!CHOLP) fwd_y = chol_fwd_lds<NV, L::LD, LW>(S.u.H, dinv, grad_l, ln, hb);
-        const float mg = chol_bwd_lds<NV, L::LD, LW>(S.u.H, dinv, fwd_y, ln, hb);
+        float mg;
+        if constexpr (LDSB) mg = chol_bwd_lds_b<NV, L::LD, LW>(S.u.H, dinv, fwd_y, ln, hb);
+        else mg = chol_bwd_lds<NV, L::LD, LW>(S.u.H, dinv, fwd_y, ln, hb);
         if (ln < NV) S.sr[ln] = -mg;
         WSYNC();
         if (PROF) { __builtin_amdgcn_s_waitcnt(0); unsigned long long t_ = __builtin_amdgcn_s_memtime(); pacc[12] += t_ - q0_; }   // triangular solves
       };
 
       update_constraint();
+      NEWTON_PRE(14);
       float gradnorm = sqrtf(gradnorm2);
       if (kmode == MODE_DEBUG && A.dbg != nullptr) {
         // dump position/velocity-stage intermediates before the solve
@@ -2745,11 +2860,14 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
         if (PROF) { __builtin_amdgcn_s_waitcnt(0); q1_ = __builtin_amdgcn_s_memtime(); }
         // ---- exact line search on the piecewise-quadratic cost (PrimalSearch)
         const float sr_l = ln < NV ? S.sr[ln] : 0.f;
-        const float Mv = mulM(S.sr);
+        float Mv;
+        if constexpr (LDSB) Mv = ln < NV ? lds_row_dot<NV>(S.M[ln], S.sr) : 0.f;
+        else Mv = mulM(S.sr);
         float q0[RPL], q1[RPL], q2[RPL];
 #pragma unroll
         for (int rr = 0; rr < RPL; rr++) {
-          Jv[rr] = rowdot(S.sr, rr);
+          if constexpr (LDSB) Jv[rr] = rdense[rr] ? lds_row_dot<NV>(S.J[ln + LW * rr], S.sr) : 0.f;
+          else Jv[rr] = rowdot(S.sr, rr);
           q0[rr] = 0.5f * rD[rr] * Jaref[rr] * Jaref[rr]; q1[rr] = rD[rr] * Jaref[rr] * Jv[rr]; q2[rr] = 0.5f * rD[rr] * Jv[rr] * Jv[rr];
         }
         const float xf0 = qacc_l - faref, xl0 = lsg * qacc_l - laref, vl = lsg * sr_l;   // dof rows: J a - aref now, J s = +-s_dof
@@ -2940,6 +3058,7 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
         }
       };
       // Environments of one wave iterate together: `act` marks the ones still running, the wave leaves when none is.
+      if (PROF && !HF) qn_ = __builtin_amdgcn_s_memtime();
       bool act = true;
 #pragma nounroll
       while (true) {
@@ -2952,6 +3071,8 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
         if (act) act = newton_iterate();
         wave_priority(st_newton + niter);
       }
+      NEWTON_PRE(15);
+#undef NEWTON_PRE
       st_newton += niter;
       st_rows += nefc;
       if (kmode == MODE_DEBUG && A.dbg != nullptr) {
@@ -3019,7 +3140,8 @@ __device__ __forceinline__ void env_body(KArgsP kargs_p, const int env, typename
           WSYNC();
           const float y = chol_park_fwd<NV, L::LD, LW>(S.u.H, a_row, dinv, rhs, ln, hb);
           WSYNC();
-          qa = chol_bwd_lds<NV, L::LD, LW>(S.u.H, dinv, y, ln, hb);
+          if constexpr (LDSB) qa = chol_bwd_lds_b<NV, L::LD, LW>(S.u.H, dinv, y, ln, hb);
+          else qa = chol_bwd_lds<NV, L::LD, LW>(S.u.H, dinv, y, ln, hb);
         } else {
           chol_lower<NV, LW>(a_row, dinv, ln, hb);
           WSYNC();
@@ -3358,7 +3480,7 @@ __global__ __launch_bounds__(64, waves_per_simd(163840 / (int)sizeof(typename KT
   const int K = A.roll_steps;
 #pragma nounroll
   for (int k = 0; k < K; k++) {
-    env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, false, 0, KMODE, 1, false>(kargs_p, env, SS, 0, k);   // row batch 1, scalar Cholesky: KTraits::ROWB, CHOLP
+    env_body<NV, NB, RPL, HF, GTM, SC, false, 1, MCT, false, 0, KMODE, 1, false, false>(kargs_p, env, SS, 0, k);   // row batch 1, scalar Cholesky, one wait per LDS pair: KTraits::ROWB, CHOLP, LDSB
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
     if (A.ovf != nullptr && __builtin_amdgcn_readfirstlane(A.ovf[env]) != 0) break;   // abandoned at step k: the fix kernel continues
@@ -3589,6 +3711,43 @@ __global__ __launch_bounds__(64) void chol_probe_kernel(const float* rows, const
     }
     if (ln < NV) sol[((size_t)i * 2 + form) * NV + ln] = x;
     WSYNC();
+  }
+}
+
+// Diagnostic / test kernel (cosim_debug_forward "ldsbatch"): both forms of the solver primitives that KTraits::LDSB rewrites, on operands
+// given directly, one problem per wave.  Per problem in: A [64][NV] (lane l's row: rows < NV play M, all 64 play J), v [NV], the parked
+// factor Lp [NV][NV] (what chol_park stores), dinv [NV], rhs [NV].  Form 0 is the one-read-at-a-time form (the dot product as
+// dot_term's chain straight from LDS, chol_fwd_lds / chol_bwd_lds), form 1 lds_row_dot and chol_fwd_lds_b / chol_bwd_lds_b.  Out per
+// problem and form: A v [64], forward [NV], backward of the forward's result [NV].
+template <int NV>
+__global__ __launch_bounds__(64) void ldsbatch_probe_kernel(const float* in, int n, float* out) {
+  constexpr int LD = NV | 1, PER = 64 * NV + NV * NV + 3 * NV, OPER = 2 * (64 + 2 * NV);
+  __shared__ float Am[64][LD], Lm[NV][LD], vs[NV + 1];
+  const int ln = threadIdx.x, i = (int)blockIdx.x;
+  if (i >= n) return;
+  const float* p = in + (size_t)i * PER;
+  const float *pv = p + 64 * NV, *pL = pv + NV, *pd = pL + NV * NV, *pr = pd + NV;
+  for (int k = 0; k < NV; k++) Am[ln][k] = p[ln * NV + k];
+  if (ln < NV) { vs[ln] = pv[ln]; for (int k = 0; k < NV; k++) Lm[ln][k] = pL[ln * NV + k]; }
+  const float dinv = ln < NV ? pd[ln] : 1.f, rhs = ln < NV ? pr[ln] : 0.f;
+  __syncthreads();
+#pragma unroll
+  for (int form = 0; form < 2; form++) {
+    float* o = out + (size_t)i * OPER + form * (64 + 2 * NV);
+    float d, y, x;
+    if (form == 0) {
+      d = 0.f;
+#pragma unroll
+      for (int k = 0; k < NV; k++) d = dot_term(k, Am[ln][k], vs[k], d);
+      y = chol_fwd_lds<NV, LD, 64>(Lm, dinv, rhs, ln, 0);
+      x = chol_bwd_lds<NV, LD, 64>(Lm, dinv, y, ln, 0);
+    } else {
+      d = lds_row_dot<NV>(Am[ln], vs);
+      y = chol_fwd_lds_b<NV, LD, 64>(Lm, dinv, rhs, ln, 0);
+      x = chol_bwd_lds_b<NV, LD, 64>(Lm, dinv, y, ln, 0);
+    }
+    o[ln] = d;
+    if (ln < NV) { o[64 + ln] = y; o[64 + NV + ln] = x; }
   }
 }
 

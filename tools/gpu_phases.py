@@ -46,6 +46,10 @@ if acc[19] > 0:
           f"{acc[22]/sub:.1f} full-MPR batches (inside mpr_penetration {acc[21]/sub:.0f} cycles, set-up before it {acc[23]/sub:.0f}); cycles: sub-grids {acc[16]/sub:.0f}, probe passes {acc[17]/sub:.0f}, "
           f"full batches {acc[18]/sub:.0f}")
 elif acc[16] > 0:
+    if acc[31] > 0:
+        head = acc[31] - acc[10:15].sum()
+        print(f"  Newton total beside its sub-phases: J qacc + M qacc {acc[29]:.0f} cycles, first constraint update {acc[30]:.0f}, loop head (ballot, priority, "
+              f"branches) {head:.0f}; unstamped rest {acc[7] - acc[29] - acc[30] - acc[31]:.0f}")
     print(f"  robot-robot pairs (broadphase + MPR): {acc[16]:.0f} cycles = {100*acc[16]/tot:.1f} % of the step")
     print(f"  contact-twist Hessian: per-body matrices {acc[17]:.0f} cycles ({100*acc[17]/tot:.1f} %), tree pass {acc[18]:.0f} cycles ({100*acc[18]/tot:.1f} %)")
 sub = int(env.cm.blob.frame_skip)
