@@ -101,7 +101,7 @@ class BatchedEnv:
                  ranges: Optional[int] = None, deferred_join: Optional[bool] = None, hfield_fixup: Optional[bool] = None,
                  spawn=None, history=None, ledger: Optional[int] = None, scenarios=None, scenario_mode: Optional[str] = None,
                  fall=None, failure_traces=None, streams: Optional[int] = None, check_slots: Optional[int] = None,
-                 curves: Optional[bool] = None):
+                 curves: Optional[bool] = None, search: Optional[int] = None):
         """``ranges`` > 1: ``step()`` issues the fleet as that many launches over contiguous env ranges on engine-owned HIP streams
         (``cosim_set_param "ranges"``).  With ``deferred_join`` the caller's stream is NOT made to wait for them inside ``step()``:
         call ``join()`` before consuming ``state`` / ``terminated`` / ``info`` on the current stream (``get_data``, ``reset``,
@@ -145,6 +145,12 @@ class BatchedEnv:
         keeps per-scenario ensemble time series on the device, see ``set_scenarios`` / ``curves()``.  Default:
         ``config["engine"].get("curves")`` / off: a table's curves are carried but not armed, and no launch, pointer or byte differs
         from a table without curves.
+
+        ``search``: arm the limit search the scenario table holds (a scenario's ``"search"``, ``cosim_amd/scenario.py``): every env of
+        such a row keeps a level that scales the row's pushes / commands and moves when its episodes end, and the engine keeps the
+        last ``search`` (1..64) trial records of every env, see ``set_scenarios`` / ``search()``.  Needs ``auto_reset`` and mode
+        ``"env"``.  Default: ``config["engine"].get("search")`` / none: a table's items are carried but not armed, and no launch,
+        pointer or byte differs from a table without them.
 
         ``fall``: a fall rule -- a ``FallRule`` or a dict ``{"tilt", "height", "grace", "bodies"}`` (``cosim_amd/fall.py``) -- see
         ``set_fall``.  Default: ``config["engine"].get("fall")`` / none: an episode ends early only through the robot's own
@@ -268,12 +274,14 @@ class BatchedEnv:
         self._cmd_out = self._row_out = None
         self.check_slots = 0
         self.curves_armed = False
+        self.search_slots = 0
         self._curve_groups = None                                   # (tensor, G, names) of set_curve_groups: the tensor is kept alive here
         scenarios = scenarios if scenarios is not None else eng_cfg.get("scenarios")
         if scenarios is not None:
             self.set_scenarios(scenarios, scenario_mode if scenario_mode is not None else eng_cfg.get("scenario_mode", "env"),
                                check_slots=check_slots if check_slots is not None else eng_cfg.get("check_slots"),
-                               curves=curves if curves is not None else eng_cfg.get("curves"))
+                               curves=curves if curves is not None else eng_cfg.get("curves"),
+                               search=search if search is not None else eng_cfg.get("search"))
 
     # ------------------------------------------------------------------ domain randomisation (XMLManager step 3)
     def _randomise(self, gain_noise: float):
@@ -648,7 +656,8 @@ class BatchedEnv:
         return self._meta_words()[:, 15].clone()
 
     # ------------------------------------------------------------------ scenario table (cosim_scenario_set)
-    def set_scenarios(self, scenarios, mode: str = "env", check_slots: Optional[int] = None, curves: Optional[bool] = None):
+    def set_scenarios(self, scenarios, mode: str = "env", check_slots: Optional[int] = None, curves: Optional[bool] = None,
+                      search: Optional[int] = None):
         """Give every env its own test: a table of S scenarios, each a command schedule and a push schedule keyed by the env's own
         episode step (``cosim_amd/scenario.py``; ``None`` clears the table).  Env with global id ``g`` runs row ``g mod S`` (mode
         ``"env"``) or, in mode ``"cycle"`` (needs ``auto_reset``), row ``(g + episodes it has ended) mod S``: one scenario per
@@ -692,7 +701,21 @@ class BatchedEnv:
         of the same counts and sizes are rewritten in place (captured graphs pick them up; groups set by ``set_curve_groups`` stay).
         Any other call FORGETS the groups of ``set_curve_groups`` -- the cells they split are freed -- so set them again.  ``None`` /
         ``False``: the curves are not armed (what an earlier call armed is cleared).  Limits: state signals take no sample on a step that ends the episode; open
-        episodes are not in the cells; curves are not part of a ``snapshot()``."""
+        episodes are not in the cells; curves are not part of a ``snapshot()``.
+
+        ``search`` (1..64) arms the table's limit search (``cosim_set_param "search"``): every env whose scenario holds a
+        ``"search"`` item keeps a level -- ``search_levels()`` -- that the scenario kernel multiplies into the row's push vectors
+        and / or command keyframes; behind the step that ends an episode of the env a small rule on the device judges it by the
+        ledger's flags (``fail_on``) and moves the level: down after a failure, up after a pass, by a step that halves.  An episode is
+        a counted trial only if it began at a reset (one that began at ``restore`` / ``set_state`` may have missed its push window);
+        after ``trials`` counted trials the env is done and its level frozen.  The last ``search`` trial records of every env are kept;
+        ``search()`` reads records and trials, ``search_remaining()`` one word.  A call with the same scenarios holding items and the
+        same ``search`` rewrites the items in place and KEEPS the records (captured graphs pick the new bounds up); any other call
+        begins every search anew.  ``None`` / 0: the search is not armed (what an earlier call armed is cleared).  Set the ledger and
+        the search together and their episode ordinals agree.  Needs ``auto_reset`` and mode ``"env"``.  A ``"tilt"`` / ``"height"`` /
+        ``"contact"`` in ``fail_on`` while no fall rule is set is accepted and never fires.  Limits: the level scales pushes and
+        commands only, not parameter windows or fault values; a check verdict is no failure criterion; the records are not part of a
+        ``snapshot()``; per-rank thresholds are not merged."""
         from .scenario import MODES, ScenarioTable
         t = self.torch
         if scenarios is None:
@@ -753,6 +776,13 @@ class BatchedEnv:
             self.engine.scenario_curves_set(None)
         if not self.curves_armed or self.engine.query("scenario_curve_groups") == 0:   # the engine dropped the groups with the cells they split
             self._curve_groups = None
+        # and the limit search
+        armed, self.search_slots = self.search_slots, 0
+        if search and table.has_search:
+            self.engine.search_set(table.pack_search(int(search)))
+            self.search_slots = int(search)
+        elif armed > 0:
+            self.engine.search_set(None)
 
     def _drop_scenarios(self):
         """The env forgets its scenario table and what rode with it (checks, curves, curve groups)."""
@@ -760,6 +790,7 @@ class BatchedEnv:
         self._info_views = None
         self.check_slots = 0
         self.curves_armed = False
+        self.search_slots = 0
         self._curve_groups = None
 
     def set_curve_groups(self, groups, n_groups: Optional[int] = None, names=None):
@@ -837,6 +868,42 @@ class BatchedEnv:
         if not self.curves_armed:
             raise ValueError("clear_curves(): no curves are armed")
         self.engine.scenario_curves_clear()
+
+    # ------------------------------------------------------------------ limit search (cosim_set_param "search")
+    def _search_words(self, name: str, shape):
+        t = self.torch
+        buf = t.empty((self.num_envs, *shape), dtype=t.int32, device=self.device)
+        self.engine.get(name, buf.data_ptr(), self._stream())
+        return buf
+
+    def search(self, include_trials: bool = True):
+        """The fleet's limit search so far as a ``SearchResult`` (``cosim_amd/search.py``): per env its level, step, counted trials,
+        fails, reversals, bracket and threshold; with ``include_trials`` one row per ended episode still in the rings, sorted by
+        (global env id, episode), with the level it ran at and its outcome.  Joins the range streams and reads the device once;
+        nothing is read per step.  Raises ``ValueError`` if no search is armed."""
+        from .search import NCNT, TRIAL_WORDS, SearchResult, search_rows
+        if self.search_slots <= 0:
+            raise ValueError("search(): no search is armed (BatchedEnv(scenarios=TABLE, search=SLOTS) or set_scenarios(..., search=SLOTS))")
+        state = self._search_words("search_state", (NCNT,))
+        ring = self._search_words("search_trials", (self.search_slots, TRIAL_WORDS)) if include_trials else None
+        self.torch.cuda.current_stream(self.device).synchronize()
+        rows = search_rows(self.scenario_table, self.scenario_mode, np.arange(self.env_id0, self.env_id0 + self.num_envs))
+        return SearchResult.from_raw(state.cpu().numpy(), ring.cpu().numpy() if include_trials else None, rows, self.env_id0)
+
+    def search_remaining(self) -> int:
+        """Envs with a search item that still have trials left.  Joins the range streams and reads one device word (a synchronising
+        call).  Raises ``ValueError`` if no search is armed."""
+        if self.search_slots <= 0:
+            raise ValueError("search_remaining(): no search is armed (BatchedEnv(scenarios=TABLE, search=SLOTS) or set_scenarios(..., search=SLOTS))")
+        return self.engine.query("search_remaining")
+
+    def search_levels(self):
+        """The level each env's next step will run at: a float32 tensor ``[N]`` (a copy; 0 for an env whose scenario has no item).
+        Joins the ranges.  Raises ``ValueError`` if no search is armed."""
+        from .search import LEVEL, NCNT
+        if self.search_slots <= 0:
+            raise ValueError("search_levels(): no search is armed (BatchedEnv(scenarios=TABLE, search=SLOTS) or set_scenarios(..., search=SLOTS))")
+        return self._search_words("search_state", (NCNT,))[:, LEVEL].contiguous().view(self.torch.float32)
 
     def check_names(self) -> dict:
         """What a check's ``index`` is resolved against on this env (``scenario.check_names``)."""

@@ -43,6 +43,10 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
     fall:     {tilt: 0.8, height: 0.1, grace: 5, bodies: [base_link]}  # fall rule (cosim_amd/fall.py): end an episode on tilt (rad), base
                                                                        # height (m) or contact of the listed bodies; or engine: {fall: {...}};
                                                                        # same as --fall-*; runs under --graph and --pipelined too
+    search:   8                                                        # arm the scenarios' search: items (a scenario may hold search: {lo, hi,
+                                                                       # rule, trials, targets, fail_on, ...}: a per-env level that scales its
+                                                                       # pushes / commands and moves when an episode ends) and keep 8 trials per
+                                                                       # env; or engine: {search: 8}; same as --search; needs scenario_mode env
 
 Flags given on the command line override the file.
 """
@@ -144,6 +148,14 @@ def main(argv=None) -> int:
     ap.add_argument("--verdicts-out", default=None, metavar="PATH.npz", help="with --check-slots: write this rank's verdict records here")
     ap.add_argument("--require-pass", action="store_true",
                     help="with --check-slots: exit status 3 if any ended episode failed a check (a sweep can gate a CI job)")
+    ap.add_argument("--search", type=int, default=None, metavar="SLOTS",
+                    help="arm the limit search of the scenario table (a scenario's \"search\"): a per-env level that scales the row's pushes / "
+                         "commands and moves when an episode ends; keeps the last SLOTS (1..64) trials of every env; its summary goes into the "
+                         "report as \"episodes.search\" (also under --graph / --pipelined)")
+    ap.add_argument("--search-out", default=None, metavar="PATH.npz", help="with --search: write this rank's search records and trials here")
+    ap.add_argument("--until-searched", action="store_true", help="with --search: stop once every env has spent its trials (or after --steps)")
+    ap.add_argument("--search-poll", type=int, default=50, metavar="STEPS",
+                    help="with --until-searched: ask the device every STEPS control steps (one word; between graph replays under --graph)")
     ap.add_argument("--curves", action="store_true", default=None,
                     help="keep the response curves of the scenario table on the device (a scenario's \"curves\"): per-scenario ensemble time "
                          "series split by outcome; their summary goes into the report as \"episodes.curves\" (also under --graph / --pipelined)")
@@ -164,7 +176,7 @@ def main(argv=None) -> int:
         if not isinstance(sess, dict):
             ap.error("--config: the YAML document must be a mapping")
         unknown = set(sess) - {"env", "engine", "random", "observation", "hardware", "policy", "steps", "commands", "pushes", "report",
-                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces", "check_slots", "curves", "curves_by"}
+                               "trace_env", "percentiles", "hfield_fixup", "spawn", "ledger", "scenarios", "scenario_mode", "fall", "failure_traces", "check_slots", "curves", "curves_by", "search"}
         if unknown:
             ap.error(f"--config: unknown top-level keys {sorted(unknown)}")
     s_env, s_eng, s_pol = sess.get("env", {}) or {}, sess.get("engine", {}) or {}, sess.get("policy", {}) or {}
@@ -267,6 +279,17 @@ def main(argv=None) -> int:
         ap.error("--verdicts-out / --require-pass need --check-slots SLOTS")
     if args.check_slots and scenarios is None:
         ap.error("--check-slots needs --scenarios: checks are rows of a scenario table")
+    args.search = int(opt(args.search, "search", 0))
+    if not 0 <= args.search <= 64:
+        ap.error("--search SLOTS: 1..64")
+    if (args.search_out or args.until_searched) and args.search < 1:
+        ap.error("--search-out / --until-searched need --search SLOTS")
+    if args.search and scenarios is None:
+        ap.error("--search needs --scenarios: a search item is a row of a scenario table")
+    if args.search and scenario_mode != "env":
+        ap.error("--search needs scenario mode env: the search keeps one record per env")
+    if args.search_poll < 1:
+        ap.error("--search-poll STEPS: at least 1")
     args.curves = bool(opt(args.curves, "curves", False))
     if args.curves_out and not args.curves:
         ap.error("--curves-out needs --curves")
@@ -338,9 +361,11 @@ def main(argv=None) -> int:
             else:
                 cfg[section][k] = v
     env = BatchedEnv(cfg, num_envs=hi - lo, device=dev, seed=args.seed, auto_reset=True, env_id0=lo, hfield_fixup=args.hfield_fixup,
-                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, failure_traces=ftrace or False, check_slots=args.check_slots or None, curves=args.curves or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
+                     spawn=spawn or None, history=tuple(args.history) if args.history else None, ledger=args.ledger, scenarios=scenarios, scenario_mode=scenario_mode, fall=fall or None, failure_traces=ftrace or False, check_slots=args.check_slots or None, curves=args.curves or None, search=args.search or None, **({"ranges": args.ranges, "deferred_join": True} if args.pipelined else {}))
     if args.check_slots and env.check_slots < 1:
         ap.error("--check-slots: the scenario table holds no checks")
+    if args.search and env.search_slots < 1:
+        ap.error("--search: the scenario table holds no search item")
     if args.curves and not env.curves_armed:
         ap.error("--curves: the scenario table holds no curves")
     if policy_files:
@@ -374,6 +399,10 @@ def main(argv=None) -> int:
     run = Runner(env, policy, reporter=rep)
     for i, v in enumerate(commands[0][1:1 + env.command_dim]):
         run.update_command(i, v)
+    if args.until_searched:
+        if world > 1:
+            ap.error("--until-searched: one process (the ranks of a torchrun would stop at different steps)")
+        run.stop_when(lambda: env.search_remaining() == 0, args.search_poll)
 
     def before_step(k):
         """What the reference's UI thread does between two loop iterations: key-driven command changes and the push button."""
@@ -427,6 +456,9 @@ def main(argv=None) -> int:
     verdicts = env.verdicts() if args.check_slots else None          # verdict records stay per rank too
     if args.verdicts_out:
         verdicts.save(rank_path(args.verdicts_out, rank, world))
+    search = env.search() if args.search else None                   # search records and thresholds stay per rank too
+    if args.search_out:
+        search.save(rank_path(args.search_out, rank, world))
     if args.curves_out:                                              # the fleet's curves: the cells are all-reduced, every rank holds them
         fleet = rep.fleet_curves()
         if rank == 0:
@@ -447,6 +479,7 @@ def main(argv=None) -> int:
                                          if k not in ("checks", "by_scenario")}} if verdicts is not None else {}),
                           **({"curves": {k: ({name: {q: v[q] for q in ("episodes", "episodes_truncated", "episodes_terminated")} for name, v in x.items()}
                                              if k == "by_policy" else x) for k, x in out["episodes"]["curves"].items()}} if args.curves else {}),
+                          **({"search": "{done}/{envs}".format(**out["episodes"]["search"].get("fleet", out["episodes"]["search"]))} if search is not None else {}),
                           **({"failure_traces": traces.summary()} if traces is not None else {}),
                           **({"by_scenario": {k: {q: v[q] for q in ("episodes", "terminated")} for k, v in out["episodes"]["by_scenario"].items()}}
                              if "by_scenario" in out.get("episodes", {}) else {}),

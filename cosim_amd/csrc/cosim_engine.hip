@@ -23,6 +23,7 @@
 #include "cosim_actfault.hip"
 #include "cosim_checks.hip"
 #include "cosim_curves.hip"
+#include "cosim_search.hip"
 #include "cosim_plan.h"
 #include "cosim_ranges.h"
 #include "cosim_tables.h"
@@ -182,6 +183,14 @@ struct cosim_engine {
   int cur_groups = 0;                     // G; 0: no groups, one plane, curves_step_kernel
   const int32_t* cur_group = nullptr;     // [n_envs], the caller's
   unsigned* d_cur_ungrouped = nullptr;    // one word: ended episodes whose group word was outside [0, G)
+  // limit search of the scenario table (cosim_set_param "search", cosim_search.hip): scenario_search_step_kernel in the place of
+  // scenario_step_kernel, search_step_kernel behind every range's last launch of a step, behind the curves'
+  char* d_srch = nullptr;         // one allocation: has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip
+  SrchTable srch = {};            // device pointers into d_srch; n_items 0: no search, no launches, scenario_step_kernel
+  int* d_srch_rec = nullptr;      // [n_envs][SRCH_NCNT]
+  int* d_srch_ring = nullptr;     // [n_envs][srch_slots][4]
+  int* d_srch_rem = nullptr;      // one word: envs with an item that are not done
+  int srch_slots = 0;
   // fall rules (cosim_fall_set): kernel arguments of every step launch; fall_mask 0 = none (meta word 15 is not written)
   float fall_min_up = -1.f, fall_min_height = 0.f;
   int fall_grace = 0, fall_mask = 0;
@@ -694,6 +703,12 @@ static int scenario_launch(cosim_engine* e, int first, int count, const float* c
   a.tab = e->scn; a.state = e->d_state; a.cmd_in = commands_dev; a.cmd_out = e->scn_cmd_out; a.row_out = e->scn_row_out; a.mask = mask;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.reset = reset;
+  if (e->srch.n_items > 0) {   // a search is armed: the same schedule with every env's level multiplied in
+    ScnSearchArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.scn = a; sa.srch = e->srch; sa.rec = e->d_srch_rec;
+    return launch_small<64, 64>(scenario_search_step_kernel, sa, count, s);
+  }
   return launch_small<64, 64>(scenario_step_kernel, a, count, s);
 }
 
@@ -851,7 +866,42 @@ static void curves_free(cosim_engine* e) {
   memset(&e->cur, 0, sizeof e->cur);
 }
 
+// ---- limit search of the scenario table (cosim_search.hip)
+static SrchArgs search_args(cosim_engine* e) {
+  SrchArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->srch; a.state = e->d_state; a.scn_row = e->scn_row_out;
+  a.rec = e->d_srch_rec; a.ring = e->d_srch_ring; a.remaining = e->d_srch_rem;
+  a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.slots = e->srch_slots;
+  a.fall = e->fall_mask != 0; a.scn_off = e->scn.gid_off;
+  return a;
+}
+
+// this step's outcome of envs [first, first + count), behind the launches that wrote the step's outputs on the same stream
+static int search_step(cosim_engine* e, int first, int count, const uint8_t* term, const uint8_t* trunc, hipStream_t s) {
+  SrchArgs a = search_args(e);
+  a.term = term; a.trunc = trunc; a.first = first; a.count = count;
+  return launch_small<64, 64>(search_step_kernel, a, count, s);
+}
+
+// the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode; their levels stay
+static int search_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
+  if (e->srch.n_items <= 0) return COSIM_OK;
+  SrchArgs a = search_args(e);
+  a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
+  return launch_small<64, 64>(search_begin_kernel, a, e->n_envs, s);
+}
+
+// the search goes with its table (the caller has waited for the device)
+static void search_free(cosim_engine* e) {
+  (void)hipFree(e->d_srch); (void)hipFree(e->d_srch_rec); (void)hipFree(e->d_srch_ring); (void)hipFree(e->d_srch_rem);
+  e->d_srch = nullptr; e->d_srch_rec = nullptr; e->d_srch_ring = nullptr; e->d_srch_rem = nullptr; e->srch_slots = 0;
+  memset(&e->srch, 0, sizeof e->srch);
+}
+
 static void scenario_free(cosim_engine* e) {
+  search_free(e);
   scnparams_free(e);
   obsfault_free(e);
   actfault_free(e);
@@ -909,8 +959,8 @@ static void ftrace_free(cosim_engine* e) {
   e->d_ft_buf = nullptr; e->d_ft_cnt = nullptr; e->ft_frames = 0; e->ft_keep = 0; e->ft_mask = 0;
 }
 
-// ---- the observers: ledger, failure traces, checks, curves -- in that order at every site.  Each kernel writes only its own buffers.
-static_assert(LEDGER_NO_RESET == FT_NO_RESET && FT_NO_RESET == CHK_NO_RESET, "one flag value for \"did not begin at a reset\"");
+// ---- the observers: ledger, failure traces, checks, curves, limit search -- in that order at every site.  Each kernel writes only its own buffers.
+static_assert(LEDGER_NO_RESET == FT_NO_RESET && FT_NO_RESET == CHK_NO_RESET && CHK_NO_RESET == SRCH_NO_RESET, "one flag value for \"did not begin at a reset\"");
 
 // behind a reset / set / restore on the same stream: the masked envs (null: all; with a restore's source index: those it did not
 // refuse) begin an episode; flag 0 or LEDGER_NO_RESET.  Behind the reset because meta[14] is the new episode's spawn row
@@ -918,7 +968,8 @@ static int observers_begin(cosim_engine* e, const uint8_t* mask, const int* src,
   RC_TRY(ledger_begin(e, mask, src, n_rows, flag, s));
   RC_TRY(ftrace_begin(e, mask, src, n_rows, flag, s));
   RC_TRY(checks_begin(e, mask, src, n_rows, flag, s));
-  return curves_begin(e, mask, src, n_rows, s);
+  RC_TRY(curves_begin(e, mask, src, n_rows, s));
+  return search_begin(e, mask, src, n_rows, flag, s);
 }
 
 // behind the last launch of a step (rollout: of `rows` steps, where only the ledger can be armed) of envs [first, first + count) on
@@ -929,6 +980,7 @@ static int observers_step(cosim_engine* e, int first, int count, int rows, const
   if (e->ft_frames > 0) RC_TRY(ftrace_step(e, first, count, actions, cmd, info, term, trunc, s));
   if (e->chk.n_scn > 0) RC_TRY(checks_step(e, first, count, cmd, info, term, trunc, s));
   if (e->cur.n_scn > 0) RC_TRY(curves_step(e, first, count, cmd, info, term, trunc, s));
+  if (e->srch.n_items > 0 && rows == 1) RC_TRY(search_step(e, first, count, term, trunc, s));   // reads no info row
   return COSIM_OK;
 }
 
@@ -1488,6 +1540,17 @@ static int newton_cap(const cosim_engine* e) {
 static int ls_cap(const cosim_engine* e) { return e->max_ls < 0 ? e->model.ls_iterations : (e->max_ls < e->model.ls_iterations ? e->max_ls : e->model.ls_iterations); }
 
 // "scenario_curve_ungrouped": joins the ranges, waits and reads the device word (0 with no groups); held at INT_MAX
+// envs with a search item that have trials left (cosim_query "search_remaining"): joins the ranges and reads the one word
+static int search_remaining(cosim_engine* e) {
+  if (e->srch.n_items <= 0) return 0;
+  HIP_TRY(hipSetDevice(e->device));
+  RC_TRY(join_ranges(e, 0));
+  HIP_TRY(hipDeviceSynchronize());
+  int v = 0;
+  HIP_TRY(hipMemcpy(&v, e->d_srch_rem, sizeof v, hipMemcpyDeviceToHost));
+  return v;
+}
+
 static int curves_ungrouped(cosim_engine* e) {
   if (e->cur_groups <= 0) return 0;
   HIP_TRY(hipSetDevice(e->device));
@@ -1548,6 +1611,9 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "scenario_curve_ungrouped") return curves_ungrouped(const_cast<cosim_engine_t*>(e));   // synchronising: joins, reads one device word
   if (n == "scenario_curve_stage_words") return e->cur.n_scn > 0 ? e->cur.SW : 0;   // stage words per env
   if (n == "scenario_check_words") return e->chk.n_scn > 0 ? checks_words(e->chk.I) : 0;   // 32-bit words of a verdict record: 8 + 2 I
+  if (n == "search") return e->srch.n_items;      // scenarios of the table with a search item armed (0: no search, no launches, scenario_step_kernel)
+  if (n == "search_slots") return e->srch_slots;  // trial records per env
+  if (n == "search_remaining") return search_remaining(const_cast<cosim_engine_t*>(e));   // synchronising: joins, reads one device word
   if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
   if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
@@ -1555,6 +1621,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
 
 static int obsfault_set(cosim_engine* e, const int32_t* words, int count);   // (below, with the other tables of the scenario family)
 static int actfault_set(cosim_engine* e, const int32_t* words, int count);
+static int search_set(cosim_engine* e, const int32_t* words, int count);
 
 int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int count) {
   if (!e || !name || !host) return fail(COSIM_EINVAL, "cosim_set_param: null argument");
@@ -1572,6 +1639,7 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
   else if (n == "meaninertia") { off = L.p_mean; width = 1; }
   else if (n == "obs_faults") return obsfault_set(e, reinterpret_cast<const int32_t*>(host), count);   // a table of 32-bit words, not floats (include/cosim.h)
   else if (n == "action_faults") return actfault_set(e, reinterpret_cast<const int32_t*>(host), count);   // likewise
+  else if (n == "search") return search_set(e, reinterpret_cast<const int32_t*>(host), count);   // likewise
   else if (n == "solver_tolerance") { e->tol32 = host[0]; return COSIM_OK; }
   else if (n == "ls_tolerance_scale") { e->ls_scale = host[0]; return COSIM_OK; }
   else if (n == "max_newton") { e->max_newton = (int)host[0]; return COSIM_OK; }
@@ -2044,6 +2112,14 @@ int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream)
                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return COSIM_OK;
   }
+  const bool srch_state = std::string(name) == "search_state";
+  if (srch_state || std::string(name) == "search_trials") {   // int32 [N][16] / [N][slots][4], contiguous: the search's records / trial rings
+    if (e->srch.n_items == 0) return fail(COSIM_EINVAL, std::string("cosim_get: ") + name + ": no search is armed (cosim_set_param \"search\")");
+    RC_TRY(join_ranges(e, (hipStream_t)stream));
+    const size_t words = (size_t)e->n_envs * (srch_state ? (size_t)SRCH_NCNT : (size_t)e->srch_slots * SRCH_TRIAL_WORDS);
+    HIP_TRY(hipMemcpyAsync(out_dev, srch_state ? e->d_srch_rec : e->d_srch_ring, words * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return COSIM_OK;
+  }
   int off, width;
   int rc = locate(e, name, &off, &width);
   if (rc) return rc;
@@ -2301,6 +2377,7 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
     return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
   }
   if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
+  if (n_scn != e->scn.n_scn || mode == SCN_MODE_CYCLE) search_free(e);   // so is the search; its one record per env needs mode env
   if (n_scn != e->scn.n_scn) { scnparams_free(e); obsfault_free(e); actfault_free(e); checks_free(e); curves_free(e); }   // parameter windows, faults, checks and curves are rows of the table they were set for: another S drops them
   pk.patch(e->d_scn);
   tab.mode = mode;
@@ -2419,6 +2496,65 @@ static int actfault_set(cosim_engine* e, const int32_t* words, int count) {
   RC_TRY(fault_table_set(e, ACF_SETTER, "action faults", e->d_actflt, e->actflt, actfault_free, actfault_buffers, actfault_validate, words, count));
   e->act_in_obs = false;
   for (int el = 0; el < e->ho.frame_dim; el++) e->act_in_obs = e->act_in_obs || e->ho.el_field[el] == CS_OBS_LAST_ACTION;
+  return COSIM_OK;
+}
+
+// Limit search of the scenario table that is set (cosim_set_param "search"): `words` is S | slots | has[S] | lo | hi | x0 | d0 | d_min |
+// rule | trials | targets | fail_mask | rev_skip ([S] each, floats as their bits); the one word 0 clears.  A table with the S, the
+// slots and the has[] of the one that is armed is rewritten in place and the records stay (captured graphs pick the new bounds up);
+// anything else allocates anew and search_init_kernel begins every env's search at its item's start level.
+static int search_set(cosim_engine* e, const int32_t* words, int count) {
+  const std::string fn = "cosim_set_param \"search\"";
+  if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the search)");
+  const int n_scn = words[0];
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_scn == 0) return table_clear(e, 0, search_free);
+  if (n_scn < 0 || (long long)count != 2 + 11ll * n_scn)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios takes " + std::to_string(2 + 11ll * (n_scn < 0 ? 0 : n_scn)));
+  const int32_t* w = words + 2;
+  const size_t S = (size_t)n_scn;
+  const auto f = [&](int k) { return reinterpret_cast<const float*>(w + k * S); };
+  const SrchRaw raw = {n_scn, words[1], w, f(1), f(2), f(3), f(4), f(5), w + 6 * S, w + 7 * S, w + 8 * S, w + 9 * S, w + 10 * S};
+  RC_TRY(table_quiesce(e, 0));
+  std::vector<int32_t> adr;   // key_adr | push_adr of the table that is set: the head of its image
+  if (n_scn == e->scn.n_scn) {
+    adr.resize(2 * (S + 1));
+    HIP_TRY(hipMemcpy(adr.data(), e->d_scn, adr.size() * 4, hipMemcpyDeviceToHost));
+  }
+  const SrchDims dims = {e->scn.n_scn, e->scn.mode, e->ho.auto_reset, adr.data(), adr.data() + S + 1};
+  const SrchShape v = validate_search(dims, raw);
+  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  SrchTable tab = {};
+  WordPacker pk;
+  pack_search(pk, tab, raw, v);
+  bool in_place = e->srch.n_scn == n_scn && e->srch.n_items == v.n && e->srch_slots == raw.slots;
+  if (in_place) {
+    std::vector<int32_t> old;
+    RC_TRY(table_download(e->d_srch, pk, old));
+    in_place = search_same_rows(pk, tab, old.data());
+  }
+  const size_t N = (size_t)e->n_envs;
+  auto alloc = [&]() -> hipError_t {
+    search_free(e);
+    hipError_t r;
+    if ((r = hipMalloc(&e->d_srch, pk.bytes())) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_srch_rec, N * SRCH_NCNT * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMalloc(&e->d_srch_ring, N * raw.slots * SRCH_TRIAL_WORDS * sizeof(int))) != hipSuccess) return r;
+    return hipMalloc(&e->d_srch_rem, sizeof(int));
+  };
+  hipError_t r = in_place ? hipSuccess : alloc();
+  if (r == hipSuccess) r = hipMemcpy(e->d_srch, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) { search_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r)); }
+  pk.patch(e->d_srch);
+  e->srch = tab;
+  e->srch_slots = raw.slots;
+  if (in_place) return COSIM_OK;
+  // every env's record, ring and the remaining word once (the range streams do not order with the null stream: wait here, cold path)
+  SrchArgs a = search_args(e);
+  a.flag = e->stepped ? SRCH_NO_RESET : 0;
+  for (int env = 0; env < e->n_envs; env++) a.n_armed += raw.has[(e->scn.gid_off + (unsigned)env) % (unsigned)n_scn];
+  RC_TRY(launch_small<64, 64>(search_init_kernel, a, e->n_envs, 0));
+  HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
 }
 

@@ -1,5 +1,5 @@
 // cosim_tables.h — what the host does with a table of the scenario family before it reaches the device (cosim_scenario_set,
-// cosim_scenario_params_set, cosim_set_param "obs_faults" / "action_faults", cosim_scenario_checks_set, cosim_scenario_curves_set, include/cosim.h): the rules every such table is
+// cosim_scenario_params_set, cosim_set_param "obs_faults" / "action_faults" / "search", cosim_scenario_checks_set, cosim_scenario_curves_set, include/cosim.h): the rules every such table is
 // held to, one validator per setter, and the packer that lays a table's arrays into one allocation.  Plain C++ with no HIP in it:
 // cosim_engine.hip and a host program (tests/tables_host.cpp) both compile it.
 //
@@ -18,6 +18,7 @@
 #include "cosim_curves.h"
 #include "cosim_obsfault.h"
 #include "cosim_scnparams.h"
+#include "cosim_search.h"
 
 namespace cosim {
 
@@ -404,6 +405,58 @@ inline bool curves_same_sizes(const WordPacker& pk, const CurTable& tab, const i
   return pk.same(&tab.adr, old) && pk.same(&tab.bins, old) && pk.same(&tab.nt, old) && pk.same(&tab.soff, old) && pk.same(&tab.coff, old) &&
          pk.same(&tab.cw, old);
 }
+
+// ---- cosim_set_param "search".  Image: has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip, [S] each
+struct SrchRaw {
+  int n_scn;   // the table's first word
+  int slots;
+  const int32_t* has; const float *lo, *hi, *x0, *d0, *d_min; const int32_t *rule, *trials, *targets, *fail_mask, *rev_skip;
+};
+// what the validator needs to know of the scenario table that is set; key_adr / push_adr: its row addresses [S + 1] (read only once S matches)
+struct SrchDims { int n_scn, mode, auto_reset; const int32_t *key_adr, *push_adr; };
+struct SrchShape { std::string err; int n = 0; };   // n: scenarios that have an item
+
+// A fall bit in fail_mask while no fall rule is set is NOT refused: the bit never fires (the rule may be set later).
+inline SrchShape validate_search(const SrchDims& d, const SrchRaw& r) {
+  const std::string fn = "cosim_set_param \"search\"";
+  SrchShape v;
+  if (d.n_scn == 0) TAB_TRY(fn + ": no scenario table is set (cosim_scenario_set): a search item is a row of a table; set the table first");
+  if (r.n_scn != d.n_scn) TAB_TRY(fn + ": " + std::to_string(r.n_scn) + " scenarios, the table that is set has " + std::to_string(d.n_scn));
+  if (d.mode == SCN_MODE_CYCLE) TAB_TRY(fn + ": the scenario mode is cycle: the search keeps one record per env, which needs the env's row to stay (mode env)");
+  if (!d.auto_reset) TAB_TRY(fn + ": the search needs auto_reset: without it no episode follows the one that ended");
+  if (r.slots < 1 || r.slots > SRCH_MAX_SLOTS) TAB_TRY(fn + ": slots " + std::to_string(r.slots) + " outside 1..64");
+  for (int s = 0; s < r.n_scn; s++) {
+    const std::string who = fn + ": scenario " + std::to_string(s);
+    if (r.has[s] != 0 && r.has[s] != 1) TAB_TRY(who + ": has " + std::to_string(r.has[s]) + " is neither 0 nor 1");
+    if (!r.has[s]) continue;
+    v.n++;
+    if (!std::isfinite(r.lo[s]) || !std::isfinite(r.hi[s])) TAB_TRY(who + ": lo / hi is not finite");
+    if (!(r.lo[s] < r.hi[s])) TAB_TRY(who + ": hi is not above lo");
+    if (!(r.x0[s] >= r.lo[s] && r.x0[s] <= r.hi[s])) TAB_TRY(who + ": the start level lies outside [lo, hi]");
+    if (!std::isfinite(r.d0[s]) || !(r.d_min[s] > 0.f) || !(r.d_min[s] <= r.d0[s])) TAB_TRY(who + ": the steps must hold 0 < d_min <= d0");
+    if (r.rule[s] != SRCH_BISECT && r.rule[s] != SRCH_STAIRCASE) TAB_TRY(who + ": unknown rule " + std::to_string(r.rule[s]) + " (0 bisect, 1 staircase)");
+    if (r.trials[s] < 1 || r.trials[s] > SRCH_MAX_TRIALS) TAB_TRY(who + ": trials " + std::to_string(r.trials[s]) + " outside 1..2^20");
+    if (r.targets[s] < 1 || r.targets[s] > (SRCH_PUSHES | SRCH_COMMANDS)) TAB_TRY(who + ": targets " + std::to_string(r.targets[s]) + " names nothing (1 pushes | 2 commands)");
+    if (r.fail_mask[s] == 0 || (r.fail_mask[s] & ~SRCH_FAIL_BITS))
+      TAB_TRY(who + ": fail_mask " + std::to_string(r.fail_mask[s]) + " must be a non-empty set of 1 terminated | 4 non-finite | 32 tilt | 64 height | 128 contact");
+    if (r.rev_skip[s] < 0 || r.rev_skip[s] > SRCH_MAX_REV_SKIP) TAB_TRY(who + ": rev_skip " + std::to_string(r.rev_skip[s]) + " outside 0..255");
+    if ((r.targets[s] & SRCH_PUSHES) && d.push_adr[s + 1] == d.push_adr[s]) TAB_TRY(who + ": the target is the pushes and the scenario has no push window");
+    if ((r.targets[s] & SRCH_COMMANDS) && d.key_adr[s + 1] == d.key_adr[s]) TAB_TRY(who + ": the target is the commands and the scenario has no keyframe");
+  }
+  if (v.n == 0) TAB_TRY(fn + ": the table holds no search item (the one word 0 clears the search)");
+  return v;
+}
+
+inline void pack_search(WordPacker& pk, SrchTable& tab, const SrchRaw& r, const SrchShape& v) {
+  const size_t S = (size_t)r.n_scn;
+  pk.add(&tab.has, r.has, S); pk.add(&tab.lo, r.lo, S); pk.add(&tab.hi, r.hi, S); pk.add(&tab.x0, r.x0, S); pk.add(&tab.d0, r.d0, S);
+  pk.add(&tab.d_min, r.d_min, S); pk.add(&tab.rule, r.rule, S); pk.add(&tab.trials, r.trials, S); pk.add(&tab.targets, r.targets, S);
+  pk.add(&tab.fail_mask, r.fail_mask, S); pk.add(&tab.rev_skip, r.rev_skip, S);
+  tab.n_scn = r.n_scn; tab.n_items = v.n;
+}
+
+// A table of the S of the one whose image `old` is may be written over it, the records kept, if the same scenarios have an item.
+inline bool search_same_rows(const WordPacker& pk, const SrchTable& tab, const int32_t* old) { return pk.same(&tab.has, old); }
 
 #undef TAB_TRY
 

@@ -77,7 +77,7 @@ _ABI_ROWS = (
     ("cosim_create", _ci, [_vp, _vp, _vp, _vp, _vp, _vp, _ci, _ci, ctypes.c_uint64, ctypes.c_int64, _pvp]),
     ("cosim_destroy", _ci, [_vp]),
     ("cosim_query", _ci, [_vp, _cs]),
-    ("cosim_set_param", _ci, [_vp, _cs, _vp, _ci]),      # also the word tables "obs_faults" and "action_faults": no entry point of their own
+    ("cosim_set_param", _ci, [_vp, _cs, _vp, _ci]),      # also the word tables "obs_faults", "action_faults" and "search": no entry point of their own
     ("cosim_reset", _ci, [_vp] * 5),
     ("cosim_step", _ci, [_vp] * 8),
     ("cosim_step_range", _ci, [_vp, _ci, _ci] + [_vp] * 7),
@@ -431,6 +431,12 @@ class Engine:
         """Action faults, through ``cosim_set_param "action_faults"``: ``csr`` = the six host arrays ``(adr, t, actuator, op, ord,
         value)`` of ``ScenarioTable.pack_action_faults`` (``None``: clear the faults), the word table of the observation faults."""
         self._word_table_set("scenario_action_faults_set", b"action_faults", csr)
+
+    def search_set(self, words):
+        """Limit search, through ``cosim_set_param "search"``: ``words`` = the int32 word table of ``ScenarioTable.pack_search`` (``S |
+        slots | has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip``; ``None``: clear the search)."""
+        words = np.zeros(1, dtype=np.int32) if words is None else np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+        self._check(self.L.cosim_set_param(self.h, b"search", words.ctypes.data, int(words.size)))
 
     def scenario_checks_set(self, csr, slots: int = 0):
         """``cosim_scenario_checks_set``: ``csr`` = the seven host arrays ``(adr, t, signal, index, mode, cmp, bound)`` of

@@ -163,6 +163,8 @@ class FleetReporter:
             if "by_group" in cs:                                       # set_curve_groups(policy table): the planes are the policies
                 cs["by_policy"] = cs.pop("by_group")
             out.setdefault("episodes", {})["curves"] = cs
+        if getattr(self.env, "search_slots", 0) > 0:
+            out.setdefault("episodes", {})["search"] = self.search()
         return out
 
     def fleet_curves(self):
@@ -189,6 +191,17 @@ class FleetReporter:
             cv = Curves(cells, cv.adr, cv.spec, cv.lohi, cv.bins, cv.names, groups=cv.groups, group_names=cv.group_names if cv.grouped else None,
                         ungrouped=int(lost.item()))
         return cv
+
+    def search(self) -> dict:
+        """The env's limit search (``BatchedEnv(scenarios=TABLE, search=SLOTS)``) summarised: ``SearchResult.summary()`` plus
+        ``by_scenario``.  Under ``torch.distributed`` the integer counts are all-reduced (``fleet``); the thresholds stay this rank's."""
+        import torch.distributed as dist
+        r = self.env.search(include_trials=False)
+        out = r.summary()
+        out["by_scenario"] = {str(k): x for k, x in r.by_scenario().items()}
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+            out["fleet"] = self._allreduce_counts(r.counts())
+        return out
 
     def checks(self) -> dict:
         """The verdicts of the env's scenario checks (``BatchedEnv(scenarios=TABLE, check_slots=SLOTS)``) summarised:

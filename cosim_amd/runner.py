@@ -53,6 +53,10 @@ class Runner:
         if getattr(policy, "rotate_every", None) is not None and not env.auto_reset:
             raise ValueError(f"Runner: {type(policy).__name__}(rotate_every={policy.rotate_every}) moves an env to its next policy when an episode "
                              "ends, which needs an env built with auto_reset=True (as scenario mode 'cycle' does)")
+        if getattr(env, "search_slots", 0) > 0 and not env.auto_reset:
+            raise ValueError(f"Runner: the env's limit search (search={env.search_slots}) moves an env's level when an episode "
+                             "ends, which needs an env built with auto_reset=True (as scenario mode 'cycle' does)")
+        self.until, self.until_poll = None, 50                     # stop_when(fn, poll): checked every `poll` steps by every loop
 
     def update_command(self, index: int, value: float):            # tester.py:41-46
         if index < self.env.command_dim:
@@ -66,6 +70,16 @@ class Runner:
 
     def stop(self):
         self._stop = True
+
+    def stop_when(self, fn: Optional[Callable[[], bool]], poll: int = 50):
+        """End a run once ``fn()`` is true: every loop asks after every ``poll``-th control step, between graph replays under
+        ``test_graphed`` (``fn`` may synchronise, e.g. ``env.search_remaining() == 0``).  ``None`` clears it."""
+        if int(poll) < 1:
+            raise ValueError(f"Runner.stop_when: poll {poll!r} must be >= 1")
+        self.until, self.until_poll = fn, int(poll)
+
+    def _until(self, steps: int) -> bool:
+        return self.until is not None and steps > 0 and steps % self.until_poll == 0 and bool(self.until())
 
     def _one_env_info(self, info: dict, i: int) -> dict:
         out = {}
@@ -104,7 +118,7 @@ class Runner:
             steps = resume.steps
         start = steps
         done_all, done_seen = False, None
-        while not done_all and not self._stop and (max_steps is None or steps - start < max_steps):
+        while not done_all and not self._stop and (max_steps is None or steps - start < max_steps) and not self._until(steps - start):
             if before_step is not None:
                 before_step(steps)
             env.receive_user_command(self.user_command)            # tester.py:68
@@ -167,7 +181,7 @@ class Runner:
             st.wait_stream(cur)                                    # the reset, the command upload and `action` are ready
         ring = [[t.cuda.Event() for _ in range(max(inflight, 1))] for _ in env.range_list]
         steps = 0
-        while steps < max_steps and not self._stop:
+        while steps < max_steps and not self._stop and not self._until(steps):
             if self._push_event or not np.array_equal(last_cmd, self.user_command):
                 env.join()                                         # whole-fleet inputs change: the ranges meet here
                 t.cuda.current_stream(env.device).synchronize()
@@ -243,7 +257,7 @@ class Runner:
         with t.cuda.graph(graph):
             one_step()
         steps = warmup                            # capturing records the step, it does not run it
-        while steps < max_steps and not self._stop:
+        while steps < max_steps and not self._stop and not self._until(steps):
             env.receive_user_command(self.user_command)
             if self._push_event:
                 env.event("push", self._push_vel)

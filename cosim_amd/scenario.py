@@ -59,6 +59,13 @@ step kernel was given one step earlier (the effective one: a held channel stays 
 ``"clip"`` ``x > value ? value : (x < -value ? -value : x)`` (a saturating output; NaN stays NaN).  At episode step 0 ``"hold"`` / ``"drop"``
 change nothing.  ``last_action`` in the observation stays the policy's own output.  At most 256 items per scenario after expansion.
 ``reference_action_faults`` is the numpy twin of one step of the kernel's rule, exact.
+
+Limit search (``cosim_set_param "search"``, csrc/cosim_search.hip): a scenario may hold ONE ``"search": {"lo", "hi", "start" = the
+middle, "step" = (hi - lo) / 4, "min_step" = (hi - lo) / 256, "rule": "bisect" | "staircase", "trials", "targets": ["pushes" |
+"commands", ...], "fail_on": ["terminated" | "nonfinite" | "tilt" | "height" | "contact", ...], "rev_skip" = 0}``: every env of the row
+keeps a level in ``[lo, hi]`` that is multiplied into the row's push vectors and / or command keyframes and moved when an episode of
+the env ends -- down after a failure (an ended episode with one of the ``fail_on`` ledger flags), up after a pass.  ``cosim_amd/search.py``
+has the result container and the numpy twin; ``reference_schedule(level=...)`` is the twin of the scaled schedule.
 """
 from __future__ import annotations
 
@@ -85,6 +92,11 @@ REFUSED_PARAM_FIELDS = ("body_mass", "body_invweight0", "dof_invweight0", "meani
 FAULT_OPS = {"scale": 0, "bias": 1, "set": 2, "noise": 3, "hold": 4, "drop": 5}
 ACTION_FAULT_OPS = dict(FAULT_OPS, clip=6)
 MAX_FAULT_ITEMS = MAX_ACTION_FAULT_ITEMS = 256
+SEARCH_RULES = {"bisect": 0, "staircase": 1}
+SEARCH_TARGETS = {"pushes": 1, "commands": 2}
+SEARCH_FAIL_ON = {"terminated": 1, "nonfinite": 4, "tilt": 32, "height": 64, "contact": 128}   # the ledger's flag values
+MAX_SEARCH_SLOTS, MAX_SEARCH_TRIALS, MAX_SEARCH_REV_SKIP = 64, 1 << 20, 255
+_SEARCH_KEYS = ("lo", "hi", "start", "step", "min_step", "rule", "trials", "targets", "fail_on", "rev_skip")
 
 
 class _FaultKind(NamedTuple):
@@ -196,9 +208,10 @@ class ScenarioTable:
         self.curve_rows, self.curves = [], None
         self.fault_rows, self.faults = [], None                   # (the attributes the two _FaultKind name)
         self.action_fault_rows, self.action_faults = [], None
+        self.search = []                                          # per scenario: None or the item as a dict of _SEARCH_KEYS
         for s, sc in enumerate(scenarios):
             sc = sc or {}
-            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "faults", "action_faults", "name"}:
+            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "faults", "action_faults", "search", "name"}:
                 raise ValueError(f"ScenarioTable: scenario {s}: a mapping with the keys 'commands' and 'pushes' is expected, got {sc!r}")
             keys, pushes = [], []
             for r, row in enumerate(sc.get("commands") or []):
@@ -235,6 +248,7 @@ class ScenarioTable:
             self.curve_rows.append(_curve_rows(s, sc.get("curves") or []))
             for kind in FAULT_KINDS:
                 getattr(self, kind.rows).append(_fault_kind_rows(kind, s, sc.get(kind.key) or []))
+            self.search.append(_search_item(s, sc.get("search"), bool(pushes), bool(keys)))
         if names is not None or not self.has_params:
             self.resolve(names or {})
         cn = (names or {}).get("checks")
@@ -429,6 +443,46 @@ class ScenarioTable:
         """Per scenario, the names of its curve items (the given name, or one made from the item's fields)."""
         return [[it[8] for it in c] for c in self._resolved_curves()]
 
+    # ---- limit search: at most one item per scenario
+    @property
+    def has_search(self) -> bool:
+        return any(it is not None for it in self.search)
+
+    def pack_search(self, slots: int) -> np.ndarray:
+        """The int32 word table ``cosim_set_param "search"`` takes: ``S | slots | has[S] | lo | hi | x0 | d0 | d_min | rule | trials |
+        targets | fail_mask | rev_skip`` (``[S]`` each, floats as their bits; zeros for a scenario without an item)."""
+        if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)) or not 1 <= int(slots) <= MAX_SEARCH_SLOTS:
+            raise ValueError(f"ScenarioTable: search slots {slots!r}: an integer 1..{MAX_SEARCH_SLOTS}")
+        S = len(self)
+        f, i = np.zeros((5, S), dtype=np.float32), np.zeros((5, S), dtype=np.int32)
+        has = np.zeros(S, dtype=np.int32)
+        for s, it in enumerate(self.search):
+            if it is None:
+                continue
+            has[s] = 1
+            f[:, s] = [it["lo"], it["hi"], it["start"], it["step"], it["min_step"]]
+            i[:, s] = [SEARCH_RULES[it["rule"]], it["trials"], sum(SEARCH_TARGETS[t] for t in it["targets"]),
+                       sum(SEARCH_FAIL_ON[t] for t in it["fail_on"]), it["rev_skip"]]
+        return np.concatenate([np.array([S, int(slots)], dtype=np.int32), has, f.view(np.int32).reshape(-1), i.reshape(-1)])
+
+    def search_from_words(self, words) -> "ScenarioTable":
+        """A table with everything of this one but the search items, which are those the word table of ``pack_search`` holds."""
+        words = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+        scn = self.to_list()
+        S = len(scn)
+        if len(words) != 2 + 11 * S or int(words[0]) != S:
+            raise ValueError(f"ScenarioTable: a search table of {int(words[0]) if len(words) else 0} scenarios in {len(words)} words, the table has {S}")
+        cols = words[2:].reshape(11, S)
+        fl = np.ascontiguousarray(cols[1:6]).view(np.float32)
+        for s, sc in enumerate(scn):
+            sc.pop("search", None)
+            if cols[0, s]:
+                sc["search"] = {"lo": float(fl[0, s]), "hi": float(fl[1, s]), "start": float(fl[2, s]), "step": float(fl[3, s]), "min_step": float(fl[4, s]),
+                                "rule": {v: k for k, v in SEARCH_RULES.items()}.get(int(cols[6, s]), int(cols[6, s])), "trials": int(cols[7, s]),
+                                "targets": [k for k, v in SEARCH_TARGETS.items() if int(cols[8, s]) & v],
+                                "fail_on": [k for k, v in SEARCH_FAIL_ON.items() if int(cols[9, s]) & v], "rev_skip": int(cols[10, s])}
+        return type(self)(scn, self.command_dim)
+
     @property
     def has_checks(self) -> bool:
         return any(self.check_rows)
@@ -547,6 +601,9 @@ class ScenarioTable:
             for sc, rows in zip(out, getattr(self, kind.rows)):
                 if rows:
                     sc[kind.key] = [[*row[:-2], float(row[-2])] + ([row[-1]] if row[-1] is not None else []) for row in rows]
+        for sc, it in zip(out, self.search):
+            if it is not None:
+                sc["search"] = {k: (list(it[k]) if isinstance(it[k], list) else it[k]) for k in _SEARCH_KEYS}
         return out
 
     def pack(self):
@@ -824,9 +881,56 @@ def _check_rows(s: int, rows) -> list:
     return out
 
 
+def _search_item(s: int, item, has_pushes: bool, has_keys: bool):
+    """The ``"search"`` value of scenario ``s`` as a dict of ``_SEARCH_KEYS`` with the defaults filled in and the floats rounded to
+    float32 (what the device holds), or ``None``.  Raises ``ValueError`` naming the scenario."""
+    if item is None:
+        return None
+    who = f"ScenarioTable: scenario {s}, search"
+    if not isinstance(item, dict) or set(item) - set(_SEARCH_KEYS):
+        raise ValueError(f"{who}: a mapping with keys out of {_SEARCH_KEYS} is expected, got {item!r}")
+    for k in ("lo", "hi", "rule", "trials", "targets", "fail_on"):
+        if k not in item:
+            raise ValueError(f"{who}: '{k}' is missing")
+    try:
+        lo, hi = float(item["lo"]), float(item["hi"])
+        start = float(item["start"]) if item.get("start") is not None else (lo + hi) / 2
+        step = float(item["step"]) if item.get("step") is not None else (hi - lo) / 4
+        min_step = float(item["min_step"]) if item.get("min_step") is not None else (hi - lo) / 256
+    except (TypeError, ValueError):
+        raise ValueError(f"{who}: lo, hi, start, step and min_step must be numbers") from None
+    lo, hi, start, step, min_step = (float(np.float32(x)) for x in (lo, hi, start, step, min_step))
+    if not (math.isfinite(lo) and math.isfinite(hi)) or not lo < hi:
+        raise ValueError(f"{who}: lo {lo} and hi {hi} must be finite with lo < hi")
+    if not lo <= start <= hi:
+        raise ValueError(f"{who}: start {start} lies outside [{lo}, {hi}]")
+    if not (math.isfinite(step) and 0 < min_step <= step):
+        raise ValueError(f"{who}: the steps must hold 0 < min_step <= step, got min_step {min_step}, step {step}")
+    rule = item["rule"]
+    if rule not in SEARCH_RULES:
+        raise ValueError(f"{who}: unknown rule {rule!r} ({', '.join(SEARCH_RULES)})")
+    trials, rev_skip = item["trials"], item.get("rev_skip", 0)
+    if isinstance(trials, bool) or not isinstance(trials, (int, np.integer)) or not 1 <= int(trials) <= MAX_SEARCH_TRIALS:
+        raise ValueError(f"{who}: trials {trials!r}: an integer 1..2^20")
+    if isinstance(rev_skip, bool) or not isinstance(rev_skip, (int, np.integer)) or not 0 <= int(rev_skip) <= MAX_SEARCH_REV_SKIP:
+        raise ValueError(f"{who}: rev_skip {rev_skip!r}: an integer 0..{MAX_SEARCH_REV_SKIP}")
+    out = {"lo": lo, "hi": hi, "start": start, "step": step, "min_step": min_step, "rule": rule, "trials": int(trials)}
+    for key, known in (("targets", SEARCH_TARGETS), ("fail_on", SEARCH_FAIL_ON)):
+        names = item[key]
+        if isinstance(names, str) or not isinstance(names, (list, tuple)) or not names or len(set(names)) != len(names) or any(n not in known for n in names):
+            raise ValueError(f"{who}: {key} {names!r}: a non-empty list of different names out of {', '.join(known)}")
+        out[key] = [n for n in known if n in names]
+    if "pushes" in out["targets"] and not has_pushes:
+        raise ValueError(f"{who}: the target is the pushes and the scenario has no push window")
+    if "commands" in out["targets"] and not has_keys:
+        raise ValueError(f"{who}: the target is the commands and the scenario has no keyframe")
+    out["rev_skip"] = int(rev_skip)
+    return out
+
+
 def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = (),
           params: Iterable = (), checks: Iterable = (), curves: Iterable = (), faults: Iterable = (),
-          action_faults: Iterable = ()) -> Iterator[dict]:
+          action_faults: Iterable = (), search: Iterable = ()) -> Iterator[dict]:
     """The cartesian product command rows x push speeds x directions x push times as scenarios, commands outermost: each holds its
     command from episode step 0 and one push of ``speed`` m/s along the world direction ``angle`` (radians about z, 0 = +x) held over
     ``(t0, t1)``.  With no speeds or no times the product is over the commands alone (no push).
@@ -837,7 +941,17 @@ def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable =
     ``"curves"`` value, possibly empty) is one more axis, inside the checks.  ``faults``: a list of fault lists (each a scenario's
     ``"faults"`` value, possibly empty) is one more axis, inside the curves: ``len(...) * len(F)`` scenarios.  ``action_faults``: a list
     of action-fault lists (each a scenario's ``"action_faults"`` value, possibly empty) is one more axis, inside the faults and innermost
-    of all: ``len(...) * len(A)`` scenarios."""
+    of the tables: ``len(...) * len(A)`` scenarios.  ``search``: a list of search items (each a scenario's ``"search"`` value, or ``None``
+    for a scenario without one) is one more axis, innermost of all: ``len(...) * len(L)`` scenarios."""
+    search = list(search)
+    if search:
+        for sc in sweep(commands, push_speeds, directions, push_times, params, checks, curves, faults, action_faults):
+            for item in search:
+                out = dict(sc)
+                if item is not None:
+                    out["search"] = dict(item)
+                yield out
+        return
     action_faults = [list(f) for f in action_faults]
     if action_faults:
         for sc in sweep(commands, push_speeds, directions, push_times, params, checks, curves, faults):
@@ -905,24 +1019,30 @@ def scenario_rows(n_scn: int, mode, gid, ep) -> np.ndarray:
     return row.astype(np.int32)
 
 
-def reference_schedule(table: ScenarioTable, mode, gid, t, ep, base_cmd):
+def reference_schedule(table: ScenarioTable, mode, gid, t, ep, base_cmd, level=None):
     """Numpy twin of ``scenario_step_kernel`` for N envs: global ids ``gid``, episode steps ``t`` (meta word 0), episodes ended ``ep``
     (meta word 11), the caller's commands ``base_cmd`` ``[N, >= command_dim]``.  Returns ``(row int32[N], cmd float32[N,
     command_dim], push_mask bool[N], push_v float32[N, 3])``: the command each env is given and the world velocity of the push that
-    is due (zero rows where none is).  Rows and commands are exact."""
+    is due (zero rows where none is).  Rows and commands are exact.  ``level`` (float32 ``[N]``): the twin of
+    ``scenario_search_step_kernel`` -- where the env's row has a search item, a selected keyframe row (target ``"commands"``) and the
+    push that is due (target ``"pushes"``) are multiplied by the env's level, one float32 multiply per word; a passed-through caller's
+    command and rows without an item are not scaled."""
     gid, t = np.asarray(gid, dtype=np.int64).reshape(-1), np.asarray(t, dtype=np.int64).reshape(-1)
     N, cd = len(gid), table.command_dim
     row = scenario_rows(len(table), mode, gid, np.asarray(ep).reshape(-1))
     cmd = np.array(np.asarray(base_cmd, dtype=np.float32).reshape(N, -1)[:, :cd], dtype=np.float32)
     mask, v = np.zeros(N, dtype=bool), np.zeros((N, 3), dtype=np.float32)
+    level = None if level is None else np.asarray(level, dtype=np.float32).reshape(N)
     for i in range(N):
+        item = table.search[row[i]] if level is not None else None
+        targets = item["targets"] if item is not None else ()
         for kt, c in table.keys[row[i]]:
             if kt > t[i]:
                 break
-            cmd[i] = c
+            cmd[i] = c * level[i] if "commands" in targets else c
         for t0, t1, pv in table.pushes[row[i]]:
             if t0 <= t[i] < t1:
-                mask[i], v[i] = True, pv
+                mask[i], v[i] = True, (pv * level[i] if "pushes" in targets else pv)
     return row, cmd, mask, v
 
 

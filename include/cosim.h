@@ -466,6 +466,52 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  * cosim_debug_forward ignore the faults.  cosim_query "action_faults" answers the number of items (0: none); cosim_get
  * "action_effective" / "action_raw" copy the last step's buffers [N][nu] to device memory (COSIM_EINVAL while no faults are set). */
 
+/* Limit search of the scenario table that is set: a per-env staircase on the scale of a scenario's pushes and commands, moved on the
+ * device by the outcome of the env's own episodes (cosim_amd/csrc/cosim_search.h has the rule).  Like the faults it has no entry point
+ * of its own: the table travels through cosim_set_param(e, "search", words, count), `words` pointing at `count` 32-BIT WORDS:
+ *   S | slots | has[S] | lo[S] | hi[S] | x0[S] | d0[S] | d_min[S] | rule[S] | trials[S] | targets[S] | fail_mask[S] | rev_skip[S]
+ * (int32 but for lo .. d_min, float bits; count = 2 + 11 S); the one word 0 clears the search.  A scenario carries at most one item
+ * (has[s] = 1): lo < hi finite bounds of the LEVEL, lo <= x0 <= hi its start, 0 < d_min <= d0 the start and the smallest step, rule 0
+ * bisect | 1 staircase, trials 1 .. 2^20 the budget of counted episodes, targets 1 push vectors | 2 command keyframes, fail_mask a
+ * non-empty set of the ledger's flags 1 terminated | 4 non-finite | 32 tilt | 64 height | 128 contact, rev_skip 0 .. 255 reversals left
+ * out of the running mean.  slots (1..64): trial records kept per env.
+ * Per env SRCH_NCNT = 16 int32 words (all floats fp32, no contraction): 0 level  1 step  2 trials  3 fails  4 last_dir (0 / +1 / -1)
+ * 5 reversals  6 rev_sum  7 rev_n  8 hi_pass  9 lo_fail  10 status (1 the open episode began at a reset | 2 done | 4 has a pass | 8 has a
+ * fail | 16 the env's row has an item)  11 episodes ended since arming (the ledger's ordinal)  12 length of the open episode  13 meta
+ * word 4 at its start  14 ended episodes that were not trials  15 zero.
+ * While a search is armed scenario_search_step_kernel runs IN THE PLACE OF scenario_step_kernel (same shape, same sites): where the
+ * env's row has an item, the selected keyframe row is key_cmd[c] * level (targets 2; a passed-through caller's command is never scaled)
+ * and the push that is due is (v0 * level, v1 * level, v2 * level) into the push arithmetic (targets 1); other rows take the unscaled
+ * expressions.  search_step_kernel runs behind every range's last launch of a control step, behind the curves', on the range's own
+ * stream: it counts the open episode's length and, on a row with terminated | truncated, builds the ledger's flags (1 | 2 | 4 if meta
+ * word 4 moved | 8 if status bit 1 is clear | (meta word 15 & 7) << 5 while a fall rule is set).  The episode is a COUNTED TRIAL iff the
+ * row has an item, the env is not done and status bit 1 is set (an episode that began at cosim_restore / cosim_set may have missed its
+ * push window); then, with x = level, fail = (flags & fail_mask) != 0, dir = fail ? -1 : +1:
+ *   fail ? lo_fail = has_fail ? fminf(lo_fail, x) : x  :  hi_pass = has_pass ? fmaxf(hi_pass, x) : x
+ *   rev = last_dir != 0 && dir != last_dir;  if (rev) { reversals++; if (reversals > rev_skip) { rev_sum += x; rev_n++; } }
+ *   staircase: if (rev) step = fmaxf(step * 0.5f, d_min);  x' = x + dir * step
+ *   bisect:    x' = x + dir * step;  step = fmaxf(step * 0.5f, d_min)
+ *   level = fminf(fmaxf(x', lo), hi);  last_dir = dir;  trials++;  fails += fail;  trials >= budget: done, and 1 is taken off the
+ *   engine's one "remaining" word (the only atomic)
+ * An episode that is not counted adds 1 to word 14.  Either way episode++, length = 0, word 13 is refreshed, status bit 1 is set (the
+ * auto-reset began the next episode) and one trial record {episode, the level the episode RAN at, flags | 256 counted | 512 fail | 1024
+ * reversal, length} goes into slot episode mod slots of the env's ring.  Behind cosim_reset / cosim_restore / cosim_set the masked envs'
+ * status bit 1 becomes (flag == 0), length 0 and word 13 is refreshed: the open episode is discarded as the ledger discards it, the
+ * level does not move.  No LDS, no cross-lane traffic, no host read, no join: a captured step carries the launches.
+ * Validated on the host before anything is changed, the message naming the scenario (COSIM_EINVAL): S must be the "scenario_rows" of
+ * the table that is set; the scenario mode must be env (the state is one record per env); the engine needs auto_reset; a target must
+ * have rows to scale (pushes / keyframes of that scenario); the ranges of every field above.  A fall bit in fail_mask while no fall
+ * rule is set is NOT refused: the bit never fires.  The call joins the ranges and blocks until the device is idle.  A table with the S,
+ * the slots and the has[] of the one that is armed rewrites the items in place and KEEPS the records, so a captured graph picks new
+ * bounds up; anything else allocates anew and begins every env at x0 / d0 with an empty ring (search_init_kernel).  cosim_scenario_set
+ * with another S or with mode cycle, or clearing the table, drops the search.  A step without info_out_dev is not refused for the
+ * search alone (it reads no info row).  cosim_rollout stays refused (a scenario table is set); cosim_profile_step and
+ * cosim_debug_forward ignore the search.  cosim_query answers "search" (items armed, 0: none), "search_slots" and "search_remaining"
+ * (envs with an item and trials left: joins the ranges and reads the one word); cosim_get "search_state" copies int32 [N][16],
+ * "search_trials" int32 [N][slots][4] to device memory (COSIM_EINVAL while no search is armed).  Out of scope: a level that scales
+ * parameter windows or fault values (the level is a plain per-env word so that those kernels can read it later), a check verdict as
+ * the failure criterion, mode cycle, the search state in a snapshot, anything inside cosim_rollout. */
+
 /* Checks of the scenario table that is set: per-scenario pass / fail criteria judged on the device (cosim_amd/csrc/cosim_checks.h has
  * the rule).  Scenario s owns the items [adr[s], adr[s + 1]) (at most 64).  Item i takes one sample per control step whose PRE-STEP
  * episode clock t (meta word 0 as the scenario kernel read it ahead of that step) holds t[2i] <= t < t[2i + 1]:
