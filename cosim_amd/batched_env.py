@@ -275,6 +275,7 @@ class BatchedEnv:
         self.check_slots = 0
         self.curves_armed = False
         self.search_slots = 0
+        self._search_marked, self._search_checks = (), False   # fault kinds whose items the armed search marks; it fails on a check
         self._curve_groups = None                                   # (tensor, G, names) of set_curve_groups: the tensor is kept alive here
         scenarios = scenarios if scenarios is not None else eng_cfg.get("scenarios")
         if scenarios is not None:
@@ -713,9 +714,11 @@ class BatchedEnv:
         same ``search`` rewrites the items in place and KEEPS the records (captured graphs pick the new bounds up); any other call
         begins every search anew.  ``None`` / 0: the search is not armed (what an earlier call armed is cleared).  Set the ledger and
         the search together and their episode ordinals agree.  Needs ``auto_reset`` and mode ``"env"``.  A ``"tilt"`` / ``"height"`` /
-        ``"contact"`` in ``fail_on`` while no fall rule is set is accepted and never fires.  Limits: the level scales pushes and
-        commands only, not parameter windows or fault values; a check verdict is no failure criterion; the records are not part of a
-        ``snapshot()``; per-rank thresholds are not merged."""
+        ``"contact"`` in ``fail_on`` while no fall rule is set is accepted and never fires.  An item whose ``targets`` name
+        ``"params"`` / ``"faults"`` / ``"action_faults"`` (or ``"kind:i,j"``) has the level multiplied into the values of those listed items (the items
+        are sent marked, behind the search: the engine takes them only while it is armed); ``"harder": "down"`` moves the level up
+        after a failure; a ``"checks"`` / ``"check:NAME"`` / ``"check:I"`` in ``fail_on`` fails a trial whose selected check did not
+        pass and needs ``check_slots``.  Limits: the records are not part of a ``snapshot()``; per-rank thresholds are not merged."""
         from .scenario import MODES, ScenarioTable
         t = self.torch
         if scenarios is None:
@@ -738,51 +741,100 @@ class BatchedEnv:
             table.resolve_checks(self.check_names())
         if curves and table.has_curves:
             table.resolve_curves(self.check_names())
-        if self._cmd_out is None:                                   # persistent: captured graphs hold these pointers
-            self._cmd_out = t.zeros_like(self.user_command)
-            self._row_out = t.zeros((self.num_envs,), dtype=t.int32, device=self.device)
+        will_search = bool(search) and table.has_search
+        if will_search:
+            for s_, it in enumerate(table.search):
+                if it is not None and it["check_mask"] and not (check_slots and table.has_checks):
+                    raise ValueError(f"set_scenarios: scenario {s_}, search: fail_on {it['fail_on']!r} names a check and the checks are not armed "
+                                     "(pass check_slots)")
+        old_table, old_marked = self.scenario_table, self._search_marked
         try:
-            self.engine.scenario_set(table.pack(), MODES[mode], self._cmd_out.data_ptr() if self.command_dim > 0 else None,
-                                     self._row_out.data_ptr(), self._stream())
-        except Exception:
-            if self.engine.query("scenario_rows") == 0:             # the engine dropped its table (a failed upload): so does the env
-                self._drop_scenarios()
+            # What the armed search holds in place comes off first: marked fault items are rewritten unmarked (in place: same items), and a
+            # search that fails on a check is disarmed where the next one does not.
+            for key in self._search_marked:
+                self._send_items(self.scenario_table, key, False)
+            self._search_marked = ()
+            if self._search_checks and not (will_search and any(it is not None and it["check_mask"] for it in table.search)):
+                self.engine.search_set(None)
+                self.search_slots, self._search_checks = 0, False
+            if self._cmd_out is None:                                   # persistent: captured graphs hold these pointers
+                self._cmd_out = t.zeros_like(self.user_command)
+                self._row_out = t.zeros((self.num_envs,), dtype=t.int32, device=self.device)
+            try:
+                self.engine.scenario_set(table.pack(), MODES[mode], self._cmd_out.data_ptr() if self.command_dim > 0 else None,
+                                         self._row_out.data_ptr(), self._stream())
+            except Exception:
+                if self.engine.query("scenario_rows") == 0:             # the engine dropped its table (a failed upload): so does the env
+                    self._drop_scenarios()
+                raise
+            self.scenario_table, self.scenario_mode = table, mode
+            self._info_views = None
+            # parameter windows ride with the table: set the ones it holds, clear what an earlier table left
+            if table.has_params:
+                self.engine.scenario_params_set(table.pack_params())
+            elif self.engine.query("scenario_param_items") > 0:
+                self.engine.scenario_params_set(None)
+            for kind in FAULT_KINDS:                                    # so do the observation and the action faults
+                if any(getattr(table, kind.rows)):
+                    getattr(self.engine, kind.setter)(table._pack_fault_items(kind))
+                elif self.engine.query(kind.param) > 0:
+                    getattr(self.engine, kind.setter)(None)
+            # so do the checks, once they are armed
+            self.check_slots = 0
+            if check_slots and table.has_checks:
+                self.engine.scenario_checks_set(table.pack_checks(), check_slots)
+                self.check_slots = check_slots
+            elif self.engine.query("scenario_check_items") > 0:
+                self.engine.scenario_checks_set(None)
+            # and the curves
+            self.curves_armed = False
+            if curves and table.has_curves:
+                self.engine.scenario_curves_set(table.pack_curves())
+                self.curves_armed = True
+            elif self.engine.query("scenario_curve_items") > 0:
+                self.engine.scenario_curves_set(None)
+            if not self.curves_armed or self.engine.query("scenario_curve_groups") == 0:   # the engine dropped the groups with the cells they split
+                self._curve_groups = None
+            # and the limit search
+            armed, self.search_slots = self.search_slots, 0
+            if will_search:
+                self.engine.search_set(table.pack_search(int(search)))
+                self.search_slots = int(search)
+                self._search_checks = any(it is not None and it["check_mask"] for it in table.search)
+                # the items the search scales carry their mark only now: the engine takes a marked table while that search is armed
+                marked = tuple(key for key in ("params", *(k.key for k in FAULT_KINDS)) if table.has_search_marks(key))
+                for key in marked:
+                    self._send_items(table, key, True)
+                    self._search_marked += (key,)
+            elif armed > 0:
+                self.engine.search_set(None)
+                self._search_checks = False
+        except Exception as exc:
+            # A refusal part-way: where the earlier table and its search still stand, its items get their marks back -- the env would
+            # otherwise go on searching without scaling them.  If that is refused too, the exception that leaves says so.
+            if old_table is not None and self.scenario_table is old_table and self.engine.query("search") > 0:
+                self.search_slots = self.engine.query("search_slots")
+                self._search_checks = self.engine.query("search_checks") > 0
+                try:
+                    for key in old_marked:
+                        if key not in self._search_marked:
+                            self._send_items(old_table, key, True)
+                            self._search_marked += (key,)
+                except ValueError as again:
+                    left = [key for key in old_marked if key not in self._search_marked]
+                    note = (f"set_scenarios: the earlier table stays, but the marks of its {', '.join(left)} items could not be put back ({again}): "
+                            "the search that is armed does not scale them until set_scenarios is called again")
+                    exc.args = (f"{exc.args[0]}\n{note}" if exc.args and isinstance(exc.args[0], str) else note,) + tuple(exc.args[1:])
             raise
-        self.scenario_table, self.scenario_mode = table, mode
-        self._info_views = None
-        # parameter windows ride with the table: set the ones it holds, clear what an earlier table left
-        if table.has_params:
-            self.engine.scenario_params_set(table.pack_params())
-        elif self.engine.query("scenario_param_items") > 0:
-            self.engine.scenario_params_set(None)
-        for kind in FAULT_KINDS:                                    # so do the observation and the action faults
-            if any(getattr(table, kind.rows)):
-                getattr(self.engine, kind.setter)(table._pack_fault_items(kind))
-            elif self.engine.query(kind.param) > 0:
-                getattr(self.engine, kind.setter)(None)
-        # so do the checks, once they are armed
-        self.check_slots = 0
-        if check_slots and table.has_checks:
-            self.engine.scenario_checks_set(table.pack_checks(), check_slots)
-            self.check_slots = check_slots
-        elif self.engine.query("scenario_check_items") > 0:
-            self.engine.scenario_checks_set(None)
-        # and the curves
-        self.curves_armed = False
-        if curves and table.has_curves:
-            self.engine.scenario_curves_set(table.pack_curves())
-            self.curves_armed = True
-        elif self.engine.query("scenario_curve_items") > 0:
-            self.engine.scenario_curves_set(None)
-        if not self.curves_armed or self.engine.query("scenario_curve_groups") == 0:   # the engine dropped the groups with the cells they split
-            self._curve_groups = None
-        # and the limit search
-        armed, self.search_slots = self.search_slots, 0
-        if search and table.has_search:
-            self.engine.search_set(table.pack_search(int(search)))
-            self.search_slots = int(search)
-        elif armed > 0:
-            self.engine.search_set(None)
+
+    def _send_items(self, table, key: str, marks: bool):
+        """The parameter windows (``"params"``) or the faults of kind ``key`` of ``table`` to the engine, with or without the marks of
+        the table's search items."""
+        if key == "params":
+            self.engine.scenario_params_set(table.pack_params(marks=marks))
+        else:
+            kind = next(k for k in FAULT_KINDS if k.key == key)
+            getattr(self.engine, kind.setter)(table._pack_fault_items(kind, marks=marks))
 
     def _drop_scenarios(self):
         """The env forgets its scenario table and what rode with it (checks, curves, curve groups)."""
@@ -791,6 +843,7 @@ class BatchedEnv:
         self.check_slots = 0
         self.curves_armed = False
         self.search_slots = 0
+        self._search_marked, self._search_checks = (), False
         self._curve_groups = None
 
     def set_curve_groups(self, groups, n_groups: Optional[int] = None, names=None):
@@ -888,7 +941,7 @@ class BatchedEnv:
         ring = self._search_words("search_trials", (self.search_slots, TRIAL_WORDS)) if include_trials else None
         self.torch.cuda.current_stream(self.device).synchronize()
         rows = search_rows(self.scenario_table, self.scenario_mode, np.arange(self.env_id0, self.env_id0 + self.num_envs))
-        return SearchResult.from_raw(state.cpu().numpy(), ring.cpu().numpy() if include_trials else None, rows, self.env_id0)
+        return SearchResult.from_raw(state.cpu().numpy(), ring.cpu().numpy() if include_trials else None, rows, self.env_id0, self.scenario_table)
 
     def search_remaining(self) -> int:
         """Envs with a search item that still have trials left.  Joins the range streams and reads one device word (a synchronising

@@ -46,6 +46,14 @@ SCN_HD float actfault_apply(const FaultTable& F, int row, int t, const ActFaultE
   return L.x;
 }
 
+// actfault_apply under a limit search whose targets name the action faults: the row's marked items (FLT_MARK, cosim_fault.h) use
+// value * level, `level` being the level the env's open episode runs at (the search's record word 0); the others are as above.
+SCN_HD float actfault_apply_scaled(const FaultTable& F, int row, int t, const ActFaultEnv& E, int j, float x, float level) {
+  ActFaultLane L = {E, j, x, 0.f};
+  fault_walk<true>(F, row, t, ACF_PURPOSE, E, L, level);
+  return L.x;
+}
+
 // The words of last_action element e (actuator idx, scale el_scale) that the step kernel wrote from the action it was given, rewritten
 // from the policy's own output `raw`: the frequency cache, row 0 of the record's observation stack and the newest frame of state_out
 // (a non-stacked element: its one word behind the stack rows).  One float32 multiply, the step kernel's own.

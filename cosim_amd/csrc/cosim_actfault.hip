@@ -65,6 +65,33 @@ __global__ __launch_bounds__(64 * FLT_WAVES) void actfault_step_kernel(ActFaultA
   a.eff[w] = actfault_apply(a.flt, row, t, E, lane, x);
 }
 
+// actfault_step_kernel while a limit search whose targets name the action faults is armed (cosim_search.h): the same wave = env
+// shape at the same site, with the env's level -- word 0 of its search record, one scalar per wave -- multiplied into the values of
+// the row's marked items.  It runs behind the scenario kernel, ahead of the step, so the level is the one the open episode runs at.
+struct ActFaultSearchArgs {
+  ActFaultArgs flt;
+  const int* srch_rec;     // [N][srch_ncnt] the search's records: word 0 is the level this step runs at
+  int srch_ncnt;
+};
+
+__global__ __launch_bounds__(64 * FLT_WAVES) void actfault_search_step_kernel(ActFaultSearchArgs sa) {
+  const ActFaultArgs& a = sa.flt;
+  const int lane = (int)threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * FLT_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
+  if (i >= a.count) return;   // the last block's tail
+  const int env = a.first + i;
+  if (env >= a.n_envs) return;
+  if (lane >= a.nu) return;
+  const float* rec = a.state + (size_t)env * a.s_stride;
+  int t, row;
+  ActFaultEnv E = {fault_wave_key(a.tab, reinterpret_cast<const int*>(rec + a.s_meta), env, a.seed_lo, a.seed_hi, a.env_id0, &t, &row), rec + a.s_lastact};
+  const float level = __int_as_float(__builtin_amdgcn_readfirstlane(sa.srch_rec[(size_t)env * sa.srch_ncnt]));
+  const size_t w = (size_t)env * a.nu + lane;
+  const float x = a.actions[w];
+  a.raw[w] = x;
+  a.eff[w] = actfault_apply_scaled(a.flt, row, t, E, lane, x, level);
+}
+
 __global__ __launch_bounds__(64 * FLT_WAVES) void actfault_obs_kernel(ActObsArgs a) {
   const int lane = (int)threadIdx.x & 63;
   const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * FLT_WAVES + ((int)threadIdx.x >> 6));   // one value per wave

@@ -191,6 +191,15 @@ struct cosim_engine {
   int* d_srch_ring = nullptr;     // [n_envs][srch_slots][4]
   int* d_srch_rem = nullptr;      // one word: envs with an item that are not done
   int srch_slots = 0;
+  // what the other setters hold their tables against while a search is armed: the host's copy of has | lo | hi | targets, the union
+  // of the items' targets and whether an item fails on a check (search_step_checks_kernel in the place of search_step_kernel)
+  std::vector<int32_t> h_srch_has, h_srch_targets;
+  std::vector<float> h_srch_lo, h_srch_hi;
+  int srch_kinds = 0;
+  bool srch_chk = false;
+  int actflt_marked = 0;          // action-fault items of the table that carry FLT_MARK (actfault_search_step_kernel scales them)
+  int obsflt_marked = 0;          // observation-fault items that carry FLT_MARK (obsfault_search_step_kernel)
+  int scnpar_marked = 0;          // parameter items whose op carries SCNPAR_MARK (scnparams_search_step_kernel)
   // fall rules (cosim_fall_set): kernel arguments of every step launch; fall_mask 0 = none (meta word 15 is not written)
   float fall_min_up = -1.f, fall_min_height = 0.f;
   int fall_grace = 0, fall_mask = 0;
@@ -716,6 +725,7 @@ static int scenario_launch(cosim_engine* e, int first, int count, const float* c
 static void scnparams_free(cosim_engine* e) {
   (void)hipFree(e->d_scnpar); (void)hipFree(e->d_params_eff);
   e->d_scnpar = nullptr; e->d_params_eff = nullptr; memset(&e->scnpar, 0, sizeof e->scnpar);
+  e->scnpar_marked = 0;
 }
 
 // directly behind scenario_launch, same envs, same stream: the effective parameter records of this step (reset: of the masked envs at t = 0)
@@ -725,6 +735,10 @@ static int scnparams_launch(cosim_engine* e, int first, int count, const uint8_t
   a.tab = e->scn; a.par = e->scnpar; a.state = e->d_state; a.base = e->d_params; a.eff = e->d_params_eff; a.mask = mask;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.p_stride = e->lay.p_stride; a.reset = reset;
+  if (e->srch.n_items > 0 && (e->srch_kinds & SRCH_PARAMS)) {   // a search whose targets name the windows is armed: marked items are scaled by the env's level
+    const ScnParSearchArgs sa = {a, e->d_srch_rec, SRCH_NCNT};
+    return launch_small<SCNPAR_WAVES, 64 * SCNPAR_WAVES>(scnparams_search_step_kernel, sa, count, s);
+  }
   return launch_small<SCNPAR_WAVES, 64 * SCNPAR_WAVES>(scnparams_step_kernel, a, count, s);
 }
 
@@ -732,7 +746,12 @@ static int scnparams_launch(cosim_engine* e, int first, int count, const uint8_t
 static void obsfault_free(cosim_engine* e) {
   (void)hipFree(e->d_obsflt);
   e->d_obsflt = nullptr; memset(&e->obsflt, 0, sizeof e->obsflt);
+  e->obsflt_marked = 0;
 }
+
+// a search whose targets name the observation faults is armed: obsfault_search_step_kernel in the place of obsfault_step_kernel, and at
+// the step site behind the search's kernel
+static bool obsfault_searched(const cosim_engine* e) { return e->srch.n_items > 0 && (e->srch_kinds & SRCH_OBS_FAULTS) != 0; }
 
 // behind the last launch of a step (reset: of the reset, for the envs under its mask) that writes the state record or state_out of
 // envs [first, first + count), same stream: what the policy sees of those envs
@@ -744,6 +763,10 @@ static int obsfault_launch(cosim_engine* e, int first, int count, float* state_o
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_stack = e->lay.s_stack;
   a.sd = e->ho.stacked_dim; a.S = e->ho.stack_size; a.frame_dim = e->ho.frame_dim; a.state_dim = e->ho.state_dim;
   a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
+  if (obsfault_searched(e)) {   // marked items are scaled by the level of the episode the observation belongs to
+    const ObsFaultSearchArgs sa = {a, e->d_srch_rec, SRCH_NCNT};
+    return launch_small<FLT_WAVES, 64 * FLT_WAVES>(obsfault_search_step_kernel, sa, count, s);
+  }
   return launch_small<FLT_WAVES, 64 * FLT_WAVES>(obsfault_step_kernel, a, count, s);
 }
 
@@ -751,6 +774,7 @@ static int obsfault_launch(cosim_engine* e, int first, int count, float* state_o
 static void actfault_free(cosim_engine* e) {
   (void)hipFree(e->d_actflt); (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw);
   e->d_actflt = nullptr; e->d_actions_eff = nullptr; e->d_actions_raw = nullptr; memset(&e->actflt, 0, sizeof e->actflt);
+  e->actflt_marked = 0;
 }
 
 // ahead of the first launch of a control step of envs [first, first + count), same stream, behind the scenario and parameter-window
@@ -762,6 +786,11 @@ static int actfault_launch(cosim_engine* e, int first, int count, const float* a
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_lastact = e->lay.s_lastact; a.nu = e->model.nu;
   a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
+  // a search whose targets name the action faults is armed: the same walk with every env's level multiplied into its marked items
+  if (e->srch.n_items > 0 && (e->srch_kinds & SRCH_ACT_FAULTS)) {
+    const ActFaultSearchArgs sa = {a, e->d_srch_rec, SRCH_NCNT};
+    return launch_small<FLT_WAVES, 64 * FLT_WAVES>(actfault_search_step_kernel, sa, count, s);
+  }
   return launch_small<FLT_WAVES, 64 * FLT_WAVES>(actfault_step_kernel, a, count, s);
 }
 
@@ -882,6 +911,10 @@ static SrchArgs search_args(cosim_engine* e) {
 static int search_step(cosim_engine* e, int first, int count, const uint8_t* term, const uint8_t* trunc, hipStream_t s) {
   SrchArgs a = search_args(e);
   a.term = term; a.trunc = trunc; a.first = first; a.count = count;
+  if (e->srch_chk && e->chk.n_scn > 0) {   // an item fails on a check: the same rule with the verdict record checks_step_kernel closed behind this step
+    const SrchChkArgs ca = {a, {e->d_chk_cnt, e->d_chk_rec, CHK_NCNT, e->chk_slots, checks_words(e->chk.I)}};
+    return launch_small<64, 64>(search_step_checks_kernel, ca, count, s);
+  }
   return launch_small<64, 64>(search_step_kernel, a, count, s);
 }
 
@@ -898,6 +931,7 @@ static void search_free(cosim_engine* e) {
   (void)hipFree(e->d_srch); (void)hipFree(e->d_srch_rec); (void)hipFree(e->d_srch_ring); (void)hipFree(e->d_srch_rem);
   e->d_srch = nullptr; e->d_srch_rec = nullptr; e->d_srch_ring = nullptr; e->d_srch_rem = nullptr; e->srch_slots = 0;
   memset(&e->srch, 0, sizeof e->srch);
+  e->h_srch_has.clear(); e->h_srch_targets.clear(); e->h_srch_lo.clear(); e->h_srch_hi.clear(); e->srch_kinds = 0; e->srch_chk = false;
 }
 
 static void scenario_free(cosim_engine* e) {
@@ -1613,6 +1647,11 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "scenario_check_words") return e->chk.n_scn > 0 ? checks_words(e->chk.I) : 0;   // 32-bit words of a verdict record: 8 + 2 I
   if (n == "search") return e->srch.n_items;      // scenarios of the table with a search item armed (0: no search, no launches, scenario_step_kernel)
   if (n == "search_slots") return e->srch_slots;  // trial records per env
+  if (n == "search_targets") return e->srch.n_items > 0 ? e->srch_kinds : 0;   // union of the armed items' targets (16: actfault_search_step_kernel in the place of actfault_step_kernel)
+  if (n == "search_checks") return e->srch.n_items > 0 && e->srch_chk;          // an armed item fails on a check (search_step_checks_kernel in the place of search_step_kernel)
+  if (n == "action_faults_marked") return e->actflt_marked;                     // action-fault items the search scales
+  if (n == "obs_faults_marked") return e->obsflt_marked;                        // observation-fault items the search scales
+  if (n == "scenario_param_items_marked") return e->scnpar_marked;              // parameter items the search scales
   if (n == "search_remaining") return search_remaining(const_cast<cosim_engine_t*>(e));   // synchronising: joins, reads one device word
   if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
   if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
@@ -1975,11 +2014,24 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   // observation is faulted once), ahead of the observers and the history pack, which then hold what the policy saw
   // action faults: last_action is what the policy put out, not what the bus delivered; the observation faults compose on top
   if (act_faults && e->act_in_obs) RC_TRY(actfault_obs_launch(e, first, count, state_out_dev, s));
-  if (faults) {
+  // While a search scales observation faults the launch goes BEHIND the observers: the observation a step that ended an episode
+  // returns is clock 0 of the next one and takes the level search_step_kernel has just moved.  No observer reads what the fault kernel
+  // writes (stack row 0 of the record, state_out): they read the info row, the flags, the command, qpos / qvel and the meta words, so
+  // the two orders give the observers the same words.  The history pack stays behind both (the caller issues it after this returns).
+  // The timing pair closes behind the fault launch in either order, so in the moved order a timed launch's span also holds the
+  // observers' kernels (ledger, traces, checks, curves, search), which it does not hold otherwise: kernel_ms of such a run is not
+  // comparable with one of the plain order.
+  const bool faults_last = faults && obsfault_searched(e);
+  if (faults && !faults_last) {
     RC_TRY(obsfault_launch(e, first, count, state_out_dev, nullptr, s));
     if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
   }
-  return observers_step(e, first, count, 1, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s);
+  RC_TRY(observers_step(e, first, count, 1, actions_dev, scenario_cmd(e, commands_dev), info_out_dev, terminated_dev, truncated_dev, s));
+  if (faults_last) {
+    RC_TRY(obsfault_launch(e, first, count, state_out_dev, nullptr, s));
+    if (slot >= 0) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
+  }
+  return COSIM_OK;
 }
 
 // Spawn table: validate on the host (a message that names the row), upload, place every row on the heightfield with
@@ -2363,6 +2415,9 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
   const ScnRaw raw = {n_scn, key_adr, key_t, key_cmd, push_adr, push_t, push_v};
   const ScnShape v = validate_scenario(table_dims(e), raw);
   if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  if (n_scn == e->scn.n_scn && mode == SCN_MODE_CYCLE && e->actflt_marked + e->obsflt_marked + e->scnpar_marked > 0)
+    return fail(COSIM_EINVAL, "cosim_scenario_set: mode cycle drops the limit search and " + std::to_string(e->actflt_marked + e->obsflt_marked + e->scnpar_marked) +
+                                  " parameter or fault items are marked for it: clear or unmark them first");
   RC_TRY(table_quiesce(e, (hipStream_t)stream));
   ScnTable tab = {};
   WordPacker pk;
@@ -2397,7 +2452,9 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   if (n_scn == 0) return table_clear(e, 0, scnparams_free);
   RC_TRY(table_rows_match(e, "cosim_scenario_params_set", "parameter windows", n_scn));
   const ParRaw raw = {n_scn, adr, t, field, index, op, value};
-  const ParShape v = validate_params(table_dims(e), raw);
+  const FltMarks marks = {SRCH_PARAMS, e->h_srch_has.data(), e->h_srch_targets.data(), e->h_srch_lo.data(), e->h_srch_hi.data()};
+  const bool armed = e->srch.n_items > 0 && (e->srch_kinds & SRCH_PARAMS) && n_scn == e->srch.n_scn;
+  const ParShape v = validate_params(table_dims(e), raw, armed ? &marks : nullptr);
   if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
   RC_TRY(upload_params(e));   // the effective records written below are built from the current base
   RC_TRY(table_quiesce(e, 0));
@@ -2420,6 +2477,7 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   if (!in_place) { (void)hipFree(e->d_scnpar); e->d_scnpar = d_new; }
   pk.patch(e->d_scnpar);
   e->scnpar = tab;
+  e->scnpar_marked = v.marked;
   // every env's effective record once, at its current clock: no row is ever unwritten
   RC_TRY(scnparams_launch(e, 0, e->n_envs, nullptr, 0, 0));
   HIP_TRY(hipDeviceSynchronize());
@@ -2472,11 +2530,23 @@ static int fault_table_set(cosim_engine* e, const std::string& fn, const char* w
   return COSIM_OK;
 }
 
+// the items of a fault table that passed its validator (S + 2 + 6 n words) whose element carries FLT_MARK
+static int fault_words_marked(const int32_t* words) {
+  const int n_scn = words[0], n = words[1 + n_scn];
+  const int32_t* elem = words + 1 + (n_scn + 1) + 2 * (size_t)n;
+  int m = 0;
+  for (int i = 0; i < n; i++) m += ((unsigned)elem[i] & FLT_MARK) != 0;
+  return m;
+}
 static FltShape obsfault_validate(const cosim_engine* e, const FltRaw& raw) {
-  return validate_faults({e->ho.frame_dim, e->ho.stacked_dim, e->ho.stack_size, e->ho.el_field, CS_OBS_COMMAND}, raw);
+  const FltMarks marks = {SRCH_OBS_FAULTS, e->h_srch_has.data(), e->h_srch_targets.data(), e->h_srch_lo.data(), e->h_srch_hi.data()};
+  const bool armed = obsfault_searched(e) && raw.n_scn == e->srch.n_scn;
+  return validate_faults({e->ho.frame_dim, e->ho.stacked_dim, e->ho.stack_size, e->ho.el_field, CS_OBS_COMMAND}, raw, armed ? &marks : nullptr);
 }
 static int obsfault_set(cosim_engine* e, const int32_t* words, int count) {
-  return fault_table_set(e, OBF_SETTER, "observation faults", e->d_obsflt, e->obsflt, obsfault_free, nullptr, obsfault_validate, words, count);
+  RC_TRY(fault_table_set(e, OBF_SETTER, "observation faults", e->d_obsflt, e->obsflt, obsfault_free, nullptr, obsfault_validate, words, count));
+  e->obsflt_marked = e->obsflt.n_items > 0 ? fault_words_marked(words) : 0;
+  return COSIM_OK;
 }
 
 // the two action buffers: both or neither; zeroed, so that a read ahead of the first step finds no stale bytes
@@ -2491,16 +2561,24 @@ static hipError_t actfault_buffers(cosim_engine* e) {
   return r;
 }
 
-static FltShape actfault_validate(const cosim_engine* e, const FltRaw& raw) { return validate_action_faults(e->model.nu, raw); }
+// marked items are held against the search that is armed, if its targets name the action faults
+static FltShape actfault_validate(const cosim_engine* e, const FltRaw& raw) {
+  const FltMarks marks = {SRCH_ACT_FAULTS, e->h_srch_has.data(), e->h_srch_targets.data(), e->h_srch_lo.data(), e->h_srch_hi.data()};
+  const bool armed = e->srch.n_items > 0 && (e->srch_kinds & SRCH_ACT_FAULTS) && raw.n_scn == e->srch.n_scn;
+  return validate_action_faults(e->model.nu, raw, armed ? &marks : nullptr);
+}
 static int actfault_set(cosim_engine* e, const int32_t* words, int count) {
   RC_TRY(fault_table_set(e, ACF_SETTER, "action faults", e->d_actflt, e->actflt, actfault_free, actfault_buffers, actfault_validate, words, count));
+  e->actflt_marked = e->actflt.n_items > 0 ? fault_words_marked(words) : 0;
   e->act_in_obs = false;
   for (int el = 0; el < e->ho.frame_dim; el++) e->act_in_obs = e->act_in_obs || e->ho.el_field[el] == CS_OBS_LAST_ACTION;
   return COSIM_OK;
 }
 
 // Limit search of the scenario table that is set (cosim_set_param "search"): `words` is S | slots | has[S] | lo | hi | x0 | d0 | d_min |
-// rule | trials | targets | fail_mask | rev_skip ([S] each, floats as their bits); the one word 0 clears.  A table with the S, the
+// rule | trials | targets | fail_mask | rev_skip ([S] each, floats as their bits), 2 + 11 S words, or with harder | chk_lo | chk_hi
+// behind them 2 + 14 S; the one word 0 clears.  While marked items are set (action faults) the search they are held against is
+// neither replaced nor cleared: clear or unmark them first.  A table with the S, the
 // slots and the has[] of the one that is armed is rewritten in place and the records stay (captured graphs pick the new bounds up);
 // anything else allocates anew and search_init_kernel begins every env's search at its item's start level.
 static int search_set(cosim_engine* e, const int32_t* words, int count) {
@@ -2508,26 +2586,52 @@ static int search_set(cosim_engine* e, const int32_t* words, int count) {
   if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the search)");
   const int n_scn = words[0];
   HIP_TRY(hipSetDevice(e->device));
+  if (e->actflt_marked > 0)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->actflt_marked) + " action-fault items are marked for the search that is armed: clear or unmark them "
+                                   "(cosim_set_param \"action_faults\") before the search is replaced or cleared");
+  if (e->obsflt_marked > 0)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->obsflt_marked) + " observation-fault items are marked for the search that is armed: clear or unmark them "
+                                   "(cosim_set_param \"obs_faults\") before the search is replaced or cleared");
+  if (e->scnpar_marked > 0)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->scnpar_marked) + " parameter items are marked for the search that is armed: clear or unmark them "
+                                   "(cosim_scenario_params_set) before the search is replaced or cleared");
   if (n_scn == 0) return table_clear(e, 0, search_free);
-  if (n_scn < 0 || (long long)count != 2 + 11ll * n_scn)
-    return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios takes " + std::to_string(2 + 11ll * (n_scn < 0 ? 0 : n_scn)));
+  const bool long_form = n_scn > 0 && (long long)count == 2 + 14ll * n_scn;
+  if (n_scn < 0 || ((long long)count != 2 + 11ll * n_scn && !long_form))
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios takes " + std::to_string(2 + 11ll * (n_scn < 0 ? 0 : n_scn)) +
+                                  " or, with harder and the check masks, " + std::to_string(2 + 14ll * (n_scn < 0 ? 0 : n_scn)));
   const int32_t* w = words + 2;
   const size_t S = (size_t)n_scn;
   const auto f = [&](int k) { return reinterpret_cast<const float*>(w + k * S); };
-  const SrchRaw raw = {n_scn, words[1], w, f(1), f(2), f(3), f(4), f(5), w + 6 * S, w + 7 * S, w + 8 * S, w + 9 * S, w + 10 * S};
+  SrchRaw raw = {n_scn, words[1], w, f(1), f(2), f(3), f(4), f(5), w + 6 * S, w + 7 * S, w + 8 * S, w + 9 * S, w + 10 * S};
+  if (long_form) { raw.harder = w + 11 * S; raw.chk_lo = w + 12 * S; raw.chk_hi = w + 13 * S; }
   RC_TRY(table_quiesce(e, 0));
   std::vector<int32_t> adr;   // key_adr | push_adr of the table that is set: the head of its image
   if (n_scn == e->scn.n_scn) {
     adr.resize(2 * (S + 1));
     HIP_TRY(hipMemcpy(adr.data(), e->d_scn, adr.size() * 4, hipMemcpyDeviceToHost));
   }
-  const SrchDims dims = {e->scn.n_scn, e->scn.mode, e->ho.auto_reset, adr.data(), adr.data() + S + 1};
+  std::vector<int32_t> chk_adr;   // the row addresses of the checks that are armed: the head of their image
+  if (n_scn == e->chk.n_scn) {
+    chk_adr.resize(S + 1);
+    HIP_TRY(hipMemcpy(chk_adr.data(), e->d_chk, chk_adr.size() * 4, hipMemcpyDeviceToHost));
+  }
+  SrchDims dims = {e->scn.n_scn, e->scn.mode, e->ho.auto_reset, adr.data(), adr.data() + S + 1, chk_adr.empty() ? nullptr : chk_adr.data()};
+  std::vector<int32_t> kind_adr[3];   // the row addresses of the item tables that are set: the head of each image
+  const struct { const char* d; int n_scn, n_items; const int32_t** slot; } kinds[3] = {
+      {e->d_scnpar, e->scnpar.n_scn, e->scnpar.n_items, &dims.par_adr}, {e->d_obsflt, e->obsflt.n_scn, e->obsflt.n_items, &dims.obs_adr}, {e->d_actflt, e->actflt.n_scn, e->actflt.n_items, &dims.act_adr}};
+  for (int k = 0; k < 3; k++) {
+    if (kinds[k].n_items <= 0 || kinds[k].n_scn != n_scn) continue;
+    kind_adr[k].resize(S + 1);
+    HIP_TRY(hipMemcpy(kind_adr[k].data(), kinds[k].d, (S + 1) * 4, hipMemcpyDeviceToHost));
+    *kinds[k].slot = kind_adr[k].data();
+  }
   const SrchShape v = validate_search(dims, raw);
   if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
   SrchTable tab = {};
   WordPacker pk;
   pack_search(pk, tab, raw, v);
-  bool in_place = e->srch.n_scn == n_scn && e->srch.n_items == v.n && e->srch_slots == raw.slots;
+  bool in_place = e->srch.n_scn == n_scn && e->srch.n_items == v.n && e->srch_slots == raw.slots && (e->srch.harder != nullptr) == long_form;
   if (in_place) {
     std::vector<int32_t> old;
     RC_TRY(table_download(e->d_srch, pk, old));
@@ -2548,6 +2652,14 @@ static int search_set(cosim_engine* e, const int32_t* words, int count) {
   pk.patch(e->d_srch);
   e->srch = tab;
   e->srch_slots = raw.slots;
+  e->h_srch_has.assign(raw.has, raw.has + S); e->h_srch_targets.assign(raw.targets, raw.targets + S);
+  e->h_srch_lo.assign(raw.lo, raw.lo + S); e->h_srch_hi.assign(raw.hi, raw.hi + S);
+  e->srch_kinds = 0; e->srch_chk = false;
+  for (size_t k = 0; k < S; k++) {
+    if (!raw.has[k]) continue;
+    e->srch_kinds |= raw.targets[k];
+    e->srch_chk = e->srch_chk || (long_form && (raw.chk_lo[k] | raw.chk_hi[k]) != 0);
+  }
   if (in_place) return COSIM_OK;
   // every env's record, ring and the remaining word once (the range streams do not order with the null stream: wait here, cold path)
   SrchArgs a = search_args(e);
@@ -2582,6 +2694,8 @@ int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
                               const int32_t* mode, const int32_t* cmp, const float* bound, int slots) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: null engine");
   HIP_TRY(hipSetDevice(e->device));
+  const char* const srch_msg = ": the limit search that is armed fails on a check: clear the search (cosim_set_param \"search\") before the checks are cleared or laid out anew";
+  if (n_scn == 0 && e->srch_chk) return fail(COSIM_EINVAL, std::string("cosim_scenario_checks_set") + srch_msg);
   if (n_scn == 0) return table_clear(e, 0, checks_free);
   RC_TRY(table_rows_match(e, "cosim_scenario_checks_set", "checks", n_scn));
   const ChkRaw raw = {n_scn, adr, t, signal, index, mode, cmp, bound, slots};
@@ -2597,6 +2711,7 @@ int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
     RC_TRY(table_download(e->d_chk, pk, old));
     in_place = checks_same_rows(pk, tab, old.data());
   }
+  if (!in_place && e->srch_chk) return fail(COSIM_EINVAL, std::string("cosim_scenario_checks_set") + srch_msg);
   const size_t N = (size_t)e->n_envs, I = (size_t)v.I, W = (size_t)checks_words(v.I);
   auto alloc = [&]() -> hipError_t {   // everything anew: the table, clean accumulators, counters and records at zero
     checks_free(e);
@@ -2620,6 +2735,8 @@ int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   // every env starts an open episode with clean accumulators at its current clock -- in place too: no verdict mixes two sets of values
   // (the range streams do not order with the null stream: wait here, cold path)
   RC_TRY(checks_begin(e, nullptr, nullptr, 0, e->stepped ? CHK_NO_RESET : 0, 0));
+  // a search that fails on a check judges an episode by its verdict: the episode that lost its samples here is no trial
+  if (e->srch_chk) RC_TRY(search_begin(e, nullptr, nullptr, 0, e->stepped ? SRCH_NO_RESET : 0, 0));
   HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
 }

@@ -18,6 +18,11 @@
 // Philox4x32-10, first output word, key (seed_lo, seed_hi), counter (c0, purpose | index << 8, gid_lo, gid_hi): purpose 7 for
 // observations, 8 for actions; noise: index = el; drop: index = 0x10000 + ord (elements are below 256, so the ranges are disjoint).
 // At clock 0 there is no previous word: hold and drop are the identity there.
+//
+// A MARKED item (bit FLT_MARK of el; elements are below 256) is one a limit search scales (cosim_search.h): the walk a search's
+// kernel runs (fault_walk<true>) uses v = value * level for it, one float32 multiply, contraction off, done first, in the place of
+// value -- drop compares its draw against v -- and the item's own rule runs next.  hold has no value and is never marked.  The
+// unmarked items of the same row, and every item under fault_walk<false>, take the expressions above bit for bit.
 #pragma once
 #include "cosim_scenario.h"
 
@@ -26,6 +31,7 @@ namespace cosim {
 enum { FLT_SCALE = 0, FLT_BIAS = 1, FLT_SET = 2, FLT_NOISE = 3, FLT_HOLD = 4, FLT_DROP = 5, FLT_CLIP = 6, FLT_NOP = 7 };
 constexpr int FLT_MAX_ITEMS = 256;          // per scenario, expanded
 constexpr unsigned FLT_DROP_INDEX = 0x10000u;
+constexpr unsigned FLT_MARK = 0x8000u;      // of the el field: a limit search scales the item's value
 constexpr int FLT_CHUNK = 4;                // item records fetched at a time; the item array is padded by FLT_CHUNK - 1 records
 
 struct FaultTable {
@@ -83,8 +89,9 @@ SCN_HD float fault_op(float x, int op, float value, float prev, int el, unsigned
 // draw for the item (its elements are lost together) and hold to nop at clock 0.  Returns whether any item held.
 // Nothing here depends on the lane: the row is the same for every lane of an env, so on the device the records come through scalar
 // loads and every branch up to L.item's compare of el is taken by the whole wave.
-template <class Lane>
-SCN_HD bool fault_walk(const FaultTable& F, int row, int t, unsigned purpose, const FaultKey& K, Lane& L) {
+// MARKED: the walk of a search's kernel; `level` is the env's level, the same for the whole wave.
+template <bool MARKED = false, class Lane>
+SCN_HD bool fault_walk(const FaultTable& F, int row, int t, unsigned purpose, const FaultKey& K, Lane& L, float level = 1.f) {
 #if defined(__clang__)
 #pragma clang fp contract(off)
 #endif
@@ -105,8 +112,9 @@ SCN_HD bool fault_walk(const FaultTable& F, int row, int t, unsigned purpose, co
       const int t0 = w[4 * j], t1 = w[4 * j + 1];
       if (!(t0 <= t && t < t1)) continue;
       const unsigned key = (unsigned)w[4 * j + 2];
-      const float value = fault_bits(w[4 * j + 3]);
-      const int el = (int)(key & 0xffffu), ord = (int)(key >> 24);
+      float value = fault_bits(w[4 * j + 3]);
+      if (MARKED && (key & FLT_MARK)) value = value * level;
+      const int el = (int)(key & (MARKED ? 0xffffu & ~FLT_MARK : 0xffffu)), ord = (int)(key >> 24);
       int op = (int)((key >> 16) & 0xffu);
       if (!loaded) {
         loaded = true;

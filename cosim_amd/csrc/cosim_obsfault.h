@@ -67,10 +67,12 @@ struct ObsFaultLane {
 
 // One env in row `row` at observation clock t, lane `lane` of `lanes`, NP passes from pass0 on.  (The kernel: lanes 64, pass0 0,
 // NP = MAXFRAME / 64.)
-template <int NP>
-SCN_HD void obsfault_apply(const FaultTable& F, int row, int t, const ObsFaultEnv& E, int lane, int lanes, int pass0) {
+// MARKED: under a limit search whose targets name the observation faults, the row's marked items (FLT_MARK, cosim_fault.h) use
+// value * level; `level` is that of the episode the observation belongs to.
+template <int NP, bool MARKED = false>
+SCN_HD void obsfault_apply(const FaultTable& F, int row, int t, const ObsFaultEnv& E, int lane, int lanes, int pass0, float level = 1.f) {
   ObsFaultLane<NP> L = {E, lane, lanes, pass0, {}, {}, {}};
-  if (fault_walk(F, row, t, OBF_PURPOSE, E, L)) L.store(t == 0);
+  if (fault_walk<MARKED>(F, row, t, OBF_PURPOSE, E, L, level)) L.store(t == 0);
 }
 
 }  // namespace cosim

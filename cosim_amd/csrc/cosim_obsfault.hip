@@ -45,4 +45,30 @@ __global__ __launch_bounds__(64 * FLT_WAVES) void obsfault_step_kernel(ObsFaultA
   obsfault_apply<OBF_PASSES>(a.flt, row, t, E, lane, 64, 0);
 }
 
+// obsfault_step_kernel while a limit search whose targets name the observation faults is armed.  An observation is scaled by the
+// level of the episode it belongs to: on the step that ends episode e the returned observation is clock 0 of episode e + 1, so at the
+// step site the engine issues this launch BEHIND search_step_kernel, which has moved the level by then (neither the observers nor the
+// search read the words written here: stack row 0 and state_out).  The reset site needs no change: the level does not move there.
+struct ObsFaultSearchArgs {
+  ObsFaultArgs flt;
+  const int* srch_rec;     // [N][srch_ncnt]
+  int srch_ncnt;
+};
+
+__global__ __launch_bounds__(64 * FLT_WAVES) void obsfault_search_step_kernel(ObsFaultSearchArgs sa) {
+  const ObsFaultArgs& a = sa.flt;
+  const int lane = (int)threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * FLT_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
+  if (i >= a.count) return;   // the last block's tail
+  const int env = a.first + i;
+  if (env >= a.n_envs) return;
+  if (a.mask != nullptr && a.mask[env] == 0) return;
+  float* rec = a.state + (size_t)env * a.s_stride;
+  int t, row;
+  ObsFaultEnv E = {fault_wave_key(a.tab, reinterpret_cast<const int*>(rec + a.s_meta), env, a.seed_lo, a.seed_hi, a.env_id0, &t, &row),
+                   rec + a.s_stack, a.state_out + (size_t)env * a.state_dim, a.sd, a.S, a.frame_dim};
+  const float level = __int_as_float(__builtin_amdgcn_readfirstlane(sa.srch_rec[(size_t)env * sa.srch_ncnt]));
+  obsfault_apply<OBF_PASSES, true>(a.flt, row, t, E, lane, 64, 0, level);
+}
+
 }  // namespace cosim

@@ -40,4 +40,29 @@ __global__ __launch_bounds__(64 * SCNPAR_WAVES) void scnparams_step_kernel(ScnPa
   scnparams_apply(a.par, row, t, a.base + p0, a.eff + p0, a.p_stride, lane, 64);
 }
 
+// scnparams_step_kernel while a limit search whose targets name the parameter windows is armed: the same wave = env shape at the same
+// sites, with the env's level -- word 0 of its search record, one scalar per wave -- multiplied into the values of the row's marked
+// items.  It runs behind the scenario kernel, ahead of the step: the level is the one the open episode runs at (a reset does not move it).
+struct ScnParSearchArgs {
+  ScnParArgs par;
+  const int* srch_rec;     // [N][srch_ncnt]
+  int srch_ncnt;
+};
+
+__global__ __launch_bounds__(64 * SCNPAR_WAVES) void scnparams_search_step_kernel(ScnParSearchArgs sa) {
+  const ScnParArgs& a = sa.par;
+  const int lane = (int)threadIdx.x & 63;
+  const int i = __builtin_amdgcn_readfirstlane((int)blockIdx.x * SCNPAR_WAVES + ((int)threadIdx.x >> 6));   // one value per wave
+  if (i >= a.count) return;   // the last block's tail
+  const int env = a.first + i;
+  if (env >= a.n_envs) return;
+  if (a.reset && a.mask != nullptr && a.mask[env] == 0) return;
+  const int* meta = reinterpret_cast<const int*>(a.state + (size_t)env * a.s_stride + a.s_meta);
+  const int t = a.reset ? 0 : __builtin_amdgcn_readfirstlane(meta[0]);
+  const int row = scenario_row(a.tab, env, __builtin_amdgcn_readfirstlane(meta[11]));
+  const float level = __int_as_float(__builtin_amdgcn_readfirstlane(sa.srch_rec[(size_t)env * sa.srch_ncnt]));
+  const size_t p0 = (size_t)env * a.p_stride;
+  scnparams_apply(a.par, row, t, a.base + p0, a.eff + p0, a.p_stride, lane, 64, true, level);
+}
+
 }  // namespace cosim

@@ -1,15 +1,20 @@
 // cosim_search.h — the per-env rule of a scenario table's limit search (cosim_set_param "search", include/cosim.h), as inline
 // functions that the device kernels (cosim_search.hip) and a plain host C++ program (tests/search_lanes.cpp) both compile.
 //
-// A scenario carries at most one search item (lo, hi, x0, d0, d_min, rule, trials, targets, fail_mask, rev_skip).  Every env whose
-// row has one keeps a LEVEL, a float32 word inside [lo, hi] that the scenario kernel multiplies into the row's push vectors
-// (targets bit 1) and / or command keyframes (bit 2).  When an episode of the env ends, its outcome moves the level:
+// A scenario carries at most one search item (lo, hi, x0, d0, d_min, rule, trials, targets, fail_mask, rev_skip, harder, check mask).
+// Every env whose row has one keeps a LEVEL, a float32 word inside [lo, hi] that the scenario kernel multiplies into the row's push
+// vectors (targets bit 1) and / or command keyframes (bit 2), and the parameter-window, observation-fault and action-fault kernels
+// into the values of the row's MARKED items of their kind (bits 4, 8, 16; cosim_scnparams.h, cosim_fault.h).  When an episode of the env ends, its outcome moves the level:
 //   flags = 1 terminated | 2 truncated | 4 meta[4] moved | 8 the episode did not begin at a reset | (meta[15] & 7) << 5 with a fall
 //           rule set -- the ledger's flags (cosim_ledger.hip), restated here
 //   the episode is a COUNTED TRIAL iff the row has an item, the env is not done and the episode began at a reset (one that began
 //   at a restore / set_state may have missed its push window)
-//   fail = (flags & fail_mask) != 0, dir = fail ? -1 : +1, x = level:
+//   fail = (flags & fail_mask) != 0 || a selected check of the ended episode is not passed: (fail mask | incomplete mask) of the
+//     verdict record the checks kernel closed behind this same step (cosim_checks.h, record words 4..7) & the item's check mask
+//   harder up (0):   dir = fail ? -1 : +1, x = level:
 //     fail ? lo_fail = has_fail ? fminf(lo_fail, x) : x : hi_pass = has_pass ? fmaxf(hi_pass, x) : x
+//   harder down (1): dir = fail ? +1 : -1 (a LOWER level is harder: friction, a gain scale); the two bracket words then hold the
+//     highest failure and the lowest pass: fail ? lo_fail = has_fail ? fmaxf(lo_fail, x) : x : hi_pass = has_pass ? fminf(hi_pass, x) : x
 //     rev = last_dir != 0 && dir != last_dir;  a reversal beyond the first rev_skip adds x to rev_sum (rev_n++)
 //     staircase: on a reversal step = fmaxf(step * 0.5f, d_min), then x' = x + dir * step
 //     bisect:    x' = x + dir * step, then step = fmaxf(step * 0.5f, d_min)
@@ -21,7 +26,7 @@
 // 11 episodes ended since arming (the ledger's ordinal)  12 length of the open episode  13 meta[4] at its start  14 ended episodes
 // that were not trials  15 zero.
 // Trial record, 4 words, in slot (episode mod slots) of the env's ring: episode, the level the episode RAN at (bits),
-// flags | 256 counted | 512 fail | 1024 reversal, length.
+// flags | 256 counted | 512 fail | 1024 reversal | 2048 failed by a check, length.
 #pragma once
 #include <stddef.h>
 #include <string.h>
@@ -31,10 +36,12 @@
 namespace cosim {
 
 enum { SRCH_BISECT = 0, SRCH_STAIRCASE = 1 };
-enum { SRCH_PUSHES = 1, SRCH_COMMANDS = 2 };
+enum { SRCH_PUSHES = 1, SRCH_COMMANDS = 2, SRCH_PARAMS = 4, SRCH_OBS_FAULTS = 8, SRCH_ACT_FAULTS = 16 };
+enum { SRCH_HARDER_UP = 0, SRCH_HARDER_DOWN = 1 };
 enum { SRCH_AT_RESET = 1, SRCH_DONE = 2, SRCH_HAS_PASS = 4, SRCH_HAS_FAIL = 8, SRCH_HAS_ITEM = 16 };
 // the ledger's flag values (cosim_ledger.hip) and the three a trial record adds
-enum { SRCH_TERMINATED = 1, SRCH_TRUNCATED = 2, SRCH_NONFINITE = 4, SRCH_NO_RESET = 8, SRCH_COUNTED = 256, SRCH_FAILED = 512, SRCH_REVERSAL = 1024 };
+enum { SRCH_TERMINATED = 1, SRCH_TRUNCATED = 2, SRCH_NONFINITE = 4, SRCH_NO_RESET = 8, SRCH_COUNTED = 256, SRCH_FAILED = 512, SRCH_REVERSAL = 1024,
+       SRCH_BY_CHECK = 2048 };
 constexpr int SRCH_NCNT = 16, SRCH_TRIAL_WORDS = 4, SRCH_MAX_SLOTS = 64, SRCH_MAX_TRIALS = 1 << 20, SRCH_MAX_REV_SKIP = 255;
 constexpr int SRCH_FAIL_BITS = 1 | 4 | 32 | 64 | 128;   // what a fail_mask may select: terminated, non-finite, tilt, height, contact
 enum { SRCH_LEVEL = 0, SRCH_STEP, SRCH_TRIALS, SRCH_FAILS, SRCH_LAST_DIR, SRCH_REVERSALS, SRCH_REV_SUM, SRCH_REV_N, SRCH_HI_PASS, SRCH_LO_FAIL,
@@ -53,9 +60,13 @@ struct SrchTable {
   const int32_t* fail_mask;
   const int32_t* rev_skip;
   int n_scn, n_items;        // n_items: scenarios that have one
+  // the long form's columns; null (the short form): harder up, no check
+  const int32_t* harder;     // [S] SRCH_HARDER_*
+  const int32_t* chk_lo;     // [S] the selected checks of the row, bit i = check item i (low, high word)
+  const int32_t* chk_hi;
 };
 
-struct SrchItem { float lo, hi, x0, d0, d_min; int has, rule, trials, targets, fail_mask, rev_skip; };
+struct SrchItem { float lo, hi, x0, d0, d_min; int has, rule, trials, targets, fail_mask, rev_skip, harder, chk_lo, chk_hi; };
 
 struct SrchArgs {
   SrchTable tab;
@@ -90,6 +101,10 @@ SCN_HD SrchItem search_item(const SrchTable& T, int row) {
   it.rule = SCN_TAB_CAST(int32_t, T.rule)[row]; it.trials = SCN_TAB_CAST(int32_t, T.trials)[row];
   it.targets = SCN_TAB_CAST(int32_t, T.targets)[row]; it.fail_mask = SCN_TAB_CAST(int32_t, T.fail_mask)[row];
   it.rev_skip = SCN_TAB_CAST(int32_t, T.rev_skip)[row];
+  it.harder = 0; it.chk_lo = 0; it.chk_hi = 0;
+  if (T.harder != nullptr) {
+    it.harder = SCN_TAB_CAST(int32_t, T.harder)[row]; it.chk_lo = SCN_TAB_CAST(int32_t, T.chk_lo)[row]; it.chk_hi = SCN_TAB_CAST(int32_t, T.chk_hi)[row];
+  }
   return it;
 }
 
@@ -121,12 +136,15 @@ SCN_HD int search_trial(int* rec, const SrchItem& it, bool fail) {
   const float x = search_float(rec[SRCH_LEVEL]);
   float step = search_float(rec[SRCH_STEP]);
   int status = rec[SRCH_STATUS];
-  const int dir = fail ? -1 : 1, last = rec[SRCH_LAST_DIR];
+  const bool down = it.harder == SRCH_HARDER_DOWN;
+  const int dir = (fail != down) ? -1 : 1, last = rec[SRCH_LAST_DIR];
   if (fail) {
-    rec[SRCH_LO_FAIL] = search_bits((status & SRCH_HAS_FAIL) ? fminf(search_float(rec[SRCH_LO_FAIL]), x) : x);
+    const float old = search_float(rec[SRCH_LO_FAIL]);
+    rec[SRCH_LO_FAIL] = search_bits((status & SRCH_HAS_FAIL) ? (down ? fmaxf(old, x) : fminf(old, x)) : x);
     status |= SRCH_HAS_FAIL;
   } else {
-    rec[SRCH_HI_PASS] = search_bits((status & SRCH_HAS_PASS) ? fmaxf(search_float(rec[SRCH_HI_PASS]), x) : x);
+    const float old = search_float(rec[SRCH_HI_PASS]);
+    rec[SRCH_HI_PASS] = search_bits((status & SRCH_HAS_PASS) ? (down ? fminf(old, x) : fmaxf(old, x)) : x);
     status |= SRCH_HAS_PASS;
   }
   const bool rev = last != 0 && dir != last;
@@ -160,16 +178,20 @@ SCN_HD int search_trial(int* rec, const SrchItem& it, bool fail) {
 }
 
 // One env behind one control step.  `rec`: its SRCH_NCNT words; `ring`: its slots * 4 trial words; `meta`: the env's meta words as
-// the step left them.  Returns 1 if the env became done on this step (the caller takes 1 off the engine's "remaining" word).
-SCN_HD int search_step_lane(int* rec, int* ring, int slots, const SrchItem& it, int te, int tr, const int* meta, int fall) {
+// the step left them; `verdict`: the verdict record the checks kernel closed for the episode this step ended (read only on a step
+// with a done flag and an item that selects a check), or null.  Returns 1 if the env became done on this step (the caller takes 1
+// off the engine's "remaining" word).
+SCN_HD int search_step_lane(int* rec, int* ring, int slots, const SrchItem& it, int te, int tr, const int* meta, int fall, const int* verdict = nullptr) {
   const int length = rec[SRCH_LENGTH] + 1;
   if (!(te | tr)) { rec[SRCH_LENGTH] = length; return 0; }
   const int status = rec[SRCH_STATUS], nan_now = meta[4];
   const int flags = search_flags(te, tr, nan_now, rec[SRCH_NAN0], status, fall, meta[15]);
   const int level = rec[SRCH_LEVEL], episode = rec[SRCH_EPISODE];
   int extra = 0;
-  if (it.has && !(status & SRCH_DONE) && (status & SRCH_AT_RESET)) extra = search_trial(rec, it, (flags & it.fail_mask) != 0);
-  else rec[SRCH_UNCOUNTED]++;
+  if (it.has && !(status & SRCH_DONE) && (status & SRCH_AT_RESET)) {
+    const bool by_check = verdict != nullptr && ((((verdict[4] | verdict[6]) & it.chk_lo) | ((verdict[5] | verdict[7]) & it.chk_hi)) != 0);
+    extra = search_trial(rec, it, (flags & it.fail_mask) != 0 || by_check) | (by_check ? SRCH_BY_CHECK : 0);
+  } else rec[SRCH_UNCOUNTED]++;
   int* t = ring + (size_t)((unsigned)episode % (unsigned)slots) * SRCH_TRIAL_WORDS;
   t[0] = episode; t[1] = level; t[2] = flags | extra; t[3] = length;
   rec[SRCH_EPISODE] = episode + 1;

@@ -9,6 +9,8 @@
 // the item's rule and writes one trial record into the env's ring.  Lane = env, 64-lane blocks, no LDS, no cross-lane traffic, no
 // host read, no join: a captured step carries the launches.  The kernels write only the search's own buffers (the scenario kernel:
 // what scenario_step_kernel writes); the one atomic is the decrement of the engine's "remaining" word when an env spends its budget.
+// search_step_checks_kernel is search_step_kernel for a search with an item that fails on a check: it also reads the verdict record
+// checks_step_kernel closed behind the same step.  The level's third reader, actfault_search_step_kernel, is in cosim_actfault.hip.
 #include "cosim_search.h"
 
 namespace cosim {
@@ -47,6 +49,41 @@ __global__ __launch_bounds__(64) void search_step_kernel(SrchArgs a) {
   // the usual step moves one word of the record (length); the table is read only on a step that ends the episode
   const SrchItem it = (te | tr) ? search_item(a.tab, a.scn_row[env]) : SrchItem();
   const int became_done = search_step_lane(a.rec + (size_t)env * SRCH_NCNT, a.ring + (size_t)env * a.slots * SRCH_TRIAL_WORDS, a.slots, it, te, tr, meta, a.fall);
+  if (became_done) atomicSub(a.remaining, 1);
+}
+
+// where the verdict records of the scenario checks lie (cosim_checks.h): counters [N][ncnt] (word 0: episodes ended), rings
+// [N][slots][words]
+struct SrchVerdicts {
+  const int* cnt;
+  const int* rec;
+  int ncnt, slots, words;
+};
+
+// search_step_kernel of a search with an item that selects a check.  checks_step_kernel ran behind this same step ahead of this
+// launch on the same stream: on a step with a done flag it closed the ended episode's record and moved its own ordinal on, so the
+// record is the one of ordinal cnt[0] - 1 (the checks' own count: the two ordinals need not agree).
+struct SrchChkArgs {
+  SrchArgs srch;
+  SrchVerdicts v;
+};
+
+__global__ __launch_bounds__(64) void search_step_checks_kernel(SrchChkArgs s) {
+  const SrchArgs& a = s.srch;
+  const SrchVerdicts& v = s.v;
+  const int i = (int)blockIdx.x * 64 + (int)threadIdx.x;
+  if (i >= a.count) return;   // the last wave's tail
+  const int env = a.first + i;
+  if (env >= a.n_envs) return;
+  const int te = a.term[env] != 0, tr = a.trunc[env] != 0;
+  const int* meta = reinterpret_cast<const int*>(a.state + (size_t)env * a.s_stride + a.s_meta);
+  const SrchItem it = (te | tr) ? search_item(a.tab, a.scn_row[env]) : SrchItem();
+  const int* verdict = nullptr;
+  if ((te | tr) && it.has && (it.chk_lo | it.chk_hi) != 0) {
+    const unsigned closed = (unsigned)v.cnt[(size_t)env * v.ncnt] - 1u;
+    verdict = v.rec + ((size_t)env * v.slots + (size_t)(closed % (unsigned)v.slots)) * v.words;
+  }
+  const int became_done = search_step_lane(a.rec + (size_t)env * SRCH_NCNT, a.ring + (size_t)env * a.slots * SRCH_TRIAL_WORDS, a.slots, it, te, tr, meta, a.fall, verdict);
   if (became_done) atomicSub(a.remaining, 1);
 }
 

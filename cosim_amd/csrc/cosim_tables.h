@@ -188,9 +188,12 @@ struct ParRaw {
   int n_scn;   // that of the scenario table that is set
   const int32_t *adr, *t, *field, *index, *op; const float* value;
 };
-struct ParShape { std::string err; int n = 0; std::vector<int32_t> word; };
+struct ParShape { std::string err; int n = 0, marked = 0; std::vector<int32_t> word; };   // marked: items a limit search scales
+// The limit search that is armed, as a marked item (SCNPAR_MARK of an op word, FLT_MARK of a fault's elem) is held against it: `bit` is
+// the kind's SRCH_* target.  Null where no search is armed: a marked item is refused then.
+struct FltMarks { int bit; const int32_t *has, *targets; const float *lo, *hi; };
 
-inline ParShape validate_params(const TableDims& d, const ParRaw& r) {
+inline ParShape validate_params(const TableDims& d, const ParRaw& r, const FltMarks* marks = nullptr) {
   const std::string fn = "cosim_scenario_params_set";
   ParShape v;
   const RowAdr rows[1] = {{"adr", r.adr, "parameter items", SCNPAR_MAX_ITEMS, r.t && r.field && r.index && r.op && r.value}};
@@ -203,8 +206,16 @@ inline ParShape validate_params(const TableDims& d, const ParRaw& r) {
       int32_t word = 0;
       TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
       TAB_TRY(field_rule(row, d, r.field[i], r.index[i], &word));
-      if (r.op[i] != SCNPAR_SCALE && r.op[i] != SCNPAR_SET) TAB_TRY(row + ": unknown op " + std::to_string(r.op[i]) + " (0 scale, 1 set)");
+      const bool mark = r.op[i] >= 0 && (r.op[i] & SCNPAR_MARK) != 0;
+      const int op = mark ? (r.op[i] & ~SCNPAR_MARK) : r.op[i];
+      if (op != SCNPAR_SCALE && op != SCNPAR_SET) TAB_TRY(row + ": unknown op " + std::to_string(r.op[i]) + " (0 scale, 1 set)");
       if (!std::isfinite(r.value[i])) TAB_TRY(row + ": value is not finite");
+      if (mark) {
+        if (!marks || !marks->has[s] || !(marks->targets[s] & marks->bit))
+          TAB_TRY(row + ": the item is marked for a limit search and no search whose targets name the parameter windows is armed on the scenario (cosim_set_param \"search\" first)");
+        if (!std::isfinite(r.value[i] * marks->lo[s]) || !std::isfinite(r.value[i] * marks->hi[s])) TAB_TRY(row + ": value * level is not finite at an end of the search's range");
+        v.marked++;
+      }
       v.word.push_back(word);
     }
   }
@@ -225,14 +236,14 @@ struct FltRaw {
   int n_scn;   // that of the scenario table that is set
   const int32_t *adr, *t, *elem, *op, *ord; const float* value;
 };
-struct FltShape { std::string err; int n = 0; std::vector<int32_t> item; };
+struct FltShape { std::string err; int n = 0, marked = 0; std::vector<int32_t> item; };   // marked: items a limit search scales
 // what the two kinds differ in besides their rules: how the messages name the setter and an item, the highest op and the list an unknown one is answered with
 struct FltKind { const char *setter, *noun; int max_op; const char* ops; };
 
 // The rules of both kinds, in the order they are reported in.  elem_rule(row, el) is the kind's word on an element, ahead of the op;
 // op_rule(row, el, op, value) its word on an op the shared rules have passed, behind them.
 template <class ElemRule, class OpRule>
-inline FltShape validate_fault_items(const FltKind& kind, const FltRaw& r, ElemRule elem_rule, OpRule op_rule) {
+inline FltShape validate_fault_items(const FltKind& kind, const FltRaw& r, ElemRule elem_rule, OpRule op_rule, const FltMarks* marks = nullptr) {
   const std::string fn = kind.setter, noun = kind.noun, nouns = noun + "s";
   FltShape v;
   const RowAdr rows[1] = {{"adr", r.adr, nouns.c_str(), FLT_MAX_ITEMS, r.t && r.elem && r.op && r.ord && r.value}};
@@ -243,19 +254,33 @@ inline FltShape validate_fault_items(const FltKind& kind, const FltRaw& r, ElemR
     const std::string who = fn + ": scenario " + std::to_string(s);
     for (int i = r.adr[s]; i < r.adr[s + 1]; i++) {
       const std::string row = who + ", " + noun + " " + std::to_string(i - r.adr[s]);
-      const int el = r.elem[i], op = r.op[i];
+      const bool mark = r.elem[i] >= 0 && ((unsigned)r.elem[i] & FLT_MARK) != 0;
+      const int el = mark ? (int)((unsigned)r.elem[i] & ~FLT_MARK) : r.elem[i], op = r.op[i];
       TAB_TRY(window_rule(row, r.t[2 * i], r.t[2 * i + 1]));
+      if (mark && (!marks || !marks->has[s] || !(marks->targets[s] & marks->bit)))
+        TAB_TRY(row + ": the item is marked for a limit search and no search whose targets name these items is armed on the scenario (cosim_set_param \"search\" first)");
       TAB_TRY(elem_rule(row, el));
       if (op < FLT_SCALE || op > kind.max_op) TAB_TRY(row + ": unknown op " + std::to_string(op) + " " + kind.ops);
       if (!std::isfinite(r.value[i])) TAB_TRY(row + ": value is not finite");
       if (op == FLT_NOISE && r.value[i] < 0.f) TAB_TRY(row + ": a noise amplitude must be >= 0");
       if (op == FLT_DROP && !(r.value[i] >= 0.f && r.value[i] <= 1.f)) TAB_TRY(row + ": a drop probability must lie in [0, 1]");
       TAB_TRY(op_rule(row, el, op, r.value[i]));
+      if (mark) {   // the kind's value rule at both ends of the search's range, as the kernel computes them
+        if (op == FLT_HOLD) TAB_TRY(row + ": a hold has no value and cannot be marked for a limit search");
+        const float ends[2] = {r.value[i] * marks->lo[s], r.value[i] * marks->hi[s]};
+        for (const float x : ends) {
+          if (!std::isfinite(x)) TAB_TRY(row + ": value * level is not finite at an end of the search's range");
+          if (op == FLT_NOISE && x < 0.f) TAB_TRY(row + ": a noise amplitude must be >= 0 at both ends of the search's range");
+          if (op == FLT_DROP && !(x >= 0.f && x <= 1.f)) TAB_TRY(row + ": a drop probability must lie in [0, 1] at both ends of the search's range");
+          TAB_TRY(op_rule(row, el, op, x));
+        }
+        v.marked++;
+      }
       if (r.ord[i] < 0 || r.ord[i] >= FLT_MAX_ITEMS) TAB_TRY(row + ": ordinal " + std::to_string(r.ord[i]) + " outside 0..255");
       int32_t vb;
       memcpy(&vb, &r.value[i], 4);
       v.item.push_back(r.t[2 * i]); v.item.push_back(r.t[2 * i + 1]);
-      v.item.push_back((int32_t)((unsigned)el | (unsigned)op << 16 | (unsigned)r.ord[i] << 24)); v.item.push_back(vb);
+      v.item.push_back((int32_t)((unsigned)el | (mark ? FLT_MARK : 0u) | (unsigned)op << 16 | (unsigned)r.ord[i] << 24)); v.item.push_back(vb);
     }
   }
   v.n = r.adr[r.n_scn];
@@ -275,7 +300,7 @@ struct ObsDims {
   const unsigned char* el_field;   // [frame_dim] CS_OBS_* of every frame element
   int command_field;               // CS_OBS_COMMAND
 };
-inline FltShape validate_faults(const ObsDims& d, const FltRaw& r) {
+inline FltShape validate_faults(const ObsDims& d, const FltRaw& r, const FltMarks* marks = nullptr) {
   const auto elem_rule = [&d](const std::string& row, int e) {
     if (e < 0 || e >= d.frame_dim) return row + ": element " + std::to_string(e) + " out of range: the frame has " + std::to_string(d.frame_dim) + " elements";
     if (d.el_field[e] != d.command_field) return std::string();
@@ -285,16 +310,16 @@ inline FltShape validate_faults(const ObsDims& d, const FltRaw& r) {
     if ((op != FLT_HOLD && op != FLT_DROP) || (e < d.stacked_dim && d.stack_size >= 2)) return std::string();
     return row + ": hold / drop needs a stacked element and stack_size >= 2: there is no previous frame in the record";
   };
-  return validate_fault_items({OBF_SETTER, "fault item", FLT_DROP, "(0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop)"}, r, elem_rule, op_rule);
+  return validate_fault_items({OBF_SETTER, "fault item", FLT_DROP, "(0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop)"}, r, elem_rule, op_rule, marks);
 }
 
 // actions: `elem` is an actuator index
-inline FltShape validate_action_faults(int nu, const FltRaw& r) {
+inline FltShape validate_action_faults(int nu, const FltRaw& r, const FltMarks* marks = nullptr) {
   const auto elem_rule = [nu](const std::string& row, int j) {
     return j >= 0 && j < nu ? std::string() : row + ": actuator " + std::to_string(j) + " out of range: the model has " + std::to_string(nu) + " actuators";
   };
   const auto op_rule = [](const std::string& row, int, int op, float value) { return op == FLT_CLIP && value < 0.f ? row + ": a clip bound must be >= 0" : std::string(); };
-  return validate_fault_items({ACF_SETTER, "action-fault item", FLT_CLIP, "(0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop, 6 clip)"}, r, elem_rule, op_rule);
+  return validate_fault_items({ACF_SETTER, "action-fault item", FLT_CLIP, "(0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop, 6 clip)"}, r, elem_rule, op_rule, marks);
 }
 
 // ---- cosim_scenario_checks_set.  Image: adr | t | signal | index | mode | cmp | bound
@@ -406,14 +431,22 @@ inline bool curves_same_sizes(const WordPacker& pk, const CurTable& tab, const i
          pk.same(&tab.cw, old);
 }
 
-// ---- cosim_set_param "search".  Image: has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip, [S] each
+// ---- cosim_set_param "search".  Image: has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip, [S] each; the
+// long form adds harder | chk_lo | chk_hi
 struct SrchRaw {
   int n_scn;   // the table's first word
   int slots;
   const int32_t* has; const float *lo, *hi, *x0, *d0, *d_min; const int32_t *rule, *trials, *targets, *fail_mask, *rev_skip;
+  const int32_t *harder = nullptr, *chk_lo = nullptr, *chk_hi = nullptr;   // the long form's columns (null: the short form)
 };
-// what the validator needs to know of the scenario table that is set; key_adr / push_adr: its row addresses [S + 1] (read only once S matches)
-struct SrchDims { int n_scn, mode, auto_reset; const int32_t *key_adr, *push_adr; };
+// what the validator needs to know of the scenario table that is set; key_adr / push_adr: its row addresses [S + 1] (read only once S
+// matches); chk_adr: those of the checks that are armed (null: none are)
+// par_adr / obs_adr / act_adr: the row addresses of the parameter windows, observation faults and action faults that are set (null: none)
+struct SrchDims {
+  int n_scn, mode, auto_reset; const int32_t *key_adr, *push_adr; const int32_t* chk_adr = nullptr;
+  const int32_t *par_adr = nullptr, *obs_adr = nullptr, *act_adr = nullptr;
+};
+constexpr int SRCH_TARGET_BITS = SRCH_PUSHES | SRCH_COMMANDS | SRCH_PARAMS | SRCH_OBS_FAULTS | SRCH_ACT_FAULTS;
 struct SrchShape { std::string err; int n = 0; };   // n: scenarios that have an item
 
 // A fall bit in fail_mask while no fall rule is set is NOT refused: the bit never fires (the rule may be set later).
@@ -436,9 +469,26 @@ inline SrchShape validate_search(const SrchDims& d, const SrchRaw& r) {
     if (!std::isfinite(r.d0[s]) || !(r.d_min[s] > 0.f) || !(r.d_min[s] <= r.d0[s])) TAB_TRY(who + ": the steps must hold 0 < d_min <= d0");
     if (r.rule[s] != SRCH_BISECT && r.rule[s] != SRCH_STAIRCASE) TAB_TRY(who + ": unknown rule " + std::to_string(r.rule[s]) + " (0 bisect, 1 staircase)");
     if (r.trials[s] < 1 || r.trials[s] > SRCH_MAX_TRIALS) TAB_TRY(who + ": trials " + std::to_string(r.trials[s]) + " outside 1..2^20");
-    if (r.targets[s] < 1 || r.targets[s] > (SRCH_PUSHES | SRCH_COMMANDS)) TAB_TRY(who + ": targets " + std::to_string(r.targets[s]) + " names nothing (1 pushes | 2 commands)");
-    if (r.fail_mask[s] == 0 || (r.fail_mask[s] & ~SRCH_FAIL_BITS))
-      TAB_TRY(who + ": fail_mask " + std::to_string(r.fail_mask[s]) + " must be a non-empty set of 1 terminated | 4 non-finite | 32 tilt | 64 height | 128 contact");
+    if (r.targets[s] < 1 || (r.targets[s] & ~SRCH_TARGET_BITS))
+      TAB_TRY(who + ": targets " + std::to_string(r.targets[s]) + " names nothing (1 pushes | 2 commands | 4 parameter windows | 8 observation faults | 16 action faults)");
+    {   // an item kind (4, 8, 16) names the items of a table that is set; with no such table the word names nothing a search knew before them
+      const struct { int bit; const int32_t* adr; const char* what; } kinds[3] = {{SRCH_PARAMS, d.par_adr, "parameter windows and the scenario has no parameter item"},
+          {SRCH_OBS_FAULTS, d.obs_adr, "observation faults and the scenario has no fault item"}, {SRCH_ACT_FAULTS, d.act_adr, "action faults and the scenario has no action-fault item"}};
+      for (const auto& k : kinds) {
+        if (!(r.targets[s] & k.bit)) continue;
+        if (!k.adr) TAB_TRY(who + ": targets " + std::to_string(r.targets[s]) + " names nothing (1 pushes | 2 commands)");
+        if (k.adr[s + 1] == k.adr[s]) TAB_TRY(who + ": the target is the " + k.what);
+      }
+    }
+    const unsigned long long chk = r.harder ? (unsigned long long)(uint32_t)r.chk_lo[s] | (unsigned long long)(uint32_t)r.chk_hi[s] << 32 : 0ull;
+    if ((r.fail_mask[s] == 0 && chk == 0ull) || (r.fail_mask[s] & ~SRCH_FAIL_BITS))
+      TAB_TRY(who + ": fail_mask " + std::to_string(r.fail_mask[s]) + " must be a non-empty set of 1 terminated | 4 non-finite | 32 tilt | 64 height | 128 contact (empty only with a check selected)");
+    if (r.harder && r.harder[s] != SRCH_HARDER_UP && r.harder[s] != SRCH_HARDER_DOWN) TAB_TRY(who + ": harder " + std::to_string(r.harder[s]) + " is neither 0 (up) nor 1 (down)");
+    if (chk != 0ull) {
+      if (!d.chk_adr) TAB_TRY(who + ": the item fails on a check and no checks are armed (cosim_scenario_checks_set): arm the checks first");
+      const int nc = d.chk_adr[s + 1] - d.chk_adr[s];
+      if (nc < 64 && (chk >> nc) != 0ull) TAB_TRY(who + ": the item fails on a check the scenario does not have: it has " + std::to_string(nc) + " check items");
+    }
     if (r.rev_skip[s] < 0 || r.rev_skip[s] > SRCH_MAX_REV_SKIP) TAB_TRY(who + ": rev_skip " + std::to_string(r.rev_skip[s]) + " outside 0..255");
     if ((r.targets[s] & SRCH_PUSHES) && d.push_adr[s + 1] == d.push_adr[s]) TAB_TRY(who + ": the target is the pushes and the scenario has no push window");
     if ((r.targets[s] & SRCH_COMMANDS) && d.key_adr[s + 1] == d.key_adr[s]) TAB_TRY(who + ": the target is the commands and the scenario has no keyframe");
@@ -452,6 +502,7 @@ inline void pack_search(WordPacker& pk, SrchTable& tab, const SrchRaw& r, const 
   pk.add(&tab.has, r.has, S); pk.add(&tab.lo, r.lo, S); pk.add(&tab.hi, r.hi, S); pk.add(&tab.x0, r.x0, S); pk.add(&tab.d0, r.d0, S);
   pk.add(&tab.d_min, r.d_min, S); pk.add(&tab.rule, r.rule, S); pk.add(&tab.trials, r.trials, S); pk.add(&tab.targets, r.targets, S);
   pk.add(&tab.fail_mask, r.fail_mask, S); pk.add(&tab.rev_skip, r.rev_skip, S);
+  if (r.harder) { pk.add(&tab.harder, r.harder, S); pk.add(&tab.chk_lo, r.chk_lo, S); pk.add(&tab.chk_hi, r.chk_hi, S); }
   tab.n_scn = r.n_scn; tab.n_items = v.n;
 }
 

@@ -434,7 +434,8 @@ class Engine:
 
     def search_set(self, words):
         """Limit search, through ``cosim_set_param "search"``: ``words`` = the int32 word table of ``ScenarioTable.pack_search`` (``S |
-        slots | has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip``; ``None``: clear the search)."""
+        slots | has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip``, in its long form ``| harder | chk_lo |
+        chk_hi``; ``None``: clear the search)."""
         words = np.zeros(1, dtype=np.int32) if words is None else np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
         self._check(self.L.cosim_set_param(self.h, b"search", words.ctypes.data, int(words.size)))
 

@@ -66,6 +66,15 @@ middle, "step" = (hi - lo) / 4, "min_step" = (hi - lo) / 256, "rule": "bisect" |
 keeps a level in ``[lo, hi]`` that is multiplied into the row's push vectors and / or command keyframes and moved when an episode of
 the env ends -- down after a failure (an ended episode with one of the ``fail_on`` ledger flags), up after a pass.  ``cosim_amd/search.py``
 has the result container and the numpy twin; ``reference_schedule(level=...)`` is the twin of the scaled schedule.
+``targets`` also takes ``"params"``, ``"faults"`` and ``"action_faults"`` (every listed item of that kind in the row) or ``"kind:i,j"``
+(the listed items with the ordinals i, j, counted before ``"*"`` is expanded): a MARKED item uses ``float32(value * level)`` in the place
+of its value (a window: ``scale`` becomes ``base * v``, ``set`` becomes ``v``; ``drop``: as its probability; a ``hold`` has no value and
+cannot be marked), the row's other items are untouched; ``reference_params`` / ``reference_obs_faults`` / ``reference_action_faults``
+``(level=...)`` are the twins.  Parameter windows and action faults take the level the open episode runs at, an observation fault the
+level of the episode its observation belongs to.  ``"harder":
+"up" | "down"`` (default up): with ``"down"`` a LOWER level is harder (a gain scale, a friction): a failure moves the level up, a pass
+down.  ``fail_on`` also takes ``"checks"`` (any check of the row), ``"check:NAME"`` and ``"check:I"``: a trial fails too if a selected
+check of the ended episode did not pass (failed or incomplete); the checks must be armed (``check_slots``).
 """
 from __future__ import annotations
 
@@ -94,9 +103,14 @@ ACTION_FAULT_OPS = dict(FAULT_OPS, clip=6)
 MAX_FAULT_ITEMS = MAX_ACTION_FAULT_ITEMS = 256
 SEARCH_RULES = {"bisect": 0, "staircase": 1}
 SEARCH_TARGETS = {"pushes": 1, "commands": 2}
+SEARCH_ITEM_TARGETS = {"params": 4, "faults": 8, "action_faults": 16}   # kinds whose MARKED items the level scales ("kind" or "kind:i,j")
+PARAM_MARK = 0x100                             # of a packed parameter item's op word: a search scales its value
+SEARCH_HARDER = {"up": 0, "down": 1}
+FAULT_MARK = 0x8000                            # of a packed fault item's element: a search scales its value
 SEARCH_FAIL_ON = {"terminated": 1, "nonfinite": 4, "tilt": 32, "height": 64, "contact": 128}   # the ledger's flag values
 MAX_SEARCH_SLOTS, MAX_SEARCH_TRIALS, MAX_SEARCH_REV_SKIP = 64, 1 << 20, 255
 _SEARCH_KEYS = ("lo", "hi", "start", "step", "min_step", "rule", "trials", "targets", "fail_on", "rev_skip")
+_SEARCH_OPT_KEYS = ("harder",)                 # emitted only when not the default
 
 
 class _FaultKind(NamedTuple):
@@ -248,7 +262,8 @@ class ScenarioTable:
             self.curve_rows.append(_curve_rows(s, sc.get("curves") or []))
             for kind in FAULT_KINDS:
                 getattr(self, kind.rows).append(_fault_kind_rows(kind, s, sc.get(kind.key) or []))
-            self.search.append(_search_item(s, sc.get("search"), bool(pushes), bool(keys)))
+            self.search.append(_search_item(s, sc.get("search"), bool(pushes), bool(keys),
+                                            {"params": self.param_windows[s], **{k.key: getattr(self, k.rows)[s] for k in FAULT_KINDS}}, self.check_rows[s]))
         if names is not None or not self.has_params:
             self.resolve(names or {})
         cn = (names or {}).get("checks")
@@ -285,8 +300,26 @@ class ScenarioTable:
             raise ValueError(f"ScenarioTable: the {kind.what} are not resolved yet: {kind.unresolved}")
         return getattr(self, kind.key)
 
-    def _pack_fault_items(self, kind: _FaultKind):
-        return _pack_items(self._resolved_items(kind), 2, (np.int32, np.int32, np.int32, np.float32))
+    def _pack_fault_items(self, kind: _FaultKind, marks: bool = False):
+        """The CSR form of the kind's items; ``marks``: the items a search item of their row marks carry ``FAULT_MARK`` in their
+        element (the engine takes such a table only while that search is armed)."""
+        adr, t, elem, op, ord_, value = _pack_items(self._resolved_items(kind), 2, (np.int32, np.int32, np.int32, np.float32))
+        if marks:
+            for s in range(len(self)):
+                m = self.search_marks(kind.key, s)
+                if m:
+                    sl = slice(int(adr[s]), int(adr[s + 1]))
+                    elem[sl] |= np.where(np.isin(ord_[sl], m), FAULT_MARK, 0).astype(np.int32)
+        return adr, t, elem, op, ord_, value
+
+    def search_marks(self, key: str, s: int) -> list:
+        """The ordinals of the listed items of kind ``key`` (``"params"``, ``"faults"``, ``"action_faults"``) that scenario ``s``'s
+        search item marks, ascending."""
+        it = self.search[s]
+        return list(it["marks"].get(key, ())) if it is not None else []
+
+    def has_search_marks(self, key: str) -> bool:
+        return any(self.search_marks(key, s) for s in range(len(self)))
 
     def _faults_from_csr(self, kind: _FaultKind, adr, t, elem, op, ord, value, listed) -> "ScenarioTable":
         """A table with everything of this one but the faults of ``kind``, which are those the CSR arrays hold, not resolved yet: the
@@ -450,7 +483,9 @@ class ScenarioTable:
 
     def pack_search(self, slots: int) -> np.ndarray:
         """The int32 word table ``cosim_set_param "search"`` takes: ``S | slots | has[S] | lo | hi | x0 | d0 | d_min | rule | trials |
-        targets | fail_mask | rev_skip`` (``[S]`` each, floats as their bits; zeros for a scenario without an item)."""
+        targets | fail_mask | rev_skip`` (``[S]`` each, floats as their bits; zeros for a scenario without an item), ``2 + 11 S`` words.
+        Only when an item uses ``harder="down"`` or fails on a check, three more columns follow: ``harder | chk_lo | chk_hi`` (the
+        64-bit mask of the selected checks of the row), ``2 + 14 S`` words."""
         if isinstance(slots, bool) or not isinstance(slots, (int, np.integer)) or not 1 <= int(slots) <= MAX_SEARCH_SLOTS:
             raise ValueError(f"ScenarioTable: search slots {slots!r}: an integer 1..{MAX_SEARCH_SLOTS}")
         S = len(self)
@@ -461,18 +496,27 @@ class ScenarioTable:
                 continue
             has[s] = 1
             f[:, s] = [it["lo"], it["hi"], it["start"], it["step"], it["min_step"]]
-            i[:, s] = [SEARCH_RULES[it["rule"]], it["trials"], sum(SEARCH_TARGETS[t] for t in it["targets"]),
-                       sum(SEARCH_FAIL_ON[t] for t in it["fail_on"]), it["rev_skip"]]
-        return np.concatenate([np.array([S, int(slots)], dtype=np.int32), has, f.view(np.int32).reshape(-1), i.reshape(-1)])
+            i[:, s] = [SEARCH_RULES[it["rule"]], it["trials"], search_target_bits(it), search_fail_mask(it), it["rev_skip"]]
+        words = [np.array([S, int(slots)], dtype=np.int32), has, f.view(np.int32).reshape(-1), i.reshape(-1)]
+        if any(it is not None and (it["harder"] != "up" or it["check_mask"]) for it in self.search):
+            x = np.zeros((3, S), dtype=np.uint32)
+            for s, it in enumerate(self.search):
+                if it is not None:
+                    x[:, s] = [SEARCH_HARDER[it["harder"]], it["check_mask"] & 0xFFFFFFFF, it["check_mask"] >> 32]
+            words.append(x.view(np.int32).reshape(-1))
+        return np.concatenate(words)
 
     def search_from_words(self, words) -> "ScenarioTable":
-        """A table with everything of this one but the search items, which are those the word table of ``pack_search`` holds."""
+        """A table with everything of this one but the search items, which are those the word table of ``pack_search`` holds.  The
+        words say WHICH KINDS an item marks (targets 4, 8, 16), not which ordinals: those travel as mark bits in the kinds' own item
+        tables.  Where this table's own item of the row names the kind, its ordinals are kept; else the whole kind is marked -- and
+        if that would mark a ``hold`` the item is refused like any other (``ValueError``): pass the ordinals in the table instead."""
         words = np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
         scn = self.to_list()
         S = len(scn)
-        if len(words) != 2 + 11 * S or int(words[0]) != S:
+        if len(words) not in (2 + 11 * S, 2 + 14 * S) or int(words[0]) != S:
             raise ValueError(f"ScenarioTable: a search table of {int(words[0]) if len(words) else 0} scenarios in {len(words)} words, the table has {S}")
-        cols = words[2:].reshape(11, S)
+        cols = words[2:].reshape(-1, S)
         fl = np.ascontiguousarray(cols[1:6]).view(np.float32)
         for s, sc in enumerate(scn):
             sc.pop("search", None)
@@ -481,6 +525,20 @@ class ScenarioTable:
                                 "rule": {v: k for k, v in SEARCH_RULES.items()}.get(int(cols[6, s]), int(cols[6, s])), "trials": int(cols[7, s]),
                                 "targets": [k for k, v in SEARCH_TARGETS.items() if int(cols[8, s]) & v],
                                 "fail_on": [k for k, v in SEARCH_FAIL_ON.items() if int(cols[9, s]) & v], "rev_skip": int(cols[10, s])}
+                # which listed items a kind's bit marks travels in that kind's item table: this table's own item says it, else all are
+                old = self.search[s]["targets"] if self.search[s] is not None else []
+                for k, v in SEARCH_ITEM_TARGETS.items():
+                    if int(cols[8, s]) & v:
+                        sc["search"]["targets"] += [n for n in old if n.partition(":")[0] == k] or [k]
+                if len(cols) > 11:
+                    if int(cols[11, s]):
+                        sc["search"]["harder"] = {v: k for k, v in SEARCH_HARDER.items()}.get(int(cols[11, s]), int(cols[11, s]))
+                    mask = (int(cols[12, s]) & 0xFFFFFFFF) | (int(cols[13, s]) & 0xFFFFFFFF) << 32
+                    nc = len(self.check_rows[s])
+                    if mask and nc and mask == (1 << nc) - 1:
+                        sc["search"]["fail_on"].append("checks")
+                    else:
+                        sc["search"]["fail_on"] += [f"check:{i}" for i in range(64) if mask >> i & 1]
         return type(self)(scn, self.command_dim)
 
     @property
@@ -524,9 +582,9 @@ class ScenarioTable:
         """Expand the windows against ``names`` (field -> list of entry names): ``self.params[s]`` becomes the list of items ``(t0, t1,
         field id, index, op id, float32 value)`` in listed order, ``"*"`` and names that several entries share expanded in index
         order.  Raises ``ValueError`` naming the scenario and the row: unknown name, index out of range, more than 256 items."""
-        out = []
+        out, out_ords = [], []
         for s, wins in enumerate(self.param_windows):
-            items = []
+            items, ords = [], []
             for r, (t0, t1, field, index, op, value) in enumerate(wins):
                 who = f"ScenarioTable: scenario {s}, parameter window {r}"
                 if field not in names:
@@ -541,10 +599,12 @@ class ScenarioTable:
                         raise ValueError(f"{who}: index {index} out of range: '{field}' has {len(entries)} entries")
                     idx = [index]
                 items += [(t0, t1, PARAM_FIELDS[field], i, PARAM_OPS[op], value) for i in idx]
+                ords += [r] * len(idx)
             if len(items) > MAX_PARAM_ITEMS:
                 raise ValueError(f"ScenarioTable: scenario {s}: {len(items)} parameter items after expansion, at most {MAX_PARAM_ITEMS}")
             out.append(items)
-        self.params = out
+            out_ords.append(ords)
+        self.params, self.param_ords = out, out_ords                # param_ords[s][k]: the listed window item k was expanded from
         return self
 
     @property
@@ -604,6 +664,7 @@ class ScenarioTable:
         for sc, it in zip(out, self.search):
             if it is not None:
                 sc["search"] = {k: (list(it[k]) if isinstance(it[k], list) else it[k]) for k in _SEARCH_KEYS}
+                sc["search"].update({k: it[k] for k in _SEARCH_OPT_KEYS if it[k] != "up"})
         return out
 
     def pack(self):
@@ -613,10 +674,18 @@ class ScenarioTable:
         push_adr, push_t, push_v = _pack_items(self.pushes, 2, (np.float32,))
         return key_adr, key_t.reshape(-1), key_cmd.reshape(len(key_t), self.command_dim), push_adr, push_t, push_v.reshape(-1, 3)
 
-    def pack_params(self):
+    def pack_params(self, marks: bool = False):
         """``(adr int32[S + 1], t int32[n, 2], field int32[n], index int32[n], op int32[n], value float32[n])``: the expanded items
-        in the CSR form of ``cosim_scenario_params_set``."""
-        return _pack_items(self._resolved(), 2, (np.int32, np.int32, np.int32, np.float32))
+        in the CSR form of ``cosim_scenario_params_set``.  ``marks``: the items a search item of their row marks carry ``PARAM_MARK``
+        in their op word (the engine takes such a table only while that search is armed)."""
+        adr, t, field, index, op, value = _pack_items(self._resolved(), 2, (np.int32, np.int32, np.int32, np.float32))
+        if marks:
+            for s in range(len(self)):
+                m = self.search_marks("params", s)
+                if m:
+                    sl = slice(int(adr[s]), int(adr[s + 1]))
+                    op[sl] |= np.where(np.isin(self.param_ords[s], m), PARAM_MARK, 0).astype(np.int32)
+        return adr, t, field, index, op, value
 
     def params_from_csr(self, adr, t, field, index, op, value, names: dict = None) -> "ScenarioTable":
         """A table with this one's commands and pushes and the windows that the CSR arrays of ``pack_params`` hold (one window per
@@ -881,13 +950,63 @@ def _check_rows(s: int, rows) -> list:
     return out
 
 
-def _search_item(s: int, item, has_pushes: bool, has_keys: bool):
+def search_target_bits(it: dict) -> int:
+    """The ``targets`` word of a search item (``_search_item``)."""
+    return sum(SEARCH_TARGETS[t] for t in it["targets"] if t in SEARCH_TARGETS) | sum(SEARCH_ITEM_TARGETS[k] for k in it["marks"])
+
+
+def search_fail_mask(it: dict) -> int:
+    """The ledger flags a search item fails on (its checks are ``it["check_mask"]``)."""
+    return sum(SEARCH_FAIL_ON[t] for t in it["fail_on"] if t in SEARCH_FAIL_ON)
+
+
+class _ParamKind(NamedTuple):
+    """Parameter windows as a kind a search may mark: what ``_search_marks`` reads of a ``_FaultKind``."""
+    key: str = "params"
+    noun: str = "parameter window"
+
+
+def _search_marks(who: str, kind, name: str, rows, lo: float, hi: float) -> list:
+    """The ordinals a target ``"kind"`` / ``"kind:i,j"`` marks among the listed ``rows`` of its kind, each held to the kind's value rule
+    at both ends of the level's range."""
+    _, colon, rest = name.partition(":")
+    if not rows:
+        raise ValueError(f"{who}: the target is '{name}' and the scenario lists no {kind.noun}")
+    if colon:
+        try:
+            ords = sorted({int(x) for x in rest.split(",")})
+        except ValueError:
+            raise ValueError(f"{who}: target {name!r}: '{kind.key}:' is followed by ordinals, e.g. '{kind.key}:0,2'") from None
+        bad = [o for o in ords if not 0 <= o < len(rows)]
+        if bad or not ords:
+            raise ValueError(f"{who}: target {name!r}: ordinal {bad[0] if bad else rest!r} outside the scenario's {len(rows)} listed {kind.noun}s")
+    else:
+        ords = list(range(len(rows)))
+    for o in ords:
+        op, value = (rows[o][-2], np.float32(rows[o][-1])) if kind.key == "params" else (rows[o][-3], np.float32(rows[o][-2]))
+        if op == "hold":
+            raise ValueError(f"{who}: target {name!r} would mark {kind.noun} {o}, a hold: a hold has no value to scale")
+        with np.errstate(all="ignore"):
+            ends = [float(value * np.float32(lo)), float(value * np.float32(hi))]
+        for x in ends:
+            if not math.isfinite(x):
+                raise ValueError(f"{who}: target {name!r}, {kind.noun} {o}: value * level is not finite at an end of [lo, hi]")
+            if op in ("noise", "clip") and x < 0:
+                raise ValueError(f"{who}: target {name!r}, {kind.noun} {o}: a {op} value must stay >= 0 over [lo, hi], got {x!r}")
+            if op == "drop" and not 0.0 <= x <= 1.0:
+                raise ValueError(f"{who}: target {name!r}, {kind.noun} {o}: a drop probability must stay in [0, 1] over [lo, hi], got {x!r}")
+    return ords
+
+
+def _search_item(s: int, item, has_pushes: bool, has_keys: bool, fault_rows: dict = None, check_rows=()):
     """The ``"search"`` value of scenario ``s`` as a dict of ``_SEARCH_KEYS`` with the defaults filled in and the floats rounded to
-    float32 (what the device holds), or ``None``.  Raises ``ValueError`` naming the scenario."""
+    float32 (what the device holds), or ``None``; besides the keys: ``harder``, ``marks`` (kind -> the marked ordinals of the
+    scenario's listed items ``fault_rows[kind]``) and ``check_mask`` (bit i: check i of ``check_rows`` is a failure criterion).  Raises
+    ``ValueError`` naming the scenario."""
     if item is None:
         return None
     who = f"ScenarioTable: scenario {s}, search"
-    if not isinstance(item, dict) or set(item) - set(_SEARCH_KEYS):
+    if not isinstance(item, dict) or set(item) - set(_SEARCH_KEYS) - set(_SEARCH_OPT_KEYS):
         raise ValueError(f"{who}: a mapping with keys out of {_SEARCH_KEYS} is expected, got {item!r}")
     for k in ("lo", "hi", "rule", "trials", "targets", "fail_on"):
         if k not in item:
@@ -914,12 +1033,49 @@ def _search_item(s: int, item, has_pushes: bool, has_keys: bool):
         raise ValueError(f"{who}: trials {trials!r}: an integer 1..2^20")
     if isinstance(rev_skip, bool) or not isinstance(rev_skip, (int, np.integer)) or not 0 <= int(rev_skip) <= MAX_SEARCH_REV_SKIP:
         raise ValueError(f"{who}: rev_skip {rev_skip!r}: an integer 0..{MAX_SEARCH_REV_SKIP}")
+    harder = item.get("harder", "up")
+    if not isinstance(harder, str) or harder not in SEARCH_HARDER:
+        raise ValueError(f"{who}: harder {harder!r}: 'up' or 'down'")
     out = {"lo": lo, "hi": hi, "start": start, "step": step, "min_step": min_step, "rule": rule, "trials": int(trials)}
+    kinds = {"params": _ParamKind(), **{k.key: k for k in FAULT_KINDS}}
+    check_names = [r[7] for r in check_rows]
+
+    def extra(key, n):      # whether n is one of the forms beyond the plain names
+        if not isinstance(n, str):
+            return False
+        if key == "targets":
+            return n.partition(":")[0] in kinds
+        return n == "checks" or n.startswith("check:")
     for key, known in (("targets", SEARCH_TARGETS), ("fail_on", SEARCH_FAIL_ON)):
         names = item[key]
-        if isinstance(names, str) or not isinstance(names, (list, tuple)) or not names or len(set(names)) != len(names) or any(n not in known for n in names):
-            raise ValueError(f"{who}: {key} {names!r}: a non-empty list of different names out of {', '.join(known)}")
-        out[key] = [n for n in known if n in names]
+        if (isinstance(names, str) or not isinstance(names, (list, tuple)) or not names or len(set(names)) != len(names)
+                or any(n not in known and not extra(key, n) for n in names)):
+            more = ", ".join(f"{k}[:i,j]" for k in kinds) if key == "targets" else "checks, check:NAME, check:I"
+            raise ValueError(f"{who}: {key} {names!r}: a non-empty list of different names out of {', '.join(known)}, {more}")
+        out[key] = [n for n in known if n in names] + [n for n in names if n not in known]
+    out["marks"], out["check_mask"] = {}, 0
+    for n in out["targets"]:
+        kind = kinds.get(n.partition(":")[0])
+        if kind is None:
+            continue
+        if kind.key in out["marks"]:
+            raise ValueError(f"{who}: targets {item['targets']!r}: '{kind.key}' is named twice")
+        out["marks"][kind.key] = _search_marks(who, kind, n, (fault_rows or {}).get(kind.key) or [], lo, hi)
+    for n in out["fail_on"]:
+        if n == "checks":
+            if not check_rows:
+                raise ValueError(f"{who}: fail_on 'checks' and the scenario has no check")
+            out["check_mask"] |= (1 << len(check_rows)) - 1
+        elif n.startswith("check:"):
+            ref = n[len("check:"):]
+            idx = [i for i, cn in enumerate(check_names) if cn == ref]
+            if not idx and ref.isdigit() and int(ref) < len(check_rows):
+                idx = [int(ref)]
+            if not idx:
+                raise ValueError(f"{who}: fail_on {n!r}: the scenario has no check of that name or ordinal (it has {len(check_rows)}: "
+                                 f"{', '.join(str(c) for c in check_names) or 'none'})")
+            out["check_mask"] |= sum(1 << i for i in idx)
+    out["harder"] = harder
     if "pushes" in out["targets"] and not has_pushes:
         raise ValueError(f"{who}: the target is the pushes and the scenario has no push window")
     if "commands" in out["targets"] and not has_keys:
@@ -1046,21 +1202,35 @@ def reference_schedule(table: ScenarioTable, mode, gid, t, ep, base_cmd, level=N
     return row, cmd, mask, v
 
 
-def reference_params(table: ScenarioTable, mode, gid, t, ep, base_params, layout: dict) -> np.ndarray:
+def reference_params(table: ScenarioTable, mode, gid, t, ep, base_params, layout: dict, level=None) -> np.ndarray:
     """Numpy twin of ``scnparams_step_kernel`` for N envs: global ids ``gid``, episode steps ``t`` (meta word 0), episodes ended ``ep``
     (meta word 11), the base parameter records ``base_params`` ``[N, stride]`` and ``layout`` (``param_layout``: word offset per
-    field).  Returns the effective records float32 ``[N, stride]``, exact: a word under no window that holds is the base word."""
+    field).  Returns the effective records float32 ``[N, stride]``, exact: a word under no window that holds is the base word.
+    ``level`` (float32 ``[N]``, ``None``: no search): the twin of ``scnparams_search_step_kernel`` -- an item its row's search item marks
+    uses ``v = float32(value * level)`` of the env: ``scale`` gives ``base * v``, ``set`` gives ``v``."""
     gid, t = np.asarray(gid, dtype=np.int64).reshape(-1), np.asarray(t, dtype=np.int64).reshape(-1)
     base = np.ascontiguousarray(base_params, dtype=np.float32).reshape(len(gid), -1)
     eff = base.copy()
     row = scenario_rows(len(table), mode, gid, np.asarray(ep).reshape(-1))
     items = table._resolved()
     for i in range(len(gid)):
-        for t0, t1, field, index, op, value in items[row[i]]:
+        marks = table.search_marks("params", row[i]) if level is not None else []
+        for k, (t0, t1, field, index, op, value) in enumerate(items[row[i]]):
             if t0 <= t[i] < t1:
                 w = layout[_FIELD_NAMES[field]] + index
-                eff[i, w] = np.float32(value) if op == PARAM_OPS["set"] else base[i, w] * np.float32(value)
+                v = np.float32(value)
+                if marks and table.param_ords[row[i]][k] in marks:
+                    v = np.float32(v * np.float32(np.asarray(level, dtype=np.float32).reshape(-1)[i]))
+                eff[i, w] = v if op == PARAM_OPS["set"] else np.float32(base[i, w] * v)
     return eff
+
+
+def _level_value(table: ScenarioTable, key: str, r: int, ordinal: int, value, level):
+    """The value word of item ``ordinal`` of row ``r`` for envs at ``level`` (``[M]`` float32 or ``None``): ``float32(value * level)``
+    where the row's search item marks the item, else the value itself."""
+    if level is None or ordinal not in table.search_marks(key, r):
+        return np.float32(value)
+    return (np.float32(value) * np.asarray(level, dtype=np.float32)).astype(np.float32)
 
 
 def _fault_op(name: str, el: int, ordinal: int, value, x, prev, first, draw) -> np.ndarray:
@@ -1068,13 +1238,13 @@ def _fault_op(name: str, el: int, ordinal: int, value, x, prev, first, draw) -> 
     (csrc/cosim_fault.h) compute it: ``prev`` ``[M]`` the previous words, ``first`` ``[M]`` bool the envs at clock 0 (hold and drop are
     the identity there), ``draw(index)`` the envs' Philox words of the kind's purpose."""
     from . import rng
-    v = np.float32(value)
+    v = np.asarray(value, dtype=np.float32)                         # one word, or one per env (a search's marked item)
     if name == "scale":
         x = x * v
     elif name == "bias":
         x = x + v
     elif name == "set":
-        x = np.full_like(x, v)
+        x = np.broadcast_to(v, x.shape).astype(np.float32)
     elif name == "noise":
         x = x + (v * rng.fault_noise_u(draw(el))).astype(np.float32)
     elif name == "clip":
@@ -1085,14 +1255,16 @@ def _fault_op(name: str, el: int, ordinal: int, value, x, prev, first, draw) -> 
     return x.astype(np.float32)
 
 
-def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count, seed: int, frames, layout: dict, active=None) -> np.ndarray:
+def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count, seed: int, frames, layout: dict, active=None, level=None) -> np.ndarray:
     """Numpy twin of ``obsfault_step_kernel`` over a run of K observations of N envs, exact.  ``gid`` ``[N]`` global ids; per
     observation k the POST-step meta words ``t_obs[k]`` (word 0), ``ep[k]`` (word 11) and ``step_count[k]`` (word 1), each ``[K, N]``;
     ``frames`` ``[K, N, frame_dim]`` float32, the CLEAN newest frame of every observation (the first ``stacked_dim`` words and the
     non-stacked tail of a fault-free run's ``state_out`` row); ``layout`` (``fault_layout``).  ``active`` ``[K, N]`` bool (default: all):
     observations an env did not take part in (a masked reset's other envs) leave its stack alone and repeat its row.  The twin
     emulates the roll and the fill -- an env's first observation must be a fill (``t_obs = 0``) -- and returns the faulted
-    ``state_out`` rows ``[K, N, state_dim]``, stack rows included."""
+    ``state_out`` rows ``[K, N, state_dim]``, stack rows included.  ``level`` (float32 ``[K, N]``, ``None``: no search): the twin of
+    ``obsfault_search_step_kernel`` -- per observation the level of the episode it belongs to (behind a step that ended a counted
+    trial: the level AFTER the move); an item its row's search item marks uses ``float32(value * level)``."""
     from . import rng
     gid = np.asarray(gid, dtype=np.int64).reshape(-1)
     N, sd, fd, S = len(gid), int(layout["stacked_dim"]), int(layout["frame_dim"]), int(layout["stack_size"])
@@ -1122,7 +1294,8 @@ def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count,
                     continue
                 x = stack[m, 0, e] if e < sd else tail[m, e - sd]
                 draw = lambda index: rng.first_word(seed, gid[m].astype(np.uint64), step_count[k, m].astype(u32), rng.PURPOSE_OBS_FAULT, index)   # noqa: E731
-                x = _fault_op(_OBS_FAULTS.op_names[op], e, ordinal, value, x, stack[m, 1, e] if e < sd and S > 1 else x, t_obs[k, m] == 0, draw)
+                v = _level_value(table, _OBS_FAULTS.key, r, ordinal, value, None if level is None else np.asarray(level, dtype=np.float32).reshape(K, N)[k, m])
+                x = _fault_op(_OBS_FAULTS.op_names[op], e, ordinal, v, x, stack[m, 1, e] if e < sd and S > 1 else x, t_obs[k, m] == 0, draw)
                 if e >= sd:
                     tail[m, e - sd] = x
                 else:
@@ -1136,12 +1309,13 @@ def reference_obs_faults(table: ScenarioTable, mode, gid, t_obs, ep, step_count,
     return out
 
 
-def reference_action_faults(table: ScenarioTable, mode, gid, t, ep, step_count, seed: int, raw, prev_eff) -> np.ndarray:
+def reference_action_faults(table: ScenarioTable, mode, gid, t, ep, step_count, seed: int, raw, prev_eff, level=None) -> np.ndarray:
     """Numpy twin of ONE step of ``actfault_step_kernel`` for N envs, exact.  ``gid`` ``[N]`` global ids; the PRE-STEP meta words ``t``
     (word 0), ``ep`` (word 11) and ``step_count`` (word 1), each ``[N]``; ``raw`` ``[N, nu]`` float32, the caller's actions; ``prev_eff``
     ``[N, nu]`` float32, the record's ``s_lastact``: the effective action of the env's previous step, zeros where that step ended the
     episode (or none was taken).  Returns the effective actions ``[N, nu]``: an actuator under no holding item keeps the caller's
-    bits."""
+    bits.  ``level`` (float32 ``[N]``, ``None``: no search): the twin of ``actfault_search_step_kernel`` -- an item its row's search item
+    marks uses ``float32(value * level)`` of the env, the level its open episode runs at."""
     from . import rng
     gid = np.asarray(gid, dtype=np.int64).reshape(-1)
     N = len(gid)
@@ -1158,7 +1332,8 @@ def reference_action_faults(table: ScenarioTable, mode, gid, t, ep, step_count, 
             if not m.any():
                 continue
             draw = lambda index: rng.first_word(seed, gid[m].astype(np.uint64), step_count[m].astype(u32), rng.PURPOSE_ACTION_FAULT, index)   # noqa: E731
-            eff[m, j] = _fault_op(_ACTION_FAULTS.op_names[op], j, ordinal, value, eff[m, j], prev[m, j], t[m] == 0, draw)
+            v = _level_value(table, _ACTION_FAULTS.key, r, ordinal, value, None if level is None else np.asarray(level, dtype=np.float32).reshape(N)[m])
+            eff[m, j] = _fault_op(_ACTION_FAULTS.op_names[op], j, ordinal, v, eff[m, j], prev[m, j], t[m] == 0, draw)
     return eff
 
 

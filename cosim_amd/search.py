@@ -1,10 +1,12 @@
-"""Limit search: a per-env staircase on a scenario's push and command scale, kept on the device (``cosim_set_param "search"``,
+"""Limit search: a per-env staircase on a scenario's push, command, parameter-window and fault scale, kept on the device (``cosim_set_param "search"``,
 csrc/cosim_search.hip).
 
 "What is the hardest push this checkpoint survives?"  A scenario of a ``ScenarioTable`` may hold one search item
 (``cosim_amd/scenario.py``).  Every env of such a row keeps a LEVEL in ``[lo, hi]`` that the scenario kernel multiplies into the
-row's pushes and / or command keyframes; when an episode of the env ends, a small rule on the device moves the level down after a
-failure and up after a pass -- no host read, no re-planning between runs.  ``SearchResult`` is the per-env records and the trial rings
+row's pushes and / or command keyframes, and the parameter-window and fault kernels into the values of the row's marked items; when an
+episode of the env ends, a small rule on the device moves the level down after a failure and up after a pass (``harder="down"``: the
+other way round) -- no host read, no re-planning between runs.  A failure is a ledger flag of the item's ``fail_on`` or a selected
+check of the ended episode that did not pass.  ``SearchResult`` is the per-env records and the trial rings
 on the host, with the summaries a sweep asks for; ``(env, episode)`` joins a trial to the ledger's record of the same episode.
 ``SearchTwin`` / ``reference_search`` are the numpy twin of the three kernels: the same float32 operations in the same order, so its
 words equal the device's bit for bit.  No torch, no GPU in this module.
@@ -13,22 +15,23 @@ Record words (int32 ``[N, 16]``): 0 level, 1 step, 2 trials, 3 fails, 4 last_dir
 lo_fail, 10 status (1 the open episode began at a reset | 2 done | 4 has a pass | 8 has a fail | 16 the row has an item), 11 episodes
 ended since arming, 12 length of the open episode, 13 meta word 4 at its start, 14 ended episodes that were no trials, 15 zero.
 Trial words (int32 ``[N, slots, 4]``, episode ``o`` in slot ``o mod slots``): episode, the level it RAN at, flags | 256 counted | 512
-failed | 1024 reversal, length.
+failed | 1024 reversal | 2048 failed by a check, length.  With ``harder="down"`` word 8 holds the LOWEST pass and word 9 the HIGHEST failure.
 """
 from __future__ import annotations
 
+import json
 from types import SimpleNamespace
 from typing import Optional, Sequence
 
 import numpy as np
 
 from . import records as rc
-from .scenario import SEARCH_FAIL_ON, SEARCH_RULES, scenario_rows
+from .scenario import SEARCH_RULES, scenario_rows, search_fail_mask
 
 NCNT, TRIAL_WORDS = 16, 4
 LEVEL, STEP, TRIALS, FAILS, LAST_DIR, REVERSALS, REV_SUM, REV_N, HI_PASS, LO_FAIL, STATUS, EPISODE, LENGTH, NAN0, UNCOUNTED = range(15)
 AT_RESET, DONE, HAS_PASS, HAS_FAIL, HAS_ITEM = 1, 2, 4, 8, 16
-COUNTED, FAILED, REVERSAL = 256, 512, 1024
+COUNTED, FAILED, REVERSAL, BY_CHECK = 256, 512, 1024, 2048
 _F32 = np.float32
 
 
@@ -90,12 +93,13 @@ class SearchTwin:
         x, step = _float(s[LEVEL]), _float(s[STEP])
         lo, hi, d_min = _F32(it["lo"]), _F32(it["hi"]), _F32(it["min_step"])
         status, last = int(s[STATUS]), int(s[LAST_DIR])
-        d = -1 if fail else 1
+        down = it["harder"] == "down"
+        d = -1 if fail != down else 1
         if fail:
-            s[LO_FAIL] = _bits(np.fmin(_float(s[LO_FAIL]), x) if status & HAS_FAIL else x)
+            s[LO_FAIL] = _bits((np.fmax if down else np.fmin)(_float(s[LO_FAIL]), x) if status & HAS_FAIL else x)
             status |= HAS_FAIL
         else:
-            s[HI_PASS] = _bits(np.fmax(_float(s[HI_PASS]), x) if status & HAS_PASS else x)
+            s[HI_PASS] = _bits((np.fmin if down else np.fmax)(_float(s[HI_PASS]), x) if status & HAS_PASS else x)
             status |= HAS_PASS
         rev = last != 0 and d != last
         if rev:
@@ -119,12 +123,18 @@ class SearchTwin:
         s[STATUS] = status
         return COUNTED | (FAILED if fail else 0) | (REVERSAL if rev else 0)
 
-    def step(self, terminated, truncated, meta4, meta15=None):
-        """Behind one control step: the done flags it returned and meta words 4 and 15 of every env as it left them."""
+    def step(self, terminated, truncated, meta4, meta15=None, check_fail=None, check_incomplete=None):
+        """Behind one control step: the done flags it returned and meta words 4 and 15 of every env as it left them.  ``check_fail`` /
+        ``check_incomplete`` (uint64 ``[N]``, read only where the step ended an episode): the two masks of the verdict record the
+        checks closed for that episode; needed only where an item fails on a check."""
         N = len(self.rows)
         te_all, tr_all = np.asarray(terminated).reshape(N) != 0, np.asarray(truncated).reshape(N) != 0
         meta4 = np.asarray(meta4, dtype=np.int64).reshape(N)
         meta15 = np.zeros(N, dtype=np.int64) if meta15 is None else np.asarray(meta15, dtype=np.int64).reshape(N)
+        bad = np.zeros(N, dtype=np.uint64)
+        for m in (check_fail, check_incomplete):
+            if m is not None:
+                bad |= np.asarray(m).astype(np.uint64).reshape(N)
         with np.errstate(all="ignore"):
             for i in range(N):
                 s = self.state[i]
@@ -139,8 +149,8 @@ class SearchTwin:
                 it = self.table.search[int(self.rows[i])]
                 extra = 0
                 if it is not None and not status & DONE and status & AT_RESET:
-                    fail_mask = sum(SEARCH_FAIL_ON[n] for n in it["fail_on"])
-                    extra = self._trial(s, it, (flags & fail_mask) != 0)
+                    by_check = (int(bad[i]) & it["check_mask"]) != 0
+                    extra = self._trial(s, it, (flags & search_fail_mask(it)) != 0 or by_check) | (BY_CHECK if by_check else 0)
                     if int(s[STATUS]) & DONE:
                         self.remaining -= 1
                 else:
@@ -151,7 +161,8 @@ class SearchTwin:
 
 
 def reference_search(table, slots: int, rows, events: Sequence, fall: bool = False, flag: int = 0, meta4=None):
-    """``SearchTwin`` run over ``events``: ``("step", terminated [N], truncated [N], meta4 [N], meta15 [N] or None)`` for a control step,
+    """``SearchTwin`` run over ``events``: ``("step", terminated [N], truncated [N], meta4 [N], meta15 [N] or None[, check_fail [N],
+    check_incomplete [N]])`` for a control step,
     ``("begin", mask or None, flag, meta4 [N])`` for a reset (flag 0) or a restore / set_state (8) ahead of the next one.  Returns
     ``(state int32 [N, 16], ring int32 [N, slots, 4], remaining)``."""
     twin = SearchTwin(table, slots, rows, fall, flag, meta4)
@@ -172,9 +183,12 @@ class SearchResult:
     (``rev_sum / rev_n`` where ``rev_n > 0``, else the middle of the bracket where both ends exist, else NaN), ``episodes`` (ended since
     arming), ``uncounted``.  Per trial ``[R]``, sorted by (env, episode): ``trial_env``, ``episode``, ``trial_level`` (the level the
     episode ran at), ``flags``, ``counted``, ``failed``, ``reversal``, ``length``.  ``lost`` int64 ``[N]``: trials the ring overwrote.
-    Without the rings (``include_trials=False``) there are no trial rows and ``lost`` is zero."""
+    Without the rings (``include_trials=False``) there are no trial rows and ``lost`` is zero.  ``harder`` int ``[N]``: 0 where a
+    higher level is harder (the default), 1 where a lower one is (the item's ``harder="down"``): there ``bracket`` is (the LOWEST pass,
+    the HIGHEST failure) -- column 0 is the pass end and column 1 the failure end for both signs, and the threshold lies between
+    them.  ``items``: per scenario row with an item, ``{"harder", "targets", "fail_on"}`` as the table states them (empty if unknown)."""
 
-    def __init__(self, state, scenario, trial_words, trial_env, lost, slots: int = 0, env_id0: int = 0):
+    def __init__(self, state, scenario, trial_words, trial_env, lost, slots: int = 0, env_id0: int = 0, harder=None, items: dict = None):
         self.state = np.ascontiguousarray(state, dtype=np.int32).reshape(-1, NCNT)
         N = len(self.state)
         self.scenario = np.ascontiguousarray(scenario, dtype=np.int64).reshape(N)
@@ -182,6 +196,8 @@ class SearchResult:
         self.trial_env = np.ascontiguousarray(trial_env, dtype=np.int64).reshape(-1)
         self.lost = np.ascontiguousarray(lost, dtype=np.int64).reshape(N)
         self.slots, self.env_id0 = int(slots), int(env_id0)
+        self.harder = np.zeros(N, dtype=np.int64) if harder is None else np.ascontiguousarray(harder, dtype=np.int64).reshape(N)
+        self.items = {int(r): dict(v) for r, v in (items or {}).items()}
         if len(self.trial_env) != len(self.trial_words):
             raise ValueError(f"SearchResult: {len(self.trial_words)} trial records but {len(self.trial_env)} env ids")
         s = self.state
@@ -210,14 +226,22 @@ class SearchResult:
         return len(self.trial_words)
 
     @classmethod
-    def from_raw(cls, state, ring, scenario, env_id0: int = 0) -> "SearchResult":
+    def from_raw(cls, state, ring, scenario, env_id0: int = 0, table=None) -> "SearchResult":
         """From what ``cosim_get "search_state"`` / ``"search_trials"`` copy: records ``[N, 16]``, rings ``[N, slots, 4]`` or ``None``;
-        ``scenario`` ``[N]``: the table row of every env."""
+        ``scenario`` ``[N]``: the table row of every env; ``table``: the ``ScenarioTable`` whose items ran (``harder`` and ``items``
+        come from it; without it every row reads as ``harder="up"``)."""
         state = np.asarray(state, dtype=np.int32).reshape(-1, NCNT)
+        scenario = np.asarray(scenario, dtype=np.int64).reshape(len(state))
+        harder, items = None, None
+        if table is not None:
+            items = {r: {"harder": it["harder"], "targets": list(it["targets"]), "fail_on": list(it["fail_on"])}
+                     for r, it in enumerate(table.search) if it is not None}
+            harder = np.array([int(r in items and items[r]["harder"] == "down") for r in scenario], dtype=np.int64)
         if ring is None:
-            return cls(state, scenario, np.zeros((0, TRIAL_WORDS), np.int32), np.zeros(0, np.int64), np.zeros(len(state), np.int64), 0, env_id0)
+            return cls(state, scenario, np.zeros((0, TRIAL_WORDS), np.int32), np.zeros(0, np.int64), np.zeros(len(state), np.int64), 0, env_id0,
+                       harder, items)
         words, env, lost = rc.unroll_rings(ring, state[:, EPISODE])
-        return cls(state, scenario, words, env + int(env_id0), lost, np.shape(ring)[1], env_id0)
+        return cls(state, scenario, words, env + int(env_id0), lost, np.shape(ring)[1], env_id0, harder, items)
 
     def ended(self) -> np.ndarray:
         """Mask of the trial rows that are ended episodes: all of them (the rings hold no open episode)."""
@@ -248,8 +272,9 @@ class SearchResult:
         return {**self.counts(), **self._cell(self.has_item)}
 
     def by_scenario(self) -> dict:
-        """Per scenario row with an item: threshold quantiles over its envs, done share, fail share."""
-        return {int(r): self._cell(self.has_item & (self.scenario == r)) for r in np.unique(self.scenario[self.has_item])}
+        """Per scenario row with an item: threshold quantiles over its envs, done share, fail share, and the row's ``harder``,
+        ``targets`` and ``fail_on`` where the table is known."""
+        return {int(r): {**self._cell(self.has_item & (self.scenario == r)), **self.items.get(int(r), {})} for r in np.unique(self.scenario[self.has_item])}
 
     def by_policy(self, table) -> dict:
         """``by_scenario`` cells per policy of a static ``policy.PolicyTable`` (or of an int array with the policy of each local env),
@@ -262,7 +287,8 @@ class SearchResult:
     def survival(self, bins) -> dict:
         """The empirical psychometric curve: per scenario row, the pass share of its counted trials per level bin.  ``bins``: the bin
         edges (ascending, as ``numpy.histogram`` takes them) or a bin count over each row's observed level range.  Returns ``{row:
-        {"edges", "trials", "passed", "pass_share" (NaN for an empty bin)}}``."""
+        {"edges", "trials", "passed", "pass_share" (NaN for an empty bin), "harder"}}``: with ``harder`` ``"up"`` the share falls as the
+        level rises, with ``"down"`` it rises."""
         out = {}
         loc = self.trial_env - self.env_id0
         row_of = self.scenario[loc] if len(loc) else np.zeros(0, dtype=np.int64)
@@ -274,7 +300,8 @@ class SearchResult:
             p, _ = np.histogram(lv[~self.failed[m]], bins=edges)
             with np.errstate(all="ignore"):
                 share = np.where(n > 0, p / np.maximum(n, 1), np.nan)
-            out[int(r)] = {"edges": edges, "trials": n, "passed": p, "pass_share": share}
+            down = bool(self.harder[self.scenario == r].any())
+            out[int(r)] = {"edges": edges, "trials": n, "passed": p, "pass_share": share, "harder": "down" if down else "up"}
         return out
 
     def join(self, ledger) -> np.ndarray:
@@ -293,17 +320,20 @@ class SearchResult:
             raise ValueError("SearchResult.merge: the env ranges are not adjacent (a result holds one contiguous range of global ids)")
         return SearchResult(np.concatenate([lo.state, hi.state]), np.concatenate([lo.scenario, hi.scenario]),
                             np.concatenate([lo.trial_words, hi.trial_words]), np.concatenate([lo.trial_env, hi.trial_env]),
-                            np.concatenate([lo.lost, hi.lost]), max(lo.slots, hi.slots), lo.env_id0)
+                            np.concatenate([lo.lost, hi.lost]), max(lo.slots, hi.slots), lo.env_id0, np.concatenate([lo.harder, hi.harder]),
+                            {**lo.items, **hi.items})
 
     def save(self, path: str):
         """One ``.npz`` of plain arrays (no pickle)."""
         np.savez(path, state=self.state, scenario=self.scenario, trial_words=self.trial_words, trial_env=self.trial_env, lost=self.lost,
-                 header=rc.header(self.slots, self.env_id0))
+                 header=rc.header(self.slots, self.env_id0), harder=self.harder, items=np.array(json.dumps({str(r): v for r, v in self.items.items()})))
 
     @classmethod
     def load(cls, path: str) -> "SearchResult":
         with np.load(path, allow_pickle=False) as z:
-            return cls(z["state"], z["scenario"], z["trial_words"], z["trial_env"], z["lost"], *rc.read_header(z))
+            harder = z["harder"] if "harder" in z.files else None
+            items = {int(r): v for r, v in json.loads(str(z["items"])).items()} if "items" in z.files else None
+            return cls(z["state"], z["scenario"], z["trial_words"], z["trial_env"], z["lost"], *rc.read_header(z), harder, items)
 
 
 def same_search(a: SearchResult, b: SearchResult) -> Optional[str]:

@@ -470,11 +470,15 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  * device by the outcome of the env's own episodes (cosim_amd/csrc/cosim_search.h has the rule).  Like the faults it has no entry point
  * of its own: the table travels through cosim_set_param(e, "search", words, count), `words` pointing at `count` 32-BIT WORDS:
  *   S | slots | has[S] | lo[S] | hi[S] | x0[S] | d0[S] | d_min[S] | rule[S] | trials[S] | targets[S] | fail_mask[S] | rev_skip[S]
- * (int32 but for lo .. d_min, float bits; count = 2 + 11 S); the one word 0 clears the search.  A scenario carries at most one item
+ * (int32 but for lo .. d_min, float bits; count = 2 + 11 S), or with three more columns harder[S] | chk_lo[S] | chk_hi[S] behind them
+ * (count = 2 + 14 S; the short form reads as harder 0, no check); the one word 0 clears the search.  A scenario carries at most one item
  * (has[s] = 1): lo < hi finite bounds of the LEVEL, lo <= x0 <= hi its start, 0 < d_min <= d0 the start and the smallest step, rule 0
- * bisect | 1 staircase, trials 1 .. 2^20 the budget of counted episodes, targets 1 push vectors | 2 command keyframes, fail_mask a
- * non-empty set of the ledger's flags 1 terminated | 4 non-finite | 32 tilt | 64 height | 128 contact, rev_skip 0 .. 255 reversals left
- * out of the running mean.  slots (1..64): trial records kept per env.
+ * bisect | 1 staircase, trials 1 .. 2^20 the budget of counted episodes, targets 1 push vectors | 2 command keyframes | the MARKED items
+ * of the row's 4 parameter windows | 8 observation faults | 16 action faults (the scenario must hold items of that kind), fail_mask a set of the
+ * ledger's flags 1 terminated | 4 non-finite | 32 tilt | 64 height | 128 contact (empty only where a check is selected), rev_skip
+ * 0 .. 255 reversals left out of the running mean; harder 0 up (a higher level is harder) | 1 down; chk_lo / chk_hi the 64-bit mask of
+ * the row's check items (cosim_scenario_checks_set, bit i = item i) that are failure criteria: the checks must be armed, with that
+ * many items in the row.  slots (1..64): trial records kept per env.
  * Per env SRCH_NCNT = 16 int32 words (all floats fp32, no contraction): 0 level  1 step  2 trials  3 fails  4 last_dir (0 / +1 / -1)
  * 5 reversals  6 rev_sum  7 rev_n  8 hi_pass  9 lo_fail  10 status (1 the open episode began at a reset | 2 done | 4 has a pass | 8 has a
  * fail | 16 the env's row has an item)  11 episodes ended since arming (the ledger's ordinal)  12 length of the open episode  13 meta
@@ -486,8 +490,11 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  * stream: it counts the open episode's length and, on a row with terminated | truncated, builds the ledger's flags (1 | 2 | 4 if meta
  * word 4 moved | 8 if status bit 1 is clear | (meta word 15 & 7) << 5 while a fall rule is set).  The episode is a COUNTED TRIAL iff the
  * row has an item, the env is not done and status bit 1 is set (an episode that began at cosim_restore / cosim_set may have missed its
- * push window); then, with x = level, fail = (flags & fail_mask) != 0, dir = fail ? -1 : +1:
+ * push window); then, with x = level, fail = (flags & fail_mask) != 0 || a selected check is NOT PASSED ((fail mask | incomplete mask)
+ * & the item's check mask != 0, the two masks being words 4..7 of the verdict record checks_step_kernel closed behind this same step;
+ * its own episode counter names the slot), dir = fail ? -1 : +1, with harder 1 dir = fail ? +1 : -1:
  *   fail ? lo_fail = has_fail ? fminf(lo_fail, x) : x  :  hi_pass = has_pass ? fmaxf(hi_pass, x) : x
+ *   (harder 1: fmaxf for lo_fail, fminf for hi_pass -- the two words then hold the HIGHEST failure and the LOWEST pass)
  *   rev = last_dir != 0 && dir != last_dir;  if (rev) { reversals++; if (reversals > rev_skip) { rev_sum += x; rev_n++; } }
  *   staircase: if (rev) step = fmaxf(step * 0.5f, d_min);  x' = x + dir * step
  *   bisect:    x' = x + dir * step;  step = fmaxf(step * 0.5f, d_min)
@@ -495,9 +502,25 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  *   engine's one "remaining" word (the only atomic)
  * An episode that is not counted adds 1 to word 14.  Either way episode++, length = 0, word 13 is refreshed, status bit 1 is set (the
  * auto-reset began the next episode) and one trial record {episode, the level the episode RAN at, flags | 256 counted | 512 fail | 1024
- * reversal, length} goes into slot episode mod slots of the env's ring.  Behind cosim_reset / cosim_restore / cosim_set the masked envs'
+ * reversal | 2048 failed by a check, length} goes into slot episode mod slots of the env's ring.  Behind cosim_reset / cosim_restore / cosim_set the masked envs'
  * status bit 1 becomes (flag == 0), length 0 and word 13 is refreshed: the open episode is discarded as the ledger discards it, the
  * level does not move.  No LDS, no cross-lane traffic, no host read, no join: a captured step carries the launches.
+ * While an armed item fails on a check search_step_checks_kernel runs IN THE PLACE OF search_step_kernel (the same rule, handed the
+ * checks' counters and rings); cosim_scenario_checks_set then refuses to clear the checks or to lay them out anew, and an in-place
+ * rewrite of them also begins the search's open episodes anew (not at a reset: no trial).  While an armed item's targets hold 4 / 8 /
+ * 16, scnparams_search_step_kernel / obsfault_search_step_kernel / actfault_search_step_kernel runs IN THE PLACE OF the plain kernel
+ * of that kind: a MARKED item -- a parameter item whose op carries bit 8 (0x100), a fault item whose elem carries bit 15 (0x8000;
+ * elements are below 256) -- uses v = value * level (one fp32 multiply, first) for value: a window's scale is base * v and its set is
+ * v, a fault's drop compares its draw against v; unmarked items take the unscaled expressions.  Parameter windows and action faults
+ * run ahead of the step and read the level the open episode runs at.  An observation fault is scaled by the level of the episode
+ * its observation belongs to: while a search whose targets hold 8 is armed the observation-fault launch of a step is issued BEHIND
+ * search_step_kernel (no observer reads the stack row or state_out it writes; the history pack stays behind it), so the observation
+ * returned by the step that ended an episode carries the level after the move; the reset site is unchanged.  The setters
+ * (cosim_scenario_params_set, cosim_set_param "obs_faults" / "action_faults") accept a marked item only while a search whose targets
+ * hold the kind's word is armed on the item's scenario, never on a hold, and hold it to the value rules at both fp32(value * lo) and
+ * fp32(value * hi); while marked items are set, cosim_set_param "search" refuses to replace or clear the search and
+ * cosim_scenario_set to switch to mode cycle.  With no such target and no check selected the engine launches exactly the kernels,
+ * in the order, it launches without them.
  * Validated on the host before anything is changed, the message naming the scenario (COSIM_EINVAL): S must be the "scenario_rows" of
  * the table that is set; the scenario mode must be env (the state is one record per env); the engine needs auto_reset; a target must
  * have rows to scale (pushes / keyframes of that scenario); the ranges of every field above.  A fall bit in fail_mask while no fall
@@ -506,11 +529,12 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  * bounds up; anything else allocates anew and begins every env at x0 / d0 with an empty ring (search_init_kernel).  cosim_scenario_set
  * with another S or with mode cycle, or clearing the table, drops the search.  A step without info_out_dev is not refused for the
  * search alone (it reads no info row).  cosim_rollout stays refused (a scenario table is set); cosim_profile_step and
- * cosim_debug_forward ignore the search.  cosim_query answers "search" (items armed, 0: none), "search_slots" and "search_remaining"
+ * cosim_debug_forward ignore the search.  cosim_query answers "search" (items armed, 0: none), "search_slots", "search_targets" (the
+ * union of the armed items' targets), "search_checks" (an armed item fails on a check), "scenario_param_items_marked", "obs_faults_marked",
+ * "action_faults_marked" and "search_remaining"
  * (envs with an item and trials left: joins the ranges and reads the one word); cosim_get "search_state" copies int32 [N][16],
- * "search_trials" int32 [N][slots][4] to device memory (COSIM_EINVAL while no search is armed).  Out of scope: a level that scales
- * parameter windows or fault values (the level is a plain per-env word so that those kernels can read it later), a check verdict as
- * the failure criterion, mode cycle, the search state in a snapshot, anything inside cosim_rollout. */
+ * "search_trials" int32 [N][slots][4] to device memory (COSIM_EINVAL while no search is armed).  Out of scope: scaled window times, gains other than
+ * the plain multiply, marks on a hold, mode cycle, the search state in a snapshot, anything inside cosim_rollout. */
 
 /* Checks of the scenario table that is set: per-scenario pass / fail criteria judged on the device (cosim_amd/csrc/cosim_checks.h has
  * the rule).  Scenario s owns the items [adr[s], adr[s + 1]) (at most 64).  Item i takes one sample per control step whose PRE-STEP
