@@ -362,6 +362,9 @@ class BatchedEnv:
         Returns ``(states [K, N, state_dim], terminated [K, N], truncated [K, N], info_buf [K, N, info_dim] or None)``: row k is what
         ``step(actions[k])`` would have returned (auto-reset included).  ``self.state`` etc. keep the last row."""
         assert self.reset_flag is True, "Call 'reset()' before calling 'step()'."
+        if self.scenario_table is not None and self.scenario_table.has_latency:
+            raise ValueError("rollout(): latency is set and the delay lines are written between steps, which one rollout launch does not leave; "
+                             "step() or set a table without 'latency'")
         if self.scenario_table is not None:
             raise ValueError("rollout(): a scenario table is set and one rollout launch reads one command row; step() or set_scenarios(None)")
         if self.failure_traces_cfg is not None:
@@ -684,6 +687,12 @@ class BatchedEnv:
         last step's kernels were handed.  They act from the next ``step()`` on.  Limits: set before capturing a graph; not part of a
         ``snapshot()`` (nothing is kept per env: the same table set again continues bit for bit).
 
+        Latency rides with the table too (a scenario's ``"latency"``, ``cosim_set_param "latency"``): k-step delays of the command
+        channel and of observation elements, served by per-env delay lines on the device ahead of the fault kernels at the same two
+        sites; ``latency()`` returns the expanded items.  A table with the same items per scenario whose delays fit the lines' depth
+        is rewritten in place and keeps the lines; any other restarts them.  Limits: set before capturing a graph; the lines are not
+        part of a ``snapshot()``: ``restore`` / ``fork`` / ``set_state`` restart the lines of the envs they touch.
+
         ``check_slots`` (1..64) arms the table's checks (``cosim_scenario_checks_set``): behind every control step the engine samples
         every item of the env's scenario whose window holds at the step's pre-step episode clock -- the clock this step's keyframes
         and pushes were keyed on -- and closes the items into one verdict record when the episode ends, on the device, with no host
@@ -736,6 +745,8 @@ class BatchedEnv:
             table.resolve_faults(self.fault_names())
         if table.has_action_faults:                                 # actuator names, "*" and ranges against this env's model
             table.resolve_action_faults(self.actuator_names())
+        if table.has_latency:                                       # channels, names and "*" against this env's observation config and model
+            table.resolve_latency(self.fault_names(), self.actuator_names())
         check_slots = int(check_slots or 0)
         if check_slots and table.has_checks:                        # names and ranges against this env's model
             table.resolve_checks(self.check_names())
@@ -779,6 +790,15 @@ class BatchedEnv:
                     getattr(self.engine, kind.setter)(table._pack_fault_items(kind))
                 elif self.engine.query(kind.param) > 0:
                     getattr(self.engine, kind.setter)(None)
+            if table.has_latency:                                       # and the latency lines
+                try:
+                    self.engine.latency_set(table.pack_latency())
+                except Exception:                                       # refused (the lines' size cap): the engine has none, and neither has the env's table
+                    if self.engine.query("latency") == 0:
+                        table.latency_rows, table.latency = [[] for _ in table.latency_rows], [[] for _ in table.latency_rows]
+                    raise
+            elif self.engine.query("latency") > 0:
+                self.engine.latency_set(None)
             # so do the checks, once they are armed
             self.check_slots = 0
             if check_slots and table.has_checks:
@@ -1003,10 +1023,22 @@ class BatchedEnv:
         ``cosim_query "action_faults"`` counts them."""
         return self._fault_items(FAULT_KINDS[1])
 
+    def latency(self) -> list:
+        """The expanded latency items of the scenario table that is set, per scenario: ``(t0, t1, channel kind (0 action, 1
+        observation), element, ordinal of the listed item, steps, jitter)`` (``ScenarioTable.latency``); an empty list per scenario
+        without any, ``[]`` with no table.  ``cosim_query "latency"`` counts them, ``"latency_depth"`` is the depth of the lines."""
+        if self.scenario_table is None:
+            return []
+        items = [list(f) for f in self.scenario_table.latency or [[] for _ in range(len(self.scenario_table))]]
+        if sum(len(f) for f in items) != self.engine.query("latency"):
+            raise RuntimeError(f"latency(): the table holds {sum(len(f) for f in items)} items and the engine {self.engine.query('latency')}: "
+                               "the latency was set or cleared behind the env (Engine.latency_set); call set_scenarios again")
+        return items
+
     def effective_action(self):
-        """What the last ``step()``'s kernels were handed as the action while action faults are set: a float32 tensor ``[N, nu]`` (a
-        copy; zeros before the first step), ``None`` when no action faults are set.  Joins the ranges."""
-        if self.engine.query("action_faults") == 0:
+        """What the last ``step()``'s kernels were handed as the action while action faults or a latency of the command channel are
+        set: a float32 tensor ``[N, nu]`` (a copy; zeros before the first step), ``None`` when neither is set.  Joins the ranges."""
+        if self.engine.query("action_faults") == 0 and self.engine.query("latency_action_items") == 0:
             return None
         out = self.torch.empty((self.num_envs, self.action_dim), dtype=self.torch.float32, device=self.device)
         self.engine.get("action_effective", out.data_ptr(), self._stream())

@@ -39,7 +39,8 @@ the push every loop iteration while ``_push_event`` is set) as a schedule:
                                                                        # (cosim_amd/scenario.py; or a YAML file: --scenarios); unlike
                                                                        # commands: / pushes: they run under --graph and --pipelined too;
                                                                        # a scenario may also hold params:, faults:, action_faults:
-                                                                       # ([[t0, t1, index, op, value], ...]: what the motors are told), ...
+                                                                       # ([[t0, t1, index, op, value], ...]: what the motors are told),
+                                                                       # latency: ([[t0, t1, channel, index, steps, jitter], ...]: k-step delays), ...
     fall:     {tilt: 0.8, height: 0.1, grace: 5, bodies: [base_link]}  # fall rule (cosim_amd/fall.py): end an episode on tilt (rad), base
                                                                        # height (m) or contact of the listed bodies; or engine: {fall: {...}};
                                                                        # same as --fall-*; runs under --graph and --pipelined too
@@ -489,6 +490,8 @@ def main(argv=None) -> int:
                              if env.scenario_table is not None and env.scenario_table.has_params else {}),
                           **({kind.param: sum(len(f) for f in getattr(env.scenario_table, kind.key))     # expanded items, as the engine counts them
                               for kind in FAULT_KINDS if env.scenario_table is not None and any(getattr(env.scenario_table, kind.rows))}),
+                          **({"latency": env.scenario_table.n_latency_items}                             # likewise
+                             if env.scenario_table is not None and env.scenario_table.has_latency else {}),
                           **({"percentiles": {k: {q: round(x, 5) for q, x in v.items()} for k, v in out["percentiles"].items()}}
                              if "percentiles" in out else {})}))
     env.close()

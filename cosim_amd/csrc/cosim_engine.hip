@@ -8,6 +8,7 @@
 #include <time.h>
 #include <string.h>
 
+#include <atomic>
 #include <string>
 #include <vector>
 
@@ -24,6 +25,7 @@
 #include "cosim_checks.hip"
 #include "cosim_curves.hip"
 #include "cosim_search.hip"
+#include "cosim_latency.hip"
 #include "cosim_plan.h"
 #include "cosim_ranges.h"
 #include "cosim_tables.h"
@@ -158,6 +160,15 @@ struct cosim_engine {
   float* d_actions_eff = nullptr; // [n_envs][nu] effective actions: what the step kernels are handed while faults are set
   float* d_actions_raw = nullptr; // [n_envs][nu] the caller's actions of the last step (last_action is rebuilt from them)
   bool act_in_obs = false;        // the observation has last_action elements
+  // latency lines of the scenario table (cosim_set_param "latency", cosim_latency.hip): latency_act_kernel ahead of actfault_step_kernel,
+  // latency_obs_kernel ahead of obsfault_step_kernel; while action items are set they share d_actions_eff / d_actions_raw with the action faults
+  char* d_lat = nullptr;          // one allocation: act_adr | obs_adr | act_item | obs_item
+  LatTable lat = {};              // device pointers into d_lat; n_act + n_obs 0: no latency, no launches
+  float* d_lat_act_line = nullptr;   // [n_envs][depth][nu], with action items
+  float* d_lat_obs_line = nullptr;   // [n_envs][depth][frame_dim], with observation items
+  int* d_lat_from = nullptr;      // [2][n_envs]: the clock each env's action / observation line is valid from (< 0: invalid)
+  float* d_lat_eff = nullptr;     // [n_envs][nu] the delivered actions while action faults are set too: what actfault_step_kernel reads
+  float* d_lat_spare = nullptr;   // [n_envs][nu] where actfault_step_kernel's copy of them goes then
   float* d_params_eff = nullptr;  // [n_envs][p_stride] effective records: what base_args hands the step kernels while windows are set
   // checks of the scenario table (cosim_scenario_checks_set, cosim_checks.hip): checks_step_kernel behind every range's last launch of a
   // step, behind the ledger's
@@ -209,14 +220,20 @@ struct cosim_engine {
 
 // One launcher for every kernel: n envs (narrowphase: envs x waves per env) at ENVS_PER_BLOCK envs per one-wave block -- 1, 2 (two envs
 // per wave) or 64 (the fix-up kernels: a wave scans the flags of 64 envs)
+// kernel launches issued through the two launchers below by every engine of the process (cosim_query "launches"): what a test
+// compares between two runs to hold that a table which is not set launches nothing
+static std::atomic<unsigned> g_launches{0u};
+
 template <auto KERNEL, int ENVS_PER_BLOCK = 1>
 static void launch_k(cosim_engine*, const KArgs& a, int n, hipStream_t s) {
+  g_launches.fetch_add(1u, std::memory_order_relaxed);
   hipLaunchKernelGGL(KERNEL, dim3((n + ENVS_PER_BLOCK - 1) / ENVS_PER_BLOCK), dim3(64), 0, s, a);
 }
 // ... and one for the small kernels beside them (ledger, traces, scenario family, snapshots): `count` envs (rows, cell blocks) at
 // PER_BLOCK of them per block of THREADS threads
 template <int PER_BLOCK, int THREADS, class K, class A>
 static int launch_small(K kernel, const A& a, int count, hipStream_t s) {
+  g_launches.fetch_add(1u, std::memory_order_relaxed);
   hipLaunchKernelGGL(kernel, dim3((count + PER_BLOCK - 1) / PER_BLOCK), dim3(THREADS), 0, s, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
@@ -770,19 +787,28 @@ static int obsfault_launch(cosim_engine* e, int first, int count, float* state_o
   return launch_small<FLT_WAVES, 64 * FLT_WAVES>(obsfault_step_kernel, a, count, s);
 }
 
+// the two action buffers go when neither the action faults nor the latency's action items need them
+static void action_buffers_release(cosim_engine* e) {
+  if (e->actflt.n_items > 0 || e->lat.n_act > 0) return;
+  (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw);
+  e->d_actions_eff = nullptr; e->d_actions_raw = nullptr;
+}
+
 // the action faults go with their table too (the caller has waited for the device)
 static void actfault_free(cosim_engine* e) {
-  (void)hipFree(e->d_actflt); (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw);
-  e->d_actflt = nullptr; e->d_actions_eff = nullptr; e->d_actions_raw = nullptr; memset(&e->actflt, 0, sizeof e->actflt);
+  (void)hipFree(e->d_actflt);
+  e->d_actflt = nullptr; memset(&e->actflt, 0, sizeof e->actflt);
   e->actflt_marked = 0;
+  action_buffers_release(e);
 }
 
 // ahead of the first launch of a control step of envs [first, first + count), same stream, behind the scenario and parameter-window
 // kernels: the effective and the raw action rows of those envs
-static int actfault_launch(cosim_engine* e, int first, int count, const float* actions, hipStream_t s) {
+// (`raw`: where the kernel's copy of `actions` goes: d_actions_raw, or a spare while the latency kernel has written that buffer)
+static int actfault_launch(cosim_engine* e, int first, int count, const float* actions, float* raw, hipStream_t s) {
   ActFaultArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->scn; a.flt = e->actflt; a.state = e->d_state; a.actions = actions; a.eff = e->d_actions_eff; a.raw = e->d_actions_raw;
+  a.tab = e->scn; a.flt = e->actflt; a.state = e->d_state; a.actions = actions; a.eff = e->d_actions_eff; a.raw = raw;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_lastact = e->lay.s_lastact; a.nu = e->model.nu;
   a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
@@ -803,6 +829,55 @@ static int actfault_obs_launch(cosim_engine* e, int first, int count, float* sta
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_cache = e->lay.s_cache; a.s_stack = e->lay.s_stack; a.nu = e->model.nu;
   return launch_small<FLT_WAVES, 64 * FLT_WAVES>(actfault_obs_kernel, a, count, s);
+}
+
+// ---- latency lines of the scenario table (cosim_latency.hip)
+// the latency goes with its table (the caller has waited for the device)
+static void latency_drop(cosim_engine* e) {   // what the latency alone owns
+  (void)hipFree(e->d_lat); (void)hipFree(e->d_lat_act_line); (void)hipFree(e->d_lat_obs_line); (void)hipFree(e->d_lat_from);
+  (void)hipFree(e->d_lat_eff); (void)hipFree(e->d_lat_spare);
+  e->d_lat = nullptr; e->d_lat_act_line = nullptr; e->d_lat_obs_line = nullptr; e->d_lat_from = nullptr; e->d_lat_eff = nullptr; e->d_lat_spare = nullptr;
+  memset(&e->lat, 0, sizeof e->lat);
+}
+static void latency_free(cosim_engine* e) {
+  latency_drop(e);
+  action_buffers_release(e);
+}
+
+// ahead of actfault_launch and of the first launch of a control step of envs [first, first + count), same stream: the delivered and
+// the raw action rows of those envs.  With action faults set too the delivered rows go to d_lat_eff, which the fault kernel then reads.
+static int latency_act_launch(cosim_engine* e, int first, int count, const float* actions, hipStream_t s) {
+  LatActArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->scn; a.lat = e->lat; a.state = e->d_state; a.actions = actions;
+  a.eff = e->actflt.n_items > 0 ? e->d_lat_eff : e->d_actions_eff; a.raw = e->d_actions_raw;
+  a.line = e->d_lat_act_line; a.from = e->d_lat_from;
+  a.n_envs = e->n_envs; a.first = first; a.count = count;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.nu = e->model.nu;
+  a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
+  return launch_small<FLT_WAVES, 64 * FLT_WAVES>(latency_act_kernel, a, count, s);
+}
+
+// behind the last launch of a step (reset: of the reset, for the envs under its mask) that writes the state record or state_out of
+// those envs and behind actfault_obs_kernel, ahead of obsfault_launch, same stream
+static int latency_obs_launch(cosim_engine* e, int first, int count, float* state_out, const uint8_t* mask, hipStream_t s) {
+  LatObsArgs a;
+  memset(&a, 0, sizeof a);
+  a.tab = e->scn; a.lat = e->lat; a.state = e->d_state; a.state_out = state_out; a.mask = mask;
+  a.line = e->d_lat_obs_line; a.from = e->d_lat_from + e->n_envs;
+  a.n_envs = e->n_envs; a.first = first; a.count = count;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_stack = e->lay.s_stack;
+  a.sd = e->ho.stacked_dim; a.S = e->ho.stack_size; a.frame_dim = e->ho.frame_dim; a.state_dim = e->ho.state_dim;
+  a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
+  return launch_small<FLT_WAVES, 64 * FLT_WAVES>(latency_obs_kernel, a, count, s);
+}
+
+// behind a set / restore on the same stream: the lines of the masked envs (null: all; with a restore's source index: those it did
+// not refuse) are invalid; each restarts at the clock its kernel finds next.  (A reset needs none: both kernels restart a line at clock 0.)
+static int latency_cut(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, hipStream_t s) {
+  if (e->lat.n_act + e->lat.n_obs == 0) return COSIM_OK;
+  const LatCutArgs a = {e->d_lat_from, e->d_lat_from + e->n_envs, mask, src, n_rows, e->n_envs};
+  return launch_small<64, 64>(latency_cut_kernel, a, e->n_envs, s);
 }
 
 // ---- checks of the scenario table (cosim_checks.hip)
@@ -939,6 +1014,7 @@ static void scenario_free(cosim_engine* e) {
   scnparams_free(e);
   obsfault_free(e);
   actfault_free(e);
+  latency_free(e);
   checks_free(e);
   curves_free(e);
   (void)hipFree(e->d_scn);
@@ -999,6 +1075,7 @@ static_assert(LEDGER_NO_RESET == FT_NO_RESET && FT_NO_RESET == CHK_NO_RESET && C
 // behind a reset / set / restore on the same stream: the masked envs (null: all; with a restore's source index: those it did not
 // refuse) begin an episode; flag 0 or LEDGER_NO_RESET.  Behind the reset because meta[14] is the new episode's spawn row
 static int observers_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
+  if (flag == LEDGER_NO_RESET) RC_TRY(latency_cut(e, mask, src, n_rows, s));   // a host cut that is no reset: the latency lines of those envs restart
   RC_TRY(ledger_begin(e, mask, src, n_rows, flag, s));
   RC_TRY(ftrace_begin(e, mask, src, n_rows, flag, s));
   RC_TRY(checks_begin(e, mask, src, n_rows, flag, s));
@@ -1636,6 +1713,11 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
   if (n == "scenario_param_items") return e->scnpar.n_items;   // expanded parameter-window items of the table (0: none, no launches)
   if (n == "obs_faults") return e->obsflt.n_items;   // expanded observation-fault items of the table (0: none, no launches)
+  if (n == "launches") return (int)(g_launches.load(std::memory_order_relaxed) & 0x7fffffffu);   // kernel launches the engines of this process have issued through launch_k / launch_small, modulo 2^31 (a capture counts what it records, a replay nothing)
+  if (n == "latency") return e->lat.n_act + e->lat.n_obs;   // expanded latency items of the table, both kinds (0: none, no launches, no pointer changes)
+  if (n == "latency_action_items") return e->lat.n_act;     // ... of the command channel
+  if (n == "latency_obs_items") return e->lat.n_obs;        // ... of observation elements
+  if (n == "latency_depth") return e->lat.depth;            // D: clocks a line holds (0: none)
   if (n == "action_faults") return e->actflt.n_items;   // expanded action-fault items of the table (0: none, no launches, the caller's action pointer)
   if (n == "scenario_check_items") return e->chk.n_scn > 0 ? e->chk.I : 0;   // I: items per env a verdict record holds (0: no checks, no launches)
   if (n == "scenario_check_slots") return e->chk_slots;                      // verdict records per env
@@ -1661,6 +1743,7 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
 static int obsfault_set(cosim_engine* e, const int32_t* words, int count);   // (below, with the other tables of the scenario family)
 static int actfault_set(cosim_engine* e, const int32_t* words, int count);
 static int search_set(cosim_engine* e, const int32_t* words, int count);
+static int latency_set(cosim_engine* e, const int32_t* words, int count);
 
 int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int count) {
   if (!e || !name || !host) return fail(COSIM_EINVAL, "cosim_set_param: null argument");
@@ -1679,6 +1762,7 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
   else if (n == "obs_faults") return obsfault_set(e, reinterpret_cast<const int32_t*>(host), count);   // a table of 32-bit words, not floats (include/cosim.h)
   else if (n == "action_faults") return actfault_set(e, reinterpret_cast<const int32_t*>(host), count);   // likewise
   else if (n == "search") return search_set(e, reinterpret_cast<const int32_t*>(host), count);   // likewise
+  else if (n == "latency") return latency_set(e, reinterpret_cast<const int32_t*>(host), count);   // likewise
   else if (n == "solver_tolerance") { e->tol32 = host[0]; return COSIM_OK; }
   else if (n == "ls_tolerance_scale") { e->ls_scale = host[0]; return COSIM_OK; }
   else if (n == "max_newton") { e->max_newton = (int)host[0]; return COSIM_OK; }
@@ -1785,6 +1869,7 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   a.mode = MODE_RESET; a.mask = mask_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
   e->plan.reset.launch(e, a, e->n_envs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
+  if (e->lat.n_obs > 0) RC_TRY(latency_obs_launch(e, 0, e->n_envs, state_out_dev, mask_dev, (hipStream_t)stream));   // clock 0: the line restarts with the first reading
   if (e->obsflt.n_items > 0) RC_TRY(obsfault_launch(e, 0, e->n_envs, state_out_dev, mask_dev, (hipStream_t)stream));   // the reset's observation is a fill at clock 0
   if (mask_dev == nullptr) e->stepped = false;
   return observers_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
@@ -1858,6 +1943,8 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
   if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_rollout") + LEDGER_INFO_MSG);
   if (e->ft_frames > 0)
     return fail(COSIM_EINVAL, "cosim_rollout: failure traces are set (cosim_ftrace_set): one launch leaves one state record for all its steps, so the per-step state is not there to copy; step with cosim_step or switch the traces off");
+  if (e->lat.n_act + e->lat.n_obs > 0)
+    return fail(COSIM_EINVAL, "cosim_rollout: latency is set (cosim_set_param \"latency\"): one launch takes all its steps and the delay lines are written between steps; step with cosim_step or clear the latency");
   if (e->scn.n_scn > 0)
     return fail(COSIM_EINVAL, "cosim_rollout: a scenario table is set (cosim_scenario_set): one launch reads one command row; step with cosim_step or clear the table");
   e->stepped = true;
@@ -1984,9 +2071,15 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   if (e->scnpar.n_items > 0) RC_TRY(scnparams_launch(e, first, count, nullptr, 0, s));
   // action faults: this step's effective actions of the range, ahead of every launch that reads the action (the fused and step-only
   // kernels, the two-envs-per-wave kernel, the split pipeline's first substep and the fix-up kernels' redo: all read a.actions)
-  const bool act_faults = e->actflt.n_items > 0;
+  // latency comes first: the delivered action is what the action faults take as the caller's word; with latency alone the step
+  // kernels read the delivered rows themselves
+  const bool act_faults = e->actflt.n_items > 0, act_lat = e->lat.n_act > 0;
+  if (act_lat) {
+    RC_TRY(latency_act_launch(e, first, count, actions_dev, s));
+    a.actions = e->d_actions_eff;
+  }
   if (act_faults) {
-    RC_TRY(actfault_launch(e, first, count, actions_dev, s));
+    RC_TRY(actfault_launch(e, first, count, act_lat ? e->d_lat_eff : actions_dev, act_lat ? e->d_lat_spare : e->d_actions_raw, s));
     a.actions = e->d_actions_eff;
   }
   if (p.split) {
@@ -2013,7 +2106,9 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   // observation faults: behind the last launch that writes the range's state records or state_out (the redo included: a redone env's
   // observation is faulted once), ahead of the observers and the history pack, which then hold what the policy saw
   // action faults: last_action is what the policy put out, not what the bus delivered; the observation faults compose on top
-  if (act_faults && e->act_in_obs) RC_TRY(actfault_obs_launch(e, first, count, state_out_dev, s));
+  if ((act_faults || act_lat) && e->act_in_obs) RC_TRY(actfault_obs_launch(e, first, count, state_out_dev, s));
+  // latency of observation elements: on the newest frame as the step (and the restore above) left it, ahead of the observation faults
+  if (e->lat.n_obs > 0) RC_TRY(latency_obs_launch(e, first, count, state_out_dev, nullptr, s));
   // While a search scales observation faults the launch goes BEHIND the observers: the observation a step that ended an episode
   // returns is clock 0 of the next one and takes the level search_step_kernel has just moved.  No observer reads what the fault kernel
   // writes (stack row 0 of the record, state_out): they read the info row, the flags, the command, qpos / qvel and the meta words, so
@@ -2158,7 +2253,8 @@ int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream)
   HIP_TRY(hipSetDevice(e->device));
   const bool act_eff = std::string(name) == "action_effective";
   if (act_eff || std::string(name) == "action_raw") {   // [N][nu], contiguous: the last step's rows of the action faults' buffers
-    if (e->actflt.n_items == 0) return fail(COSIM_EINVAL, std::string("cosim_get: ") + name + ": no action faults are set (cosim_set_param \"action_faults\")");
+    if (e->actflt.n_items == 0 && e->lat.n_act == 0)
+      return fail(COSIM_EINVAL, std::string("cosim_get: ") + name + ": no action faults are set (cosim_set_param \"action_faults\") and no latency of the command channel (cosim_set_param \"latency\")");
     RC_TRY(join_ranges(e, (hipStream_t)stream));
     HIP_TRY(hipMemcpyAsync(out_dev, act_eff ? e->d_actions_eff : e->d_actions_raw, (size_t)e->n_envs * e->model.nu * sizeof(float),
                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
@@ -2433,7 +2529,7 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
   }
   if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
   if (n_scn != e->scn.n_scn || mode == SCN_MODE_CYCLE) search_free(e);   // so is the search; its one record per env needs mode env
-  if (n_scn != e->scn.n_scn) { scnparams_free(e); obsfault_free(e); actfault_free(e); checks_free(e); curves_free(e); }   // parameter windows, faults, checks and curves are rows of the table they were set for: another S drops them
+  if (n_scn != e->scn.n_scn) { scnparams_free(e); obsfault_free(e); actfault_free(e); latency_free(e); checks_free(e); curves_free(e); }   // parameter windows, faults, checks and curves are rows of the table they were set for: another S drops them
   pk.patch(e->d_scn);
   tab.mode = mode;
   tab.gid_off = (unsigned)(((e->env_id0 % n_scn) + n_scn) % n_scn);
@@ -2570,6 +2666,95 @@ static FltShape actfault_validate(const cosim_engine* e, const FltRaw& raw) {
 static int actfault_set(cosim_engine* e, const int32_t* words, int count) {
   RC_TRY(fault_table_set(e, ACF_SETTER, "action faults", e->d_actflt, e->actflt, actfault_free, actfault_buffers, actfault_validate, words, count));
   e->actflt_marked = e->actflt.n_items > 0 ? fault_words_marked(words) : 0;
+  e->act_in_obs = false;
+  for (int el = 0; el < e->ho.frame_dim; el++) e->act_in_obs = e->act_in_obs || e->ho.el_field[el] == CS_OBS_LAST_ACTION;
+  return COSIM_OK;
+}
+
+// Latency lines of the scenario table that is set (cosim_set_param "latency"): `words` is S | act_adr[S + 1] | obs_adr[S + 1] |
+// act[na][6] | obs[no][6], an item being (t0, t1, el, ord, steps, jitter), na = act_adr[S], no = obs_adr[S]; the one word 0 clears.
+// A table with the row addresses of the one that is set whose largest delay still fits the depth D is rewritten in place: the device
+// pointers, D and the lines stay, captured graphs pick the new items up.  Anything else is a fresh allocation: D = the largest
+// steps + jitter, plus 1, and every line invalid (it restarts at the clock its kernel finds next).  Nothing is launched.
+static int latency_set(cosim_engine* e, const int32_t* words, int count) {
+  const std::string fn = LAT_SETTER;
+  if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the latency)");
+  const int n_scn = words[0];
+  HIP_TRY(hipSetDevice(e->device));
+  if (n_scn == 0) return table_clear(e, 0, latency_free);
+  RC_TRY(table_rows_match(e, fn, "latency items", n_scn));
+  const size_t S1 = (size_t)n_scn + 1;
+  if ((size_t)count < 1 + 2 * S1) return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words do not hold the row addresses of " + std::to_string(n_scn) + " scenarios");
+  const int32_t *act_adr = words + 1, *obs_adr = act_adr + S1;
+  const long long na = act_adr[n_scn], no = obs_adr[n_scn];   // (the validator holds every row inside [0, adr[S]] before it reads an item by these addresses)
+  if (na < 0 || no < 0 || (long long)count != 1 + 2 * (long long)S1 + 6 * (na + no))
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios and " + std::to_string(na) + " + " + std::to_string(no) +
+                                  " items takes " + std::to_string(1 + 2 * (long long)S1 + 6 * ((na < 0 ? 0 : na) + (no < 0 ? 0 : no))));
+  const LatRaw raw = {n_scn, act_adr, obs_adr, obs_adr + S1, obs_adr + S1 + 6 * na};
+  const LatShape v = validate_latency(e->model.nu, {e->ho.frame_dim, e->ho.stacked_dim, e->ho.stack_size, e->ho.el_field, CS_OBS_COMMAND}, raw);
+  if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
+  const int N = e->n_envs, nu = e->model.nu, fd = e->ho.frame_dim;
+  LatTable tab = {};
+  WordPacker pk;
+  pack_latency(pk, tab, raw, v);
+  RC_TRY(table_quiesce(e, 0));
+  bool in_place = e->lat.n_scn == n_scn && e->lat.n_act == v.n_act && e->lat.n_obs == v.n_obs && v.max_delay + 1 <= e->lat.depth;
+  if (in_place) {   // ... and every scenario keeps its counts: an env keeps the kinds it has a line for
+    std::vector<int32_t> old;
+    RC_TRY(table_download(e->d_lat, pk, old));
+    in_place = latency_same_rows(pk, tab, old.data());
+  }
+  if (in_place) {
+    const hipError_t r = hipMemcpy(e->d_lat, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+    if (r != hipSuccess) { latency_free(e); return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r)); }   // may be half written: no latency then
+    tab.depth = e->lat.depth;
+    pk.patch(e->d_lat);
+    e->lat = tab;
+    return COSIM_OK;
+  }
+  const int D = v.max_delay + 1;
+  const size_t cap = (size_t)256 << 20;
+  const size_t act_bytes = (size_t)N * D * nu * sizeof(float), obs_bytes = (size_t)N * D * fd * sizeof(float);
+  if (v.n_act > 0 && act_bytes > cap)
+    return fail(COSIM_EINVAL, fn + ": the action lines take " + std::to_string(N) + " envs x depth " + std::to_string(D) + " x " + std::to_string(nu) + " actuators x 4 = " +
+                                  std::to_string(act_bytes) + " bytes, more than 256 MiB: fewer envs or a shorter delay");
+  if (v.n_obs > 0 && obs_bytes > cap)
+    return fail(COSIM_EINVAL, fn + ": the observation lines take " + std::to_string(N) + " envs x depth " + std::to_string(D) + " x " + std::to_string(fd) + " frame elements x 4 = " +
+                                  std::to_string(obs_bytes) + " bytes, more than 256 MiB: fewer envs or a shorter delay");
+  // a fresh allocation replaces the one that is set only once it is complete: a failure leaves the latency that was set
+  char* d_new = nullptr;
+  float *act_line = nullptr, *obs_line = nullptr, *eff = nullptr, *spare = nullptr, *a_eff = e->d_actions_eff, *a_raw = e->d_actions_raw;
+  int* from = nullptr;
+  const size_t rows = (size_t)N * nu * sizeof(float);
+  auto run = [&]() -> hipError_t {
+    hipError_t r;
+    if ((r = hipMalloc(&d_new, pk.bytes())) != hipSuccess) return r;
+    if ((r = hipMalloc(&from, 2 * (size_t)N * sizeof(int))) != hipSuccess) return r;
+    if ((r = hipMemset(from, 0xff, 2 * (size_t)N * sizeof(int))) != hipSuccess) return r;   // -1: every line invalid
+    if (v.n_act > 0) {
+      if ((r = hipMalloc(&act_line, act_bytes)) != hipSuccess || (r = hipMemset(act_line, 0, act_bytes)) != hipSuccess) return r;
+      if ((r = hipMalloc(&eff, rows)) != hipSuccess || (r = hipMemset(eff, 0, rows)) != hipSuccess) return r;
+      if ((r = hipMalloc(&spare, rows)) != hipSuccess || (r = hipMemset(spare, 0, rows)) != hipSuccess) return r;
+      if (!a_eff && ((r = hipMalloc(&a_eff, rows)) != hipSuccess || (r = hipMemset(a_eff, 0, rows)) != hipSuccess)) return r;
+      if (!a_raw && ((r = hipMalloc(&a_raw, rows)) != hipSuccess || (r = hipMemset(a_raw, 0, rows)) != hipSuccess)) return r;
+    }
+    if (v.n_obs > 0 && ((r = hipMalloc(&obs_line, obs_bytes)) != hipSuccess || (r = hipMemset(obs_line, 0, obs_bytes)) != hipSuccess)) return r;
+    return hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  };
+  const hipError_t r = run();
+  if (r != hipSuccess) {
+    (void)hipFree(d_new); (void)hipFree(from); (void)hipFree(act_line); (void)hipFree(obs_line); (void)hipFree(eff); (void)hipFree(spare);
+    if (a_eff != e->d_actions_eff) (void)hipFree(a_eff);
+    if (a_raw != e->d_actions_raw) (void)hipFree(a_raw);
+    return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
+  }
+  latency_drop(e);
+  e->d_actions_eff = a_eff; e->d_actions_raw = a_raw;
+  e->d_lat = d_new; e->d_lat_from = from; e->d_lat_act_line = act_line; e->d_lat_obs_line = obs_line; e->d_lat_eff = eff; e->d_lat_spare = spare;
+  pk.patch(e->d_lat);
+  tab.depth = D;
+  e->lat = tab;
+  action_buffers_release(e);   // no action items now and no action faults: the two buffers go
   e->act_in_obs = false;
   for (int el = 0; el < e->ho.frame_dim; el++) e->act_in_obs = e->act_in_obs || e->ho.el_field[el] == CS_OBS_LAST_ACTION;
   return COSIM_OK;
@@ -2904,6 +3089,8 @@ int cosim_profile_step(cosim_engine_t* e, const float* actions_dev, const float*
                        uint8_t* truncated_dev, double* cycles_out16) {
   if (!e || !actions_dev || !state_out_dev || !terminated_dev || !truncated_dev || !cycles_out16) return fail(COSIM_EINVAL, "cosim_profile_step: null argument");
   if (!has(e->plan.prof)) return fail(COSIM_EINVAL, "cosim_profile_step: no diagnostic kernel for this model");
+  if (e->lat.n_act + e->lat.n_obs > 0)
+    return fail(COSIM_EINVAL, "cosim_profile_step: latency is set (cosim_set_param \"latency\"): the diagnostic step advances the clocks without writing the delay lines, so a later step would deliver a stale slot; clear the latency first");
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
   if (rc) return rc;

@@ -16,6 +16,7 @@
 
 #include "cosim_actfault.h"
 #include "cosim_curves.h"
+#include "cosim_latency.h"
 #include "cosim_obsfault.h"
 #include "cosim_scnparams.h"
 #include "cosim_search.h"
@@ -321,6 +322,60 @@ inline FltShape validate_action_faults(int nu, const FltRaw& r, const FltMarks* 
   const auto op_rule = [](const std::string& row, int, int op, float value) { return op == FLT_CLIP && value < 0.f ? row + ": a clip bound must be >= 0" : std::string(); };
   return validate_fault_items({ACF_SETTER, "action-fault item", FLT_CLIP, "(0 scale, 1 bias, 2 set, 3 noise, 4 hold, 5 drop, 6 clip)"}, r, elem_rule, op_rule, marks);
 }
+
+// ---- cosim_set_param "latency".  Image: act_adr | obs_adr | act_item | obs_item ([n][4]: t0, t1, el | ord << 16, steps | jitter << 8: cosim_latency.h)
+struct LatRaw {
+  int n_scn;   // that of the scenario table that is set
+  const int32_t *act_adr, *obs_adr;
+  const int32_t *act, *obs;   // [n][6]: t0, t1, el, ord, steps, jitter
+};
+struct LatShape { std::string err; int n_act = 0, n_obs = 0, max_delay = 0; std::vector<int32_t> act_item, obs_item; };
+
+inline LatShape validate_latency(int nu, const ObsDims& d, const LatRaw& r) {
+  const std::string fn = LAT_SETTER;
+  LatShape v;
+  const RowAdr rows[2] = {{"act_adr", r.act_adr, "action latency items", LAT_MAX_ITEMS, r.act != nullptr},
+                          {"obs_adr", r.obs_adr, "observation latency items", LAT_MAX_ITEMS, r.obs != nullptr}};
+  TAB_TRY(row_heads(fn, rows));
+  for (int s = 0; s < r.n_scn; s++) TAB_TRY(row_rule(fn + ": scenario " + std::to_string(s), rows, s));
+  for (int kind = 0; kind < 2; kind++) {
+    const int32_t* adr = kind ? r.obs_adr : r.act_adr;
+    const int32_t* it = kind ? r.obs : r.act;
+    std::vector<int32_t>& out = kind ? v.obs_item : v.act_item;
+    for (int s = 0; s < r.n_scn; s++) {
+      for (int i = adr[s]; i < adr[s + 1]; i++) {
+        const std::string row = fn + ": scenario " + std::to_string(s) + (kind ? ", observation latency item " : ", action latency item ") + std::to_string(i - adr[s]);
+        const int32_t* w = it + 6 * (size_t)i;
+        const int el = w[2], ord = w[3], steps = w[4], jitter = w[5];
+        TAB_TRY(window_rule(row, w[0], w[1]));
+        if (!kind && (el < 0 || el >= nu)) TAB_TRY(row + ": actuator " + std::to_string(el) + " out of range: the model has " + std::to_string(nu) + " actuators");
+        if (kind && (el < 0 || el >= d.frame_dim)) TAB_TRY(row + ": element " + std::to_string(el) + " out of range: the frame has " + std::to_string(d.frame_dim) + " elements");
+        if (kind && d.el_field[el] == d.command_field)
+          TAB_TRY(row + ": element " + std::to_string(el) + " is a command word and is refused: the command words are the scenario's keyframes");
+        if (steps < 0) TAB_TRY(row + ": steps " + std::to_string(steps) + " is negative");
+        if (jitter < 0) TAB_TRY(row + ": jitter " + std::to_string(jitter) + " is negative");
+        if ((long long)steps + jitter > LAT_MAX_DELAY)
+          TAB_TRY(row + ": steps " + std::to_string(steps) + " + jitter " + std::to_string(jitter) + " is more than " + std::to_string(LAT_MAX_DELAY));
+        if (ord < 0 || ord > LAT_MAX_ORD) TAB_TRY(row + ": ordinal " + std::to_string(ord) + " outside 0..65535");
+        if (steps + jitter > v.max_delay) v.max_delay = steps + jitter;
+        out.push_back(w[0]); out.push_back(w[1]);
+        out.push_back((int32_t)((unsigned)el | (unsigned)ord << 16)); out.push_back((int32_t)((unsigned)steps | (unsigned)jitter << 8));
+      }
+    }
+  }
+  v.n_act = r.act_adr[r.n_scn]; v.n_obs = r.obs_adr[r.n_scn];
+  if (v.n_act + v.n_obs == 0) TAB_TRY(fn + ": the table holds no latency item (n_scn = 0 clears the latency)");
+  return v;
+}
+
+inline void pack_latency(WordPacker& pk, LatTable& tab, const LatRaw& r, const LatShape& v) {
+  const size_t S1 = (size_t)r.n_scn + 1;
+  pk.add(&tab.act_adr, r.act_adr, S1); pk.add(&tab.obs_adr, r.obs_adr, S1);
+  pk.add(&tab.act_item, v.act_item.data(), v.act_item.size()); pk.add(&tab.obs_item, v.obs_item.data(), v.obs_item.size());
+  tab.n_scn = r.n_scn; tab.n_act = v.n_act; tab.n_obs = v.n_obs;
+}
+// whether the image holds the row addresses of `old`, an image of the same counts: every env keeps the kinds it had a line for
+inline bool latency_same_rows(const WordPacker& pk, const LatTable& tab, const int32_t* old) { return pk.same(&tab.act_adr, old) && pk.same(&tab.obs_adr, old); }
 
 // ---- cosim_scenario_checks_set.  Image: adr | t | signal | index | mode | cmp | bound
 struct ChkRaw {

@@ -432,6 +432,13 @@ class Engine:
         value)`` of ``ScenarioTable.pack_action_faults`` (``None``: clear the faults), the word table of the observation faults."""
         self._word_table_set("scenario_action_faults_set", b"action_faults", csr)
 
+    def latency_set(self, words):
+        """Latency lines, through ``cosim_set_param "latency"``: ``words`` = the int32 word table of ``ScenarioTable.pack_latency`` (``S |
+        act_adr | obs_adr | act[na][6] | obs[no][6]``, an item being ``(t0, t1, element, ord, steps, jitter)``; ``None``: clear the
+        latency)."""
+        words = np.zeros(1, dtype=np.int32) if words is None else np.ascontiguousarray(words, dtype=np.int32).reshape(-1)
+        self._check(self.L.cosim_set_param(self.h, b"latency", words.ctypes.data, int(words.size)))
+
     def search_set(self, words):
         """Limit search, through ``cosim_set_param "search"``: ``words`` = the int32 word table of ``ScenarioTable.pack_search`` (``S |
         slots | has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip``, in its long form ``| harder | chk_lo |

@@ -17,6 +17,8 @@ Purposes: 0 action-delay draw, 1 sensor noise (index = frame element), 2 init-qp
 ``e`` (< 256), mapped by ``fault_noise_u``; ``drop``: index = ``0x10000 + ord``, the listed item's ordinal, mapped by ``fault_drop_u``),
 8 action faults of a scenario table (``csrc/cosim_actfault.h``; step = meta word 1 as the step FINDS it; ``noise``: index = actuator
 ``j``; ``drop``: index = ``0x10000 + ord``; the same two maps).  ``csrc/cosim_fault.h`` has the draws and the maps of both.
+9 latency jitter of a scenario table (``csrc/cosim_latency.h``; step = meta word 1 as the kernel of the channel kind finds it: pre-step
+for actions, post-step for observations; index = the listed item's ordinal; mapped into ``0..jitter`` by ``latency_jitter``).
 """
 from __future__ import annotations
 
@@ -30,6 +32,7 @@ PURPOSE_DELAY, PURPOSE_SENSOR, PURPOSE_INIT, PURPOSE_MASS, PURPOSE_GAIN = 0, 1, 
 PURPOSE_SPAWN, PURPOSE_SPAWN_POSE = 5, 6
 PURPOSE_OBS_FAULT = 7
 PURPOSE_ACTION_FAULT = 8
+PURPOSE_LATENCY = 9
 FAULT_DROP_INDEX = 0x10000
 
 
@@ -87,6 +90,12 @@ def fault_noise_u(x):
     """uint32 -> float32 in [-1, 1): ``(x >> 8) * 2^-23 - 1``, exact (the device ``fault_noise_u``, ``csrc/cosim_fault.h``)."""
     x = np.asarray(x, dtype=np.uint32)
     return ((x >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 8388608.0) - np.float32(1.0)).astype(np.float32)
+
+
+def latency_jitter(x, jitter: int):
+    """uint32 -> int in ``0..jitter``: ``((x >> 8) * (jitter + 1)) >> 24``, exact (the device ``latency_jitter``, ``csrc/cosim_latency.h``)."""
+    x = np.asarray(x, dtype=np.uint32)
+    return (((x >> np.uint32(8)).astype(np.uint64) * np.uint64(int(jitter) + 1)) >> np.uint64(24)).astype(np.int64)
 
 
 def fault_drop_u(x):

@@ -75,6 +75,19 @@ level of the episode its observation belongs to.  ``"harder":
 "up" | "down"`` (default up): with ``"down"`` a LOWER level is harder (a gain scale, a friction): a failure moves the level up, a pass
 down.  ``fail_on`` also takes ``"checks"`` (any check of the row), ``"check:NAME"`` and ``"check:I"``: a trial fails too if a selected
 check of the ended episode did not pass (failed or incomplete); the checks must be armed (``check_slots``).
+
+Latency (``cosim_set_param "latency"``, csrc/cosim_latency.hip): a scenario may hold ``"latency": [[t0, t1, channel, index, steps], ...]``
+(optional trailing entries: an int ``jitter``, default 0, and a string name; or a dict with the keys ``t0, t1, channel, index, steps,
+jitter, name``): a timed TRANSPORT DELAY of ``steps`` control steps plus ``0..jitter`` drawn per step and listed item.  ``channel`` is
+``"action"`` (what the drives are told arrives late; ``index`` an actuator index, an actuator name or ``"*"``; keyed on the pre-step
+episode clock, as an action fault) or an observation name (what the policy sees arrives late; ``index`` an int or ``"*"``; ``command``
+is refused; keyed on the observation's own clock, as an observation fault).  ``steps >= 0``, ``jitter >= 0``, ``steps + jitter <= 63``;
+at most 256 expanded items per scenario and channel kind.  Per element the LAST listed item that holds gives the delay; delays do not
+compose.  Every env whose row lists an item of a kind keeps a line of the channel's clean words on the device, written at every clock,
+inside and outside the windows, so a window that opens in mid-episode delivers the history before it.  Before the line holds the
+word asked for, an observation is the line's first reading and an action is 0 after a reset (nothing has arrived yet), the first
+word after a host cut in mid-episode.  Latency comes ahead of the faults: they take the delivered word.  ``last_action`` in the
+observation stays the policy's own output.  ``LatencyTwin`` is the numpy twin, exact; the lines are not part of a snapshot.
 """
 from __future__ import annotations
 
@@ -111,6 +124,9 @@ SEARCH_FAIL_ON = {"terminated": 1, "nonfinite": 4, "tilt": 32, "height": 64, "co
 MAX_SEARCH_SLOTS, MAX_SEARCH_TRIALS, MAX_SEARCH_REV_SKIP = 64, 1 << 20, 255
 _SEARCH_KEYS = ("lo", "hi", "start", "step", "min_step", "rule", "trials", "targets", "fail_on", "rev_skip")
 _SEARCH_OPT_KEYS = ("harder",)                 # emitted only when not the default
+MAX_LATENCY_ITEMS, MAX_LATENCY_DELAY = 256, 63 # expanded items per scenario and channel kind; steps + jitter
+_LATENCY_KEYS = ("t0", "t1", "channel", "index", "steps", "jitter")
+LATENCY_ACTION, LATENCY_OBS = 0, 1             # the channel kind of an expanded item
 
 
 class _FaultKind(NamedTuple):
@@ -223,9 +239,10 @@ class ScenarioTable:
         self.fault_rows, self.faults = [], None                   # (the attributes the two _FaultKind name)
         self.action_fault_rows, self.action_faults = [], None
         self.search = []                                          # per scenario: None or the item as a dict of _SEARCH_KEYS
+        self.latency_rows, self.latency = [], None                # the rows as written; per scenario the expanded items (resolve_latency)
         for s, sc in enumerate(scenarios):
             sc = sc or {}
-            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "faults", "action_faults", "search", "name"}:
+            if not isinstance(sc, dict) or set(sc) - {"commands", "pushes", "params", "checks", "curves", "faults", "action_faults", "search", "latency", "name"}:
                 raise ValueError(f"ScenarioTable: scenario {s}: a mapping with the keys 'commands' and 'pushes' is expected, got {sc!r}")
             keys, pushes = [], []
             for r, row in enumerate(sc.get("commands") or []):
@@ -262,6 +279,7 @@ class ScenarioTable:
             self.curve_rows.append(_curve_rows(s, sc.get("curves") or []))
             for kind in FAULT_KINDS:
                 getattr(self, kind.rows).append(_fault_kind_rows(kind, s, sc.get(kind.key) or []))
+            self.latency_rows.append(_latency_rows(s, sc.get("latency") or []))
             self.search.append(_search_item(s, sc.get("search"), bool(pushes), bool(keys),
                                             {"params": self.param_windows[s], **{k.key: getattr(self, k.rows)[s] for k in FAULT_KINDS}}, self.check_rows[s]))
         if names is not None or not self.has_params:
@@ -277,6 +295,138 @@ class ScenarioTable:
         an = (names or {}).get("action_faults")
         if an is not None or not self.has_action_faults:
             self.resolve_action_faults(an or [])
+        ln = (names or {}).get("latency")
+        if ln is not None or not self.has_latency:
+            self.resolve_latency(*(ln or ({"stacked": [], "non_stacked": [], "stack_size": 1}, [])))
+
+    # ---- latency: the rows as written, their expansion, packing and the way back
+    @property
+    def has_latency(self) -> bool:
+        return any(self.latency_rows)
+
+    def resolve_latency(self, names: dict, actuators) -> "ScenarioTable":
+        """Expand the latency rows against ``names`` (``fault_names(...)``, ``BatchedEnv.fault_names()``) and ``actuators`` (the model's
+        actuator names in order): ``self.latency[s]`` becomes the list of items ``(t0, t1, channel kind, element, ord, steps, jitter)`` in
+        listed order, ``"*"`` expanded in index order -- kind ``LATENCY_ACTION`` with an actuator, ``LATENCY_OBS`` with a frame element;
+        ``ord`` is the ordinal of the listed item (its elements share one jitter draw).  Raises ``ValueError`` naming the scenario and
+        the item: unknown channel or actuator, index out of range, more than 256 items of a kind."""
+        actuators = list(actuators)
+        nu = len(actuators)
+        first, e = {}, 0
+        for lst in (names["stacked"], names["non_stacked"]):
+            for n, d in lst:
+                first.setdefault(n, (e, int(d)))
+                e += int(d)
+        out = []
+        for s, rows in enumerate(self.latency_rows):
+            items = []
+            for r, (t0, t1, channel, index, steps, jitter, _) in enumerate(rows):
+                who = f"ScenarioTable: scenario {s}, latency item {r}"
+                if channel == "action":
+                    if index == "*":
+                        els = list(range(nu))
+                    elif isinstance(index, str):
+                        els = [i for i, n in enumerate(actuators) if n == index]
+                        if not els:
+                            raise ValueError(f"{who}: unknown actuator '{index}' (the model has {', '.join(map(str, actuators)) or 'none'})")
+                    elif not 0 <= index < nu:
+                        raise ValueError(f"{who}: index {index} out of range: the model has {nu} actuators")
+                    else:
+                        els = [index]
+                    kind = LATENCY_ACTION
+                else:
+                    if channel not in first:
+                        raise ValueError(f"{who}: unknown channel '{channel}' ('action' or an observation: the env observes {', '.join(first) or 'nothing'})")
+                    e0, dim = first[channel]
+                    if isinstance(index, str) and index != "*":
+                        raise ValueError(f"{who}: index must be an int or '*' on an observation, got {index!r}")
+                    if index != "*" and not 0 <= index < dim:
+                        raise ValueError(f"{who}: index {index} out of range: '{channel}' has {dim} entries")
+                    els = [e0 + i for i in (range(dim) if index == "*" else [index])]
+                    kind = LATENCY_OBS
+                items += [(t0, t1, kind, el, r, steps, jitter) for el in els]
+            for kind, what in ((LATENCY_ACTION, "action"), (LATENCY_OBS, "observation")):
+                n = sum(1 for it in items if it[2] == kind)
+                if n > MAX_LATENCY_ITEMS:
+                    raise ValueError(f"ScenarioTable: scenario {s}: {n} {what} latency items after expansion, at most {MAX_LATENCY_ITEMS}")
+            out.append(items)
+        self.latency = out
+        return self
+
+    def _carry_latency(self, new: "ScenarioTable") -> "ScenarioTable":
+        """``new``, a table rebuilt from this one's ``to_list()`` (the ``*_from_csr`` helpers), with this one's expanded latency
+        items: its latency rows are this one's, so the expansion is too."""
+        if new.latency is None and self.latency is not None:
+            new.latency = [list(f) for f in self.latency]
+        return new
+
+    def _resolved_latency(self) -> list:
+        if self.latency is None:
+            raise ValueError("ScenarioTable: the latency items are not resolved yet: pass names={'latency': (fault_names(...), [actuator names])} "
+                             "or call resolve_latency")
+        return self.latency
+
+    @property
+    def n_latency_items(self) -> int:
+        return sum(len(f) for f in self._resolved_latency())
+
+    @property
+    def latency_depth(self) -> int:
+        """The depth D of the lines a fresh allocation gets: the largest ``steps + jitter``, plus 1."""
+        return 1 + max((it[5] + it[6] for f in self._resolved_latency() for it in f), default=0)
+
+    def pack_latency(self) -> np.ndarray:
+        """The expanded items as the int32 word table ``Engine.latency_set`` sends through ``cosim_set_param "latency"``: ``S |
+        act_adr[S + 1] | obs_adr[S + 1] | act[na][6] | obs[no][6]``, an item being ``(t0, t1, element, ord, steps, jitter)``."""
+        adr, items = ([0], [0]), ([], [])
+        for f in self._resolved_latency():
+            for kind in (LATENCY_ACTION, LATENCY_OBS):
+                items[kind].extend([t0, t1, el, r, steps, jitter] for t0, t1, k, el, r, steps, jitter in f if k == kind)
+                adr[kind].append(len(items[kind]))
+        flat = [w for kind in (LATENCY_ACTION, LATENCY_OBS) for it in items[kind] for w in it]
+        return np.array([len(self)] + adr[0] + adr[1] + flat, dtype=np.int32)
+
+    def latency_from_words(self, words, names: dict, actuators) -> "ScenarioTable":
+        """A table with everything of this one but the latency, which is what the word table of ``pack_latency`` holds: the items of
+        one ``ord`` become one listed item again (``"*"`` if they cover the channel, else one item per element), resolved against
+        ``names`` and ``actuators``."""
+        words = np.asarray(words, dtype=np.int64).reshape(-1)
+        S = int(words[0])
+        scn = self.to_list()
+        if S != len(scn):
+            raise ValueError(f"ScenarioTable: latency for {S} scenarios, the table has {len(scn)}")
+        adr = (words[1:S + 2], words[S + 2:2 * S + 3])
+        na, no = int(adr[0][-1]), int(adr[1][-1])
+        body = words[2 * S + 3:]
+        if len(body) != 6 * (na + no):
+            raise ValueError(f"ScenarioTable: latency words: {len(body)} item words, {na} + {no} items take {6 * (na + no)}")
+        recs = (body[:6 * na].reshape(-1, 6), body[6 * na:].reshape(-1, 6))
+        actuators = list(actuators)
+        spans, e = [], 0
+        for n, d in list(names["stacked"]) + list(names["non_stacked"]):
+            spans.append((n, e, int(d)))
+            e += int(d)
+        for s, sc in enumerate(scn):
+            sc.pop("latency", None)
+            groups = {}                                             # ord -> (kind, head, [elements])
+            for kind in (LATENCY_ACTION, LATENCY_OBS):
+                for t0, t1, el, r, steps, jitter in recs[kind][int(adr[kind][s]):int(adr[kind][s + 1])].tolist():
+                    groups.setdefault(r, (kind, (t0, t1, steps, jitter), []))[2].append(el)
+            rows = []
+            for r in sorted(groups):
+                kind, (t0, t1, steps, jitter), els = groups[r]
+                if kind == LATENCY_ACTION:
+                    channel, idx, whole = "action", els, len(actuators) > 1 and els == list(range(len(actuators)))
+                else:
+                    span = [sp for sp in spans if sp[1] <= els[0] < sp[1] + sp[2]]
+                    if not span:
+                        raise ValueError(f"ScenarioTable: scenario {s}, latency item {r}: element {els[0]} outside the frame")
+                    channel, e0, d = span[0]
+                    idx, whole = [k - e0 for k in els], d > 1 and els == list(range(e0, e0 + d))
+                rows += [[t0, t1, channel, "*" if whole else k, steps, jitter] for k in (["*"] if whole else idx)]
+            if rows:
+                sc["latency"] = rows
+        return type(self)(scn, self.command_dim).resolve_latency(names, actuators)
 
     # ---- faults, both kinds: the rows as written, their expansion, packing and the way back
     def _expand_faults(self, kind: _FaultKind, elements) -> "ScenarioTable":
@@ -343,7 +493,7 @@ class ScenarioTable:
                 i = j
             if rows:
                 sc[kind.key] = rows
-        return type(self)(scn, self.command_dim)
+        return self._carry_latency(type(self)(scn, self.command_dim))
 
     @property
     def has_action_faults(self) -> bool:
@@ -539,7 +689,7 @@ class ScenarioTable:
                         sc["search"]["fail_on"].append("checks")
                     else:
                         sc["search"]["fail_on"] += [f"check:{i}" for i in range(64) if mask >> i & 1]
-        return type(self)(scn, self.command_dim)
+        return self._carry_latency(type(self)(scn, self.command_dim))
 
     @property
     def has_checks(self) -> bool:
@@ -665,6 +815,9 @@ class ScenarioTable:
             if it is not None:
                 sc["search"] = {k: (list(it[k]) if isinstance(it[k], list) else it[k]) for k in _SEARCH_KEYS}
                 sc["search"].update({k: it[k] for k in _SEARCH_OPT_KEYS if it[k] != "up"})
+        for sc, rows in zip(out, self.latency_rows):
+            if rows:
+                sc["latency"] = [[*row[:-1]] + ([row[-1]] if row[-1] is not None else []) for row in rows]
         return out
 
     def pack(self):
@@ -700,7 +853,7 @@ class ScenarioTable:
                      float(np.float32(value[i]))] for i in range(int(adr[s]), int(adr[s + 1]))]
             if rows:
                 sc["params"] = rows
-        return type(self)(scn, self.command_dim, names=names)
+        return self._carry_latency(type(self)(scn, self.command_dim, names=names))
 
     @classmethod
     def from_csr(cls, key_adr, key_t, key_cmd, push_adr, push_t, push_v, command_dim: int) -> "ScenarioTable":
@@ -791,6 +944,60 @@ def _fault_kind_rows(kind: _FaultKind, s: int, rows) -> list:
         if name is not None and not isinstance(name, str):
             raise ValueError(f"{who}: the name must be a string, got {name!r}")
         out.append((int(t0f), int(t1f), *row[2:-3], index if isinstance(index, str) else int(index), op, value, name))
+    return out
+
+
+def _latency_rows(s: int, rows) -> list:
+    """The ``"latency"`` rows of scenario ``s``, checked for everything that needs no observation config and no model: ``(t0, t1,
+    channel, index, steps, jitter, name or None)``."""
+    out = []
+    if not isinstance(rows, (list, tuple)):
+        raise ValueError(f"ScenarioTable: scenario {s}: 'latency' must be a list of items, got {rows!r}")
+    is_int = lambda x: isinstance(x, (int, np.integer)) and not isinstance(x, bool)   # noqa: E731
+    for r, row in enumerate(rows):
+        who = f"ScenarioTable: scenario {s}, latency item {r}"
+        name, jitter = None, 0
+        if isinstance(row, dict):
+            if set(row) - set(_LATENCY_KEYS) - {"name"} or any(k not in row for k in _LATENCY_KEYS if k not in ("index", "jitter")):
+                raise ValueError(f"{who}: a mapping with the keys {', '.join(_LATENCY_KEYS)} (and 'name') is expected, got {row!r}")
+            name, jitter = row.get("name"), row.get("jitter", 0)
+            row = [row["t0"], row["t1"], row["channel"], row.get("index", "*"), row["steps"]]
+        elif isinstance(row, (list, tuple)) and len(row) in (6, 7):
+            tail = list(row[5:])
+            if len(tail) == 2:
+                jitter, name = tail
+            elif isinstance(tail[0], str):
+                name = tail[0]
+            else:
+                jitter = tail[0]
+            row = list(row[:5])
+        if not isinstance(row, (list, tuple)) or len(row) != 5:
+            raise ValueError(f"{who}: expected [t0, t1, channel, index, steps] with an optional jitter and an optional name, got {row!r}")
+        t0, t1, channel, index, steps = row
+        try:
+            t0f, t1f = float(t0), float(t1)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: times must be numbers, got {row!r}") from None
+        if not (math.isfinite(t0f) and math.isfinite(t1f)) or t0f != int(t0f) or t1f != int(t1f) or not 0 <= t0f < MAX_TIME or not 0 <= t1f <= MAX_TIME:
+            raise ValueError(f"{who}: times must be control steps in [0, 2^30)")
+        if t1f <= t0f:
+            raise ValueError(f"{who}: t1 {int(t1f)} is not after t0 {int(t0f)}")
+        if channel == "command":
+            raise ValueError(f"{who}: channel 'command' is refused: the command words are the scenario's keyframes ('commands')")
+        if not isinstance(channel, str):
+            raise ValueError(f"{who}: channel must be 'action' or the name of an observation, got {channel!r}")
+        for what, x in (("steps", steps), ("jitter", jitter)):
+            if not is_int(x):
+                raise ValueError(f"{who}: {what} must be an int, got {x!r}")
+            if x < 0:
+                raise ValueError(f"{who}: {what} {int(x)} is negative")
+        if steps + jitter > MAX_LATENCY_DELAY:
+            raise ValueError(f"{who}: steps {int(steps)} + jitter {int(jitter)} is more than {MAX_LATENCY_DELAY}")
+        if not (is_int(index) or (isinstance(index, str) and (channel == "action" or index == "*"))):
+            raise ValueError(f"{who}: index must be an int or '*' (on 'action' also an actuator name), got {index!r}")
+        if name is not None and not isinstance(name, str):
+            raise ValueError(f"{who}: the name must be a string, got {name!r}")
+        out.append((int(t0f), int(t1f), channel, index if isinstance(index, str) else int(index), int(steps), int(jitter), name))
     return out
 
 
@@ -1086,7 +1293,7 @@ def _search_item(s: int, item, has_pushes: bool, has_keys: bool, fault_rows: dic
 
 def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable = (0.0,), push_times: Iterable = (),
           params: Iterable = (), checks: Iterable = (), curves: Iterable = (), faults: Iterable = (),
-          action_faults: Iterable = (), search: Iterable = ()) -> Iterator[dict]:
+          action_faults: Iterable = (), search: Iterable = (), latency: Iterable = ()) -> Iterator[dict]:
     """The cartesian product command rows x push speeds x directions x push times as scenarios, commands outermost: each holds its
     command from episode step 0 and one push of ``speed`` m/s along the world direction ``angle`` (radians about z, 0 = +x) held over
     ``(t0, t1)``.  With no speeds or no times the product is over the commands alone (no push).
@@ -1098,7 +1305,19 @@ def sweep(commands: Iterable, push_speeds: Iterable = (), directions: Iterable =
     ``"faults"`` value, possibly empty) is one more axis, inside the curves: ``len(...) * len(F)`` scenarios.  ``action_faults``: a list
     of action-fault lists (each a scenario's ``"action_faults"`` value, possibly empty) is one more axis, inside the faults and innermost
     of the tables: ``len(...) * len(A)`` scenarios.  ``search``: a list of search items (each a scenario's ``"search"`` value, or ``None``
-    for a scenario without one) is one more axis, innermost of all: ``len(...) * len(L)`` scenarios."""
+    for a scenario without one) is one more axis, inside the action faults: ``len(...) * len(L)`` scenarios.  ``latency``: a list of
+    latency lists (each a scenario's ``"latency"`` value, possibly empty) is one more axis, innermost of all: ``len(...) * len(Y)``
+    scenarios -- ``latency=[[], [[0, 1000, "action", "*", 2]], [[0, 1000, "action", "*", 4]]]`` with ``by_scenario()`` is the latency
+    a policy still tolerates."""
+    latency = [list(f) for f in latency]
+    if latency:
+        for sc in sweep(commands, push_speeds, directions, push_times, params, checks, curves, faults, action_faults, search):
+            for fl in latency:
+                out = dict(sc)
+                if fl:
+                    out["latency"] = [dict(f) if isinstance(f, dict) else list(f) for f in fl]
+                yield out
+        return
     search = list(search)
     if search:
         for sc in sweep(commands, push_speeds, directions, push_times, params, checks, curves, faults, action_faults):
@@ -1335,6 +1554,83 @@ def reference_action_faults(table: ScenarioTable, mode, gid, t, ep, step_count, 
             v = _level_value(table, _ACTION_FAULTS.key, r, ordinal, value, None if level is None else np.asarray(level, dtype=np.float32).reshape(N)[m])
             eff[m, j] = _fault_op(_ACTION_FAULTS.op_names[op], j, ordinal, v, eff[m, j], prev[m, j], t[m] == 0, draw)
     return eff
+
+
+class LatencyTwin:
+    """Numpy twin of ``latency_act_kernel`` / ``latency_obs_kernel`` (csrc/cosim_latency.hip) for N envs, exact.  It keeps what the
+    engine keeps: per channel kind a line ``[N, D, width]`` of clean words (slot = clock mod D, D = ``depth`` or the table's
+    ``latency_depth``) and per env the clock ``from`` its line is valid from (below 0: invalid).  ``gid`` ``[N]`` global env ids, ``nu``
+    and ``frame_dim`` the widths.  A reset needs no call: clock 0 restarts a line."""
+
+    def __init__(self, table: ScenarioTable, mode, gid, seed: int, nu: int, frame_dim: int, depth: int = None):
+        self.table, self.mode, self.seed = table, mode, int(seed)
+        self.gid = np.asarray(gid, dtype=np.int64).reshape(-1)
+        self.N = len(self.gid)
+        self.D = int(depth or table.latency_depth)
+        if self.D < table.latency_depth:
+            raise ValueError(f"LatencyTwin: depth {self.D} is below the table's {table.latency_depth}")
+        self.width = (int(nu), int(frame_dim))
+        self.line = [np.zeros((self.N, self.D, w), dtype=np.float32) for w in self.width]
+        self.valid_from = [np.full(self.N, -1, dtype=np.int64) for _ in self.width]
+
+    def cut(self, mask=None):
+        """A host cut that is no reset (``restore``, ``fork``, ``set_state``) of the envs under ``mask`` (default: all): their lines are
+        invalid and restart at the next clock their kernel finds."""
+        m = np.ones(self.N, dtype=bool) if mask is None else np.asarray(mask, dtype=bool).reshape(self.N)
+        for f in self.valid_from:
+            f[m] = -1
+
+    def _step(self, kind: int, words, t, ep, step_count, active):
+        from . import rng
+        N, D, W = self.N, self.D, self.width[kind]
+        x = np.ascontiguousarray(words, dtype=np.float32).reshape(N, W)
+        t, ep, step_count = (np.asarray(a).astype(np.int64).reshape(N) for a in (t, ep, step_count))
+        act = np.ones(N, dtype=bool) if active is None else np.asarray(active, dtype=bool).reshape(N)
+        row = scenario_rows(len(self.table), self.mode, self.gid, ep)
+        items = self.table._resolved_latency()
+        k, has = np.zeros((N, W), dtype=np.int64), np.zeros(N, dtype=bool)
+        for r in np.unique(row[act]):
+            its = [it for it in items[r] if it[2] == kind]
+            if not its:
+                continue
+            in_row = act & (row == r)
+            has |= in_row
+            for t0, t1, _, el, ordinal, steps, jitter in its:      # the last listed item that holds wins
+                m = in_row & (t0 <= t) & (t < t1)
+                if not m.any():
+                    continue
+                kk = np.full(int(m.sum()), steps, dtype=np.int64)
+                if jitter > 0:
+                    w = rng.first_word(self.seed, self.gid[m].astype(np.uint64), step_count[m].astype(np.uint32), rng.PURPOSE_LATENCY, ordinal)
+                    kk = kk + rng.latency_jitter(w, jitter)
+                k[m, el] = np.minimum(kk, D - 1)
+        f = self.valid_from[kind]
+        restart = has & ((t == 0) | (f < 0) | (f > t))
+        f[restart] = t[restart]
+        line = self.line[kind]
+        idx = np.nonzero(has)[0]
+        line[idx, t[idx] % D] = x[idx]
+        c = t[:, None] - k
+        late = c >= f[:, None]
+        src = np.where(late, c, f[:, None])
+        got = line[np.arange(N)[:, None], np.mod(src, D), np.arange(W)[None, :]]
+        if kind == LATENCY_ACTION:                                  # nothing has arrived yet after a reset
+            got = np.where(~late & (f == 0)[:, None], np.float32(0.0), got)
+        return np.where(has[:, None] & (k > 0), got, x).astype(np.float32)
+
+    def step_actions(self, raw, t, ep, step_count) -> np.ndarray:
+        """One control step: ``raw`` ``[N, nu]`` float32, the caller's actions; the PRE-STEP meta words ``t`` (word 0), ``ep`` (word 11)
+        and ``step_count`` (word 1), each ``[N]``.  Returns the delivered actions ``[N, nu]``: what the step kernels (or the action
+        faults) are handed."""
+        return self._step(LATENCY_ACTION, raw, t, ep, step_count, None)
+
+    def step_obs(self, frames, t_obs, ep, step_count, active=None) -> np.ndarray:
+        """One observation: ``frames`` ``[N, frame_dim]`` float32, the CLEAN newest frame (the first ``stacked_dim`` words and the
+        non-stacked tail of a latency-free run's ``state_out`` row); the POST-step meta words ``t_obs``, ``ep``, ``step_count``, each
+        ``[N]``; ``active`` ``[N]`` bool (default: all): the envs a masked reset touched.  Returns the delivered newest frames ``[N,
+        frame_dim]`` (an env that is not active gets its clean row back); ``reference_obs_faults`` over them emulates the stack's roll
+        and fill, with or without faults on top."""
+        return self._step(LATENCY_OBS, frames, t_obs, ep, step_count, active)
 
 
 def push_reference(quat, v) -> np.ndarray:

@@ -466,6 +466,39 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  * cosim_debug_forward ignore the faults.  cosim_query "action_faults" answers the number of items (0: none); cosim_get
  * "action_effective" / "action_raw" copy the last step's buffers [N][nu] to device memory (COSIM_EINVAL while no faults are set). */
 
+/* Latency lines of the scenario table that is set: timed k-step delays of the command channel (policy -> drives) and of observation
+ * elements (sensor -> policy) per env, on the device (cosim_amd/csrc/cosim_latency.h has the rule).  No entry point of their own:
+ * the table travels through cosim_set_param(e, "latency", words, count), `words` pointing at `count` 32-BIT WORDS, all int32:
+ *   S | act_adr[S + 1] | obs_adr[S + 1] | act[na][6] | obs[no][6],   na = act_adr[S], no = obs_adr[S],   count = 2 S + 3 + 6 (na + no)
+ * the one word 0 clears the latency.  Scenario s owns the action items [act_adr[s], act_adr[s + 1]) and the observation items
+ * [obs_adr[s], obs_adr[s + 1]) (at most 256 each).  An item is (t0, t1, el, ord, steps, jitter): el ONE actuator (0 <= el < nu) or
+ * ONE frame element (0 <= el < frame_dim, not a command word), ord (0..65535) the ordinal of the listed item it was expanded from,
+ * steps >= 0, jitter >= 0, steps + jitter <= 63.  It holds while t0 <= t < t1 of the env's PRE-STEP episode clock (actions) or of the
+ * observation's own clock (observations: meta word 0 as the step or reset left it); the row is that of cosim_scenario_set on the same
+ * meta words.  The engine keeps per env and kind a LINE of the channel's clean words of the last D clocks (D = the largest
+ * steps + jitter of the table, plus 1; [N][D][nu] and [N][D][frame_dim] floats, each at most 256 MiB) and the clock `from` the line is
+ * valid from.  An env whose row lists an item of the kind writes the clean word of every element to slot t mod D at every clock, inside
+ * and outside the windows; `from` becomes t at t == 0 and where a host cut invalidated the line (cosim_set, cosim_restore: the envs
+ * they touch).  Per element the LAST listed item that holds gives the delay k = steps + j, j = ((w >> 8) * (jitter + 1)) >> 24 with w the
+ * first Philox4x32-10 word keyed (seed_lo, seed_hi), counter (meta word 1 at the site, 9 | ord << 8, gid_lo, gid_hi) (jitter 0: no draw);
+ * k == 0 keeps the element's bits; else with c = t - k the delivered word is the line's of clock c if c >= from, otherwise for an
+ * observation the line's of clock `from`, for an action 0.0f if from == 0 and the line's of clock `from` if not.
+ * latency_act_kernel (cosim_latency.hip) runs ahead of actfault_step_kernel and of the step: the step kernels (or, if they are set,
+ * the action faults as their x) are handed the delivered action; last_action stays the policy's own output (actfault_obs_kernel runs
+ * with latency alone too).  latency_obs_kernel runs behind the step's last writer and actfault_obs_kernel, ahead of the observation
+ * faults' kernel, and behind a reset under its mask: delivered words go to row 0 of the observation stack (a non-stacked element: its
+ * word behind the stack rows) and to state_out.  Both work under a deferred join and inside a captured graph; set or clear the latency
+ * before capturing.  A table with the row addresses of the one that is set whose largest delay fits D is rewritten in place and keeps
+ * the lines; anything else allocates anew with every line invalid.  The call joins the ranges and blocks until the device is idle; it
+ * launches nothing.  S must be the "scenario_rows" of the table that is set; cosim_scenario_set with another S, or clearing the table,
+ * drops the latency.  Validated on the host before anything is changed, the message names the scenario and the item (COSIM_EINVAL).
+ * The lines are not part of a snapshot.  cosim_rollout is refused while latency is set, and so is cosim_profile_step: the diagnostic
+ * step advances the clocks without writing the lines, and a later step would deliver a stale slot (the faults, which keep nothing per
+ * env, it merely ignores).  cosim_query "launches" answers the kernel launches the engines of the process have issued through the
+ * engine's launchers, modulo 2^31: with no latency set a run issues exactly what it issued before.  cosim_query "latency" answers the number of
+ * items of both kinds (0: none: not a launch or a pointer differs), "latency_action_items" / "latency_obs_items" those of a kind,
+ * "latency_depth" D; cosim_get "action_effective" / "action_raw" work with action items alone. */
+
 /* Limit search of the scenario table that is set: a per-env staircase on the scale of a scenario's pushes and commands, moved on the
  * device by the outcome of the env's own episodes (cosim_amd/csrc/cosim_search.h has the rule).  Like the faults it has no entry point
  * of its own: the table travels through cosim_set_param(e, "search", words, count), `words` pointing at `count` 32-BIT WORDS:
