@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "../../include/cosim_actor.h"
 #include "cosim_kernels.hip"
 #include "cosim_mlp.hip"
 #include "cosim_spawn.hip"
@@ -1122,6 +1123,7 @@ struct TableCore {
 // what cosim_policy_table_create hands out: the core, the descriptors and the launch's leading dimension
 struct cosim_policy_table : TableCore {
   PolDesc* d_desc = nullptr;
+  PolExt* d_ext = nullptr;   // [K] or null: no policy has extras, the plain grouped kernel runs
   int ld = 0;
 };
 
@@ -1157,6 +1159,13 @@ static int table_upload(TableCore& t, const std::vector<float>& image, const voi
   HIP_TRY(hipMemcpy(*d_desc, desc, desc_bytes, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(t.d_rows, tl.rows.data(), b_rows, hipMemcpyHostToDevice));
   HIP_TRY(hipMemcpy(t.d_tiles, tl.tiles.data(), b_tiles, hipMemcpyHostToDevice));
+  return COSIM_OK;
+}
+
+// a table's second per-policy record
+static int upload_words(PolExt** dst, const void* src, size_t bytes) {
+  HIP_TRY(hipMalloc(dst, bytes));
+  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
   return COSIM_OK;
 }
 
@@ -1262,54 +1271,107 @@ static int table_lists(TableCore* p, int range, int* rows_host, int* tiles_host,
   return COSIM_OK;
 }
 
+// cosim_mlp_extras_t (include/cosim_actor.h) is handed to cosim_poltab.h as PolExtRaw: the same layout, field by field
+#define EXTRAS_SAME(f) (offsetof(cosim_mlp_extras_t, f) == offsetof(PolExtRaw, f) && sizeof(cosim_mlp_extras_t::f) == sizeof(PolExtRaw::f))
+static_assert(sizeof(cosim_mlp_extras_t) == sizeof(PolExtRaw) && EXTRAS_SAME(n_in) && EXTRAS_SAME(n_out) && EXTRAS_SAME(in_op) && EXTRAS_SAME(out_op) &&
+              EXTRAS_SAME(in_vec) && EXTRAS_SAME(out_vec) && EXTRAS_SAME(in_lo) && EXTRAS_SAME(in_hi) && EXTRAS_SAME(out_lo) && EXTRAS_SAME(out_hi) &&
+              EXTRAS_SAME(ln_where) && EXTRAS_SAME(ln_eps) && EXTRAS_SAME(ln_gamma) && EXTRAS_SAME(ln_beta),
+              "cosim_mlp_extras_t is PolExtRaw (cosim_poltab.h)");
+#undef EXTRAS_SAME
+
+// cosim_mlp_forward and cosim_mlp_forward_ex (fn: the entry point's name for the messages; ext null: the plain one)
+static int mlp_forward_any(const char* fn, const float* x_dev, int n, int n_layers, const int* dims, const float* const* w_dev,
+                           const float* const* b_dev, const int* act, const float* act_alpha, const PolExtRaw* ext, float clip, float* out_dev,
+                           void* stream) {
+  const auto who = [fn]() { return std::string(fn); };
+  if (!x_dev || !dims || !w_dev || !act || !out_dev || n <= 0) return fail(COSIM_EINVAL, who() + ": bad argument");
+  if (n_layers < 1 || n_layers > MLP_MAXL) return fail(COSIM_EINVAL, who() + ": 1..6 layers");
+  MlpArgs a;
+  memset(&a, 0, sizeof a);
+  int maxd = 0;
+  for (int l = 0; l <= n_layers; l++) {
+    if (dims[l] < 1 || dims[l] > MLP_MAXD) return fail(COSIM_EINVAL, who() + ": layer width outside 1..512");
+    a.dims[l] = dims[l];
+    if (dims[l] > maxd) maxd = dims[l];
+  }
+  for (int l = 0; l < n_layers; l++) {
+    if (!w_dev[l]) return fail(COSIM_EINVAL, who() + ": null weight");
+    a.w[l] = w_dev[l]; a.b[l] = b_dev ? b_dev[l] : nullptr; a.act[l] = act[l]; a.act_alpha[l] = act_alpha ? act_alpha[l] : 1.f;
+  }
+  a.x = x_dev; a.out = out_dev; a.nl = n_layers; a.n = n; a.clip = clip; a.ld = maxd | 1;
+  const size_t lds = (size_t)2 * 32 * a.ld * sizeof(float);
+  if (ext) {
+    const std::string err = check_extras(who(), *ext, n_layers);
+    if (!err.empty()) return fail(COSIM_EINVAL, err);
+  }
+  if (ext && ext_used(*ext, n_layers)) {
+    MlpExt x;
+    memset(&x, 0, sizeof x);
+    x.n_in = ext->n_in; x.n_out = ext->n_out;
+    for (int i = 0; i < ext->n_in; i++) x.in[i] = MlpStage{ext->in_op[i], ext->in_op[i] != 5 ? ext->in_vec[i] : nullptr, ext->in_lo[i], ext->in_hi[i]};
+    for (int i = 0; i < ext->n_out; i++) x.out[i] = MlpStage{ext->out_op[i], ext->out_op[i] != 5 ? ext->out_vec[i] : nullptr, ext->out_lo[i], ext->out_hi[i]};
+    for (int s = 0; s < n_layers; s++)
+      if (ext->ln_where[s]) x.ln[s] = MlpLn{ext->ln_where[s], ext->ln_gamma[s], ext->ln_beta[s], ext->ln_eps[s]};
+    RC_TRY(kernel_needs_lds<mlp_forward_ext_kernel>(lds, fn));
+    hipLaunchKernelGGL(mlp_forward_ext_kernel, dim3((n + 31) / 32), dim3(256), lds, (hipStream_t)stream, a, x);
+  } else {
+    RC_TRY(kernel_needs_lds<mlp_forward_kernel>(lds, fn));
+    hipLaunchKernelGGL(mlp_forward_kernel, dim3((n + 31) / 32), dim3(256), lds, (hipStream_t)stream, a);
+  }
+  HIP_TRY(hipGetLastError());
+  return COSIM_OK;
+}
+
 extern "C" {
 
 // Fused actor MLP (cosim_mlp.hip): out = clip(act_L(... act_1(x W_1^T + b_1) ...)).  All pointers are device pointers; dims has
 // n_layers + 1 entries; act / act_alpha one entry per layer (0 none, 1 relu, 2 tanh, 3 elu, 4 sigmoid, 5 leaky relu).
 int cosim_mlp_forward(const float* x_dev, int n, int n_layers, const int* dims, const float* const* w_dev, const float* const* b_dev,
                       const int* act, const float* act_alpha, float clip, float* out_dev, void* stream) {
-  if (!x_dev || !dims || !w_dev || !act || !out_dev || n <= 0) return fail(COSIM_EINVAL, "cosim_mlp_forward: bad argument");
-  if (n_layers < 1 || n_layers > MLP_MAXL) return fail(COSIM_EINVAL, "cosim_mlp_forward: 1..6 layers");
-  MlpArgs a;
-  memset(&a, 0, sizeof a);
-  int maxd = 0;
-  for (int l = 0; l <= n_layers; l++) {
-    if (dims[l] < 1 || dims[l] > MLP_MAXD) return fail(COSIM_EINVAL, "cosim_mlp_forward: layer width outside 1..512");
-    a.dims[l] = dims[l];
-    if (dims[l] > maxd) maxd = dims[l];
-  }
-  for (int l = 0; l < n_layers; l++) {
-    if (!w_dev[l]) return fail(COSIM_EINVAL, "cosim_mlp_forward: null weight");
-    a.w[l] = w_dev[l]; a.b[l] = b_dev ? b_dev[l] : nullptr; a.act[l] = act[l]; a.act_alpha[l] = act_alpha ? act_alpha[l] : 1.f;
-  }
-  a.x = x_dev; a.out = out_dev; a.nl = n_layers; a.n = n; a.clip = clip; a.ld = maxd | 1;
-  const size_t lds = (size_t)2 * 32 * a.ld * sizeof(float);
-  RC_TRY(kernel_needs_lds<mlp_forward_kernel>(lds, "cosim_mlp_forward"));
-  hipLaunchKernelGGL(mlp_forward_kernel, dim3((n + 31) / 32), dim3(256), lds, (hipStream_t)stream, a);
-  HIP_TRY(hipGetLastError());
-  return COSIM_OK;
+  return mlp_forward_any("cosim_mlp_forward", x_dev, n, n_layers, dims, w_dev, b_dev, act, act_alpha, nullptr, clip, out_dev, stream);
+}
+
+// The same with an extended actor's stages and LayerNorms (cosim_mlp.hip: mlp_forward_ext_kernel); null or empty extras: the launch above.
+int cosim_mlp_forward_ex(const float* x_dev, int n, int n_layers, const int* dims, const float* const* w_dev, const float* const* b_dev,
+                         const int* act, const float* act_alpha, const cosim_mlp_extras_t* extras, float clip, float* out_dev, void* stream) {
+  return mlp_forward_any("cosim_mlp_forward_ex", x_dev, n, n_layers, dims, w_dev, b_dev, act, act_alpha, reinterpret_cast<const PolExtRaw*>(extras),
+                         clip, out_dev, stream);
 }
 
 // Policy table (cosim_poltab.h, mlp_grouped_kernel): K actors over one fleet, one launch per evaluation.  create checks and packs the
 // host arrays, builds the tile list and uploads everything once; forward only launches.
-int cosim_policy_table_create(int n_policies, const int* n_layers, const int* dims, const int* act, const float* act_alpha,
-                              const float* const* w_host, const float* const* b_host, int n, const int* policy_of_row, int n_ranges,
-                              const int* ranges, cosim_policy_table** out) {
-  if (!out) return fail(COSIM_EINVAL, "cosim_policy_table_create: null argument");
+static int policy_table_make(const char* fn, const PolRaw& raw, cosim_policy_table** out) {
+  if (!out) return fail(COSIM_EINVAL, std::string(fn) + ": null argument");
   *out = nullptr;
-  const PolRaw raw = {n_policies, n_layers, dims, act, act_alpha, w_host, b_host, n, policy_of_row, n_ranges, ranges};
-  const PolShape shape = validate_policy_table(raw);
+  const PolShape shape = validate_policy_table(raw, fn);
   if (!shape.err.empty()) return fail(COSIM_EINVAL, shape.err);
   const PolImage im = pack_policy_image(raw);
   cosim_policy_table* p = new cosim_policy_table;
-  p->K = n_policies; p->ld = shape.maxd | 1;
-  p->por.assign(policy_of_row, policy_of_row + n); p->ranges.assign(ranges, ranges + 2 * n_ranges);
-  int rc = kernel_needs_lds<mlp_grouped_kernel>((size_t)2 * 32 * p->ld * sizeof(float), "cosim_policy_table_create");
+  p->K = raw.K; p->ld = shape.maxd | 1;
+  p->por.assign(raw.policy_of_row, raw.policy_of_row + raw.n); p->ranges.assign(raw.ranges, raw.ranges + 2 * raw.n_ranges);
+  const size_t lds = (size_t)2 * 32 * p->ld * sizeof(float);
+  int rc = im.ext.empty() ? kernel_needs_lds<mlp_grouped_kernel>(lds, fn) : kernel_needs_lds<mlp_grouped_ext_kernel>(lds, fn);
   if (!rc) rc = table_upload(*p, im.words, im.desc.data(), im.desc.size() * sizeof(PolDesc), (void**)&p->d_desc,
-                             build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges));
+                             build_policy_tiles(raw.policy_of_row, raw.K, raw.ranges, raw.n_ranges));
+  if (!rc && !im.ext.empty()) rc = upload_words(&p->d_ext, im.ext.data(), im.ext.size() * sizeof(PolExt));
   if (rc) { cosim_policy_table_destroy(p); return rc; }
   *out = p;
   return COSIM_OK;
+}
+
+int cosim_policy_table_create(int n_policies, const int* n_layers, const int* dims, const int* act, const float* act_alpha,
+                              const float* const* w_host, const float* const* b_host, int n, const int* policy_of_row, int n_ranges,
+                              const int* ranges, cosim_policy_table** out) {
+  const PolRaw raw = {n_policies, n_layers, dims, act, act_alpha, w_host, b_host, n, policy_of_row, n_ranges, ranges};
+  return policy_table_make("cosim_policy_table_create", raw, out);
+}
+
+int cosim_policy_table_create_ex(int n_policies, const int* n_layers, const int* dims, const int* act, const float* act_alpha,
+                                 const float* const* w_host, const float* const* b_host, const cosim_mlp_extras_t* extras, int n,
+                                 const int* policy_of_row, int n_ranges, const int* ranges, cosim_policy_table** out) {
+  const PolRaw raw = {n_policies, n_layers, dims, act, act_alpha, w_host, b_host, n, policy_of_row, n_ranges, ranges,
+                      reinterpret_cast<const PolExtRaw*>(extras)};
+  return policy_table_make("cosim_policy_table_create_ex", raw, out);
 }
 
 // range: an index into the ranges given to create, or -1 for all of them.  No allocation, no host read of device memory and no
@@ -1319,7 +1381,9 @@ static int policy_table_launch(cosim_policy_table* p, const float* x_dev, float*
   a.x = x_dev; a.out = out_dev; a.image = p->d_image; a.desc = p->d_desc; a.rows = p->d_rows; a.tiles = p->d_tiles;
   a.tile_first = range < 0 ? 0 : p->tile_span[2 * range]; a.ld = p->ld; a.clip = clip;
   const int tile_count = range < 0 ? p->n_tiles : p->tile_span[2 * range + 1];
-  hipLaunchKernelGGL(mlp_grouped_kernel, dim3(tile_count), dim3(256), (size_t)2 * 32 * p->ld * sizeof(float), s, a);
+  const size_t lds = (size_t)2 * 32 * p->ld * sizeof(float);
+  if (p->d_ext) hipLaunchKernelGGL(mlp_grouped_ext_kernel, dim3(tile_count), dim3(256), lds, s, a, (const PolExt*)p->d_ext);
+  else hipLaunchKernelGGL(mlp_grouped_kernel, dim3(tile_count), dim3(256), lds, s, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
 }
@@ -1346,7 +1410,7 @@ int cosim_policy_table_lists(cosim_policy_table* p, int range, int* rows_host, i
 
 int cosim_policy_table_destroy(cosim_policy_table* p) {
   if (!p) return COSIM_OK;
-  (void)hipFree(p->d_desc);
+  (void)hipFree(p->d_desc); (void)hipFree(p->d_ext);
   table_free(*p);
   delete p;
   return COSIM_OK;

@@ -52,12 +52,108 @@ struct MlpLayer {
   float alpha;
 };
 
+// ---- what an EXTENDED actor adds to the chain (cosim_mlp_forward_ex, cosim_policy_table_create_ex): elementwise stages on the
+// observation and on the action, and LayerNorm behind a layer.  The plain kernels compile none of it (mlp_layers<false>).
+// One stage item: y = y (op) v[column] for op 1 add, 2 sub, 3 mul, 4 div; 5: clamp to [lo, hi] (an absent bound is -+inf).
+struct MlpStage { int op; const float* v; float lo, hi; };
+// LayerNorm of slot s (0: the observation, l + 1: layer l's output, width dims[s]): where 0 none, 1 ahead of the layer's activation,
+// 2 behind it
+struct MlpLn { int where; const float *g, *b; float eps; };
+// an extended actor as cosim_mlp_forward_ex launches it: every vector a device pointer
+struct MlpExt {
+  int n_in, n_out;
+  MlpStage in[POL_MAXS], out[POL_MAXS];
+  MlpLn ln[POL_MAXL + 1];
+  __device__ MlpStage in_item(int i) const { return in[i]; }
+  __device__ MlpStage out_item(int i) const { return out[i]; }
+  __device__ MlpLn ln_of(int s) const { return ln[s]; }
+};
+// the same out of a table's record: word offsets into the table's image
+struct PolExtView {
+  const PolExt* E;
+  const float* image;
+  const int n_out;
+  __device__ MlpStage item(const PolStage& s) const { return MlpStage{s.op, s.off >= 0 ? image + s.off : nullptr, s.lo, s.hi}; }
+  __device__ MlpStage in_item(int i) const { return item(E->in[i]); }
+  __device__ MlpStage out_item(int i) const { return item(E->out[i]); }
+  __device__ MlpLn ln_of(int s) const {
+    return MlpLn{E->ln_where[s], E->ln_g[s] >= 0 ? image + E->ln_g[s] : nullptr, E->ln_b[s] >= 0 ? image + E->ln_b[s] : nullptr, E->ln_eps[s]};
+  }
+};
+struct NoExt {};
+
+// One stage item on one word: exactly the ONE fp32 operation the ONNX node names, so a stage gives the interpreter's bits.  No
+// contraction (a Mul followed by an Add must not become an FMA), division correctly rounded, the clamp two compares and selects as
+// MlpArgs::clip (NaN stays NaN, +-inf becomes the bound).
+__device__ __forceinline__ float mlp_stage_op(float y, int op, float c, float lo, float hi) {
+#pragma clang fp contract(off)
+  switch (op) {
+    case 1: return y + c;
+    case 2: return y - c;
+    case 3: return y * c;
+    case 4: return __fdiv_rn(y, c);
+    case 5: return y < lo ? lo : (y > hi ? hi : y);
+    default: return y;
+  }
+}
+
+// The input stage on the word of column c as it is loaded into the tile: the items in listed order.
+template <class Ext>
+__device__ __forceinline__ float mlp_input_stage(float v, int c, int n_in, const Ext& X) {
+#pragma unroll
+  for (int i = 0; i < POL_MAXS; i++)
+    if (i < n_in) {
+      const MlpStage s = X.in_item(i);
+      v = mlp_stage_op(v, s.op, s.v != nullptr ? s.v[c] : 0.f, s.lo, s.hi);
+    }
+  return v;
+}
+
+// LayerNorm over the first W columns of every row of one 32-row tile, in place, then the activation `act` (0: none); all 256 threads,
+// the caller synchronises on both sides.  Eight lanes per row (row = t >> 3, s = t & 7); lane s takes the columns 32 j + 4 s + k
+// (k = 0..3), j and k ascending, and the eight partial sums meet in a butterfly over lane ^ 1, ^ 2, ^ 4 -- every lane of the row ends
+// with the same bits (a + b = b + a).  Two passes: the mean, then the mean of squared deviations.  A row's statistics are a function of
+// that row's W words alone: not of the tile row, the other rows, the launch's size or its kernel.  LDS: a ds_read_b32 is served in
+// groups of 32 lanes = 4 rows x 8 lanes over 32 banks; with the columns 4 s + k the bank is (r ld + 4 s + k) mod 32, and r ld mod 4
+// differs for the four rows because ld is odd: no conflict at any width.
+__device__ __forceinline__ void mlp_layernorm(float* tl, int ld, int W, const float* g, const float* b, float eps, int act, float alpha) {
+  const int t = threadIdx.x, s4 = 4 * (t & 7);
+  float* r = tl + (t >> 3) * ld;
+  float sum = 0.f;
+  for (int c0 = s4; c0 < W; c0 += 32)
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (c0 + k < W) sum += r[c0 + k];
+  sum += __shfl_xor(sum, 1); sum += __shfl_xor(sum, 2); sum += __shfl_xor(sum, 4);
+  const float mean = sum / (float)W;
+  float sq = 0.f;
+  for (int c0 = s4; c0 < W; c0 += 32)
+#pragma unroll
+    for (int k = 0; k < 4; k++)
+      if (c0 + k < W) { const float d = r[c0 + k] - mean; sq += d * d; }
+  sq += __shfl_xor(sq, 1); sq += __shfl_xor(sq, 2); sq += __shfl_xor(sq, 4);
+  const float rstd = 1.f / sqrtf(sq / (float)W + eps);
+  for (int c0 = s4; c0 < W; c0 += 32)
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const int c = c0 + k;
+      if (c < W) {
+        const float y = (r[c] - mean) * rstd * g[c] + (b != nullptr ? b[c] : 0.f);
+        r[c] = mlp_act(y, act, alpha);
+      }
+    }
+}
+
 // The layer loop of one 32-env tile whose input rows stand in tile 0 of `lds` ([2][32][ld]; the caller has synchronised).  Both
 // kernels below run it.  layer_of(L): layer L; out_row(r): the row of `out` that tile row r is written to, < 0 for none.  An output
 // element is a chain of MFMA steps over k whose operands are the env's own inputs and the weights: which tile row the env sits in,
 // and what the other rows hold, does not enter it.
-template <class LayerOf, class RowOf>
-__device__ __forceinline__ void mlp_layers(float* lds, int ld, int nl, float clip, float* out, LayerOf layer_of, RowOf out_row) {
+// EXT (X: MlpExt or PolExtView; the plain kernels pass NoExt and compile what they always did): a layer with LayerNorm ahead of its
+// activation stores the pre-activation and mlp_layernorm applies norm and activation to the finished tile; with LayerNorm behind it
+// the epilogue is unchanged and the pass only normalises; the last layer's epilogue runs the output stage between the activation and
+// the clip.  The two ping-pong tiles are all the LDS there is.
+template <bool EXT, class LayerOf, class RowOf, class Ext>
+__device__ __forceinline__ void mlp_layers(float* lds, int ld, int nl, float clip, float* out, LayerOf layer_of, RowOf out_row, const Ext& X) {
   typedef float f32x16 __attribute__((ext_vector_type(16)));
   auto tile = [&](int which, int r, int c) -> float& { return lds[(which * 32 + r) * ld + c]; };
   const int t = threadIdx.x, l = t & 63, wave = t >> 6;
@@ -69,9 +165,28 @@ __device__ __forceinline__ void mlp_layers(float* lds, int ld, int nl, float cli
     const float* Bv = ly.Bv;
     const bool last = L == nl - 1;
     const int row_a = l & 31, kk = l >> 5;
+    MlpLn ln = {0, nullptr, nullptr, 0.f};
+    int n_out = 0;
+    if constexpr (EXT) {
+      if (!last) ln = X.ln_of(L + 1);
+      else n_out = X.n_out;
+    }
     for (int ti = wave; ti * 32 < O; ti += 4) {
       const int o0 = ti * 32, col = o0 + (l & 31);
       const float bias = (Bv != nullptr && col < O) ? Bv[col] : 0.f;
+      MlpStage so[POL_MAXS];
+      float sc[POL_MAXS];
+      if constexpr (EXT) {
+#pragma unroll
+        for (int i = 0; i < POL_MAXS; i++) {
+          so[i] = MlpStage{0, nullptr, 0.f, 0.f};
+          sc[i] = 0.f;
+          if (i < n_out) {
+            so[i] = X.out_item(i);
+            if (so[i].v != nullptr && col < O) sc[i] = so[i].v[col];
+          }
+        }
+      }
       f32x16 acc;
 #pragma unroll
       for (int v = 0; v < 16; v++) acc[v] = bias;
@@ -94,8 +209,15 @@ __device__ __forceinline__ void mlp_layers(float* lds, int ld, int nl, float cli
 #pragma unroll
       for (int v = 0; v < 16; v++) {
         const int row = (v & 3) + 8 * (v >> 2) + 4 * (l >> 5);
-        float y = mlp_act(acc[v], ly.act, ly.alpha);
+        float y;
+        if constexpr (EXT) y = ln.where == 1 ? acc[v] : mlp_act(acc[v], ly.act, ly.alpha);
+        else y = mlp_act(acc[v], ly.act, ly.alpha);
         if (last) {
+          if constexpr (EXT) {
+#pragma unroll
+            for (int i = 0; i < POL_MAXS; i++)
+              if (i < n_out) y = mlp_stage_op(y, so[i].op, sc[i], so[i].lo, so[i].hi);
+          }
           if (clip > 0.f) y = y < -clip ? -clip : (y > clip ? clip : y);
           const long long orow = out_row(row);
           if (col < O && orow >= 0) out[(size_t)orow * O + col] = y;
@@ -105,6 +227,22 @@ __device__ __forceinline__ void mlp_layers(float* lds, int ld, int nl, float cli
     }
     __syncthreads();
     cur ^= 1;
+    if constexpr (EXT) {
+      if (ln.where != 0) {   // uniform: the tile the layer has just finished, all 32 rows of it
+        mlp_layernorm(lds + cur * 32 * ld, ld, O, ln.g, ln.b, ln.eps, ln.where == 1 ? ly.act : 0, ly.alpha);
+        __syncthreads();
+      }
+    }
+  }
+}
+
+// The observation's own LayerNorm (slot 0) on the input tile, behind the input stage; the caller has synchronised and does again.
+template <class Ext>
+__device__ __forceinline__ void mlp_input_layernorm(float* lds, int ld, int I, const Ext& X) {
+  const MlpLn ln = X.ln_of(0);
+  if (ln.where != 0) {
+    mlp_layernorm(lds, ld, I, ln.g, ln.b, ln.eps, 0, 1.f);
+    __syncthreads();
   }
 }
 
@@ -122,9 +260,28 @@ __global__ __launch_bounds__(256) void mlp_forward_kernel(MlpArgs A) {
     }
   }
   __syncthreads();
-  mlp_layers(mlp_lds, ld, A.nl, A.clip, A.out,
-             [&](int L) { return MlpLayer{A.w[L], A.b[L], A.dims[L], A.dims[L + 1], A.act[L], A.act_alpha[L]}; },
-             [&](int row) -> long long { return n0 + row < A.n ? (long long)(n0 + row) : -1; });
+  mlp_layers<false>(mlp_lds, ld, A.nl, A.clip, A.out,
+                    [&](int L) { return MlpLayer{A.w[L], A.b[L], A.dims[L], A.dims[L + 1], A.act[L], A.act_alpha[L]}; },
+                    [&](int row) -> long long { return n0 + row < A.n ? (long long)(n0 + row) : -1; }, NoExt{});
+}
+
+// The extended instantiation of the kernel above (cosim_mlp_forward_ex): the input stage on every word of a real row as it is loaded
+// (the rows behind n stay zero), the observation's LayerNorm, then the extended layer loop.
+__global__ __launch_bounds__(256) void mlp_forward_ext_kernel(MlpArgs A, MlpExt X) {
+  extern __shared__ float mlp_lds[];   // [2][32][ld]
+  const int ld = A.ld;
+  const int t = threadIdx.x;
+  const int n0 = blockIdx.x * 32;
+  const int I = A.dims[0];
+  for (int e = t; e < 32 * I; e += 256) {
+    const int r = e / I, c = e - r * I;
+    mlp_lds[r * ld + c] = (n0 + r < A.n) ? mlp_input_stage(A.x[(size_t)(n0 + r) * I + c], c, X.n_in, X) : 0.f;
+  }
+  __syncthreads();
+  mlp_input_layernorm(mlp_lds, ld, I, X);
+  mlp_layers<true>(mlp_lds, ld, A.nl, A.clip, A.out,
+                   [&](int L) { return MlpLayer{A.w[L], A.b[L], A.dims[L], A.dims[L + 1], A.act[L], A.act_alpha[L]}; },
+                   [&](int row) -> long long { return n0 + row < A.n ? (long long)(n0 + row) : -1; }, X);
 }
 
 // K policies over one fleet in one launch (cosim_policy_table_forward; the table is made and checked by cosim_poltab.h): a workgroup
@@ -162,12 +319,40 @@ __global__ __launch_bounds__(256) void mlp_grouped_kernel(PolTabArgs A) {
     }
   }
   __syncthreads();
-  mlp_layers(mlp_lds, ld, D->nl, A.clip, A.out,
-             [&](int L) {
-               const int bo = D->boff[L];
-               return MlpLayer{A.image + D->woff[L], bo >= 0 ? A.image + bo : nullptr, D->dims[L], D->dims[L + 1], D->act[L], D->alpha[L]};
-             },
-             [&](int row) -> long long { return tile_row[row]; });
+  mlp_layers<false>(mlp_lds, ld, D->nl, A.clip, A.out,
+                    [&](int L) {
+                      const int bo = D->boff[L];
+                      return MlpLayer{A.image + D->woff[L], bo >= 0 ? A.image + bo : nullptr, D->dims[L], D->dims[L + 1], D->act[L], D->alpha[L]};
+                    },
+                    [&](int row) -> long long { return tile_row[row]; }, NoExt{});
+}
+
+// The extended instantiation of the grouped kernel: a table in which at least one policy has extras runs it for all of its tiles
+// (`ext`: one record per policy, all zero for a plain one, which then gets the bits of the plain kernel: the same MFMA chains).
+__global__ __launch_bounds__(256) void mlp_grouped_ext_kernel(PolTabArgs A, const PolExt* ext) {
+  extern __shared__ float mlp_lds[];   // [2][32][ld]
+  __shared__ int tile_row[32];
+  const int ld = A.ld;
+  const int t = threadIdx.x;
+  const PolTile T = A.tiles[A.tile_first + blockIdx.x];
+  if (T.count == 0) return;
+  const PolDesc* D = A.desc + T.policy;
+  const PolExtView X = {ext + T.policy, A.image, ext[T.policy].n_out};
+  if (t < 32) tile_row[t] = t < T.count ? A.rows[T.start + t] : -1;
+  __syncthreads();
+  const int I = D->dims[0], n_in = X.E->n_in;
+  for (int e = t; e < 32 * I; e += 256) {
+    const int r = e / I, c = e - r * I, src = tile_row[r];
+    mlp_lds[r * ld + c] = src >= 0 ? mlp_input_stage(A.x[(size_t)src * I + c], c, n_in, X) : 0.f;
+  }
+  __syncthreads();
+  mlp_input_layernorm(mlp_lds, ld, I, X);
+  mlp_layers<true>(mlp_lds, ld, D->nl, A.clip, A.out,
+                   [&](int L) {
+                     const int bo = D->boff[L];
+                     return MlpLayer{A.image + D->woff[L], bo >= 0 ? A.image + bo : nullptr, D->dims[L], D->dims[L + 1], D->act[L], D->alpha[L]};
+                   },
+                   [&](int row) -> long long { return tile_row[row]; }, X);
 }
 
 // The lists of a ROTATING table, rebuilt on the device ahead of every grouped launch (cosim_policy_table_forward_rotating; rule and
@@ -456,12 +641,12 @@ __global__ __launch_bounds__(256) void lstm_actor_grouped_kernel(RecTabArgs A) {
   if (ne > 0) {
     // the last encoder layer reads tile (ne - 1) & 1; its output rows go to the other tile, [32][I], and from there into [x_enc | h]
     float* enc = rec_lds + (ne & 1) * 32 * ld;
-    mlp_layers(rec_lds, ld, ne, 0.f, enc,
+    mlp_layers<false>(rec_lds, ld, ne, 0.f, enc,
                [&](int L) {
                  const int bo = D->eboff[L];
                  return MlpLayer{A.image + D->ewoff[L], bo >= 0 ? A.image + bo : nullptr, D->edims[L], D->edims[L + 1], D->eact[L], D->ealpha[L]};
                },
-               [&](int row) -> long long { return row; });
+               [&](int row) -> long long { return row; }, NoExt{});
     for (int e = t; e < 32 * I; e += 256) {
       const int r = e / I, k = e - r * I;
       xh[r * ldx + k] = enc[r * I + k];
@@ -492,12 +677,12 @@ __global__ __launch_bounds__(256) void lstm_actor_grouped_kernel(RecTabArgs A) {
     }
   }
   __syncthreads();
-  mlp_layers(rec_lds, ld, D->nh, A.clip, A.out,
+  mlp_layers<false>(rec_lds, ld, D->nh, A.clip, A.out,
              [&](int L) {
                const int bo = D->hboff[L];
                return MlpLayer{A.image + D->hwoff[L], bo >= 0 ? A.image + bo : nullptr, D->hdims[L], D->hdims[L + 1], D->hact[L], D->halpha[L]};
              },
-             [&](int row) -> long long { return tile_row[row]; });
+             [&](int row) -> long long { return tile_row[row]; }, NoExt{});
 }
 
 // Reporter side of the loop (core/reporter.py:210-218, 429-442, 506-508): count / sum / sum of squares per metric column over

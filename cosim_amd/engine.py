@@ -140,6 +140,11 @@ _ABI_ROWS = (
 )
 ABI = {name: (restype, argtypes) for name, restype, argtypes in _ABI_ROWS}
 EXPORTS = list(ABI)
+# include/cosim_actor.h, the same way (tests/test_actor_graph_host.py holds it against that header)
+ABI_ACTOR = {
+    "cosim_mlp_forward_ex": (_ci, [_vp, _ci, _ci] + [_vp] * 6 + [_cf, _vp, _vp]),
+    "cosim_policy_table_create_ex": (_ci, [_ci] + [_vp] * 7 + [_ci, _vp, _ci, _vp, _pvp]),
+}
 
 _lib = None
 
@@ -156,7 +161,7 @@ def load_library():
         raise RuntimeError(f"{LIB_PATH} is missing: run `python -c 'import __graft_entry__ as g; g.build()'` "
                            "(the HIP engine has no CPU fallback)")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in ABI.items():
+    for name, (restype, argtypes) in {**ABI, **ABI_ACTOR}.items():
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     if L.cosim_model_sizeof() != ctypes.sizeof(CosimModel):

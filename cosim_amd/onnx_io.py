@@ -1,6 +1,6 @@
 """ONNX files without the ``onnx`` package or onnxruntime (neither is available in this build): a small protobuf wire-format decoder
-(``read_onnx``), a tiny interpreter over the operator subset RL policy exports use (``OnnxGraph``: Gemm / MatMul / Add / activations /
-LSTM / shape glue, on torch tensors) and the writer the tests and the synthetic policies use (``write_onnx``, ``write_random_mlp``,
+(``read_onnx``), a tiny interpreter over the operator subset RL policy exports use (``OnnxGraph``: Gemm / MatMul / elementwise / activations /
+LayerNormalization and its ReduceMean / Pow / Sqrt spelling / LSTM / shape glue, on torch tensors) and the writer the tests and the synthetic policies use (``write_onnx``, ``write_random_mlp``,
 ``write_random_lstm``, ``write_recurrent_actor``).  ``policy.py`` builds the policies and the tables on top of it and re-exports
 every name of this module that was imported from there.
 """
@@ -194,6 +194,19 @@ class OnnxGraph:
                 lo = x[1] if len(x) > 1 and x[1] is not None else a.get("min")
                 hi = x[2] if len(x) > 2 and x[2] is not None else a.get("max")
                 y = t.clamp(x[0], min=None if lo is None else float(lo), max=None if hi is None else float(hi))
+            elif op == "LayerNormalization":
+                ax = a.get("axis", -1) % x[0].dim()
+                y = t.nn.functional.layer_norm(x[0], tuple(x[0].shape[ax:]), x[1], x[2] if len(x) > 2 else None, float(a.get("epsilon", 1e-5)))
+            elif op == "ReduceMean":
+                axes = a.get("axes")
+                if axes is None and len(x) > 1 and x[1] is not None:
+                    axes = [int(v) for v in x[1].tolist()]
+                keep = bool(a.get("keepdims", 1))
+                y = x[0].mean(dim=tuple(axes) if axes else tuple(range(x[0].dim())), keepdim=keep)
+            elif op == "Pow":
+                y = t.pow(x[0], x[1])
+            elif op == "Sqrt":
+                y = t.sqrt(x[0])
             elif op == "Flatten":
                 ax = a.get("axis", 1)
                 y = x[0].reshape(int(np.prod(x[0].shape[:ax])) if ax else 1, -1)
@@ -393,21 +406,45 @@ def write_random_lstm(path: str, state_dim: int, action_dim: int, hidden: int = 
 
 
 def write_random_mlp(path: str, state_dim: int, action_dim: int, hidden=(256, 128), seed: int = 0, activation: str = "Elu",
-                     bias_scale: float = 0.0):
+                     bias_scale: float = 0.0, normaliser: bool = False, layer_norm: bool = False, output_scale=None):
     """A random-weight actor with the usual export shape (Gemm + activation ... Gemm): stands in for the missing policy files.
     Biases are ``bias_scale * standard_normal`` from a generator of their own: the default 0 writes all-zero biases and exactly the
-    weights (and bytes) earlier versions wrote for the same seed."""
+    weights (and bytes) earlier versions wrote for the same seed.
+
+    What trained actors carry besides (``_actor_graph``), each from a generator of its own, so the weights stay those of the seed and
+    the defaults write the bytes they always did: ``normaliser`` -- ``Clip((obs - mean) / std, -5, 5)`` ahead of the first layer (mean
+    N(0, 1), std uniform in [0.5, 2]); ``layer_norm`` -- ``LayerNormalization`` between every hidden Gemm and its activation (scale 1 +
+    0.3 N, bias 0.2 N); ``output_scale`` (a number or one per action) -- ``Tanh`` then ``Mul`` behind the last Gemm."""
     rng = np.random.default_rng(seed)
     brng = np.random.default_rng([seed, 1])
     dims = [state_dim, *hidden, action_dim]
     nodes, init, x = [], {}, "obs"
+    if normaliser:
+        nrng = np.random.default_rng([seed, 3])
+        init["obs_mean"] = nrng.standard_normal(state_dim).astype(np.float32)
+        init["obs_std"] = nrng.uniform(0.5, 2.0, state_dim).astype(np.float32)
+        init["obs_lo"], init["obs_hi"] = np.array(-5.0, np.float32), np.array(5.0, np.float32)
+        nodes += [{"op": "Sub", "inputs": ["obs", "obs_mean"], "outputs": ["obs_c"]}, {"op": "Div", "inputs": ["obs_c", "obs_std"], "outputs": ["obs_n"]},
+                  {"op": "Clip", "inputs": ["obs_n", "obs_lo", "obs_hi"], "outputs": ["obs_k"]}]
+        x = "obs_k"
+    lrng = np.random.default_rng([seed, 4])
     for li in range(len(dims) - 1):
         w = (rng.standard_normal((dims[li + 1], dims[li])) / np.sqrt(dims[li])).astype(np.float32)
         b = (bias_scale * brng.standard_normal(dims[li + 1])).astype(np.float32) if bias_scale else np.zeros(dims[li + 1], dtype=np.float32)
         init[f"w{li}"], init[f"b{li}"] = w, b
-        y = f"h{li}" if li < len(dims) - 2 else "actions"
-        nodes.append({"op": "Gemm", "inputs": [x, f"w{li}", f"b{li}"], "outputs": [y + "_lin" if li < len(dims) - 2 else y], "attrs": {"transB": 1}})
-        if li < len(dims) - 2:
-            nodes.append({"op": activation, "inputs": [y + "_lin"], "outputs": [y]})
+        hidden_layer = li < len(dims) - 2
+        y = f"h{li}" if hidden_layer else "actions"
+        lin = y + "_lin" if hidden_layer or output_scale is not None else y
+        nodes.append({"op": "Gemm", "inputs": [x, f"w{li}", f"b{li}"], "outputs": [lin], "attrs": {"transB": 1}})
+        if hidden_layer:
+            if layer_norm:
+                init[f"g{li}"] = (1.0 + 0.3 * lrng.standard_normal(dims[li + 1])).astype(np.float32)
+                init[f"beta{li}"] = (0.2 * lrng.standard_normal(dims[li + 1])).astype(np.float32)
+                nodes.append({"op": "LayerNormalization", "inputs": [lin, f"g{li}", f"beta{li}"], "outputs": [y + "_ln"], "attrs": {"axis": -1, "epsilon": 1e-5}})
+                lin = y + "_ln"
+            nodes.append({"op": activation, "inputs": [lin], "outputs": [y]})
+        elif output_scale is not None:
+            init["action_scale"] = np.broadcast_to(np.asarray(output_scale, np.float32), (action_dim,)).copy()
+            nodes += [{"op": "Tanh", "inputs": [lin], "outputs": ["actions_t"]}, {"op": "Mul", "inputs": ["actions_t", "action_scale"], "outputs": [y]}]
         x = y
     write_onnx(path, nodes, init, ["obs"], ["actions"])

@@ -68,6 +68,219 @@ def _mlp_chain(model: dict):
     return layers
 
 
+_STAGE_OP = {"Add": 1, "Sub": 2, "Mul": 3, "Div": 4, "Clip": 5}      # the op codes of cosim_mlp_extras_t (include/cosim_actor.h)
+
+
+def _actor_graph(model: dict):
+    """The graph as an EXTENDED actor -- what ``cosim_mlp_forward_ex`` and ``cosim_policy_table_create_ex`` evaluate in one launch:
+
+        actor  := input{0..4} [LN] layer{1..6} output{0..4}
+        input  := Sub(x, c) | Div(x, c) | Add | Mul (either operand order) | Clip(x, lo, hi)
+        layer  := linear [LN] [act]  |  linear act LN            (the last layer carries no LN)
+        linear := Gemm(transB=1, alpha=beta=1)  |  MatMul(x, Wt) [Add(., b)]
+        output := Mul | Add | Sub(y, c) | Div(y, c) | Clip(y, lo, hi)
+
+    ``c``: an fp32 initialiser or ``Constant`` output of shape ``[]``, ``[1]``, ``[W]`` or ``[1, W]``; ``LN``: ``LayerNormalization`` over the
+    last axis with a scale; activations: those of ``_ACT``; widths 1..512.  Returns ``(description, None)`` or ``(None, reason)`` with
+    the reason naming the node.  ``description``: ``layers`` -- what ``_mlp_chain`` returns (for every graph it accepts: exactly that,
+    and nothing else below); ``input`` / ``output`` -- stage items ``(code, vector [W] or None, lo, hi)``; ``ln`` -- ``{slot: (where, scale,
+    bias or None, eps)}``, slot 0 the observation, ``l + 1`` layer ``l``, where 1 ahead of the activation and 2 behind it."""
+    if len(model["inputs"]) != 1 or len(model["outputs"]) != 1:
+        return None, f"{len(model['inputs'])} graph inputs and {len(model['outputs'])} outputs, not one of each"
+    init = dict(model["init"])
+    body = []
+    for n in model["nodes"]:
+        if n["op"] == "Constant" and isinstance(n["attrs"].get("value"), np.ndarray):
+            init[n["outputs"][0]] = n["attrs"]["value"]
+        else:
+            body.append(n)
+    used = {name for n in body for name in n["inputs"]} | set(model["outputs"])
+
+    def tag(n):
+        return f"node '{n['op']}' -> '{n['outputs'][0] if n['outputs'] else ''}'"
+
+    def stage_item(n, cur):
+        """A stage item on ``cur``: ``((code, constant or None, lo, hi), None)`` or ``(None, reason)``."""
+        ins = [i for i in n["inputs"]]
+        if n["op"] == "Clip":
+            if not ins or ins[0] != cur:
+                return None, f"{tag(n)} does not clip the tensor before it"
+            bounds = []
+            for k, key in ((1, "min"), (2, "max")):
+                v = n["attrs"].get(key)
+                if len(ins) > k and ins[k]:
+                    if ins[k] not in init or np.asarray(init[ins[k]]).size != 1:
+                        return None, f"{tag(n)}: bound '{ins[k]}' is not a constant scalar"
+                    if np.asarray(init[ins[k]]).dtype != np.float32:
+                        return None, f"{tag(n)}: bound '{ins[k]}' is {np.asarray(init[ins[k]]).dtype}, not fp32"
+                    v = float(np.asarray(init[ins[k]]).ravel()[0])
+                bounds.append(v)
+            lo, hi = (-np.inf if bounds[0] is None else float(bounds[0])), (np.inf if bounds[1] is None else float(bounds[1]))
+            return (5, None, lo, hi), None
+        if len(ins) != 2 or cur not in ins:
+            return None, f"{tag(n)} does not take the tensor before it and a constant"
+        other = ins[1] if ins[0] == cur else ins[0]
+        if n["op"] in ("Sub", "Div") and ins[0] != cur:
+            return None, f"{tag(n)}: {'c - x' if n['op'] == 'Sub' else 'c / x'} (the constant on the left) is outside the fused subset"
+        if other not in init:
+            return None, f"{tag(n)}: operand '{other}' is not a constant"
+        c = np.asarray(init[other])
+        if c.dtype != np.float32:
+            return None, f"{tag(n)}: constant '{other}' is {c.dtype}, not fp32"
+        return (_STAGE_OP[n["op"]], c, 0.0, 0.0), None
+
+    def widen(items, W, what):
+        """The items' constants broadcast to vectors ``[W]``: ``(items, None)`` or ``(None, reason)``."""
+        out = []
+        for code, c, lo, hi in items:
+            if c is not None:
+                if c.shape not in ((), (1,), (W,), (1, W)):
+                    return None, f"a constant of shape {c.shape} in the {what} stage, whose width is {W}"
+                c = np.ascontiguousarray(np.broadcast_to(c.reshape(-1), (W,)), dtype=np.float32)
+            out.append((code, c, lo, hi))
+        return out, None
+
+    def layer_norm(n, cur, W):
+        a, ins = n["attrs"], n["inputs"]
+        if not ins or ins[0] != cur:
+            return None, f"{tag(n)} does not normalise the tensor before it"
+        if a.get("axis", -1) not in (-1, 1):
+            return None, f"{tag(n)}: axis {a.get('axis')} (the last axis only)"
+        if len(ins) < 2 or not ins[1]:
+            return None, f"{tag(n)}: LayerNormalization without scale"
+        if any(o and o in used for o in n["outputs"][1:]):
+            return None, f"{tag(n)}: its Mean / InvStdDev outputs are used"
+        g = init.get(ins[1])
+        b = init.get(ins[2]) if len(ins) > 2 and ins[2] else None
+        if g is None or (len(ins) > 2 and ins[2] and b is None):
+            return None, f"{tag(n)}: scale or bias is not an initialiser"
+        if g.dtype != np.float32 or (b is not None and b.dtype != np.float32):
+            return None, f"{tag(n)}: scale or bias is not fp32"
+        if W is not None and (g.shape != (W,) or (b is not None and b.shape != (W,))):
+            return None, f"{tag(n)}: scale {g.shape} / bias {None if b is None else b.shape} for width {W}"
+        eps = float(np.float32(a.get("epsilon", 1e-5)))
+        if not (np.isfinite(eps) and eps > 0):
+            return None, f"{tag(n)}: epsilon {eps}"
+        return (g, b, eps), None
+
+    i, cur = 0, model["inputs"][0]
+    raw_in, ln, layers = [], {}, []
+    while i < len(body) and body[i]["op"] in _STAGE_OP:
+        if len(raw_in) == 4:
+            return None, f"{tag(body[i])}: a fifth item in the input stage (at most 4)"
+        item, why = stage_item(body[i], cur)
+        if item is None:
+            return None, why
+        raw_in.append(item)
+        cur, i = body[i]["outputs"][0], i + 1
+    if i < len(body) and body[i]["op"] == "LayerNormalization":
+        got, why = layer_norm(body[i], cur, None)
+        if got is None:
+            return None, why
+        ln[0] = (1, *got)
+        cur, i = body[i]["outputs"][0], i + 1
+    while i < len(body) and body[i]["op"] in ("Gemm", "MatMul"):
+        n = body[i]
+        a, ins = n["attrs"], n["inputs"]
+        if n["op"] == "Gemm":
+            if ins[0] != cur or a.get("transB", 0) != 1 or a.get("transA", 0) or a.get("alpha", 1.0) != 1.0 or a.get("beta", 1.0) != 1.0:
+                return None, f"{tag(n)}: not Gemm(transB=1, alpha=beta=1, transA=0) on the tensor before it"
+            if ins[1] not in model["init"]:
+                return None, f"{tag(n)}: weight '{ins[1]}' is not an initialiser"
+            w = model["init"][ins[1]]
+            b = model["init"].get(ins[2]) if len(ins) > 2 and ins[2] else None
+            if w.ndim != 2 or w.dtype != np.float32 or (b is not None and (b.shape != (w.shape[0],) or b.dtype != np.float32)) or \
+                    (len(ins) > 2 and ins[2] and b is None):
+                return None, f"{tag(n)}: weight or bias is not an fp32 initialiser of shape [O, I] / [O]"
+            cur, i = n["outputs"][0], i + 1
+        else:
+            if len(ins) != 2 or ins[0] != cur or ins[1] not in model["init"]:
+                return None, f"{tag(n)}: MatMul with a non-initialiser weight (x @ Wt with Wt an initialiser [I, O] only)"
+            wt = model["init"][ins[1]]
+            if wt.ndim != 2 or wt.dtype != np.float32:
+                return None, f"{tag(n)}: weight '{ins[1]}' is {wt.dtype} {wt.shape}, not fp32 [I, O]"
+            w, b = np.ascontiguousarray(wt.T), None
+            cur, i = n["outputs"][0], i + 1
+            if i < len(body) and body[i]["op"] == "Add" and cur in body[i]["inputs"] and len(body[i]["inputs"]) == 2:
+                other = [x for x in body[i]["inputs"] if x != cur]
+                c = init.get(other[0]) if other else None
+                if c is not None and c.dtype == np.float32 and c.shape == (w.shape[0],):
+                    b = c
+                    cur, i = body[i]["outputs"][0], i + 1
+        if len(layers) == 6:
+            return None, f"{tag(n)}: a seventh layer (1..6)"
+        if max(w.shape) > 512:
+            return None, f"{tag(n)}: width {max(w.shape)} (1..512)"
+        if layers and w.shape[1] != layers[-1][0].shape[0]:
+            return None, f"{tag(n)}: input width {w.shape[1]} differs from the layer before it ({layers[-1][0].shape[0]})"
+        act, alpha, where, norm = 0, 1.0, 0, None
+        for _ in range(2):
+            if i < len(body) and body[i]["op"] in _ACT and body[i]["inputs"] == [cur] and act == 0:
+                act = _ACT[body[i]["op"]]
+                alpha = float(body[i]["attrs"].get("alpha", 1.0 if act == 3 else 0.01))
+                cur, i = body[i]["outputs"][0], i + 1
+            elif i < len(body) and body[i]["op"] == "LayerNormalization" and norm is None:
+                norm, why = layer_norm(body[i], cur, w.shape[0])
+                if norm is None:
+                    return None, why
+                where = 2 if act else 1
+                cur, i = body[i]["outputs"][0], i + 1
+        if norm is not None:
+            ln[len(layers) + 1] = (where, *norm)
+        layers.append((w, b, act, alpha))
+    if not layers:
+        return None, (f"{tag(body[i])} is not part of the fused actor grammar" if i < len(body) else "no linear layer")
+    raw_out = []
+    while i < len(body) and body[i]["op"] in _STAGE_OP:
+        if len(raw_out) == 4:
+            return None, f"{tag(body[i])}: a fifth item in the output stage (at most 4)"
+        item, why = stage_item(body[i], cur)
+        if item is None:
+            return None, why
+        raw_out.append(item)
+        cur, i = body[i]["outputs"][0], i + 1
+    if i < len(body):
+        return None, f"{tag(body[i])} is not part of the fused actor grammar"
+    if cur != model["outputs"][0]:
+        return None, f"the graph output '{model['outputs'][0]}' is not the end of the chain ('{cur}')"
+    if len(layers) in ln:
+        return None, "LayerNormalization on the last layer"
+    in_dim = layers[0][0].shape[1]
+    if 0 in ln and (ln[0][1].shape != (in_dim,) or (ln[0][2] is not None and ln[0][2].shape != (in_dim,))):
+        return None, f"LayerNormalization on the observation: scale {ln[0][1].shape} for width {in_dim}"
+    stage_in, why = widen(raw_in, in_dim, "input")
+    if stage_in is None:
+        return None, why
+    stage_out, why = widen(raw_out, layers[-1][0].shape[0], "output")
+    if stage_out is None:
+        return None, why
+    return {"layers": layers, "input": stage_in, "output": stage_out, "ln": ln}, None
+
+
+class _Extras(ctypes.Structure):
+    """``cosim_mlp_extras_t`` (include/cosim_actor.h)."""
+    _fields_ = [("n_in", ctypes.c_int32), ("n_out", ctypes.c_int32), ("in_op", ctypes.c_int32 * 4), ("out_op", ctypes.c_int32 * 4),
+                ("in_vec", ctypes.c_void_p * 4), ("out_vec", ctypes.c_void_p * 4),
+                ("in_lo", ctypes.c_float * 4), ("in_hi", ctypes.c_float * 4), ("out_lo", ctypes.c_float * 4), ("out_hi", ctypes.c_float * 4),
+                ("ln_where", ctypes.c_int32 * 7), ("ln_eps", ctypes.c_float * 7), ("ln_gamma", ctypes.c_void_p * 7), ("ln_beta", ctypes.c_void_p * 7)]
+
+
+def _has_extras(desc: dict) -> bool:
+    return bool(desc["input"] or desc["output"] or desc["ln"])
+
+
+def _fill_extras(e: "_Extras", desc: dict, place):
+    """One actor's extras into ``e``; ``place(array) -> address`` puts a vector where the callee reads it (device or host) and keeps it."""
+    e.n_in, e.n_out = len(desc["input"]), len(desc["output"])
+    for items, op, vec, lo, hi in ((desc["input"], e.in_op, e.in_vec, e.in_lo, e.in_hi), (desc["output"], e.out_op, e.out_vec, e.out_lo, e.out_hi)):
+        for k, (code, c, l, h) in enumerate(items):
+            op[k], lo[k], hi[k] = code, l, h
+            vec[k] = None if c is None else place(c)
+    for slot, (where, g, b, eps) in desc["ln"].items():
+        e.ln_where[slot], e.ln_eps[slot] = where, eps
+        e.ln_gamma[slot], e.ln_beta[slot] = place(g), None if b is None else place(b)
+
+
 _SHAPE_ONLY = ("Unsqueeze", "Squeeze", "Reshape", "Identity")
 
 
@@ -147,8 +360,10 @@ def _recurrent_actor(model: dict):
 class MLPPolicy:
     """``core/policy.py:5-21``: ``get_action(state[N, state_dim]) -> action[N, action_dim]`` in [-1, 1].
 
-    A graph that is a plain Gemm / activation chain runs as ONE launch of the engine's fused MFMA kernel
-    (``cosim_mlp_forward``, csrc/cosim_mlp.hip) when the policy lives on a GPU; anything else goes through the interpreter."""
+    A graph of the fused actor grammar (``_actor_graph``: a Gemm / activation chain, optionally with an observation normaliser,
+    LayerNorm, MatMul + Add layers and an output stage) runs as ONE launch of the engine's fused MFMA kernel (``cosim_mlp_forward``, or
+    ``cosim_mlp_forward_ex`` when it has any of the extras; csrc/cosim_mlp.hip) when the policy lives on a GPU; anything else goes
+    through the interpreter.  ``_fused`` is not None exactly when the fused path runs."""
 
     def __init__(self, policy_path: str, device=None, fused: Optional[bool] = None):
         import torch
@@ -157,17 +372,25 @@ class MLPPolicy:
         model = read_onnx(policy_path)
         self.graph = OnnxGraph(model, self.device)
         self.input_name = self.graph.inputs[0]
-        chain = _mlp_chain(model) if (fused is not False and self.device.type == "cuda") else None
-        if fused and chain is None:
-            raise ValueError("fused=True needs a Gemm/activation chain on a GPU device")
+        desc, why = _actor_graph(model) if (fused is not False and self.device.type == "cuda") else (None, f"the device is '{self.device}', not a GPU")
+        if fused and desc is None:
+            raise ValueError(f"fused=True needs a graph of the fused actor grammar (a Gemm/activation chain and its extras) on a GPU device: {why}")
         self._fused = None
-        if chain is not None:
+        if desc is not None:
             from .engine import load_library
+            chain = desc["layers"]
             ws = [torch.as_tensor(np.ascontiguousarray(w), device=self.device) for w, *_ in chain]
             bs = [None if b is None else torch.as_tensor(np.ascontiguousarray(b), device=self.device) for _, b, *_ in chain]
             nl = len(chain)
+            extras, vecs = None, []
+            if _has_extras(desc):
+                def place(a):
+                    vecs.append(torch.as_tensor(np.array(a, dtype=np.float32), device=self.device))
+                    return vecs[-1].data_ptr()
+                extras = _Extras()
+                _fill_extras(extras, desc, place)
             self._fused = dict(
-                L=load_library(), nl=nl, keep=(ws, bs),
+                L=load_library(), nl=nl, keep=(ws, bs, vecs), extras=extras,
                 dims=(ctypes.c_int * (nl + 1))(chain[0][0].shape[1], *[w.shape[0] for w, *_ in chain]),
                 w=(ctypes.c_void_p * nl)(*[w.data_ptr() for w in ws]),
                 b=(ctypes.c_void_p * nl)(*[None if b is None else b.data_ptr() for b in bs]),
@@ -180,8 +403,12 @@ class MLPPolicy:
     def _forward(self, x, out):
         """One launch of the fused kernel on the CURRENT stream: ``out[:] = actor(x)``, both contiguous fp32 rows on the policy's device."""
         f = self._fused
-        rc = f["L"].cosim_mlp_forward(x.data_ptr(), x.shape[0], f["nl"], f["dims"], f["w"], f["b"], f["act"], f["alpha"], 1.0, out.data_ptr(),
-                                      self.torch.cuda.current_stream(self.device).cuda_stream)
+        stream = self.torch.cuda.current_stream(self.device).cuda_stream
+        if f["extras"] is None:
+            rc = f["L"].cosim_mlp_forward(x.data_ptr(), x.shape[0], f["nl"], f["dims"], f["w"], f["b"], f["act"], f["alpha"], 1.0, out.data_ptr(), stream)
+        else:
+            rc = f["L"].cosim_mlp_forward_ex(x.data_ptr(), x.shape[0], f["nl"], f["dims"], f["w"], f["b"], f["act"], f["alpha"], ctypes.byref(f["extras"]),
+                                             1.0, out.data_ptr(), stream)
         if rc != 0:
             raise RuntimeError(f["L"].cosim_last_error().decode())
 
@@ -367,6 +594,7 @@ class _FleetTable:
         self.policy_now = self._base.clone()
 
     _entry = None         # the subclass's family of entry points: "cosim_policy_table" has _create, _rotate, _destroy ...
+    _create_suffix = "_create"   # "_create_ex": a PolicyTable with an extended actor among its files
     recurrent = False     # a recurrent table's done flags also zero the state, so its static launch takes them too
 
     @staticmethod
@@ -398,7 +626,7 @@ class _FleetTable:
         rng = np.ascontiguousarray(np.asarray(self.ranges, dtype=np.int32).reshape(-1, 2))
         handle = ctypes.c_void_p()
         with self.torch.cuda.device(self.device):
-            if getattr(L, self._entry + "_create")(len(self.paths), *policy_args, self.num_envs, por.ctypes.data, len(self.ranges), rng.ctypes.data,
+            if getattr(L, self._entry + self._create_suffix)(len(self.paths), *policy_args, self.num_envs, por.ctypes.data, len(self.ranges), rng.ctypes.data,
                                                     ctypes.byref(handle)) != 0:
                 return L.cosim_last_error().decode()
             self._lib, self._handle = L, handle
@@ -539,7 +767,9 @@ class PolicyTable(_FleetTable):
     ``assign``: ``"interleave"`` -- ``g mod K``; ``"cross"`` -- ``(g // S) mod K`` with ``S = scenarios`` (in scenario mode ``env``, where
     env ``g`` runs scenario ``g mod S``, every (scenario, policy) pair gets the same share of envs); or an int array with one entry per
     LOCAL env.  ``ranges``: the env's ``range_list`` (``get_action_range`` evaluates one of them on the current stream); default: one
-    range.  Every file must be a Gemm / activation chain (``_mlp_chain``) with the first file's input and output width.  On a
+    range.  Every file must be an actor of the fused grammar (``_actor_graph``: a Gemm / activation chain, optionally with an observation
+    normaliser, LayerNorm, MatMul + Add layers and an output stage; plain and extended files may share a table) with the first file's
+    input and output width.  On a
     non-CUDA device, or with ``fused=False``, each policy's interpreter runs on its own rows and the results are scattered: the
     torch twin of the kernel.  Stateless: a ``Snapshot`` stores nothing for it.
 
@@ -565,14 +795,16 @@ class PolicyTable(_FleetTable):
         import torch
         self._setup_fleet(policy_paths, num_envs, device, env_id0, scenarios, names)
         paths, K, N = self.paths, len(self.paths), self.num_envs
-        chains, models = [], []
+        chains, models, descs = [], [], []
         for p in paths:
             model = read_onnx(p)
             if any(n["op"] == "LSTM" for n in model["nodes"]):
                 raise ValueError(f"PolicyTable: {p}: an LSTM policy (recurrent policies in a table are out of scope)")
-            chain = _mlp_chain(model)
-            if chain is None:
-                raise ValueError(f"PolicyTable: {p}: the graph is not a plain Gemm / activation chain (1..6 layers, widths up to 512, fp32)")
+            desc, why = _actor_graph(model)
+            if desc is None:
+                raise ValueError(f"PolicyTable: {p}: the graph is not a plain Gemm / activation chain (1..6 layers, widths up to 512, fp32) nor one with "
+                                 f"the extras of the fused actor grammar: {why}")
+            chain = desc["layers"]
             i0, o0 = (chains[0][0][0].shape[1], chains[0][-1][0].shape[0]) if chains else (chain[0][0].shape[1], chain[-1][0].shape[0])
             if chain[0][0].shape[1] != i0:
                 raise ValueError(f"PolicyTable: {p}: input width {chain[0][0].shape[1]} differs from {i0} of {paths[0]}")
@@ -580,6 +812,8 @@ class PolicyTable(_FleetTable):
                 raise ValueError(f"PolicyTable: {p}: output width {chain[-1][0].shape[0]} differs from {o0} of {paths[0]}")
             chains.append(chain)
             models.append(model)
+            descs.append(desc)
+        self._descs = descs
         self.in_dim, self.out_dim = int(chains[0][0][0].shape[1]), int(chains[0][-1][0].shape[0])
         self._setup_assign(assign, ranges)
         self._out = torch.zeros((N, self.out_dim), dtype=torch.float32, device=self.device)
@@ -592,6 +826,15 @@ class PolicyTable(_FleetTable):
 
     def _create(self, chains):
         layers, keep = self._pack_layers(chains, [c[0][0].shape[1] for c in chains], 6)   # keep: alive until create has copied them
+        if any(_has_extras(d) for d in self._descs):      # one record per policy (all zero for a plain file), host vectors
+            def place(a):
+                keep.append(np.ascontiguousarray(a, dtype=np.float32))
+                return keep[-1].ctypes.data
+            extras = (_Extras * len(chains))()
+            for e, d in zip(extras, self._descs):
+                _fill_extras(e, d, place)
+            self._create_suffix = "_create_ex"
+            layers = (*layers, extras)
         msg = self._open(*layers)
         if msg is not None:
             raise RuntimeError(msg)
