@@ -9,6 +9,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -27,6 +28,7 @@
 #include "cosim_curves.hip"
 #include "cosim_search.hip"
 #include "cosim_latency.hip"
+#include "cosim_devbuf.h"
 #include "cosim_plan.h"
 #include "cosim_ranges.h"
 #include "cosim_tables.h"
@@ -47,6 +49,170 @@ static int fail(int code, const std::string& msg) {
     hipError_t _e = (expr);                                                                   \
     if (_e != hipSuccess) return fail(COSIM_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
   } while (0)
+// the same for a call whose message names the entry point (`who`), not the expression; HIP_TRY_CLEAR also takes the error out of
+// hipGetLastError, where it would otherwise stick
+#define HIP_TRY_AS(who, expr)                                                                 \
+  do {                                                                                        \
+    const hipError_t _e = (expr);                                                             \
+    if (_e != hipSuccess) return fail(COSIM_EHIP, std::string(who) + ": " + hipGetErrorString(_e)); \
+  } while (0)
+#define HIP_TRY_CLEAR(who, expr)                                                              \
+  do {                                                                                        \
+    const hipError_t _e = (expr);                                                             \
+    if (_e != hipSuccess) { (void)hipGetLastError(); return fail(COSIM_EHIP, std::string(who) + ": " + hipGetErrorString(_e)); } \
+  } while (0)
+
+// ---- the allocator policies of DevBuf (cosim_devbuf.h): every allocation of the library is made and released here
+// device allocations that are live in this process (cosim_query "device_buffers"): what a test compares to hold that nothing leaked
+static std::atomic<int> g_device_buffers{0};
+
+struct HipDevice {
+  using error_t = hipError_t;
+  static constexpr error_t ok = hipSuccess;
+  static error_t malloc(void** p, size_t bytes) {
+    const error_t r = hipMalloc(p, bytes);
+    if (r == ok && *p) g_device_buffers.fetch_add(1, std::memory_order_relaxed);
+    return r;
+  }
+  static void free(void* p) {
+    (void)hipFree(p);
+    g_device_buffers.fetch_sub(1, std::memory_order_relaxed);
+  }
+  static error_t memset(void* p, int v, size_t bytes) { return hipMemset(p, v, bytes); }
+  static error_t to_device(void* dst, const void* host, size_t bytes) { return hipMemcpy(dst, host, bytes, hipMemcpyHostToDevice); }
+  static error_t to_host(void* host, const void* src, size_t bytes) { return hipMemcpy(host, src, bytes, hipMemcpyDeviceToHost); }
+};
+struct HipPinned {   // page-locked host memory (not counted)
+  using error_t = hipError_t;
+  static constexpr error_t ok = hipSuccess;
+  static error_t malloc(void** p, size_t bytes) { return hipHostMalloc(p, bytes, hipHostMallocDefault); }
+  static void free(void* p) { (void)hipHostFree(p); }
+};
+template <class T> using Dev = DevBuf<T, HipDevice>;
+template <class T> using Pinned = DevBuf<T, HipPinned>;
+
+// ---- what each feature holds on the device, with the scalars that mean something only beside it: assigning an empty group drops the
+// feature.  The caller has waited for the device (table_quiesce / hipDeviceSynchronize): no launch in flight touches what goes.
+// spawn table (cosim_spawn_set): base poses the reset block takes instead of init_qpos[0:7]; placed by spawn_place_kernel
+struct Spawn {
+  Dev<float> table;           // [rows][8]
+  std::vector<float> host;    // host copy of the placed table (cosim_spawn_get)
+  int rows = 0, mode = 0;
+};
+// the error word of the gather kernel and its pinned host copy ([2] each): both or neither
+struct SnapErr {
+  Dev<int> dev;
+  Pinned<int> host;
+};
+// history ring (cosim_history_set): every `every`-th cosim_step packs each range's rows into slot (capture number) mod slots
+struct History {
+  Dev<float> ring;            // [slots][n_envs][snapshot_floats]
+  int slots = 0, every = 0;
+  long calls = 0, captures = 0;   // cosim_step calls / captures since cosim_history_set
+  std::vector<long> call_of;      // per slot: the call count its capture was taken after
+};
+// episode ledger (cosim_ledger_set, cosim_ledger.hip): ledger_step_kernel behind every range's last launch of a step / rollout
+struct Ledger {
+  Dev<double> sum;            // [LEDGER_NSUM][n_envs]
+  Dev<float> peak;            // [2][n_envs]
+  Dev<int> acc;               // [LEDGER_NINT][n_envs]
+  Dev<int> rec;               // [n_envs][slots][16]
+  int slots = 0;
+};
+// failure traces (cosim_ftrace_set, cosim_ftrace.hip): ftrace_step_kernel behind every range's last launch of a step, behind the ledger's
+struct Ftrace {
+  Dev<int> buf;               // [n_envs][keep + 1][FT_HDR + frames * F]
+  Dev<int> cnt;               // [n_envs][FT_NCNT]
+  int frames = 0, keep = 0, mask = 0;
+};
+// scenario table (cosim_scenario_set, cosim_scenario.hip): scenario_step_kernel ahead of every range's first launch of a step / reset
+struct Scenario {
+  Dev<char> image;            // one allocation: key_adr | push_adr | key_t | push_t | key_cmd | push_v
+  ScnTable tab = {};          // device pointers into the image; n_scn 0: no table, no scenario launches
+  int nkey = 0, npush = 0;
+  float* cmd_out = nullptr;   // [n_envs][command_dim] caller-owned: what the step kernels read as the command while a table is set
+  int32_t* row_out = nullptr; // [n_envs] caller-owned
+};
+// parameter windows of the scenario table (cosim_scenario_params_set, cosim_scnparams.hip): scnparams_step_kernel behind every scenario launch
+struct ScnParams {
+  Dev<char> image;            // one allocation: adr | t | word | op | value
+  ScnParTable tab = {};       // device pointers into the image; n_items 0: no windows, no launches, the step kernels read d_params
+  Dev<float> eff;             // [n_envs][p_stride] effective records: what base_args hands the step kernels while windows are set
+  int marked = 0;             // items whose op carries SCNPAR_MARK (scnparams_search_step_kernel scales them)
+};
+// observation faults (cosim_set_param "obs_faults", cosim_obsfault.hip): obsfault_step_kernel behind every step's / reset's last launch;
+// action faults (cosim_set_param "action_faults", cosim_actfault.hip): actfault_step_kernel ahead of every control step's first launch,
+// actfault_obs_kernel behind its last
+struct Faults {
+  Dev<char> image;            // one allocation: adr | item
+  FaultTable tab = {};        // device pointers into the image; n_items 0: no faults, no launches
+  int marked = 0;             // items that carry FLT_MARK (the *_search_step_kernel of the kind scales them)
+};
+// the two action rows, shared by the action faults and the latency's action items: there while either kind has items (action_rows_release)
+struct ActionRows {
+  Dev<float> eff;             // [n_envs][nu] effective actions: what the step kernels are handed while faults are set
+  Dev<float> raw;             // [n_envs][nu] the caller's actions of the last step (last_action is rebuilt from them)
+  // both or neither; zeroed, so that a read ahead of the first step finds no stale bytes
+  hipError_t alloc(size_t count) {
+    hipError_t r = eff.alloc_zeroed(count);
+    if (r == hipSuccess) r = raw.alloc_zeroed(count);
+    if (r != hipSuccess) eff.reset();
+    return r;
+  }
+};
+// latency lines of the scenario table (cosim_set_param "latency", cosim_latency.hip): latency_act_kernel ahead of actfault_step_kernel,
+// latency_obs_kernel ahead of obsfault_step_kernel
+struct Latency {
+  Dev<char> image;            // one allocation: act_adr | obs_adr | act_item | obs_item
+  LatTable tab = {};          // device pointers into the image; n_act + n_obs 0: no latency, no launches
+  Dev<float> act_line;        // [n_envs][depth][nu], with action items
+  Dev<float> obs_line;        // [n_envs][depth][frame_dim], with observation items
+  Dev<int> from;              // [2][n_envs]: the clock each env's action / observation line is valid from (< 0: invalid)
+  Dev<float> eff;             // [n_envs][nu] the delivered actions while action faults are set too: what actfault_step_kernel reads
+  Dev<float> spare;           // [n_envs][nu] where actfault_step_kernel's copy of them goes then
+};
+// checks of the scenario table (cosim_scenario_checks_set, cosim_checks.hip): checks_step_kernel behind every range's last launch of a
+// step, behind the ledger's
+struct Checks {
+  Dev<char> image;            // one allocation: adr | t | signal | index | mode | cmp | bound
+  ChkTable tab = {};          // device pointers into the image; n_scn 0: no checks, no launches
+  Dev<float> ext;             // [n_envs][I]
+  Dev<int> aux, n;            // [n_envs][I]
+  Dev<double> sum;            // [n_envs][I]
+  Dev<int> cnt;               // [n_envs][CHK_NCNT]
+  Dev<int> rec;               // [n_envs][slots][8 + 2 I]
+  int slots = 0;
+};
+// response curves of the scenario table (cosim_scenario_curves_set, cosim_curves.hip): curves_step_kernel behind every range's last
+// launch of a step, behind the checks'.  Groups (cosim_scenario_curves_groups): with G > 0 the cells are G planes of `words`, and the
+// step launches curves_step_grouped_kernel, which reads the caller's group word of an env when its episode ends; they go with the cells they split
+struct Curves {
+  Dev<char> image;            // one allocation: adr | t | signal | index | bins | nt | soff | coff | cw | lo | hi | inv_w
+  CurTable tab = {};          // device pointers into the image; n_scn 0: no curves, no launches
+  Dev<int> stage;             // [n_envs][SW]
+  Dev<int> clk;               // [n_envs]
+  Dev<unsigned> cells;        // max(G, 1) planes of `words` 32-bit words
+  size_t words = 0;
+  int groups = 0;                     // G; 0: no groups, one plane, curves_step_kernel
+  const int32_t* group = nullptr;     // [n_envs], the caller's
+  Dev<unsigned> ungrouped;            // one word: ended episodes whose group word was outside [0, G)
+};
+// limit search of the scenario table (cosim_set_param "search", cosim_search.hip): scenario_search_step_kernel in the place of
+// scenario_step_kernel, search_step_kernel behind every range's last launch of a step, behind the curves'
+struct Search {
+  Dev<char> image;            // one allocation: has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip
+  SrchTable tab = {};         // device pointers into the image; n_items 0: no search, no launches, scenario_step_kernel
+  Dev<int> rec;               // [n_envs][SRCH_NCNT]
+  Dev<int> ring;              // [n_envs][slots][4]
+  Dev<int> rem;               // one word: envs with an item that are not done
+  int slots = 0;
+  // what the other setters hold their tables against while a search is armed: the host's copy of has | lo | hi | targets, the union
+  // of the items' targets and whether an item fails on a check (search_step_checks_kernel in the place of search_step_kernel)
+  std::vector<int32_t> has, targets;
+  std::vector<float> lo, hi;
+  int kinds = 0;
+  bool on_check = false;
+};
 
 struct cosim_engine {
   int n_envs = 0, device = 0;
@@ -55,15 +221,15 @@ struct cosim_engine {
   DevModel hm;  // host copies
   DevObs ho;
   Layout lay;
-  DevModel* d_model = nullptr;
-  DevObs* d_obs = nullptr;
-  float *d_state = nullptr, *d_params = nullptr, *d_hull_vert = nullptr, *d_hfield = nullptr, *d_hfield_mip = nullptr, *d_dbg = nullptr;
-  int *d_hull_adr = nullptr, *d_hull_nbr = nullptr;
-  float4* d_hull_cell = nullptr;    // support maps of the hulls (cosim_hullmap.h)
-  float4* d_hull_cand = nullptr;
+  Dev<DevModel> d_model;
+  Dev<DevObs> d_obs;
+  Dev<float> d_state, d_params, d_hull_vert, d_hfield, d_hfield_mip, d_dbg;
+  Dev<int> d_hull_adr, d_hull_nbr;
+  Dev<float4> d_hull_cell;          // support maps of the hulls (cosim_hullmap.h)
+  Dev<float4> d_hull_cand;
   int hullmap_of_geom[64];          // what DevModel::g_hullmap holds while "support_map" is on
-  unsigned* d_pairs = nullptr;   // robot-robot candidate pairs (geom1 | geom2 << 16)
-  float4* d_gext = nullptr;      // per geom: MPR centre (body frame), raw sliding friction
+  Dev<unsigned> d_pairs;         // robot-robot candidate pairs (geom1 | geom2 << 16)
+  Dev<float4> d_gext;            // per geom: MPR centre (body frame), raw sliding friction
   std::vector<float> h_params;
   bool params_dirty = true;
   uint64_t seed = 0;
@@ -92,9 +258,9 @@ struct cosim_engine {
   Switches sw;
   Plan<launch_fn> plan;
   int narrow_waves = 6;   // split pipeline: waves per env of the narrowphase kernel
-  float *d_xcon = nullptr, *d_xstate = nullptr;   // split pipeline: contact record and state between the two kernels of a substep
-  int* d_xcnt = nullptr;
-  int* d_ovf = nullptr;   // [n_envs] flags, set by the fleet kernel, cleared by the fix-up kernel
+  Dev<float> d_xcon, d_xstate;   // split pipeline: contact record and state between the two kernels of a substep
+  Dev<int> d_xcnt;
+  Dev<int> d_ovf;   // [n_envs] flags, set by the fleet kernel, cleared by the fix-up kernel
   // range launches: the fleet is cut into n_ranges contiguous env ranges, carried by n_streams <= n_ranges engine-owned streams
   // (cosim_ranges.h: as many as the process has hardware queues for).  cosim_step issues one launch sequence per stream over the
   // union of its group of consecutive ranges, so that a group's next control step fills the tail of the others' launches (a launch
@@ -117,101 +283,25 @@ struct cosim_engine {
   int inflight = 2;   // 0: unbounded
   std::vector<hipEvent_t> ring;   // [n_streams][inflight]
   long ring_pos = 0;
-  // spawn table (cosim_spawn_set): base poses the reset block takes instead of init_qpos[0:7]; placed by spawn_place_kernel
-  float* d_spawn = nullptr;       // [spawn_rows][8]
-  std::vector<float> h_spawn;     // host copy of the placed table (cosim_spawn_get)
-  int spawn_rows = 0, spawn_mode = 0;
+  Spawn spawn;
   // snapshots (cosim_snapshot.hip).  A restore with parameters leaves h_params behind the device: the mirror is read back before the
   // next per-env cosim_set_param edits it (that call rewrites the whole table from the mirror)
   bool params_mirror_stale = false;
-  int* d_snap_err = nullptr;      // [2] error word of the gather kernel
-  int* h_snap_err = nullptr;      // pinned host copy
-  // history ring (cosim_history_set): every `hist_every`-th cosim_step packs each range's rows into slot (capture number) mod slots
-  float* d_hist = nullptr;        // [hist_slots][n_envs][snapshot_floats]
-  int hist_slots = 0, hist_every = 0;
-  long hist_calls = 0, hist_captures = 0;   // cosim_step calls / captures since cosim_history_set
-  std::vector<long> hist_call_of;           // per slot: the call count its capture was taken after
-  // episode ledger (cosim_ledger_set, cosim_ledger.hip): ledger_step_kernel behind every range's last launch of a step / rollout
-  double* d_led_sum = nullptr;    // [LEDGER_NSUM][n_envs]
-  float* d_led_peak = nullptr;    // [2][n_envs]
-  int* d_led_acc = nullptr;       // [LEDGER_NINT][n_envs]
-  int* d_led_rec = nullptr;       // [n_envs][led_slots][16]
-  int led_slots = 0;
-  // failure traces (cosim_ftrace_set, cosim_ftrace.hip): ftrace_step_kernel behind every range's last launch of a step, behind the ledger's
-  int* d_ft_buf = nullptr;        // [n_envs][ft_keep + 1][FT_HDR + ft_frames * F]
-  int* d_ft_cnt = nullptr;        // [n_envs][FT_NCNT]
-  int ft_frames = 0, ft_keep = 0, ft_mask = 0;
+  SnapErr snap_err;               // there from the first restore with a source index on
+  History hist;
+  Ledger led;
+  Ftrace ft;
   bool stepped = false;           // stepped (or restored / overwritten) since the last whole-fleet reset: such an episode gets flag 8
-  // scenario table (cosim_scenario_set, cosim_scenario.hip): scenario_step_kernel ahead of every range's first launch of a step / reset
-  char* d_scn = nullptr;          // one allocation: key_adr | push_adr | key_t | push_t | key_cmd | push_v
-  ScnTable scn = {};              // device pointers into d_scn; n_scn 0: no table, no scenario launches
-  int scn_nkey = 0, scn_npush = 0;
-  float* scn_cmd_out = nullptr;   // [n_envs][command_dim] caller-owned: what the step kernels read as the command while a table is set
-  int32_t* scn_row_out = nullptr; // [n_envs] caller-owned
-  // parameter windows of the scenario table (cosim_scenario_params_set, cosim_scnparams.hip): scnparams_step_kernel behind every scenario launch
-  char* d_scnpar = nullptr;       // one allocation: adr | t | word | op | value
-  ScnParTable scnpar = {};        // device pointers into d_scnpar; n_items 0: no windows, no launches, the step kernels read d_params
-  // observation faults of the scenario table (cosim_set_param "obs_faults", cosim_obsfault.hip): obsfault_step_kernel behind every step's / reset's last launch
-  char* d_obsflt = nullptr;       // one allocation: adr | item
-  FaultTable obsflt = {};         // device pointers into d_obsflt; n_items 0: no faults, no launches
-  // action faults of the scenario table (cosim_set_param "action_faults", cosim_actfault.hip): actfault_step_kernel ahead of every control
-  // step's first launch, actfault_obs_kernel behind its last
-  char* d_actflt = nullptr;       // one allocation: adr | item
-  FaultTable actflt = {};         // device pointers into d_actflt; n_items 0: no faults, no launches, the step kernels read the caller's actions
-  float* d_actions_eff = nullptr; // [n_envs][nu] effective actions: what the step kernels are handed while faults are set
-  float* d_actions_raw = nullptr; // [n_envs][nu] the caller's actions of the last step (last_action is rebuilt from them)
+  // the scenario table and what is set for its rows (scenario_free says what goes with it)
+  Scenario scn;
+  ScnParams par;
+  Faults obsflt, actflt;
+  ActionRows act;
   bool act_in_obs = false;        // the observation has last_action elements
-  // latency lines of the scenario table (cosim_set_param "latency", cosim_latency.hip): latency_act_kernel ahead of actfault_step_kernel,
-  // latency_obs_kernel ahead of obsfault_step_kernel; while action items are set they share d_actions_eff / d_actions_raw with the action faults
-  char* d_lat = nullptr;          // one allocation: act_adr | obs_adr | act_item | obs_item
-  LatTable lat = {};              // device pointers into d_lat; n_act + n_obs 0: no latency, no launches
-  float* d_lat_act_line = nullptr;   // [n_envs][depth][nu], with action items
-  float* d_lat_obs_line = nullptr;   // [n_envs][depth][frame_dim], with observation items
-  int* d_lat_from = nullptr;      // [2][n_envs]: the clock each env's action / observation line is valid from (< 0: invalid)
-  float* d_lat_eff = nullptr;     // [n_envs][nu] the delivered actions while action faults are set too: what actfault_step_kernel reads
-  float* d_lat_spare = nullptr;   // [n_envs][nu] where actfault_step_kernel's copy of them goes then
-  float* d_params_eff = nullptr;  // [n_envs][p_stride] effective records: what base_args hands the step kernels while windows are set
-  // checks of the scenario table (cosim_scenario_checks_set, cosim_checks.hip): checks_step_kernel behind every range's last launch of a
-  // step, behind the ledger's
-  char* d_chk = nullptr;          // one allocation: adr | t | signal | index | mode | cmp | bound
-  ChkTable chk = {};              // device pointers into d_chk; n_scn 0: no checks, no launches
-  float* d_chk_ext = nullptr;     // [n_envs][I]
-  int* d_chk_aux = nullptr;       // [n_envs][I]
-  int* d_chk_n = nullptr;         // [n_envs][I]
-  double* d_chk_sum = nullptr;    // [n_envs][I]
-  int* d_chk_cnt = nullptr;       // [n_envs][CHK_NCNT]
-  int* d_chk_rec = nullptr;       // [n_envs][chk_slots][8 + 2 I]
-  int chk_slots = 0;
-  // response curves of the scenario table (cosim_scenario_curves_set, cosim_curves.hip): curves_step_kernel behind every range's last
-  // launch of a step, behind the checks'
-  char* d_cur = nullptr;          // one allocation: adr | t | signal | index | bins | nt | soff | coff | cw | lo | hi | inv_w
-  CurTable cur = {};              // device pointers into d_cur; n_scn 0: no curves, no launches
-  int* d_cur_stage = nullptr;     // [n_envs][SW]
-  int* d_cur_clk = nullptr;       // [n_envs]
-  unsigned* d_cur_cells = nullptr;   // cur_words 32-bit words
-  size_t cur_words = 0;
-  // groups of the curves (cosim_scenario_curves_groups): with G > 0 the cells are G planes of cur_words, and the step launches
-  // curves_step_grouped_kernel, which reads the caller's group word of an env when its episode ends
-  int cur_groups = 0;                     // G; 0: no groups, one plane, curves_step_kernel
-  const int32_t* cur_group = nullptr;     // [n_envs], the caller's
-  unsigned* d_cur_ungrouped = nullptr;    // one word: ended episodes whose group word was outside [0, G)
-  // limit search of the scenario table (cosim_set_param "search", cosim_search.hip): scenario_search_step_kernel in the place of
-  // scenario_step_kernel, search_step_kernel behind every range's last launch of a step, behind the curves'
-  char* d_srch = nullptr;         // one allocation: has | lo | hi | x0 | d0 | d_min | rule | trials | targets | fail_mask | rev_skip
-  SrchTable srch = {};            // device pointers into d_srch; n_items 0: no search, no launches, scenario_step_kernel
-  int* d_srch_rec = nullptr;      // [n_envs][SRCH_NCNT]
-  int* d_srch_ring = nullptr;     // [n_envs][srch_slots][4]
-  int* d_srch_rem = nullptr;      // one word: envs with an item that are not done
-  int srch_slots = 0;
-  // what the other setters hold their tables against while a search is armed: the host's copy of has | lo | hi | targets, the union
-  // of the items' targets and whether an item fails on a check (search_step_checks_kernel in the place of search_step_kernel)
-  std::vector<int32_t> h_srch_has, h_srch_targets;
-  std::vector<float> h_srch_lo, h_srch_hi;
-  int srch_kinds = 0;
-  bool srch_chk = false;
-  int actflt_marked = 0;          // action-fault items of the table that carry FLT_MARK (actfault_search_step_kernel scales them)
-  int obsflt_marked = 0;          // observation-fault items that carry FLT_MARK (obsfault_search_step_kernel)
-  int scnpar_marked = 0;          // parameter items whose op carries SCNPAR_MARK (scnparams_search_step_kernel)
+  Latency lat;
+  Checks chk;
+  Curves cur;
+  Search srch;
   // fall rules (cosim_fall_set): kernel arguments of every step launch; fall_mask 0 = none (meta word 15 is not written)
   float fall_min_up = -1.f, fall_min_height = 0.f;
   int fall_grace = 0, fall_mask = 0;
@@ -585,7 +675,7 @@ static int refresh_param_mirror(cosim_engine* e);
 
 static int upload_params(cosim_engine* e) {
   if (!e->params_dirty) return COSIM_OK;
-  HIP_TRY(hipMemcpy(e->d_params, e->h_params.data(), e->h_params.size() * sizeof(float), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(e->d_params.get(), e->h_params.data(), e->h_params.size() * sizeof(float), hipMemcpyHostToDevice));
   e->params_dirty = false;
   return COSIM_OK;
 }
@@ -651,7 +741,7 @@ static const char* const HIST_CAPTURE_MSG =
 static SnapArgs snap_args(cosim_engine* e) {
   SnapArgs a;
   memset(&a, 0, sizeof a);
-  a.state = e->d_state; a.params = e->d_params; a.s_stride = e->lay.s_stride; a.p_stride = e->lay.p_stride;
+  a.state = e->d_state.get(); a.params = e->d_params.get(); a.s_stride = e->lay.s_stride; a.p_stride = e->lay.p_stride;
   a.n_envs = e->n_envs; a.n_rows = e->n_envs; a.env_first = 0; a.env_count = e->n_envs;
   return a;
 }
@@ -661,26 +751,26 @@ static int refresh_param_mirror(cosim_engine* e) {
   if (!e->params_mirror_stale) return COSIM_OK;
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(e->h_params.data(), e->d_params, e->h_params.size() * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(e->h_params.data(), e->d_params.get(), e->h_params.size() * sizeof(float), hipMemcpyDeviceToHost));
   e->params_mirror_stale = false;
   return COSIM_OK;
 }
 
 // this cosim_step call is the `every`-th since the last capture
-static bool history_due(const cosim_engine* e) { return e->hist_slots > 0 && (e->hist_calls + 1) % e->hist_every == 0; }
+static bool history_due(const cosim_engine* e) { return e->hist.slots > 0 && (e->hist.calls + 1) % e->hist.every == 0; }
 
 static int history_pack(cosim_engine* e, int first, int count, hipStream_t s) {
   SnapArgs a = snap_args(e);
-  a.rows = e->d_hist + (size_t)(e->hist_captures % e->hist_slots) * e->n_envs * (size_t)(a.s_stride + a.p_stride);
+  a.rows = e->hist.ring.get() + (size_t)(e->hist.captures % e->hist.slots) * e->n_envs * (size_t)(a.s_stride + a.p_stride);
   a.env_first = first; a.env_count = count;
   return launch_small<1, 64>(snapshot_pack_kernel, a, count, s);
 }
 
 static void history_count(cosim_engine* e) {   // after a cosim_step call was issued in full
-  if (e->hist_slots <= 0) return;
+  if (e->hist.slots <= 0) return;
   const bool due = history_due(e);
-  e->hist_calls++;
-  if (due) { e->hist_call_of[e->hist_captures % e->hist_slots] = e->hist_calls; e->hist_captures++; }
+  e->hist.calls++;
+  if (due) { e->hist.call_of[e->hist.captures % e->hist.slots] = e->hist.calls; e->hist.captures++; }
 }
 
 // ---- episode ledger (cosim_ledger.hip)
@@ -691,12 +781,12 @@ static const char* const LEDGER_INFO_MSG =
 static LedgerArgs ledger_args(cosim_engine* e) {
   LedgerArgs a;
   memset(&a, 0, sizeof a);
-  a.state = e->d_state; a.sum = e->d_led_sum; a.peak = e->d_led_peak; a.acc = e->d_led_acc; a.rec = e->d_led_rec;
+  a.state = e->d_state.get(); a.sum = e->led.sum.get(); a.peak = e->led.peak.get(); a.acc = e->led.acc.get(); a.rec = e->led.rec.get();
   a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs; a.rows = 1;
   a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.ncmd = e->ho.command_dim < 3 ? e->ho.command_dim : 3; a.cmd_stride = e->ho.command_dim;
-  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.slots = e->led_slots; a.spawn_rows = e->spawn_rows;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.slots = e->led.slots; a.spawn_rows = e->spawn.rows;
   a.fall = e->fall_mask != 0;
-  if (e->scn.n_scn > 0) { a.scn_row = e->scn_row_out; a.scn_rows = e->scn.n_scn; a.scn_mode = e->scn.mode; a.scn_off = e->scn.gid_off; }
+  if (e->scn.tab.n_scn > 0) { a.scn_row = e->scn.row_out; a.scn_rows = e->scn.tab.n_scn; a.scn_mode = e->scn.tab.mode; a.scn_off = e->scn.tab.gid_off; }
   return a;
 }
 
@@ -711,7 +801,7 @@ static int ledger_step(cosim_engine* e, int first, int count, int K, const float
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode, what they had open is dropped
 static int ledger_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
-  if (e->led_slots <= 0) return COSIM_OK;
+  if (e->led.slots <= 0) return COSIM_OK;
   LedgerArgs a = ledger_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
   return launch_small<64, 64>(ledger_begin_kernel, a, e->n_envs, s);
@@ -720,87 +810,63 @@ static int ledger_begin(cosim_engine* e, const uint8_t* mask, const int* src, in
 // ---- scenario table (cosim_scenario.hip)
 // the command buffer the step kernels, the ledger and the reporter read: the scenario kernel's output while a table is set
 static const float* scenario_cmd(const cosim_engine* e, const float* commands_dev) {
-  return e->scn.n_scn > 0 && e->ho.command_dim > 0 ? e->scn_cmd_out : commands_dev;
+  return e->scn.tab.n_scn > 0 && e->ho.command_dim > 0 ? e->scn.cmd_out : commands_dev;
 }
 
 // ahead of the step (reset: of the reset, for the envs under its mask) of envs [first, first + count) on the same stream
 static int scenario_launch(cosim_engine* e, int first, int count, const float* commands_dev, const uint8_t* mask, int reset, hipStream_t s) {
   ScnArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->scn; a.state = e->d_state; a.cmd_in = commands_dev; a.cmd_out = e->scn_cmd_out; a.row_out = e->scn_row_out; a.mask = mask;
+  a.tab = e->scn.tab; a.state = e->d_state.get(); a.cmd_in = commands_dev; a.cmd_out = e->scn.cmd_out; a.row_out = e->scn.row_out; a.mask = mask;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.reset = reset;
-  if (e->srch.n_items > 0) {   // a search is armed: the same schedule with every env's level multiplied in
+  if (e->srch.tab.n_items > 0) {   // a search is armed: the same schedule with every env's level multiplied in
     ScnSearchArgs sa;
     memset(&sa, 0, sizeof sa);
-    sa.scn = a; sa.srch = e->srch; sa.rec = e->d_srch_rec;
+    sa.scn = a; sa.srch = e->srch.tab; sa.rec = e->srch.rec.get();
     return launch_small<64, 64>(scenario_search_step_kernel, sa, count, s);
   }
   return launch_small<64, 64>(scenario_step_kernel, a, count, s);
-}
-
-// the windows go with their table (the caller has waited for the device)
-static void scnparams_free(cosim_engine* e) {
-  (void)hipFree(e->d_scnpar); (void)hipFree(e->d_params_eff);
-  e->d_scnpar = nullptr; e->d_params_eff = nullptr; memset(&e->scnpar, 0, sizeof e->scnpar);
-  e->scnpar_marked = 0;
 }
 
 // directly behind scenario_launch, same envs, same stream: the effective parameter records of this step (reset: of the masked envs at t = 0)
 static int scnparams_launch(cosim_engine* e, int first, int count, const uint8_t* mask, int reset, hipStream_t s) {
   ScnParArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->scn; a.par = e->scnpar; a.state = e->d_state; a.base = e->d_params; a.eff = e->d_params_eff; a.mask = mask;
+  a.tab = e->scn.tab; a.par = e->par.tab; a.state = e->d_state.get(); a.base = e->d_params.get(); a.eff = e->par.eff.get(); a.mask = mask;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.p_stride = e->lay.p_stride; a.reset = reset;
-  if (e->srch.n_items > 0 && (e->srch_kinds & SRCH_PARAMS)) {   // a search whose targets name the windows is armed: marked items are scaled by the env's level
-    const ScnParSearchArgs sa = {a, e->d_srch_rec, SRCH_NCNT};
+  if (e->srch.tab.n_items > 0 && (e->srch.kinds & SRCH_PARAMS)) {   // a search whose targets name the windows is armed: marked items are scaled by the env's level
+    const ScnParSearchArgs sa = {a, e->srch.rec.get(), SRCH_NCNT};
     return launch_small<SCNPAR_WAVES, 64 * SCNPAR_WAVES>(scnparams_search_step_kernel, sa, count, s);
   }
   return launch_small<SCNPAR_WAVES, 64 * SCNPAR_WAVES>(scnparams_step_kernel, a, count, s);
 }
 
-// the faults go with their table (the caller has waited for the device)
-static void obsfault_free(cosim_engine* e) {
-  (void)hipFree(e->d_obsflt);
-  e->d_obsflt = nullptr; memset(&e->obsflt, 0, sizeof e->obsflt);
-  e->obsflt_marked = 0;
-}
-
 // a search whose targets name the observation faults is armed: obsfault_search_step_kernel in the place of obsfault_step_kernel, and at
 // the step site behind the search's kernel
-static bool obsfault_searched(const cosim_engine* e) { return e->srch.n_items > 0 && (e->srch_kinds & SRCH_OBS_FAULTS) != 0; }
+static bool obsfault_searched(const cosim_engine* e) { return e->srch.tab.n_items > 0 && (e->srch.kinds & SRCH_OBS_FAULTS) != 0; }
 
 // behind the last launch of a step (reset: of the reset, for the envs under its mask) that writes the state record or state_out of
 // envs [first, first + count), same stream: what the policy sees of those envs
 static int obsfault_launch(cosim_engine* e, int first, int count, float* state_out, const uint8_t* mask, hipStream_t s) {
   ObsFaultArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->scn; a.flt = e->obsflt; a.state = e->d_state; a.state_out = state_out; a.mask = mask;
+  a.tab = e->scn.tab; a.flt = e->obsflt.tab; a.state = e->d_state.get(); a.state_out = state_out; a.mask = mask;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_stack = e->lay.s_stack;
   a.sd = e->ho.stacked_dim; a.S = e->ho.stack_size; a.frame_dim = e->ho.frame_dim; a.state_dim = e->ho.state_dim;
   a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
   if (obsfault_searched(e)) {   // marked items are scaled by the level of the episode the observation belongs to
-    const ObsFaultSearchArgs sa = {a, e->d_srch_rec, SRCH_NCNT};
+    const ObsFaultSearchArgs sa = {a, e->srch.rec.get(), SRCH_NCNT};
     return launch_small<FLT_WAVES, 64 * FLT_WAVES>(obsfault_search_step_kernel, sa, count, s);
   }
   return launch_small<FLT_WAVES, 64 * FLT_WAVES>(obsfault_step_kernel, a, count, s);
 }
 
-// the two action buffers go when neither the action faults nor the latency's action items need them
-static void action_buffers_release(cosim_engine* e) {
-  if (e->actflt.n_items > 0 || e->lat.n_act > 0) return;
-  (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw);
-  e->d_actions_eff = nullptr; e->d_actions_raw = nullptr;
-}
-
-// the action faults go with their table too (the caller has waited for the device)
-static void actfault_free(cosim_engine* e) {
-  (void)hipFree(e->d_actflt);
-  e->d_actflt = nullptr; memset(&e->actflt, 0, sizeof e->actflt);
-  e->actflt_marked = 0;
-  action_buffers_release(e);
+// the two action rows go when neither the action faults nor the latency's action items need them: called behind every change of either
+static void action_rows_release(cosim_engine* e) {
+  if (e->actflt.tab.n_items == 0 && e->lat.tab.n_act == 0) e->act = {};
 }
 
 // ahead of the first launch of a control step of envs [first, first + count), same stream, behind the scenario and parameter-window
@@ -809,13 +875,13 @@ static void actfault_free(cosim_engine* e) {
 static int actfault_launch(cosim_engine* e, int first, int count, const float* actions, float* raw, hipStream_t s) {
   ActFaultArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->scn; a.flt = e->actflt; a.state = e->d_state; a.actions = actions; a.eff = e->d_actions_eff; a.raw = raw;
+  a.tab = e->scn.tab; a.flt = e->actflt.tab; a.state = e->d_state.get(); a.actions = actions; a.eff = e->act.eff.get(); a.raw = raw;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_lastact = e->lay.s_lastact; a.nu = e->model.nu;
   a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
   // a search whose targets name the action faults is armed: the same walk with every env's level multiplied into its marked items
-  if (e->srch.n_items > 0 && (e->srch_kinds & SRCH_ACT_FAULTS)) {
-    const ActFaultSearchArgs sa = {a, e->d_srch_rec, SRCH_NCNT};
+  if (e->srch.tab.n_items > 0 && (e->srch.kinds & SRCH_ACT_FAULTS)) {
+    const ActFaultSearchArgs sa = {a, e->srch.rec.get(), SRCH_NCNT};
     return launch_small<FLT_WAVES, 64 * FLT_WAVES>(actfault_search_step_kernel, sa, count, s);
   }
   return launch_small<FLT_WAVES, 64 * FLT_WAVES>(actfault_step_kernel, a, count, s);
@@ -826,33 +892,21 @@ static int actfault_launch(cosim_engine* e, int first, int count, const float* a
 static int actfault_obs_launch(cosim_engine* e, int first, int count, float* state_out, hipStream_t s) {
   ActObsArgs a;
   memset(&a, 0, sizeof a);
-  a.ob = e->d_obs; a.state = e->d_state; a.state_out = state_out; a.raw = e->d_actions_raw;
+  a.ob = e->d_obs.get(); a.state = e->d_state.get(); a.state_out = state_out; a.raw = e->act.raw.get();
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_cache = e->lay.s_cache; a.s_stack = e->lay.s_stack; a.nu = e->model.nu;
   return launch_small<FLT_WAVES, 64 * FLT_WAVES>(actfault_obs_kernel, a, count, s);
 }
 
 // ---- latency lines of the scenario table (cosim_latency.hip)
-// the latency goes with its table (the caller has waited for the device)
-static void latency_drop(cosim_engine* e) {   // what the latency alone owns
-  (void)hipFree(e->d_lat); (void)hipFree(e->d_lat_act_line); (void)hipFree(e->d_lat_obs_line); (void)hipFree(e->d_lat_from);
-  (void)hipFree(e->d_lat_eff); (void)hipFree(e->d_lat_spare);
-  e->d_lat = nullptr; e->d_lat_act_line = nullptr; e->d_lat_obs_line = nullptr; e->d_lat_from = nullptr; e->d_lat_eff = nullptr; e->d_lat_spare = nullptr;
-  memset(&e->lat, 0, sizeof e->lat);
-}
-static void latency_free(cosim_engine* e) {
-  latency_drop(e);
-  action_buffers_release(e);
-}
-
 // ahead of actfault_launch and of the first launch of a control step of envs [first, first + count), same stream: the delivered and
 // the raw action rows of those envs.  With action faults set too the delivered rows go to d_lat_eff, which the fault kernel then reads.
 static int latency_act_launch(cosim_engine* e, int first, int count, const float* actions, hipStream_t s) {
   LatActArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->scn; a.lat = e->lat; a.state = e->d_state; a.actions = actions;
-  a.eff = e->actflt.n_items > 0 ? e->d_lat_eff : e->d_actions_eff; a.raw = e->d_actions_raw;
-  a.line = e->d_lat_act_line; a.from = e->d_lat_from;
+  a.tab = e->scn.tab; a.lat = e->lat.tab; a.state = e->d_state.get(); a.actions = actions;
+  a.eff = e->actflt.tab.n_items > 0 ? e->lat.eff.get() : e->act.eff.get(); a.raw = e->act.raw.get();
+  a.line = e->lat.act_line.get(); a.from = e->lat.from.get();
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.nu = e->model.nu;
   a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
@@ -864,8 +918,8 @@ static int latency_act_launch(cosim_engine* e, int first, int count, const float
 static int latency_obs_launch(cosim_engine* e, int first, int count, float* state_out, const uint8_t* mask, hipStream_t s) {
   LatObsArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->scn; a.lat = e->lat; a.state = e->d_state; a.state_out = state_out; a.mask = mask;
-  a.line = e->d_lat_obs_line; a.from = e->d_lat_from + e->n_envs;
+  a.tab = e->scn.tab; a.lat = e->lat.tab; a.state = e->d_state.get(); a.state_out = state_out; a.mask = mask;
+  a.line = e->lat.obs_line.get(); a.from = e->lat.from.get() + e->n_envs;
   a.n_envs = e->n_envs; a.first = first; a.count = count;
   a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.s_stack = e->lay.s_stack;
   a.sd = e->ho.stacked_dim; a.S = e->ho.stack_size; a.frame_dim = e->ho.frame_dim; a.state_dim = e->ho.state_dim;
@@ -876,8 +930,8 @@ static int latency_obs_launch(cosim_engine* e, int first, int count, float* stat
 // behind a set / restore on the same stream: the lines of the masked envs (null: all; with a restore's source index: those it did
 // not refuse) are invalid; each restarts at the clock its kernel finds next.  (A reset needs none: both kernels restart a line at clock 0.)
 static int latency_cut(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, hipStream_t s) {
-  if (e->lat.n_act + e->lat.n_obs == 0) return COSIM_OK;
-  const LatCutArgs a = {e->d_lat_from, e->d_lat_from + e->n_envs, mask, src, n_rows, e->n_envs};
+  if (e->lat.tab.n_act + e->lat.tab.n_obs == 0) return COSIM_OK;
+  const LatCutArgs a = {e->lat.from.get(), e->lat.from.get() + e->n_envs, mask, src, n_rows, e->n_envs};
   return launch_small<64, 64>(latency_cut_kernel, a, e->n_envs, s);
 }
 
@@ -889,12 +943,12 @@ static const char* const CHECKS_INFO_MSG =
 static ChkArgs checks_args(cosim_engine* e) {
   ChkArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->chk; a.state = e->d_state; a.scn_row = e->scn_row_out;
-  a.ext = e->d_chk_ext; a.aux = e->d_chk_aux; a.n = e->d_chk_n; a.sum = e->d_chk_sum; a.cnt = e->d_chk_cnt; a.rec = e->d_chk_rec;
+  a.tab = e->chk.tab; a.state = e->d_state.get(); a.scn_row = e->scn.row_out;
+  a.ext = e->chk.ext.get(); a.aux = e->chk.aux.get(); a.n = e->chk.n.get(); a.sum = e->chk.sum.get(); a.cnt = e->chk.cnt.get(); a.rec = e->chk.rec.get();
   a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
   a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.cmd_stride = e->ho.command_dim;
-  a.s_stride = e->lay.s_stride; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.s_meta = e->lay.s_meta; a.slots = e->chk_slots;
-  a.scn_mode = e->scn.mode; a.scn_off = e->scn.gid_off;
+  a.s_stride = e->lay.s_stride; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.s_meta = e->lay.s_meta; a.slots = e->chk.slots;
+  a.scn_mode = e->scn.tab.mode; a.scn_off = e->scn.tab.gid_off;
   return a;
 }
 
@@ -909,18 +963,10 @@ static int checks_step(cosim_engine* e, int first, int count, const float* cmd, 
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode with clean accumulators
 static int checks_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
-  if (e->chk.n_scn <= 0) return COSIM_OK;
+  if (e->chk.tab.n_scn <= 0) return COSIM_OK;
   ChkArgs a = checks_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
   return launch_small<CHK_WAVES, 64 * CHK_WAVES>(checks_begin_kernel, a, e->n_envs, s);
-}
-
-// the checks go with their table (the caller has waited for the device)
-static void checks_free(cosim_engine* e) {
-  (void)hipFree(e->d_chk); (void)hipFree(e->d_chk_ext); (void)hipFree(e->d_chk_aux); (void)hipFree(e->d_chk_n); (void)hipFree(e->d_chk_sum);
-  (void)hipFree(e->d_chk_cnt); (void)hipFree(e->d_chk_rec);
-  e->d_chk = nullptr; e->d_chk_ext = nullptr; e->d_chk_aux = nullptr; e->d_chk_n = nullptr; e->d_chk_sum = nullptr; e->d_chk_cnt = nullptr;
-  e->d_chk_rec = nullptr; e->chk_slots = 0; memset(&e->chk, 0, sizeof e->chk);
 }
 
 // ---- response curves of the scenario table (cosim_curves.hip)
@@ -931,12 +977,12 @@ static const char* const CURVES_INFO_MSG =
 static CurArgs curves_args(cosim_engine* e) {
   CurArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->cur; a.state = e->d_state; a.scn_row = e->scn_row_out;
-  a.stage = e->d_cur_stage; a.clk = e->d_cur_clk; a.cells = e->d_cur_cells;
+  a.tab = e->cur.tab; a.state = e->d_state.get(); a.scn_row = e->scn.row_out;
+  a.stage = e->cur.stage.get(); a.clk = e->cur.clk.get(); a.cells = e->cur.cells.get();
   a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
   a.info_dim = e->ho.info_dim; a.nu = e->model.nu; a.cmd_stride = e->ho.command_dim;
   a.s_stride = e->lay.s_stride; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.s_meta = e->lay.s_meta;
-  if (e->cur_groups > 0) { a.group = e->cur_group; a.n_groups = e->cur_groups; a.plane_words = e->cur_words; a.ungrouped = e->d_cur_ungrouped; }
+  if (e->cur.groups > 0) { a.group = e->cur.group; a.n_groups = e->cur.groups; a.plane_words = e->cur.words; a.ungrouped = e->cur.ungrouped.get(); }
   return a;
 }
 
@@ -946,12 +992,12 @@ static int curves_step(cosim_engine* e, int first, int count, const float* cmd, 
   CurArgs a = curves_args(e);
   a.cmd = a.cmd_stride > 0 ? cmd : nullptr; a.info = info; a.term = term; a.trunc = trunc;
   a.first = first; a.count = count;
-  return launch_small<CUR_WAVES, 64 * CUR_WAVES>(e->cur_groups > 0 ? curves_step_grouped_kernel : curves_step_kernel, a, count, s);
+  return launch_small<CUR_WAVES, 64 * CUR_WAVES>(e->cur.groups > 0 ? curves_step_grouped_kernel : curves_step_kernel, a, count, s);
 }
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode with an empty stage
 static int curves_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, hipStream_t s) {
-  if (e->cur.n_scn <= 0) return COSIM_OK;
+  if (e->cur.tab.n_scn <= 0) return COSIM_OK;
   CurArgs a = curves_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows;
   return launch_small<CUR_WAVES, 64 * CUR_WAVES>(curves_begin_kernel, a, e->n_envs, s);
@@ -959,27 +1005,19 @@ static int curves_begin(cosim_engine* e, const uint8_t* mask, const int* src, in
 
 // every cell back to empty; with groups every plane, and the `ungrouped` word to zero
 static int curves_zero(cosim_engine* e, hipStream_t s) {
-  if (e->cur_groups > 0) return launch_small<1, 256>(curves_clear_grouped_kernel, curves_args(e), 2 * e->cur.n_items * e->cur_groups, s);
-  return launch_small<1, 256>(curves_clear_kernel, curves_args(e), 2 * e->cur.n_items, s);
-}
-
-// the curves go with their table (the caller has waited for the device)
-static void curves_free(cosim_engine* e) {
-  (void)hipFree(e->d_cur); (void)hipFree(e->d_cur_stage); (void)hipFree(e->d_cur_clk); (void)hipFree(e->d_cur_cells); (void)hipFree(e->d_cur_ungrouped);
-  e->d_cur = nullptr; e->d_cur_stage = nullptr; e->d_cur_clk = nullptr; e->d_cur_cells = nullptr; e->cur_words = 0;
-  e->d_cur_ungrouped = nullptr; e->cur_groups = 0; e->cur_group = nullptr;   // the groups go with the cells they split
-  memset(&e->cur, 0, sizeof e->cur);
+  if (e->cur.groups > 0) return launch_small<1, 256>(curves_clear_grouped_kernel, curves_args(e), 2 * e->cur.tab.n_items * e->cur.groups, s);
+  return launch_small<1, 256>(curves_clear_kernel, curves_args(e), 2 * e->cur.tab.n_items, s);
 }
 
 // ---- limit search of the scenario table (cosim_search.hip)
 static SrchArgs search_args(cosim_engine* e) {
   SrchArgs a;
   memset(&a, 0, sizeof a);
-  a.tab = e->srch; a.state = e->d_state; a.scn_row = e->scn_row_out;
-  a.rec = e->d_srch_rec; a.ring = e->d_srch_ring; a.remaining = e->d_srch_rem;
+  a.tab = e->srch.tab; a.state = e->d_state.get(); a.scn_row = e->scn.row_out;
+  a.rec = e->srch.rec.get(); a.ring = e->srch.ring.get(); a.remaining = e->srch.rem.get();
   a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
-  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.slots = e->srch_slots;
-  a.fall = e->fall_mask != 0; a.scn_off = e->scn.gid_off;
+  a.s_stride = e->lay.s_stride; a.s_meta = e->lay.s_meta; a.slots = e->srch.slots;
+  a.fall = e->fall_mask != 0; a.scn_off = e->scn.tab.gid_off;
   return a;
 }
 
@@ -987,8 +1025,8 @@ static SrchArgs search_args(cosim_engine* e) {
 static int search_step(cosim_engine* e, int first, int count, const uint8_t* term, const uint8_t* trunc, hipStream_t s) {
   SrchArgs a = search_args(e);
   a.term = term; a.trunc = trunc; a.first = first; a.count = count;
-  if (e->srch_chk && e->chk.n_scn > 0) {   // an item fails on a check: the same rule with the verdict record checks_step_kernel closed behind this step
-    const SrchChkArgs ca = {a, {e->d_chk_cnt, e->d_chk_rec, CHK_NCNT, e->chk_slots, checks_words(e->chk.I)}};
+  if (e->srch.on_check && e->chk.tab.n_scn > 0) {   // an item fails on a check: the same rule with the verdict record checks_step_kernel closed behind this step
+    const SrchChkArgs ca = {a, {e->chk.cnt.get(), e->chk.rec.get(), CHK_NCNT, e->chk.slots, checks_words(e->chk.tab.I)}};
     return launch_small<64, 64>(search_step_checks_kernel, ca, count, s);
   }
   return launch_small<64, 64>(search_step_kernel, a, count, s);
@@ -996,35 +1034,22 @@ static int search_step(cosim_engine* e, int first, int count, const uint8_t* ter
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode; their levels stay
 static int search_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
-  if (e->srch.n_items <= 0) return COSIM_OK;
+  if (e->srch.tab.n_items <= 0) return COSIM_OK;
   SrchArgs a = search_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
   return launch_small<64, 64>(search_begin_kernel, a, e->n_envs, s);
 }
 
-// the search goes with its table (the caller has waited for the device)
-static void search_free(cosim_engine* e) {
-  (void)hipFree(e->d_srch); (void)hipFree(e->d_srch_rec); (void)hipFree(e->d_srch_ring); (void)hipFree(e->d_srch_rem);
-  e->d_srch = nullptr; e->d_srch_rec = nullptr; e->d_srch_ring = nullptr; e->d_srch_rem = nullptr; e->srch_slots = 0;
-  memset(&e->srch, 0, sizeof e->srch);
-  e->h_srch_has.clear(); e->h_srch_targets.clear(); e->h_srch_lo.clear(); e->h_srch_hi.clear(); e->srch_kinds = 0; e->srch_chk = false;
+// what is set for the rows of a table (the caller has waited for the device): another S drops it
+static void scenario_rows_drop(cosim_engine* e) {
+  e->par = {}; e->obsflt = {}; e->actflt = {}; e->lat = {}; e->chk = {}; e->cur = {};
+  action_rows_release(e);
 }
-
+// the table and everything that goes with it
 static void scenario_free(cosim_engine* e) {
-  search_free(e);
-  scnparams_free(e);
-  obsfault_free(e);
-  actfault_free(e);
-  latency_free(e);
-  checks_free(e);
-  curves_free(e);
-  (void)hipFree(e->d_scn);
-  e->d_scn = nullptr; memset(&e->scn, 0, sizeof e->scn); e->scn_nkey = 0; e->scn_npush = 0; e->scn_cmd_out = nullptr; e->scn_row_out = nullptr;
-}
-
-static void ledger_free(cosim_engine* e) {
-  (void)hipFree(e->d_led_sum); (void)hipFree(e->d_led_peak); (void)hipFree(e->d_led_acc); (void)hipFree(e->d_led_rec);
-  e->d_led_sum = nullptr; e->d_led_peak = nullptr; e->d_led_acc = nullptr; e->d_led_rec = nullptr; e->led_slots = 0;
+  e->srch = {};
+  scenario_rows_drop(e);
+  e->scn = {};
 }
 
 // ---- failure traces (cosim_ftrace.hip)
@@ -1039,12 +1064,12 @@ static int ftrace_words(const cosim_engine* e) {
 static FtArgs ftrace_args(cosim_engine* e) {
   FtArgs a;
   memset(&a, 0, sizeof a);
-  a.state = e->d_state; a.buf = e->d_ft_buf; a.cnt = e->d_ft_cnt;
+  a.state = e->d_state.get(); a.buf = e->ft.buf.get(); a.cnt = e->ft.cnt.get();
   a.n_envs = e->n_envs; a.first = 0; a.count = e->n_envs;
   a.nq = e->model.nq; a.nv = e->model.nv; a.nu = e->model.nu; a.cd = e->ho.command_dim; a.info_dim = e->ho.info_dim; a.F = ftrace_words(e);
   a.s_stride = e->lay.s_stride; a.s_qpos = e->lay.s_qpos; a.s_qvel = e->lay.s_qvel; a.s_meta = e->lay.s_meta;
-  a.frames = e->ft_frames; a.keep = e->ft_keep; a.on_mask = e->ft_mask; a.spawn_rows = e->spawn_rows; a.fall = e->fall_mask != 0;
-  if (e->scn.n_scn > 0) { a.scn_row = e->scn_row_out; a.scn_rows = e->scn.n_scn; a.scn_mode = e->scn.mode; a.scn_off = e->scn.gid_off; }
+  a.frames = e->ft.frames; a.keep = e->ft.keep; a.on_mask = e->ft.mask; a.spawn_rows = e->spawn.rows; a.fall = e->fall_mask != 0;
+  if (e->scn.tab.n_scn > 0) { a.scn_row = e->scn.row_out; a.scn_rows = e->scn.tab.n_scn; a.scn_mode = e->scn.tab.mode; a.scn_off = e->scn.tab.gid_off; }
   return a;
 }
 
@@ -1059,15 +1084,10 @@ static int ftrace_step(cosim_engine* e, int first, int count, const float* actio
 
 // the masked envs (null: all; with a restore's source index: those it did not refuse) begin an episode in an empty window
 static int ftrace_begin(cosim_engine* e, const uint8_t* mask, const int* src, int n_rows, int flag, hipStream_t s) {
-  if (e->ft_frames <= 0) return COSIM_OK;
+  if (e->ft.frames <= 0) return COSIM_OK;
   FtArgs a = ftrace_args(e);
   a.mask = mask; a.src = src; a.n_rows = n_rows; a.flag = flag;
   return launch_small<1, 64>(ftrace_begin_kernel, a, e->n_envs, s);
-}
-
-static void ftrace_free(cosim_engine* e) {
-  (void)hipFree(e->d_ft_buf); (void)hipFree(e->d_ft_cnt);
-  e->d_ft_buf = nullptr; e->d_ft_cnt = nullptr; e->ft_frames = 0; e->ft_keep = 0; e->ft_mask = 0;
 }
 
 // ---- the observers: ledger, failure traces, checks, curves, limit search -- in that order at every site.  Each kernel writes only its own buffers.
@@ -1088,33 +1108,33 @@ static int observers_begin(cosim_engine* e, const uint8_t* mask, const int* src,
 // the same stream: plain device work, capturable.  They only read what the step wrote, and the caller's action rows, which outlive it
 static int observers_step(cosim_engine* e, int first, int count, int rows, const float* actions, const float* cmd, const float* info,
                           const uint8_t* term, const uint8_t* trunc, hipStream_t s) {
-  if (e->led_slots > 0) RC_TRY(ledger_step(e, first, count, rows, info, term, trunc, cmd, s));
-  if (e->ft_frames > 0) RC_TRY(ftrace_step(e, first, count, actions, cmd, info, term, trunc, s));
-  if (e->chk.n_scn > 0) RC_TRY(checks_step(e, first, count, cmd, info, term, trunc, s));
-  if (e->cur.n_scn > 0) RC_TRY(curves_step(e, first, count, cmd, info, term, trunc, s));
-  if (e->srch.n_items > 0 && rows == 1) RC_TRY(search_step(e, first, count, term, trunc, s));   // reads no info row
+  if (e->led.slots > 0) RC_TRY(ledger_step(e, first, count, rows, info, term, trunc, cmd, s));
+  if (e->ft.frames > 0) RC_TRY(ftrace_step(e, first, count, actions, cmd, info, term, trunc, s));
+  if (e->chk.tab.n_scn > 0) RC_TRY(checks_step(e, first, count, cmd, info, term, trunc, s));
+  if (e->cur.tab.n_scn > 0) RC_TRY(curves_step(e, first, count, cmd, info, term, trunc, s));
+  if (e->srch.tab.n_items > 0 && rows == 1) RC_TRY(search_step(e, first, count, term, trunc, s));   // reads no info row
   return COSIM_OK;
 }
 
 // why a step without info_out_dev is refused: the first armed observer's words, null if none is armed
 static const char* observers_info_msg(const cosim_engine* e) {
-  return e->led_slots > 0 ? LEDGER_INFO_MSG : e->ft_frames > 0 ? FTRACE_INFO_MSG : e->chk.n_scn > 0 ? CHECKS_INFO_MSG : e->cur.n_scn > 0 ? CURVES_INFO_MSG : nullptr;
+  return e->led.slots > 0 ? LEDGER_INFO_MSG : e->ft.frames > 0 ? FTRACE_INFO_MSG : e->chk.tab.n_scn > 0 ? CHECKS_INFO_MSG : e->cur.tab.n_scn > 0 ? CURVES_INFO_MSG : nullptr;
 }
 
 // what cosim_policy_table_rotate adds to a table (cosim_poltab.h, poltab_regroup_kernel): `every` 0 means not armed
 struct PolRotate {
   int every = 0;
-  int32_t* d_base = nullptr;      // [n] create's policy_of_row
-  PolRange* d_ranges = nullptr;   // [n_ranges]
-  int32_t* d_ntiles = nullptr;    // [n_ranges] the tiles each range holds now
+  Dev<int32_t> base;       // [n] create's policy_of_row
+  Dev<PolRange> ranges;    // [n_ranges]
+  Dev<int32_t> ntiles;     // [n_ranges] the tiles each range holds now
 };
 
 // what both kinds of table are made of: the device copies of a checked table and the launch shape of every range
 struct TableCore {
   int n = 0, device = 0, K = 0, n_tiles = 0;
-  float* d_image = nullptr;
-  int32_t* d_rows = nullptr;
-  PolTile* d_tiles = nullptr;
+  Dev<float> image;
+  Dev<int32_t> rows;
+  Dev<PolTile> tiles;
   std::vector<int32_t> tile_span;   // [n_ranges][2]: (tile_first, tile_count); armed: (tile_first, capacity)
   std::vector<int32_t> por, ranges; // create's policy_of_row [n] and ranges [n_ranges][2]
   PolRotate rot;
@@ -1122,14 +1142,14 @@ struct TableCore {
 
 // what cosim_policy_table_create hands out: the core, the descriptors and the launch's leading dimension
 struct cosim_policy_table : TableCore {
-  PolDesc* d_desc = nullptr;
-  PolExt* d_ext = nullptr;   // [K] or null: no policy has extras, the plain grouped kernel runs
+  Dev<PolDesc> desc;
+  Dev<PolExt> ext;   // [K] or empty: no policy has extras, the plain grouped kernel runs
   int ld = 0;
 };
 
 // what cosim_recurrent_table_create hands out: as above, with the launch's two leading dimensions and the state tensors' row stride
 struct cosim_recurrent_table : TableCore {
-  RecDesc* d_desc = nullptr;
+  Dev<RecDesc> desc;
   int ld_m = 0, ld_x = 0, hmax = 0;
 };
 
@@ -1148,36 +1168,17 @@ static int kernel_needs_lds(size_t lds, const char* fn) {
   return COSIM_OK;
 }
 
-// Fills a fresh core on the current device from create's checked arrays: the image, the descriptors (`desc_bytes` of them, into
-// *d_desc), the row list and the tile list.  On an error the caller destroys the table, which frees whatever was allocated so far.
-static int table_upload(TableCore& t, const std::vector<float>& image, const void* desc, size_t desc_bytes, void** d_desc, const PolTiles& tl) {
+// Fills a fresh core on the current device from create's checked arrays: the image, the descriptors (into the table's own `desc`),
+// the row list and the tile list.  On an error the caller deletes the table, whose members release what was allocated so far.
+template <class Desc>
+static int table_upload(TableCore& t, const std::vector<float>& image, const std::vector<Desc>& desc, Dev<Desc>& d_desc, const PolTiles& tl) {
   t.n = (int)tl.rows.size(); t.n_tiles = (int)tl.tiles.size(); t.tile_span = tl.tile_span;
   HIP_TRY(hipGetDevice(&t.device));
-  const size_t b_img = image.size() * 4, b_rows = tl.rows.size() * 4, b_tiles = tl.tiles.size() * sizeof(PolTile);
-  HIP_TRY(hipMalloc(&t.d_image, b_img)); HIP_TRY(hipMalloc(d_desc, desc_bytes)); HIP_TRY(hipMalloc(&t.d_rows, b_rows)); HIP_TRY(hipMalloc(&t.d_tiles, b_tiles));
-  HIP_TRY(hipMemcpy(t.d_image, image.data(), b_img, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(*d_desc, desc, desc_bytes, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(t.d_rows, tl.rows.data(), b_rows, hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(t.d_tiles, tl.tiles.data(), b_tiles, hipMemcpyHostToDevice));
+  HIP_TRY(t.image.upload(image.data(), image.size()));
+  HIP_TRY(d_desc.upload(desc.data(), desc.size()));
+  HIP_TRY(t.rows.upload(tl.rows.data(), tl.rows.size()));
+  HIP_TRY(t.tiles.upload(tl.tiles.data(), tl.tiles.size()));
   return COSIM_OK;
-}
-
-// a table's second per-policy record
-static int upload_words(PolExt** dst, const void* src, size_t bytes) {
-  HIP_TRY(hipMalloc(dst, bytes));
-  HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return COSIM_OK;
-}
-
-static void rotate_free(PolRotate& r) {
-  (void)hipFree(r.d_base); (void)hipFree(r.d_ranges); (void)hipFree(r.d_ntiles);
-  r = PolRotate();
-}
-
-// everything table_upload and table_rotate allocated (the descriptors are the table's own)
-static void table_free(TableCore& t) {
-  (void)hipFree(t.d_image); (void)hipFree(t.d_rows); (void)hipFree(t.d_tiles);
-  rotate_free(t.rot);
 }
 
 // ---- rotation, the same for both kinds of table (fn: the entry point's name for the messages)
@@ -1205,24 +1206,16 @@ static int table_rotate(TableCore* p, int every, const std::string& fn) {
   std::vector<PolTile> tiles((size_t)cap_total, PolTile{0, 0, 0, 0});
   for (int i = 0; i < n_ranges; i++)
     for (int j = 0; j < nt[i]; j++) tiles[(size_t)rg[i].tile_first + j] = tl.tiles[(size_t)tl.tile_span[2 * i] + j];
-  PolRotate r;
-  PolTile* d_tiles = nullptr;
-  auto upload = [&]() -> int {
-    HIP_TRY(hipMalloc(&r.d_base, p->por.size() * 4)); HIP_TRY(hipMalloc(&r.d_ranges, rg.size() * sizeof(PolRange)));
-    HIP_TRY(hipMalloc(&r.d_ntiles, nt.size() * 4)); HIP_TRY(hipMalloc(&d_tiles, tiles.size() * sizeof(PolTile)));
-    HIP_TRY(hipMemcpy(r.d_base, p->por.data(), p->por.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r.d_ranges, rg.data(), rg.size() * sizeof(PolRange), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(r.d_ntiles, nt.data(), nt.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_tiles, tiles.data(), tiles.size() * sizeof(PolTile), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(p->d_rows, tl.rows.data(), tl.rows.size() * 4, hipMemcpyHostToDevice));
-    return COSIM_OK;
-  };
-  const int rc = upload();
-  if (rc) { rotate_free(r); (void)hipFree(d_tiles); return rc; }
-  (void)hipFree(p->d_tiles);
-  p->d_tiles = d_tiles; p->n_tiles = cap_total; p->tile_span = span;
+  PolRotate r;   // build, then commit
+  Dev<PolTile> d_tiles;
+  HIP_TRY(r.base.upload(p->por.data(), p->por.size()));
+  HIP_TRY(r.ranges.upload(rg.data(), rg.size()));
+  HIP_TRY(r.ntiles.upload(nt.data(), nt.size()));
+  HIP_TRY(d_tiles.upload(tiles.data(), tiles.size()));
+  HIP_TRY(hipMemcpy(p->rows.get(), tl.rows.data(), tl.rows.size() * 4, hipMemcpyHostToDevice));
+  p->tiles = std::move(d_tiles); p->n_tiles = cap_total; p->tile_span = span;
   r.every = every;
-  p->rot = r;
+  p->rot = std::move(r);
   return COSIM_OK;
 }
 
@@ -1246,8 +1239,8 @@ static int table_forward_checks(TableCore* p, bool pointers, bool rotating, cons
 static int table_regroup(TableCore* p, int32_t* episode_dev, int32_t* policy_now_dev, const uint8_t* done_a_dev, const uint8_t* done_b_dev, int range,
                          hipStream_t s) {
   PolRegroupArgs g;
-  g.base = p->rot.d_base; g.episode = episode_dev; g.policy_now = policy_now_dev; g.done_a = done_a_dev; g.done_b = done_b_dev;
-  g.ranges = p->rot.d_ranges; g.rows = p->d_rows; g.tiles = p->d_tiles; g.n_tiles = p->rot.d_ntiles;
+  g.base = p->rot.base.get(); g.episode = episode_dev; g.policy_now = policy_now_dev; g.done_a = done_a_dev; g.done_b = done_b_dev;
+  g.ranges = p->rot.ranges.get(); g.rows = p->rows.get(); g.tiles = p->tiles.get(); g.n_tiles = p->rot.ntiles.get();
   g.range_first = range < 0 ? 0 : range; g.K = p->K; g.every = p->rot.every;
   hipLaunchKernelGGL(poltab_regroup_kernel, dim3(range < 0 ? (int)p->tile_span.size() / 2 : 1), dim3(RG_THREADS), 0, s, g);
   HIP_TRY(hipGetLastError());
@@ -1264,9 +1257,9 @@ static int table_lists(TableCore* p, int range, int* rows_host, int* tiles_host,
   if (dev != p->device)
     return fail(COSIM_EINVAL, fn + ": the table lives on device " + std::to_string(p->device) + ", the current device is " + std::to_string(dev));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(rows_host, p->d_rows + p->ranges[2 * range], (size_t)p->ranges[2 * range + 1] * 4, hipMemcpyDeviceToHost));
-  HIP_TRY(hipMemcpy(tiles_host, p->d_tiles + p->tile_span[2 * range], (size_t)p->tile_span[2 * range + 1] * sizeof(PolTile), hipMemcpyDeviceToHost));
-  if (p->rot.every) HIP_TRY(hipMemcpy(n_tiles_out, p->rot.d_ntiles + range, 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(rows_host, p->rows.get() + p->ranges[2 * range], (size_t)p->ranges[2 * range + 1] * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tiles_host, p->tiles.get() + p->tile_span[2 * range], (size_t)p->tile_span[2 * range + 1] * sizeof(PolTile), hipMemcpyDeviceToHost));
+  if (p->rot.every) HIP_TRY(hipMemcpy(n_tiles_out, p->rot.ntiles.get() + range, 4, hipMemcpyDeviceToHost));
   else *n_tiles_out = p->tile_span[2 * range + 1];
   return COSIM_OK;
 }
@@ -1346,16 +1339,15 @@ static int policy_table_make(const char* fn, const PolRaw& raw, cosim_policy_tab
   const PolShape shape = validate_policy_table(raw, fn);
   if (!shape.err.empty()) return fail(COSIM_EINVAL, shape.err);
   const PolImage im = pack_policy_image(raw);
-  cosim_policy_table* p = new cosim_policy_table;
+  std::unique_ptr<cosim_policy_table> p(new cosim_policy_table);
   p->K = raw.K; p->ld = shape.maxd | 1;
   p->por.assign(raw.policy_of_row, raw.policy_of_row + raw.n); p->ranges.assign(raw.ranges, raw.ranges + 2 * raw.n_ranges);
   const size_t lds = (size_t)2 * 32 * p->ld * sizeof(float);
   int rc = im.ext.empty() ? kernel_needs_lds<mlp_grouped_kernel>(lds, fn) : kernel_needs_lds<mlp_grouped_ext_kernel>(lds, fn);
-  if (!rc) rc = table_upload(*p, im.words, im.desc.data(), im.desc.size() * sizeof(PolDesc), (void**)&p->d_desc,
-                             build_policy_tiles(raw.policy_of_row, raw.K, raw.ranges, raw.n_ranges));
-  if (!rc && !im.ext.empty()) rc = upload_words(&p->d_ext, im.ext.data(), im.ext.size() * sizeof(PolExt));
-  if (rc) { cosim_policy_table_destroy(p); return rc; }
-  *out = p;
+  if (!rc) rc = table_upload(*p, im.words, im.desc, p->desc, build_policy_tiles(raw.policy_of_row, raw.K, raw.ranges, raw.n_ranges));
+  if (rc) return rc;
+  if (!im.ext.empty()) HIP_TRY(p->ext.upload(im.ext.data(), im.ext.size()));
+  *out = p.release();
   return COSIM_OK;
 }
 
@@ -1378,11 +1370,11 @@ int cosim_policy_table_create_ex(int n_policies, const int* n_layers, const int*
 // synchronisation: the launch can be captured in a graph.
 static int policy_table_launch(cosim_policy_table* p, const float* x_dev, float* out_dev, int range, float clip, hipStream_t s) {
   PolTabArgs a;
-  a.x = x_dev; a.out = out_dev; a.image = p->d_image; a.desc = p->d_desc; a.rows = p->d_rows; a.tiles = p->d_tiles;
+  a.x = x_dev; a.out = out_dev; a.image = p->image.get(); a.desc = p->desc.get(); a.rows = p->rows.get(); a.tiles = p->tiles.get();
   a.tile_first = range < 0 ? 0 : p->tile_span[2 * range]; a.ld = p->ld; a.clip = clip;
   const int tile_count = range < 0 ? p->n_tiles : p->tile_span[2 * range + 1];
   const size_t lds = (size_t)2 * 32 * p->ld * sizeof(float);
-  if (p->d_ext) hipLaunchKernelGGL(mlp_grouped_ext_kernel, dim3(tile_count), dim3(256), lds, s, a, (const PolExt*)p->d_ext);
+  if (p->ext) hipLaunchKernelGGL(mlp_grouped_ext_kernel, dim3(tile_count), dim3(256), lds, s, a, (const PolExt*)p->ext.get());
   else hipLaunchKernelGGL(mlp_grouped_kernel, dim3(tile_count), dim3(256), lds, s, a);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
@@ -1409,9 +1401,6 @@ int cosim_policy_table_lists(cosim_policy_table* p, int range, int* rows_host, i
 }
 
 int cosim_policy_table_destroy(cosim_policy_table* p) {
-  if (!p) return COSIM_OK;
-  (void)hipFree(p->d_desc); (void)hipFree(p->d_ext);
-  table_free(*p);
   delete p;
   return COSIM_OK;
 }
@@ -1435,14 +1424,13 @@ int cosim_recurrent_table_create(int n_policies, const int* n_enc, const int* en
   const RecShape shape = validate_recurrent_table(raw, lds_limit);
   if (!shape.err.empty()) return fail(COSIM_EINVAL, shape.err);
   const RecImage im = pack_recurrent_image(raw);
-  cosim_recurrent_table* p = new cosim_recurrent_table;
+  std::unique_ptr<cosim_recurrent_table> p(new cosim_recurrent_table);
   p->K = n_policies; p->ld_m = shape.ld_m; p->ld_x = shape.ld_x; p->hmax = shape.hmax;
   p->por.assign(policy_of_row, policy_of_row + n); p->ranges.assign(ranges, ranges + 2 * n_ranges);
   int rc = kernel_needs_lds<lstm_actor_grouped_kernel>((size_t)rec_lds_dynamic(p->ld_m, p->ld_x), "cosim_recurrent_table_create");
-  if (!rc) rc = table_upload(*p, im.words, im.desc.data(), im.desc.size() * sizeof(RecDesc), (void**)&p->d_desc,
-                             build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges));
-  if (rc) { cosim_recurrent_table_destroy(p); return rc; }
-  *out = p;
+  if (!rc) rc = table_upload(*p, im.words, im.desc, p->desc, build_policy_tiles(policy_of_row, n_policies, ranges, n_ranges));
+  if (rc) return rc;
+  *out = p.release();
   return COSIM_OK;
 }
 
@@ -1452,7 +1440,7 @@ static int recurrent_table_launch(cosim_recurrent_table* p, const float* x_dev, 
                                   const uint8_t* done_b_dev, int range, float clip, hipStream_t s) {
   RecTabArgs a;
   a.x = x_dev; a.h = h_dev; a.c = c_dev; a.out = out_dev; a.done_a = done_a_dev; a.done_b = done_b_dev;
-  a.image = p->d_image; a.desc = p->d_desc; a.rows = p->d_rows; a.tiles = p->d_tiles;
+  a.image = p->image.get(); a.desc = p->desc.get(); a.rows = p->rows.get(); a.tiles = p->tiles.get();
   a.tile_first = range < 0 ? 0 : p->tile_span[2 * range]; a.ld_m = p->ld_m; a.ld_x = p->ld_x; a.hmax = p->hmax; a.clip = clip;
   const int tile_count = range < 0 ? p->n_tiles : p->tile_span[2 * range + 1];
   hipLaunchKernelGGL(lstm_actor_grouped_kernel, dim3(tile_count), dim3(256), (size_t)rec_lds_dynamic(p->ld_m, p->ld_x), s, a);
@@ -1483,9 +1471,6 @@ int cosim_recurrent_table_lists(cosim_recurrent_table* p, int range, int* rows_h
 }
 
 int cosim_recurrent_table_destroy(cosim_recurrent_table* p) {
-  if (!p) return COSIM_OK;
-  (void)hipFree(p->d_desc);
-  table_free(*p);
   delete p;
   return COSIM_OK;
 }
@@ -1532,7 +1517,7 @@ const char* cosim_last_error(void) { return g_err.c_str(); }
 int cosim_model_sizeof(void) { return (int)sizeof(cosim_model_t); }
 int cosim_obs_config_sizeof(void) { return (int)sizeof(cosim_obs_config_t); }
 
-// everything cosim_create allocates, into a fresh engine; on an error the caller frees whatever was allocated so far (cosim_destroy)
+// everything cosim_create allocates, into a fresh engine; on an error the caller destroys the engine, whose members release what was allocated so far
 static int create_fill(cosim_engine* e, const cosim_model_t* model, const float* hull_vert, const int* hull_adr, const int* hull_nbr,
                        const float* hfield, int n_envs) {
   int rc = build_dev_model(e);
@@ -1594,40 +1579,32 @@ static int create_fill(cosim_engine* e, const cosim_model_t* model, const float*
     for (int g = 0; g < 64; g++) e->hm.g_hullmap[g] = e->hullmap_of_geom[g];
     if (cells.empty()) cells.assign(4 * HM_REC, 0.f);
     if (cand.empty()) cand.assign(4, 0.f);
-    HIP_TRY(hipMalloc(&e->d_hull_cell, cells.size() * sizeof(float)));
-    HIP_TRY(hipMalloc(&e->d_hull_cand, cand.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(e->d_hull_cell, cells.data(), cells.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_hull_cand, cand.data(), cand.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(e->d_hull_cell.upload(reinterpret_cast<const float4*>(cells.data()), cells.size() / 4));
+    HIP_TRY(e->d_hull_cand.upload(reinterpret_cast<const float4*>(cand.data()), cand.size() / 4));
   }
-  HIP_TRY(hipMalloc(&e->d_model, sizeof(DevModel)));
-  HIP_TRY(hipMalloc(&e->d_obs, sizeof(DevObs)));
   e->model_term_mode = e->hm.term_mode; e->model_term_bodymask = e->hm.term_bodymask;
-  HIP_TRY(hipMemcpy(e->d_model, &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
-  HIP_TRY(hipMemcpy(e->d_obs,&e->ho, sizeof(DevObs), hipMemcpyHostToDevice));
-  HIP_TRY(hipMalloc(&e->d_state, (size_t)n_envs * e->lay.s_stride * sizeof(float)));
-  HIP_TRY(hipMemset(e->d_state, 0, (size_t)n_envs * e->lay.s_stride * sizeof(float)));
-  HIP_TRY(hipMalloc(&e->d_params, (size_t)n_envs * e->lay.p_stride * sizeof(float)));
-  HIP_TRY(hipMalloc(&e->d_dbg, 8192 * sizeof(float)));
+  HIP_TRY(e->d_model.upload(&e->hm, 1));
+  HIP_TRY(e->d_obs.upload(&e->ho, 1));
+  HIP_TRY(e->d_state.alloc_zeroed((size_t)n_envs * e->lay.s_stride));
+  HIP_TRY(e->d_params.alloc((size_t)n_envs * e->lay.p_stride));
+  HIP_TRY(e->d_dbg.alloc(8192));
   if (has(e->kernels.solver)) {   // the split pipeline's buffers
-    HIP_TRY(hipMalloc(&e->d_xcon, (size_t)n_envs * XG * XC * 8 * sizeof(float)));
-    HIP_TRY(hipMalloc(&e->d_xcnt, (size_t)n_envs * XG * sizeof(int)));
-    HIP_TRY(hipMalloc(&e->d_xstate, (size_t)n_envs * XS * sizeof(float)));
-    HIP_TRY(hipMemset(e->d_xcnt, 0, (size_t)n_envs * XG * sizeof(int)));
-    HIP_TRY(hipMemset(e->d_xstate, 0, (size_t)n_envs * XS * sizeof(float)));
+    HIP_TRY(e->d_xcon.alloc((size_t)n_envs * XG * XC * 8));
+    HIP_TRY(e->d_xcnt.alloc_zeroed((size_t)n_envs * XG));
+    HIP_TRY(e->d_xstate.alloc_zeroed((size_t)n_envs * XS));
   }
-  HIP_TRY(hipMalloc(&e->d_ovf, (size_t)n_envs * sizeof(int)));
-  HIP_TRY(hipMemset(e->d_ovf, 0, (size_t)n_envs * sizeof(int)));
+  HIP_TRY(e->d_ovf.alloc_zeroed((size_t)n_envs));
   int nhv = model->nhullvert > 0 ? model->nhullvert : 1, nhe = model->nhulledge > 0 ? model->nhulledge : 1;
-  HIP_TRY(hipMalloc(&e->d_hull_vert, (size_t)nhv * 4 * sizeof(float)));   // 16 bytes per vertex on the device: one load each
-  HIP_TRY(hipMalloc(&e->d_hull_adr, (size_t)(nhv + 1) * sizeof(int)));
-  HIP_TRY(hipMalloc(&e->d_hull_nbr, (size_t)nhe * sizeof(int)));
+  HIP_TRY(e->d_hull_vert.alloc((size_t)nhv * 4));   // 16 bytes per vertex on the device: one load each
+  HIP_TRY(e->d_hull_adr.alloc((size_t)nhv + 1));
+  HIP_TRY(e->d_hull_nbr.alloc((size_t)nhe));
   if (model->nhullvert > 0) {
     if (!hull_vert || !hull_adr || !hull_nbr) return fail(COSIM_EINVAL, "cosim_create: model has mesh geoms but no hull arrays were passed");
     std::vector<float> hv4((size_t)model->nhullvert * 4, 0.f);
     for (int i = 0; i < model->nhullvert; i++) for (int k = 0; k < 3; k++) hv4[4 * (size_t)i + k] = hull_vert[3 * (size_t)i + k];
-    HIP_TRY(hipMemcpy(e->d_hull_vert, hv4.data(), hv4.size() * sizeof(float), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_hull_adr, hull_adr, (size_t)(model->nhullvert + 1) * sizeof(int), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_hull_nbr, hull_nbr, (size_t)model->nhulledge * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_hull_vert.get(), hv4.data(), hv4.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_hull_adr.get(), hull_adr, (size_t)(model->nhullvert + 1) * sizeof(int), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_hull_nbr.get(), hull_nbr, (size_t)model->nhulledge * sizeof(int), hipMemcpyHostToDevice));
   }
   {
     std::vector<unsigned> hp(model->npair > 0 ? model->npair : 1, 0u);
@@ -1635,18 +1612,15 @@ static int create_fill(cosim_engine* e, const cosim_model_t* model, const float*
     std::vector<float4> hg(model->ngeom > 0 ? model->ngeom : 1);
     for (int g = 0; g < model->ngeom; g++)
       hg[g] = make_float4((float)model->geom_center[g][0], (float)model->geom_center[g][1], (float)model->geom_center[g][2], (float)model->geom_friction[g][0]);
-    HIP_TRY(hipMalloc(&e->d_pairs, hp.size() * sizeof(unsigned)));
-    HIP_TRY(hipMalloc(&e->d_gext, hg.size() * sizeof(float4)));
-    HIP_TRY(hipMemcpy(e->d_pairs, hp.data(), hp.size() * sizeof(unsigned), hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(e->d_gext, hg.data(), hg.size() * sizeof(float4), hipMemcpyHostToDevice));
+    HIP_TRY(e->d_pairs.upload(hp.data(), hp.size()));
+    HIP_TRY(e->d_gext.upload(hg.data(), hg.size()));
   }
   if (model->ground_type == CS_GEOM_HFIELD) {
     // any cell size: the narrowphase walks however many prisms lie under a geom (1 cm cells of the stairs_* terrains included);
     // contacts beyond the kernel variant's slots are counted (cosim_get "meta", word 8), never dropped silently
     if (!hfield) return fail(COSIM_EINVAL, "cosim_create: heightfield ground but no elevation data was passed");
     size_t nh = (size_t)model->hfield_nrow * model->hfield_ncol;
-    HIP_TRY(hipMalloc(&e->d_hfield, nh * sizeof(float)));
-    HIP_TRY(hipMemcpy(e->d_hfield, hfield, nh * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(e->d_hfield.upload(hfield, nh));
     // tile maxima for the coarse terrain test ahead of the prism walk (terrain_max_under)
     const int mrow = (model->hfield_nrow + HF_TILE - 1) / HF_TILE, mcol = (model->hfield_ncol + HF_TILE - 1) / HF_TILE;
     std::vector<float> mip((size_t)mrow * mcol, 0.f);
@@ -1656,8 +1630,7 @@ static int create_fill(cosim_engine* e, const cosim_model_t* model, const float*
         const float h = hfield[(size_t)r * model->hfield_ncol + c];
         m = ((r % HF_TILE) == 0 && (c % HF_TILE) == 0) ? h : (h > m ? h : m);
       }
-    HIP_TRY(hipMalloc(&e->d_hfield_mip, mip.size() * sizeof(float)));
-    HIP_TRY(hipMemcpy(e->d_hfield_mip, mip.data(), mip.size() * sizeof(float), hipMemcpyHostToDevice));
+    HIP_TRY(e->d_hfield_mip.upload(mip.data(), mip.size()));
   }
   default_params(e);
   return set_ranges(e, 1);   // (allocates the pacing events of the single-launch path)
@@ -1675,7 +1648,7 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
   cosim_engine* e = new cosim_engine();
   e->n_envs = n_envs; e->device = device; e->model = *model; e->obs_cfg = *obs; e->seed = seed; e->env_id0 = env_id0;
   const int rc = create_fill(e, model, hull_vert, hull_adr, hull_nbr, hfield, n_envs);
-  if (rc != COSIM_OK) {   // one cleanup path: the engine, its buffers, streams and events (the message survives it)
+  if (rc != COSIM_OK) {   // one cleanup path: the engine's streams and events, then the engine with its buffers (the message survives it)
     const std::string msg = g_err;
     cosim_destroy(e);
     g_err = msg;
@@ -1688,22 +1661,12 @@ int cosim_create(const cosim_model_t* model, const float* hull_vert, const int* 
 int cosim_destroy(cosim_engine_t* e) {
   if (!e) return COSIM_OK;
   hipSetDevice(e->device);
-  hipFree(e->d_model); hipFree(e->d_obs); hipFree(e->d_state); hipFree(e->d_params); hipFree(e->d_dbg);
-  hipFree(e->d_hull_vert); hipFree(e->d_hull_adr); hipFree(e->d_hull_nbr); hipFree(e->d_hfield);
-  hipFree(e->d_hull_cell); hipFree(e->d_hull_cand); hipFree(e->d_hfield_mip);
-  hipFree(e->d_spawn);
-  hipFree(e->d_hist); hipFree(e->d_snap_err);
-  ledger_free(e);
-  ftrace_free(e);
-  scenario_free(e);
-  if (e->h_snap_err) hipHostFree(e->h_snap_err);
-  hipFree(e->d_pairs); hipFree(e->d_gext); hipFree(e->d_ovf); hipFree(e->d_xcon); hipFree(e->d_xcnt); hipFree(e->d_xstate);
   for (hipEvent_t x : e->ev) hipEventDestroy(x);
   for (hipStream_t x : e->rstream) hipStreamDestroy(x);
   for (hipEvent_t x : e->rdone) hipEventDestroy(x);
   for (hipEvent_t x : e->ring) hipEventDestroy(x);   // the pacing events: [n_streams][inflight]
   if (e->ev_in) hipEventDestroy(e->ev_in);
-  delete e;
+  delete e;   // every buffer goes with the member that owns it
   return COSIM_OK;
 }
 
@@ -1717,22 +1680,22 @@ static int ls_cap(const cosim_engine* e) { return e->max_ls < 0 ? e->model.ls_it
 // "scenario_curve_ungrouped": joins the ranges, waits and reads the device word (0 with no groups); held at INT_MAX
 // envs with a search item that have trials left (cosim_query "search_remaining"): joins the ranges and reads the one word
 static int search_remaining(cosim_engine* e) {
-  if (e->srch.n_items <= 0) return 0;
+  if (e->srch.tab.n_items <= 0) return 0;
   HIP_TRY(hipSetDevice(e->device));
   RC_TRY(join_ranges(e, 0));
   HIP_TRY(hipDeviceSynchronize());
   int v = 0;
-  HIP_TRY(hipMemcpy(&v, e->d_srch_rem, sizeof v, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&v, e->srch.rem.get(), sizeof v, hipMemcpyDeviceToHost));
   return v;
 }
 
 static int curves_ungrouped(cosim_engine* e) {
-  if (e->cur_groups <= 0) return 0;
+  if (e->cur.groups <= 0) return 0;
   HIP_TRY(hipSetDevice(e->device));
   RC_TRY(join_ranges(e, 0));
   HIP_TRY(hipDeviceSynchronize());
   unsigned v = 0;
-  HIP_TRY(hipMemcpy(&v, e->d_cur_ungrouped, sizeof v, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&v, e->cur.ungrouped.get(), sizeof v, hipMemcpyDeviceToHost));
   return v > 2147483647u ? 2147483647 : (int)v;
 }
 
@@ -1764,42 +1727,43 @@ int cosim_query(const cosim_engine_t* e, const char* name) {
   if (n == "max_newton") return newton_cap(e);   // Newton iterations per substep the solver may take
   if (n == "max_ls") return ls_cap(e);           // line-search evaluations per Newton iteration
   if (n == "frame_skip") return e->model.frame_skip;
-  if (n == "spawn_rows") return e->spawn_rows;   // rows of the spawn table (0: none, resets go to init_qpos)
-  if (n == "spawn_mode") return e->spawn_mode;   // 0: row = global env id mod rows; 1: drawn per episode
+  if (n == "spawn_rows") return e->spawn.rows;   // rows of the spawn table (0: none, resets go to init_qpos)
+  if (n == "spawn_mode") return e->spawn.mode;   // 0: row = global env id mod rows; 1: drawn per episode
   if (n == "snapshot_floats") return e->lay.s_stride + e->lay.p_stride;   // float32 words of a snapshot row: state record + parameter record
-  if (n == "history_slots") return e->hist_slots;
-  if (n == "history_every") return e->hist_every;
-  if (n == "ledger_slots") return e->led_slots;   // records per env the episode ledger keeps (0: no ledger, no ledger launches)
-  if (n == "ftrace_frames") return e->ft_frames;  // frames per failure-trace window (0: no traces, no trace launches)
-  if (n == "ftrace_keep") return e->ft_keep;      // traces kept per env
+  if (n == "history_slots") return e->hist.slots;
+  if (n == "history_every") return e->hist.every;
+  if (n == "ledger_slots") return e->led.slots;   // records per env the episode ledger keeps (0: no ledger, no ledger launches)
+  if (n == "ftrace_frames") return e->ft.frames;  // frames per failure-trace window (0: no traces, no trace launches)
+  if (n == "ftrace_keep") return e->ft.keep;      // traces kept per env
   if (n == "ftrace_frame_words") return ftrace_words(e);   // F: 32-bit words of a frame for this model (answered with traces off too)
-  if (n == "ftrace_mask") return e->ft_mask;      // ledger flags that freeze a window
-  if (n == "scenario_rows") return e->scn.n_scn;  // scenarios of the table (0: none, no scenario launches)
-  if (n == "scenario_param_items") return e->scnpar.n_items;   // expanded parameter-window items of the table (0: none, no launches)
-  if (n == "obs_faults") return e->obsflt.n_items;   // expanded observation-fault items of the table (0: none, no launches)
+  if (n == "ftrace_mask") return e->ft.mask;      // ledger flags that freeze a window
+  if (n == "scenario_rows") return e->scn.tab.n_scn;  // scenarios of the table (0: none, no scenario launches)
+  if (n == "scenario_param_items") return e->par.tab.n_items;   // expanded parameter-window items of the table (0: none, no launches)
+  if (n == "obs_faults") return e->obsflt.tab.n_items;   // expanded observation-fault items of the table (0: none, no launches)
   if (n == "launches") return (int)(g_launches.load(std::memory_order_relaxed) & 0x7fffffffu);   // kernel launches the engines of this process have issued through launch_k / launch_small, modulo 2^31 (a capture counts what it records, a replay nothing)
-  if (n == "latency") return e->lat.n_act + e->lat.n_obs;   // expanded latency items of the table, both kinds (0: none, no launches, no pointer changes)
-  if (n == "latency_action_items") return e->lat.n_act;     // ... of the command channel
-  if (n == "latency_obs_items") return e->lat.n_obs;        // ... of observation elements
-  if (n == "latency_depth") return e->lat.depth;            // D: clocks a line holds (0: none)
-  if (n == "action_faults") return e->actflt.n_items;   // expanded action-fault items of the table (0: none, no launches, the caller's action pointer)
-  if (n == "scenario_check_items") return e->chk.n_scn > 0 ? e->chk.I : 0;   // I: items per env a verdict record holds (0: no checks, no launches)
-  if (n == "scenario_check_slots") return e->chk_slots;                      // verdict records per env
-  if (n == "scenario_curve_items") return e->cur.n_items;   // curve items of the table (0: no curves, no launches)
-  if (n == "scenario_curve_words") return (int)e->cur_words;   // 32-bit words of all cells (at most 2^26)
-  if (n == "scenario_curve_groups") return e->cur_groups;   // G of cosim_scenario_curves_groups (0: no groups)
+  if (n == "device_buffers") return g_device_buffers.load(std::memory_order_relaxed);   // device allocations of this library that are live in this process, every engine and table together: equal before and after means nothing leaked
+  if (n == "latency") return e->lat.tab.n_act + e->lat.tab.n_obs;   // expanded latency items of the table, both kinds (0: none, no launches, no pointer changes)
+  if (n == "latency_action_items") return e->lat.tab.n_act;     // ... of the command channel
+  if (n == "latency_obs_items") return e->lat.tab.n_obs;        // ... of observation elements
+  if (n == "latency_depth") return e->lat.tab.depth;            // D: clocks a line holds (0: none)
+  if (n == "action_faults") return e->actflt.tab.n_items;   // expanded action-fault items of the table (0: none, no launches, the caller's action pointer)
+  if (n == "scenario_check_items") return e->chk.tab.n_scn > 0 ? e->chk.tab.I : 0;   // I: items per env a verdict record holds (0: no checks, no launches)
+  if (n == "scenario_check_slots") return e->chk.slots;                      // verdict records per env
+  if (n == "scenario_curve_items") return e->cur.tab.n_items;   // curve items of the table (0: no curves, no launches)
+  if (n == "scenario_curve_words") return (int)e->cur.words;   // 32-bit words of all cells (at most 2^26)
+  if (n == "scenario_curve_groups") return e->cur.groups;   // G of cosim_scenario_curves_groups (0: no groups)
   if (n == "scenario_curve_ungrouped") return curves_ungrouped(const_cast<cosim_engine_t*>(e));   // synchronising: joins, reads one device word
-  if (n == "scenario_curve_stage_words") return e->cur.n_scn > 0 ? e->cur.SW : 0;   // stage words per env
-  if (n == "scenario_check_words") return e->chk.n_scn > 0 ? checks_words(e->chk.I) : 0;   // 32-bit words of a verdict record: 8 + 2 I
-  if (n == "search") return e->srch.n_items;      // scenarios of the table with a search item armed (0: no search, no launches, scenario_step_kernel)
-  if (n == "search_slots") return e->srch_slots;  // trial records per env
-  if (n == "search_targets") return e->srch.n_items > 0 ? e->srch_kinds : 0;   // union of the armed items' targets (16: actfault_search_step_kernel in the place of actfault_step_kernel)
-  if (n == "search_checks") return e->srch.n_items > 0 && e->srch_chk;          // an armed item fails on a check (search_step_checks_kernel in the place of search_step_kernel)
-  if (n == "action_faults_marked") return e->actflt_marked;                     // action-fault items the search scales
-  if (n == "obs_faults_marked") return e->obsflt_marked;                        // observation-fault items the search scales
-  if (n == "scenario_param_items_marked") return e->scnpar_marked;              // parameter items the search scales
+  if (n == "scenario_curve_stage_words") return e->cur.tab.n_scn > 0 ? e->cur.tab.SW : 0;   // stage words per env
+  if (n == "scenario_check_words") return e->chk.tab.n_scn > 0 ? checks_words(e->chk.tab.I) : 0;   // 32-bit words of a verdict record: 8 + 2 I
+  if (n == "search") return e->srch.tab.n_items;      // scenarios of the table with a search item armed (0: no search, no launches, scenario_step_kernel)
+  if (n == "search_slots") return e->srch.slots;  // trial records per env
+  if (n == "search_targets") return e->srch.tab.n_items > 0 ? e->srch.kinds : 0;   // union of the armed items' targets (16: actfault_search_step_kernel in the place of actfault_step_kernel)
+  if (n == "search_checks") return e->srch.tab.n_items > 0 && e->srch.on_check;          // an armed item fails on a check (search_step_checks_kernel in the place of search_step_kernel)
+  if (n == "action_faults_marked") return e->actflt.marked;                     // action-fault items the search scales
+  if (n == "obs_faults_marked") return e->obsflt.marked;                        // observation-fault items the search scales
+  if (n == "scenario_param_items_marked") return e->par.marked;              // parameter items the search scales
   if (n == "search_remaining") return search_remaining(const_cast<cosim_engine_t*>(e));   // synchronising: joins, reads one device word
-  if (n == "scenario_mode") return e->scn.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
+  if (n == "scenario_mode") return e->scn.tab.mode;   // 0: row = global env id mod rows; 1: advanced by one per episode of the env
   if (n == "fall") return e->fall_mask;           // fall rules in force (cosim_fall_set): 1 tilt | 2 height | 4 body contact; 0: none
   return fail(COSIM_EINVAL, "cosim_query: unknown name " + n);
 }
@@ -1863,7 +1827,7 @@ int cosim_set_param(cosim_engine_t* e, const char* name, const float* host, int 
   else if (n == "support_map") {   // 0: mesh support queries scan the whole hull (A/B and tests); 1: through the support maps (default)
     HIP_TRY(hipDeviceSynchronize());
     for (int g = 0; g < 64; g++) e->hm.g_hullmap[g] = (int)host[0] != 0 ? e->hullmap_of_geom[g] : -1;
-    HIP_TRY(hipMemcpy(e->d_model, &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_model.get(), &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
     return COSIM_OK;
   }
   else if (is_switch(n)) {   // "split", "narrow_occupancy", "step_kernel", "fixup", "hfield_fixup", "contact_twist", "envs_per_wave": DESIGN 4.17
@@ -1902,18 +1866,18 @@ static int drain_events(cosim_engine* e) {
 static KArgs base_args(cosim_engine* e) {
   KArgs a;
   memset(&a, 0, sizeof a);
-  a.dm = e->d_model; a.ob = e->d_obs; a.lay = e->lay; a.state = e->d_state;
-  a.params = e->scnpar.n_items > 0 ? e->d_params_eff : e->d_params;   // parameter windows: the effective records (cosim_scnparams.hip)
-  a.hull_vert = e->d_hull_vert; a.hull_adr = e->d_hull_adr; a.hull_nbr = e->d_hull_nbr; a.hfield = e->d_hfield;
-  a.hull_cell = e->d_hull_cell; a.hull_cand = e->d_hull_cand; a.hfield_mip = e->d_hfield_mip;
-  a.pairs = e->d_pairs; a.gext = e->d_gext;
+  a.dm = e->d_model.get(); a.ob = e->d_obs.get(); a.lay = e->lay; a.state = e->d_state.get();
+  a.params = e->par.tab.n_items > 0 ? e->par.eff.get() : e->d_params.get();   // parameter windows: the effective records (cosim_scnparams.hip)
+  a.hull_vert = e->d_hull_vert.get(); a.hull_adr = e->d_hull_adr.get(); a.hull_nbr = e->d_hull_nbr.get(); a.hfield = e->d_hfield.get();
+  a.hull_cell = e->d_hull_cell.get(); a.hull_cand = e->d_hull_cand.get(); a.hfield_mip = e->d_hfield_mip.get();
+  a.pairs = e->d_pairs.get(); a.gext = e->d_gext.get();
   a.n_envs = e->n_envs; a.seed_lo = (unsigned)e->seed; a.seed_hi = (unsigned)(e->seed >> 32); a.env_id0 = e->env_id0;
   a.tol32 = e->tol32; a.ls_scale = e->ls_scale; a.max_newton = newton_cap(e); a.max_ls = ls_cap(e); a.nsub_override = e->nsub_override; a.pair_coop = e->pair_coop; a.pair_boxbox = e->pair_boxbox; a.block_cull = e->block_cull; a.coop_walk = e->coop_walk;
   for (int k = 0; k < 4; k++) a.prio[k] = e->prio[k];
   a.ovf = nullptr; a.roll_steps = 1;
-  a.spawn = e->d_spawn; a.spawn_rows = e->spawn_rows; a.spawn_mode = e->spawn_mode;
-  a.spawn_off = e->spawn_rows > 0 ? (unsigned)(((e->env_id0 % e->spawn_rows) + e->spawn_rows) % e->spawn_rows) : 0u;
-  a.xcon = e->d_xcon; a.xcnt = e->d_xcnt; a.xstate = e->d_xstate; a.nw = e->narrow_waves; a.sub_index = 0; a.sub_total = 0;
+  a.spawn = e->spawn.table.get(); a.spawn_rows = e->spawn.rows; a.spawn_mode = e->spawn.mode;
+  a.spawn_off = e->spawn.rows > 0 ? (unsigned)(((e->env_id0 % e->spawn.rows) + e->spawn.rows) % e->spawn.rows) : 0u;
+  a.xcon = e->d_xcon.get(); a.xcnt = e->d_xcnt.get(); a.xstate = e->d_xstate.get(); a.nw = e->narrow_waves; a.sub_index = 0; a.sub_total = 0;
   a.fall_min_up = e->fall_min_up; a.fall_min_height = e->fall_min_height; a.fall_grace = e->fall_grace; a.fall_mask = e->fall_mask;
   return a;
 }
@@ -1923,18 +1887,18 @@ int cosim_reset(cosim_engine_t* e, const uint8_t* mask_dev, const float* command
   HIP_TRY(hipSetDevice(e->device));
   RC_TRY(upload_params(e));
   RC_TRY(join_ranges(e, (hipStream_t)stream));
-  if (e->scn.n_scn > 0) {   // the reset's state vector carries the scenario's first command
+  if (e->scn.tab.n_scn > 0) {   // the reset's state vector carries the scenario's first command
     if (e->ho.command_dim > 0 && !commands_dev)
       return fail(COSIM_EINVAL, "cosim_reset: a scenario table is set (cosim_scenario_set) and commands_dev is NULL: the scenario kernel passes the caller's command through where a scenario has no keyframe yet");
     RC_TRY(scenario_launch(e, 0, e->n_envs, commands_dev, mask_dev, 1, (hipStream_t)stream));
-    if (e->scnpar.n_items > 0) RC_TRY(scnparams_launch(e, 0, e->n_envs, mask_dev, 1, (hipStream_t)stream));
+    if (e->par.tab.n_items > 0) RC_TRY(scnparams_launch(e, 0, e->n_envs, mask_dev, 1, (hipStream_t)stream));
   }
   KArgs a = base_args(e);
   a.mode = MODE_RESET; a.mask = mask_dev; a.commands = scenario_cmd(e, commands_dev); a.state_out = state_out_dev;
   e->plan.reset.launch(e, a, e->n_envs, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
-  if (e->lat.n_obs > 0) RC_TRY(latency_obs_launch(e, 0, e->n_envs, state_out_dev, mask_dev, (hipStream_t)stream));   // clock 0: the line restarts with the first reading
-  if (e->obsflt.n_items > 0) RC_TRY(obsfault_launch(e, 0, e->n_envs, state_out_dev, mask_dev, (hipStream_t)stream));   // the reset's observation is a fill at clock 0
+  if (e->lat.tab.n_obs > 0) RC_TRY(latency_obs_launch(e, 0, e->n_envs, state_out_dev, mask_dev, (hipStream_t)stream));   // clock 0: the line restarts with the first reading
+  if (e->obsflt.tab.n_items > 0) RC_TRY(obsfault_launch(e, 0, e->n_envs, state_out_dev, mask_dev, (hipStream_t)stream));   // the reset's observation is a fill at clock 0
   if (mask_dev == nullptr) e->stepped = false;
   return observers_begin(e, mask_dev, nullptr, 0, 0, (hipStream_t)stream);
 }
@@ -1946,7 +1910,7 @@ int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* command
     HIP_TRY(hipSetDevice(e->device));
     hipStreamCaptureStatus cap1 = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap1));
-    if (e->hist_slots > 0 && cap1 != hipStreamCaptureStatusNone) return fail(COSIM_EINVAL, HIST_CAPTURE_MSG);
+    if (e->hist.slots > 0 && cap1 != hipStreamCaptureStatusNone) return fail(COSIM_EINVAL, HIST_CAPTURE_MSG);
     const bool paced = e->inflight > 0 && cap1 == hipStreamCaptureStatusNone && (int)e->ring.size() >= e->inflight;
     if (paced && e->ring_pos >= e->inflight) HIP_TRY(hipEventSynchronize(e->ring[e->ring_pos % e->inflight]));
     int rc = cosim_step_range(e, 0, e->n_envs, actions_dev, commands_dev, state_out_dev, terminated_dev, truncated_dev, info_out_dev, stream);
@@ -1966,7 +1930,7 @@ int cosim_step(cosim_engine_t* e, const float* actions_dev, const float* command
   // an idle caller stream).  Not while capturing: a query is illegal there, and the fork edge is what ties the range streams in.
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   HIP_TRY(hipStreamIsCapturing(cs, &cap));
-  if (e->hist_slots > 0 && cap != hipStreamCaptureStatusNone) return fail(COSIM_EINVAL, HIST_CAPTURE_MSG);
+  if (e->hist.slots > 0 && cap != hipStreamCaptureStatusNone) return fail(COSIM_EINVAL, HIST_CAPTURE_MSG);
   bool wait_in = true;
   if (cap == hipStreamCaptureStatusNone) {
     const hipError_t q = hipStreamQuery(cs);
@@ -2004,12 +1968,12 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
   const Plan<launch_fn>& p = e->plan;
   if (!has(p.rollout)) return fail(COSIM_EINVAL, "cosim_rollout: no rollout kernel for this model / terrain / kernel variant");
   if (e->ho.command_dim > 0 && !commands_dev) return fail(COSIM_EINVAL, "cosim_rollout: commands_dev is required when command_dim > 0");
-  if (e->led_slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_rollout") + LEDGER_INFO_MSG);
-  if (e->ft_frames > 0)
+  if (e->led.slots > 0 && !info_out_dev) return fail(COSIM_EINVAL, std::string("cosim_rollout") + LEDGER_INFO_MSG);
+  if (e->ft.frames > 0)
     return fail(COSIM_EINVAL, "cosim_rollout: failure traces are set (cosim_ftrace_set): one launch leaves one state record for all its steps, so the per-step state is not there to copy; step with cosim_step or switch the traces off");
-  if (e->lat.n_act + e->lat.n_obs > 0)
+  if (e->lat.tab.n_act + e->lat.tab.n_obs > 0)
     return fail(COSIM_EINVAL, "cosim_rollout: latency is set (cosim_set_param \"latency\"): one launch takes all its steps and the delay lines are written between steps; step with cosim_step or clear the latency");
-  if (e->scn.n_scn > 0)
+  if (e->scn.tab.n_scn > 0)
     return fail(COSIM_EINVAL, "cosim_rollout: a scenario table is set (cosim_scenario_set): one launch reads one command row; step with cosim_step or clear the table");
   e->stepped = true;
   HIP_TRY(hipSetDevice(e->device));
@@ -2019,7 +1983,7 @@ int cosim_rollout(cosim_engine_t* e, int steps, const float* actions_dev, const 
   KArgs a = base_args(e);
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = commands_dev; a.state_out = state_out_dev;
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev; a.roll_steps = steps;
-  a.ovf = has(p.rollout_fix) ? e->d_ovf : nullptr;
+  a.ovf = has(p.rollout_fix) ? e->d_ovf.get() : nullptr;
   const int nr = e->n_ranges > 1 ? e->n_streams : 1;   // launch sequences: one per group of ranges
   if (e->n_ranges > 1) HIP_TRY(hipEventRecord(e->ev_in, cs));
   for (int i = 0; i < nr; i++) {
@@ -2112,9 +2076,9 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   a.terminated = terminated_dev; a.truncated = truncated_dev; a.info = info_out_dev;
   a.env_first = first; a.env_count = count;
   const Plan<launch_fn>& p = e->plan;
-  if (p.narrow_diag) a.dbg = e->d_dbg;   // diagnostic narrowphase build accumulates its counters there
+  if (p.narrow_diag) a.dbg = e->d_dbg.get();   // diagnostic narrowphase build accumulates its counters there
   // the fix-up behind this launch: the split pipeline's after each solver launch ("hfield_fixup"), else the one after the fleet kernel
-  a.ovf = has(p.fixup) ? e->d_ovf : nullptr;
+  a.ovf = has(p.fixup) ? e->d_ovf.get() : nullptr;
   hipStream_t s = (hipStream_t)stream;
   // kernel timing: one HIP event pair per launch on the launch stream, read back in cosim_kernel_time() (no sync here)
   int slot = -1;
@@ -2129,22 +2093,22 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   }
   // scenario table: this step's command and push of every env of the range, ahead of the step's first launch (plain device work:
   // capturable); inside the timing pair, so cosim_kernel_time() includes it
-  if (e->scn.n_scn > 0) RC_TRY(scenario_launch(e, first, count, commands_dev, nullptr, 0, s));
+  if (e->scn.tab.n_scn > 0) RC_TRY(scenario_launch(e, first, count, commands_dev, nullptr, 0, s));
   // parameter windows: this step's effective parameter records of the range, ahead of every launch that reads them (the substep
   // launches of the split pipeline and the fix-up kernels' redo included: all are handed the same pointer by base_args)
-  if (e->scnpar.n_items > 0) RC_TRY(scnparams_launch(e, first, count, nullptr, 0, s));
+  if (e->par.tab.n_items > 0) RC_TRY(scnparams_launch(e, first, count, nullptr, 0, s));
   // action faults: this step's effective actions of the range, ahead of every launch that reads the action (the fused and step-only
   // kernels, the two-envs-per-wave kernel, the split pipeline's first substep and the fix-up kernels' redo: all read a.actions)
   // latency comes first: the delivered action is what the action faults take as the caller's word; with latency alone the step
   // kernels read the delivered rows themselves
-  const bool act_faults = e->actflt.n_items > 0, act_lat = e->lat.n_act > 0;
+  const bool act_faults = e->actflt.tab.n_items > 0, act_lat = e->lat.tab.n_act > 0;
   if (act_lat) {
     RC_TRY(latency_act_launch(e, first, count, actions_dev, s));
-    a.actions = e->d_actions_eff;
+    a.actions = e->act.eff.get();
   }
   if (act_faults) {
-    RC_TRY(actfault_launch(e, first, count, act_lat ? e->d_lat_eff : actions_dev, act_lat ? e->d_lat_spare : e->d_actions_raw, s));
-    a.actions = e->d_actions_eff;
+    RC_TRY(actfault_launch(e, first, count, act_lat ? e->lat.eff.get() : actions_dev, act_lat ? e->lat.spare.get() : e->act.raw.get(), s));
+    a.actions = e->act.eff.get();
   }
   if (p.split) {
     // one pair of launches per substep: the prism walk (narrow_waves waves per env), then the solver with the contacts it left; with
@@ -2161,7 +2125,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
     }
   } else p.step.launch(e, a, count, s);
   HIP_TRY(hipGetLastError());
-  const bool faults = e->obsflt.n_items > 0;   // observation faults: the timing pair closes behind their launch
+  const bool faults = e->obsflt.tab.n_items > 0;   // observation faults: the timing pair closes behind their launch
   if (slot >= 0 && !faults) HIP_TRY(hipEventRecord(e->ev[slot + 1], s));
   if (a.ovf && !p.split) {   // envs the fleet kernel flagged (more contacts than it has slots for) are redone by the large-capacity kernel
     p.fixup.launch(e, a, count, s);
@@ -2172,7 +2136,7 @@ int cosim_step_range(cosim_engine_t* e, int first, int count, const float* actio
   // action faults: last_action is what the policy put out, not what the bus delivered; the observation faults compose on top
   if ((act_faults || act_lat) && e->act_in_obs) RC_TRY(actfault_obs_launch(e, first, count, state_out_dev, s));
   // latency of observation elements: on the newest frame as the step (and the restore above) left it, ahead of the observation faults
-  if (e->lat.n_obs > 0) RC_TRY(latency_obs_launch(e, first, count, state_out_dev, nullptr, s));
+  if (e->lat.tab.n_obs > 0) RC_TRY(latency_obs_launch(e, first, count, state_out_dev, nullptr, s));
   // While a search scales observation faults the launch goes BEHIND the observers: the observation a step that ended an episode
   // returns is clock 0 of the next one and takes the level search_step_kernel has just moved.  No observer reads what the fault kernel
   // writes (stack row 0 of the record, state_out): they read the info row, the flags, the command, qpos / qvel and the meta words, so
@@ -2203,8 +2167,7 @@ int cosim_spawn_set(cosim_engine_t* e, const float* xyyaw_host, int rows, const 
   { int rc = join_ranges(e, cs); if (rc) return rc; }
   if (rows == 0) {   // clear: resets go back to init_qpos (launches already enqueued keep the table they were given)
     HIP_TRY(hipStreamSynchronize(cs));
-    HIP_TRY(hipFree(e->d_spawn));
-    e->d_spawn = nullptr; e->spawn_rows = 0; e->spawn_mode = 0; e->h_spawn.clear();
+    e->spawn = {};
     return COSIM_OK;
   }
   const cosim_model_t& m = e->model;
@@ -2229,38 +2192,31 @@ int cosim_spawn_set(cosim_engine_t* e, const float* xyyaw_host, int rows, const 
         return fail(COSIM_EINVAL, "cosim_spawn_set: row " + std::to_string(r) + " puts footprint geom " + std::to_string(g) + " off the heightfield");
     }
   }
-  if (rows != e->spawn_rows) {   // a new size: a new table (the same size is rewritten in place, the pointer stays for captured graphs)
+  if (rows != e->spawn.rows) {   // a new size: a new table (the same size is rewritten in place, the pointer stays for captured graphs)
     HIP_TRY(hipStreamSynchronize(cs));
-    HIP_TRY(hipFree(e->d_spawn));
-    e->d_spawn = nullptr; e->spawn_rows = 0; e->h_spawn.clear();
-    HIP_TRY(hipMalloc(&e->d_spawn, (size_t)rows * 8 * sizeof(float)));
+    e->spawn.table.reset(); e->spawn.rows = 0; e->spawn.host.clear();   // drop first
+    HIP_TRY(e->spawn.table.alloc((size_t)rows * 8));
   }
-  float *d_in = nullptr, *d_foot = nullptr;
+  const char* const fn = "cosim_spawn_set";
+  Dev<float> d_in, d_foot;   // the two input buffers live for this call
   std::vector<float> placed((size_t)rows * 8);
-  auto run = [&]() -> hipError_t {   // (one exit, so that the two input buffers are released on every path)
-    hipError_t r;
-    if ((r = hipMalloc(&d_in, (size_t)rows * 3 * sizeof(float))) != hipSuccess) return r;
-    if ((r = hipMalloc(&d_foot, (size_t)(n_foot > 0 ? n_foot : 1) * 4 * sizeof(float))) != hipSuccess) return r;
-    if ((r = hipMemcpy(d_in, xyyaw_host, (size_t)rows * 3 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return r;
-    if (n_foot > 0 && (r = hipMemcpy(d_foot, footprint_host, (size_t)n_foot * 4 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return r;
-    SpawnArgs a;
-    memset(&a, 0, sizeof a);
-    a.xyyaw = d_in; a.foot = reinterpret_cast<const float4*>(d_foot); a.out = e->d_spawn; a.hfield = hf ? e->d_hfield : nullptr;
-    a.rows = rows; a.n_foot = n_foot; a.nrow = m.hfield_nrow; a.ncol = m.hfield_ncol;
-    a.sx = (float)m.hfield_size[0]; a.sy = (float)m.hfield_size[1]; a.sz = (float)m.hfield_size[2];
-    a.gx = (float)m.ground_pos[0]; a.gy = (float)m.ground_pos[1];
-    a.init_z = (float)m.init_qpos[2]; a.clearance = clearance;
-    for (int k = 0; k < 4; k++) a.iq[k] = (float)m.init_qpos[3 + k];
-    hipLaunchKernelGGL(spawn_place_kernel, dim3(rows), dim3(64), 0, cs, a);   // behind the steps already on the stream: they keep the old rows
-    if ((r = hipGetLastError()) != hipSuccess) return r;
-    if ((r = hipStreamSynchronize(cs)) != hipSuccess) return r;
-    return hipMemcpy(placed.data(), e->d_spawn, placed.size() * sizeof(float), hipMemcpyDeviceToHost);
-  };
-  const hipError_t r = run();
-  (void)hipFree(d_in); (void)hipFree(d_foot);
-  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_spawn_set: ") + hipGetErrorString(r));
-  e->h_spawn.swap(placed);
-  e->spawn_rows = rows; e->spawn_mode = per_episode != 0;
+  HIP_TRY_AS(fn, d_in.upload(xyyaw_host, (size_t)rows * 3));
+  HIP_TRY_AS(fn, d_foot.alloc((size_t)(n_foot > 0 ? n_foot : 1) * 4));
+  if (n_foot > 0) HIP_TRY_AS(fn, hipMemcpy(d_foot.get(), footprint_host, (size_t)n_foot * 4 * sizeof(float), hipMemcpyHostToDevice));
+  SpawnArgs a;
+  memset(&a, 0, sizeof a);
+  a.xyyaw = d_in.get(); a.foot = reinterpret_cast<const float4*>(d_foot.get()); a.out = e->spawn.table.get(); a.hfield = hf ? e->d_hfield.get() : nullptr;
+  a.rows = rows; a.n_foot = n_foot; a.nrow = m.hfield_nrow; a.ncol = m.hfield_ncol;
+  a.sx = (float)m.hfield_size[0]; a.sy = (float)m.hfield_size[1]; a.sz = (float)m.hfield_size[2];
+  a.gx = (float)m.ground_pos[0]; a.gy = (float)m.ground_pos[1];
+  a.init_z = (float)m.init_qpos[2]; a.clearance = clearance;
+  for (int k = 0; k < 4; k++) a.iq[k] = (float)m.init_qpos[3 + k];
+  hipLaunchKernelGGL(spawn_place_kernel, dim3(rows), dim3(64), 0, cs, a);   // behind the steps already on the stream: they keep the old rows
+  HIP_TRY_AS(fn, hipGetLastError());
+  HIP_TRY_AS(fn, hipStreamSynchronize(cs));   // (the input buffers go behind it)
+  HIP_TRY_AS(fn, e->spawn.table.download(placed.data(), placed.size()));
+  e->spawn.host.swap(placed);
+  e->spawn.rows = rows; e->spawn.mode = per_episode != 0;
   return COSIM_OK;
 }
 
@@ -2287,7 +2243,7 @@ int cosim_fall_set(cosim_engine_t* e, float min_up, float min_height, int grace_
     if (rc) return rc;
     HIP_TRY(hipDeviceSynchronize());
     e->hm.term_mode = term_mode; e->hm.term_bodymask = bodymask;
-    HIP_TRY(hipMemcpy(e->d_model, &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(e->d_model.get(), &e->hm, sizeof(DevModel), hipMemcpyHostToDevice));
   }
   const int posture = (min_up > -1.f ? 1 : 0) | (min_height > 0.f ? 2 : 0);
   const bool on = posture != 0 || n_bodies >= 0;   // everything off: the model's own list, no cause bookkeeping
@@ -2298,9 +2254,9 @@ int cosim_fall_set(cosim_engine_t* e, float min_up, float min_height, int grace_
 
 int cosim_spawn_get(cosim_engine_t* e, float* poses_host, int capacity) {
   if (!e || (capacity > 0 && !poses_host)) return fail(COSIM_EINVAL, "cosim_spawn_get: null argument");
-  const int n = e->spawn_rows < capacity ? e->spawn_rows : capacity;
-  for (int r = 0; r < n; r++) memcpy(poses_host + 7 * (size_t)r, e->h_spawn.data() + 8 * (size_t)r, 7 * sizeof(float));
-  return e->spawn_rows;
+  const int n = e->spawn.rows < capacity ? e->spawn.rows : capacity;
+  for (int r = 0; r < n; r++) memcpy(poses_host + 7 * (size_t)r, e->spawn.host.data() + 8 * (size_t)r, 7 * sizeof(float));
+  return e->spawn.rows;
 }
 
 static int locate(cosim_engine* e, const std::string& n, int* off, int* width) {
@@ -2317,19 +2273,19 @@ int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream)
   HIP_TRY(hipSetDevice(e->device));
   const bool act_eff = std::string(name) == "action_effective";
   if (act_eff || std::string(name) == "action_raw") {   // [N][nu], contiguous: the last step's rows of the action faults' buffers
-    if (e->actflt.n_items == 0 && e->lat.n_act == 0)
+    if (e->actflt.tab.n_items == 0 && e->lat.tab.n_act == 0)
       return fail(COSIM_EINVAL, std::string("cosim_get: ") + name + ": no action faults are set (cosim_set_param \"action_faults\") and no latency of the command channel (cosim_set_param \"latency\")");
     RC_TRY(join_ranges(e, (hipStream_t)stream));
-    HIP_TRY(hipMemcpyAsync(out_dev, act_eff ? e->d_actions_eff : e->d_actions_raw, (size_t)e->n_envs * e->model.nu * sizeof(float),
+    HIP_TRY(hipMemcpyAsync(out_dev, act_eff ? e->act.eff.get() : e->act.raw.get(), (size_t)e->n_envs * e->model.nu * sizeof(float),
                            hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return COSIM_OK;
   }
   const bool srch_state = std::string(name) == "search_state";
   if (srch_state || std::string(name) == "search_trials") {   // int32 [N][16] / [N][slots][4], contiguous: the search's records / trial rings
-    if (e->srch.n_items == 0) return fail(COSIM_EINVAL, std::string("cosim_get: ") + name + ": no search is armed (cosim_set_param \"search\")");
+    if (e->srch.tab.n_items == 0) return fail(COSIM_EINVAL, std::string("cosim_get: ") + name + ": no search is armed (cosim_set_param \"search\")");
     RC_TRY(join_ranges(e, (hipStream_t)stream));
-    const size_t words = (size_t)e->n_envs * (srch_state ? (size_t)SRCH_NCNT : (size_t)e->srch_slots * SRCH_TRIAL_WORDS);
-    HIP_TRY(hipMemcpyAsync(out_dev, srch_state ? e->d_srch_rec : e->d_srch_ring, words * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    const size_t words = (size_t)e->n_envs * (srch_state ? (size_t)SRCH_NCNT : (size_t)e->srch.slots * SRCH_TRIAL_WORDS);
+    HIP_TRY(hipMemcpyAsync(out_dev, srch_state ? e->srch.rec.get() : e->srch.ring.get(), words * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     return COSIM_OK;
   }
   int off, width;
@@ -2337,7 +2293,7 @@ int cosim_get(cosim_engine_t* e, const char* name, float* out_dev, void* stream)
   if (rc) return rc;
   rc = join_ranges(e, (hipStream_t)stream);
   if (rc) return rc;
-  HIP_TRY(hipMemcpy2DAsync(out_dev, width * sizeof(float), e->d_state + off, e->lay.s_stride * sizeof(float), width * sizeof(float),
+  HIP_TRY(hipMemcpy2DAsync(out_dev, width * sizeof(float), e->d_state.get() + off, e->lay.s_stride * sizeof(float), width * sizeof(float),
                            e->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   return COSIM_OK;
 }
@@ -2348,7 +2304,7 @@ int cosim_set(cosim_engine_t* e, const char* name, const float* in_dev, void* st
   int off, width;
   RC_TRY(locate(e, name, &off, &width));
   RC_TRY(join_ranges(e, (hipStream_t)stream));
-  HIP_TRY(hipMemcpy2DAsync(e->d_state + off, e->lay.s_stride * sizeof(float), in_dev, width * sizeof(float), width * sizeof(float),
+  HIP_TRY(hipMemcpy2DAsync(e->d_state.get() + off, e->lay.s_stride * sizeof(float), in_dev, width * sizeof(float), width * sizeof(float),
                            e->n_envs, hipMemcpyDeviceToDevice, (hipStream_t)stream));
   e->stepped = true;
   return observers_begin(e, nullptr, nullptr, 0, LEDGER_NO_RESET, (hipStream_t)stream);
@@ -2379,26 +2335,28 @@ int cosim_restore(cosim_engine_t* e, const float* snap_dev, int snap_rows, const
   hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
   HIP_TRY(hipStreamIsCapturing(cs, &cap));
   if (src_index_dev) {
-    if (!e->d_snap_err) {
+    if (!e->snap_err.dev) {
       if (cap != hipStreamCaptureStatusNone) return fail(COSIM_EINVAL, "cosim_restore: the first restore with a source index allocates; call it once outside the capture");
-      HIP_TRY(hipMalloc(&e->d_snap_err, 2 * sizeof(int)));
-      HIP_TRY(hipHostMalloc(&e->h_snap_err, 2 * sizeof(int), hipHostMallocDefault));
+      SnapErr pair;   // both or neither: a failure of the second leaves no device word behind for the next call to trust
+      HIP_TRY(pair.dev.alloc(2));
+      HIP_TRY(pair.host.alloc(2));
+      e->snap_err = std::move(pair);
     }
-    HIP_TRY(hipMemsetAsync(e->d_snap_err, 0, 2 * sizeof(int), cs));
+    HIP_TRY(hipMemsetAsync(e->snap_err.dev.get(), 0, 2 * sizeof(int), cs));
   }
   SnapArgs a = snap_args(e);
   a.rows = const_cast<float*>(snap_dev); a.n_rows = snap_rows; a.src = src_index_dev; a.mask = mask_dev;
-  a.err = src_index_dev ? e->d_snap_err : nullptr; a.with_params = with_params != 0;
+  a.err = src_index_dev ? e->snap_err.dev.get() : nullptr; a.with_params = with_params != 0;
   RC_TRY(launch_small<1, 64>(snapshot_gather_kernel, a, e->n_envs, cs));
   if (with_params) e->params_mirror_stale = true;
   e->stepped = true;
   RC_TRY(observers_begin(e, mask_dev, src_index_dev, snap_rows, LEDGER_NO_RESET, cs));
   if (src_index_dev && cap == hipStreamCaptureStatusNone) {   // the kernel skipped what it refused; report it
-    HIP_TRY(hipMemcpyAsync(e->h_snap_err, e->d_snap_err, 2 * sizeof(int), hipMemcpyDeviceToHost, cs));
+    HIP_TRY(hipMemcpyAsync(e->snap_err.host.get(), e->snap_err.dev.get(), 2 * sizeof(int), hipMemcpyDeviceToHost, cs));
     HIP_TRY(hipStreamSynchronize(cs));
-    if (e->h_snap_err[0] > 0)
-      return fail(COSIM_EINVAL, "cosim_restore: source index of env " + std::to_string(e->n_envs - e->h_snap_err[1]) + " is outside [0, " +
-                                    std::to_string(snap_rows) + "); " + std::to_string(e->h_snap_err[0]) + " env(s) were left untouched");
+    if (e->snap_err.host.get()[0] > 0)
+      return fail(COSIM_EINVAL, "cosim_restore: source index of env " + std::to_string(e->n_envs - e->snap_err.host.get()[1]) + " is outside [0, " +
+                                    std::to_string(snap_rows) + "); " + std::to_string(e->snap_err.host.get()[0]) + " env(s) were left untouched");
   }
   return COSIM_OK;
 }
@@ -2407,28 +2365,26 @@ int cosim_history_set(cosim_engine_t* e, int slots, int every) {
   if (!e || slots < 0 || slots > 65536 || (slots > 0 && every < 1)) return fail(COSIM_EINVAL, "cosim_history_set: slots must be 0..65536 and every >= 1");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());   // launches in flight may still write the old ring
-  HIP_TRY(hipFree(e->d_hist));
-  e->d_hist = nullptr; e->hist_slots = 0; e->hist_every = 0; e->hist_calls = 0; e->hist_captures = 0; e->hist_call_of.clear();
+  e->hist = {};   // drop first: the ring can be gigabytes
   if (slots == 0) return COSIM_OK;
-  const size_t bytes = (size_t)slots * e->n_envs * (size_t)(e->lay.s_stride + e->lay.p_stride) * sizeof(float);
-  HIP_TRY(hipMalloc(&e->d_hist, bytes));
-  e->hist_slots = slots; e->hist_every = every; e->hist_call_of.assign(slots, 0);
+  HIP_TRY(e->hist.ring.alloc((size_t)slots * e->n_envs * (size_t)(e->lay.s_stride + e->lay.p_stride)));
+  e->hist.slots = slots; e->hist.every = every; e->hist.call_of.assign(slots, 0);
   return COSIM_OK;
 }
 
 int cosim_history_get(cosim_engine_t* e, int age, float* out_dev, int* steps_ago, void* stream) {
   if (!e || !out_dev) return fail(COSIM_EINVAL, "cosim_history_get: null argument");
-  if (e->hist_slots <= 0) return fail(COSIM_EINVAL, "cosim_history_get: no history is set (cosim_history_set)");
-  if (age < 0 || age >= e->hist_slots) return fail(COSIM_EINVAL, "cosim_history_get: age " + std::to_string(age) + " outside the ring of " + std::to_string(e->hist_slots) + " slots");
-  if ((long)age >= e->hist_captures)
-    return fail(COSIM_EINVAL, "cosim_history_get: capture of age " + std::to_string(age) + " does not exist yet (" + std::to_string(e->hist_captures) + " taken)");
+  if (e->hist.slots <= 0) return fail(COSIM_EINVAL, "cosim_history_get: no history is set (cosim_history_set)");
+  if (age < 0 || age >= e->hist.slots) return fail(COSIM_EINVAL, "cosim_history_get: age " + std::to_string(age) + " outside the ring of " + std::to_string(e->hist.slots) + " slots");
+  if ((long)age >= e->hist.captures)
+    return fail(COSIM_EINVAL, "cosim_history_get: capture of age " + std::to_string(age) + " does not exist yet (" + std::to_string(e->hist.captures) + " taken)");
   HIP_TRY(hipSetDevice(e->device));
   int rc = join_ranges(e, (hipStream_t)stream);
   if (rc) return rc;
-  const int slot = (int)((e->hist_captures - 1 - age) % e->hist_slots);
+  const int slot = (int)((e->hist.captures - 1 - age) % e->hist.slots);
   const size_t row_floats = (size_t)e->n_envs * (size_t)(e->lay.s_stride + e->lay.p_stride);
-  HIP_TRY(hipMemcpyAsync(out_dev, e->d_hist + slot * row_floats, row_floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-  if (steps_ago) *steps_ago = (int)(e->hist_calls - e->hist_call_of[slot]);
+  HIP_TRY(hipMemcpyAsync(out_dev, e->hist.ring.get() + slot * row_floats, row_floats * sizeof(float), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  if (steps_ago) *steps_ago = (int)(e->hist.calls - e->hist.call_of[slot]);
   return COSIM_OK;
 }
 
@@ -2436,21 +2392,16 @@ int cosim_ledger_set(cosim_engine_t* e, int slots) {
   if (!e || slots < 0 || slots > 4096) return fail(COSIM_EINVAL, "cosim_ledger_set: slots must be 0..4096");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());   // every range's launches in flight may still write the old buffers
-  ledger_free(e);
+  e->led = {};   // drop first
   if (slots == 0) return COSIM_OK;
   const size_t N = (size_t)e->n_envs;
-  auto alloc = [&]() -> hipError_t {
-    hipError_t r;
-    if ((r = hipMalloc(&e->d_led_sum, LEDGER_NSUM * N * sizeof(double))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_led_peak, 2 * N * sizeof(float))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_led_acc, LEDGER_NINT * N * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_led_rec, N * slots * LEDGER_WORDS * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMemset(e->d_led_acc, 0, LEDGER_NINT * N * sizeof(int))) != hipSuccess) return r;
-    return hipMemset(e->d_led_rec, 0, N * slots * LEDGER_WORDS * sizeof(int));
-  };
-  const hipError_t r = alloc();
-  if (r != hipSuccess) { ledger_free(e); return fail(COSIM_EHIP, std::string("cosim_ledger_set: ") + hipGetErrorString(r)); }
-  e->led_slots = slots;
+  Ledger led;
+  HIP_TRY_AS("cosim_ledger_set", led.sum.alloc(LEDGER_NSUM * N));
+  HIP_TRY_AS("cosim_ledger_set", led.peak.alloc(2 * N));
+  HIP_TRY_AS("cosim_ledger_set", led.acc.alloc_zeroed(LEDGER_NINT * N));
+  HIP_TRY_AS("cosim_ledger_set", led.rec.alloc_zeroed(N * slots * LEDGER_WORDS));
+  e->led = std::move(led);
+  e->led.slots = slots;
   // every env starts an open episode at length 0 (the range streams do not order with the null stream: wait here, cold path)
   RC_TRY(ledger_begin(e, nullptr, nullptr, 0, e->stepped ? LEDGER_NO_RESET : 0, 0));
   HIP_TRY(hipDeviceSynchronize());
@@ -2459,14 +2410,14 @@ int cosim_ledger_set(cosim_engine_t* e, int slots) {
 
 int cosim_ledger_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream) {
   if (!e || !records_dev || !counts_dev) return fail(COSIM_EINVAL, "cosim_ledger_get: null argument");
-  if (e->led_slots <= 0) return fail(COSIM_EINVAL, "cosim_ledger_get: no ledger is set (cosim_ledger_set)");
+  if (e->led.slots <= 0) return fail(COSIM_EINVAL, "cosim_ledger_get: no ledger is set (cosim_ledger_set)");
   if (open_dev && ((uintptr_t)open_dev & 15)) return fail(COSIM_EINVAL, "cosim_ledger_get: open_dev must be 16-byte aligned");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
   RC_TRY(join_ranges(e, cs));
   const size_t N = (size_t)e->n_envs;
-  HIP_TRY(hipMemcpyAsync(records_dev, e->d_led_rec, N * e->led_slots * LEDGER_WORDS * sizeof(int), hipMemcpyDeviceToDevice, cs));
-  HIP_TRY(hipMemcpyAsync(counts_dev, e->d_led_acc + 2 * N, N * sizeof(int), hipMemcpyDeviceToDevice, cs));
+  HIP_TRY(hipMemcpyAsync(records_dev, e->led.rec.get(), N * e->led.slots * LEDGER_WORDS * sizeof(int), hipMemcpyDeviceToDevice, cs));
+  HIP_TRY(hipMemcpyAsync(counts_dev, e->led.acc.get() + 2 * N, N * sizeof(int), hipMemcpyDeviceToDevice, cs));
   if (open_dev) {
     LedgerArgs a = ledger_args(e);
     a.rec = open_dev;
@@ -2483,24 +2434,16 @@ int cosim_ftrace_set(cosim_engine_t* e, int frames, int keep, int on_mask) {
     return fail(COSIM_EINVAL, "cosim_ftrace_set: on_mask " + std::to_string(on_mask) + " must be a non-empty subset of 1|2|4|32|64|128");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());   // every range's launches in flight may still write the old buffers
-  ftrace_free(e);
+  e->ft = {};   // drop first: the windows can be gigabytes
   if (frames == 0) return COSIM_OK;
   const size_t N = (size_t)e->n_envs;
-  const size_t bytes = N * (size_t)(keep + 1) * ftrace_buf_words(frames, ftrace_words(e)) * sizeof(int);
-  auto alloc = [&]() -> hipError_t {
-    hipError_t r;
-    if ((r = hipMalloc(&e->d_ft_buf, bytes)) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_ft_cnt, N * FT_NCNT * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMemset(e->d_ft_cnt, 0, N * FT_NCNT * sizeof(int))) != hipSuccess) return r;
-    return hipMemset(e->d_ft_buf, 0, bytes);
-  };
-  const hipError_t r = alloc();
-  if (r != hipSuccess) {
-    ftrace_free(e);
-    (void)hipGetLastError();
-    return fail(COSIM_EHIP, "cosim_ftrace_set: " + std::to_string(bytes) + " bytes of trace buffers: " + hipGetErrorString(r));
-  }
-  e->ft_frames = frames; e->ft_keep = keep; e->ft_mask = on_mask;
+  const size_t words = N * (size_t)(keep + 1) * ftrace_buf_words(frames, ftrace_words(e));
+  const auto who = [&]() { return "cosim_ftrace_set: " + std::to_string(words * sizeof(int)) + " bytes of trace buffers"; };
+  Ftrace ft;
+  HIP_TRY_CLEAR(who(), ft.buf.alloc_zeroed(words));
+  HIP_TRY_CLEAR(who(), ft.cnt.alloc_zeroed(N * FT_NCNT));
+  e->ft = std::move(ft);
+  e->ft.frames = frames; e->ft.keep = keep; e->ft.mask = on_mask;
   // every env starts an open episode in an empty window (the range streams do not order with the null stream: wait here, cold path)
   RC_TRY(ftrace_begin(e, nullptr, nullptr, 0, e->stepped ? FT_NO_RESET : 0, 0));
   HIP_TRY(hipDeviceSynchronize());
@@ -2509,15 +2452,15 @@ int cosim_ftrace_set(cosim_engine_t* e, int frames, int keep, int on_mask) {
 
 int cosim_ftrace_get(cosim_engine_t* e, int32_t* buffers_dev, int32_t* counts_dev, int32_t* open_dev, void* stream) {
   if (!e || !buffers_dev || !counts_dev) return fail(COSIM_EINVAL, "cosim_ftrace_get: null argument");
-  if (e->ft_frames <= 0) return fail(COSIM_EINVAL, "cosim_ftrace_get: no failure traces are set (cosim_ftrace_set)");
+  if (e->ft.frames <= 0) return fail(COSIM_EINVAL, "cosim_ftrace_get: no failure traces are set (cosim_ftrace_set)");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
   RC_TRY(join_ranges(e, cs));
   const size_t N = (size_t)e->n_envs;
-  const size_t bytes = N * (size_t)(e->ft_keep + 1) * ftrace_buf_words(e->ft_frames, ftrace_words(e)) * sizeof(int);
-  HIP_TRY(hipMemcpyAsync(buffers_dev, e->d_ft_buf, bytes, hipMemcpyDeviceToDevice, cs));
+  const size_t bytes = N * (size_t)(e->ft.keep + 1) * ftrace_buf_words(e->ft.frames, ftrace_words(e)) * sizeof(int);
+  HIP_TRY(hipMemcpyAsync(buffers_dev, e->ft.buf.get(), bytes, hipMemcpyDeviceToDevice, cs));
   // counters 0..2 of every env: working buffer, traces triggered, traces lost
-  HIP_TRY(hipMemcpy2DAsync(counts_dev, 3 * sizeof(int), e->d_ft_cnt, FT_NCNT * sizeof(int), 3 * sizeof(int), N, hipMemcpyDeviceToDevice, cs));
+  HIP_TRY(hipMemcpy2DAsync(counts_dev, 3 * sizeof(int), e->ft.cnt.get(), FT_NCNT * sizeof(int), 3 * sizeof(int), N, hipMemcpyDeviceToDevice, cs));
   if (open_dev) {
     FtArgs a = ftrace_args(e);
     a.open_out = open_dev;
@@ -2547,8 +2490,8 @@ static int table_clear(cosim_engine* e, hipStream_t s, void (*drop)(cosim_engine
 
 // windows, checks and curves (`what`) are rows of the scenario table that is set
 static int table_rows_match(const cosim_engine* e, const std::string& fn, const char* what, int n_scn) {
-  if (e->scn.n_scn == 0) return fail(COSIM_EINVAL, fn + ": no scenario table is set (cosim_scenario_set): " + what + " are rows of a table; set the table first");
-  if (n_scn != e->scn.n_scn) return fail(COSIM_EINVAL, fn + ": " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.n_scn));
+  if (e->scn.tab.n_scn == 0) return fail(COSIM_EINVAL, fn + ": no scenario table is set (cosim_scenario_set): " + what + " are rows of a table; set the table first");
+  if (n_scn != e->scn.tab.n_scn) return fail(COSIM_EINVAL, fn + ": " + std::to_string(n_scn) + " scenarios, the table that is set has " + std::to_string(e->scn.tab.n_scn));
   return COSIM_OK;
 }
 
@@ -2575,31 +2518,31 @@ int cosim_scenario_set(cosim_engine_t* e, int n_scn, const int32_t* key_adr, con
   const ScnRaw raw = {n_scn, key_adr, key_t, key_cmd, push_adr, push_t, push_v};
   const ScnShape v = validate_scenario(table_dims(e), raw);
   if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
-  if (n_scn == e->scn.n_scn && mode == SCN_MODE_CYCLE && e->actflt_marked + e->obsflt_marked + e->scnpar_marked > 0)
-    return fail(COSIM_EINVAL, "cosim_scenario_set: mode cycle drops the limit search and " + std::to_string(e->actflt_marked + e->obsflt_marked + e->scnpar_marked) +
+  if (n_scn == e->scn.tab.n_scn && mode == SCN_MODE_CYCLE && e->actflt.marked + e->obsflt.marked + e->par.marked > 0)
+    return fail(COSIM_EINVAL, "cosim_scenario_set: mode cycle drops the limit search and " + std::to_string(e->actflt.marked + e->obsflt.marked + e->par.marked) +
                                   " parameter or fault items are marked for it: clear or unmark them first");
   RC_TRY(table_quiesce(e, (hipStream_t)stream));
   ScnTable tab = {};
   WordPacker pk;
   pack_scenario(pk, tab, cd, raw, v);
   // other sizes: a new allocation, which replaces the old one only once it is filled (a failure leaves the table that was set)
-  const bool in_place = n_scn == e->scn.n_scn && v.nkey == e->scn_nkey && v.npush == e->scn_npush;
-  char* d_new = e->d_scn;
-  if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
-  const hipError_t r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  const bool in_place = n_scn == e->scn.tab.n_scn && v.nkey == e->scn.nkey && v.npush == e->scn.npush;
+  Dev<char> fresh;
+  if (!in_place) HIP_TRY(fresh.alloc(pk.bytes()));
+  const hipError_t r = hipMemcpy(in_place ? e->scn.image.get() : fresh.get(), pk.data(), pk.bytes(), hipMemcpyHostToDevice);
   if (r != hipSuccess) {   // a new allocation is dropped and the old table stays; an in-place rewrite may be half written: no table then
-    if (in_place) scenario_free(e); else (void)hipFree(d_new);
+    if (in_place) scenario_free(e);
     return fail(COSIM_EHIP, std::string("cosim_scenario_set: ") + hipGetErrorString(r));
   }
-  if (!in_place) { (void)hipFree(e->d_scn); e->d_scn = d_new; }
-  if (n_scn != e->scn.n_scn || mode == SCN_MODE_CYCLE) search_free(e);   // so is the search; its one record per env needs mode env
-  if (n_scn != e->scn.n_scn) { scnparams_free(e); obsfault_free(e); actfault_free(e); latency_free(e); checks_free(e); curves_free(e); }   // parameter windows, faults, checks and curves are rows of the table they were set for: another S drops them
-  pk.patch(e->d_scn);
+  if (!in_place) e->scn.image = std::move(fresh);
+  if (n_scn != e->scn.tab.n_scn || mode == SCN_MODE_CYCLE) e->srch = {};   // so is the search; its one record per env needs mode env
+  if (n_scn != e->scn.tab.n_scn) scenario_rows_drop(e);   // parameter windows, faults, latency, checks and curves are rows of the table they were set for: another S drops them
+  pk.patch(e->scn.image.get());
   tab.mode = mode;
   tab.gid_off = (unsigned)(((e->env_id0 % n_scn) + n_scn) % n_scn);
-  e->scn = tab;
-  e->scn_nkey = v.nkey; e->scn_npush = v.npush;
-  e->scn_cmd_out = cmd_out_dev; e->scn_row_out = row_out_dev;
+  e->scn.tab = tab;
+  e->scn.nkey = v.nkey; e->scn.npush = v.npush;
+  e->scn.cmd_out = cmd_out_dev; e->scn.row_out = row_out_dev;
   return COSIM_OK;
 }
 
@@ -2609,11 +2552,11 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
                               const int32_t* op, const float* value) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_params_set: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) return table_clear(e, 0, scnparams_free);
+  if (n_scn == 0) return table_clear(e, 0, [](cosim_engine* x) { x->par = {}; });
   RC_TRY(table_rows_match(e, "cosim_scenario_params_set", "parameter windows", n_scn));
   const ParRaw raw = {n_scn, adr, t, field, index, op, value};
-  const FltMarks marks = {SRCH_PARAMS, e->h_srch_has.data(), e->h_srch_targets.data(), e->h_srch_lo.data(), e->h_srch_hi.data()};
-  const bool armed = e->srch.n_items > 0 && (e->srch_kinds & SRCH_PARAMS) && n_scn == e->srch.n_scn;
+  const FltMarks marks = {SRCH_PARAMS, e->srch.has.data(), e->srch.targets.data(), e->srch.lo.data(), e->srch.hi.data()};
+  const bool armed = e->srch.tab.n_items > 0 && (e->srch.kinds & SRCH_PARAMS) && n_scn == e->srch.tab.n_scn;
   const ParShape v = validate_params(table_dims(e), raw, armed ? &marks : nullptr);
   if (!v.err.empty()) return fail(COSIM_EINVAL, v.err);
   RC_TRY(upload_params(e));   // the effective records written below are built from the current base
@@ -2621,23 +2564,21 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   ScnParTable tab = {};
   WordPacker pk;
   pack_params(pk, tab, raw, v);
-  const bool in_place = e->scnpar.n_items == v.n && e->scnpar.n_scn == n_scn;
-  char* d_new = e->d_scnpar;
-  if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
-  if (!e->d_params_eff) {
-    const hipError_t r = hipMalloc(&e->d_params_eff, (size_t)e->n_envs * e->lay.p_stride * sizeof(float));
-    if (r != hipSuccess) { e->d_params_eff = nullptr; if (!in_place) (void)hipFree(d_new); return fail(COSIM_EHIP, std::string("cosim_scenario_params_set: ") + hipGetErrorString(r)); }
-  }
-  const hipError_t r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-  if (r != hipSuccess) {   // a new allocation is dropped and the old items stay; an in-place rewrite may be half written: no windows then
-    if (in_place) scnparams_free(e);
-    else { (void)hipFree(d_new); if (e->scnpar.n_items == 0) { (void)hipFree(e->d_params_eff); e->d_params_eff = nullptr; } }
+  const bool in_place = e->par.tab.n_items == v.n && e->par.tab.n_scn == n_scn;
+  Dev<char> fresh;
+  Dev<float> eff;
+  if (!in_place) HIP_TRY(fresh.alloc(pk.bytes()));
+  if (!e->par.eff) HIP_TRY_AS("cosim_scenario_params_set", eff.alloc((size_t)e->n_envs * e->lay.p_stride));
+  const hipError_t r = hipMemcpy(in_place ? e->par.image.get() : fresh.get(), pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) {   // new allocations are dropped and the old items stay; an in-place rewrite may be half written: no windows then
+    if (in_place) e->par = {};
     return fail(COSIM_EHIP, std::string("cosim_scenario_params_set: ") + hipGetErrorString(r));
   }
-  if (!in_place) { (void)hipFree(e->d_scnpar); e->d_scnpar = d_new; }
-  pk.patch(e->d_scnpar);
-  e->scnpar = tab;
-  e->scnpar_marked = v.marked;
+  if (!in_place) e->par.image = std::move(fresh);
+  if (eff) e->par.eff = std::move(eff);
+  pk.patch(e->par.image.get());
+  e->par.tab = tab;
+  e->par.marked = v.marked;
   // every env's effective record once, at its current clock: no row is ever unwritten
   RC_TRY(scnparams_launch(e, 0, e->n_envs, nullptr, 0, 0));
   HIP_TRY(hipDeviceSynchronize());
@@ -2647,10 +2588,10 @@ int cosim_scenario_params_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
 // Faults of the scenario table that is set, either kind (cosim_set_param "obs_faults" / "action_faults"): `words` is S | adr[S + 1] |
 // t[n][2] | elem[n] | op[n] | ord[n] | value[n] (float bits), n = adr[S]; S = 0 clears.  Items of the counts of the ones that are
 // set are rewritten in place: the device pointers stay, captured graphs pick the new values up.  Nothing is launched: the faults
-// act from the next step (observations: or reset) on.  The kind gives its allocation and table, how they are dropped, its validator
-// (cosim_tables.h) and, if it has any, the buffers it needs beside the table: `buffers` allocates them ahead of the copy.
-static int fault_table_set(cosim_engine* e, const std::string& fn, const char* what, char*& d_tab, FaultTable& slot, void (*drop)(cosim_engine*),
-                           hipError_t (*buffers)(cosim_engine*), FltShape (*validate)(const cosim_engine*, const FltRaw&), const int32_t* words, int count) {
+// act from the next step (observations: or reset) on.  The kind gives its group, how it is dropped, its validator (cosim_tables.h)
+// and whether it needs the two action rows beside the table: they are allocated ahead of the copy.
+static int fault_table_set(cosim_engine* e, const std::string& fn, const char* what, Faults& set, void (*drop)(cosim_engine*), bool action_rows,
+                           FltShape (*validate)(const cosim_engine*, const FltRaw&), const int32_t* words, int count) {
   if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the faults)");
   const int n_scn = words[0];
   HIP_TRY(hipSetDevice(e->device));
@@ -2670,23 +2611,20 @@ static int fault_table_set(cosim_engine* e, const std::string& fn, const char* w
   FaultTable tab = {};
   WordPacker pk;
   pack_faults(pk, tab, raw, v);
-  const bool in_place = slot.n_items == v.n && slot.n_scn == n_scn;
-  char* d_new = d_tab;
-  if (!in_place) HIP_TRY(hipMalloc(&d_new, pk.bytes()));
-  hipError_t r = buffers ? buffers(e) : hipSuccess;
-  if (r != hipSuccess) {
-    if (!in_place) (void)hipFree(d_new);
-    return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
-  }
-  r = hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-  if (r != hipSuccess) {   // a new allocation is dropped and the old items stay (with none set before, neither do the kind's buffers); an in-place rewrite may be half written: no faults then
+  const bool in_place = set.tab.n_items == v.n && set.tab.n_scn == n_scn;
+  Dev<char> fresh;
+  ActionRows rows;
+  if (!in_place) HIP_TRY(fresh.alloc(pk.bytes()));
+  if (action_rows && !e->act.eff) HIP_TRY_AS(fn, rows.alloc((size_t)e->n_envs * e->model.nu));
+  const hipError_t r = hipMemcpy(in_place ? set.image.get() : fresh.get(), pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) {   // new allocations are dropped and the old items stay; an in-place rewrite may be half written: no faults then
     if (in_place) drop(e);
-    else { (void)hipFree(d_new); if (slot.n_items == 0) drop(e); }
     return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
   }
-  if (!in_place) { (void)hipFree(d_tab); d_tab = d_new; }
-  pk.patch(d_tab);
-  slot = tab;
+  if (!in_place) set.image = std::move(fresh);
+  if (rows.eff) e->act = std::move(rows);
+  pk.patch(set.image.get());
+  set.tab = tab;
   return COSIM_OK;
 }
 
@@ -2699,37 +2637,25 @@ static int fault_words_marked(const int32_t* words) {
   return m;
 }
 static FltShape obsfault_validate(const cosim_engine* e, const FltRaw& raw) {
-  const FltMarks marks = {SRCH_OBS_FAULTS, e->h_srch_has.data(), e->h_srch_targets.data(), e->h_srch_lo.data(), e->h_srch_hi.data()};
-  const bool armed = obsfault_searched(e) && raw.n_scn == e->srch.n_scn;
+  const FltMarks marks = {SRCH_OBS_FAULTS, e->srch.has.data(), e->srch.targets.data(), e->srch.lo.data(), e->srch.hi.data()};
+  const bool armed = obsfault_searched(e) && raw.n_scn == e->srch.tab.n_scn;
   return validate_faults({e->ho.frame_dim, e->ho.stacked_dim, e->ho.stack_size, e->ho.el_field, CS_OBS_COMMAND}, raw, armed ? &marks : nullptr);
 }
 static int obsfault_set(cosim_engine* e, const int32_t* words, int count) {
-  RC_TRY(fault_table_set(e, OBF_SETTER, "observation faults", e->d_obsflt, e->obsflt, obsfault_free, nullptr, obsfault_validate, words, count));
-  e->obsflt_marked = e->obsflt.n_items > 0 ? fault_words_marked(words) : 0;
+  RC_TRY(fault_table_set(e, OBF_SETTER, "observation faults", e->obsflt, [](cosim_engine* x) { x->obsflt = {}; }, false, obsfault_validate, words, count));
+  e->obsflt.marked = e->obsflt.tab.n_items > 0 ? fault_words_marked(words) : 0;
   return COSIM_OK;
-}
-
-// the two action buffers: both or neither; zeroed, so that a read ahead of the first step finds no stale bytes
-static hipError_t actfault_buffers(cosim_engine* e) {
-  if (e->d_actions_eff) return hipSuccess;
-  const size_t bytes = (size_t)e->n_envs * e->model.nu * sizeof(float);
-  hipError_t r = hipMalloc(&e->d_actions_eff, bytes);
-  if (r == hipSuccess) r = hipMalloc(&e->d_actions_raw, bytes);
-  if (r == hipSuccess) r = hipMemset(e->d_actions_eff, 0, bytes);
-  if (r == hipSuccess) r = hipMemset(e->d_actions_raw, 0, bytes);
-  if (r != hipSuccess) { (void)hipFree(e->d_actions_eff); (void)hipFree(e->d_actions_raw); e->d_actions_eff = nullptr; e->d_actions_raw = nullptr; }
-  return r;
 }
 
 // marked items are held against the search that is armed, if its targets name the action faults
 static FltShape actfault_validate(const cosim_engine* e, const FltRaw& raw) {
-  const FltMarks marks = {SRCH_ACT_FAULTS, e->h_srch_has.data(), e->h_srch_targets.data(), e->h_srch_lo.data(), e->h_srch_hi.data()};
-  const bool armed = e->srch.n_items > 0 && (e->srch_kinds & SRCH_ACT_FAULTS) && raw.n_scn == e->srch.n_scn;
+  const FltMarks marks = {SRCH_ACT_FAULTS, e->srch.has.data(), e->srch.targets.data(), e->srch.lo.data(), e->srch.hi.data()};
+  const bool armed = e->srch.tab.n_items > 0 && (e->srch.kinds & SRCH_ACT_FAULTS) && raw.n_scn == e->srch.tab.n_scn;
   return validate_action_faults(e->model.nu, raw, armed ? &marks : nullptr);
 }
 static int actfault_set(cosim_engine* e, const int32_t* words, int count) {
-  RC_TRY(fault_table_set(e, ACF_SETTER, "action faults", e->d_actflt, e->actflt, actfault_free, actfault_buffers, actfault_validate, words, count));
-  e->actflt_marked = e->actflt.n_items > 0 ? fault_words_marked(words) : 0;
+  RC_TRY(fault_table_set(e, ACF_SETTER, "action faults", e->actflt, [](cosim_engine* x) { x->actflt = {}; action_rows_release(x); }, true, actfault_validate, words, count));
+  e->actflt.marked = e->actflt.tab.n_items > 0 ? fault_words_marked(words) : 0;
   e->act_in_obs = false;
   for (int el = 0; el < e->ho.frame_dim; el++) e->act_in_obs = e->act_in_obs || e->ho.el_field[el] == CS_OBS_LAST_ACTION;
   return COSIM_OK;
@@ -2745,7 +2671,7 @@ static int latency_set(cosim_engine* e, const int32_t* words, int count) {
   if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the latency)");
   const int n_scn = words[0];
   HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) return table_clear(e, 0, latency_free);
+  if (n_scn == 0) return table_clear(e, 0, [](cosim_engine* x) { x->lat = {}; action_rows_release(x); });
   RC_TRY(table_rows_match(e, fn, "latency items", n_scn));
   const size_t S1 = (size_t)n_scn + 1;
   if ((size_t)count < 1 + 2 * S1) return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words do not hold the row addresses of " + std::to_string(n_scn) + " scenarios");
@@ -2762,18 +2688,18 @@ static int latency_set(cosim_engine* e, const int32_t* words, int count) {
   WordPacker pk;
   pack_latency(pk, tab, raw, v);
   RC_TRY(table_quiesce(e, 0));
-  bool in_place = e->lat.n_scn == n_scn && e->lat.n_act == v.n_act && e->lat.n_obs == v.n_obs && v.max_delay + 1 <= e->lat.depth;
+  bool in_place = e->lat.tab.n_scn == n_scn && e->lat.tab.n_act == v.n_act && e->lat.tab.n_obs == v.n_obs && v.max_delay + 1 <= e->lat.tab.depth;
   if (in_place) {   // ... and every scenario keeps its counts: an env keeps the kinds it has a line for
     std::vector<int32_t> old;
-    RC_TRY(table_download(e->d_lat, pk, old));
+    RC_TRY(table_download(e->lat.image.get(), pk, old));
     in_place = latency_same_rows(pk, tab, old.data());
   }
   if (in_place) {
-    const hipError_t r = hipMemcpy(e->d_lat, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-    if (r != hipSuccess) { latency_free(e); return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r)); }   // may be half written: no latency then
-    tab.depth = e->lat.depth;
-    pk.patch(e->d_lat);
-    e->lat = tab;
+    const hipError_t r = hipMemcpy(e->lat.image.get(), pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+    if (r != hipSuccess) { e->lat = {}; action_rows_release(e); return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r)); }   // may be half written: no latency then
+    tab.depth = e->lat.tab.depth;
+    pk.patch(e->lat.image.get());
+    e->lat.tab = tab;
     return COSIM_OK;
   }
   const int D = v.max_delay + 1;
@@ -2785,40 +2711,27 @@ static int latency_set(cosim_engine* e, const int32_t* words, int count) {
   if (v.n_obs > 0 && obs_bytes > cap)
     return fail(COSIM_EINVAL, fn + ": the observation lines take " + std::to_string(N) + " envs x depth " + std::to_string(D) + " x " + std::to_string(fd) + " frame elements x 4 = " +
                                   std::to_string(obs_bytes) + " bytes, more than 256 MiB: fewer envs or a shorter delay");
-  // a fresh allocation replaces the one that is set only once it is complete: a failure leaves the latency that was set
-  char* d_new = nullptr;
-  float *act_line = nullptr, *obs_line = nullptr, *eff = nullptr, *spare = nullptr, *a_eff = e->d_actions_eff, *a_raw = e->d_actions_raw;
-  int* from = nullptr;
-  const size_t rows = (size_t)N * nu * sizeof(float);
-  auto run = [&]() -> hipError_t {
-    hipError_t r;
-    if ((r = hipMalloc(&d_new, pk.bytes())) != hipSuccess) return r;
-    if ((r = hipMalloc(&from, 2 * (size_t)N * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMemset(from, 0xff, 2 * (size_t)N * sizeof(int))) != hipSuccess) return r;   // -1: every line invalid
-    if (v.n_act > 0) {
-      if ((r = hipMalloc(&act_line, act_bytes)) != hipSuccess || (r = hipMemset(act_line, 0, act_bytes)) != hipSuccess) return r;
-      if ((r = hipMalloc(&eff, rows)) != hipSuccess || (r = hipMemset(eff, 0, rows)) != hipSuccess) return r;
-      if ((r = hipMalloc(&spare, rows)) != hipSuccess || (r = hipMemset(spare, 0, rows)) != hipSuccess) return r;
-      if (!a_eff && ((r = hipMalloc(&a_eff, rows)) != hipSuccess || (r = hipMemset(a_eff, 0, rows)) != hipSuccess)) return r;
-      if (!a_raw && ((r = hipMalloc(&a_raw, rows)) != hipSuccess || (r = hipMemset(a_raw, 0, rows)) != hipSuccess)) return r;
-    }
-    if (v.n_obs > 0 && ((r = hipMalloc(&obs_line, obs_bytes)) != hipSuccess || (r = hipMemset(obs_line, 0, obs_bytes)) != hipSuccess)) return r;
-    return hipMemcpy(d_new, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-  };
-  const hipError_t r = run();
-  if (r != hipSuccess) {
-    (void)hipFree(d_new); (void)hipFree(from); (void)hipFree(act_line); (void)hipFree(obs_line); (void)hipFree(eff); (void)hipFree(spare);
-    if (a_eff != e->d_actions_eff) (void)hipFree(a_eff);
-    if (a_raw != e->d_actions_raw) (void)hipFree(a_raw);
-    return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r));
+  // a fresh group replaces the one that is set only once it is complete: a failure leaves the latency that was set
+  Latency fresh;
+  ActionRows act;
+  const size_t rows = (size_t)N * nu;
+  HIP_TRY_AS(fn, fresh.image.alloc(pk.bytes()));
+  HIP_TRY_AS(fn, fresh.from.alloc(2 * (size_t)N));
+  HIP_TRY_AS(fn, hipMemset(fresh.from.get(), 0xff, 2 * (size_t)N * sizeof(int)));   // -1: every line invalid
+  if (v.n_act > 0) {
+    HIP_TRY_AS(fn, fresh.act_line.alloc_zeroed(rows * D));
+    HIP_TRY_AS(fn, fresh.eff.alloc_zeroed(rows));
+    HIP_TRY_AS(fn, fresh.spare.alloc_zeroed(rows));
+    if (!e->act.eff) HIP_TRY_AS(fn, act.alloc(rows));
   }
-  latency_drop(e);
-  e->d_actions_eff = a_eff; e->d_actions_raw = a_raw;
-  e->d_lat = d_new; e->d_lat_from = from; e->d_lat_act_line = act_line; e->d_lat_obs_line = obs_line; e->d_lat_eff = eff; e->d_lat_spare = spare;
-  pk.patch(e->d_lat);
+  if (v.n_obs > 0) HIP_TRY_AS(fn, fresh.obs_line.alloc_zeroed((size_t)N * D * fd));
+  HIP_TRY_AS(fn, hipMemcpy(fresh.image.get(), pk.data(), pk.bytes(), hipMemcpyHostToDevice));
+  pk.patch(fresh.image.get());
   tab.depth = D;
-  e->lat = tab;
-  action_buffers_release(e);   // no action items now and no action faults: the two buffers go
+  fresh.tab = tab;
+  e->lat = std::move(fresh);
+  if (act.eff) e->act = std::move(act);
+  action_rows_release(e);   // no action items now and no action faults: the two rows go
   e->act_in_obs = false;
   for (int el = 0; el < e->ho.frame_dim; el++) e->act_in_obs = e->act_in_obs || e->ho.el_field[el] == CS_OBS_LAST_ACTION;
   return COSIM_OK;
@@ -2835,16 +2748,16 @@ static int search_set(cosim_engine* e, const int32_t* words, int count) {
   if (count < 1) return fail(COSIM_EINVAL, fn + ": an empty table (one word, 0, clears the search)");
   const int n_scn = words[0];
   HIP_TRY(hipSetDevice(e->device));
-  if (e->actflt_marked > 0)
-    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->actflt_marked) + " action-fault items are marked for the search that is armed: clear or unmark them "
+  if (e->actflt.marked > 0)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->actflt.marked) + " action-fault items are marked for the search that is armed: clear or unmark them "
                                    "(cosim_set_param \"action_faults\") before the search is replaced or cleared");
-  if (e->obsflt_marked > 0)
-    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->obsflt_marked) + " observation-fault items are marked for the search that is armed: clear or unmark them "
+  if (e->obsflt.marked > 0)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->obsflt.marked) + " observation-fault items are marked for the search that is armed: clear or unmark them "
                                    "(cosim_set_param \"obs_faults\") before the search is replaced or cleared");
-  if (e->scnpar_marked > 0)
-    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->scnpar_marked) + " parameter items are marked for the search that is armed: clear or unmark them "
+  if (e->par.marked > 0)
+    return fail(COSIM_EINVAL, fn + ": " + std::to_string(e->par.marked) + " parameter items are marked for the search that is armed: clear or unmark them "
                                    "(cosim_scenario_params_set) before the search is replaced or cleared");
-  if (n_scn == 0) return table_clear(e, 0, search_free);
+  if (n_scn == 0) return table_clear(e, 0, [](cosim_engine* x) { x->srch = {}; });
   const bool long_form = n_scn > 0 && (long long)count == 2 + 14ll * n_scn;
   if (n_scn < 0 || ((long long)count != 2 + 11ll * n_scn && !long_form))
     return fail(COSIM_EINVAL, fn + ": " + std::to_string(count) + " words, a table of " + std::to_string(n_scn) + " scenarios takes " + std::to_string(2 + 11ll * (n_scn < 0 ? 0 : n_scn)) +
@@ -2856,19 +2769,19 @@ static int search_set(cosim_engine* e, const int32_t* words, int count) {
   if (long_form) { raw.harder = w + 11 * S; raw.chk_lo = w + 12 * S; raw.chk_hi = w + 13 * S; }
   RC_TRY(table_quiesce(e, 0));
   std::vector<int32_t> adr;   // key_adr | push_adr of the table that is set: the head of its image
-  if (n_scn == e->scn.n_scn) {
+  if (n_scn == e->scn.tab.n_scn) {
     adr.resize(2 * (S + 1));
-    HIP_TRY(hipMemcpy(adr.data(), e->d_scn, adr.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(adr.data(), e->scn.image.get(), adr.size() * 4, hipMemcpyDeviceToHost));
   }
   std::vector<int32_t> chk_adr;   // the row addresses of the checks that are armed: the head of their image
-  if (n_scn == e->chk.n_scn) {
+  if (n_scn == e->chk.tab.n_scn) {
     chk_adr.resize(S + 1);
-    HIP_TRY(hipMemcpy(chk_adr.data(), e->d_chk, chk_adr.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(chk_adr.data(), e->chk.image.get(), chk_adr.size() * 4, hipMemcpyDeviceToHost));
   }
-  SrchDims dims = {e->scn.n_scn, e->scn.mode, e->ho.auto_reset, adr.data(), adr.data() + S + 1, chk_adr.empty() ? nullptr : chk_adr.data()};
+  SrchDims dims = {e->scn.tab.n_scn, e->scn.tab.mode, e->ho.auto_reset, adr.data(), adr.data() + S + 1, chk_adr.empty() ? nullptr : chk_adr.data()};
   std::vector<int32_t> kind_adr[3];   // the row addresses of the item tables that are set: the head of each image
   const struct { const char* d; int n_scn, n_items; const int32_t** slot; } kinds[3] = {
-      {e->d_scnpar, e->scnpar.n_scn, e->scnpar.n_items, &dims.par_adr}, {e->d_obsflt, e->obsflt.n_scn, e->obsflt.n_items, &dims.obs_adr}, {e->d_actflt, e->actflt.n_scn, e->actflt.n_items, &dims.act_adr}};
+      {e->par.image.get(), e->par.tab.n_scn, e->par.tab.n_items, &dims.par_adr}, {e->obsflt.image.get(), e->obsflt.tab.n_scn, e->obsflt.tab.n_items, &dims.obs_adr}, {e->actflt.image.get(), e->actflt.tab.n_scn, e->actflt.tab.n_items, &dims.act_adr}};
   for (int k = 0; k < 3; k++) {
     if (kinds[k].n_items <= 0 || kinds[k].n_scn != n_scn) continue;
     kind_adr[k].resize(S + 1);
@@ -2880,40 +2793,40 @@ static int search_set(cosim_engine* e, const int32_t* words, int count) {
   SrchTable tab = {};
   WordPacker pk;
   pack_search(pk, tab, raw, v);
-  bool in_place = e->srch.n_scn == n_scn && e->srch.n_items == v.n && e->srch_slots == raw.slots && (e->srch.harder != nullptr) == long_form;
+  bool in_place = e->srch.tab.n_scn == n_scn && e->srch.tab.n_items == v.n && e->srch.slots == raw.slots && (e->srch.tab.harder != nullptr) == long_form;
   if (in_place) {
     std::vector<int32_t> old;
-    RC_TRY(table_download(e->d_srch, pk, old));
+    RC_TRY(table_download(e->srch.image.get(), pk, old));
     in_place = search_same_rows(pk, tab, old.data());
   }
   const size_t N = (size_t)e->n_envs;
-  auto alloc = [&]() -> hipError_t {
-    search_free(e);
-    hipError_t r;
-    if ((r = hipMalloc(&e->d_srch, pk.bytes())) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_srch_rec, N * SRCH_NCNT * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_srch_ring, N * raw.slots * SRCH_TRIAL_WORDS * sizeof(int))) != hipSuccess) return r;
-    return hipMalloc(&e->d_srch_rem, sizeof(int));
-  };
-  hipError_t r = in_place ? hipSuccess : alloc();
-  if (r == hipSuccess) r = hipMemcpy(e->d_srch, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-  if (r != hipSuccess) { search_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r)); }
-  pk.patch(e->d_srch);
-  e->srch = tab;
-  e->srch_slots = raw.slots;
-  e->h_srch_has.assign(raw.has, raw.has + S); e->h_srch_targets.assign(raw.targets, raw.targets + S);
-  e->h_srch_lo.assign(raw.lo, raw.lo + S); e->h_srch_hi.assign(raw.hi, raw.hi + S);
-  e->srch_kinds = 0; e->srch_chk = false;
+  if (!in_place) {   // drop first, then everything anew
+    e->srch = {};
+    Search fresh;
+    HIP_TRY_CLEAR(fn, fresh.image.alloc(pk.bytes()));
+    HIP_TRY_CLEAR(fn, fresh.rec.alloc(N * SRCH_NCNT));
+    HIP_TRY_CLEAR(fn, fresh.ring.alloc(N * raw.slots * SRCH_TRIAL_WORDS));
+    HIP_TRY_CLEAR(fn, fresh.rem.alloc(1));
+    e->srch = std::move(fresh);
+  }
+  const hipError_t r = hipMemcpy(e->srch.image.get(), pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) { e->srch = {}; (void)hipGetLastError(); return fail(COSIM_EHIP, fn + ": " + hipGetErrorString(r)); }
+  pk.patch(e->srch.image.get());
+  e->srch.tab = tab;
+  e->srch.slots = raw.slots;
+  e->srch.has.assign(raw.has, raw.has + S); e->srch.targets.assign(raw.targets, raw.targets + S);
+  e->srch.lo.assign(raw.lo, raw.lo + S); e->srch.hi.assign(raw.hi, raw.hi + S);
+  e->srch.kinds = 0; e->srch.on_check = false;
   for (size_t k = 0; k < S; k++) {
     if (!raw.has[k]) continue;
-    e->srch_kinds |= raw.targets[k];
-    e->srch_chk = e->srch_chk || (long_form && (raw.chk_lo[k] | raw.chk_hi[k]) != 0);
+    e->srch.kinds |= raw.targets[k];
+    e->srch.on_check = e->srch.on_check || (long_form && (raw.chk_lo[k] | raw.chk_hi[k]) != 0);
   }
   if (in_place) return COSIM_OK;
   // every env's record, ring and the remaining word once (the range streams do not order with the null stream: wait here, cold path)
   SrchArgs a = search_args(e);
   a.flag = e->stepped ? SRCH_NO_RESET : 0;
-  for (int env = 0; env < e->n_envs; env++) a.n_armed += raw.has[(e->scn.gid_off + (unsigned)env) % (unsigned)n_scn];
+  for (int env = 0; env < e->n_envs; env++) a.n_armed += raw.has[(e->scn.tab.gid_off + (unsigned)env) % (unsigned)n_scn];
   RC_TRY(launch_small<64, 64>(search_init_kernel, a, e->n_envs, 0));
   HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
@@ -2932,7 +2845,7 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity) {
   rc = join_ranges(e, 0);
   if (rc) return rc;
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(host, e->scnpar.n_items > 0 ? e->d_params_eff : e->d_params, words * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(host, e->par.tab.n_items > 0 ? e->par.eff.get() : e->d_params.get(), words * sizeof(float), hipMemcpyDeviceToHost));
   return e->lay.p_stride;
 }
 
@@ -2944,8 +2857,8 @@ int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_checks_set: null engine");
   HIP_TRY(hipSetDevice(e->device));
   const char* const srch_msg = ": the limit search that is armed fails on a check: clear the search (cosim_set_param \"search\") before the checks are cleared or laid out anew";
-  if (n_scn == 0 && e->srch_chk) return fail(COSIM_EINVAL, std::string("cosim_scenario_checks_set") + srch_msg);
-  if (n_scn == 0) return table_clear(e, 0, checks_free);
+  if (n_scn == 0 && e->srch.on_check) return fail(COSIM_EINVAL, std::string("cosim_scenario_checks_set") + srch_msg);
+  if (n_scn == 0) return table_clear(e, 0, [](cosim_engine* x) { x->chk = {}; });
   RC_TRY(table_rows_match(e, "cosim_scenario_checks_set", "checks", n_scn));
   const ChkRaw raw = {n_scn, adr, t, signal, index, mode, cmp, bound, slots};
   const ChkShape v = validate_checks(table_dims(e), raw);
@@ -2954,38 +2867,37 @@ int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   ChkTable tab = {};
   WordPacker pk;
   pack_checks(pk, tab, raw, v);
-  bool in_place = e->chk.n_scn == n_scn && e->chk.n_items == v.n && e->chk.I == v.I && e->chk_slots == slots;
+  bool in_place = e->chk.tab.n_scn == n_scn && e->chk.tab.n_items == v.n && e->chk.tab.I == v.I && e->chk.slots == slots;
   if (in_place) {
     std::vector<int32_t> old;
-    RC_TRY(table_download(e->d_chk, pk, old));
+    RC_TRY(table_download(e->chk.image.get(), pk, old));
     in_place = checks_same_rows(pk, tab, old.data());
   }
-  if (!in_place && e->srch_chk) return fail(COSIM_EINVAL, std::string("cosim_scenario_checks_set") + srch_msg);
+  if (!in_place && e->srch.on_check) return fail(COSIM_EINVAL, std::string("cosim_scenario_checks_set") + srch_msg);
   const size_t N = (size_t)e->n_envs, I = (size_t)v.I, W = (size_t)checks_words(v.I);
-  auto alloc = [&]() -> hipError_t {   // everything anew: the table, clean accumulators, counters and records at zero
-    checks_free(e);
-    hipError_t r;
-    if ((r = hipMalloc(&e->d_chk, pk.bytes())) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_chk_ext, N * I * sizeof(float))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_chk_aux, N * I * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_chk_n, N * I * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_chk_sum, N * I * sizeof(double))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_chk_cnt, N * CHK_NCNT * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_chk_rec, N * slots * W * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMemset(e->d_chk_cnt, 0, N * CHK_NCNT * sizeof(int))) != hipSuccess) return r;
-    return hipMemset(e->d_chk_rec, 0, N * slots * W * sizeof(int));
-  };
-  hipError_t r = in_place ? hipSuccess : alloc();
-  if (r == hipSuccess) r = hipMemcpy(e->d_chk, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-  if (r != hipSuccess) { checks_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_checks_set: ") + hipGetErrorString(r)); }
-  pk.patch(e->d_chk);
-  e->chk = tab;
-  e->chk_slots = slots;
+  if (!in_place) {   // drop first, then everything anew: the table, clean accumulators, counters and records at zero
+    const char* const fn = "cosim_scenario_checks_set";
+    e->chk = {};
+    Checks fresh;
+    HIP_TRY_CLEAR(fn, fresh.image.alloc(pk.bytes()));
+    HIP_TRY_CLEAR(fn, fresh.ext.alloc(N * I));
+    HIP_TRY_CLEAR(fn, fresh.aux.alloc(N * I));
+    HIP_TRY_CLEAR(fn, fresh.n.alloc(N * I));
+    HIP_TRY_CLEAR(fn, fresh.sum.alloc(N * I));
+    HIP_TRY_CLEAR(fn, fresh.cnt.alloc_zeroed(N * CHK_NCNT));
+    HIP_TRY_CLEAR(fn, fresh.rec.alloc_zeroed(N * slots * W));
+    e->chk = std::move(fresh);
+  }
+  const hipError_t r = hipMemcpy(e->chk.image.get(), pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) { e->chk = {}; (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_checks_set: ") + hipGetErrorString(r)); }
+  pk.patch(e->chk.image.get());
+  e->chk.tab = tab;
+  e->chk.slots = slots;
   // every env starts an open episode with clean accumulators at its current clock -- in place too: no verdict mixes two sets of values
   // (the range streams do not order with the null stream: wait here, cold path)
   RC_TRY(checks_begin(e, nullptr, nullptr, 0, e->stepped ? CHK_NO_RESET : 0, 0));
   // a search that fails on a check judges an episode by its verdict: the episode that lost its samples here is no trial
-  if (e->srch_chk) RC_TRY(search_begin(e, nullptr, nullptr, 0, e->stepped ? SRCH_NO_RESET : 0, 0));
+  if (e->srch.on_check) RC_TRY(search_begin(e, nullptr, nullptr, 0, e->stepped ? SRCH_NO_RESET : 0, 0));
   HIP_TRY(hipDeviceSynchronize());
   return COSIM_OK;
 }
@@ -2994,13 +2906,13 @@ int cosim_scenario_checks_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
 // int32[N][words]; joins the ranges, asynchronous on the caller's stream otherwise.
 int cosim_scenario_checks_get(cosim_engine_t* e, int32_t* records_dev, int32_t* counts_dev, int32_t* open_dev, void* stream) {
   if (!e || !records_dev || !counts_dev) return fail(COSIM_EINVAL, "cosim_scenario_checks_get: null argument");
-  if (e->chk.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_checks_get: no checks are set (cosim_scenario_checks_set)");
+  if (e->chk.tab.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_checks_get: no checks are set (cosim_scenario_checks_set)");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
   RC_TRY(join_ranges(e, cs));
-  const size_t N = (size_t)e->n_envs, W = (size_t)checks_words(e->chk.I);
-  HIP_TRY(hipMemcpyAsync(records_dev, e->d_chk_rec, N * e->chk_slots * W * sizeof(int), hipMemcpyDeviceToDevice, cs));
-  HIP_TRY(hipMemcpy2DAsync(counts_dev, sizeof(int), e->d_chk_cnt, CHK_NCNT * sizeof(int), sizeof(int), N, hipMemcpyDeviceToDevice, cs));
+  const size_t N = (size_t)e->n_envs, W = (size_t)checks_words(e->chk.tab.I);
+  HIP_TRY(hipMemcpyAsync(records_dev, e->chk.rec.get(), N * e->chk.slots * W * sizeof(int), hipMemcpyDeviceToDevice, cs));
+  HIP_TRY(hipMemcpy2DAsync(counts_dev, sizeof(int), e->chk.cnt.get(), CHK_NCNT * sizeof(int), sizeof(int), N, hipMemcpyDeviceToDevice, cs));
   if (open_dev) {
     ChkArgs a = checks_args(e);
     a.rec = open_dev;
@@ -3016,7 +2928,7 @@ int cosim_scenario_curves_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
                               const float* lo, const float* hi, const int32_t* bins) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_curves_set: null engine");
   HIP_TRY(hipSetDevice(e->device));
-  if (n_scn == 0) return table_clear(e, 0, curves_free);
+  if (n_scn == 0) return table_clear(e, 0, [](cosim_engine* x) { x->cur = {}; });
   RC_TRY(table_rows_match(e, "cosim_scenario_curves_set", "curves", n_scn));
   const CurRaw raw = {n_scn, adr, t, signal, index, lo, hi, bins};
   const CurShape v = validate_curves(table_dims(e), e->n_envs, raw);
@@ -3025,27 +2937,28 @@ int cosim_scenario_curves_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
   CurTable tab = {};
   WordPacker pk;
   pack_curves(pk, tab, raw, v);
-  bool in_place = e->cur.n_scn == n_scn && e->cur.n_items == v.n && e->cur.SW == (int)v.SW && e->cur_words == v.cells;
+  bool in_place = e->cur.tab.n_scn == n_scn && e->cur.tab.n_items == v.n && e->cur.tab.SW == (int)v.SW && e->cur.words == v.cells;
   if (in_place) {
     std::vector<int32_t> old;
-    RC_TRY(table_download(e->d_cur, pk, old));
+    RC_TRY(table_download(e->cur.image.get(), pk, old));
     in_place = curves_same_sizes(pk, tab, old.data());
   }
   const size_t N = (size_t)e->n_envs;
-  auto alloc = [&]() -> hipError_t {   // everything anew: the table, the stage, the clocks and the cells
-    curves_free(e);
-    hipError_t r;
-    if ((r = hipMalloc(&e->d_cur, pk.bytes())) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_cur_stage, (N * v.SW > 0 ? N * v.SW : 1) * sizeof(int))) != hipSuccess) return r;
-    if ((r = hipMalloc(&e->d_cur_clk, N * sizeof(int))) != hipSuccess) return r;
-    return hipMalloc(&e->d_cur_cells, v.cells * sizeof(unsigned));
-  };
-  hipError_t r = in_place ? hipSuccess : alloc();
-  if (r == hipSuccess) r = hipMemcpy(e->d_cur, pk.data(), pk.bytes(), hipMemcpyHostToDevice);
-  if (r != hipSuccess) { curves_free(e); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_set: ") + hipGetErrorString(r)); }
-  pk.patch(e->d_cur);
-  e->cur = tab;
-  e->cur_words = v.cells;
+  if (!in_place) {   // drop first (the groups too), then everything anew: the table, the stage, the clocks and the cells
+    const char* const fn = "cosim_scenario_curves_set";
+    e->cur = {};
+    Curves fresh;
+    HIP_TRY_CLEAR(fn, fresh.image.alloc(pk.bytes()));
+    HIP_TRY_CLEAR(fn, fresh.stage.alloc(N * v.SW > 0 ? N * v.SW : 1));
+    HIP_TRY_CLEAR(fn, fresh.clk.alloc(N));
+    HIP_TRY_CLEAR(fn, fresh.cells.alloc(v.cells));
+    e->cur = std::move(fresh);
+  }
+  const hipError_t r = hipMemcpy(e->cur.image.get(), pk.data(), pk.bytes(), hipMemcpyHostToDevice);
+  if (r != hipSuccess) { e->cur = {}; (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_set: ") + hipGetErrorString(r)); }
+  pk.patch(e->cur.image.get());
+  e->cur.tab = tab;
+  e->cur.words = v.cells;
   return cosim_scenario_curves_clear(e);
 }
 
@@ -3053,7 +2966,7 @@ int cosim_scenario_curves_set(cosim_engine_t* e, int n_scn, const int32_t* adr, 
 // order with the null stream: join and wait, cold path).
 int cosim_scenario_curves_clear(cosim_engine_t* e) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_curves_clear: null engine");
-  if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_clear: no curves are set (cosim_scenario_curves_set)");
+  if (e->cur.tab.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_clear: no curves are set (cosim_scenario_curves_set)");
   HIP_TRY(hipSetDevice(e->device));
   RC_TRY(join_ranges(e, 0));
   HIP_TRY(hipDeviceSynchronize());
@@ -3068,24 +2981,22 @@ int cosim_scenario_curves_clear(cosim_engine_t* e) {
 // Every call empties the cells.  Refusals first, then join and wait, allocate, clear, begin.
 int cosim_scenario_curves_groups(cosim_engine_t* e, int n_groups, const int32_t* group_dev) {
   if (!e) return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: null engine");
-  if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: no curves are set (cosim_scenario_curves_set): groups split the cells of curves");
+  if (e->cur.tab.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: no curves are set (cosim_scenario_curves_set): groups split the cells of curves");
   if (n_groups < 0 || n_groups > CUR_MAX_GROUPS)
     return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: n_groups " + std::to_string(n_groups) + " outside 0..64 (0: no groups)");
   if (n_groups > 0 && !group_dev) return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: n_groups " + std::to_string(n_groups) + " with a null group_dev");
-  if ((size_t)n_groups * e->cur_words * sizeof(unsigned) > CUR_MAX_BYTES)
-    return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: " + std::to_string(n_groups) + " planes of " + std::to_string(e->cur_words) +
+  if ((size_t)n_groups * e->cur.words * sizeof(unsigned) > CUR_MAX_BYTES)
+    return fail(COSIM_EINVAL, "cosim_scenario_curves_groups: " + std::to_string(n_groups) + " planes of " + std::to_string(e->cur.words) +
                                   " words: the cells would exceed 256 MiB (a design limit)");
   HIP_TRY(hipSetDevice(e->device));
   RC_TRY(table_quiesce(e, 0));
   // the new planes replace the old ones only once both allocations stand (a failure leaves the cells and the groups that were set)
-  unsigned* cells = nullptr;
-  unsigned* lost = e->d_cur_ungrouped;
-  hipError_t r = hipMalloc(&cells, (size_t)(n_groups > 0 ? n_groups : 1) * e->cur_words * sizeof(unsigned));
-  if (r == hipSuccess && n_groups > 0 && !lost) r = hipMalloc(&lost, sizeof(unsigned));
-  if (r != hipSuccess) { (void)hipFree(cells); (void)hipGetLastError(); return fail(COSIM_EHIP, std::string("cosim_scenario_curves_groups: ") + hipGetErrorString(r)); }
-  (void)hipFree(e->d_cur_cells);
-  e->d_cur_cells = cells; e->d_cur_ungrouped = lost;
-  e->cur_groups = n_groups; e->cur_group = n_groups > 0 ? group_dev : nullptr;
+  Dev<unsigned> cells, lost;
+  HIP_TRY_CLEAR("cosim_scenario_curves_groups", cells.alloc((size_t)(n_groups > 0 ? n_groups : 1) * e->cur.words));
+  if (n_groups > 0 && !e->cur.ungrouped) HIP_TRY_CLEAR("cosim_scenario_curves_groups", lost.alloc(1));
+  e->cur.cells = std::move(cells);
+  if (lost) e->cur.ungrouped = std::move(lost);
+  e->cur.groups = n_groups; e->cur.group = n_groups > 0 ? group_dev : nullptr;
   return cosim_scenario_curves_clear(e);
 }
 
@@ -3093,11 +3004,11 @@ int cosim_scenario_curves_groups(cosim_engine_t* e, int n_groups, const int32_t*
 // asynchronous on the caller's stream otherwise.
 int cosim_scenario_curves_get(cosim_engine_t* e, uint32_t* cells_dev, void* stream) {
   if (!e || !cells_dev) return fail(COSIM_EINVAL, "cosim_scenario_curves_get: null argument");
-  if (e->cur.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_get: no curves are set (cosim_scenario_curves_set)");
+  if (e->cur.tab.n_scn <= 0) return fail(COSIM_EINVAL, "cosim_scenario_curves_get: no curves are set (cosim_scenario_curves_set)");
   HIP_TRY(hipSetDevice(e->device));
   hipStream_t cs = (hipStream_t)stream;
   RC_TRY(join_ranges(e, cs));
-  HIP_TRY(hipMemcpyAsync(cells_dev, e->d_cur_cells, (size_t)(e->cur_groups > 0 ? e->cur_groups : 1) * e->cur_words * sizeof(unsigned), hipMemcpyDeviceToDevice, cs));
+  HIP_TRY(hipMemcpyAsync(cells_dev, e->cur.cells.get(), (size_t)(e->cur.groups > 0 ? e->cur.groups : 1) * e->cur.words * sizeof(unsigned), hipMemcpyDeviceToDevice, cs));
   return COSIM_OK;
 }
 
@@ -3119,7 +3030,7 @@ int cosim_event_push(cosim_engine_t* e, const float* v_dev, const uint8_t* mask_
   if (!e || !v_dev) return fail(COSIM_EINVAL, "cosim_event_push: null argument");
   HIP_TRY(hipSetDevice(e->device));
   { int rc = join_ranges(e, (hipStream_t)stream); if (rc) return rc; }
-  hipLaunchKernelGGL(push_kernel, dim3((e->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->d_state, e->lay, v_dev, mask_dev, e->n_envs);
+  hipLaunchKernelGGL(push_kernel, dim3((e->n_envs + 255) / 256), dim3(256), 0, (hipStream_t)stream, e->d_state.get(), e->lay, v_dev, mask_dev, e->n_envs);
   HIP_TRY(hipGetLastError());
   return COSIM_OK;
 }
@@ -3135,9 +3046,9 @@ int cosim_debug_forward(cosim_engine_t* e, int env, const char* name, float* hos
   if (rc) return rc;
   rc = join_ranges(e, 0);
   if (rc) return rc;
-  HIP_TRY(hipMemset(e->d_dbg, 0, 8192 * sizeof(float)));
+  HIP_TRY(hipMemset(e->d_dbg.get(), 0, 8192 * sizeof(float)));
   KArgs a = base_args(e);
-  a.mode = MODE_DEBUG; a.dbg = e->d_dbg; a.dbg_env = env;
+  a.mode = MODE_DEBUG; a.dbg = e->d_dbg.get(); a.dbg_env = env;
   // split: the product's own pair of kernels; with the heightfield fix-up on, every contact the fix-up kernel would keep (where the
   // fleet kernel exists at that capacity); else the kernel that resets (two-per-wave: both groups replay env `env`, same dump twice)
   if (e->plan.split) e->plan.narrow.launch(e, a, e->narrow_waves, 0);
@@ -3145,7 +3056,7 @@ int cosim_debug_forward(cosim_engine_t* e, int env, const char* name, float* hos
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   int n = capacity < 8192 ? capacity : 8192;
-  HIP_TRY(hipMemcpy(host_out, e->d_dbg, (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(host_out, e->d_dbg.get(), (size_t)n * sizeof(float), hipMemcpyDeviceToHost));
   return COSIM_OK;
 }
 
@@ -3153,23 +3064,23 @@ int cosim_profile_step(cosim_engine_t* e, const float* actions_dev, const float*
                        uint8_t* truncated_dev, double* cycles_out16) {
   if (!e || !actions_dev || !state_out_dev || !terminated_dev || !truncated_dev || !cycles_out16) return fail(COSIM_EINVAL, "cosim_profile_step: null argument");
   if (!has(e->plan.prof)) return fail(COSIM_EINVAL, "cosim_profile_step: no diagnostic kernel for this model");
-  if (e->lat.n_act + e->lat.n_obs > 0)
+  if (e->lat.tab.n_act + e->lat.tab.n_obs > 0)
     return fail(COSIM_EINVAL, "cosim_profile_step: latency is set (cosim_set_param \"latency\"): the diagnostic step advances the clocks without writing the delay lines, so a later step would deliver a stale slot; clear the latency first");
   HIP_TRY(hipSetDevice(e->device));
   int rc = upload_params(e);
   if (rc) return rc;
   rc = join_ranges(e, 0);
   if (rc) return rc;
-  HIP_TRY(hipMemset(e->d_dbg, 0, 8192 * sizeof(float)));
+  HIP_TRY(hipMemset(e->d_dbg.get(), 0, 8192 * sizeof(float)));
   KArgs a = base_args(e);
   a.mode = MODE_STEP; a.actions = actions_dev; a.commands = commands_dev; a.state_out = state_out_dev;
-  a.terminated = terminated_dev; a.truncated = truncated_dev; a.dbg = e->d_dbg;
+  a.terminated = terminated_dev; a.truncated = truncated_dev; a.dbg = e->d_dbg.get();
   e->stepped = true;
   e->plan.prof.launch(e, a, e->n_envs, 0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipDeviceSynchronize());
   unsigned long long raw[32];
-  HIP_TRY(hipMemcpy(raw, e->d_dbg, sizeof raw, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(raw, e->d_dbg.get(), sizeof raw, hipMemcpyDeviceToHost));
   for (int i = 0; i < 32; i++) cycles_out16[i] = (double)raw[i] / (double)(e->n_envs / e->sw.epw);   // per wave
   return COSIM_OK;
 }
@@ -3180,37 +3091,21 @@ int cosim_debug_support(cosim_engine_t* e, int geom, const float* dirs_host, int
   if (!e || !dirs_host || !out_host || n_dirs < 1 || geom < 0 || geom >= e->hm.ngeom) return fail(COSIM_EINVAL, "cosim_debug_support: bad argument");
   if (e->hm.rec[geom].g_type != CS_GEOM_MESH) return fail(COSIM_EINVAL, "cosim_debug_support: not a mesh geom");
   HIP_TRY(hipSetDevice(e->device));
-  float *d_dirs = nullptr, *d_out = nullptr;
-  auto run = [&]() -> hipError_t {   // (one exit, so that the two scratch buffers are released on every path)
-    hipError_t r;
-    if ((r = hipMalloc(&d_dirs, (size_t)n_dirs * 3 * sizeof(float))) != hipSuccess) return r;
-    if ((r = hipMalloc(&d_out, (size_t)n_dirs * 6 * sizeof(float))) != hipSuccess) return r;
-    if ((r = hipMemcpy(d_dirs, dirs_host, (size_t)n_dirs * 3 * sizeof(float), hipMemcpyHostToDevice)) != hipSuccess) return r;
-    const HullGraph H{e->d_hull_vert, e->d_hull_adr, e->d_hull_nbr, e->d_hull_cell, e->d_hull_cand};
-    hipLaunchKernelGGL(support_probe_kernel, dim3((n_dirs + 63) / 64), dim3(64), 0, 0, e->d_model, H, geom, d_dirs, n_dirs, d_out, use_map);
-    if ((r = hipGetLastError()) != hipSuccess) return r;
-    if ((r = hipDeviceSynchronize()) != hipSuccess) return r;
-    return hipMemcpy(out_host, d_out, (size_t)n_dirs * 6 * sizeof(float), hipMemcpyDeviceToHost);
-  };
-  const hipError_t r = run();
-  (void)hipFree(d_dirs); (void)hipFree(d_out);
-  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_support: ") + hipGetErrorString(r));
+  const char* const fn = "cosim_debug_support";
+  Dev<float> d_dirs, d_out;   // scratch of this call
+  HIP_TRY_AS(fn, d_dirs.upload(dirs_host, (size_t)n_dirs * 3));
+  HIP_TRY_AS(fn, d_out.alloc((size_t)n_dirs * 6));
+  const HullGraph H{e->d_hull_vert.get(), e->d_hull_adr.get(), e->d_hull_nbr.get(), e->d_hull_cell.get(), e->d_hull_cand.get()};
+  hipLaunchKernelGGL(support_probe_kernel, dim3((n_dirs + 63) / 64), dim3(64), 0, 0, e->d_model.get(), H, geom, d_dirs.get(), n_dirs, d_out.get(), use_map);
+  HIP_TRY_AS(fn, hipGetLastError());
+  HIP_TRY_AS(fn, hipDeviceSynchronize());
+  HIP_TRY_AS(fn, d_out.download(out_host, (size_t)n_dirs * 6));
   return COSIM_OK;
 }
 
 // Test hooks: the device's pair routines (MPR on primitives, MPR prism - primitive, box-box) on pairs given in host arrays; the engine
 // handle names the device only.  Kinds without an O(1) support in these kernels are rejected (no silent zero-size geom).
 namespace {
-struct DbgBuf {   // a device buffer that lives for one call
-  void* p = nullptr;
-  ~DbgBuf() { if (p) (void)hipFree(p); }
-  hipError_t alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 1); }
-  hipError_t upload(const void* host, size_t bytes) {
-    const hipError_t r = alloc(bytes);
-    return r != hipSuccess ? r : hipMemcpy(p, host, bytes, hipMemcpyHostToDevice);
-  }
-  hipError_t download(void* host, size_t bytes) const { return hipMemcpy(host, p, bytes, hipMemcpyDeviceToHost); }
-};
 bool prim_kind(int k) { return k == CS_GEOM_SPHERE || k == CS_GEOM_CYLINDER || k == CS_GEOM_BOX; }
 hipError_t dbg_finish() {
   const hipError_t r = hipGetLastError();
@@ -3223,16 +3118,18 @@ int cosim_debug_mpr_prims(cosim_engine_t* e, const int* kinds_host, const float*
   for (int i = 0; i < 2 * n; i++)
     if (!prim_kind(kinds_host[i])) return fail(COSIM_EINVAL, "cosim_debug_mpr_prims: geom kind is not sphere / cylinder / box");
   HIP_TRY(hipSetDevice(e->device));
-  DbgBuf kinds, geo, irec, frec;
-  hipError_t r;
-  if ((r = kinds.upload(kinds_host, (size_t)n * 2 * sizeof(int))) == hipSuccess && (r = geo.upload(geo_host, (size_t)n * 20 * sizeof(float))) == hipSuccess &&
-      (r = irec.alloc((size_t)n * 3 * sizeof(int))) == hipSuccess && (r = frec.alloc((size_t)n * 7 * sizeof(float))) == hipSuccess) {
-    if (coop) hipLaunchKernelGGL(mpr_prims_probe_kernel<true>, dim3(n), dim3(64), 0, 0, (const int*)kinds.p, (const float*)geo.p, n, (int*)irec.p, (float*)frec.p);
-    else hipLaunchKernelGGL(mpr_prims_probe_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, 0, (const int*)kinds.p, (const float*)geo.p, n, (int*)irec.p, (float*)frec.p);
-    if ((r = dbg_finish()) == hipSuccess && (r = irec.download(irec_host, (size_t)n * 3 * sizeof(int))) == hipSuccess)
-      r = frec.download(frec_host, (size_t)n * 7 * sizeof(float));
-  }
-  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_mpr_prims: ") + hipGetErrorString(r));
+  const char* const fn = "cosim_debug_mpr_prims";
+  Dev<int> kinds, irec;   // device buffers that live for this call
+  Dev<float> geo, frec;
+  HIP_TRY_AS(fn, kinds.upload(kinds_host, (size_t)n * 2));
+  HIP_TRY_AS(fn, geo.upload(geo_host, (size_t)n * 20));
+  HIP_TRY_AS(fn, irec.alloc((size_t)n * 3));
+  HIP_TRY_AS(fn, frec.alloc((size_t)n * 7));
+  if (coop) hipLaunchKernelGGL(mpr_prims_probe_kernel<true>, dim3(n), dim3(64), 0, 0, (const int*)kinds.get(), (const float*)geo.get(), n, irec.get(), frec.get());
+  else hipLaunchKernelGGL(mpr_prims_probe_kernel<false>, dim3((n + 63) / 64), dim3(64), 0, 0, (const int*)kinds.get(), (const float*)geo.get(), n, irec.get(), frec.get());
+  HIP_TRY_AS(fn, dbg_finish());
+  HIP_TRY_AS(fn, irec.download(irec_host, (size_t)n * 3));
+  HIP_TRY_AS(fn, frec.download(frec_host, (size_t)n * 7));
   return COSIM_OK;
 }
 
@@ -3241,33 +3138,36 @@ int cosim_debug_mpr_prism(cosim_engine_t* e, const float* prism_host, const int*
   for (int i = 0; i < n; i++)
     if (!prim_kind(kinds_host[i])) return fail(COSIM_EINVAL, "cosim_debug_mpr_prism: geom kind is not sphere / cylinder / box");
   HIP_TRY(hipSetDevice(e->device));
-  DbgBuf prism, kinds, geo, irec, frec;
-  hipError_t r;
-  if ((r = prism.upload(prism_host, (size_t)n * 10 * sizeof(float))) == hipSuccess && (r = kinds.upload(kinds_host, (size_t)n * sizeof(int))) == hipSuccess &&
-      (r = geo.upload(geo_host, (size_t)n * 10 * sizeof(float))) == hipSuccess && (r = irec.alloc((size_t)n * 3 * sizeof(int))) == hipSuccess &&
-      (r = frec.alloc((size_t)n * 7 * sizeof(float))) == hipSuccess) {
-    hipLaunchKernelGGL(mpr_prism_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, (const float*)prism.p, (const int*)kinds.p, (const float*)geo.p, n, (int*)irec.p,
-                       (float*)frec.p);
-    if ((r = dbg_finish()) == hipSuccess && (r = irec.download(irec_host, (size_t)n * 3 * sizeof(int))) == hipSuccess)
-      r = frec.download(frec_host, (size_t)n * 7 * sizeof(float));
-  }
-  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_mpr_prism: ") + hipGetErrorString(r));
+  const char* const fn = "cosim_debug_mpr_prism";
+  Dev<int> kinds, irec;
+  Dev<float> prism, geo, frec;
+  HIP_TRY_AS(fn, prism.upload(prism_host, (size_t)n * 10));
+  HIP_TRY_AS(fn, kinds.upload(kinds_host, (size_t)n));
+  HIP_TRY_AS(fn, geo.upload(geo_host, (size_t)n * 10));
+  HIP_TRY_AS(fn, irec.alloc((size_t)n * 3));
+  HIP_TRY_AS(fn, frec.alloc((size_t)n * 7));
+  hipLaunchKernelGGL(mpr_prism_probe_kernel, dim3((n + 63) / 64), dim3(64), 0, 0, (const float*)prism.get(), (const int*)kinds.get(), (const float*)geo.get(), n, irec.get(),
+                     frec.get());
+  HIP_TRY_AS(fn, dbg_finish());
+  HIP_TRY_AS(fn, irec.download(irec_host, (size_t)n * 3));
+  HIP_TRY_AS(fn, frec.download(frec_host, (size_t)n * 7));
   return COSIM_OK;
 }
 
 int cosim_debug_box_box(cosim_engine_t* e, const float* geo_host, const float* margin_host, int n, int* count_host, float* out_host) {
   if (!e || !geo_host || !margin_host || !count_host || !out_host || n < 1) return fail(COSIM_EINVAL, "cosim_debug_box_box: bad argument");
   HIP_TRY(hipSetDevice(e->device));
-  DbgBuf geo, margin, cnt, out;
-  hipError_t r;
-  if ((r = geo.upload(geo_host, (size_t)n * 20 * sizeof(float))) == hipSuccess && (r = margin.upload(margin_host, (size_t)n * sizeof(float))) == hipSuccess &&
-      (r = cnt.alloc((size_t)n * sizeof(int))) == hipSuccess && (r = out.alloc((size_t)n * 35 * sizeof(float))) == hipSuccess &&
-      (r = hipMemset(out.p, 0, (size_t)n * 35 * sizeof(float))) == hipSuccess) {
-    hipLaunchKernelGGL(box_box_probe_kernel, dim3(n), dim3(64), 0, 0, (const float*)geo.p, (const float*)margin.p, n, (int*)cnt.p, (float*)out.p);
-    if ((r = dbg_finish()) == hipSuccess && (r = cnt.download(count_host, (size_t)n * sizeof(int))) == hipSuccess)
-      r = out.download(out_host, (size_t)n * 35 * sizeof(float));
-  }
-  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_box_box: ") + hipGetErrorString(r));
+  const char* const fn = "cosim_debug_box_box";
+  Dev<float> geo, margin, out;
+  Dev<int> cnt;
+  HIP_TRY_AS(fn, geo.upload(geo_host, (size_t)n * 20));
+  HIP_TRY_AS(fn, margin.upload(margin_host, (size_t)n));
+  HIP_TRY_AS(fn, cnt.alloc((size_t)n));
+  HIP_TRY_AS(fn, out.alloc_zeroed((size_t)n * 35));
+  hipLaunchKernelGGL(box_box_probe_kernel, dim3(n), dim3(64), 0, 0, (const float*)geo.get(), (const float*)margin.get(), n, cnt.get(), out.get());
+  HIP_TRY_AS(fn, dbg_finish());
+  HIP_TRY_AS(fn, cnt.download(count_host, (size_t)n));
+  HIP_TRY_AS(fn, out.download(out_host, (size_t)n * 35));
   return COSIM_OK;
 }
 
@@ -3278,18 +3178,17 @@ static int debug_cholesky(cosim_engine_t* e, int nv, float* io, int capacity) {
   const int per = 64 * (nv + 1), n = capacity / per;
   if (capacity < per || capacity % per) return fail(COSIM_EINVAL, "cosim_debug_forward cholesky: capacity is not n * 64 * (order + 1)");
   HIP_TRY(hipSetDevice(e->device));
-  DbgBuf in, out;
+  const char* const fn = "cosim_debug_forward cholesky";
+  Dev<float> in, out;
   const size_t nfac = (size_t)n * 2 * nv * nv, nvec = (size_t)n * 2 * nv;   // nfac + 2 nvec < capacity: the answer fits the caller's block
-  hipError_t r;
-  if ((r = in.upload(io, (size_t)capacity * sizeof(float))) == hipSuccess && (r = out.alloc((nfac + 2 * nvec) * sizeof(float))) == hipSuccess &&
-      (r = hipMemset(out.p, 0, (nfac + 2 * nvec) * sizeof(float))) == hipSuccess) {
-    const float *rows = (const float*)in.p, *rhs = rows + (size_t)n * 64 * nv;
-    float *fac = (float*)out.p, *dinv = fac + nfac, *sol = dinv + nvec;
-    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, 0, rows, rhs, n, fac, dinv, sol); };
-    if (nv == 18) launch(chol_probe_kernel<18>); else if (nv == 10) launch(chol_probe_kernel<10>); else launch(chol_probe_kernel<7>);
-    if ((r = dbg_finish()) == hipSuccess) r = out.download(io, (nfac + 2 * nvec) * sizeof(float));
-  }
-  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_forward cholesky: ") + hipGetErrorString(r));
+  HIP_TRY_AS(fn, in.upload(io, (size_t)capacity));
+  HIP_TRY_AS(fn, out.alloc_zeroed(nfac + 2 * nvec));
+  const float *rows = in.get(), *rhs = rows + (size_t)n * 64 * nv;
+  float *fac = out.get(), *dinv = fac + nfac, *sol = dinv + nvec;
+  auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, 0, rows, rhs, n, fac, dinv, sol); };
+  if (nv == 18) launch(chol_probe_kernel<18>); else if (nv == 10) launch(chol_probe_kernel<10>); else launch(chol_probe_kernel<7>);
+  HIP_TRY_AS(fn, dbg_finish());
+  HIP_TRY_AS(fn, out.download(io, nfac + 2 * nvec));
   return COSIM_OK;
 }
 
@@ -3301,16 +3200,15 @@ static int debug_ldsbatch(cosim_engine_t* e, int nv, float* io, int capacity) {
   const int per = 64 * nv + nv * nv + 3 * nv, n = capacity / per;
   if (capacity < per || capacity % per) return fail(COSIM_EINVAL, "cosim_debug_forward ldsbatch: capacity is not n * (64 nv + nv nv + 3 nv)");
   HIP_TRY(hipSetDevice(e->device));
-  DbgBuf in, out;
+  const char* const fn = "cosim_debug_forward ldsbatch";
+  Dev<float> in, out;
   const size_t nout = (size_t)n * 2 * (64 + 2 * nv);   // < capacity: the answer fits the caller's block
-  hipError_t r;
-  if ((r = in.upload(io, (size_t)capacity * sizeof(float))) == hipSuccess && (r = out.alloc(nout * sizeof(float))) == hipSuccess &&
-      (r = hipMemset(out.p, 0, nout * sizeof(float))) == hipSuccess) {
-    auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, 0, (const float*)in.p, n, (float*)out.p); };
-    if (nv == 18) launch(ldsbatch_probe_kernel<18>); else if (nv == 10) launch(ldsbatch_probe_kernel<10>); else launch(ldsbatch_probe_kernel<7>);
-    if ((r = dbg_finish()) == hipSuccess) r = out.download(io, nout * sizeof(float));
-  }
-  if (r != hipSuccess) return fail(COSIM_EHIP, std::string("cosim_debug_forward ldsbatch: ") + hipGetErrorString(r));
+  HIP_TRY_AS(fn, in.upload(io, (size_t)capacity));
+  HIP_TRY_AS(fn, out.alloc_zeroed(nout));
+  auto launch = [&](auto kern) { hipLaunchKernelGGL(kern, dim3(n), dim3(64), 0, 0, (const float*)in.get(), n, out.get()); };
+  if (nv == 18) launch(ldsbatch_probe_kernel<18>); else if (nv == 10) launch(ldsbatch_probe_kernel<10>); else launch(ldsbatch_probe_kernel<7>);
+  HIP_TRY_AS(fn, dbg_finish());
+  HIP_TRY_AS(fn, out.download(io, nout));
   return COSIM_OK;
 }
 
@@ -3318,8 +3216,8 @@ int cosim_debug_counters(cosim_engine_t* e, unsigned long long* out32, int clear
   if (!e || !out32) return fail(COSIM_EINVAL, "cosim_debug_counters: null argument");
   HIP_TRY(hipSetDevice(e->device));
   HIP_TRY(hipDeviceSynchronize());
-  HIP_TRY(hipMemcpy(out32, e->d_dbg, 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-  if (clear) HIP_TRY(hipMemset(e->d_dbg, 0, 8192 * sizeof(float)));
+  HIP_TRY(hipMemcpy(out32, e->d_dbg.get(), 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+  if (clear) HIP_TRY(hipMemset(e->d_dbg.get(), 0, 8192 * sizeof(float)));
   return COSIM_OK;
 }
 

@@ -499,6 +499,12 @@ int cosim_scenario_params_get(cosim_engine_t* e, float* host, int capacity);
  * items of both kinds (0: none: not a launch or a pointer differs), "latency_action_items" / "latency_obs_items" those of a kind,
  * "latency_depth" D; cosim_get "action_effective" / "action_raw" work with action items alone. */
 
+/* cosim_query "device_buffers" answers the device allocations of this library that are live in the process: the buffers of every
+ * engine and of every policy / recurrent table together, each counted from its allocation to its release (page-locked host memory is
+ * not counted).  Like "launches" it is one process-wide number whichever engine is asked.  The same number before a feature is set
+ * and after it is cleared, or before a handle is created and after it is destroyed, means that nothing was left behind; a test can
+ * hold that exactly, where the free memory of a shared device says nothing. */
+
 /* Limit search of the scenario table that is set: a per-env staircase on the scale of a scenario's pushes and commands, moved on the
  * device by the outcome of the env's own episodes (cosim_amd/csrc/cosim_search.h has the rule).  Like the faults it has no entry point
  * of its own: the table travels through cosim_set_param(e, "search", words, count), `words` pointing at `count` 32-BIT WORDS:

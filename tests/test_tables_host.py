@@ -387,7 +387,36 @@ def test_device_code_is_what_it_was():
     assert re.search(r"^ksize_tables\s+identical$", text, flags=re.M) and re.search(r"^kres_tables\s+identical$", text, flags=re.M)
 
 
+def test_device_code_is_what_it_was_before_the_owning_buffers():
+    """profiles/devbuf_codeobj.txt: the same comparison across the change that gave every device allocation an owner."""
+    text = open(os.path.join(ROOT, "profiles", "devbuf_codeobj.txt")).read()
+    h = dict(re.findall(r"^text_sha256_(parent|this)\s+([0-9a-f]{64})$", text, flags=re.M))
+    assert set(h) == {"parent", "this"} and h["parent"] == h["this"]
+    assert re.search(r"^text_section\s+byte-identical$", text, flags=re.M)
+    assert re.search(r"^ksize_tables\s+identical$", text, flags=re.M) and re.search(r"^kres_tables\s+identical$", text, flags=re.M)
+
+
 def test_each_rule_is_written_once():
     csrc = os.path.join(ROOT, "cosim_amd", "csrc")
     src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)))
     assert src.count("times outside [0, 2^30)") == 1 and src.count("unknown signal ") == 1 and src.count("row addresses must not decrease") == 1
+
+
+def test_the_engine_allocates_in_one_place():
+    """csrc/cosim_devbuf.h owns every allocation: the four calls occur once each, in the allocator policies, and the
+    hand-written cleanup helpers are gone from csrc/."""
+    csrc = os.path.join(ROOT, "cosim_amd", "csrc")
+    engine = open(os.path.join(csrc, "cosim_engine.hip")).read()
+    for call in ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree("):
+        assert engine.count(call) == 1, call
+    policies = engine[engine.index("struct HipDevice"):engine.index("template <class T> using Dev")]
+    assert all(call in policies for call in ("hipMalloc(", "hipFree(", "hipHostMalloc(", "hipHostFree("))
+    src = "".join(open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)))
+    for name in ("scnparams_free", "obsfault_free", "actfault_free", "latency_drop", "latency_free", "checks_free", "curves_free", "search_free",
+                 "ledger_free", "ftrace_free", "rotate_free", "table_free", "DbgBuf"):
+        assert not re.search(r"\b%s\b" % name, src), name
+    # the four that must name no buffer: they assign groups and delete, nothing else
+    for fn in ("int cosim_destroy", "int cosim_policy_table_destroy", "int cosim_recurrent_table_destroy", "static void scenario_free"):
+        body = engine[engine.index("%s(" % fn):]
+        body = body[:body.index("\n}\n")]
+        assert ".get()" not in body and ".reset()" not in body and "d_" not in body, fn
